@@ -6,6 +6,7 @@ one shared-tile all-reduce and the row gather.
 
     python bench.py --gpus 1 --steps 5 --warmup 2
     python bench.py --gpus 8                      # starts its own 8 ranks (torch.distributed.run children)
+    python bench.py --dump-outputs out/           # also writes the last timed report as out/<column>.npy (dump_outputs)
 
 A "step" is one full generateCytosineReport(bam) on the resident batch: thresholding,
 the tile index, the LDS-histogram tile kernel with the majority rule, and the ordered
@@ -96,7 +97,12 @@ def _parse():
     ap.add_argument("--no-extras", action="store_true", help="only the contract fields (no streamed / d2h / cfg2u / strong_cfg3)")
     ap.add_argument("--strong-steps", type=int, default=3)
     ap.add_argument("--host-threads", type=int, default=0, help="file workload: BGZF inflate / packing / report writer threads (0 = min(cores, 16))")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the report of the last timed step to DIR/<column>.npy (float64; see dump_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def _free_port():
@@ -282,6 +288,38 @@ def timed_run(cx, wl, rows, L, steps, warmup, gather=False, keep=False, n_chr=No
         del rep, step, eng
         bam.close()
     return out
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, rep):
+    """--dump-outputs: the report table of the last timed step, as its caller receives it, one float64 file per column
+    (DIR/<column>.npy; every column fits float64 exactly).  A table larger than 64 MB in that form is written as a fixed
+    sample: row_index.npy holds the row numbers (numpy default_rng(0), sorted) and every column file those rows.  Always
+    written: nrow.npy (the table's row count) and column_sums.npy, the sum of every column over ALL rows in sorted
+    column-name order (integer columns summed exactly in int64, float columns NaN-skipping in float64).  The inputs
+    are seeded, so two builds run with the same arguments can be compared file by file."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    names = sorted(rep)
+    cols = {k: rep[k] if isinstance(rep[k], torch.Tensor) else torch.from_numpy(np.ascontiguousarray(rep[k])) for k in names}
+    nrow = rep.nrow
+    keep = max(1, (DUMP_BYTES - 4096) // (8 * (len(names) + 1)))   # + row_index.npy
+    idx = None
+    if nrow > keep:
+        idx = np.sort(np.random.default_rng(0).choice(nrow, keep, replace=False))
+        np.save(os.path.join(out_dir, "row_index.npy"), idx.astype(np.float64))
+    sums = []
+    for k in names:
+        c = cols[k]
+        sums.append(float(c.double().nansum()) if c.is_floating_point() else float(c.long().sum()))
+        if idx is not None:
+            c = c[torch.from_numpy(idx).to(c.device)]
+        np.save(os.path.join(out_dir, k + ".npy"), c.cpu().numpy().astype(np.float64))
+    np.save(os.path.join(out_dir, "nrow.npy"), np.array([nrow], dtype=np.float64))
+    np.save(os.path.join(out_dir, "column_sums.npy"), np.array(sums, dtype=np.float64))
 
 
 def selfcheck(cx, n_total):
@@ -555,6 +593,7 @@ def file_workload(cx, args):
     path, nrec = cx.synth.write_bam_paired(os.path.join(tmp, "in.bam"), pairs, threads=nth)
     out_path = os.path.join(tmp, "report.tsv")
     parts = []
+    last = [None]
 
     def step():
         t0 = time.perf_counter()
@@ -570,6 +609,8 @@ def file_workload(cx, args):
         parts.append((t1 - t0, t2 - t1, t3 - t2, t4 - t3))
         n, nrow = bam.n, rep.nrow
         bam.close()
+        if args.dump_outputs:
+            last[0] = rep
         return n, nrow
 
     for _ in range(max(1, args.warmup)):
@@ -581,6 +622,8 @@ def file_workload(cx, args):
         n_templ, nrow = step()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last[0])
     avg = [sum(p[i] for p in parts) / len(parts) * 1e3 for i in range(4)]
     out = {
         "metric": "Mreads/s BAM file -> CX report file (generateCytosineReport; read = BAM record)",
@@ -635,6 +678,8 @@ def main():
     res = timed_run(cx, wl, rows, L, args.steps, args.warmup, gather=gathered, keep=True)
     bam, rep = res["bam"], res["rep"]
     n_total = res["n_total"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, rep)                     # N > 1: rank 0's rows (all rows with --gather)
 
     if world == 1 and not args.no_selfcheck:
         check = n1_selfcheck(cx, wl, res, L)
