@@ -56,6 +56,12 @@ class ReportColumn(C.Structure):
                 ("nlevels", C.c_int32)]
 
 
+class VcfTable(C.Structure):
+    _fields_ = [("nrec", C.c_int64), ("nrec_file", C.c_int64), ("n_chrom", C.c_int32), ("chrom_names", C.POINTER(C.c_char_p)),
+                ("chrom", C.POINTER(C.c_int32)), ("pos", C.POINTER(C.c_int32)), ("ref", C.c_void_p), ("alt", C.c_void_p),
+                ("names", C.c_void_p), ("names_bytes", C.c_int64)]
+
+
 class PatternTable(C.Structure):
     _fields_ = [("npat", C.c_int64), ("ncol", C.c_int32), ("positions", C.POINTER(C.c_int32))] + \
                [(k, C.POINTER(C.c_int32)) for k in ("strand", "start", "end", "nbase")] + \
@@ -84,6 +90,10 @@ _SIGS = {
     "epi_get_xm_beta": (C.c_int, [_VP, _VP, _I64, _CS, _CS, _VP]),
     "epi_cx_report": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _I64, _CS, C.POINTER(CxTable)]),
     "epi_mhl_report": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _I64, _CS, C.c_int, C.c_int, _F64, C.POINTER(MhlTable)]),
+    "epi_get_base_freqs": (C.c_int, [_VP, _VP, _I64, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP]),
+    "epi_fisher_exact": (C.c_int, [_VP, _VP, _VP, _VP, _I64, _VP, C.c_int]),
+    "epi_read_vcf": (C.c_int, [_CS, C.POINTER(VcfTable)]),
+    "epi_vcf_free": (None, [C.POINTER(VcfTable)]),
     "epi_preprocess_bam": (C.c_int, [_CS, C.POINTER(BamOptions), C.POINTER(Templates)]),
     "epi_templates_free": (None, [C.POINTER(Templates)]),
     "epi_write_report": (C.c_int, [_CS, C.POINTER(ReportColumn), _I32, _I64, _I32, _I32]),
@@ -108,6 +118,7 @@ _SIGS = {
     "epi_batch_view": (C.c_int, [_VP, C.POINTER(_VP), C.POINTER(_VP), C.POINTER(_VP), C.POINTER(_I64)]),
     "epi_batch_threshold_reads_dev": (C.c_int, [_VP, _CS, _CS, _CS, _CS, _U32, _F64, _F64, _VP, _VP]),
     "epi_batch_get_xm_beta_dev": (C.c_int, [_VP, _CS, _CS, _VP, _VP]),
+    "epi_batch_base_freqs_dev": (C.c_int, [_VP, _VP, _VP, _VP, _I64, _VP, _VP]),
     "epi_batch_match_target_dev": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _VP, _VP]),
     "epi_batch_extract_patterns": (C.c_int, [_VP, _I32, _I32, _I32, _I32, _CS, _F64, _I32, _I32, _VP, _I32, _VP,
                                            C.POINTER(PatternTable)]),
@@ -162,7 +173,7 @@ def load():
         raise EpihipError(EPI_ERR_NODEVICE,
                           "libepihip.so is not built (%s missing): run `python -c 'import __graft_entry__ as g; g.build()'`; "
                           "there is no CPU fallback" % LIB_PATH)
-    host_only = bool(os.environ.get("EPIHIP_HOST_ONLY"))     # `make asan` library: BAM producer + report writer only
+    host_only = bool(os.environ.get("EPIHIP_HOST_ONLY"))     # `make asan` library: BAM producer, VCF reader, Fisher test, writer
     if not host_only:
         try:
             import torch  # noqa: F401  (loads torch's libamdhip64 first; ours resolves to the same SONAME)

@@ -1105,3 +1105,42 @@ static int preprocess_impl(const char *path, const epi_bam_options *opt_in, epi_
   for (size_t i = 0; i < names.size(); i++) out->target_names[i] = strdup(names[i].c_str());
   return EPI_OK;
 }
+
+// ---- whole-file inflate for the other host readers (vcf_reader.cpp) ----------------------------------------------
+// BGZF through the same block scan and parallel inflate as the BAM reader; a gzip file that is not BGZF through zlib
+// (any number of members); anything else is returned as it is.
+int epi::read_text_file(const char *path, std::vector<uint8_t> &out, int nthreads) {
+  out.clear();
+  FileView file;
+  if (open_file(path, file) != EPI_OK) return fail(EPI_ERR_ARG, "Unable to open file for reading: %s", path);
+  if (file.n < 2 || file.p[0] != 0x1f || file.p[1] != 0x8b) { out.assign(file.p, file.p + file.n); return EPI_OK; }
+  std::vector<Block> blocks;
+  if (bgzf_scan(file.p, file.n, blocks) == EPI_OK) {
+    size_t u = 0;
+    for (Block &b : blocks) { b.upos = u; u += b.ulen; }
+    out.resize(u);
+    return bgzf_inflate_range(file.p, blocks, 0, blocks.size(), out.data(), nthreads);
+  }
+  z_stream zs;
+  memset(&zs, 0, sizeof(zs));
+  if (inflateInit2(&zs, 15 + 32) != Z_OK) return fail(EPI_ERR_NOMEM, "inflateInit2 failed");
+  zs.next_in = const_cast<Bytef *>(file.p);
+  zs.avail_in = (uInt)file.n;                                // (a gzip file that is not BGZF: small, below 4 GiB)
+  uint8_t buf[1 << 16];
+  int rc = Z_OK;
+  for (;;) {
+    zs.next_out = buf;
+    zs.avail_out = sizeof(buf);
+    rc = inflate(&zs, Z_NO_FLUSH);
+    out.insert(out.end(), buf, buf + (sizeof(buf) - zs.avail_out));
+    if (rc == Z_STREAM_END) {
+      if (zs.avail_in == 0) break;
+      if (inflateReset(&zs) != Z_OK) { rc = Z_DATA_ERROR; break; }   // the next member
+      continue;
+    }
+    if (rc != Z_OK) break;
+  }
+  inflateEnd(&zs);
+  if (rc != Z_STREAM_END) return fail(EPI_ERR_ARG, "corrupt gzip file: %s", path);
+  return EPI_OK;
+}

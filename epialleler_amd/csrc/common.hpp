@@ -175,6 +175,7 @@ struct epi_batch {
   uint32_t cx_last_ctx_of_plane = 0;
   epi::DevBuf pass_tmp;                        // pass flags when thresholding could not be fused and the caller wants none
   epi::DevBuf host_io;                         // device side of the host-pointer calls (pass flags / per-read beta)
+  epi::DevBuf bf_flag;                         // base frequencies: the sites' sortedness verdict (base_freqs.hip)
   epi::DevBuf mhl_keep_tab;                    // fused lMHL: passing out-of-context counts per total (k_mhl_keep_table)
   int32_t mhl_keep_len = -1;
   double mhl_keep_oo = 0.0;
@@ -228,6 +229,9 @@ int read_scalars(epi_batch *b, hipStream_t s, const void *d_src, size_t bytes, v
 // costs ~9 ms of page faults on the copy threads -- twice the copy itself.
 void *table_block(size_t bytes);
 void table_block_release(void *p);
+
+// The bytes of a plain, gzip or BGZF file (bam_pack.cpp: BGZF blocks inflated by `nthreads` threads).
+int read_text_file(const char *path, std::vector<uint8_t> &out, int nthreads);
 
 // util kernels (util.hip)
 int scan_exclusive_u32(const uint32_t *d_in, uint32_t *d_out, int64_t n, uint32_t *d_total,

@@ -1,6 +1,6 @@
 // Rcpp shim: epialleleR's hot-path exports re-implemented as thin calls into libepihip.so (include/epihip.h).
 // Drop these definitions in place of src/rcpp_threshold_reads.cpp, src/rcpp_get_xm_beta.cpp, src/rcpp_cx_report.cpp,
-// src/rcpp_mhl_report.cpp and (optionally) the three readers of src/rcpp_read_bam.cpp: the [[Rcpp::export]] names and
+// src/rcpp_mhl_report.cpp, src/rcpp_get_base_freqs.cpp, src/rcpp_fep.cpp and (optionally) the three readers of src/rcpp_read_bam.cpp: the [[Rcpp::export]] names and
 // signatures are the reference's, so R/RcppExports.R, src/RcppExports.cpp and every R caller stay unchanged (see
 // INTEGRATION.md).  NOT compiled in this repository's image (no R, Rcpp or HTSlib here); everything that does not
 // touch an SEXP lives in epihip_shim_core.hpp, which IS compiled and tested here (tests/cpp/test_shim_core.cpp).
@@ -244,4 +244,40 @@ void rcpp_hip_materialize_seqxm(Rcpp::DataFrame &df) {
   Rcpp::XPtr<std::vector<std::string>> seqxm((SEXP)df.attr("seqxm_xptr"));
   Rcpp::XPtr<epihip_shim::TemplatesGuard> tg(soa);
   if (seqxm->empty() && tg->t.n > 0) epihip_shim::materialize(tg->t, *seqxm);
+}
+
+// ---- generateVcfReport's two exports (src/rcpp_get_base_freqs.cpp, src/rcpp_fep.cpp) ----------------------------------
+
+// [[Rcpp::export("rcpp_get_base_freqs")]]
+Rcpp::NumericMatrix rcpp_get_base_freqs(Rcpp::DataFrame &df, std::vector<bool> pass, Rcpp::DataFrame &vcf) {
+  Rcpp::IntegerVector rname = df["rname"], strand = df["strand"], start = df["start"], templid = df["templid"];
+  Rcpp::IntegerVector vcf_chr = vcf["seqnames"], vcf_pos = vcf["start"];
+  const R_xlen_t n = rname.size(), m = vcf_pos.size();
+  if ((R_xlen_t)pass.size() != n) Rcpp::stop("pass must have one entry per row");
+  epihip_shim::Soa s;
+  SEXP soa = df.attr("seqxm_soa_xptr");
+  if (soa != R_NilValue) {
+    Rcpp::XPtr<epihip_shim::TemplatesGuard> tg(soa);
+    epihip_shim::gather_soa(tg->t, templid.begin(), (int64_t)n, s, []() { Rcpp::checkUserInterrupt(); });
+  } else {
+    Rcpp::XPtr<std::vector<std::string>> seqxm((SEXP)df.attr("seqxm_xptr"));
+    epihip_shim::gather_rows(*seqxm, templid.begin(), (int64_t)n, s, []() { Rcpp::checkUserInterrupt(); });
+  }
+  std::vector<int32_t> p((size_t)n + 1);
+  for (R_xlen_t x = 0; x < n; x++) p[(size_t)x] = pass[(size_t)x] ? 1 : 0;
+  Rcpp::NumericMatrix res(m, 20);
+  try {
+    epihip_shim::base_freqs_into(s, rname.begin(), strand.begin(), start.begin(), (int64_t)n, p.data(), vcf_chr.begin(),
+                                 vcf_pos.begin(), (int64_t)m, res.begin());
+  } catch (const std::exception &e) { Rcpp::stop("%s", e.what()); }
+  return res;
+}
+
+// [[Rcpp::export]]
+std::vector<double> rcpp_fep(Rcpp::DataFrame &df, std::vector<std::string> colnames) {
+  Rcpp::NumericVector A = df[colnames[0]], B = df[colnames[1]], C = df[colnames[2]], D = df[colnames[3]];   // (NA_real_ is NaN)
+  std::vector<double> p((size_t)A.size());
+  try { epihip_shim::fep_into(A.begin(), B.begin(), C.begin(), D.begin(), (int64_t)A.size(), p.data()); }
+  catch (const std::exception &e) { Rcpp::stop("%s", e.what()); }
+  return p;
 }

@@ -10,10 +10,14 @@
 //  * gather_soa, RowOrder  the same row semantics for the producer's SoA, and the staleness check of the cached batch
 //  * *_report_into      the report tables copied straight into columns the caller owns (R vectors): one D2H copy
 //  * table guards       epi_cx_table / epi_mhl_table of the one-call entry points stay library-owned until freed
+//  * base_freqs_into    rcpp_get_base_freqs: gathered rows + VCF sites -> the nsite x 20 matrix in the caller's memory
+//  * fep_into           rcpp_fep: four count columns (R integers, or doubles with NA) -> two-sided p-values
 #pragma once
 #include <stdint.h>
 #include <string.h>
+#include <cmath>
 #include <stdexcept>
+#include <type_traits>
 #include <string>
 #include <vector>
 #include "epihip.h"
@@ -194,5 +198,30 @@ struct TemplatesGuard {                       // owner behind `seqxm_soa_xptr`
   TemplatesGuard &operator=(const TemplatesGuard &) = delete;
   ~TemplatesGuard() { epi_templates_free(&t); }
 };
+
+// rcpp_get_base_freqs (src/rcpp_get_base_freqs.cpp:15-57): `out` is the column-major nsite x 20 NumericMatrix.  pass as R
+// logicals (NULL = all TRUE); vcf_chr are factor codes over the BAM's rname levels (NA_integer_ = INT32_MIN: zero row).
+inline void base_freqs_into(const Soa &s, const int32_t *rname, const int32_t *strand, const int32_t *start, int64_t n,
+                            const int32_t *pass, const int32_t *vcf_chr, const int32_t *vcf_pos, int64_t nsite, double *out) {
+  check(epi_get_base_freqs(s.xm.data(), s.off.data(), n, rname, strand, start, pass, vcf_chr, vcf_pos, nsite, out));
+}
+
+// rcpp_fep (src/rcpp_fep.cpp:10-36) over columns of any numeric type: NA (INT32_MIN, or NaN in a double column) in any
+// cell gives NaN (NA_real_)
+template <class T>
+inline void fep_into(const T *a, const T *b, const T *c, const T *d, int64_t n, double *out, int nthreads = 1) {
+  std::vector<int32_t> v[4];
+  const T *src[4] = {a, b, c, d};
+  for (int k = 0; k < 4; k++) {
+    v[k].resize((size_t)n);
+    for (int64_t i = 0; i < n; i++) {
+      const T x = src[k][i];
+      bool na = false;
+      if constexpr (std::is_floating_point<T>::value) na = std::isnan(x);
+      v[k][(size_t)i] = na ? INT32_MIN : (int32_t)x;
+    }
+  }
+  check(epi_fisher_exact(v[0].data(), v[1].data(), v[2].data(), v[3].data(), n, out, nthreads));
+}
 
 }  // namespace epihip_shim

@@ -14,6 +14,13 @@
  *   epi_mhl_report       <-  rcpp_mhl_report       src/rcpp_mhl_report.cpp:46-228
  *                            (.Call "_epialleleR_rcpp_mhl_report",      R/RcppExports.R:40-42)
  *
+ * and, for generateVcfReport (R/generateVcfReport.R, .getBaseFreqReport R/internal.R:611-676):
+ *
+ *   epi_get_base_freqs   <-  rcpp_get_base_freqs   src/rcpp_get_base_freqs.cpp:15-57
+ *                            (.Call "_epialleleR_rcpp_get_base_freqs",  R/RcppExports.R)
+ *   epi_fisher_exact     <-  rcpp_fep              src/rcpp_fep.cpp:10-36 (host code)
+ *                            (.Call "_epialleleR_rcpp_fep",             R/RcppExports.R)
+ *
  * Input layout (what an R/Rcpp shim gathers from the data.frame + seqxm_xptr,
  * see INTEGRATION.md): templates in ROW order (i.e. already sorted by
  * (rname,start) as .readBam leaves them, R/internal.R:193-195):
@@ -91,6 +98,42 @@ int epi_mhl_report(const uint8_t *xm, const int64_t *off, const int32_t *rname,
                    const int32_t *strand, const int32_t *start, int64_t n,
                    const char *ctx, int hmax, int hmin, double max_ooctx_meth_frac,
                    epi_mhl_table *out);
+
+/* rcpp_get_base_freqs (src/rcpp_get_base_freqs.cpp:15-57): per VCF site, the bases of the reads that cover it, by
+ * strand and pass.  out is the reference's nsite x 20 NumericMatrix, column-major (out[col * nsite + i]); columns
+ * U+ACGTN, U-ACGTN, M+ACGTN, M-ACGTN, i.e. col = seq_nt16_int[byte >> 4] + (strand - 1) * 5 + pass * 10 (any code but
+ * A, C, G, T -- the 0xF? filler between mates included -- is N).  Sites in the caller's order; site_chr are rname
+ * factor codes, INT32_MIN (NA) gives a zero row.  The non-NA sites must be sorted by (code, pos) (the reference's
+ * stated precondition, :5): otherwise EPI_ERR_UNSORTED, as for rows out of (rname, start) order.  Rows whose strand
+ * is not 1 or 2 count nowhere.  pass may be NULL (all TRUE; NA is TRUE). */
+int epi_get_base_freqs(const uint8_t *xm, const int64_t *off, int64_t n, const int32_t *rname, const int32_t *strand,
+                       const int32_t *start, const int32_t *pass, const int32_t *site_chr, const int32_t *site_pos,
+                       int64_t nsite, double *out /* [20][nsite] */);
+
+/* rcpp_fep (src/rcpp_fep.cpp:10-36): two-sided Fisher exact p-value of each 2x2 table (a[i] b[i] / c[i] d[i]), the
+ * tables no more probable than the observed one (relative tolerance 1e-7) summed, clamped at 1.  NA (INT32_MIN) or a
+ * negative count in any cell gives NaN (NA_real_).  Host code (no device needed), `nthreads` threads. */
+int epi_fisher_exact(const int32_t *a, const int32_t *b, const int32_t *c, const int32_t *d, int64_t n, double *p_out,
+                     int nthreads);
+
+/* ---- VCF reader (.readVcf, R/internal.R:230-267: VariantAnnotation::readVcf(info = NA, geno = NA), then expand())
+ * Plain, gzip or BGZF text; the fixed columns CHROM POS ID REF ALT only.  One row per ALT allele of every record, in
+ * file order, keeping the rows .getBaseFreqReport keeps (R/internal.R:617-620): a one-base REF and a one-character ALT
+ * ("." is no allele).  Contigs are numbered in the order of the ##contig header lines, then of first appearance.
+ * Names: the ID column, or CHROM:POS_REF/ALT (ALT as written, all alleles) when it is ".". */
+typedef struct {               /* library-owned; release with epi_vcf_free */
+  int64_t nrec;                /* rows */
+  int64_t nrec_file;           /* data lines of the file */
+  int32_t n_chrom;
+  char **chrom_names;          /* [n_chrom] */
+  int32_t *chrom;              /* [nrec] 0-based index into chrom_names */
+  int32_t *pos;                /* [nrec] 1-based POS */
+  char *ref, *alt;             /* [nrec] one character each */
+  char *names;                 /* nrec NUL-terminated names back to back (names_bytes bytes) */
+  int64_t names_bytes;
+} epi_vcf;
+int epi_read_vcf(const char *path, epi_vcf *out);
+void epi_vcf_free(epi_vcf *v);
 
 /* ---- host-side producer (preprocessBam) ----------------------------------
  * BAM file -> packed templates sorted by (rname,start), as SoA host buffers (xm in
@@ -277,6 +320,15 @@ int epi_batch_extract_patterns(epi_batch *b, int32_t target_rname, int32_t targe
                                int32_t reverse_offset, const int32_t *hlght /* sorted, unique, inside the target */,
                                int32_t nhlght, void *stream, epi_pattern_table *out);
 void epi_pattern_table_free(epi_pattern_table *t);
+
+/* rcpp_get_base_freqs on a resident batch (see epi_get_base_freqs): d_site_chr / d_site_pos are nsite device int32
+ * (rname codes, 1-based positions) sorted by (code, pos), NA-coded sites removed -- equal keys (multi-ALT records) are
+ * allowed; EPI_ERR_UNSORTED otherwise, or when the rows are not sorted by (rname, start).  d_counts [20][nsite] u32 is
+ * overwritten (column-major as the drop-in's matrix).  d_pass: per-row flags or NULL = all TRUE.  Reads the rows through
+ * the batch's own view (every row layout).  Synchronises `stream` once (the two sortedness verdicts), then queues the
+ * counting kernel.  The counts are additive over row shards. */
+int epi_batch_base_freqs_dev(epi_batch *b, const int32_t *d_pass /* NULL = all TRUE */, const int32_t *d_site_chr,
+                             const int32_t *d_site_pos, int64_t nsite, uint32_t *d_counts /* [20][nsite] */, void *stream);
 
 /* ---- multi-GPU (row-range shards; see DESIGN.md "Multi-GPU") -------------
  * Tiles are cut on an absolute position grid (epi_tile_positions() wide), so
