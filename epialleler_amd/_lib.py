@@ -94,6 +94,15 @@ _SIGS = {
     "epi_fisher_exact": (C.c_int, [_VP, _VP, _VP, _VP, _I64, _VP, C.c_int]),
     "epi_read_vcf": (C.c_int, [_CS, C.POINTER(VcfTable)]),
     "epi_vcf_free": (None, [C.POINTER(VcfTable)]),
+    "epi_read_genome": (C.c_int, [_CS, C.c_int, C.POINTER(_VP)]),
+    "epi_genome_free": (None, [_VP]),
+    "epi_genome_count": (_I32, [_VP]),
+    "epi_genome_name": (C.c_char_p, [_VP, _I32]),
+    "epi_genome_length": (_I64, [_VP, _I32]),
+    "epi_genome_sequence": (_VP, [_VP, _I32]),
+    "epi_call_methylation": (C.c_int, [_VP, _CS, _CS, _VP, C.c_int, C.POINTER(_I64), C.POINTER(_I64)]),
+    "epi_call_methylation_windowed": (C.c_int, [_VP, _CS, _CS, _VP, _CS, C.c_int, _I32, C.POINTER(_I64), C.POINTER(_I64)]),
+    "epi_bgzf_write_file": (C.c_int, [_CS, _VP, _I64, C.c_int]),
     "epi_preprocess_bam": (C.c_int, [_CS, C.POINTER(BamOptions), C.POINTER(Templates)]),
     "epi_templates_free": (None, [C.POINTER(Templates)]),
     "epi_write_report": (C.c_int, [_CS, C.POINTER(ReportColumn), _I32, _I64, _I32, _I32]),

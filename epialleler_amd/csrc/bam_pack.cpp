@@ -1106,6 +1106,342 @@ static int preprocess_impl(const char *path, const epi_bam_options *opt_in, epi_
   return EPI_OK;
 }
 
+// ---- callMethylation: BAM in, BAM out (rcpp_call_methylation_genome, src/rcpp_call_methylation.cpp:27-177, with
+// .callMethylation's tag choice, R/internal.R:405-432) ------------------------------------------------------------------
+// The file goes through the reader's block scan, parallel inflate and parse_record window by window.  Per window the
+// host picks the records to call (mapped, carrying the strand tag, no XM yet), checks them and packs their CIGAR and
+// SEQ; the GPU computes their XM bytes (call_methylation.hip); the records are then written out in input order -- the
+// called ones with XG (when the tag was YD or ZS) and XM appended -- and deflated into BGZF blocks by `nthreads`
+// threads.  Host memory is bounded by the window (inflated bytes, the records written out, the packed call inputs).
+#ifndef EPI_HOST_ONLY
+namespace {
+
+// bam_aux_get: the tag's type byte, or NULL when the record has no such tag (or its aux data is malformed before it)
+const uint8_t *aux_find(const Rec &r, char a, char b) {
+  const uint8_t *p = r.aux;
+  while (p + 3 <= r.end) {
+    const bool hit = (char)p[0] == a && (char)p[1] == b;
+    const char ty = (char)p[2];
+    if (hit) return p + 2;
+    p += 3;
+    switch (ty) {
+      case 'A': case 'c': case 'C': p += 1; break;
+      case 's': case 'S': p += 2; break;
+      case 'i': case 'I': case 'f': p += 4; break;
+      case 'Z': case 'H': {
+        const uint8_t *e = (const uint8_t *)memchr(p, 0, (size_t)(r.end - p));
+        if (!e) return nullptr;
+        p = e + 1;
+        break;
+      }
+      case 'B': {
+        if (p + 5 > r.end) return nullptr;
+        const char st = (char)p[0];
+        const size_t es = (st == 'c' || st == 'C') ? 1 : (st == 's' || st == 'S') ? 2 : 4;
+        p += 5 + (size_t)rd32(p + 1) * es;
+        break;
+      }
+      default: return nullptr;
+    }
+  }
+  return nullptr;
+}
+
+enum StrandTag { TAG_XG = 0, TAG_YD = 1, TAG_ZS = 2 };
+
+struct Window {                       // what one window's records turn into
+  std::vector<uint8_t> call;          // per record: 1 = call it
+  std::vector<uint8_t> s_meth, s_conv;
+  std::vector<uint64_t> out_off;      // per record: where its output starts (n + 1 entries)
+  std::vector<int64_t> call_idx;      // per record: its index among the called ones
+  std::vector<CallRec> crec;
+  std::vector<uint32_t> cigar;
+  std::vector<uint8_t> seq, xm;
+  std::vector<uint8_t> out;
+};
+
+}  // namespace
+
+static int call_impl(epi_engine *eng, const char *in_path, const char *out_path, epi_genome *g, const char *force_tag,
+                     int nthreads, int32_t window_kib, int64_t *nrecs_out, int64_t *ncalled_out) {
+  FileView file;
+  EPI_TRY(open_file(in_path, file));
+  std::vector<Block> blocks;
+  EPI_TRY(bgzf_scan(file.p, file.n, blocks));
+  const size_t window = window_kib > 0 ? (size_t)window_kib * 1024 : (size_t)64 << 20;
+  const size_t K = nthreads > 1 ? (size_t)(nthreads > 16 ? 16 : nthreads) : 1;
+  std::vector<uint8_t> buf;
+  std::vector<size_t> roff;
+  std::vector<Rec> recs;
+  std::vector<std::string> names;
+  std::vector<int64_t> lens;
+  size_t carry = 0, bi = 0, hdr_end = 0;
+  bool header_done = false, checked = false;
+  StrandTag tag = TAG_XG;
+  BgzfWriter out;
+  CallWork wk;
+  Window W;
+  int64_t nrecs = 0, ncalled = 0;
+  // phase times (EPIHIP_BAM_TIMING, as for the reader): inflate + index, host preparation, GPU, splice, deflate + write
+  const bool timing = epi::options().bam_timing != 0;
+  auto tnow = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+  double t_phase[5] = {0, 0, 0, 0, 0}, t_mark = tnow();
+  auto lap = [&](int k) { const double t = tnow(); t_phase[k] += t - t_mark; t_mark = t; };
+
+  // runs f(lo, hi) over K ranges of [0, n) on K threads; the first error wins
+  auto parallel = [&](size_t n, auto &&f) -> int {
+    const size_t k = n < 4096 ? 1 : K;
+    std::vector<int> rcs(k, EPI_OK);
+    std::vector<std::string> msgs(k);
+    auto run = [&](size_t t) {
+      try {
+        rcs[t] = f(n * t / k, n * (t + 1) / k);
+      } catch (const std::bad_alloc &) {
+        rcs[t] = fail(EPI_ERR_NOMEM, "epi_call_methylation: out of host memory");
+      }
+      if (rcs[t] != EPI_OK) msgs[t] = epi_last_error();
+    };
+    std::vector<std::thread> th;
+    for (size_t t = 1; t < k; t++) th.emplace_back(run, t);
+    run(0);
+    for (auto &t : th) t.join();
+    for (size_t t = 0; t < k; t++)
+      if (rcs[t] != EPI_OK) return fail(rcs[t], "%s", msgs[t].c_str());
+    return EPI_OK;
+  };
+
+  for (bool final = blocks.empty();;) {
+    size_t b1 = bi, add = 0;
+    while (b1 < blocks.size() && (b1 == bi || add + blocks[b1].ulen <= window)) { blocks[b1].upos = carry + add; add += blocks[b1].ulen; b1++; }
+    final = b1 == blocks.size();
+    buf.resize(carry + add);
+    EPI_TRY(bgzf_inflate_range(file.p, blocks, bi, b1, buf.data(), nthreads));
+    bi = b1;
+    size_t p = hdr_end;
+    if (!header_done) {                                      // magic, text, reference names and lengths
+      if (buf.size() >= 4 && memcmp(buf.data(), "BAM\1", 4) != 0) return fail(EPI_ERR_ARG, "Unable to read input BAM header");
+      bool complete = false;
+      do {
+        if (buf.size() < 12) break;
+        size_t q = 8 + (size_t)rd32(buf.data() + 4);
+        if (q + 4 > buf.size()) break;
+        const uint32_t n_ref = rd32(buf.data() + q);
+        q += 4;
+        names.clear(); lens.clear();
+        bool ok = true;
+        for (uint32_t i = 0; i < n_ref && ok; i++) {
+          if (q + 4 > buf.size()) { ok = false; break; }
+          const uint32_t l = rd32(buf.data() + q);
+          if (q + 4 + (size_t)l + 4 > buf.size()) { ok = false; break; }
+          if (l == 0 || buf[q + 4 + l - 1] != 0) return fail(EPI_ERR_ARG, "Unable to read input BAM header");
+          names.emplace_back((const char *)buf.data() + q + 4);
+          lens.push_back((int64_t)rd32(buf.data() + q + 4 + l));
+          q += 4 + (size_t)l + 4;
+        }
+        if (!ok) break;
+        hdr_end = q;
+        complete = true;
+      } while (0);
+      if (!complete) {
+        if (final) return fail(EPI_ERR_ARG, "Unable to read input BAM header");
+        carry = buf.size();
+        continue;
+      }
+      header_done = true;
+      p = hdr_end;
+    }
+    // the window's complete records
+    roff.clear();
+    while (p + 4 <= buf.size()) {
+      const uint32_t bs = rd32(buf.data() + p);
+      if (p + 4 + (size_t)bs > buf.size()) break;            // cut by the window
+      roff.push_back(p);
+      p += 4 + (size_t)bs;
+    }
+    if (final && p != buf.size()) return fail(EPI_ERR_ARG, "truncated BAM record");
+    const size_t nrec = roff.size();
+    recs.resize(nrec);
+    EPI_TRY(parallel(nrec, [&](size_t lo, size_t hi) -> int {
+      for (size_t i = lo; i < hi; i++)
+        if (!parse_record(buf.data() + roff[i] + 4, rd32(buf.data() + roff[i]), &recs[i])) return fail(EPI_ERR_ARG, "corrupt BAM record");
+      return EPI_OK;
+    }));
+    lap(0);
+    if (!checked) {
+      if (nrec < 1024 && !final) { carry = buf.size(); continue; }   // .checkBam looks at the first 1024 records
+      // ---- .callMethylation (R/internal.R:412-423): the strand tag from the first 1024 records ----
+      bool tXG = false, tYD = false, tZS = false;
+      for (size_t i = 0; i < nrec && i < 1024; i++) {
+        tXG |= aux_find(recs[i], 'X', 'G') != nullptr;
+        tYD |= aux_find(recs[i], 'Y', 'D') != nullptr;
+        tZS |= aux_find(recs[i], 'Z', 'S') != nullptr;
+      }
+      if (force_tag) tag = strcmp(force_tag, "XG") == 0 ? TAG_XG : strcmp(force_tag, "YD") == 0 ? TAG_YD : TAG_ZS;
+      else if (nrec == 0) return fail(EPI_ERR_ARG, "Empty file provided! Exiting");
+      else if (tXG) tag = TAG_XG;
+      else if (tYD) tag = TAG_YD;
+      else if (tZS) tag = TAG_ZS;
+      else return fail(EPI_ERR_ARG, "Unable to call methylation: neither of XG/YD/ZS tags is present (genome strand unknown).\nExiting");
+      // ---- the output and the header check (src/rcpp_call_methylation.cpp:41-72) ----
+      EPI_TRY(out.open(out_path));
+      const int32_t ng = epi_genome_count(g);
+      for (size_t i = 0; i < names.size(); i++)
+        if ((int32_t)i >= ng || epi_genome_length(g, (int32_t)i) != lens[i] || names[i] != epi_genome_name(g, (int32_t)i))
+          return fail(EPI_ERR_ARG, "BAM reference sequence doesn't match the provided genome sequence");
+      EPI_TRY(out.write(buf.data(), hdr_end, nthreads));     // the input header, verbatim
+      checked = true;
+    }
+    const uint8_t *tag_name = (const uint8_t *)(tag == TAG_XG ? "XG" : tag == TAG_YD ? "YD" : "ZS");
+
+    // ---- which records are called, and how large each one is written out ----
+    W.call.resize(nrec); W.s_meth.resize(nrec); W.s_conv.resize(nrec); W.out_off.resize(nrec + 1);
+    EPI_TRY(parallel(nrec, [&](size_t lo, size_t hi) -> int {
+      for (size_t i = lo; i < hi; i++) {
+        const Rec &r = recs[i];
+        const uint32_t bs = rd32(buf.data() + roff[i]);
+        W.call[i] = 0;
+        W.out_off[i + 1] = 4 + (uint64_t)bs;
+        const uint8_t *st = aux_find(r, (char)tag_name[0], (char)tag_name[1]);
+        if ((r.flag & 4) || !st || aux_find(r, 'X', 'M')) continue;      // written unchanged (:84-89)
+        // the strand tag's first two characters (bam_aux_get's pointer [1] and [2])
+        const uint8_t c1 = st + 1 < r.end ? st[1] : 0, c2 = st + 2 < r.end ? st[2] : 0;
+        if (tag == TAG_XG) { W.s_meth[i] = c1; W.s_conv[i] = c2; }
+        else {
+          const bool ga = tag == TAG_YD ? c1 == 'r' : c1 == '-';            // (:92-97)
+          W.s_meth[i] = ga ? 'G' : 'C'; W.s_conv[i] = ga ? 'A' : 'T';
+        }
+        // the checks that keep every access in bounds (the reference reads out of bounds here)
+        if (r.tid < 0 || (size_t)r.tid >= names.size()) return fail(EPI_ERR_ARG, "corrupt BAM record %s: reference id out of range", r.qname);
+        if (r.pos < 0) return fail(EPI_ERR_ARG, "corrupt BAM record %s: position out of range", r.qname);
+        uint64_t qlen = 0, rlen = 0;
+        for (uint32_t k = 0; k < r.n_cigar; k++) {
+          const uint32_t c = rd32(r.cigar + 4 * k), op = c & 0xF, len = c >> 4;
+          if (op > 9) return fail(EPI_ERR_ARG, "Unknown CIGAR operation for BAM entry %s", r.qname);
+          if (op == 0 || op == 1 || op == 4 || op == 7 || op == 8) qlen += len;
+          if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) rlen += len;
+        }
+        if (qlen != (uint64_t)r.l_seq) return fail(EPI_ERR_ARG, "corrupt BAM record %s: CIGAR does not match the sequence length", r.qname);
+        if ((uint64_t)r.pos + rlen > (uint64_t)lens[(size_t)r.tid])
+          return fail(EPI_ERR_ARG, "corrupt BAM record %s: alignment runs past the end of reference sequence %s", r.qname, names[(size_t)r.tid].c_str());
+        const uint64_t grown = (uint64_t)bs + (tag == TAG_XG ? 0 : 6) + 4 + (uint64_t)r.l_seq;
+        if (grown > 0x7FFFFFFFull) return fail(EPI_ERR_ARG, "corrupt BAM record %s: record too large", r.qname);
+        W.call[i] = 1;
+        W.out_off[i + 1] = 4 + grown;
+      }
+      return EPI_OK;
+    }));
+    // ---- offsets: output bytes, and the packed inputs / XM bytes of the called records ----
+    W.out_off[0] = 0;
+    W.call_idx.resize(nrec);
+    int64_t ncall = 0, ncig = 0, nseq = 0, nxm = 0;
+    W.crec.clear();
+    for (size_t i = 0; i < nrec; i++) {
+      W.out_off[i + 1] += W.out_off[i];
+      if (!W.call[i]) continue;
+      const Rec &r = recs[i];
+      CallRec c;
+      memset(&c, 0, sizeof(c));
+      c.cig_off = ncig; c.seq_off = nseq; c.xm_off = nxm;
+      c.tid = r.tid; c.pos = r.pos; c.l_seq = r.l_seq; c.n_cig = (int32_t)r.n_cigar;
+      c.s_meth = W.s_meth[i]; c.s_conv = W.s_conv[i];
+      W.crec.push_back(c);
+      W.call_idx[i] = ncall++;
+      ncig += r.n_cigar; nseq += ((int64_t)r.l_seq + 1) / 2; nxm += r.l_seq;
+    }
+    W.cigar.resize((size_t)ncig); W.seq.resize((size_t)nseq); W.xm.resize((size_t)nxm);
+    EPI_TRY(parallel(nrec, [&](size_t lo, size_t hi) -> int {
+      for (size_t i = lo; i < hi; i++) {
+        if (!W.call[i]) continue;
+        const Rec &r = recs[i];
+        const CallRec &c = W.crec[(size_t)W.call_idx[i]];
+        if (r.n_cigar) memcpy(W.cigar.data() + c.cig_off, r.cigar, 4 * (size_t)r.n_cigar);
+        if (r.l_seq) memcpy(W.seq.data() + c.seq_off, r.seq, ((size_t)r.l_seq + 1) / 2);
+      }
+      return EPI_OK;
+    }));
+    lap(1);
+    // ---- the GPU: XM of every called record ----
+    EPI_TRY(call_methylation_window(eng, g, wk, W.crec.data(), ncall, W.cigar.data(), ncig, W.seq.data(), nseq, nxm, W.xm.data()));
+    lap(2);
+    // ---- the records, in input order, with the new tags appended (bam_aux_append / bam_aux_update_str) ----
+    W.out.resize((size_t)W.out_off[nrec]);
+    EPI_TRY(parallel(nrec, [&](size_t lo, size_t hi) -> int {
+      for (size_t i = lo; i < hi; i++) {
+        const uint8_t *src = buf.data() + roff[i];
+        const uint32_t bs = rd32(src);
+        uint8_t *o = W.out.data() + W.out_off[i];
+        if (!W.call[i]) { memcpy(o, src, 4 + (size_t)bs); continue; }
+        const uint64_t nb = W.out_off[i + 1] - W.out_off[i] - 4;
+        o[0] = (uint8_t)nb; o[1] = (uint8_t)(nb >> 8); o[2] = (uint8_t)(nb >> 16); o[3] = (uint8_t)(nb >> 24);
+        memcpy(o + 4, src + 4, bs);
+        o += 4 + (size_t)bs;
+        if (tag != TAG_XG) {
+          const bool ga = W.s_meth[i] == 'G';
+          const uint8_t xg[6] = {'X', 'G', 'Z', (uint8_t)(ga ? 'G' : 'C'), (uint8_t)(ga ? 'A' : 'T'), 0};
+          memcpy(o, xg, 6);
+          o += 6;
+        }
+        o[0] = 'X'; o[1] = 'M'; o[2] = 'Z';
+        const Rec &r = recs[i];
+        if (r.l_seq) memcpy(o + 3, W.xm.data() + W.crec[(size_t)W.call_idx[i]].xm_off, (size_t)r.l_seq);
+        o[3 + r.l_seq] = 0;
+      }
+      return EPI_OK;
+    }));
+    lap(3);
+    EPI_TRY(out.write(W.out.data(), W.out.size(), nthreads));
+    lap(4);
+    nrecs += (int64_t)nrec;
+    ncalled += ncall;
+    carry = buf.size() - p;
+    if (carry) memmove(buf.data(), buf.data() + p, carry);
+    buf.resize(carry);
+    hdr_end = 0;
+    if (final) break;
+  }
+  if (!checked) return fail(EPI_ERR_ARG, "Empty file provided! Exiting");
+  EPI_TRY(out.close());
+  lap(4);
+  if (timing)
+    fprintf(stderr, "[call] inflate+index %.3f s  prepare %.3f s  gpu %.3f s  splice %.3f s  deflate+write %.3f s\n",
+            t_phase[0], t_phase[1], t_phase[2], t_phase[3], t_phase[4]);
+  *nrecs_out = nrecs;
+  *ncalled_out = ncalled;
+  return EPI_OK;
+}
+
+extern "C" int epi_call_methylation_windowed(epi_engine *eng, const char *in_path, const char *out_path, epi_genome *g,
+                                             const char *tag, int nthreads, int32_t window_kib, int64_t *nrecs,
+                                             int64_t *ncalled) {
+  if (!in_path || !out_path || !g || !nrecs || !ncalled) return fail(EPI_ERR_ARG, "epi_call_methylation: NULL argument");
+  if (tag && strcmp(tag, "XG") != 0 && strcmp(tag, "YD") != 0 && strcmp(tag, "ZS") != 0)
+    return fail(EPI_ERR_ARG, "epi_call_methylation: tag must be XG, YD or ZS");
+  *nrecs = 0; *ncalled = 0;
+  if (!eng) EPI_TRY(epi_default_engine(&eng));               // no device: fails here, before any file is touched
+  int rc;
+  bool wrote = false;
+  try {
+    struct stat st;
+    wrote = !(*out_path && stat(out_path, &st) == 0);        // (a partial output is removed only if this call created it)
+    rc = call_impl(eng, in_path, out_path, g, tag, nthreads, window_kib, nrecs, ncalled);
+  } catch (const std::bad_alloc &) {
+    rc = fail(EPI_ERR_NOMEM, "epi_call_methylation: out of host memory");
+  } catch (...) {
+    rc = fail(EPI_ERR_ARG, "epi_call_methylation: unexpected failure while reading %s", in_path);
+  }
+  if (rc != EPI_OK) {
+    *nrecs = 0; *ncalled = 0;
+    if (wrote && *out_path) (void)unlink(out_path);
+  }
+  return rc;
+}
+
+extern "C" int epi_call_methylation(epi_engine *eng, const char *in_path, const char *out_path, epi_genome *g, int nthreads,
+                                    int64_t *nrecs, int64_t *ncalled) {
+  return epi_call_methylation_windowed(eng, in_path, out_path, g, nullptr, nthreads, 0, nrecs, ncalled);
+}
+#endif  // EPI_HOST_ONLY
+
 // ---- whole-file inflate for the other host readers (vcf_reader.cpp) ----------------------------------------------
 // BGZF through the same block scan and parallel inflate as the BAM reader; a gzip file that is not BGZF through zlib
 // (any number of members); anything else is returned as it is.

@@ -233,6 +233,44 @@ void table_block_release(void *p);
 // The bytes of a plain, gzip or BGZF file (bam_pack.cpp: BGZF blocks inflated by `nthreads` threads).
 int read_text_file(const char *path, std::vector<uint8_t> &out, int nthreads);
 
+// BGZF output (bgzf_writer.cpp): blocks of at most 0xff00 input bytes, deflated by `nthreads` threads, written in order;
+// close() appends the end-of-file block.  Each write() ends with a short block (callers write large pieces).
+class BgzfWriter {
+ public:
+  BgzfWriter() = default;
+  BgzfWriter(const BgzfWriter &) = delete;
+  BgzfWriter &operator=(const BgzfWriter &) = delete;
+  ~BgzfWriter();
+  int open(const char *path);
+  int write(const uint8_t *data, size_t n, int nthreads);
+  int close();
+ private:
+  void *f_ = nullptr;
+};
+
+// genome.cpp: the genome's bytes and contig offsets on `device`, uploaded by the first call there and kept resident
+int genome_device(epi_genome *g, int device, const uint8_t **d_seq, const int64_t **d_off);
+
+// call_methylation.hip: one window of records to call.  The host fills the records and the packed CIGAR / SEQ arrays
+// while it parses the BAM records; the kernels write each record's XM bytes to xm + xm_off.
+struct CallRec {
+  int64_t cig_off;     // first CIGAR op in the window's packed u32 array
+  int64_t seq_off;     // first byte of the record's 4-bit SEQ in the window's packed array
+  int64_t xm_off;      // first XM byte of the record in the window's output
+  int32_t tid, pos;    // contig (genome index) and 0-based leftmost position
+  int32_t l_seq, n_cig;
+  uint8_t s_meth, s_conv;   // the strand tag's two characters: 'C','T' (forward table) or 'G','A' (reverse table)
+  uint8_t pad[6];
+};
+static_assert(sizeof(CallRec) == 48, "CallRec layout");
+struct CallWork {      // device buffers of the windows, grown on demand
+  DevBuf recs, cig, seq, ref, xm;
+  ~CallWork();
+};
+int call_methylation_window(epi_engine *eng, epi_genome *g, CallWork &wk, const CallRec *recs, int64_t nrec,
+                            const uint32_t *cigar, int64_t ncig, const uint8_t *seq, int64_t nseq, int64_t nxm,
+                            uint8_t *xm_out);
+
 // util kernels (util.hip)
 int scan_exclusive_u32(const uint32_t *d_in, uint32_t *d_out, int64_t n, uint32_t *d_total,
                        DevBuf &tmp, hipStream_t s);
@@ -279,7 +317,7 @@ struct Options {
   int pr_group = 0;          // EPIHIP_GROUP         lanes per read of the general per-read kernel
   int pr_rpg = 0;            // EPIHIP_PR_RPG
   int pr_wide = 1;           // EPIHIP_PR_WIDE=0
-  int bam_timing = 0;        // EPIHIP_BAM_TIMING    phase times of the BAM reader on stderr
+  int bam_timing = 0;        // EPIHIP_BAM_TIMING    phase times of the BAM reader and of callMethylation on stderr
   int no_hugepage = 0;       // EPIHIP_NO_HUGEPAGE   plain malloc for the BAM reader's large buffers (A/B runs)
   int no_libdeflate = 0;     // EPIHIP_NO_LIBDEFLATE zlib's inflate for the BGZF blocks although libdeflate.so.0 can be loaded
 };

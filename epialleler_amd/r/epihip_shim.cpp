@@ -1,6 +1,7 @@
 // Rcpp shim: epialleleR's hot-path exports re-implemented as thin calls into libepihip.so (include/epihip.h).
 // Drop these definitions in place of src/rcpp_threshold_reads.cpp, src/rcpp_get_xm_beta.cpp, src/rcpp_cx_report.cpp,
-// src/rcpp_mhl_report.cpp, src/rcpp_get_base_freqs.cpp, src/rcpp_fep.cpp and (optionally) the three readers of src/rcpp_read_bam.cpp: the [[Rcpp::export]] names and
+// src/rcpp_mhl_report.cpp, src/rcpp_get_base_freqs.cpp, src/rcpp_fep.cpp, src/rcpp_read_genome.cpp,
+// src/rcpp_call_methylation.cpp and (optionally) the three readers of src/rcpp_read_bam.cpp: the [[Rcpp::export]] names and
 // signatures are the reference's, so R/RcppExports.R, src/RcppExports.cpp and every R caller stay unchanged (see
 // INTEGRATION.md).  NOT compiled in this repository's image (no R, Rcpp or HTSlib here); everything that does not
 // touch an SEXP lives in epihip_shim_core.hpp, which IS compiled and tested here (tests/cpp/test_shim_core.cpp).
@@ -280,4 +281,27 @@ std::vector<double> rcpp_fep(Rcpp::DataFrame &df, std::vector<std::string> colna
   try { epihip_shim::fep_into(A.begin(), B.begin(), C.begin(), D.begin(), (int64_t)A.size(), p.data()); }
   catch (const std::exception &e) { Rcpp::stop("%s", e.what()); }
   return p;
+}
+
+// ---- preprocessGenome / callMethylation's two exports (src/rcpp_read_genome.cpp, src/rcpp_call_methylation.cpp) ----------
+
+// [[Rcpp::export]]
+Rcpp::List rcpp_read_genome(std::string fn, int nthreads) {
+  std::vector<uint64_t> rid, rlen;
+  std::vector<std::string> rname;
+  Rcpp::XPtr<epihip_shim::GenomeGuard> gg(new epihip_shim::GenomeGuard(), true);
+  try { epihip_shim::read_genome_into(fn, nthreads, *gg, rid, rname, rlen); }
+  catch (const std::exception &e) { Rcpp::stop("%s", e.what()); }
+  Rcpp::List res = Rcpp::List::create(Rcpp::Named("rid") = rid, Rcpp::Named("rname") = rname, Rcpp::Named("rlen") = rlen);
+  res.attr("rseq_xptr") = gg;                               // the sequences (and their resident device copies)
+  return res;
+}
+
+// [[Rcpp::export]]
+Rcpp::List rcpp_call_methylation_genome(std::string in_fn, std::string out_fn, Rcpp::List &genome, std::string tag, int nthreads) {
+  Rcpp::XPtr<epihip_shim::GenomeGuard> gg((SEXP)genome.attr("rseq_xptr"));
+  int64_t nrecs = 0, ncalled = 0;
+  try { epihip_shim::call_methylation(in_fn, out_fn, *gg, tag, nthreads, &nrecs, &ncalled); }
+  catch (const std::exception &e) { Rcpp::stop("%s", e.what()); }
+  return Rcpp::List::create(Rcpp::Named("nrecs") = (double)nrecs, Rcpp::Named("ncalled") = (double)ncalled);
 }

@@ -12,6 +12,9 @@
 //  * table guards       epi_cx_table / epi_mhl_table of the one-call entry points stay library-owned until freed
 //  * base_freqs_into    rcpp_get_base_freqs: gathered rows + VCF sites -> the nsite x 20 matrix in the caller's memory
 //  * fep_into           rcpp_fep: four count columns (R integers, or doubles with NA) -> two-sided p-values
+//  * GenomeGuard, read_genome_into   rcpp_read_genome: the FASTA file -> rid / rname / rlen and the epi_genome the list's
+//                       `rseq_xptr` owns
+//  * call_methylation   rcpp_call_methylation_genome: BAM in, BAM out, with the strand tag R chose
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -222,6 +225,37 @@ inline void fep_into(const T *a, const T *b, const T *c, const T *d, int64_t n, 
     }
   }
   check(epi_fisher_exact(v[0].data(), v[1].data(), v[2].data(), v[3].data(), n, out, nthreads));
+}
+
+// rcpp_read_genome (src/rcpp_read_genome.cpp:50-98): the sequences stay in the library; the list's rseq_xptr owns them
+struct GenomeGuard {
+  epi_genome *g = nullptr;
+  GenomeGuard() = default;
+  GenomeGuard(const GenomeGuard &) = delete;
+  GenomeGuard &operator=(const GenomeGuard &) = delete;
+  ~GenomeGuard() { epi_genome_free(g); }
+};
+inline void read_genome_into(const std::string &fn, int nthreads, GenomeGuard &gg, std::vector<uint64_t> &rid,
+                             std::vector<std::string> &rname, std::vector<uint64_t> &rlen) {
+  epi_genome_free(gg.g);
+  gg.g = nullptr;
+  check(epi_read_genome(fn.c_str(), nthreads > 0 ? nthreads : 1, &gg.g));
+  const int32_t n = epi_genome_count(gg.g);
+  rid.resize((size_t)n); rname.resize((size_t)n); rlen.resize((size_t)n);
+  for (int32_t i = 0; i < n; i++) {
+    rid[(size_t)i] = (uint64_t)i;
+    rname[(size_t)i] = epi_genome_name(gg.g, i);
+    rlen[(size_t)i] = (uint64_t)epi_genome_length(gg.g, i);
+  }
+}
+
+// rcpp_call_methylation_genome (src/rcpp_call_methylation.cpp:27-177): `tag` is what .callMethylation chose (XG/YD/ZS);
+// the default engine's device does the calls
+inline void call_methylation(const std::string &in_fn, const std::string &out_fn, const GenomeGuard &gg, const std::string &tag,
+                             int nthreads, int64_t *nrecs, int64_t *ncalled) {
+  if (!gg.g) throw std::runtime_error("genome object has no sequences attached");
+  check(epi_call_methylation_windowed(nullptr, in_fn.c_str(), out_fn.c_str(), gg.g, tag.c_str(), nthreads > 0 ? nthreads : 1, 0,
+                                      nrecs, ncalled));
 }
 
 }  // namespace epihip_shim

@@ -135,6 +135,35 @@ typedef struct {               /* library-owned; release with epi_vcf_free */
 int epi_read_vcf(const char *path, epi_vcf *out);
 void epi_vcf_free(epi_vcf *v);
 
+/* ---- genome and methylation calling (preprocessGenome / callMethylation) ------------------------------------------
+ * epi_read_genome: a FASTA file (plain, gzip or BGZF; no index needed) -> the sequences in file order.  A name is the
+ * header line up to the first whitespace; every byte other than aAcCgGtTnN becomes 'N', lower case becomes upper case;
+ * a repeated name is an error.  The object uploads itself to a device the first time a call there needs it and stays
+ * resident until epi_genome_free. */
+typedef struct epi_genome epi_genome;
+int epi_read_genome(const char *path, int nthreads, epi_genome **out);
+void epi_genome_free(epi_genome *g);
+int32_t epi_genome_count(const epi_genome *g);
+const char *epi_genome_name(const epi_genome *g, int32_t i);       /* NULL when i is out of range */
+int64_t epi_genome_length(const epi_genome *g, int32_t i);         /* -1 when i is out of range */
+const char *epi_genome_sequence(const epi_genome *g, int32_t i);   /* epi_genome_length(g, i) bytes, not NUL-terminated */
+
+/* rcpp_call_methylation_genome + .callMethylation (R/internal.R:405-432): the strand tag (XG, else YD, else ZS) is chosen
+ * from the first 1024 records; the header's reference sequences must equal the genome's; every record is written in
+ * input order, records that are mapped, carry the strand tag and have no XM get XG (when absent) and XM computed on
+ * the GPU.  engine NULL: the default engine.  The output is BGZF written by `nthreads` compressing threads.
+ * _windowed: tag "XG" / "YD" / "ZS" forces the strand tag (rcpp_call_methylation_genome's own contract: no check of the
+ * first records), NULL chooses it as above; window_kib: inflated bytes per processing window (0: the default), only
+ * memory use and batch sizes depend on it. */
+int epi_call_methylation(struct epi_engine *eng, const char *in_path, const char *out_path, epi_genome *g, int nthreads,
+                         int64_t *nrecs, int64_t *ncalled);
+int epi_call_methylation_windowed(struct epi_engine *eng, const char *in_path, const char *out_path, epi_genome *g,
+                                  const char *tag, int nthreads, int32_t window_kib, int64_t *nrecs, int64_t *ncalled);
+
+/* BGZF writer (host): `n` bytes as blocks of at most 0xff00 input bytes (BC extra field, CRC32), compressed at level 6 by
+ * `nthreads` threads and written in order, then the 28-byte end-of-file block. */
+int epi_bgzf_write_file(const char *path, const uint8_t *data, int64_t n, int nthreads);
+
 /* ---- host-side producer (preprocessBam) ----------------------------------
  * BAM file -> packed templates sorted by (rname,start), as SoA host buffers (xm in
  * pinned memory when a HIP device is usable).  Replaces rcpp_check_bam

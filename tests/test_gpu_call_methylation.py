@@ -1,0 +1,384 @@
+"""callMethylation on the GPU: every known answer of the reference's test_callMethylation.R (tests/golden/call_expected.json)
+and record-exact parity of the output BAM with a Python restatement of rcpp_call_methylation_genome
+(src/rcpp_call_methylation.cpp:27-177), on the fixtures and on seeded synthetic BAMs over a synthetic genome."""
+import gzip
+import json
+import os
+import random
+import struct
+
+import numpy as np
+import pytest
+
+import epialleler_amd as ea
+from oracle import bamio
+from helpers import GOLDEN, write_bam
+
+pytestmark = pytest.mark.gpu
+
+BAMS = os.path.join(GOLDEN, "bam")
+FASTA = os.path.join(BAMS, "reference.fasta.gz")
+with open(os.path.join(GOLDEN, "call_expected.json")) as _f:
+    EXPECTED = json.load(_f)
+
+NT16 = b"=ACMGRSVTWYHKDBN"
+
+
+# ---- the restatement ----------------------------------------------------------------------------------------------
+
+def read_fasta(path):
+    """name -> upper-case ACGTN bytes (faidx: name up to the first whitespace, printable bytes only)."""
+    data = gzip.open(path, "rb").read() if open(path, "rb").read(2) == b"\x1f\x8b" else open(path, "rb").read()
+    keep = bytes(c if chr(c) in "ACGTN" else ord("N") for c in range(256))
+    out, name = {}, None
+    for line in data.split(b"\n"):
+        if line.startswith(b">"):
+            name = line[1:].split()[0].decode()
+            out[name] = bytearray()
+        elif name is not None:
+            out[name] += bytes(c for c in line if 33 <= c <= 126).upper().translate(keep)
+    return {k: bytes(v) for k, v in out.items()}
+
+
+def _tri_ok(c):
+    return c in (1, 3, 4, 6, 7)
+
+
+def ctx_forward(b0, b1, b2):
+    if b0 != 3 or not _tri_ok(b1) or not _tri_ok(b2):
+        return ord(".")
+    return ord("z") if b1 == 7 else ord("x") if b2 == 7 else ord("h")
+
+
+def ctx_reverse(b0, b1, b2):
+    if b2 != 7 or not _tri_ok(b0) or not _tri_ok(b1):
+        return ord(".")
+    return ord("z") if b1 == 3 else ord("x") if b0 == 3 else ord("h")
+
+
+def split_bam(path):
+    """(header bytes, [raw record bytes incl. block_size]) of the inflated stream."""
+    with gzip.open(path, "rb") as f:
+        data = f.read()
+    p = 8 + struct.unpack_from("<i", data, 4)[0]
+    n_ref = struct.unpack_from("<i", data, p)[0]
+    p += 4
+    for _ in range(n_ref):
+        p += 4 + struct.unpack_from("<i", data, p)[0] + 4
+    header, raws = data[:p], []
+    while p < len(data):
+        bs = struct.unpack_from("<i", data, p)[0]
+        raws.append(data[p:p + 4 + bs])
+        p += 4 + bs
+    return header, raws
+
+
+def call_xm(rec, g, s_meth, s_conv):
+    """XM of one record: the reference in query space with two bases of halo, the triad context, the call."""
+    pos, rs, rpos = rec.pos, bytearray(), 0
+    for v in rec.cigar:
+        op, ln = int(v) & 15, int(v) >> 4
+        if op in (0, 7):
+            rs += g[pos + rpos:pos + rpos + ln]
+            rpos += ln
+        elif op == 8:
+            rs += b"N" * ln
+            rpos += ln
+        elif op in (1, 4):
+            rs += b"N" * ln
+        elif op in (2, 3):
+            rpos += ln
+    left = len(g) - pos - rpos
+    full = bytes([g[pos - 2] if pos >= 2 else 78, g[pos - 1] if pos >= 1 else 78]) + bytes(rs) + \
+        bytes([g[pos + rpos] if left >= 1 else 78, g[pos + rpos + 1] if left >= 2 else 78])
+    fwd = s_meth == ord("C")
+    xm = bytearray()
+    for i in range(len(rec.qual)):
+        t = full[i + 2:i + 5] if fwd else full[i:i + 3]
+        x = (ctx_forward if fwd else ctx_reverse)(t[0] & 7, t[1] & 7, t[2] & 7)
+        if x != ord("."):
+            nib = (int(rec.seq[i >> 1]) >> 4) if i % 2 == 0 else (int(rec.seq[i >> 1]) & 15)
+            base = NT16[nib]
+            if base == s_meth:
+                x &= 0xDF
+            elif base != s_conv:
+                x = ord(".")
+        xm.append(x)
+    return bytes(xm)
+
+
+def expected_output(in_path, genome):
+    """(inflated output stream, nrecs, ncalled) as rcpp_call_methylation_genome writes it."""
+    names, recs = bamio.read_bam_records(in_path)
+    header, raws = split_bam(in_path)
+    assert len(raws) == len(recs)
+    first = recs[:1024]
+    tag = "XG" if any("XG" in r.tags for r in first) else "YD" if any("YD" in r.tags for r in first) else \
+        "ZS" if any("ZS" in r.tags for r in first) else None
+    assert tag is not None
+    out, ncalled = bytearray(header), 0
+    for r, raw in zip(recs, raws):
+        if (r.flag & 4) or tag not in r.tags or "XM" in r.tags:
+            out += raw
+            continue
+        val = r.tags[tag][1]
+        extra = b""
+        if tag == "XG":
+            s_meth, s_conv = val[0], (val[1] if len(val) > 1 else 0)
+        else:
+            ga = val[:1] == (b"r" if tag == "YD" else b"-")
+            s_meth, s_conv = (ord("G"), ord("A")) if ga else (ord("C"), ord("T"))
+            extra = b"XGZ" + (b"GA" if ga else b"CT") + b"\0"
+        xm = call_xm(r, genome[names[r.tid]], s_meth, s_conv)
+        body = raw[4:] + extra + b"XMZ" + xm + b"\0"
+        out += struct.pack("<i", len(body)) + body
+        ncalled += 1
+    return bytes(out), len(recs), ncalled
+
+
+def inflate(path):
+    with gzip.open(path, "rb") as f:
+        return f.read()
+
+
+def assert_parity(in_path, out_path, genome_fa, res):
+    want, nrecs, ncalled = expected_output(in_path, read_fasta(genome_fa))
+    assert res == {"nrecs": nrecs, "ncalled": ncalled}
+    got = inflate(out_path)
+    assert len(got) == len(want)
+    assert got == want
+
+
+# ---- fixtures: known answers ----------------------------------------------------------------------------------------
+
+@pytest.fixture(scope="module")
+def genome():
+    return ea.preprocessGenome(FASTA, verbose=False)
+
+
+def _input(expr):
+    return expr.split('input.bam.file="')[1].split('"')[0]
+
+
+def _tagged(recs):
+    return "XM" if any("XM" in r.tags for r in recs[:1024]) else None
+
+
+@pytest.mark.parametrize("expr", sorted(EXPECTED["calls"]))
+def test_known_calls(expr, genome, tmp_path):
+    want = EXPECTED["calls"][expr]
+    src = os.path.join(BAMS, _input(expr))
+    out = str(tmp_path / "output.bam")
+    res = ea.callMethylation(src, out, genome, nthreads=1 if "nthreads=0" in expr else 2, verbose=False)
+    assert res == {"nrecs": want["nrecs"], "ncalled": want["ncalled"]}
+    _, recs = bamio.read_bam_records(out)
+    chk = bamio.check_bam(recs)
+    assert (chk["paired"], chk["sorted"], _tagged(recs)) == (want["paired"], want["sorted"], want["tagged"])
+    p = ea.preprocessBam(out)                                      # the output is a valid input of the report functions
+    assert p.n > 0
+    assert_parity(src, out, FASTA, res)
+
+
+@pytest.mark.parametrize("expr", sorted(EXPECTED["exceptions"]))
+def test_known_exceptions(expr, genome, tmp_path):
+    case = EXPECTED["exceptions"][expr]
+    src = os.path.join(BAMS, case["input"]) if case["input"] else ""
+    out = str(tmp_path / "output.bam") if case["output"] else ""
+    with pytest.raises(Exception):
+        ea.callMethylation(src, out, genome, nthreads=1, verbose=False)
+
+
+def test_exception_messages(genome, tmp_path):
+    out = str(tmp_path / "o.bam")
+    with pytest.raises(ValueError, match="Empty file provided"):
+        ea.callMethylation(os.path.join(BAMS, "empty.bam"), out, genome, verbose=False)
+    with pytest.raises(ValueError, match="neither of XG/YD/ZS tags is present"):
+        ea.callMethylation(os.path.join(BAMS, "bwameth-se-unsort.bam"), out, genome, verbose=False)
+    with pytest.raises(ValueError, match="doesn't match the provided genome"):
+        ea.callMethylation(os.path.join(BAMS, "amplicon000meth.bam"), out, genome, verbose=False)
+    with pytest.raises(ValueError, match="output BAM file for writing"):
+        ea.callMethylation(os.path.join(BAMS, "dragen-se-unsort-xg.bam"), "", genome, verbose=False)
+    assert not os.path.exists(out)                                  # a failed call leaves no partial file behind
+
+
+@pytest.mark.parametrize("expr", sorted(EXPECTED["cx_identical"]))
+def test_known_cx_comparisons(expr, genome, tmp_path):
+    case = EXPECTED["cx_identical"][expr]
+    out = str(tmp_path / "output.bam")
+    ea.callMethylation(os.path.join(BAMS, case["input"]), out, genome, nthreads=1, verbose=False)
+    ref = ea.generateCytosineReport(os.path.join(BAMS, case["ref"]), threshold_reads=False, report_context="CX")
+    call = ea.generateCytosineReport(out, threshold_reads=False, report_context="CX")
+    same = ref.nrow == call.nrow and set(ref) == set(call) and all(np.array_equal(np.asarray(ref[k]), np.asarray(call[k]))
+                                                                  for k in ref)
+    assert same == case["identical"]
+
+
+def test_genome_path_accepted(tmp_path):
+    out = str(tmp_path / "o.bam")
+    res = ea.callMethylation(os.path.join(BAMS, "bsmap-se-unsort-zs.bam"), out, FASTA, verbose=False)
+    assert res == {"nrecs": 100, "ncalled": 100}
+
+
+# ---- synthetic genome and BAMs --------------------------------------------------------------------------------------
+
+CONTIGS = (("chrA", 20000), ("chrB", 700), ("chrC", 64))
+
+
+def write_genome(path, rng):
+    """Lower case, N runs and IUPAC codes in the genome, wrapped at 60."""
+    seqs = {}
+    with open(path, "w") as f:
+        for name, ln in CONTIGS:
+            s = [rng.choice("ACGTACGTACGTacgtNRYKMSWn") for _ in range(ln)]
+            for k in range(0, ln, 97):                               # CpG-rich stretches so every context occurs
+                s[k:k + 4] = list("CGCG")[:max(0, min(4, ln - k))]
+            s = "".join(s[:ln])
+            seqs[name] = s
+            f.write(">%s some description\n" % name)
+            for i in range(0, ln, 60):
+                f.write(s[i:i + 60] + "\n")
+    return seqs
+
+
+def random_read(rng, contig_len, qlen_target, pos=None, end_gap=None, all_ops=True):
+    """(pos 1-based, cigar, seq) with the aligned span inside the contig."""
+    ops = []
+    q = 0
+    if all_ops and rng.random() < 0.5:
+        ops.append((5, rng.randint(1, 5)))                               # H
+    if rng.random() < 0.4:
+        ops.append((4, rng.randint(1, 6)))                               # S
+    while q < qlen_target:
+        op = rng.choice((0, 0, 0, 7, 8, 1, 2, 3, 6)) if all_ops else 0
+        ln = rng.randint(1, 40) if op in (0, 7) else rng.randint(1, 4)
+        if op == 3:
+            ln = rng.randint(1, 30)
+        ops.append((op, ln))
+        if op in (0, 1, 7, 8):
+            q += ln
+    if rng.random() < 0.4:
+        ops.append((4, rng.randint(1, 6)))
+    if all_ops and rng.random() < 0.3:
+        ops.append((5, rng.randint(1, 5)))
+    qlen = sum(ln for op, ln in ops if op in (0, 1, 4, 7, 8))
+    span = sum(ln for op, ln in ops if op in (0, 2, 3, 7, 8))
+    fixed = pos if pos is not None else end_gap if end_gap is not None else 0
+    if span + fixed > contig_len:
+        return random_read(rng, contig_len, max(1, qlen_target // 2), pos, end_gap, all_ops)
+    if pos is None:
+        pos = contig_len - span - end_gap if end_gap is not None else rng.randint(0, contig_len - span)
+    seq = "".join(rng.choice("ACGTACGTACGTN") for _ in range(qlen))
+    return pos + 1, ops, seq
+
+
+def synth_records(rng, tag, n, long_reads=False):
+    vals = {"XG": ("CT", "GA"), "YD": ("f", "r"), "ZS": ("++", "+-", "-+", "--")}[tag]
+    recs = []
+    for k in range(n):
+        tid = rng.randrange(len(CONTIGS))
+        clen = CONTIGS[tid][1]
+        pos = end_gap = None
+        if k % 17 == 0:
+            pos = k % 2                                                 # reads at contig positions 0 and 1
+        elif k % 17 == 1:
+            end_gap = (k // 17) % 2                                     # ... ending 0 or 1 base before the end
+        qlen = rng.randint(1, 60) if clen < 100 else rng.randint(20, 160)
+        p, cigar, seq = random_read(rng, clen, qlen, pos, end_gap)
+        r = {"seq": seq, "pos": p, "cigar": cigar, "tid": tid, "flag": rng.choice((0, 16, 99, 147, 83, 163)),
+             "qname": "r%06d" % k, "tags": {tag: vals[k % len(vals)], "NM": "0"}}
+        u = k % 23
+        if u == 5:
+            r["flag"] |= 4                                               # unmapped: written unchanged
+        elif u == 7:
+            r["tags"]["XM"] = "." * len(seq)                             # already called: unchanged
+        elif u == 11:
+            del r["tags"][tag]                                           # no strand tag: unchanged
+        recs.append(r)
+    if long_reads:
+        for k, ln in enumerate((1500, 10000, 10000)):
+            p, cigar, seq = random_read(rng, CONTIGS[0][1], ln, all_ops=(k != 2))
+            recs.append({"seq": seq, "pos": p, "cigar": cigar, "tid": 0, "qname": "long%d" % k,
+                         "tags": {tag: vals[k % len(vals)]}})
+    return recs
+
+
+@pytest.fixture(scope="module")
+def synth_genome(tmp_path_factory):
+    d = tmp_path_factory.mktemp("synth_genome")
+    rng = random.Random(20261015)
+    seqs = write_genome(str(d / "g.fa"), rng)
+    return str(d / "g.fa"), seqs, ea.preprocessGenome(str(d / "g.fa"), verbose=False)
+
+
+@pytest.mark.parametrize("tag", ["XG", "YD", "ZS"])
+def test_synthetic_parity(tag, synth_genome, tmp_path):
+    fa, seqs, g = synth_genome
+    rng = random.Random({"XG": 1, "YD": 2, "ZS": 3}[tag])
+    recs = synth_records(rng, tag, 1500, long_reads=True)
+    ops = {op for r in recs for op, _ in r["cigar"]}
+    assert ops >= {0, 1, 2, 3, 4, 5, 6, 7, 8}
+    src = write_bam(str(tmp_path / "in.bam"), recs, refs=CONTIGS)
+    out = str(tmp_path / "out.bam")
+    res = ea.callMethylation(src, out, g, nthreads=4, verbose=False)
+    assert_parity(src, out, fa, res)
+    assert 0 < res["ncalled"] < res["nrecs"]
+
+
+def test_synthetic_windows(synth_genome, tmp_path):
+    """A file much larger than the window: records cut by window seams, the first 1024 records gathered over several."""
+    fa, seqs, g = synth_genome
+    rng = random.Random(7)
+    recs = synth_records(rng, "ZS", 4000)
+    src = write_bam(str(tmp_path / "in.bam"), recs, refs=CONTIGS)
+    inflated = len(inflate(src))
+    window_kib = 64
+    assert inflated > 3 * window_kib * 1024
+    out = str(tmp_path / "out.bam")
+    res = ea.callMethylation(src, out, g, nthreads=3, verbose=False, window_kib=window_kib)
+    assert_parity(src, out, fa, res)
+    out1 = str(tmp_path / "out1.bam")
+    assert ea.callMethylation(src, out1, g, nthreads=1, verbose=False) == res
+    assert inflate(out1) == inflate(out)
+
+
+def test_output_is_bgzf(synth_genome, tmp_path):
+    fa, seqs, g = synth_genome
+    recs = synth_records(random.Random(11), "YD", 600)
+    src = write_bam(str(tmp_path / "in.bam"), recs, refs=CONTIGS)
+    out = str(tmp_path / "out.bam")
+    ea.callMethylation(src, out, g, nthreads=2, verbose=False)
+    data = open(out, "rb").read()
+    assert data[-28:] == bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
+    p = 0
+    while p < len(data):
+        assert data[p:p + 4] == b"\x1f\x8b\x08\x04" and data[p + 12:p + 14] == b"BC"
+        bsize = struct.unpack_from("<H", data, p + 16)[0] + 1
+        assert struct.unpack_from("<I", data, p + bsize - 4)[0] <= 0xff00
+        p += bsize
+    assert p == len(data)
+
+
+def test_read_past_contig_end_rejected(synth_genome, tmp_path):
+    fa, seqs, g = synth_genome
+    recs = [{"seq": "ACGT" * 5, "pos": 700 - 10 + 1, "tid": 1, "tags": {"XG": "CT"}}]       # 20 bases from 690 on a 700 bp contig
+    src = write_bam(str(tmp_path / "in.bam"), recs, refs=CONTIGS)
+    out = str(tmp_path / "out.bam")
+    with pytest.raises(ValueError, match="past the end"):
+        ea.callMethylation(src, out, g, verbose=False)
+
+
+def test_cigar_length_mismatch_rejected(synth_genome, tmp_path):
+    fa, seqs, g = synth_genome
+    recs = [{"seq": "ACGT" * 5, "pos": 10, "tid": 0, "cigar": [(0, 15)], "tags": {"YD": "f"}}]
+    src = write_bam(str(tmp_path / "in.bam"), recs, refs=CONTIGS)
+    with pytest.raises(ValueError, match="CIGAR does not match"):
+        ea.callMethylation(src, str(tmp_path / "out.bam"), g, verbose=False)
+
+
+def test_forced_tag(genome, tmp_path):
+    """rcpp_call_methylation_genome with the tag .callMethylation would choose gives the same file."""
+    src = os.path.join(BAMS, "bwameth-se-unsort-yd.bam")
+    a, b = str(tmp_path / "a.bam"), str(tmp_path / "b.bam")
+    ra = ea.callMethylation(src, a, genome, verbose=False)
+    rb = ea.rcpp_call_methylation_genome(src, b, genome, "YD", 1)
+    assert ra == rb and inflate(a) == inflate(b)
