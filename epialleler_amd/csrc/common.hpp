@@ -320,6 +320,8 @@ struct Options {
   int bam_timing = 0;        // EPIHIP_BAM_TIMING    phase times of the BAM reader and of callMethylation on stderr
   int no_hugepage = 0;       // EPIHIP_NO_HUGEPAGE   plain malloc for the BAM reader's large buffers (A/B runs)
   int no_libdeflate = 0;     // EPIHIP_NO_LIBDEFLATE zlib's inflate for the BGZF blocks although libdeflate.so.0 can be loaded
+  int64_t upload_piece = 0; // EPIHIP_UPLOAD_PIECE=<bytes>  piece size of the host-to-device copies of epi_batch_upload (0: by the
+                             //                      source; at most 64 MiB from pageable memory, the size of the pinned staging buffers)
 };
 const Options &options();
 

@@ -235,7 +235,9 @@ static bool is_pinned_host(const void *h_src) {
 }
 
 static int staged_upload(epi_engine *eng, void *d_dst, const void *h_src, size_t bytes) {
-  const size_t chunk = 64u << 20;
+  const size_t stage = 64u << 20;                          // the pinned staging buffers
+  size_t chunk = stage;
+  if (options().upload_piece > 0 && (size_t)options().upload_piece < stage) chunk = (size_t)options().upload_piece;   // EPIHIP_UPLOAD_PIECE
   if (bytes && is_pinned_host(h_src)) {
     // pinned source (what the producer hands over): no staging copy, hipMemcpyAsync straight from the caller's buffer
     EPI_HIP(hipMemcpyAsync(d_dst, h_src, bytes, hipMemcpyHostToDevice, eng->copy_stream));
@@ -243,10 +245,10 @@ static int staged_upload(epi_engine *eng, void *d_dst, const void *h_src, size_t
   }
   if (!eng->pinned[0]) {
     for (int i = 0; i < 2; i++) {
-      EPI_HIP(hipHostMalloc(&eng->pinned[i], chunk, hipHostMallocDefault));
+      EPI_HIP(hipHostMalloc(&eng->pinned[i], stage, hipHostMallocDefault));
       EPI_HIP(hipEventCreateWithFlags(&eng->pinned_done[i], hipEventDisableTiming));
     }
-    eng->pinned_bytes = chunk;
+    eng->pinned_bytes = stage;
   }
   for (int i = 0; i < 2; i++) EPI_HIP(hipEventSynchronize(eng->pinned_done[i]));   // (a device-to-host copy may have used them)
   size_t done = 0;
@@ -277,6 +279,10 @@ static int upload_rows_congruent(epi_engine *eng, const uint8_t *h_xm, const int
     chunk = ((size_t)nbytes / 8 + ((1u << 20) - 1)) & ~(size_t)((1u << 20) - 1);
     if (chunk < (16u << 20)) chunk = 16u << 20;
     if (chunk > (256u << 20)) chunk = 256u << 20;
+  }
+  if (options().upload_piece > 0) {                        // EPIHIP_UPLOAD_PIECE (test hook): pieces of that size
+    chunk = (size_t)options().upload_piece;
+    if (!pinned_src && chunk > (64u << 20)) chunk = 64u << 20;
   }
   if (eng->dev_stage_bytes < chunk) {
     for (int i = 0; i < 2; i++) {

@@ -64,6 +64,8 @@ static void read_options() {
   o.bam_timing = getenv("EPIHIP_BAM_TIMING") != nullptr;
   o.no_libdeflate = getenv("EPIHIP_NO_LIBDEFLATE") != nullptr;
   o.no_hugepage = getenv("EPIHIP_NO_HUGEPAGE") != nullptr;
+  if (const char *e = getenv("EPIHIP_UPLOAD_PIECE")) o.upload_piece = strtoll(e, nullptr, 10);
+  if (o.upload_piece < 0) o.upload_piece = 0;
   g_options = o;
 }
 

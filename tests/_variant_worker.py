@@ -32,6 +32,7 @@ def main():
     sets.append(synth_np.random_templates(rng, 5000, 0, 305, 2, 120000))
     sets.append(synth_np.random_templates(rng, 6000, 100, 300, 1, 40))
     sets.append(synth_np.generate_uniform(n_total=12000, mean_len=300, n_chr=2, ragged=False, gap_every=0, pileup=(3000, 900)))
+    sets.append(H.tie_batch())                                          # n_m / n_all and o_m / o_all on, below and above the thresholds
     for t in sets:
         bam = ea.ProcessedBam.from_arrays(t["xm"], t["off"], t["rname"], t["strand"], t["start"], t.get("levels"))
         try:
@@ -41,11 +42,14 @@ def main():
                 got = ea.rcpp_cx_report(bam, pv, ctx)
                 want = orc.cx_report(t["xm"], t["off"], t["rname"], t["strand"], t["start"], pv, ctx)
                 H.assert_reports_equal(dict(got), want)
-            for ctx in ("Z", "ZXH"):                                      # thresholding fused into the tile kernel
-                got, gp = ea.cytosine_report_fused(bam, c["ctx_meth"], c["ctx_unmeth"], c["ooctx_meth"], c["ooctx_unmeth"], 2, 0.5, 0.1,
-                                                   ctx, return_pass=True)
-                assert np.array_equal(gp.astype(np.int32), p)
-                H.assert_reports_equal(dict(got), orc.cx_report(t["xm"], t["off"], t["rname"], t["strand"], t["start"], p, ctx))
+            for mn, mb, mo in ((2, 0.5, 0.1), (3, 1 / 3, 0.0)):          # the default table and another one
+                pt = p if (mn, mb, mo) == (2, 0.5, 0.1) else orc.threshold_reads(t["xm"], t["off"], c["ctx_meth"], c["ctx_unmeth"],
+                                                                                  c["ooctx_meth"], c["ooctx_unmeth"], mn, mb, mo)
+                for ctx in ("Z", "ZXH"):                                  # thresholding fused into the tile kernel
+                    got, gp = ea.cytosine_report_fused(bam, c["ctx_meth"], c["ctx_unmeth"], c["ooctx_meth"], c["ooctx_unmeth"], mn, mb, mo,
+                                                       ctx, return_pass=True)
+                    assert np.array_equal(gp.astype(np.int32), pt), (mn, mb, mo, ctx)
+                    H.assert_reports_equal(dict(got), orc.cx_report(t["xm"], t["off"], t["rname"], t["strand"], t["start"], pt, ctx))
             for hmax, hmin, moo in ((0, 0, 0.1), (3, 2, 1.0)):
                 got = ea.rcpp_mhl_report(bam, "Zz", hmax, hmin, moo)
                 want = orc.mhl_report(t["xm"], t["off"], t["rname"], t["strand"], t["start"], "Zz", hmax, hmin, moo)

@@ -176,3 +176,103 @@ def dirty_allocator(bam):
     import torch
     junk = torch.full((max(bam.n, 1),), 0x5A5A5A5A, dtype=torch.int32, device="cuda:%d" % (bam.device or 0))
     del junk
+
+
+# ---- plain restatements of the per-read decisions (numpy, float64), independent of the oracle and of the kernels -------
+
+def class_counts(xm, off, letters):
+    """Per row: sum over the letters of a class string of the count of that letter's context index in the row (a repeated
+    letter counts twice, as in rcpp_threshold_reads.cpp:39-47)."""
+    xm = np.asarray(xm, np.uint8)
+    off = np.asarray(off, np.int64)
+    n = off.size - 1
+    lens = np.diff(off)
+    row = np.repeat(np.arange(n, dtype=np.int64), lens)
+    hist = np.bincount(row * 16 + (xm[:int(off[-1])] & 15), minlength=16 * n).reshape(n, 16).astype(np.int64)
+    out = np.zeros(n, np.int64)
+    for ch in letters:
+        out += hist[:, ctx_to_idx(ch)]
+    return out
+
+
+def threshold_np(xm, off, cls4, min_n, min_beta, max_oo):
+    """rcpp_threshold_reads.cpp:43-70: a read passes when it has a methylated context base, at least min_n context bases
+    (unsigned compare), !(n_m / n_all < min_beta), and no out-of-context base or !(o_m / o_all > max_oo) -- divisions and
+    comparisons in float64, so NaN thresholds compare false as they do there.  cls4 = (ctx_meth, ctx_unmeth, ooctx_meth,
+    ooctx_unmeth)."""
+    n_m, n_u, o_m, o_u = (class_counts(xm, off, c) for c in cls4)
+    n_all = n_m + n_u
+    with np.errstate(invalid="ignore", divide="ignore"):
+        frac = n_m.astype(np.float64) / n_all.astype(np.float64)
+        ofrac = o_m.astype(np.float64) / (o_m + o_u).astype(np.float64)
+    ok = (n_m != 0) & ~(n_all < (int(min_n) & 0xFFFFFFFF)) & ~(frac < np.float64(min_beta))
+    ok &= ~((o_m > 0) & (ofrac > np.float64(max_oo)))
+    return ok.astype(np.int32)
+
+
+def mhl_keep_np(xm, off, ctx, hmin, max_oo):
+    """The read filter of rcpp_mhl_report.cpp:160-179: h = the read's bases whose context index is one of ctx's letters;
+    out-of-context methylated codes 2,5,6,7 and unmethylated 10,13,14,15 (only those not in ctx);
+    keep = !((int)h < hmin || o_m / (o_m + o_u) > max_oo), with 0 / 0 = NaN (kept)."""
+    xm = np.asarray(xm, np.uint8)
+    off = np.asarray(off, np.int64)
+    n = off.size - 1
+    row = np.repeat(np.arange(n, dtype=np.int64), np.diff(off))
+    hist = np.bincount(row * 16 + (xm[:int(off[-1])] & 15), minlength=16 * n).reshape(n, 16).astype(np.int64)
+    in_ctx = np.zeros(16, bool)
+    in_ctx[[ctx_to_idx(c) for c in ctx]] = True
+    h = hist[:, in_ctx].sum(axis=1)
+    o_m = hist[:, [i for i in (2, 5, 6, 7) if not in_ctx[i]]].sum(axis=1)
+    o_u = hist[:, [i for i in (10, 13, 14, 15) if not in_ctx[i]]].sum(axis=1)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        frac = o_m.astype(np.float64) / (o_m + o_u).astype(np.float64)
+    return ~((h < int(hmin)) | (frac > np.float64(max_oo)))
+
+
+def subset(t, keep):
+    """The templates of t whose keep flag is set (same order)."""
+    keep = np.asarray(keep, bool)
+    lens = np.diff(t["off"])
+    out = {k: t[k][keep] for k in ("rname", "strand", "start")}
+    out["xm"] = t["xm"][:int(t["off"][-1])][np.repeat(keep, lens)]
+    out["off"] = np.concatenate(([0], np.cumsum(lens[keep]))).astype(np.int64)
+    return out
+
+
+# (n_m, n_all) and (o_m, o_all) exactly at the thresholds the tests use, one call below and one above: 3/10 at 0.3,
+# 1/3 at 1/3, 9/10 at 0.9, 1/2 at 0.5, 1/10 at 0.1, all at 1.0 and none at 0.0
+TIE_FRACS = ((3, 10), (6, 20), (1, 3), (5, 15), (33, 99), (9, 10), (27, 30), (1, 2), (5, 10), (1, 1), (4, 4), (1, 10), (3, 30), (7, 70))
+
+
+def tie_batch(seed=0):
+    """Templates whose context / out-of-context fractions sit exactly on, one call below and one call above the threshold
+    values of the test grids, under CG (Z/z, out of context X,H/x,h) and under CHG (X/x, out of context Z,H/z,h)
+    thresholding; with n_m = 0 < n_u, o_m = 0 < o_u, n_all = 2 and 3, rows without calls and empty rows."""
+    rng = np.random.default_rng(seed)
+    npat = {(0, 0), (0, 3), (1, 2), (2, 2), (0, 2), (2, 3), (1, 3)}
+    for m, a in TIE_FRACS:
+        npat.update({(m, a), (max(m - 1, 0), a), (min(m + 1, a), a)})
+    opat = {(0, 0), (0, 5), (1, 1), (1, 10), (0, 10), (2, 10), (3, 30), (2, 30), (4, 30), (7, 70), (6, 70), (8, 70), (5, 5)}
+    xms = []
+    for meth, unmeth, om, ou in (("Z", "z", "X", "x"), ("X", "x", "Z", "z")):
+        for nm, na in sorted(npat):
+            for o_m, o_a in sorted(opat):
+                s = list(meth * nm + unmeth * (na - nm) + om * o_m + ou * (o_a - o_m) + "." * int(rng.integers(0, 12)))
+                rng.shuffle(s)
+                xms.append("".join(s))
+    xms += ["", "....", "", "-.+", ""]
+    n = len(xms)
+    order = rng.permutation(n)
+    xms = [xms[i] for i in order]
+    return templates_from_xm(xms, [int(v) for v in rng.integers(1, 30000, n)], [int(v) for v in rng.integers(1, 3, n)],
+                             rnames=[int(v) for v in rng.integers(1, 3, n)])
+
+
+# (min_n, min_beta, max_oo) at ties, limits and odd values: NaN, negative, above 1, -0.0, min_n above every count
+THRESHOLD_GRID = ((0, 0.0, 1.0), (1, 0.3, 0.0), (3, 1.0, 0.1), (2, 1 / 3, 0.1), (5, 0.9, 0.0), (2, float("nan"), float("nan")),
+                  (2, -0.5, 1.5), (70000, 0.5, 0.1), (2, -0.0, -0.0))
+
+
+def cls4(ctx):
+    c = CONTEXT_TO_BASES[ctx]
+    return c["ctx_meth"], c["ctx_unmeth"], c["ooctx_meth"], c["ooctx_unmeth"]

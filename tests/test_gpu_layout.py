@@ -39,17 +39,21 @@ def _view(ea, bam):
 
 
 def _check_layout(t, xm, off, ln, modulus):
-    n = len(t["start"])
+    """The layout rules, and the whole arena byte for byte against one built here from the source rows at the device's
+    offsets with filler (0xFB) everywhere else.  modulus 0: rows back to back, the arena is the source."""
     want_len = np.diff(t["off"]).astype(np.int32)
     assert np.array_equal(ln, want_len)
-    assert np.all(off[:-1] % modulus == t["start"].astype(np.int64) % modulus)
-    assert np.all(off[:-1] + ln <= off[1:]) and np.all(off[1:] - off[:-1] - ln < modulus)
-    for x in list(range(min(n, 50))) + list(range(max(n - 50, 0), n)) + list(range(0, n, max(n // 200, 1))):
-        assert np.array_equal(xm[off[x]:off[x] + ln[x]], t["xm"][t["off"][x]:t["off"][x + 1]]), x
-    fill = np.ones(len(xm), dtype=bool)                       # everything that is not a row is filler
-    for x in range(n):
-        fill[off[x]:off[x] + ln[x]] = False
-    assert np.all(xm[fill] == 0xFB)
+    if modulus:
+        assert np.all(off[:-1] % modulus == t["start"].astype(np.int64) % modulus)
+        assert np.all(off[:-1] + ln <= off[1:]) and np.all(off[1:] - off[:-1] - ln < modulus)
+    else:
+        assert np.array_equal(off, t["off"])
+    nsrc = int(t["off"][-1])
+    want = np.full(len(xm), 0xFB, np.uint8)
+    want[np.repeat(off[:-1] - t["off"][:-1], want_len) + np.arange(nsrc, dtype=np.int64)] = t["xm"][:nsrc]
+    if not np.array_equal(xm, want):
+        bad = np.flatnonzero(xm != want)
+        raise AssertionError("%d arena bytes differ, first at %d (row %d)" % (bad.size, bad[0], np.searchsorted(off, bad[0], "right") - 1))
 
 
 @pytest.mark.parametrize("case", ["ragged", "tiny", "long", "empty_rows"])
