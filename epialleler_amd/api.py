@@ -81,6 +81,7 @@ class ProcessedBam:
         self._batch = None
         self.realign = True     # adopted device columns: let the engine lay the rows out its own way (from_device)
         self._keep = None       # owner of the host buffers the numpy columns are views of (producer output, pinned tensors)
+        self.ncalled = 0        # records called on the way in (preprocessBam(genome=))
 
     @classmethod
     def from_arrays(cls, xm, off, rname, strand, start, levels=None, keepalive=None, device=None):
@@ -189,21 +190,40 @@ def _as_bam(bam):
 
 def preprocessBam(bam_file, paired=None, min_mapq=0, min_baseq=0, min_prob=-1, highest_prob=True,
                   skip_duplicates=False, skip_secondary=True, skip_qcfail=True, skip_supplementary=True,
-                  trim=0, nthreads=1, verbose=False, window_kib=0):
+                  trim=0, nthreads=1, verbose=False, window_kib=0, genome=None):
     """R/preprocessBam.R:197-237.  An already preprocessed object is returned untouched (:226-235);
     a path is decoded by the library's host-side producer (epi_preprocess_bam: zlib BGZF reader + the
-    reference's template packer), which yields the sorted SoA batch directly."""
+    reference's template packer), which yields the sorted SoA batch directly.
+
+    genome: a FASTA path or a Genome (preprocessGenome).  The records callMethylation would call (mapped, carrying the
+    strand tag, no XM) are called on the GPU inside the reader (epi_preprocess_bam_genome): the result equals
+    preprocessBam(callMethylation(bam_file, tmp, genome); tmp) with the same options, errors included, and no BAM is
+    written.  `ncalled` on the result counts the called records (0 without a genome).  There is no CPU path: without
+    a device this raises EpihipError."""
     if isinstance(bam_file, (ProcessedBam, dict)):
         return _as_bam(bam_file)
     import os
     lib = _lib.load()
+    eng = None
+    if genome is not None:
+        from .genome import preprocessGenome
+        genome = preprocessGenome(genome, nthreads=nthreads, verbose=verbose)
+        eng = C.c_void_p()
+        _lib.check(lib.epi_default_engine(C.byref(eng)))          # no device: EpihipError (as rcpp_call_methylation_genome)
     trim2 = (list(np.atleast_1d(trim)) * 2)[:2]                       # head(rep.int(trim, 2), 2)
     opt = _lib.BamOptions(int(min_mapq), int(min_baseq), int(bool(skip_duplicates)), int(bool(skip_secondary)),
                           int(bool(skip_qcfail)), int(bool(skip_supplementary)), int(trim2[0]), int(trim2[1]),
                           -1 if paired is None else int(bool(paired)), max(int(nthreads), 1), int(min_prob),
                           int(bool(highest_prob)), int(window_kib))
     t = _lib.Templates()
-    rc = lib.epi_preprocess_bam(os.path.expanduser(str(bam_file)).encode(), C.byref(opt), C.byref(t))
+    ncalled = C.c_int64(0)
+    path = os.path.expanduser(str(bam_file)).encode()
+    if genome is None:
+        rc = lib.epi_preprocess_bam(path, C.byref(opt), C.byref(t))
+    else:
+        rc = lib.epi_preprocess_bam_genome(eng, path, C.byref(opt), genome._h, C.byref(t), C.byref(ncalled))
+    if genome is not None and rc not in (_lib.EPI_OK, _lib.EPI_ERR_ARG):
+        _lib.check(rc)                                                # device / HIP failures: EpihipError
     if rc != _lib.EPI_OK:
         msg = lib.epi_last_error().decode("utf-8", "replace")
         raise ValueError(msg)                                         # stop(..., call.=FALSE) in the reference
@@ -224,6 +244,7 @@ def preprocessBam(bam_file, paired=None, min_mapq=0, min_baseq=0, min_prob=-1, h
     bam = ProcessedBam.from_arrays(view(t.xm, t.nbytes), view(t.off, n + 1), view(t.rname, n), view(t.strand, n),
                                    view(t.start, n), levels, keepalive=keep)
     bam.nrecs, bam.npushed, bam.paired, bam.pinned = int(t.nrecs), int(n), bool(t.paired), bool(t.pinned)
+    bam.ncalled = int(ncalled.value)
     return bam
 
 

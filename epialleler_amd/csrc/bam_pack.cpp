@@ -450,14 +450,15 @@ void epi_templates_free(epi_templates *t) {
   memset(t, 0, sizeof(*t));
 }
 
-static int preprocess_impl(const char *path, const epi_bam_options *opt_in, epi_templates *out);
+static int preprocess_impl(const char *path, const epi_bam_options *opt_in, epi_templates *out, epi_engine *eng,
+                           epi_genome *genome, int64_t *ncalled_out);
 
 int epi_preprocess_bam(const char *path, const epi_bam_options *opt_in, epi_templates *out) {
   if (!path || !out) return fail(EPI_ERR_ARG, "epi_preprocess_bam: NULL argument");
   memset(out, 0, sizeof(*out));
   int rc;
   try {                                                     // nothing may unwind through the C boundary
-    rc = preprocess_impl(path, opt_in, out);
+    rc = preprocess_impl(path, opt_in, out, nullptr, nullptr, nullptr);
   } catch (const std::bad_alloc &) {
     rc = fail(EPI_ERR_NOMEM, "epi_preprocess_bam: out of host memory");
   } catch (...) {
@@ -465,6 +466,29 @@ int epi_preprocess_bam(const char *path, const epi_bam_options *opt_in, epi_temp
   }
   if (rc != EPI_OK) epi_templates_free(out);
   return rc;
+}
+
+int epi_preprocess_bam_genome(epi_engine *eng, const char *path, const epi_bam_options *opt_in, epi_genome *g,
+                              epi_templates *out, int64_t *ncalled) {
+  if (!path || !out || !g || !ncalled) return fail(EPI_ERR_ARG, "epi_preprocess_bam_genome: NULL argument");
+  memset(out, 0, sizeof(*out));
+  *ncalled = 0;
+#ifdef EPI_HOST_ONLY
+  (void)eng; (void)opt_in;
+  return fail(EPI_ERR_NODEVICE, "epi_preprocess_bam_genome: the calls are made on the GPU; this build has no device code");
+#else
+  if (!eng) EPI_TRY(epi_default_engine(&eng));               // no device: fails here, before the file is read
+  int rc;
+  try {
+    rc = preprocess_impl(path, opt_in, out, eng, g, ncalled);
+  } catch (const std::bad_alloc &) {
+    rc = fail(EPI_ERR_NOMEM, "epi_preprocess_bam: out of host memory");
+  } catch (...) {
+    rc = fail(EPI_ERR_ARG, "epi_preprocess_bam: unexpected failure while reading %s", path);
+  }
+  if (rc != EPI_OK) { epi_templates_free(out); *ncalled = 0; }
+  return rc;
+#endif
 }
 
 }  // extern "C"
@@ -501,7 +525,215 @@ static uint64_t cigar_qlen(const Rec &r) {
   return q;
 }
 
-static int preprocess_impl(const char *path, const epi_bam_options *opt_in, epi_templates *out) {
+// ---- callMethylation's call set (rcpp_call_methylation_genome, src/rcpp_call_methylation.cpp:27-177, with
+// .callMethylation's tag choice, R/internal.R:405-432): which records are called and what the GPU needs for them.
+// Shared by callMethylation (BAM out, call_impl below) and preprocessBam with a genome (preprocess_impl), so that the
+// second sees exactly the records, strand letters and errors the first would have produced. ----------------------
+namespace {
+
+// bam_aux_get: the tag's type byte, or NULL when the record has no such tag (or its aux data is malformed before it)
+const uint8_t *aux_find(const Rec &r, char a, char b) {
+  const uint8_t *p = r.aux;
+  while (p + 3 <= r.end) {
+    const bool hit = (char)p[0] == a && (char)p[1] == b;
+    const char ty = (char)p[2];
+    if (hit) return p + 2;
+    p += 3;
+    switch (ty) {
+      case 'A': case 'c': case 'C': p += 1; break;
+      case 's': case 'S': p += 2; break;
+      case 'i': case 'I': case 'f': p += 4; break;
+      case 'Z': case 'H': {
+        const uint8_t *e = (const uint8_t *)memchr(p, 0, (size_t)(r.end - p));
+        if (!e) return nullptr;
+        p = e + 1;
+        break;
+      }
+      case 'B': {
+        if (p + 5 > r.end) return nullptr;
+        const char st = (char)p[0];
+        const size_t es = (st == 'c' || st == 'C') ? 1 : (st == 's' || st == 'S') ? 2 : 4;
+        p += 5 + (size_t)rd32(p + 1) * es;
+        break;
+      }
+      default: return nullptr;
+    }
+  }
+  return nullptr;
+}
+
+enum StrandTag { TAG_XG = 0, TAG_YD = 1, TAG_ZS = 2 };
+
+// runs f(lo, hi) over K ranges of [0, n) on K threads (one thread below 4096 items); the first range's error wins
+template <class F>
+int parallel_ranges(size_t K, size_t n, const char *who, F &&f) {
+  const size_t k = n < 4096 ? 1 : K;
+  std::vector<int> rcs(k, EPI_OK);
+  std::vector<std::string> msgs(k);
+  auto run = [&](size_t t) {
+    try {
+      rcs[t] = f(n * t / k, n * (t + 1) / k);
+    } catch (const std::bad_alloc &) {
+      rcs[t] = fail(EPI_ERR_NOMEM, "%s: out of host memory", who);
+    }
+    if (rcs[t] != EPI_OK) msgs[t] = epi_last_error();
+  };
+  std::vector<std::thread> th;
+  for (size_t t = 1; t < k; t++) th.emplace_back(run, t);
+  run(0);
+  for (auto &t : th) t.join();
+  for (size_t t = 0; t < k; t++)
+    if (rcs[t] != EPI_OK) return fail(rcs[t], "%s", msgs[t].c_str());
+  return EPI_OK;
+}
+
+// .callMethylation (R/internal.R:412-423): the strand tag from the first 1024 records; force_tag ("XG" / "YD" / "ZS")
+// skips the look (rcpp_call_methylation_genome's own contract)
+int call_choose_tag(const Rec *recs, size_t nrec, const char *force_tag, StrandTag *tag) {
+  bool tXG = false, tYD = false, tZS = false;
+  for (size_t i = 0; i < nrec && i < 1024; i++) {
+    tXG |= aux_find(recs[i], 'X', 'G') != nullptr;
+    tYD |= aux_find(recs[i], 'Y', 'D') != nullptr;
+    tZS |= aux_find(recs[i], 'Z', 'S') != nullptr;
+  }
+  if (force_tag) *tag = strcmp(force_tag, "XG") == 0 ? TAG_XG : strcmp(force_tag, "YD") == 0 ? TAG_YD : TAG_ZS;
+  else if (nrec == 0) return fail(EPI_ERR_ARG, "Empty file provided! Exiting");
+  else if (tXG) *tag = TAG_XG;
+  else if (tYD) *tag = TAG_YD;
+  else if (tZS) *tag = TAG_ZS;
+  else return fail(EPI_ERR_ARG, "Unable to call methylation: neither of XG/YD/ZS tags is present (genome strand unknown).\nExiting");
+  return EPI_OK;
+}
+
+// the header's reference sequences must be the genome's, by name and length (src/rcpp_call_methylation.cpp:41-72)
+int call_check_genome(epi_genome *g, const std::vector<std::string> &names, const std::vector<int64_t> &lens) {
+  const int32_t ng = epi_genome_count(g);
+  for (size_t i = 0; i < names.size(); i++)
+    if ((int32_t)i >= ng || epi_genome_length(g, (int32_t)i) != lens[i] || names[i] != epi_genome_name(g, (int32_t)i))
+      return fail(EPI_ERR_ARG, "BAM reference sequence doesn't match the provided genome sequence");
+  return EPI_OK;
+}
+
+struct CallSet {                      // the records of one window to call
+  std::vector<uint8_t> call;          // per record: 1 = call it
+  std::vector<uint8_t> s_meth, s_conv;
+  std::vector<int64_t> call_idx;      // per called record of the packed range: its index among the called ones
+  std::vector<CallRec> crec;
+  std::vector<uint32_t> cigar;
+  std::vector<uint8_t> seq;
+  std::vector<uint8_t> xm;            // the GPU's output: l_seq bytes per called record, at its xm_off
+  int64_t ncig = 0, nseq = 0, nxm = 0;
+};
+
+// Which of recs[0, n) are called (mapped, carrying the strand tag, no XM: :84-89), their strand letters (the tag's first
+// two characters, or the strand YD / ZS names: :92-97), and the checks that keep every access in bounds (DESIGN.md
+// section 2: the reference reads out of bounds here).  A called record grows by the XG tag (YD / ZS input) and XM.
+int call_select(const Rec *recs, size_t n, StrandTag tag, const std::vector<std::string> &names,
+                const std::vector<int64_t> &lens, size_t K, const char *who, CallSet &S) {
+  const char t0 = tag == TAG_XG ? 'X' : tag == TAG_YD ? 'Y' : 'Z', t1 = tag == TAG_XG ? 'G' : tag == TAG_YD ? 'D' : 'S';
+  S.call.resize(n); S.s_meth.resize(n); S.s_conv.resize(n);
+  return parallel_ranges(K, n, who, [&](size_t lo, size_t hi) -> int {
+    for (size_t i = lo; i < hi; i++) {
+      const Rec &r = recs[i];
+      S.call[i] = 0;
+      const uint8_t *st = aux_find(r, t0, t1);
+      if ((r.flag & 4) || !st || aux_find(r, 'X', 'M')) continue;          // written unchanged
+      // the strand tag's first two characters (bam_aux_get's pointer [1] and [2])
+      const uint8_t c1 = st + 1 < r.end ? st[1] : 0, c2 = st + 2 < r.end ? st[2] : 0;
+      if (tag == TAG_XG) { S.s_meth[i] = c1; S.s_conv[i] = c2; }
+      else {
+        const bool ga = tag == TAG_YD ? c1 == 'r' : c1 == '-';
+        S.s_meth[i] = ga ? 'G' : 'C'; S.s_conv[i] = ga ? 'A' : 'T';
+      }
+      if (r.tid < 0 || (size_t)r.tid >= names.size()) return fail(EPI_ERR_ARG, "corrupt BAM record %s: reference id out of range", r.qname);
+      if (r.pos < 0) return fail(EPI_ERR_ARG, "corrupt BAM record %s: position out of range", r.qname);
+      uint64_t qlen = 0, rlen = 0;
+      for (uint32_t k = 0; k < r.n_cigar; k++) {
+        const uint32_t c = rd32(r.cigar + 4 * k), op = c & 0xF, len = c >> 4;
+        if (op > 9) return fail(EPI_ERR_ARG, "Unknown CIGAR operation for BAM entry %s", r.qname);
+        if (op == 0 || op == 1 || op == 4 || op == 7 || op == 8) qlen += len;
+        if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) rlen += len;
+      }
+      if (qlen != (uint64_t)r.l_seq) return fail(EPI_ERR_ARG, "corrupt BAM record %s: CIGAR does not match the sequence length", r.qname);
+      if ((uint64_t)r.pos + rlen > (uint64_t)lens[(size_t)r.tid])
+        return fail(EPI_ERR_ARG, "corrupt BAM record %s: alignment runs past the end of reference sequence %s", r.qname, names[(size_t)r.tid].c_str());
+      const uint64_t bs = (uint64_t)(r.end - (const uint8_t *)r.qname) + 32;   // block_size (the name follows 32 fixed bytes)
+      if (bs + (tag == TAG_XG ? 0 : 6) + 4 + (uint64_t)r.l_seq > 0x7FFFFFFFull)
+        return fail(EPI_ERR_ARG, "corrupt BAM record %s: record too large", r.qname);
+      S.call[i] = 1;
+    }
+    return EPI_OK;
+  });
+}
+
+// the CallRec, CIGAR and SEQ inputs of the called records among recs[0, n) (n: at most call_select's range)
+int call_pack_inputs(const Rec *recs, size_t n, size_t K, const char *who, CallSet &S) {
+  S.call_idx.resize(n);
+  S.crec.clear();
+  int64_t ncig = 0, nseq = 0, nxm = 0;
+  for (size_t i = 0; i < n; i++) {
+    if (!S.call[i]) continue;
+    const Rec &r = recs[i];
+    CallRec c;
+    memset(&c, 0, sizeof(c));
+    c.cig_off = ncig; c.seq_off = nseq; c.xm_off = nxm;
+    c.tid = r.tid; c.pos = r.pos; c.l_seq = r.l_seq; c.n_cig = (int32_t)r.n_cigar;
+    c.s_meth = S.s_meth[i]; c.s_conv = S.s_conv[i];
+    S.call_idx[i] = (int64_t)S.crec.size();
+    S.crec.push_back(c);
+    ncig += r.n_cigar; nseq += ((int64_t)r.l_seq + 1) / 2; nxm += r.l_seq;
+  }
+  S.ncig = ncig; S.nseq = nseq; S.nxm = nxm;
+  S.cigar.resize((size_t)ncig); S.seq.resize((size_t)nseq); S.xm.resize((size_t)nxm);
+  return parallel_ranges(K, n, who, [&](size_t lo, size_t hi) -> int {
+    for (size_t i = lo; i < hi; i++) {
+      if (!S.call[i]) continue;
+      const Rec &r = recs[i];
+      const CallRec &c = S.crec[(size_t)S.call_idx[i]];
+      if (r.n_cigar) memcpy(S.cigar.data() + c.cig_off, r.cigar, 4 * (size_t)r.n_cigar);
+      if (r.l_seq) memcpy(S.seq.data() + c.seq_off, r.seq, ((size_t)r.l_seq + 1) / 2);
+    }
+    return EPI_OK;
+  });
+}
+
+// whether a walk over the record's aux fields (as aux_z makes it) ends exactly at the record's end: tags appended to
+// the record are then found by a later walk, otherwise they lie beyond a malformed field and are not
+bool aux_clean(const Rec &r) {
+  const uint8_t *p = r.aux;
+  while (p + 3 <= r.end) {
+    const char ty = (char)p[2];
+    p += 3;
+    switch (ty) {
+      case 'A': case 'c': case 'C': p += 1; break;
+      case 's': case 'S': p += 2; break;
+      case 'i': case 'I': case 'f': p += 4; break;
+      case 'Z': case 'H': {
+        const uint8_t *e = (const uint8_t *)memchr(p, 0, (size_t)(r.end - p));
+        if (!e) return false;
+        p = e + 1;
+        break;
+      }
+      case 'B': {
+        if (p + 5 > r.end) return false;
+        const char st = (char)p[0];
+        const size_t es = (st == 'c' || st == 'C') ? 1 : (st == 's' || st == 'S') ? 2 : 4;
+        p += 5 + (size_t)rd32(p + 1) * es;
+        break;
+      }
+      default: return false;
+    }
+  }
+  return p == r.end;
+}
+
+}  // namespace
+
+// genome != NULL (epi_preprocess_bam_genome): the records callMethylation would call are called on the GPU, window by
+// window, into packed template bytes, and the packers read them in place of XG / XM -- the result is that of
+// preprocessBam(callMethylation(path)) without the BAM in between.
+static int preprocess_impl(const char *path, const epi_bam_options *opt_in, epi_templates *out, epi_engine *eng,
+                           epi_genome *genome, int64_t *ncalled_out) {
   epi_bam_options opt;
   if (opt_in) opt = *opt_in;
   else { memset(&opt, 0, sizeof(opt)); opt.skip_secondary = opt.skip_qcfail = opt.skip_supplementary = 1; opt.paired = -1; opt.nthreads = 1; opt.min_prob = -1; opt.highest_prob = 1; }
@@ -603,6 +835,16 @@ static int preprocess_impl(const char *path, const epi_bam_options *opt_in, epi_
   size_t carry = 0, bi = 0, hdr_end = 0;
   bool header_done = false, checked = false, paired = false, tMM = false;
   std::vector<std::string> names;
+  std::vector<int64_t> lens;                                // reference lengths (the genome check)
+  // with a genome, the header messages are callMethylation's: it reads the file first
+  const char *hdr_msg = genome ? "Unable to read input BAM header" : "Unable to read BAM header";
+  StrandTag tag = TAG_XG;
+  CallSet CS;                                               // with a genome: the window's records to call
+  int64_t ncalled = 0;
+  double t_call = 0;
+#ifndef EPI_HOST_ONLY
+  CallWork wk;
+#endif
   struct RecBuf {                                           // the window's records (not value-initialised: 80 bytes x millions)
     Rec *p = nullptr;
     size_t n = 0, cap = 0;
@@ -637,6 +879,24 @@ static int preprocess_impl(const char *path, const epi_bam_options *opt_in, epi_
   // a record that enters a template must be self-consistent: the CIGAR consumes exactly the stored bases, XM covers
   // them, the reference id exists (HTSlib rejects such records while reading; without the checks they index past
   // the record)
+  // XG's first letter and the XM bytes of record ri, as the packers see them: from its own tags, or -- a record called on
+  // the way in (genome) -- as callMethylation would have written it: its own XG, else the appended one (s_meth), and the
+  // appended XM, here the packed bytes the GPU made (*pcall).  false: not usable (no XG / XM string).
+  auto xg_xm = [&](size_t ri, const Rec &r, char *s, const char **xm, const uint8_t **pcall) -> bool {
+    bool pg, pm;
+    const char *xg = aux_z(r, 'X', 'G', &pg);
+    *xm = nullptr; *pcall = nullptr;
+    if (genome && CS.call[ri]) {
+      if (!aux_clean(r) || (pg && !xg)) return false;       // (the appended tags cannot be reached / XG is not a string)
+      *s = pg ? xg[0] : (char)CS.s_meth[ri];
+      *pcall = CS.xm.data() + CS.crec[(size_t)CS.call_idx[ri]].xm_off;
+      return true;
+    }
+    *xm = aux_z(r, 'X', 'M', &pm);
+    if (!pg || !pm || !xg || !*xm) return false;
+    *s = xg[0];
+    return true;
+  };
   auto use_record = [&](const Rec &r, const char *xm) -> int {
     if (r.tid < 0 || (size_t)r.tid >= names.size()) return fail(EPI_ERR_ARG, "corrupt BAM record %s: reference id out of range", r.qname);
     if (cigar_qlen(r) != (uint64_t)r.l_seq) return fail(EPI_ERR_ARG, "corrupt BAM record %s: CIGAR does not match the sequence length", r.qname);
@@ -741,9 +1001,10 @@ static int preprocess_impl(const char *path, const epi_bam_options *opt_in, epi_
     for (size_t ri = r_lo; ri < r_hi; ri++) {
       const Rec &r = recs[ri];
       if ((r.flag & skip_flags_pe) || !(r.flag & 0x2) || (int)r.mapq < opt.min_mapq) continue;   // :76-78
-      bool pg, pm;
-      const char *xg = aux_z(r, 'X', 'G', &pg), *xm = aux_z(r, 'X', 'M', &pm);
-      if (!pg || !pm || !xg || !xm) continue;                                                   // :80-82
+      char xg0;
+      const char *xm;
+      const uint8_t *pcall;
+      if (!xg_xm(ri, r, &xg0, &xm, &pcall)) continue;                                           // :80-82
       EPI_TRY(use_record(r, xm));
       if (!tname || strcmp(tname, r.qname) != 0) {                                              // :85
         if (t_strand != 0) push_template();
@@ -752,16 +1013,17 @@ static int preprocess_impl(const char *path, const epi_bam_options *opt_in, epi_
         t_start = r.pos < r.mpos ? r.pos : r.mpos;                                              // :92-93
         if (r.isize == INT32_MIN) return fail(EPI_ERR_ARG, "corrupt BAM record %s: template length", r.qname);
         t_width = r.isize < 0 ? -r.isize : r.isize;                                             // :94
-        t_strand = 2 - (xg[0] == 'C' ? 1 : 0);                                                  // :95
+        t_strand = 2 - (xg0 == 'C' ? 1 : 0);                                                    // :95
         if ((size_t)t_width > tq.size()) { tq.resize((size_t)t_width, q0); ts.resize((size_t)t_width, 0xFB); }
       }
       uint32_t dest_end = 0;
       if (r.pos < t_start) return fail(EPI_ERR_ARG, "corrupt BAM record %s: starts before its template", r.qname);
       const uint32_t dest0 = (uint32_t)(r.pos - t_start);                                       // :118
-      packed_bytes(r, xm, pb);                                                                  // (nt16 << 4) | ctx_idx per query base
+      if (!pcall) packed_bytes(r, xm, pb);                                                      // (nt16 << 4) | ctx_idx per query base
+      const uint8_t *pbase = pcall ? pcall : pb.data();
       EPI_TRY(apply_cigar(r, dest0, [&](uint32_t qpos, uint32_t dpos, uint32_t len) {
         if ((size_t)dpos + len > tq.size()) { tq.resize((size_t)dpos + len, q0); ts.resize((size_t)dpos + len, 0xFB); }
-        const uint8_t *__restrict__ ql = r.qual + qpos, *__restrict__ pq = pb.data() + qpos;
+        const uint8_t *__restrict__ ql = r.qual + qpos, *__restrict__ pq = pbase + qpos;
         uint8_t *__restrict__ tqd = tq.data() + dpos, *__restrict__ tsd = ts.data() + dpos;
         for (uint32_t j = 0; j < len; j++) {                                                    // :127 strictly higher quality wins
           const bool w = ql[j] > tqd[j];                                                        // (selects, not branches: the loop vectorises)
@@ -781,9 +1043,10 @@ static int preprocess_impl(const char *path, const epi_bam_options *opt_in, epi_
     for (size_t ri = r_lo; ri < r_hi; ri++) {
       const Rec &r = recs[ri];
       if ((r.flag & skip_flags) || (int)r.mapq < opt.min_mapq) continue;                        // :240-241
-      bool pg, pm;
-      const char *xg = aux_z(r, 'X', 'G', &pg), *xm = aux_z(r, 'X', 'M', &pm);
-      if (!pg || !pm || !xg || !xm) continue;
+      char xg0;
+      const char *xm;
+      const uint8_t *pcall;
+      if (!xg_xm(ri, r, &xg0, &xm, &pcall)) continue;
       EPI_TRY(use_record(r, xm));
       uint32_t width = 0;                                                                       // bam_cigar2rlen, :255
       for (uint32_t i = 0; i < r.n_cigar; i++) {
@@ -792,14 +1055,15 @@ static int preprocess_impl(const char *path, const epi_bam_options *opt_in, epi_
       }
       buf.assign(width, 0xFB);                                                                  // :265
       uint32_t dest_end = 0;
-      packed_bytes(r, xm, pb);
+      if (!pcall) packed_bytes(r, xm, pb);
+      const uint8_t *pbase = pcall ? pcall : pb.data();
       EPI_TRY(apply_cigar(r, 0, [&](uint32_t qpos, uint32_t dpos, uint32_t len) {
-        const uint8_t *__restrict__ ql = r.qual + qpos, *__restrict__ pq = pb.data() + qpos;
+        const uint8_t *__restrict__ ql = r.qual + qpos, *__restrict__ pq = pbase + qpos;
         uint8_t *__restrict__ bd = buf.data() + dpos;
         for (uint32_t j = 0; j < len; j++) bd[j] = (int)ql[j] >= opt.min_baseq ? pq[j] : bd[j]; // :278
       }, &dest_end));
       P.rname.push_back(r.tid + 1);                                                             // :303-306
-      P.strand.push_back(xg[0] == 'C' ? 1 : 2);
+      P.strand.push_back(xg0 == 'C' ? 1 : 2);
       P.start.push_back(r.pos + trim5 + 1);
       const int keep = (int)dest_end - (trim5 + trim3);
       if (keep > 0) P.bytes.insert(P.bytes.end(), buf.begin() + trim5, buf.begin() + trim5 + keep);
@@ -879,19 +1143,20 @@ static int preprocess_impl(const char *path, const epi_bam_options *opt_in, epi_
       bool complete = false;
       do {
         if (buf.size() < 12) break;
-        if (memcmp(buf.data(), "BAM\1", 4) != 0) return fail(EPI_ERR_ARG, "Unable to read BAM header");
+        if (memcmp(buf.data(), "BAM\1", 4) != 0) return fail(EPI_ERR_ARG, "%s", hdr_msg);
         size_t q = 8 + (size_t)rd32(buf.data() + 4);
         if (q + 4 > buf.size()) break;
         const uint32_t n_ref = rd32(buf.data() + q);
         q += 4;
-        names.clear();
+        names.clear(); lens.clear();
         bool ok = true;
         for (uint32_t i = 0; i < n_ref && ok; i++) {
           if (q + 4 > buf.size()) { ok = false; break; }
           const uint32_t l = rd32(buf.data() + q);
           if (q + 4 + (size_t)l + 4 > buf.size()) { ok = false; break; }
-          if (l == 0 || buf[q + 4 + l - 1] != 0) return fail(EPI_ERR_ARG, "Unable to read BAM header");
+          if (l == 0 || buf[q + 4 + l - 1] != 0) return fail(EPI_ERR_ARG, "%s", hdr_msg);
           names.emplace_back((const char *)buf.data() + q + 4);
+          lens.push_back((int64_t)rd32(buf.data() + q + 4 + l));
           q += 4 + (size_t)l + 4;
         }
         if (!ok) break;
@@ -899,7 +1164,7 @@ static int preprocess_impl(const char *path, const epi_bam_options *opt_in, epi_
         complete = true;
       } while (0);
       if (!complete) {
-        if (final) return fail(EPI_ERR_ARG, "Unable to read BAM header");
+        if (final) return fail(EPI_ERR_ARG, "%s", hdr_msg);
         carry = buf.size();                                  // the header is longer than a window: read on
         continue;
       }
@@ -964,10 +1229,19 @@ static int preprocess_impl(const char *path, const epi_bam_options *opt_in, epi_
       if (bad) return fail(EPI_ERR_ARG, "corrupt BAM record");
     }
     if (final && p != buf.size()) return fail(EPI_ERR_ARG, "truncated BAM record");
+    const size_t KT = opt.nthreads > 1 ? (size_t)(opt.nthreads > 16 ? 16 : opt.nthreads) : 1;
     if (!checked) {
       if (recs.size() < 1024 && !final) { carry = buf.size(); continue; }   // .checkBam looks at the first 1024 records
       lap("index");
+      // with a genome, callMethylation's own checks come first: the strand tag, the header against the genome
+      if (genome) {
+        EPI_TRY(call_choose_tag(recs.begin(), recs.size(), nullptr, &tag));
+        EPI_TRY(call_check_genome(genome, names, lens));
+      }
+      // (and its per-record checks over the whole window, before anything of it is packed)
+      if (genome) { const double t0 = tnow(); EPI_TRY(call_select(recs.begin(), recs.size(), tag, names, lens, KT, "epi_preprocess_bam", CS)); t_call += tnow() - t0; }
       // ---- .checkBam over the first 1024 records (src/rcpp_check_bam.cpp:40-50, R/internal.R:82-120) ----
+      // (with a genome, as callMethylation's output would show them: a record to call carries XG and XM)
       size_t nrecs = 0, npaired = 0, ntempls = 0;
       bool tXG = false, tXM = false, tYD = false, tZS = false;
       const char *prevq = nullptr;
@@ -975,7 +1249,9 @@ static int preprocess_impl(const char *path, const epi_bam_options *opt_in, epi_
         if (nrecs >= 1024) break;
         nrecs++;
         if (r.flag & 0x2) npaired++;
-        tXG |= has_tag(r, 'X', 'G'); tXM |= has_tag(r, 'X', 'M'); tYD |= has_tag(r, 'Y', 'D'); tZS |= has_tag(r, 'Z', 'S');
+        const bool called = genome && CS.call[nrecs - 1];
+        tXG |= called || has_tag(r, 'X', 'G'); tXM |= called || has_tag(r, 'X', 'M');
+        tYD |= has_tag(r, 'Y', 'D'); tZS |= has_tag(r, 'Z', 'S');
         tMM |= has_tag(r, 'M', 'M') || has_tag(r, 'M', 'm');
         if (prevq && strcmp(prevq, r.qname) == 0) ntempls++;
         prevq = r.qname;
@@ -990,6 +1266,10 @@ static int preprocess_impl(const char *path, const epi_bam_options *opt_in, epi_
       if (paired && !sorted) return fail(EPI_ERR_ARG, "BAM file seems to be paired-end but not sorted by name! Please sort using 'samtools sort -n -o out.bam in.bam'. Exiting");
       if (opt.paired >= 0 && (opt.paired != 0) != paired) return fail(EPI_ERR_ARG, "Expected endness is different from detected! Exiting");
       checked = true;
+    } else if (genome) {
+      const double t0 = tnow();
+      EPI_TRY(call_select(recs.begin(), recs.size(), tag, names, lens, KT, "epi_preprocess_bam", CS));
+      t_call += tnow() - t0;
     }
     // paired-end: the records of the window's last QNAME wait for the next window (their mate may be in it)
     size_t r_end = recs.size();
@@ -997,6 +1277,21 @@ static int preprocess_impl(const char *path, const epi_bam_options *opt_in, epi_
       const char *lastq = recs[r_end - 1].qname;
       while (r_end > 0 && strcmp(recs[r_end - 1].qname, lastq) == 0) r_end--;
       if (r_end == 0) { carry = buf.size(); continue; }      // one template fills the window: read on
+    }
+    if (genome) {                                            // the records about to be packed: called once, here
+      const double t0 = tnow();
+      EPI_TRY(call_pack_inputs(recs.begin(), r_end, KT, "epi_preprocess_bam", CS));
+      const int64_t ncall = (int64_t)CS.crec.size();
+      ncalled += ncall;
+#ifndef EPI_HOST_ONLY
+      if (!tMM)                                              // (the MM/ML packer reads no XG / XM)
+        EPI_TRY(call_methylation_window(eng, genome, wk, CS.crec.data(), ncall, CS.cigar.data(), CS.ncig, CS.seq.data(),
+                                        CS.nseq, CS.nxm, CALL_PACKED, CS.xm.data()));
+#else
+      (void)eng;
+      return fail(EPI_ERR_NODEVICE, "epi_preprocess_bam_genome: this build has no device code");
+#endif
+      t_call += tnow() - t0;
     }
     EPI_TRY(pack_window(r_end));
     nrecs_total += r_end;
@@ -1013,6 +1308,7 @@ static int preprocess_impl(const char *path, const epi_bam_options *opt_in, epi_
   buf.release();
 
   lap("pack");
+  if (timing && genome) fprintf(stderr, "[bam] (of which call selection, inputs and GPU %.3f s)\n", t_call);
   // ---- templid := 0..N-1 ; setorder(rname, start) -- stable (R/internal.R:193-195) ----
   const size_t n = P.rname.size();
   std::vector<uint32_t> order(n);
@@ -1100,6 +1396,7 @@ static int preprocess_impl(const char *path, const epi_bam_options *opt_in, epi_
   out->nbytes = w;
   out->xm_capacity = (int64_t)cap;
   out->nrecs = (int64_t)nrecs_total;
+  if (ncalled_out) *ncalled_out = ncalled;
   out->paired = paired ? 1 : 0;
   out->n_targets = (int32_t)names.size();
   for (size_t i = 0; i < names.size(); i++) out->target_names[i] = strdup(names[i].c_str());
@@ -1116,47 +1413,8 @@ static int preprocess_impl(const char *path, const epi_bam_options *opt_in, epi_
 #ifndef EPI_HOST_ONLY
 namespace {
 
-// bam_aux_get: the tag's type byte, or NULL when the record has no such tag (or its aux data is malformed before it)
-const uint8_t *aux_find(const Rec &r, char a, char b) {
-  const uint8_t *p = r.aux;
-  while (p + 3 <= r.end) {
-    const bool hit = (char)p[0] == a && (char)p[1] == b;
-    const char ty = (char)p[2];
-    if (hit) return p + 2;
-    p += 3;
-    switch (ty) {
-      case 'A': case 'c': case 'C': p += 1; break;
-      case 's': case 'S': p += 2; break;
-      case 'i': case 'I': case 'f': p += 4; break;
-      case 'Z': case 'H': {
-        const uint8_t *e = (const uint8_t *)memchr(p, 0, (size_t)(r.end - p));
-        if (!e) return nullptr;
-        p = e + 1;
-        break;
-      }
-      case 'B': {
-        if (p + 5 > r.end) return nullptr;
-        const char st = (char)p[0];
-        const size_t es = (st == 'c' || st == 'C') ? 1 : (st == 's' || st == 'S') ? 2 : 4;
-        p += 5 + (size_t)rd32(p + 1) * es;
-        break;
-      }
-      default: return nullptr;
-    }
-  }
-  return nullptr;
-}
-
-enum StrandTag { TAG_XG = 0, TAG_YD = 1, TAG_ZS = 2 };
-
 struct Window {                       // what one window's records turn into
-  std::vector<uint8_t> call;          // per record: 1 = call it
-  std::vector<uint8_t> s_meth, s_conv;
   std::vector<uint64_t> out_off;      // per record: where its output starts (n + 1 entries)
-  std::vector<int64_t> call_idx;      // per record: its index among the called ones
-  std::vector<CallRec> crec;
-  std::vector<uint32_t> cigar;
-  std::vector<uint8_t> seq, xm;
   std::vector<uint8_t> out;
 };
 
@@ -1180,6 +1438,7 @@ static int call_impl(epi_engine *eng, const char *in_path, const char *out_path,
   StrandTag tag = TAG_XG;
   BgzfWriter out;
   CallWork wk;
+  CallSet S;
   Window W;
   int64_t nrecs = 0, ncalled = 0;
   // phase times (EPIHIP_BAM_TIMING, as for the reader): inflate + index, host preparation, GPU, splice, deflate + write
@@ -1188,27 +1447,7 @@ static int call_impl(epi_engine *eng, const char *in_path, const char *out_path,
   double t_phase[5] = {0, 0, 0, 0, 0}, t_mark = tnow();
   auto lap = [&](int k) { const double t = tnow(); t_phase[k] += t - t_mark; t_mark = t; };
 
-  // runs f(lo, hi) over K ranges of [0, n) on K threads; the first error wins
-  auto parallel = [&](size_t n, auto &&f) -> int {
-    const size_t k = n < 4096 ? 1 : K;
-    std::vector<int> rcs(k, EPI_OK);
-    std::vector<std::string> msgs(k);
-    auto run = [&](size_t t) {
-      try {
-        rcs[t] = f(n * t / k, n * (t + 1) / k);
-      } catch (const std::bad_alloc &) {
-        rcs[t] = fail(EPI_ERR_NOMEM, "epi_call_methylation: out of host memory");
-      }
-      if (rcs[t] != EPI_OK) msgs[t] = epi_last_error();
-    };
-    std::vector<std::thread> th;
-    for (size_t t = 1; t < k; t++) th.emplace_back(run, t);
-    run(0);
-    for (auto &t : th) t.join();
-    for (size_t t = 0; t < k; t++)
-      if (rcs[t] != EPI_OK) return fail(rcs[t], "%s", msgs[t].c_str());
-    return EPI_OK;
-  };
+  auto parallel = [&](size_t n, auto &&f) -> int { return parallel_ranges(K, n, "epi_call_methylation", f); };
 
   for (bool final = blocks.empty();;) {
     size_t b1 = bi, add = 0;
@@ -1269,99 +1508,29 @@ static int call_impl(epi_engine *eng, const char *in_path, const char *out_path,
     lap(0);
     if (!checked) {
       if (nrec < 1024 && !final) { carry = buf.size(); continue; }   // .checkBam looks at the first 1024 records
-      // ---- .callMethylation (R/internal.R:412-423): the strand tag from the first 1024 records ----
-      bool tXG = false, tYD = false, tZS = false;
-      for (size_t i = 0; i < nrec && i < 1024; i++) {
-        tXG |= aux_find(recs[i], 'X', 'G') != nullptr;
-        tYD |= aux_find(recs[i], 'Y', 'D') != nullptr;
-        tZS |= aux_find(recs[i], 'Z', 'S') != nullptr;
-      }
-      if (force_tag) tag = strcmp(force_tag, "XG") == 0 ? TAG_XG : strcmp(force_tag, "YD") == 0 ? TAG_YD : TAG_ZS;
-      else if (nrec == 0) return fail(EPI_ERR_ARG, "Empty file provided! Exiting");
-      else if (tXG) tag = TAG_XG;
-      else if (tYD) tag = TAG_YD;
-      else if (tZS) tag = TAG_ZS;
-      else return fail(EPI_ERR_ARG, "Unable to call methylation: neither of XG/YD/ZS tags is present (genome strand unknown).\nExiting");
+      EPI_TRY(call_choose_tag(recs.data(), nrec, force_tag, &tag));
       // ---- the output and the header check (src/rcpp_call_methylation.cpp:41-72) ----
       EPI_TRY(out.open(out_path));
-      const int32_t ng = epi_genome_count(g);
-      for (size_t i = 0; i < names.size(); i++)
-        if ((int32_t)i >= ng || epi_genome_length(g, (int32_t)i) != lens[i] || names[i] != epi_genome_name(g, (int32_t)i))
-          return fail(EPI_ERR_ARG, "BAM reference sequence doesn't match the provided genome sequence");
+      EPI_TRY(call_check_genome(g, names, lens));
       EPI_TRY(out.write(buf.data(), hdr_end, nthreads));     // the input header, verbatim
       checked = true;
     }
-    const uint8_t *tag_name = (const uint8_t *)(tag == TAG_XG ? "XG" : tag == TAG_YD ? "YD" : "ZS");
-
     // ---- which records are called, and how large each one is written out ----
-    W.call.resize(nrec); W.s_meth.resize(nrec); W.s_conv.resize(nrec); W.out_off.resize(nrec + 1);
-    EPI_TRY(parallel(nrec, [&](size_t lo, size_t hi) -> int {
-      for (size_t i = lo; i < hi; i++) {
-        const Rec &r = recs[i];
-        const uint32_t bs = rd32(buf.data() + roff[i]);
-        W.call[i] = 0;
-        W.out_off[i + 1] = 4 + (uint64_t)bs;
-        const uint8_t *st = aux_find(r, (char)tag_name[0], (char)tag_name[1]);
-        if ((r.flag & 4) || !st || aux_find(r, 'X', 'M')) continue;      // written unchanged (:84-89)
-        // the strand tag's first two characters (bam_aux_get's pointer [1] and [2])
-        const uint8_t c1 = st + 1 < r.end ? st[1] : 0, c2 = st + 2 < r.end ? st[2] : 0;
-        if (tag == TAG_XG) { W.s_meth[i] = c1; W.s_conv[i] = c2; }
-        else {
-          const bool ga = tag == TAG_YD ? c1 == 'r' : c1 == '-';            // (:92-97)
-          W.s_meth[i] = ga ? 'G' : 'C'; W.s_conv[i] = ga ? 'A' : 'T';
-        }
-        // the checks that keep every access in bounds (the reference reads out of bounds here)
-        if (r.tid < 0 || (size_t)r.tid >= names.size()) return fail(EPI_ERR_ARG, "corrupt BAM record %s: reference id out of range", r.qname);
-        if (r.pos < 0) return fail(EPI_ERR_ARG, "corrupt BAM record %s: position out of range", r.qname);
-        uint64_t qlen = 0, rlen = 0;
-        for (uint32_t k = 0; k < r.n_cigar; k++) {
-          const uint32_t c = rd32(r.cigar + 4 * k), op = c & 0xF, len = c >> 4;
-          if (op > 9) return fail(EPI_ERR_ARG, "Unknown CIGAR operation for BAM entry %s", r.qname);
-          if (op == 0 || op == 1 || op == 4 || op == 7 || op == 8) qlen += len;
-          if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) rlen += len;
-        }
-        if (qlen != (uint64_t)r.l_seq) return fail(EPI_ERR_ARG, "corrupt BAM record %s: CIGAR does not match the sequence length", r.qname);
-        if ((uint64_t)r.pos + rlen > (uint64_t)lens[(size_t)r.tid])
-          return fail(EPI_ERR_ARG, "corrupt BAM record %s: alignment runs past the end of reference sequence %s", r.qname, names[(size_t)r.tid].c_str());
-        const uint64_t grown = (uint64_t)bs + (tag == TAG_XG ? 0 : 6) + 4 + (uint64_t)r.l_seq;
-        if (grown > 0x7FFFFFFFull) return fail(EPI_ERR_ARG, "corrupt BAM record %s: record too large", r.qname);
-        W.call[i] = 1;
-        W.out_off[i + 1] = 4 + grown;
-      }
-      return EPI_OK;
-    }));
-    // ---- offsets: output bytes, and the packed inputs / XM bytes of the called records ----
+    EPI_TRY(call_select(recs.data(), nrec, tag, names, lens, K, "epi_call_methylation", S));
+    W.out_off.resize(nrec + 1);
     W.out_off[0] = 0;
-    W.call_idx.resize(nrec);
-    int64_t ncall = 0, ncig = 0, nseq = 0, nxm = 0;
-    W.crec.clear();
     for (size_t i = 0; i < nrec; i++) {
-      W.out_off[i + 1] += W.out_off[i];
-      if (!W.call[i]) continue;
       const Rec &r = recs[i];
-      CallRec c;
-      memset(&c, 0, sizeof(c));
-      c.cig_off = ncig; c.seq_off = nseq; c.xm_off = nxm;
-      c.tid = r.tid; c.pos = r.pos; c.l_seq = r.l_seq; c.n_cig = (int32_t)r.n_cigar;
-      c.s_meth = W.s_meth[i]; c.s_conv = W.s_conv[i];
-      W.crec.push_back(c);
-      W.call_idx[i] = ncall++;
-      ncig += r.n_cigar; nseq += ((int64_t)r.l_seq + 1) / 2; nxm += r.l_seq;
+      const uint64_t bs = rd32(buf.data() + roff[i]);
+      W.out_off[i + 1] = W.out_off[i] + 4 + bs + (S.call[i] ? (tag == TAG_XG ? 0 : 6) + 4 + (uint64_t)r.l_seq : 0);
     }
-    W.cigar.resize((size_t)ncig); W.seq.resize((size_t)nseq); W.xm.resize((size_t)nxm);
-    EPI_TRY(parallel(nrec, [&](size_t lo, size_t hi) -> int {
-      for (size_t i = lo; i < hi; i++) {
-        if (!W.call[i]) continue;
-        const Rec &r = recs[i];
-        const CallRec &c = W.crec[(size_t)W.call_idx[i]];
-        if (r.n_cigar) memcpy(W.cigar.data() + c.cig_off, r.cigar, 4 * (size_t)r.n_cigar);
-        if (r.l_seq) memcpy(W.seq.data() + c.seq_off, r.seq, ((size_t)r.l_seq + 1) / 2);
-      }
-      return EPI_OK;
-    }));
+    // ---- the packed inputs of the called records ----
+    EPI_TRY(call_pack_inputs(recs.data(), nrec, K, "epi_call_methylation", S));
+    const int64_t ncall = (int64_t)S.crec.size();
     lap(1);
     // ---- the GPU: XM of every called record ----
-    EPI_TRY(call_methylation_window(eng, g, wk, W.crec.data(), ncall, W.cigar.data(), ncig, W.seq.data(), nseq, nxm, W.xm.data()));
+    EPI_TRY(call_methylation_window(eng, g, wk, S.crec.data(), ncall, S.cigar.data(), S.ncig, S.seq.data(), S.nseq, S.nxm,
+                                    CALL_XM, S.xm.data()));
     lap(2);
     // ---- the records, in input order, with the new tags appended (bam_aux_append / bam_aux_update_str) ----
     W.out.resize((size_t)W.out_off[nrec]);
@@ -1370,20 +1539,20 @@ static int call_impl(epi_engine *eng, const char *in_path, const char *out_path,
         const uint8_t *src = buf.data() + roff[i];
         const uint32_t bs = rd32(src);
         uint8_t *o = W.out.data() + W.out_off[i];
-        if (!W.call[i]) { memcpy(o, src, 4 + (size_t)bs); continue; }
+        if (!S.call[i]) { memcpy(o, src, 4 + (size_t)bs); continue; }
         const uint64_t nb = W.out_off[i + 1] - W.out_off[i] - 4;
         o[0] = (uint8_t)nb; o[1] = (uint8_t)(nb >> 8); o[2] = (uint8_t)(nb >> 16); o[3] = (uint8_t)(nb >> 24);
         memcpy(o + 4, src + 4, bs);
         o += 4 + (size_t)bs;
         if (tag != TAG_XG) {
-          const bool ga = W.s_meth[i] == 'G';
+          const bool ga = S.s_meth[i] == 'G';
           const uint8_t xg[6] = {'X', 'G', 'Z', (uint8_t)(ga ? 'G' : 'C'), (uint8_t)(ga ? 'A' : 'T'), 0};
           memcpy(o, xg, 6);
           o += 6;
         }
         o[0] = 'X'; o[1] = 'M'; o[2] = 'Z';
         const Rec &r = recs[i];
-        if (r.l_seq) memcpy(o + 3, W.xm.data() + W.crec[(size_t)W.call_idx[i]].xm_off, (size_t)r.l_seq);
+        if (r.l_seq) memcpy(o + 3, S.xm.data() + S.crec[(size_t)S.call_idx[i]].xm_off, (size_t)r.l_seq);
         o[3 + r.l_seq] = 0;
       }
       return EPI_OK;

@@ -11,7 +11,9 @@
 //   k_call_xm        per query base: the triad at offsets 0..2 (forward table, strand C/T) or -2..0 (reverse table,
 //                    strand G/A) keys a 512-entry context table in LDS; a base with a context is upper case when the
 //                    read shows the methylated base, '.' when it shows neither that nor the converted one, and lower
-//                    case otherwise.
+//                    case otherwise.  Two output forms of one kernel: the XM letter (callMethylation, BAM out) or the
+//                    reader's packed template byte (nt16 << 4) | ctx_to_idx(XM) (preprocessBam with a genome), which is
+//                    what bam_pack.cpp's packed_bytes() makes of SEQ and the XM letter.
 // The kernel boundary orders the scratch writes of the first before the reads of the second.  The host (bam_pack.cpp)
 // has checked every record it hands over: the contig exists, the CIGAR consumes exactly l_seq query bases and the
 // aligned span lies inside the contig; the kernels still keep every genome read inside its contig.
@@ -90,6 +92,7 @@ __global__ __launch_bounds__(256) void k_call_refspace(const CallRec *__restrict
   }
 }
 
+template <CallForm kForm>
 __global__ __launch_bounds__(256) void k_call_xm(const CallRec *__restrict__ recs, int64_t nrec, const uint8_t *__restrict__ seq,
                                                  const uint8_t *__restrict__ ref, uint8_t *__restrict__ xm) {
   __shared__ uint8_t s_ctx[2][512];                  // [0]: forward table, [1]: reverse table
@@ -111,15 +114,15 @@ __global__ __launch_bounds__(256) void k_call_xm(const CallRec *__restrict__ rec
   for (int32_t q = lane; q < c.l_seq; q += 64) {
     const uint32_t key = ((uint32_t)rf[q + sh] << 6) | ((uint32_t)rf[q + sh + 1] << 3) | (uint32_t)rf[q + sh + 2];
     uint8_t x = s_ctx[t][key];
+    const uint8_t b = sq[q >> 1];
+    const uint32_t nib = (q & 1) ? (b & 15u) : (b >> 4);
     if (x != '.') {
-      const uint8_t b = sq[q >> 1];
-      const uint32_t nib = (q & 1) ? (b & 15u) : (b >> 4);
       // seq_nt16_str "=ACMGRSVTWYHKDBN": the base as a letter
       const uint8_t ch = (uint8_t)"=ACMGRSVTWYHKDBN"[nib];
       if (ch == meth) x &= 0xDF;
       else if (ch != conv) x = '.';
     }
-    o[q] = x;
+    o[q] = kForm == CALL_PACKED ? (uint8_t)((nib << 4) | ctx_to_idx(x)) : x;
   }
 }
 
@@ -129,7 +132,7 @@ CallWork::~CallWork() { recs.release(); cig.release(); seq.release(); ref.releas
 
 int call_methylation_window(epi_engine *eng, epi_genome *g, CallWork &wk, const CallRec *recs, int64_t nrec,
                             const uint32_t *cigar, int64_t ncig, const uint8_t *seq, int64_t nseq, int64_t nxm,
-                            uint8_t *xm_out) {
+                            CallForm form, uint8_t *xm_out) {
   if (nrec <= 0) return EPI_OK;
   EPI_HIP(hipSetDevice(eng->device));
   const uint8_t *d_gseq = nullptr;
@@ -150,8 +153,12 @@ int call_methylation_window(epi_engine *eng, epi_genome *g, CallWork &wk, const 
   hipLaunchKernelGGL(k_call_refspace, dim3((unsigned)nblk), dim3(256), 0, s, wk.recs.as<CallRec>(), nrec, wk.cig.as<uint32_t>(),
                      d_gseq, d_goff, wk.ref.as<uint8_t>());
   EPI_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_call_xm, dim3((unsigned)nblk), dim3(256), 0, s, wk.recs.as<CallRec>(), nrec, wk.seq.as<uint8_t>(),
-                     wk.ref.as<uint8_t>(), wk.xm.as<uint8_t>());
+  if (form == CALL_PACKED)
+    hipLaunchKernelGGL(k_call_xm<CALL_PACKED>, dim3((unsigned)nblk), dim3(256), 0, s, wk.recs.as<CallRec>(), nrec,
+                       wk.seq.as<uint8_t>(), wk.ref.as<uint8_t>(), wk.xm.as<uint8_t>());
+  else
+    hipLaunchKernelGGL(k_call_xm<CALL_XM>, dim3((unsigned)nblk), dim3(256), 0, s, wk.recs.as<CallRec>(), nrec,
+                       wk.seq.as<uint8_t>(), wk.ref.as<uint8_t>(), wk.xm.as<uint8_t>());
   EPI_HIP(hipGetLastError());
   prof_end("call_methylation", s);
   if (nxm > 0) EPI_TRY(copy_to_host(eng, xm_out, wk.xm.p, (size_t)nxm, s));

@@ -252,7 +252,10 @@ class BgzfWriter {
 int genome_device(epi_genome *g, int device, const uint8_t **d_seq, const int64_t **d_off);
 
 // call_methylation.hip: one window of records to call.  The host fills the records and the packed CIGAR / SEQ arrays
-// while it parses the BAM records; the kernels write each record's XM bytes to xm + xm_off.
+// while it parses the BAM records; the kernels write each record's l_seq output bytes to xm + xm_off, in one of two
+// forms: the XM letters (callMethylation) or the packed template bytes (nt16 << 4) | ctx_to_idx(XM) (preprocessBam
+// with a genome).
+enum CallForm { CALL_XM = 0, CALL_PACKED = 1 };
 struct CallRec {
   int64_t cig_off;     // first CIGAR op in the window's packed u32 array
   int64_t seq_off;     // first byte of the record's 4-bit SEQ in the window's packed array
@@ -269,7 +272,7 @@ struct CallWork {      // device buffers of the windows, grown on demand
 };
 int call_methylation_window(epi_engine *eng, epi_genome *g, CallWork &wk, const CallRec *recs, int64_t nrec,
                             const uint32_t *cigar, int64_t ncig, const uint8_t *seq, int64_t nseq, int64_t nxm,
-                            uint8_t *xm_out);
+                            CallForm form, uint8_t *xm_out);
 
 // util kernels (util.hip)
 int scan_exclusive_u32(const uint32_t *d_in, uint32_t *d_out, int64_t n, uint32_t *d_total,
@@ -367,7 +370,7 @@ __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {       // sum over
 }
 #endif
 
-inline unsigned ctx_to_idx(unsigned char c) { return ((unsigned(c) + 2u) >> 2) & 15u; }   // src/epialleleR.h:28
+__host__ __device__ inline unsigned ctx_to_idx(unsigned char c) { return ((unsigned(c) + 2u) >> 2) & 15u; }   // src/epialleleR.h:28
 
 // A grid holds fewer than 2^32 threads (a larger one wraps silently): refuse instead.
 inline int check_grid(int64_t blocks, int threads, const char *what) {

@@ -197,6 +197,26 @@ typedef struct {       /* library-owned; release with epi_templates_free */
 int epi_preprocess_bam(const char *path, const epi_bam_options *opt /* NULL = R defaults */, epi_templates *out);
 void epi_templates_free(epi_templates *t);
 
+/* preprocessBam with a genome: methylation is called inside the reader, on the GPU, for BAM files that carry only a
+ * strand tag (bwa-meth YD, BSMAP ZS, uncalled DRAGEN / Bismark XG).  The contract is the composition
+ *     epi_preprocess_bam_genome(eng, in, opt, g, out, &ncalled)
+ *         == epi_call_methylation(eng, in, tmp, g, ...) followed by epi_preprocess_bam(tmp, opt, out)
+ * with nothing written to disk: the same xm bytes, off, rname, strand, start, target names, paired and nrecs.
+ *  - The strand tag (XG, else YD, else ZS) comes from the first 1024 records; a record is called when it is mapped,
+ *    carries that tag and has no XM.  Every other record is read as epi_preprocess_bam reads it (a record with XM keeps
+ *    its own).  A called record's strand is its XG's first letter, or for YD / ZS input the XG callMethylation would
+ *    append ('C': strand 1, 'G': strand 2).
+ *  - callMethylation's errors are raised with its messages, before the records concerned are packed: empty file, none
+ *    of XG/YD/ZS, header vs genome mismatch, an alignment past its contig's end, a CIGAR that does not consume l_seq
+ *    bases, an unknown CIGAR op -- also for records the options would have dropped.  Then epi_preprocess_bam's errors,
+ *    with .checkBam's tag flags taken as if the file had been called.
+ *  - *ncalled: the number of records callMethylation would have called, whatever the options drop later.
+ * engine NULL: the default engine (no device: EPI_ERR_NODEVICE; there is no CPU path).  Without a genome use
+ * epi_preprocess_bam, which this leaves unchanged. */
+int epi_preprocess_bam_genome(struct epi_engine *eng /* NULL: default */, const char *path,
+                              const epi_bam_options *opt /* NULL: R defaults */, epi_genome *g, epi_templates *out,
+                              int64_t *ncalled);
+
 /* ---- report writer (.writeReport, R/internal.R:274-287) -------------------
  * The table as a tab-separated file with a header line, what data.table::fwrite(report, quote=FALSE, sep="\t",
  * col.names=TRUE, compress=if (gzip) "gzip" else "none") writes: integers in decimal, factor columns as their
