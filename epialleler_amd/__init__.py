@@ -1,7 +1,7 @@
 """epialleler_amd -- MI355X-native engine for epialleleR's per-read methylation-call
 aggregation hot path (rcpp_threshold_reads / rcpp_get_xm_beta / rcpp_cx_report /
 rcpp_mhl_report, rcpp_get_base_freqs for generateVcfReport, rcpp_call_methylation_genome for
-callMethylation) behind the reference's own R-level interface.
+callMethylation, rcpp_simulate_bam for simulateBam) behind the reference's own R-level interface.
 
 Compute lives in csrc/ (hand-written HIP for gfx950 behind the C ABI of
 include/epihip.h); this package is the host-side mirror of the R functions.
@@ -12,5 +12,6 @@ from .api import (CONTEXT_TO_BASES, CONTEXT_LEVELS, STRAND_LEVELS, ProcessedBam,
 from .bed import (Bed, Ecdf, extractPatterns, generateAmpliconReport, generateBedEcdf, generateBedReport,  # noqa: F401
                   generateCaptureReport, readBed)
 from .genome import Genome, callMethylation, preprocessGenome, rcpp_call_methylation_genome, rcpp_read_genome  # noqa: F401
+from .simulate import rcpp_simulate_bam, simulateBam  # noqa: F401
 from .vcf import Vcf, generateVcfReport, rcpp_fep, rcpp_get_base_freqs, readVcf  # noqa: F401
 from ._lib import EpihipError  # noqa: F401

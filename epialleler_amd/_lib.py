@@ -68,6 +68,11 @@ class PatternTable(C.Structure):
                [("beta", C.POINTER(C.c_double)), ("fnv", C.POINTER(C.c_uint64)), ("cells", C.POINTER(C.c_int32))]
 
 
+class SimColumn(C.Structure):
+    _fields_ = [("name", C.c_char_p), ("kind", C.c_int32), ("type", C.c_char), ("values", C.c_void_p),
+                ("offsets", C.c_void_p), ("len", C.c_int64), ("period", C.c_int64)]
+
+
 def build(force=False):
     """Compile every HIP translation unit for gfx950 (hipcc cross-compiles without a GPU)."""
     cmd = ["make", "-C", CSRC, "-j8", "libepihip.so"]
@@ -102,6 +107,8 @@ _SIGS = {
     "epi_genome_sequence": (_VP, [_VP, _I32]),
     "epi_call_methylation": (C.c_int, [_VP, _CS, _CS, _VP, C.c_int, C.POINTER(_I64), C.POINTER(_I64)]),
     "epi_call_methylation_windowed": (C.c_int, [_VP, _CS, _CS, _VP, _CS, C.c_int, _I32, C.POINTER(_I64), C.POINTER(_I64)]),
+    "epi_simulate_bam": (C.c_int, [_VP, _CS, C.POINTER(C.c_char_p), _I32, _I64, C.POINTER(SimColumn), C.POINTER(SimColumn), _I32,
+                                   C.c_uint64, C.c_int, _I32, C.POINTER(_I64)]),
     "epi_bgzf_write_file": (C.c_int, [_CS, _VP, _I64, C.c_int]),
     "epi_preprocess_bam": (C.c_int, [_CS, C.POINTER(BamOptions), C.POINTER(Templates)]),
     "epi_preprocess_bam_genome": (C.c_int, [_VP, _CS, C.POINTER(BamOptions), _VP, C.POINTER(Templates), C.POINTER(_I64)]),

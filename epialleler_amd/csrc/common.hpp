@@ -370,6 +370,18 @@ __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {       // sum over
 }
 #endif
 
+// Counter-based hashing (splitmix64's finaliser), shared by the synthetic generator (synth.hip) and simulateBam's random
+// bases (simulate_bam.hip); tests/synth_np.py and epialleler_amd/simulate.py restate it in numpy.
+__host__ __device__ __forceinline__ uint64_t mix64(uint64_t z) {
+  z += 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+__host__ __device__ __forceinline__ uint64_t hash3(uint64_t seed, uint64_t stream, uint64_t idx) {
+  return mix64(mix64(seed + stream * 0xD1B54A32D192ED03ull) ^ idx);
+}
+
 __host__ __device__ inline unsigned ctx_to_idx(unsigned char c) { return ((unsigned(c) + 2u) >> 2) & 15u; }   // src/epialleleR.h:28
 
 // A grid holds fewer than 2^32 threads (a larger one wraps silently): refuse instead.

@@ -12,16 +12,6 @@
 
 namespace epi {
 
-__host__ __device__ __forceinline__ uint64_t mix64(uint64_t z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-__host__ __device__ __forceinline__ uint64_t hash3(uint64_t seed, uint64_t stream, uint64_t idx) {
-  return mix64(mix64(seed + stream * 0xD1B54A32D192ED03ull) ^ idx);
-}
-
 constexpr int64_t kSynthChunk = 1LL << 30;   // dwords per launch of the byte kernels
 
 struct SynthGeom {

@@ -1,7 +1,7 @@
 // Rcpp shim: epialleleR's hot-path exports re-implemented as thin calls into libepihip.so (include/epihip.h).
 // Drop these definitions in place of src/rcpp_threshold_reads.cpp, src/rcpp_get_xm_beta.cpp, src/rcpp_cx_report.cpp,
 // src/rcpp_mhl_report.cpp, src/rcpp_get_base_freqs.cpp, src/rcpp_fep.cpp, src/rcpp_read_genome.cpp,
-// src/rcpp_call_methylation.cpp and (optionally) the three readers of src/rcpp_read_bam.cpp: the [[Rcpp::export]] names and
+// src/rcpp_call_methylation.cpp, src/rcpp_simulate_bam.cpp and (optionally) the three readers of src/rcpp_read_bam.cpp: the [[Rcpp::export]] names and
 // signatures are the reference's, so R/RcppExports.R, src/RcppExports.cpp and every R caller stay unchanged (see
 // INTEGRATION.md).  NOT compiled in this repository's image (no R, Rcpp or HTSlib here); everything that does not
 // touch an SEXP lives in epihip_shim_core.hpp, which IS compiled and tested here (tests/cpp/test_shim_core.cpp).
@@ -304,4 +304,44 @@ Rcpp::List rcpp_call_methylation_genome(std::string in_fn, std::string out_fn, R
   try { epihip_shim::call_methylation(in_fn, out_fn, *gg, tag, nthreads, &nrecs, &ncalled); }
   catch (const std::exception &e) { Rcpp::stop("%s", e.what()); }
   return Rcpp::List::create(Rcpp::Named("nrecs") = (double)nrecs, Rcpp::Named("ncalled") = (double)ncalled);
+}
+
+// ---- simulateBam's export (src/rcpp_simulate_bam.cpp) ------------------------------------------------------------------
+
+// [[Rcpp::export]]
+int rcpp_simulate_bam(std::vector<std::string> header, Rcpp::DataFrame &fields, Rcpp::DataFrame &i_tags,
+                      Rcpp::DataFrame &f_tags, Rcpp::DataFrame &s_tags, Rcpp::DataFrame &a_tags,
+                      std::vector<std::string> a_types, std::string out_fn) {
+  epihip_shim::SimFields f;
+  f.qname = Rcpp::as<std::vector<std::string>>(fields["qname"]);
+  f.flag = Rcpp::as<std::vector<int32_t>>(fields["flag"]);
+  f.tid = Rcpp::as<std::vector<int32_t>>(fields["tid"]);
+  f.pos = Rcpp::as<std::vector<int64_t>>(fields["pos"]);
+  f.mapq = Rcpp::as<std::vector<int32_t>>(fields["mapq"]);
+  f.cigar = Rcpp::as<std::vector<std::string>>(fields["cigar"]);
+  f.mtid = Rcpp::as<std::vector<int32_t>>(fields["mtid"]);
+  f.mpos = Rcpp::as<std::vector<int64_t>>(fields["mpos"]);
+  f.isize = Rcpp::as<std::vector<int64_t>>(fields["isize"]);
+  f.seq = Rcpp::as<std::vector<std::string>>(fields["seq"]);
+  f.qual = Rcpp::as<std::vector<std::string>>(fields["qual"]);
+  std::vector<epihip_shim::SimTag> tags;
+  auto names = [](Rcpp::DataFrame &d) { return Rcpp::as<std::vector<std::string>>(d.names()); };
+  std::vector<std::string> n = names(i_tags);
+  for (size_t c = 0; c < n.size(); c++) { epihip_shim::SimTag t; t.name = n[c]; t.group = 'i'; t.i = Rcpp::as<std::vector<int32_t>>(i_tags[c]); tags.push_back(t); }
+  n = names(f_tags);
+  for (size_t c = 0; c < n.size(); c++) { epihip_shim::SimTag t; t.name = n[c]; t.group = 'f'; t.f = Rcpp::as<std::vector<double>>(f_tags[c]); tags.push_back(t); }
+  n = names(s_tags);
+  for (size_t c = 0; c < n.size(); c++) { epihip_shim::SimTag t; t.name = n[c]; t.group = 's'; t.s = Rcpp::as<std::vector<std::string>>(s_tags[c]); tags.push_back(t); }
+  n = names(a_tags);
+  for (size_t c = 0; c < n.size(); c++) {
+    epihip_shim::SimTag t;
+    t.name = n[c]; t.group = 'a'; t.type = a_types[c][0];
+    Rcpp::List l = a_tags[c];
+    for (R_xlen_t k = 0; k < l.size(); k++) t.a.push_back(Rcpp::as<std::vector<double>>(l[k]));
+    tags.push_back(t);
+  }
+  int64_t nw = 0;
+  try { nw = epihip_shim::simulate_bam(header, f, tags, out_fn); }
+  catch (const std::exception &e) { Rcpp::stop("%s", e.what()); }
+  return (int)nw;
 }

@@ -15,6 +15,8 @@
 //  * GenomeGuard, read_genome_into   rcpp_read_genome: the FASTA file -> rid / rname / rlen and the epi_genome the list's
 //                       `rseq_xptr` owns
 //  * call_methylation   rcpp_call_methylation_genome: BAM in, BAM out, with the strand tag R chose
+//  * SimColumns, simulate_bam   rcpp_simulate_bam: the data.frames R has recycled to nrecs -> epi_sim_column (len =
+//                       period = nrecs), the records assembled on the GPU
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -256,6 +258,128 @@ inline void call_methylation(const std::string &in_fn, const std::string &out_fn
   if (!gg.g) throw std::runtime_error("genome object has no sequences attached");
   check(epi_call_methylation_windowed(nullptr, in_fn.c_str(), out_fn.c_str(), gg.g, tag.c_str(), nthreads > 0 ? nthreads : 1, 0,
                                       nrecs, ncalled));
+}
+
+// rcpp_simulate_bam (src/rcpp_simulate_bam.cpp): .simulateBam has recycled every column to nrecs, so each one is shipped
+// with len = period = nrecs.  The column structs point into the vectors held here.
+struct SimTag {
+  std::string name;
+  char group = 'i';                      // 'i' (integer), 'f' (float), 's' (string), 'a' (array)
+  char type = 0;                         // arrays: the subtype R chose (a_types), c C s S i I f
+  std::vector<int32_t> i;
+  std::vector<double> f;
+  std::vector<std::string> s;
+  std::vector<std::vector<double>> a;
+};
+struct SimFields {
+  std::vector<std::string> qname, cigar, seq, qual;
+  std::vector<int32_t> flag, tid, mapq, mtid;
+  std::vector<int64_t> pos, mpos, isize;   // hts_pos_t in the reference
+};
+struct SimColumns {
+  std::vector<epi_sim_column> fields, tags;
+  std::vector<std::vector<int32_t>> i32;
+  std::vector<std::vector<float>> f32;
+  std::vector<std::vector<char>> bytes;
+  std::vector<std::vector<int64_t>> offs;
+  int64_t nrecs = 0;
+};
+inline void sim_strings(SimColumns &c, const std::vector<std::string> &v, epi_sim_column &col) {
+  std::vector<char> b;
+  std::vector<int64_t> o(1, 0);
+  for (const std::string &x : v) { b.insert(b.end(), x.begin(), x.end()); o.push_back((int64_t)b.size()); }
+  b.push_back(0);
+  c.bytes.push_back(std::move(b));
+  c.offs.push_back(std::move(o));
+  col.kind = EPI_SIM_STR;
+  col.values = c.bytes.back().data();
+  col.offsets = c.offs.back().data();
+}
+inline void sim_ints(SimColumns &c, std::vector<int32_t> v, epi_sim_column &col) {
+  c.i32.push_back(std::move(v));
+  col.kind = EPI_SIM_I32;
+  col.values = c.i32.back().data();
+}
+inline std::vector<int32_t> sim_narrow(const std::vector<int64_t> &v, const char *what) {
+  std::vector<int32_t> r(v.size());
+  for (size_t k = 0; k < v.size(); k++) {
+    if (v[k] < INT32_MIN || v[k] > INT32_MAX) throw std::runtime_error(std::string("Positional data is too large for BAM format: ") + what);
+    r[k] = (int32_t)v[k];
+  }
+  return r;
+}
+inline void sim_columns(const SimFields &f, const std::vector<SimTag> &tags, SimColumns &c) {
+  const size_t n = f.qname.size();
+  const std::vector<size_t> lens = {f.flag.size(), f.tid.size(), f.pos.size(), f.mapq.size(), f.cigar.size(),
+                                    f.mtid.size(), f.mpos.size(), f.isize.size(), f.seq.size(), f.qual.size()};
+  for (size_t l : lens)
+    if (l != n) throw std::runtime_error("rcpp_simulate_bam: the fields differ in length");
+  c = SimColumns();
+  c.nrecs = (int64_t)n;
+  const size_t ncol = 2 * (EPI_SIM_NFIELDS + tags.size()) + 8;   // reserved: the structs point into these vectors
+  c.i32.reserve(ncol); c.f32.reserve(ncol); c.bytes.reserve(ncol); c.offs.reserve(ncol);
+  c.fields.assign(EPI_SIM_NFIELDS, epi_sim_column());
+  for (epi_sim_column &col : c.fields) { memset(&col, 0, sizeof(col)); col.len = col.period = (int64_t)(n ? n : 1); }
+  sim_strings(c, f.qname, c.fields[0]);
+  sim_ints(c, f.flag, c.fields[1]);
+  sim_ints(c, f.tid, c.fields[2]);
+  sim_ints(c, sim_narrow(f.pos, "pos"), c.fields[3]);
+  sim_ints(c, f.mapq, c.fields[4]);
+  sim_strings(c, f.cigar, c.fields[5]);
+  sim_ints(c, f.mtid, c.fields[6]);
+  sim_ints(c, sim_narrow(f.mpos, "mpos"), c.fields[7]);
+  sim_ints(c, sim_narrow(f.isize, "isize"), c.fields[8]);
+  sim_strings(c, f.seq, c.fields[9]);
+  sim_strings(c, f.qual, c.fields[10]);
+  c.tags.assign(tags.size(), epi_sim_column());
+  for (size_t k = 0; k < tags.size(); k++) {
+    const SimTag &t = tags[k];
+    epi_sim_column &col = c.tags[k];
+    memset(&col, 0, sizeof(col));
+    col.name = t.name.c_str();
+    col.len = col.period = (int64_t)(n ? n : 1);
+    const size_t len = t.group == 'i' ? t.i.size() : t.group == 'f' ? t.f.size() : t.group == 's' ? t.s.size() : t.a.size();
+    if (t.name.size() != 2 || len != n) throw std::runtime_error("rcpp_simulate_bam: bad tag column " + t.name);
+    if (t.group == 'i') {
+      sim_ints(c, t.i, col);
+    } else if (t.group == 'f') {
+      c.f32.emplace_back(t.f.begin(), t.f.end());            // bam_aux_update_float(float)
+      col.kind = EPI_SIM_F32;
+      col.values = c.f32.back().data();
+    } else if (t.group == 's') {
+      sim_strings(c, t.s, col);
+    } else {
+      if (!t.type || !strchr("cCsSiIf", t.type)) throw std::runtime_error("rcpp_simulate_bam: bad array type for " + t.name);
+      std::vector<int64_t> o(1, 0);
+      std::vector<int32_t> iv;
+      std::vector<float> fv;
+      for (const std::vector<double> &x : t.a) {
+        for (double d : x) {                                   // save_array_tag: static_cast<T>(value)
+          if (t.type == 'f') fv.push_back((float)d);
+          else iv.push_back(t.type == 'I' ? (int32_t)(uint32_t)d : (int32_t)d);
+        }
+        o.push_back((int64_t)(t.type == 'f' ? fv.size() : iv.size()));
+      }
+      if (t.type == 'f') { fv.push_back(0.0f); c.f32.push_back(std::move(fv)); col.values = c.f32.back().data(); }
+      else { iv.push_back(0); c.i32.push_back(std::move(iv)); col.values = c.i32.back().data(); }
+      c.offs.push_back(std::move(o));
+      col.kind = EPI_SIM_ARR;
+      col.type = t.type;
+      col.offsets = c.offs.back().data();
+    }
+  }
+}
+// the default engine's device assembles the records; returns the number written
+inline int64_t simulate_bam(const std::vector<std::string> &header, const SimFields &f, const std::vector<SimTag> &tags,
+                            const std::string &out_fn, uint64_t seed = 0, int nthreads = 1) {
+  SimColumns c;
+  sim_columns(f, tags, c);
+  std::vector<const char *> lines;
+  for (const std::string &h : header) lines.push_back(h.c_str());
+  int64_t nw = 0;
+  check(epi_simulate_bam(nullptr, out_fn.c_str(), lines.data(), (int32_t)lines.size(), c.nrecs, c.fields.data(),
+                         c.tags.empty() ? nullptr : c.tags.data(), (int32_t)c.tags.size(), seed, nthreads, 0, &nw));
+  return nw;
 }
 
 }  // namespace epihip_shim

@@ -160,6 +160,37 @@ int epi_call_methylation(struct epi_engine *eng, const char *in_path, const char
 int epi_call_methylation_windowed(struct epi_engine *eng, const char *in_path, const char *out_path, epi_genome *g,
                                   const char *tag, int nthreads, int32_t window_kib, int64_t *nrecs, int64_t *ncalled);
 
+/* ---- simulateBam (rcpp_simulate_bam, R/internal.R:296-403) ----------------------------------------------------------
+ * One column of records, as the caller supplied it: record i reads element (i % period) % len, so a short column is
+ * recycled on the device and never expanded on the host.  `fields` are always EPI_SIM_NFIELDS columns in this order:
+ *   qname (STR, or NONE: "q%04d" of i + 1), flag, tid, pos (0-based), mapq (I32), cigar (STR, or NONE: "<l_seq>M"),
+ *   mtid, mpos (0-based), isize (I32, or NONE: l_seq), seq (STR, or RANDOM), qual (STR with '!'-based letters, or NONE:
+ *   'F' for every base).
+ * RANDOM seq: `values` holds the int32 lengths of the random strings; base k of string j is
+ *   "ACTG"[hash3(seed, 0x53494D, (j << 32) | k) >> 62]   (hash3 of synth.hip).
+ * Tag columns carry their two-letter `name`; they are written in the order given, with the encodings of HTSlib's
+ * bam_aux_update_int (I32: the narrowest of c C s S i I), _float (F32: 'f'), _str (STR: 'Z') and _array (ARR: 'B',
+ * subtype `type` of c C s S i I f; `values` int32 elements, or float for 'f', `offsets` the len + 1 element offsets). */
+enum { EPI_SIM_NONE = 0, EPI_SIM_I32 = 1, EPI_SIM_F32 = 2, EPI_SIM_STR = 3, EPI_SIM_ARR = 4, EPI_SIM_RANDOM = 5 };
+enum { EPI_SIM_NFIELDS = 11 };
+typedef struct {
+  const char *name;          /* tag columns: the tag's two letters; fields: ignored */
+  int32_t kind;              /* EPI_SIM_* */
+  char type;                 /* EPI_SIM_ARR: the array subtype */
+  const void *values;        /* I32 / RANDOM: int32[len]; F32: float[len]; STR: the bytes; ARR: int32 or float elements */
+  const int64_t *offsets;    /* STR: len + 1 byte offsets into values; ARR: len + 1 element offsets; otherwise NULL */
+  int64_t len;               /* elements (strings, arrays); >= 1 unless kind is NONE */
+  int64_t period;            /* >= 1 */
+} epi_sim_column;
+/* Writes `nrecs` records after a header made of `lines` (sam_hdr_add_lines: @SQ SN / LN give the reference sequences, in
+ * order).  Every record is sized and checked on the GPU before the file is opened, so an invalid call leaves no file;
+ * then the records are assembled on the GPU window by window (~64 MiB of uncompressed BAM each, window_kib overrides)
+ * and deflated by `nthreads` threads while the next window is built.  engine NULL: the default engine.  Errors use the
+ * reference's messages ("Unable to fill CIGAR array", "Unable to fill BAM record", ...) with the failing record. */
+int epi_simulate_bam(struct epi_engine *eng, const char *out_path, const char *const *lines, int32_t nlines, int64_t nrecs,
+                     const epi_sim_column *fields, const epi_sim_column *tags, int32_t ntags, uint64_t seed, int nthreads,
+                     int32_t window_kib, int64_t *nwritten);
+
 /* BGZF writer (host): `n` bytes as blocks of at most 0xff00 input bytes (BC extra field, CRC32), compressed at level 6 by
  * `nthreads` threads and written in order, then the 28-byte end-of-file block. */
 int epi_bgzf_write_file(const char *path, const uint8_t *data, int64_t n, int nthreads);
