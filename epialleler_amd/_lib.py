@@ -112,6 +112,7 @@ _SIGS = {
     "epi_bgzf_write_file": (C.c_int, [_CS, _VP, _I64, C.c_int]),
     "epi_preprocess_bam": (C.c_int, [_CS, C.POINTER(BamOptions), C.POINTER(Templates)]),
     "epi_preprocess_bam_genome": (C.c_int, [_VP, _CS, C.POINTER(BamOptions), _VP, C.POINTER(Templates), C.POINTER(_I64)]),
+    "epi_preprocess_bam_anyorder": (C.c_int, [_VP, _CS, C.POINTER(BamOptions), C.POINTER(Templates)]),
     "epi_templates_free": (None, [C.POINTER(Templates)]),
     "epi_write_report": (C.c_int, [_CS, C.POINTER(ReportColumn), _I32, _I64, _I32, _I32]),
     "epi_engine_create": (C.c_int, [C.c_int, C.POINTER(_VP)]),

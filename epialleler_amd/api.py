@@ -190,7 +190,7 @@ def _as_bam(bam):
 
 def preprocessBam(bam_file, paired=None, min_mapq=0, min_baseq=0, min_prob=-1, highest_prob=True,
                   skip_duplicates=False, skip_secondary=True, skip_qcfail=True, skip_supplementary=True,
-                  trim=0, nthreads=1, verbose=False, window_kib=0, genome=None):
+                  trim=0, nthreads=1, verbose=False, window_kib=0, genome=None, mates=None):
     """R/preprocessBam.R:197-237.  An already preprocessed object is returned untouched (:226-235);
     a path is decoded by the library's host-side producer (epi_preprocess_bam: zlib BGZF reader + the
     reference's template packer), which yields the sorted SoA batch directly.
@@ -199,7 +199,16 @@ def preprocessBam(bam_file, paired=None, min_mapq=0, min_baseq=0, min_prob=-1, h
     strand tag, no XM) are called on the GPU inside the reader (epi_preprocess_bam_genome): the result equals
     preprocessBam(callMethylation(bam_file, tmp, genome); tmp) with the same options, errors included, and no BAM is
     written.  `ncalled` on the result counts the called records (0 without a genome).  There is no CPU path: without
-    a device this raises EpihipError."""
+    a device this raises EpihipError.
+
+    mates: "adjacent" (None, the default) reads paired-end input whose mates are neighbours, as the reference does (a
+    file that is not name-sorted is refused).  "anywhere" pairs the mates through their QNAMEs wherever they lie
+    (coordinate-sorted input, DRAGEN's default) and merges the templates on the GPU (epi_preprocess_bam_anyorder): the
+    result equals preprocessBam of the file regrouped by QNAME, READ1 before READ2 (include/epihip.h).  Single-end and
+    long-read files read as with "adjacent".  Not together with genome=; no CPU path (EpihipError without a device)."""
+    mates = _match_arg(mates, ("adjacent", "anywhere"), "mates")
+    if mates == "anywhere" and genome is not None:
+        raise ValueError("mates='anywhere' cannot be combined with genome= (yet)")
     if isinstance(bam_file, (ProcessedBam, dict)):
         return _as_bam(bam_file)
     import os
@@ -210,6 +219,9 @@ def preprocessBam(bam_file, paired=None, min_mapq=0, min_baseq=0, min_prob=-1, h
         genome = preprocessGenome(genome, nthreads=nthreads, verbose=verbose)
         eng = C.c_void_p()
         _lib.check(lib.epi_default_engine(C.byref(eng)))          # no device: EpihipError (as rcpp_call_methylation_genome)
+    if mates == "anywhere":
+        eng = C.c_void_p()
+        _lib.check(lib.epi_default_engine(C.byref(eng)))          # no device: EpihipError, before the file is read
     trim2 = (list(np.atleast_1d(trim)) * 2)[:2]                       # head(rep.int(trim, 2), 2)
     opt = _lib.BamOptions(int(min_mapq), int(min_baseq), int(bool(skip_duplicates)), int(bool(skip_secondary)),
                           int(bool(skip_qcfail)), int(bool(skip_supplementary)), int(trim2[0]), int(trim2[1]),
@@ -218,11 +230,13 @@ def preprocessBam(bam_file, paired=None, min_mapq=0, min_baseq=0, min_prob=-1, h
     t = _lib.Templates()
     ncalled = C.c_int64(0)
     path = os.path.expanduser(str(bam_file)).encode()
-    if genome is None:
-        rc = lib.epi_preprocess_bam(path, C.byref(opt), C.byref(t))
-    else:
+    if genome is not None:
         rc = lib.epi_preprocess_bam_genome(eng, path, C.byref(opt), genome._h, C.byref(t), C.byref(ncalled))
-    if genome is not None and rc not in (_lib.EPI_OK, _lib.EPI_ERR_ARG):
+    elif mates == "anywhere":
+        rc = lib.epi_preprocess_bam_anyorder(eng, path, C.byref(opt), C.byref(t))
+    else:
+        rc = lib.epi_preprocess_bam(path, C.byref(opt), C.byref(t))
+    if eng is not None and rc not in (_lib.EPI_OK, _lib.EPI_ERR_ARG):
         _lib.check(rc)                                                # device / HIP failures: EpihipError
     if rc != _lib.EPI_OK:
         msg = lib.epi_last_error().decode("utf-8", "replace")

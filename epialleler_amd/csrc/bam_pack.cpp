@@ -402,10 +402,8 @@ struct Packed {
 };
 
 // (nt16 << 4) | ctx_idx(XM) of every query base of a record (src/epialleleR.h:28,32): two bases per byte of SEQ
-inline void packed_bytes(const Rec &r, const char *xm, std::vector<uint8_t> &pb) {
+inline void pack_query(const Rec &r, const char *xm, uint8_t *__restrict__ o) {
   const size_t n = (size_t)r.l_seq;
-  pb.resize(n + 2);
-  uint8_t *__restrict__ o = pb.data();
   const uint8_t *__restrict__ s = r.seq;
   const unsigned char *__restrict__ x = reinterpret_cast<const unsigned char *>(xm);
   for (size_t i = 0; i + 1 < n; i += 2) {
@@ -414,6 +412,10 @@ inline void packed_bytes(const Rec &r, const char *xm, std::vector<uint8_t> &pb)
     o[i + 1] = (uint8_t)(((b << 4) & 0xF0) | (((x[i + 1] + 2u) >> 2) & 15u));
   }
   if (n & 1) o[n - 1] = (uint8_t)((s[(n - 1) >> 1] & 0xF0) | (((x[n - 1] + 2u) >> 2) & 15u));
+}
+inline void packed_bytes(const Rec &r, const char *xm, std::vector<uint8_t> &pb) {
+  pb.resize((size_t)r.l_seq + 2);
+  pack_query(r, xm, pb.data());
 }
 
 // walk the CIGAR of one record into the template buffers; returns the reference position after the last op
@@ -434,6 +436,50 @@ int apply_cigar(const Rec &r, uint32_t dest0, F &&on_match, uint32_t *dest_end) 
   return EPI_OK;
 }
 
+// QNAME -> template id (mates = "anywhere"), ids given in the order the keys are first added.  Open addressing over a
+// power-of-two table with the exact string compare; the keys are kept back to back (NUL-terminated), which also names
+// the template in messages after its records' window is gone.
+class QnameMap {
+ public:
+  static uint64_t hash(const char *q) {                      // FNV-1a, finalised
+    uint64_t h = 0xCBF29CE484222325ull;
+    for (; *q; q++) h = (h ^ (uint8_t)*q) * 0x100000001B3ull;
+    return mix64(h);
+  }
+  uint32_t find_or_add(const char *q, uint64_t h) {
+    if (2 * (hash_.size() + 1) > slot_.size()) grow();
+    const size_t mask = slot_.size() - 1;
+    size_t i = (size_t)h & mask;
+    for (; slot_[i]; i = (i + 1) & mask) {
+      const uint32_t g = slot_[i] - 1;
+      if (hash_[g] == h && strcmp(name(g), q) == 0) return g;
+    }
+    const uint32_t g = (uint32_t)hash_.size();
+    slot_[i] = g + 1;
+    hash_.push_back(h);
+    off_.push_back(names_.size());
+    names_.insert(names_.end(), q, q + strlen(q) + 1);
+    return g;
+  }
+  const char *name(uint32_t g) const { return names_.data() + off_[g]; }
+  size_t size() const { return hash_.size(); }
+
+ private:
+  void grow() {
+    slot_.assign(slot_.empty() ? 4096 : 2 * slot_.size(), 0u);
+    const size_t mask = slot_.size() - 1;
+    for (uint32_t g = 0; g < (uint32_t)hash_.size(); g++) {
+      size_t i = (size_t)hash_[g] & mask;
+      while (slot_[i]) i = (i + 1) & mask;
+      slot_[i] = g + 1;
+    }
+  }
+  std::vector<uint32_t> slot_;     // id + 1, 0: empty
+  std::vector<uint64_t> hash_;     // per id
+  std::vector<size_t> off_;        // per id: its key in names_
+  std::vector<char> names_;
+};
+
 }  // namespace
 
 extern "C" {
@@ -451,14 +497,14 @@ void epi_templates_free(epi_templates *t) {
 }
 
 static int preprocess_impl(const char *path, const epi_bam_options *opt_in, epi_templates *out, epi_engine *eng,
-                           epi_genome *genome, int64_t *ncalled_out);
+                           epi_genome *genome, int64_t *ncalled_out, bool anyorder);
 
 int epi_preprocess_bam(const char *path, const epi_bam_options *opt_in, epi_templates *out) {
   if (!path || !out) return fail(EPI_ERR_ARG, "epi_preprocess_bam: NULL argument");
   memset(out, 0, sizeof(*out));
   int rc;
   try {                                                     // nothing may unwind through the C boundary
-    rc = preprocess_impl(path, opt_in, out, nullptr, nullptr, nullptr);
+    rc = preprocess_impl(path, opt_in, out, nullptr, nullptr, nullptr, false);
   } catch (const std::bad_alloc &) {
     rc = fail(EPI_ERR_NOMEM, "epi_preprocess_bam: out of host memory");
   } catch (...) {
@@ -480,13 +526,34 @@ int epi_preprocess_bam_genome(epi_engine *eng, const char *path, const epi_bam_o
   if (!eng) EPI_TRY(epi_default_engine(&eng));               // no device: fails here, before the file is read
   int rc;
   try {
-    rc = preprocess_impl(path, opt_in, out, eng, g, ncalled);
+    rc = preprocess_impl(path, opt_in, out, eng, g, ncalled, false);
   } catch (const std::bad_alloc &) {
     rc = fail(EPI_ERR_NOMEM, "epi_preprocess_bam: out of host memory");
   } catch (...) {
     rc = fail(EPI_ERR_ARG, "epi_preprocess_bam: unexpected failure while reading %s", path);
   }
   if (rc != EPI_OK) { epi_templates_free(out); *ncalled = 0; }
+  return rc;
+#endif
+}
+
+int epi_preprocess_bam_anyorder(epi_engine *eng, const char *path, const epi_bam_options *opt_in, epi_templates *out) {
+  if (!path || !out) return fail(EPI_ERR_ARG, "epi_preprocess_bam_anyorder: NULL argument");
+  memset(out, 0, sizeof(*out));
+#ifdef EPI_HOST_ONLY
+  (void)eng; (void)opt_in;
+  return fail(EPI_ERR_NODEVICE, "epi_preprocess_bam_anyorder: templates are assembled on the GPU; this build has no device code");
+#else
+  if (!eng) EPI_TRY(epi_default_engine(&eng));               // no device: fails here, before the file is read
+  int rc;
+  try {
+    rc = preprocess_impl(path, opt_in, out, eng, nullptr, nullptr, true);
+  } catch (const std::bad_alloc &) {
+    rc = fail(EPI_ERR_NOMEM, "epi_preprocess_bam: out of host memory");
+  } catch (...) {
+    rc = fail(EPI_ERR_ARG, "epi_preprocess_bam: unexpected failure while reading %s", path);
+  }
+  if (rc != EPI_OK) epi_templates_free(out);
   return rc;
 #endif
 }
@@ -732,8 +799,13 @@ bool aux_clean(const Rec &r) {
 // genome != NULL (epi_preprocess_bam_genome): the records callMethylation would call are called on the GPU, window by
 // window, into packed template bytes, and the packers read them in place of XG / XM -- the result is that of
 // preprocessBam(callMethylation(path)) without the BAM in between.
+//
+// anyorder (epi_preprocess_bam_anyorder, mates = "anywhere"): paired-end records are paired through their QNAMEs wherever
+// they lie in the file.  Per window, the kept records get their template ids and their CIGAR ops, packed query bytes and
+// qualities go to a device arena; at the end of the file the host orders each template's records and lays out the rows,
+// and assemble_templates.hip merges them on the GPU.
 static int preprocess_impl(const char *path, const epi_bam_options *opt_in, epi_templates *out, epi_engine *eng,
-                           epi_genome *genome, int64_t *ncalled_out) {
+                           epi_genome *genome, int64_t *ncalled_out, bool anyorder) {
   epi_bam_options opt;
   if (opt_in) opt = *opt_in;
   else { memset(&opt, 0, sizeof(opt)); opt.skip_secondary = opt.skip_qcfail = opt.skip_supplementary = 1; opt.paired = -1; opt.nthreads = 1; opt.min_prob = -1; opt.highest_prob = 1; }
@@ -1129,6 +1201,118 @@ static int preprocess_impl(const char *path, const epi_bam_options *opt_in, epi_
     return EPI_OK;
   };
 
+  // ---- mates = "anywhere": the kept records of paired-end input, wherever their mates are ----
+  // Per kept record the small columns below (and its QNAME, once per template, in qmap); its CIGAR ops, packed query bytes
+  // and qualities go to the device arena at aoff, 4 * n_cig + 2 * l_seq bytes rounded up to 4.
+  struct Kept {
+    uint32_t gid;                  // template id: the order of the templates' first kept records in the file
+    int32_t tid, pos, mpos, isize;
+    uint32_t rspan;                // reference length of the CIGAR (M D N = X), as apply_cigar sums it
+    int64_t aoff;
+    int32_t n_cig, l_seq;
+    uint8_t cls, strand;           // flag & 0xC0 (merge order); XG's first letter
+  };
+  auto kept_bytes = [](const Kept &k) { return ((size_t)k.n_cig * 4 + 2 * (size_t)k.l_seq + 3) & ~(size_t)3; };
+  bool asm_mode = false;                                    // anyorder && paired-end short-read input (set by the check)
+  QnameMap qmap;
+  std::vector<Kept> kept;
+  std::vector<uint8_t> wk_keep;                             // per record of the window
+  std::vector<char> wk_xg;
+  std::vector<const char *> wk_xm;
+  std::vector<uint32_t> wk_span, wk_ri;
+  std::vector<uint64_t> wk_hash;
+  size_t arena_used = 0;
+  int stage_k = 0;
+  double t_pair = 0, t_upload = 0, t_inflate = 0, t_parse = 0;
+#ifndef EPI_HOST_ONLY
+  DevBuf arena;                                             // sized by the file's inflated bytes: a kept record's inputs are
+  struct ArenaRelease { DevBuf *a; ~ArenaRelease() { a->release(); } } arena_release{&arena};   // smaller than the record
+#endif
+  // the window's records [0, nrec): which are kept (pack_pe's filters and checks), their template ids, and their inputs
+  // queued for upload
+  auto collect_window = [&](size_t nrec) -> int {
+    double t0 = tnow();
+    const size_t KT = opt.nthreads > 1 ? (size_t)(opt.nthreads > 16 ? 16 : opt.nthreads) : 1;
+    const uint16_t skip_flags_pe = skip_flags | 8;
+    wk_keep.resize(nrec); wk_xg.resize(nrec); wk_xm.resize(nrec); wk_span.resize(nrec); wk_hash.resize(nrec);
+    EPI_TRY(parallel_ranges(KT, nrec, "epi_preprocess_bam", [&](size_t lo, size_t hi) -> int {
+      for (size_t ri = lo; ri < hi; ri++) {
+        const Rec &r = recs[ri];
+        wk_keep[ri] = 0;
+        if ((r.flag & skip_flags_pe) || !(r.flag & 0x2) || (int)r.mapq < opt.min_mapq) continue;   // pack_pe's filters
+        char xg0;
+        const char *xm;
+        const uint8_t *pcall;
+        if (!xg_xm(ri, r, &xg0, &xm, &pcall)) continue;
+        EPI_TRY(use_record(r, xm));
+        uint32_t span = 0;
+        EPI_TRY(apply_cigar(r, 0, [](uint32_t, uint32_t, uint32_t) {}, &span));
+        wk_keep[ri] = 1; wk_xg[ri] = xg0; wk_xm[ri] = xm; wk_span[ri] = span;
+        wk_hash[ri] = QnameMap::hash(r.qname);
+      }
+      return EPI_OK;
+    }));
+    const size_t k0 = kept.size();                          // ids in file order: the same for every nthreads
+    wk_ri.clear();
+    size_t wbytes = 0;
+    for (size_t ri = 0; ri < nrec; ri++) {
+      if (!wk_keep[ri]) continue;
+      const Rec &r = recs[ri];
+      Kept k;
+      k.gid = qmap.find_or_add(r.qname, wk_hash[ri]);
+      k.tid = r.tid; k.pos = r.pos; k.mpos = r.mpos; k.isize = r.isize; k.rspan = wk_span[ri];
+      k.n_cig = (int32_t)r.n_cigar; k.l_seq = r.l_seq;
+      k.cls = (uint8_t)(r.flag & 0xC0); k.strand = (uint8_t)(2 - (wk_xg[ri] == 'C' ? 1 : 0));
+      k.aoff = (int64_t)(arena_used + wbytes);
+      wbytes += kept_bytes(k);
+      kept.push_back(k);
+      wk_ri.push_back((uint32_t)ri);
+    }
+    const double t1 = tnow();
+    t_pair += t1 - t0;
+#ifndef EPI_HOST_ONLY
+    if (arena_used + wbytes > arena.cap) return fail(EPI_ERR_STATE, "epi_preprocess_bam_anyorder: device arena too small");
+    auto fill = [&](size_t i, uint8_t *o) {                 // kept record k0 + i -> its arena bytes at o
+      const Rec &r = recs[wk_ri[i]];
+      if (r.n_cigar) memcpy(o, r.cigar, 4 * (size_t)r.n_cigar);
+      o += 4 * (size_t)r.n_cigar;
+      pack_query(r, wk_xm[wk_ri[i]], o);
+      if (r.l_seq) memcpy(o + r.l_seq, r.qual, (size_t)r.l_seq);
+    };
+    // through the engine's two pinned staging buffers: filled by the threads while the copy stream drains the other one
+    const size_t nk = kept.size() - k0;
+    for (size_t i = 0; i < nk;) {
+      uint8_t *st;
+      size_t cap;
+      EPI_TRY(stage_buffer(eng, stage_k, &st, &cap));
+      size_t j = i, bytes = 0;
+      while (j < nk && bytes + kept_bytes(kept[k0 + j]) <= cap) bytes += kept_bytes(kept[k0 + j++]);
+      if (j == i) {                                         // one record larger than a staging buffer: a copy of its own
+        std::vector<uint8_t> big(kept_bytes(kept[k0 + i]));
+        fill(i, big.data());
+        EPI_HIP(hipMemcpy(arena.as<uint8_t>() + kept[k0 + i].aoff, big.data(), big.size(), hipMemcpyHostToDevice));
+        i++;
+        continue;
+      }
+      const int64_t a0 = kept[k0 + i].aoff;
+      EPI_TRY(parallel_ranges(KT, j - i, "epi_preprocess_bam", [&](size_t lo, size_t hi) -> int {
+        for (size_t x = i + lo; x < i + hi; x++) fill(x, st + (kept[k0 + x].aoff - a0));
+        return EPI_OK;
+      }));
+      EPI_TRY(stage_send(eng, stage_k, arena.as<uint8_t>() + a0, bytes));
+      stage_k ^= 1;
+      i = j;
+    }
+#else
+    (void)k0; (void)stage_k;
+#endif
+    arena_used += wbytes;
+    t_upload += tnow() - t1;
+    return EPI_OK;
+  };
+  size_t total_inflated = 0;
+  for (const Block &b : blocks) total_inflated += b.ulen;
+
   // ---- the windows ----
   for (bool final = blocks.empty(); ;) {
     size_t b1 = bi, add = 0;
@@ -1136,7 +1320,10 @@ static int preprocess_impl(const char *path, const epi_bam_options *opt_in, epi_
     while (b1 < blocks.size() && (b1 == bi || add + blocks[b1].ulen <= window)) { blocks[b1].upos = carry + add; add += blocks[b1].ulen; b1++; }
     final = b1 == blocks.size();
     buf.resize(carry + add);
+    double tw = tnow();
     EPI_TRY(bgzf_inflate_range(file.p, blocks, bi, b1, buf.data(), opt.nthreads));
+    t_inflate += tnow() - tw;
+    tw = tnow();
     bi = b1;
     size_t p = hdr_end;
     if (!header_done) {                                      // BAM header: magic, text, reference names
@@ -1229,6 +1416,7 @@ static int preprocess_impl(const char *path, const epi_bam_options *opt_in, epi_
       if (bad) return fail(EPI_ERR_ARG, "corrupt BAM record");
     }
     if (final && p != buf.size()) return fail(EPI_ERR_ARG, "truncated BAM record");
+    t_parse += tnow() - tw;
     const size_t KT = opt.nthreads > 1 ? (size_t)(opt.nthreads > 16 ? 16 : opt.nthreads) : 1;
     if (!checked) {
       if (recs.size() < 1024 && !final) { carry = buf.size(); continue; }   // .checkBam looks at the first 1024 records
@@ -1263,9 +1451,16 @@ static int preprocess_impl(const char *path, const epi_bam_options *opt_in, epi_
       if (!tXG && tZS) return fail(EPI_ERR_ARG, "No XG tags found (though ZS tags are there)! BSMAP alignment? If so, make methylation calls using epialleleR::callMethylation. Exiting");
       if (!tXM && tXG) return fail(EPI_ERR_ARG, "No XM tags found! Was methylation called successfully? If not, make methylation calls using epialleleR::callMethylation. Exiting");
       if (!tMM && !(tXG && tXM)) return fail(EPI_ERR_ARG, "No known methylation tags found! Exiting");
-      if (paired && !sorted) return fail(EPI_ERR_ARG, "BAM file seems to be paired-end but not sorted by name! Please sort using 'samtools sort -n -o out.bam in.bam'. Exiting");
+      if (paired && !sorted && !anyorder) return fail(EPI_ERR_ARG, "BAM file seems to be paired-end but not sorted by name! Please sort using 'samtools sort -n -o out.bam in.bam'. Exiting");
       if (opt.paired >= 0 && (opt.paired != 0) != paired) return fail(EPI_ERR_ARG, "Expected endness is different from detected! Exiting");
       checked = true;
+      asm_mode = anyorder && paired && !tMM;
+#ifndef EPI_HOST_ONLY
+      if (asm_mode) {
+        EPI_HIP(hipSetDevice(eng->device));
+        EPI_TRY(arena.ensure(total_inflated));
+      }
+#endif
     } else if (genome) {
       const double t0 = tnow();
       EPI_TRY(call_select(recs.begin(), recs.size(), tag, names, lens, KT, "epi_preprocess_bam", CS));
@@ -1273,7 +1468,7 @@ static int preprocess_impl(const char *path, const epi_bam_options *opt_in, epi_
     }
     // paired-end: the records of the window's last QNAME wait for the next window (their mate may be in it)
     size_t r_end = recs.size();
-    if (!final && paired && !tMM && r_end > 0) {
+    if (!final && paired && !tMM && !asm_mode && r_end > 0) {
       const char *lastq = recs[r_end - 1].qname;
       while (r_end > 0 && strcmp(recs[r_end - 1].qname, lastq) == 0) r_end--;
       if (r_end == 0) { carry = buf.size(); continue; }      // one template fills the window: read on
@@ -1293,7 +1488,8 @@ static int preprocess_impl(const char *path, const epi_bam_options *opt_in, epi_
 #endif
       t_call += tnow() - t0;
     }
-    EPI_TRY(pack_window(r_end));
+    if (asm_mode) EPI_TRY(collect_window(r_end));
+    else EPI_TRY(pack_window(r_end));
     nrecs_total += r_end;
     const size_t keep_from = r_end < recs.size() ? roff[r_end] : p;
     carry = buf.size() - keep_from;
@@ -1302,10 +1498,55 @@ static int preprocess_impl(const char *path, const epi_bam_options *opt_in, epi_
     recs.clear();
     if (final) break;
   }
+  // mates = "anywhere": every template's records are known now.  Each one's records go in merge order (flag & 0xC0, then
+  // file order: READ1 before READ2), the first gives rname, start, width and strand, and the rest may widen it -- pack_pe's
+  // rules and errors on G(F), without touching a byte (the kernel merges them once the rows have their places).
+  std::vector<AsmRec> arec;                                 // kept records in merge order, template after template
+  std::vector<int64_t> tpl_lo;                              // per template: its first record in arec (n + 1 entries)
+  const double t_g0 = tnow();
+  if (asm_mode) {
+    const size_t G = qmap.size(), NK = kept.size();
+    tpl_lo.assign(G + 1, 0);
+    for (const Kept &k : kept) tpl_lo[k.gid + 1]++;
+    for (size_t g = 0; g < G; g++) tpl_lo[g + 1] += tpl_lo[g];
+    std::vector<uint32_t> mo(NK);                           // kept records by template, in file order (a stable counting sort)
+    {
+      std::vector<int64_t> cur(tpl_lo.begin(), tpl_lo.end() - 1);
+      for (size_t i = 0; i < NK; i++) mo[(size_t)cur[kept[i].gid]++] = (uint32_t)i;
+    }
+    arec.resize(NK);
+    P.rname.reserve(G); P.strand.reserve(G); P.start.reserve(G); len.reserve(G);
+    for (size_t g = 0; g < G; g++) {
+      uint32_t *m = mo.data() + tpl_lo[g], nm = (uint32_t)(tpl_lo[g + 1] - tpl_lo[g]);
+      for (uint32_t a = 1; a < nm; a++)                     // (stable insertion sort by flag & 0xC0: a template has few records)
+        for (uint32_t b = a; b > 0 && kept[m[b]].cls < kept[m[b - 1]].cls; b--) std::swap(m[b], m[b - 1]);
+      const Kept &f = kept[m[0]];
+      const int t_start = f.pos < f.mpos ? f.pos : f.mpos;                                     // :92-93
+      if (f.isize == INT32_MIN) return fail(EPI_ERR_ARG, "corrupt BAM record %s: template length", qmap.name((uint32_t)g));
+      int t_width = f.isize < 0 ? -f.isize : f.isize;                                          // :94
+      for (uint32_t a = 0; a < nm; a++) {
+        const Kept &k = kept[m[a]];
+        if (k.pos < t_start) return fail(EPI_ERR_ARG, "corrupt BAM record %s: starts before its template", qmap.name((uint32_t)g));
+        const uint32_t dest0 = (uint32_t)(k.pos - t_start), dest_end = dest0 + k.rspan;     // :118 (apply_cigar's sum)
+        if (dest_end > 0x7FFFFFFFu) return fail(EPI_ERR_ARG, "corrupt BAM record %s: template too wide", qmap.name((uint32_t)g));
+        if (t_width < (int)dest_end) t_width = (int)dest_end;                                  // :151
+        AsmRec &x = arec[(size_t)tpl_lo[g] + a];
+        x.arena_off = k.aoff; x.dest0 = (int32_t)dest0; x.n_cig = k.n_cig; x.l_seq = k.l_seq; x.pad = 0;
+      }
+      P.rname.push_back(f.tid + 1);                                                            // :61-69
+      P.strand.push_back(f.strand);
+      P.start.push_back(t_start + trim5 + 1);
+      const int keep = t_width - (trim5 + trim3);
+      len.push_back(keep > 0 ? keep : 0);
+    }
+    std::vector<Kept>().swap(kept);
+  }
   if (!tMM && paired && P.rname.empty()) {                  // the reference pushes its (never opened) template all the same, :155
     P.rname.push_back(1); P.strand.push_back(0); P.start.push_back(trim5 + 1); src.push_back(nullptr); len.push_back(0);
+    if (asm_mode) tpl_lo.push_back(tpl_lo.back());
   }
   buf.release();
+  const double t_group = tnow() - t_g0;
 
   lap("pack");
   if (timing && genome) fprintf(stderr, "[bam] (of which call selection, inputs and GPU %.3f s)\n", t_call);
@@ -1377,7 +1618,7 @@ static int preprocess_impl(const char *path, const epi_bam_options *opt_in, epi_
     auto run = [&](size_t k) {
       for (size_t i = n * k / K; i < n * (k + 1) / K; i++) {
         const uint32_t t = order[i];
-        if (len[t]) memcpy(out->xm + out->off[i], src[t], (size_t)len[t]);
+        if (len[t] && !asm_mode) memcpy(out->xm + out->off[i], src[t], (size_t)len[t]);
         out->rname[i] = P.rname[t]; out->strand[i] = P.strand[t]; out->start[i] = P.start[t];
       }
     };
@@ -1385,6 +1626,31 @@ static int preprocess_impl(const char *path, const epi_bam_options *opt_in, epi_
     for (size_t k = 1; k < K; k++) th.emplace_back(run, k);
     run(0);
     for (auto &t : th) t.join();
+  }
+  if (asm_mode) {                                           // the rows, merged on the GPU in their output slots
+#ifndef EPI_HOST_ONLY
+    std::vector<AsmTpl> tpl(n);
+    int64_t qbytes = 0;
+    for (size_t i = 0; i < n; i++) {
+      const uint32_t t = order[i];
+      AsmTpl &x = tpl[i];
+      x.out_off = out->off[i]; x.rec_lo = tpl_lo[t]; x.nrec = (int32_t)(tpl_lo[t + 1] - tpl_lo[t]); x.keep = len[t];
+      x.q_off = 0;
+      if (len[t] > kAsmLdsWidth) { x.q_off = qbytes; qbytes += len[t]; }
+    }
+    const double t0 = tnow();
+    EPI_HIP(hipStreamSynchronize(eng->copy_stream));         // (the arena's last uploads)
+    t_upload += tnow() - t0;
+    const uint8_t q0 = (uint8_t)(opt.min_baseq - (opt.min_baseq > 0 ? 1 : 0));   // src/rcpp_read_bam.cpp:30,57
+    double t_kernel = 0, t_d2h = 0;
+    EPI_TRY(assemble_templates(eng, arena.as<uint8_t>(), tpl.data(), (int64_t)n, arec.data(), (int64_t)arec.size(), q0,
+                               trim5, w, qbytes, out->xm, &t_kernel, &t_d2h));
+    if (timing)
+      fprintf(stderr, "[bam] (anywhere: inflate %.3f s, parse %.3f s, pairing %.3f s, upload %.3f s, grouping %.3f s, "
+                      "kernel %.3f s, D2H %.3f s)\n", t_inflate, t_parse, t_pair, t_upload, t_group, t_kernel, t_d2h);
+#else
+    (void)t_group;
+#endif
   }
   // 0xFB padding up to the 16-byte boundary the kernels may read to, plus a little (a buffer pinned ahead can be much
   // larger than the templates: its tail stays untouched and is not part of xm_capacity)

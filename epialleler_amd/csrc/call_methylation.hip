@@ -3,9 +3,9 @@
 //
 // Two kernels, one wavefront per record in both; the lanes span query positions, 64 at a time, so a read of several
 // kilobases is spread over the wave like a short one:
-//   k_call_refspace  the CIGAR, 64 ops at a time: query and reference lengths are scanned across the lanes (DPP),
-//                    the prefixes go to LDS, and each lane finds the op of its query position by a 6-step search over
-//                    them.  M / = copy the genome base, X / I / S give N, D / N move the reference only, H / P / B do
+//   k_call_refspace  the CIGAR, 64 ops at a time (wave_cigar_walk, cigar_walk.hpp): query and reference lengths are
+//                    scanned across the lanes (DPP), the prefixes go to LDS, and each lane finds the op of its query
+//                    position by a 6-step search over them.  M / = copy the genome base, X / I / S give N, D / N move the reference only, H / P / B do
 //                    nothing.  Output: the record's reference in query space as 3-bit codes, with two bases of halo on
 //                    each side (N beyond the contig), in a scratch array.
 //   k_call_xm        per query base: the triad at offsets 0..2 (forward table, strand C/T) or -2..0 (reverse table,
@@ -18,6 +18,7 @@
 // has checked every record it hands over: the contig exists, the CIGAR consumes exactly l_seq query bases and the
 // aligned span lies inside the contig; the kernels still keep every genome read inside its contig.
 #include "common.hpp"
+#include "cigar_walk.hpp"
 
 namespace epi {
 namespace {
@@ -35,20 +36,10 @@ __device__ __forceinline__ uint8_t ctx_reverse_dev(uint32_t b0, uint32_t b1, uin
   return b1 == 3 ? 'z' : b0 == 3 ? 'x' : 'h';
 }
 
-__device__ __forceinline__ uint32_t lane_read(uint32_t v, int lane) { return (uint32_t)__builtin_amdgcn_readlane((int)v, lane); }
-
-// LDS written by some lanes of the wave and read by others: keep the compiler's order and wait for the writes
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 __global__ __launch_bounds__(256) void k_call_refspace(const CallRec *__restrict__ recs, int64_t nrec,
                                                        const uint32_t *__restrict__ cigar, const uint8_t *__restrict__ gseq,
                                                        const int64_t *__restrict__ goff, uint8_t *__restrict__ ref) {
-  __shared__ uint32_t s_qe[kWaves][64], s_rs[kWaves][64];
-  __shared__ uint8_t s_op[kWaves][64];
+  __shared__ CigarLds s_cig[kWaves];
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int64_t r = (int64_t)blockIdx.x * kWaves + w;
   if (r >= nrec) return;                              // (whole waves: no workgroup barrier below)
@@ -57,37 +48,11 @@ __global__ __launch_bounds__(256) void k_call_refspace(const CallRec *__restrict
   const uint8_t *g = gseq + g0;
   uint8_t *out = ref + c.xm_off + 4 * r;              // out[2 + q]: query base q; out[0, 1] and out[l_seq + 2, 3]: halo
   auto base_at = [&](int64_t gi) -> uint8_t { return (uint8_t)((gi >= 0 && gi < glen ? g[gi] : 'N') & 7); };
-  uint32_t qcarry = 0, rcarry = 0;
-  for (int32_t o0 = 0; o0 < c.n_cig; o0 += 64) {
-    const int32_t o = o0 + lane;
-    uint32_t op = 9, len = 0;                           // (lanes past the last op: 'B', which consumes nothing)
-    if (o < c.n_cig) { const uint32_t v = cigar[c.cig_off + o]; op = v & 15; len = v >> 4; }
-    const uint32_t ql = (op == 0 || op == 1 || op == 4 || op == 7 || op == 8) ? len : 0;
-    const uint32_t rl = (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) ? len : 0;
-    const uint32_t qe = qcarry + wave_scan_u32(ql), re = rcarry + wave_scan_u32(rl);
-    s_qe[w][lane] = qe;
-    s_rs[w][lane] = re - rl;
-    s_op[w][lane] = (uint8_t)op;
-    wave_lds_sync();
-    const uint32_t qend = lane_read(qe, 63);
-    for (uint32_t q0 = qcarry; q0 < qend; q0 += 64) {
-      const uint32_t q = q0 + lane;
-      if (q < qend && q < (uint32_t)c.l_seq) {
-        int k = 0;                                      // ops of this group that end at or before q
-#pragma unroll
-        for (int s = 32; s > 0; s >>= 1) k += s_qe[w][k + s - 1] <= q ? s : 0;
-        const uint32_t qs = k > 0 ? s_qe[w][k - 1] : qcarry, opk = s_op[w][k];
-        uint8_t b = 'N' & 7;
-        if (opk == 0 || opk == 7) b = base_at((int64_t)c.pos + s_rs[w][k] + (q - qs));
-        out[2 + q] = b;
-      }
-    }
-    qcarry = qend;
-    rcarry = lane_read(re, 63);
-    wave_lds_sync();                                    // (the next group overwrites the prefixes)
-  }
+  const uint32_t rlen = wave_cigar_walk(cigar + c.cig_off, c.n_cig, c.l_seq, s_cig[w], lane, [&](uint32_t q, uint32_t op, uint32_t rq) {
+    out[2 + q] = (op == 0 || op == 7) ? base_at((int64_t)c.pos + rq) : (uint8_t)('N' & 7);
+  });
   if (lane < 4) {
-    const int64_t gi = lane < 2 ? (int64_t)c.pos - 2 + lane : (int64_t)c.pos + rcarry + (lane - 2);
+    const int64_t gi = lane < 2 ? (int64_t)c.pos - 2 + lane : (int64_t)c.pos + rlen + (lane - 2);
     out[lane < 2 ? lane : c.l_seq + lane] = base_at(gi);
   }
 }

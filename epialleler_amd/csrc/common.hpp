@@ -274,6 +274,38 @@ int call_methylation_window(epi_engine *eng, epi_genome *g, CallWork &wk, const 
                             const uint32_t *cigar, int64_t ncig, const uint8_t *seq, int64_t nseq, int64_t nxm,
                             CallForm form, uint8_t *xm_out);
 
+// assemble_templates.hip: preprocessBam(mates = "anywhere").  The reader uploads every kept record's CIGAR ops, packed
+// query bytes (nt16 << 4) | ctx and QUAL to a device arena (at AsmRec::arena_off: 4 * n_cig bytes of ops, l_seq packed
+// bytes, l_seq qualities); at the end of the file it knows each template's records in merge order and its output row,
+// and the kernel merges them there.
+struct AsmRec {
+  int64_t arena_off;   // 4-byte aligned
+  int32_t dest0;       // reference offset of the record's first aligned base from the template's start
+  int32_t n_cig, l_seq;
+  int32_t pad;
+};
+static_assert(sizeof(AsmRec) == 24, "AsmRec layout");
+struct AsmTpl {
+  int64_t out_off;     // the row's first byte in the output
+  int64_t rec_lo;      // its records: AsmRec [rec_lo, rec_lo + nrec), in merge order
+  int64_t q_off;       // rows wider than kAsmLdsWidth: their qualities in the global scratch (else unused)
+  int32_t nrec;
+  int32_t keep;        // row length: the template's width less both trims (0 when the trims cover it)
+};
+static_assert(sizeof(AsmTpl) == 32, "AsmTpl layout");
+// Rows longer than this are merged in global memory (the row itself and a quality scratch) instead of LDS.
+constexpr int kAsmLdsWidth = 2048;
+// rows [0, ntpl) -> nbytes bytes at h_out (pinned or pageable); qbytes: the scratch the wide rows need.  The arena must
+// be complete (the caller has synchronised its uploads).  *t_kernel, *t_d2h: seconds spent (synchronised).
+int assemble_templates(epi_engine *eng, const uint8_t *d_arena, const AsmTpl *tpl, int64_t ntpl, const AsmRec *recs,
+                       int64_t nrec, uint8_t q0, int32_t trim5, int64_t nbytes, int64_t qbytes, uint8_t *h_out,
+                       double *t_kernel, double *t_d2h);
+// The engine's two pinned staging buffers (engine.hip), for a producer that writes its bytes straight into them:
+// stage_buffer waits until buffer k (0 or 1) is free and returns it; stage_send queues its first `bytes` to d_dst on
+// the engine's copy stream.  The caller synchronises the copy stream after its last send.
+int stage_buffer(epi_engine *eng, int k, uint8_t **buf, size_t *cap);
+int stage_send(epi_engine *eng, int k, void *d_dst, size_t bytes);
+
 // util kernels (util.hip)
 int scan_exclusive_u32(const uint32_t *d_in, uint32_t *d_out, int64_t n, uint32_t *d_total,
                        DevBuf &tmp, hipStream_t s);

@@ -347,6 +347,20 @@ static int ensure_staging(epi_engine *eng) {
   return EPI_OK;
 }
 
+int stage_buffer(epi_engine *eng, int k, uint8_t **buf, size_t *cap) {
+  EPI_TRY(ensure_staging(eng));
+  EPI_HIP(hipEventSynchronize(eng->pinned_done[k & 1]));
+  *buf = static_cast<uint8_t *>(eng->pinned[k & 1]);
+  *cap = eng->pinned_bytes;
+  return EPI_OK;
+}
+
+int stage_send(epi_engine *eng, int k, void *d_dst, size_t bytes) {
+  if (bytes) EPI_HIP(hipMemcpyAsync(d_dst, eng->pinned[k & 1], bytes, hipMemcpyHostToDevice, eng->copy_stream));
+  EPI_HIP(hipEventRecord(eng->pinned_done[k & 1], eng->copy_stream));
+  return EPI_OK;
+}
+
 // A large pageable destination that has not been touched yet (a column the caller has just allocated) is faulted in by the
 // copy below: with transparent huge pages in `madvise` mode the hint turns ~40 000 4 KiB faults of a 10 M-row table into ~80.
 static void advise_huge(void *p, size_t n) {

@@ -248,6 +248,30 @@ int epi_preprocess_bam_genome(struct epi_engine *eng /* NULL: default */, const 
                               const epi_bam_options *opt /* NULL: R defaults */, epi_genome *g, epi_templates *out,
                               int64_t *ncalled);
 
+/* preprocessBam(mates = "anywhere"): paired-end input whose mates lie anywhere in the file (coordinate-sorted, DRAGEN's
+ * default output, or any other order).  The contract is
+ *     epi_preprocess_bam_anyorder(eng, F, opt, out)  ==  epi_preprocess_bam(G(F), opt, out)
+ * for the xm bytes, off, rname, strand, start, target names, paired and nrecs, where G(F) is F with its records regrouped:
+ *  - records with one QNAME form one group; groups appear in the order of each QNAME's first KEPT record in F (kept: none
+ *    of the skip flags, 4 and 8 included, flag 2 set, mapq >= min_mapq, usable XG and XM -- what the paired-end packer
+ *    uses).  Groups without a kept record produce nothing.  G keeps every record, so nrecs counts all of them.
+ *  - within a group, records are ordered by flag & 0xC0 ascending (READ1 before READ2, as samtools sort -n puts them),
+ *    ties in their order in F.
+ * That fixes the template merge's order: the first record gives rname, start (min(pos, mpos)), width (|isize|) and
+ * strand; in an overlap the strictly higher quality wins (a tie keeps the earlier record's byte); the template widens
+ * over dovetails and trailing D / N.  Rows with equal (rname, start) keep that order through the stable sort.
+ *  - .checkBam's checks come from the first 1024 records of F as in epi_preprocess_bam (paired detection, tags, empty
+ *    file, endness), except the name-sorted check, which is skipped.  Single-end and long-read (MM/ML) input gives
+ *    exactly epi_preprocess_bam's result.
+ *  - Errors carry the messages epi_preprocess_bam gives on G(F); with several bad records another one may be named.
+ * Memory: device memory for the kept records' packed inputs (CIGAR ops, one packed byte and one quality per base;
+ * allocated once, sized by the file's inflated bytes) plus, while the rows are merged, the output bytes and the
+ * per-record and per-template tables; host memory for one window of inflated records (window_kib) plus ~48 bytes per kept
+ * record and one QNAME key per template.  The rows are merged on the GPU (assemble_templates.hip).  engine NULL: the
+ * default engine (no device: EPI_ERR_NODEVICE before the file is read; there is no CPU path).  Without a genome only. */
+int epi_preprocess_bam_anyorder(struct epi_engine *eng /* NULL: default */, const char *path,
+                                const epi_bam_options *opt /* NULL: R defaults */, epi_templates *out);
+
 /* ---- report writer (.writeReport, R/internal.R:274-287) -------------------
  * The table as a tab-separated file with a header line, what data.table::fwrite(report, quote=FALSE, sep="\t",
  * col.names=TRUE, compress=if (gzip) "gzip" else "none") writes: integers in decimal, factor columns as their
