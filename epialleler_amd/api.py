@@ -312,21 +312,39 @@ def _ptr_array(tensors):
     return arr
 
 
+def _cx_columns(bam, ctx, report):
+    """The six int32 columns of a CX report.  They are allocated before the report runs, as many rows as the last report
+    on this batch with these contexts had (the row count depends on the rows and the contexts alone), so that the tile
+    kernel can write them itself; `report(cols, cap, nrow, written)` runs it.  When it could not (first report, pile-ups,
+    ...) the rows come from the library's row pool as before."""
+    torch = _torch()
+    lib = _lib.load()
+    b = bam.batch()
+    dev = "cuda:%d" % bam.device
+    cap = C.c_int64(-1)
+    _lib.check(lib.epi_batch_cx_report_capacity(b, _lib.enc(ctx), C.byref(cap)))
+    cap = max(cap.value, 0)
+    buf = torch.empty((6, cap), dtype=torch.int32, device=dev)    # one allocation, before the kernels are queued
+    nrow, written = C.c_int64(0), C.c_int(0)
+    report(_ptr_array(buf.unbind(0)) if cap else None, cap, nrow, written)
+    n = nrow.value
+    if not written.value:
+        if n > cap:
+            buf = torch.empty((6, n), dtype=torch.int32, device=dev)
+        if n:
+            _lib.check(lib.epi_batch_cx_fetch_dev(b, _ptr_array(buf.unbind(0)), _stream(bam.device)))
+    return [c[:n] for c in buf.unbind(0)]
+
+
 def rcpp_cx_report(df, pass_, ctx, as_device=False):
     """src/rcpp_cx_report.cpp:34-159 -> columns rname,strand,pos,context,meth,unmeth (int32)."""
-    torch = _torch()
     lib = _lib.load()
     bam = _as_bam(df)
     b = bam.batch()
-    dev = "cuda:%d" % bam.device
     p = _pass_tensor(bam, pass_)
-    nrow = C.c_int64(0)
-    _lib.check(lib.epi_batch_cx_report_dev(b, C.c_void_p(p.data_ptr()) if p is not None and bam.n else None,
-                                           _lib.enc(ctx), _stream(bam.device), C.byref(nrow)))
-    n = nrow.value
-    cols = list(torch.empty((6, n), dtype=torch.int32, device=dev).unbind(0))   # one allocation: the GPU idles meanwhile
-    if n:
-        _lib.check(lib.epi_batch_cx_fetch_dev(b, _ptr_array(cols), _stream(bam.device)))
+    cols = _cx_columns(bam, ctx, lambda cols, cap, nrow, written: _lib.check(lib.epi_batch_cx_report_into_dev(
+        b, C.c_void_p(p.data_ptr()) if p is not None and bam.n else None, _lib.enc(ctx), cols, cap, _stream(bam.device),
+        C.byref(nrow), C.byref(written))))
     names = ("rname", "strand", "pos", "context", "meth", "unmeth")
     if not as_device:
         cols = [c.cpu().numpy() for c in cols]
@@ -344,15 +362,11 @@ def cytosine_report_fused(df, ctx_meth, ctx_unmeth, ooctx_meth, ooctx_unmeth, mi
     b = bam.batch()
     dev = "cuda:%d" % bam.device
     pass_out = torch.empty(max(bam.n, 1), dtype=torch.int32, device=dev) if return_pass else None
-    nrow = C.c_int64(0)
-    _lib.check(lib.epi_batch_cytosine_report_dev(
+    cols = _cx_columns(bam, ctx, lambda cols, cap, nrow, written: _lib.check(lib.epi_batch_cytosine_report_into_dev(
         b, _lib.enc(ctx_meth), _lib.enc(ctx_unmeth), _lib.enc(ooctx_meth), _lib.enc(ooctx_unmeth), int(min_n_ctx),
         float(min_ctx_meth_frac), float(max_ooctx_meth_frac), _lib.enc(ctx),
-        C.c_void_p(pass_out.data_ptr()) if pass_out is not None else None, _stream(bam.device), C.byref(nrow)))
-    n = nrow.value
-    cols = list(torch.empty((6, n), dtype=torch.int32, device=dev).unbind(0))
-    if n:
-        _lib.check(lib.epi_batch_cx_fetch_dev(b, _ptr_array(cols), _stream(bam.device)))
+        C.c_void_p(pass_out.data_ptr()) if pass_out is not None else None, cols, cap, _stream(bam.device),
+        C.byref(nrow), C.byref(written))))
     names = ("rname", "strand", "pos", "context", "meth", "unmeth")
     if not as_device:
         cols = [c.cpu().numpy() for c in cols]

@@ -162,6 +162,12 @@ struct epi_batch {
   epi::DevBuf mhlf_fold_slab;                  // call counters of tiles over 255 rows (kernels built without the LDS fold array)
   bool mhl_shared_fused = false;               // the lMHL slabs attached are in the fused kernel's layout (mhl_common.hpp)
   uint32_t cx_last_slot = 0, cx_last_ovf = 0;  // layout of the last CX report (the sharded second half emits into it)
+  // CX reports written straight into the caller's columns (cx_report.hip, direct mode): the tile offsets and row counts
+  // of the last pool report, for its context mask (key = mask | 1 << 31; 0: none), tile size and tile count
+  epi::DevBuf cx_prev_off, cx_prev_cnt;
+  uint32_t cx_prev_key = 0;
+  int32_t cx_prev_T = 0, cx_prev_nt = 0;
+  int64_t cx_prev_nrow = 0;
   // One host synchronisation for a sharded CX report (comm.hip): with cx_defer set the first half queues its kernels and
   // returns without reading anything back; the second half reads and checks everything at once.  Allowed only when an
   // earlier report on this (immutable) batch and tile size found no ultra-deep tile that the host would have to finish
@@ -335,6 +341,8 @@ struct Options {
   int cx_slot = -1;          // EPIHIP_CX_SLOT       pool rows per tile slot of the CX report (-1: adaptive)
   int cx_lean = 1;           // EPIHIP_CX_LEAN=0     the general (u16-folding) CX kernel for every tile
   int cx_walk = 0;           // EPIHIP_CX_WALK=K     timing builds with -DEPI_CX_WALK_BUILD only: K consecutive tiles per workgroup of the lean CX kernel
+  int cx_direct = 1;         // EPIHIP_CX_DIRECT=0   CX reports through the row pool and the gather even where the tile kernel could
+                             //                      write the caller's columns
   int heavy_rows = 0;        // EPIHIP_HEAVY_ROWS    candidate rows above which a tile is split / set aside (0: default)
   int tile_hint = 1;         // EPIHIP_TILE_HINT=0   tile index counted and scanned by every call
   int realign = 16;          // EPIHIP_REALIGN=0/4/8/16 epi_batch_upload / epi_batch_realign: keep the rows back to back / start them at

@@ -38,7 +38,9 @@
 //    second visit is an L2 hit thanks to the XCD-aware tile order).
 // After a barrier the workgroup prefix-sums the coverage array, lists the cells with any call (ballot ranks), applies
 // the rule and writes (key, meth, unmeth) in position order into the tile's slot of the row pool; k_cx_gather places
-// the pool rows in the final table.  Ultra-deep tiles are split over many workgroups through a slab in HBM; tiles
+// the pool rows in the final table.  When the batch keeps the tile offsets of an earlier report with the same contexts and
+// every tile is finished inside the launch (direct mode), the emit writes the final columns itself.  Ultra-deep tiles are
+// split over many workgroups through a slab in HBM; tiles
 // shared with other ranks of a sharded run hand over the same slab for the RCCL all-reduce.
 #include "common.hpp"
 #include "tile_common.hpp"
@@ -107,6 +109,15 @@ struct Cx2Args {
   uint32_t *dbg;                          // check build only (EPI_CHECK): first index violation; null in the product
   int64_t nrows;                          // rows of the batch (check build)
   int walk;                               // walking lean kernel: consecutive tiles per workgroup
+  // Direct mode (prev_off != null): the emit writes the final columns rname, strand, pos, context, meth, unmeth itself --
+  // no pool, no scan, no gather.  A tile's first row is where the last pool report on this batch with the same contexts
+  // put it: a tile's row count depends on the rows and the contexts alone (thresholds change M, not which cells pass the
+  // rule, rcpp_cx_report.cpp:63-71).  A tile whose count differs writes nothing and is counted in *mismatch (the host
+  // then reruns the report through the pool).
+  const uint32_t *prev_off, *prev_nrow;   // first output row / row count of every tile
+  uint32_t *mismatch;
+  int32_t *out[6];                        // the caller's columns ...
+  int64_t out_cap;                        // ... and the rows they hold
 };
 
 // LEAN: no position of the batch is covered by more than 255 rows (RowStats::deep == 0, tiles.hip), so the u8 counters
@@ -609,6 +620,11 @@ __device__ __forceinline__ uint32_t cx_pool_reserve(const Cx2Args &a, int tile, 
   return a.ovf_base + o;
 }
 
+// A tile that emits nothing in this launch (set aside, handed over): in direct mode its recorded count must be 0.
+__device__ __forceinline__ void cx_direct_none(const Cx2Args &a, int tile, uint32_t tid) {
+  if (a.prev_off && tid == 0 && a.prev_nrow[tile] != 0u) atomicAdd(a.mismatch, 1u);
+}
+
 // Where the emit phase reads a tile's sums from: LDS (u16 pairs, packed coverage) ...
 template <int T, int NP> struct CxSrcLds {
   const uint32_t *wide, *cov;             // cov already prefix-summed
@@ -731,6 +747,36 @@ __device__ __forceinline__ void cx2_emit(const Cx2Args &a, int tile, const SRC &
   }
   if (lane == 0) s_scan[wave] = carry;
   __syncthreads();
+  if (a.prev_off) {
+    // direct mode: the rows straight into the caller's columns at the recorded offset (the arithmetic of k_cx_gather)
+    if (tid == 0) {
+      uint32_t acc = 0;
+      for (int w = 0; w < NW; w++) { const uint32_t t = s_scan[w]; s_scan[w] = acc; acc += t; }
+      const uint32_t base = a.prev_off[tile];
+      const bool good = acc == a.prev_nrow[tile] && (int64_t)base + acc <= a.out_cap;
+      if (!good) atomicAdd(a.mismatch, 1u);
+      s_scan[NW + 1] = good ? base : 0xFFFFFFFFu;
+    }
+    __syncthreads();
+    const uint32_t base = s_scan[NW + 1];
+    if (base != 0xFFFFFFFFu) {
+      const Tile td = a.tiles[tile];
+      const uint32_t w0 = base + s_scan[wave];
+#pragma unroll
+      for (int jj = 0; jj < IT; jj++) {
+        if (ok[jj]) {
+          const uint32_t o = w0 + off[jj];
+          a.out[0][o] = td.rname;
+          a.out[1][o] = 1 + (int32_t)((key[jj] >> 3) & 1u);
+          a.out[2][o] = (int32_t)(td.pos0 + (int64_t)(key[jj] >> 4));
+          a.out[3][o] = (int32_t)(key[jj] & 7u);
+          a.out[4][o] = (int32_t)me[jj];
+          a.out[5][o] = (int32_t)un[jj];
+        }
+      }
+    }
+    return;
+  }
   if (tid == 0) {
     uint32_t acc = 0;
     for (int w = 0; w < NW; w++) { const uint32_t t = s_scan[w]; s_scan[w] = acc; acc += t; }
@@ -934,6 +980,7 @@ __device__ __forceinline__ bool cx2_tile(const Cx2Args &a, int tile, const Tile 
       a.tile_nrow[tile] = 0;
       a.tile_base[tile] = 0;
     }
+    cx_direct_none(a, tile, L.tid);
     return false;
   }
   if constexpr (LEAN) {
@@ -952,6 +999,7 @@ __device__ __forceinline__ bool cx2_tile(const Cx2Args &a, int tile, const Tile 
       __syncthreads();
       if (*s_flag) {
         if (L.tid == 0) { a.deep_list[atomicAdd(a.deep_count, 1u)] = (uint32_t)tile; a.tile_nrow[tile] = 0; a.tile_base[tile] = 0; }
+        cx_direct_none(a, tile, L.tid);
         return false;
       }
     }
@@ -962,10 +1010,11 @@ __device__ __forceinline__ bool cx2_tile(const Cx2Args &a, int tile, const Tile 
     // shared with another rank: hand the raw sums over (a carried-in coverage is part of the first difference)
     cx2_dump_slab<T, NP, LEAN, WG, PAD>(L, a.slab + (int64_t)td.slot * (kCxPlanes * T));
     if (L.tid == 0) { a.tile_nrow[tile] = 0; a.tile_base[tile] = 0; }
+    cx_direct_none(a, tile, L.tid);
     if constexpr (PAD > 0) { __syncthreads(); cx2_prefix<T, WG>(L.cov, s_scan, L.tid); }    // (the walk goes on from the summed coverage)
     return true;
   }
-  if (EPI_CX_ABLATE & 16) { if (L.tid == 0) { a.tile_nrow[tile] = 0; a.tile_base[tile] = 0; } return true; }
+  if (EPI_CX_ABLATE & 16) { if (L.tid == 0) { a.tile_nrow[tile] = 0; a.tile_base[tile] = 0; } cx_direct_none(a, tile, L.tid); return true; }
   // (a list-free emit -- every thread ruling on its own 8 cells, two barriers instead of four -- measured 1-2 % slower)
   cx2_prefix<T, WG>(L.cov, s_scan, L.tid);
   if constexpr (LEAN) {
@@ -1225,6 +1274,7 @@ __global__ __launch_bounds__(CX_WG, 8) void k_cxp_tiles(Cx2Args a, int ntiles, i
       a.tile_nrow[tile] = 0;
       a.tile_base[tile] = 0;
     }
+    cx_direct_none(a, tile, threadIdx.x);
     return;
   }
   __syncthreads();
@@ -1235,9 +1285,14 @@ __global__ __launch_bounds__(CX_WG, 8) void k_cxp_tiles(Cx2Args a, int ntiles, i
   if (td.slot >= 0) {                                     // shared with another rank: hand the sums over
     cxp_dump_slab(a, cnt, np, a.slab + (int64_t)td.slot * (kCxPlanes * CXP_T));
     if (threadIdx.x == 0) { a.tile_nrow[tile] = 0; a.tile_base[tile] = 0; }
+    cx_direct_none(a, tile, threadIdx.x);
     return;
   }
-  if (EPI_CX_ABLATE & 16) { if (threadIdx.x == 0) { a.tile_nrow[tile] = 0; a.tile_base[tile] = 0; } return; }   // timing builds: no emit
+  if (EPI_CX_ABLATE & 16) {                               // timing builds: no emit
+    if (threadIdx.x == 0) { a.tile_nrow[tile] = 0; a.tile_base[tile] = 0; }
+    cx_direct_none(a, tile, threadIdx.x);
+    return;
+  }
   cx2_emit<CXP_T, 3>(a, tile, cxp_source(a, cnt), s_scan, s_list);
 }
 
@@ -1562,12 +1617,28 @@ static bool make_fused_lut(const CxThreshold &t, uint32_t ctx_of_plane, int np, 
 // The CX report on a resident batch.  thr != null: thresholding fused into the tile kernel when the batch allows it
 // (the report's one context is the thresholding context, reads of at most ~5 kb), else a separate pass of the
 // per-read kernel first.
-static int cx_report_impl(epi_batch *b, const int32_t *d_pass, const CxThreshold *thr, int32_t *d_pass_out, const char *ctx,
-                          hipStream_t s, int64_t *nrow_out) {
-  *nrow_out = 0;
-  b->last_kind = 0;
+// Direct mode: rows of the report whose tile offsets the batch keeps (cx_prev_*) if it had these contexts, else -1.
+static int64_t cx_recorded_nrow(const epi_batch *b, uint32_t ctx_mask) {
+  return b->cx_prev_key == (ctx_mask | 0x80000000u) ? b->cx_prev_nrow : -1;
+}
+static uint32_t cx_ctx_mask(const char *ctx) {
   uint32_t ctx_mask = 0;                                   // rcpp_cx_report.cpp:88-91
   for (const unsigned char *c = reinterpret_cast<const unsigned char *>(ctx); *c; c++) ctx_mask |= 1u << ctx_to_idx(*c);
+  return ctx_mask;
+}
+
+// d_cols / cap (may be null / 0): the caller's six columns.  The tile kernel writes them itself (*written = 1) when the batch
+// keeps the tile offsets of an earlier report with these contexts and its rows fit, and every tile is finished inside the
+// launch -- no position covered by more than 255 rows (RowStats::deep == 0: no deep list, and a tile with many candidate
+// rows is worked in place, not set aside), not a sharded report; otherwise the row pool is filled for
+// epi_batch_cx_fetch_* as before, and its tile offsets are kept for the next report.
+static int cx_report_impl(epi_batch *b, const int32_t *d_pass, const CxThreshold *thr, int32_t *d_pass_out, const char *ctx,
+                          hipStream_t s, int64_t *nrow_out, int32_t *const *d_cols = nullptr, int64_t cap = 0,
+                          int *written = nullptr) {
+  *nrow_out = 0;
+  if (written) *written = 0;
+  b->last_kind = 0;
+  const uint32_t ctx_mask = cx_ctx_mask(ctx);
 
   Cx2Args a;
   memset(&a, 0, sizeof(a));
@@ -1677,6 +1748,7 @@ static int cx_report_impl(epi_batch *b, const int32_t *d_pass, const CxThreshold
   a.heavy_rows = 16384;
   if (options().heavy_rows > 0) a.heavy_rows = options().heavy_rows;   // test hook (EPIHIP_HEAVY_ROWS)
   if (a.heavy_rows > 16384) a.heavy_rows = 16384;          // u16 pairs and the packed coverage halves: a base adds at most 2
+  const int heavy_rows = a.heavy_rows;
   a.heavy_chunk = a.heavy_rows / 4 > 64 ? a.heavy_rows / 4 : 64;
   if (a.heavy_chunk > 256) a.heavy_chunk = 256;            // (a 20 000-row pile-up is then 80 work items, not 5)
   EPI_TRY(b->heavy_list.ensure((size_t)nt * 4));
@@ -1702,10 +1774,24 @@ static int cx_report_impl(epi_batch *b, const int32_t *d_pass, const CxThreshold
   a.dbg = b->diag.as<uint32_t>();
   EPI_HIP(hipMemsetAsync(a.dbg, 0, 32, s));
 #endif
+  const int64_t rec = cx_recorded_nrow(b, ctx_mask);
+  bool direct = d_cols && cap > 0 && cap <= 0x7FFFFFFF && rec >= 0 && rec <= cap && st.deep == 0 && nshared == 0 && a.walk == 0 &&
+                options().cx_direct;
+  for (int i = 0; direct && i < 6; i++) if (!d_cols[i]) direct = false;
+  if (direct && (b->cx_prev_T != T || b->cx_prev_nt != nt)) direct = false;
+  if (direct) {
+    a.prev_off = b->cx_prev_off.as<uint32_t>();
+    a.prev_nrow = b->cx_prev_cnt.as<uint32_t>();
+    a.mismatch = cursor;                                   // (misc[1]: the pool cursor, unused in direct mode)
+    for (int i = 0; i < 6; i++) a.out[i] = d_cols[i];
+    a.out_cap = cap;
+    a.heavy_rows = 0x7FFFFFFF;                             // worked in place: with deep == 0 no counter can overflow
+  }
   uint32_t used_total[2] = {0, 0};
   bool host_heavy = false;                                 // ultra-deep tiles had to be finished after the synchronisation
   b->cx_deferred = false;
-  for (int attempt = 0; attempt < 2; attempt++) {
+  for (int attempt = 0, pool_runs = 0; pool_runs < 2; attempt++) {
+    if (!direct) a.prev_off = nullptr;
     a.pool_key = b->pool_key.as<uint32_t>();
     a.pool_meth = b->pool_a.as<uint32_t>();
     a.pool_unmeth = b->pool_b.as<uint32_t>();
@@ -1740,6 +1826,29 @@ static int cx_report_impl(epi_batch *b, const int32_t *d_pass, const CxThreshold
       prof_end("cx_heavy", s);
     }
     EPI_HIP(hipGetLastError());
+    if (direct) {
+      // rows are in the caller's columns; misc[1] = tiles whose row count differed from the kept one.  One sync, as on the
+      // pool path.
+      uint32_t host9[9];
+      EPI_TRY(read_scalars(b, s, cursor - 1, 36, host9));
+      if (nt_hinted && host9[0] != (uint32_t)nt) {
+        for (int i = 0; i < 4; i++) b->tile_hint_T[i] = 0;
+        return fail(EPI_ERR_STATE, "the rows of this batch changed since an earlier report (tile count %u, was %d)", host9[0], nt);
+      }
+      if (host9[1] == 0) {
+        b->last_kind = 0;                                  // (nothing to fetch: the rows are where the caller wants them)
+        b->last_nrow = 0;
+        *nrow_out = b->cx_prev_nrow;
+        if (written) *written = 1;
+        return EPI_OK;
+      }
+      // the rows of this batch changed: the table from the pool, whose offsets are kept instead
+      b->cx_prev_key = 0;
+      direct = false;
+      a.heavy_rows = heavy_rows;
+      continue;
+    }
+    pool_runs++;
     if (b->cx_defer && nshared > 0 && attempt == 0 && nt_hinted && b->cx_noheavy_T == T && b->cx_noheavy_rows == a.heavy_rows) {
       // sharded report with one host synchronisation: nothing is read back here; epi_batch_cx_finish_shared checks the tile
       // count, the heavy-tile count and the pool at its own synchronisation (comm.hip reruns the first half into a scratch
@@ -1789,7 +1898,7 @@ static int cx_report_impl(epi_batch *b, const int32_t *d_pass, const CxThreshold
     }
 #endif
     if (ovf_base + used_total[0] + headroom <= a.pool_cap) break;
-    if (attempt == 1) return fail(EPI_ERR_STATE, "row pool overflow after regrow");
+    if (pool_runs == 2) return fail(EPI_ERR_STATE, "row pool overflow after regrow");
     EPI_TRY(ensure_pool(b, ovf_base + used_total[0] + (used_total[0] >> 4) + 1024 + headroom));   // exact need is known now: rerun once
     if (nshared > 0)   // the rerun adds into the slab again
       EPI_HIP(hipMemsetAsync(b->d_slab, 0, (size_t)nshared * kCxPlanes * T * 4, s));
@@ -1801,6 +1910,18 @@ static int cx_report_impl(epi_batch *b, const int32_t *d_pass, const CxThreshold
   b->last_kind = 1;
   b->last_nrow = used_total[1];
   *nrow_out = used_total[1];
+  if (b->cx_prev_key != (ctx_mask | 0x80000000u) || b->cx_prev_T != T || b->cx_prev_nt != nt) {
+    // keep this report's tile offsets for the next one with these contexts (device copies; the pool and the row counts are
+    // the next report's to overwrite)
+    EPI_TRY(b->cx_prev_off.ensure((size_t)nt * 4));
+    EPI_TRY(b->cx_prev_cnt.ensure((size_t)nt * 4));
+    EPI_HIP(hipMemcpyAsync(b->cx_prev_off.p, b->tile_out.p, (size_t)nt * 4, hipMemcpyDeviceToDevice, s));
+    EPI_HIP(hipMemcpyAsync(b->cx_prev_cnt.p, b->tile_nrow.p, (size_t)nt * 4, hipMemcpyDeviceToDevice, s));
+    b->cx_prev_key = ctx_mask | 0x80000000u;
+    b->cx_prev_T = T;
+    b->cx_prev_nt = nt;
+    b->cx_prev_nrow = used_total[1];
+  }
   return EPI_OK;
 }
 
@@ -1829,12 +1950,35 @@ int epi_batch_cytosine_report_dev(epi_batch *b, const char *ctx_meth, const char
                                   const char *ooctx_unmeth, uint32_t min_n_ctx, double min_ctx_meth_frac,
                                   double max_ooctx_meth_frac, const char *ctx, int32_t *d_pass_out, void *stream,
                                   int64_t *nrow_out) {
-  if (!b || !ctx || !nrow_out || !ctx_meth || !ctx_unmeth) return fail(EPI_ERR_ARG, "epi_batch_cytosine_report_dev: NULL argument");
+  return epi_batch_cytosine_report_into_dev(b, ctx_meth, ctx_unmeth, ooctx_meth, ooctx_unmeth, min_n_ctx, min_ctx_meth_frac,
+                                            max_ooctx_meth_frac, ctx, d_pass_out, nullptr, 0, stream, nrow_out, nullptr);
+}
+
+int epi_batch_cx_report_capacity(epi_batch *b, const char *ctx, int64_t *nrow) {
+  if (!b || !ctx || !nrow) return fail(EPI_ERR_ARG, "epi_batch_cx_report_capacity: NULL argument");
+  *nrow = cx_recorded_nrow(b, cx_ctx_mask(ctx));
+  return EPI_OK;
+}
+
+int epi_batch_cx_report_into_dev(epi_batch *b, const int32_t *d_pass, const char *ctx, int32_t *const d_cols[6], int64_t cap,
+                                 void *stream, int64_t *nrow_out, int *written) {
+  if (!b || !ctx || !nrow_out || !written || cap < 0 || (cap > 0 && !d_cols))
+    return fail(EPI_ERR_ARG, "epi_batch_cx_report_into_dev: bad arguments");
+  EPI_HIP(hipSetDevice(b->eng->device));
+  return cx_report_impl(b, d_pass, nullptr, nullptr, ctx, pick_stream(b, stream), nrow_out, d_cols, cap, written);
+}
+
+int epi_batch_cytosine_report_into_dev(epi_batch *b, const char *ctx_meth, const char *ctx_unmeth, const char *ooctx_meth,
+                                       const char *ooctx_unmeth, uint32_t min_n_ctx, double min_ctx_meth_frac,
+                                       double max_ooctx_meth_frac, const char *ctx, int32_t *d_pass_out,
+                                       int32_t *const d_cols[6], int64_t cap, void *stream, int64_t *nrow_out, int *written) {
+  if (!b || !ctx || !nrow_out || !ctx_meth || !ctx_unmeth || cap < 0 || (cap > 0 && !d_cols))
+    return fail(EPI_ERR_ARG, "epi_batch_cytosine_report_dev: bad arguments");
   EPI_HIP(hipSetDevice(b->eng->device));
   CxThreshold t;
   t.cls[0] = ctx_meth; t.cls[1] = ctx_unmeth; t.cls[2] = ooctx_meth ? ooctx_meth : ""; t.cls[3] = ooctx_unmeth ? ooctx_unmeth : "";
   t.prm.min_n_ctx = min_n_ctx; t.prm.min_ctx_meth_frac = min_ctx_meth_frac; t.prm.max_ooctx_meth_frac = max_ooctx_meth_frac;
-  return cx_report_impl(b, nullptr, &t, d_pass_out, ctx, pick_stream(b, stream), nrow_out);
+  return cx_report_impl(b, nullptr, &t, d_pass_out, ctx, pick_stream(b, stream), nrow_out, d_cols, cap, written);
 }
 
 // Second half of a sharded report: the slab has been sum-reduced across ranks;

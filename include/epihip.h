@@ -397,6 +397,20 @@ int epi_batch_cytosine_report_dev(epi_batch *b, const char *ctx_meth, const char
                                   const char *ooctx_unmeth, uint32_t min_n_ctx, double min_ctx_meth_frac,
                                   double max_ooctx_meth_frac, const char *ctx, int32_t *d_pass_out /* may be NULL */,
                                   void *stream, int64_t *nrow_out);
+/* The same reports written straight into the caller's six int32 columns of `cap` rows each (rname, strand, pos, context,
+ * meth, unmeth).  *written = 1: the columns hold the *nrow_out rows, nothing to fetch.  That happens when every tile
+ * is finished inside the tile kernel's launch -- no position of the batch covered by more than 255 rows, not a sharded
+ * report -- and the row count recorded by an earlier report on this batch with the same contexts fits `cap`.
+ * *written = 0: as epi_batch_cx_report_dev / epi_batch_cytosine_report_dev; continue with epi_batch_cx_fetch_*.
+ * Synchronises `stream` in both cases.  Library-owned memory is never handed out as the report. */
+int epi_batch_cx_report_into_dev(epi_batch *b, const int32_t *d_pass /* NULL = all TRUE */, const char *ctx,
+                                 int32_t *const d_cols[6], int64_t cap, void *stream, int64_t *nrow_out, int *written);
+int epi_batch_cytosine_report_into_dev(epi_batch *b, const char *ctx_meth, const char *ctx_unmeth, const char *ooctx_meth,
+                                       const char *ooctx_unmeth, uint32_t min_n_ctx, double min_ctx_meth_frac,
+                                       double max_ooctx_meth_frac, const char *ctx, int32_t *d_pass_out /* may be NULL */,
+                                       int32_t *const d_cols[6], int64_t cap, void *stream, int64_t *nrow_out, int *written);
+/* Capacity query: *nrow = rows of the last report on this batch with the contexts of `ctx` (-1: none yet). */
+int epi_batch_cx_report_capacity(epi_batch *b, const char *ctx, int64_t *nrow);
 int epi_batch_cx_fetch_dev(epi_batch *b, int32_t *const d_cols[6], void *stream);
 int epi_batch_cx_fetch_host(epi_batch *b, int32_t *const h_cols[6], void *stream);
 
