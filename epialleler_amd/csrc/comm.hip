@@ -22,6 +22,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <string>
 #include <rccl/rccl.h>
 
 namespace epi {
@@ -130,7 +131,8 @@ void forced_keys(int64_t first, int64_t last, int n, std::vector<int64_t> *keys,
 
 struct epi_shard_plan {                         // what a (batch, tile grid, communicator) triple needs per report; remembered on the batch
   uint64_t comm_serial = 0;
-  int T = 0, kind = 0;
+  int T = 0, kind = 0;                          // kind: 0 = CX, 1 = lMHL
+  std::string ctx;                              // lMHL: the context string the plan was made for
   std::vector<int64_t> keys;
   std::vector<int32_t> owned;
   bool fused = false;                           // lMHL: all ranks can take the one-pass kernel
@@ -276,12 +278,11 @@ int epi_batch_mhl_report_sharded(epi_batch *b, epi_comm *c, const char *ctx, int
   hipStream_t s = pick_stream(b, stream);
   *nrow_out = 0;
   c->last_bytes = 0;
-  // the plan depends on the context string only through "can every rank take the one-pass kernel": keyed by its hash
-  int kind = 1;
-  for (const unsigned char *p = reinterpret_cast<const unsigned char *>(ctx); *p; p++) kind = kind * 31 + *p;
-  kind |= 1 << 30;
+  // the plan depends on the context string only through "can every rank take the one-pass kernel": keyed by the string
+  // itself (two strings with the same letters' indices, "Zz" and "[[", may still differ in that decision)
+  const int kind = 1;
   epi_shard_plan *plan = nullptr;
-  for (auto &p : b->shard_plans) if (p->comm_serial == c->serial && p->kind == kind) plan = p.get();
+  for (auto &p : b->shard_plans) if (p->comm_serial == c->serial && p->kind == kind && p->ctx == ctx) plan = p.get();
   if (!plan) {
     // both tile grids' ranges and whether this rank's rows allow the one-pass kernel: one all-gather decides path and tiles
     int32_t ok = 0;
@@ -296,7 +297,7 @@ int epi_batch_mhl_report_sharded(epi_batch *b, epi_comm *c, const char *ctx, int
     std::vector<int64_t> ranges((size_t)2 * c->world);
     for (int r = 0; r < c->world; r++) { ranges[2 * r] = all[5 * r + (fused ? 2 : 0)]; ranges[2 * r + 1] = all[5 * r + (fused ? 3 : 1)]; }
     std::shared_ptr<epi_shard_plan> np(new epi_shard_plan());
-    np->comm_serial = c->serial; np->kind = kind; np->fused = fused;
+    np->comm_serial = c->serial; np->kind = kind; np->ctx = ctx; np->fused = fused;
     np->T = fused ? epi_mhl_fused_tile_positions() : epi_mhl_tile_positions();
     std::vector<int32_t> owner;
     if (c->world == 1 && c->test_shared > 0) forced_keys(ranges[0], ranges[1], c->test_shared, &np->keys, &owner);

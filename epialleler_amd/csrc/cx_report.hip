@@ -111,9 +111,11 @@ struct Cx2Args {
   int walk;                               // walking lean kernel: consecutive tiles per workgroup
   // Direct mode (prev_off != null): the emit writes the final columns rname, strand, pos, context, meth, unmeth itself --
   // no pool, no scan, no gather.  A tile's first row is where the last pool report on this batch with the same contexts
-  // put it: a tile's row count depends on the rows and the contexts alone (thresholds change M, not which cells pass the
-  // rule, rcpp_cx_report.cpp:63-71).  A tile whose count differs writes nothing and is counted in *mismatch (the host
-  // then reruns the report through the pool).
+  // put it.  For valid XM codes a tile's row count depends on the rows and the contexts alone (thresholds change M, not
+  // which cells pass the rule, rcpp_cx_report.cpp:63-71); for the low nibbles the packer never produces (1, 3, 4) a
+  // failed read counts differently (idx | 8 is skipped at 11, doubled at 9, rcpp_cx_report.cpp:122-127), and rewritten
+  // rows change it too.  So every tile checks its count: one that differs writes nothing and is counted in *mismatch
+  // (the host then reruns the report through the pool).
   const uint32_t *prev_off, *prev_nrow;   // first output row / row count of every tile
   uint32_t *mismatch;
   int32_t *out[6];                        // the caller's columns ...
@@ -1631,7 +1633,10 @@ static uint32_t cx_ctx_mask(const char *ctx) {
 // keeps the tile offsets of an earlier report with these contexts and its rows fit, and every tile is finished inside the
 // launch -- no position covered by more than 255 rows (RowStats::deep == 0: no deep list, and a tile with many candidate
 // rows is worked in place, not set aside), not a sharded report; otherwise the row pool is filled for
-// epi_batch_cx_fetch_* as before, and its tile offsets are kept for the next report.
+// epi_batch_cx_fetch_* as before, and its tile offsets are kept for the next report.  The kept offsets are only valid
+// while every tile's row count is the kept one: true for valid XM codes whatever `pass` is, not for the unused low
+// nibbles 1, 3 and 4 under failed reads, nor for rows rewritten in place.  A launch in which any tile's count differs
+// (misc[1] != 0) forgets the record and reruns through the pool (*written = 0), which keeps its offsets instead.
 static int cx_report_impl(epi_batch *b, const int32_t *d_pass, const CxThreshold *thr, int32_t *d_pass_out, const char *ctx,
                           hipStream_t s, int64_t *nrow_out, int32_t *const *d_cols = nullptr, int64_t cap = 0,
                           int *written = nullptr) {

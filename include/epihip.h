@@ -400,8 +400,11 @@ int epi_batch_cytosine_report_dev(epi_batch *b, const char *ctx_meth, const char
 /* The same reports written straight into the caller's six int32 columns of `cap` rows each (rname, strand, pos, context,
  * meth, unmeth).  *written = 1: the columns hold the *nrow_out rows, nothing to fetch.  That happens when every tile
  * is finished inside the tile kernel's launch -- no position of the batch covered by more than 255 rows, not a sharded
- * report -- and the row count recorded by an earlier report on this batch with the same contexts fits `cap`.
- * *written = 0: as epi_batch_cx_report_dev / epi_batch_cytosine_report_dev; continue with epi_batch_cx_fetch_*.
+ * report -- and the row count recorded by an earlier report on this batch with the same contexts fits `cap`, and every
+ * tile yields as many rows as it did then.  For valid XM codes that count does not depend on `pass` or the thresholds;
+ * for the low nibbles 1, 3 and 4 (never produced by the packer) a failed read counts differently, and rows rewritten in
+ * place may change it: a tile whose count differs makes the call rerun through the row pool (*written = 0) and replaces
+ * the record.  *written = 0: as epi_batch_cx_report_dev / epi_batch_cytosine_report_dev; continue with epi_batch_cx_fetch_*.
  * Synchronises `stream` in both cases.  Library-owned memory is never handed out as the report. */
 int epi_batch_cx_report_into_dev(epi_batch *b, const int32_t *d_pass /* NULL = all TRUE */, const char *ctx,
                                  int32_t *const d_cols[6], int64_t cap, void *stream, int64_t *nrow_out, int *written);

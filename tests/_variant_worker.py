@@ -39,17 +39,20 @@ def main():
             c = H.CONTEXT_TO_BASES["CG"]
             p = orc.threshold_reads(t["xm"], t["off"], c["ctx_meth"], c["ctx_unmeth"], c["ooctx_meth"], c["ooctx_unmeth"], 2, 0.5, 0.1)
             for ctx, pv in (("Z", None), ("ZXH", p), ("ZX", p)):
-                got = ea.rcpp_cx_report(bam, pv, ctx)
                 want = orc.cx_report(t["xm"], t["off"], t["rname"], t["strand"], t["start"], pv, ctx)
-                H.assert_reports_equal(dict(got), want)
+                for _ in range(2):                                        # the second one may be written by the tile kernel
+                    got = ea.rcpp_cx_report(bam, pv, ctx)
+                    H.assert_reports_equal(dict(got), want)
             for mn, mb, mo in ((2, 0.5, 0.1), (3, 1 / 3, 0.0)):          # the default table and another one
                 pt = p if (mn, mb, mo) == (2, 0.5, 0.1) else orc.threshold_reads(t["xm"], t["off"], c["ctx_meth"], c["ctx_unmeth"],
                                                                                   c["ooctx_meth"], c["ooctx_unmeth"], mn, mb, mo)
                 for ctx in ("Z", "ZXH"):                                  # thresholding fused into the tile kernel
-                    got, gp = ea.cytosine_report_fused(bam, c["ctx_meth"], c["ctx_unmeth"], c["ooctx_meth"], c["ooctx_unmeth"], mn, mb, mo,
-                                                       ctx, return_pass=True)
-                    assert np.array_equal(gp.astype(np.int32), pt), (mn, mb, mo, ctx)
-                    H.assert_reports_equal(dict(got), orc.cx_report(t["xm"], t["off"], t["rname"], t["strand"], t["start"], pt, ctx))
+                    want = orc.cx_report(t["xm"], t["off"], t["rname"], t["strand"], t["start"], pt, ctx)
+                    for _ in range(2):
+                        got, gp = ea.cytosine_report_fused(bam, c["ctx_meth"], c["ctx_unmeth"], c["ooctx_meth"], c["ooctx_unmeth"], mn,
+                                                           mb, mo, ctx, return_pass=True)
+                        assert np.array_equal(gp.astype(np.int32), pt), (mn, mb, mo, ctx)
+                        H.assert_reports_equal(dict(got), want)
             for hmax, hmin, moo in ((0, 0, 0.1), (3, 2, 1.0)):
                 got = ea.rcpp_mhl_report(bam, "Zz", hmax, hmin, moo)
                 want = orc.mhl_report(t["xm"], t["off"], t["rname"], t["strand"], t["start"], "Zz", hmax, hmin, moo)

@@ -1,0 +1,268 @@
+"""Long mixed sequences of calls on a few batches at once, every result against the oracle.  Most speed-ups keep state on
+the batch for the next call (remembered tile counts, threshold tables, pool slot sizes, the direct-mode record of the
+last CX report's tile offsets); a cache keyed on the wrong thing only shows in such a sequence.  Batches come from the
+fuzz generator plus one with raw garbage bytes (the unused low nibbles 1, 3 and 4, which count differently under a
+failed read), through every constructor.  Every CX call through the C entry points also checks `written` against the
+rule of include/epihip.h, predicted from the oracle's tables alone: the tile kernel writes the caller's columns when the
+last pool report on the batch had the same contexts, no position is deeper than 255 rows, the kept row count is above 0
+and fits, and every tile of the absolute grid yields as many rows as then.  Bounded by a list of seeds; a failure names
+its seed and step."""
+import collections
+
+import numpy as np
+import pytest
+
+import helpers as H
+import synth_np
+import test_extract_patterns as TP
+import test_gpu_cx_direct as D
+import test_gpu_fuzz as F
+from oracle import oracle as orc
+
+pytestmark = pytest.mark.gpu
+
+SEEDS = list(range(5000, 5060))
+GROUPS = 6
+CX_LETTERS = ("Z", "ZZ", "Zz", "X", "ZX", "ZXH", "H")
+NAMED = ("CG", "CHG", "CHH", "CxG", "CX")
+MHL_CTX = ("Zz", "Xx", "Hh", "ZzXx", "ZzXxHh")
+PASSES = ("none", "oracle", "random", "false", "na")
+MAKERS = ("arrays", "pinned", "device", "zero_copy")
+OPS = (("cx_c", 8), ("cx_py", 2), ("fused_py", 2), ("gcr", 1), ("mhl", 2), ("thr", 1), ("beta", 1), ("pat", 1), ("reopen", 1))
+NA = -2 ** 31
+# Paths over the whole seed list: C-level CX calls (`written` asserted) and Python-level ones (py_: tables only).  pool:
+# no record with these contexts yet; fallback: a direct launch in which some tile's count differed, the new row count
+# above / not above the kept one (above: the Python columns are allocated again).
+MIN_PATHS = {"pool": 150, "direct": 100, "fallback_above": 8, "fallback_below": 8, "py_direct": 40, "py_fallback_above": 5}
+RAN = {}                                               # group -> its path counts (this session)
+
+
+@pytest.fixture(scope="module")
+def ea():
+    import epialleler_amd
+    return epialleler_amd
+
+
+def ctx_mask(letters):
+    m = 0
+    for ch in letters:
+        m |= 1 << H.ctx_to_idx(ch)
+    return m
+
+
+def deep(t):
+    """k_row_stats: some row x + 255 of the same rname starts before the end of row x (u8 counters could overflow)."""
+    n = t["start"].size
+    if n <= 255:
+        return False
+    L = np.diff(t["off"])
+    s = t["start"].astype(np.int64)
+    x = np.arange(n - 255)
+    return bool(np.any((L[x] > 0) & (t["rname"][x + 255] == t["rname"][x]) & (s[x + 255] < s[x] + L[x])))
+
+
+class Slot:
+    """One batch of the sequence and what the library should remember about it."""
+
+    def __init__(self, ea, t, maker):
+        self.t, self.maker = t, maker
+        self.n = t["start"].size
+        self.deep = deep(t)
+        self.open(ea, maker)
+
+    def open(self, ea, maker):
+        import torch
+        t = self.t
+        self.maker = maker
+        self.rec = None                                # (context mask, per-tile counts, row count) of the kept record
+        nb = int(t["off"][-1])
+        if maker == "arrays":
+            self.bam = ea.ProcessedBam.from_arrays(t["xm"], t["off"], t["rname"], t["strand"], t["start"])
+        elif maker == "pinned":
+            cols = [torch.from_numpy(np.ascontiguousarray(t[k])).pin_memory() for k in ("xm", "off", "rname", "strand", "start")]
+            self.bam = ea.ProcessedBam.from_pinned(cols[0], nb, *cols[1:])
+        else:
+            xm = torch.full(((nb + 15) // 16 * 16 + 16,), 0xFB, dtype=torch.uint8, device="cuda:0")
+            xm[:nb] = torch.from_numpy(t["xm"]).cuda()
+            dev = lambda k: torch.from_numpy(np.ascontiguousarray(t[k])).cuda()
+            self.bam = ea.ProcessedBam.from_device(xm, nb, dev("off"), dev("rname"), dev("strand"), dev("start"),
+                                                   realign=maker == "device")
+
+    def predict(self, letters, want, T):
+        """(path, capacity the library reports before the call); updates the record as the library does."""
+        mask = ctx_mask(letters)
+        counts, nrow = D.tile_counts(want, T), int(want["pos"].size)
+        same = self.rec is not None and self.rec[0] == mask
+        cap = self.rec[2] if same else -1
+        if not same:
+            path = "pool"
+        elif self.rec[2] > 0 and not self.deep:
+            path = "direct" if self.rec[1] == counts else ("fallback_above" if nrow > self.rec[2] else "fallback_below")
+        else:
+            path = "pool_again"                        # same contexts, but pile-ups or an empty kept table: the record stays
+        if self.n > 0 and path in ("pool", "fallback_above", "fallback_below"):
+            self.rec = (mask, counts, nrow)
+        return path, cap
+
+
+def make_slots(ea, rng, seed):
+    ts = [F.make_batch(rng, seed * 7 + k)[1] for k in range(int(rng.integers(2, 4)))]
+    ts.append(synth_np.random_templates(rng, int(rng.integers(50, 3000)), 0, int(rng.integers(20, 500)), int(rng.integers(1, 4)),
+                                        int(rng.integers(200, 20000)), p_garbage=float(rng.choice([0.02, 0.1, 0.3]))))
+    return [Slot(ea, t, MAKERS[(seed + k) % len(MAKERS)]) for k, t in enumerate(ts)]
+
+
+def pick_pass(rng, s, kind, c4=None, thr=None):
+    t = s.t
+    if kind == "none":
+        return None
+    if kind == "oracle":
+        return orc.threshold_reads(t["xm"], t["off"], *c4, *thr)
+    if kind == "random":
+        return rng.integers(0, 2, size=s.n).astype(np.int32)
+    if kind == "false":
+        return np.zeros(s.n, np.int32)
+    p = rng.integers(0, 2, size=s.n).astype(np.int32)
+    p[rng.random(s.n) < 0.3] = NA                      # R's NA: non-zero, so TRUE
+    return p
+
+
+def cpu(rep):
+    return {k: (v.cpu().numpy() if hasattr(v, "cpu") else v) for k, v in dict(rep).items()}
+
+
+def run_seed(ea, seed, paths):
+    lib = ea._lib.load()
+    rng = np.random.default_rng(seed)
+    slots = make_slots(ea, rng, seed)
+    last = {}                                          # slot -> the last CX call's (letters, pass kind, thresholds)
+    ops, weights = zip(*OPS)
+    weights = np.asarray(weights, np.float64) / sum(weights)
+    nsteps = int(rng.integers(15, 26))
+    try:
+        for step in range(nsteps):
+            # the garbage batch (last) 40 % of the time: only its reads change a tile's row count with `pass`
+            k = len(slots) - 1 if rng.random() < 0.4 else int(rng.integers(0, len(slots) - 1))
+            s = slots[k]
+            t = s.t
+            op = str(rng.choice(ops, p=weights))
+            c4 = H.cls4(str(rng.choice(NAMED)))
+            thr = (int(rng.choice(F.MN)), float(rng.choice(F.MB)), float(rng.choice(F.MO)))
+            what = (step, op, k, s.maker)
+            try:
+                if op in ("cx_c", "cx_py", "fused_py", "gcr"):
+                    if k in last and rng.random() < 0.6:   # the same contexts again, often the same pass: direct mode's chance
+                        letters, pk, c4, thr = last[k]
+                        if rng.random() < 0.5:
+                            pk = str(rng.choice(PASSES))
+                    else:
+                        letters, pk = str(rng.choice(CX_LETTERS)), str(rng.choice(PASSES))
+                    fused = op == "fused_py" or (op == "cx_c" and rng.random() < 0.3)
+                    named = None
+                    if op == "gcr":
+                        named = str(rng.choice(NAMED))
+                        letters = H.CONTEXT_TO_BASES[named]["ctx_meth"]
+                        fused = rng.random() < 0.5
+                        c4, thr = H.cls4(named), (2, 0.5, 0.1)
+                        pk = "none"
+                    if fused:
+                        pk = "oracle"
+                    last[k] = (letters, pk, c4, thr)
+                    p = pick_pass(rng, s, pk, c4, thr)
+                    want = orc.cx_report(t["xm"], t["off"], t["rname"], t["strand"], t["start"], p, letters)
+                    T = lib.epi_cx_tile_positions(letters.encode())
+                    path, cap = s.predict(letters, want, T)
+                    what += (letters, pk, fused, thr, path)
+                    assert D.capacity(ea, s.bam, letters) == cap, ("capacity", cap)
+                    if op == "cx_c":
+                        named_thr = [n for n in NAMED if H.cls4(n) == c4][0]
+                        got, written = D.report(ea, s.bam, named_thr, fused, letters=letters, thr=thr, pass_=p)
+                        H.assert_reports_equal(got, want)
+                        assert written == (path == "direct"), ("written", written)
+                        paths[path] += 1
+                    else:
+                        H.dirty_allocator(s.bam)
+                        if op == "cx_py":
+                            got = ea.rcpp_cx_report(s.bam, p, letters)
+                        elif op == "fused_py":
+                            got, gp = ea.cytosine_report_fused(s.bam, *c4, *thr, letters, return_pass=True)
+                            assert np.array_equal(gp.astype(np.int32), p), "fused pass"
+                        else:
+                            dev = bool(rng.random() < 0.5)
+                            got = ea.generateCytosineReport(s.bam, threshold_reads=fused, threshold_context=named, as_device=dev)
+                        H.assert_reports_equal(cpu(got), want)
+                        paths["py_" + path] += 1
+                elif op == "mhl":
+                    hctx = str(rng.choice(MHL_CTX))
+                    hmax, hmin = int(rng.choice([0, 0, 1, 3, 50])), int(rng.choice([0, 0, 2, 5]))
+                    moo = float(rng.choice([0.1, 0.0, 1.0, float("nan"), -0.5]))
+                    what += (hctx, hmax, hmin, moo)
+                    H.assert_reports_equal(cpu(ea.rcpp_mhl_report(s.bam, hctx, hmax, hmin, moo, as_device=bool(rng.random() < 0.3))),
+                                           orc.mhl_report(t["xm"], t["off"], t["rname"], t["strand"], t["start"], hctx, hmax, hmin, moo),
+                                           float_cols=("length", "lmhl"))
+                elif op == "thr":
+                    what += (c4, thr)
+                    H.dirty_allocator(s.bam)
+                    got = ea.rcpp_threshold_reads(s.bam, *c4, *thr)
+                    assert np.array_equal(got.astype(np.int32), orc.threshold_reads(t["xm"], t["off"], *c4, *thr)), "threshold"
+                elif op == "beta":
+                    got = ea.rcpp_get_xm_beta(s.bam, c4[0], c4[1])
+                    want = orc.get_xm_beta(t["xm"], t["off"], c4[0], c4[1])
+                    assert np.array_equal(got.view(np.uint64), want.view(np.uint64)), "beta"
+                elif op == "pat":
+                    if s.n == 0:
+                        continue
+                    x = int(rng.integers(0, s.n))
+                    rn, ts = int(t["rname"][x]), int(t["start"][x]) + int(rng.integers(0, 50))
+                    te = ts + int(rng.integers(0, 600))
+                    ctx = str(rng.choice(["Zz", "ZzXx", "HhXxZz", "Hh"]))
+                    clip, ro, mo = bool(rng.integers(0, 2)), int(rng.integers(0, 3)), int(rng.integers(1, 30))
+                    freq = float(rng.choice([0.0, 0.01, 0.2]))
+                    hl = sorted({int(v) for v in rng.integers(ts, te + 1, size=int(rng.integers(0, 4)))})
+                    what += (rn, ts, te, ctx, clip, ro, mo, freq, hl)
+                    rep = ea.rcpp_extract_patterns(s.bam, rn, ts, te, mo, ctx, freq, clip, ro, hl)
+                    o = orc.extract_patterns(t["xm"], t["off"], t["rname"], t["strand"], t["start"], rn, ts, te, mo, ctx, freq, clip, ro, hl)
+                    a = TP.table_from_report(rep)
+                    b = TP.table_from(o["strand"], o["start"], o["end"], o["nbase"], o["beta"], ["%016X" % int(v) for v in o["fnv"]],
+                                      o["positions"], o["cells"])
+                    assert a["positions"] == b["positions"] and a["pattern"] == b["pattern"], "patterns"
+                    for c in ("strand", "start", "end", "nbase", "cells"):
+                        assert np.array_equal(a[c], b[c]), c
+                    assert np.array_equal(np.asarray(a["beta"], np.float64).view(np.uint64),
+                                          np.asarray(b["beta"], np.float64).view(np.uint64)), "pattern beta"
+                else:                                      # reopen: a fresh batch of the same rows, maybe another constructor
+                    s.bam.close()
+                    last.pop(k, None)
+                    s.open(ea, str(rng.choice(MAKERS)))
+                    what += (s.maker,)
+            except AssertionError as e:
+                raise AssertionError("seed %d, step %d: %r: %s" % (seed, step, what, e)) from e
+    finally:
+        for s in slots:
+            s.bam.close()
+
+
+def run_group(ea, group):
+    paths = collections.Counter()
+    for seed in SEEDS[group::GROUPS]:
+        run_seed(ea, seed, paths)
+    RAN[group] = paths
+    return paths
+
+
+@pytest.mark.parametrize("group", range(GROUPS))
+def test_sequences(ea, group):
+    paths = run_group(ea, group)
+    print("group %d paths: %s" % (group, dict(sorted(paths.items()))))
+    assert paths["pool"] and paths["direct"]
+
+
+def test_paths_over_all_seeds(ea):
+    """Every path of the direct-mode rule was taken (and checked) a minimum number of times over the whole seed list; the
+    groups not run in this session are run here."""
+    total = collections.Counter()
+    for g in range(GROUPS):
+        total.update(RAN[g] if g in RAN else run_group(ea, g))
+    print("paths over all seeds: %s" % dict(sorted(total.items())))
+    for p, m in MIN_PATHS.items():
+        assert total[p] >= m, (p, dict(total))

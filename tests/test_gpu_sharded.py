@@ -294,3 +294,50 @@ def test_rccl_two_gpus(tmp_path):
         H.assert_reports_equal(dict(np.load(os.path.join(str(tmp_path), "nccl_%s_cx.npz" % name))), want)
         wm = orc.mhl_report(t["xm"], t["off"], t["rname"], t["strand"], t["start"], "Zz", 0, 0, 0.1)
         H.assert_reports_equal(dict(np.load(os.path.join(str(tmp_path), "nccl_%s_mhl.npz" % name))), wm, float_cols=("length", "lmhl"))
+
+
+def _plan_worker(rank, port, outdir):
+    """One rank, 5 forced shared tiles: lMHL plans of contexts whose letters share context indices ("Zz" and "[[": '[' is
+    read as 'Z'; a once hashed key made them collide although only "Zz" can take the one-pass kernel) in both orders on one
+    batch, a six-letter context, and a sharded CX report between two plain ones on the same batch."""
+    sys.path.insert(0, HERE)
+    sys.path.insert(0, os.path.dirname(HERE))
+    os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+    import torch
+    torch.cuda.set_device(0)
+    import epialleler_amd as ea
+    from epialleler_amd import distributed as D
+    import test_gpu_cx_direct as X
+    t = _case("wgs")
+    written = []
+    for order in (("Zz", "[["), ("[[", "Zz"), ("ZzXxHh", "Zz")):
+        shard = ea.ProcessedBam.from_arrays(t["xm"], t["off"], t["rname"], t["strand"], t["start"])
+        eng = D.HipShardEngine(shard).attach_comm(test_shared=5)
+        for k, ctx in enumerate(order * 2):                 # (the second round reuses the remembered plans)
+            rep = D.sharded_mhl_report(eng, ctx, 0, 0, 0.1, gather=True)
+            np.savez(os.path.join(outdir, "plan_%s_%d.npz" % ("".join(order), k)), **{c: v.cpu().numpy() for c, v in rep.items()})
+        first, w1 = X.report(ea, shard, "CG", False)
+        rep = D.sharded_cx_report(eng, None, "Z", gather=True)
+        second, w2 = X.report(ea, shard, "CG", False)
+        written.append((w1, w2))
+        for name, tab in (("first", first), ("sharded", {c: v.cpu().numpy() for c, v in rep.items()}), ("second", second)):
+            np.savez(os.path.join(outdir, "plan_%s_cx_%s.npz" % ("".join(order), name)), **tab)
+        eng.close_comm()
+        shard.close()
+    np.save(os.path.join(outdir, "plan_written.npy"), np.asarray(written, bool))
+
+
+def test_mhl_plan_keyed_by_context(tmp_path):
+    import torch.multiprocessing as mp
+    mp.spawn(_plan_worker, args=(_free_port(), str(tmp_path)), nprocs=1, join=True)
+    t = _case("wgs")
+    want_cx = orc.cx_report(t["xm"], t["off"], t["rname"], t["strand"], t["start"], None, "Z")
+    for order in (("Zz", "[["), ("[[", "Zz"), ("ZzXxHh", "Zz")):
+        for k, ctx in enumerate(order * 2):
+            want = orc.mhl_report(t["xm"], t["off"], t["rname"], t["strand"], t["start"], ctx, 0, 0, 0.1)
+            got = dict(np.load(os.path.join(str(tmp_path), "plan_%s_%d.npz" % ("".join(order), k))))
+            H.assert_reports_equal(got, want, float_cols=("length", "lmhl"))
+        for name in ("first", "sharded", "second"):
+            H.assert_reports_equal(dict(np.load(os.path.join(str(tmp_path), "plan_%s_cx_%s.npz" % ("".join(order), name)))), want_cx)
+    # a plain report, a sharded one (which keeps no offsets), then the plain one again: written by the tile kernel
+    assert np.load(os.path.join(str(tmp_path), "plan_written.npy")).tolist() == [[False, True]] * 3

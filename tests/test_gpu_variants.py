@@ -42,6 +42,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
     {"EPIHIP_MHL_MULTI": "1"},                                           # lMHL pass 1: wavefront-per-read kernel for every read
     {"EPIHIP_MHL_MULTI": "1", "EPIHIP_MHL_TILE_GROUP": "64", "EPIHIP_HEAVY_ROWS": "500"},
     {"EPIHIP_MHL_FUSED": "0", "EPIHIP_MHL_SUMS": "64", "EPIHIP_HEAVY_ROWS": "500"},   # lMHL pass 2 with u64 LDS sums where u32 would do
+    {"EPIHIP_CX_DIRECT": "0"},                                           # second CX reports through the pool as well (no direct mode)
+    {"EPIHIP_CX_DIRECT": "0", "EPIHIP_HEAVY_ROWS": "100"},
 ])
 def test_cx_kernel_variants(env):
     e = dict(os.environ)
