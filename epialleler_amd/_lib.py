@@ -141,6 +141,9 @@ _SIGS = {
     "epi_batch_extract_patterns": (C.c_int, [_VP, _I32, _I32, _I32, _I32, _CS, _F64, _I32, _I32, _VP, _I32, _VP,
                                            C.POINTER(PatternTable)]),
     "epi_pattern_table_free": (None, [C.POINTER(PatternTable)]),
+    "epi_batch_extract_patterns_multi": (C.c_int, [_VP, _I32, _VP, _VP, _VP, _I32, _CS, _F64, _I32, _I32, _VP, _VP, _VP,
+                                                 C.POINTER(PatternTable)]),
+    "epi_batch_extract_patterns_multi_stats": (C.c_int, [_VP, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64)]),
     "epi_batch_cx_report_dev": (C.c_int, [_VP, _VP, _CS, _VP, C.POINTER(_I64)]),
     "epi_batch_cytosine_report_dev": (C.c_int, [_VP, _CS, _CS, _CS, _CS, _U32, _F64, _F64, _CS, _VP, _VP, C.POINTER(_I64)]),
     "epi_batch_cx_report_into_dev": (C.c_int, [_VP, _VP, _CS, C.POINTER(_VP), _I64, _VP, C.POINTER(_I64), C.POINTER(C.c_int)]),

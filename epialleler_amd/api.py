@@ -418,24 +418,58 @@ def rcpp_extract_patterns(df, target_rname, target_start, target_end, min_overla
                                               C.c_void_p(hl.ctypes.data) if hl.size else None, int(hl.size),
                                               _stream(bam.device), C.byref(t)))
     try:
-        k, m = int(t.npat), int(t.ncol)
-        if k == 0:
-            return Report({}, bam.levels)
-        take = lambda ptr, n, dt: np.ctypeslib.as_array(ptr, shape=(n,)).astype(dt, copy=True)
-        cols = {"seqnames": np.full(k, int(target_rname), np.int32)}
-        for nm in ("strand", "start", "end", "nbase"):
-            cols[nm] = take(getattr(t, nm), k, np.int32)
-        cols["beta"] = take(t.beta, k, np.float64)
-        cols["pattern"] = np.asarray(["%016X" % int(v) for v in take(t.fnv, k, np.uint64)], object)      # :174-176
-        pos = take(t.positions, m, np.int32)
-        cells = take(t.cells, m * k, np.int32).reshape(m, k)
-        for i in range(m):
-            cols[str(int(pos[i]))] = cells[i]
+        return _pattern_report(t, target_rname, bam)
     finally:
         lib.epi_pattern_table_free(C.byref(t))
+
+
+def _pattern_report(t, target_rname, bam):
+    """An epi_pattern_table (still owned by the library) -> Report."""
+    k, m = int(t.npat), int(t.ncol)
+    if k == 0:
+        return Report({}, bam.levels)
+    take = lambda ptr, n, dt: np.ctypeslib.as_array(ptr, shape=(n,)).astype(dt, copy=True)
+    cols = {"seqnames": np.full(k, int(target_rname), np.int32)}
+    for nm in ("strand", "start", "end", "nbase"):
+        cols[nm] = take(getattr(t, nm), k, np.int32)
+    cols["beta"] = take(t.beta, k, np.float64)
+    cols["pattern"] = np.asarray(["%016X" % int(v) for v in take(t.fnv, k, np.uint64)], object)      # :174-176
+    pos = take(t.positions, m, np.int32)
+    cells = take(t.cells, m * k, np.int32).reshape(m, k)
+    for i in range(m):
+        cols[str(int(pos[i]))] = cells[i]
     rep = Report(cols, bam.levels)
     rep.pattern_levels = PATTERN_LEVELS
     return rep
+
+
+def rcpp_extract_patterns_multi(df, targets, min_overlap, ctx, min_ctx_freq, clip, reverse_offset, hlght=None):
+    """rcpp_extract_patterns for every target of a list in one pass over the candidate rows
+    (epi_batch_extract_patterns_multi).  targets: a sequence of (rname_code, start, end); hlght: None, or one sequence
+    of highlight positions per target (sorted, unique, inside the target).  Returns one Report per target, each what
+    rcpp_extract_patterns(df, *targets[k], ..., hlght[k]) returns."""
+    lib = _lib.load()
+    bam = _as_bam(df)
+    tg = np.ascontiguousarray(np.asarray(list(targets), dtype=np.int64).reshape(-1, 3).T, dtype=np.int32)    # [3][nt]
+    nt = tg.shape[1]
+    if hlght is not None and len(hlght) != nt:
+        raise ValueError("hlght must hold one sequence of positions per target")
+    b = bam.batch()
+    hl_off = np.zeros(nt + 1, np.int64)
+    if hlght is not None:
+        np.cumsum([len(h) for h in hlght], out=hl_off[1:])
+    hl = np.ascontiguousarray([p for h in hlght for p in h] if hlght is not None else [], dtype=np.int32)
+    tabs = (_lib.PatternTable * max(nt, 1))()
+    ptr = lambda a: C.c_void_p(a.ctypes.data) if a.size else None
+    _lib.check(lib.epi_batch_extract_patterns_multi(b, nt, ptr(tg[0]), ptr(tg[1]), ptr(tg[2]), int(min_overlap), _lib.enc(ctx),
+                                                    float(min_ctx_freq), int(bool(clip)), int(reverse_offset), ptr(hl),
+                                                    C.c_void_p(hl_off.ctypes.data) if hlght is not None else None,
+                                                    _stream(bam.device), tabs))
+    try:
+        return [_pattern_report(tabs[k], tg[0, k], bam) for k in range(nt)]
+    finally:
+        for k in range(nt):
+            lib.epi_pattern_table_free(C.byref(tabs[k]))
 
 
 # ---- exported R API ------------------------------------------------------------------------------

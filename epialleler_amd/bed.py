@@ -11,7 +11,7 @@ import numpy as np
 
 from . import _lib
 from .api import (CONTEXT_TO_BASES, Report, _CTX_CHOICES, _as_bam, _match_arg, _stream, preprocessBam,
-                  rcpp_extract_patterns, rcpp_get_xm_beta, rcpp_threshold_reads, writeReport)
+                  rcpp_extract_patterns, rcpp_extract_patterns_multi, rcpp_get_xm_beta, rcpp_threshold_reads, writeReport)
 
 NA_INTEGER = -2 ** 31
 
@@ -172,6 +172,15 @@ def generateBedEcdf(bam, bed, bed_type=None, bed_rows=(1,), zero_based_bed=False
     return out
 
 
+def _pattern_bed(bed, zero_based_bed):
+    """The `bed` argument of extractPatterns: a Bed, a string "chr:start-end", or a path."""
+    if isinstance(bed, str) and ":" in bed and "-" in bed.rsplit(":", 1)[1] and not __import__("os").path.exists(bed):
+        chrom, rng = bed.rsplit(":", 1)                                        # as("chr:start-end", "GRanges")
+        a, b_ = rng.split("-")
+        return Bed([chrom], [int(a)], [int(b_)])
+    return bed if isinstance(bed, Bed) else readBed(bed, zero_based_bed)
+
+
 def extractPatterns(bam, bed, bed_row=1, zero_based_bed=False, match_min_overlap=1, extract_context=None,
                     min_context_freq=0.01, clip_patterns=False, strand_offset=None, highlight_positions=(), verbose=False,
                     **preprocess_args):
@@ -180,12 +189,7 @@ def extractPatterns(bam, bed, bed_row=1, zero_based_bed=False, match_min_overlap
     extract_context = _match_arg(extract_context, _CTX_CHOICES, "extract.context")
     if strand_offset is None:
         strand_offset = {"CG": 1, "CHG": 2, "CHH": 0, "CxG": 0, "CX": 0}[extract_context]
-    if isinstance(bed, str) and ":" in bed and "-" in bed.rsplit(":", 1)[1] and not __import__("os").path.exists(bed):
-        chrom, rng = bed.rsplit(":", 1)                                        # as("chr:start-end", "GRanges")
-        a, b_ = rng.split("-")
-        bed = Bed([chrom], [int(a)], [int(b_)])
-    elif not isinstance(bed, Bed):
-        bed = readBed(bed, zero_based_bed)
+    bed = _pattern_bed(bed, zero_based_bed)
     bam = _as_bam(preprocessBam(bam, **preprocess_args))
     row = int(np.atleast_1d(bed_row)[0]) - 1
     if row < 0 or row >= len(bed):
@@ -200,3 +204,43 @@ def extractPatterns(bam, bed, bed_row=1, zero_based_bed=False, match_min_overlap
                                 clip_patterns, int(strand_offset), hl)
     rep.bed = bed.names()[row]
     return rep
+
+
+def extractPatternsBed(bam, bed, bed_rows=None, zero_based_bed=False, match_min_overlap=1, extract_context=None,
+                       min_context_freq=0.01, clip_patterns=False, strand_offset=None, highlight_positions=(), verbose=False,
+                       **preprocess_args):
+    """extractPatterns for many BED rows in one pass on the GPU (epi_batch_extract_patterns_multi): the list
+    [extractPatterns(bam, bed, bed_row=r, ...) for r in bed_rows], at the cost of the reads on the targets instead of
+    one scan of the batch per target.  bed_rows: 1-based rows in the order wanted, duplicates allowed, None = every
+    row in BED order; a row outside the BED gives the empty Report the single call gives.  highlight_positions: one
+    list for the call, every target uses the positions inside it.  The BAM is preprocessed once."""
+    extract_context = _match_arg(extract_context, _CTX_CHOICES, "extract.context")
+    if bed_rows is not None:
+        bed_rows = list(np.atleast_1d(np.asarray(bed_rows, object)))
+        for r in bed_rows:
+            if isinstance(r, (bool, np.bool_)) or not isinstance(r, (int, np.integer)):
+                raise ValueError("'bed.rows' should be None or 1-based integer row numbers, not %r" % (r,))
+    if strand_offset is None:
+        strand_offset = {"CG": 1, "CHG": 2, "CHH": 0, "CxG": 0, "CX": 0}[extract_context]
+    bed = _pattern_bed(bed, zero_based_bed)
+    bam = _as_bam(preprocessBam(bam, **preprocess_args))
+    rows = list(range(len(bed))) if bed_rows is None else [int(r) - 1 for r in bed_rows]
+    levels = list(bam.levels) if bam.levels is not None else []
+    code = {c: i + 1 for i, c in enumerate(levels)}
+    hl_all = np.unique(np.atleast_1d(np.asarray(highlight_positions, np.int64)))
+    keep = [k for k, r in enumerate(rows) if 0 <= r < len(bed)]
+    targets, hl = [], []
+    for k in keep:
+        r = rows[k]
+        start, end = int(bed.start[r]), int(bed.end[r])
+        targets.append((code.get(bed.chrom[r], NA_INTEGER), start, end))       # factor(seqnames, levels=levels(rname))
+        hl.append([int(p) for p in hl_all[(hl_all >= start) & (hl_all <= end)]])
+    c = CONTEXT_TO_BASES[extract_context]
+    reps = rcpp_extract_patterns_multi(bam, targets, match_min_overlap, c["ctx_meth"] + c["ctx_unmeth"], min_context_freq,
+                                       clip_patterns, int(strand_offset), hl)
+    names = bed.names()
+    out = [Report({}, bam.levels) for _ in rows]                               # data.table()[bed.row] of a missing row: no target
+    for k, rep in zip(keep, reps):
+        rep.bed = names[rows[k]]
+        out[k] = rep
+    return out

@@ -67,6 +67,8 @@ static void read_options() {
   o.no_hugepage = getenv("EPIHIP_NO_HUGEPAGE") != nullptr;
   if (const char *e = getenv("EPIHIP_UPLOAD_PIECE")) o.upload_piece = strtoll(e, nullptr, 10);
   if (o.upload_piece < 0) o.upload_piece = 0;
+  if (const char *e = getenv("EPIHIP_PAT_GROUP_BYTES")) o.pat_group_bytes = strtoll(e, nullptr, 10);
+  if (o.pat_group_bytes < 0) o.pat_group_bytes = 0;
   g_options = o;
 }
 

@@ -8,6 +8,8 @@
 //   k_pat_extract  one thread per overlapping read: its cell per valid position, methylated / total counts and the
 //                  FNV-1a hash of (position, base) pairs, highlighted bases appended (:133-166)
 //   host           drops empty patterns (:152) and returns the table.
+// epi_batch_extract_patterns_multi (second half of this file) runs the same per-read rules for every target of a list in
+// O(1) launches and host round trips: candidate row ranges by search, one flat list of (target, row) pairs.
 // Quirks of the reference kept as they are: with clip=TRUE the byte loop ends at `overlap`,
 // not at begin+overlap (:86,:132), and position bytes enter the hash sign-extended (char pointer, epialleleR.h:8-13).
 #include "common.hpp"
@@ -59,16 +61,20 @@ __global__ __launch_bounds__(256) void k_pat_flag(PatArgs a, uint32_t *__restric
   flag[x] = pat_span(a, x).ok ? 1u : 0u;
 }
 
-__global__ __launch_bounds__(256) void k_pat_count(PatArgs a, const uint32_t *__restrict__ flag, uint32_t *__restrict__ cnt) {
-  const int64_t x = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (x >= a.n || !flag[x]) return;
-  const PatSpan s = pat_span(a, x);
+// row x overlaps the target (s = pat_span(a, x), s.ok): one count per in-context position of its span
+__device__ __forceinline__ void pat_count_row(const PatArgs &a, int64_t x, const PatSpan &s, uint32_t *__restrict__ cnt) {
   const uint8_t *p = a.xm + a.off[x];
   for (uint32_t i = s.begin_i; i < s.end_i; i++) {
     if (!((a.ctx_mask >> (p[i] & 15u)) & 1u)) continue;
     const int64_t w = (int64_t)(int32_t)(s.start_x + i - s.offset_x) - a.pos_lo;
     if (w >= 0 && w < a.nwin) atomicAdd(cnt + w, 1u);
   }
+}
+
+__global__ __launch_bounds__(256) void k_pat_count(PatArgs a, const uint32_t *__restrict__ flag, uint32_t *__restrict__ cnt) {
+  const int64_t x = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (x >= a.n || !flag[x]) return;
+  pat_count_row(a, x, pat_span(a, x), cnt);
 }
 
 struct PatOut {
@@ -85,13 +91,10 @@ __device__ __forceinline__ void fnv_char(unsigned long long &h, uint32_t v) {   
   }
 }
 
-__global__ __launch_bounds__(256) void k_pat_extract(PatArgs a, const uint32_t *__restrict__ flag, const uint32_t *__restrict__ cidx,
-                                                      const int32_t *__restrict__ colmap, const int32_t *__restrict__ hlght,
-                                                      const int32_t *__restrict__ hcol, int32_t nhlght, int64_t npat0, PatOut o) {
-  const int64_t x = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (x >= a.n || !flag[x]) return;
-  const PatSpan s = pat_span(a, x);
-  const uint32_t c = cidx[x];
+// row x overlaps the target (s = pat_span(a, x), s.ok) and is its c-th overlapping row: cells, counts and hash
+__device__ __forceinline__ void pat_extract_row(const PatArgs &a, int64_t x, const PatSpan &s, uint32_t c,
+                                                const int32_t *__restrict__ colmap, const int32_t *__restrict__ hlght,
+                                                const int32_t *__restrict__ hcol, int32_t nhlght, int64_t npat0, const PatOut &o) {
   const uint8_t *p = a.xm + a.off[x];
   uint32_t meth = 0, total = 0;
   unsigned long long fnv = 14695981039346656037ull;
@@ -131,9 +134,194 @@ __global__ __launch_bounds__(256) void k_pat_extract(PatArgs a, const uint32_t *
   o.fnv[c] = fnv;
 }
 
+__global__ __launch_bounds__(256) void k_pat_extract(PatArgs a, const uint32_t *__restrict__ flag, const uint32_t *__restrict__ cidx,
+                                                      const int32_t *__restrict__ colmap, const int32_t *__restrict__ hlght,
+                                                      const int32_t *__restrict__ hcol, int32_t nhlght, int64_t npat0, PatOut o) {
+  const int64_t x = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (x >= a.n || !flag[x]) return;
+  pat_extract_row(a, x, pat_span(a, x), cidx[x], colmap, hlght, hcol, nhlght, npat0, o);
+}
+
+// ---- every target of a list at once (epi_batch_extract_patterns_multi) -------------------------------------------------
+// Rows sorted by (rname, start): the rows that can overlap target t lie in one range [row_lo, row_hi), found by search.
+// The ranges of a group of targets are laid end to end as one flat list of (target, candidate row) pairs; pre[] is the
+// u64 exclusive scan of the range lengths, and thread j finds its target as the last t with pre[t] <= j.  flag / cidx
+// are indexed by pair, cnt / colmap by the targets' windows laid end to end: every target owns a slice of each.
+struct PatTarget {
+  int64_t row_lo;                 // its candidate rows: row_lo + (j - pre[t])
+  int64_t pos_lo, nwin;           // its window of positions, as PatArgs
+  int64_t win_off;                // its slice of cnt / colmap
+  int64_t hl_off;                 // its highlight positions: hl[hl_off .. hl_off + nhl), columns hcol[...]
+  int32_t rname, start, end, nhl;
+};
+struct PatSlice {                 // what the host decided for a target between the two passes
+  int64_t cell_off;               // its [ncol][npat0] cells in the cell scratch
+  uint32_t base_abs;              // cidx of its first overlapping row
+  uint32_t base_rel;              // its first slot in the per-pattern arrays
+  uint32_t npat0, pad;
+};
+struct PatMulti {
+  const uint8_t *xm;
+  const int64_t *off;
+  const int32_t *len, *rname, *strand, *start;
+  uint32_t reverse_offset, ctx_mask;
+  int32_t min_overlap, clip;
+  const PatTarget *tg;
+  const uint64_t *pre;            // [ng + 1]
+  int32_t ng;
+};
+
+__device__ __forceinline__ PatArgs pat_args_of(const PatMulti &m, const PatTarget &g) {
+  PatArgs a;
+  a.xm = m.xm; a.off = m.off; a.len = m.len; a.rname = m.rname; a.strand = m.strand; a.start = m.start; a.n = 0;
+  a.target_rname = (uint32_t)g.rname; a.target_start = (uint32_t)g.start; a.target_end = (uint32_t)g.end;
+  a.reverse_offset = m.reverse_offset; a.min_overlap = m.min_overlap; a.clip = m.clip; a.ctx_mask = m.ctx_mask;
+  a.pos_lo = g.pos_lo; a.nwin = g.nwin;
+  return a;
+}
+
+// last t in [0, ng) with pre[t] <= j (pre[0] = 0 <= j < pre[ng]); at most 32 steps
+__device__ __forceinline__ int32_t pat_target_of(const uint64_t *__restrict__ pre, int32_t ng, uint64_t j) {
+  int32_t a = 0, b = ng;
+  for (int it = 0; it < 32 && b - a > 1; it++) {
+    const int32_t m = a + ((b - a) >> 1);
+    if (pre[m] <= j) a = m; else b = m;
+  }
+  return a;
+}
+
+// first row in [0, n) with (rname, start) >= (qr, qp); at most 64 steps
+__device__ __forceinline__ int64_t pat_row_lower_bound(const int32_t *__restrict__ rname, const int32_t *__restrict__ start, int64_t n,
+                                                       int32_t qr, int64_t qp) {
+  int64_t a = 0, b = n;
+  for (int it = 0; it < 64 && a < b; it++) {
+    const int64_t m = a + ((b - a) >> 1);
+    const int32_t r = rname[m];
+    if (r < qr || (r == qr && (int64_t)start[m] < qp)) a = m + 1; else b = m;
+  }
+  return a;
+}
+
+// One lane per target: rng[2t], rng[2t+1] = its candidate rows, those on its rname that start in
+// [start - reach - lmax + 1, end + reach] (reach = 0 for min_overlap >= 1: pat_span accepts no other row).
+// rng[2 * nt] != 0: some target's rname holds a row with a negative start (pat_span's unsigned arithmetic lets such a
+// row overlap anything; the caller takes the per-target path).
+__global__ __launch_bounds__(256) void k_patm_ranges(const int32_t *__restrict__ rname, const int32_t *__restrict__ start, int64_t n,
+                                                     const int32_t *__restrict__ tgt /* [3][nt] rname, start, end */, int32_t nt,
+                                                     int64_t lmax, int64_t reach, int64_t *__restrict__ rng) {
+  const int32_t t = (int32_t)(blockIdx.x * 256 + threadIdx.x);
+  if (t >= nt) return;
+  const int32_t qr = tgt[t];
+  const int64_t ts = tgt[nt + t], te = tgt[2 * (int64_t)nt + t];
+  const int64_t lo = pat_row_lower_bound(rname, start, n, qr, ts - reach - lmax + 1);
+  int64_t hi = pat_row_lower_bound(rname, start, n, qr, te + reach + 1);
+  if (hi < lo) hi = lo;
+  rng[2 * (int64_t)t] = lo;
+  rng[2 * (int64_t)t + 1] = hi;
+  const int64_t first = pat_row_lower_bound(rname, start, n, qr, INT64_MIN);
+  if (first < n && rname[first] == qr && start[first] < 0) rng[2 * (int64_t)nt] = 1;
+}
+
+// pass 1, one thread per pair: does the row overlap its target (-> flag), and if so its in-context positions (-> cnt)
+__global__ __launch_bounds__(256) void k_patm_flag_count(PatMulti m, uint64_t npairs, uint32_t *__restrict__ flag, uint32_t *__restrict__ cnt) {
+  const uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (j >= npairs) return;
+  const int32_t t = pat_target_of(m.pre, m.ng, j);
+  const PatTarget g = m.tg[t];
+  const PatArgs a = pat_args_of(m, g);
+  const int64_t x = g.row_lo + (int64_t)(j - m.pre[t]);
+  const PatSpan s = pat_span(a, x);
+  flag[j] = s.ok ? 1u : 0u;
+  if (s.ok) pat_count_row(a, x, s, cnt + g.win_off);
+}
+
+// base[t] = overlapping rows before target t's range (base[ng], the total, is the scan's)
+__global__ __launch_bounds__(256) void k_patm_bases(const uint64_t *__restrict__ pre, int32_t ng, uint64_t npairs,
+                                                    const uint32_t *__restrict__ cidx, uint32_t *__restrict__ base) {
+  const int32_t t = (int32_t)(blockIdx.x * 256 + threadIdx.x);
+  if (t >= ng) return;
+  base[t] = pre[t] < npairs ? cidx[pre[t]] : base[ng];
+}
+
+// pass 2, one thread per pair j0 + k, k < npairs: the pairs of the group's targets whose results share the scratch this time
+__global__ __launch_bounds__(256) void k_patm_extract(PatMulti m, uint64_t j0, uint64_t npairs, const uint32_t *__restrict__ flag,
+                                                      const uint32_t *__restrict__ cidx, const PatSlice *__restrict__ sl,
+                                                      const int32_t *__restrict__ colmap, const int32_t *__restrict__ hl,
+                                                      const int32_t *__restrict__ hcol, PatOut o) {
+  const uint64_t k = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (k >= npairs) return;
+  const uint64_t j = j0 + k;
+  if (!flag[j]) return;
+  const int32_t t = pat_target_of(m.pre, m.ng, j);
+  const PatTarget g = m.tg[t];
+  const PatSlice q = sl[t];
+  const PatArgs a = pat_args_of(m, g);
+  const int64_t x = g.row_lo + (int64_t)(j - m.pre[t]);
+  PatOut ot;
+  ot.nonempty = o.nonempty + q.base_rel; ot.strand = o.strand + q.base_rel; ot.start = o.start + q.base_rel; ot.end = o.end + q.base_rel;
+  ot.nbase = o.nbase + q.base_rel; ot.meth = o.meth + q.base_rel; ot.fnv = o.fnv + q.base_rel;
+  ot.cells = o.cells + q.cell_off;
+  pat_extract_row(a, x, pat_span(a, x), cidx[j] - q.base_abs, colmap + g.win_off, hl + g.hl_off, hcol + g.hl_off, g.nhl, (int64_t)q.npat0, ot);
+}
+
 }  // namespace epi
 
 using namespace epi;
+
+extern "C" void epi_pattern_table_free(epi_pattern_table *t);
+
+// The host's decision between the two passes: valid positions = seen in >= min_ctx_freq of the npat0 overlapping reads
+// and not highlighted (:103-108), the highlight positions (:110-112), merged in position order (:185).  cnt / colmap:
+// the nwin positions from pos_lo on (colmap: column of a valid position, else -1); hcol[k]: column of hlght[k].
+static void pat_choose_columns(const uint32_t *cnt, int64_t nwin, int64_t pos_lo, uint32_t npat0, double min_ctx_freq,
+                               const int32_t *hlght, int32_t nhlght, std::vector<int32_t> &cols, int32_t *colmap, int32_t *hcol) {
+  cols.clear();
+  for (int64_t w = 0; w < nwin; w++) {
+    colmap[w] = -1;
+    if (!cnt[w]) continue;
+    const int32_t pos = (int32_t)(pos_lo + w);
+    if ((double)cnt[w] / npat0 >= min_ctx_freq && std::find(hlght, hlght + nhlght, pos) == hlght + nhlght) cols.push_back(pos);
+  }
+  const size_t npatcols = cols.size();
+  for (int32_t k = 0; k < nhlght; k++) cols.push_back(hlght[k]);
+  std::vector<int32_t> patcols(cols.begin(), cols.begin() + (long)npatcols);
+  std::sort(cols.begin(), cols.end());
+  cols.erase(std::unique(cols.begin(), cols.end()), cols.end());       // std::map keys are unique
+  for (int32_t pos : patcols) colmap[(int64_t)pos - pos_lo] = (int32_t)(std::lower_bound(cols.begin(), cols.end(), pos) - cols.begin());
+  for (int32_t k = 0; k < nhlght; k++) hcol[k] = (int32_t)(std::lower_bound(cols.begin(), cols.end(), hlght[k]) - cols.begin());
+}
+
+// The table of one target from the P0 slots its overlapping rows filled: keeps the non-empty patterns, in row order
+// (:152, :166-176).  cells: [ncol][P0].
+static int pat_fill_table(epi_pattern_table *out, size_t P0, int32_t ncol, const int32_t *cols, const int32_t *nonempty,
+                          const int32_t *strand, const int32_t *start, const int32_t *end, const int32_t *nbase, const int32_t *meth,
+                          const unsigned long long *fnv, const int32_t *cells) {
+  size_t np = 0;
+  for (size_t c = 0; c < P0; c++) np += nonempty[c] != 0;
+  if (np == 0) return EPI_OK;
+  out->npat = (int64_t)np;
+  out->ncol = ncol;
+  out->positions = (int32_t *)malloc(((size_t)ncol + 1) * 4);
+  out->strand = (int32_t *)malloc(np * 4); out->start = (int32_t *)malloc(np * 4); out->end = (int32_t *)malloc(np * 4);
+  out->nbase = (int32_t *)malloc(np * 4); out->beta = (double *)malloc(np * 8); out->fnv = (uint64_t *)malloc(np * 8);
+  out->cells = (int32_t *)malloc(((size_t)ncol * np + 1) * 4);
+  if (!out->positions || !out->strand || !out->start || !out->end || !out->nbase || !out->beta || !out->fnv || !out->cells) {
+    epi_pattern_table_free(out);
+    return fail(EPI_ERR_NOMEM, "epi_batch_extract_patterns: out of host memory");
+  }
+  memcpy(out->positions, cols, (size_t)ncol * 4);
+  size_t w = 0;
+  for (size_t c = 0; c < P0; c++) {
+    if (!nonempty[c]) continue;
+    out->strand[w] = strand[c]; out->start[w] = start[c]; out->end[w] = end[c];
+    out->nbase[w] = nbase[c];
+    out->beta[w] = (double)(uint32_t)meth[c] / (uint32_t)nbase[c];                                // :173
+    out->fnv[w] = fnv[c];
+    for (int32_t k = 0; k < ncol; k++) out->cells[(size_t)k * np + w] = cells[(size_t)k * P0 + c];
+    w++;
+  }
+  return EPI_OK;
+}
 
 extern "C" {
 
@@ -188,22 +376,10 @@ int epi_batch_extract_patterns(epi_batch *b, int32_t target_rname, int32_t targe
   std::vector<uint32_t> h_cnt((size_t)a.nwin);
   PAT_HIP(hipMemcpy(h_cnt.data(), cnt.p, (size_t)a.nwin * 4, hipMemcpyDeviceToHost));
 
-  // valid positions (:103-108), highlight positions (:110-112), merged in position order (:185)
   std::vector<int32_t> cols;
-  for (int64_t w = 0; w < a.nwin; w++) {
-    if (!h_cnt[(size_t)w]) continue;
-    const int32_t pos = (int32_t)(a.pos_lo + w);
-    if ((double)h_cnt[(size_t)w] / npat0 >= min_ctx_freq && std::find(hlght, hlght + nhlght, pos) == hlght + nhlght) cols.push_back(pos);
-  }
-  const size_t npatcols = cols.size();
-  for (int32_t k = 0; k < nhlght; k++) cols.push_back(hlght[k]);
-  std::vector<int32_t> patcols(cols.begin(), cols.begin() + (long)npatcols);
-  std::sort(cols.begin(), cols.end());
-  cols.erase(std::unique(cols.begin(), cols.end()), cols.end());       // std::map keys are unique
+  std::vector<int32_t> h_colmap((size_t)a.nwin), h_hcol((size_t)(nhlght > 0 ? nhlght : 1), 0);
+  pat_choose_columns(h_cnt.data(), a.nwin, a.pos_lo, npat0, min_ctx_freq, hlght, nhlght, cols, h_colmap.data(), h_hcol.data());
   const int32_t ncol = (int32_t)cols.size();
-  std::vector<int32_t> h_colmap((size_t)a.nwin, -1), h_hcol((size_t)(nhlght > 0 ? nhlght : 1), 0);
-  for (int32_t pos : patcols) h_colmap[(size_t)((int64_t)pos - a.pos_lo)] = (int32_t)(std::lower_bound(cols.begin(), cols.end(), pos) - cols.begin());
-  for (int32_t k = 0; k < nhlght; k++) h_hcol[(size_t)k] = (int32_t)(std::lower_bound(cols.begin(), cols.end(), hlght[k]) - cols.begin());
   PAT_HIP(hipMemcpy(colmap.p, h_colmap.data(), (size_t)a.nwin * 4, hipMemcpyHostToDevice));
   PAT_TRY(d_hl.ensure((size_t)(nhlght > 0 ? nhlght : 1) * 4));
   PAT_TRY(d_hc.ensure((size_t)(nhlght > 0 ? nhlght : 1) * 4));
@@ -234,31 +410,277 @@ int epi_batch_extract_patterns(epi_batch *b, int32_t target_rname, int32_t targe
 #undef PAT_TRY
 #undef PAT_HIP
 
-  // keep the non-empty patterns, in row order (:152, :166-176)
-  size_t np = 0;
-  for (size_t c = 0; c < P0; c++) np += h_i[c] != 0;
-  if (np == 0) return EPI_OK;
-  out->npat = (int64_t)np;
-  out->ncol = ncol;
-  out->positions = (int32_t *)malloc(((size_t)ncol + 1) * 4);
-  out->strand = (int32_t *)malloc(np * 4); out->start = (int32_t *)malloc(np * 4); out->end = (int32_t *)malloc(np * 4);
-  out->nbase = (int32_t *)malloc(np * 4); out->beta = (double *)malloc(np * 8); out->fnv = (uint64_t *)malloc(np * 8);
-  out->cells = (int32_t *)malloc(((size_t)ncol * np + 1) * 4);
-  if (!out->positions || !out->strand || !out->start || !out->end || !out->nbase || !out->beta || !out->fnv || !out->cells) {
-    epi_pattern_table_free(out);
-    return fail(EPI_ERR_NOMEM, "epi_batch_extract_patterns: out of host memory");
+  const int32_t *r = h_i.data();
+  return pat_fill_table(out, P0, ncol, cols.data(), r, r + P0, r + 2 * P0, r + 3 * P0, r + 4 * P0, r + 5 * P0, h_f.data(), h_cells.data());
+}
+
+}  // extern "C"
+
+// ---- epi_batch_extract_patterns_multi ---------------------------------------------------------------------------------
+namespace {
+
+constexpr int64_t kPatGroupBytes = 256LL << 20;   // scratch cap of a group of targets (include/epihip.h)
+
+struct PatmScratch {
+  DevBuf tgt, rng, meta, flag, cidx, cb, colmap, sl, hl, res;
+  size_t peak = 0;
+  void note() {
+    const size_t v = tgt.cap + rng.cap + meta.cap + flag.cap + cidx.cap + cb.cap + colmap.cap + sl.cap + hl.cap + res.cap;
+    if (v > peak) peak = v;
   }
-  memcpy(out->positions, cols.data(), (size_t)ncol * 4);
-  size_t w = 0;
-  for (size_t c = 0; c < P0; c++) {
-    if (!h_i[c]) continue;
-    out->strand[w] = h_i[P0 + c]; out->start[w] = h_i[2 * P0 + c]; out->end[w] = h_i[3 * P0 + c];
-    out->nbase[w] = h_i[4 * P0 + c];
-    out->beta[w] = (double)(uint32_t)h_i[5 * P0 + c] / (uint32_t)h_i[4 * P0 + c];                 // :173
-    out->fnv[w] = h_f[c];
-    for (int32_t k = 0; k < ncol; k++) out->cells[(size_t)k * np + w] = h_cells[(size_t)k * P0 + c];
-    w++;
+  ~PatmScratch() { tgt.release(); rng.release(); meta.release(); flag.release(); cidx.release(); cb.release(); colmap.release(); sl.release(); hl.release(); res.release(); }
+};
+
+struct PatmCall {                 // what every group of a call shares
+  epi_batch *b;
+  hipStream_t s;
+  const int32_t *t_rname, *t_start, *t_end;
+  const int64_t *row_lo, *row_hi; // [ntargets]
+  const int64_t *pos_lo, *nwin;   // [ntargets]
+  const int32_t *hlght;
+  const int64_t *hlght_off;       // may be null
+  double min_ctx_freq;
+  int64_t cap;
+  PatMulti m;                     // tg / pre / ng filled per group
+  epi_pattern_table *out;
+};
+
+// targets [ta, tb): two passes, three host synchronisations (plus one per further cell batch)
+int patm_group(PatmCall &c, PatmScratch &w, int32_t ta, int32_t tb) {
+  epi_batch *b = c.b;
+  hipStream_t s = c.s;
+  const int32_t ng = tb - ta;
+  std::vector<uint64_t> meta((size_t)(ng + 1) + ((size_t)ng * sizeof(PatTarget) + 7) / 8);
+  uint64_t *pre = meta.data();
+  PatTarget *tg = reinterpret_cast<PatTarget *>(meta.data() + ng + 1);
+  const int64_t hl0 = c.hlght_off ? c.hlght_off[ta] : 0;
+  int64_t W = 0;
+  pre[0] = 0;
+  for (int32_t k = 0; k < ng; k++) {
+    const int32_t t = ta + k;
+    PatTarget &g = tg[k];
+    g.row_lo = c.row_lo[t]; g.pos_lo = c.pos_lo[t]; g.nwin = c.nwin[t]; g.win_off = W;
+    g.hl_off = c.hlght_off ? c.hlght_off[t] - hl0 : 0;
+    g.nhl = c.hlght_off ? (int32_t)(c.hlght_off[t + 1] - c.hlght_off[t]) : 0;
+    g.rname = c.t_rname[t]; g.start = c.t_start[t]; g.end = c.t_end[t];
+    W += g.nwin;
+    pre[k + 1] = pre[k] + (uint64_t)(c.row_hi[t] - c.row_lo[t]);
   }
+  const uint64_t P = pre[ng];
+  const int64_t H = c.hlght_off ? c.hlght_off[tb] - hl0 : 0;
+  if (P == 0) return EPI_OK;                                  // no candidate row: every table of the group is empty
+  const int64_t nbp = (int64_t)((P + 255) / 256);
+  EPI_TRY(check_grid(nbp, 256, "epi_batch_extract_patterns_multi"));
+  b->patm_pairs += (int64_t)P;
+
+  // pass 1: overlap flags and position counts, the flags scanned into pattern slots
+  const size_t nbase = ((size_t)ng + 2) & ~(size_t)1;         // base[ng + 1] (padded to an even count), then the counts
+  EPI_TRY(w.meta.ensure(meta.size() * 8));
+  EPI_TRY(w.flag.ensure((size_t)P * 4));
+  EPI_TRY(w.cidx.ensure((size_t)P * 4));
+  EPI_TRY(w.cb.ensure((nbase + (size_t)W) * 4));
+  w.note();
+  EPI_HIP(hipMemcpyAsync(w.meta.p, meta.data(), meta.size() * 8, hipMemcpyHostToDevice, s));
+  EPI_HIP(hipMemsetAsync(w.cb.p, 0, (nbase + (size_t)W) * 4, s));
+  PatMulti m = c.m;
+  m.pre = w.meta.as<uint64_t>();
+  m.tg = reinterpret_cast<const PatTarget *>(w.meta.as<uint64_t>() + ng + 1);
+  m.ng = ng;
+  uint32_t *d_base = w.cb.as<uint32_t>(), *d_cnt = d_base + nbase;
+  prof_begin("extract_patterns_multi", s);
+  hipLaunchKernelGGL(k_patm_flag_count, dim3((unsigned)nbp), dim3(256), 0, s, m, P, w.flag.as<uint32_t>(), d_cnt);
+  EPI_TRY(scan_exclusive_u32(w.flag.as<uint32_t>(), w.cidx.as<uint32_t>(), (int64_t)P, d_base + ng, b->scan_tmp, s));
+  hipLaunchKernelGGL(k_patm_bases, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, s, m.pre, ng, P, w.cidx.as<uint32_t>(), d_base);
+  EPI_HIP(hipGetLastError());
+  prof_end("extract_patterns_multi", s);
+  std::vector<uint32_t> h_cb(nbase + (size_t)W);
+  EPI_HIP(hipMemcpyAsync(h_cb.data(), w.cb.p, h_cb.size() * 4, hipMemcpyDeviceToHost, s));
+  EPI_HIP(hipStreamSynchronize(s));
+  const uint32_t *h_base = h_cb.data(), *h_cnt = h_cb.data() + nbase;
+  if (h_base[ng] == 0) return EPI_OK;                         // no row overlaps any target of the group
+
+  // the host's decision for every target; cell batches of at most `cap` result bytes
+  std::vector<std::vector<int32_t>> cols((size_t)ng);
+  std::vector<int32_t> h_colmap((size_t)W, -1), h_hl((size_t)(2 * H + 2), 0);
+  int32_t *h_hcol = h_hl.data() + H;
+  if (H > 0) memcpy(h_hl.data(), c.hlght + hl0, (size_t)H * 4);
+  std::vector<PatSlice> sl((size_t)ng);
+  std::vector<int32_t> cuts(1, 0);                            // batch i: targets [cuts[i], cuts[i + 1])
+  int64_t bytes = 0, cell_off = 0;
+  uint32_t rel = 0;
+  for (int32_t k = 0; k < ng; k++) {
+    const PatTarget &g = tg[k];
+    const uint32_t npat0 = h_base[k + 1] - h_base[k];
+    if (npat0) pat_choose_columns(h_cnt + g.win_off, g.nwin, g.pos_lo, npat0, c.min_ctx_freq, h_hl.data() + g.hl_off, g.nhl, cols[(size_t)k],
+                                  h_colmap.data() + g.win_off, h_hcol + g.hl_off);
+    const int64_t cells = (int64_t)cols[(size_t)k].size() * npat0, need = 32LL * npat0 + 4 * cells;
+    if (bytes > 0 && bytes + need > c.cap) { cuts.push_back(k); bytes = 0; cell_off = 0; rel = 0; }
+    sl[(size_t)k].cell_off = cell_off; sl[(size_t)k].base_abs = h_base[k]; sl[(size_t)k].base_rel = rel; sl[(size_t)k].npat0 = npat0; sl[(size_t)k].pad = 0;
+    bytes += need; cell_off += cells; rel += npat0;
+  }
+  cuts.push_back(ng);
+  EPI_TRY(w.colmap.ensure((size_t)W * 4));
+  EPI_TRY(w.sl.ensure(sl.size() * sizeof(PatSlice)));
+  EPI_TRY(w.hl.ensure(h_hl.size() * 4));
+  EPI_HIP(hipMemcpyAsync(w.colmap.p, h_colmap.data(), (size_t)W * 4, hipMemcpyHostToDevice, s));
+  EPI_HIP(hipMemcpyAsync(w.sl.p, sl.data(), sl.size() * sizeof(PatSlice), hipMemcpyHostToDevice, s));
+  EPI_HIP(hipMemcpyAsync(w.hl.p, h_hl.data(), h_hl.size() * 4, hipMemcpyHostToDevice, s));
+
+  // pass 2, batch by batch: [fnv u64][nonempty, strand, start, end, nbase, meth i32] x slots, then the cells
+  std::vector<uint64_t> h_res;
+  for (size_t i = 0; i + 1 < cuts.size(); i++) {
+    const int32_t sa = cuts[i], sb = cuts[i + 1];
+    const size_t Ps = h_base[sb] - h_base[sa];
+    if (Ps == 0) continue;
+    size_t C = 0;
+    for (int32_t k = sa; k < sb; k++) C += cols[(size_t)k].size() * sl[(size_t)k].npat0;
+    const size_t rbytes = 32 * Ps + 4 * C;
+    EPI_TRY(w.res.ensure(rbytes + 64));
+    w.note();
+    PatOut o;
+    int32_t *ip = w.res.as<int32_t>();
+    o.fnv = reinterpret_cast<unsigned long long *>(ip);
+    int32_t *q = ip + 2 * Ps;
+    o.nonempty = q; o.strand = q + Ps; o.start = q + 2 * Ps; o.end = q + 3 * Ps; o.nbase = q + 4 * Ps; o.meth = q + 5 * Ps;
+    o.cells = q + 6 * Ps;
+    if (C) EPI_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(o.cells), INT32_MIN, C, s));             // NA_INTEGER
+    const uint64_t j0 = pre[sa], np = pre[sb] - pre[sa];
+    prof_begin("extract_patterns_multi", s);
+    hipLaunchKernelGGL(k_patm_extract, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, s, m, j0, np, w.flag.as<uint32_t>(),
+                       w.cidx.as<uint32_t>(), w.sl.as<PatSlice>(), w.colmap.as<int32_t>(), w.hl.as<int32_t>(), w.hl.as<int32_t>() + H, o);
+    EPI_HIP(hipGetLastError());
+    prof_end("extract_patterns_multi", s);
+    h_res.resize((rbytes + 7) / 8);
+    EPI_HIP(hipMemcpyAsync(h_res.data(), w.res.p, rbytes, hipMemcpyDeviceToHost, s));
+    EPI_HIP(hipStreamSynchronize(s));
+    const unsigned long long *h_f = reinterpret_cast<const unsigned long long *>(h_res.data());
+    const int32_t *r = reinterpret_cast<const int32_t *>(h_res.data()) + 2 * Ps, *h_cells = r + 6 * Ps;
+    for (int32_t k = sa; k < sb; k++) {
+      const PatSlice &q1 = sl[(size_t)k];
+      if (!q1.npat0) continue;
+      const int32_t *rk = r + q1.base_rel;
+      EPI_TRY(pat_fill_table(c.out + ta + k, q1.npat0, (int32_t)cols[(size_t)k].size(), cols[(size_t)k].data(), rk, rk + Ps, rk + 2 * Ps,
+                             rk + 3 * Ps, rk + 4 * Ps, rk + 5 * Ps, h_f + q1.base_rel, h_cells + q1.cell_off));
+    }
+  }
+  return EPI_OK;
+}
+
+int patm_run(epi_batch *b, int32_t nt, const int32_t *t_rname, const int32_t *t_start, const int32_t *t_end, int32_t min_overlap,
+             const char *ctx, double min_ctx_freq, int32_t clip, int32_t reverse_offset, const int32_t *hlght, const int64_t *hlght_off,
+             void *stream, epi_pattern_table *out) {
+  EPI_HIP(hipSetDevice(b->eng->device));
+  hipStream_t s = pick_stream(b, stream);
+  EPI_TRY(fetch_row_stats(b, s));
+  if (b->h_stats.bad_len) return fail(EPI_ERR_ARG, "offsets are not non-decreasing, or start+length exceeds int32");
+  const int64_t lmax = b->h_stats.max_len;
+  auto one_by_one = [&]() {                                   // rows in any order: every target scans the batch
+    for (int32_t t = 0; t < nt; t++) {
+      const int64_t h0 = hlght_off ? hlght_off[t] : 0, h1 = hlght_off ? hlght_off[t + 1] : 0;
+      EPI_TRY(epi_batch_extract_patterns(b, t_rname[t], t_start[t], t_end[t], min_overlap, ctx, min_ctx_freq, clip, reverse_offset,
+                                         h1 > h0 ? hlght + h0 : nullptr, (int32_t)(h1 - h0), stream, out + t));
+    }
+    return (int)EPI_OK;
+  };
+  bool ranges_ok = !b->h_stats.unsorted;
+  std::vector<int64_t> pos_lo((size_t)nt), nwin((size_t)nt);
+  for (int32_t t = 0; t < nt; t++) {
+    if (t_start[t] < 0 || t_end[t] < 0) ranges_ok = false;    // (pat_span compares unsigned)
+    pos_lo[(size_t)t] = (int64_t)t_start[t] - lmax - (int64_t)reverse_offset - 2;
+    int64_t nw = ((int64_t)t_end[t] - (int64_t)t_start[t]) + 2 * lmax + (int64_t)reverse_offset + 8;
+    if (nw < 1) nw = 1;
+    if (nw > (1LL << 31)) return fail(EPI_ERR_ARG, "epi_batch_extract_patterns: target too wide");
+    nwin[(size_t)t] = nw;
+  }
+  if (!ranges_ok) return one_by_one();
+
+  // candidate rows of every target
+  PatmScratch w;
+  std::vector<int32_t> h_tgt((size_t)3 * nt);
+  memcpy(h_tgt.data(), t_rname, (size_t)nt * 4);
+  memcpy(h_tgt.data() + nt, t_start, (size_t)nt * 4);
+  memcpy(h_tgt.data() + 2 * (size_t)nt, t_end, (size_t)nt * 4);
+  std::vector<int64_t> h_rng((size_t)2 * nt + 1);
+  EPI_TRY(w.tgt.ensure(h_tgt.size() * 4));
+  EPI_TRY(w.rng.ensure(h_rng.size() * 8));
+  w.note();
+  EPI_HIP(hipMemcpyAsync(w.tgt.p, h_tgt.data(), h_tgt.size() * 4, hipMemcpyHostToDevice, s));
+  EPI_HIP(hipMemsetAsync(w.rng.p, 0, h_rng.size() * 8, s));
+  const int64_t reach = min_overlap >= 1 ? 0 : 1 - (int64_t)min_overlap;
+  EPI_TRY(check_grid(((int64_t)nt + 255) / 256, 256, "epi_batch_extract_patterns_multi"));
+  prof_begin("extract_patterns_multi", s);
+  hipLaunchKernelGGL(k_patm_ranges, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, s, b->rname, b->start, b->n, w.tgt.as<int32_t>(), nt,
+                     lmax, reach, w.rng.as<int64_t>());
+  EPI_HIP(hipGetLastError());
+  prof_end("extract_patterns_multi", s);
+  EPI_HIP(hipMemcpyAsync(h_rng.data(), w.rng.p, h_rng.size() * 8, hipMemcpyDeviceToHost, s));
+  EPI_HIP(hipStreamSynchronize(s));
+  if (h_rng[(size_t)2 * nt]) return one_by_one();
+  std::vector<int64_t> row_lo((size_t)nt), row_hi((size_t)nt);
+  for (int32_t t = 0; t < nt; t++) { row_lo[(size_t)t] = h_rng[2 * (size_t)t]; row_hi[(size_t)t] = h_rng[2 * (size_t)t + 1]; }
+
+  PatmCall c;
+  c.b = b; c.s = s; c.t_rname = t_rname; c.t_start = t_start; c.t_end = t_end;
+  c.row_lo = row_lo.data(); c.row_hi = row_hi.data(); c.pos_lo = pos_lo.data(); c.nwin = nwin.data();
+  c.hlght = hlght; c.hlght_off = hlght_off; c.min_ctx_freq = min_ctx_freq; c.out = out;
+  c.cap = options().pat_group_bytes > 0 ? options().pat_group_bytes : kPatGroupBytes;
+  c.m.xm = b->xm; c.m.off = b->off; c.m.len = b->len; c.m.rname = b->rname; c.m.strand = b->strand; c.m.start = b->start;
+  c.m.reverse_offset = (uint32_t)reverse_offset; c.m.min_overlap = min_overlap; c.m.clip = clip ? 1 : 0;
+  c.m.ctx_mask = 0;
+  for (const unsigned char *p = reinterpret_cast<const unsigned char *>(ctx); *p; p++) c.m.ctx_mask |= 1u << ctx_to_idx(*p);
+  c.m.tg = nullptr; c.m.pre = nullptr; c.m.ng = 0;
+
+  // groups of consecutive targets whose pass-1 scratch (40 B per pair, 8 B per window position) fits the cap
+  int rc = EPI_OK;
+  for (int32_t ta = 0; ta < nt && rc == EPI_OK;) {
+    int64_t bytes = 0;
+    int32_t tb = ta;
+    while (tb < nt) {
+      const int64_t need = 40 * (row_hi[(size_t)tb] - row_lo[(size_t)tb]) + 8 * nwin[(size_t)tb] + 128;
+      if (tb > ta && bytes + need > c.cap) break;
+      bytes += need;
+      tb++;
+    }
+    rc = patm_group(c, w, ta, tb);
+    b->patm_groups++;
+    ta = tb;
+  }
+  if (w.peak > (size_t)b->patm_scratch) b->patm_scratch = (int64_t)w.peak;
+  return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int epi_batch_extract_patterns_multi(epi_batch *b, int32_t ntargets, const int32_t *target_rname, const int32_t *target_start,
+                                     const int32_t *target_end, int32_t min_overlap, const char *ctx, double min_ctx_freq, int32_t clip,
+                                     int32_t reverse_offset, const int32_t *hlght, const int64_t *hlght_off, void *stream,
+                                     epi_pattern_table *out) {
+  if (!b || !ctx || ntargets < 0 || (ntargets > 0 && (!target_rname || !target_start || !target_end || !out)))
+    return fail(EPI_ERR_ARG, "epi_batch_extract_patterns_multi: bad arguments");
+  if (ntargets > 0) memset(out, 0, (size_t)ntargets * sizeof(*out));
+  if (hlght_off) {
+    for (int32_t t = 0; t < ntargets; t++)
+      if (hlght_off[t] < 0 || hlght_off[t + 1] < hlght_off[t] || hlght_off[t + 1] - hlght_off[t] > 0x7FFFFFFF)
+        return fail(EPI_ERR_ARG, "epi_batch_extract_patterns_multi: hlght_off is not a CSR offset array");
+    if (ntargets > 0 && hlght_off[ntargets] > hlght_off[0] && !hlght)
+      return fail(EPI_ERR_ARG, "epi_batch_extract_patterns_multi: hlght is NULL");
+  }
+  b->patm_groups = 0; b->patm_pairs = 0; b->patm_scratch = 0;
+  if (ntargets == 0 || b->n == 0) return EPI_OK;
+  const int rc = patm_run(b, ntargets, target_rname, target_start, target_end, min_overlap, ctx, min_ctx_freq, clip, reverse_offset,
+                          hlght, hlght_off, stream, out);
+  if (rc != EPI_OK)
+    for (int32_t t = 0; t < ntargets; t++) epi_pattern_table_free(out + t);
+  return rc;
+}
+
+int epi_batch_extract_patterns_multi_stats(epi_batch *b, int64_t *groups, int64_t *pairs, int64_t *scratch_bytes) {
+  if (!b) return fail(EPI_ERR_ARG, "epi_batch_extract_patterns_multi_stats: batch is NULL");
+  if (groups) *groups = b->patm_groups;
+  if (pairs) *pairs = b->patm_pairs;
+  if (scratch_bytes) *scratch_bytes = b->patm_scratch;
   return EPI_OK;
 }
 

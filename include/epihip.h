@@ -441,6 +441,30 @@ int epi_batch_extract_patterns(epi_batch *b, int32_t target_rname, int32_t targe
                                int32_t reverse_offset, const int32_t *hlght /* sorted, unique, inside the target */,
                                int32_t nhlght, void *stream, epi_pattern_table *out);
 void epi_pattern_table_free(epi_pattern_table *t);
+/* The same for every target of a list in one pass: out[t] is what epi_batch_extract_patterns returns for
+ * (target_rname[t], target_start[t], target_end[t]) with the highlight positions hlght[hlght_off[t] .. hlght_off[t+1])
+ * (each slice sorted, unique, inside its target; hlght_off NULL = none) and the same other arguments; targets may
+ * overlap, repeat and come in any order.  Each out[t] is released with epi_pattern_table_free; on any failure every
+ * out[t] is left zeroed and freed.  ntargets == 0 and an empty batch return EPI_OK.
+ * Row order: the rows must be sorted by (rname, start), as preprocessBam leaves them.  The candidate rows of a target
+ * -- its rname, start in [start - Lmax + 1, end], Lmax the longest row -- are then one row range found by search, and
+ * the work is one flat list of (target, candidate row) pairs: cost O(candidate rows), a fixed number of launches and
+ * three host synchronisations per GROUP of targets, whatever their number.  For rows in another order (adopted
+ * columns), rows or targets with negative coordinates, the call runs epi_batch_extract_patterns target by target
+ * instead: same tables, cost O(rows x targets).
+ * Memory: nothing is sized by the batch.  Consecutive targets form a group while 40 B per pair + 8 B per window position
+ * (end - start + 2 Lmax + reverse_offset + 8 per target) stay under a cap of 256 MiB; the results of a group (32 B per
+ * overlapping row + 4 B per cell) are fetched in batches under the same cap.  A target above the cap runs alone.
+ * Device scratch (allocated and freed by the call, buffers grown with 1/8 of slack) is therefore at most 600 MiB + 200 B
+ * per target unless one target exceeds the cap by itself; the host holds the same plus the tables.  Synchronises `stream`. */
+int epi_batch_extract_patterns_multi(epi_batch *b, int32_t ntargets, const int32_t *target_rname,
+                                     const int32_t *target_start, const int32_t *target_end, int32_t min_overlap,
+                                     const char *ctx, double min_ctx_freq, int32_t clip, int32_t reverse_offset,
+                                     const int32_t *hlght, const int64_t *hlght_off /* [ntargets+1] CSR, may be NULL */,
+                                     void *stream, epi_pattern_table *out /* [ntargets] */);
+/* Of the last epi_batch_extract_patterns_multi on this batch: groups run (0: the target-by-target path), (target,
+ * candidate row) pairs, peak device scratch in bytes.  Any pointer may be NULL. */
+int epi_batch_extract_patterns_multi_stats(epi_batch *b, int64_t *groups, int64_t *pairs, int64_t *scratch_bytes);
 
 /* rcpp_get_base_freqs on a resident batch (see epi_get_base_freqs): d_site_chr / d_site_pos are nsite device int32
  * (rname codes, 1-based positions) sorted by (code, pos), NA-coded sites removed -- equal keys (multi-ALT records) are
