@@ -1,6 +1,7 @@
 // Internal declarations shared by the engine's translation units (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <string>
 #include <map>
@@ -43,6 +44,30 @@ struct Tile {            // one work item of the tile kernels
   int32_t row_lo, row_hi;// candidate rows: same rname, start in (pos0 - Lmax, pos0 + kTile)
   int32_t slot;          // >=0: accumulate into shared slab slot instead of emitting
 };
+
+// The scalars the kernels of a report and the host exchange (epi_batch::misc holds one of these; report_scalars()).  The
+// tile-index pass (tiles.hip) leaves the tile count and zeroes the counters of the report that follows; the report reads
+// the block back at its synchronisation.  Kernels take `&sc->field`, the host copies into an instance of its own.
+struct Scalars {
+  uint32_t ntiles;         // [0] tiles the index pass counted (0xFFFFFFFF: a remembered count no longer holds)
+  uint32_t cursor;         // [1] rows handed out of the pool's overflow region (may exceed its size) ...
+                           //     ... or, CX direct mode (no pool): tiles whose row count differed from the kept one
+  uint32_t rows;           // [2] output rows: the total of the scan over the tiles' row counts
+  uint32_t heavy_count;    // [3] CX, two-kernel lMHL: ultra-deep tiles set aside ...
+                           //     ... or, one-pass lMHL kernel: deep tiles it listed for the two-kernel path
+  uint32_t deep_count;     // [4] CX: tiles the lean kernel hands to the general one
+  uint32_t fold_cursor;    // [5] one-pass lMHL kernel: slab slots handed out for folded call counters
+  uint32_t unused6[2];
+  uint32_t heavy_max;      // [8] candidate rows of the largest heavy tile
+  uint32_t unused9[3];
+  uint32_t rec_max[2];     // [12-13] two-kernel lMHL pass 1: a 64-bit maximum over the reads' record counts
+  uint32_t max_h;          // [14] ... and the longest stretch
+  uint32_t pat_total;      // [15] extractPatterns: patterns found
+};
+static_assert(offsetof(Scalars, ntiles) == 0 && offsetof(Scalars, cursor) == 4 && offsetof(Scalars, rows) == 8 &&
+              offsetof(Scalars, heavy_count) == 12 && offsetof(Scalars, deep_count) == 16 && offsetof(Scalars, fold_cursor) == 20 &&
+              offsetof(Scalars, heavy_max) == 32 && offsetof(Scalars, rec_max) == 48 && offsetof(Scalars, max_h) == 56 &&
+              offsetof(Scalars, pat_total) == 60 && sizeof(Scalars) == 64, "Scalars layout");
 
 // ---- device buffers that grow on demand --------------------------------------
 struct DevBuf {
@@ -146,7 +171,7 @@ struct epi_batch {
   epi::DevBuf scan_tmp;
   epi::DevBuf tiles, tile_nrow, tile_base, tile_out;
   epi::DevBuf pool_key, pool_a, pool_b, pool_c, pool_d, pool_e, pool_f;
-  epi::DevBuf misc;         // cursor etc.
+  epi::DevBuf misc;         // epi::Scalars (256 bytes allocated)
   epi::DevBuf mhl_m, mhl_h, mhl_blk, mhl_cont, mhl_cur;   // lMHL pass 1: stretch records, per-read info, record table, block carries
   size_t mhl_rec_cap = 0;   // records that fit mhl_m
   epi::DevBuf heavy_list, heavy_slab, heavy_sums;   // ultra-deep tiles: ids and dense counters (+ lMHL sums)
@@ -173,9 +198,7 @@ struct epi_batch {
   // earlier report on this (immutable) batch and tile size found no ultra-deep tile that the host would have to finish
   // before the slab may travel (cx_noheavy_T / _rows: the tile size and threshold that was observed for).
   bool cx_defer = false, cx_deferred = false;
-  bool cx_def_hinted = false;
   uint32_t cx_def_heavy_done = 0;
-  size_t cx_def_headroom = 0;
   int32_t cx_noheavy_T = 0, cx_noheavy_rows = 0;
   int cx_last_np = 0;                          // ... its number of reported contexts and their codes
   uint32_t cx_last_ctx_of_plane = 0;
@@ -199,12 +222,11 @@ struct epi_batch {
   int32_t tile_hint_nt[4] = {0, 0, 0, 0};
   int32_t tile_hint_lmax[4] = {0, 0, 0, 0};
   epi::DevBuf tile_bsum[4];                  // ... and the scanned per-block tile counts of the index build
-  int32_t last_tile = 0;    // tile size of the last CX report
   // The tile table itself is a function of (rname, start, longest row, tile size, shared keys): while the batch owns its
   // columns the table of the last build is still valid for the same tile size and keys, and build_tiles skips the pass.
   int32_t tiles_T = 0, tiles_nt = 0, tiles_lmax = 0;
   std::vector<int64_t> tiles_shared;
-  epi::DevBuf tiles_nt_dev;                  // the tile count as the index pass left it in misc[0]
+  epi::DevBuf tiles_nt_dev;                  // the tile count as the index pass left it in Scalars::ntiles
 
   // multi-GPU shared tiles
   std::vector<int64_t> shared_keys;
@@ -230,6 +252,10 @@ struct CopyPart { void *dst; const void *src; size_t bytes; };
 int copy_parts_to_host(epi_engine *eng, const CopyPart *parts, int nparts, hipStream_t s);
 int copy_to_host(epi_engine *eng, void *h_dst, const void *d_src, size_t bytes, hipStream_t s);
 int read_scalars(epi_batch *b, hipStream_t s, const void *d_src, size_t bytes, void *h_dst);  // sync D2H of a few bytes
+inline Scalars *report_scalars(const epi_batch *b) { return b->misc.as<Scalars>(); }
+inline int read_report_scalars(epi_batch *b, hipStream_t s, Scalars *h) {                   // the whole block, one sync
+  return read_scalars(b, s, report_scalars(b), sizeof(Scalars), h);
+}
 
 // Host blocks of library-owned report tables (capi.hip).  A large block given back by epi_*_table_free is kept (two blocks,
 // at most 1 GiB) and handed to the next table of a similar size: its pages are already mapped, where a fresh 168 MB block
@@ -332,7 +358,7 @@ int layout_copy_range(const uint8_t *src, int64_t c0, int64_t c1, const int64_t 
                       int64_t row_a, int64_t nrows, int g, uint8_t *dst, hipStream_t s);
 // row statistics (validated: errors for bad offsets/strands/unsorted rows) + tile table; one host sync
 // `hinted` (may be null): the caller accepts a tile count remembered from an earlier call on this batch and tile size
-// (no host round trip in the middle of the index build) and verifies it against misc[0] at its own synchronisation.
+// (no host round trip in the middle of the index build) and verifies it against Scalars::ntiles at its own synchronisation.
 int build_tiles(epi_batch *b, hipStream_t s, int32_t tile_positions, RowStats *h_stats, int32_t *ntiles_out, bool *hinted = nullptr);
 
 // Result-neutral switches (test hooks that steer a call onto a rarely taken path, A/B shapes): read from the environment
@@ -341,7 +367,6 @@ struct Options {
   int device = 0;            // EPIHIP_DEVICE        device of the default engine (host-pointer entry points)
   int cx_slot = -1;          // EPIHIP_CX_SLOT       pool rows per tile slot of the CX report (-1: adaptive)
   int cx_lean = 1;           // EPIHIP_CX_LEAN=0     the general (u16-folding) CX kernel for every tile
-  int cx_walk = 0;           // EPIHIP_CX_WALK=K     timing builds with -DEPI_CX_WALK_BUILD only: K consecutive tiles per workgroup of the lean CX kernel
   int cx_direct = 1;         // EPIHIP_CX_DIRECT=0   CX reports through the row pool and the gather even where the tile kernel could
                              //                      write the caller's columns
   int heavy_rows = 0;        // EPIHIP_HEAVY_ROWS    candidate rows above which a tile is split / set aside (0: default)

@@ -42,6 +42,12 @@
 // every tile is finished inside the launch (direct mode), the emit writes the final columns itself.  Ultra-deep tiles are
 // split over many workgroups through a slab in HBM; tiles
 // shared with other ranks of a sharded run hand over the same slab for the RCCL all-reduce.
+//
+// Host side (cx_report_impl): thresholding set-up (cx_setup_threshold), pool layout (cx_layout_pool), kernel arguments
+// (cx_fill_args, cx_bind_pool), then at most one direct-mode attempt and at most two pool runs (cx_queue_attempt,
+// cx_finish_pool_run); kernels and host exchange their counters through the fields of Scalars (common.hpp).
+// This file holds the product kernels and the compile-time knobs that measure them (EPI_CX_ABLATE and the shape
+// constants, `make timing`); experiments that lost are recorded in profiles/r04_cx_experiments.txt, not kept here.
 #include "common.hpp"
 #include "tile_common.hpp"
 #include <stdio.h>
@@ -108,7 +114,6 @@ struct Cx2Args {
   const uint32_t *tile_list, *tile_list_count;   // general kernel behind a lean one: the list to work through
   uint32_t *dbg;                          // check build only (EPI_CHECK): first index violation; null in the product
   int64_t nrows;                          // rows of the batch (check build)
-  int walk;                               // walking lean kernel: consecutive tiles per workgroup
   // Direct mode (prev_off != null): the emit writes the final columns rname, strand, pos, context, meth, unmeth itself --
   // no pool, no scan, no gather.  A tile's first row is where the last pool report on this batch with the same contexts
   // put it.  For valid XM codes a tile's row count depends on the rows and the contexts alone (thresholds change M, not
@@ -124,23 +129,18 @@ struct Cx2Args {
 
 // LEAN: no position of the batch is covered by more than 255 rows (RowStats::deep == 0, tiles.hip), so the u8 counters
 // cannot overflow however many rows a tile has: no u16 copy, no folds, the emit reads the u8 counters.
-// PAD > 0 (a WALKING workgroup, lean kernel only): the arrays hold W = T + PAD positions -- the tile and the reach of its
-// own rows into the next tile.  The workgroup works through consecutive tiles; after a tile's emit the PAD positions
-// behind it are shifted to the front and become the next tile's opening state, so that a row is analysed ONCE, by the
-// tile it starts in (without it 15 % of the PE150 row visits of a 2048-position tile are second visits of rows that
-// reach into the next tile: each a full load + thresholding decision).
-template <int T, int NP, bool LEAN = false, int PAD = 0> struct Cx2Lds {
-  static_assert(PAD == 0 || (LEAN && PAD % 16 == 0 && PAD <= T), "the window is a lean-kernel feature");
-  static constexpr int TILE = T, W = T + PAD;    // positions of the tile / held in LDS
-  static constexpr int Q = W / 4;
+template <int T, int NP, bool LEAN = false> struct Cx2Lds {
+  static constexpr int Q = T / 4;
   static constexpr int N_NARROW = 2 * NP * Q;    // u64: [strand][plane][Q], low dword = n of 4 positions (u8), high = M
   static constexpr int N_CORR = 2 * Q;           // u64: [strand][Q], low dword = skipped, high = doubled (u8 x 4)
   static constexpr int N_WIDE = LEAN ? 16 : 2 * NP * T;   // u32: [strand][plane][T] = n | M << 16 (LEAN: scan scratch only)
-  static constexpr int N_COV = W;                // u32: coverage difference array, '+' in the low half, '-' in the high half
-                                                 // (a change "behind the window" is simply not recorded)
+  static constexpr int N_COV = T;                // u32: coverage difference array, '+' in the low half, '-' in the high half
+                                                 // (a change behind the tile is simply not recorded)
   unsigned long long *narrow, *corr;
   uint32_t *wide, *cov;
-  uint32_t tid;                                  // threadIdx.x (a walking workgroup reads it anew for every tile, see k_cx_tiles)
+  uint32_t tid;                                  // threadIdx.x, read once where the arrays are declared (CX2_SHARED): the helpers below
+                                                 // take it from here -- reading the builtin at every use costs the row loop registers
+                                                 // (spill counts of 17 kernel shapes change, profiles/cx_host_refactor.txt)
 };
 
 // 16-entry byte LUT lookup of the four codes of a dword in two v_perm_b32 (X: the table in lut16_xor_form, common.hpp);
@@ -249,7 +249,7 @@ __device__ __forceinline__ void cx2_mask_upto(int hi /* 1..16 */, uint32_t (&m)[
 template <int T, int G, int NU, int NP, bool FUSED, int MODE = 0, class LT, class F>
 __device__ __forceinline__ void cx2_visit(const Cx2Args &a, Cx2Row &g, int32_t cs, int32_t cz, int sub, int rcur,
                                           const LT &L, F fetch_next, uint32_t *carry = nullptr) {
-  constexpr int C = LT::W / CX_CH, Q = LT::Q;                       // chunks / u64 cells per strand of the window (= the tile unless the workgroup walks)
+  constexpr int C = T / CX_CH, Q = LT::Q;                           // chunks / u64 cells per strand of the tile
   const int32_t cb = cs + sub;                                      // this lane's chunks: cb + u*G
   const int32_t tl = cz - cb;                                       // chunk u is part of the visit iff u*G <= tl
   uint32_t w[NU][4];
@@ -418,7 +418,7 @@ __device__ __forceinline__ void cx2_visit(const Cx2Args &a, Cx2Row &g, int32_t c
     uint32_t clean = 0xFFFFFFFFu;                                     // bit 3 of every nibble stays set while no rare code was seen
 #pragma unroll
     for (int u = 0; u < NU; u++) {
-      const bool inside = (uint32_t)(cb + u * G) < (uint32_t)C;      // (always: the visit stays inside the window)
+      const bool inside = (uint32_t)(cb + u * G) < (uint32_t)C;      // (always: the visit stays inside the tile)
 #pragma unroll
       for (int e = 0; e < 2; e++) {
         const uint32_t pk = (w[u][2 * e] & 0x0F0F0F0Fu) | ((w[u][2 * e + 1] << 4) & 0xF0F0F0F0u);
@@ -485,25 +485,15 @@ __device__ __forceinline__ void cx2_visit(const Cx2Args &a, Cx2Row &g, int32_t c
 // wavefront step); the next step's row columns are fetched while the current row's bytes are in flight.
 template <int T, int G, int NU, int NP, bool FUSED, int WG, class LT>
 __device__ __forceinline__ void cx2_rows(const Cx2Args &a, const Tile &td, int row_lo, int row_hi, const LT &L) {
-  constexpr int R = 64 / G, NW = WG / 64, C = LT::W / CX_CH, TW = LT::W;
+  constexpr int R = 64 / G, NW = WG / 64, C = T / CX_CH;
   const int lane = L.tid & 63, wave = L.tid >> 6;
   const int sub = lane & (G - 1), grp = lane / G;
   Tile tb = td;
   tb.row_hi = row_hi;
   int r = row_lo + wave * R + grp;
   RowVals v = cx_load_row(a.c, tb, r);
-#ifdef EPI_CX_TOUCH
-  // Timing builds: one dword per 128-byte line of the row this lane group will work on TWO steps from now is requested
-  // (and dropped) a step ahead of its columns: the bytes are on their way from HBM into the L2 while the step in between
-  // is worked on.  Rows lie back to back in xm, so the row two steps ahead starts about as far behind the next step's row
-  // as that one behind the current row.
-  uint32_t touched = 0;
-#endif
   for (int rbase = row_lo + wave * R; rbase < row_hi; rbase += NW * R) {
     const int rcur = r;
-#ifdef EPI_CX_TOUCH
-    const int64_t o_cur = v.o;
-#endif
     if (!EPI_DEV_CHECK(a.dbg, !v.ok || (rcur >= 0 && rcur < a.nrows && v.len >= 0 && (v.sd == 1 || v.sd == 2 || v.len == 0)), 22, rcur, v.sd)) return;
     r += NW * R;
     RowVals nv;
@@ -550,34 +540,22 @@ __device__ __forceinline__ void cx2_rows(const Cx2Args &a, const Tile &td, int r
         }
       }
       if (sub == 0) {                                                 // coverage: +1 on the row's positions inside the tile
-        const int32_t ca = g.rel > 0 ? g.rel : 0, cb = g.rel + v.len < TW ? g.rel + v.len : TW;
+        const int32_t ca = g.rel > 0 ? g.rel : 0, cb = g.rel + v.len < T ? g.rel + v.len : T;
         const uint32_t unit = g.sidx ? 65536u : 1u;
-        if (ca < cb && !(EPI_CX_ABLATE & 32)) { atomicAdd(L.cov + ca, unit); if (cb < TW) atomicAdd(L.cov + cb, 0u - unit); }
+        if (ca < cb && !(EPI_CX_ABLATE & 32)) { atomicAdd(L.cov + ca, unit); if (cb < T) atomicAdd(L.cov + cb, 0u - unit); }
       }
     } else if (FUSED && v.ok && sub == 0 && a.pass_out && (uint32_t)((uint32_t)v.st - (uint32_t)td.pos0) < (uint32_t)T) {
       a.pass_out[rcur] = 0;             // an empty read has no call of the context: fails (rcpp_threshold_reads.cpp:43)
     }
     fetch_next();
     v = nv;
-#ifdef EPI_CX_TOUCH
-    asm volatile("" :: "v"(touched));                       // (the previous request has come back by now; its value is of no interest)
-    {
-      int64_t t = v.o + (v.o - o_cur) + 128 * sub;
-      if (!v.ok || t < 0) t = 0;
-      if (t > a.xm_cap - 4) t = a.xm_cap - 4;
-      touched = *reinterpret_cast<const uint32_t *>(a.c.xm + (t & ~(int64_t)3));
-    }
-#endif
   }
-#ifdef EPI_CX_TOUCH
-  asm volatile("" :: "v"(touched));
-#endif
 }
 
 // u8 counters -> u16 pairs, skipped / doubled codes -> coverage difference array.  Every cell has one owner thread.
-template <int T, int NP, bool LEAN, int WG, int PAD = 0>
-__device__ __forceinline__ void cx2_flush(const Cx2Lds<T, NP, LEAN, PAD> &L) {
-  constexpr int Q = Cx2Lds<T, NP, LEAN, PAD>::Q, TW = Cx2Lds<T, NP, LEAN, PAD>::W;
+template <int T, int NP, bool LEAN, int WG>
+__device__ __forceinline__ void cx2_flush(const Cx2Lds<T, NP, LEAN> &L) {
+  constexpr int Q = Cx2Lds<T, NP, LEAN>::Q;
   if constexpr (!LEAN) {
     for (int i = L.tid; i < 2 * NP * Q; i += WG) {
       const unsigned long long v = L.narrow[i];
@@ -608,7 +586,7 @@ __device__ __forceinline__ void cx2_flush(const Cx2Lds<T, NP, LEAN, PAD> &L) {
       if (d != prev) atomicAdd(L.cov + 4 * q + j, (uint32_t)((d - prev) * unit));
       prev = d;
     }
-    if (prev != 0 && 4 * q + 4 < TW) atomicAdd(L.cov + 4 * q + 4, (uint32_t)(-prev * unit));
+    if (prev != 0 && 4 * q + 4 < T) atomicAdd(L.cov + 4 * q + 4, (uint32_t)(-prev * unit));
   }
 }
 
@@ -623,7 +601,7 @@ __device__ __forceinline__ uint32_t cx_pool_reserve(const Cx2Args &a, int tile, 
 }
 
 // A tile that emits nothing in this launch (set aside, handed over): in direct mode its recorded count must be 0.
-__device__ __forceinline__ void cx_direct_none(const Cx2Args &a, int tile, uint32_t tid) {
+__device__ __forceinline__ void cx_direct_none(const Cx2Args &a, int tile, uint32_t tid = threadIdx.x) {
   if (a.prev_off && tid == 0 && a.prev_nrow[tile] != 0u) atomicAdd(a.mismatch, 1u);
 }
 
@@ -810,17 +788,16 @@ __device__ __forceinline__ void cx2_emit(const Cx2Args &a, int tile, const SRC &
 
 // Adds a tile's (folded) LDS sums into its dense slab [16][T] in HBM (shared tiles, heavy tiles).  The coverage
 // array goes over un-summed: difference arrays add across work items and ranks like everything else.
-template <int T, int NP, bool LEAN, int WG, int PAD = 0>
-__device__ __forceinline__ void cx2_dump_slab(const Cx2Lds<T, NP, LEAN, PAD> &L, int32_t *slab) {
+template <int T, int NP, bool LEAN, int WG>
+__device__ __forceinline__ void cx2_dump_slab(const Cx2Lds<T, NP, LEAN> &L, int32_t *slab) {
   uint32_t *dst = reinterpret_cast<uint32_t *>(slab);
   if constexpr (LEAN) {
-    constexpr int Q = Cx2Lds<T, NP, LEAN, PAD>::Q;
+    constexpr int Q = Cx2Lds<T, NP, LEAN>::Q;
     for (int i = L.tid; i < 2 * NP * Q; i += WG) {
       const unsigned long long v = L.narrow[i];
       if (v == 0ull) continue;
       const uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
       const int sp = i / Q, q = i - sp * Q;
-      if (PAD > 0 && q >= T / 4) continue;                 // (behind the tile: the next tile's share of a walking workgroup's window)
 #pragma unroll
       for (int j = 0; j < 4; j++) {
         const uint32_t n = (lo >> (8 * j)) & 255u, M = (hi >> (8 * j)) & 255u;
@@ -857,15 +834,15 @@ __device__ __forceinline__ int cx_tile_of_block(int b, int ntiles) {
 }
 
 // workgroups per CU by LDS (the u8 arrays double as the emit phase's candidate lists) and the 2048-thread limit
-template <int T, int NP, bool LEAN = false, int PAD = 0> constexpr int cx2_lds_bytes() {
-  using LdsT = Cx2Lds<T, NP, LEAN, PAD>;
+template <int T, int NP, bool LEAN = false> constexpr int cx2_lds_bytes() {
+  using LdsT = Cx2Lds<T, NP, LEAN>;
   return (LdsT::N_NARROW + LdsT::N_CORR) * 8 + (LdsT::N_WIDE + LdsT::N_COV) * 4;
 }
 #ifndef EPI_CX_WPS
 #define EPI_CX_WPS 8
 #endif
-template <int T, int NP, int NU = 3, bool LEAN = false, int WG = CX_WG, int PAD = 0> constexpr int cx2_waves_per_simd() {
-  const int by_lds = (160 * 1024) / (cx2_lds_bytes<T, NP, LEAN, PAD>() + 64), by_thr = 2048 / WG;
+template <int T, int NP, int NU = 3, bool LEAN = false, int WG = CX_WG> constexpr int cx2_waves_per_simd() {
+  const int by_lds = (160 * 1024) / (cx2_lds_bytes<T, NP, LEAN>() + 64), by_thr = 2048 / WG;
   int wgs = by_lds < by_thr ? by_lds : by_thr;
   if (NU >= 4 && wgs * WG > 1536) wgs = 1536 / WG;        // five chunks per lane in flight need ~80 VGPRs: 6 waves per SIMD
   if (wgs * WG / 256 > EPI_CX_WPS) wgs = EPI_CX_WPS * 256 / WG;
@@ -874,8 +851,8 @@ template <int T, int NP, int NU = 3, bool LEAN = false, int WG = CX_WG, int PAD 
 
 // LDS of a tile workgroup.  The emit phase's candidate lists (4 T bytes) and scan scratch reuse arrays that are dead by
 // then: the u8 counters and `corr` (general kernel), or `corr` and the small `wide` stub (LEAN: the counters are read).
-#define CX2_SHARED(T, NP, LEAN, PAD)                                                                             \
-  using LdsT = Cx2Lds<T, NP, LEAN, PAD>;                                                                         \
+#define CX2_SHARED(T, NP, LEAN)                                                                                  \
+  using LdsT = Cx2Lds<T, NP, LEAN>;                                                                              \
   __shared__ __attribute__((aligned(16))) unsigned long long s_u8[LdsT::N_NARROW + LdsT::N_CORR];                \
   __shared__ __attribute__((aligned(16))) uint32_t s_wide[LdsT::N_WIDE];                                         \
   __shared__ __attribute__((aligned(16))) uint32_t s_cov[LdsT::N_COV];                                           \
@@ -886,9 +863,9 @@ template <int T, int NP, int NU = 3, bool LEAN = false, int WG = CX_WG, int PAD 
   LdsT L;                                                                                                         \
   L.narrow = s_u8; L.corr = s_u8 + LdsT::N_NARROW; L.wide = s_wide; L.cov = s_cov; L.tid = threadIdx.x;
 
-template <int T, int NP, bool LEAN, int WG, int PAD = 0>
-__device__ __forceinline__ void cx2_clear(const Cx2Lds<T, NP, LEAN, PAD> &L) {
-  using LdsT = Cx2Lds<T, NP, LEAN, PAD>;
+template <int T, int NP, bool LEAN, int WG>
+__device__ __forceinline__ void cx2_clear(const Cx2Lds<T, NP, LEAN> &L) {
+  using LdsT = Cx2Lds<T, NP, LEAN>;
   uint4 *z = reinterpret_cast<uint4 *>(L.narrow);
   for (int i = L.tid; i < (LdsT::N_NARROW + LdsT::N_CORR) / 2; i += WG) z[i] = make_uint4(0, 0, 0, 0);
   if constexpr (!LEAN) {
@@ -900,8 +877,8 @@ __device__ __forceinline__ void cx2_clear(const Cx2Lds<T, NP, LEAN, PAD> &L) {
 }
 
 // rows [row_lo, row_hi) of a tile, folded every CX_FLUSH_ROWS rows; leaves everything in `wide` and `cov`
-template <int T, int G, int NU, int NP, bool FUSED, bool LEAN, int WG, int PAD = 0>
-__device__ __forceinline__ void cx2_accumulate(const Cx2Args &a, const Tile &td, int row_lo, int row_hi, const Cx2Lds<T, NP, LEAN, PAD> &L) {
+template <int T, int G, int NU, int NP, bool FUSED, bool LEAN, int WG>
+__device__ __forceinline__ void cx2_accumulate(const Cx2Args &a, const Tile &td, int row_lo, int row_hi, const Cx2Lds<T, NP, LEAN> &L) {
   if constexpr (LEAN) {
     cx2_rows<T, G, NU, NP, FUSED, WG>(a, td, row_lo, row_hi, L);
   } else {
@@ -911,7 +888,7 @@ __device__ __forceinline__ void cx2_accumulate(const Cx2Args &a, const Tile &td,
     }
   }
   __syncthreads();
-  cx2_flush<T, NP, LEAN, WG, PAD>(L);
+  cx2_flush<T, NP, LEAN, WG>(L);
   __syncthreads();
 }
 
@@ -922,57 +899,11 @@ __device__ __forceinline__ void cx2_accumulate(const Cx2Args &a, const Tile &td,
 #endif
 template <bool LEAN> constexpr int cx2_wg() { return LEAN ? EPI_CX_LEAN_WG : CX_WG; }
 
-// A walking workgroup's step from one tile to the next: the PAD positions behind the tile become the front of the window.
-// `narrow` moves as it is; `cov` -- prefix-summed in place over the tile by now -- hands on its running sum (the coverage
-// entering the next tile) in the new first entry, followed by the un-summed differences behind the tile; `corr` was folded
-// into `cov` by the flush and then used as the emit's candidate list: cleared.  Values travel through registers between
-// two barriers (source and destination ranges of different threads overlap).
-template <int T, int NP, int WG, int PAD>
-__device__ __forceinline__ void cx2_shift(const Cx2Lds<T, NP, true, PAD> &L) {
-  using LdsT = Cx2Lds<T, NP, true, PAD>;
-  constexpr int Q = LdsT::Q, QT = T / 4, QP = PAD / 4, NN = 2 * NP * QP;      // u64 cells per strand and plane: window, tile, overhang
-  constexpr int KN = (NN + WG - 1) / WG, KC = (PAD + WG - 1) / WG;
-  unsigned long long nv[KN];
-  uint32_t cv[KC];
-#pragma unroll
-  for (int k = 0; k < KN; k++) {
-    const int i = (int)L.tid + k * WG;
-    nv[k] = i < NN ? L.narrow[(i / QP) * Q + QT + (i % QP)] : 0ull;
-  }
-#pragma unroll
-  for (int k = 0; k < KC; k++) {
-    const int i = (int)L.tid + k * WG;
-    cv[k] = i < PAD ? L.cov[T + i] + (i == 0 ? L.cov[T - 1] : 0u) : 0u;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < KN; k++) {
-    const int i = (int)L.tid + k * WG;
-    if (i < NN) L.narrow[(i / QP) * Q + (i % QP)] = nv[k];
-  }
-#pragma unroll
-  for (int k = 0; k < KC; k++) {
-    const int i = (int)L.tid + k * WG;
-    if (i < PAD) L.cov[i] = cv[k];
-  }
-  // everything behind the carried part starts at zero (16-byte stores: QP, QT and PAD are multiples of 4)
-  for (int i = L.tid; i < 2 * NP * (QT / 2); i += WG) {
-    const int sp = i / (QT / 2), j = i - sp * (QT / 2);
-    *reinterpret_cast<uint4 *>(L.narrow + sp * Q + QP + 2 * j) = make_uint4(0, 0, 0, 0);
-  }
-  for (int i = L.tid; i < T / 4; i += WG) *reinterpret_cast<uint4 *>(L.cov + PAD + 4 * i) = make_uint4(0, 0, 0, 0);
-  for (int i = L.tid; i < LdsT::N_CORR / 2; i += WG) *reinterpret_cast<uint4 *>(L.corr + 2 * i) = make_uint4(0, 0, 0, 0);
-}
-
-// One tile: accumulate, then hand over (heavy / shared / deep tiles) or emit.  `fresh`: the arrays do not hold the previous
-// tile's overhang (always, unless the workgroup walks): they are cleared and every candidate row of the tile is visited;
-// otherwise only the rows that start in the tile, [row_from, row_hi).  Returns false when the tile was handed over without
-// being accumulated (a walking workgroup then has nothing to carry on).
-template <int T, int G, int NU, int NP, bool FUSED, bool LEAN, int PAD, class LdsT>
-__device__ __forceinline__ bool cx2_tile(const Cx2Args &a, int tile, const Tile &td, bool fresh, int row_from, const LdsT &L, uint32_t *s_scan,
-                                         uint16_t *s_list, int *s_flag) {
+// One tile: clear, accumulate the candidate rows [td.row_lo, td.row_hi), then hand over (heavy / shared / deep tiles) or emit.
+template <int T, int G, int NU, int NP, bool FUSED, bool LEAN, class LdsT>
+__device__ __forceinline__ void cx2_tile(const Cx2Args &a, int tile, const Tile &td, const LdsT &L, uint32_t *s_scan, uint16_t *s_list, int *s_flag) {
   constexpr int WG = cx2_wg<LEAN>();
-  if (fresh) cx2_clear<T, NP, LEAN, WG, PAD>(L);
+  cx2_clear<T, NP, LEAN, WG>(L);
   if (td.row_hi - td.row_lo > a.heavy_rows) {
     // one workgroup would crawl through this pile-up alone: k_cx_heavy splits it by row chunks instead
     if (L.tid == 0) {
@@ -983,14 +914,13 @@ __device__ __forceinline__ bool cx2_tile(const Cx2Args &a, int tile, const Tile 
       a.tile_base[tile] = 0;
     }
     cx_direct_none(a, tile, L.tid);
-    return false;
+    return;
   }
   if constexpr (LEAN) {
     // u8 counters hold 255 rows per position.  Few enough candidate rows: safe.  Else the sorted starts decide: rows
     // covering a position p all start before the end of the first of them, so if row x + 255 starts at or behind the end
     // of row x for every candidate x, no position of the tile is covered by more than 255 rows (tiles.hip: k_row_stats
-    // asks the same of the whole batch).  A tile that fails goes to the general kernel's list.  (The overhang a walking
-    // workgroup carries into the tile comes from candidate rows of the tile as well: the criterion covers it.)
+    // asks the same of the whole batch).  A tile that fails goes to the general kernel's list.
     if (a.deep_list && td.row_hi - td.row_lo > CX_FLUSH_ROWS) {
       if (L.tid == 0) *s_flag = 0;
       __syncthreads();
@@ -1002,21 +932,20 @@ __device__ __forceinline__ bool cx2_tile(const Cx2Args &a, int tile, const Tile 
       if (*s_flag) {
         if (L.tid == 0) { a.deep_list[atomicAdd(a.deep_count, 1u)] = (uint32_t)tile; a.tile_nrow[tile] = 0; a.tile_base[tile] = 0; }
         cx_direct_none(a, tile, L.tid);
-        return false;
+        return;
       }
     }
   }
   __syncthreads();
-  cx2_accumulate<T, G, NU, NP, FUSED, LEAN, WG, PAD>(a, td, row_from, td.row_hi, L);
+  cx2_accumulate<T, G, NU, NP, FUSED, LEAN, WG>(a, td, td.row_lo, td.row_hi, L);
   if (td.slot >= 0) {
-    // shared with another rank: hand the raw sums over (a carried-in coverage is part of the first difference)
-    cx2_dump_slab<T, NP, LEAN, WG, PAD>(L, a.slab + (int64_t)td.slot * (kCxPlanes * T));
+    // shared with another rank: hand the raw sums over
+    cx2_dump_slab<T, NP, LEAN, WG>(L, a.slab + (int64_t)td.slot * (kCxPlanes * T));
     if (L.tid == 0) { a.tile_nrow[tile] = 0; a.tile_base[tile] = 0; }
     cx_direct_none(a, tile, L.tid);
-    if constexpr (PAD > 0) { __syncthreads(); cx2_prefix<T, WG>(L.cov, s_scan, L.tid); }    // (the walk goes on from the summed coverage)
-    return true;
+    return;
   }
-  if (EPI_CX_ABLATE & 16) { if (L.tid == 0) { a.tile_nrow[tile] = 0; a.tile_base[tile] = 0; } cx_direct_none(a, tile, L.tid); return true; }
+  if (EPI_CX_ABLATE & 16) { if (L.tid == 0) { a.tile_nrow[tile] = 0; a.tile_base[tile] = 0; } cx_direct_none(a, tile, L.tid); return; }
   // (a list-free emit -- every thread ruling on its own 8 cells, two barriers instead of four -- measured 1-2 % slower)
   cx2_prefix<T, WG>(L.cov, s_scan, L.tid);
   if constexpr (LEAN) {
@@ -1029,79 +958,35 @@ __device__ __forceinline__ bool cx2_tile(const Cx2Args &a, int tile, const Tile 
     src.wide = L.wide; src.cov = L.cov;
     cx2_emit<T, NP, WG>(a, tile, src, s_scan, s_list, L.tid);
   }
-  return true;
 }
 
-template <int T, int G, int NU, int NP, bool FUSED, bool LEAN, int PAD = 0>
-__global__ __launch_bounds__(cx2_wg<LEAN>(), (cx2_waves_per_simd<T, NP, NU, LEAN, cx2_wg<LEAN>(), PAD>())) void k_cx_tiles(Cx2Args a, int ntiles) {
-  CX2_SHARED(T, NP, LEAN, PAD)
+template <int T, int G, int NU, int NP, bool FUSED, bool LEAN>
+__global__ __launch_bounds__(cx2_wg<LEAN>(), (cx2_waves_per_simd<T, NP, NU, LEAN, cx2_wg<LEAN>()>())) void k_cx_tiles(Cx2Args a, int ntiles) {
+  CX2_SHARED(T, NP, LEAN)
   __shared__ int s_flag;
-#ifdef EPI_CX_LDS_PAD                                      // timing builds: LDS that nobody uses (workgroups per CU by LDS)
-  __shared__ uint32_t s_pad[EPI_CX_LDS_PAD / 4];
-  if (a.xm_cap == -12345) s_pad[threadIdx.x] = 1;
-#endif
   if constexpr (!LEAN) {
     if (a.tile_list) {                                    // behind a lean launch: the tiles it listed, however many (fixed grid)
       const uint32_t n = *a.tile_list_count;
       for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
         const int tile = (int)a.tile_list[i];
         const Tile td = a.tiles[tile];
-        cx2_tile<T, G, NU, NP, FUSED, LEAN, 0>(a, tile, td, true, td.row_lo, L, s_scan, s_list, &s_flag);
+        cx2_tile<T, G, NU, NP, FUSED, LEAN>(a, tile, td, L, s_scan, s_list, &s_flag);
         __syncthreads();                                  // (the next tile clears the arrays the emit just read)
       }
       return;
     }
   }
-  if constexpr (PAD > 0) {
-    // A WALKING workgroup: a.walk consecutive entries of the tile table.  While the next entry is the genomic neighbour of
-    // the one just finished, its opening state is the shifted overhang and only the rows that start in it -- the rows
-    // behind the previous entry's last row -- are visited; the first tile of a walk, and one behind a gap, a change of
-    // reference sequence or a tile that was handed over (heavy, deep), starts from cleared arrays and visits all its
-    // candidate rows, like a workgroup that does not walk.
-    const int walk = a.walk;
-    const int nruns = (ntiles + walk - 1) / walk;
-    const int run = cx_tile_of_block(blockIdx.x, nruns);
-    if (run >= nruns) return;
-    const int t0 = run * walk, t1 = t0 + walk < ntiles ? t0 + walk : ntiles;
-    // (the tile table through a constant-address-space pointer: it was written by the index kernel before this one and is
-    //  read-only here, and this way a descriptor is a scalar load -- the next tile's is requested a whole tile ahead)
-    typedef const Tile __attribute__((address_space(4))) *TileK;
-    const TileK tk = (TileK)(uintptr_t)a.tiles;
-    bool carry = false;
-    int64_t prev_pos0 = 0;
-    int32_t prev_rname = 0, prev_row_hi = 0;
-    auto tile_at = [&](int i) { Tile t; t.pos0 = tk[i].pos0; t.rname = tk[i].rname; t.row_lo = tk[i].row_lo; t.row_hi = tk[i].row_hi; t.slot = tk[i].slot; return t; };
-    Tile td = tile_at(t0);
-    for (int tile = t0; tile < t1; tile++) {
-      const Tile nxt = tile_at(tile + 1 < t1 ? tile + 1 : tile);
-      // The thread index is read anew for every tile (it passes through an empty asm): everything derived from it
-      // (lane-dependent LDS addresses, list slots of the emit) is otherwise computed once in front of the loop and kept in
-      // vector registers throughout (21 of them spilled to scratch, measured; this kernel does not survive scratch)
-      { uint32_t t = threadIdx.x; asm volatile("" : "+v"(t)); L.tid = t; }
-      const bool cont = carry && td.rname == prev_rname && td.pos0 == prev_pos0 + T;
-      const bool done = cx2_tile<T, G, NU, NP, FUSED, LEAN, PAD>(a, tile, td, !cont, cont ? prev_row_hi : td.row_lo, L, s_scan, s_list, &s_flag);
-      carry = done;
-      if (tile + 1 < t1) {
-        __syncthreads();                                  // (the emit has read the counters; a handed-over tile leaves them untouched)
-        if (done) { cx2_shift<T, NP, cx2_wg<LEAN>(), PAD>(L); __syncthreads(); }
-      }
-      prev_pos0 = td.pos0; prev_rname = td.rname; prev_row_hi = td.row_hi;
-      td = nxt;
-    }
-    return;
-  } else {
-    const int tile = cx_tile_of_block(blockIdx.x, ntiles);
-    if (tile >= ntiles) return;
-    const Tile td = a.tiles[tile];                        // (in flight while the counters are cleared)
-    cx2_tile<T, G, NU, NP, FUSED, LEAN, 0>(a, tile, td, true, td.row_lo, L, s_scan, s_list, &s_flag);
-  }
+  const int tile = cx_tile_of_block(blockIdx.x, ntiles);
+  if (tile >= ntiles) return;
+  const Tile td = a.tiles[tile];                          // (in flight while the counters are cleared)
+  cx2_tile<T, G, NU, NP, FUSED, LEAN>(a, tile, td, L, s_scan, s_list, &s_flag);
 }
 
 // One chunk of the candidate rows of one heavy tile: LDS sums as usual, then added into the tile's slab in HBM (or
 // straight into its shared slab slot when other ranks contribute too).
 template <int T, int G, int NU, int NP, bool FUSED>
 __global__ __launch_bounds__(CX_WG, (cx2_waves_per_simd<T, NP, NU>())) void k_cx_heavy(Cx2Args a) {
-  CX2_SHARED(T, NP, false, 0)
+  CX2_SHARED(T, NP, false)
   const uint32_t hi_idx = (uint32_t)a.heavy_first + blockIdx.y;
   if (hi_idx >= *a.heavy_count) return;
   const int tile = (int)a.heavy_list[hi_idx];
@@ -1165,7 +1050,7 @@ constexpr int CXP_T = EPI_CXP_T;
 template <int G, int U0, int U1>
 __device__ __forceinline__ void cxp_add_range(const uint32_t (&w)[CX_NU], const RowSlice &cur) {
   if constexpr (U0 < U1) {
-    if (U0 * G <= cur.tl) cx_add_dword<CXP_T, 4 * G * U0, U0 == 0, true>(w[U0], cur.tl == U0 * G, cur);
+    if (U0 * G <= cur.tl) cx_add_dword<CXP_T, 4 * G * U0, U0 == 0>(w[U0], cur.tl == U0 * G, cur);
     cxp_add_range<G, U0 + 1, U1>(w, cur);
   }
 }
@@ -1178,19 +1063,19 @@ __device__ __forceinline__ void cxp_accumulate(const RowCols &c, const Tile &td,
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int sub = lane & (G - 1), grp = lane / G;
   int r = td.row_lo + wave * R + grp;
-  RowSlice cur = cx_row_slice<CXP_T, G, true>(c, td, r, sub, cnt);
+  RowSlice cur = cx_row_slice<CXP_T, G>(c, td, r, sub, cnt);
   for (int rbase = td.row_lo + wave * R; rbase < td.row_hi; rbase += NW * R) {
     uint32_t w[CX_NU];                                    // every load of the slice is in flight before the first is used
 #pragma unroll
     for (int u = 0; u < CX_NU; u++) w[u] = u * G <= cur.tl ? cur.src[u * G] : 0u;
     r += NW * R;
-    const RowSlice nxt = cx_row_slice<CXP_T, G, true>(c, td, r, sub, cnt);
+    const RowSlice nxt = cx_row_slice<CXP_T, G>(c, td, r, sub, cnt);
     cxp_add_range<G, 0, CX_NU>(w, cur);
     for (int k = sub + CX_NU * G; k < cur.nd; k += G) {   // slices longer than CX_NU*G dwords
       RowSlice t = cur;
 #pragma unroll
       for (int j = 0; j < 4; j++) t.dst[j] = cur.dst[j] + 4 * (k - sub);
-      cx_add_dword<CXP_T, 0, false, true>(cur.src[k - sub], k == cur.nd - 1, t);
+      cx_add_dword<CXP_T, 0, false>(cur.src[k - sub], k == cur.nd - 1, t);
     }
     cur = nxt;
   }
@@ -1276,7 +1161,7 @@ __global__ __launch_bounds__(CX_WG, 8) void k_cxp_tiles(Cx2Args a, int ntiles, i
       a.tile_nrow[tile] = 0;
       a.tile_base[tile] = 0;
     }
-    cx_direct_none(a, tile, threadIdx.x);
+    cx_direct_none(a, tile);
     return;
   }
   __syncthreads();
@@ -1287,12 +1172,12 @@ __global__ __launch_bounds__(CX_WG, 8) void k_cxp_tiles(Cx2Args a, int ntiles, i
   if (td.slot >= 0) {                                     // shared with another rank: hand the sums over
     cxp_dump_slab(a, cnt, np, a.slab + (int64_t)td.slot * (kCxPlanes * CXP_T));
     if (threadIdx.x == 0) { a.tile_nrow[tile] = 0; a.tile_base[tile] = 0; }
-    cx_direct_none(a, tile, threadIdx.x);
+    cx_direct_none(a, tile);
     return;
   }
   if (EPI_CX_ABLATE & 16) {                               // timing builds: no emit
     if (threadIdx.x == 0) { a.tile_nrow[tile] = 0; a.tile_base[tile] = 0; }
-    cx_direct_none(a, tile, threadIdx.x);
+    cx_direct_none(a, tile);
     return;
   }
   cx2_emit<CXP_T, 3>(a, tile, cxp_source(a, cnt), s_scan, s_list);
@@ -1431,21 +1316,8 @@ static bool cx_fused_fits(const RowStats &st) {
 constexpr unsigned CX_HEAVY_CAP = 8, CX_HEAVY_GRID = 128;   // ultra-deep tiles finished without a host round trip, work items each
 constexpr unsigned CX_LIST_GRID = 512;        // workgroups of the general kernel behind a lean launch (they loop over the list)
 
-// (timing builds) A walking workgroup's window holds CX_PAD positions behind its tile: rows of up to CX_PAD - 15 bytes (a row's last
-// position-aligned chunk may end 15 positions behind its last byte), i.e. PE150 templates; four lanes per row.
-[[maybe_unused]] constexpr int CX_PAD = 320;
-
 template <int T, int NU, int NP, bool FUSED, bool LEAN>
 static void launch_cx_tiles(int g, int nt, hipStream_t s, const Cx2Args &a) {
-#ifdef EPI_CX_WALK_BUILD                                  // timing builds only (measured slower, profiles/r04_cx_experiments.txt): not in the product
-  if constexpr (LEAN && NP == 1 && NU <= 5) {
-    if (a.walk > 0 && g == 4 && !a.tile_list) {
-      const int nruns = (nt + a.walk - 1) / a.walk;
-      hipLaunchKernelGGL((k_cx_tiles<T, 4, NU, NP, FUSED, true, CX_PAD>), dim3((unsigned)(((nruns + 7) / 8) * 8)), dim3(cx2_wg<true>()), 0, s, a, nt);
-      return;
-    }
-  }
-#endif
   const unsigned nb = a.tile_list ? CX_LIST_GRID : (unsigned)(((nt + 7) / 8) * 8);
   switch (g) {
     case 4: if constexpr (FUSED || LEAN) { hipLaunchKernelGGL((k_cx_tiles<T, 4, NU, NP, FUSED, LEAN>), dim3(nb), dim3(cx2_wg<LEAN>()), 0, s, a, nt); } break;
@@ -1538,8 +1410,8 @@ static void launch_cx(bool heavy, int np, bool fused, bool lean, int shape, int 
 
 static void launch_cx_emit_slab(int np, int nshared, hipStream_t s, const Cx2Args &a, const int32_t *owned, const int32_t *slot_tile) {
   if (np == 1) hipLaunchKernelGGL((k_cx_emit_slab<CX_T1, 1>), dim3((unsigned)nshared), dim3(CX_WG), 0, s, a, owned, slot_tile);
-  else if (np == 2) hipLaunchKernelGGL((k_cx_emit_slab<1024, 2>), dim3((unsigned)nshared), dim3(CX_WG), 0, s, a, owned, slot_tile);
-  else hipLaunchKernelGGL((k_cx_emit_slab<1024, 3>), dim3((unsigned)nshared), dim3(CX_WG), 0, s, a, owned, slot_tile);
+  else if (np == 2) hipLaunchKernelGGL((k_cx_emit_slab<CXP_T, 2>), dim3((unsigned)nshared), dim3(CX_WG), 0, s, a, owned, slot_tile);
+  else hipLaunchKernelGGL((k_cx_emit_slab<CXP_T, 3>), dim3((unsigned)nshared), dim3(CX_WG), 0, s, a, owned, slot_tile);
 }
 
 static int ensure_pool(epi_batch *b, size_t rows) {
@@ -1616,19 +1488,244 @@ static bool make_fused_lut(const CxThreshold &t, uint32_t ctx_of_plane, int np, 
   return true;
 }
 
-// The CX report on a resident batch.  thr != null: thresholding fused into the tile kernel when the batch allows it
-// (the report's one context is the thresholding context, reads of at most ~5 kb), else a separate pass of the
-// per-read kernel first.
-// Direct mode: rows of the report whose tile offsets the batch keeps (cx_prev_*) if it had these contexts, else -1.
-static int64_t cx_recorded_nrow(const epi_batch *b, uint32_t ctx_mask) {
-  return b->cx_prev_key == (ctx_mask | 0x80000000u) ? b->cx_prev_nrow : -1;
-}
 static uint32_t cx_ctx_mask(const char *ctx) {
   uint32_t ctx_mask = 0;                                   // rcpp_cx_report.cpp:88-91
   for (const unsigned char *c = reinterpret_cast<const unsigned char *>(ctx); *c; c++) ctx_mask |= 1u << ctx_to_idx(*c);
   return ctx_mask;
 }
+// Direct mode: rows of the report whose tile offsets the batch keeps (cx_prev_*) if it had these contexts, else -1.
+static int64_t cx_recorded_nrow(const epi_batch *b, uint32_t ctx_mask) {
+  return b->cx_prev_key == (ctx_mask | 0x80000000u) ? b->cx_prev_nrow : -1;
+}
 
+// What one report call has decided before it queues a tile kernel.
+struct CxPlan {
+  int T, np;                              // tile positions, reported contexts
+  int32_t nt;                             // tiles ...
+  bool nt_hinted;                         // ... a count remembered from an earlier call, verified at the report's synchronisation
+  bool fused;                             // thresholding inside the tile kernel
+  bool lean;                              // u8 counters without folds (single-context reports)
+  bool per_tile;                          // ... decided tile by tile: the deep ones are listed for the general kernel
+  bool chained;                           // fixed-grid heavy-tile launches are queued right behind the tile kernel
+  int shape, shape_heavy;                 // lanes per row * 8 + chunks per lane: tile kernel / general and heavy-tile kernels
+  int32_t nshared;                        // tiles shared with other ranks ...
+  size_t headroom;                        // ... and the pool rows kept free for them (they are emitted later into the same pool)
+  uint32_t slot;                          // pool rows per tile slot (0: every tile through the cursor)
+  size_t ovf_base;                        // first row of the overflow region = nt * slot
+};
+
+// A remembered tile count that the index pass could not confirm: the rows were changed under the batch.
+static int cx_check_tile_count(epi_batch *b, bool hinted, uint32_t counted, int32_t nt) {
+  if (!hinted || counted == (uint32_t)nt) return EPI_OK;
+  for (int i = 0; i < 4; i++) b->tile_hint_T[i] = 0;
+  return fail(EPI_ERR_STATE, "the rows of this batch changed since an earlier report (tile count %u, was %d)", counted, nt);
+}
+
+// Thresholding of a cytosine report.  Fused into the tile kernel when the batch and the class strings allow it: its LUT and
+// the decision table over the possible class totals (filled on the device with the reference's own expressions, kept while
+// the thresholds do not change) go into `a`.  Else the per-read kernel decides first, into the caller's buffer or a scratch
+// column, and *d_pass is its output.
+static int cx_setup_threshold(epi_batch *b, const CxThreshold &thr, const RowStats &st, CxPlan &p, int32_t *d_pass_out, hipStream_t s,
+                              Cx2Args &a, const int32_t **d_pass) {
+  uint32_t fill4 = 0;
+  if (p.nt > 0 && p.np > 0 && cx_fused_fits(st) && make_fused_lut(thr, a.ctx_of_plane, p.np, &a.lut_s, &fill4)) {
+    p.fused = true;
+    a.lut_sx = lut16_xor_form(a.lut_s);
+    a.thr = thr.prm;
+    a.fill4 = fill4;
+    a.pass_out = d_pass_out;
+    // (field by field: the caller's struct may carry padding; doubles bitwise, so that a NaN threshold compares equal to itself)
+    const bool same = b->thr_tab_len == st.max_len && b->thr_tab_prm.min_n_ctx == thr.prm.min_n_ctx &&
+                      memcmp(&b->thr_tab_prm.min_ctx_meth_frac, &thr.prm.min_ctx_meth_frac, sizeof(double)) == 0 &&
+                      memcmp(&b->thr_tab_prm.max_ooctx_meth_frac, &thr.prm.max_ooctx_meth_frac, sizeof(double)) == 0;
+    if (!same) {
+      EPI_TRY(b->thr_tab.ensure((size_t)(st.max_len + 1) * 4));
+      hipLaunchKernelGGL(k_thr_table, dim3((unsigned)(st.max_len / 256 + 1)), dim3(256), 0, s, thr.prm, st.max_len, b->thr_tab.as<uint32_t>());
+      EPI_HIP(hipGetLastError());
+      b->thr_tab_len = st.max_len;
+      memset(&b->thr_tab_prm, 0, sizeof(ThrParams));
+      b->thr_tab_prm.min_n_ctx = thr.prm.min_n_ctx;
+      b->thr_tab_prm.min_ctx_meth_frac = thr.prm.min_ctx_meth_frac;
+      b->thr_tab_prm.max_ooctx_meth_frac = thr.prm.max_ooctx_meth_frac;
+    }
+    a.thr_tab = b->thr_tab.as<uint32_t>();
+  } else if (b->n > 0) {
+    int32_t *dst = d_pass_out;
+    if (!dst) { EPI_TRY(b->pass_tmp.ensure((size_t)b->n * 4)); dst = b->pass_tmp.as<int32_t>(); }
+    EPI_TRY(epi_batch_threshold_reads_dev(b, thr.cls[0], thr.cls[1], thr.cls[2] ? thr.cls[2] : "", thr.cls[3] ? thr.cls[3] : "",
+                                          thr.prm.min_n_ctx, thr.prm.min_ctx_meth_frac, thr.prm.max_ooctx_meth_frac, dst, s));
+    *d_pass = dst;
+  }
+  return EPI_OK;
+}
+
+// Row pool = one slot per tile + an overflow region behind the slots (cx_pool_reserve).  The slot size starts at a typical
+// density of reported cytosines (CpG ~6 % of the (pos,strand) cells of a tile, all contexts ~40 %) and doubles for the next
+// call when more than 1/8 of the rows went through the overflow cursor (cx_report_impl); an overflow of the region itself
+// is detected after the run and costs one rerun with the exact size.
+static uint32_t &cx_slot_state(epi_batch *b, uint32_t ctx_mask) { return (ctx_mask & ~(1u << 7)) ? b->cx_slot_wide : b->cx_slot_cg; }
+
+static int cx_layout_pool(epi_batch *b, uint32_t ctx_mask, CxPlan &p) {
+  const int T = p.T;
+  uint32_t &slot_state = cx_slot_state(b, ctx_mask);
+  if (!slot_state) slot_state = (ctx_mask & ~(1u << 7)) ? (uint32_t)(3 * T) / 4 : (uint32_t)T / 8;
+  uint32_t slot = slot_state > (uint32_t)(2 * T) ? (uint32_t)(2 * T) : slot_state;
+  if (options().cx_slot >= 0 && options().cx_slot <= 2 * T) slot = (uint32_t)options().cx_slot;   // test hook (EPIHIP_CX_SLOT)
+  while (slot && (unsigned long long)p.nt * slot > 0xC0000000ull) slot >>= 1;   // row indices are u32
+  size_t ovf_base = (size_t)p.nt * slot;
+  for (;;) {
+    const size_t ovf = (ovf_base >> 4) > 65536 ? (ovf_base >> 4) : 65536;
+    if (b->pool_cap >= ovf_base + ovf + p.headroom) break;
+    const int rc = ensure_pool(b, ovf_base + ovf + p.headroom);
+    if (rc == EPI_OK) break;
+    b->pool_cap = 0;                                       // (a failed growth has released the old buffers)
+    if (!slot) return rc;
+    slot = 0;                                              // the slots do not fit in device memory: every tile through the
+    ovf_base = 0;                                          // cursor, the pool sized by the rows actually produced
+  }
+  p.slot = slot;
+  p.ovf_base = ovf_base;
+  b->cx_last_slot = slot;
+  b->cx_last_ovf = (uint32_t)ovf_base;
+  return EPI_OK;
+}
+
+// The batch's tile table, row pool (as it is now: a regrown pool is bound again) and the layout of its last report
+static void cx_bind_pool(const epi_batch *b, Cx2Args &a) {
+  a.tiles = b->tiles.as<Tile>();
+  a.cursor = &report_scalars(b)->cursor;
+  a.tile_nrow = b->tile_nrow.as<uint32_t>();
+  a.tile_base = b->tile_base.as<uint32_t>();
+  a.slab = b->d_slab;
+  a.pool_key = b->pool_key.as<uint32_t>();
+  a.pool_meth = b->pool_a.as<uint32_t>();
+  a.pool_unmeth = b->pool_b.as<uint32_t>();
+  a.pool_cap = (uint32_t)(b->pool_cap > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : b->pool_cap);
+  a.slot_rows = b->cx_last_slot;
+  a.ovf_base = b->cx_last_ovf;
+}
+
+// Everything else the tile kernels of this report read: the rows, the heavy-tile thresholds and lists, the deep list.
+static int cx_fill_args(epi_batch *b, const CxPlan &p, const int32_t *d_pass, hipStream_t s, Cx2Args &a) {
+  Scalars *sc = report_scalars(b);
+  a.c.xm = b->xm; a.c.off = b->off; a.c.len = b->len; a.c.start = b->start; a.c.strand = b->strand; a.c.pass = p.fused ? nullptr : d_pass;
+  a.xm_cap = (b->nbytes + 15) / 16 * 16;                   // (both batch constructors guarantee this much)
+  cx_bind_pool(b, a);
+  a.heavy_rows = 16384;
+  if (options().heavy_rows > 0) a.heavy_rows = options().heavy_rows;   // test hook (EPIHIP_HEAVY_ROWS)
+  if (a.heavy_rows > 16384) a.heavy_rows = 16384;          // u16 pairs and the packed coverage halves: a base adds at most 2
+  a.heavy_chunk = a.heavy_rows / 4 > 64 ? a.heavy_rows / 4 : 64;
+  if (a.heavy_chunk > 256) a.heavy_chunk = 256;            // (a 20 000-row pile-up is then 80 work items, not 5)
+  EPI_TRY(b->heavy_list.ensure((size_t)p.nt * 4));
+  a.heavy_list = b->heavy_list.as<uint32_t>();
+  a.heavy_count = &sc->heavy_count;
+  a.heavy_max = &sc->heavy_max;
+  a.heavy_slab = nullptr;
+  if (p.per_tile) {
+    EPI_TRY(b->deep_list.ensure((size_t)p.nt * 4));
+    a.deep_list = b->deep_list.as<uint32_t>();
+    a.deep_count = &sc->deep_count;
+  }
+  a.nrows = b->n;
+#ifdef EPI_CHECK
+  EPI_TRY(b->diag.ensure(256));
+  a.dbg = b->diag.as<uint32_t>();
+  EPI_HIP(hipMemsetAsync(a.dbg, 0, 32, s));
+#endif
+  return EPI_OK;
+}
+
+// Queues one attempt at all tiles: the tile kernel, the general kernel for the tiles a lean one listed, and fixed-grid
+// launches for the first CX_HEAVY_CAP ultra-deep tiles.  rezero: not the first attempt of the call (for that one the
+// tile-index pass has zeroed the counters).
+static int cx_queue_attempt(epi_batch *b, const CxPlan &p, Cx2Args &a, hipStream_t s, bool rezero) {
+  if (rezero) {
+    Scalars *sc = report_scalars(b);
+    EPI_HIP(hipMemsetAsync(&sc->cursor, 0, offsetof(Scalars, fold_cursor) - offsetof(Scalars, cursor), s));   // cursor, rows, heavy and deep count
+    EPI_HIP(hipMemsetAsync(&sc->heavy_max, 0, 4, s));
+  }
+  prof_begin("cx_tiles", s);
+  launch_cx(false, p.np, p.fused, p.lean, p.shape, p.nt, dim3(1), s, a);
+  prof_end("cx_tiles", s);
+  if (p.per_tile) {                                        // the tiles the lean kernel listed, by the general kernel
+    Cx2Args g = a;
+    g.tile_list = a.deep_list;
+    g.tile_list_count = a.deep_count;
+    g.deep_list = nullptr; g.deep_count = nullptr;
+    prof_begin("cx_deep", s);
+    launch_cx(false, p.np, p.fused, false, p.shape_heavy, p.nt, dim3(1), s, g);
+    prof_end("cx_deep", s);
+  }
+  // Batches with deep positions may also hold ultra-deep tiles (set aside by the kernels above): the first CX_HEAVY_CAP of
+  // them are split, reduced and emitted by fixed-grid launches queued right here -- no host round trip for one pile-up
+  // in a WGS batch; a larger number is finished by cx_finish_pool_run, once the count is known.
+  if (p.chained) {
+    EPI_TRY(b->heavy_slab.ensure((size_t)CX_HEAVY_CAP * kCxPlanes * p.T * 4));
+    a.heavy_slab = b->heavy_slab.as<int32_t>();
+    a.heavy_first = 0;
+    EPI_HIP(hipMemsetAsync(a.heavy_slab, 0, (size_t)CX_HEAVY_CAP * kCxPlanes * p.T * 4, s));
+    prof_begin("cx_heavy", s);
+    launch_cx(true, p.np, p.fused, p.lean, p.shape_heavy, p.nt, dim3(CX_HEAVY_GRID, CX_HEAVY_CAP), s, a);
+    prof_end("cx_heavy", s);
+  }
+  EPI_HIP(hipGetLastError());
+  return EPI_OK;
+}
+
+// Behind a queued pool attempt: the tiles' row offsets are queued right away and the scalars come back in one
+// synchronisation.  Ultra-deep tiles that the chained launches did not cover are finished here (*host_heavy): split each over
+// ceil(rows / chunk) workgroups, reduce in HBM, emit, rescan, read again.
+static int cx_finish_pool_run(epi_batch *b, const CxPlan &p, Cx2Args &a, hipStream_t s, int attempt, Scalars *host, bool *host_heavy) {
+  Scalars *sc = report_scalars(b);
+  EPI_TRY(scan_exclusive_u32(a.tile_nrow, b->tile_out.as<uint32_t>(), p.nt, &sc->rows, b->scan_tmp, s));
+  EPI_TRY(read_report_scalars(b, s, host));
+  EPI_TRY(cx_check_tile_count(b, p.nt_hinted, host->ntiles, p.nt));
+  const uint32_t heavy_done = p.chained ? CX_HEAVY_CAP : 0u;
+  if (host->heavy_count > heavy_done) {
+    *host_heavy = true;
+    b->cx_noheavy_T = 0;
+    const uint32_t nheavy = host->heavy_count - heavy_done, nchunks = (host->heavy_max + (uint32_t)a.heavy_chunk - 1) / (uint32_t)a.heavy_chunk;
+    a.heavy_first = (int)heavy_done;
+    EPI_TRY(b->heavy_slab.ensure((size_t)nheavy * kCxPlanes * p.T * 4));
+    a.heavy_slab = b->heavy_slab.as<int32_t>();
+    EPI_HIP(hipMemsetAsync(a.heavy_slab, 0, (size_t)nheavy * kCxPlanes * p.T * 4, s));
+    prof_begin("cx_heavy", s);
+    launch_cx(true, p.np, p.fused, p.lean, p.shape_heavy, p.nt, dim3(nchunks, nheavy), s, a);
+    prof_end("cx_heavy", s);
+    EPI_HIP(hipGetLastError());
+    EPI_TRY(scan_exclusive_u32(a.tile_nrow, b->tile_out.as<uint32_t>(), p.nt, &sc->rows, b->scan_tmp, s));
+    EPI_TRY(read_report_scalars(b, s, host));
+  }
+#ifdef EPI_CHECK
+  {
+    uint32_t d[8];
+    EPI_HIP(hipMemcpy(d, a.dbg, 32, hipMemcpyDeviceToHost));
+    if (d[0]) return fail(EPI_ERR_STATE, "CX index check %u failed: v0=%lld v1=%d block=%u thread=%u (n=%lld nt=%d attempt=%d)", d[0],
+                          (long long)(((uint64_t)d[5] << 32) | d[1]), (int)d[2], d[3], d[4], (long long)b->n, p.nt, attempt);
+  }
+#endif
+  (void)attempt;
+  return EPI_OK;
+}
+
+// Keeps this pool report's tile offsets for the next report with these contexts (device copies; the pool and the row counts
+// are the next report's to overwrite)
+static int cx_keep_offsets(epi_batch *b, uint32_t ctx_mask, const CxPlan &p, uint32_t nrow, hipStream_t s) {
+  if (b->cx_prev_key == (ctx_mask | 0x80000000u) && b->cx_prev_T == p.T && b->cx_prev_nt == p.nt) return EPI_OK;
+  EPI_TRY(b->cx_prev_off.ensure((size_t)p.nt * 4));
+  EPI_TRY(b->cx_prev_cnt.ensure((size_t)p.nt * 4));
+  EPI_HIP(hipMemcpyAsync(b->cx_prev_off.p, b->tile_out.p, (size_t)p.nt * 4, hipMemcpyDeviceToDevice, s));
+  EPI_HIP(hipMemcpyAsync(b->cx_prev_cnt.p, b->tile_nrow.p, (size_t)p.nt * 4, hipMemcpyDeviceToDevice, s));
+  b->cx_prev_key = ctx_mask | 0x80000000u;
+  b->cx_prev_T = p.T;
+  b->cx_prev_nt = p.nt;
+  b->cx_prev_nrow = nrow;
+  return EPI_OK;
+}
+
+// The CX report on a resident batch.  thr != null: thresholding fused into the tile kernel when the batch allows it
+// (the report's one context is the thresholding context, reads of at most ~5 kb), else a separate pass of the
+// per-read kernel first.
 // d_cols / cap (may be null / 0): the caller's six columns.  The tile kernel writes them itself (*written = 1) when the batch
 // keeps the tile offsets of an earlier report with these contexts and its rows fit, and every tile is finished inside the
 // launch -- no position covered by more than 255 rows (RowStats::deep == 0: no deep list, and a tile with many candidate
@@ -1636,7 +1733,7 @@ static uint32_t cx_ctx_mask(const char *ctx) {
 // epi_batch_cx_fetch_* as before, and its tile offsets are kept for the next report.  The kept offsets are only valid
 // while every tile's row count is the kept one: true for valid XM codes whatever `pass` is, not for the unused low
 // nibbles 1, 3 and 4 under failed reads, nor for rows rewritten in place.  A launch in which any tile's count differs
-// (misc[1] != 0) forgets the record and reruns through the pool (*written = 0), which keeps its offsets instead.
+// forgets the record and reruns through the pool (*written = 0), which keeps its offsets instead.
 static int cx_report_impl(epi_batch *b, const int32_t *d_pass, const CxThreshold *thr, int32_t *d_pass_out, const char *ctx,
                           hipStream_t s, int64_t *nrow_out, int32_t *const *d_cols = nullptr, int64_t cap = 0,
                           int *written = nullptr) {
@@ -1647,287 +1744,103 @@ static int cx_report_impl(epi_batch *b, const int32_t *d_pass, const CxThreshold
 
   Cx2Args a;
   memset(&a, 0, sizeof(a));
-  const int np = make_report_lut(ctx_mask, &a.lut_r, &a.ctx_of_plane);
+  CxPlan p = {};
+  p.np = make_report_lut(ctx_mask, &a.lut_r, &a.ctx_of_plane);
   a.lut_rx = lut16_xor_form(a.lut_r);
-  const int T = cx_tile_for(np);
-  RowStats st;
-  int32_t nt = 0;
-  bool nt_hinted = false;
-  EPI_TRY(build_tiles(b, s, T, &st, &nt, &nt_hinted));
-  b->last_ntiles = nt;
-  b->last_tile = T;
   a.fill4 = 0x0C0C0C0Cu;                                   // '.': never a call, never skipped, also when lower-cased
-  bool fused = false;
-  if (thr) {
-    uint32_t fill4 = 0;
-    if (nt > 0 && np > 0 && cx_fused_fits(st) && make_fused_lut(*thr, a.ctx_of_plane, np, &a.lut_s, &fill4)) {
-      fused = true;
-      a.lut_sx = lut16_xor_form(a.lut_s);
-      a.thr = thr->prm;
-      a.fill4 = fill4;
-      a.pass_out = d_pass_out;
-      // decisions from a table over the possible class totals (filled on the device with the reference's own
-      // expressions); kept while the thresholds do not change
-      // (field by field: the caller's struct may carry padding; doubles bitwise, so that a NaN threshold compares equal to itself)
-      const bool same = b->thr_tab_len == st.max_len && b->thr_tab_prm.min_n_ctx == thr->prm.min_n_ctx &&
-                        memcmp(&b->thr_tab_prm.min_ctx_meth_frac, &thr->prm.min_ctx_meth_frac, sizeof(double)) == 0 &&
-                        memcmp(&b->thr_tab_prm.max_ooctx_meth_frac, &thr->prm.max_ooctx_meth_frac, sizeof(double)) == 0;
-      if (!same) {
-        EPI_TRY(b->thr_tab.ensure((size_t)(st.max_len + 1) * 4));
-        hipLaunchKernelGGL(k_thr_table, dim3((unsigned)(st.max_len / 256 + 1)), dim3(256), 0, s, thr->prm, st.max_len, b->thr_tab.as<uint32_t>());
-        EPI_HIP(hipGetLastError());
-        b->thr_tab_len = st.max_len;
-        memset(&b->thr_tab_prm, 0, sizeof(ThrParams));
-        b->thr_tab_prm.min_n_ctx = thr->prm.min_n_ctx;
-        b->thr_tab_prm.min_ctx_meth_frac = thr->prm.min_ctx_meth_frac;
-        b->thr_tab_prm.max_ooctx_meth_frac = thr->prm.max_ooctx_meth_frac;
-      }
-      a.thr_tab = b->thr_tab.as<uint32_t>();
-    } else if (b->n > 0) {
-      // not fusable: the per-read kernel decides first (into the caller's buffer, or a scratch column)
-      int32_t *dst = d_pass_out;
-      if (!dst) { EPI_TRY(b->pass_tmp.ensure((size_t)b->n * 4)); dst = b->pass_tmp.as<int32_t>(); }
-      EPI_TRY(epi_batch_threshold_reads_dev(b, thr->cls[0], thr->cls[1], thr->cls[2] ? thr->cls[2] : "", thr->cls[3] ? thr->cls[3] : "",
-                                            thr->prm.min_n_ctx, thr->prm.min_ctx_meth_frac, thr->prm.max_ooctx_meth_frac, dst, s));
-      d_pass = dst;
-    }
-  }
-  if (nt == 0 || np == 0) {                                // no rows, or a context string without H/X/Z: an empty table
+  p.T = cx_tile_for(p.np);
+  RowStats st;
+  EPI_TRY(build_tiles(b, s, p.T, &st, &p.nt, &p.nt_hinted));
+  b->last_ntiles = p.nt;
+  if (thr) EPI_TRY(cx_setup_threshold(b, *thr, st, p, d_pass_out, s, a, &d_pass));
+  if (p.nt == 0 || p.np == 0) {                            // no rows, or a context string without H/X/Z: an empty table
     // (a rank of a sharded run without rows still takes part in the exchange: its second half returns the empty table)
     b->last_kind = !b->shared_keys.empty() && b->d_slab ? 3 : 1; b->last_nrow = 0; b->last_ntiles = 0;
     return EPI_OK;
   }
+  const int T = p.T, np = p.np;
+  const int32_t nt = p.nt;
 
   EPI_TRY(b->tile_nrow.ensure((size_t)nt * 4));
   EPI_TRY(b->tile_base.ensure((size_t)nt * 4));
   EPI_TRY(b->tile_out.ensure((size_t)(nt + 1) * 4));
-  // Row pool = one slot per tile + an overflow region behind the slots (cx_pool_reserve).  The slot size starts
-  // at a typical density of reported cytosines (CpG ~6 % of the (pos,strand) cells of a tile, all contexts ~40 %)
-  // and doubles for the next call when more than 1/8 of the rows went through the overflow cursor; an overflow of
-  // the region itself is detected below and costs one rerun with the exact size.
-  const int32_t nshared = (int32_t)b->shared_keys.size();
-  const size_t headroom = nshared > 0 ? (size_t)nshared * 2 * T : 0;   // shared tiles are emitted later into the same pool
-  uint32_t &slot_state = (ctx_mask & ~(1u << 7)) ? b->cx_slot_wide : b->cx_slot_cg;
-  if (!slot_state) slot_state = (ctx_mask & ~(1u << 7)) ? (uint32_t)(3 * T) / 4 : (uint32_t)T / 8;
-  uint32_t slot = slot_state > (uint32_t)(2 * T) ? (uint32_t)(2 * T) : slot_state;
-  if (options().cx_slot >= 0 && options().cx_slot <= 2 * T) slot = (uint32_t)options().cx_slot;   // test hook (EPIHIP_CX_SLOT)
-  while (slot && (unsigned long long)nt * slot > 0xC0000000ull) slot >>= 1;   // row indices are u32
-  size_t ovf_base = (size_t)nt * slot;
-  for (;;) {
-    const size_t ovf = (ovf_base >> 4) > 65536 ? (ovf_base >> 4) : 65536;
-    if (b->pool_cap >= ovf_base + ovf + headroom) break;
-    const int rc = ensure_pool(b, ovf_base + ovf + headroom);
-    if (rc == EPI_OK) break;
-    b->pool_cap = 0;                                       // (a failed growth has released the old buffers)
-    if (!slot) return rc;
-    slot = 0;                                              // the slots do not fit in device memory: every tile through the
-    ovf_base = 0;                                          // cursor, the pool sized by the rows actually produced
-  }
-  uint32_t *cursor = b->misc.as<uint32_t>() + 1;           // misc[1] = pool cursor, misc[2] = nrow total
+  p.nshared = (int32_t)b->shared_keys.size();
+  p.headroom = p.nshared > 0 ? (size_t)p.nshared * 2 * T : 0;
+  EPI_TRY(cx_layout_pool(b, ctx_mask, p));
   // Single-context reports run the LEAN kernel (u8 counters, no folds).  Where a position may be covered by more than
   // 255 rows -- RowStats::deep says whether that can happen anywhere in the batch -- the lean kernel decides tile by tile
   // and lists the deep ones for the general kernel, which is queued right behind it (no host round trip in between).
-  bool lean = np == 1;
-  if (!options().cx_lean) lean = false;                    // test hook (EPIHIP_CX_LEAN=0): the general kernel for every tile
-  const bool per_tile = lean && st.deep != 0;
-  // lanes per row * 8 + chunks per lane; the heavy-tile kernel is the general one (three chunks per lane)
-  const int grp = np > 1 ? pick_cxp_group(st) * 8 : pick_cx_shape(st, T, fused, lean);
-  const int grp_heavy = np > 1 ? grp : pick_cx_shape(st, T, fused, false);
-
-  // Walking workgroups (timing builds, EPI_CX_WALK_BUILD + EPIHIP_CX_WALK=K; lean kernel, rows of up to CX_PAD - 15 bytes = the
-  // four-lane shapes): every row analysed once, by the tile it starts in.  Bit-exact, but slower than one tile per
-  // workgroup at every K on config 2 (the second visits it removes are L2 hits and the kernel is bound by its memory
-  // pipeline and by the number of resident workgroups, not by row visits): profiles/r04_cx_experiments.txt.
-  a.walk = 0;
-#ifdef EPI_CX_WALK_BUILD
-  if (lean && np == 1 && (grp >> 3) == 4 && (grp & 7) <= 5 && (int64_t)st.max_len + (CX_CH - 1) <= CX_PAD && options().cx_walk > 0)
-    a.walk = options().cx_walk > 64 ? 64 : options().cx_walk;
-#endif
-  a.c.xm = b->xm; a.c.off = b->off; a.c.len = b->len; a.c.start = b->start; a.c.strand = b->strand; a.c.pass = fused ? nullptr : d_pass;
-  a.xm_cap = (b->nbytes + 15) / 16 * 16;                   // (both batch constructors guarantee this much)
-  a.tiles = b->tiles.as<Tile>();
-  a.cursor = cursor;
-  a.tile_nrow = b->tile_nrow.as<uint32_t>();
-  a.tile_base = b->tile_base.as<uint32_t>();
-  a.slab = b->d_slab;
-  a.heavy_rows = 16384;
-  if (options().heavy_rows > 0) a.heavy_rows = options().heavy_rows;   // test hook (EPIHIP_HEAVY_ROWS)
-  if (a.heavy_rows > 16384) a.heavy_rows = 16384;          // u16 pairs and the packed coverage halves: a base adds at most 2
-  const int heavy_rows = a.heavy_rows;
-  a.heavy_chunk = a.heavy_rows / 4 > 64 ? a.heavy_rows / 4 : 64;
-  if (a.heavy_chunk > 256) a.heavy_chunk = 256;            // (a 20 000-row pile-up is then 80 work items, not 5)
-  EPI_TRY(b->heavy_list.ensure((size_t)nt * 4));
-  a.heavy_list = b->heavy_list.as<uint32_t>();
-  a.heavy_count = b->misc.as<uint32_t>() + 3;             // misc[3] = heavy tiles, misc[8] = their largest row count
-  a.heavy_max = b->misc.as<uint32_t>() + 8;
-  a.heavy_slab = nullptr;
-  if (per_tile) {
-    EPI_TRY(b->deep_list.ensure((size_t)nt * 4));
-    a.deep_list = b->deep_list.as<uint32_t>();
-    a.deep_count = b->misc.as<uint32_t>() + 4;            // misc[4] = tiles handed from the lean to the general kernel
-  }
-  a.slot_rows = slot;
-  a.ovf_base = (uint32_t)ovf_base;
-  b->cx_last_slot = slot;
-  b->cx_last_ovf = (uint32_t)ovf_base;
+  p.lean = np == 1 && options().cx_lean;                   // test hook (EPIHIP_CX_LEAN=0): the general kernel for every tile
+  p.per_tile = p.lean && st.deep != 0;
+  p.chained = st.deep != 0;
+  // the heavy-tile kernel is the general one (three chunks per lane)
+  p.shape = np > 1 ? pick_cxp_group(st) * 8 : pick_cx_shape(st, T, p.fused, p.lean);
+  p.shape_heavy = np > 1 ? p.shape : pick_cx_shape(st, T, p.fused, false);
   b->cx_last_np = np;
   b->cx_last_ctx_of_plane = a.ctx_of_plane;
-  EPI_TRY(check_grid(((int64_t)nt + 7) / 8 * 8, np == 1 && lean ? cx2_wg<true>() : CX_WG, "CX tile kernel"));
-  a.nrows = b->n;
-#ifdef EPI_CHECK
-  EPI_TRY(b->diag.ensure(256));
-  a.dbg = b->diag.as<uint32_t>();
-  EPI_HIP(hipMemsetAsync(a.dbg, 0, 32, s));
-#endif
-  const int64_t rec = cx_recorded_nrow(b, ctx_mask);
-  bool direct = d_cols && cap > 0 && cap <= 0x7FFFFFFF && rec >= 0 && rec <= cap && st.deep == 0 && nshared == 0 && a.walk == 0 &&
-                options().cx_direct;
-  for (int i = 0; direct && i < 6; i++) if (!d_cols[i]) direct = false;
-  if (direct && (b->cx_prev_T != T || b->cx_prev_nt != nt)) direct = false;
-  if (direct) {
-    a.prev_off = b->cx_prev_off.as<uint32_t>();
-    a.prev_nrow = b->cx_prev_cnt.as<uint32_t>();
-    a.mismatch = cursor;                                   // (misc[1]: the pool cursor, unused in direct mode)
-    for (int i = 0; i < 6; i++) a.out[i] = d_cols[i];
-    a.out_cap = cap;
-    a.heavy_rows = 0x7FFFFFFF;                             // worked in place: with deep == 0 no counter can overflow
-  }
-  uint32_t used_total[2] = {0, 0};
-  bool host_heavy = false;                                 // ultra-deep tiles had to be finished after the synchronisation
+  EPI_TRY(check_grid(((int64_t)nt + 7) / 8 * 8, np == 1 && p.lean ? cx2_wg<true>() : CX_WG, "CX tile kernel"));
+  EPI_TRY(cx_fill_args(b, p, d_pass, s, a));
   b->cx_deferred = false;
-  for (int attempt = 0, pool_runs = 0; pool_runs < 2; attempt++) {
-    if (!direct) a.prev_off = nullptr;
-    a.pool_key = b->pool_key.as<uint32_t>();
-    a.pool_meth = b->pool_a.as<uint32_t>();
-    a.pool_unmeth = b->pool_b.as<uint32_t>();
-    a.pool_cap = (uint32_t)(b->pool_cap > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : b->pool_cap);
-    if (attempt > 0) {                                   // (the tile-index pass zeroed them for the first attempt)
-      EPI_HIP(hipMemsetAsync(cursor, 0, 16, s));         // cursor, total, heavy count, deep count
-      EPI_HIP(hipMemsetAsync(a.heavy_max, 0, 4, s));
+
+  // Direct mode, at most once and in front of the pool runs: the rows go straight into the caller's columns and the one
+  // synchronisation brings back the number of tiles whose row count differed from the kept one (Scalars::cursor: no pool).
+  const int64_t rec = cx_recorded_nrow(b, ctx_mask);
+  bool direct = d_cols && cap > 0 && cap <= 0x7FFFFFFF && rec >= 0 && rec <= cap && st.deep == 0 && p.nshared == 0 && options().cx_direct &&
+                b->cx_prev_T == T && b->cx_prev_nt == nt;
+  for (int i = 0; direct && i < 6; i++) if (!d_cols[i]) direct = false;
+  if (direct) {
+    Cx2Args d = a;
+    d.prev_off = b->cx_prev_off.as<uint32_t>();
+    d.prev_nrow = b->cx_prev_cnt.as<uint32_t>();
+    d.mismatch = d.cursor;
+    for (int i = 0; i < 6; i++) d.out[i] = d_cols[i];
+    d.out_cap = cap;
+    d.heavy_rows = 0x7FFFFFFF;                             // worked in place: with deep == 0 no counter can overflow
+    EPI_TRY(cx_queue_attempt(b, p, d, s, false));
+    Scalars host;
+    EPI_TRY(read_report_scalars(b, s, &host));
+    EPI_TRY(cx_check_tile_count(b, p.nt_hinted, host.ntiles, nt));
+    if (host.cursor == 0) {
+      b->last_kind = 0;                                    // (nothing to fetch: the rows are where the caller wants them)
+      b->last_nrow = 0;
+      *nrow_out = b->cx_prev_nrow;
+      if (written) *written = 1;
+      return EPI_OK;
     }
-    prof_begin("cx_tiles", s);
-    launch_cx(false, np, fused, lean, grp, nt, dim3(1), s, a);
-    prof_end("cx_tiles", s);
-    if (per_tile) {                                      // the tiles the lean kernel listed, by the general kernel
-      Cx2Args g = a;
-      g.tile_list = a.deep_list;
-      g.tile_list_count = a.deep_count;
-      g.deep_list = nullptr; g.deep_count = nullptr;
-      prof_begin("cx_deep", s);
-      launch_cx(false, np, fused, false, grp_heavy, nt, dim3(1), s, g);
-      prof_end("cx_deep", s);
-    }
-    // Batches with deep positions may also hold ultra-deep tiles (set aside by the kernels above): the first CX_HEAVY_CAP of
-    // them are split, reduced and emitted by fixed-grid launches queued right here -- no host round trip for one pile-up
-    // in a WGS batch; a larger number is finished below, once the count is known.
-    const bool chained = st.deep != 0;
-    if (chained) {
-      EPI_TRY(b->heavy_slab.ensure((size_t)CX_HEAVY_CAP * kCxPlanes * T * 4));
-      a.heavy_slab = b->heavy_slab.as<int32_t>();
-      a.heavy_first = 0;
-      EPI_HIP(hipMemsetAsync(a.heavy_slab, 0, (size_t)CX_HEAVY_CAP * kCxPlanes * T * 4, s));
-      prof_begin("cx_heavy", s);
-      launch_cx(true, np, fused, lean, grp_heavy, nt, dim3(CX_HEAVY_GRID, CX_HEAVY_CAP), s, a);
-      prof_end("cx_heavy", s);
-    }
-    EPI_HIP(hipGetLastError());
-    if (direct) {
-      // rows are in the caller's columns; misc[1] = tiles whose row count differed from the kept one.  One sync, as on the
-      // pool path.
-      uint32_t host9[9];
-      EPI_TRY(read_scalars(b, s, cursor - 1, 36, host9));
-      if (nt_hinted && host9[0] != (uint32_t)nt) {
-        for (int i = 0; i < 4; i++) b->tile_hint_T[i] = 0;
-        return fail(EPI_ERR_STATE, "the rows of this batch changed since an earlier report (tile count %u, was %d)", host9[0], nt);
-      }
-      if (host9[1] == 0) {
-        b->last_kind = 0;                                  // (nothing to fetch: the rows are where the caller wants them)
-        b->last_nrow = 0;
-        *nrow_out = b->cx_prev_nrow;
-        if (written) *written = 1;
-        return EPI_OK;
-      }
-      // the rows of this batch changed: the table from the pool, whose offsets are kept instead
-      b->cx_prev_key = 0;
-      direct = false;
-      a.heavy_rows = heavy_rows;
-      continue;
-    }
-    pool_runs++;
-    if (b->cx_defer && nshared > 0 && attempt == 0 && nt_hinted && b->cx_noheavy_T == T && b->cx_noheavy_rows == a.heavy_rows) {
+    b->cx_prev_key = 0;                                    // the rows of this batch changed: the table from the pool, whose offsets are kept instead
+  }
+
+  // Pool runs: at most two, the second with a pool regrown to the size the first one asked for.
+  Scalars host;
+  bool host_heavy = false;                                 // ultra-deep tiles had to be finished after the synchronisation
+  for (int run = 0;; run++) {
+    cx_bind_pool(b, a);
+    EPI_TRY(cx_queue_attempt(b, p, a, s, direct || run > 0));
+    if (run == 0 && b->cx_defer && p.nshared > 0 && p.nt_hinted && b->cx_noheavy_T == T && b->cx_noheavy_rows == a.heavy_rows) {
       // sharded report with one host synchronisation: nothing is read back here; epi_batch_cx_finish_shared checks the tile
       // count, the heavy-tile count and the pool at its own synchronisation (comm.hip reruns the first half into a scratch
       // slab if the pool turns out too small)
       b->cx_deferred = true;
-      b->cx_def_hinted = nt_hinted;
-      b->cx_def_heavy_done = chained ? CX_HEAVY_CAP : 0u;
-      b->cx_def_headroom = headroom;
+      b->cx_def_heavy_done = p.chained ? CX_HEAVY_CAP : 0u;
       b->last_kind = 3;
       return EPI_OK;
     }
-    // row offsets of the tiles are queued right away; {rows handed out, total rows, heavy tiles} come back in one sync
-    EPI_TRY(scan_exclusive_u32(a.tile_nrow, b->tile_out.as<uint32_t>(), nt, cursor + 1, b->scan_tmp, s));
-    uint32_t host9[9];
-    EPI_TRY(read_scalars(b, s, cursor - 1, 36, host9));    // misc[0..8]
-    uint32_t *host = host9 + 1;
-    if (nt_hinted && host9[0] != (uint32_t)nt) {
-      for (int i = 0; i < 4; i++) b->tile_hint_T[i] = 0;
-      return fail(EPI_ERR_STATE, "the rows of this batch changed since an earlier report (tile count %u, was %d)", host9[0], nt);
-    }
-    const uint32_t heavy_done = chained ? CX_HEAVY_CAP : 0u;
-    if (host[2] > heavy_done) {
-      host_heavy = true;
-      b->cx_noheavy_T = 0;
-      // ultra-deep tiles were set aside (and not finished above): split each over ceil(rows/chunk) workgroups, reduce in
-      // HBM, emit, rescan
-      const uint32_t nheavy = host[2] - heavy_done, nchunks = (host[7] + (uint32_t)a.heavy_chunk - 1) / (uint32_t)a.heavy_chunk;
-      a.heavy_first = (int)heavy_done;
-      EPI_TRY(b->heavy_slab.ensure((size_t)nheavy * kCxPlanes * T * 4));
-      a.heavy_slab = b->heavy_slab.as<int32_t>();
-      EPI_HIP(hipMemsetAsync(a.heavy_slab, 0, (size_t)nheavy * kCxPlanes * T * 4, s));
-      prof_begin("cx_heavy", s);
-      launch_cx(true, np, fused, lean, grp_heavy, nt, dim3(nchunks, nheavy), s, a);
-      prof_end("cx_heavy", s);
-      EPI_HIP(hipGetLastError());
-      EPI_TRY(scan_exclusive_u32(a.tile_nrow, b->tile_out.as<uint32_t>(), nt, cursor + 1, b->scan_tmp, s));
-      EPI_TRY(read_scalars(b, s, cursor, 8, host));
-    }
-    used_total[0] = host[0];
-    used_total[1] = host[1];
-#ifdef EPI_CHECK
-    {
-      uint32_t d[8];
-      EPI_HIP(hipMemcpy(d, a.dbg, 32, hipMemcpyDeviceToHost));
-      if (d[0]) return fail(EPI_ERR_STATE, "CX index check %u failed: v0=%lld v1=%d block=%u thread=%u (n=%lld nt=%d attempt=%d)", d[0],
-                            (long long)(((uint64_t)d[5] << 32) | d[1]), (int)d[2], d[3], d[4], (long long)b->n, nt, attempt);
-    }
-#endif
-    if (ovf_base + used_total[0] + headroom <= a.pool_cap) break;
-    if (pool_runs == 2) return fail(EPI_ERR_STATE, "row pool overflow after regrow");
-    EPI_TRY(ensure_pool(b, ovf_base + used_total[0] + (used_total[0] >> 4) + 1024 + headroom));   // exact need is known now: rerun once
-    if (nshared > 0)   // the rerun adds into the slab again
-      EPI_HIP(hipMemsetAsync(b->d_slab, 0, (size_t)nshared * kCxPlanes * T * 4, s));
+    EPI_TRY(cx_finish_pool_run(b, p, a, s, run + (direct ? 1 : 0), &host, &host_heavy));
+    if (p.ovf_base + host.cursor + p.headroom <= a.pool_cap) break;
+    if (run == 1) return fail(EPI_ERR_STATE, "row pool overflow after regrow");
+    EPI_TRY(ensure_pool(b, p.ovf_base + host.cursor + (host.cursor >> 4) + 1024 + p.headroom));   // exact need is known now: rerun once
+    if (p.nshared > 0)   // the rerun adds into the slab again
+      EPI_HIP(hipMemsetAsync(b->d_slab, 0, (size_t)p.nshared * kCxPlanes * T * 4, s));
   }
-  if (used_total[0] > used_total[1] / 8 && slot_state < (uint32_t)(2 * T)) slot_state *= 2;   // too many tiles outgrew their slot
+  uint32_t &slot_state = cx_slot_state(b, ctx_mask);
+  if (host.cursor > host.rows / 8 && slot_state < (uint32_t)(2 * T)) slot_state *= 2;   // too many tiles outgrew their slot
   // (no ultra-deep tile was left for the host to finish: a later sharded report on this batch may defer its synchronisation)
   if (!host_heavy) { b->cx_noheavy_T = T; b->cx_noheavy_rows = a.heavy_rows; }
-  if (nshared > 0) { b->last_kind = 3; return EPI_OK; }     // caller continues with epi_batch_cx_finish_shared
+  if (p.nshared > 0) { b->last_kind = 3; return EPI_OK; }   // caller continues with epi_batch_cx_finish_shared
   b->last_kind = 1;
-  b->last_nrow = used_total[1];
-  *nrow_out = used_total[1];
-  if (b->cx_prev_key != (ctx_mask | 0x80000000u) || b->cx_prev_T != T || b->cx_prev_nt != nt) {
-    // keep this report's tile offsets for the next one with these contexts (device copies; the pool and the row counts are
-    // the next report's to overwrite)
-    EPI_TRY(b->cx_prev_off.ensure((size_t)nt * 4));
-    EPI_TRY(b->cx_prev_cnt.ensure((size_t)nt * 4));
-    EPI_HIP(hipMemcpyAsync(b->cx_prev_off.p, b->tile_out.p, (size_t)nt * 4, hipMemcpyDeviceToDevice, s));
-    EPI_HIP(hipMemcpyAsync(b->cx_prev_cnt.p, b->tile_nrow.p, (size_t)nt * 4, hipMemcpyDeviceToDevice, s));
-    b->cx_prev_key = ctx_mask | 0x80000000u;
-    b->cx_prev_T = T;
-    b->cx_prev_nt = nt;
-    b->cx_prev_nrow = used_total[1];
-  }
-  return EPI_OK;
+  b->last_nrow = host.rows;
+  *nrow_out = host.rows;
+  return cx_keep_offsets(b, ctx_mask, p, host.rows, s);
 }
 
 }  // namespace epi
@@ -1939,10 +1852,9 @@ extern "C" {
 int epi_tile_positions(void) { return cx_tile_for(1); }
 
 int epi_cx_tile_positions(const char *ctx) {
-  uint32_t ctx_mask = 0, cop = 0;
-  if (ctx) for (const unsigned char *c = reinterpret_cast<const unsigned char *>(ctx); *c; c++) ctx_mask |= 1u << ctx_to_idx(*c);
+  uint32_t cop = 0;
   ClassLut l;
-  return cx_tile_for(make_report_lut(ctx_mask, &l, &cop));
+  return cx_tile_for(make_report_lut(ctx ? cx_ctx_mask(ctx) : 0u, &l, &cop));
 }
 
 int epi_batch_cx_report_dev(epi_batch *b, const int32_t *d_pass, const char *ctx, void *stream, int64_t *nrow_out) {
@@ -1995,53 +1907,34 @@ int epi_batch_cx_finish_shared(epi_batch *b, const char *ctx, void *stream, int6
   hipStream_t s = pick_stream(b, stream);
   const int32_t nt = b->last_ntiles;
   if (nt == 0) { b->last_kind = 1; b->last_nrow = 0; *nrow_out = 0; return EPI_OK; }   // this rank holds no rows: owns no tile
-  uint32_t *cursor = b->misc.as<uint32_t>() + 1;
   Cx2Args a;
   memset(&a, 0, sizeof(a));
-  a.tiles = b->tiles.as<Tile>();
+  cx_bind_pool(b, a);
   a.ctx_of_plane = b->cx_last_ctx_of_plane;
-  a.cursor = cursor;
-  a.tile_nrow = b->tile_nrow.as<uint32_t>();
-  a.tile_base = b->tile_base.as<uint32_t>();
-  a.slab = b->d_slab;
-  a.pool_key = b->pool_key.as<uint32_t>();
-  a.pool_meth = b->pool_a.as<uint32_t>();
-  a.pool_unmeth = b->pool_b.as<uint32_t>();
-  a.pool_cap = (uint32_t)(b->pool_cap > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : b->pool_cap);
-  a.slot_rows = b->cx_last_slot;
-  a.ovf_base = b->cx_last_ovf;
   launch_cx_emit_slab(b->cx_last_np, (int)b->shared_keys.size(), s, a, b->d_shared_owned.as<int32_t>(),
                       b->d_slot_tile.as<int32_t>());
   EPI_HIP(hipGetLastError());
-  uint32_t *d_total = b->misc.as<uint32_t>() + 2;
-  EPI_TRY(scan_exclusive_u32(a.tile_nrow, b->tile_out.as<uint32_t>(), nt, d_total, b->scan_tmp, s));
-  uint32_t ut[2] = {0, 0};                                  // {overflow rows handed out, total rows}: one sync
+  EPI_TRY(scan_exclusive_u32(a.tile_nrow, b->tile_out.as<uint32_t>(), nt, &report_scalars(b)->rows, b->scan_tmp, s));
+  Scalars host;                                             // overflow rows handed out, total rows: one sync
+  EPI_TRY(read_report_scalars(b, s, &host));
   if (b->cx_deferred) {
     // the first half read nothing back: its checks happen here, with the report's only synchronisation
     b->cx_deferred = false;
-    uint32_t host9[9];
-    EPI_TRY(read_scalars(b, s, cursor - 1, 36, host9));     // misc[0..8]
-    if (b->cx_def_hinted && host9[0] != (uint32_t)nt) {
-      for (int i = 0; i < 4; i++) b->tile_hint_T[i] = 0;
-      return fail(EPI_ERR_STATE, "the rows of this batch changed since an earlier report (tile count %u, was %d)", host9[0], nt);
-    }
-    if (host9[3] > b->cx_def_heavy_done) {
+    EPI_TRY(cx_check_tile_count(b, true, host.ntiles, nt));
+    if (host.heavy_count > b->cx_def_heavy_done) {
       b->cx_noheavy_T = 0;
-      return fail(EPI_ERR_STATE, "ultra-deep tiles appeared in a batch that had none (%u): the rows of this batch changed", host9[3]);
+      return fail(EPI_ERR_STATE, "ultra-deep tiles appeared in a batch that had none (%u): the rows of this batch changed", host.heavy_count);
     }
-    if ((size_t)a.ovf_base + host9[1] > a.pool_cap) {         // (the cursor has served the shared tiles' rows as well by now)
+    if ((size_t)a.ovf_base + host.cursor > a.pool_cap) {      // (the cursor has served the shared tiles' rows as well by now)
       // the pool was too small for the rows of this report: the caller reruns the first half (which grows it) into a
       // scratch slab and emits the shared tiles from the slab that has already been reduced
       b->last_kind = 0;
       return EPI_RETRY_POOL;
     }
-    ut[0] = host9[1]; ut[1] = host9[2];
-  } else {
-    EPI_TRY(read_scalars(b, s, cursor, 8, ut));
   }
   // cannot overflow: the first half kept 2*kTile rows per shared tile free
-  if ((size_t)a.ovf_base + ut[0] > a.pool_cap) return fail(EPI_ERR_STATE, "row pool overflow in sharded report");
-  const uint32_t total = ut[1];
+  if ((size_t)a.ovf_base + host.cursor > a.pool_cap) return fail(EPI_ERR_STATE, "row pool overflow in sharded report");
+  const uint32_t total = host.rows;
   b->last_kind = 1;
   b->last_nrow = total;
   *nrow_out = total;

@@ -971,7 +971,7 @@ bool mhl_fused_eligible(epi_batch *b, uint32_t ctx_mask, const RowStats &st) {
 
 static void fill_args_common(epi_batch *b, MhlFArgs &a) {
   a.tiles = b->tiles.as<Tile>();
-  a.cursor = b->misc.as<uint32_t>() + 1;                   // misc layout as in the CX report: [1] cursor, [2] rows, [3] deep tiles
+  a.cursor = &report_scalars(b)->cursor;
   a.tile_nrow = b->tile_nrow.as<uint32_t>();
   a.tile_base = b->tile_base.as<uint32_t>();
   a.pool_key = b->pool_key.as<uint32_t>();
@@ -1045,7 +1045,8 @@ int mhl_fused_report(epi_batch *b, uint32_t ctx_mask, uint32_t H, int hmin, doub
     }
     a.keep_tab = b->mhl_keep_tab.as<uint32_t>();
   }
-  a.deep_count = b->misc.as<uint32_t>() + 3;
+  Scalars *sc = report_scalars(b);
+  a.deep_count = &sc->heavy_count;                         // (this kernel's deep tiles share the heavy tiles' counter)
   a.deep_list = b->heavy_list.as<uint32_t>();
   // The fast variant comes with and without the LDS array of folded call counters.  Without it a workgroup needs 4 KB less
   // LDS (five per CU instead of four) and a tile of more than 255 rows folds its u8 counters into a slot of a slab in HBM
@@ -1055,7 +1056,7 @@ int mhl_fused_report(epi_batch *b, uint32_t ctx_mask, uint32_t H, int hmin, doub
   const uint32_t fold_slots = options().mhlf_fold_slots >= 0 && (uint32_t)options().mhlf_fold_slots < MHLF_FOLD_SLOTS
                                   ? (uint32_t)options().mhlf_fold_slots : MHLF_FOLD_SLOTS;   // (test hook: fewer)
   a.max_rows = MHLF_FAST_ROWS;
-  a.fold_slab = nullptr; a.fold_cursor = b->misc.as<uint32_t>() + 5; a.fold_slots = 0;
+  a.fold_slab = nullptr; a.fold_cursor = &sc->fold_cursor; a.fold_slots = 0;
   if (!fold) {
     EPI_TRY(b->mhlf_fold_slab.ensure((size_t)MHLF_FOLD_SLOTS * 2 * T * 4));
     a.fold_slab = b->mhlf_fold_slab.as<uint32_t>();
@@ -1074,12 +1075,11 @@ int mhl_fused_report(epi_batch *b, uint32_t ctx_mask, uint32_t H, int hmin, doub
   a.dbg = b->diag.as<uint32_t>();
   EPI_HIP(hipMemsetAsync(a.dbg, 0, 32, s));
 #endif
-  uint32_t *cursor = b->misc.as<uint32_t>() + 1;
-  uint32_t host[3] = {0, 0, 0};
+  Scalars host;
   for (int attempt = 0; attempt < 2; attempt++) {
     fill_args_common(b, a);
     if (attempt > 0) {
-      EPI_HIP(hipMemsetAsync(cursor, 0, 20, s));           // misc[1..5]
+      EPI_HIP(hipMemsetAsync(&sc->cursor, 0, offsetof(Scalars, unused6) - offsetof(Scalars, cursor), s));   // cursor .. fold_cursor
       if (nshared > 0) {                                   // the rerun adds into the slabs again
         EPI_HIP(hipMemsetAsync(a.slab_cnt, 0, (size_t)nshared * MHLF_CNT_PLANES * T * 4, s));
         EPI_HIP(hipMemsetAsync(a.slab_sum, 0, (size_t)nshared * MHLF_SUM_PLANES * T * 8, s));
@@ -1094,30 +1094,27 @@ int mhl_fused_report(epi_batch *b, uint32_t ctx_mask, uint32_t H, int hmin, doub
     if (wide_first) launch_mhl_fused<true>(gc_wide, grid, nt, s, a); else launch_mhl_fused<false>(gc, grid, nt, s, a, fold);
     prof_end("mhl_tiles", s);
     EPI_HIP(hipGetLastError());
-    EPI_TRY(scan_exclusive_u32(a.tile_nrow, b->tile_out.as<uint32_t>(), nt, cursor + 1, b->scan_tmp, s));
-    uint32_t host4[6];
-    EPI_TRY(read_scalars(b, s, cursor - 1, 24, host4));    // {tile count, overflow rows handed out, total rows, deep tiles, -, fold slots asked for}
-    if (nt_hinted && host4[0] != (uint32_t)nt) {
+    EPI_TRY(scan_exclusive_u32(a.tile_nrow, b->tile_out.as<uint32_t>(), nt, &sc->rows, b->scan_tmp, s));
+    EPI_TRY(read_report_scalars(b, s, &host));
+    if (nt_hinted && host.ntiles != (uint32_t)nt) {
       for (int i = 0; i < 4; i++) b->tile_hint_T[i] = 0;
-      return fail(EPI_ERR_STATE, "the rows of this batch changed since an earlier report (tile count %u, was %d)", host4[0], nt);
+      return fail(EPI_ERR_STATE, "the rows of this batch changed since an earlier report (tile count %u, was %d)", host.ntiles, nt);
     }
-    if (host4[3] > 0) {
+    const uint32_t ndeep = host.heavy_count, fold_asked = host.fold_cursor;
+    if (ndeep > 0) {
       // tiles the fast variant set aside (too many rows, sums that could wrap u32): the WIDE variant redoes exactly those
       a.tile_list = a.deep_list;
       prof_begin("mhl_deep", s);
-      launch_mhl_fused<true>(gc_wide, host4[3], (int)host4[3], s, a);
+      launch_mhl_fused<true>(gc_wide, ndeep, (int)ndeep, s, a);
       prof_end("mhl_deep", s);
       EPI_HIP(hipGetLastError());
-      EPI_TRY(scan_exclusive_u32(a.tile_nrow, b->tile_out.as<uint32_t>(), nt, cursor + 1, b->scan_tmp, s));
-      uint32_t again[2];
-      EPI_TRY(read_scalars(b, s, cursor, 8, again));
-      host4[1] = again[0]; host4[2] = again[1];
-      b->mhlf_prefer_wide = host4[3] > (uint32_t)nt / 2;   // most tiles needed the wide sums: start there next time
+      EPI_TRY(scan_exclusive_u32(a.tile_nrow, b->tile_out.as<uint32_t>(), nt, &sc->rows, b->scan_tmp, s));
+      EPI_TRY(read_report_scalars(b, s, &host));
+      b->mhlf_prefer_wide = ndeep > (uint32_t)nt / 2;   // most tiles needed the wide sums: start there next time
       b->mhlf_prefer_wide_H = H;
     }
-    if (!fold && host4[5] > fold_slots / 2) b->mhlf_prefer_fold = true;   // many tiles over 255 rows: LDS fold array next time
+    if (!fold && fold_asked > fold_slots / 2) b->mhlf_prefer_fold = true;   // many tiles over 255 rows: LDS fold array next time
     // (rows per tile are a property of the immutable batch, not of the report's parameters: this one may stay)
-    host[0] = host4[1]; host[1] = host4[2]; host[2] = host4[3];
 #ifdef EPI_CHECK
     {
       uint32_t d[8];
@@ -1126,23 +1123,24 @@ int mhl_fused_report(epi_batch *b, uint32_t ctx_mask, uint32_t H, int hmin, doub
                             (int)d[1], (int)d[2], d[3], d[4], (long long)b->n, nt);
     }
 #endif
-    if (ovf_base + host[0] + headroom <= a.pool_cap) break;
+    if (ovf_base + host.cursor + headroom <= a.pool_cap) break;
     if (attempt == 1) return fail(EPI_ERR_STATE, "row pool overflow after regrow");
-    EPI_TRY(ensure_mhl_pool(b, ovf_base + host[0] + (host[0] >> 4) + 1024 + headroom));
+    EPI_TRY(ensure_mhl_pool(b, ovf_base + host.cursor + (host.cursor >> 4) + 1024 + headroom));
   }
-  if (host[0] > host[1] / 8 && b->mhlf_slot < 2u * T) b->mhlf_slot *= 2;
+  if (host.cursor > host.rows / 8 && b->mhlf_slot < 2u * T) b->mhlf_slot *= 2;
   *done = true;
   if (nshared > 0) { b->last_kind = 5; return EPI_OK; }    // caller continues with epi_batch_mhl_finish_shared
   b->last_kind = 2;
-  b->last_nrow = host[1];
-  *nrow_out = host[1];
+  b->last_nrow = host.rows;
+  *nrow_out = host.rows;
   return EPI_OK;
 }
 
 // Second half of a sharded lMHL report on the fused path: the slabs have been sum-reduced across ranks.
 int mhl_fused_finish_shared(epi_batch *b, hipStream_t s, int64_t *nrow_out) {
   const int32_t nt = b->last_ntiles;
-  uint32_t *cursor = b->misc.as<uint32_t>() + 1;
+  Scalars *sc = report_scalars(b);
+  Scalars host;
   if (nt > 0 && !b->shared_keys.empty()) {
     MhlFArgs a{};
     memset(&a, 0, sizeof(a));
@@ -1153,14 +1151,13 @@ int mhl_fused_finish_shared(epi_batch *b, hipStream_t s, int64_t *nrow_out) {
     hipLaunchKernelGGL(k_mhlf_emit_slab, dim3((unsigned)b->shared_keys.size()), dim3(MHLF_WG), 0, s, a, b->d_shared_owned.as<int32_t>(),
                        b->d_slot_tile.as<int32_t>());
     EPI_HIP(hipGetLastError());
-    EPI_TRY(scan_exclusive_u32(a.tile_nrow, b->tile_out.as<uint32_t>(), nt, cursor + 1, b->scan_tmp, s));
-    uint32_t ut[2] = {0, 0};
-    EPI_TRY(read_scalars(b, s, cursor, 8, ut));
-    if ((size_t)a.ovf_base + ut[0] > a.pool_cap) return fail(EPI_ERR_STATE, "row pool overflow in sharded lMHL report");
-    b->last_nrow = ut[1];
+    EPI_TRY(scan_exclusive_u32(a.tile_nrow, b->tile_out.as<uint32_t>(), nt, &sc->rows, b->scan_tmp, s));
+    EPI_TRY(read_report_scalars(b, s, &host));
+    if ((size_t)a.ovf_base + host.cursor > a.pool_cap) return fail(EPI_ERR_STATE, "row pool overflow in sharded lMHL report");
+    b->last_nrow = host.rows;
   } else {
     b->last_nrow = 0;
-    if (nt > 0) { uint32_t ut[2] = {0, 0}; EPI_TRY(read_scalars(b, s, cursor, 8, ut)); b->last_nrow = ut[1]; }
+    if (nt > 0) { EPI_TRY(read_report_scalars(b, s, &host)); b->last_nrow = host.rows; }
   }
   b->last_kind = 2;
   *nrow_out = b->last_nrow;

@@ -460,7 +460,7 @@ __device__ __forceinline__ MhlRow mhl_load_row(const MhlArgs &a, const Tile &td,
 template <int G>
 __device__ __forceinline__ MhlSlice mhl_slice_of(const MhlArgs &a, const MhlRow &row, const Tile &td, int sub, uint32_t *cnt) {
   MhlSlice m;
-  m.rs = cx_slice_of<MHL_T, G, true>(a.c, row.v, td, sub, cnt);
+  m.rs = cx_slice_of<MHL_T, G>(a.c, row.v, td, sub, cnt);
   m.pos0 = 0; m.pf = 0; m.pe = 0; m.sidx = 0; m.hs = 0; m.rel = 0; m.blk0 = 0; m.blk1 = -1; m.rb = 0; m.rn = 0;
   if (m.rs.nd > 0) {
     m.hs = (uint32_t)row.hrow | (row.skips ? 0x80000000u : 0u);
@@ -489,7 +489,7 @@ __device__ __forceinline__ MhlSlice mhl_slice_of(const MhlArgs &a, const MhlRow 
 template <int OFF, bool FIRST, class ST>
 __device__ __forceinline__ void mhl_add_dword(uint32_t w, int k, const MhlSlice &m, const MhlLds<ST> &L) {
   // the packed counter LUT also flags the stray nibbles (bits 6-7 of its bytes: 1 = nibble 3, 2 = nibble 4, 3 = nibble 8)
-  const uint32_t f4 = cx_add_dword<MHL_T, OFF, FIRST, true>(w, k == m.rs.nd - 1, m.rs);
+  const uint32_t f4 = cx_add_dword<MHL_T, OFF, FIRST>(w, k == m.rs.nd - 1, m.rs);
   if (f4 == 0u) return;                                  // common case: nothing but the counters
 #pragma unroll
   for (int j = 0; j < 4; j++) {
@@ -705,7 +705,7 @@ __device__ __forceinline__ void mhl_emit(const MhlArgs &a, int tile, const MhlLd
   }
 }
 
-constexpr int MHL_LDS_CNT = cx_lds_dwords<MHL_T, true>() + 2 * kCxGuard;
+constexpr int MHL_LDS_CNT = cx_lds_dwords<MHL_T>() + 2 * kCxGuard;
 
 template <class ST>
 __device__ __forceinline__ MhlLds<ST> mhl_lds(uint32_t *cnt, ST *sums) {
@@ -761,7 +761,7 @@ __global__ __launch_bounds__(WG, (mhl_waves_per_simd<WG, ST>())) void k_mhl_tile
   mhl_accumulate<G, WG>(a, td, L);
   __syncthreads();
   if (td.slot >= 0) {                                    // shared with another rank: hand the raw sums over
-    cx_dump_slab<T, WG, true>(L.cnt, reinterpret_cast<int32_t *>(a.shared_cnt + (int64_t)td.slot * (16 * T)));
+    cx_dump_slab<T, WG>(L.cnt, reinterpret_cast<int32_t *>(a.shared_cnt + (int64_t)td.slot * (16 * T)));
     mhl_dump_sums<WG>(sums, a.shared_sums + (int64_t)td.slot * MHL_NSUM);
     if (threadIdx.x == 0) { a.tile_nrow[tile] = 0; a.tile_base[tile] = 0; }
     return;
@@ -789,7 +789,7 @@ __global__ __launch_bounds__(WG, (mhl_waves_per_simd<WG, ST>())) void k_mhl_heav
   __syncthreads();
   uint32_t *dc = td.slot >= 0 ? a.shared_cnt + (int64_t)td.slot * (16 * T) : a.heavy_cnt + (int64_t)blockIdx.y * (16 * T);
   unsigned long long *ds = td.slot >= 0 ? a.shared_sums + (int64_t)td.slot * MHL_NSUM : a.heavy_sums + (int64_t)blockIdx.y * MHL_NSUM;
-  cx_dump_slab<T, WG, true>(L.cnt, reinterpret_cast<int32_t *>(dc));
+  cx_dump_slab<T, WG>(L.cnt, reinterpret_cast<int32_t *>(dc));
   mhl_dump_sums<WG>(sums, ds);
 }
 
@@ -1020,7 +1020,8 @@ int epi_batch_mhl_report_dev(epi_batch *b, const char *ctx, int hmax, int hmin, 
   }
   EPI_TRY(b->mhl_cur.ensure((size_t)MHL_REGIONS * MHL_CUR_STRIDE * 8));
   unsigned long long *rec_cursor = b->mhl_cur.as<unsigned long long>();
-  unsigned long long *rec_max = reinterpret_cast<unsigned long long *>(b->misc.as<uint32_t>() + 12);   // misc[12..13]
+  Scalars *sc = report_scalars(b);
+  unsigned long long *rec_max = reinterpret_cast<unsigned long long *>(sc->rec_max);
 
   RowsArgs ra;
   ra.xm = b->xm; ra.off = b->off; ra.len = b->len; ra.n = b->n;
@@ -1030,12 +1031,11 @@ int epi_batch_mhl_report_dev(epi_batch *b, const char *ctx, int hmax, int hmin, 
   ra.blkrec = b->mhl_blk.as<uint2>();
   ra.rec_cursor = rec_cursor;
   ra.cont = multi ? b->mhl_cont.as<uint32_t>() : nullptr;
-  ra.max_h = b->misc.as<uint32_t>() + 14;                    // misc[14]
+  ra.max_h = &sc->max_h;
 
   EPI_TRY(b->tile_nrow.ensure((size_t)nt * 4));
   EPI_TRY(b->tile_base.ensure((size_t)nt * 4));
   EPI_TRY(b->tile_out.ensure((size_t)(nt + 1) * 4));
-  uint32_t *cursor = b->misc.as<uint32_t>() + 1;
 
   MhlArgs a;
   a.c.xm = b->xm; a.c.off = b->off; a.c.len = b->len; a.c.start = b->start; a.c.strand = b->strand; a.c.pass = nullptr;
@@ -1050,7 +1050,7 @@ int epi_batch_mhl_report_dev(epi_batch *b, const char *ctx, int hmax, int hmin, 
 #endif
   a.tiles = b->tiles.as<Tile>();
   a.ctx_mask = ctx_mask; a.H = H;
-  a.cursor = cursor;
+  a.cursor = &sc->cursor;
   a.tile_nrow = b->tile_nrow.as<uint32_t>();
   a.tile_base = b->tile_base.as<uint32_t>();
   a.heavy_rows = 16384;
@@ -1061,8 +1061,8 @@ int epi_batch_mhl_report_dev(epi_batch *b, const char *ctx, int hmax, int hmin, 
   a.heavy_chunk = a.heavy_rows / 4 > 64 ? a.heavy_rows / 4 : 64;
   EPI_TRY(b->heavy_list.ensure((size_t)nt * 4));
   a.heavy_list = b->heavy_list.as<uint32_t>();
-  a.heavy_count = b->misc.as<uint32_t>() + 3;             // misc layout as in the CX report
-  a.heavy_max = b->misc.as<uint32_t>() + 8;
+  a.heavy_count = &sc->heavy_count;
+  a.heavy_max = &sc->heavy_max;
   a.heavy_cnt = nullptr;
   a.heavy_sums = nullptr;
   a.shared_cnt = reinterpret_cast<uint32_t *>(b->d_mhl_cnt_slab);
@@ -1119,9 +1119,9 @@ int epi_batch_mhl_report_dev(epi_batch *b, const char *ctx, int hmax, int hmin, 
     prof_end("mhl_rows", s);
     hipLaunchKernelGGL(k_mhl_cursor_max, dim3(1), dim3(MHL_REGIONS), 0, s, rec_cursor, rec_max);
     EPI_HIP(hipGetLastError());
-    uint32_t p1[3];                                        // {fullest record region (u64), largest haplotype size}
-    EPI_TRY(read_scalars(b, s, rec_max, 12, p1));
-    const unsigned long long rec_used = ((unsigned long long)p1[1] << 32) | p1[0];
+    Scalars host;                                          // pass 1: fullest record region, largest haplotype size
+    EPI_TRY(read_report_scalars(b, s, &host));
+    const unsigned long long rec_used = ((unsigned long long)host.rec_max[1] << 32) | host.rec_max[0];
     if (rec_used > b->mhl_rec_cap / MHL_REGIONS) {         // record space ran out: the need is known now, redo pass 1
       if (attempt == 2) return fail(EPI_ERR_STATE, "stretch record overflow after regrow");
       const unsigned long long want = (rec_used + rec_used / 16 + 64) * MHL_REGIONS;
@@ -1132,7 +1132,7 @@ int epi_batch_mhl_report_dev(epi_batch *b, const char *ctx, int hmax, int hmin, 
     }
     // u32 LDS sums if no position of a tile (or heavy-tile chunk) can reach 2^31: rows x (the largest value a read
     // can add: S(h) >= h, S(M) <= S(h) for M <= h; + 1 for a stray nibble at the position)
-    uint32_t hcap = p1[2] > 65535u ? 65535u : p1[2];
+    uint32_t hcap = host.max_h > 65535u ? 65535u : host.max_h;
     if (hcap >= H) hcap = H;
     const unsigned long long vmax = nrS(hcap) > 1 ? nrS(hcap) : 1;
     const unsigned long long narrow_rows = ((1ull << 31) - 1) / (vmax + 1);
@@ -1152,14 +1152,14 @@ int epi_batch_mhl_report_dev(epi_batch *b, const char *ctx, int hmax, int hmin, 
     a.pool_de = b->pool_f.as<unsigned long long>();
     a.pool_cap = (uint32_t)(mhl_pool_rows(b) > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : mhl_pool_rows(b));
     if (attempt > 0) {                                   // (the tile-index pass zeroed them for the first attempt)
-      EPI_HIP(hipMemsetAsync(cursor, 0, 12, s));         // cursor, total, heavy count
+      EPI_HIP(hipMemsetAsync(&sc->cursor, 0, offsetof(Scalars, deep_count) - offsetof(Scalars, cursor), s));   // cursor, rows, heavy count
       EPI_HIP(hipMemsetAsync(a.heavy_max, 0, 4, s));
     }
     prof_begin("mhl_tiles", s);
     if (narrow) launch_mhl_tiles<uint32_t>(tg, nt, s, a); else launch_mhl_tiles<unsigned long long>(tg, nt, s, a);
     prof_end("mhl_tiles", s);
     EPI_HIP(hipGetLastError());
-    EPI_TRY(scan_exclusive_u32(a.tile_nrow, b->tile_out.as<uint32_t>(), nt, cursor + 1, b->scan_tmp, s));
+    EPI_TRY(scan_exclusive_u32(a.tile_nrow, b->tile_out.as<uint32_t>(), nt, &sc->rows, b->scan_tmp, s));
 #ifdef EPI_MHL_CHECK
     {
       uint32_t d[8];
@@ -1168,10 +1168,9 @@ int epi_batch_mhl_report_dev(epi_batch *b, const char *ctx, int hmax, int hmin, 
                             (int)d[1], (int)d[2], d[3], d[4], (long long)b->n, nt, attempt);
     }
 #endif
-    uint32_t host[8];
-    EPI_TRY(read_scalars(b, s, cursor, 32, host));         // misc[1..8]
-    if (host[2] > 0) {                                     // pile-ups: split, reduce in HBM, emit, rescan
-      const uint32_t nheavy = host[2], nchunks = (host[7] + (uint32_t)a.heavy_chunk - 1) / (uint32_t)a.heavy_chunk;
+    EPI_TRY(read_report_scalars(b, s, &host));
+    if (host.heavy_count > 0) {                            // pile-ups: split, reduce in HBM, emit, rescan
+      const uint32_t nheavy = host.heavy_count, nchunks = (host.heavy_max + (uint32_t)a.heavy_chunk - 1) / (uint32_t)a.heavy_chunk;
       EPI_TRY(b->heavy_slab.ensure((size_t)nheavy * 16 * MHL_T * 4));
       EPI_TRY(b->heavy_sums.ensure((size_t)nheavy * MHL_NSUM * 8));
       a.heavy_cnt = b->heavy_slab.as<uint32_t>();
@@ -1182,11 +1181,11 @@ int epi_batch_mhl_report_dev(epi_batch *b, const char *ctx, int hmax, int hmin, 
       if (narrow) launch_mhl_heavy<uint32_t>(tg, nheavy, nchunks, s, a); else launch_mhl_heavy<unsigned long long>(tg, nheavy, nchunks, s, a);
       prof_end("mhl_heavy", s);
       EPI_HIP(hipGetLastError());
-      EPI_TRY(scan_exclusive_u32(a.tile_nrow, b->tile_out.as<uint32_t>(), nt, cursor + 1, b->scan_tmp, s));
-      EPI_TRY(read_scalars(b, s, cursor, 8, host));
+      EPI_TRY(scan_exclusive_u32(a.tile_nrow, b->tile_out.as<uint32_t>(), nt, &sc->rows, b->scan_tmp, s));
+      EPI_TRY(read_report_scalars(b, s, &host));
     }
-    used_total[0] = host[0];
-    used_total[1] = host[1];
+    used_total[0] = host.cursor;
+    used_total[1] = host.rows;
     if (ovf_base + used_total[0] + headroom <= a.pool_cap) break;
     if (attempt == 2) return fail(EPI_ERR_STATE, "row pool overflow after regrow");
     EPI_TRY(ensure_mhl_pool(b, ovf_base + used_total[0] + (used_total[0] >> 4) + 1024 + headroom));
@@ -1249,12 +1248,12 @@ int epi_batch_mhl_finish_shared(epi_batch *b, void *stream, int64_t *nrow_out) {
   if (b->last_kind == 5) return mhl_fused_finish_shared(b, s, nrow_out);   // the one-pass kernel's slabs
   const int32_t nt = b->last_ntiles;
   if (nt == 0) { b->last_kind = 2; b->last_nrow = 0; *nrow_out = 0; return EPI_OK; }   // this rank holds no rows: owns no tile
-  uint32_t *cursor = b->misc.as<uint32_t>() + 1;
+  Scalars *sc = report_scalars(b);
   MhlArgs a;
   memset(&a, 0, sizeof(a));
   a.tiles = b->tiles.as<Tile>();
   a.ctx_mask = b->mhl_ctx_mask;
-  a.cursor = cursor;
+  a.cursor = &sc->cursor;
   a.tile_nrow = b->tile_nrow.as<uint32_t>();
   a.tile_base = b->tile_base.as<uint32_t>();
   a.shared_cnt = reinterpret_cast<uint32_t *>(b->d_mhl_cnt_slab);
@@ -1270,13 +1269,13 @@ int epi_batch_mhl_finish_shared(epi_batch *b, void *stream, int64_t *nrow_out) {
   hipLaunchKernelGGL((k_mhl_emit_slab<MHL_WG>), dim3((unsigned)b->shared_keys.size()), dim3(MHL_WG), 0, s, a,
                      b->d_shared_owned.as<int32_t>(), b->d_slot_tile.as<int32_t>());
   EPI_HIP(hipGetLastError());
-  EPI_TRY(scan_exclusive_u32(a.tile_nrow, b->tile_out.as<uint32_t>(), nt, cursor + 1, b->scan_tmp, s));
-  uint32_t ut[2] = {0, 0};
-  EPI_TRY(read_scalars(b, s, cursor, 8, ut));
-  if ((size_t)a.ovf_base + ut[0] > a.pool_cap) return fail(EPI_ERR_STATE, "row pool overflow in sharded lMHL report");
+  EPI_TRY(scan_exclusive_u32(a.tile_nrow, b->tile_out.as<uint32_t>(), nt, &sc->rows, b->scan_tmp, s));
+  Scalars host;
+  EPI_TRY(read_report_scalars(b, s, &host));
+  if ((size_t)a.ovf_base + host.cursor > a.pool_cap) return fail(EPI_ERR_STATE, "row pool overflow in sharded lMHL report");
   b->last_kind = 2;
-  b->last_nrow = ut[1];
-  *nrow_out = ut[1];
+  b->last_nrow = host.rows;
+  *nrow_out = host.rows;
   return EPI_OK;
 }
 

@@ -364,7 +364,7 @@ int epi_batch_extract_patterns(epi_batch *b, int32_t target_rname, int32_t targe
   PAT_TRY(cnt.ensure((size_t)a.nwin * 4));
   PAT_TRY(colmap.ensure((size_t)a.nwin * 4));
   PAT_TRY(b->misc.ensure(256));
-  uint32_t *d_total = b->misc.as<uint32_t>() + 15;          // misc[15]
+  uint32_t *d_total = &report_scalars(b)->pat_total;
   hipLaunchKernelGGL(k_pat_flag, dim3(nb), dim3(256), 0, s, a, flag.as<uint32_t>());
   PAT_TRY(scan_exclusive_u32(flag.as<uint32_t>(), cidx.as<uint32_t>(), b->n, d_total, b->scan_tmp, s));
   PAT_HIP(hipMemsetAsync(cnt.p, 0, (size_t)a.nwin * 4, s));

@@ -1,5 +1,5 @@
-// Device code shared by the tile kernels (CX report and lMHL): the nibble LUT, the per-lane view of
-// a row's in-tile slice and the branch-free "four bases -> four LDS atomics" step.
+// Device code shared by the tile kernels (multi-context CX report and lMHL): the packed nibble LUT, the per-lane
+// view of a row's in-tile slice and the branch-free "four bases -> four LDS atomics" step.
 #pragma once
 #include "common.hpp"
 
@@ -10,17 +10,13 @@ namespace epi {
 #endif
 constexpr int CX_NU = EPI_CX_NU;              // dword loads a lane keeps in flight per row
 
-// nibble -> (counter slot, increment) as a 16-entry byte LUT for v_perm_b32: bits 0-2 = slot (see
-// enum in common.hpp), bits 4-5 = increment.
-//   code:     0    1    2    3    4    5    6    7 |   8    9   10   11 |  12   13   14   15
-//   byte:  0x11 0x11 0x12 0x11 0x11 0x11 0x14 0x16 | 0x11 0x21 0x13 0x00 | 0x10 0x11 0x15 0x17
-// increment 0 = skipped ('+'/'-' and filler, rcpp_cx_report.cpp:123: the atomic still issues but adds
-// nothing); 2 = nibble 9, which IS the reference's coverage slot and so counts twice (:126-127).
-constexpr uint32_t kLutLo0 = 0x11121111u, kLutLo1 = 0x16141111u, kLutHi0 = 0x00132111u, kLutHi1 = 0x17151110u;
-// Packed variant (two u16 counters per LDS dword: pair 0 = ('.', other), 1 = (H, h), 2 = (X, x), 3 = (Z, z); the
-// even slot in the low half): byte = [increment of the high half: bits 4-5][pair: bits 2-3][increment of the low half: bits 0-1]
+// nibble -> (counter pair, increments) as a 16-entry byte LUT for v_perm_b32.  Two u16 counters per LDS dword: pair
+// 0 = ('.', other), 1 = (H, h), 2 = (X, x), 3 = (Z, z), the first of a pair in the low half;
+// byte = [increment of the high half: bits 4-5][pair: bits 2-3][increment of the low half: bits 0-1]
 //   code:     0    1    2    3    4    5    6    7 |   8    9   10   11 |  12   13   14   15
 //   byte:  0x10 0x10 0x05 0x50 0x90 0x10 0x09 0x0D | 0xD0 0x20 0x14 0x00 | 0x01 0x10 0x18 0x1C
+// no increment = skipped ('+'/'-' and filler, rcpp_cx_report.cpp:123: the atomic still issues but adds nothing);
+// 2 = nibble 9, which IS the reference's coverage slot and so counts twice (:126-127).
 // bits 6-7 (ignored by the counters) flag the stray nibbles the lMHL kernel needs: 1 = nibble 3, 2 = nibble 4, 3 = nibble 8
 constexpr uint32_t kPkLo0 = 0x50051010u, kPkLo1 = 0x0D091090u, kPkHi0 = 0x001420D0u, kPkHi1 = 0x1C181001u;
 constexpr int kCxGuard = 4;               // dwords of LDS padding around the counters (see cx_add_dword)
@@ -64,7 +60,7 @@ __device__ __forceinline__ RowVals cx_load_row(const RowCols &a, const Tile &td,
   return v;
 }
 
-template <int T, int G, bool PK = false>
+template <int T, int G>
 __device__ __forceinline__ RowSlice cx_slice_of(const RowCols &a, const RowVals &v, const Tile &td, int sub, uint32_t *cnt) {
   RowSlice m;
   m.src = nullptr; m.dst[0] = m.dst[1] = m.dst[2] = m.dst[3] = cnt; m.rot8 = 0; m.nd = 0; m.tl = -1; m.lc4 = 0; m.pick0 = 0x03020100u;
@@ -87,7 +83,7 @@ __device__ __forceinline__ RowSlice cx_slice_of(const RowCols &a, const RowVals 
       // rows (and row alignments d) they work on, so the 32 lanes always hit 32 different banks.
       const int d = lo - rel - e_lo;
       const int rot = ((int)((threadIdx.x & 31) >> 3) - d) & 3;
-      uint32_t *dst0 = cnt + (v.sd - 1) * (PK ? 4 : 8) * T + d + 4 * sub;
+      uint32_t *dst0 = cnt + (v.sd - 1) * 4 * T + d + 4 * sub;
       m.rot8 = rot * 8;
 #pragma unroll
       for (int j = 0; j < 4; j++) m.dst[j] = dst0 + ((j + rot) & 3);
@@ -100,76 +96,55 @@ __device__ __forceinline__ RowSlice cx_slice_of(const RowCols &a, const RowVals 
   return m;
 }
 
-template <int T, int G, bool PK = false>
+template <int T, int G>
 __device__ __forceinline__ RowSlice cx_row_slice(const RowCols &a, const Tile &td, int r, int sub, uint32_t *cnt) {
-  return cx_slice_of<T, G, PK>(a, cx_load_row(a, td, r), td, sub, cnt);
+  return cx_slice_of<T, G>(a, cx_load_row(a, td, r), td, sub, cnt);
 }
 
 // One dword (four bases) of a row into the LDS counters.  Every lane issues all four atomics: bytes
-// outside the slice and skipped codes are turned into "+0 on plane 0" by the masks, never branched
+// outside the slice and skipped codes are turned into "+0 on pair 0" by the masks, never branched
 // around.  A masked byte can sit up to 3 cells outside [0,T): the counters carry kCxGuard cells of
 // padding for that.  The byte order is rotated per lane (RowSlice::rot8) so that the 32 lanes of a half
-// wavefront always hit 32 different LDS banks.
-template <int T, int OFF, bool FIRST, bool PK = false>
-__device__ __forceinline__ uint32_t cx_add_dword(uint32_t w, bool last, const RowSlice &m) {   // returns the stray-nibble flags (packed LUT)
+// wavefront always hit 32 different LDS banks.  Returns the stray-nibble flags (bits 6-7 of the LUT bytes).
+template <int T, int OFF, bool FIRST>
+__device__ __forceinline__ uint32_t cx_add_dword(uint32_t w, bool last, const RowSlice &m) {
   const uint32_t lo3 = w & 0x07070707u;                  // low three bits of the four codes (unpack_ctx_idx)
   // 16-entry byte LUT = two v_perm lookups (codes 0-7 / 8-15) + a third v_perm that picks, per byte,
   // the second result when bit 3 of the code is set or the read is lower-cased (selector j + 4*bit3):
   // no multiply, no masks
   const uint32_t pick = ((w >> 1) & 0x04040404u) | m.pick0;
-  uint32_t s4 = __builtin_amdgcn_perm(__builtin_amdgcn_perm(PK ? kPkHi1 : kLutHi1, PK ? kPkHi0 : kLutHi0, lo3),
-                                      __builtin_amdgcn_perm(PK ? kPkLo1 : kLutLo1, PK ? kPkLo0 : kLutLo0, lo3), pick);
+  uint32_t s4 = __builtin_amdgcn_perm(__builtin_amdgcn_perm(kPkHi1, kPkHi0, lo3), __builtin_amdgcn_perm(kPkLo1, kPkLo0, lo3), pick);
   uint32_t vm = last ? m.mask_last : ~0u;
   if (FIRST) vm &= m.mask_first;
   s4 &= vm;
   const uint32_t stray = s4 & 0xC0C0C0C0u;               // byte j = base j of the dword (before the rotation)
   s4 = __builtin_amdgcn_alignbit(s4, s4, m.rot8);        // rotate right by rot bytes: byte j <- byte (j+rot)&3
-  if constexpr (PK) {
-    // value added to the pair's dword = low increment | high increment << 16, put together by one v_perm per base
-    const uint32_t lo4 = s4 & 0x03030303u, hi4 = (s4 >> 4) & 0x03030303u;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-      uint32_t plane = __builtin_amdgcn_ubfe(s4, 8 * j + 2, 2);
-      asm("" : "+v"(plane));
-      const uint32_t val = __builtin_amdgcn_perm(hi4, lo4, 0x0C000C00u | ((4u + j) << 16) | (uint32_t)j);
-      atomicAdd(m.dst[j] + OFF + plane * T, val);
-    }
-    return stray;
-  }
+  // value added to the pair's dword = low increment | high increment << 16, put together by one v_perm per base
+  const uint32_t lo4 = s4 & 0x03030303u, hi4 = (s4 >> 4) & 0x03030303u;
 #pragma unroll
   for (int j = 0; j < 4; j++) {                          // OFF = 4 * (this dword's index - the lane's first index)
-    uint32_t plane = __builtin_amdgcn_ubfe(s4, 8 * j, 3);
+    uint32_t plane = __builtin_amdgcn_ubfe(s4, 8 * j + 2, 2);
     asm("" : "+v"(plane));                               // keep v_bfe_u32 + v_lshl_add_u32 (hipcc otherwise re-derives
                                                          // the address with shift + and + add: one more VALU per base)
-    const uint32_t inc = __builtin_amdgcn_ubfe(s4, 8 * j + 4, 2);
-    atomicAdd(m.dst[j] + OFF + plane * T, inc);
+    const uint32_t val = __builtin_amdgcn_perm(hi4, lo4, 0x0C000C00u | ((4u + j) << 16) | (uint32_t)j);
+    atomicAdd(m.dst[j] + OFF + plane * T, val);
   }
-  return 0u;
+  return stray;
 }
 
-// LDS dwords of one tile's counters: u32 [strand][8][T], or packed u16 pairs [strand][4][T] (tile_common.hpp)
-template <int T, bool PK> constexpr int cx_lds_dwords() { return (PK ? 8 : kCxPlanes) * T; }
-// waves per SIMD the kernel is compiled for: as many workgroups per CU as LDS (160 KiB) and 2048 threads allow
-template <int T, int WG, bool PK> constexpr int cx_waves_per_simd() {
-  const int by_lds = (160 * 1024) / (cx_lds_dwords<T, PK>() * 4 + 256 + (PK ? 4 * T : 0)), by_thr = 2048 / WG;   // + emit candidate lists
-  const int wgs = by_lds < by_thr ? by_lds : by_thr;
-  return wgs * WG / 256;
-}
+// LDS dwords of one tile's counters: packed u16 pairs [strand][4][T]
+template <int T> constexpr int cx_lds_dwords() { return 8 * T; }
 
 // Adds a tile's LDS counters into its dense u32 slab [16][T] in HBM (shared tiles, heavy tiles).
-template <int T, int WG, bool PK>
+template <int T, int WG>
 __device__ __forceinline__ void cx_dump_slab(const uint32_t *cnt, int32_t *slab) {
   uint32_t *dst = reinterpret_cast<uint32_t *>(slab);
-  for (int i = threadIdx.x; i < cx_lds_dwords<T, PK>(); i += WG) {
+  for (int i = threadIdx.x; i < cx_lds_dwords<T>(); i += WG) {
     const uint32_t v = cnt[i];
     if (!v) continue;
-    if constexpr (PK) {
-      const int pl = i / T, p = i % T;                      // pl = strand*4 + pair -> planes 2*pl (low half), 2*pl+1
-      if (v & 0xFFFFu) atomicAdd(dst + (2 * pl) * T + p, v & 0xFFFFu);
-      if (v >> 16) atomicAdd(dst + (2 * pl + 1) * T + p, v >> 16);
-    } else {
-      atomicAdd(dst + i, v);
-    }
+    const int pl = i / T, p = i % T;                      // pl = strand*4 + pair -> planes 2*pl (low half), 2*pl+1
+    if (v & 0xFFFFu) atomicAdd(dst + (2 * pl) * T + p, v & 0xFFFFu);
+    if (v >> 16) atomicAdd(dst + (2 * pl + 1) * T + p, v >> 16);
   }
 }
 

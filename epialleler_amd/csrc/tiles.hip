@@ -116,21 +116,21 @@ struct __attribute__((packed, aligned(4))) TileI4 { int32_t v[4]; };   // 16 byt
 
 // VERIFY (with FILL): `bsum` is the scanned block-sum array remembered from an earlier call on this batch and tile
 // size (the count pass, the scan and the host round trip are skipped); every block checks its own total against it and
-// the table's capacity `cap` is the remembered tile count.  misc[0] (zeroed before the launch) ends up as that count,
+// the table's capacity `cap` is the remembered tile count.  sc->ntiles (zeroed before the launch) ends up as that count,
 // or as 0xFFFFFFFF when any block disagrees -- the rows were changed under the batch -- which the caller reports.
 template <bool FILL, bool VERIFY = false>
 __global__ __launch_bounds__(TB_THREADS) void k_tile_pass(const int32_t *__restrict__ start, const int32_t *__restrict__ rname,
                                                            int64_t n, int32_t lmax, int32_t sh, uint32_t *__restrict__ bsum,
                                                            Tile *__restrict__ tiles, const int64_t *__restrict__ shared_keys,
                                                            int32_t nshared, int32_t *__restrict__ slot_tile,
-                                                           uint32_t *__restrict__ misc, int64_t cap) {
+                                                           Scalars *__restrict__ sc, int64_t cap) {
   // (cap = entries of `tiles`: the count may be one remembered from an earlier call -- a batch that was changed since
   //  must not write behind the table before the host notices)
   __shared__ uint32_t s_tot[TB_THREADS / 64];
   if (FILL && blockIdx.x == 0 && threadIdx.x == 0) {       // the report kernels' counters start at zero (saves three memsets)
-    misc[1] = 0; misc[2] = 0; misc[3] = 0; misc[8] = 0;    // pool cursor, output rows, heavy tiles, largest heavy tile
-    misc[4] = 0;                                           // tiles the lean CX kernel hands to the general one
-    misc[5] = 0;                                           // slab slots the one-pass lMHL kernel has handed out
+    sc->cursor = 0; sc->rows = 0; sc->heavy_count = 0; sc->heavy_max = 0;
+    sc->deep_count = 0;
+    sc->fold_cursor = 0;
   }
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t x0 = (int64_t)blockIdx.x * TB_ROWS + (int64_t)threadIdx.x * TB_ITEMS;
@@ -174,8 +174,8 @@ __global__ __launch_bounds__(TB_THREADS) void k_tile_pass(const int32_t *__restr
   if constexpr (VERIFY) {
     if (threadIdx.x == 0) {
       const uint32_t expect = (blockIdx.x + 1 < gridDim.x ? bsum[blockIdx.x + 1] : (uint32_t)cap) - bsum[blockIdx.x];
-      if (btot != expect) atomicMax(misc, 0xFFFFFFFFu);
-      else if (blockIdx.x == 0) atomicMax(misc, (uint32_t)cap);
+      if (btot != expect) atomicMax(&sc->ntiles, 0xFFFFFFFFu);
+      else if (blockIdx.x == 0) atomicMax(&sc->ntiles, (uint32_t)cap);
     }
   }
   uint32_t before = bsum[blockIdx.x] + wbase + inc - tot;  // tiles created by rows before the thread's first row
@@ -219,11 +219,11 @@ __global__ __launch_bounds__(TB_THREADS) void k_tile_pass(const int32_t *__restr
   }
 }
 
-// what the index pass leaves in misc when the table itself is reused: the tile count and the report kernels' zeroed counters
-__global__ void k_misc_reset(uint32_t *__restrict__ misc, const uint32_t *__restrict__ nt) {
+// what the index pass leaves in the scalars when the table itself is reused: the tile count and the report kernels' zeroed counters
+__global__ void k_misc_reset(Scalars *__restrict__ sc, const uint32_t *__restrict__ nt) {
   if (threadIdx.x == 0) {
-    misc[0] = nt[0];
-    misc[1] = 0; misc[2] = 0; misc[3] = 0; misc[4] = 0; misc[5] = 0; misc[8] = 0;
+    sc->ntiles = nt[0];
+    sc->cursor = 0; sc->rows = 0; sc->heavy_count = 0; sc->deep_count = 0; sc->fold_cursor = 0; sc->heavy_max = 0;
   }
 }
 
@@ -269,9 +269,8 @@ int build_tiles(epi_batch *b, hipStream_t s, int32_t T, RowStats *h, int32_t *nt
   if ((T & (T - 1)) != 0) return fail(EPI_ERR_ARG, "tile size must be a power of two");
   const int sh = log2_tile(T);
   EPI_TRY(b->misc.ensure(256));
-  // misc layout (u32): [0] tile count, [1] pool cursor, [2] output rows, [3] heavy tiles, [8] largest heavy tile
-  uint32_t *d_misc = b->misc.as<uint32_t>();
-  if (b->n == 0) { EPI_HIP(hipMemsetAsync(d_misc, 0, 36, s)); return EPI_OK; }
+  Scalars *sc = report_scalars(b);
+  if (b->n == 0) { EPI_HIP(hipMemsetAsync(sc, 0, offsetof(Scalars, heavy_max) + 4, s)); return EPI_OK; }
   EPI_TRY(fetch_row_stats(b, s));
   *h = b->h_stats;
   if (h->bad_len) return fail(EPI_ERR_ARG, "offsets are not non-decreasing, or start+length exceeds int32");
@@ -289,14 +288,14 @@ int build_tiles(epi_batch *b, hipStream_t s, int32_t T, RowStats *h, int32_t *nt
     b->tiles_T = 0;
     if (!b->cols_owned) return EPI_OK;
     EPI_TRY(b->tiles_nt_dev.ensure(4));
-    EPI_HIP(hipMemcpyAsync(b->tiles_nt_dev.p, d_misc, 4, hipMemcpyDeviceToDevice, s));
+    EPI_HIP(hipMemcpyAsync(b->tiles_nt_dev.p, &sc->ntiles, 4, hipMemcpyDeviceToDevice, s));
     b->tiles_T = T; b->tiles_nt = (int32_t)nt; b->tiles_lmax = lmax; b->tiles_shared = b->shared_keys;
     return EPI_OK;
   };
   if (use_hint && hinted && b->cols_owned && b->tiles_T == T && b->tiles_lmax == lmax && b->tiles_shared == b->shared_keys) {
     // the batch owns its columns and the table of the last build was made for this tile size and these shared keys: it is
-    // still there (tiles, d_slot_tile); misc[0] gets the count the pass had left, which the caller compares as always
-    hipLaunchKernelGGL(k_misc_reset, dim3(1), dim3(64), 0, s, d_misc, b->tiles_nt_dev.as<uint32_t>());   // (one launch instead of three copies)
+    // still there (tiles, d_slot_tile); sc->ntiles gets the count the pass had left, which the caller compares as always
+    hipLaunchKernelGGL(k_misc_reset, dim3(1), dim3(64), 0, s, sc, b->tiles_nt_dev.as<uint32_t>());   // (one launch instead of three copies)
     EPI_HIP(hipGetLastError());
     *hinted = true;
     *ntiles_out = b->tiles_nt;
@@ -305,7 +304,7 @@ int build_tiles(epi_batch *b, hipStream_t s, int32_t T, RowStats *h, int32_t *nt
   if (use_hint && hinted && slot >= 0 && b->tile_hint_lmax[slot] == lmax) {
     // The tile count and the per-block offsets are functions of the batch's rows and T alone: with those of an earlier
     // call the table is allocated up front and filled by ONE pass that verifies them block by block; the caller
-    // compares misc[0] with the count when it next synchronises anyway.
+    // compares sc->ntiles with the count when it next synchronises anyway.
     const uint32_t nt = (uint32_t)b->tile_hint_nt[slot];
     EPI_TRY(b->tiles.ensure((size_t)nt * sizeof(Tile)));
     const int32_t nshared = (int32_t)b->shared_keys.size();
@@ -313,11 +312,11 @@ int build_tiles(epi_batch *b, hipStream_t s, int32_t T, RowStats *h, int32_t *nt
       EPI_TRY(b->d_slot_tile.ensure((size_t)nshared * 4));
       EPI_HIP(hipMemsetAsync(b->d_slot_tile.p, 0xFF, (size_t)nshared * 4, s));
     }
-    EPI_HIP(hipMemsetAsync(d_misc, 0, 4, s));
+    EPI_HIP(hipMemsetAsync(&sc->ntiles, 0, 4, s));
     prof_begin("tile_index", s);
     hipLaunchKernelGGL((k_tile_pass<true, true>), dim3((unsigned)nb), dim3(TB_THREADS), 0, s, b->start, b->rname, b->n, lmax, sh,
                        b->tile_bsum[slot].as<uint32_t>(), b->tiles.as<Tile>(), b->d_shared_keys.as<int64_t>(), nshared,
-                       b->d_slot_tile.as<int32_t>(), d_misc, (int64_t)nt);
+                       b->d_slot_tile.as<int32_t>(), sc, (int64_t)nt);
     prof_end("tile_index", s);
     EPI_HIP(hipGetLastError());
     EPI_TRY(remember_table(nt));
@@ -329,11 +328,11 @@ int build_tiles(epi_batch *b, hipStream_t s, int32_t T, RowStats *h, int32_t *nt
   EPI_TRY(b->scan_tmp.ensure((size_t)nb * 4));
   uint32_t *bsum = b->scan_tmp.as<uint32_t>();
   hipLaunchKernelGGL((k_tile_pass<false>), dim3((unsigned)nb), dim3(TB_THREADS), 0, s, b->start, b->rname, b->n, lmax, sh, bsum,
-                     (Tile *)nullptr, (const int64_t *)nullptr, 0, (int32_t *)nullptr, d_misc, (int64_t)0);
+                     (Tile *)nullptr, (const int64_t *)nullptr, 0, (int32_t *)nullptr, sc, (int64_t)0);
   EPI_HIP(hipGetLastError());
-  EPI_TRY(scan_block_sums_inplace(bsum, nb, d_misc, s));
+  EPI_TRY(scan_block_sums_inplace(bsum, nb, &sc->ntiles, s));
   uint32_t nt = 0;
-  EPI_TRY(read_scalars(b, s, d_misc, 4, &nt));
+  EPI_TRY(read_scalars(b, s, &sc->ntiles, 4, &nt));
   if (nt <= 0x7FFFFFF0u) {                                 // remember count and block offsets for the one-pass path above
     for (int i = 0; i < 4 && slot < 0; i++) if (b->tile_hint_T[i] == 0) slot = i;
     if (slot >= 0 && b->tile_bsum[slot].ensure((size_t)nb * 4) == EPI_OK &&
@@ -349,7 +348,7 @@ int build_tiles(epi_batch *b, hipStream_t s, int32_t T, RowStats *h, int32_t *nt
     EPI_HIP(hipMemsetAsync(b->d_slot_tile.p, 0xFF, (size_t)nshared * 4, s));
   }
   hipLaunchKernelGGL((k_tile_pass<true>), dim3((unsigned)nb), dim3(TB_THREADS), 0, s, b->start, b->rname, b->n, lmax, sh, bsum,
-                     b->tiles.as<Tile>(), b->d_shared_keys.as<int64_t>(), nshared, b->d_slot_tile.as<int32_t>(), d_misc, (int64_t)nt);
+                     b->tiles.as<Tile>(), b->d_shared_keys.as<int64_t>(), nshared, b->d_slot_tile.as<int32_t>(), sc, (int64_t)nt);
   EPI_HIP(hipGetLastError());
   EPI_TRY(remember_table(nt));
   *ntiles_out = (int32_t)nt;
