@@ -276,3 +276,162 @@ THRESHOLD_GRID = ((0, 0.0, 1.0), (1, 0.3, 0.0), (3, 1.0, 0.1), (2, 1 / 3, 0.1), 
 def cls4(ctx):
     c = CONTEXT_TO_BASES[ctx]
     return c["ctx_meth"], c["ctx_unmeth"], c["ooctx_meth"], c["ooctx_unmeth"]
+
+
+# ---- plain restatements of the BED path (numpy, int64 / float64), independent of the kernel and of bed.py ---------------
+
+NA_INT = -2 ** 31
+
+
+def _bed_hits(t, bed, capture, param, lo, hi):
+    """(hi - lo) x nbed boolean matrix: does read x fit BED row i (src/rcpp_match_target.cpp:34-38 / :70-73), in int64."""
+    b_chr, b_s, b_e = (np.asarray(a, np.int64)[None, :] for a in bed)
+    rs = np.asarray(t["start"][lo:hi], np.int64)[:, None]
+    re_ = rs + np.diff(t["off"])[lo:hi].astype(np.int64)[:, None] - 1          # read_end = start + len - 1
+    same = np.asarray(t["rname"][lo:hi], np.int64)[:, None] == b_chr
+    if capture:
+        return same & (np.minimum(re_, b_e) - np.maximum(rs, b_s) + 1 >= int(param))
+    return same & ((np.abs(rs - b_s) <= int(param)) | (np.abs(re_ - b_e) <= int(param)))
+
+
+def match_target_np(t, bed, capture, param, block=256, with_nfit=False):
+    """rcpp_match_amplicon / rcpp_match_capture: the 1-based number of the FIRST BED row a read fits, or NA_INT.  bed =
+    (rname code, start, end) integer arrays, NA_INT for an NA chromosome (it equals no rname).  Blocks of reads against
+    all BED rows: a hit matrix, argmax of the first hit.  with_nfit: also the number of rows every read fits."""
+    n, nbed = len(t["start"]), len(bed[0])
+    res = np.full(n, NA_INT, np.int32)
+    nfit = np.zeros(n, np.int64)
+    if nbed:
+        for lo in range(0, n, block):
+            hit = _bed_hits(t, bed, capture, param, lo, min(lo + block, n))
+            nfit[lo:lo + block] = hit.sum(axis=1)
+            res[lo:lo + block] = np.where(hit.any(axis=1), hit.argmax(axis=1) + 1, NA_INT)
+    return (res, nfit) if with_nfit else res
+
+
+def match_target_loop(t, bed, capture, param, rows=None):
+    """The same as the two nested loops of the reference, for a few hundred reads (rows: which ones, default all)."""
+    lens = np.diff(t["off"])
+    bed_rows = [(int(c), int(s), int(e)) for c, s, e in zip(*bed)]
+    rows = range(len(t["start"])) if rows is None else rows
+    res = []
+    for x in rows:
+        rs = int(t["start"][x])
+        re_ = rs + int(lens[x]) - 1
+        r = NA_INT
+        for i, (c, s, e) in enumerate(bed_rows):
+            if int(t["rname"][x]) != c:
+                continue
+            if (min(re_, e) - max(rs, s) + 1 >= param) if capture else (abs(rs - s) <= param or abs(re_ - e) <= param):
+                r = i + 1
+                break
+        res.append(r)
+    return np.asarray(res, np.int32)
+
+
+def bed_report_np(t, pass_, match, nbed):
+    """.getBedReport (R/internal.R:529-561) per BED row plus the NA slot (index nbed) of the unmatched reads: reads on
+    strand 1 / strand 2 and VEF = passing / all, float64, NaN for a slot without a read on either strand (the NA that
+    merge(all=TRUE) leaves).  A strand-0 row (the placeholder template) is counted nowhere.  has_na: the NA row exists."""
+    strand = np.asarray(t["strand"])
+    match = np.asarray(match, np.int64)
+    pass_ = np.asarray(pass_) != 0
+    slot = np.where(match < 0, nbed, match - 1)
+    npl = np.zeros(nbed + 1)
+    nmi = np.zeros(nbed + 1)
+    npass = np.zeros(nbed + 1)
+    for x in range(strand.size):
+        if strand[x] == 1:
+            npl[slot[x]] += 1
+        elif strand[x] == 2:
+            nmi[slot[x]] += 1
+        else:
+            continue
+        npass[slot[x]] += bool(pass_[x])
+    seen = (npl + nmi) > 0
+    with np.errstate(invalid="ignore", divide="ignore"):
+        vef = npass / (npl + nmi)
+    nan = lambda a: np.where(seen, a, np.nan)
+    return {"nreads+": nan(npl), "nreads-": nan(nmi), "VEF": nan(vef), "has_na": bool(seen[nbed])}
+
+
+def ecdf_np(x, q):
+    """stats::ecdf(x)(q): the share of x that is <= q, for every q."""
+    x = np.asarray(x, np.float64)
+    return np.asarray([np.count_nonzero(x <= v) / x.size for v in np.atleast_1d(np.asarray(q, np.float64))])
+
+
+def beta_np(xm, off, meth, unmeth):
+    """src/rcpp_get_xm_beta.cpp:37-39: n_meth / max(n_meth + n_unmeth, 1) per read, float64."""
+    n_m, n_u = class_counts(xm, off, meth), class_counts(xm, off, unmeth)
+    return n_m.astype(np.float64) / np.maximum(n_m + n_u, 1).astype(np.float64)
+
+
+# ---- the synthetic batch and BED of the BED-path tests (fixed seed; treat what these return as read-only) --------------
+
+MATCH_LEVELS = ("c1", "c2", "c3")
+MATCH_AMPLICON = (-1, 0, 1, 2, 5, 1000)                  # match.tolerance: nothing, exact, ..., everything on the chromosome
+MATCH_CAPTURE = (-50, 0, 1, 2, 30, 150, 400)             # match.min.overlap: within a gap, touching, ..., longer than any read
+MATCH_INTERIOR = {False: (0, 1, 2, 5), True: (0, 1, 2, 30, 150)}
+
+
+@functools.lru_cache(maxsize=None)
+def match_templates(seed=20240611):
+    """3001 ragged templates (empty ones among them) on three rnames, about 1 % with the placeholder's strand code 0."""
+    import synth_np
+    rng = np.random.default_rng(seed)
+    t = synth_np.random_templates(rng, 3001, 0, 300, 3, 60000)
+    t["strand"][rng.random(3001) < 0.01] = 0
+    return t
+
+
+@functools.lru_cache(maxsize=None)
+def match_bed(seed=20240611, nbed=2500):
+    """An unsorted BED of 2500 rows as (chromosome names, codes, start, end): chromosomes c1..c3, c4 (no read is on it)
+    and one that is not among the levels at all (code NA); end - start in -5..120; 600 rows are a read's own range
+    moved by -3..+3 at either end; 100 rows are copies of other rows."""
+    t = match_templates(seed)
+    rng = np.random.default_rng(seed + 1)
+    n = len(t["start"])
+    code = rng.choice(np.asarray([1, 2, 3, 4, NA_INT], np.int64), size=nbed, p=[0.3, 0.3, 0.3, 0.05, 0.05])
+    start = rng.integers(1, 60001, size=nbed).astype(np.int64)
+    end = start + rng.integers(-5, 121, size=nbed)
+    rows = rng.choice(nbed, size=600, replace=False)
+    reads = rng.choice(n, size=600, replace=False)
+    code[rows] = t["rname"][reads]
+    start[rows] = t["start"][reads].astype(np.int64) + rng.integers(-3, 4, size=600)
+    end[rows] = t["start"][reads].astype(np.int64) + np.diff(t["off"])[reads] - 1 + rng.integers(-3, 4, size=600)
+    dst = rng.choice(nbed, size=100, replace=False)
+    src = rng.integers(0, nbed, size=100)
+    code[dst], start[dst], end[dst] = code[src], start[src], end[src]
+    names = ["chrUn" if c == NA_INT else "c%d" % c for c in code]
+    return names, code, start, end
+
+
+def match_codes(names, levels=MATCH_LEVELS):
+    """factor(seqnames, levels=levels(rname)) as integer codes: NA_INT for a chromosome that is not a level."""
+    return np.asarray([levels.index(c) + 1 if c in levels else NA_INT for c in names], np.int64)
+
+
+@functools.lru_cache(maxsize=None)
+def match_want(capture, param, nbed=2500):
+    """(first fitting row, number of fitting rows) of every template against the first nbed rows of match_bed()."""
+    names, _, start, end = match_bed()
+    return match_target_np(match_templates(), (match_codes(names)[:nbed], start[:nbed], end[:nbed]), capture, param, with_nfit=True)
+
+
+def assert_match_design():
+    """What the synthetic case must give under the restatement alone, or it tests less than it says: at every interior
+    parameter some reads match and some do not, first matches fall into each of the kernel's three LDS chunks of 1024
+    rows, and at least 50 reads fit several rows (so that 'first' differs from 'any')."""
+    for capture in (False, True):
+        for param in MATCH_INTERIOR[capture]:
+            want, nfit = match_want(capture, param)
+            share = np.mean(want > 0)
+            assert 0 < share < 1, (capture, param, share)
+            for lo, hi in ((1, 1024), (1025, 2048), (2049, 2500)):
+                assert np.any((want >= lo) & (want <= hi)), (capture, param, lo)
+            multi = nfit > 1
+            if capture or param > 0:                       # (an exact start or end shared by several rows is rare)
+                assert np.count_nonzero(multi) >= 50, (capture, param, np.count_nonzero(multi))
+            assert np.all(want[multi] > 0)
