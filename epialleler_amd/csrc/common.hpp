@@ -146,6 +146,18 @@ constexpr int kLenBins[kLenBinCount] = {12, 16, 20, 24, 32, 40, 48, 64, 80, 96, 
 
 struct epi_shard_plan;      // comm.hip: shared tile keys of a (batch, tile grid, communicator) triple
 
+namespace epi {
+// What the last report call left on a batch; the first half of a sharded report is continued by its *_finish_shared call
+enum ReportKind {
+  KIND_NONE = 0,
+  KIND_CX = 1,              // finished CX report
+  KIND_MHL = 2,             // finished lMHL report
+  KIND_CX_SHARED = 3,       // first half of a sharded CX report
+  KIND_MHL_SHARED = 4,      // ... of a sharded lMHL report, two-kernel path (slabs in k_mhl_tiles' layout)
+  KIND_MHLF_SHARED = 5,     // ... of a sharded lMHL report, one-pass kernel (slabs in its layout, mhl_common.hpp)
+};
+}  // namespace epi
+
 struct epi_batch {
   epi_engine *eng = nullptr;
   int64_t n = 0, nbytes = 0;
@@ -215,7 +227,7 @@ struct epi_batch {
   size_t pool_cap2 = 0;     // rows that fit pool_d/pool_e (lMHL doubles)
 
   // state of the last report (for fetch)
-  int last_kind = 0;        // 0 none, 1 cx, 2 mhl; 3 / 4 / 5: first half of a sharded cx / two-kernel lMHL / fused lMHL report
+  epi::ReportKind last_kind = epi::KIND_NONE;
   int64_t last_nrow = 0;
   int32_t last_ntiles = 0;
   int32_t tile_hint_T[4] = {0, 0, 0, 0};    // tile counts of this (immutable) batch by tile size, as found by earlier calls
@@ -361,6 +373,14 @@ int layout_copy_range(const uint8_t *src, int64_t c0, int64_t c1, const int64_t 
 // (no host round trip in the middle of the index build) and verifies it against Scalars::ntiles at its own synchronisation.
 int build_tiles(epi_batch *b, hipStream_t s, int32_t tile_positions, RowStats *h_stats, int32_t *ntiles_out, bool *hinted = nullptr);
 
+// Row pool of a report: a slot per tile + an overflow region (the scheme: tiles.hip, with layout_pool)
+struct PoolLayout {
+  uint32_t slot;            // pool rows per tile slot (0: every tile through the cursor)
+  size_t ovf_base;          // first row of the overflow region = nt * slot
+};
+int layout_pool(epi_batch *b, uint32_t slot, int T, int32_t nt, size_t headroom, int hook_slot, int (*reserve)(epi_batch *, size_t rows),
+                PoolLayout *out);
+
 // Result-neutral switches (test hooks that steer a call onto a rarely taken path, A/B shapes): read from the environment
 // ONCE per process into this struct; epi_options_reload() re-reads it (tests that change a hook inside one process).
 struct Options {
@@ -378,9 +398,7 @@ struct Options {
   int mhl_wg = 0;            // EPIHIP_MHL_WG        256 / 512 (two-kernel path)
   int mhl_tile_group = 0;    // EPIHIP_MHL_TILE_GROUP
   int mhl_multi = 0;         // EPIHIP_MHL_MULTI     wavefront-per-read pass 1
-  int mhl_group_g = 0, mhl_group_c = 0;   // EPIHIP_MHL_GROUP="G,C"
   int mhl_sums = 0;          // EPIHIP_MHL_SUMS      32 / 64
-  int mhlf_shape = 0;        // EPIHIP_MHLF_SHAPE="G,CA[,CB]"  lane shape of the one-pass lMHL kernel, as G * 100 + CA * 10 + CB
   int mhlf_fold = -1;        // EPIHIP_MHLF_FOLD=0/1 one-pass lMHL kernel without / with the LDS array of folded call counters (-1: by the batch)
   int mhlf_fold_slots = -1;  // EPIHIP_MHLF_FOLD_SLOTS  slab slots of the kernel without it (-1: default)
   int pr_group = 0;          // EPIHIP_GROUP         lanes per read of the general per-read kernel
@@ -416,7 +434,6 @@ __device__ __forceinline__ bool epi_dev_check(uint32_t *dbg, bool ok, uint32_t c
 #endif
 #endif
 
-// context-string helpers (host)
 // Wave-level scans and reductions as DPP moves (row_shr 1, 2, 4, 8 inside a row of 16 lanes, then row_bcast:15 into
 // rows 1 and 3 and row_bcast:31 into rows 2 and 3): VALU instructions, where __shfl_* is a ds_bpermute through the
 // LDS pipe with ~100 cycles of latency.  Device code only.
@@ -450,6 +467,12 @@ __host__ __device__ __forceinline__ uint64_t hash3(uint64_t seed, uint64_t strea
 }
 
 __host__ __device__ inline unsigned ctx_to_idx(unsigned char c) { return ((unsigned(c) + 2u) >> 2) & 15u; }   // src/epialleleR.h:28
+// the codes of a report's context string as a bit mask (rcpp_cx_report.cpp:88-91, rcpp_mhl_report.cpp:104-107)
+inline uint32_t ctx_mask_of(const char *ctx) {
+  uint32_t ctx_mask = 0;
+  for (const unsigned char *c = reinterpret_cast<const unsigned char *>(ctx); *c; c++) ctx_mask |= 1u << ctx_to_idx(*c);
+  return ctx_mask;
+}
 
 // A grid holds fewer than 2^32 threads (a larger one wraps silently): refuse instead.
 inline int check_grid(int64_t blocks, int threads, const char *what) {

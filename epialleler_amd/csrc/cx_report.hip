@@ -1488,11 +1488,6 @@ static bool make_fused_lut(const CxThreshold &t, uint32_t ctx_of_plane, int np, 
   return true;
 }
 
-static uint32_t cx_ctx_mask(const char *ctx) {
-  uint32_t ctx_mask = 0;                                   // rcpp_cx_report.cpp:88-91
-  for (const unsigned char *c = reinterpret_cast<const unsigned char *>(ctx); *c; c++) ctx_mask |= 1u << ctx_to_idx(*c);
-  return ctx_mask;
-}
 // Direct mode: rows of the report whose tile offsets the batch keeps (cx_prev_*) if it had these contexts, else -1.
 static int64_t cx_recorded_nrow(const epi_batch *b, uint32_t ctx_mask) {
   return b->cx_prev_key == (ctx_mask | 0x80000000u) ? b->cx_prev_nrow : -1;
@@ -1510,8 +1505,7 @@ struct CxPlan {
   int shape, shape_heavy;                 // lanes per row * 8 + chunks per lane: tile kernel / general and heavy-tile kernels
   int32_t nshared;                        // tiles shared with other ranks ...
   size_t headroom;                        // ... and the pool rows kept free for them (they are emitted later into the same pool)
-  uint32_t slot;                          // pool rows per tile slot (0: every tile through the cursor)
-  size_t ovf_base;                        // first row of the overflow region = nt * slot
+  PoolLayout pool;                        // slot rows per tile, first row of the overflow region
 };
 
 // A remembered tile count that the index pass could not confirm: the rows were changed under the batch.
@@ -1559,34 +1553,16 @@ static int cx_setup_threshold(epi_batch *b, const CxThreshold &thr, const RowSta
   return EPI_OK;
 }
 
-// Row pool = one slot per tile + an overflow region behind the slots (cx_pool_reserve).  The slot size starts at a typical
-// density of reported cytosines (CpG ~6 % of the (pos,strand) cells of a tile, all contexts ~40 %) and doubles for the next
-// call when more than 1/8 of the rows went through the overflow cursor (cx_report_impl); an overflow of the region itself
-// is detected after the run and costs one rerun with the exact size.
+// The remembered slot size of the row pool (layout_pool, tiles.hip): it starts at a typical density of reported cytosines
+// (CpG ~6 % of the (pos,strand) cells of a tile, all contexts ~40 %) and is doubled by cx_report_impl.
 static uint32_t &cx_slot_state(epi_batch *b, uint32_t ctx_mask) { return (ctx_mask & ~(1u << 7)) ? b->cx_slot_wide : b->cx_slot_cg; }
 
 static int cx_layout_pool(epi_batch *b, uint32_t ctx_mask, CxPlan &p) {
-  const int T = p.T;
   uint32_t &slot_state = cx_slot_state(b, ctx_mask);
-  if (!slot_state) slot_state = (ctx_mask & ~(1u << 7)) ? (uint32_t)(3 * T) / 4 : (uint32_t)T / 8;
-  uint32_t slot = slot_state > (uint32_t)(2 * T) ? (uint32_t)(2 * T) : slot_state;
-  if (options().cx_slot >= 0 && options().cx_slot <= 2 * T) slot = (uint32_t)options().cx_slot;   // test hook (EPIHIP_CX_SLOT)
-  while (slot && (unsigned long long)p.nt * slot > 0xC0000000ull) slot >>= 1;   // row indices are u32
-  size_t ovf_base = (size_t)p.nt * slot;
-  for (;;) {
-    const size_t ovf = (ovf_base >> 4) > 65536 ? (ovf_base >> 4) : 65536;
-    if (b->pool_cap >= ovf_base + ovf + p.headroom) break;
-    const int rc = ensure_pool(b, ovf_base + ovf + p.headroom);
-    if (rc == EPI_OK) break;
-    b->pool_cap = 0;                                       // (a failed growth has released the old buffers)
-    if (!slot) return rc;
-    slot = 0;                                              // the slots do not fit in device memory: every tile through the
-    ovf_base = 0;                                          // cursor, the pool sized by the rows actually produced
-  }
-  p.slot = slot;
-  p.ovf_base = ovf_base;
-  b->cx_last_slot = slot;
-  b->cx_last_ovf = (uint32_t)ovf_base;
+  if (!slot_state) slot_state = (ctx_mask & ~(1u << 7)) ? (uint32_t)(3 * p.T) / 4 : (uint32_t)p.T / 8;
+  EPI_TRY(layout_pool(b, slot_state, p.T, p.nt, p.headroom, options().cx_slot, ensure_pool, &p.pool));   // test hook (EPIHIP_CX_SLOT)
+  b->cx_last_slot = p.pool.slot;
+  b->cx_last_ovf = (uint32_t)p.pool.ovf_base;
   return EPI_OK;
 }
 
@@ -1739,8 +1715,8 @@ static int cx_report_impl(epi_batch *b, const int32_t *d_pass, const CxThreshold
                           int *written = nullptr) {
   *nrow_out = 0;
   if (written) *written = 0;
-  b->last_kind = 0;
-  const uint32_t ctx_mask = cx_ctx_mask(ctx);
+  b->last_kind = KIND_NONE;
+  const uint32_t ctx_mask = ctx_mask_of(ctx);
 
   Cx2Args a;
   memset(&a, 0, sizeof(a));
@@ -1755,7 +1731,7 @@ static int cx_report_impl(epi_batch *b, const int32_t *d_pass, const CxThreshold
   if (thr) EPI_TRY(cx_setup_threshold(b, *thr, st, p, d_pass_out, s, a, &d_pass));
   if (p.nt == 0 || p.np == 0) {                            // no rows, or a context string without H/X/Z: an empty table
     // (a rank of a sharded run without rows still takes part in the exchange: its second half returns the empty table)
-    b->last_kind = !b->shared_keys.empty() && b->d_slab ? 3 : 1; b->last_nrow = 0; b->last_ntiles = 0;
+    b->last_kind = !b->shared_keys.empty() && b->d_slab ? KIND_CX_SHARED : KIND_CX; b->last_nrow = 0; b->last_ntiles = 0;
     return EPI_OK;
   }
   const int T = p.T, np = p.np;
@@ -1801,7 +1777,7 @@ static int cx_report_impl(epi_batch *b, const int32_t *d_pass, const CxThreshold
     EPI_TRY(read_report_scalars(b, s, &host));
     EPI_TRY(cx_check_tile_count(b, p.nt_hinted, host.ntiles, nt));
     if (host.cursor == 0) {
-      b->last_kind = 0;                                    // (nothing to fetch: the rows are where the caller wants them)
+      b->last_kind = KIND_NONE;                                    // (nothing to fetch: the rows are where the caller wants them)
       b->last_nrow = 0;
       *nrow_out = b->cx_prev_nrow;
       if (written) *written = 1;
@@ -1822,13 +1798,13 @@ static int cx_report_impl(epi_batch *b, const int32_t *d_pass, const CxThreshold
       // slab if the pool turns out too small)
       b->cx_deferred = true;
       b->cx_def_heavy_done = p.chained ? CX_HEAVY_CAP : 0u;
-      b->last_kind = 3;
+      b->last_kind = KIND_CX_SHARED;
       return EPI_OK;
     }
     EPI_TRY(cx_finish_pool_run(b, p, a, s, run + (direct ? 1 : 0), &host, &host_heavy));
-    if (p.ovf_base + host.cursor + p.headroom <= a.pool_cap) break;
+    if (p.pool.ovf_base + host.cursor + p.headroom <= a.pool_cap) break;
     if (run == 1) return fail(EPI_ERR_STATE, "row pool overflow after regrow");
-    EPI_TRY(ensure_pool(b, p.ovf_base + host.cursor + (host.cursor >> 4) + 1024 + p.headroom));   // exact need is known now: rerun once
+    EPI_TRY(ensure_pool(b, p.pool.ovf_base + host.cursor + (host.cursor >> 4) + 1024 + p.headroom));   // exact need is known now: rerun once
     if (p.nshared > 0)   // the rerun adds into the slab again
       EPI_HIP(hipMemsetAsync(b->d_slab, 0, (size_t)p.nshared * kCxPlanes * T * 4, s));
   }
@@ -1836,8 +1812,8 @@ static int cx_report_impl(epi_batch *b, const int32_t *d_pass, const CxThreshold
   if (host.cursor > host.rows / 8 && slot_state < (uint32_t)(2 * T)) slot_state *= 2;   // too many tiles outgrew their slot
   // (no ultra-deep tile was left for the host to finish: a later sharded report on this batch may defer its synchronisation)
   if (!host_heavy) { b->cx_noheavy_T = T; b->cx_noheavy_rows = a.heavy_rows; }
-  if (p.nshared > 0) { b->last_kind = 3; return EPI_OK; }   // caller continues with epi_batch_cx_finish_shared
-  b->last_kind = 1;
+  if (p.nshared > 0) { b->last_kind = KIND_CX_SHARED; return EPI_OK; }   // caller continues with epi_batch_cx_finish_shared
+  b->last_kind = KIND_CX;
   b->last_nrow = host.rows;
   *nrow_out = host.rows;
   return cx_keep_offsets(b, ctx_mask, p, host.rows, s);
@@ -1854,7 +1830,7 @@ int epi_tile_positions(void) { return cx_tile_for(1); }
 int epi_cx_tile_positions(const char *ctx) {
   uint32_t cop = 0;
   ClassLut l;
-  return cx_tile_for(make_report_lut(ctx ? cx_ctx_mask(ctx) : 0u, &l, &cop));
+  return cx_tile_for(make_report_lut(ctx ? ctx_mask_of(ctx) : 0u, &l, &cop));
 }
 
 int epi_batch_cx_report_dev(epi_batch *b, const int32_t *d_pass, const char *ctx, void *stream, int64_t *nrow_out) {
@@ -1873,7 +1849,7 @@ int epi_batch_cytosine_report_dev(epi_batch *b, const char *ctx_meth, const char
 
 int epi_batch_cx_report_capacity(epi_batch *b, const char *ctx, int64_t *nrow) {
   if (!b || !ctx || !nrow) return fail(EPI_ERR_ARG, "epi_batch_cx_report_capacity: NULL argument");
-  *nrow = cx_recorded_nrow(b, cx_ctx_mask(ctx));
+  *nrow = cx_recorded_nrow(b, ctx_mask_of(ctx));
   return EPI_OK;
 }
 
@@ -1902,11 +1878,11 @@ int epi_batch_cytosine_report_into_dev(epi_batch *b, const char *ctx_meth, const
 // emit the shared tiles this rank owns, then order all rows.
 int epi_batch_cx_finish_shared(epi_batch *b, const char *ctx, void *stream, int64_t *nrow_out) {
   if (!b || !ctx || !nrow_out) return fail(EPI_ERR_ARG, "epi_batch_cx_finish_shared: NULL argument");
-  if (b->last_kind != 3) return fail(EPI_ERR_STATE, "epi_batch_cx_finish_shared without a sharded epi_batch_cx_report_dev");
+  if (b->last_kind != KIND_CX_SHARED) return fail(EPI_ERR_STATE, "epi_batch_cx_finish_shared without a sharded epi_batch_cx_report_dev");
   EPI_HIP(hipSetDevice(b->eng->device));
   hipStream_t s = pick_stream(b, stream);
   const int32_t nt = b->last_ntiles;
-  if (nt == 0) { b->last_kind = 1; b->last_nrow = 0; *nrow_out = 0; return EPI_OK; }   // this rank holds no rows: owns no tile
+  if (nt == 0) { b->last_kind = KIND_CX; b->last_nrow = 0; *nrow_out = 0; return EPI_OK; }   // this rank holds no rows: owns no tile
   Cx2Args a;
   memset(&a, 0, sizeof(a));
   cx_bind_pool(b, a);
@@ -1928,14 +1904,14 @@ int epi_batch_cx_finish_shared(epi_batch *b, const char *ctx, void *stream, int6
     if ((size_t)a.ovf_base + host.cursor > a.pool_cap) {      // (the cursor has served the shared tiles' rows as well by now)
       // the pool was too small for the rows of this report: the caller reruns the first half (which grows it) into a
       // scratch slab and emits the shared tiles from the slab that has already been reduced
-      b->last_kind = 0;
+      b->last_kind = KIND_NONE;
       return EPI_RETRY_POOL;
     }
   }
   // cannot overflow: the first half kept 2*kTile rows per shared tile free
   if ((size_t)a.ovf_base + host.cursor > a.pool_cap) return fail(EPI_ERR_STATE, "row pool overflow in sharded report");
   const uint32_t total = host.rows;
-  b->last_kind = 1;
+  b->last_kind = KIND_CX;
   b->last_nrow = total;
   *nrow_out = total;
   return EPI_OK;
@@ -1996,7 +1972,7 @@ int epi_batch_tile_key_range_for(epi_batch *b, int tile_positions, void *stream,
 
 int epi_batch_cx_fetch_dev(epi_batch *b, int32_t *const d_cols[6], void *stream) {
   if (!b || !d_cols) return fail(EPI_ERR_ARG, "epi_batch_cx_fetch_dev: NULL argument");
-  if (b->last_kind != 1) return fail(EPI_ERR_STATE, "epi_batch_cx_fetch_dev: no finished CX report on this batch");
+  if (b->last_kind != KIND_CX) return fail(EPI_ERR_STATE, "epi_batch_cx_fetch_dev: no finished CX report on this batch");
   if (b->last_nrow == 0) return EPI_OK;
   for (int i = 0; i < 6; i++) if (!d_cols[i]) return fail(EPI_ERR_ARG, "epi_batch_cx_fetch_dev: NULL column");
   EPI_HIP(hipSetDevice(b->eng->device));
@@ -2014,7 +1990,7 @@ int epi_batch_cx_fetch_dev(epi_batch *b, int32_t *const d_cols[6], void *stream)
 
 int epi_batch_cx_fetch_host(epi_batch *b, int32_t *const h_cols[6], void *stream) {
   if (!b || !h_cols) return fail(EPI_ERR_ARG, "epi_batch_cx_fetch_host: NULL argument");
-  if (b->last_kind != 1) return fail(EPI_ERR_STATE, "epi_batch_cx_fetch_host: no finished CX report on this batch");
+  if (b->last_kind != KIND_CX) return fail(EPI_ERR_STATE, "epi_batch_cx_fetch_host: no finished CX report on this batch");
   const int64_t nrow = b->last_nrow;
   if (nrow == 0) return EPI_OK;
   EPI_HIP(hipSetDevice(b->eng->device));

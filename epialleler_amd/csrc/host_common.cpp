@@ -47,15 +47,7 @@ static void read_options() {
   if (o.mhl_wg != 256 && o.mhl_wg != 512) o.mhl_wg = 0;
   geti("EPIHIP_MHL_TILE_GROUP", &o.mhl_tile_group);
   o.mhl_multi = getenv("EPIHIP_MHL_MULTI") != nullptr;
-  if (const char *e = getenv("EPIHIP_MHL_GROUP")) { int g = 0, c = 0; if (sscanf(e, "%d,%d", &g, &c) == 2) { o.mhl_group_g = g; o.mhl_group_c = c; } else o.mhl_group_g = -1; }
   geti("EPIHIP_MHL_SUMS", &o.mhl_sums);
-  if (const char *e = getenv("EPIHIP_MHLF_SHAPE")) {
-    int g = 0, ca = 0, cb = 0;
-    const int nf = sscanf(e, "%d,%d,%d", &g, &ca, &cb);
-    const bool two = nf == 3 && cb == 2 && ca == 3 && g >= 4 && g <= 32;
-    if (nf >= 2 && (g == 2 || g == 4 || g == 8 || g == 16 || g == 32 || g == 64) && ca >= 2 && ca <= 4 && (nf == 2 || cb == 0 || two))
-      o.mhlf_shape = g * 100 + ca * 10 + (nf == 3 ? cb : 0);
-  }
   if (const char *e = getenv("EPIHIP_MHLF_FOLD")) o.mhlf_fold = atoi(e) != 0;
   geti("EPIHIP_MHLF_FOLD_SLOTS", &o.mhlf_fold_slots);
   geti("EPIHIP_GROUP", &o.pr_group);

@@ -189,7 +189,7 @@ int realign_batch(epi_batch *b, int modulus, hipStream_t s) {
   if (modulus != 4 && modulus != 8 && modulus != 16) return fail(EPI_ERR_ARG, "realign: modulus must be 4, 8 or 16");
   if (b->congruent == modulus || b->n == 0) { b->congruent = modulus; return EPI_OK; }
   if (!b->stats_queued || !b->len) return fail(EPI_ERR_STATE, "realign: the batch has no row lengths yet");
-  if (b->last_kind != 0) return fail(EPI_ERR_STATE, "epi_batch_realign: call it before the first report on the batch");
+  if (b->last_kind != KIND_NONE) return fail(EPI_ERR_STATE, "epi_batch_realign: call it before the first report on the batch");
   EPI_HIP(hipStreamWaitEvent(s, b->stats_done, 0));       // len[] is written by k_row_stats, possibly on another stream
   DevBuf new_off, new_xm;
   int rc = EPI_OK;

@@ -162,8 +162,56 @@ __device__ __forceinline__ ST mhl_wave_scan(ST v) {
 // ---- host helpers defined in mhl_report.hip ---------------------------------------------------------------------------
 size_t mhl_pool_rows(const epi_batch *b);
 int ensure_mhl_pool(epi_batch *b, size_t rows);
+int mhl_layout_pool(epi_batch *b, uint32_t &slot_state, int T, int32_t nt, size_t headroom, PoolLayout *l);
 int pick_mhl_group(int32_t max_len);             // lanes per read x chunks per lane as G * 8 + C (0: longer than 64 lanes cover)
 MhlLut make_mhl_lut(uint32_t ctx_mask);
+// Tail of the second half of a sharded report, either path: the tiles' row offsets, the one synchronisation, the pool
+// check, the finished report's state
+int mhl_finish_rows(epi_batch *b, hipStream_t s, int64_t *nrow_out);
+
+// Check build (EPI_CHECK, EPI_MHL_CHECK): the record of the first index violation {code, v0, v1, block, thread} that the
+// kernels of either path fill -- cleared before a report's first kernel, read back behind an attempt
+inline int mhl_check_begin(epi_batch *b, hipStream_t s, uint32_t **dbg) {
+  EPI_TRY(b->diag.ensure(256));
+  *dbg = b->diag.as<uint32_t>();
+  EPI_HIP(hipMemsetAsync(*dbg, 0, 32, s));
+  return EPI_OK;
+}
+inline int mhl_check_end(const epi_batch *b, const uint32_t *dbg, const char *what, int32_t nt, int attempt) {
+  uint32_t d[8];
+  EPI_HIP(hipMemcpy(d, dbg, 32, hipMemcpyDeviceToHost));
+  if (d[0]) return fail(EPI_ERR_STATE, "%s index check %u failed: v0=%d v1=%d block=%u thread=%u (n=%lld nt=%d attempt=%d)", what, d[0],
+                        (int)d[1], (int)d[2], d[3], d[4], (long long)b->n, nt, attempt);
+  return EPI_OK;
+}
+
+// The haplotype context (2 = H, 6 = X, 7 = Z) of a mask that is exactly one context in both cases (generateMhlReport's
+// "Hh", "Xx", "Zz"); 0 for every other mask.
+inline uint32_t mhl_single_context(uint32_t ctx_mask) {
+  for (uint32_t c : {2u, 6u, 7u}) if (ctx_mask == ((1u << c) | (1u << (c + 8)))) return c;
+  return 0;
+}
+
+// rows of the pool that a kernel may address (row indices are u32)
+inline uint32_t mhl_pool_cap(const epi_batch *b) { return (uint32_t)(mhl_pool_rows(b) > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : mhl_pool_rows(b)); }
+
+// The batch's tile table, row pool (as it is now: a regrown pool is bound again) and the layout of its last lMHL report, into
+// the argument struct of either path (MhlArgs, MhlFArgs: the members have the same names)
+template <class Args>
+inline void mhl_bind_pool(const epi_batch *b, Args &a) {
+  a.tiles = b->tiles.as<Tile>();
+  a.cursor = &report_scalars(b)->cursor;
+  a.tile_nrow = b->tile_nrow.as<uint32_t>();
+  a.tile_base = b->tile_base.as<uint32_t>();
+  a.pool_key = b->pool_key.as<uint32_t>();
+  a.pool_cov = b->pool_a.as<uint32_t>();
+  a.pool_hs = b->pool_d.as<unsigned long long>();
+  a.pool_nu = b->pool_e.as<unsigned long long>();
+  a.pool_de = b->pool_f.as<unsigned long long>();
+  a.pool_cap = mhl_pool_cap(b);
+  a.slot_rows = b->mhl_last_slot;
+  a.ovf_base = b->mhl_last_ovf;
+}
 
 // ---- the fused path (mhl_fused.hip) --------------------------------------------------------------------------------------
 #ifndef EPI_MHLF_T                                // (timing builds vary it; the product uses this value)
@@ -175,7 +223,7 @@ constexpr int MHLF_CNT_PLANES = 4, MHLF_SUM_PLANES = 6;   // shared-tile slabs: 
 // *done = false: the batch is not eligible -- the caller runs the two-kernel path instead.
 int mhl_fused_report(epi_batch *b, uint32_t ctx_mask, uint32_t H, int hmin, double max_oo, hipStream_t s,
                      int64_t *nrow_out, bool *done);
-bool mhl_fused_eligible(epi_batch *b, uint32_t ctx_mask, const RowStats &st);
+bool mhl_fused_eligible(uint32_t ctx_mask, const RowStats &st);
 int mhl_fused_finish_shared(epi_batch *b, hipStream_t s, int64_t *nrow_out);
 
 }  // namespace epi

@@ -879,10 +879,6 @@ static MhlLut make_mhlf_lut2(uint32_t ctx_mask) {
 // wherever it starts inside its first 16 bytes (ties: fewer lanes).  One block per lane (CB = 0: CA = 2, 3, 4, 512-thread
 // workgroups) or two (CA = 3, CB = 2: 80 bytes per lane, 256-thread workgroups).
 static int pick_mhlf_shape(int32_t max_len) {
-  if (options().mhlf_shape > 0) {                          // A/B runs (EPIHIP_MHLF_SHAPE="G,CA[,CB]"); must cover the reads
-    const int g = options().mhlf_shape / 100, ca = options().mhlf_shape / 10 % 10, cb = options().mhlf_shape % 10;
-    if ((int64_t)g * 16 * (ca + cb) >= (int64_t)max_len + 15) return options().mhlf_shape;
-  }
   int best = 0;
   int64_t best_cap = 0;
   for (int g = 2; g <= 64; g <<= 1)
@@ -901,7 +897,6 @@ static int pick_mhlf_shape(int32_t max_len) {
 // longest row.  One 1 kb template among 100 000 PE150 ones used to make every row pay for 1 kb (scratch/outlier_cost.py).
 static int pick_mhlf_shape_hist(const RowStats &st, int64_t n, int32_t nt, int T) {
   const int wide = pick_mhlf_shape(st.max_len);
-  if (options().mhlf_shape) return wide;
   double total = 0;
   for (int k = 0; k < kLenBinCount; k++) total += st.len_hist[k];
   if (total == 0 || nt <= 0 || !wide) return wide;
@@ -960,177 +955,178 @@ static void launch_mhl_fused(int shape, unsigned grid, int nt, hipStream_t s, co
   }
 }
 
-bool mhl_fused_eligible(epi_batch *b, uint32_t ctx_mask, const RowStats &st) {
-  (void)b;
-  if (!options().mhl_fused || options().mhl_group_g != 0) return false;    // test hooks: the two-kernel path / its lane shapes
-  bool one = false;
-  for (uint32_t c : {2u, 6u, 7u}) if (ctx_mask == ((1u << c) | (1u << (c + 8)))) one = true;
-  if (!one) return false;                                  // one context, both cases (generateMhlReport's "Zz", "Xx", "Hh")
-  return pick_mhl_group(st.max_len) != 0;                  // reads of one block of lanes (up to 64 x 64 bytes)
+// The one-pass kernel takes a report when it is switched on (EPIHIP_MHL_FUSED), the report has one haplotype context in both
+// cases, the rows are short enough for one block of lanes (up to 64 x 64 bytes), and EPIHIP_MHL_MULTI (the two-kernel path's
+// wavefront-per-read pass 1, for tests) is not set.
+bool mhl_fused_eligible(uint32_t ctx_mask, const RowStats &st) {
+  return options().mhl_fused && !options().mhl_multi && mhl_single_context(ctx_mask) != 0 && pick_mhl_group(st.max_len) != 0;
 }
 
-static void fill_args_common(epi_batch *b, MhlFArgs &a) {
-  a.tiles = b->tiles.as<Tile>();
-  a.cursor = &report_scalars(b)->cursor;
-  a.tile_nrow = b->tile_nrow.as<uint32_t>();
-  a.tile_base = b->tile_base.as<uint32_t>();
-  a.pool_key = b->pool_key.as<uint32_t>();
-  a.pool_cov = b->pool_a.as<uint32_t>();
-  a.pool_hs = b->pool_d.as<unsigned long long>();
-  a.pool_nu = b->pool_e.as<unsigned long long>();
-  a.pool_de = b->pool_f.as<unsigned long long>();
-  a.pool_cap = (uint32_t)(mhl_pool_rows(b) > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : mhl_pool_rows(b));
-  a.slab_cnt = b->d_mhl_cnt_slab;
-  a.slab_sum = reinterpret_cast<unsigned long long *>(b->d_mhl_sum_slab);
+// ---- the one-pass report on the host -------------------------------------------------------------------------------------
+
+// What one report call has decided before it queues a tile kernel.
+struct MhlfPlan {
+  int32_t nt;                             // tiles ...
+  bool nt_hinted;                         // ... a count remembered from an earlier call, verified at the report's synchronisation
+  int32_t nshared;                        // tiles shared with other ranks ...
+  size_t headroom;                        // ... and the pool rows kept free for them (they are emitted later into the same pool)
+  PoolLayout pool;                        // slot rows per tile, first row of the overflow region
+  int shape, shape_wide;                  // lane shapes: the fast variant's, for the bulk of the rows / the one that holds every row
+  bool fold;                              // fast variant with the LDS array of folded call counters
+  uint32_t fold_slots;                    // ... without it: slab slots for the tiles of more than 255 rows
+};
+
+// Decision table over 0 .. longest row; kept while max_oo does not change (bitwise: a NaN compares equal to itself)
+static int mhlf_keep_table(epi_batch *b, int32_t max_len, double max_oo, hipStream_t s, MhlFArgs &a) {
+  if (b->mhl_keep_len != max_len || memcmp(&b->mhl_keep_oo, &max_oo, sizeof(double)) != 0) {
+    EPI_TRY(b->mhl_keep_tab.ensure((size_t)(max_len + 1) * 4));
+    hipLaunchKernelGGL(k_mhl_keep_table, dim3((unsigned)(max_len / 256 + 1)), dim3(256), 0, s, max_oo, max_len, b->mhl_keep_tab.as<uint32_t>());
+    EPI_HIP(hipGetLastError());
+    b->mhl_keep_len = max_len;
+    b->mhl_keep_oo = max_oo;
+  }
+  a.keep_tab = b->mhl_keep_tab.as<uint32_t>();
+  return EPI_OK;
 }
 
-// The fused path.  *done = false: the batch is not eligible -- the caller runs the two-kernel path instead.  With shared
-// tiles attached (epi_batch_mhl_set_shared with the fused layout) the report stops after the accumulation (last_kind 5):
-// the caller all-reduces the slabs and continues with mhl_fused_finish_shared.
-int mhl_fused_report(epi_batch *b, uint32_t ctx_mask, uint32_t H, int hmin, double max_oo, hipStream_t s,
-                     int64_t *nrow_out, bool *done) {
-  *done = false;
-  const int32_t nshared = (int32_t)b->shared_keys.size();
-  if (nshared > 0 && !b->mhl_shared_fused) return EPI_OK;  // the slabs attached are the two-kernel path's
-  constexpr int T = MHLF_T;
-  RowStats st;
-  int32_t nt = 0;
-  bool nt_hinted = false;                                  // (a remembered tile count is verified at the synchronisation below)
-  EPI_TRY(build_tiles(b, s, T, &st, &nt, &nt_hinted));
-  if (!mhl_fused_eligible(b, ctx_mask, st)) {
-    if (nshared > 0) return fail(EPI_ERR_STATE, "shared tiles were attached for the one-pass lMHL kernel, but this batch needs the two-kernel path");
-    return EPI_OK;
+// The fast variant comes with and without the LDS array of folded call counters.  Without it a workgroup needs 4 KB less
+// LDS (five per CU instead of four) and a tile of more than 255 rows folds its u8 counters into a slot of a slab in HBM
+// (MHLF_FOLD_SLOTS of them; a tile that finds none left goes to the WIDE variant with the other deep tiles).  Batches whose
+// tiles average well below 255 rows start there; one that runs out of slots switches the batch over.
+static int mhlf_pick_fold(epi_batch *b, MhlfPlan &p, MhlFArgs &a) {
+  p.fold = options().mhlf_fold >= 0 ? options().mhlf_fold != 0 : (b->mhlf_prefer_fold || (double)b->n > 150.0 * (double)p.nt);
+  p.fold_slots = options().mhlf_fold_slots >= 0 && (uint32_t)options().mhlf_fold_slots < MHLF_FOLD_SLOTS
+                     ? (uint32_t)options().mhlf_fold_slots : MHLF_FOLD_SLOTS;   // (test hook: fewer)
+  a.fold_cursor = &report_scalars(b)->fold_cursor;
+  if (!p.fold) {
+    EPI_TRY(b->mhlf_fold_slab.ensure((size_t)MHLF_FOLD_SLOTS * 2 * MHLF_T * 4));
+    a.fold_slab = b->mhlf_fold_slab.as<uint32_t>();
+    a.fold_slots = p.fold_slots;
   }
-  const int gc_wide = pick_mhlf_shape(st.max_len);         // holds every row
-  const int gc = pick_mhlf_shape_hist(st, b->n, nt, T);    // the fast variant's: for the bulk of the rows
-  uint32_t k = 0;
-  for (uint32_t c : {2u, 6u, 7u}) if (ctx_mask == ((1u << c) | (1u << (c + 8)))) k = c;
-  b->last_ntiles = nt;
-  if (nt == 0) { b->last_kind = nshared > 0 ? 5 : 2; b->last_nrow = 0; *done = true; return EPI_OK; }
-  EPI_TRY(b->tile_nrow.ensure((size_t)nt * 4));
-  EPI_TRY(b->tile_base.ensure((size_t)nt * 4));
-  EPI_TRY(b->tile_out.ensure((size_t)(nt + 1) * 4));
-  EPI_TRY(b->heavy_list.ensure((size_t)nt * 4));          // the deep list
-  if (!b->mhlf_slot) b->mhlf_slot = T / 8;
-  uint32_t slot = b->mhlf_slot > 2u * T ? 2u * T : b->mhlf_slot;
-  if (options().mhl_slot >= 0 && options().mhl_slot <= 2 * T) slot = (uint32_t)options().mhl_slot;   // test hook (EPIHIP_MHL_SLOT)
-  while (slot && (unsigned long long)nt * slot > 0xC0000000ull) slot >>= 1;
-  const size_t headroom = nshared > 0 ? (size_t)nshared * 2 * T : 0;   // shared tiles are emitted later into the same pool
-  size_t ovf_base = (size_t)nt * slot;
-  for (;;) {
-    const size_t ovf = (ovf_base >> 4) > 65536 ? (ovf_base >> 4) : 65536;
-    if (mhl_pool_rows(b) >= ovf_base + ovf + headroom) break;
-    const int rc = ensure_mhl_pool(b, ovf_base + ovf + headroom);
-    if (rc == EPI_OK) break;
-    b->pool_cap = 0; b->pool_cap2 = 0;
-    if (!slot) return rc;
-    slot = 0;
-    ovf_base = 0;
-  }
-  MhlFArgs a{};
-  memset(&a, 0, sizeof(a));
+  return EPI_OK;
+}
+
+// Everything else the kernels of this report read, but the pool (mhl_bind_pool, per attempt)
+static int mhlf_fill_args(epi_batch *b, uint32_t ctx_mask, uint32_t H, int hmin, hipStream_t s, MhlFArgs &a) {
+  const uint32_t k = mhl_single_context(ctx_mask);
   a.xm = b->xm; a.off = b->off; a.len = b->len; a.start = b->start; a.strand = b->strand;
   a.xm_cap = (b->nbytes + 15) / 16 * 16;
   a.k7 = k * 0x01010101u;
   a.lut2 = make_mhlf_lut2(ctx_mask);
   a.hmin = (int32_t)hmin; a.H = H; a.ctx = k;
-  {                                                        // decision table over 0 .. longest row; kept while max_oo does not change
-    const bool same = b->mhl_keep_len == st.max_len && memcmp(&b->mhl_keep_oo, &max_oo, sizeof(double)) == 0;
-    if (!same) {
-      EPI_TRY(b->mhl_keep_tab.ensure((size_t)(st.max_len + 1) * 4));
-      hipLaunchKernelGGL(k_mhl_keep_table, dim3((unsigned)(st.max_len / 256 + 1)), dim3(256), 0, s, max_oo, st.max_len, b->mhl_keep_tab.as<uint32_t>());
-      EPI_HIP(hipGetLastError());
-      b->mhl_keep_len = st.max_len;
-      b->mhl_keep_oo = max_oo;
-    }
-    a.keep_tab = b->mhl_keep_tab.as<uint32_t>();
-  }
-  Scalars *sc = report_scalars(b);
-  a.deep_count = &sc->heavy_count;                         // (this kernel's deep tiles share the heavy tiles' counter)
+  a.deep_count = &report_scalars(b)->heavy_count;          // (this kernel's deep tiles share the heavy tiles' counter)
   a.deep_list = b->heavy_list.as<uint32_t>();
-  // The fast variant comes with and without the LDS array of folded call counters.  Without it a workgroup needs 4 KB less
-  // LDS (five per CU instead of four) and a tile of more than 255 rows folds its u8 counters into a slot of a slab in HBM
-  // (MHLF_FOLD_SLOTS of them; a tile that finds none left goes to the WIDE variant with the other deep tiles).  Batches whose
-  // tiles average well below 255 rows start there; one that runs out of slots switches the batch over.
-  const bool fold = options().mhlf_fold >= 0 ? options().mhlf_fold != 0 : (b->mhlf_prefer_fold || (double)b->n > 150.0 * (double)nt);
-  const uint32_t fold_slots = options().mhlf_fold_slots >= 0 && (uint32_t)options().mhlf_fold_slots < MHLF_FOLD_SLOTS
-                                  ? (uint32_t)options().mhlf_fold_slots : MHLF_FOLD_SLOTS;   // (test hook: fewer)
   a.max_rows = MHLF_FAST_ROWS;
-  a.fold_slab = nullptr; a.fold_cursor = &sc->fold_cursor; a.fold_slots = 0;
-  if (!fold) {
-    EPI_TRY(b->mhlf_fold_slab.ensure((size_t)MHLF_FOLD_SLOTS * 2 * T * 4));
-    a.fold_slab = b->mhlf_fold_slab.as<uint32_t>();
-    a.fold_slots = fold_slots;
-  }
   if (options().heavy_rows > 0 && options().heavy_rows < a.max_rows) a.max_rows = options().heavy_rows;   // test hook (EPIHIP_HEAVY_ROWS)
-  a.slot_rows = slot;
-  a.ovf_base = (uint32_t)ovf_base;
-  b->mhl_last_slot = slot;
-  b->mhl_last_ovf = (uint32_t)ovf_base;
-  b->mhl_ctx_mask = ctx_mask;
-  EPI_TRY(check_grid(((int64_t)nt + 7) / 8 * 8, MHLF_WG, "lMHL tile kernel"));
+  a.slab_cnt = b->d_mhl_cnt_slab;
+  a.slab_sum = reinterpret_cast<unsigned long long *>(b->d_mhl_sum_slab);
   a.nrows = b->n;
 #ifdef EPI_CHECK
-  EPI_TRY(b->diag.ensure(256));
-  a.dbg = b->diag.as<uint32_t>();
-  EPI_HIP(hipMemsetAsync(a.dbg, 0, 32, s));
+  EPI_TRY(mhl_check_begin(b, s, &a.dbg));
 #endif
-  Scalars host;
-  for (int attempt = 0; attempt < 2; attempt++) {
-    fill_args_common(b, a);
-    if (attempt > 0) {
-      EPI_HIP(hipMemsetAsync(&sc->cursor, 0, offsetof(Scalars, unused6) - offsetof(Scalars, cursor), s));   // cursor .. fold_cursor
-      if (nshared > 0) {                                   // the rerun adds into the slabs again
-        EPI_HIP(hipMemsetAsync(a.slab_cnt, 0, (size_t)nshared * MHLF_CNT_PLANES * T * 4, s));
-        EPI_HIP(hipMemsetAsync(a.slab_sum, 0, (size_t)nshared * MHLF_SUM_PLANES * T * 8, s));
-      }
+  return EPI_OK;
+}
+
+// What a finished attempt teaches the batch for its next report
+static void mhlf_learn(epi_batch *b, const MhlfPlan &p, uint32_t H, uint32_t ndeep, uint32_t fold_asked) {
+  if (ndeep > 0) {
+    b->mhlf_prefer_wide = ndeep > (uint32_t)p.nt / 2;      // most tiles needed the wide sums: start there next time
+    b->mhlf_prefer_wide_H = H;
+  }
+  // (rows per tile are a property of the immutable batch, not of the report's parameters: this one may stay)
+  if (!p.fold && fold_asked > p.fold_slots / 2) b->mhlf_prefer_fold = true;   // many tiles over 255 rows: LDS fold array next time
+}
+
+// One attempt at all tiles: the fast variant (or the WIDE one where the batch has learned to start there), the tiles' row
+// offsets, and the WIDE variant again for exactly the tiles the fast one set aside (too many rows, sums that could wrap
+// u32).  For the first attempt of a call the tile-index pass has zeroed the counters.
+static int mhlf_attempt(epi_batch *b, const MhlfPlan &p, MhlFArgs &a, uint32_t H, hipStream_t s, int attempt, Scalars *host) {
+  Scalars *sc = report_scalars(b);
+  const int32_t nt = p.nt;
+  mhl_bind_pool(b, a);
+  if (attempt > 0) {
+    EPI_HIP(hipMemsetAsync(&sc->cursor, 0, offsetof(Scalars, unused6) - offsetof(Scalars, cursor), s));   // cursor .. fold_cursor
+    if (p.nshared > 0) {                                   // the rerun adds into the slabs again
+      EPI_HIP(hipMemsetAsync(a.slab_cnt, 0, (size_t)p.nshared * MHLF_CNT_PLANES * MHLF_T * 4, s));
+      EPI_HIP(hipMemsetAsync(a.slab_sum, 0, (size_t)p.nshared * MHLF_SUM_PLANES * MHLF_T * 8, s));
     }
-    a.tile_list = nullptr;
-    const unsigned grid = (unsigned)(((nt + 7) / 8) * 8);
-    prof_begin("mhl_tiles", s);
-    // (the preference was learned for one H: S(min(h, H)) shrinks with H, so a report with a smaller H starts on the fast
-    //  variant again, which lists the tiles that still need the wide sums)
-    const bool wide_first = b->mhlf_prefer_wide && H >= b->mhlf_prefer_wide_H;
-    if (wide_first) launch_mhl_fused<true>(gc_wide, grid, nt, s, a); else launch_mhl_fused<false>(gc, grid, nt, s, a, fold);
-    prof_end("mhl_tiles", s);
+  }
+  a.tile_list = nullptr;
+  prof_begin("mhl_tiles", s);
+  // (the preference was learned for one H: S(min(h, H)) shrinks with H, so a report with a smaller H starts on the fast
+  //  variant again, which lists the tiles that still need the wide sums)
+  const unsigned grid = (unsigned)(((nt + 7) / 8) * 8);
+  if (b->mhlf_prefer_wide && H >= b->mhlf_prefer_wide_H) launch_mhl_fused<true>(p.shape_wide, grid, nt, s, a);
+  else launch_mhl_fused<false>(p.shape, grid, nt, s, a, p.fold);
+  prof_end("mhl_tiles", s);
+  EPI_HIP(hipGetLastError());
+  EPI_TRY(scan_exclusive_u32(a.tile_nrow, b->tile_out.as<uint32_t>(), nt, &sc->rows, b->scan_tmp, s));
+  EPI_TRY(read_report_scalars(b, s, host));
+  if (p.nt_hinted && host->ntiles != (uint32_t)nt) {
+    for (int i = 0; i < 4; i++) b->tile_hint_T[i] = 0;
+    return fail(EPI_ERR_STATE, "the rows of this batch changed since an earlier report (tile count %u, was %d)", host->ntiles, nt);
+  }
+  const uint32_t ndeep = host->heavy_count, fold_asked = host->fold_cursor;
+  if (ndeep > 0) {
+    a.tile_list = a.deep_list;
+    prof_begin("mhl_deep", s);
+    launch_mhl_fused<true>(p.shape_wide, ndeep, (int)ndeep, s, a);
+    prof_end("mhl_deep", s);
     EPI_HIP(hipGetLastError());
     EPI_TRY(scan_exclusive_u32(a.tile_nrow, b->tile_out.as<uint32_t>(), nt, &sc->rows, b->scan_tmp, s));
-    EPI_TRY(read_report_scalars(b, s, &host));
-    if (nt_hinted && host.ntiles != (uint32_t)nt) {
-      for (int i = 0; i < 4; i++) b->tile_hint_T[i] = 0;
-      return fail(EPI_ERR_STATE, "the rows of this batch changed since an earlier report (tile count %u, was %d)", host.ntiles, nt);
-    }
-    const uint32_t ndeep = host.heavy_count, fold_asked = host.fold_cursor;
-    if (ndeep > 0) {
-      // tiles the fast variant set aside (too many rows, sums that could wrap u32): the WIDE variant redoes exactly those
-      a.tile_list = a.deep_list;
-      prof_begin("mhl_deep", s);
-      launch_mhl_fused<true>(gc_wide, ndeep, (int)ndeep, s, a);
-      prof_end("mhl_deep", s);
-      EPI_HIP(hipGetLastError());
-      EPI_TRY(scan_exclusive_u32(a.tile_nrow, b->tile_out.as<uint32_t>(), nt, &sc->rows, b->scan_tmp, s));
-      EPI_TRY(read_report_scalars(b, s, &host));
-      b->mhlf_prefer_wide = ndeep > (uint32_t)nt / 2;   // most tiles needed the wide sums: start there next time
-      b->mhlf_prefer_wide_H = H;
-    }
-    if (!fold && fold_asked > fold_slots / 2) b->mhlf_prefer_fold = true;   // many tiles over 255 rows: LDS fold array next time
-    // (rows per tile are a property of the immutable batch, not of the report's parameters: this one may stay)
-#ifdef EPI_CHECK
-    {
-      uint32_t d[8];
-      EPI_HIP(hipMemcpy(d, a.dbg, 32, hipMemcpyDeviceToHost));
-      if (d[0]) return fail(EPI_ERR_STATE, "fused lMHL index check %u failed: v0=%d v1=%d block=%u thread=%u (n=%lld nt=%d)", d[0],
-                            (int)d[1], (int)d[2], d[3], d[4], (long long)b->n, nt);
-    }
-#endif
-    if (ovf_base + host.cursor + headroom <= a.pool_cap) break;
-    if (attempt == 1) return fail(EPI_ERR_STATE, "row pool overflow after regrow");
-    EPI_TRY(ensure_mhl_pool(b, ovf_base + host.cursor + (host.cursor >> 4) + 1024 + headroom));
+    EPI_TRY(read_report_scalars(b, s, host));
   }
-  if (host.cursor > host.rows / 8 && b->mhlf_slot < 2u * T) b->mhlf_slot *= 2;
+  mhlf_learn(b, p, H, ndeep, fold_asked);
+#ifdef EPI_CHECK
+  EPI_TRY(mhl_check_end(b, a.dbg, "fused lMHL", nt, attempt));
+#endif
+  return EPI_OK;
+}
+
+// The fused path.  *done = false: the batch is not eligible -- the caller runs the two-kernel path instead.  With shared
+// tiles attached (epi_batch_mhl_set_shared with the fused layout) the report stops after the accumulation
+// (KIND_MHLF_SHARED): the caller all-reduces the slabs and continues with mhl_fused_finish_shared.
+int mhl_fused_report(epi_batch *b, uint32_t ctx_mask, uint32_t H, int hmin, double max_oo, hipStream_t s,
+                     int64_t *nrow_out, bool *done) {
+  *done = false;
+  MhlfPlan p = {};
+  p.nshared = (int32_t)b->shared_keys.size();
+  if (p.nshared > 0 && !b->mhl_shared_fused) return EPI_OK;  // the slabs attached are the two-kernel path's
+  RowStats st;
+  EPI_TRY(build_tiles(b, s, MHLF_T, &st, &p.nt, &p.nt_hinted));   // (a remembered tile count is verified at the attempt's synchronisation)
+  if (!mhl_fused_eligible(ctx_mask, st)) {
+    if (p.nshared > 0) return fail(EPI_ERR_STATE, "shared tiles were attached for the one-pass lMHL kernel, but this batch needs the two-kernel path");
+    return EPI_OK;
+  }
+  p.shape_wide = pick_mhlf_shape(st.max_len);
+  p.shape = pick_mhlf_shape_hist(st, b->n, p.nt, MHLF_T);
+  b->last_ntiles = p.nt;
+  if (p.nt == 0) { b->last_kind = p.nshared > 0 ? KIND_MHLF_SHARED : KIND_MHL; b->last_nrow = 0; *done = true; return EPI_OK; }
+  EPI_TRY(b->tile_nrow.ensure((size_t)p.nt * 4));
+  EPI_TRY(b->tile_base.ensure((size_t)p.nt * 4));
+  EPI_TRY(b->tile_out.ensure((size_t)(p.nt + 1) * 4));
+  EPI_TRY(b->heavy_list.ensure((size_t)p.nt * 4));        // the deep list
+  p.headroom = p.nshared > 0 ? (size_t)p.nshared * 2 * MHLF_T : 0;
+  EPI_TRY(mhl_layout_pool(b, b->mhlf_slot, MHLF_T, p.nt, p.headroom, &p.pool));   // (a slot size of its own: these tiles have MHLF_T positions)
+  b->mhl_ctx_mask = ctx_mask;
+  MhlFArgs a{};
+  EPI_TRY(mhlf_keep_table(b, st.max_len, max_oo, s, a));
+  EPI_TRY(mhlf_pick_fold(b, p, a));
+  EPI_TRY(check_grid(((int64_t)p.nt + 7) / 8 * 8, MHLF_WG, "lMHL tile kernel"));
+  EPI_TRY(mhlf_fill_args(b, ctx_mask, H, hmin, s, a));
+
+  // At most two attempts, the second with a pool regrown to the size the first one asked for.
+  Scalars host;
+  for (int attempt = 0;; attempt++) {
+    EPI_TRY(mhlf_attempt(b, p, a, H, s, attempt, &host));
+    if (p.pool.ovf_base + host.cursor + p.headroom <= a.pool_cap) break;
+    if (attempt == 1) return fail(EPI_ERR_STATE, "row pool overflow after regrow");
+    EPI_TRY(ensure_mhl_pool(b, p.pool.ovf_base + host.cursor + (host.cursor >> 4) + 1024 + p.headroom));
+  }
+  if (host.cursor > host.rows / 8 && b->mhlf_slot < 2u * MHLF_T) b->mhlf_slot *= 2;   // too many tiles outgrew their slot
   *done = true;
-  if (nshared > 0) { b->last_kind = 5; return EPI_OK; }    // caller continues with epi_batch_mhl_finish_shared
-  b->last_kind = 2;
+  if (p.nshared > 0) { b->last_kind = KIND_MHLF_SHARED; return EPI_OK; }    // caller continues with epi_batch_mhl_finish_shared
+  b->last_kind = KIND_MHL;
   b->last_nrow = host.rows;
   *nrow_out = host.rows;
   return EPI_OK;
@@ -1138,28 +1134,24 @@ int mhl_fused_report(epi_batch *b, uint32_t ctx_mask, uint32_t H, int hmin, doub
 
 // Second half of a sharded lMHL report on the fused path: the slabs have been sum-reduced across ranks.
 int mhl_fused_finish_shared(epi_batch *b, hipStream_t s, int64_t *nrow_out) {
-  const int32_t nt = b->last_ntiles;
-  Scalars *sc = report_scalars(b);
-  Scalars host;
-  if (nt > 0 && !b->shared_keys.empty()) {
+  if (b->last_ntiles > 0 && !b->shared_keys.empty()) {
     MhlFArgs a{};
-    memset(&a, 0, sizeof(a));
-    fill_args_common(b, a);
-    for (uint32_t c : {2u, 6u, 7u}) if (b->mhl_ctx_mask == ((1u << c) | (1u << (c + 8)))) a.ctx = c;
-    a.slot_rows = b->mhl_last_slot;
-    a.ovf_base = b->mhl_last_ovf;
+    mhl_bind_pool(b, a);
+    a.ctx = mhl_single_context(b->mhl_ctx_mask);
+    a.slab_cnt = b->d_mhl_cnt_slab;
+    a.slab_sum = reinterpret_cast<unsigned long long *>(b->d_mhl_sum_slab);
     hipLaunchKernelGGL(k_mhlf_emit_slab, dim3((unsigned)b->shared_keys.size()), dim3(MHLF_WG), 0, s, a, b->d_shared_owned.as<int32_t>(),
                        b->d_slot_tile.as<int32_t>());
     EPI_HIP(hipGetLastError());
-    EPI_TRY(scan_exclusive_u32(a.tile_nrow, b->tile_out.as<uint32_t>(), nt, &sc->rows, b->scan_tmp, s));
-    EPI_TRY(read_report_scalars(b, s, &host));
-    if ((size_t)a.ovf_base + host.cursor > a.pool_cap) return fail(EPI_ERR_STATE, "row pool overflow in sharded lMHL report");
-    b->last_nrow = host.rows;
-  } else {
-    b->last_nrow = 0;
-    if (nt > 0) { EPI_TRY(read_report_scalars(b, s, &host)); b->last_nrow = host.rows; }
+    return mhl_finish_rows(b, s, nrow_out);
   }
-  b->last_kind = 2;
+  b->last_nrow = 0;
+  if (b->last_ntiles > 0) {                                // (no shared tile after all: the first half's rows are the table)
+    Scalars host;
+    EPI_TRY(read_report_scalars(b, s, &host));
+    b->last_nrow = host.rows;
+  }
+  b->last_kind = KIND_MHL;
   *nrow_out = b->last_nrow;
   return EPI_OK;
 }

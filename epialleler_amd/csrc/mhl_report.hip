@@ -941,12 +941,6 @@ static int pick_mhl_tile_group(int32_t max_len) {
 // EPIHIP_MHL_MULTI is set): k_mhl_rows_multi.  Returned as G*8 + C.
 int pick_mhl_group(int32_t max_len) {
   if (options().mhl_multi) return 0;
-  if (options().mhl_group_g > 0) {                                         // EPIHIP_MHL_GROUP="G,C" for A/B runs; must cover the reads
-    const int g = options().mhl_group_g, c = options().mhl_group_c;
-    if ((g == 2 || g == 4 || g == 8 || g == 16 || g == 32 || g == 64) && c >= 2 && c <= 4 &&
-        (int64_t)g * 16 * c >= (int64_t)max_len + 15)
-      return g * 8 + c;
-  }
   int best = 0;
   int64_t best_cap = 0;
   for (int g = 2; g <= 64; g <<= 1)
@@ -975,6 +969,247 @@ MhlLut make_mhl_lut(uint32_t ctx_mask) {
   return l;
 }
 
+// ---- the two-kernel report on the host ----------------------------------------------------------------------------------
+
+// What one report call has decided before it queues a kernel.
+struct MhlPlan {
+  int32_t nt;                             // tiles
+  int32_t nshared;                        // tiles shared with other ranks ...
+  size_t headroom;                        // ... and the pool rows kept free for them (they are emitted later into the same pool)
+  PoolLayout pool;                        // slot rows per tile, first row of the overflow region
+  int gc;                                 // pass 1: lanes per read * 8 + chunks per lane ...
+  bool multi;                             // ... or, gc == 0, a wavefront per read (k_mhl_rows_multi)
+  size_t nblkrec;                         // ... and its per-block record table
+  int tg;                                 // pass 2: lanes per row
+  int heavy_rows;                         // candidate rows above which a tile is set aside, before the sum width lowers it
+  bool narrow;                            // u32 LDS sums (decided from pass 1's largest haplotype)
+};
+
+// Pass 1 workspace: per-read info, record table, records (grown on demand like the row pool), allocation cursors
+static int mhl_pass1_workspace(epi_batch *b, const MhlPlan &p) {
+  EPI_TRY(b->mhl_h.ensure((size_t)b->n * 16));
+  EPI_TRY(b->mhl_blk.ensure(p.nblkrec * 8));
+  if (p.multi) EPI_TRY(b->mhl_cont.ensure(p.nblkrec * 4));
+  if (b->mhl_rec_cap == 0) {
+    b->mhl_rec_cap = (size_t)b->nbytes / 48 + (size_t)b->n + 64 * MHL_REGIONS;
+    EPI_TRY(b->mhl_m.ensure(b->mhl_rec_cap * sizeof(MhlRec)));
+  }
+  return b->mhl_cur.ensure((size_t)MHL_REGIONS * MHL_CUR_STRIDE * 8);
+}
+
+// Row pool (layout_pool, tiles.hip) of either path, for its tiles of T positions and from its own remembered slot size:
+// CpG haplotypes give ~7 % of the (pos,strand) cells of a tile a row
+int mhl_layout_pool(epi_batch *b, uint32_t &slot_state, int T, int32_t nt, size_t headroom, PoolLayout *l) {
+  if (!slot_state) slot_state = (uint32_t)T / 8;
+  EPI_TRY(layout_pool(b, slot_state, T, nt, headroom, options().mhl_slot, ensure_mhl_pool, l));   // test hook (EPIHIP_MHL_SLOT)
+  b->mhl_last_slot = l->slot;
+  b->mhl_last_ovf = (uint32_t)l->ovf_base;
+  return EPI_OK;
+}
+
+// Everything the kernels of both passes read, but the records (mhl_pass1: they may be regrown), the pool (mhl_bind_pool, per
+// attempt) and the heavy-tile limits (mhl_pick_sums)
+static int mhl_fill_args(epi_batch *b, MhlPlan &p, uint32_t ctx_mask, uint32_t H, int hmin, double max_oo, hipStream_t s, RowsArgs &ra,
+                         MhlArgs &a) {
+  Scalars *sc = report_scalars(b);
+  ra.xm = b->xm; ra.off = b->off; ra.len = b->len; ra.n = b->n;
+  ra.lut = make_mhl_lut(ctx_mask);
+  ra.hmin = (int32_t)hmin; ra.max_oo = max_oo;
+  ra.rowinfo = b->mhl_h.as<int4>();
+  ra.blkrec = b->mhl_blk.as<uint2>();
+  ra.rec_cursor = b->mhl_cur.as<unsigned long long>();
+  ra.cont = p.multi ? b->mhl_cont.as<uint32_t>() : nullptr;
+  ra.max_h = &sc->max_h;
+
+  a.c.xm = b->xm; a.c.off = b->off; a.c.len = b->len; a.c.start = b->start; a.c.strand = b->strand; a.c.pass = nullptr;
+  a.rowinfo = b->mhl_h.as<int4>();
+  a.blkrec = b->mhl_blk.as<uint2>();
+  a.multi = p.multi ? 1 : 0;
+#ifdef EPI_MHL_CHECK
+  EPI_TRY(mhl_check_begin(b, s, &a.dbg));
+  a.n = b->n; a.nbytes = b->nbytes; a.nblkrec = (int64_t)p.nblkrec;
+#endif
+  a.ctx_mask = ctx_mask; a.H = H;
+  p.heavy_rows = 16384;
+  if (options().heavy_rows > 0) p.heavy_rows = options().heavy_rows;   // test hook (EPIHIP_HEAVY_ROWS)
+  if (p.heavy_rows > 32767) p.heavy_rows = 32767;          // k_mhl_tiles' packed u16 counters: a base adds at most 2 (the
+                                                           // CX kernels cap at 16384, cx_report.hip)
+  EPI_TRY(b->heavy_list.ensure((size_t)p.nt * 4));
+  a.heavy_list = b->heavy_list.as<uint32_t>();
+  a.heavy_count = &sc->heavy_count;
+  a.heavy_max = &sc->heavy_max;
+  a.shared_cnt = reinterpret_cast<uint32_t *>(b->d_mhl_cnt_slab);
+  a.shared_sums = reinterpret_cast<unsigned long long *>(b->d_mhl_sum_slab);
+  return EPI_OK;
+}
+
+// Pass 1: per-read haplotype size and stretch records; *host: the fullest record region, the largest haplotype size.
+// *rec_used: records the fullest region asked for -- more than a region holds: mhl_regrow_records, then pass 1 again.
+static int mhl_pass1(epi_batch *b, const MhlPlan &p, RowsArgs &ra, hipStream_t s, Scalars *host, unsigned long long *rec_used) {
+  Scalars *sc = report_scalars(b);
+  ra.recs = b->mhl_m.as<MhlRec>();
+  ra.rec_cap = (uint32_t)b->mhl_rec_cap;
+  EPI_HIP(hipMemsetAsync(ra.rec_cursor, 0, (size_t)MHL_REGIONS * MHL_CUR_STRIDE * 8, s));
+  EPI_HIP(hipMemsetAsync(ra.max_h, 0, 4, s));
+  prof_begin("mhl_rows", s);
+  if (p.multi) {
+    hipLaunchKernelGGL(k_mhl_rows_multi, dim3((unsigned)((b->n + 3) / 4)), dim3(256), 0, s, ra);
+  } else {
+    const int g = p.gc >> 3;
+    const unsigned nb = (unsigned)((b->n * g + 255) / 256);
+#define EPI_LAUNCH(GG)                                                                                       \
+  case GG * 8 + 2: hipLaunchKernelGGL((k_mhl_rows<GG, 2>), dim3(nb), dim3(256), 0, s, ra); break;            \
+  case GG * 8 + 3: hipLaunchKernelGGL((k_mhl_rows<GG, 3>), dim3(nb), dim3(256), 0, s, ra); break;            \
+  case GG * 8 + 4: hipLaunchKernelGGL((k_mhl_rows<GG, 4>), dim3(nb), dim3(256), 0, s, ra); break;
+    switch (p.gc) {
+      EPI_LAUNCH(2) EPI_LAUNCH(4) EPI_LAUNCH(8) EPI_LAUNCH(16) EPI_LAUNCH(32) EPI_LAUNCH(64)
+      default: return fail(EPI_ERR_ARG, "bad group size");
+    }
+#undef EPI_LAUNCH
+  }
+  prof_end("mhl_rows", s);
+  hipLaunchKernelGGL(k_mhl_cursor_max, dim3(1), dim3(MHL_REGIONS), 0, s, ra.rec_cursor, reinterpret_cast<unsigned long long *>(sc->rec_max));
+  EPI_HIP(hipGetLastError());
+  EPI_TRY(read_report_scalars(b, s, host));
+  *rec_used = ((unsigned long long)host->rec_max[1] << 32) | host->rec_max[0];
+  return EPI_OK;
+}
+
+// Record space ran out: the need is known now
+static int mhl_regrow_records(epi_batch *b, unsigned long long rec_used) {
+  const unsigned long long want = (rec_used + rec_used / 16 + 64) * MHL_REGIONS;
+  if (want > 0xFFFFFFF0ull) return fail(EPI_ERR_NOMEM, "too many methylated stretches in one batch (%llu)", want);
+  b->mhl_rec_cap = (size_t)want;
+  return b->mhl_m.ensure(b->mhl_rec_cap * sizeof(MhlRec));
+}
+
+// u32 LDS sums if no position of a tile (or heavy-tile chunk) can reach 2^31: rows x (the largest value a read can add:
+// S(h) >= h, S(M) <= S(h) for M <= h; + 1 for a stray nibble at the position); tiles are then set aside earlier
+static void mhl_pick_sums(MhlPlan &p, uint32_t max_h, uint32_t H, MhlArgs &a) {
+  uint32_t hcap = max_h > 65535u ? 65535u : max_h;
+  if (hcap >= H) hcap = H;
+  const unsigned long long vmax = nrS(hcap) > 1 ? nrS(hcap) : 1;
+  const unsigned long long narrow_rows = ((1ull << 31) - 1) / (vmax + 1);
+  p.narrow = narrow_rows >= 512;
+  if (options().mhl_sums) p.narrow = p.narrow && options().mhl_sums == 32;   // EPIHIP_MHL_SUMS=64 forces the wide kernel
+  a.heavy_rows = p.heavy_rows;
+  if (p.narrow && (unsigned long long)a.heavy_rows > narrow_rows) a.heavy_rows = (int)narrow_rows;
+  a.heavy_chunk = a.heavy_rows / 4 > 64 ? a.heavy_rows / 4 : 64;
+}
+
+// One attempt at pass 2: all tiles, their row offsets, and the pile-ups the tile kernel set aside (split, reduced in HBM,
+// emitted, rescanned).  For the first attempt of a call the tile-index pass has zeroed the counters.
+static int mhl_pass2(epi_batch *b, const MhlPlan &p, MhlArgs &a, hipStream_t s, int attempt, Scalars *host) {
+  Scalars *sc = report_scalars(b);
+  const int32_t nt = p.nt;
+  mhl_bind_pool(b, a);
+  if (attempt > 0) {
+    EPI_HIP(hipMemsetAsync(&sc->cursor, 0, offsetof(Scalars, deep_count) - offsetof(Scalars, cursor), s));   // cursor, rows, heavy count
+    EPI_HIP(hipMemsetAsync(a.heavy_max, 0, 4, s));
+  }
+  prof_begin("mhl_tiles", s);
+  if (p.narrow) launch_mhl_tiles<uint32_t>(p.tg, nt, s, a); else launch_mhl_tiles<unsigned long long>(p.tg, nt, s, a);
+  prof_end("mhl_tiles", s);
+  EPI_HIP(hipGetLastError());
+  EPI_TRY(scan_exclusive_u32(a.tile_nrow, b->tile_out.as<uint32_t>(), nt, &sc->rows, b->scan_tmp, s));
+#ifdef EPI_MHL_CHECK
+  EPI_TRY(mhl_check_end(b, a.dbg, "lMHL", nt, attempt));
+#endif
+  EPI_TRY(read_report_scalars(b, s, host));
+  if (host->heavy_count > 0) {
+    const uint32_t nheavy = host->heavy_count, nchunks = (host->heavy_max + (uint32_t)a.heavy_chunk - 1) / (uint32_t)a.heavy_chunk;
+    EPI_TRY(b->heavy_slab.ensure((size_t)nheavy * 16 * MHL_T * 4));
+    EPI_TRY(b->heavy_sums.ensure((size_t)nheavy * MHL_NSUM * 8));
+    a.heavy_cnt = b->heavy_slab.as<uint32_t>();
+    a.heavy_sums = b->heavy_sums.as<unsigned long long>();
+    EPI_HIP(hipMemsetAsync(a.heavy_cnt, 0, (size_t)nheavy * 16 * MHL_T * 4, s));
+    EPI_HIP(hipMemsetAsync(a.heavy_sums, 0, (size_t)nheavy * MHL_NSUM * 8, s));
+    prof_begin("mhl_heavy", s);
+    if (p.narrow) launch_mhl_heavy<uint32_t>(p.tg, nheavy, nchunks, s, a); else launch_mhl_heavy<unsigned long long>(p.tg, nheavy, nchunks, s, a);
+    prof_end("mhl_heavy", s);
+    EPI_HIP(hipGetLastError());
+    EPI_TRY(scan_exclusive_u32(a.tile_nrow, b->tile_out.as<uint32_t>(), nt, &sc->rows, b->scan_tmp, s));
+    EPI_TRY(read_report_scalars(b, s, host));
+  }
+  return EPI_OK;
+}
+
+// The overflow region was too small for the `used` rows that went through the cursor: the exact need is known now
+static int mhl_regrow_pool(epi_batch *b, const MhlPlan &p, const MhlArgs &a, uint32_t used, hipStream_t s) {
+  EPI_TRY(ensure_mhl_pool(b, p.pool.ovf_base + used + (used >> 4) + 1024 + p.headroom));
+  if (p.nshared > 0) {   // the rerun adds into the shared slabs again
+    EPI_HIP(hipMemsetAsync(a.shared_cnt, 0, (size_t)p.nshared * 16 * MHL_T * 4, s));
+    EPI_HIP(hipMemsetAsync(a.shared_sums, 0, (size_t)p.nshared * MHL_NSUM * 8, s));
+  }
+  return EPI_OK;
+}
+
+// The two-kernel path on a resident batch.  At most three attempts: one that finds the record space of pass 1 too small,
+// one that finds the row pool too small, and the one that fits (an attempt starts over at pass 1 in either case).
+static int mhl_report_impl(epi_batch *b, uint32_t ctx_mask, uint32_t H, int hmin, double max_oo, hipStream_t s, int64_t *nrow_out) {
+  RowStats st;
+  MhlPlan p = {};
+  EPI_TRY(build_tiles(b, s, kMhlTile, &st, &p.nt));
+  b->last_ntiles = p.nt;
+  if (p.nt == 0) {                                         // (a rank of a sharded run without rows still takes part in the exchange)
+    b->last_kind = !b->shared_keys.empty() && b->d_mhl_cnt_slab ? KIND_MHL_SHARED : KIND_MHL; b->last_nrow = 0;
+    return EPI_OK;
+  }
+  p.gc = pick_mhl_group(st.max_len);
+  p.multi = p.gc == 0;
+  p.nblkrec = p.multi ? (size_t)(b->nbytes >> MHL_BLK_SHIFT) + 2 * (size_t)b->n + 2 : 1;
+  p.tg = pick_mhl_tile_group(st.max_len);
+  EPI_TRY(mhl_pass1_workspace(b, p));
+  EPI_TRY(b->tile_nrow.ensure((size_t)p.nt * 4));
+  EPI_TRY(b->tile_base.ensure((size_t)p.nt * 4));
+  EPI_TRY(b->tile_out.ensure((size_t)(p.nt + 1) * 4));
+  RowsArgs ra{};
+  MhlArgs a{};
+  EPI_TRY(mhl_fill_args(b, p, ctx_mask, H, hmin, max_oo, s, ra, a));
+  p.nshared = (int32_t)b->shared_keys.size();
+  if (p.nshared > 0 && (!a.shared_cnt || !a.shared_sums)) return fail(EPI_ERR_STATE, "shared tiles set without lMHL slabs (use epi_batch_mhl_set_shared)");
+  p.headroom = p.nshared > 0 ? (size_t)p.nshared * 2 * MHL_T : 0;
+  EPI_TRY(mhl_layout_pool(b, b->mhl_slot, MHL_T, p.nt, p.headroom, &p.pool));
+  b->mhl_ctx_mask = ctx_mask;
+
+  Scalars host;
+  for (int attempt = 0;; attempt++) {
+    unsigned long long rec_used = 0;
+    EPI_TRY(mhl_pass1(b, p, ra, s, &host, &rec_used));
+    if (rec_used > b->mhl_rec_cap / MHL_REGIONS) {
+      if (attempt == 2) return fail(EPI_ERR_STATE, "stretch record overflow after regrow");
+      EPI_TRY(mhl_regrow_records(b, rec_used));
+      continue;
+    }
+    mhl_pick_sums(p, host.max_h, H, a);
+    a.recs = ra.recs;
+    a.rec_cap = ra.rec_cap;
+    EPI_TRY(mhl_pass2(b, p, a, s, attempt, &host));
+    if (p.pool.ovf_base + host.cursor + p.headroom <= a.pool_cap) break;
+    if (attempt == 2) return fail(EPI_ERR_STATE, "row pool overflow after regrow");
+    EPI_TRY(mhl_regrow_pool(b, p, a, host.cursor, s));
+  }
+  if (host.cursor > host.rows / 8 && b->mhl_slot < 2u * MHL_T) b->mhl_slot *= 2;   // too many tiles outgrew their slot
+  if (p.nshared > 0) { b->last_kind = KIND_MHL_SHARED; return EPI_OK; }     // caller continues with epi_batch_mhl_finish_shared
+  b->last_kind = KIND_MHL;
+  b->last_nrow = host.rows;
+  *nrow_out = host.rows;
+  return EPI_OK;
+}
+
+int mhl_finish_rows(epi_batch *b, hipStream_t s, int64_t *nrow_out) {
+  Scalars *sc = report_scalars(b);
+  EPI_TRY(scan_exclusive_u32(b->tile_nrow.as<uint32_t>(), b->tile_out.as<uint32_t>(), b->last_ntiles, &sc->rows, b->scan_tmp, s));
+  Scalars host;
+  EPI_TRY(read_report_scalars(b, s, &host));
+  // cannot overflow: the first half kept 2 T rows per shared tile free
+  if ((size_t)b->mhl_last_ovf + host.cursor > mhl_pool_cap(b)) return fail(EPI_ERR_STATE, "row pool overflow in sharded lMHL report");
+  b->last_kind = KIND_MHL;
+  b->last_nrow = host.rows;
+  *nrow_out = host.rows;
+  return EPI_OK;
+}
+
 }  // namespace epi
 
 using namespace epi;
@@ -985,221 +1220,15 @@ int epi_batch_mhl_report_dev(epi_batch *b, const char *ctx, int hmax, int hmin, 
                              void *stream, int64_t *nrow_out) {
   if (!b || !ctx || !nrow_out) return fail(EPI_ERR_ARG, "epi_batch_mhl_report_dev: NULL argument");
   *nrow_out = 0;
-  b->last_kind = 0;
+  b->last_kind = KIND_NONE;
   EPI_HIP(hipSetDevice(b->eng->device));
   hipStream_t s = pick_stream(b, stream);
-  uint32_t ctx_mask = 0;                                                     // :104-107
-  for (const unsigned char *c = reinterpret_cast<const unsigned char *>(ctx); *c; c++) ctx_mask |= 1u << ctx_to_idx(*c);
+  const uint32_t ctx_mask = ctx_mask_of(ctx);
   const uint32_t H = hmax > 0 ? (hmax < 65536 ? (uint32_t)hmax : 65536u) : 65536u;   // :112
-
-  {                                                        // short reads, one haplotype context: one pass over the bytes
-    bool done = false;
-    EPI_TRY(mhl_fused_report(b, ctx_mask, H, hmin, max_ooctx_meth_frac, s, nrow_out, &done));
-    if (done) return EPI_OK;
-  }
-
-  RowStats st;
-  int32_t nt = 0;
-  EPI_TRY(build_tiles(b, s, kMhlTile, &st, &nt));
-  b->last_ntiles = nt;
-  if (nt == 0) {                                           // (a rank of a sharded run without rows still takes part in the exchange)
-    b->last_kind = !b->shared_keys.empty() && b->d_mhl_cnt_slab ? 4 : 2; b->last_nrow = 0;
-    return EPI_OK;
-  }
-
-  // pass 1 workspace: per-read info, record table, records (grown on demand like the row pool)
-  const int gc = pick_mhl_group(st.max_len);
-  const bool multi = gc == 0;
-  const size_t nblkrec = multi ? (size_t)(b->nbytes >> MHL_BLK_SHIFT) + 2 * (size_t)b->n + 2 : 1;
-  EPI_TRY(b->mhl_h.ensure((size_t)b->n * 16));
-  EPI_TRY(b->mhl_blk.ensure(nblkrec * 8));
-  if (multi) EPI_TRY(b->mhl_cont.ensure(nblkrec * 4));
-  if (b->mhl_rec_cap == 0) {
-    b->mhl_rec_cap = (size_t)b->nbytes / 48 + (size_t)b->n + 64 * MHL_REGIONS;
-    EPI_TRY(b->mhl_m.ensure(b->mhl_rec_cap * sizeof(MhlRec)));
-  }
-  EPI_TRY(b->mhl_cur.ensure((size_t)MHL_REGIONS * MHL_CUR_STRIDE * 8));
-  unsigned long long *rec_cursor = b->mhl_cur.as<unsigned long long>();
-  Scalars *sc = report_scalars(b);
-  unsigned long long *rec_max = reinterpret_cast<unsigned long long *>(sc->rec_max);
-
-  RowsArgs ra;
-  ra.xm = b->xm; ra.off = b->off; ra.len = b->len; ra.n = b->n;
-  ra.lut = make_mhl_lut(ctx_mask);
-  ra.hmin = (int32_t)hmin; ra.max_oo = max_ooctx_meth_frac;
-  ra.rowinfo = b->mhl_h.as<int4>();
-  ra.blkrec = b->mhl_blk.as<uint2>();
-  ra.rec_cursor = rec_cursor;
-  ra.cont = multi ? b->mhl_cont.as<uint32_t>() : nullptr;
-  ra.max_h = &sc->max_h;
-
-  EPI_TRY(b->tile_nrow.ensure((size_t)nt * 4));
-  EPI_TRY(b->tile_base.ensure((size_t)nt * 4));
-  EPI_TRY(b->tile_out.ensure((size_t)(nt + 1) * 4));
-
-  MhlArgs a;
-  a.c.xm = b->xm; a.c.off = b->off; a.c.len = b->len; a.c.start = b->start; a.c.strand = b->strand; a.c.pass = nullptr;
-  a.rowinfo = b->mhl_h.as<int4>();
-  a.blkrec = b->mhl_blk.as<uint2>();
-  a.multi = multi ? 1 : 0;
-#ifdef EPI_MHL_CHECK
-  EPI_TRY(b->diag.ensure(256));
-  a.dbg = b->diag.as<uint32_t>();
-  a.n = b->n; a.nbytes = b->nbytes; a.nblkrec = (int64_t)nblkrec;
-  EPI_HIP(hipMemsetAsync(a.dbg, 0, 32, s));
-#endif
-  a.tiles = b->tiles.as<Tile>();
-  a.ctx_mask = ctx_mask; a.H = H;
-  a.cursor = &sc->cursor;
-  a.tile_nrow = b->tile_nrow.as<uint32_t>();
-  a.tile_base = b->tile_base.as<uint32_t>();
-  a.heavy_rows = 16384;
-  if (options().heavy_rows > 0) a.heavy_rows = options().heavy_rows;   // test hook (EPIHIP_HEAVY_ROWS)
-  if (a.heavy_rows > 32767) a.heavy_rows = 32767;          // k_mhl_tiles' packed u16 counters: a base adds at most 2 (the
-                                                           // CX kernels cap at 16384, cx_report.hip)
-  const int heavy_rows_base = a.heavy_rows;
-  a.heavy_chunk = a.heavy_rows / 4 > 64 ? a.heavy_rows / 4 : 64;
-  EPI_TRY(b->heavy_list.ensure((size_t)nt * 4));
-  a.heavy_list = b->heavy_list.as<uint32_t>();
-  a.heavy_count = &sc->heavy_count;
-  a.heavy_max = &sc->heavy_max;
-  a.heavy_cnt = nullptr;
-  a.heavy_sums = nullptr;
-  a.shared_cnt = reinterpret_cast<uint32_t *>(b->d_mhl_cnt_slab);
-  a.shared_sums = reinterpret_cast<unsigned long long *>(b->d_mhl_sum_slab);
-  const int32_t nshared = (int32_t)b->shared_keys.size();
-  if (nshared > 0 && (!a.shared_cnt || !a.shared_sums)) return fail(EPI_ERR_STATE, "shared tiles set without lMHL slabs (use epi_batch_mhl_set_shared)");
-  const size_t headroom = nshared > 0 ? (size_t)nshared * 2 * MHL_T : 0;
-  // row pool = a slot per tile + an overflow region (see epi_batch_cx_report_dev): CpG haplotypes give ~7 % of the
-  // (pos,strand) cells of a tile a row; the slot doubles for the next call when 1/8 of the rows outgrew it
-  if (!b->mhl_slot) b->mhl_slot = MHL_T / 8;
-  uint32_t slot = b->mhl_slot > 2u * MHL_T ? 2u * MHL_T : b->mhl_slot;
-  if (options().mhl_slot >= 0 && options().mhl_slot <= 2 * MHL_T) slot = (uint32_t)options().mhl_slot;   // test hook (EPIHIP_MHL_SLOT)
-  while (slot && (unsigned long long)nt * slot > 0xC0000000ull) slot >>= 1;   // row indices are u32
-  size_t ovf_base = (size_t)nt * slot;
-  for (;;) {
-    const size_t ovf = (ovf_base >> 4) > 65536 ? (ovf_base >> 4) : 65536;
-    if (mhl_pool_rows(b) >= ovf_base + ovf + headroom) break;
-    const int rc = ensure_mhl_pool(b, ovf_base + ovf + headroom);
-    if (rc == EPI_OK) break;
-    b->pool_cap = 0; b->pool_cap2 = 0;                     // (a failed growth has released the old buffers)
-    if (!slot) return rc;
-    slot = 0;                                              // the slots do not fit in device memory: every tile through the cursor
-    ovf_base = 0;
-  }
-  a.slot_rows = slot;
-  a.ovf_base = (uint32_t)ovf_base;
-  b->mhl_last_slot = slot;
-  b->mhl_last_ovf = (uint32_t)ovf_base;
-  b->mhl_ctx_mask = ctx_mask;
-  uint32_t used_total[2] = {0, 0};
-  const int tg = pick_mhl_tile_group(st.max_len);
-  for (int attempt = 0; attempt < 3; attempt++) {
-    // pass 1: per-read haplotype size and stretch records
-    ra.recs = b->mhl_m.as<MhlRec>();
-    ra.rec_cap = (uint32_t)b->mhl_rec_cap;
-    EPI_HIP(hipMemsetAsync(rec_cursor, 0, (size_t)MHL_REGIONS * MHL_CUR_STRIDE * 8, s));
-    EPI_HIP(hipMemsetAsync(ra.max_h, 0, 4, s));
-    prof_begin("mhl_rows", s);
-    if (multi) {
-      hipLaunchKernelGGL(k_mhl_rows_multi, dim3((unsigned)((b->n + 3) / 4)), dim3(256), 0, s, ra);
-    } else {
-      const int g = gc >> 3;
-      const unsigned nb = (unsigned)((b->n * g + 255) / 256);
-#define EPI_LAUNCH(GG)                                                                                       \
-  case GG * 8 + 2: hipLaunchKernelGGL((k_mhl_rows<GG, 2>), dim3(nb), dim3(256), 0, s, ra); break;            \
-  case GG * 8 + 3: hipLaunchKernelGGL((k_mhl_rows<GG, 3>), dim3(nb), dim3(256), 0, s, ra); break;            \
-  case GG * 8 + 4: hipLaunchKernelGGL((k_mhl_rows<GG, 4>), dim3(nb), dim3(256), 0, s, ra); break;
-      switch (gc) {
-        EPI_LAUNCH(2) EPI_LAUNCH(4) EPI_LAUNCH(8) EPI_LAUNCH(16) EPI_LAUNCH(32) EPI_LAUNCH(64)
-        default: return fail(EPI_ERR_ARG, "bad group size");
-      }
-#undef EPI_LAUNCH
-    }
-    prof_end("mhl_rows", s);
-    hipLaunchKernelGGL(k_mhl_cursor_max, dim3(1), dim3(MHL_REGIONS), 0, s, rec_cursor, rec_max);
-    EPI_HIP(hipGetLastError());
-    Scalars host;                                          // pass 1: fullest record region, largest haplotype size
-    EPI_TRY(read_report_scalars(b, s, &host));
-    const unsigned long long rec_used = ((unsigned long long)host.rec_max[1] << 32) | host.rec_max[0];
-    if (rec_used > b->mhl_rec_cap / MHL_REGIONS) {         // record space ran out: the need is known now, redo pass 1
-      if (attempt == 2) return fail(EPI_ERR_STATE, "stretch record overflow after regrow");
-      const unsigned long long want = (rec_used + rec_used / 16 + 64) * MHL_REGIONS;
-      if (want > 0xFFFFFFF0ull) return fail(EPI_ERR_NOMEM, "too many methylated stretches in one batch (%llu)", want);
-      b->mhl_rec_cap = (size_t)want;
-      EPI_TRY(b->mhl_m.ensure(b->mhl_rec_cap * sizeof(MhlRec)));
-      continue;
-    }
-    // u32 LDS sums if no position of a tile (or heavy-tile chunk) can reach 2^31: rows x (the largest value a read
-    // can add: S(h) >= h, S(M) <= S(h) for M <= h; + 1 for a stray nibble at the position)
-    uint32_t hcap = host.max_h > 65535u ? 65535u : host.max_h;
-    if (hcap >= H) hcap = H;
-    const unsigned long long vmax = nrS(hcap) > 1 ? nrS(hcap) : 1;
-    const unsigned long long narrow_rows = ((1ull << 31) - 1) / (vmax + 1);
-    bool narrow = narrow_rows >= 512;
-    if (options().mhl_sums) narrow = narrow && options().mhl_sums == 32;   // EPIHIP_MHL_SUMS=64 forces the wide kernel
-    a.heavy_rows = heavy_rows_base;
-    if (narrow && (unsigned long long)a.heavy_rows > narrow_rows) a.heavy_rows = (int)narrow_rows;
-    a.heavy_chunk = a.heavy_rows / 4 > 64 ? a.heavy_rows / 4 : 64;
-
-    // pass 2
-    a.recs = ra.recs;
-    a.rec_cap = ra.rec_cap;
-    a.pool_key = b->pool_key.as<uint32_t>();
-    a.pool_cov = b->pool_a.as<uint32_t>();
-    a.pool_hs = b->pool_d.as<unsigned long long>();
-    a.pool_nu = b->pool_e.as<unsigned long long>();
-    a.pool_de = b->pool_f.as<unsigned long long>();
-    a.pool_cap = (uint32_t)(mhl_pool_rows(b) > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : mhl_pool_rows(b));
-    if (attempt > 0) {                                   // (the tile-index pass zeroed them for the first attempt)
-      EPI_HIP(hipMemsetAsync(&sc->cursor, 0, offsetof(Scalars, deep_count) - offsetof(Scalars, cursor), s));   // cursor, rows, heavy count
-      EPI_HIP(hipMemsetAsync(a.heavy_max, 0, 4, s));
-    }
-    prof_begin("mhl_tiles", s);
-    if (narrow) launch_mhl_tiles<uint32_t>(tg, nt, s, a); else launch_mhl_tiles<unsigned long long>(tg, nt, s, a);
-    prof_end("mhl_tiles", s);
-    EPI_HIP(hipGetLastError());
-    EPI_TRY(scan_exclusive_u32(a.tile_nrow, b->tile_out.as<uint32_t>(), nt, &sc->rows, b->scan_tmp, s));
-#ifdef EPI_MHL_CHECK
-    {
-      uint32_t d[8];
-      EPI_HIP(hipMemcpy(d, a.dbg, 32, hipMemcpyDeviceToHost));
-      if (d[0]) return fail(EPI_ERR_STATE, "lMHL index check %u failed: v0=%d v1=%d block=%u thread=%u (n=%lld nt=%d attempt=%d)", d[0],
-                            (int)d[1], (int)d[2], d[3], d[4], (long long)b->n, nt, attempt);
-    }
-#endif
-    EPI_TRY(read_report_scalars(b, s, &host));
-    if (host.heavy_count > 0) {                            // pile-ups: split, reduce in HBM, emit, rescan
-      const uint32_t nheavy = host.heavy_count, nchunks = (host.heavy_max + (uint32_t)a.heavy_chunk - 1) / (uint32_t)a.heavy_chunk;
-      EPI_TRY(b->heavy_slab.ensure((size_t)nheavy * 16 * MHL_T * 4));
-      EPI_TRY(b->heavy_sums.ensure((size_t)nheavy * MHL_NSUM * 8));
-      a.heavy_cnt = b->heavy_slab.as<uint32_t>();
-      a.heavy_sums = b->heavy_sums.as<unsigned long long>();
-      EPI_HIP(hipMemsetAsync(a.heavy_cnt, 0, (size_t)nheavy * 16 * MHL_T * 4, s));
-      EPI_HIP(hipMemsetAsync(a.heavy_sums, 0, (size_t)nheavy * MHL_NSUM * 8, s));
-      prof_begin("mhl_heavy", s);
-      if (narrow) launch_mhl_heavy<uint32_t>(tg, nheavy, nchunks, s, a); else launch_mhl_heavy<unsigned long long>(tg, nheavy, nchunks, s, a);
-      prof_end("mhl_heavy", s);
-      EPI_HIP(hipGetLastError());
-      EPI_TRY(scan_exclusive_u32(a.tile_nrow, b->tile_out.as<uint32_t>(), nt, &sc->rows, b->scan_tmp, s));
-      EPI_TRY(read_report_scalars(b, s, &host));
-    }
-    used_total[0] = host.cursor;
-    used_total[1] = host.rows;
-    if (ovf_base + used_total[0] + headroom <= a.pool_cap) break;
-    if (attempt == 2) return fail(EPI_ERR_STATE, "row pool overflow after regrow");
-    EPI_TRY(ensure_mhl_pool(b, ovf_base + used_total[0] + (used_total[0] >> 4) + 1024 + headroom));
-    if (nshared > 0) {   // the rerun adds into the shared slabs again
-      EPI_HIP(hipMemsetAsync(a.shared_cnt, 0, (size_t)nshared * 16 * MHL_T * 4, s));
-      EPI_HIP(hipMemsetAsync(a.shared_sums, 0, (size_t)nshared * MHL_NSUM * 8, s));
-    }
-  }
-  if (used_total[0] > used_total[1] / 8 && b->mhl_slot < 2u * MHL_T) b->mhl_slot *= 2;   // too many tiles outgrew their slot
-  if (nshared > 0) { b->last_kind = 4; return EPI_OK; }     // caller continues with epi_batch_mhl_finish_shared
-  b->last_kind = 2;
-  b->last_nrow = used_total[1];
-  *nrow_out = used_total[1];
-  return EPI_OK;
+  bool done = false;                                       // short reads, one haplotype context: one pass over the bytes
+  EPI_TRY(mhl_fused_report(b, ctx_mask, H, hmin, max_ooctx_meth_frac, s, nrow_out, &done));
+  if (done) return EPI_OK;
+  return mhl_report_impl(b, ctx_mask, H, hmin, max_ooctx_meth_frac, s, nrow_out);
 }
 
 int epi_mhl_tile_positions(void) { return MHL_T; }
@@ -1224,11 +1253,10 @@ int epi_batch_mhl_fused_ok(epi_batch *b, const char *ctx, void *stream, int32_t 
   if (!b || !ctx || !ok_out) return fail(EPI_ERR_ARG, "epi_batch_mhl_fused_ok: NULL argument");
   *ok_out = 0;
   EPI_HIP(hipSetDevice(b->eng->device));
-  uint32_t ctx_mask = 0;
-  for (const unsigned char *c = reinterpret_cast<const unsigned char *>(ctx); *c; c++) ctx_mask |= 1u << ctx_to_idx(*c);
-  if (b->n == 0) { RowStats st; memset(&st, 0, sizeof(st)); *ok_out = mhl_fused_eligible(b, ctx_mask, st) ? 1 : 0; return EPI_OK; }
+  const uint32_t ctx_mask = ctx_mask_of(ctx);
+  if (b->n == 0) { RowStats st; memset(&st, 0, sizeof(st)); *ok_out = mhl_fused_eligible(ctx_mask, st) ? 1 : 0; return EPI_OK; }
   EPI_TRY(fetch_row_stats(b, pick_stream(b, stream)));
-  *ok_out = (!b->h_stats.bad_len && mhl_fused_eligible(b, ctx_mask, b->h_stats)) ? 1 : 0;
+  *ok_out = (!b->h_stats.bad_len && mhl_fused_eligible(ctx_mask, b->h_stats)) ? 1 : 0;
   return EPI_OK;
 }
 
@@ -1242,46 +1270,26 @@ int epi_batch_mhl_set_shared_fused(epi_batch *b, const int64_t *h_keys, const in
 // Second half of a sharded lMHL report: the slabs have been sum-reduced across ranks.
 int epi_batch_mhl_finish_shared(epi_batch *b, void *stream, int64_t *nrow_out) {
   if (!b || !nrow_out) return fail(EPI_ERR_ARG, "epi_batch_mhl_finish_shared: NULL argument");
-  if (b->last_kind != 4 && b->last_kind != 5) return fail(EPI_ERR_STATE, "epi_batch_mhl_finish_shared without a sharded epi_batch_mhl_report_dev");
+  if (b->last_kind != KIND_MHL_SHARED && b->last_kind != KIND_MHLF_SHARED)
+    return fail(EPI_ERR_STATE, "epi_batch_mhl_finish_shared without a sharded epi_batch_mhl_report_dev");
   EPI_HIP(hipSetDevice(b->eng->device));
   hipStream_t s = pick_stream(b, stream);
-  if (b->last_kind == 5) return mhl_fused_finish_shared(b, s, nrow_out);   // the one-pass kernel's slabs
-  const int32_t nt = b->last_ntiles;
-  if (nt == 0) { b->last_kind = 2; b->last_nrow = 0; *nrow_out = 0; return EPI_OK; }   // this rank holds no rows: owns no tile
-  Scalars *sc = report_scalars(b);
-  MhlArgs a;
-  memset(&a, 0, sizeof(a));
-  a.tiles = b->tiles.as<Tile>();
+  if (b->last_kind == KIND_MHLF_SHARED) return mhl_fused_finish_shared(b, s, nrow_out);   // the one-pass kernel's slabs
+  if (b->last_ntiles == 0) { b->last_kind = KIND_MHL; b->last_nrow = 0; *nrow_out = 0; return EPI_OK; }   // this rank holds no rows: owns no tile
+  MhlArgs a{};
+  mhl_bind_pool(b, a);
   a.ctx_mask = b->mhl_ctx_mask;
-  a.cursor = &sc->cursor;
-  a.tile_nrow = b->tile_nrow.as<uint32_t>();
-  a.tile_base = b->tile_base.as<uint32_t>();
   a.shared_cnt = reinterpret_cast<uint32_t *>(b->d_mhl_cnt_slab);
   a.shared_sums = reinterpret_cast<unsigned long long *>(b->d_mhl_sum_slab);
-  a.pool_key = b->pool_key.as<uint32_t>();
-  a.pool_cov = b->pool_a.as<uint32_t>();
-  a.pool_hs = b->pool_d.as<unsigned long long>();
-  a.pool_nu = b->pool_e.as<unsigned long long>();
-  a.pool_de = b->pool_f.as<unsigned long long>();
-  a.pool_cap = (uint32_t)(mhl_pool_rows(b) > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : mhl_pool_rows(b));
-  a.slot_rows = b->mhl_last_slot;
-  a.ovf_base = b->mhl_last_ovf;
   hipLaunchKernelGGL((k_mhl_emit_slab<MHL_WG>), dim3((unsigned)b->shared_keys.size()), dim3(MHL_WG), 0, s, a,
                      b->d_shared_owned.as<int32_t>(), b->d_slot_tile.as<int32_t>());
   EPI_HIP(hipGetLastError());
-  EPI_TRY(scan_exclusive_u32(a.tile_nrow, b->tile_out.as<uint32_t>(), nt, &sc->rows, b->scan_tmp, s));
-  Scalars host;
-  EPI_TRY(read_report_scalars(b, s, &host));
-  if ((size_t)a.ovf_base + host.cursor > a.pool_cap) return fail(EPI_ERR_STATE, "row pool overflow in sharded lMHL report");
-  b->last_kind = 2;
-  b->last_nrow = host.rows;
-  *nrow_out = host.rows;
-  return EPI_OK;
+  return mhl_finish_rows(b, s, nrow_out);
 }
 
 int epi_batch_mhl_fetch_dev(epi_batch *b, int32_t *const d_icols[5], double *const d_dcols[2], void *stream) {
   if (!b || !d_icols || !d_dcols) return fail(EPI_ERR_ARG, "epi_batch_mhl_fetch_dev: NULL argument");
-  if (b->last_kind != 2) return fail(EPI_ERR_STATE, "epi_batch_mhl_fetch_dev: no finished lMHL report on this batch");
+  if (b->last_kind != KIND_MHL) return fail(EPI_ERR_STATE, "epi_batch_mhl_fetch_dev: no finished lMHL report on this batch");
   if (b->last_nrow == 0) return EPI_OK;
   for (int i = 0; i < 5; i++) if (!d_icols[i]) return fail(EPI_ERR_ARG, "epi_batch_mhl_fetch_dev: NULL column");
   for (int i = 0; i < 2; i++) if (!d_dcols[i]) return fail(EPI_ERR_ARG, "epi_batch_mhl_fetch_dev: NULL column");
@@ -1301,7 +1309,7 @@ int epi_batch_mhl_fetch_dev(epi_batch *b, int32_t *const d_icols[5], double *con
 
 int epi_batch_mhl_fetch_host(epi_batch *b, int32_t *const h_icols[5], double *const h_dcols[2], void *stream) {
   if (!b || !h_icols || !h_dcols) return fail(EPI_ERR_ARG, "epi_batch_mhl_fetch_host: NULL argument");
-  if (b->last_kind != 2) return fail(EPI_ERR_STATE, "epi_batch_mhl_fetch_host: no finished lMHL report on this batch");
+  if (b->last_kind != KIND_MHL) return fail(EPI_ERR_STATE, "epi_batch_mhl_fetch_host: no finished lMHL report on this batch");
   const int64_t nrow = b->last_nrow;
   if (nrow == 0) return EPI_OK;
   EPI_HIP(hipSetDevice(b->eng->device));

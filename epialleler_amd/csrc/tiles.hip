@@ -355,4 +355,33 @@ int build_tiles(epi_batch *b, hipStream_t s, int32_t T, RowStats *h, int32_t *nt
   return EPI_OK;
 }
 
+// Row pool of a report (CX, two-kernel lMHL, one-pass lMHL) = one slot of `slot` rows per tile + an overflow region behind
+// the slots, out of which a tile that outgrows its slot takes rows through Scalars::cursor.  The caller remembers a slot
+// size per kind of report: it starts at a typical density of reported positions and doubles for the next call when more
+// than 1/8 of the rows went through the cursor; an overflow of the region itself is detected after the run and costs one
+// rerun with the exact size.  layout_pool clamps the remembered slot to 2 T (a tile has T positions on two strands),
+// lets the test hook replace it (hook_slot >= 0), halves it until the slots stay below 0xC0000000 rows (row indices are
+// u32), and has `reserve` grow that report's pool to slots + region (1/16 of the slots, at least 65 536 rows) + headroom;
+// reserve(b, rows) returns at once when the pool holds `rows` rows already.  Where the slots do not fit in device memory
+// the layout falls back to slot = 0: every tile through the cursor, the pool sized by the rows actually produced.
+int layout_pool(epi_batch *b, uint32_t slot, int T, int32_t nt, size_t headroom, int hook_slot, int (*reserve)(epi_batch *, size_t rows),
+                PoolLayout *out) {
+  if (slot > 2u * T) slot = 2u * T;
+  if (hook_slot >= 0 && hook_slot <= 2 * T) slot = (uint32_t)hook_slot;
+  while (slot && (unsigned long long)nt * slot > 0xC0000000ull) slot >>= 1;
+  size_t ovf_base = (size_t)nt * slot;
+  for (;;) {
+    const size_t ovf = (ovf_base >> 4) > 65536 ? (ovf_base >> 4) : 65536;
+    const int rc = reserve(b, ovf_base + ovf + headroom);
+    if (rc == EPI_OK) break;
+    b->pool_cap = 0; b->pool_cap2 = 0;                     // (a failed growth has released the old buffers; pool_cap2: lMHL's 64-bit columns)
+    if (!slot) return rc;
+    slot = 0;
+    ovf_base = 0;
+  }
+  out->slot = slot;
+  out->ovf_base = ovf_base;
+  return EPI_OK;
+}
+
 }  // namespace epi

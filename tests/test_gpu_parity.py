@@ -359,6 +359,31 @@ def test_lmhl_sum_width_and_lowered_heavy_threshold(ea):
         bam.close()
 
 
+@pytest.mark.parametrize("fused", ["1", "0"])
+def test_lmhl_second_attempt_after_pool_regrow(ea, hook_env, fused):
+    """The first lMHL report of a fresh batch finds the row pool at its 65 536-row minimum; with every row sent through the
+    overflow cursor (EPIHIP_MHL_SLOT=0) a table of more rows than that overflows it, and the report runs a second attempt:
+    counters zeroed again, the regrown pool bound again.  The same report once more on the batch fits at once."""
+    hook_env("EPIHIP_MHL_SLOT", "0")
+    if fused == "0":
+        hook_env("EPIHIP_MHL_FUSED", "0")
+    # 3000 reads of 100 bytes, 50 CpG sites each, 60 positions apart, strands in pairs (coverage 1 to 2 per strand), two chromosomes
+    n = 3000
+    xms = ["".join(("Zz"[(i * 5 + k) % 7 < 3] if i % 2 == 0 else ".") for i in range(100)) for k in range(n)]
+    t = H.templates_from_xm(xms, [100 + 60 * (k % (n // 2)) for k in range(n)], [1 + ((k >> 1) & 1) for k in range(n)],
+                            [1 + k // (n // 2) for k in range(n)])
+    want = orc.mhl_report(t["xm"], t["off"], t["rname"], t["strand"], t["start"], "Zz", 0, 0, 1.0)
+    assert want["pos"].size > 65536, "mis-set-up: the table must not fit the minimal pool (%d rows)" % want["pos"].size
+    bam = pb(ea, t)
+    for _ in range(2):
+        got = dict(ea.rcpp_mhl_report(bam, "Zz", 0, 0, 1.0))
+        assert set(got) == set(want) and len(want) == 7
+        for k in want:                                                    # doubles bitwise
+            g, w = (got[k].view(np.uint64), want[k].view(np.uint64)) if want[k].dtype.kind == "f" else (got[k], want[k])
+            assert g.shape == w.shape and np.array_equal(g, w), k
+    bam.close()
+
+
 def test_two_kernel_lmhl_index_boundaries(ea, hook_env):
     """The three index computations of the two-kernel lMHL path ("index bounds"): reads whose last
     byte is the last position of a 512-position tile and the last byte of the batch, reads that end one position

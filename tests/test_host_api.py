@@ -148,8 +148,9 @@ def test_write_report_double_format(tmp_path):
 def test_no_timing_switches_in_the_product_library():
     """Timing builds (phases skipped: wrong results by design) are a compile-time make target; the shipped library
     must not contain the environment switches of round 1, nor that of the walking CX kernel (an experiment that lost and
-    was removed from the source)."""
+    was removed from the source), nor the lane-shape switches of the lMHL A/B runs (the pickers choose by themselves)."""
     from epialleler_amd import _lib
     data = open(_lib.LIB_PATH, "rb").read()
-    for name in (b"EPIHIP_CX_ABLATE", b"EPIHIP_MHL_ABLATE", b"EPIHIP_CX_DIAG", b"EPIHIP_CX_WALK"):
+    for name in (b"EPIHIP_CX_ABLATE", b"EPIHIP_MHL_ABLATE", b"EPIHIP_CX_DIAG", b"EPIHIP_CX_WALK",
+                 b"EPIHIP_MHLF_SHAPE", b"EPIHIP_MHL_GROUP"):
         assert name not in data
