@@ -8,10 +8,10 @@ include/epihip.h); this package is the host-side mirror of the R functions.
 """
 from .api import (CONTEXT_TO_BASES, CONTEXT_LEVELS, STRAND_LEVELS, ProcessedBam, Report,  # noqa: F401
                   cytosine_report_fused, generateCytosineReport, generateMhlReport, preprocessBam, rcpp_cx_report,
-                  rcpp_extract_patterns, rcpp_extract_patterns_multi, rcpp_get_xm_beta, rcpp_mhl_report, rcpp_threshold_reads,
-                  writeReport)
+                  rcpp_extract_patterns, rcpp_extract_patterns_multi, rcpp_get_xm_beta, rcpp_mhl_report, rcpp_summarise_patterns_multi,
+                  rcpp_threshold_reads, writeReport)
 from .bed import (Bed, Ecdf, extractPatterns, extractPatternsBed, generateAmpliconReport, generateBedEcdf,  # noqa: F401
-                  generateBedReport, generateCaptureReport, readBed)
+                  generateBedReport, generateCaptureReport, readBed, selectPatterns, summarisePatterns)
 from .genome import Genome, callMethylation, preprocessGenome, rcpp_call_methylation_genome, rcpp_read_genome  # noqa: F401
 from .simulate import rcpp_simulate_bam, simulateBam  # noqa: F401
 from .vcf import Vcf, generateVcfReport, rcpp_fep, rcpp_get_base_freqs, readVcf  # noqa: F401

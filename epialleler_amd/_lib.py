@@ -68,6 +68,11 @@ class PatternTable(C.Structure):
                [("beta", C.POINTER(C.c_double)), ("fnv", C.POINTER(C.c_uint64)), ("cells", C.POINTER(C.c_int32))]
 
 
+class PatternSummary(C.Structure):
+    _fields_ = [("nuniq", C.c_int64), ("npat", C.c_int64), ("ncol", C.c_int32), ("positions", C.POINTER(C.c_int32)),
+                ("fnv", C.POINTER(C.c_uint64)), ("count", C.POINTER(C.c_int32)), ("cells", C.POINTER(C.c_int32))]
+
+
 class SimColumn(C.Structure):
     _fields_ = [("name", C.c_char_p), ("kind", C.c_int32), ("type", C.c_char), ("values", C.c_void_p),
                 ("offsets", C.c_void_p), ("len", C.c_int64), ("period", C.c_int64)]
@@ -144,6 +149,10 @@ _SIGS = {
     "epi_batch_extract_patterns_multi": (C.c_int, [_VP, _I32, _VP, _VP, _VP, _I32, _CS, _F64, _I32, _I32, _VP, _VP, _VP,
                                                  C.POINTER(PatternTable)]),
     "epi_batch_extract_patterns_multi_stats": (C.c_int, [_VP, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64)]),
+    "epi_pattern_summary_free": (None, [C.POINTER(PatternSummary)]),
+    "epi_batch_summarise_patterns_multi": (C.c_int, [_VP, _I32, _VP, _VP, _VP, _I32, _CS, _F64, _I32, _I32, _VP, _VP, _VP,
+                                                   C.POINTER(PatternSummary)]),
+    "epi_batch_summarise_patterns_stats": (C.c_int, [_VP, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64)]),
     "epi_batch_cx_report_dev": (C.c_int, [_VP, _VP, _CS, _VP, C.POINTER(_I64)]),
     "epi_batch_cytosine_report_dev": (C.c_int, [_VP, _CS, _CS, _CS, _CS, _U32, _F64, _F64, _CS, _VP, _VP, C.POINTER(_I64)]),
     "epi_batch_cx_report_into_dev": (C.c_int, [_VP, _VP, _CS, C.POINTER(_VP), _I64, _VP, C.POINTER(_I64), C.POINTER(C.c_int)]),

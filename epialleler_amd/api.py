@@ -443,11 +443,9 @@ def _pattern_report(t, target_rname, bam):
     return rep
 
 
-def rcpp_extract_patterns_multi(df, targets, min_overlap, ctx, min_ctx_freq, clip, reverse_offset, hlght=None):
-    """rcpp_extract_patterns for every target of a list in one pass over the candidate rows
-    (epi_batch_extract_patterns_multi).  targets: a sequence of (rname_code, start, end); hlght: None, or one sequence
-    of highlight positions per target (sorted, unique, inside the target).  Returns one Report per target, each what
-    rcpp_extract_patterns(df, *targets[k], ..., hlght[k]) returns."""
+def _patterns_multi(df, targets, hlght, fn_name, table_type, free_name, report, scalars):
+    """The call both multi-target entry points share: targets as [3][nt] int32, highlight positions as CSR, one
+    library-owned table per target turned into a Report by report(table, k) and released."""
     lib = _lib.load()
     bam = _as_bam(df)
     tg = np.ascontiguousarray(np.asarray(list(targets), dtype=np.int64).reshape(-1, 3).T, dtype=np.int32)    # [3][nt]
@@ -459,17 +457,63 @@ def rcpp_extract_patterns_multi(df, targets, min_overlap, ctx, min_ctx_freq, cli
     if hlght is not None:
         np.cumsum([len(h) for h in hlght], out=hl_off[1:])
     hl = np.ascontiguousarray([p for h in hlght for p in h] if hlght is not None else [], dtype=np.int32)
-    tabs = (_lib.PatternTable * max(nt, 1))()
+    tabs = (table_type * max(nt, 1))()
     ptr = lambda a: C.c_void_p(a.ctypes.data) if a.size else None
-    _lib.check(lib.epi_batch_extract_patterns_multi(b, nt, ptr(tg[0]), ptr(tg[1]), ptr(tg[2]), int(min_overlap), _lib.enc(ctx),
-                                                    float(min_ctx_freq), int(bool(clip)), int(reverse_offset), ptr(hl),
-                                                    C.c_void_p(hl_off.ctypes.data) if hlght is not None else None,
-                                                    _stream(bam.device), tabs))
+    min_overlap, ctx, min_ctx_freq, clip, reverse_offset = scalars
+    _lib.check(getattr(lib, fn_name)(b, nt, ptr(tg[0]), ptr(tg[1]), ptr(tg[2]), int(min_overlap), _lib.enc(ctx), float(min_ctx_freq),
+                                     int(bool(clip)), int(reverse_offset), ptr(hl),
+                                     C.c_void_p(hl_off.ctypes.data) if hlght is not None else None, _stream(bam.device), tabs))
     try:
-        return [_pattern_report(tabs[k], tg[0, k], bam) for k in range(nt)]
+        return [report(tabs[k], tg[0, k], bam) for k in range(nt)]
     finally:
         for k in range(nt):
-            lib.epi_pattern_table_free(C.byref(tabs[k]))
+            getattr(lib, free_name)(C.byref(tabs[k]))
+
+
+def rcpp_extract_patterns_multi(df, targets, min_overlap, ctx, min_ctx_freq, clip, reverse_offset, hlght=None):
+    """rcpp_extract_patterns for every target of a list in one pass over the candidate rows
+    (epi_batch_extract_patterns_multi).  targets: a sequence of (rname_code, start, end); hlght: None, or one sequence
+    of highlight positions per target (sorted, unique, inside the target).  Returns one Report per target, each what
+    rcpp_extract_patterns(df, *targets[k], ..., hlght[k]) returns."""
+    return _patterns_multi(df, targets, hlght, "epi_batch_extract_patterns_multi", _lib.PatternTable, "epi_pattern_table_free",
+                           _pattern_report, (min_overlap, ctx, min_ctx_freq, clip, reverse_offset))
+
+
+def _summary_report(t, bam, beta_letters=None):
+    """An epi_pattern_summary (still owned by the library) -> Report: pattern, one column per position, count, and with
+    beta_letters = (ctx_meth, ctx_unmeth) beta: per row meth / (meth + unmeth) over its cells, 0 without either, where the
+    cells that count are the factor codes of those letters and an NA cell counts in neither (R/plotPatterns.R:174-184)."""
+    k, m = int(t.nuniq), int(t.ncol)
+    if k == 0:
+        return Report({}, bam.levels)
+    take = lambda ptr, n, dt: np.ctypeslib.as_array(ptr, shape=(n,)).astype(dt, copy=True)
+    cols = {"pattern": np.asarray(["%016X" % int(v) for v in take(t.fnv, k, np.uint64)], object)}
+    pos = take(t.positions, m, np.int32)
+    cells = take(t.cells, m * k, np.int32).reshape(m, k)
+    for i in range(m):
+        cols[str(int(pos[i]))] = cells[i]
+    cols["count"] = take(t.count, k, np.int32)
+    if beta_letters is not None:
+        lut = np.zeros((2, len(PATTERN_LEVELS) + 1), np.int64)                 # [meth, unmeth][factor code]; NA -> code 0
+        for row, letters in zip(lut, beta_letters):
+            row[[PATTERN_LEVELS.index(ch) + 1 for ch in letters]] = 1
+        code = np.clip(cells, 0, len(PATTERN_LEVELS))
+        meth = lut[0][code].sum(axis=0).astype(np.float64)
+        total = meth + lut[1][code].sum(axis=0).astype(np.float64)
+        cols["beta"] = np.divide(meth, total, out=np.zeros(k, np.float64), where=total > 0)
+    rep = Report(cols, bam.levels)
+    rep.pattern_levels = PATTERN_LEVELS
+    return rep
+
+
+def rcpp_summarise_patterns_multi(df, targets, min_overlap, ctx, min_ctx_freq, clip, reverse_offset, hlght=None, beta_letters=None):
+    """The unique rows, by (pattern, every position column), of what rcpp_extract_patterns returns for every target of a
+    list, with their counts and in the order of their first appearance -- grouped on the GPU, so that nothing per read
+    comes to the host (epi_batch_summarise_patterns_multi).  Arguments as rcpp_extract_patterns_multi.  Returns one
+    Report per target: pattern (16 hex digits), one int32 column per position, count (int32), and with beta_letters =
+    (ctx_meth, ctx_unmeth) beta (float64, computed here from the cells)."""
+    return _patterns_multi(df, targets, hlght, "epi_batch_summarise_patterns_multi", _lib.PatternSummary, "epi_pattern_summary_free",
+                           lambda t, _, bam: _summary_report(t, bam, beta_letters), (min_overlap, ctx, min_ctx_freq, clip, reverse_offset))
 
 
 # ---- exported R API ------------------------------------------------------------------------------

@@ -11,7 +11,8 @@ import numpy as np
 
 from . import _lib
 from .api import (CONTEXT_TO_BASES, Report, _CTX_CHOICES, _as_bam, _match_arg, _stream, preprocessBam,
-                  rcpp_extract_patterns, rcpp_extract_patterns_multi, rcpp_get_xm_beta, rcpp_threshold_reads, writeReport)
+                  rcpp_extract_patterns, rcpp_extract_patterns_multi, rcpp_get_xm_beta, rcpp_summarise_patterns_multi,
+                  rcpp_threshold_reads, writeReport)
 
 NA_INTEGER = -2 ** 31
 
@@ -206,14 +207,11 @@ def extractPatterns(bam, bed, bed_row=1, zero_based_bed=False, match_min_overlap
     return rep
 
 
-def extractPatternsBed(bam, bed, bed_rows=None, zero_based_bed=False, match_min_overlap=1, extract_context=None,
-                       min_context_freq=0.01, clip_patterns=False, strand_offset=None, highlight_positions=(), verbose=False,
-                       **preprocess_args):
-    """extractPatterns for many BED rows in one pass on the GPU (epi_batch_extract_patterns_multi): the list
-    [extractPatterns(bam, bed, bed_row=r, ...) for r in bed_rows], at the cost of the reads on the targets instead of
-    one scan of the batch per target.  bed_rows: 1-based rows in the order wanted, duplicates allowed, None = every
-    row in BED order; a row outside the BED gives the empty Report the single call gives.  highlight_positions: one
-    list for the call, every target uses the positions inside it.  The BAM is preprocessed once."""
+def _pattern_calls(bam, bed, bed_rows, zero_based_bed, extract_context, strand_offset, highlight_positions, preprocess_args):
+    """What extractPatternsBed and summarisePatterns do before their GPU call: the arguments checked before any I/O, the
+    BAM preprocessed once, the requested BED rows as (rname code, start, end) with the highlight positions inside each.
+    -> (bam, bed, the requested rows 0-based, the indices of those inside the BED, their targets, their highlight
+    positions, the context letters, the strand offset)"""
     extract_context = _match_arg(extract_context, _CTX_CHOICES, "extract.context")
     if bed_rows is not None:
         bed_rows = list(np.atleast_1d(np.asarray(bed_rows, object)))
@@ -236,11 +234,102 @@ def extractPatternsBed(bam, bed, bed_rows=None, zero_based_bed=False, match_min_
         targets.append((code.get(bed.chrom[r], NA_INTEGER), start, end))       # factor(seqnames, levels=levels(rname))
         hl.append([int(p) for p in hl_all[(hl_all >= start) & (hl_all <= end)]])
     c = CONTEXT_TO_BASES[extract_context]
-    reps = rcpp_extract_patterns_multi(bam, targets, match_min_overlap, c["ctx_meth"] + c["ctx_unmeth"], min_context_freq,
-                                       clip_patterns, int(strand_offset), hl)
+    return bam, bed, rows, keep, targets, hl, c["ctx_meth"] + c["ctx_unmeth"], int(strand_offset)
+
+
+def _pattern_reports(bam, bed, rows, keep, reps):
+    """One Report per requested row: reps for those inside the BED, each with its BED row's name, and the empty Report
+    of data.table()[bed.row] for a missing row."""
     names = bed.names()
-    out = [Report({}, bam.levels) for _ in rows]                               # data.table()[bed.row] of a missing row: no target
+    out = [Report({}, bam.levels) for _ in rows]
     for k, rep in zip(keep, reps):
         rep.bed = names[rows[k]]
         out[k] = rep
+    return out
+
+
+def extractPatternsBed(bam, bed, bed_rows=None, zero_based_bed=False, match_min_overlap=1, extract_context=None,
+                       min_context_freq=0.01, clip_patterns=False, strand_offset=None, highlight_positions=(), verbose=False,
+                       **preprocess_args):
+    """extractPatterns for many BED rows in one pass on the GPU (epi_batch_extract_patterns_multi): the list
+    [extractPatterns(bam, bed, bed_row=r, ...) for r in bed_rows], at the cost of the reads on the targets instead of
+    one scan of the batch per target.  bed_rows: 1-based rows in the order wanted, duplicates allowed, None = every
+    row in BED order; a row outside the BED gives the empty Report the single call gives.  highlight_positions: one
+    list for the call, every target uses the positions inside it.  The BAM is preprocessed once."""
+    bam, bed, rows, keep, targets, hl, ctx, offset = _pattern_calls(bam, bed, bed_rows, zero_based_bed, extract_context, strand_offset,
+                                                                    highlight_positions, preprocess_args)
+    reps = rcpp_extract_patterns_multi(bam, targets, match_min_overlap, ctx, min_context_freq, clip_patterns, offset, hl)
+    return _pattern_reports(bam, bed, rows, keep, reps)
+
+
+def summarisePatterns(bam, bed, bed_rows=None, zero_based_bed=False, match_min_overlap=1, extract_context=None,
+                      min_context_freq=0.01, clip_patterns=False, strand_offset=None, highlight_positions=(),
+                      bin_context=None, verbose=False, **preprocess_args):
+    """The epiallele frequency table of every requested BED row: what plotPatterns makes of extractPatterns' table
+    before it draws (R/plotPatterns.R:170-184).  For a row r, with P = extractPatterns(bam, bed, bed_row=r, ...), the
+    Report holds the unique rows of P by (pattern, every position column) in the order of their first appearance in P:
+    `pattern` (16 hex digits), one column per position, `count`, and `beta` (float64) for bin_context (default: the
+    first choice, "CG", as plotPatterns' bin.context).  Strand, start, end and nbase are not part of the key and are not
+    returned.  The rows are grouped on the GPU (epi_batch_summarise_patterns_multi): nothing per read comes to the
+    host.  bed_rows as extractPatternsBed: 1-based, duplicates allowed, None = every row; a row outside the BED, or one
+    without patterns, gives an empty Report.  `.bed` and `.pattern_levels` as on extractPatterns' Report."""
+    bin_context = _match_arg(bin_context, _CTX_CHOICES, "bin.context")
+    bam, bed, rows, keep, targets, hl, ctx, offset = _pattern_calls(bam, bed, bed_rows, zero_based_bed, extract_context, strand_offset,
+                                                                    highlight_positions, preprocess_args)
+    cb = CONTEXT_TO_BASES[bin_context]
+    reps = rcpp_summarise_patterns_multi(bam, targets, match_min_overlap, ctx, min_context_freq, clip_patterns, offset, hl,
+                                         (cb["ctx_meth"], cb["ctx_unmeth"]))
+    return _pattern_reports(bam, bed, rows, keep, reps)
+
+
+def selectPatterns(summary, order_by="beta", beta_range=(0, 1), nbins=10, npatterns_per_bin=2):
+    """The table plotPatterns returns invisibly (R/plotPatterns.R:168, :186-188), from a summarisePatterns Report: the
+    most frequent unique patterns of every beta bin.
+      bins  nbins + 1 equally spaced edges over beta_range (seq(from, to, length.out=nbins + 1))
+      bin   findInterval(beta, bins, all.inside=TRUE), 1-based, for a beta inside the closed range; other rows are dropped
+      rows  a stable sort by count, descending; per bin, in the order the bins first appear in that sorted table, the first
+            npatterns_per_bin[bin - 1] rows (the value is recycled to nbins entries; float("inf") keeps all)
+      I     number of selected rows - rank; rank 1 is the first row in decreasing (order_by, beta, count) order, ties in
+            table order
+    Returns a Report with the summary's columns plus `bin` (int32) and `I` (int32); `.bins` holds the edges.
+    These semantics are read from the reference's source; nothing here can run R, so they are not pinned against it,
+    and the last bits of the bin edges (R's seq against numpy's linspace) are not pinned either."""
+    if order_by not in ("beta", "count"):
+        raise ValueError("'order.by' should be one of 'beta', 'count'")
+    nbins = int(nbins)
+    if nbins < 1:
+        raise ValueError("'nbins' should be at least 1")
+    lo, hi = (float(v) for v in beta_range)
+    if not lo <= hi:
+        raise ValueError("'beta.range' should be (from, to) with from <= to")
+    per = np.resize(np.atleast_1d(np.asarray(npatterns_per_bin, np.float64)), nbins)
+    bins = np.linspace(lo, hi, nbins + 1)
+    out = Report({}, getattr(summary, "levels", {}).get("rname"))
+    for a in ("bed", "pattern_levels"):
+        if hasattr(summary, a):
+            setattr(out, a, getattr(summary, a))
+    out.bins = bins
+    if not summary:
+        return out
+    beta, count = np.asarray(summary["beta"], np.float64), np.asarray(summary["count"])
+    inside = np.flatnonzero((beta >= lo) & (beta <= hi))
+    bin_ = np.clip(np.searchsorted(bins, beta[inside], side="right"), 1, nbins)          # all.inside=TRUE
+    order = np.argsort(-count[inside].astype(np.int64), kind="stable")
+    taken = {}
+    for j in order:                                                            # (groups in order of first appearance)
+        taken.setdefault(int(bin_[j]), [])
+        if len(taken[int(bin_[j])]) < per[int(bin_[j]) - 1]:
+            taken[int(bin_[j])].append(j)
+    sel = np.asarray([j for js in taken.values() for j in js], np.int64)
+    idx = inside[sel]
+    for k in summary:
+        out[k] = np.asarray(summary[k])[idx]
+    out["bin"] = bin_[sel].astype(np.int32)
+    n = idx.size
+    cnt = count[idx].astype(np.float64)
+    # decreasing (order_by, beta, count), ties in table order: a stable sort on the negated keys, the last key first
+    rank = np.lexsort((-cnt, -beta[idx], -(cnt if order_by == "count" else beta[idx])))
+    I = np.empty(n, np.int32)
+    I[rank] = n - np.arange(1, n + 1)
+    out["I"] = I
     return out

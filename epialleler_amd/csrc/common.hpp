@@ -218,6 +218,7 @@ struct epi_batch {
   epi::DevBuf host_io;                         // device side of the host-pointer calls (pass flags / per-read beta)
   epi::DevBuf bf_flag;                         // base frequencies: the sites' sortedness verdict (base_freqs.hip)
   int64_t patm_groups = 0, patm_pairs = 0, patm_scratch = 0;   // last epi_batch_extract_patterns_multi: groups, pairs, peak scratch bytes
+  int64_t pats_groups = 0, pats_pairs = 0, pats_fallback = 0;  // last epi_batch_summarise_patterns_multi: groups, pairs, targets grouped on the host
   epi::DevBuf mhl_keep_tab;                    // fused lMHL: passing out-of-context counts per total (k_mhl_keep_table)
   int32_t mhl_keep_len = -1;
   double mhl_keep_oo = 0.0;
@@ -407,6 +408,7 @@ struct Options {
   int bam_timing = 0;        // EPIHIP_BAM_TIMING    phase times of the BAM reader and of callMethylation on stderr
   int no_hugepage = 0;       // EPIHIP_NO_HUGEPAGE   plain malloc for the BAM reader's large buffers (A/B runs)
   int no_libdeflate = 0;     // EPIHIP_NO_LIBDEFLATE zlib's inflate for the BGZF blocks although libdeflate.so.0 can be loaded
+  int pat_hash_bits = 0;         // EPIHIP_PAT_HASH_BITS=<k>  epi_batch_summarise_patterns_multi groups by the low k bits of the hash (1-63; else all 64)
   int64_t pat_group_bytes = 0;   // EPIHIP_PAT_GROUP_BYTES=<bytes>  scratch cap of a group of targets in epi_batch_extract_patterns_multi (0: 256 MiB)
   int64_t upload_piece = 0; // EPIHIP_UPLOAD_PIECE=<bytes>  piece size of the host-to-device copies of epi_batch_upload (0: by the
                              //                      source; at most 64 MiB from pageable memory, the size of the pinned staging buffers)

@@ -60,6 +60,7 @@ static void read_options() {
   if (o.upload_piece < 0) o.upload_piece = 0;
   if (const char *e = getenv("EPIHIP_PAT_GROUP_BYTES")) o.pat_group_bytes = strtoll(e, nullptr, 10);
   if (o.pat_group_bytes < 0) o.pat_group_bytes = 0;
+  geti("EPIHIP_PAT_HASH_BITS", &o.pat_hash_bits);
   g_options = o;
 }
 

@@ -10,12 +10,15 @@
 //   host           drops empty patterns (:152) and returns the table.
 // epi_batch_extract_patterns_multi (second half of this file) runs the same per-read rules for every target of a list in
 // O(1) launches and host round trips: candidate row ranges by search, one flat list of (target, row) pairs.
+// epi_batch_summarise_patterns_multi runs the same two passes and then groups every target's patterns on the device
+// (k_pats_*): only the unique patterns and their counts come to the host.
 // Quirks of the reference kept as they are: with clip=TRUE the byte loop ends at `overlap`,
 // not at begin+overlap (:86,:132), and position bytes enter the hash sign-extended (char pointer, epialleleR.h:8-13).
 #include "common.hpp"
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
+#include <unordered_map>
 #include <vector>
 
 namespace epi {
@@ -264,11 +267,167 @@ __global__ __launch_bounds__(256) void k_patm_extract(PatMulti m, uint64_t j0, u
   pat_extract_row(a, x, pat_span(a, x), cidx[j] - q.base_abs, colmap + g.win_off, hl + g.hl_off, hcol + g.hl_off, g.nhl, (int64_t)q.npat0, ot);
 }
 
+// ---- unique patterns with their counts (epi_batch_summarise_patterns_multi) --------------------------------------------
+// R/plotPatterns.R:172, patterns[, .(count=.N), by=c("pattern", base.positions)], for every target of a cell batch while its
+// slots (fnv, nonempty, cells[ncol][npat0]) are on the device.  Every target owns a slice of one open-addressing table
+// (power-of-two capacity >= 2 x its slots, keyed by the hash; the FNV offset basis, which no non-empty pattern has, is the
+// empty key).  insert -> verify (a slot whose cells differ from those of its entry's first slot: two patterns share a key,
+// the target is flagged and the host groups it by (hash, cells) instead) -> scans of the first-occurrence flags -> emit.
+struct PatEntry { unsigned long long key; uint32_t count, first; };
+struct PatSumSlice {              // a target's slice of the table
+  int64_t tab_off;
+  uint32_t mask;                  // capacity - 1
+  uint32_t ncol;
+};
+struct PatSum {
+  const PatSlice *sl;             // the group's targets; this batch: [sa, sb), slots [0, nslot) by base_rel
+  const PatSumSlice *ss;
+  int32_t sa, sb;
+  uint32_t nslot;
+  const unsigned long long *fnv;
+  const int32_t *nonempty, *cells;
+  PatEntry *tab;
+  uint32_t *ent;                  // [nslot] a slot's entry inside its target's slice
+  uint32_t *collide;              // [sb - sa]
+  unsigned long long key_mask;    // EPIHIP_PAT_HASH_BITS
+};
+constexpr unsigned long long kPatEmptyKey = 14695981039346656037ull;
+
+// last t in [sa, sb) with sl[t].base_rel <= i (targets without slots share their successor's base_rel and come before it)
+__device__ __forceinline__ int32_t pat_slot_target(const PatSlice *__restrict__ sl, int32_t sa, int32_t sb, uint32_t i) {
+  int32_t a = sa, b = sb;
+  for (int it = 0; it < 32 && b - a > 1; it++) {
+    const int32_t m = a + ((b - a) >> 1);
+    if (sl[m].base_rel <= i) a = m; else b = m;
+  }
+  return a;
+}
+
+__global__ __launch_bounds__(256) void k_pats_init(PatEntry *__restrict__ tab, int64_t n) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= n) return;
+  PatEntry v;
+  v.key = kPatEmptyKey; v.count = 0u; v.first = 0xFFFFFFFFu;
+  tab[e] = v;
+}
+
+// the entry of `key` in the slice s: linear probe from the key's home, the slice is never full (capacity >= 2 x slots)
+__device__ __forceinline__ bool pat_probe(PatEntry *__restrict__ e0, uint32_t mask, unsigned long long key, uint32_t &p) {
+  p = (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> 32) & mask;
+  for (uint32_t step = 0; step <= mask; step++) {
+    const unsigned long long prev = atomicCAS(&e0[p].key, kPatEmptyKey, key);
+    if (prev == kPatEmptyKey || prev == key) return true;
+    p = (p + 1u) & mask;
+  }
+  return false;
+}
+
+// One thread per slot.  A deep amplicon has most of its reads on one pattern, so a wave adds once per distinct
+// (target, key) among its lanes, not once per lane: the lowest remaining lane's pair is broadcast, the lanes that hold
+// the same pair are balloted, and that lane (the leader; slots rise with the lane, so its slot is the smallest of them)
+// probes and adds the ballot's population count.  EPI_PATS_PER_LANE (timing builds): every lane probes and adds 1.
+__global__ __launch_bounds__(256) void k_pats_insert(PatSum q) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  bool todo = i < q.nslot && q.nonempty[i] != 0;
+  int32_t t = 0;
+  unsigned long long key = 0;
+  if (todo) {
+    t = pat_slot_target(q.sl, q.sa, q.sb, i);
+    key = q.fnv[i] & q.key_mask;
+  }
+  const bool mine = todo;
+  uint32_t e = 0;
+#ifdef EPI_PATS_PER_LANE
+  if (todo) {
+    const PatSumSlice s = q.ss[t];
+    PatEntry *e0 = q.tab + s.tab_off;
+    if (pat_probe(e0, s.mask, key, e)) { atomicAdd(&e0[e].count, 1u); atomicMin(&e0[e].first, i); }
+    else q.collide[t - q.sa] = 1u;
+  }
+#else
+  while (todo) {
+    const int32_t t0 = __builtin_amdgcn_readfirstlane(t);
+    const uint32_t lo0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)key);
+    const uint32_t hi0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(key >> 32));
+    const bool match = t == t0 && (uint32_t)key == lo0 && (uint32_t)(key >> 32) == hi0;
+    const unsigned long long mb = __ballot(match);
+    uint32_t p = 0;
+    if ((uint32_t)(__ffsll((long long)mb) - 1) == (threadIdx.x & 63u)) {    // the leader: the lowest lane still here
+      const PatSumSlice s = q.ss[t];
+      PatEntry *e0 = q.tab + s.tab_off;
+      if (pat_probe(e0, s.mask, key, p)) { atomicAdd(&e0[p].count, (uint32_t)__popcll(mb)); atomicMin(&e0[p].first, i); }
+      else q.collide[t - q.sa] = 1u;
+    }
+    p = (uint32_t)__builtin_amdgcn_readfirstlane((int)p);
+    if (match) { e = p; todo = false; }
+  }
+#endif
+  if (mine) q.ent[i] = e;
+}
+
+// first[i] = 1 for a slot that is the first of its entry (wfirst: its ncol, the cells it will emit); every other
+// non-empty slot compares its hash and cells with that first slot's, column by column (neighbouring slots coalesce)
+__global__ __launch_bounds__(256) void k_pats_verify(PatSum q, uint32_t *__restrict__ first, uint32_t *__restrict__ wfirst) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= q.nslot) return;
+  uint32_t f1 = 0, w = 0;
+  if (q.nonempty[i]) {
+    const int32_t t = pat_slot_target(q.sl, q.sa, q.sb, i);
+    const PatSlice sl = q.sl[t];
+    const PatSumSlice ss = q.ss[t];
+    const uint32_t f = q.tab[ss.tab_off + (q.ent[i] & ss.mask)].first;
+    if (f == i) {
+      f1 = 1u; w = ss.ncol;
+    } else if (f < sl.base_rel || f > i) {                             // (only after a failed probe)
+      q.collide[t - q.sa] = 1u;
+    } else {
+      bool same = q.fnv[i] == q.fnv[f];
+      const int32_t *c = q.cells + sl.cell_off;
+      const uint32_t li = i - sl.base_rel, lf = f - sl.base_rel;
+      for (uint32_t k = 0; k < ss.ncol; k++) same = same && c[(int64_t)k * sl.npat0 + li] == c[(int64_t)k * sl.npat0 + lf];
+      if (!same) q.collide[t - q.sa] = 1u;
+    }
+  }
+  first[i] = f1;
+  wfirst[i] = w;
+}
+
+// ubase[k] / wbase[k] = unique patterns / emitted cells before the batch's k-th target (the totals, [nb], are the scans')
+__global__ __launch_bounds__(256) void k_pats_bases(const PatSlice *__restrict__ sl, int32_t sa, int32_t nb, uint32_t nslot,
+                                                    const uint32_t *__restrict__ uidx, const uint32_t *__restrict__ widx,
+                                                    uint32_t *__restrict__ ubase, uint32_t *__restrict__ wbase) {
+  const int32_t k = (int32_t)(blockIdx.x * 256 + threadIdx.x);
+  if (k >= nb) return;
+  const uint32_t r = sl[sa + k].base_rel;
+  ubase[k] = r < nslot ? uidx[r] : ubase[nb];
+  wbase[k] = r < nslot ? widx[r] : wbase[nb];
+}
+
+// out: [fnv u64 x U][count u32 x U][cells i32, per target [ncol][nuniq]], U = ubase[nb] <= nslot
+__global__ __launch_bounds__(256) void k_pats_emit(PatSum q, const uint32_t *__restrict__ first, const uint32_t *__restrict__ uidx,
+                                                   const uint32_t *__restrict__ ubase, const uint32_t *__restrict__ wbase,
+                                                   unsigned long long *__restrict__ out) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= q.nslot || !first[i]) return;
+  const int32_t t = pat_slot_target(q.sl, q.sa, q.sb, i);
+  const int32_t k = t - q.sa, nb = q.sb - q.sa;
+  const PatSlice sl = q.sl[t];
+  const PatSumSlice ss = q.ss[t];
+  const uint32_t U = ubase[nb], u = uidx[i], nu = ubase[k + 1] - ubase[k], lu = u - ubase[k], li = i - sl.base_rel;
+  uint32_t *count = reinterpret_cast<uint32_t *>(out + U);
+  int32_t *oc = reinterpret_cast<int32_t *>(count + U) + wbase[k];
+  out[u] = q.fnv[i];
+  count[u] = q.tab[ss.tab_off + (q.ent[i] & ss.mask)].count;
+  const int32_t *c = q.cells + sl.cell_off;
+  for (uint32_t col = 0; col < ss.ncol; col++) oc[(int64_t)col * nu + lu] = c[(int64_t)col * sl.npat0 + li];
+}
+
 }  // namespace epi
 
 using namespace epi;
 
 extern "C" void epi_pattern_table_free(epi_pattern_table *t);
+extern "C" void epi_pattern_summary_free(epi_pattern_summary *t);
 
 // The host's decision between the two passes: valid positions = seen in >= min_ctx_freq of the npat0 overlapping reads
 // and not highlighted (:103-108), the highlight positions (:110-112), merged in position order (:185).  cnt / colmap:
@@ -423,13 +582,20 @@ constexpr int64_t kPatGroupBytes = 256LL << 20;   // scratch cap of a group of t
 
 struct PatmScratch {
   DevBuf tgt, rng, meta, flag, cidx, cb, colmap, sl, hl, res;
+  DevBuf ss, tab, slot, ub, sout;   // the summary path: table slices, table, 5 x u32 per slot, bases and collide words, output
   size_t peak = 0;
   void note() {
-    const size_t v = tgt.cap + rng.cap + meta.cap + flag.cap + cidx.cap + cb.cap + colmap.cap + sl.cap + hl.cap + res.cap;
+    const size_t v = tgt.cap + rng.cap + meta.cap + flag.cap + cidx.cap + cb.cap + colmap.cap + sl.cap + hl.cap + res.cap +
+                     ss.cap + tab.cap + slot.cap + ub.cap + sout.cap;
     if (v > peak) peak = v;
   }
-  ~PatmScratch() { tgt.release(); rng.release(); meta.release(); flag.release(); cidx.release(); cb.release(); colmap.release(); sl.release(); hl.release(); res.release(); }
+  ~PatmScratch() {
+    tgt.release(); rng.release(); meta.release(); flag.release(); cidx.release(); cb.release(); colmap.release(); sl.release(); hl.release(); res.release();
+    ss.release(); tab.release(); slot.release(); ub.release(); sout.release();
+  }
 };
+
+struct PatmStats { int64_t groups = 0, pairs = 0, scratch = 0, fallback = 0; };
 
 struct PatmCall {                 // what every group of a call shares
   epi_batch *b;
@@ -442,10 +608,163 @@ struct PatmCall {                 // what every group of a call shares
   double min_ctx_freq;
   int64_t cap;
   PatMulti m;                     // tg / pre / ng filled per group
-  epi_pattern_table *out;
+  epi_pattern_table *out;         // the tables, or ...
+  epi_pattern_summary *sum;       // ... the summaries (exactly one of the two is set)
+  unsigned long long key_mask;    // the bits of the hash the summary groups by (EPIHIP_PAT_HASH_BITS)
+  PatmStats *st;
 };
 
-// targets [ta, tb): two passes, three host synchronisations (plus one per further cell batch)
+// capacity of a target's table slice: the power of two >= 2 x its slots, 8 at the least (no slots: no slice)
+int64_t pat_table_capacity(uint32_t npat0) {
+  if (!npat0) return 0;
+  int64_t cap = 8;
+  while (cap < 2 * (int64_t)npat0) cap <<= 1;
+  return cap;
+}
+
+// a summary from nuniq unique rows: fnv / count [nuniq], cells [ncol][nuniq]
+int pat_fill_summary(epi_pattern_summary *out, size_t nuniq, int32_t ncol, const int32_t *cols, const uint64_t *fnv, const int32_t *count,
+                     const int32_t *cells) {
+  if (nuniq == 0) return EPI_OK;
+  out->nuniq = (int64_t)nuniq;
+  out->ncol = ncol;
+  out->positions = (int32_t *)malloc(((size_t)ncol + 1) * 4);
+  out->fnv = (uint64_t *)malloc(nuniq * 8);
+  out->count = (int32_t *)malloc(nuniq * 4);
+  out->cells = (int32_t *)malloc(((size_t)ncol * nuniq + 1) * 4);
+  if (!out->positions || !out->fnv || !out->count || !out->cells) {
+    epi_pattern_summary_free(out);
+    return fail(EPI_ERR_NOMEM, "epi_batch_summarise_patterns_multi: out of host memory");
+  }
+  memcpy(out->positions, cols, (size_t)ncol * 4);
+  memcpy(out->fnv, fnv, nuniq * 8);
+  memcpy(out->count, count, nuniq * 4);
+  memcpy(out->cells, cells, (size_t)ncol * nuniq * 4);
+  int64_t np = 0;
+  for (size_t u = 0; u < nuniq; u++) np += count[u];
+  out->npat = np;
+  return EPI_OK;
+}
+
+// The host's grouping, by (hash, cells) in order of first appearance: the P0 slots of a target (nonempty: null = all are;
+// cells [ncol][P0]).  Exact whatever the hashes are: the summary of a target whose table saw two patterns under one key,
+// and of the targets of the target-by-target path.
+int pat_summarise_host(epi_pattern_summary *out, size_t P0, int32_t ncol, const int32_t *cols, const int32_t *nonempty,
+                       const uint64_t *fnv, const int32_t *cells) {
+  std::unordered_multimap<uint64_t, uint32_t> seen;           // hash -> unique rows that have it
+  std::vector<uint32_t> first;                                // unique row -> its first slot
+  std::vector<int32_t> count;
+  for (size_t c = 0; c < P0; c++) {
+    if (nonempty && !nonempty[c]) continue;
+    auto rng = seen.equal_range(fnv[c]);
+    bool found = false;
+    for (auto it = rng.first; it != rng.second && !found; ++it) {
+      const size_t f = first[it->second];
+      bool same = true;
+      for (int32_t k = 0; k < ncol && same; k++) same = cells[(size_t)k * P0 + c] == cells[(size_t)k * P0 + f];
+      if (same) { count[it->second]++; found = true; }
+    }
+    if (!found) { seen.emplace(fnv[c], (uint32_t)first.size()); first.push_back((uint32_t)c); count.push_back(1); }
+  }
+  const size_t U = first.size();
+  std::vector<uint64_t> ufnv(U);
+  std::vector<int32_t> ucells((size_t)ncol * U + 1);
+  for (size_t u = 0; u < U; u++) {
+    ufnv[u] = fnv[first[u]];
+    for (int32_t k = 0; k < ncol; k++) ucells[(size_t)k * U + u] = cells[(size_t)k * P0 + first[u]];
+  }
+  return pat_fill_summary(out, U, ncol, cols, ufnv.data(), count.data(), ucells.data());
+}
+
+// The summaries of the group's targets [sa, sb), whose Ps slots and C cells pass 2 has just left in `o`: table, verify,
+// scans and emit on the device, then two host synchronisations (the unique counts and collide words; the unique rows) and a
+// third when targets are regrouped on the host (their slots).
+int patm_summarise_batch(PatmCall &c, PatmScratch &w, const std::vector<PatSlice> &sl, const std::vector<PatSumSlice> &ss,
+                         const std::vector<std::vector<int32_t>> &cols, int32_t ta, int32_t sa, int32_t sb, size_t Ps, size_t C,
+                         const PatOut &o) {
+  hipStream_t s = c.s;
+  const int32_t nb = sb - sa;
+  int64_t TE = 0;
+  for (int32_t k = sa; k < sb; k++) TE += pat_table_capacity(sl[(size_t)k].npat0);
+  const bool on_device = Ps < (1u << 30) && C < (1u << 31) && TE < (1LL << 32);    // u32 slot and cell indices
+  std::vector<uint32_t> h_ub(3 * (size_t)nb + 2, 0);          // ubase[nb + 1], wbase[nb + 1], collide[nb]
+  std::vector<uint64_t> h_out;
+  if (on_device) {
+    const int64_t nbs = (int64_t)((Ps + 255) / 256), nbt = (TE + 255) / 256;
+    EPI_TRY(check_grid(nbs, 256, "epi_batch_summarise_patterns_multi"));
+    EPI_TRY(check_grid(nbt, 256, "epi_batch_summarise_patterns_multi"));
+    EPI_TRY(w.tab.ensure((size_t)TE * sizeof(PatEntry)));
+    EPI_TRY(w.slot.ensure(5 * Ps * 4));
+    EPI_TRY(w.ub.ensure(h_ub.size() * 4));
+    EPI_TRY(w.sout.ensure(12 * Ps + 4 * C + 16));
+    w.note();
+    uint32_t *ent = w.slot.as<uint32_t>(), *first = ent + Ps, *wfirst = ent + 2 * Ps, *uidx = ent + 3 * Ps, *widx = ent + 4 * Ps;
+    uint32_t *ubase = w.ub.as<uint32_t>(), *wbase = ubase + nb + 1, *collide = wbase + nb + 1;
+    PatSum q;
+    q.sl = w.sl.as<PatSlice>(); q.ss = w.ss.as<PatSumSlice>(); q.sa = sa; q.sb = sb; q.nslot = (uint32_t)Ps;
+    q.fnv = o.fnv; q.nonempty = o.nonempty; q.cells = o.cells;
+    q.tab = w.tab.as<PatEntry>(); q.ent = ent; q.collide = collide; q.key_mask = c.key_mask;
+    EPI_HIP(hipMemsetAsync(w.ub.p, 0, h_ub.size() * 4, s));
+    prof_begin("summarise_patterns", s);
+    hipLaunchKernelGGL(k_pats_init, dim3((unsigned)nbt), dim3(256), 0, s, q.tab, TE);
+    prof_begin("summarise_patterns_insert", s);
+    hipLaunchKernelGGL(k_pats_insert, dim3((unsigned)nbs), dim3(256), 0, s, q);
+    prof_end("summarise_patterns_insert", s);
+    hipLaunchKernelGGL(k_pats_verify, dim3((unsigned)nbs), dim3(256), 0, s, q, first, wfirst);
+    EPI_TRY(scan_exclusive_u32(first, uidx, (int64_t)Ps, ubase + nb, c.b->scan_tmp, s));
+    EPI_TRY(scan_exclusive_u32(wfirst, widx, (int64_t)Ps, wbase + nb, c.b->scan_tmp, s));
+    hipLaunchKernelGGL(k_pats_bases, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, s, q.sl, sa, nb, q.nslot, uidx, widx, ubase, wbase);
+    hipLaunchKernelGGL(k_pats_emit, dim3((unsigned)nbs), dim3(256), 0, s, q, first, uidx, ubase, wbase, w.sout.as<unsigned long long>());
+    EPI_HIP(hipGetLastError());
+    prof_end("summarise_patterns", s);
+    EPI_HIP(hipMemcpyAsync(h_ub.data(), w.ub.p, h_ub.size() * 4, hipMemcpyDeviceToHost, s));
+    EPI_HIP(hipStreamSynchronize(s));
+    const size_t U = h_ub[(size_t)nb], WC = h_ub[2 * (size_t)nb + 1];
+    if (U > Ps || WC > C) return fail(EPI_ERR_STATE, "epi_batch_summarise_patterns_multi: more unique rows than slots");
+    h_out.resize((12 * U + 4 * WC + 7) / 8 + 1);
+    if (U) {
+      EPI_HIP(hipMemcpyAsync(h_out.data(), w.sout.p, 12 * U + 4 * WC, hipMemcpyDeviceToHost, s));
+      EPI_HIP(hipStreamSynchronize(s));
+    }
+  } else {
+    EPI_HIP(hipStreamSynchronize(s));
+  }
+  const uint32_t *ubase = h_ub.data(), *wbase = ubase + nb + 1, *collide = wbase + nb + 1;
+  const size_t U = ubase[nb];
+  const uint64_t *u_fnv = h_out.data();
+  const int32_t *u_count = reinterpret_cast<const int32_t *>(h_out.data() + U), *u_cells = u_count + U;
+  struct Slots { int32_t k; std::vector<uint64_t> fnv; std::vector<int32_t> nonempty, cells; };
+  std::vector<Slots> back;                                    // the targets the host groups after all, their slots fetched
+  for (int32_t k = sa; k < sb; k++) {
+    const PatSlice &q1 = sl[(size_t)k];
+    if (!q1.npat0) continue;
+    const std::vector<int32_t> &ck = cols[(size_t)k];
+    const int32_t ncol = (int32_t)ck.size();
+    if (on_device && !collide[k - sa]) {
+      EPI_TRY(pat_fill_summary(c.sum + ta + k, ubase[k - sa + 1] - ubase[k - sa], ncol, ck.data(), u_fnv + ubase[k - sa],
+                               u_count + ubase[k - sa], u_cells + wbase[k - sa]));
+      continue;
+    }
+    // two patterns of this target share a key (or the batch is too large for the device's indices)
+    c.st->fallback++;
+    const size_t n0 = q1.npat0;
+    back.emplace_back();
+    Slots &f = back.back();
+    f.k = k; f.fnv.resize(n0); f.nonempty.resize(n0); f.cells.resize((size_t)ncol * n0 + 1);
+    EPI_HIP(hipMemcpyAsync(f.fnv.data(), o.fnv + q1.base_rel, n0 * 8, hipMemcpyDeviceToHost, s));
+    EPI_HIP(hipMemcpyAsync(f.nonempty.data(), o.nonempty + q1.base_rel, n0 * 4, hipMemcpyDeviceToHost, s));
+    if (ncol) EPI_HIP(hipMemcpyAsync(f.cells.data(), o.cells + q1.cell_off, (size_t)ncol * n0 * 4, hipMemcpyDeviceToHost, s));
+  }
+  if (!back.empty()) EPI_HIP(hipStreamSynchronize(s));
+  for (const Slots &f : back) {
+    const std::vector<int32_t> &ck = cols[(size_t)f.k];
+    EPI_TRY(pat_summarise_host(c.sum + ta + f.k, sl[(size_t)f.k].npat0, (int32_t)ck.size(), ck.data(), f.nonempty.data(), f.fnv.data(),
+                               f.cells.data()));
+  }
+  return EPI_OK;
+}
+
+// targets [ta, tb): two passes, three host synchronisations (plus one per further cell batch; the summaries: two per cell batch)
 int patm_group(PatmCall &c, PatmScratch &w, int32_t ta, int32_t tb) {
   epi_batch *b = c.b;
   hipStream_t s = c.s;
@@ -471,7 +790,7 @@ int patm_group(PatmCall &c, PatmScratch &w, int32_t ta, int32_t tb) {
   if (P == 0) return EPI_OK;                                  // no candidate row: every table of the group is empty
   const int64_t nbp = (int64_t)((P + 255) / 256);
   EPI_TRY(check_grid(nbp, 256, "epi_batch_extract_patterns_multi"));
-  b->patm_pairs += (int64_t)P;
+  c.st->pairs += (int64_t)P;
 
   // pass 1: overlap flags and position counts, the flags scanned into pattern slots
   const size_t nbase = ((size_t)ng + 2) & ~(size_t)1;         // base[ng + 1] (padded to an even count), then the counts
@@ -505,23 +824,34 @@ int patm_group(PatmCall &c, PatmScratch &w, int32_t ta, int32_t tb) {
   int32_t *h_hcol = h_hl.data() + H;
   if (H > 0) memcpy(h_hl.data(), c.hlght + hl0, (size_t)H * 4);
   std::vector<PatSlice> sl((size_t)ng);
+  std::vector<PatSumSlice> ss(c.sum ? (size_t)ng : 0);
   std::vector<int32_t> cuts(1, 0);                            // batch i: targets [cuts[i], cuts[i + 1])
-  int64_t bytes = 0, cell_off = 0;
+  int64_t bytes = 0, cell_off = 0, tab_off = 0;
   uint32_t rel = 0;
   for (int32_t k = 0; k < ng; k++) {
     const PatTarget &g = tg[k];
     const uint32_t npat0 = h_base[k + 1] - h_base[k];
     if (npat0) pat_choose_columns(h_cnt + g.win_off, g.nwin, g.pos_lo, npat0, c.min_ctx_freq, h_hl.data() + g.hl_off, g.nhl, cols[(size_t)k],
                                   h_colmap.data() + g.win_off, h_hcol + g.hl_off);
-    const int64_t cells = (int64_t)cols[(size_t)k].size() * npat0, need = 32LL * npat0 + 4 * cells;
-    if (bytes > 0 && bytes + need > c.cap) { cuts.push_back(k); bytes = 0; cell_off = 0; rel = 0; }
+    const int64_t cells = (int64_t)cols[(size_t)k].size() * npat0;
+    int64_t need = 32LL * npat0 + 4 * cells, tcap = 0;
+    if (c.sum) {                                              // + its table slice, 20 B per slot and the unique rows at their most
+      tcap = pat_table_capacity(npat0);
+      need += 16 * tcap + 20LL * npat0 + 12LL * npat0 + 4 * cells;
+    }
+    if (bytes > 0 && bytes + need > c.cap) { cuts.push_back(k); bytes = 0; cell_off = 0; rel = 0; tab_off = 0; }
     sl[(size_t)k].cell_off = cell_off; sl[(size_t)k].base_abs = h_base[k]; sl[(size_t)k].base_rel = rel; sl[(size_t)k].npat0 = npat0; sl[(size_t)k].pad = 0;
-    bytes += need; cell_off += cells; rel += npat0;
+    if (c.sum) { ss[(size_t)k].tab_off = tab_off; ss[(size_t)k].mask = tcap ? (uint32_t)(tcap - 1) : 0u; ss[(size_t)k].ncol = (uint32_t)cols[(size_t)k].size(); }
+    bytes += need; cell_off += cells; rel += npat0; tab_off += tcap;
   }
   cuts.push_back(ng);
   EPI_TRY(w.colmap.ensure((size_t)W * 4));
   EPI_TRY(w.sl.ensure(sl.size() * sizeof(PatSlice)));
   EPI_TRY(w.hl.ensure(h_hl.size() * 4));
+  if (c.sum) {
+    EPI_TRY(w.ss.ensure(ss.size() * sizeof(PatSumSlice)));
+    EPI_HIP(hipMemcpyAsync(w.ss.p, ss.data(), ss.size() * sizeof(PatSumSlice), hipMemcpyHostToDevice, s));
+  }
   EPI_HIP(hipMemcpyAsync(w.colmap.p, h_colmap.data(), (size_t)W * 4, hipMemcpyHostToDevice, s));
   EPI_HIP(hipMemcpyAsync(w.sl.p, sl.data(), sl.size() * sizeof(PatSlice), hipMemcpyHostToDevice, s));
   EPI_HIP(hipMemcpyAsync(w.hl.p, h_hl.data(), h_hl.size() * 4, hipMemcpyHostToDevice, s));
@@ -550,6 +880,10 @@ int patm_group(PatmCall &c, PatmScratch &w, int32_t ta, int32_t tb) {
                        w.cidx.as<uint32_t>(), w.sl.as<PatSlice>(), w.colmap.as<int32_t>(), w.hl.as<int32_t>(), w.hl.as<int32_t>() + H, o);
     EPI_HIP(hipGetLastError());
     prof_end("extract_patterns_multi", s);
+    if (c.sum) {                                              // the slots stay on the device
+      EPI_TRY(patm_summarise_batch(c, w, sl, ss, cols, ta, sa, sb, Ps, C, o));
+      continue;
+    }
     h_res.resize((rbytes + 7) / 8);
     EPI_HIP(hipMemcpyAsync(h_res.data(), w.res.p, rbytes, hipMemcpyDeviceToHost, s));
     EPI_HIP(hipStreamSynchronize(s));
@@ -568,7 +902,7 @@ int patm_group(PatmCall &c, PatmScratch &w, int32_t ta, int32_t tb) {
 
 int patm_run(epi_batch *b, int32_t nt, const int32_t *t_rname, const int32_t *t_start, const int32_t *t_end, int32_t min_overlap,
              const char *ctx, double min_ctx_freq, int32_t clip, int32_t reverse_offset, const int32_t *hlght, const int64_t *hlght_off,
-             void *stream, epi_pattern_table *out) {
+             void *stream, epi_pattern_table *out, epi_pattern_summary *sum, PatmStats &st) {
   EPI_HIP(hipSetDevice(b->eng->device));
   hipStream_t s = pick_stream(b, stream);
   EPI_TRY(fetch_row_stats(b, s));
@@ -577,8 +911,14 @@ int patm_run(epi_batch *b, int32_t nt, const int32_t *t_rname, const int32_t *t_
   auto one_by_one = [&]() {                                   // rows in any order: every target scans the batch
     for (int32_t t = 0; t < nt; t++) {
       const int64_t h0 = hlght_off ? hlght_off[t] : 0, h1 = hlght_off ? hlght_off[t + 1] : 0;
+      epi_pattern_table one;
       EPI_TRY(epi_batch_extract_patterns(b, t_rname[t], t_start[t], t_end[t], min_overlap, ctx, min_ctx_freq, clip, reverse_offset,
-                                         h1 > h0 ? hlght + h0 : nullptr, (int32_t)(h1 - h0), stream, out + t));
+                                         h1 > h0 ? hlght + h0 : nullptr, (int32_t)(h1 - h0), stream, sum ? &one : out + t));
+      if (!sum || !one.npat) continue;                        // the summary of a table: the host's grouping
+      st.fallback++;
+      const int rc = pat_summarise_host(sum + t, (size_t)one.npat, one.ncol, one.positions, nullptr, one.fnv, one.cells);
+      epi_pattern_table_free(&one);
+      EPI_TRY(rc);
     }
     return (int)EPI_OK;
   };
@@ -622,7 +962,9 @@ int patm_run(epi_batch *b, int32_t nt, const int32_t *t_rname, const int32_t *t_
   PatmCall c;
   c.b = b; c.s = s; c.t_rname = t_rname; c.t_start = t_start; c.t_end = t_end;
   c.row_lo = row_lo.data(); c.row_hi = row_hi.data(); c.pos_lo = pos_lo.data(); c.nwin = nwin.data();
-  c.hlght = hlght; c.hlght_off = hlght_off; c.min_ctx_freq = min_ctx_freq; c.out = out;
+  c.hlght = hlght; c.hlght_off = hlght_off; c.min_ctx_freq = min_ctx_freq; c.out = out; c.sum = sum; c.st = &st;
+  const int hb = options().pat_hash_bits;
+  c.key_mask = hb >= 1 && hb <= 63 ? (1ull << hb) - 1ull : ~0ull;
   c.cap = options().pat_group_bytes > 0 ? options().pat_group_bytes : kPatGroupBytes;
   c.m.xm = b->xm; c.m.off = b->off; c.m.len = b->len; c.m.rname = b->rname; c.m.strand = b->strand; c.m.start = b->start;
   c.m.reverse_offset = (uint32_t)reverse_offset; c.m.min_overlap = min_overlap; c.m.clip = clip ? 1 : 0;
@@ -642,11 +984,25 @@ int patm_run(epi_batch *b, int32_t nt, const int32_t *t_rname, const int32_t *t_
       tb++;
     }
     rc = patm_group(c, w, ta, tb);
-    b->patm_groups++;
+    st.groups++;
     ta = tb;
   }
-  if (w.peak > (size_t)b->patm_scratch) b->patm_scratch = (int64_t)w.peak;
+  if (w.peak > (size_t)st.scratch) st.scratch = (int64_t)w.peak;
   return rc;
+}
+
+// the arguments both multi-target entry points take
+int patm_check_args(const char *what, const epi_batch *b, int32_t ntargets, const int32_t *target_rname, const int32_t *target_start,
+                    const int32_t *target_end, const char *ctx, const int32_t *hlght, const int64_t *hlght_off, const void *out) {
+  if (!b || !ctx || ntargets < 0 || (ntargets > 0 && (!target_rname || !target_start || !target_end || !out)))
+    return fail(EPI_ERR_ARG, "%s: bad arguments", what);
+  if (hlght_off) {
+    for (int32_t t = 0; t < ntargets; t++)
+      if (hlght_off[t] < 0 || hlght_off[t + 1] < hlght_off[t] || hlght_off[t + 1] - hlght_off[t] > 0x7FFFFFFF)
+        return fail(EPI_ERR_ARG, "%s: hlght_off is not a CSR offset array", what);
+    if (ntargets > 0 && hlght_off[ntargets] > hlght_off[0] && !hlght) return fail(EPI_ERR_ARG, "%s: hlght is NULL", what);
+  }
+  return EPI_OK;
 }
 
 }  // namespace
@@ -657,23 +1013,48 @@ int epi_batch_extract_patterns_multi(epi_batch *b, int32_t ntargets, const int32
                                      const int32_t *target_end, int32_t min_overlap, const char *ctx, double min_ctx_freq, int32_t clip,
                                      int32_t reverse_offset, const int32_t *hlght, const int64_t *hlght_off, void *stream,
                                      epi_pattern_table *out) {
-  if (!b || !ctx || ntargets < 0 || (ntargets > 0 && (!target_rname || !target_start || !target_end || !out)))
-    return fail(EPI_ERR_ARG, "epi_batch_extract_patterns_multi: bad arguments");
-  if (ntargets > 0) memset(out, 0, (size_t)ntargets * sizeof(*out));
-  if (hlght_off) {
-    for (int32_t t = 0; t < ntargets; t++)
-      if (hlght_off[t] < 0 || hlght_off[t + 1] < hlght_off[t] || hlght_off[t + 1] - hlght_off[t] > 0x7FFFFFFF)
-        return fail(EPI_ERR_ARG, "epi_batch_extract_patterns_multi: hlght_off is not a CSR offset array");
-    if (ntargets > 0 && hlght_off[ntargets] > hlght_off[0] && !hlght)
-      return fail(EPI_ERR_ARG, "epi_batch_extract_patterns_multi: hlght is NULL");
-  }
+  if (ntargets > 0 && out) memset(out, 0, (size_t)ntargets * sizeof(*out));
+  EPI_TRY(patm_check_args("epi_batch_extract_patterns_multi", b, ntargets, target_rname, target_start, target_end, ctx, hlght, hlght_off, out));
   b->patm_groups = 0; b->patm_pairs = 0; b->patm_scratch = 0;
   if (ntargets == 0 || b->n == 0) return EPI_OK;
+  PatmStats st;
   const int rc = patm_run(b, ntargets, target_rname, target_start, target_end, min_overlap, ctx, min_ctx_freq, clip, reverse_offset,
-                          hlght, hlght_off, stream, out);
+                          hlght, hlght_off, stream, out, nullptr, st);
+  b->patm_groups = st.groups; b->patm_pairs = st.pairs; b->patm_scratch = st.scratch;
   if (rc != EPI_OK)
     for (int32_t t = 0; t < ntargets; t++) epi_pattern_table_free(out + t);
   return rc;
+}
+
+void epi_pattern_summary_free(epi_pattern_summary *t) {
+  if (!t) return;
+  free(t->positions); free(t->fnv); free(t->count); free(t->cells);
+  memset(t, 0, sizeof(*t));
+}
+
+int epi_batch_summarise_patterns_multi(epi_batch *b, int32_t ntargets, const int32_t *target_rname, const int32_t *target_start,
+                                       const int32_t *target_end, int32_t min_overlap, const char *ctx, double min_ctx_freq,
+                                       int32_t clip, int32_t reverse_offset, const int32_t *hlght, const int64_t *hlght_off,
+                                       void *stream, epi_pattern_summary *out) {
+  if (ntargets > 0 && out) memset(out, 0, (size_t)ntargets * sizeof(*out));
+  EPI_TRY(patm_check_args("epi_batch_summarise_patterns_multi", b, ntargets, target_rname, target_start, target_end, ctx, hlght, hlght_off, out));
+  b->pats_groups = 0; b->pats_pairs = 0; b->pats_fallback = 0;
+  if (ntargets == 0 || b->n == 0) return EPI_OK;
+  PatmStats st;
+  const int rc = patm_run(b, ntargets, target_rname, target_start, target_end, min_overlap, ctx, min_ctx_freq, clip, reverse_offset,
+                          hlght, hlght_off, stream, nullptr, out, st);
+  b->pats_groups = st.groups; b->pats_pairs = st.pairs; b->pats_fallback = st.fallback;
+  if (rc != EPI_OK)
+    for (int32_t t = 0; t < ntargets; t++) epi_pattern_summary_free(out + t);
+  return rc;
+}
+
+int epi_batch_summarise_patterns_stats(epi_batch *b, int64_t *groups, int64_t *pairs, int64_t *fallback_targets) {
+  if (!b) return fail(EPI_ERR_ARG, "epi_batch_summarise_patterns_stats: batch is NULL");
+  if (groups) *groups = b->pats_groups;
+  if (pairs) *pairs = b->pats_pairs;
+  if (fallback_targets) *fallback_targets = b->pats_fallback;
+  return EPI_OK;
 }
 
 int epi_batch_extract_patterns_multi_stats(epi_batch *b, int64_t *groups, int64_t *pairs, int64_t *scratch_bytes) {

@@ -466,6 +466,42 @@ int epi_batch_extract_patterns_multi(epi_batch *b, int32_t ntargets, const int32
  * candidate row) pairs, peak device scratch in bytes.  Any pointer may be NULL. */
 int epi_batch_extract_patterns_multi_stats(epi_batch *b, int64_t *groups, int64_t *pairs, int64_t *scratch_bytes);
 
+/* The unique patterns of every target with their counts: what plotPatterns makes of extractPatterns' table before it
+ * draws, patterns[, .(count=.N), by=c("pattern", base.positions)] (R/plotPatterns.R:170-172).  With P the table
+ * epi_batch_extract_patterns returns for target t and the same arguments, out[t] holds the unique rows of P by (fnv, every
+ * cell) in the order of their first appearance in P: fnv, count, cells[col * nuniq + u]; npat = P's rows = the sum of the
+ * counts.  Strand, start, end and nbase are not part of the key and are not returned.  Library-owned, released with
+ * epi_pattern_summary_free; on any failure every out[t] is left zeroed and freed.  nuniq = 0: P is empty.
+ * The rows are grouped on the device, behind the second pass of epi_batch_extract_patterns_multi (same arguments, same
+ * groups of targets): one open-addressing table per batch of results, every target a slice of a power-of-two capacity
+ * >= 2 x its overlapping rows, keyed by the hash; a wave adds once per distinct key among its lanes.  Every row is then
+ * compared, cell by cell, with the first row of its table entry.  A target in which two different patterns met under one
+ * key is grouped on the host instead, by (fnv, cells), from its per-row results: the result never rests on the hash.
+ * So are the targets of the target-by-target path (rows in another order, negative coordinates).
+ * Transfer: 12 B + 4 B per column for every UNIQUE pattern, plus 12 B per target; nothing per row.
+ * Memory: as epi_batch_extract_patterns_multi, and inside the same cap: a batch of results counts 16 B per table entry
+ * (at most 4 x the overlapping rows + 8 per target), 20 B per overlapping row and its unique rows at their most (12 B per
+ * overlapping row + 4 B per cell) on top of that call's 32 B per overlapping row + 4 B per cell.  The device indexes slots,
+ * cells and table entries with 32 bits: a batch of results with 2^30 overlapping rows, 2^31 cells or 2^32 table entries or
+ * more (one target far above the cap) is grouped on the host, its targets counted as such.  Synchronises `stream`. */
+typedef struct {
+  int64_t nuniq, npat;
+  int32_t ncol;
+  int32_t *positions;                       /* [ncol] */
+  uint64_t *fnv;                            /* [nuniq] */
+  int32_t *count;                           /* [nuniq] */
+  int32_t *cells;                           /* [ncol][nuniq] */
+} epi_pattern_summary;
+void epi_pattern_summary_free(epi_pattern_summary *t);
+int epi_batch_summarise_patterns_multi(epi_batch *b, int32_t ntargets, const int32_t *target_rname,
+                                       const int32_t *target_start, const int32_t *target_end, int32_t min_overlap,
+                                       const char *ctx, double min_ctx_freq, int32_t clip, int32_t reverse_offset,
+                                       const int32_t *hlght, const int64_t *hlght_off /* [ntargets+1] CSR, may be NULL */,
+                                       void *stream, epi_pattern_summary *out /* [ntargets] */);
+/* Of the last epi_batch_summarise_patterns_multi on this batch: groups run (0: the target-by-target path), (target,
+ * candidate row) pairs, targets that were grouped on the host.  Any pointer may be NULL. */
+int epi_batch_summarise_patterns_stats(epi_batch *b, int64_t *groups, int64_t *pairs, int64_t *fallback_targets);
+
 /* rcpp_get_base_freqs on a resident batch (see epi_get_base_freqs): d_site_chr / d_site_pos are nsite device int32
  * (rname codes, 1-based positions) sorted by (code, pos), NA-coded sites removed -- equal keys (multi-ALT records) are
  * allowed; EPI_ERR_UNSORTED otherwise, or when the rows are not sorted by (rname, start).  d_counts [20][nsite] u32 is
