@@ -224,11 +224,11 @@ def test_genome_path_accepted(tmp_path):
 CONTIGS = (("chrA", 20000), ("chrB", 700), ("chrC", 64))
 
 
-def write_genome(path, rng):
+def write_genome(path, rng, contigs=CONTIGS):
     """Lower case, N runs and IUPAC codes in the genome, wrapped at 60."""
     seqs = {}
     with open(path, "w") as f:
-        for name, ln in CONTIGS:
+        for name, ln in contigs:
             s = [rng.choice("ACGTACGTACGTacgtNRYKMSWn") for _ in range(ln)]
             for k in range(0, ln, 97):                               # CpG-rich stretches so every context occurs
                 s[k:k + 4] = list("CGCG")[:max(0, min(4, ln - k))]
@@ -271,12 +271,12 @@ def random_read(rng, contig_len, qlen_target, pos=None, end_gap=None, all_ops=Tr
     return pos + 1, ops, seq
 
 
-def synth_records(rng, tag, n, long_reads=False):
+def synth_records(rng, tag, n, long_reads=False, contigs=CONTIGS):
     vals = {"XG": ("CT", "GA"), "YD": ("f", "r"), "ZS": ("++", "+-", "-+", "--")}[tag]
     recs = []
     for k in range(n):
-        tid = rng.randrange(len(CONTIGS))
-        clen = CONTIGS[tid][1]
+        tid = rng.randrange(len(contigs))
+        clen = contigs[tid][1]
         pos = end_gap = None
         if k % 17 == 0:
             pos = k % 2                                                 # reads at contig positions 0 and 1
@@ -296,7 +296,7 @@ def synth_records(rng, tag, n, long_reads=False):
         recs.append(r)
     if long_reads:
         for k, ln in enumerate((1500, 10000, 10000)):
-            p, cigar, seq = random_read(rng, CONTIGS[0][1], ln, all_ops=(k != 2))
+            p, cigar, seq = random_read(rng, contigs[0][1], ln, all_ops=(k != 2))
             recs.append({"seq": seq, "pos": p, "cigar": cigar, "tid": 0, "qname": "long%d" % k,
                          "tags": {tag: vals[k % len(vals)]}})
     return recs
@@ -339,6 +339,37 @@ def test_synthetic_windows(synth_genome, tmp_path):
     out1 = str(tmp_path / "out1.bam")
     assert ea.callMethylation(src, out1, g, nthreads=1, verbose=False) == res
     assert inflate(out1) == inflate(out)
+
+
+MANY_CONTIGS = tuple(("contig_%05d_thirty_characters" % i, 64) for i in range(3000))
+
+
+def many_contigs_input(tmp_path):
+    """(fasta, genome, BAM): 3000 reference sequences, so the BAM header is far longer than a BGZF block, and 200
+    single-end records over them."""
+    assert all(len(name) == 30 for name, _ in MANY_CONTIGS)
+    rng = random.Random(3000)
+    fa = str(tmp_path / "many.fa")
+    write_genome(fa, rng, MANY_CONTIGS)
+    recs = synth_records(rng, "YD", 200, contigs=MANY_CONTIGS)
+    for r in recs:
+        r["flag"] = (r["flag"] & 4) | rng.choice((0, 16))
+    src = write_bam(str(tmp_path / "many.bam"), recs, refs=MANY_CONTIGS)
+    assert len(inflate(src)) > 3 * 65536
+    return fa, ea.preprocessGenome(fa, verbose=False), src
+
+
+def test_header_longer_than_a_window(tmp_path):
+    """window_kib = 1: a window is one BGZF block, so the reader reads on over several before the header is complete;
+    the header is then written out verbatim."""
+    fa, g, src = many_contigs_input(tmp_path)
+    out = str(tmp_path / "out.bam")
+    res = ea.callMethylation(src, out, g, nthreads=2, verbose=False, window_kib=1)
+    assert_parity(src, out, fa, res)
+    assert 0 < res["ncalled"] < res["nrecs"] == 200
+    whole = str(tmp_path / "whole.bam")
+    assert ea.callMethylation(src, whole, g, nthreads=2, verbose=False) == res
+    assert inflate(whole) == inflate(out)
 
 
 def test_output_is_bgzf(synth_genome, tmp_path):

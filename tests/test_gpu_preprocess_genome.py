@@ -16,7 +16,7 @@ import pytest
 
 import epialleler_amd as ea
 from helpers import GOLDEN, write_bam
-from test_gpu_call_methylation import CONTIGS, EXPECTED, random_read, synth_records, write_genome
+from test_gpu_call_methylation import CONTIGS, EXPECTED, many_contigs_input, random_read, synth_records, write_genome
 
 pytestmark = pytest.mark.gpu
 
@@ -269,6 +269,15 @@ def test_contract_synthetic(tag, layout, synth_genome, tmp_path):
         assert got is not None and got.n > 0
         assert got.paired == (layout == "pe")
         assert 0 < got.ncalled < got.nrecs == len(recs)
+
+
+def test_contract_header_longer_than_a_window(tmp_path):
+    """The header of 3000 reference sequences spans several one-block windows, for both sides of the contract."""
+    _, g, src = many_contigs_input(tmp_path)
+    got = check_contract(src, g, tmp_path, {"window_kib": 1})
+    assert got is not None and got.n > 0 and not got.paired and len(got.levels) == 3000
+    assert 0 < got.ncalled < got.nrecs == 200
+    assert_same_templates(got, ea.preprocessBam(src, genome=g))
 
 
 # ---- 4. errors -----------------------------------------------------------------------------------------------------

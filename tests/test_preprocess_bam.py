@@ -179,6 +179,45 @@ def test_malformed_pairs_and_truncation(ea, tmp_path):
     assert "truncated BAM record" in str(ei.value)
 
 
+def _same_table(a, b):
+    for k in ("xm", "off", "rname", "strand", "start"):
+        assert np.array_equal(a.host[k], b.host[k]), k
+    assert list(a.levels) == list(b.levels) and a.nrecs == b.nrecs and a.paired == b.paired
+
+
+def test_header_longer_than_a_window(ea, tmp_path):
+    """3000 reference names: the header is over 65536 bytes, so it crosses a BGZF block and, at window_kib = 1 (a window
+    is one block), the reader has to read on before it has the whole header."""
+    refs = tuple(("contig_%05d_with_a_long_name" % i, 100000) for i in range(3000))
+    recs = [_rec(qname=b"h%02d\0" % i, pos=10 + i, tid=0 if i % 2 == 0 else 2999) for i in range(50)]
+    path = _raw_bam(tmp_path / "hdr.bam", recs, refs=refs)
+    whole = ea.preprocessBam(path)
+    piecewise = ea.preprocessBam(path, window_kib=1)
+    _same_table(whole, piecewise)
+    assert whole.n == 50 and len(whole.levels) == 3000 and list(whole.levels) == [nm for nm, _ in refs]
+    assert sorted(set(whole.host["rname"].tolist())) == [1, 3000]
+
+
+def test_template_larger_than_the_window(ea, tmp_path):
+    """A name-sorted pair of two 70000-base mates between small pairs: at window_kib = 1 neither mate fits a window, and
+    the first waits for the second over several of them."""
+    def pair(q, pos, n=8, xm=b"z..Z.h.x"):
+        return [_rec(qname=q, flag=99, pos=pos, mpos=pos, tlen=n, l_seq=n, cigar=((0, n),), xm=xm),
+                _rec(qname=q, flag=147, pos=pos, mpos=pos, tlen=-n, l_seq=n, cigar=((0, n),), xm=xm)]
+    recs = []
+    for i in range(600):
+        recs += pair(b"a%04d\0" % i, 100 + i)
+    recs += pair(b"big\0", 200, 70000, b"z" * 70000)
+    for i in range(100):
+        recs += pair(b"c%04d\0" % i, 900 + i)
+    path = _raw_bam(tmp_path / "big.bam", recs)
+    whole = ea.preprocessBam(path)
+    piecewise = ea.preprocessBam(path, window_kib=1, nthreads=3)
+    _same_table(whole, piecewise)
+    assert whole.n == 701 and whole.nrecs == 1402 and whole.paired
+    assert int(np.diff(whole.host["off"]).max()) == 70000
+
+
 def test_threads_give_the_same_table_on_a_generated_bam(tmp_path):
     """150 k templates (enough for the threaded range sort + pairwise merges and several packing segments): one thread
     and eight threads, whole file and 4 MiB windows, must produce the same sorted table byte for byte."""
