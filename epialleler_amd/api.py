@@ -399,6 +399,39 @@ def rcpp_mhl_report(df, ctx, hmax, hmin, max_ooctx_meth_frac, as_device=False):
     return Report(dict(zip(names, cols)), bam.levels)
 
 
+def rcpp_heterogeneity_report(df, ctx, k, max_ooctx_meth_frac, min_reads=1, max_window_span=0, as_device=False,
+                              with_counts=False):
+    """Per window of k neighbouring sites of the un-thresholded cytosine report (include/epihip.h,
+    epi_batch_heterogeneity_report_dev): rname, strand, pos, end, context, nreads, npatterns (int32), beta, epipolymorphism,
+    entropy, pdr (float64).  ctx: context letters in both cases, as for rcpp_mhl_report.  with_counts: the Report's
+    `counts` attribute holds the [nrow, 2^k] int32 pattern histogram of the reported windows."""
+    torch = _torch()
+    lib = _lib.load()
+    bam = _as_bam(df)
+    b = bam.batch()
+    dev = "cuda:%d" % bam.device
+    nrow = C.c_int64(0)
+    _lib.check(lib.epi_batch_heterogeneity_report_dev(b, _lib.enc(ctx), int(k), float(max_ooctx_meth_frac), int(min_reads),
+                                                      int(max_window_span), _stream(bam.device), C.byref(nrow)))
+    n = nrow.value
+    icols = list(torch.empty((7, n), dtype=torch.int32, device=dev).unbind(0))
+    dcols = list(torch.empty((4, n), dtype=torch.float64, device=dev).unbind(0))
+    counts = torch.empty((n, 1 << int(k)), dtype=torch.int32, device=dev) if with_counts else None
+    if n:
+        _lib.check(lib.epi_batch_heterogeneity_fetch_dev(b, _ptr_array(icols), _ptr_array(dcols),
+                                                         C.c_void_p(counts.data_ptr()) if with_counts else None,
+                                                         _stream(bam.device)))
+    cols = icols + dcols
+    if not as_device:
+        cols = [c.cpu().numpy() for c in cols]
+        counts = counts.cpu().numpy() if with_counts else None
+    names = ("rname", "strand", "pos", "end", "context", "nreads", "npatterns", "beta", "epipolymorphism", "entropy", "pdr")
+    rep = Report(dict(zip(names, cols)), bam.levels)
+    if with_counts:
+        rep.counts = counts
+    return rep
+
+
 PATTERN_LEVELS = ("NA1", "H", "A", "C", "NA5", "X", "Z", "NA8", "NA9", "h", "G", "T", "N", "x", "z", "NA16")   # :192-195
 NA_INTEGER = -2 ** 31
 
@@ -558,6 +591,26 @@ def generateMhlReport(bam, report_file=None, haplotype_context=None, max_haploty
     c = CONTEXT_TO_BASES[haplotype_context]
     rep = rcpp_mhl_report(bam, c["ctx_meth"] + c["ctx_unmeth"], max_haplotype_window, min_haplotype_length,
                           max_outofcontext_beta, as_device=as_device)
+    if report_file is None:
+        return rep
+    writeReport(rep, report_file, gzip)
+    return None
+
+
+def generateHeterogeneityReport(bam, report_file=None, window_context=None, window_sites=4, min_reads=1, max_window_span=0,
+                                max_outofcontext_beta=0.1, gzip=False, verbose=False, as_device=False, **preprocess_args):
+    """Within-sample heterogeneity per window of `window_sites` (2 to 6) neighbouring cytosines of `window_context`:
+    epipolymorphism, methylation entropy and the fraction of discordant reads, with the window's read count, pattern
+    count and beta.  The sites are those of generateCytosineReport(threshold_reads=False, report_context=window_context),
+    the reads those generateMhlReport keeps under max_outofcontext_beta; windows with fewer than min_reads reads, or
+    (max_window_span > 0) spanning more than max_window_span bases, are left out.  The reference has no such report."""
+    window_context = _match_arg(window_context, _CTX_CHOICES, "window.context")
+    if isinstance(window_sites, bool) or int(window_sites) != window_sites or not 2 <= int(window_sites) <= 6:
+        raise ValueError("'window.sites' should be an integer from 2 to 6")
+    bam = preprocessBam(bam, **preprocess_args)
+    c = CONTEXT_TO_BASES[window_context]
+    rep = rcpp_heterogeneity_report(bam, c["ctx_meth"] + c["ctx_unmeth"], int(window_sites), max_outofcontext_beta,
+                                    min_reads, max_window_span, as_device=as_device)
     if report_file is None:
         return rep
     writeReport(rep, report_file, gzip)

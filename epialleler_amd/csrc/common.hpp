@@ -155,6 +155,7 @@ enum ReportKind {
   KIND_CX_SHARED = 3,       // first half of a sharded CX report
   KIND_MHL_SHARED = 4,      // ... of a sharded lMHL report, two-kernel path (slabs in k_mhl_tiles' layout)
   KIND_MHLF_SHARED = 5,     // ... of a sharded lMHL report, one-pass kernel (slabs in its layout, mhl_common.hpp)
+  KIND_HET = 6,             // finished heterogeneity report
 };
 }  // namespace epi
 
@@ -226,6 +227,13 @@ struct epi_batch {
   int32_t thr_tab_len = -1;
   epi::ThrParams thr_tab_prm = {0, 0.0, 0.0};
   size_t pool_cap2 = 0;     // rows that fit pool_d/pool_e (lMHL doubles)
+  // heterogeneity report (heterogeneity.hip): its own copy of the site table (the CX report's six columns), the '+' rank of
+  // every site, the per-strand search table (key, context), the pattern counters [site][2^k], the keep flags and output
+  // rows of the windows, two scalars ('+' sites, reported rows); and what the fetch needs to know of the last report
+  epi::DevBuf het_cx, het_rank, het_flag, het_key, het_sctx, het_counts, het_out, het_scal;
+  int64_t het_nsite = 0, het_max_span = 0;
+  int32_t het_k = 0;
+  uint32_t het_min_reads = 1;
 
   // state of the last report (for fetch)
   epi::ReportKind last_kind = epi::KIND_NONE;

@@ -1,0 +1,400 @@
+// Heterogeneity report: epiallele entropy, epipolymorphism and the fraction of discordant reads per window of k
+// neighbouring sites (include/epihip.h, epi_batch_heterogeneity_report_dev, has the definitions).  No reference interface
+// is replaced; the report composes two reference rules: the site table is rcpp_cx_report with an all-TRUE pass vector
+// (src/rcpp_cx_report.cpp:58-80, the majority rule) and the rows that count are those the read rule of rcpp_mhl_report
+// keeps (src/rcpp_mhl_report.cpp:172-179, hmin = 0).
+//
+// Data path, all on the report's stream:
+//  (a) the un-thresholded CX report of the batch, fetched into het_cx (six columns of N rows, in (rname, pos, strand)
+//      order).  A scan over "strand is +" gives every row its ordinal in a table split per strand: '+' sites at
+//      [0, n1), '-' sites at [n1, N), each sorted by (rname, pos).  k_het_sites writes that table: a 64-bit key
+//      (rname << 32) + (pos + 2^31) to search in, and the site's context code.
+//  (b) k_het_count: a group of G lanes (16, or 64 for long rows) takes a row.  It reads the row once for the read rule,
+//      finds its site range [lo, hi) by a (G + 1)-ary search, and walks it G sites at a time: every lane loads the one byte at
+//      its site, two ballots give the group's valid and methylated masks, the lane of the LAST site of a window takes
+//      the k bits that end at it (the previous round's last k - 1 bits carried over) and, when all k are valid, adds 1
+//      to counts[first site of the window][pattern].  Windows never leave the row's (rname, strand): [lo, hi) does not.
+//  (c) k_het_keep (a thread per CX row = per window start): n, min_reads, the span cap -> a flag; util.hip's scan turns
+//      the flags into output rows; k_het_emit (at fetch) computes the metrics into the caller's columns.  The bin sums
+//      run over the bins in ascending order inside one thread: no launch shape enters the result.
+//
+// Contention.  Rows arrive sorted by (rname, start): on a deep amplicon the rows of a wave share their windows and mostly
+// their pattern.  With 16-lane groups the four rows of a wave walk the same sites when they start together, so lane j
+// of every group then holds the same counter: the lanes compare their counter index with the three lanes j + 16 m
+// and the lowest of a set adds the set's size.  EPI_HET_PER_LANE (make timing-het) adds 1 per lane instead;
+// profiles/heterogeneity_report.txt has both on the two workloads.
+#include "common.hpp"
+#include <string.h>
+
+namespace epi {
+
+constexpr int HET_WG = 256;
+constexpr int kHetMinK = 2, kHetMaxK = 6;
+constexpr int64_t kHetCountsCap = 4LL << 30;          // bytes of counters (nsites * 2^k * 4) a report may allocate
+constexpr int64_t kHetLongRow = 512;                  // mean row bytes above which a whole wave takes a row
+
+struct HetArgs {
+  const uint8_t *xm;
+  const int64_t *off;
+  const int32_t *len, *rname, *strand, *start;
+  int64_t n;
+  const unsigned long long *key;      // [N] per-strand site table
+  const uint8_t *sctx;                // [N] context code of the site (2 CHH, 6 CHG, 7 CG)
+  const uint32_t *n1;                 // '+' sites
+  uint32_t N;
+  int32_t k;
+  uint32_t oom_mask, oou_mask;        // out-of-context methylated / unmethylated nibble codes (those not in the context)
+  double max_oo;
+  uint32_t *counts;                   // [N << k]
+};
+
+__device__ __forceinline__ unsigned long long het_key(int32_t rname, int64_t pos) {
+  return ((unsigned long long)(uint32_t)rname << 32) + (unsigned long long)(pos + kPosBias);
+}
+
+// First index in [a, b) whose key is >= key, searched by the G lanes of a group at once: the lanes probe G evenly spaced
+// entries, the ballot of "below the key" (ones, then zeros: the table is sorted) picks one of the G + 1 parts, and a part of
+// at most G entries is probed whole.  log_{G+1} dependent loads instead of log_2: 6 instead of 22 for 3.5 M sites and 16
+// lanes, and the loads are what the kernel waits for.  Every lane of the wave calls this together; the lanes of a group pass
+// the same a, b and key (a = b: nothing to search).
+template <int G>
+__device__ __forceinline__ uint32_t het_lower_bound(const unsigned long long *__restrict__ keys, uint32_t a, uint32_t b,
+                                                    unsigned long long key, uint32_t sub, uint32_t grp) {
+  const unsigned long long gmask = G == 64 ? ~0ull : ((1ull << (G % 64)) - 1ull);
+  while (__ballot(a < b) != 0ull) {
+    const uint32_t span = b - a;
+    const bool last = span <= (uint32_t)G;
+    const uint32_t m = last ? a + sub : a + (uint32_t)(((uint64_t)span * (sub + 1u)) / (uint32_t)(G + 1));
+    const bool below = m < b && keys[m] < key;
+    const uint32_t cnt = (uint32_t)__popcll((__ballot(below) >> (grp * G)) & gmask);
+    if (last) {
+      a = b = a + cnt;
+    } else {
+      const uint32_t na = cnt > 0u ? a + (uint32_t)(((uint64_t)span * cnt) / (uint32_t)(G + 1)) + 1u : a;
+      const uint32_t nb = cnt < (uint32_t)G ? a + (uint32_t)(((uint64_t)span * (cnt + 1u)) / (uint32_t)(G + 1)) : b;
+      a = na; b = nb;
+    }
+  }
+  return a;
+}
+
+__global__ __launch_bounds__(HET_WG) void k_het_strand_flag(const int32_t *__restrict__ strand, uint32_t N, uint32_t *__restrict__ flag) {
+  const uint32_t i = blockIdx.x * (uint32_t)HET_WG + threadIdx.x;
+  if (i < N) flag[i] = strand[i] == 1 ? 1u : 0u;
+}
+
+// ordinal of CX row i in the per-strand table (rank: '+' rows in front of it)
+__device__ __forceinline__ uint32_t het_ordinal(int32_t strand, uint32_t i, uint32_t rank, uint32_t n1) {
+  return strand == 1 ? rank : n1 + (i - rank);
+}
+
+__global__ __launch_bounds__(HET_WG) void k_het_sites(const int32_t *__restrict__ rname, const int32_t *__restrict__ strand,
+                                                      const int32_t *__restrict__ pos, const int32_t *__restrict__ context,
+                                                      const uint32_t *__restrict__ rank, const uint32_t *__restrict__ n1p, uint32_t N,
+                                                      unsigned long long *__restrict__ key, uint8_t *__restrict__ sctx) {
+  const uint32_t i = blockIdx.x * (uint32_t)HET_WG + threadIdx.x;
+  if (i >= N) return;
+  const uint32_t g = het_ordinal(strand[i], i, rank[i], *n1p);
+  if (g >= N) return;
+  key[g] = het_key(rname[i], pos[i]);
+  sctx[g] = (uint8_t)context[i];
+}
+
+template <int G>
+__global__ __launch_bounds__(HET_WG) void k_het_count(HetArgs a) {
+  constexpr int GPW = 64 / G;                                // groups per wave
+  const uint32_t lane = threadIdx.x & 63u, sub = lane % G, grp = lane / G;
+  const int64_t row = ((int64_t)blockIdx.x * (HET_WG / 64) + (threadIdx.x >> 6)) * GPW + grp;
+  const bool have = row < a.n;
+  const int32_t st = have ? a.strand[row] : 0;
+  const int32_t len = have && (st == 1 || st == 2) ? a.len[row] : 0;
+  const int64_t off = have ? a.off[row] : 0;
+  const int32_t start = have ? a.start[row] : 0;
+  const uint8_t *__restrict__ p = a.xm + off;
+
+  // the read rule (rcpp_mhl_report.cpp:172-179, hmin = 0): four bytes per lane and step
+  uint32_t om = 0, ou = 0;
+  for (int32_t c = (int32_t)sub * 4; c < len; c += G * 4) {
+    uint32_t w = 0x0C0C0C0Cu;                                // '.': in neither class
+    if (c + 4 <= len) memcpy(&w, p + c, 4);
+    else for (int32_t j = 0; c + j < len; j++) w = (w & ~(0xFFu << (8 * j))) | ((uint32_t)p[c + j] << (8 * j));
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const uint32_t nib = (w >> (8 * j)) & 15u;
+      om += (a.oom_mask >> nib) & 1u;
+      ou += (a.oou_mask >> nib) & 1u;
+    }
+  }
+#pragma unroll
+  for (int d = 1; d < G; d <<= 1) { om += __shfl_xor(om, d, 64); ou += __shfl_xor(ou, d, 64); }
+  const double frac = (double)om / (double)((uint64_t)om + ou);       // :178 (0 / 0 = NaN: kept)
+  const bool keep = len > 0 && !(frac > a.max_oo);
+
+  // the row's sites: [lo, hi) of its strand's part of the table
+  uint32_t lo = 0, hi = 0;
+  {
+    const uint32_t n1 = *a.n1;
+    const uint32_t s0 = st == 1 ? 0u : n1, s1 = st == 1 ? n1 : a.N;
+    const int32_t rn = keep ? a.rname[row] : 0;
+    lo = het_lower_bound<G>(a.key, keep ? s0 : 0u, keep ? s1 : 0u, het_key(rn, (int64_t)start), sub, grp);
+    const uint32_t cap = (uint64_t)lo + (uint32_t)len < s1 ? lo + (uint32_t)len : s1;   // at most one site per position
+    hi = het_lower_bound<G>(a.key, keep ? lo : 0u, keep ? cap : 0u, het_key(rn, (int64_t)start + len), sub, grp);
+  }
+
+  const int k = a.k;
+  const unsigned long long gmask = G == 64 ? ~0ull : ((1ull << (G % 64)) - 1ull);
+  const uint32_t full = (1u << k) - 1u;
+  unsigned long long carry_v = 0, carry_m = 0;               // the k - 1 sites in front of this round, oldest at bit 0
+  for (uint32_t base = lo; __ballot(base < hi) != 0ull; base += G) {
+    const uint32_t g = base + sub;
+    bool valid = false, meth = false;
+    if (g < hi) {
+      const int32_t pos = (int32_t)(uint32_t)((a.key[g] & 0xFFFFFFFFull) - (unsigned long long)kPosBias);
+      const uint32_t nib = p[pos - start] & 15u;             // start <= pos < start + len: the search's bounds
+      valid = (nib & 7u) == a.sctx[g];
+      meth = valid && nib < 8u;
+    }
+    const unsigned long long sv = (__ballot(valid) >> (grp * G)) & gmask, sm = (__ballot(meth) >> (grp * G)) & gmask;
+    // the k sites that end at this lane's: from this round, and from the carry for the first k - 1 lanes
+    const int back = k - 1;
+    unsigned long long wv, wm;
+    if ((int)sub >= back) { wv = sv >> (sub - back); wm = sm >> (sub - back); }
+    else { wv = (sv << (back - sub)) | (carry_v >> sub); wm = (sm << (back - sub)) | (carry_m >> sub); }
+    const bool covered = ((uint32_t)wv & full) == full && g < hi;
+    const uint32_t idx = covered ? ((g - (uint32_t)back) << k) | ((uint32_t)wm & full) : 0xFFFFFFFFu;
+#if defined(EPI_HET_PER_LANE)
+    if (covered) atomicAdd(&a.counts[idx], 1u);
+#else
+    if (G < 64) {
+      // rows of one wave that walk the same sites hold the same counter in lane `sub` of their groups
+      uint32_t same = 1u;
+      bool first = true;
+#pragma unroll
+      for (int m = 1; m < GPW; m++) {
+        const uint32_t other = __shfl(idx, (int)((lane + m * G) & 63u), 64);
+        const bool below = ((lane + m * G) & 63u) < lane;
+        if (other == idx) { same++; if (below) first = false; }
+      }
+      if (covered && first) atomicAdd(&a.counts[idx], same);
+    } else {
+      if (covered) atomicAdd(&a.counts[idx], 1u);
+    }
+#endif
+    carry_v = (sv >> (G - back)) & ((1ull << back) - 1ull);
+    carry_m = (sm >> (G - back)) & ((1ull << back) - 1ull);
+  }
+}
+
+struct HetFinish {
+  const int32_t *rname, *strand, *pos, *context;   // the CX table
+  const uint32_t *rank, *n1;
+  const unsigned long long *key;
+  const uint32_t *counts;
+  uint32_t N;
+  int32_t k;
+  uint32_t min_reads;
+  int64_t max_span;
+};
+
+// the window that starts at CX row i: its counters, or null when fewer than k sites follow on its (rname, strand)
+__device__ __forceinline__ const uint32_t *het_window(const HetFinish &f, uint32_t i, int32_t *end) {
+  const int32_t st = f.strand[i];
+  const uint32_t n1 = *f.n1;
+  const uint32_t g = het_ordinal(st, i, f.rank[i], n1), seg_end = st == 1 ? n1 : f.N;
+  const uint32_t last = g + (uint32_t)f.k - 1u;
+  if (last >= seg_end) return nullptr;
+  const unsigned long long kl = f.key[last];
+  if ((uint32_t)(kl >> 32) != (uint32_t)f.rname[i]) return nullptr;
+  *end = (int32_t)(uint32_t)((kl & 0xFFFFFFFFull) - (unsigned long long)kPosBias);
+  return f.counts + ((size_t)g << f.k);
+}
+
+__global__ __launch_bounds__(HET_WG) void k_het_keep(HetFinish f, uint32_t *__restrict__ flag) {
+  const uint32_t i = blockIdx.x * (uint32_t)HET_WG + threadIdx.x;
+  if (i >= f.N) return;
+  int32_t end = 0;
+  const uint32_t *c = het_window(f, i, &end);
+  uint32_t keep = 0;
+  if (c) {
+    uint64_t n = 0;
+    for (int b = 0; b < (1 << f.k); b++) n += c[b];
+    const int64_t span = (int64_t)end - (int64_t)f.pos[i] + 1;
+    keep = n >= (uint64_t)f.min_reads && (f.max_span == 0 || span <= f.max_span) ? 1u : 0u;
+  }
+  flag[i] = keep;
+}
+
+struct HetOut {
+  int32_t *rname, *strand, *pos, *end, *context, *nreads, *npatterns;
+  double *beta, *epipoly, *entropy, *pdr;
+  int32_t *counts;                    // [nrow][2^k] or null
+};
+
+__global__ __launch_bounds__(HET_WG) void k_het_emit(HetFinish f, const uint32_t *__restrict__ flag, const uint32_t *__restrict__ out_off,
+                                                     HetOut o) {
+  const uint32_t i = blockIdx.x * (uint32_t)HET_WG + threadIdx.x;
+  if (i >= f.N || !flag[i]) return;
+  int32_t end = 0;
+  const uint32_t *c = het_window(f, i, &end);
+  if (!c) return;
+  const int nb = 1 << f.k;
+  const uint32_t r = out_off[i];
+  uint64_t n = 0, nmeth = 0;
+  int32_t npat = 0;
+  for (int b = 0; b < nb; b++) { const uint32_t v = c[b]; n += v; nmeth += (uint64_t)v * (uint32_t)__popc(b); npat += v ? 1 : 0; }
+  const double dn = (double)n;
+  double sq = 0.0, ent = 0.0;
+  for (int b = 0; b < nb; b++) {                              // ascending bins
+    const uint32_t v = c[b];
+    if (o.counts) o.counts[(size_t)r * nb + b] = (int32_t)v;
+    if (!v) continue;
+    const double pb = (double)v / dn;
+    sq += pb * pb;
+    ent += pb * log2(pb);
+  }
+  o.rname[r] = f.rname[i]; o.strand[r] = f.strand[i]; o.pos[r] = f.pos[i]; o.end[r] = end; o.context[r] = f.context[i];
+  o.nreads[r] = (int32_t)n; o.npatterns[r] = npat;
+  o.beta[r] = (double)nmeth / (dn * (double)f.k);
+  o.epipoly[r] = 1.0 - sq;
+  o.entropy[r] = -ent / (double)f.k;
+  o.pdr[r] = 1.0 - (double)((uint64_t)c[0] + c[nb - 1]) / dn;
+}
+
+static void het_finish_args(const epi_batch *b, HetFinish &f) {
+  const int32_t *cx = b->het_cx.as<int32_t>();
+  const size_t N = (size_t)b->het_nsite;
+  f.rname = cx; f.strand = cx + N; f.pos = cx + 2 * N; f.context = cx + 3 * N;
+  f.rank = b->het_rank.as<uint32_t>();
+  f.n1 = b->het_scal.as<uint32_t>();
+  f.key = b->het_key.as<unsigned long long>();
+  f.counts = b->het_counts.as<uint32_t>();
+  f.N = (uint32_t)N;
+  f.k = b->het_k;
+  f.min_reads = b->het_min_reads;
+  f.max_span = b->het_max_span;
+}
+
+static int het_report(epi_batch *b, const char *ctx, int k, double max_oo, int32_t min_reads, int32_t max_span, hipStream_t s,
+                      int64_t *nrow_out) {
+  // (a) the site table: the un-thresholded CX report of the reported context(s), methylated letters only as in
+  //     generateCytosineReport (the table has a row per position whose majority is one of them, either case)
+  char rep_ctx[8];
+  int nrep = 0;
+  uint32_t ctx_mask = ctx_mask_of(ctx);
+  for (const char *c = "HXZ"; *c; c++)
+    if (ctx_mask & ((1u << ctx_to_idx((unsigned char)*c)) | (1u << (ctx_to_idx((unsigned char)*c) + 8)))) rep_ctx[nrep++] = *c;
+  rep_ctx[nrep] = 0;
+  int64_t nsite = 0;
+  EPI_TRY(epi_batch_cx_report_dev(b, nullptr, rep_ctx, s, &nsite));
+  const bool whole = b->last_kind == KIND_CX;
+  b->last_kind = KIND_NONE;
+  if (!whole)
+    return fail(EPI_ERR_STATE, "epi_batch_heterogeneity_report_dev: the batch is set up for a sharded report (the sharded form is not built)");
+  b->het_nsite = nsite; b->het_k = k;
+  b->het_min_reads = (uint32_t)(min_reads > 1 ? min_reads : 1);
+  b->het_max_span = max_span;
+  if (nsite < k) { b->last_kind = KIND_HET; b->last_nrow = 0; b->het_nsite = 0; return EPI_OK; }
+  if (nsite >= (1LL << 31) || (nsite << k) * 4 > kHetCountsCap)
+    return fail(EPI_ERR_ARG, "epi_batch_heterogeneity_report_dev: %lld sites x %d patterns need %lld bytes of counters, above the cap of %lld",
+                (long long)nsite, 1 << k, (long long)((nsite << k) * 4), (long long)kHetCountsCap);
+  const size_t N = (size_t)nsite;
+  const int64_t nb_sites = ((int64_t)N + HET_WG - 1) / HET_WG;
+  constexpr int rows16 = HET_WG / 16, rows64 = HET_WG / 64;
+  const bool wide = b->nbytes > kHetLongRow * b->n;
+  const int64_t nb_rows = (b->n + (wide ? rows64 : rows16) - 1) / (wide ? rows64 : rows16);
+  EPI_TRY(check_grid(nb_sites, HET_WG, "heterogeneity site kernels"));
+  EPI_TRY(check_grid(nb_rows, HET_WG, "heterogeneity counting kernel"));
+
+  EPI_TRY(b->het_cx.ensure(N * 6 * 4));
+  EPI_TRY(b->het_rank.ensure(N * 4));
+  EPI_TRY(b->het_flag.ensure(N * 4));
+  EPI_TRY(b->het_key.ensure(N * 8));
+  EPI_TRY(b->het_sctx.ensure(N));
+  EPI_TRY(b->het_scal.ensure(64));
+  EPI_TRY(b->het_counts.ensure((N << k) * 4));
+  int32_t *cx = b->het_cx.as<int32_t>();
+  int32_t *cols[6];
+  for (int i = 0; i < 6; i++) cols[i] = cx + (size_t)i * N;
+  b->last_kind = KIND_CX;                                  // (for the fetch of the table that has just been made)
+  const int rc = epi_batch_cx_fetch_dev(b, cols, s);
+  b->last_kind = KIND_NONE;
+  EPI_TRY(rc);
+  uint32_t *scal = b->het_scal.as<uint32_t>();             // [0] '+' sites, [1] reported rows
+  uint32_t *flag = b->het_flag.as<uint32_t>(), *rank = b->het_rank.as<uint32_t>();
+  hipLaunchKernelGGL(k_het_strand_flag, dim3((unsigned)nb_sites), dim3(HET_WG), 0, s, cols[1], (uint32_t)N, flag);
+  EPI_TRY(scan_exclusive_u32(flag, rank, (int64_t)N, &scal[0], b->scan_tmp, s));
+  hipLaunchKernelGGL(k_het_sites, dim3((unsigned)nb_sites), dim3(HET_WG), 0, s, cols[0], cols[1], cols[2], cols[3], rank, &scal[0],
+                     (uint32_t)N, b->het_key.as<unsigned long long>(), b->het_sctx.as<uint8_t>());
+  EPI_HIP(hipGetLastError());
+
+  // (b) the histograms
+  EPI_HIP(hipMemsetAsync(b->het_counts.p, 0, (N << k) * 4, s));
+  HetArgs a;
+  a.xm = b->xm; a.off = b->off; a.len = b->len; a.rname = b->rname; a.strand = b->strand; a.start = b->start; a.n = b->n;
+  a.key = b->het_key.as<unsigned long long>(); a.sctx = b->het_sctx.as<uint8_t>(); a.n1 = &scal[0]; a.N = (uint32_t)N; a.k = k;
+  a.oom_mask = ((1u << 2) | (1u << 5) | (1u << 6) | (1u << 7)) & ~ctx_mask;           // rcpp_mhl_report.cpp:176-177
+  a.oou_mask = ((1u << 10) | (1u << 13) | (1u << 14) | (1u << 15)) & ~ctx_mask;
+  a.max_oo = max_oo;
+  a.counts = b->het_counts.as<uint32_t>();
+  prof_begin("het_count", s);
+  if (wide) hipLaunchKernelGGL((k_het_count<64>), dim3((unsigned)nb_rows), dim3(HET_WG), 0, s, a);
+  else hipLaunchKernelGGL((k_het_count<16>), dim3((unsigned)nb_rows), dim3(HET_WG), 0, s, a);
+  prof_end("het_count", s);
+  EPI_HIP(hipGetLastError());
+
+  // (c) which windows are reported, and where
+  HetFinish f;
+  het_finish_args(b, f);
+  hipLaunchKernelGGL(k_het_keep, dim3((unsigned)nb_sites), dim3(HET_WG), 0, s, f, flag);
+  EPI_HIP(hipGetLastError());
+  EPI_TRY(b->het_out.ensure(N * 4));
+  EPI_TRY(scan_exclusive_u32(flag, b->het_out.as<uint32_t>(), (int64_t)N, &scal[1], b->scan_tmp, s));
+  uint32_t h[2];
+  EPI_TRY(read_scalars(b, s, scal, sizeof(h), h));
+  b->last_kind = KIND_HET;
+  b->last_nrow = h[1];
+  *nrow_out = h[1];
+  return EPI_OK;
+}
+
+}  // namespace epi
+
+using namespace epi;
+
+extern "C" {
+
+int epi_batch_heterogeneity_report_dev(epi_batch *b, const char *ctx, int k, double max_ooctx_meth_frac, int32_t min_reads,
+                                       int32_t max_window_span, void *stream, int64_t *nrow_out) {
+  if (!b || !ctx || !nrow_out) return fail(EPI_ERR_ARG, "epi_batch_heterogeneity_report_dev: NULL argument");
+  *nrow_out = 0;
+  if (k < kHetMinK || k > kHetMaxK)
+    return fail(EPI_ERR_ARG, "epi_batch_heterogeneity_report_dev: k = %d, windows hold %d to %d sites", k, kHetMinK, kHetMaxK);
+  if (max_window_span < 0) return fail(EPI_ERR_ARG, "epi_batch_heterogeneity_report_dev: negative max_window_span");
+  b->last_kind = KIND_NONE;
+  EPI_HIP(hipSetDevice(b->eng->device));
+  return het_report(b, ctx, k, max_ooctx_meth_frac, min_reads, max_window_span, pick_stream(b, stream), nrow_out);
+}
+
+int epi_batch_heterogeneity_fetch_dev(epi_batch *b, int32_t *const d_icols[7], double *const d_dcols[4], int32_t *d_counts,
+                                      void *stream) {
+  if (!b || !d_icols || !d_dcols) return fail(EPI_ERR_ARG, "epi_batch_heterogeneity_fetch_dev: NULL argument");
+  if (b->last_kind != KIND_HET) return fail(EPI_ERR_STATE, "epi_batch_heterogeneity_fetch_dev: no finished heterogeneity report on this batch");
+  if (b->last_nrow == 0) return EPI_OK;
+  for (int i = 0; i < 7; i++) if (!d_icols[i]) return fail(EPI_ERR_ARG, "epi_batch_heterogeneity_fetch_dev: NULL column");
+  for (int i = 0; i < 4; i++) if (!d_dcols[i]) return fail(EPI_ERR_ARG, "epi_batch_heterogeneity_fetch_dev: NULL column");
+  EPI_HIP(hipSetDevice(b->eng->device));
+  hipStream_t s = pick_stream(b, stream);
+  HetFinish f;
+  het_finish_args(b, f);
+  HetOut o;
+  o.rname = d_icols[0]; o.strand = d_icols[1]; o.pos = d_icols[2]; o.end = d_icols[3]; o.context = d_icols[4];
+  o.nreads = d_icols[5]; o.npatterns = d_icols[6];
+  o.beta = d_dcols[0]; o.epipoly = d_dcols[1]; o.entropy = d_dcols[2]; o.pdr = d_dcols[3];
+  o.counts = d_counts;
+  const unsigned nb = (unsigned)(((int64_t)f.N + HET_WG - 1) / HET_WG);
+  hipLaunchKernelGGL(k_het_emit, dim3(nb), dim3(HET_WG), 0, s, f, b->het_flag.as<uint32_t>(), b->het_out.as<uint32_t>(), o);
+  EPI_HIP(hipGetLastError());
+  return EPI_OK;
+}
+
+}  // extern "C"

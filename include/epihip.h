@@ -422,6 +422,42 @@ int epi_batch_mhl_report_dev(epi_batch *b, const char *ctx, int hmax, int hmin,
 int epi_batch_mhl_fetch_dev(epi_batch *b, int32_t *const d_icols[5], double *const d_dcols[2], void *stream);
 int epi_batch_mhl_fetch_host(epi_batch *b, int32_t *const h_icols[5], double *const h_dcols[2], void *stream);
 
+/* Heterogeneity report: epipolymorphism (Landan 2012), methylation entropy (Xie 2011) and the fraction of discordant
+ * reads (Landau 2014) of every window of k neighbouring sites.  No reference interface is replaced -- the reference has
+ * no such report; this one composes two of its rules: the site table of rcpp_cx_report (src/rcpp_cx_report.cpp:58-80,
+ * the majority rule) and the read rule of rcpp_mhl_report (src/rcpp_mhl_report.cpp:172-179).
+ *  ctx       context letters in both cases, as for the lMHL report ("Zz", "XxZz", ...), k = 2 .. 6 sites per window.
+ *  Sites     the rows (rname, strand, pos, context) of the un-thresholded CX report of the whole batch for the upper-case
+ *            letters of ctx (pass all TRUE); the row filter below never changes them.  Per (rname, strand) they are
+ *            ordered by pos, s_0 < s_1 < ... < s_{m-1}.
+ *  Windows   window j (0 <= j <= m - k) is (s_j ... s_{j+k-1}); a window never spans two sequences or strands.
+ *  Calls     a row of strand 1 or 2 has a call at a site of its own (rname, strand) when start <= pos < start + length
+ *            and the low nibble x of its byte at pos - start has (x & 7) == the site's context code; methylated when
+ *            x < 8.  Everything else ('.', '-', another context, a call where there is no site) is no call.
+ *  Kept rows the read rule of the lMHL report with hmin = 0: with o_m / o_u the row's methylated / unmethylated calls in
+ *            the contexts NOT in ctx, a row is dropped when o_m / (o_m + o_u) > max_ooctx_meth_frac (0 / 0 is NaN: kept).
+ *  Counts    a kept row with a call at all k sites of a window adds 1 to counts[window][p], bit i of p set when its call
+ *            at the window's i-th site is methylated.  A gap inside a window: nothing for that window.
+ *  Metrics   n = sum of the 2^k bins, p_i = counts[i] / n; nreads = n; npatterns = nonzero bins;
+ *            beta = sum_p counts[p] popcount(p) / (n k); epipolymorphism = 1 - sum p_i^2;
+ *            entropy = -(1 / k) sum_{p_i > 0} p_i log2 p_i; pdr = 1 - (counts[0] + counts[2^k - 1]) / n.
+ *            float64, bins summed in ascending order: no launch shape enters a result.
+ *  Rows      a window is reported when n >= max(min_reads, 1) and (max_window_span == 0 or
+ *            s_{j+k-1} - s_j + 1 <= max_window_span), in the order of the CX rows the windows start on:
+ *            (rname, pos of the first site, strand).
+ * Two steps as for the lMHL report: report_dev runs the report (synchronises `stream`, the row count comes back), fetch_dev
+ * writes the rows into seven int32 columns (rname, strand, pos, end = pos of the last site, context of the first site,
+ * nreads, npatterns), four double columns (beta, epipolymorphism, entropy, pdr) and, unless NULL, d_counts [nrow][2^k]
+ * int32.  The counters are u32 (n cannot exceed the row count); nsites * 2^k * 4 bytes above 4 GiB: EPI_ERR_ARG before any
+ * counter is allocated.  The report runs a CX report of its own first, so it leaves the batch as that would, and any
+ * later report returns what it returns without it; fetch_dev after any other report: EPI_ERR_STATE.  Single GPU only:
+ * the counts are additive over row shards once the site table is common, the sharded form is not built (a batch with
+ * shared tiles attached: EPI_ERR_STATE). */
+int epi_batch_heterogeneity_report_dev(epi_batch *b, const char *ctx, int k, double max_ooctx_meth_frac, int32_t min_reads,
+                                       int32_t max_window_span, void *stream, int64_t *nrow_out);
+int epi_batch_heterogeneity_fetch_dev(epi_batch *b, int32_t *const d_icols[7], double *const d_dcols[4],
+                                      int32_t *d_counts /* may be NULL */, void *stream);
+
 /* rcpp_extract_patterns (src/rcpp_extract_patterns.cpp:26-211; caller .getPatterns, R/internal.R:683-714):
  * methylation patterns of the reads overlapping one target.  Library-owned host table: per pattern strand, start,
  * end, nbase, beta, the FNV-1a hash the R side prints as 16 hex digits ("pattern"), the ordered column positions
