@@ -412,7 +412,12 @@ int epi_batch_cytosine_report_into_dev(epi_batch *b, const char *ctx_meth, const
                                        const char *ooctx_unmeth, uint32_t min_n_ctx, double min_ctx_meth_frac,
                                        double max_ooctx_meth_frac, const char *ctx, int32_t *d_pass_out /* may be NULL */,
                                        int32_t *const d_cols[6], int64_t cap, void *stream, int64_t *nrow_out, int *written);
-/* Capacity query: *nrow = rows of the last report on this batch with the contexts of `ctx` (-1: none yet). */
+/* Capacity query: *nrow = the row count recorded on this batch for the contexts of `ctx` (-1: no record with these
+ * contexts).  One record is kept per batch.  A pool report (*written = 0, epi_batch_cx_report_dev, the CX report inside a
+ * heterogeneity report) makes it when the batch has none with its contexts, and a direct launch whose tile counts
+ * differed replaces it; a pool report that meets a record with its own contexts leaves it as it is.  So the count is that
+ * of the report that MADE the record, which need not be the last report with these contexts: under another `pass` the
+ * unused low nibbles 1, 3 and 4 give another count, and then the next direct launch reruns through the pool. */
 int epi_batch_cx_report_capacity(epi_batch *b, const char *ctx, int64_t *nrow);
 int epi_batch_cx_fetch_dev(epi_batch *b, int32_t *const d_cols[6], void *stream);
 int epi_batch_cx_fetch_host(epi_batch *b, int32_t *const h_cols[6], void *stream);
@@ -449,8 +454,11 @@ int epi_batch_mhl_fetch_host(epi_batch *b, int32_t *const h_icols[5], double *co
  * writes the rows into seven int32 columns (rname, strand, pos, end = pos of the last site, context of the first site,
  * nreads, npatterns), four double columns (beta, epipolymorphism, entropy, pdr) and, unless NULL, d_counts [nrow][2^k]
  * int32.  The counters are u32 (n cannot exceed the row count); nsites * 2^k * 4 bytes above 4 GiB: EPI_ERR_ARG before any
- * counter is allocated.  The report runs a CX report of its own first, so it leaves the batch as that would, and any
- * later report returns what it returns without it; fetch_dev after any other report: EPI_ERR_STATE.  Single GPU only:
+ * counter is allocated.  The report runs a CX report of its own first -- epi_batch_cx_report_dev(b, NULL, the
+ * upper-case letters of ctx) -- and leaves the direct-mode record (epi_batch_cx_report_capacity) as that call would: a
+ * record with those contexts stays as it is, also one made under another `pass`, any other is replaced by this table's.
+ * No later report's table depends on it.  Only epi_batch_heterogeneity_fetch_dev may follow the report: it after any
+ * other report, or another report's fetch after this one, is EPI_ERR_STATE.  Single GPU only:
  * the counts are additive over row shards once the site table is common, the sharded form is not built (a batch with
  * shared tiles attached: EPI_ERR_STATE). */
 int epi_batch_heterogeneity_report_dev(epi_batch *b, const char *ctx, int k, double max_ooctx_meth_frac, int32_t min_reads,

@@ -5,8 +5,11 @@ fuzz generator plus one with raw garbage bytes (the unused low nibbles 1, 3 and 
 failed read), through every constructor.  Every CX call through the C entry points also checks `written` against the
 rule of include/epihip.h, predicted from the oracle's tables alone: the tile kernel writes the caller's columns when the
 last pool report on the batch had the same contexts, no position is deeper than 255 rows, the kept row count is above 0
-and fits, and every tile of the absolute grid yields as many rows as then.  Bounded by a list of seeds; a failure names
-its seed and step."""
+and fits, and every tile of the absolute grid yields as many rows as then.  The reports that came later take part as
+operations of their own, each checked as in test_gpu_fuzz_reports.py: the heterogeneity report (whose own CX report keeps
+or replaces the direct-mode record: Slot.het, with the capacity the library reports afterwards and the `written` of the
+next C-level CX call against it), base frequencies, and the multi-target pattern tables and summaries, which keep
+scratch groups and hash tables on the batch.  Bounded by a list of seeds; a failure names its seed and step."""
 import collections
 
 import numpy as np
@@ -17,6 +20,7 @@ import synth_np
 import test_extract_patterns as TP
 import test_gpu_cx_direct as D
 import test_gpu_fuzz as F
+import test_gpu_fuzz_reports as R
 from oracle import oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -28,12 +32,17 @@ NAMED = ("CG", "CHG", "CHH", "CxG", "CX")
 MHL_CTX = ("Zz", "Xx", "Hh", "ZzXx", "ZzXxHh")
 PASSES = ("none", "oracle", "random", "false", "na")
 MAKERS = ("arrays", "pinned", "device", "zero_copy")
-OPS = (("cx_c", 8), ("cx_py", 2), ("fused_py", 2), ("gcr", 1), ("mhl", 2), ("thr", 1), ("beta", 1), ("pat", 1), ("reopen", 1))
+OPS = (("cx_c", 8), ("cx_py", 2), ("fused_py", 2), ("gcr", 1), ("mhl", 2), ("thr", 1), ("beta", 1), ("pat", 1), ("reopen", 1),
+       ("het", 2), ("freqs", 1), ("pat_multi", 1), ("summ", 1))
 NA = -2 ** 31
 # Paths over the whole seed list: C-level CX calls (`written` asserted) and Python-level ones (py_: tables only).  pool:
 # no record with these contexts yet; fallback: a direct launch in which some tile's count differed, the new row count
 # above / not above the kept one (above: the Python columns are allocated again).
-MIN_PATHS = {"pool": 150, "direct": 100, "fallback_above": 8, "fallback_below": 8, "py_direct": 40, "py_fallback_above": 5}
+# het_replaces / het_keeps: a heterogeneity report whose own CX report replaced the record / met one with its contexts and
+# left it alone; direct_after_het: a C-level direct launch on a record that a heterogeneity report was the last to touch
+# (kept or made; repeated launches count); direct_after_het_replaces: such a launch on a record that the report MADE.
+MIN_PATHS = {"pool": 150, "direct": 100, "fallback_above": 8, "fallback_below": 8, "py_direct": 40, "py_fallback_above": 5,
+             "het_replaces": 5, "het_keeps": 5, "direct_after_het": 5, "direct_after_het_replaces": 5}
 RAN = {}                                               # group -> its path counts (this session)
 
 
@@ -75,6 +84,8 @@ class Slot:
         t = self.t
         self.maker = maker
         self.rec = None                                # (context mask, per-tile counts, row count) of the kept record
+        self.after_het = False                         # a heterogeneity report was the last call to keep or replace it
+        self.het_made = False                          # the record is one that a heterogeneity report made
         nb = int(t["off"][-1])
         if maker == "arrays":
             self.bam = ea.ProcessedBam.from_arrays(t["xm"], t["off"], t["rname"], t["strand"], t["start"])
@@ -102,7 +113,23 @@ class Slot:
             path = "pool_again"                        # same contexts, but pile-ups or an empty kept table: the record stays
         if self.n > 0 and path in ("pool", "fallback_above", "fallback_below"):
             self.rec = (mask, counts, nrow)
+            self.after_het = self.het_made = False
         return path, cap
+
+    def het(self, letters, sites, T):
+        """What a heterogeneity report does to the record: its own CX report is a pool report without caller columns, for the
+        upper-case letters of its context, all rows passing (`sites`: that table).  A record with the same contexts stays
+        as it is, also one made under another pass vector (cx_keep_offsets); any other is replaced by this table's tile
+        counts and row count.  -> the path's name"""
+        mask = ctx_mask(letters)
+        if self.n == 0:
+            return "het_empty"
+        self.after_het = True
+        if self.rec is not None and self.rec[0] == mask:
+            return "het_keeps"
+        self.rec = (mask, D.tile_counts(sites, T), int(sites["pos"].size))
+        self.het_made = True
+        return "het_replaces"
 
 
 def make_slots(ea, rng, seed):
@@ -113,18 +140,27 @@ def make_slots(ea, rng, seed):
 
 
 def pick_pass(rng, s, kind, c4=None, thr=None):
-    t = s.t
-    if kind == "none":
-        return None
-    if kind == "oracle":
-        return orc.threshold_reads(t["xm"], t["off"], *c4, *thr)
-    if kind == "random":
-        return rng.integers(0, 2, size=s.n).astype(np.int32)
-    if kind == "false":
-        return np.zeros(s.n, np.int32)
-    p = rng.integers(0, 2, size=s.n).astype(np.int32)
-    p[rng.random(s.n) < 0.3] = NA                      # R's NA: non-zero, so TRUE
-    return p
+    return R.pick_pass(rng, s.t, kind, c4, thr)
+
+
+def named_of(letters):
+    """the named context whose cytosine report has the contexts of `letters` (None: there is none)"""
+    for name in NAMED:
+        if ctx_mask(H.CONTEXT_TO_BASES[name]["ctx_meth"]) == ctx_mask(letters):
+            return name
+    return None
+
+
+def refused_fetch(ea, s, which):
+    """the lMHL or the CX fetch right after a heterogeneity report: a call sequence error, and the batch is as before"""
+    import torch
+    from epialleler_amd import _lib, api
+    lib = _lib.load()
+    ic = list(torch.empty((6, 8), dtype=torch.int32, device="cuda:%d" % (s.bam.device or 0)).unbind(0))
+    dc = list(torch.empty((2, 8), dtype=torch.float64, device="cuda:%d" % (s.bam.device or 0)).unbind(0))
+    if which == "mhl":
+        return lib.epi_batch_mhl_fetch_dev(s.bam.batch(), api._ptr_array(ic[:5]), api._ptr_array(dc), None) == _lib.EPI_ERR_STATE
+    return lib.epi_batch_cx_fetch_dev(s.bam.batch(), api._ptr_array(ic), None) == _lib.EPI_ERR_STATE
 
 
 def cpu(rep):
@@ -171,6 +207,7 @@ def run_seed(ea, seed, paths):
                     p = pick_pass(rng, s, pk, c4, thr)
                     want = orc.cx_report(t["xm"], t["off"], t["rname"], t["strand"], t["start"], p, letters)
                     T = lib.epi_cx_tile_positions(letters.encode())
+                    after_het, het_made = s.after_het, s.het_made
                     path, cap = s.predict(letters, want, T)
                     what += (letters, pk, fused, thr, path)
                     assert D.capacity(ea, s.bam, letters) == cap, ("capacity", cap)
@@ -180,6 +217,8 @@ def run_seed(ea, seed, paths):
                         H.assert_reports_equal(got, want)
                         assert written == (path == "direct"), ("written", written)
                         paths[path] += 1
+                        paths["direct_after_het"] += path == "direct" and after_het
+                        paths["direct_after_het_replaces"] += path == "direct" and het_made
                     else:
                         H.dirty_allocator(s.bam)
                         if op == "cx_py":
@@ -230,6 +269,32 @@ def run_seed(ea, seed, paths):
                         assert np.array_equal(a[c], b[c]), c
                     assert np.array_equal(np.asarray(a["beta"], np.float64).view(np.uint64),
                                           np.asarray(b["beta"], np.float64).view(np.uint64)), "pattern beta"
+                elif op == "het":
+                    name = named_of(last[k][0]) if k in last and rng.random() < 0.6 else None    # the CX ops' coin: the same contexts again
+                    call = R.draw_het(rng, t, ctx=name)
+                    fetch = str(rng.choice(["none", "none", "mhl", "cx"]))
+                    letters = H.CONTEXT_TO_BASES[call[0]]["ctx_meth"]
+                    what += call + (fetch,)
+                    want = R.het_want(t, call)
+                    if want is None:
+                        paths["het_skipped"] += 1
+                        continue
+                    hp = s.het(letters, want["sites"], lib.epi_cx_tile_positions(letters.encode()))
+                    what += (hp,)
+                    R.check_het(ea, s.bam, t, call, want)
+                    assert D.capacity(ea, s.bam, letters) == (s.rec[2] if s.n else -1), ("capacity after het", s.rec and s.rec[2])
+                    paths[hp] += 1
+                    last[k] = (letters, "none", H.cls4(call[0]), thr)
+                    if fetch != "none":
+                        assert refused_fetch(ea, s, fetch), "fetch after a heterogeneity report"
+                elif op == "freqs":
+                    f = R.draw_freqs(rng, t)
+                    what += (f["pass_kind"], int(f["chr"].size))
+                    R.check_freqs(ea, s.bam, t, f)
+                elif op in ("pat_multi", "summ"):
+                    p = R.draw_patterns(rng, t)
+                    what += tuple(p[q] for q in ("targets", "mo", "ctx", "freq", "clip", "ro", "hl", "bin"))
+                    (R.check_multi if op == "pat_multi" else R.check_summ)(ea, s.bam, t, p)
                 else:                                      # reopen: a fresh batch of the same rows, maybe another constructor
                     s.bam.close()
                     last.pop(k, None)
