@@ -1,17 +1,21 @@
-// rcpp_extract_patterns (src/rcpp_extract_patterns.cpp:26-211): methylation patterns of the reads that overlap one
-// target region.  The work is confined to that region (a few thousand reads), so this is three small kernels around
-// two host decisions, not a bandwidth problem:
-//   k_pat_flag     one thread per row: does the read overlap the target by min_overlap (:79-86)?  -> scan -> its index
-//   k_pat_count    one thread per overlapping read: how often is each in-context position seen (:87-96)
-//   host           valid positions = seen in >= min_ctx_freq of the overlapping reads and not highlighted (:103-108),
-//                  merged with the highlight positions, ordered (:185)
-//   k_pat_extract  one thread per overlapping read: its cell per valid position, methylated / total counts and the
-//                  FNV-1a hash of (position, base) pairs, highlighted bases appended (:133-166)
-//   host           drops empty patterns (:152) and returns the table.
-// epi_batch_extract_patterns_multi (second half of this file) runs the same per-read rules for every target of a list in
-// O(1) launches and host round trips: candidate row ranges by search, one flat list of (target, row) pairs.
-// epi_batch_summarise_patterns_multi runs the same two passes and then groups every target's patterns on the device
-// (k_pats_*): only the unique patterns and their counts come to the host.
+// rcpp_extract_patterns (src/rcpp_extract_patterns.cpp:26-211): methylation patterns of the reads that overlap a target
+// region, for one target (epi_batch_extract_patterns) or every target of a list (epi_batch_extract_patterns_multi).  The
+// work is confined to the targets (a few thousand reads each), so this is two small passes around one host decision,
+// not a bandwidth problem.  One path serves both calls: a GROUP of targets, each with a range of candidate rows; the
+// ranges laid end to end are one flat list of (target, candidate row) pairs.
+//   k_patm_ranges      rows sorted by (rname, start): one lane per target finds its candidate rows by search
+//   k_patm_flag_count  pass 1, one thread per pair: does the read overlap its target by min_overlap (:79-86)?  -> scan ->
+//                      its slot; and how often is each in-context position seen (:87-96)
+//   host               valid positions = seen in >= min_ctx_freq of the overlapping reads and not highlighted (:103-108),
+//                      merged with the highlight positions, ordered (:185)
+//   k_patm_extract     pass 2, one thread per overlapping pair: its cell per valid position, methylated / total counts and
+//                      the FNV-1a hash of (position, base) pairs, highlighted bases appended (:133-166)
+//   host               drops empty patterns (:152) and returns the tables.
+// A list whose rows are sorted and whose coordinates are not negative runs as groups of ranged targets, in O(1) launches
+// and host round trips per group.  The single call, and every target of any other list, is a group of ONE target whose
+// candidate rows are all rows [0, n): pat_span rejects the rows of other rnames itself, so neither pass relies on the range
+// being tight.  epi_batch_summarise_patterns_multi runs the same two passes and then groups every target's patterns on
+// the device (k_pats_*): only the unique patterns and their counts come to the host.
 // Quirks of the reference kept as they are: with clip=TRUE the byte loop ends at `overlap`,
 // not at begin+overlap (:86,:132), and position bytes enter the hash sign-extended (char pointer, epialleleR.h:8-13).
 #include "common.hpp"
@@ -23,136 +27,12 @@
 
 namespace epi {
 
-struct PatArgs {
-  const uint8_t *xm;
-  const int64_t *off;             // row x owns xm[off[x] .. off[x] + len[x])
-  const int32_t *len;
-  const int32_t *rname, *strand, *start;
-  int64_t n;
-  uint32_t target_rname, target_start, target_end, reverse_offset;
-  int32_t min_overlap, clip;
-  uint32_t ctx_mask;
-  int64_t pos_lo;                 // window of positions that can occur: [pos_lo, pos_lo + nwin)
-  int64_t nwin;
-};
-
-struct PatSpan { uint32_t start_x, begin_i, end_i, offset_x; bool ok; };
-
-__device__ __forceinline__ PatSpan pat_span(const PatArgs &a, int64_t x) {
-  PatSpan s;
-  s.ok = false; s.start_x = 0; s.begin_i = 0; s.end_i = 0; s.offset_x = 0;
-  if (a.rname[x] != (int32_t)a.target_rname) return s;                      // :78
-  const uint32_t size_x = (uint32_t)a.len[x];
-  const uint32_t start_x = (uint32_t)a.start[x];
-  const uint32_t end_x = start_x + size_x - 1u;
-  const uint32_t over_start = start_x > a.target_start ? start_x : a.target_start;
-  const uint32_t over_end = end_x < a.target_end ? end_x : a.target_end;
-  const int32_t overlap = (int32_t)(over_end - over_start + 1u);            // :84
-  if (overlap < a.min_overlap) return s;
-  s.ok = true;
-  s.start_x = start_x;
-  s.offset_x = a.strand[x] == 2 ? a.reverse_offset : 0u;
-  s.begin_i = a.clip ? over_start - start_x : 0u;
-  s.end_i = a.clip ? (uint32_t)overlap : size_x;
-  if (s.end_i > size_x) s.end_i = size_x;                                   // (the reference would read past the string)
-  return s;
-}
-
-__global__ __launch_bounds__(256) void k_pat_flag(PatArgs a, uint32_t *__restrict__ flag) {
-  const int64_t x = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (x >= a.n) return;
-  flag[x] = pat_span(a, x).ok ? 1u : 0u;
-}
-
-// row x overlaps the target (s = pat_span(a, x), s.ok): one count per in-context position of its span
-__device__ __forceinline__ void pat_count_row(const PatArgs &a, int64_t x, const PatSpan &s, uint32_t *__restrict__ cnt) {
-  const uint8_t *p = a.xm + a.off[x];
-  for (uint32_t i = s.begin_i; i < s.end_i; i++) {
-    if (!((a.ctx_mask >> (p[i] & 15u)) & 1u)) continue;
-    const int64_t w = (int64_t)(int32_t)(s.start_x + i - s.offset_x) - a.pos_lo;
-    if (w >= 0 && w < a.nwin) atomicAdd(cnt + w, 1u);
-  }
-}
-
-__global__ __launch_bounds__(256) void k_pat_count(PatArgs a, const uint32_t *__restrict__ flag, uint32_t *__restrict__ cnt) {
-  const int64_t x = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (x >= a.n || !flag[x]) return;
-  pat_count_row(a, x, pat_span(a, x), cnt);
-}
-
-struct PatOut {
-  int32_t *nonempty, *strand, *start, *end, *nbase, *meth;
-  unsigned long long *fnv;
-  int32_t *cells;                 // [ncol][npat0]
-};
-
-__device__ __forceinline__ void fnv_char(unsigned long long &h, uint32_t v) {   // four bytes through a (signed) char pointer
-#pragma unroll
-  for (int k = 0; k < 4; k++) {
-    h ^= (unsigned long long)(long long)(signed char)((v >> (8 * k)) & 0xFFu);
-    h *= 1099511628211ull;
-  }
-}
-
-// row x overlaps the target (s = pat_span(a, x), s.ok) and is its c-th overlapping row: cells, counts and hash
-__device__ __forceinline__ void pat_extract_row(const PatArgs &a, int64_t x, const PatSpan &s, uint32_t c,
-                                                const int32_t *__restrict__ colmap, const int32_t *__restrict__ hlght,
-                                                const int32_t *__restrict__ hcol, int32_t nhlght, int64_t npat0, const PatOut &o) {
-  const uint8_t *p = a.xm + a.off[x];
-  uint32_t meth = 0, total = 0;
-  unsigned long long fnv = 14695981039346656037ull;
-  for (uint32_t i = s.begin_i; i < s.end_i; i++) {
-    const uint32_t base = p[i] & 15u;
-    if (!((a.ctx_mask >> base) & 1u)) continue;
-    const uint32_t pos = s.start_x + i - s.offset_x;
-    const int64_t w = (int64_t)(int32_t)pos - a.pos_lo;
-    if (w < 0 || w >= a.nwin) continue;
-    const int32_t col = colmap[w];
-    if (col < 0) continue;                                                   // :141
-    o.cells[(int64_t)col * npat0 + c] = (int32_t)base;                       // :143
-    meth += !(base & 8u);
-    total++;
-    fnv_char(fnv, pos);                                                      // :147
-    fnv ^= (unsigned long long)base; fnv *= 1099511628211ull;                // :148
-  }
-  const bool nonempty = fnv != 14695981039346656037ull;
-  if (nonempty) {
-    static const uint8_t factor_map[16] = {13, 3, 4, 13, 11, 13, 13, 13, 12, 13, 13, 13, 13, 13, 13, 13};   // :47
-    for (int32_t k = 0; k < nhlght; k++) {                                   // :154-164
-      const uint32_t hp = (uint32_t)hlght[k] - s.start_x;
-      if (hp >= s.begin_i && hp < s.end_i) {
-        const uint32_t base = factor_map[(p[hp] >> 4) & 15u];
-        o.cells[(int64_t)hcol[k] * npat0 + c] = (int32_t)base;
-        fnv_char(fnv, (uint32_t)hlght[k]);
-        fnv ^= (unsigned long long)base; fnv *= 1099511628211ull;
-      }
-    }
-  }
-  o.nonempty[c] = nonempty ? 1 : 0;
-  o.strand[c] = a.strand[x];
-  o.start[c] = (int32_t)(s.start_x + s.begin_i);
-  o.end[c] = (int32_t)(s.start_x + s.end_i - 1u);
-  o.nbase[c] = (int32_t)total;
-  o.meth[c] = (int32_t)meth;
-  o.fnv[c] = fnv;
-}
-
-__global__ __launch_bounds__(256) void k_pat_extract(PatArgs a, const uint32_t *__restrict__ flag, const uint32_t *__restrict__ cidx,
-                                                      const int32_t *__restrict__ colmap, const int32_t *__restrict__ hlght,
-                                                      const int32_t *__restrict__ hcol, int32_t nhlght, int64_t npat0, PatOut o) {
-  const int64_t x = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (x >= a.n || !flag[x]) return;
-  pat_extract_row(a, x, pat_span(a, x), cidx[x], colmap, hlght, hcol, nhlght, npat0, o);
-}
-
-// ---- every target of a list at once (epi_batch_extract_patterns_multi) -------------------------------------------------
-// Rows sorted by (rname, start): the rows that can overlap target t lie in one range [row_lo, row_hi), found by search.
 // The ranges of a group of targets are laid end to end as one flat list of (target, candidate row) pairs; pre[] is the
 // u64 exclusive scan of the range lengths, and thread j finds its target as the last t with pre[t] <= j.  flag / cidx
 // are indexed by pair, cnt / colmap by the targets' windows laid end to end: every target owns a slice of each.
 struct PatTarget {
   int64_t row_lo;                 // its candidate rows: row_lo + (j - pre[t])
-  int64_t pos_lo, nwin;           // its window of positions, as PatArgs
+  int64_t pos_lo, nwin;           // window of positions that can occur: [pos_lo, pos_lo + nwin)
   int64_t win_off;                // its slice of cnt / colmap
   int64_t hl_off;                 // its highlight positions: hl[hl_off .. hl_off + nhl), columns hcol[...]
   int32_t rname, start, end, nhl;
@@ -165,7 +45,7 @@ struct PatSlice {                 // what the host decided for a target between 
 };
 struct PatMulti {
   const uint8_t *xm;
-  const int64_t *off;
+  const int64_t *off;             // row x owns xm[off[x] .. off[x] + len[x])
   const int32_t *len, *rname, *strand, *start;
   uint32_t reverse_offset, ctx_mask;
   int32_t min_overlap, clip;
@@ -174,23 +54,116 @@ struct PatMulti {
   int32_t ng;
 };
 
-__device__ __forceinline__ PatArgs pat_args_of(const PatMulti &m, const PatTarget &g) {
-  PatArgs a;
-  a.xm = m.xm; a.off = m.off; a.len = m.len; a.rname = m.rname; a.strand = m.strand; a.start = m.start; a.n = 0;
-  a.target_rname = (uint32_t)g.rname; a.target_start = (uint32_t)g.start; a.target_end = (uint32_t)g.end;
-  a.reverse_offset = m.reverse_offset; a.min_overlap = m.min_overlap; a.clip = m.clip; a.ctx_mask = m.ctx_mask;
-  a.pos_lo = g.pos_lo; a.nwin = g.nwin;
+struct PatSpan { uint32_t start_x, begin_i, end_i, offset_x; bool ok; };
+
+__device__ __forceinline__ PatSpan pat_span(const PatMulti &m, const PatTarget &g, int64_t x) {
+  PatSpan s;
+  s.ok = false; s.start_x = 0; s.begin_i = 0; s.end_i = 0; s.offset_x = 0;
+  if (m.rname[x] != g.rname) return s;                                      // :78
+  const uint32_t target_start = (uint32_t)g.start, target_end = (uint32_t)g.end;
+  const uint32_t size_x = (uint32_t)m.len[x];
+  const uint32_t start_x = (uint32_t)m.start[x];
+  const uint32_t end_x = start_x + size_x - 1u;
+  const uint32_t over_start = start_x > target_start ? start_x : target_start;
+  const uint32_t over_end = end_x < target_end ? end_x : target_end;
+  const int32_t overlap = (int32_t)(over_end - over_start + 1u);            // :84
+  if (overlap < m.min_overlap) return s;
+  s.ok = true;
+  s.start_x = start_x;
+  s.offset_x = m.strand[x] == 2 ? m.reverse_offset : 0u;
+  s.begin_i = m.clip ? over_start - start_x : 0u;
+  s.end_i = m.clip ? (uint32_t)overlap : size_x;
+  if (s.end_i > size_x) s.end_i = size_x;                                   // (the reference would read past the string)
+  return s;
+}
+
+// row x overlaps the target (s = pat_span(m, g, x), s.ok): one count per in-context position of its span
+__device__ __forceinline__ void pat_count_row(const PatMulti &m, const PatTarget &g, int64_t x, const PatSpan &s, uint32_t *__restrict__ cnt) {
+  const uint8_t *p = m.xm + m.off[x];
+  for (uint32_t i = s.begin_i; i < s.end_i; i++) {
+    if (!((m.ctx_mask >> (p[i] & 15u)) & 1u)) continue;
+    const int64_t w = (int64_t)(int32_t)(s.start_x + i - s.offset_x) - g.pos_lo;
+    if (w >= 0 && w < g.nwin) atomicAdd(cnt + w, 1u);
+  }
+}
+
+struct PatOut {
+  int32_t *nonempty, *strand, *start, *end, *nbase, *meth;
+  unsigned long long *fnv;
+  int32_t *cells;                 // [ncol][npat0]
+  // a target's part of a batch of results: its slots begin at `rel`, its cells at `cell_off`
+  __host__ __device__ PatOut of(uint32_t rel, int64_t cell_off) const {
+    PatOut t;
+    t.nonempty = nonempty + rel; t.strand = strand + rel; t.start = start + rel; t.end = end + rel;
+    t.nbase = nbase + rel; t.meth = meth + rel; t.fnv = fnv + rel;
+    t.cells = cells + cell_off;
+    return t;
+  }
+};
+
+__device__ __forceinline__ void fnv_char(unsigned long long &h, uint32_t v) {   // four bytes through a (signed) char pointer
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    h ^= (unsigned long long)(long long)(signed char)((v >> (8 * k)) & 0xFFu);
+    h *= 1099511628211ull;
+  }
+}
+
+// row x overlaps the target (s = pat_span(m, g, x), s.ok) and is its c-th overlapping row: cells, counts and hash
+__device__ __forceinline__ void pat_extract_row(const PatMulti &m, const PatTarget &g, int64_t x, const PatSpan &s, uint32_t c,
+                                                const int32_t *__restrict__ colmap, const int32_t *__restrict__ hlght,
+                                                const int32_t *__restrict__ hcol, int64_t npat0, const PatOut &o) {
+  const uint8_t *p = m.xm + m.off[x];
+  uint32_t meth = 0, total = 0;
+  unsigned long long fnv = 14695981039346656037ull;
+  for (uint32_t i = s.begin_i; i < s.end_i; i++) {
+    const uint32_t base = p[i] & 15u;
+    if (!((m.ctx_mask >> base) & 1u)) continue;
+    const uint32_t pos = s.start_x + i - s.offset_x;
+    const int64_t w = (int64_t)(int32_t)pos - g.pos_lo;
+    if (w < 0 || w >= g.nwin) continue;
+    const int32_t col = colmap[w];
+    if (col < 0) continue;                                                   // :141
+    o.cells[(int64_t)col * npat0 + c] = (int32_t)base;                       // :143
+    meth += !(base & 8u);
+    total++;
+    fnv_char(fnv, pos);                                                      // :147
+    fnv ^= (unsigned long long)base; fnv *= 1099511628211ull;                // :148
+  }
+  const bool nonempty = fnv != 14695981039346656037ull;
+  if (nonempty) {
+    static const uint8_t factor_map[16] = {13, 3, 4, 13, 11, 13, 13, 13, 12, 13, 13, 13, 13, 13, 13, 13};   // :47
+    for (int32_t k = 0; k < g.nhl; k++) {                                    // :154-164
+      const uint32_t hp = (uint32_t)hlght[k] - s.start_x;
+      if (hp >= s.begin_i && hp < s.end_i) {
+        const uint32_t base = factor_map[(p[hp] >> 4) & 15u];
+        o.cells[(int64_t)hcol[k] * npat0 + c] = (int32_t)base;
+        fnv_char(fnv, (uint32_t)hlght[k]);
+        fnv ^= (unsigned long long)base; fnv *= 1099511628211ull;
+      }
+    }
+  }
+  o.nonempty[c] = nonempty ? 1 : 0;
+  o.strand[c] = m.strand[x];
+  o.start[c] = (int32_t)(s.start_x + s.begin_i);
+  o.end[c] = (int32_t)(s.start_x + s.end_i - 1u);
+  o.nbase[c] = (int32_t)total;
+  o.meth[c] = (int32_t)meth;
+  o.fnv[c] = fnv;
+}
+
+// last t in [a, b) with key(t) <= v, for keys that do not decrease and key(a) <= v; at most 32 steps
+template <class V, class Key> __device__ __forceinline__ int32_t pat_last_le(int32_t a, int32_t b, V v, Key key) {
+  for (int it = 0; it < 32 && b - a > 1; it++) {
+    const int32_t m = a + ((b - a) >> 1);
+    if (key(m) <= v) a = m; else b = m;
+  }
   return a;
 }
 
-// last t in [0, ng) with pre[t] <= j (pre[0] = 0 <= j < pre[ng]); at most 32 steps
+// the target of pair j (pre[0] = 0 <= j < pre[ng])
 __device__ __forceinline__ int32_t pat_target_of(const uint64_t *__restrict__ pre, int32_t ng, uint64_t j) {
-  int32_t a = 0, b = ng;
-  for (int it = 0; it < 32 && b - a > 1; it++) {
-    const int32_t m = a + ((b - a) >> 1);
-    if (pre[m] <= j) a = m; else b = m;
-  }
-  return a;
+  return pat_last_le(0, ng, j, [&](int32_t t) { return pre[t]; });
 }
 
 // first row in [0, n) with (rname, start) >= (qr, qp); at most 64 steps
@@ -205,10 +178,10 @@ __device__ __forceinline__ int64_t pat_row_lower_bound(const int32_t *__restrict
   return a;
 }
 
-// One lane per target: rng[2t], rng[2t+1] = its candidate rows, those on its rname that start in
-// [start - reach - lmax + 1, end + reach] (reach = 0 for min_overlap >= 1: pat_span accepts no other row).
+// Rows sorted by (rname, start), one lane per target: rng[2t], rng[2t+1] = its candidate rows, those on its rname that
+// start in [start - reach - lmax + 1, end + reach] (reach = 0 for min_overlap >= 1: pat_span accepts no other row).
 // rng[2 * nt] != 0: some target's rname holds a row with a negative start (pat_span's unsigned arithmetic lets such a
-// row overlap anything; the caller takes the per-target path).
+// row overlap anything; the caller runs every target against all rows).
 __global__ __launch_bounds__(256) void k_patm_ranges(const int32_t *__restrict__ rname, const int32_t *__restrict__ start, int64_t n,
                                                      const int32_t *__restrict__ tgt /* [3][nt] rname, start, end */, int32_t nt,
                                                      int64_t lmax, int64_t reach, int64_t *__restrict__ rng) {
@@ -231,11 +204,10 @@ __global__ __launch_bounds__(256) void k_patm_flag_count(PatMulti m, uint64_t np
   if (j >= npairs) return;
   const int32_t t = pat_target_of(m.pre, m.ng, j);
   const PatTarget g = m.tg[t];
-  const PatArgs a = pat_args_of(m, g);
   const int64_t x = g.row_lo + (int64_t)(j - m.pre[t]);
-  const PatSpan s = pat_span(a, x);
+  const PatSpan s = pat_span(m, g, x);
   flag[j] = s.ok ? 1u : 0u;
-  if (s.ok) pat_count_row(a, x, s, cnt + g.win_off);
+  if (s.ok) pat_count_row(m, g, x, s, cnt + g.win_off);
 }
 
 // base[t] = overlapping rows before target t's range (base[ng], the total, is the scan's)
@@ -258,13 +230,9 @@ __global__ __launch_bounds__(256) void k_patm_extract(PatMulti m, uint64_t j0, u
   const int32_t t = pat_target_of(m.pre, m.ng, j);
   const PatTarget g = m.tg[t];
   const PatSlice q = sl[t];
-  const PatArgs a = pat_args_of(m, g);
   const int64_t x = g.row_lo + (int64_t)(j - m.pre[t]);
-  PatOut ot;
-  ot.nonempty = o.nonempty + q.base_rel; ot.strand = o.strand + q.base_rel; ot.start = o.start + q.base_rel; ot.end = o.end + q.base_rel;
-  ot.nbase = o.nbase + q.base_rel; ot.meth = o.meth + q.base_rel; ot.fnv = o.fnv + q.base_rel;
-  ot.cells = o.cells + q.cell_off;
-  pat_extract_row(a, x, pat_span(a, x), cidx[j] - q.base_abs, colmap + g.win_off, hl + g.hl_off, hcol + g.hl_off, g.nhl, (int64_t)q.npat0, ot);
+  pat_extract_row(m, g, x, pat_span(m, g, x), cidx[j] - q.base_abs, colmap + g.win_off, hl + g.hl_off, hcol + g.hl_off, (int64_t)q.npat0,
+                  o.of(q.base_rel, q.cell_off));
 }
 
 // ---- unique patterns with their counts (epi_batch_summarise_patterns_multi) --------------------------------------------
@@ -295,12 +263,7 @@ constexpr unsigned long long kPatEmptyKey = 14695981039346656037ull;
 
 // last t in [sa, sb) with sl[t].base_rel <= i (targets without slots share their successor's base_rel and come before it)
 __device__ __forceinline__ int32_t pat_slot_target(const PatSlice *__restrict__ sl, int32_t sa, int32_t sb, uint32_t i) {
-  int32_t a = sa, b = sb;
-  for (int it = 0; it < 32 && b - a > 1; it++) {
-    const int32_t m = a + ((b - a) >> 1);
-    if (sl[m].base_rel <= i) a = m; else b = m;
-  }
-  return a;
+  return pat_last_le(sa, sb, i, [&](int32_t t) { return sl[t].base_rel; });
 }
 
 __global__ __launch_bounds__(256) void k_pats_init(PatEntry *__restrict__ tab, int64_t n) {
@@ -422,6 +385,7 @@ __global__ __launch_bounds__(256) void k_pats_emit(PatSum q, const uint32_t *__r
   for (uint32_t col = 0; col < ss.ncol; col++) oc[(int64_t)col * nu + lu] = c[(int64_t)col * sl.npat0 + li];
 }
 
+
 }  // namespace epi
 
 using namespace epi;
@@ -429,11 +393,119 @@ using namespace epi;
 extern "C" void epi_pattern_table_free(epi_pattern_table *t);
 extern "C" void epi_pattern_summary_free(epi_pattern_summary *t);
 
+// ---- the host side -------------------------------------------------------------------------------------------------------
+namespace {
+
+constexpr int64_t kPatGroupBytes = 256LL << 20;   // scratch cap of a group of targets (include/epihip.h)
+
+enum PatBuf {                     // the device scratch of a call
+  kTgt, kRng, kMeta, kFlag, kCidx, kCb, kColmap, kSl, kHl, kRes,
+  kSs, kTab, kSlot, kUb, kSout,   // the summary path: table slices, table, 5 x u32 per slot, bases and collide words, output
+  kPatBufs
+};
+struct PatmScratch {
+  DevBuf buf[kPatBufs];
+  size_t peak = 0;
+  DevBuf &operator[](PatBuf i) { return buf[i]; }
+  void note() {
+    size_t v = 0;
+    for (const DevBuf &d : buf) v += d.cap;
+    if (v > peak) peak = v;
+  }
+  ~PatmScratch() { for (DevBuf &d : buf) d.release(); }
+};
+
+struct PatmStats { int64_t groups = 0, pairs = 0, scratch = 0, fallback = 0; };
+
+struct PatmCall {                 // what every group of a call shares
+  epi_batch *b;
+  hipStream_t s;
+  const char *entry, *label;      // whose errors and whose profiler label the launches go under
+  const int32_t *t_rname, *t_start, *t_end;
+  const int64_t *rng;             // [2 * ntargets] the candidate rows of target t: [rng[2t], rng[2t + 1])
+  const int64_t *pos_lo, *nwin;   // [ntargets]
+  const int32_t *hlght;
+  const int64_t *hlght_off;       // may be null
+  double min_ctx_freq;
+  int64_t cap;
+  PatMulti m;                     // tg / pre / ng filled per group
+  epi_pattern_table *out;         // the tables, or ...
+  epi_pattern_summary *sum;       // ... the summaries (exactly one of the two is set)
+  unsigned long long key_mask;    // the bits of the hash the summary groups by (EPIHIP_PAT_HASH_BITS)
+  PatmStats *st;
+};
+
+struct PatGroup {                 // targets [ta, ta + ng) of a call, as the steps of patm_group hand them on
+  int32_t ta = 0, ng = 0;
+  std::vector<uint64_t> meta;     // as the device reads it: pre[ng + 1], then tg[ng]
+  const uint64_t *pre = nullptr;
+  const PatTarget *tg = nullptr;
+  int64_t W = 0, H = 0, hl0 = 0;  // window and highlight positions of the group; its first highlight position in c.hlght
+  PatMulti m;                     // the call's, with the group's pre / tg on the device
+  size_t nbase = 0;               // base[ng + 1], padded to an even count
+  std::vector<uint32_t> h_cb;     // pass 1, fetched: base[nbase], cnt[W]
+  std::vector<std::vector<int32_t>> cols;   // the plan: per target its column positions,
+  std::vector<int32_t> h_colmap, h_hl;      // colmap[W]; hl[H], hcol[H],
+  std::vector<PatSlice> sl;
+  std::vector<PatSumSlice> ss;    // (summaries only)
+  std::vector<int32_t> cuts;      // and cell batch i: targets [cuts[i], cuts[i + 1])
+  const uint32_t *h_base() const { return h_cb.data(); }
+  const uint32_t *h_cnt() const { return h_cb.data() + nbase; }
+};
+
+struct PatBatch {                 // a cell batch: targets [sa, sb) of a group, their Ps slots and C cells, in `o` after pass 2
+  int32_t sa, sb;
+  size_t Ps, C;
+  PatOut o;
+};
+
+// the per-slot arrays and the cells of ns slots in one buffer: [fnv u64][nonempty, strand, start, end, nbase, meth i32] x ns, cells
+PatOut pat_out_at(void *base, size_t ns) {
+  PatOut o;
+  o.fnv = reinterpret_cast<unsigned long long *>(base);                // 8-byte aligned first
+  int32_t *q = reinterpret_cast<int32_t *>(base) + 2 * ns;
+  o.nonempty = q; o.strand = q + ns; o.start = q + 2 * ns; o.end = q + 3 * ns; o.nbase = q + 4 * ns; o.meth = q + 5 * ns;
+  o.cells = q + 6 * ns;
+  return o;
+}
+
+// the longest row (it bounds the window of positions); refuses a batch whose rows are not well-formed
+int pat_longest_row(epi_batch *b, hipStream_t s, int64_t *lmax) {
+  EPI_TRY(fetch_row_stats(b, s));
+  if (b->h_stats.bad_len) return fail(EPI_ERR_ARG, "offsets are not non-decreasing, or start+length exceeds int32");
+  *lmax = b->h_stats.max_len;
+  return EPI_OK;
+}
+
+// the window of positions the rows that overlap a target can name: [pos_lo, pos_lo + nwin)
+int pat_window(int32_t start, int32_t end, int64_t lmax, int32_t reverse_offset, int64_t *pos_lo, int64_t *nwin) {
+  *pos_lo = (int64_t)start - lmax - (int64_t)reverse_offset - 2;
+  *nwin = ((int64_t)end - (int64_t)start) + 2 * lmax + (int64_t)reverse_offset + 8;
+  if (*nwin < 1) *nwin = 1;
+  if (*nwin > (1LL << 31)) return fail(EPI_ERR_ARG, "epi_batch_extract_patterns: target too wide");
+  return EPI_OK;
+}
+
+// what a call's groups share, but for its targets, results and statistics
+PatmCall patm_call(epi_batch *b, hipStream_t s, int32_t min_overlap, const char *ctx, double min_ctx_freq, int32_t clip,
+                   int32_t reverse_offset) {
+  PatmCall c = {};
+  c.b = b; c.s = s; c.min_ctx_freq = min_ctx_freq;
+  c.entry = "epi_batch_extract_patterns_multi"; c.label = "extract_patterns_multi";
+  const int hb = options().pat_hash_bits;
+  c.key_mask = hb >= 1 && hb <= 63 ? (1ull << hb) - 1ull : ~0ull;
+  c.cap = options().pat_group_bytes > 0 ? options().pat_group_bytes : kPatGroupBytes;
+  c.m.xm = b->xm; c.m.off = b->off; c.m.len = b->len; c.m.rname = b->rname; c.m.strand = b->strand; c.m.start = b->start;
+  c.m.reverse_offset = (uint32_t)reverse_offset; c.m.min_overlap = min_overlap; c.m.clip = clip ? 1 : 0;
+  c.m.ctx_mask = ctx_mask_of(ctx);
+  return c;
+}
+
 // The host's decision between the two passes: valid positions = seen in >= min_ctx_freq of the npat0 overlapping reads
 // and not highlighted (:103-108), the highlight positions (:110-112), merged in position order (:185).  cnt / colmap:
 // the nwin positions from pos_lo on (colmap: column of a valid position, else -1); hcol[k]: column of hlght[k].
-static void pat_choose_columns(const uint32_t *cnt, int64_t nwin, int64_t pos_lo, uint32_t npat0, double min_ctx_freq,
-                               const int32_t *hlght, int32_t nhlght, std::vector<int32_t> &cols, int32_t *colmap, int32_t *hcol) {
+void pat_choose_columns(const uint32_t *cnt, int64_t nwin, int64_t pos_lo, uint32_t npat0, double min_ctx_freq,
+                        const int32_t *hlght, int32_t nhlght, std::vector<int32_t> &cols, int32_t *colmap, int32_t *hcol) {
   cols.clear();
   for (int64_t w = 0; w < nwin; w++) {
     colmap[w] = -1;
@@ -450,13 +522,11 @@ static void pat_choose_columns(const uint32_t *cnt, int64_t nwin, int64_t pos_lo
   for (int32_t k = 0; k < nhlght; k++) hcol[k] = (int32_t)(std::lower_bound(cols.begin(), cols.end(), hlght[k]) - cols.begin());
 }
 
-// The table of one target from the P0 slots its overlapping rows filled: keeps the non-empty patterns, in row order
-// (:152, :166-176).  cells: [ncol][P0].
-static int pat_fill_table(epi_pattern_table *out, size_t P0, int32_t ncol, const int32_t *cols, const int32_t *nonempty,
-                          const int32_t *strand, const int32_t *start, const int32_t *end, const int32_t *nbase, const int32_t *meth,
-                          const unsigned long long *fnv, const int32_t *cells) {
+// The table of one target from the P0 slots its overlapping rows filled (o: on the host, cells [ncol][P0]): keeps the
+// non-empty patterns, in row order (:152, :166-176).
+int pat_fill_table(epi_pattern_table *out, size_t P0, int32_t ncol, const int32_t *cols, const PatOut &o) {
   size_t np = 0;
-  for (size_t c = 0; c < P0; c++) np += nonempty[c] != 0;
+  for (size_t c = 0; c < P0; c++) np += o.nonempty[c] != 0;
   if (np == 0) return EPI_OK;
   out->npat = (int64_t)np;
   out->ncol = ncol;
@@ -471,148 +541,16 @@ static int pat_fill_table(epi_pattern_table *out, size_t P0, int32_t ncol, const
   memcpy(out->positions, cols, (size_t)ncol * 4);
   size_t w = 0;
   for (size_t c = 0; c < P0; c++) {
-    if (!nonempty[c]) continue;
-    out->strand[w] = strand[c]; out->start[w] = start[c]; out->end[w] = end[c];
-    out->nbase[w] = nbase[c];
-    out->beta[w] = (double)(uint32_t)meth[c] / (uint32_t)nbase[c];                                // :173
-    out->fnv[w] = fnv[c];
-    for (int32_t k = 0; k < ncol; k++) out->cells[(size_t)k * np + w] = cells[(size_t)k * P0 + c];
+    if (!o.nonempty[c]) continue;
+    out->strand[w] = o.strand[c]; out->start[w] = o.start[c]; out->end[w] = o.end[c];
+    out->nbase[w] = o.nbase[c];
+    out->beta[w] = (double)(uint32_t)o.meth[c] / (uint32_t)o.nbase[c];                            // :173
+    out->fnv[w] = o.fnv[c];
+    for (int32_t k = 0; k < ncol; k++) out->cells[(size_t)k * np + w] = o.cells[(size_t)k * P0 + c];
     w++;
   }
   return EPI_OK;
 }
-
-extern "C" {
-
-void epi_pattern_table_free(epi_pattern_table *t) {
-  if (!t) return;
-  free(t->positions); free(t->strand); free(t->start); free(t->end); free(t->nbase); free(t->beta); free(t->fnv); free(t->cells);
-  memset(t, 0, sizeof(*t));
-}
-
-int epi_batch_extract_patterns(epi_batch *b, int32_t target_rname, int32_t target_start, int32_t target_end, int32_t min_overlap,
-                               const char *ctx, double min_ctx_freq, int32_t clip, int32_t reverse_offset, const int32_t *hlght,
-                               int32_t nhlght, void *stream, epi_pattern_table *out) {
-  if (!b || !ctx || !out || nhlght < 0 || (nhlght > 0 && !hlght)) return fail(EPI_ERR_ARG, "epi_batch_extract_patterns: bad arguments");
-  memset(out, 0, sizeof(*out));
-  if (b->n == 0) return EPI_OK;
-  EPI_HIP(hipSetDevice(b->eng->device));
-  hipStream_t s = pick_stream(b, stream);
-  EPI_TRY(fetch_row_stats(b, s));                           // the longest read bounds the window of positions
-  if (b->h_stats.bad_len) return fail(EPI_ERR_ARG, "offsets are not non-decreasing, or start+length exceeds int32");
-  const int64_t lmax = b->h_stats.max_len;
-
-  PatArgs a;
-  a.xm = b->xm; a.off = b->off; a.len = b->len; a.rname = b->rname; a.strand = b->strand; a.start = b->start; a.n = b->n;
-  a.target_rname = (uint32_t)target_rname; a.target_start = (uint32_t)target_start; a.target_end = (uint32_t)target_end;
-  a.reverse_offset = (uint32_t)reverse_offset; a.min_overlap = min_overlap; a.clip = clip ? 1 : 0;
-  a.ctx_mask = 0;
-  for (const unsigned char *c = reinterpret_cast<const unsigned char *>(ctx); *c; c++) a.ctx_mask |= 1u << ctx_to_idx(*c);
-  a.pos_lo = (int64_t)target_start - lmax - (int64_t)reverse_offset - 2;
-  a.nwin = ((int64_t)target_end - (int64_t)target_start) + 2 * lmax + (int64_t)reverse_offset + 8;
-  if (a.nwin < 1) a.nwin = 1;
-  if (a.nwin > (1LL << 31)) return fail(EPI_ERR_ARG, "epi_batch_extract_patterns: target too wide");
-
-  const unsigned nb = (unsigned)((b->n + 255) / 256);
-  DevBuf flag, cidx, cnt, colmap, d_hl, d_hc, outbuf, cells;
-  auto cleanup = [&]() { flag.release(); cidx.release(); cnt.release(); colmap.release(); d_hl.release(); d_hc.release(); outbuf.release(); cells.release(); };
-#define PAT_TRY(x) do { int rc_ = (x); if (rc_ != EPI_OK) { cleanup(); return rc_; } } while (0)
-#define PAT_HIP(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { cleanup(); return fail(EPI_ERR_HIP, "%s: %s", #x, hipGetErrorString(e_)); } } while (0)
-  PAT_TRY(flag.ensure((size_t)b->n * 4));
-  PAT_TRY(cidx.ensure((size_t)b->n * 4));
-  PAT_TRY(cnt.ensure((size_t)a.nwin * 4));
-  PAT_TRY(colmap.ensure((size_t)a.nwin * 4));
-  PAT_TRY(b->misc.ensure(256));
-  uint32_t *d_total = &report_scalars(b)->pat_total;
-  hipLaunchKernelGGL(k_pat_flag, dim3(nb), dim3(256), 0, s, a, flag.as<uint32_t>());
-  PAT_TRY(scan_exclusive_u32(flag.as<uint32_t>(), cidx.as<uint32_t>(), b->n, d_total, b->scan_tmp, s));
-  PAT_HIP(hipMemsetAsync(cnt.p, 0, (size_t)a.nwin * 4, s));
-  hipLaunchKernelGGL(k_pat_count, dim3(nb), dim3(256), 0, s, a, flag.as<uint32_t>(), cnt.as<uint32_t>());
-  PAT_HIP(hipGetLastError());
-  uint32_t npat0 = 0;
-  PAT_TRY(read_scalars(b, s, d_total, 4, &npat0));
-  if (npat0 == 0) { cleanup(); return EPI_OK; }             // no read overlaps the target: empty table (:183)
-  std::vector<uint32_t> h_cnt((size_t)a.nwin);
-  PAT_HIP(hipMemcpy(h_cnt.data(), cnt.p, (size_t)a.nwin * 4, hipMemcpyDeviceToHost));
-
-  std::vector<int32_t> cols;
-  std::vector<int32_t> h_colmap((size_t)a.nwin), h_hcol((size_t)(nhlght > 0 ? nhlght : 1), 0);
-  pat_choose_columns(h_cnt.data(), a.nwin, a.pos_lo, npat0, min_ctx_freq, hlght, nhlght, cols, h_colmap.data(), h_hcol.data());
-  const int32_t ncol = (int32_t)cols.size();
-  PAT_HIP(hipMemcpy(colmap.p, h_colmap.data(), (size_t)a.nwin * 4, hipMemcpyHostToDevice));
-  PAT_TRY(d_hl.ensure((size_t)(nhlght > 0 ? nhlght : 1) * 4));
-  PAT_TRY(d_hc.ensure((size_t)(nhlght > 0 ? nhlght : 1) * 4));
-  if (nhlght > 0) {
-    PAT_HIP(hipMemcpy(d_hl.p, hlght, (size_t)nhlght * 4, hipMemcpyHostToDevice));
-    PAT_HIP(hipMemcpy(d_hc.p, h_hcol.data(), (size_t)nhlght * 4, hipMemcpyHostToDevice));
-  }
-  const size_t P0 = npat0;
-  PAT_TRY(outbuf.ensure(P0 * (6 * 4 + 8) + 64));
-  PAT_TRY(cells.ensure((size_t)(ncol > 0 ? ncol : 1) * P0 * 4));
-  PatOut o;
-  int32_t *ip = outbuf.as<int32_t>();
-  o.fnv = reinterpret_cast<unsigned long long *>(ip);                  // 8-byte aligned first
-  int32_t *q = ip + 2 * P0;
-  o.nonempty = q; o.strand = q + P0; o.start = q + 2 * P0; o.end = q + 3 * P0; o.nbase = q + 4 * P0; o.meth = q + 5 * P0;
-  o.cells = cells.as<int32_t>();
-  PAT_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(cells.p), INT32_MIN, (size_t)(ncol > 0 ? ncol : 1) * P0, s));   // NA_INTEGER
-  hipLaunchKernelGGL(k_pat_extract, dim3(nb), dim3(256), 0, s, a, flag.as<uint32_t>(), cidx.as<uint32_t>(), colmap.as<int32_t>(),
-                     d_hl.as<int32_t>(), d_hc.as<int32_t>(), nhlght, (int64_t)P0, o);
-  PAT_HIP(hipGetLastError());
-  PAT_HIP(hipStreamSynchronize(s));
-  std::vector<int32_t> h_i(6 * P0), h_cells((size_t)(ncol > 0 ? ncol : 1) * P0);
-  std::vector<unsigned long long> h_f(P0);
-  PAT_HIP(hipMemcpy(h_f.data(), o.fnv, P0 * 8, hipMemcpyDeviceToHost));
-  PAT_HIP(hipMemcpy(h_i.data(), o.nonempty, 6 * P0 * 4, hipMemcpyDeviceToHost));
-  PAT_HIP(hipMemcpy(h_cells.data(), cells.p, h_cells.size() * 4, hipMemcpyDeviceToHost));
-  cleanup();
-#undef PAT_TRY
-#undef PAT_HIP
-
-  const int32_t *r = h_i.data();
-  return pat_fill_table(out, P0, ncol, cols.data(), r, r + P0, r + 2 * P0, r + 3 * P0, r + 4 * P0, r + 5 * P0, h_f.data(), h_cells.data());
-}
-
-}  // extern "C"
-
-// ---- epi_batch_extract_patterns_multi ---------------------------------------------------------------------------------
-namespace {
-
-constexpr int64_t kPatGroupBytes = 256LL << 20;   // scratch cap of a group of targets (include/epihip.h)
-
-struct PatmScratch {
-  DevBuf tgt, rng, meta, flag, cidx, cb, colmap, sl, hl, res;
-  DevBuf ss, tab, slot, ub, sout;   // the summary path: table slices, table, 5 x u32 per slot, bases and collide words, output
-  size_t peak = 0;
-  void note() {
-    const size_t v = tgt.cap + rng.cap + meta.cap + flag.cap + cidx.cap + cb.cap + colmap.cap + sl.cap + hl.cap + res.cap +
-                     ss.cap + tab.cap + slot.cap + ub.cap + sout.cap;
-    if (v > peak) peak = v;
-  }
-  ~PatmScratch() {
-    tgt.release(); rng.release(); meta.release(); flag.release(); cidx.release(); cb.release(); colmap.release(); sl.release(); hl.release(); res.release();
-    ss.release(); tab.release(); slot.release(); ub.release(); sout.release();
-  }
-};
-
-struct PatmStats { int64_t groups = 0, pairs = 0, scratch = 0, fallback = 0; };
-
-struct PatmCall {                 // what every group of a call shares
-  epi_batch *b;
-  hipStream_t s;
-  const int32_t *t_rname, *t_start, *t_end;
-  const int64_t *row_lo, *row_hi; // [ntargets]
-  const int64_t *pos_lo, *nwin;   // [ntargets]
-  const int32_t *hlght;
-  const int64_t *hlght_off;       // may be null
-  double min_ctx_freq;
-  int64_t cap;
-  PatMulti m;                     // tg / pre / ng filled per group
-  epi_pattern_table *out;         // the tables, or ...
-  epi_pattern_summary *sum;       // ... the summaries (exactly one of the two is set)
-  unsigned long long key_mask;    // the bits of the hash the summary groups by (EPIHIP_PAT_HASH_BITS)
-  PatmStats *st;
-};
 
 // capacity of a target's table slice: the power of two >= 2 x its slots, 8 at the least (no slots: no slice)
 int64_t pat_table_capacity(uint32_t npat0) {
@@ -676,227 +614,337 @@ int pat_summarise_host(epi_pattern_summary *out, size_t P0, int32_t ncol, const 
   return pat_fill_summary(out, U, ncol, cols, ufnv.data(), count.data(), ucells.data());
 }
 
-// The summaries of the group's targets [sa, sb), whose Ps slots and C cells pass 2 has just left in `o`: table, verify,
-// scans and emit on the device, then two host synchronisations (the unique counts and collide words; the unique rows) and a
-// third when targets are regrouped on the host (their slots).
-int patm_summarise_batch(PatmCall &c, PatmScratch &w, const std::vector<PatSlice> &sl, const std::vector<PatSumSlice> &ss,
-                         const std::vector<std::vector<int32_t>> &cols, int32_t ta, int32_t sa, int32_t sb, size_t Ps, size_t C,
-                         const PatOut &o) {
+// ---- the summaries of a cell batch ---------------------------------------------------------------------------------------
+// Groups the batch's slots on the device: table, verify, scans and emit.  Fetches ubase[nb + 1], wbase[nb + 1] and the
+// collide words [nb] into h_ub.
+int pats_group_fetch_counts(PatmCall &c, PatmScratch &w, const PatBatch &bt, int64_t TE, std::vector<uint32_t> &h_ub) {
   hipStream_t s = c.s;
-  const int32_t nb = sb - sa;
-  int64_t TE = 0;
-  for (int32_t k = sa; k < sb; k++) TE += pat_table_capacity(sl[(size_t)k].npat0);
-  const bool on_device = Ps < (1u << 30) && C < (1u << 31) && TE < (1LL << 32);    // u32 slot and cell indices
-  std::vector<uint32_t> h_ub(3 * (size_t)nb + 2, 0);          // ubase[nb + 1], wbase[nb + 1], collide[nb]
-  std::vector<uint64_t> h_out;
-  if (on_device) {
-    const int64_t nbs = (int64_t)((Ps + 255) / 256), nbt = (TE + 255) / 256;
-    EPI_TRY(check_grid(nbs, 256, "epi_batch_summarise_patterns_multi"));
-    EPI_TRY(check_grid(nbt, 256, "epi_batch_summarise_patterns_multi"));
-    EPI_TRY(w.tab.ensure((size_t)TE * sizeof(PatEntry)));
-    EPI_TRY(w.slot.ensure(5 * Ps * 4));
-    EPI_TRY(w.ub.ensure(h_ub.size() * 4));
-    EPI_TRY(w.sout.ensure(12 * Ps + 4 * C + 16));
-    w.note();
-    uint32_t *ent = w.slot.as<uint32_t>(), *first = ent + Ps, *wfirst = ent + 2 * Ps, *uidx = ent + 3 * Ps, *widx = ent + 4 * Ps;
-    uint32_t *ubase = w.ub.as<uint32_t>(), *wbase = ubase + nb + 1, *collide = wbase + nb + 1;
-    PatSum q;
-    q.sl = w.sl.as<PatSlice>(); q.ss = w.ss.as<PatSumSlice>(); q.sa = sa; q.sb = sb; q.nslot = (uint32_t)Ps;
-    q.fnv = o.fnv; q.nonempty = o.nonempty; q.cells = o.cells;
-    q.tab = w.tab.as<PatEntry>(); q.ent = ent; q.collide = collide; q.key_mask = c.key_mask;
-    EPI_HIP(hipMemsetAsync(w.ub.p, 0, h_ub.size() * 4, s));
-    prof_begin("summarise_patterns", s);
-    hipLaunchKernelGGL(k_pats_init, dim3((unsigned)nbt), dim3(256), 0, s, q.tab, TE);
-    prof_begin("summarise_patterns_insert", s);
-    hipLaunchKernelGGL(k_pats_insert, dim3((unsigned)nbs), dim3(256), 0, s, q);
-    prof_end("summarise_patterns_insert", s);
-    hipLaunchKernelGGL(k_pats_verify, dim3((unsigned)nbs), dim3(256), 0, s, q, first, wfirst);
-    EPI_TRY(scan_exclusive_u32(first, uidx, (int64_t)Ps, ubase + nb, c.b->scan_tmp, s));
-    EPI_TRY(scan_exclusive_u32(wfirst, widx, (int64_t)Ps, wbase + nb, c.b->scan_tmp, s));
-    hipLaunchKernelGGL(k_pats_bases, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, s, q.sl, sa, nb, q.nslot, uidx, widx, ubase, wbase);
-    hipLaunchKernelGGL(k_pats_emit, dim3((unsigned)nbs), dim3(256), 0, s, q, first, uidx, ubase, wbase, w.sout.as<unsigned long long>());
-    EPI_HIP(hipGetLastError());
-    prof_end("summarise_patterns", s);
-    EPI_HIP(hipMemcpyAsync(h_ub.data(), w.ub.p, h_ub.size() * 4, hipMemcpyDeviceToHost, s));
-    EPI_HIP(hipStreamSynchronize(s));
-    const size_t U = h_ub[(size_t)nb], WC = h_ub[2 * (size_t)nb + 1];
-    if (U > Ps || WC > C) return fail(EPI_ERR_STATE, "epi_batch_summarise_patterns_multi: more unique rows than slots");
-    h_out.resize((12 * U + 4 * WC + 7) / 8 + 1);
-    if (U) {
-      EPI_HIP(hipMemcpyAsync(h_out.data(), w.sout.p, 12 * U + 4 * WC, hipMemcpyDeviceToHost, s));
-      EPI_HIP(hipStreamSynchronize(s));
-    }
-  } else {
-    EPI_HIP(hipStreamSynchronize(s));
-  }
+  const int32_t nb = bt.sb - bt.sa;
+  const size_t Ps = bt.Ps;
+  const int64_t nbs = (int64_t)((Ps + 255) / 256), nbt = (TE + 255) / 256;
+  EPI_TRY(check_grid(nbs, 256, "epi_batch_summarise_patterns_multi"));
+  EPI_TRY(check_grid(nbt, 256, "epi_batch_summarise_patterns_multi"));
+  EPI_TRY(w[kTab].ensure((size_t)TE * sizeof(PatEntry)));
+  EPI_TRY(w[kSlot].ensure(5 * Ps * 4));
+  EPI_TRY(w[kUb].ensure(h_ub.size() * 4));
+  EPI_TRY(w[kSout].ensure(12 * Ps + 4 * bt.C + 16));
+  w.note();
+  uint32_t *ent = w[kSlot].as<uint32_t>(), *first = ent + Ps, *wfirst = ent + 2 * Ps, *uidx = ent + 3 * Ps, *widx = ent + 4 * Ps;
+  uint32_t *ubase = w[kUb].as<uint32_t>(), *wbase = ubase + nb + 1, *collide = wbase + nb + 1;
+  PatSum q;
+  q.sl = w[kSl].as<PatSlice>(); q.ss = w[kSs].as<PatSumSlice>(); q.sa = bt.sa; q.sb = bt.sb; q.nslot = (uint32_t)Ps;
+  q.fnv = bt.o.fnv; q.nonempty = bt.o.nonempty; q.cells = bt.o.cells;
+  q.tab = w[kTab].as<PatEntry>(); q.ent = ent; q.collide = collide; q.key_mask = c.key_mask;
+  EPI_HIP(hipMemsetAsync(w[kUb].p, 0, h_ub.size() * 4, s));
+  prof_begin("summarise_patterns", s);
+  hipLaunchKernelGGL(k_pats_init, dim3((unsigned)nbt), dim3(256), 0, s, q.tab, TE);
+  prof_begin("summarise_patterns_insert", s);
+  hipLaunchKernelGGL(k_pats_insert, dim3((unsigned)nbs), dim3(256), 0, s, q);
+  prof_end("summarise_patterns_insert", s);
+  hipLaunchKernelGGL(k_pats_verify, dim3((unsigned)nbs), dim3(256), 0, s, q, first, wfirst);
+  EPI_TRY(scan_exclusive_u32(first, uidx, (int64_t)Ps, ubase + nb, c.b->scan_tmp, s));
+  EPI_TRY(scan_exclusive_u32(wfirst, widx, (int64_t)Ps, wbase + nb, c.b->scan_tmp, s));
+  hipLaunchKernelGGL(k_pats_bases, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, s, q.sl, bt.sa, nb, q.nslot, uidx, widx, ubase, wbase);
+  hipLaunchKernelGGL(k_pats_emit, dim3((unsigned)nbs), dim3(256), 0, s, q, first, uidx, ubase, wbase, w[kSout].as<unsigned long long>());
+  EPI_HIP(hipGetLastError());
+  prof_end("summarise_patterns", s);
+  EPI_HIP(hipMemcpyAsync(h_ub.data(), w[kUb].p, h_ub.size() * 4, hipMemcpyDeviceToHost, s));
+  EPI_HIP(hipStreamSynchronize(s));
+  return EPI_OK;
+}
+
+// Fetches the U unique rows the device emitted: [fnv u64 x U][count u32 x U][cells i32, per target [ncol][nuniq]]
+int pats_fetch_unique_rows(PatmCall &c, PatmScratch &w, const PatBatch &bt, const std::vector<uint32_t> &h_ub, std::vector<uint64_t> &h_out) {
+  const size_t nb = (size_t)(bt.sb - bt.sa), U = h_ub[nb], WC = h_ub[2 * nb + 1];
+  if (U > bt.Ps || WC > bt.C) return fail(EPI_ERR_STATE, "epi_batch_summarise_patterns_multi: more unique rows than slots");
+  h_out.resize((12 * U + 4 * WC + 7) / 8 + 1);
+  if (!U) return EPI_OK;
+  EPI_HIP(hipMemcpyAsync(h_out.data(), w[kSout].p, 12 * U + 4 * WC, hipMemcpyDeviceToHost, c.s));
+  EPI_HIP(hipStreamSynchronize(c.s));
+  return EPI_OK;
+}
+
+// The summaries of the batch's targets from the device's unique rows.  -> regroup: the targets in which two patterns share
+// a key, or all of them when the batch was too large for the device's indices; counted as grouped on the host.
+int pats_fill_from_device(PatmCall &c, const PatGroup &g, const PatBatch &bt, bool on_device, const std::vector<uint32_t> &h_ub,
+                          const std::vector<uint64_t> &h_out, std::vector<int32_t> &regroup) {
+  const int32_t nb = bt.sb - bt.sa;
   const uint32_t *ubase = h_ub.data(), *wbase = ubase + nb + 1, *collide = wbase + nb + 1;
   const size_t U = ubase[nb];
   const uint64_t *u_fnv = h_out.data();
   const int32_t *u_count = reinterpret_cast<const int32_t *>(h_out.data() + U), *u_cells = u_count + U;
-  struct Slots { int32_t k; std::vector<uint64_t> fnv; std::vector<int32_t> nonempty, cells; };
-  std::vector<Slots> back;                                    // the targets the host groups after all, their slots fetched
-  for (int32_t k = sa; k < sb; k++) {
-    const PatSlice &q1 = sl[(size_t)k];
-    if (!q1.npat0) continue;
-    const std::vector<int32_t> &ck = cols[(size_t)k];
-    const int32_t ncol = (int32_t)ck.size();
-    if (on_device && !collide[k - sa]) {
-      EPI_TRY(pat_fill_summary(c.sum + ta + k, ubase[k - sa + 1] - ubase[k - sa], ncol, ck.data(), u_fnv + ubase[k - sa],
-                               u_count + ubase[k - sa], u_cells + wbase[k - sa]));
+  for (int32_t k = bt.sa; k < bt.sb; k++) {
+    if (!g.sl[(size_t)k].npat0) continue;
+    if (!on_device || collide[k - bt.sa]) {
+      c.st->fallback++;
+      regroup.push_back(k);
       continue;
     }
-    // two patterns of this target share a key (or the batch is too large for the device's indices)
-    c.st->fallback++;
-    const size_t n0 = q1.npat0;
-    back.emplace_back();
-    Slots &f = back.back();
-    f.k = k; f.fnv.resize(n0); f.nonempty.resize(n0); f.cells.resize((size_t)ncol * n0 + 1);
-    EPI_HIP(hipMemcpyAsync(f.fnv.data(), o.fnv + q1.base_rel, n0 * 8, hipMemcpyDeviceToHost, s));
-    EPI_HIP(hipMemcpyAsync(f.nonempty.data(), o.nonempty + q1.base_rel, n0 * 4, hipMemcpyDeviceToHost, s));
-    if (ncol) EPI_HIP(hipMemcpyAsync(f.cells.data(), o.cells + q1.cell_off, (size_t)ncol * n0 * 4, hipMemcpyDeviceToHost, s));
-  }
-  if (!back.empty()) EPI_HIP(hipStreamSynchronize(s));
-  for (const Slots &f : back) {
-    const std::vector<int32_t> &ck = cols[(size_t)f.k];
-    EPI_TRY(pat_summarise_host(c.sum + ta + f.k, sl[(size_t)f.k].npat0, (int32_t)ck.size(), ck.data(), f.nonempty.data(), f.fnv.data(),
-                               f.cells.data()));
+    const std::vector<int32_t> &ck = g.cols[(size_t)k];
+    const uint32_t u0 = ubase[k - bt.sa];
+    EPI_TRY(pat_fill_summary(c.sum + g.ta + k, ubase[k - bt.sa + 1] - u0, (int32_t)ck.size(), ck.data(), u_fnv + u0, u_count + u0,
+                             u_cells + wbase[k - bt.sa]));
   }
   return EPI_OK;
 }
 
-// targets [ta, tb): two passes, three host synchronisations (plus one per further cell batch; the summaries: two per cell batch)
-int patm_group(PatmCall &c, PatmScratch &w, int32_t ta, int32_t tb) {
-  epi_batch *b = c.b;
-  hipStream_t s = c.s;
+// The summaries of the targets of `regroup` by the host's grouping: fetches the slots pass 2 left for them
+int pats_regroup_on_host(PatmCall &c, const PatGroup &g, const PatBatch &bt, const std::vector<int32_t> &regroup) {
+  struct Slots { std::vector<uint64_t> fnv; std::vector<int32_t> nonempty, cells; };
+  std::vector<Slots> back(regroup.size());
+  for (size_t i = 0; i < regroup.size(); i++) {
+    const PatSlice &q = g.sl[(size_t)regroup[i]];
+    const size_t n0 = q.npat0, ncol = g.cols[(size_t)regroup[i]].size();
+    Slots &f = back[i];
+    f.fnv.resize(n0); f.nonempty.resize(n0); f.cells.resize(ncol * n0 + 1);
+    EPI_HIP(hipMemcpyAsync(f.fnv.data(), bt.o.fnv + q.base_rel, n0 * 8, hipMemcpyDeviceToHost, c.s));
+    EPI_HIP(hipMemcpyAsync(f.nonempty.data(), bt.o.nonempty + q.base_rel, n0 * 4, hipMemcpyDeviceToHost, c.s));
+    if (ncol) EPI_HIP(hipMemcpyAsync(f.cells.data(), bt.o.cells + q.cell_off, ncol * n0 * 4, hipMemcpyDeviceToHost, c.s));
+  }
+  EPI_HIP(hipStreamSynchronize(c.s));
+  for (size_t i = 0; i < regroup.size(); i++) {
+    const std::vector<int32_t> &ck = g.cols[(size_t)regroup[i]];
+    EPI_TRY(pat_summarise_host(c.sum + g.ta + regroup[i], g.sl[(size_t)regroup[i]].npat0, (int32_t)ck.size(), ck.data(), back[i].nonempty.data(),
+                               back[i].fnv.data(), back[i].cells.data()));
+  }
+  return EPI_OK;
+}
+
+// The summaries of a batch whose slots pass 2 has just left on the device: two host synchronisations (the counts, the
+// unique rows) and a third when targets are regrouped on the host (their slots).
+int patm_summarise_batch(PatmCall &c, PatmScratch &w, const PatGroup &g, const PatBatch &bt) {
+  const int32_t nb = bt.sb - bt.sa;
+  int64_t TE = 0;
+  for (int32_t k = bt.sa; k < bt.sb; k++) TE += pat_table_capacity(g.sl[(size_t)k].npat0);
+  const bool on_device = bt.Ps < (1u << 30) && bt.C < (1u << 31) && TE < (1LL << 32);    // u32 slot and cell indices
+  std::vector<uint32_t> h_ub(3 * (size_t)nb + 2, 0);          // ubase[nb + 1], wbase[nb + 1], collide[nb]
+  std::vector<uint64_t> h_out;
+  if (on_device) {
+    EPI_TRY(pats_group_fetch_counts(c, w, bt, TE, h_ub));
+    EPI_TRY(pats_fetch_unique_rows(c, w, bt, h_ub, h_out));
+  } else {
+    EPI_HIP(hipStreamSynchronize(c.s));
+  }
+  std::vector<int32_t> regroup;
+  EPI_TRY(pats_fill_from_device(c, g, bt, on_device, h_ub, h_out, regroup));
+  return regroup.empty() ? EPI_OK : pats_regroup_on_host(c, g, bt, regroup);
+}
+
+// ---- a group of targets ----------------------------------------------------------------------------------------------------
+// what the device reads of targets [ta, tb): every target's rows, window and highlight positions, the pairs before it
+void patm_layout(const PatmCall &c, int32_t ta, int32_t tb, PatGroup &g) {
   const int32_t ng = tb - ta;
-  std::vector<uint64_t> meta((size_t)(ng + 1) + ((size_t)ng * sizeof(PatTarget) + 7) / 8);
-  uint64_t *pre = meta.data();
-  PatTarget *tg = reinterpret_cast<PatTarget *>(meta.data() + ng + 1);
-  const int64_t hl0 = c.hlght_off ? c.hlght_off[ta] : 0;
-  int64_t W = 0;
+  g.ta = ta; g.ng = ng;
+  g.meta.assign((size_t)(ng + 1) + ((size_t)ng * sizeof(PatTarget) + 7) / 8, 0);
+  uint64_t *pre = g.meta.data();
+  PatTarget *tg = reinterpret_cast<PatTarget *>(g.meta.data() + ng + 1);
+  g.hl0 = c.hlght_off ? c.hlght_off[ta] : 0;
+  g.H = c.hlght_off ? c.hlght_off[tb] - g.hl0 : 0;
+  g.W = 0;
   pre[0] = 0;
   for (int32_t k = 0; k < ng; k++) {
     const int32_t t = ta + k;
-    PatTarget &g = tg[k];
-    g.row_lo = c.row_lo[t]; g.pos_lo = c.pos_lo[t]; g.nwin = c.nwin[t]; g.win_off = W;
-    g.hl_off = c.hlght_off ? c.hlght_off[t] - hl0 : 0;
-    g.nhl = c.hlght_off ? (int32_t)(c.hlght_off[t + 1] - c.hlght_off[t]) : 0;
-    g.rname = c.t_rname[t]; g.start = c.t_start[t]; g.end = c.t_end[t];
-    W += g.nwin;
-    pre[k + 1] = pre[k] + (uint64_t)(c.row_hi[t] - c.row_lo[t]);
+    PatTarget &q = tg[k];
+    q.row_lo = c.rng[2 * (size_t)t]; q.pos_lo = c.pos_lo[t]; q.nwin = c.nwin[t]; q.win_off = g.W;
+    q.hl_off = c.hlght_off ? c.hlght_off[t] - g.hl0 : 0;
+    q.nhl = c.hlght_off ? (int32_t)(c.hlght_off[t + 1] - c.hlght_off[t]) : 0;
+    q.rname = c.t_rname[t]; q.start = c.t_start[t]; q.end = c.t_end[t];
+    g.W += q.nwin;
+    pre[k + 1] = pre[k] + (uint64_t)(c.rng[2 * (size_t)t + 1] - c.rng[2 * (size_t)t]);
   }
-  const uint64_t P = pre[ng];
-  const int64_t H = c.hlght_off ? c.hlght_off[tb] - hl0 : 0;
-  if (P == 0) return EPI_OK;                                  // no candidate row: every table of the group is empty
+  g.pre = pre; g.tg = tg;
+}
+
+// Pass 1: overlap flags and position counts, the flags scanned into pattern slots.  Fetches every target's first slot and
+// the counts of its window into g.h_cb.
+int patm_pass1_fetch_counts(PatmCall &c, PatmScratch &w, PatGroup &g) {
+  hipStream_t s = c.s;
+  const int32_t ng = g.ng;
+  const uint64_t P = g.pre[ng];
   const int64_t nbp = (int64_t)((P + 255) / 256);
-  EPI_TRY(check_grid(nbp, 256, "epi_batch_extract_patterns_multi"));
+  EPI_TRY(check_grid(nbp, 256, c.entry));
   c.st->pairs += (int64_t)P;
-
-  // pass 1: overlap flags and position counts, the flags scanned into pattern slots
-  const size_t nbase = ((size_t)ng + 2) & ~(size_t)1;         // base[ng + 1] (padded to an even count), then the counts
-  EPI_TRY(w.meta.ensure(meta.size() * 8));
-  EPI_TRY(w.flag.ensure((size_t)P * 4));
-  EPI_TRY(w.cidx.ensure((size_t)P * 4));
-  EPI_TRY(w.cb.ensure((nbase + (size_t)W) * 4));
+  g.nbase = ((size_t)ng + 2) & ~(size_t)1;                    // (the counts follow base[] in one buffer)
+  g.h_cb.resize(g.nbase + (size_t)g.W);
+  EPI_TRY(w[kMeta].ensure(g.meta.size() * 8));
+  EPI_TRY(w[kFlag].ensure((size_t)P * 4));
+  EPI_TRY(w[kCidx].ensure((size_t)P * 4));
+  EPI_TRY(w[kCb].ensure(g.h_cb.size() * 4));
   w.note();
-  EPI_HIP(hipMemcpyAsync(w.meta.p, meta.data(), meta.size() * 8, hipMemcpyHostToDevice, s));
-  EPI_HIP(hipMemsetAsync(w.cb.p, 0, (nbase + (size_t)W) * 4, s));
-  PatMulti m = c.m;
-  m.pre = w.meta.as<uint64_t>();
-  m.tg = reinterpret_cast<const PatTarget *>(w.meta.as<uint64_t>() + ng + 1);
-  m.ng = ng;
-  uint32_t *d_base = w.cb.as<uint32_t>(), *d_cnt = d_base + nbase;
-  prof_begin("extract_patterns_multi", s);
-  hipLaunchKernelGGL(k_patm_flag_count, dim3((unsigned)nbp), dim3(256), 0, s, m, P, w.flag.as<uint32_t>(), d_cnt);
-  EPI_TRY(scan_exclusive_u32(w.flag.as<uint32_t>(), w.cidx.as<uint32_t>(), (int64_t)P, d_base + ng, b->scan_tmp, s));
-  hipLaunchKernelGGL(k_patm_bases, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, s, m.pre, ng, P, w.cidx.as<uint32_t>(), d_base);
+  EPI_HIP(hipMemcpyAsync(w[kMeta].p, g.meta.data(), g.meta.size() * 8, hipMemcpyHostToDevice, s));
+  EPI_HIP(hipMemsetAsync(w[kCb].p, 0, g.h_cb.size() * 4, s));
+  g.m = c.m;
+  g.m.pre = w[kMeta].as<uint64_t>();
+  g.m.tg = reinterpret_cast<const PatTarget *>(w[kMeta].as<uint64_t>() + ng + 1);
+  g.m.ng = ng;
+  uint32_t *d_base = w[kCb].as<uint32_t>(), *d_cnt = d_base + g.nbase;
+  prof_begin(c.label, s);
+  hipLaunchKernelGGL(k_patm_flag_count, dim3((unsigned)nbp), dim3(256), 0, s, g.m, P, w[kFlag].as<uint32_t>(), d_cnt);
+  EPI_TRY(scan_exclusive_u32(w[kFlag].as<uint32_t>(), w[kCidx].as<uint32_t>(), (int64_t)P, d_base + ng, c.b->scan_tmp, s));
+  hipLaunchKernelGGL(k_patm_bases, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, s, g.m.pre, ng, P, w[kCidx].as<uint32_t>(), d_base);
   EPI_HIP(hipGetLastError());
-  prof_end("extract_patterns_multi", s);
-  std::vector<uint32_t> h_cb(nbase + (size_t)W);
-  EPI_HIP(hipMemcpyAsync(h_cb.data(), w.cb.p, h_cb.size() * 4, hipMemcpyDeviceToHost, s));
+  prof_end(c.label, s);
+  EPI_HIP(hipMemcpyAsync(g.h_cb.data(), w[kCb].p, g.h_cb.size() * 4, hipMemcpyDeviceToHost, s));
   EPI_HIP(hipStreamSynchronize(s));
-  const uint32_t *h_base = h_cb.data(), *h_cnt = h_cb.data() + nbase;
-  if (h_base[ng] == 0) return EPI_OK;                         // no row overlaps any target of the group
+  return EPI_OK;
+}
 
-  // the host's decision for every target; cell batches of at most `cap` result bytes
-  std::vector<std::vector<int32_t>> cols((size_t)ng);
-  std::vector<int32_t> h_colmap((size_t)W, -1), h_hl((size_t)(2 * H + 2), 0);
-  int32_t *h_hcol = h_hl.data() + H;
-  if (H > 0) memcpy(h_hl.data(), c.hlght + hl0, (size_t)H * 4);
-  std::vector<PatSlice> sl((size_t)ng);
-  std::vector<PatSumSlice> ss(c.sum ? (size_t)ng : 0);
-  std::vector<int32_t> cuts(1, 0);                            // batch i: targets [cuts[i], cuts[i + 1])
+// The host's decision for every target and the cell batches, consecutive targets whose results stay under the cap; queues
+// the upload of what pass 2 reads of them
+int patm_plan_upload(PatmCall &c, PatmScratch &w, PatGroup &g) {
+  const size_t ng = (size_t)g.ng;
+  g.cols.assign(ng, std::vector<int32_t>());
+  g.h_colmap.assign((size_t)g.W, -1);
+  g.h_hl.assign((size_t)(2 * g.H + 2), 0);
+  int32_t *h_hcol = g.h_hl.data() + g.H;
+  if (g.H > 0) memcpy(g.h_hl.data(), c.hlght + g.hl0, (size_t)g.H * 4);
+  g.sl.assign(ng, PatSlice());
+  g.ss.assign(c.sum ? ng : 0, PatSumSlice());
+  g.cuts.assign(1, 0);
+  const uint32_t *h_base = g.h_base();
   int64_t bytes = 0, cell_off = 0, tab_off = 0;
   uint32_t rel = 0;
-  for (int32_t k = 0; k < ng; k++) {
-    const PatTarget &g = tg[k];
+  for (size_t k = 0; k < ng; k++) {
+    const PatTarget &q = g.tg[k];
     const uint32_t npat0 = h_base[k + 1] - h_base[k];
-    if (npat0) pat_choose_columns(h_cnt + g.win_off, g.nwin, g.pos_lo, npat0, c.min_ctx_freq, h_hl.data() + g.hl_off, g.nhl, cols[(size_t)k],
-                                  h_colmap.data() + g.win_off, h_hcol + g.hl_off);
-    const int64_t cells = (int64_t)cols[(size_t)k].size() * npat0;
+    if (npat0) pat_choose_columns(g.h_cnt() + q.win_off, q.nwin, q.pos_lo, npat0, c.min_ctx_freq, g.h_hl.data() + q.hl_off, q.nhl, g.cols[k],
+                                  g.h_colmap.data() + q.win_off, h_hcol + q.hl_off);
+    const int64_t cells = (int64_t)g.cols[k].size() * npat0;
     int64_t need = 32LL * npat0 + 4 * cells, tcap = 0;
     if (c.sum) {                                              // + its table slice, 20 B per slot and the unique rows at their most
       tcap = pat_table_capacity(npat0);
       need += 16 * tcap + 20LL * npat0 + 12LL * npat0 + 4 * cells;
     }
-    if (bytes > 0 && bytes + need > c.cap) { cuts.push_back(k); bytes = 0; cell_off = 0; rel = 0; tab_off = 0; }
-    sl[(size_t)k].cell_off = cell_off; sl[(size_t)k].base_abs = h_base[k]; sl[(size_t)k].base_rel = rel; sl[(size_t)k].npat0 = npat0; sl[(size_t)k].pad = 0;
-    if (c.sum) { ss[(size_t)k].tab_off = tab_off; ss[(size_t)k].mask = tcap ? (uint32_t)(tcap - 1) : 0u; ss[(size_t)k].ncol = (uint32_t)cols[(size_t)k].size(); }
+    if (bytes > 0 && bytes + need > c.cap) { g.cuts.push_back((int32_t)k); bytes = 0; cell_off = 0; rel = 0; tab_off = 0; }
+    PatSlice &sl = g.sl[k];
+    sl.cell_off = cell_off; sl.base_abs = h_base[k]; sl.base_rel = rel; sl.npat0 = npat0; sl.pad = 0;
+    if (c.sum) { g.ss[k].tab_off = tab_off; g.ss[k].mask = tcap ? (uint32_t)(tcap - 1) : 0u; g.ss[k].ncol = (uint32_t)g.cols[k].size(); }
     bytes += need; cell_off += cells; rel += npat0; tab_off += tcap;
   }
-  cuts.push_back(ng);
-  EPI_TRY(w.colmap.ensure((size_t)W * 4));
-  EPI_TRY(w.sl.ensure(sl.size() * sizeof(PatSlice)));
-  EPI_TRY(w.hl.ensure(h_hl.size() * 4));
+  g.cuts.push_back(g.ng);
+  hipStream_t s = c.s;
+  EPI_TRY(w[kColmap].ensure((size_t)g.W * 4));
+  EPI_TRY(w[kSl].ensure(g.sl.size() * sizeof(PatSlice)));
+  EPI_TRY(w[kHl].ensure(g.h_hl.size() * 4));
   if (c.sum) {
-    EPI_TRY(w.ss.ensure(ss.size() * sizeof(PatSumSlice)));
-    EPI_HIP(hipMemcpyAsync(w.ss.p, ss.data(), ss.size() * sizeof(PatSumSlice), hipMemcpyHostToDevice, s));
+    EPI_TRY(w[kSs].ensure(g.ss.size() * sizeof(PatSumSlice)));
+    EPI_HIP(hipMemcpyAsync(w[kSs].p, g.ss.data(), g.ss.size() * sizeof(PatSumSlice), hipMemcpyHostToDevice, s));
   }
-  EPI_HIP(hipMemcpyAsync(w.colmap.p, h_colmap.data(), (size_t)W * 4, hipMemcpyHostToDevice, s));
-  EPI_HIP(hipMemcpyAsync(w.sl.p, sl.data(), sl.size() * sizeof(PatSlice), hipMemcpyHostToDevice, s));
-  EPI_HIP(hipMemcpyAsync(w.hl.p, h_hl.data(), h_hl.size() * 4, hipMemcpyHostToDevice, s));
+  EPI_HIP(hipMemcpyAsync(w[kColmap].p, g.h_colmap.data(), (size_t)g.W * 4, hipMemcpyHostToDevice, s));
+  EPI_HIP(hipMemcpyAsync(w[kSl].p, g.sl.data(), g.sl.size() * sizeof(PatSlice), hipMemcpyHostToDevice, s));
+  EPI_HIP(hipMemcpyAsync(w[kHl].p, g.h_hl.data(), g.h_hl.size() * 4, hipMemcpyHostToDevice, s));
+  return EPI_OK;
+}
 
-  // pass 2, batch by batch: [fnv u64][nonempty, strand, start, end, nbase, meth i32] x slots, then the cells
-  std::vector<uint64_t> h_res;
-  for (size_t i = 0; i + 1 < cuts.size(); i++) {
-    const int32_t sa = cuts[i], sb = cuts[i + 1];
-    const size_t Ps = h_base[sb] - h_base[sa];
-    if (Ps == 0) continue;
-    size_t C = 0;
-    for (int32_t k = sa; k < sb; k++) C += cols[(size_t)k].size() * sl[(size_t)k].npat0;
-    const size_t rbytes = 32 * Ps + 4 * C;
-    EPI_TRY(w.res.ensure(rbytes + 64));
-    w.note();
-    PatOut o;
-    int32_t *ip = w.res.as<int32_t>();
-    o.fnv = reinterpret_cast<unsigned long long *>(ip);
-    int32_t *q = ip + 2 * Ps;
-    o.nonempty = q; o.strand = q + Ps; o.start = q + 2 * Ps; o.end = q + 3 * Ps; o.nbase = q + 4 * Ps; o.meth = q + 5 * Ps;
-    o.cells = q + 6 * Ps;
-    if (C) EPI_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(o.cells), INT32_MIN, C, s));             // NA_INTEGER
-    const uint64_t j0 = pre[sa], np = pre[sb] - pre[sa];
-    prof_begin("extract_patterns_multi", s);
-    hipLaunchKernelGGL(k_patm_extract, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, s, m, j0, np, w.flag.as<uint32_t>(),
-                       w.cidx.as<uint32_t>(), w.sl.as<PatSlice>(), w.colmap.as<int32_t>(), w.hl.as<int32_t>(), w.hl.as<int32_t>() + H, o);
-    EPI_HIP(hipGetLastError());
-    prof_end("extract_patterns_multi", s);
-    if (c.sum) {                                              // the slots stay on the device
-      EPI_TRY(patm_summarise_batch(c, w, sl, ss, cols, ta, sa, sb, Ps, C, o));
-      continue;
-    }
-    h_res.resize((rbytes + 7) / 8);
-    EPI_HIP(hipMemcpyAsync(h_res.data(), w.res.p, rbytes, hipMemcpyDeviceToHost, s));
-    EPI_HIP(hipStreamSynchronize(s));
-    const unsigned long long *h_f = reinterpret_cast<const unsigned long long *>(h_res.data());
-    const int32_t *r = reinterpret_cast<const int32_t *>(h_res.data()) + 2 * Ps, *h_cells = r + 6 * Ps;
-    for (int32_t k = sa; k < sb; k++) {
-      const PatSlice &q1 = sl[(size_t)k];
-      if (!q1.npat0) continue;
-      const int32_t *rk = r + q1.base_rel;
-      EPI_TRY(pat_fill_table(c.out + ta + k, q1.npat0, (int32_t)cols[(size_t)k].size(), cols[(size_t)k].data(), rk, rk + Ps, rk + 2 * Ps,
-                             rk + 3 * Ps, rk + 4 * Ps, rk + 5 * Ps, h_f + q1.base_rel, h_cells + q1.cell_off));
-    }
+// Pass 2 of one cell batch: the slots and cells of its targets into bt.o (the result buffer, cells NA_INTEGER first)
+int patm_pass2(PatmCall &c, PatmScratch &w, const PatGroup &g, PatBatch &bt) {
+  hipStream_t s = c.s;
+  EPI_TRY(w[kRes].ensure(32 * bt.Ps + 4 * bt.C + 64));
+  w.note();
+  bt.o = pat_out_at(w[kRes].p, bt.Ps);
+  if (bt.C) EPI_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(bt.o.cells), INT32_MIN, bt.C, s));
+  const uint64_t j0 = g.pre[bt.sa], np = g.pre[bt.sb] - g.pre[bt.sa];
+  prof_begin(c.label, s);
+  hipLaunchKernelGGL(k_patm_extract, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, s, g.m, j0, np, w[kFlag].as<uint32_t>(),
+                     w[kCidx].as<uint32_t>(), w[kSl].as<PatSlice>(), w[kColmap].as<int32_t>(), w[kHl].as<int32_t>(), w[kHl].as<int32_t>() + g.H,
+                     bt.o);
+  EPI_HIP(hipGetLastError());
+  prof_end(c.label, s);
+  return EPI_OK;
+}
+
+// Fetches a batch's slots and cells (h_res: the call's staging buffer) and makes the tables of its targets
+int patm_fetch_tables(PatmCall &c, PatmScratch &w, const PatGroup &g, const PatBatch &bt, std::vector<uint64_t> &h_res) {
+  const size_t rbytes = 32 * bt.Ps + 4 * bt.C;
+  h_res.resize((rbytes + 7) / 8);
+  EPI_HIP(hipMemcpyAsync(h_res.data(), w[kRes].p, rbytes, hipMemcpyDeviceToHost, c.s));
+  EPI_HIP(hipStreamSynchronize(c.s));
+  const PatOut h = pat_out_at(h_res.data(), bt.Ps);
+  for (int32_t k = bt.sa; k < bt.sb; k++) {
+    const PatSlice &q = g.sl[(size_t)k];
+    if (!q.npat0) continue;
+    const std::vector<int32_t> &ck = g.cols[(size_t)k];
+    EPI_TRY(pat_fill_table(c.out + g.ta + k, q.npat0, (int32_t)ck.size(), ck.data(), h.of(q.base_rel, q.cell_off)));
   }
+  return EPI_OK;
+}
+
+// targets [ta, tb): two passes, two host synchronisations and one more per cell batch (the summaries: two or three per batch)
+int patm_group(PatmCall &c, PatmScratch &w, int32_t ta, int32_t tb) {
+  PatGroup g;
+  patm_layout(c, ta, tb, g);
+  if (g.pre[g.ng] == 0) return EPI_OK;                        // no candidate row: every table of the group is empty
+  EPI_TRY(patm_pass1_fetch_counts(c, w, g));
+  if (g.h_base()[g.ng] == 0) return EPI_OK;                   // no row overlaps any target of the group
+  EPI_TRY(patm_plan_upload(c, w, g));
+  std::vector<uint64_t> h_res;
+  for (size_t i = 0; i + 1 < g.cuts.size(); i++) {
+    PatBatch bt;
+    bt.sa = g.cuts[i]; bt.sb = g.cuts[i + 1];
+    bt.Ps = g.h_base()[bt.sb] - g.h_base()[bt.sa];
+    if (bt.Ps == 0) continue;
+    bt.C = 0;
+    for (int32_t k = bt.sa; k < bt.sb; k++) bt.C += g.cols[(size_t)k].size() * g.sl[(size_t)k].npat0;
+    EPI_TRY(patm_pass2(c, w, g, bt));
+    EPI_TRY(c.sum ? patm_summarise_batch(c, w, g, bt) : patm_fetch_tables(c, w, g, bt, h_res));   // (a summary's slots stay on the device)
+  }
+  return EPI_OK;
+}
+
+// ---- a call ----------------------------------------------------------------------------------------------------------------
+// Target t of the call alone against all rows [0, n), its table into `out`: what epi_batch_extract_patterns is.  Leaves the
+// call's statistics alone; its launches go under the single call's label.
+int patm_all_rows(const PatmCall &c, PatmScratch &w, int32_t t, epi_pattern_table *out) {
+  const int64_t rows[2] = {0, c.b->n};
+  PatmStats unused;
+  PatmCall one = c;
+  one.t_rname += t; one.t_start += t; one.t_end += t; one.pos_lo += t; one.nwin += t;
+  if (one.hlght_off) one.hlght_off += t;
+  one.rng = rows;
+  one.out = out; one.sum = nullptr; one.st = &unused;
+  one.entry = "epi_batch_extract_patterns"; one.label = "extract_patterns";
+  return patm_group(one, w, 0, 1);
+}
+
+// Rows in any order, or coordinates below 0: every target scans the batch, cost O(rows x targets), one scratch for all.
+// The summary of such a target is the host's grouping of its table.
+int patm_target_by_target(const PatmCall &c, PatmScratch &w, int32_t nt) {
+  for (int32_t t = 0; t < nt; t++) {
+    epi_pattern_table one;
+    memset(&one, 0, sizeof(one));
+    EPI_TRY(patm_all_rows(c, w, t, c.sum ? &one : c.out + t));
+    if (!c.sum || !one.npat) continue;
+    c.st->fallback++;
+    const int rc = pat_summarise_host(c.sum + t, (size_t)one.npat, one.ncol, one.positions, nullptr, one.fnv, one.cells);
+    epi_pattern_table_free(&one);
+    EPI_TRY(rc);
+  }
+  return EPI_OK;
+}
+
+// Rows sorted by (rname, start): fetches the candidate rows of every target, rng[2t], rng[2t + 1], and rng[2 * nt] != 0 when
+// a target's rname holds a row with a negative start
+int patm_fetch_candidate_rows(PatmCall &c, PatmScratch &w, int32_t nt, int64_t lmax, int32_t min_overlap, std::vector<int64_t> &h_rng) {
+  hipStream_t s = c.s;
+  std::vector<int32_t> h_tgt((size_t)3 * nt);
+  memcpy(h_tgt.data(), c.t_rname, (size_t)nt * 4);
+  memcpy(h_tgt.data() + nt, c.t_start, (size_t)nt * 4);
+  memcpy(h_tgt.data() + 2 * (size_t)nt, c.t_end, (size_t)nt * 4);
+  h_rng.resize((size_t)2 * nt + 1);
+  EPI_TRY(w[kTgt].ensure(h_tgt.size() * 4));
+  EPI_TRY(w[kRng].ensure(h_rng.size() * 8));
+  w.note();
+  EPI_HIP(hipMemcpyAsync(w[kTgt].p, h_tgt.data(), h_tgt.size() * 4, hipMemcpyHostToDevice, s));
+  EPI_HIP(hipMemsetAsync(w[kRng].p, 0, h_rng.size() * 8, s));
+  const int64_t reach = min_overlap >= 1 ? 0 : 1 - (int64_t)min_overlap;
+  EPI_TRY(check_grid(((int64_t)nt + 255) / 256, 256, c.entry));
+  prof_begin(c.label, s);
+  hipLaunchKernelGGL(k_patm_ranges, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, s, c.b->rname, c.b->start, c.b->n, w[kTgt].as<int32_t>(), nt,
+                     lmax, reach, w[kRng].as<int64_t>());
+  EPI_HIP(hipGetLastError());
+  prof_end(c.label, s);
+  EPI_HIP(hipMemcpyAsync(h_rng.data(), w[kRng].p, h_rng.size() * 8, hipMemcpyDeviceToHost, s));
+  EPI_HIP(hipStreamSynchronize(s));
   return EPI_OK;
 }
 
@@ -905,80 +953,32 @@ int patm_run(epi_batch *b, int32_t nt, const int32_t *t_rname, const int32_t *t_
              void *stream, epi_pattern_table *out, epi_pattern_summary *sum, PatmStats &st) {
   EPI_HIP(hipSetDevice(b->eng->device));
   hipStream_t s = pick_stream(b, stream);
-  EPI_TRY(fetch_row_stats(b, s));
-  if (b->h_stats.bad_len) return fail(EPI_ERR_ARG, "offsets are not non-decreasing, or start+length exceeds int32");
-  const int64_t lmax = b->h_stats.max_len;
-  auto one_by_one = [&]() {                                   // rows in any order: every target scans the batch
-    for (int32_t t = 0; t < nt; t++) {
-      const int64_t h0 = hlght_off ? hlght_off[t] : 0, h1 = hlght_off ? hlght_off[t + 1] : 0;
-      epi_pattern_table one;
-      EPI_TRY(epi_batch_extract_patterns(b, t_rname[t], t_start[t], t_end[t], min_overlap, ctx, min_ctx_freq, clip, reverse_offset,
-                                         h1 > h0 ? hlght + h0 : nullptr, (int32_t)(h1 - h0), stream, sum ? &one : out + t));
-      if (!sum || !one.npat) continue;                        // the summary of a table: the host's grouping
-      st.fallback++;
-      const int rc = pat_summarise_host(sum + t, (size_t)one.npat, one.ncol, one.positions, nullptr, one.fnv, one.cells);
-      epi_pattern_table_free(&one);
-      EPI_TRY(rc);
-    }
-    return (int)EPI_OK;
-  };
-  bool ranges_ok = !b->h_stats.unsorted;
+  int64_t lmax = 0;
+  EPI_TRY(pat_longest_row(b, s, &lmax));
+  bool ranged = !b->h_stats.unsorted;
   std::vector<int64_t> pos_lo((size_t)nt), nwin((size_t)nt);
   for (int32_t t = 0; t < nt; t++) {
-    if (t_start[t] < 0 || t_end[t] < 0) ranges_ok = false;    // (pat_span compares unsigned)
-    pos_lo[(size_t)t] = (int64_t)t_start[t] - lmax - (int64_t)reverse_offset - 2;
-    int64_t nw = ((int64_t)t_end[t] - (int64_t)t_start[t]) + 2 * lmax + (int64_t)reverse_offset + 8;
-    if (nw < 1) nw = 1;
-    if (nw > (1LL << 31)) return fail(EPI_ERR_ARG, "epi_batch_extract_patterns: target too wide");
-    nwin[(size_t)t] = nw;
+    if (t_start[t] < 0 || t_end[t] < 0) ranged = false;       // (pat_span compares unsigned)
+    EPI_TRY(pat_window(t_start[t], t_end[t], lmax, reverse_offset, &pos_lo[(size_t)t], &nwin[(size_t)t]));
   }
-  if (!ranges_ok) return one_by_one();
-
-  // candidate rows of every target
+  PatmCall c = patm_call(b, s, min_overlap, ctx, min_ctx_freq, clip, reverse_offset);
+  c.t_rname = t_rname; c.t_start = t_start; c.t_end = t_end; c.pos_lo = pos_lo.data(); c.nwin = nwin.data();
+  c.hlght = hlght; c.hlght_off = hlght_off; c.out = out; c.sum = sum; c.st = &st;
   PatmScratch w;
-  std::vector<int32_t> h_tgt((size_t)3 * nt);
-  memcpy(h_tgt.data(), t_rname, (size_t)nt * 4);
-  memcpy(h_tgt.data() + nt, t_start, (size_t)nt * 4);
-  memcpy(h_tgt.data() + 2 * (size_t)nt, t_end, (size_t)nt * 4);
-  std::vector<int64_t> h_rng((size_t)2 * nt + 1);
-  EPI_TRY(w.tgt.ensure(h_tgt.size() * 4));
-  EPI_TRY(w.rng.ensure(h_rng.size() * 8));
-  w.note();
-  EPI_HIP(hipMemcpyAsync(w.tgt.p, h_tgt.data(), h_tgt.size() * 4, hipMemcpyHostToDevice, s));
-  EPI_HIP(hipMemsetAsync(w.rng.p, 0, h_rng.size() * 8, s));
-  const int64_t reach = min_overlap >= 1 ? 0 : 1 - (int64_t)min_overlap;
-  EPI_TRY(check_grid(((int64_t)nt + 255) / 256, 256, "epi_batch_extract_patterns_multi"));
-  prof_begin("extract_patterns_multi", s);
-  hipLaunchKernelGGL(k_patm_ranges, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, s, b->rname, b->start, b->n, w.tgt.as<int32_t>(), nt,
-                     lmax, reach, w.rng.as<int64_t>());
-  EPI_HIP(hipGetLastError());
-  prof_end("extract_patterns_multi", s);
-  EPI_HIP(hipMemcpyAsync(h_rng.data(), w.rng.p, h_rng.size() * 8, hipMemcpyDeviceToHost, s));
-  EPI_HIP(hipStreamSynchronize(s));
-  if (h_rng[(size_t)2 * nt]) return one_by_one();
-  std::vector<int64_t> row_lo((size_t)nt), row_hi((size_t)nt);
-  for (int32_t t = 0; t < nt; t++) { row_lo[(size_t)t] = h_rng[2 * (size_t)t]; row_hi[(size_t)t] = h_rng[2 * (size_t)t + 1]; }
-
-  PatmCall c;
-  c.b = b; c.s = s; c.t_rname = t_rname; c.t_start = t_start; c.t_end = t_end;
-  c.row_lo = row_lo.data(); c.row_hi = row_hi.data(); c.pos_lo = pos_lo.data(); c.nwin = nwin.data();
-  c.hlght = hlght; c.hlght_off = hlght_off; c.min_ctx_freq = min_ctx_freq; c.out = out; c.sum = sum; c.st = &st;
-  const int hb = options().pat_hash_bits;
-  c.key_mask = hb >= 1 && hb <= 63 ? (1ull << hb) - 1ull : ~0ull;
-  c.cap = options().pat_group_bytes > 0 ? options().pat_group_bytes : kPatGroupBytes;
-  c.m.xm = b->xm; c.m.off = b->off; c.m.len = b->len; c.m.rname = b->rname; c.m.strand = b->strand; c.m.start = b->start;
-  c.m.reverse_offset = (uint32_t)reverse_offset; c.m.min_overlap = min_overlap; c.m.clip = clip ? 1 : 0;
-  c.m.ctx_mask = 0;
-  for (const unsigned char *p = reinterpret_cast<const unsigned char *>(ctx); *p; p++) c.m.ctx_mask |= 1u << ctx_to_idx(*p);
-  c.m.tg = nullptr; c.m.pre = nullptr; c.m.ng = 0;
-
+  std::vector<int64_t> h_rng;
+  if (ranged) {
+    EPI_TRY(patm_fetch_candidate_rows(c, w, nt, lmax, min_overlap, h_rng));
+    ranged = !h_rng[(size_t)2 * nt];
+  }
+  if (!ranged) return patm_target_by_target(c, w, nt);
+  c.rng = h_rng.data();
   // groups of consecutive targets whose pass-1 scratch (40 B per pair, 8 B per window position) fits the cap
   int rc = EPI_OK;
   for (int32_t ta = 0; ta < nt && rc == EPI_OK;) {
     int64_t bytes = 0;
     int32_t tb = ta;
     while (tb < nt) {
-      const int64_t need = 40 * (row_hi[(size_t)tb] - row_lo[(size_t)tb]) + 8 * nwin[(size_t)tb] + 128;
+      const int64_t need = 40 * (h_rng[2 * (size_t)tb + 1] - h_rng[2 * (size_t)tb]) + 8 * nwin[(size_t)tb] + 128;
       if (tb > ta && bytes + need > c.cap) break;
       bytes += need;
       tb++;
@@ -1008,6 +1008,31 @@ int patm_check_args(const char *what, const epi_batch *b, int32_t ntargets, cons
 }  // namespace
 
 extern "C" {
+
+void epi_pattern_table_free(epi_pattern_table *t) {
+  if (!t) return;
+  free(t->positions); free(t->strand); free(t->start); free(t->end); free(t->nbase); free(t->beta); free(t->fnv); free(t->cells);
+  memset(t, 0, sizeof(*t));
+}
+
+int epi_batch_extract_patterns(epi_batch *b, int32_t target_rname, int32_t target_start, int32_t target_end, int32_t min_overlap,
+                               const char *ctx, double min_ctx_freq, int32_t clip, int32_t reverse_offset, const int32_t *hlght,
+                               int32_t nhlght, void *stream, epi_pattern_table *out) {
+  if (!b || !ctx || !out || nhlght < 0 || (nhlght > 0 && !hlght)) return fail(EPI_ERR_ARG, "epi_batch_extract_patterns: bad arguments");
+  memset(out, 0, sizeof(*out));
+  if (b->n == 0) return EPI_OK;
+  EPI_HIP(hipSetDevice(b->eng->device));
+  hipStream_t s = pick_stream(b, stream);
+  int64_t lmax = 0, pos_lo = 0, nwin = 0;
+  EPI_TRY(pat_longest_row(b, s, &lmax));
+  EPI_TRY(pat_window(target_start, target_end, lmax, reverse_offset, &pos_lo, &nwin));
+  const int64_t hlght_off[2] = {0, nhlght};
+  PatmCall c = patm_call(b, s, min_overlap, ctx, min_ctx_freq, clip, reverse_offset);
+  c.t_rname = &target_rname; c.t_start = &target_start; c.t_end = &target_end; c.pos_lo = &pos_lo; c.nwin = &nwin;
+  c.hlght = hlght; c.hlght_off = hlght_off;
+  PatmScratch w;
+  return patm_all_rows(c, w, 0, out);
+}
 
 int epi_batch_extract_patterns_multi(epi_batch *b, int32_t ntargets, const int32_t *target_rname, const int32_t *target_start,
                                      const int32_t *target_end, int32_t min_overlap, const char *ctx, double min_ctx_freq, int32_t clip,

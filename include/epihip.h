@@ -470,7 +470,9 @@ int epi_batch_heterogeneity_fetch_dev(epi_batch *b, int32_t *const d_icols[7], d
  * methylation patterns of the reads overlapping one target.  Library-owned host table: per pattern strand, start,
  * end, nbase, beta, the FNV-1a hash the R side prints as 16 hex digits ("pattern"), the ordered column positions
  * and cells[col * npat + p] = context index / base factor code (levels as :192-195) or INT32_MIN (NA).
- * npat = 0 is the reference's empty data frame.  Synchronises `stream`. */
+ * npat = 0 is the reference's empty data frame.  One target against all rows of the batch: device scratch of 8 B per row
+ * (allocated and freed by the call), the two passes and the host round trips of epi_batch_extract_patterns_multi below.
+ * Leaves that call's statistics alone.  Synchronises `stream`. */
 typedef struct {
   int64_t npat;
   int32_t ncol;
@@ -494,8 +496,9 @@ void epi_pattern_table_free(epi_pattern_table *t);
  * -- its rname, start in [start - Lmax + 1, end], Lmax the longest row -- are then one row range found by search, and
  * the work is one flat list of (target, candidate row) pairs: cost O(candidate rows), a fixed number of launches and
  * three host synchronisations per GROUP of targets, whatever their number.  For rows in another order (adopted
- * columns), rows or targets with negative coordinates, the call runs epi_batch_extract_patterns target by target
- * instead: same tables, cost O(rows x targets).
+ * columns), rows or targets with negative coordinates, the call runs target by target instead, every target against all
+ * rows as epi_batch_extract_patterns does, with one scratch for the list: same tables, cost O(rows x targets), 8 B of
+ * scratch per row of the batch.
  * Memory: nothing is sized by the batch.  Consecutive targets form a group while 40 B per pair + 8 B per window position
  * (end - start + 2 Lmax + reverse_offset + 8 per target) stay under a cap of 256 MiB; the results of a group (32 B per
  * overlapping row + 4 B per cell) are fetched in batches under the same cap.  A target above the cap runs alone.
@@ -521,7 +524,7 @@ int epi_batch_extract_patterns_multi_stats(epi_batch *b, int64_t *groups, int64_
  * >= 2 x its overlapping rows, keyed by the hash; a wave adds once per distinct key among its lanes.  Every row is then
  * compared, cell by cell, with the first row of its table entry.  A target in which two different patterns met under one
  * key is grouped on the host instead, by (fnv, cells), from its per-row results: the result never rests on the hash.
- * So are the targets of the target-by-target path (rows in another order, negative coordinates).
+ * So are the targets of the target-by-target path (rows in another order, negative coordinates), from their tables.
  * Transfer: 12 B + 4 B per column for every UNIQUE pattern, plus 12 B per target; nothing per row.
  * Memory: as epi_batch_extract_patterns_multi, and inside the same cap: a batch of results counts 16 B per table entry
  * (at most 4 x the overlapping rows + 8 per target), 20 B per overlapping row and its unique rows at their most (12 B per

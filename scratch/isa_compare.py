@@ -33,7 +33,8 @@ def parse(path):
         text = body + desc
         for m in sorted(names, key=len, reverse=True):
             text = text.replace(m, "KERNEL")
-        text = re.sub(r"\.LBB\d+_", ".LBB_", text)
+        text = re.sub(r"BB\d+_", "BB_", text)                      # labels, and the loop headers named in comments
+        text = re.sub(r"[ \t]+;", " ;", text)                      # (comments are aligned to the label's width)
         key = re.sub(r"(k_cx_tiles<.*), 0>$", r"\1>", d.split("(")[0])
         out[key] = (text.split("\n"), meta[n])
     return out

@@ -1,7 +1,7 @@
 """extractPatternsBed on the GPU (epi_batch_extract_patterns_multi): every table equals what extractPatterns gives for
 that BED row and what the CPU oracle gives, hashes included -- on the reference's fixtures for every row and over the
-argument grid, on random batches through rcpp_extract_patterns_multi, on an unsorted batch (the target-by-target
-path), over several scratch groups, and on a 10^7-row resident batch whose size must not show in launches or scratch."""
+argument grid, on random batches through rcpp_extract_patterns_multi, on an unsorted batch and with negative coordinates
+(the target-by-target path), over several scratch groups, and on a 10^7-row resident batch whose size must not show in launches or scratch."""
 import ctypes as C
 import os
 
@@ -358,7 +358,61 @@ def test_unsorted_batch_takes_the_target_by_target_path(ea):
     assert n2 == n and st2[0] == 1
 
 
+def test_negative_coordinates_take_the_target_by_target_path(ea):
+    rng = np.random.default_rng(29)
+    t = synth_np.random_templates(rng, 300, 20, 80, 2, 2000, alphabet="..zZxXhH")
+    assert t["rname"][4] == 1 and t["rname"][-1] == 2
+    t["start"][:5] = np.sort(rng.integers(-40, 0, size=5))         # the first rows of rname 1: the order holds
+    bam = ea.ProcessedBam.from_arrays(t["xm"], t["off"], t["rname"], t["strand"], t["start"])
+    try:
+        # rows with a negative start on a target's rname; no such row, but a target with a negative start (it covers every
+        # row of rname 2, so its window holds all their positions)
+        for targets in ([(1, 100, 400), (2, 100, 400), (1, 1, 50), (2, 1500, 1900), (2, 5000, 5100)],
+                        [(2, 100, 400), (2, -5, 2100), (2, 1, 1)]):
+            reps = ea.rcpp_extract_patterns_multi(bam, targets, 1, "Zz", 0.01, False, 0)
+            assert stats(ea, bam) == (0, 0, 0)
+            assert sum(bool(rep) for rep in reps) >= 2
+            for tg, rep in zip(targets, reps):
+                tab = TP.table_from_report(rep)
+                same_table(tab, TP.table_from_report(ea.rcpp_extract_patterns(bam, tg[0], tg[1], tg[2], 1, "Zz", 0.01, False, 0)))
+                if tg[0] == 2:                                     # (a row with a negative start overlaps every target of rname 1)
+                    same_table(tab, oracle_table(t, tg, 1, "Zz", 0.01, False, 0, ()))
+    finally:
+        bam.close()
+
+
 # ---- 5. the structure ----------------------------------------------------------------------------------------------------
+
+def test_block_edges_of_the_all_rows_pass(ea):
+    rng = np.random.default_rng(31)
+    for n in (1, 255, 256, 257, 513):
+        t = synth_np.random_templates(rng, n, 20, 80, 1, 300, alphabet="..zZxXhH")
+        bam = ea.ProcessedBam.from_arrays(t["xm"], t["off"], t["rname"], t["strand"], t["start"])
+        try:
+            for tg, npat in (((1, 1, 400), n), ((1, 1000, 1100), 0)):     # every row, no row
+                tab = TP.table_from_report(ea.rcpp_extract_patterns(bam, tg[0], tg[1], tg[2], 1, "ZzXxHh", 0.0, False, 0))
+                same_table(tab, oracle_table(t, tg, 1, "ZzXxHh", 0.0, False, 0, ()))
+                assert len(tab["pattern"]) == npat                 # (a row of 20 bytes without a context byte: 4^-20)
+        finally:
+            bam.close()
+
+
+def test_single_call_keeps_its_label_and_the_multi_statistics(ea):
+    rng = np.random.default_rng(37)
+    t = synth_np.random_templates(rng, 300, 20, 80, 2, 2000, alphabet="..zZxXhH")
+    bam = ea.ProcessedBam.from_arrays(t["xm"], t["off"], t["rname"], t["strand"], t["start"])
+    try:
+        ea.rcpp_extract_patterns_multi(bam, [(1, 100, 400), (2, 100, 400)], 1, "Zz", 0.01, False, 0)
+        st = stats(ea, bam)
+        assert st[0] == 1 and st[1] > 0 and st[2] > 0
+        rep, counts = profiled(ea, lambda: ea.rcpp_extract_patterns(bam, 1, 100, 400, 1, "Zz", 0.01, False, 0),
+                               "extract_patterns_multi", "extract_patterns")
+        assert rep and counts[0] == 0 and counts[1] >= 1
+        assert stats(ea, bam) == st
+    finally:
+        bam.close()
+
+
 
 def test_launches_do_not_grow_with_the_targets(ea):
     pb = ea.preprocessBam(os.path.join(BAM, "capture.bam"))

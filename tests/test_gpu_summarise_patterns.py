@@ -323,7 +323,8 @@ def test_targets_with_3_and_70_slots_and_many_small_ones(ea):
 
 # ---- 4. unsorted rows ------------------------------------------------------------------------------------------------------
 
-def test_unsorted_rows_take_the_target_by_target_path(ea):
+def unsorted_pile_up(ea):
+    """The rows of pile_up(seed=9) and 80 more at chrA:5000, in a random order"""
     t = pile_up(seed=9)
     n = len(t["start"])
     far = H.templates_from_xm(["zZ.zZ" * 12] * 50 + ["Zz.zz" * 12] * 30, [5000] * 80, [1] * 80)
@@ -332,8 +333,12 @@ def test_unsorted_rows_take_the_target_by_target_path(ea):
     perm = np.random.default_rng(1).permutation(n + 80)
     off = np.zeros(n + 81, np.int64)
     np.cumsum([rows[i].size for i in perm], out=off[1:])
-    bam = ea.ProcessedBam.from_arrays(np.concatenate([rows[i] for i in perm]), off, np.ones(n + 80, np.int32), strand[perm], start[perm],
-                                      levels=LEVELS)
+    return ea.ProcessedBam.from_arrays(np.concatenate([rows[i] for i in perm]), off, np.ones(n + 80, np.int32), strand[perm], start[perm],
+                                       levels=LEVELS)
+
+
+def test_unsorted_rows_take_the_target_by_target_path(ea):
+    bam = unsorted_pile_up(ea)
     try:
         bed = ea.Bed(["chrA", "chrA", "chrB"], [1000, 5000, 1000], [1059, 5059, 1059])
         got = ea.summarisePatterns(bam, bed, bed_rows=[2, 1, 3, 1])
@@ -341,6 +346,24 @@ def test_unsorted_rows_take_the_target_by_target_path(ea):
         for r, g in zip([2, 1, 3, 1], got):
             same_summary(g, ea.extractPatterns(bam, bed, bed_row=r))
         assert got[0].nrow == 2 and sorted(got[0]["count"]) == [30, 50] and int(got[1]["count"].max()) >= 3000 and not got[2]
+    finally:
+        bam.close()
+
+
+def test_twenty_targets_of_the_target_by_target_path(ea):
+    """One scratch serves the whole list: every target's summary is that of its own extractPatterns call"""
+    bam = unsorted_pile_up(ea)
+    try:
+        # windows over the pile-up and the far rows, gaps without a row, and chrB
+        starts = [940 + 10 * k for k in range(14)] + [3000, 4990, 5000, 5059, 5060, 1000]
+        bed = ea.Bed(["chrA"] * 19 + ["chrB"], starts, [s + 24 for s in starts])
+        got = ea.summarisePatterns(bam, bed)
+        reps = [ea.extractPatterns(bam, bed, bed_row=r + 1) for r in range(20)]
+        nonempty = sum(bool(rep) for rep in reps)
+        assert len(got) == 20 and 10 <= nonempty < 20
+        assert stats(ea, bam) == (0, 0, nonempty)
+        for g, rep in zip(got, reps):
+            same_summary(g, rep)
     finally:
         bam.close()
 
