@@ -432,6 +432,54 @@ def rcpp_heterogeneity_report(df, ctx, k, max_ooctx_meth_frac, min_reads=1, max_
     return rep
 
 
+LINKAGE_COLUMNS = ("rname", "strand", "pos", "pos2", "context", "neighbour", "nreads", "n_uu", "n_mu", "n_um", "n_mm",
+                   "cov", "r2", "dprime")
+BLOCK_COLUMNS = ("rname", "strand", "start", "end", "nsites", "mean_r2")
+
+
+def _linkage_run(bam, ctx, max_neighbours, max_distance, max_ooctx_meth_frac, min_reads):
+    """epi_batch_linkage_report_dev on the batch of `bam`: the number of reported pairs."""
+    nrow = C.c_int64(0)
+    _lib.check(_lib.load().epi_batch_linkage_report_dev(bam.batch(), _lib.enc(ctx), int(max_neighbours), int(max_distance),
+                                                        float(max_ooctx_meth_frac), int(min_reads), _stream(bam.device),
+                                                        C.byref(nrow)))
+    return nrow.value
+
+
+def _fetch_table(bam, fetch, n, nint, names, as_device):
+    """The columns of a finished report, nint int32 ones then float64 ones, through the library's `fetch`."""
+    torch = _torch()
+    dev = "cuda:%d" % bam.device
+    icols = list(torch.empty((nint, n), dtype=torch.int32, device=dev).unbind(0))
+    dcols = list(torch.empty((len(names) - nint, n), dtype=torch.float64, device=dev).unbind(0))
+    if n:
+        _lib.check(fetch(bam.batch(), _ptr_array(icols), _ptr_array(dcols), _stream(bam.device)))
+    cols = icols + dcols
+    if not as_device:
+        cols = [c.cpu().numpy() for c in cols]
+    return Report(dict(zip(names, cols)), bam.levels)
+
+
+def rcpp_linkage_report(df, ctx, max_neighbours, max_distance, max_ooctx_meth_frac, min_reads=1, as_device=False):
+    """Per pair (s_j, s_{j+d}), d = 1 .. max_neighbours, of sites of the un-thresholded cytosine report (include/epihip.h,
+    epi_batch_linkage_report_dev): rname, strand, pos, pos2, context, neighbour, nreads, n_uu, n_mu, n_um, n_mm (int32),
+    cov, r2, dprime (float64).  ctx: context letters in both cases, as for rcpp_mhl_report."""
+    bam = _as_bam(df)
+    n = _linkage_run(bam, ctx, max_neighbours, max_distance, max_ooctx_meth_frac, min_reads)
+    return _fetch_table(bam, _lib.load().epi_batch_linkage_fetch_dev, n, 11, LINKAGE_COLUMNS, as_device)
+
+
+def rcpp_linkage_blocks(df, ctx, max_neighbours, max_distance, max_ooctx_meth_frac, min_reads, min_r2, min_sites, as_device=False):
+    """The haplotype blocks of the pair table rcpp_linkage_report computes with the same arguments
+    (epi_batch_linkage_blocks_dev): rname, strand, start, end, nsites (int32), mean_r2 (float64)."""
+    lib = _lib.load()
+    bam = _as_bam(df)
+    _linkage_run(bam, ctx, max_neighbours, max_distance, max_ooctx_meth_frac, min_reads)
+    nblock = C.c_int64(0)
+    _lib.check(lib.epi_batch_linkage_blocks_dev(bam.batch(), float(min_r2), int(min_sites), _stream(bam.device), C.byref(nblock)))
+    return _fetch_table(bam, lib.epi_batch_linkage_blocks_fetch_dev, nblock.value, 5, BLOCK_COLUMNS, as_device)
+
+
 PATTERN_LEVELS = ("NA1", "H", "A", "C", "NA5", "X", "Z", "NA8", "NA9", "h", "G", "T", "N", "x", "z", "NA16")   # :192-195
 NA_INTEGER = -2 ** 31
 
@@ -611,6 +659,57 @@ def generateHeterogeneityReport(bam, report_file=None, window_context=None, wind
     c = CONTEXT_TO_BASES[window_context]
     rep = rcpp_heterogeneity_report(bam, c["ctx_meth"] + c["ctx_unmeth"], int(window_sites), max_outofcontext_beta,
                                     min_reads, max_window_span, as_device=as_device)
+    if report_file is None:
+        return rep
+    writeReport(rep, report_file, gzip)
+    return None
+
+
+def _whole_number(value, name, lo, hi=None):
+    if isinstance(value, bool) or int(value) != value or int(value) < lo or (hi is not None and int(value) > hi):
+        raise ValueError("'%s' should be an integer %s" % (name, "from %d to %d" % (lo, hi) if hi is not None else "of at least %d" % lo))
+    return int(value)
+
+
+def _linkage_args(linkage_context, max_neighbours, max_distance):
+    return (_match_arg(linkage_context, _CTX_CHOICES, "linkage.context"), _whole_number(max_neighbours, "max.neighbours", 1, 16),
+            _whole_number(max_distance, "max.distance", 0))
+
+
+def generateLinkageReport(bam, report_file=None, linkage_context=None, max_neighbours=4, max_distance=0, min_reads=1,
+                          max_outofcontext_beta=0.1, gzip=False, verbose=False, as_device=False, **preprocess_args):
+    """Co-methylation of every cytosine of `linkage_context` with each of its next `max_neighbours` (1 to 16) neighbours on
+    the same sequence and strand, over the reads that have a call at both: the 2 x 2 table (n_uu, n_mu, n_um, n_mm; the
+    first letter is the first site's state), its covariance, r2 and D'.  The sites are those of
+    generateCytosineReport(threshold_reads=False, report_context=linkage_context), the reads those generateMhlReport keeps
+    under max_outofcontext_beta; pairs with fewer than min_reads reads, or (max_distance > 0) more than max_distance bases
+    apart, are left out.  The other half of Guo et al. 2017, where lMHL comes from; the reference has no such report."""
+    linkage_context, max_neighbours, max_distance = _linkage_args(linkage_context, max_neighbours, max_distance)
+    bam = preprocessBam(bam, **preprocess_args)
+    c = CONTEXT_TO_BASES[linkage_context]
+    rep = rcpp_linkage_report(bam, c["ctx_meth"] + c["ctx_unmeth"], max_neighbours, max_distance, max_outofcontext_beta,
+                              min_reads, as_device=as_device)
+    if report_file is None:
+        return rep
+    writeReport(rep, report_file, gzip)
+    return None
+
+
+def generateHaplotypeBlocks(bam, report_file=None, linkage_context=None, max_neighbours=4, max_distance=0, min_reads=10,
+                            max_outofcontext_beta=0.1, min_r2=0.5, min_sites=3, gzip=False, verbose=False, as_device=False,
+                            **preprocess_args):
+    """Methylation haplotype blocks: runs of at least `min_sites` neighbouring cytosines in which every site is linked
+    (r2 >= min_r2 over at least min_reads reads) to each of the up to `max_neighbours` sites of the block in front of it;
+    built greedily from each strand's first site on the pair table of generateLinkageReport with the same arguments
+    (include/epihip.h has the rule).  Columns: rname, strand, start, end, nsites, mean_r2 (of the adjacent pairs)."""
+    linkage_context, max_neighbours, max_distance = _linkage_args(linkage_context, max_neighbours, max_distance)
+    min_sites = _whole_number(min_sites, "min.sites", 2)
+    if isinstance(min_r2, bool) or not 0 <= min_r2 <= 1:
+        raise ValueError("'min.r2' should be a number from 0 to 1")
+    bam = preprocessBam(bam, **preprocess_args)
+    c = CONTEXT_TO_BASES[linkage_context]
+    rep = rcpp_linkage_blocks(bam, c["ctx_meth"] + c["ctx_unmeth"], max_neighbours, max_distance, max_outofcontext_beta,
+                              min_reads, min_r2, min_sites, as_device=as_device)
     if report_file is None:
         return rep
     writeReport(rep, report_file, gzip)

@@ -156,6 +156,7 @@ enum ReportKind {
   KIND_MHL_SHARED = 4,      // ... of a sharded lMHL report, two-kernel path (slabs in k_mhl_tiles' layout)
   KIND_MHLF_SHARED = 5,     // ... of a sharded lMHL report, one-pass kernel (slabs in its layout, mhl_common.hpp)
   KIND_HET = 6,             // finished heterogeneity report
+  KIND_LINK = 7,            // finished linkage report
 };
 }  // namespace epi
 
@@ -234,6 +235,15 @@ struct epi_batch {
   int64_t het_nsite = 0, het_max_span = 0;
   int32_t het_k = 0;
   uint32_t het_min_reads = 1;
+  // linkage report (linkage.hip): the site table and the counters [site][D][4], keep flags and output rows [site][D] live in
+  // the heterogeneity report's buffers (one report is live on a batch at a time; het_scal[2]: blocks); its own are the
+  // blocks': leading linked pairs behind a site, block length and mean r^2 at a block's first site (by table ordinal),
+  // and the blocks' flags and output rows by CX row
+  epi::DevBuf link_back, link_blen, link_bmean, link_bflag, link_bout;
+  int32_t link_D = 0;
+  uint32_t link_min_reads = 1;
+  int64_t link_max_dist = 0, link_nblock = 0;
+  bool link_blocks = false;                    // epi_batch_linkage_blocks_dev has run on the last linkage report
 
   // state of the last report (for fetch)
   epi::ReportKind last_kind = epi::KIND_NONE;

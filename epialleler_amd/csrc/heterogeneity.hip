@@ -5,6 +5,7 @@
 // keeps (src/rcpp_mhl_report.cpp:172-179, hmin = 0).
 //
 // Data path, all on the report's stream:
+// The site table, the read rule and a row's walk over its sites are shared with the linkage report (het_common.hpp).
 //  (a) the un-thresholded CX report of the batch, fetched into het_cx (six columns of N rows, in (rname, pos, strand)
 //      order).  A scan over "strand is +" gives every row its ordinal in a table split per strand: '+' sites at
 //      [0, n1), '-' sites at [n1, N), each sorted by (rname, pos).  k_het_sites writes that table: a 64-bit key
@@ -23,69 +24,21 @@
 // of every group then holds the same counter: the lanes compare their counter index with the three lanes j + 16 m
 // and the lowest of a set adds the set's size.  EPI_HET_PER_LANE (make timing-het) adds 1 per lane instead;
 // profiles/heterogeneity_report.txt has both on the two workloads.
-#include "common.hpp"
-#include <string.h>
+#include "het_common.hpp"
 
 namespace epi {
 
-constexpr int HET_WG = 256;
 constexpr int kHetMinK = 2, kHetMaxK = 6;
 constexpr int64_t kHetCountsCap = 4LL << 30;          // bytes of counters (nsites * 2^k * 4) a report may allocate
-constexpr int64_t kHetLongRow = 512;                  // mean row bytes above which a whole wave takes a row
 
-struct HetArgs {
-  const uint8_t *xm;
-  const int64_t *off;
-  const int32_t *len, *rname, *strand, *start;
-  int64_t n;
-  const unsigned long long *key;      // [N] per-strand site table
-  const uint8_t *sctx;                // [N] context code of the site (2 CHH, 6 CHG, 7 CG)
-  const uint32_t *n1;                 // '+' sites
-  uint32_t N;
+struct HetArgs : HetRows {
   int32_t k;
-  uint32_t oom_mask, oou_mask;        // out-of-context methylated / unmethylated nibble codes (those not in the context)
-  double max_oo;
   uint32_t *counts;                   // [N << k]
 };
-
-__device__ __forceinline__ unsigned long long het_key(int32_t rname, int64_t pos) {
-  return ((unsigned long long)(uint32_t)rname << 32) + (unsigned long long)(pos + kPosBias);
-}
-
-// First index in [a, b) whose key is >= key, searched by the G lanes of a group at once: the lanes probe G evenly spaced
-// entries, the ballot of "below the key" (ones, then zeros: the table is sorted) picks one of the G + 1 parts, and a part of
-// at most G entries is probed whole.  log_{G+1} dependent loads instead of log_2: 6 instead of 22 for 3.5 M sites and 16
-// lanes, and the loads are what the kernel waits for.  Every lane of the wave calls this together; the lanes of a group pass
-// the same a, b and key (a = b: nothing to search).
-template <int G>
-__device__ __forceinline__ uint32_t het_lower_bound(const unsigned long long *__restrict__ keys, uint32_t a, uint32_t b,
-                                                    unsigned long long key, uint32_t sub, uint32_t grp) {
-  const unsigned long long gmask = G == 64 ? ~0ull : ((1ull << (G % 64)) - 1ull);
-  while (__ballot(a < b) != 0ull) {
-    const uint32_t span = b - a;
-    const bool last = span <= (uint32_t)G;
-    const uint32_t m = last ? a + sub : a + (uint32_t)(((uint64_t)span * (sub + 1u)) / (uint32_t)(G + 1));
-    const bool below = m < b && keys[m] < key;
-    const uint32_t cnt = (uint32_t)__popcll((__ballot(below) >> (grp * G)) & gmask);
-    if (last) {
-      a = b = a + cnt;
-    } else {
-      const uint32_t na = cnt > 0u ? a + (uint32_t)(((uint64_t)span * cnt) / (uint32_t)(G + 1)) + 1u : a;
-      const uint32_t nb = cnt < (uint32_t)G ? a + (uint32_t)(((uint64_t)span * (cnt + 1u)) / (uint32_t)(G + 1)) : b;
-      a = na; b = nb;
-    }
-  }
-  return a;
-}
 
 __global__ __launch_bounds__(HET_WG) void k_het_strand_flag(const int32_t *__restrict__ strand, uint32_t N, uint32_t *__restrict__ flag) {
   const uint32_t i = blockIdx.x * (uint32_t)HET_WG + threadIdx.x;
   if (i < N) flag[i] = strand[i] == 1 ? 1u : 0u;
-}
-
-// ordinal of CX row i in the per-strand table (rank: '+' rows in front of it)
-__device__ __forceinline__ uint32_t het_ordinal(int32_t strand, uint32_t i, uint32_t rank, uint32_t n1) {
-  return strand == 1 ? rank : n1 + (i - rank);
 }
 
 __global__ __launch_bounds__(HET_WG) void k_het_sites(const int32_t *__restrict__ rname, const int32_t *__restrict__ strand,
@@ -105,41 +58,8 @@ __global__ __launch_bounds__(HET_WG) void k_het_count(HetArgs a) {
   constexpr int GPW = 64 / G;                                // groups per wave
   const uint32_t lane = threadIdx.x & 63u, sub = lane % G, grp = lane / G;
   const int64_t row = ((int64_t)blockIdx.x * (HET_WG / 64) + (threadIdx.x >> 6)) * GPW + grp;
-  const bool have = row < a.n;
-  const int32_t st = have ? a.strand[row] : 0;
-  const int32_t len = have && (st == 1 || st == 2) ? a.len[row] : 0;
-  const int64_t off = have ? a.off[row] : 0;
-  const int32_t start = have ? a.start[row] : 0;
-  const uint8_t *__restrict__ p = a.xm + off;
-
-  // the read rule (rcpp_mhl_report.cpp:172-179, hmin = 0): four bytes per lane and step
-  uint32_t om = 0, ou = 0;
-  for (int32_t c = (int32_t)sub * 4; c < len; c += G * 4) {
-    uint32_t w = 0x0C0C0C0Cu;                                // '.': in neither class
-    if (c + 4 <= len) memcpy(&w, p + c, 4);
-    else for (int32_t j = 0; c + j < len; j++) w = (w & ~(0xFFu << (8 * j))) | ((uint32_t)p[c + j] << (8 * j));
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-      const uint32_t nib = (w >> (8 * j)) & 15u;
-      om += (a.oom_mask >> nib) & 1u;
-      ou += (a.oou_mask >> nib) & 1u;
-    }
-  }
-#pragma unroll
-  for (int d = 1; d < G; d <<= 1) { om += __shfl_xor(om, d, 64); ou += __shfl_xor(ou, d, 64); }
-  const double frac = (double)om / (double)((uint64_t)om + ou);       // :178 (0 / 0 = NaN: kept)
-  const bool keep = len > 0 && !(frac > a.max_oo);
-
-  // the row's sites: [lo, hi) of its strand's part of the table
-  uint32_t lo = 0, hi = 0;
-  {
-    const uint32_t n1 = *a.n1;
-    const uint32_t s0 = st == 1 ? 0u : n1, s1 = st == 1 ? n1 : a.N;
-    const int32_t rn = keep ? a.rname[row] : 0;
-    lo = het_lower_bound<G>(a.key, keep ? s0 : 0u, keep ? s1 : 0u, het_key(rn, (int64_t)start), sub, grp);
-    const uint32_t cap = (uint64_t)lo + (uint32_t)len < s1 ? lo + (uint32_t)len : s1;   // at most one site per position
-    hi = het_lower_bound<G>(a.key, keep ? lo : 0u, keep ? cap : 0u, het_key(rn, (int64_t)start + len), sub, grp);
-  }
+  const HetRow<G> r(a, row, sub, grp);
+  const uint32_t lo = r.lo, hi = r.hi;
 
   const int k = a.k;
   const unsigned long long gmask = G == 64 ? ~0ull : ((1ull << (G % 64)) - 1ull);
@@ -147,13 +67,8 @@ __global__ __launch_bounds__(HET_WG) void k_het_count(HetArgs a) {
   unsigned long long carry_v = 0, carry_m = 0;               // the k - 1 sites in front of this round, oldest at bit 0
   for (uint32_t base = lo; __ballot(base < hi) != 0ull; base += G) {
     const uint32_t g = base + sub;
-    bool valid = false, meth = false;
-    if (g < hi) {
-      const int32_t pos = (int32_t)(uint32_t)((a.key[g] & 0xFFFFFFFFull) - (unsigned long long)kPosBias);
-      const uint32_t nib = p[pos - start] & 15u;             // start <= pos < start + len: the search's bounds
-      valid = (nib & 7u) == a.sctx[g];
-      meth = valid && nib < 8u;
-    }
+    bool valid, meth;
+    r.call(a, g, valid, meth);
     const unsigned long long sv = (__ballot(valid) >> (grp * G)) & gmask, sm = (__ballot(meth) >> (grp * G)) & gmask;
     // the k sites that end at this lane's: from this round, and from the carry for the first k - 1 lanes
     const int back = k - 1;
@@ -205,7 +120,7 @@ __device__ __forceinline__ const uint32_t *het_window(const HetFinish &f, uint32
   if (last >= seg_end) return nullptr;
   const unsigned long long kl = f.key[last];
   if ((uint32_t)(kl >> 32) != (uint32_t)f.rname[i]) return nullptr;
-  *end = (int32_t)(uint32_t)((kl & 0xFFFFFFFFull) - (unsigned long long)kPosBias);
+  *end = het_key_pos(kl);
   return f.counts + ((size_t)g << f.k);
 }
 
@@ -274,44 +189,34 @@ static void het_finish_args(const epi_batch *b, HetFinish &f) {
   f.max_span = b->het_max_span;
 }
 
-static int het_report(epi_batch *b, const char *ctx, int k, double max_oo, int32_t min_reads, int32_t max_span, hipStream_t s,
-                      int64_t *nrow_out) {
-  // (a) the site table: the un-thresholded CX report of the reported context(s), methylated letters only as in
-  //     generateCytosineReport (the table has a row per position whose majority is one of them, either case)
+int het_cx_sites(epi_batch *b, const char *ctx, hipStream_t s, const char *who, int64_t *nsite) {
+  // the un-thresholded CX report of the reported context(s), methylated letters only as in generateCytosineReport (the
+  // table has a row per position whose majority is one of them, either case)
   char rep_ctx[8];
   int nrep = 0;
-  uint32_t ctx_mask = ctx_mask_of(ctx);
+  const uint32_t ctx_mask = ctx_mask_of(ctx);
   for (const char *c = "HXZ"; *c; c++)
     if (ctx_mask & ((1u << ctx_to_idx((unsigned char)*c)) | (1u << (ctx_to_idx((unsigned char)*c) + 8)))) rep_ctx[nrep++] = *c;
   rep_ctx[nrep] = 0;
-  int64_t nsite = 0;
-  EPI_TRY(epi_batch_cx_report_dev(b, nullptr, rep_ctx, s, &nsite));
+  *nsite = 0;
+  EPI_TRY(epi_batch_cx_report_dev(b, nullptr, rep_ctx, s, nsite));
   const bool whole = b->last_kind == KIND_CX;
   b->last_kind = KIND_NONE;
   if (!whole)
-    return fail(EPI_ERR_STATE, "epi_batch_heterogeneity_report_dev: the batch is set up for a sharded report (the sharded form is not built)");
-  b->het_nsite = nsite; b->het_k = k;
-  b->het_min_reads = (uint32_t)(min_reads > 1 ? min_reads : 1);
-  b->het_max_span = max_span;
-  if (nsite < k) { b->last_kind = KIND_HET; b->last_nrow = 0; b->het_nsite = 0; return EPI_OK; }
-  if (nsite >= (1LL << 31) || (nsite << k) * 4 > kHetCountsCap)
-    return fail(EPI_ERR_ARG, "epi_batch_heterogeneity_report_dev: %lld sites x %d patterns need %lld bytes of counters, above the cap of %lld",
-                (long long)nsite, 1 << k, (long long)((nsite << k) * 4), (long long)kHetCountsCap);
+    return fail(EPI_ERR_STATE, "%s: the batch is set up for a sharded report (the sharded form is not built)", who);
+  return EPI_OK;
+}
+
+int het_site_table(epi_batch *b, int64_t nsite, hipStream_t s) {
   const size_t N = (size_t)nsite;
   const int64_t nb_sites = ((int64_t)N + HET_WG - 1) / HET_WG;
-  constexpr int rows16 = HET_WG / 16, rows64 = HET_WG / 64;
-  const bool wide = b->nbytes > kHetLongRow * b->n;
-  const int64_t nb_rows = (b->n + (wide ? rows64 : rows16) - 1) / (wide ? rows64 : rows16);
   EPI_TRY(check_grid(nb_sites, HET_WG, "heterogeneity site kernels"));
-  EPI_TRY(check_grid(nb_rows, HET_WG, "heterogeneity counting kernel"));
-
   EPI_TRY(b->het_cx.ensure(N * 6 * 4));
   EPI_TRY(b->het_rank.ensure(N * 4));
   EPI_TRY(b->het_flag.ensure(N * 4));
   EPI_TRY(b->het_key.ensure(N * 8));
   EPI_TRY(b->het_sctx.ensure(N));
   EPI_TRY(b->het_scal.ensure(64));
-  EPI_TRY(b->het_counts.ensure((N << k) * 4));
   int32_t *cx = b->het_cx.as<int32_t>();
   int32_t *cols[6];
   for (int i = 0; i < 6; i++) cols[i] = cx + (size_t)i * N;
@@ -326,15 +231,45 @@ static int het_report(epi_batch *b, const char *ctx, int k, double max_oo, int32
   hipLaunchKernelGGL(k_het_sites, dim3((unsigned)nb_sites), dim3(HET_WG), 0, s, cols[0], cols[1], cols[2], cols[3], rank, &scal[0],
                      (uint32_t)N, b->het_key.as<unsigned long long>(), b->het_sctx.as<uint8_t>());
   EPI_HIP(hipGetLastError());
+  return EPI_OK;
+}
+
+void het_rows_args(const epi_batch *b, uint32_t ctx_mask, double max_oo, HetRows &a) {
+  a.xm = b->xm; a.off = b->off; a.len = b->len; a.rname = b->rname; a.strand = b->strand; a.start = b->start; a.n = b->n;
+  a.key = b->het_key.as<unsigned long long>(); a.sctx = b->het_sctx.as<uint8_t>(); a.n1 = b->het_scal.as<uint32_t>();
+  a.N = (uint32_t)b->het_nsite;
+  a.oom_mask = ((1u << 2) | (1u << 5) | (1u << 6) | (1u << 7)) & ~ctx_mask;           // rcpp_mhl_report.cpp:176-177
+  a.oou_mask = ((1u << 10) | (1u << 13) | (1u << 14) | (1u << 15)) & ~ctx_mask;
+  a.max_oo = max_oo;
+}
+
+static int het_report(epi_batch *b, const char *ctx, int k, double max_oo, int32_t min_reads, int32_t max_span, hipStream_t s,
+                      int64_t *nrow_out) {
+  // (a) the site table
+  int64_t nsite = 0;
+  EPI_TRY(het_cx_sites(b, ctx, s, "epi_batch_heterogeneity_report_dev", &nsite));
+  b->het_nsite = nsite; b->het_k = k;
+  b->het_min_reads = (uint32_t)(min_reads > 1 ? min_reads : 1);
+  b->het_max_span = max_span;
+  if (nsite < k) { b->last_kind = KIND_HET; b->last_nrow = 0; b->het_nsite = 0; return EPI_OK; }
+  if (nsite >= (1LL << 31) || (nsite << k) * 4 > kHetCountsCap)
+    return fail(EPI_ERR_ARG, "epi_batch_heterogeneity_report_dev: %lld sites x %d patterns need %lld bytes of counters, above the cap of %lld",
+                (long long)nsite, 1 << k, (long long)((nsite << k) * 4), (long long)kHetCountsCap);
+  const size_t N = (size_t)nsite;
+  const int64_t nb_sites = ((int64_t)N + HET_WG - 1) / HET_WG;
+  bool wide = false;
+  const int64_t nb_rows = het_count_blocks(b, &wide);
+  EPI_TRY(check_grid(nb_rows, HET_WG, "heterogeneity counting kernel"));
+  EPI_TRY(het_site_table(b, nsite, s));
+  EPI_TRY(b->het_counts.ensure((N << k) * 4));
+  uint32_t *scal = b->het_scal.as<uint32_t>();             // [0] '+' sites, [1] reported rows
+  uint32_t *flag = b->het_flag.as<uint32_t>();
 
   // (b) the histograms
   EPI_HIP(hipMemsetAsync(b->het_counts.p, 0, (N << k) * 4, s));
   HetArgs a;
-  a.xm = b->xm; a.off = b->off; a.len = b->len; a.rname = b->rname; a.strand = b->strand; a.start = b->start; a.n = b->n;
-  a.key = b->het_key.as<unsigned long long>(); a.sctx = b->het_sctx.as<uint8_t>(); a.n1 = &scal[0]; a.N = (uint32_t)N; a.k = k;
-  a.oom_mask = ((1u << 2) | (1u << 5) | (1u << 6) | (1u << 7)) & ~ctx_mask;           // rcpp_mhl_report.cpp:176-177
-  a.oou_mask = ((1u << 10) | (1u << 13) | (1u << 14) | (1u << 15)) & ~ctx_mask;
-  a.max_oo = max_oo;
+  het_rows_args(b, ctx_mask_of(ctx), max_oo, a);
+  a.k = k;
   a.counts = b->het_counts.as<uint32_t>();
   prof_begin("het_count", s);
   if (wide) hipLaunchKernelGGL((k_het_count<64>), dim3((unsigned)nb_rows), dim3(HET_WG), 0, s, a);

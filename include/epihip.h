@@ -466,6 +466,49 @@ int epi_batch_heterogeneity_report_dev(epi_batch *b, const char *ctx, int k, dou
 int epi_batch_heterogeneity_fetch_dev(epi_batch *b, int32_t *const d_icols[7], double *const d_dcols[4],
                                       int32_t *d_counts /* may be NULL */, void *stream);
 
+/* Linkage report: the co-methylation of pairs of neighbouring sites over the reads that cover both, and the methylation
+ * haplotype blocks that follow from it (Guo et al. 2017, the paper lMHL comes from).  The reference has no such report.
+ *  ctx       context letters in both cases ("Zz", "XxZz", ...); D = max_neighbours, 1 .. 16.
+ *  Sites, calls and kept rows: exactly as for the heterogeneity report above -- the rows of the un-thresholded CX report of
+ *            the whole batch, ordered by pos per (rname, strand) as s_0 < s_1 < ...; a call where (x & 7) == the site's
+ *            context code, methylated when x < 8; the lMHL read rule with hmin = 0 and max_ooctx_meth_frac.
+ *  Pairs     pair (j, d) is (s_j, s_{j+d}) for 1 <= d <= D.  A pair never crosses a sequence or strand.
+ *  Counts    a kept row with a call at both sites adds 1 to counts[j][d-1][p], p = meth(s_j) + 2 meth(s_{j+d}) (the
+ *            heterogeneity report's bit order): the bins are n_uu, n_mu, n_um, n_mm.  What the row shows at the sites in
+ *            between does not matter: a '.' or another context between the two is not a gap.  Counters are u32;
+ *            nsites * D * 16 bytes above 4 GiB: EPI_ERR_ARG before anything is allocated (epi_linkage_counter_bytes is that
+ *            check on its own: the bytes, or EPI_ERR_ARG).
+ *  Metrics   float64, from the four integers: n = sum of the bins; margins A = n_mm + n_mu, a = n_um + n_uu,
+ *            B = n_mm + n_um, b = n_mu + n_uu; num = n_mm n_uu - n_mu n_um, exact in int64; cov = num / n^2 (n^2 as the
+ *            product of two doubles); r2 = num^2 / (A a B b), the product taken left to right in double;
+ *            dprime = num / min(A b, a B) when num > 0, num / min(A B, a b) when num < 0, 0 when num == 0.  r2 and dprime
+ *            are NaN when any margin is 0.  No launch shape enters a result.
+ *  Rows      pair (j, d) is reported when n >= max(min_reads, 1) and (max_distance == 0 or s_{j+d} - s_j <= max_distance),
+ *            in the order of the CX row s_j is on, then d ascending.
+ *  Columns   eleven int32 (rname, strand, pos, pos2, context of s_j, neighbour = d, nreads, n_uu, n_mu, n_um, n_mm) and
+ *            three double (cov, r2, dprime).
+ *  Blocks    (epi_batch_linkage_blocks_dev: min_r2 in [0, 1], min_sites >= 2, on the pair table of the last report)  pair
+ *            (j, d) is linked when it is reported and r2 >= min_r2; NaN is not linked.  back[e] is the largest
+ *            t <= min(D, ordinal of e in its strand) such that the pairs (e - d, d) are linked for every d = 1 .. t.
+ *            Blocks are built greedily and do not overlap, per (rname, strand): start at the strand's first site s with
+ *            e = s; extend while e + 1 is on the strand and back[e + 1] >= min(D, e + 1 - s); emit (s .. e) when
+ *            e - s + 1 >= min_sites; restart at s = e + 1.  Five int32 columns (rname, strand, start, end, nsites) and
+ *            one double: mean_r2, the mean of the block's nsites - 1 adjacent (d = 1) r2 values, summed in ascending
+ *            site order by one thread.  Block rows are in the order of the CX rows of their first sites.
+ * Steps and state as for the heterogeneity report: report_dev runs the report (synchronises `stream`), fetch_dev writes the
+ * rows.  blocks_dev and the two linkage fetches are valid only after a linkage report (blocks_fetch_dev only after
+ * blocks_dev on it); any other report's fetch after a linkage report, or a linkage fetch after any other report, is
+ * EPI_ERR_STATE.  blocks_dev does not invalidate the pair table, and may be repeated with other arguments.  The CX report
+ * inside leaves the direct-mode record exactly as epi_batch_cx_report_dev(b, NULL, the upper-case letters of ctx) would.
+ * Single GPU only: the counts are additive over row shards once the site table is common, the sharded form is not built
+ * (a batch with shared tiles attached: EPI_ERR_STATE). */
+int epi_batch_linkage_report_dev(epi_batch *b, const char *ctx, int max_neighbours, int32_t max_distance,
+                                 double max_ooctx_meth_frac, int32_t min_reads, void *stream, int64_t *nrow_out);
+int epi_batch_linkage_fetch_dev(epi_batch *b, int32_t *const d_icols[11], double *const d_dcols[3], void *stream);
+int epi_batch_linkage_blocks_dev(epi_batch *b, double min_r2, int32_t min_sites, void *stream, int64_t *nblock_out);
+int epi_batch_linkage_blocks_fetch_dev(epi_batch *b, int32_t *const d_icols[5], double *const d_dcols[1], void *stream);
+int epi_linkage_counter_bytes(int64_t nsites, int max_neighbours, int64_t *bytes_out);
+
 /* rcpp_extract_patterns (src/rcpp_extract_patterns.cpp:26-211; caller .getPatterns, R/internal.R:683-714):
  * methylation patterns of the reads overlapping one target.  Library-owned host table: per pattern strand, start,
  * end, nbase, beta, the FNV-1a hash the R side prints as 16 hex digits ("pattern"), the ordered column positions
