@@ -166,6 +166,9 @@ _SIGS = {
     "epi_batch_mhl_fetch_host": (C.c_int, [_VP, C.POINTER(_VP), C.POINTER(_VP), _VP]),
     "epi_batch_heterogeneity_report_dev": (C.c_int, [_VP, _CS, C.c_int, _F64, _I32, _I32, _VP, C.POINTER(_I64)]),
     "epi_batch_heterogeneity_fetch_dev": (C.c_int, [_VP, C.POINTER(_VP), C.POINTER(_VP), _VP, _VP]),
+    "epi_heterogeneity_counter_bytes": (C.c_int, [_I64, C.c_int, C.POINTER(_I64)]),
+    "epi_batch_heterogeneity_compare_dev": (C.c_int, [_VP, _VP, _CS, C.c_int, _F64, _I32, _I32, _VP, C.POINTER(_I64), C.POINTER(_I64)]),
+    "epi_batch_heterogeneity_compare_fetch_dev": (C.c_int, [_VP, C.POINTER(_VP), C.POINTER(_VP), _VP, _VP, _VP]),
     "epi_batch_linkage_report_dev": (C.c_int, [_VP, _CS, C.c_int, _I32, _F64, _I32, _VP, C.POINTER(_I64)]),
     "epi_batch_linkage_fetch_dev": (C.c_int, [_VP, C.POINTER(_VP), C.POINTER(_VP), _VP]),
     "epi_batch_linkage_blocks_dev": (C.c_int, [_VP, _F64, _I32, _VP, C.POINTER(_I64)]),

@@ -432,6 +432,51 @@ def rcpp_heterogeneity_report(df, ctx, k, max_ooctx_meth_frac, min_reads=1, max_
     return rep
 
 
+HETEROGENEITY_COMPARE_COLUMNS = ("rname", "strand", "pos", "end", "context", "nreads_a", "nreads_b", "npatterns_a", "npatterns_b", "df",
+                                 "beta_a", "beta_b", "entropy_a", "entropy_b", "epipolymorphism_a", "epipolymorphism_b", "pdr_a", "pdr_b",
+                                 "delta_beta", "delta_entropy", "jsd", "tvd", "g")
+
+
+def rcpp_heterogeneity_compare(df_a, df_b, ctx, k, max_ooctx_meth_frac, min_reads=1, max_window_span=0, as_device=False,
+                               with_counts=False):
+    """Per window of k neighbouring sites that the un-thresholded cytosine reports of both inputs have (include/epihip.h,
+    epi_batch_heterogeneity_compare_dev): rname, strand, pos, end, context, nreads_a, nreads_b, npatterns_a, npatterns_b, df
+    (int32), beta, entropy, epipolymorphism and pdr of either input, delta_beta, delta_entropy, jsd, tvd, g (float64).
+    Both inputs under one sequence dictionary (differing `levels`: ValueError), on one device.  The Report carries df_a's
+    levels and `ncommon`, the number of common sites; with_counts: `counts_a` and `counts_b` hold the [nrow, 2^k] int32
+    pattern histograms of the reported windows."""
+    bam_a, bam_b = _as_bam(df_a), _as_bam(df_b)
+    if bam_a.levels != bam_b.levels:
+        raise ValueError("the two inputs have different sequence names (levels): their rname codes cannot be compared")
+    torch = _torch()
+    lib = _lib.load()
+    a = bam_a.batch()
+    b = bam_b.batch(bam_a.device)
+    if bam_b.device != bam_a.device:
+        raise ValueError("the two inputs are on different devices (%s and %s)" % (bam_a.device, bam_b.device))
+    dev = "cuda:%d" % bam_a.device
+    ncommon, nrow = C.c_int64(0), C.c_int64(0)
+    _lib.check(lib.epi_batch_heterogeneity_compare_dev(a, b, _lib.enc(ctx), int(k), float(max_ooctx_meth_frac), int(min_reads),
+                                                       int(max_window_span), _stream(bam_a.device), C.byref(ncommon), C.byref(nrow)))
+    n = nrow.value
+    icols = list(torch.empty((10, n), dtype=torch.int32, device=dev).unbind(0))
+    dcols = list(torch.empty((13, n), dtype=torch.float64, device=dev).unbind(0))
+    counts = [torch.empty((n, 1 << int(k)), dtype=torch.int32, device=dev) for _ in range(2)] if with_counts else [None, None]
+    if n:
+        _lib.check(lib.epi_batch_heterogeneity_compare_fetch_dev(a, _ptr_array(icols), _ptr_array(dcols),
+                                                                 *[C.c_void_p(c.data_ptr()) if with_counts else None for c in counts],
+                                                                 _stream(bam_a.device)))
+    cols = icols + dcols
+    if not as_device:
+        cols = [c.cpu().numpy() for c in cols]
+        counts = [c.cpu().numpy() if with_counts else None for c in counts]
+    rep = Report(dict(zip(HETEROGENEITY_COMPARE_COLUMNS, cols)), bam_a.levels)
+    rep.ncommon = ncommon.value
+    if with_counts:
+        rep.counts_a, rep.counts_b = counts
+    return rep
+
+
 LINKAGE_COLUMNS = ("rname", "strand", "pos", "pos2", "context", "neighbour", "nreads", "n_uu", "n_mu", "n_um", "n_mm",
                    "cov", "r2", "dprime")
 BLOCK_COLUMNS = ("rname", "strand", "start", "end", "nsites", "mean_r2")
@@ -659,6 +704,31 @@ def generateHeterogeneityReport(bam, report_file=None, window_context=None, wind
     c = CONTEXT_TO_BASES[window_context]
     rep = rcpp_heterogeneity_report(bam, c["ctx_meth"] + c["ctx_unmeth"], int(window_sites), max_outofcontext_beta,
                                     min_reads, max_window_span, as_device=as_device)
+    if report_file is None:
+        return rep
+    writeReport(rep, report_file, gzip)
+    return None
+
+
+def compareHeterogeneity(bam_a, bam_b, report_file=None, window_context=None, window_sites=4, min_reads=1, max_window_span=0,
+                         max_outofcontext_beta=0.1, gzip=False, verbose=False, as_device=False, **preprocess_args):
+    """Two samples against each other per window of `window_sites` (2 to 6) neighbouring cytosines of `window_context`
+    that the cytosine reports of BOTH have (generateCytosineReport(threshold_reads=False, report_context=window_context);
+    same position, strand and context): what generateHeterogeneityReport gives for either sample on these windows
+    (columns *_a, *_b), delta_beta and delta_entropy (b minus a), the Jensen-Shannon divergence of the two epiallele
+    histograms in bits (jsd), their total variation distance (tvd) and the likelihood-ratio statistic g of the 2 x 2^k
+    table with its degrees of freedom df (no p-value is computed).  Windows with fewer than min_reads reads in either
+    sample, or (max_window_span > 0) spanning more than max_window_span bases, are left out.  Both inputs go through
+    preprocessBam with the same preprocess_args and must have the same sequence names.  The Report's `ncommon` is the
+    number of common sites.  The reference has no such report."""
+    window_context = _match_arg(window_context, _CTX_CHOICES, "window.context")
+    if isinstance(window_sites, bool) or int(window_sites) != window_sites or not 2 <= int(window_sites) <= 6:
+        raise ValueError("'window.sites' should be an integer from 2 to 6")
+    bam_a = preprocessBam(bam_a, **preprocess_args)
+    bam_b = preprocessBam(bam_b, **preprocess_args)
+    c = CONTEXT_TO_BASES[window_context]
+    rep = rcpp_heterogeneity_compare(bam_a, bam_b, c["ctx_meth"] + c["ctx_unmeth"], int(window_sites), max_outofcontext_beta,
+                                     min_reads, max_window_span, as_device=as_device)
     if report_file is None:
         return rep
     writeReport(rep, report_file, gzip)

@@ -157,6 +157,7 @@ enum ReportKind {
   KIND_MHLF_SHARED = 5,     // ... of a sharded lMHL report, one-pass kernel (slabs in its layout, mhl_common.hpp)
   KIND_HET = 6,             // finished heterogeneity report
   KIND_LINK = 7,            // finished linkage report
+  KIND_HETCMP = 8,          // finished heterogeneity comparison (on its first batch; the second is left at KIND_NONE)
 };
 }  // namespace epi
 
@@ -244,6 +245,10 @@ struct epi_batch {
   uint32_t link_min_reads = 1;
   int64_t link_max_dist = 0, link_nblock = 0;
   bool link_blocks = false;                    // epi_batch_linkage_blocks_dev has run on the last linkage report
+  // heterogeneity comparison (het_compare.hip), all on its first batch a: the common site table and what follows from it
+  // live in a's heterogeneity buffers (het_counts: a's side, het_scal[3]: common sites); its own are a's un-intersected
+  // CX table, which the common one is compacted from, and the counters of the second batch's rows
+  epi::DevBuf cmp_cx, cmp_counts_b;
 
   // state of the last report (for fetch)
   epi::ReportKind last_kind = epi::KIND_NONE;

@@ -1,6 +1,8 @@
-// What the heterogeneity report (heterogeneity.hip) and the linkage report (linkage.hip) share: the per-strand site table
-// of the batch's un-thresholded CX report, the read rule, a row's site range in that table and its call at a site.  Both
-// reports count on the same data path (heterogeneity.hip has its description); they differ in what a row adds to.
+// What the heterogeneity report (heterogeneity.hip), the linkage report (linkage.hip) and the heterogeneity comparison
+// (het_compare.hip) share: the per-strand site table of the batch's un-thresholded CX report, the read rule, a row's site
+// range in that table and its call at a site.  All count on the same data path (heterogeneity.hip has its description);
+// the reports differ in what a row adds to, the comparison counts two batches with the heterogeneity report's kernel on
+// the sites both have.
 #pragma once
 #include "common.hpp"
 #include <string.h>
@@ -117,15 +119,55 @@ struct HetRow {
   }
 };
 
+// What the kernels behind the counting see (heterogeneity.hip, het_compare.hip): the site table in CX row order, the
+// per-strand table and the counters of the windows
+struct HetFinish {
+  const int32_t *rname, *strand, *pos, *context;   // the CX table
+  const uint32_t *rank, *n1;
+  const unsigned long long *key;
+  const uint32_t *counts;
+  uint32_t N;
+  int32_t k;
+  uint32_t min_reads;
+  int64_t max_span;
+};
+
+// the window that starts at CX row i: its counters, or null when fewer than k sites follow on its (rname, strand)
+__device__ __forceinline__ const uint32_t *het_window(const HetFinish &f, uint32_t i, int32_t *end) {
+  const int32_t st = f.strand[i];
+  const uint32_t n1 = *f.n1;
+  const uint32_t g = het_ordinal(st, i, f.rank[i], n1), seg_end = st == 1 ? n1 : f.N;
+  const uint32_t last = g + (uint32_t)f.k - 1u;
+  if (last >= seg_end) return nullptr;
+  const unsigned long long kl = f.key[last];
+  if ((uint32_t)(kl >> 32) != (uint32_t)f.rname[i]) return nullptr;
+  *end = het_key_pos(kl);
+  return f.counts + ((size_t)g << f.k);
+}
+
+constexpr int kHetMinK = 2, kHetMaxK = 6;
+// bytes of counters (nsites * 2^k * 4) of a heterogeneity report or of one side of a comparison, or -1 when a report
+// refuses them: above 4 GiB, or sites beyond 32-bit ordinals
+int64_t het_counter_bytes(int64_t nsites, int k);
+
 // Host side (heterogeneity.hip).  het_cx_sites: the un-thresholded CX report of the upper-case letters of ctx, as
 // epi_batch_cx_report_dev(b, NULL, those) runs it; refuses a batch set up for a sharded report (`who` names the caller in
 // the message) and leaves last_kind = KIND_NONE.  het_site_table: that report's six columns fetched into het_cx, every
 // row's '+' rank in het_rank, the per-strand table in het_key / het_sctx and the '+' site count in het_scal[0]
-// (het_scal[1] is the caller's); nsite >= 1.  het_flag holds nsite scratch words afterwards.
+// (het_scal[1] is the caller's); nsite >= 1.  het_flag holds nsite scratch words afterwards.  Its two halves on their
+// own: het_cx_fetch brings the six columns into `cx` ([6][nsite]), het_strand_table makes rank, key, context and '+'
+// count from a table of nsite rows that is in het_cx already (its first four columns, [.][nsite]).
 int het_cx_sites(epi_batch *b, const char *ctx, hipStream_t s, const char *who, int64_t *nsite);
+int het_cx_fetch(epi_batch *b, int64_t nsite, hipStream_t s, DevBuf &cx);
+int het_strand_table(epi_batch *b, int64_t nsite, hipStream_t s);
 int het_site_table(epi_batch *b, int64_t nsite, hipStream_t s);
 // the rows, the table and the read rule's masks for the contexts of ctx_mask
 void het_rows_args(const epi_batch *b, uint32_t ctx_mask, double max_oo, HetRows &a);
+// the site table, window size, thresholds and counters (het_counts) of the last report on b
+void het_finish_args(const epi_batch *b, HetFinish &f);
+// k_het_count<16> or <64> (heterogeneity.hip): the rows of `a` add to counts [a.N << k], which the caller has zeroed;
+// nb_rows and wide are het_count_blocks' of the batch the rows are of
+int het_count_launch(const HetRows &a, int k, uint32_t *counts, int64_t nb_rows, bool wide, hipStream_t s);
 // workgroups of a counting kernel, and whether a whole wave takes a row
 inline int64_t het_count_blocks(const epi_batch *b, bool *wide) {
   *wide = b->nbytes > kHetLongRow * b->n;

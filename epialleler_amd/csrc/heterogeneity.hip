@@ -28,7 +28,6 @@
 
 namespace epi {
 
-constexpr int kHetMinK = 2, kHetMaxK = 6;
 constexpr int64_t kHetCountsCap = 4LL << 30;          // bytes of counters (nsites * 2^k * 4) a report may allocate
 
 struct HetArgs : HetRows {
@@ -100,30 +99,6 @@ __global__ __launch_bounds__(HET_WG) void k_het_count(HetArgs a) {
   }
 }
 
-struct HetFinish {
-  const int32_t *rname, *strand, *pos, *context;   // the CX table
-  const uint32_t *rank, *n1;
-  const unsigned long long *key;
-  const uint32_t *counts;
-  uint32_t N;
-  int32_t k;
-  uint32_t min_reads;
-  int64_t max_span;
-};
-
-// the window that starts at CX row i: its counters, or null when fewer than k sites follow on its (rname, strand)
-__device__ __forceinline__ const uint32_t *het_window(const HetFinish &f, uint32_t i, int32_t *end) {
-  const int32_t st = f.strand[i];
-  const uint32_t n1 = *f.n1;
-  const uint32_t g = het_ordinal(st, i, f.rank[i], n1), seg_end = st == 1 ? n1 : f.N;
-  const uint32_t last = g + (uint32_t)f.k - 1u;
-  if (last >= seg_end) return nullptr;
-  const unsigned long long kl = f.key[last];
-  if ((uint32_t)(kl >> 32) != (uint32_t)f.rname[i]) return nullptr;
-  *end = het_key_pos(kl);
-  return f.counts + ((size_t)g << f.k);
-}
-
 __global__ __launch_bounds__(HET_WG) void k_het_keep(HetFinish f, uint32_t *__restrict__ flag) {
   const uint32_t i = blockIdx.x * (uint32_t)HET_WG + threadIdx.x;
   if (i >= f.N) return;
@@ -175,7 +150,7 @@ __global__ __launch_bounds__(HET_WG) void k_het_emit(HetFinish f, const uint32_t
   o.pdr[r] = 1.0 - (double)((uint64_t)c[0] + c[nb - 1]) / dn;
 }
 
-static void het_finish_args(const epi_batch *b, HetFinish &f) {
+void het_finish_args(const epi_batch *b, HetFinish &f) {
   const int32_t *cx = b->het_cx.as<int32_t>();
   const size_t N = (size_t)b->het_nsite;
   f.rname = cx; f.strand = cx + N; f.pos = cx + 2 * N; f.context = cx + 3 * N;
@@ -207,29 +182,56 @@ int het_cx_sites(epi_batch *b, const char *ctx, hipStream_t s, const char *who, 
   return EPI_OK;
 }
 
-int het_site_table(epi_batch *b, int64_t nsite, hipStream_t s) {
+int het_cx_fetch(epi_batch *b, int64_t nsite, hipStream_t s, DevBuf &cx) {
+  const size_t N = (size_t)nsite;
+  EPI_TRY(cx.ensure(N * 6 * 4));
+  int32_t *cols[6];
+  for (int i = 0; i < 6; i++) cols[i] = cx.as<int32_t>() + (size_t)i * N;
+  b->last_kind = KIND_CX;                                  // (for the fetch of the table that has just been made)
+  const int rc = epi_batch_cx_fetch_dev(b, cols, s);
+  b->last_kind = KIND_NONE;
+  return rc;
+}
+
+int het_strand_table(epi_batch *b, int64_t nsite, hipStream_t s) {
   const size_t N = (size_t)nsite;
   const int64_t nb_sites = ((int64_t)N + HET_WG - 1) / HET_WG;
   EPI_TRY(check_grid(nb_sites, HET_WG, "heterogeneity site kernels"));
-  EPI_TRY(b->het_cx.ensure(N * 6 * 4));
   EPI_TRY(b->het_rank.ensure(N * 4));
   EPI_TRY(b->het_flag.ensure(N * 4));
   EPI_TRY(b->het_key.ensure(N * 8));
   EPI_TRY(b->het_sctx.ensure(N));
   EPI_TRY(b->het_scal.ensure(64));
-  int32_t *cx = b->het_cx.as<int32_t>();
-  int32_t *cols[6];
-  for (int i = 0; i < 6; i++) cols[i] = cx + (size_t)i * N;
-  b->last_kind = KIND_CX;                                  // (for the fetch of the table that has just been made)
-  const int rc = epi_batch_cx_fetch_dev(b, cols, s);
-  b->last_kind = KIND_NONE;
-  EPI_TRY(rc);
+  const int32_t *cx = b->het_cx.as<int32_t>();
   uint32_t *scal = b->het_scal.as<uint32_t>();             // [0] '+' sites, [1] reported rows
   uint32_t *flag = b->het_flag.as<uint32_t>(), *rank = b->het_rank.as<uint32_t>();
-  hipLaunchKernelGGL(k_het_strand_flag, dim3((unsigned)nb_sites), dim3(HET_WG), 0, s, cols[1], (uint32_t)N, flag);
+  hipLaunchKernelGGL(k_het_strand_flag, dim3((unsigned)nb_sites), dim3(HET_WG), 0, s, cx + N, (uint32_t)N, flag);
   EPI_TRY(scan_exclusive_u32(flag, rank, (int64_t)N, &scal[0], b->scan_tmp, s));
-  hipLaunchKernelGGL(k_het_sites, dim3((unsigned)nb_sites), dim3(HET_WG), 0, s, cols[0], cols[1], cols[2], cols[3], rank, &scal[0],
+  hipLaunchKernelGGL(k_het_sites, dim3((unsigned)nb_sites), dim3(HET_WG), 0, s, cx, cx + N, cx + 2 * N, cx + 3 * N, rank, &scal[0],
                      (uint32_t)N, b->het_key.as<unsigned long long>(), b->het_sctx.as<uint8_t>());
+  EPI_HIP(hipGetLastError());
+  return EPI_OK;
+}
+
+int het_site_table(epi_batch *b, int64_t nsite, hipStream_t s) {
+  EPI_TRY(check_grid((nsite + HET_WG - 1) / HET_WG, HET_WG, "heterogeneity site kernels"));
+  EPI_TRY(het_cx_fetch(b, nsite, s, b->het_cx));
+  return het_strand_table(b, nsite, s);
+}
+
+int64_t het_counter_bytes(int64_t nsites, int k) {
+  if (nsites < 0 || k < kHetMinK || k > kHetMaxK || nsites >= (1LL << 31)) return -1;
+  const int64_t bytes = (nsites << k) * 4;
+  return bytes > kHetCountsCap ? -1 : bytes;
+}
+
+int het_count_launch(const HetRows &rows, int k, uint32_t *counts, int64_t nb_rows, bool wide, hipStream_t s) {
+  HetArgs a;
+  static_cast<HetRows &>(a) = rows;
+  a.k = k;
+  a.counts = counts;
+  if (wide) hipLaunchKernelGGL((k_het_count<64>), dim3((unsigned)nb_rows), dim3(HET_WG), 0, s, a);
+  else hipLaunchKernelGGL((k_het_count<16>), dim3((unsigned)nb_rows), dim3(HET_WG), 0, s, a);
   EPI_HIP(hipGetLastError());
   return EPI_OK;
 }
@@ -252,7 +254,7 @@ static int het_report(epi_batch *b, const char *ctx, int k, double max_oo, int32
   b->het_min_reads = (uint32_t)(min_reads > 1 ? min_reads : 1);
   b->het_max_span = max_span;
   if (nsite < k) { b->last_kind = KIND_HET; b->last_nrow = 0; b->het_nsite = 0; return EPI_OK; }
-  if (nsite >= (1LL << 31) || (nsite << k) * 4 > kHetCountsCap)
+  if (het_counter_bytes(nsite, k) < 0)
     return fail(EPI_ERR_ARG, "epi_batch_heterogeneity_report_dev: %lld sites x %d patterns need %lld bytes of counters, above the cap of %lld",
                 (long long)nsite, 1 << k, (long long)((nsite << k) * 4), (long long)kHetCountsCap);
   const size_t N = (size_t)nsite;
@@ -267,15 +269,12 @@ static int het_report(epi_batch *b, const char *ctx, int k, double max_oo, int32
 
   // (b) the histograms
   EPI_HIP(hipMemsetAsync(b->het_counts.p, 0, (N << k) * 4, s));
-  HetArgs a;
+  HetRows a;
   het_rows_args(b, ctx_mask_of(ctx), max_oo, a);
-  a.k = k;
-  a.counts = b->het_counts.as<uint32_t>();
   prof_begin("het_count", s);
-  if (wide) hipLaunchKernelGGL((k_het_count<64>), dim3((unsigned)nb_rows), dim3(HET_WG), 0, s, a);
-  else hipLaunchKernelGGL((k_het_count<16>), dim3((unsigned)nb_rows), dim3(HET_WG), 0, s, a);
+  const int rc_count = het_count_launch(a, k, b->het_counts.as<uint32_t>(), nb_rows, wide, s);
   prof_end("het_count", s);
-  EPI_HIP(hipGetLastError());
+  EPI_TRY(rc_count);
 
   // (c) which windows are reported, and where
   HetFinish f;
@@ -297,6 +296,19 @@ static int het_report(epi_batch *b, const char *ctx, int k, double max_oo, int32
 using namespace epi;
 
 extern "C" {
+
+int epi_heterogeneity_counter_bytes(int64_t nsites, int k, int64_t *bytes_out) {
+  if (!bytes_out) return fail(EPI_ERR_ARG, "epi_heterogeneity_counter_bytes: NULL argument");
+  *bytes_out = 0;
+  if (nsites < 0 || k < kHetMinK || k > kHetMaxK)
+    return fail(EPI_ERR_ARG, "epi_heterogeneity_counter_bytes: %lld sites, k = %d (%d to %d)", (long long)nsites, k, kHetMinK, kHetMaxK);
+  const int64_t bytes = het_counter_bytes(nsites, k);
+  if (bytes < 0)
+    return fail(EPI_ERR_ARG, "epi_heterogeneity_counter_bytes: %lld sites x %d patterns need more than %lld bytes of counters",
+                (long long)nsites, 1 << k, (long long)kHetCountsCap);
+  *bytes_out = bytes;
+  return EPI_OK;
+}
 
 int epi_batch_heterogeneity_report_dev(epi_batch *b, const char *ctx, int k, double max_ooctx_meth_frac, int32_t min_reads,
                                        int32_t max_window_span, void *stream, int64_t *nrow_out) {
@@ -327,7 +339,9 @@ int epi_batch_heterogeneity_fetch_dev(epi_batch *b, int32_t *const d_icols[7], d
   o.beta = d_dcols[0]; o.epipoly = d_dcols[1]; o.entropy = d_dcols[2]; o.pdr = d_dcols[3];
   o.counts = d_counts;
   const unsigned nb = (unsigned)(((int64_t)f.N + HET_WG - 1) / HET_WG);
+  prof_begin("het_emit", s);
   hipLaunchKernelGGL(k_het_emit, dim3(nb), dim3(HET_WG), 0, s, f, b->het_flag.as<uint32_t>(), b->het_out.as<uint32_t>(), o);
+  prof_end("het_emit", s);
   EPI_HIP(hipGetLastError());
   return EPI_OK;
 }

@@ -466,6 +466,49 @@ int epi_batch_heterogeneity_report_dev(epi_batch *b, const char *ctx, int k, dou
 int epi_batch_heterogeneity_fetch_dev(epi_batch *b, int32_t *const d_icols[7], double *const d_dcols[4],
                                       int32_t *d_counts /* may be NULL */, void *stream);
 
+/* The check a heterogeneity report, and a comparison for each of its two sides, makes before it allocates counters:
+ * *bytes_out = nsites * 2^k * 4, or EPI_ERR_ARG above 4 GiB, for nsites >= 2^31 or outside 0 <= nsites, 2 <= k <= 6. */
+int epi_heterogeneity_counter_bytes(int64_t nsites, int k, int64_t *bytes_out);
+
+/* Heterogeneity comparison: the epiallele histograms of two batches over the windows of the sites both have, and how far
+ * the two histograms of a window are apart (the two-sample question of Landan 2012, Landau 2014 and Guo 2017: tumour
+ * against normal).  The reference has no such report.  a and b are batches of one engine (else EPI_ERR_ARG); a == b is
+ * allowed.  ctx, k (2 .. 6), max_ooctx_meth_frac, calls and kept rows: exactly as for epi_batch_heterogeneity_report_dev.
+ *  Common sites  the rows of a's un-thresholded CX report (upper-case letters of ctx, pass all TRUE) for which b's
+ *            un-thresholded CX report has a row with the same rname, strand, pos AND context code: a position whose
+ *            majority context differs between the two is not common.  rname codes are compared as integers (both
+ *            batches under one sequence dictionary).  Per (rname, strand) they are ordered by pos; window j is common
+ *            sites j .. j+k-1 of one (rname, strand).  A site of one batch that is not common is ignored by both: it is
+ *            neither a gap nor a call, windows span over it.
+ *  Counts    counts_a[window][p] from a's kept rows, counts_b[window][p] from b's: the heterogeneity report's rule and bit
+ *            order, on the common table.  u32 counters; each of the two arrays is ncommon * 2^k * 4 bytes, above 4 GiB:
+ *            EPI_ERR_ARG before any counter is allocated (epi_heterogeneity_counter_bytes).
+ *  Rows      a window is reported when n_a >= max(min_reads, 1) and n_b >= max(min_reads, 1) and (max_window_span == 0 or
+ *            last - first + 1 <= max_window_span, over the common sites), in the order of a's CX rows the windows start on.
+ *  Columns   ten int32: rname, strand, pos, end, context of the first site, nreads_a, nreads_b, npatterns_a,
+ *            npatterns_b, df = the bins that are nonzero in counts_a + counts_b, minus 1.  Thirteen double: beta_a, beta_b,
+ *            entropy_a, entropy_b, epipolymorphism_a, epipolymorphism_b, pdr_a, pdr_b (the heterogeneity report's
+ *            formulas, per batch); delta_beta = beta_b - beta_a; delta_entropy = entropy_b - entropy_a; and with
+ *            p_i = counts_a[i] / n_a, q_i = counts_b[i] / n_b, m_i = (p_i + q_i) / 2, bins ascending:
+ *            jsd = sum_i [p_i > 0: p_i log2(p_i / m_i) / 2] + [q_i > 0: q_i log2(q_i / m_i) / 2], clamped to [0, 1] (the
+ *            Jensen-Shannon divergence in bits); tvd = sum_i |p_i - q_i| / 2; g = 2 sum O ln(O / E) over the nonzero
+ *            cells of the 2 x 2^k table, E = (batch total * bin total) / (n_a + n_b), a's bins first, then b's, each
+ *            ascending (the likelihood-ratio statistic; with df what a chi-square routine needs -- a p-value is not
+ *            computed).  float64, summed by one thread in the stated order: no launch shape enters a result.
+ * compare_dev runs both batches' CX reports and the comparison (synchronises `stream`); *ncommon_out = the common sites,
+ * *nrow_out = the reported windows.  Fewer than k common sites: an empty report.  compare_fetch_dev writes the columns
+ * and, unless NULL, d_counts_a / d_counts_b [nrow][2^k] int32.  State: the comparison lives on a alone.  Only
+ * compare_fetch_dev may follow on a: any other fetch on a after the comparison, or compare_fetch_dev after any other
+ * report on a, is EPI_ERR_STATE.  b is left without a report (any fetch on b: EPI_ERR_STATE) and holds nothing of the
+ * comparison, so a later report on b does not disturb the fetch.  Both batches keep their direct-mode record exactly as
+ * epi_batch_cx_report_dev(., NULL, the upper-case letters of ctx) leaves it.  Single GPU only: a batch with shared tiles
+ * attached, on either side, is EPI_ERR_STATE. */
+int epi_batch_heterogeneity_compare_dev(epi_batch *a, epi_batch *b, const char *ctx, int k, double max_ooctx_meth_frac,
+                                        int32_t min_reads, int32_t max_window_span, void *stream, int64_t *ncommon_out,
+                                        int64_t *nrow_out);
+int epi_batch_heterogeneity_compare_fetch_dev(epi_batch *a, int32_t *const d_icols[10], double *const d_dcols[13],
+                                              int32_t *d_counts_a, int32_t *d_counts_b /* either may be NULL */, void *stream);
+
 /* Linkage report: the co-methylation of pairs of neighbouring sites over the reads that cover both, and the methylation
  * haplotype blocks that follow from it (Guo et al. 2017, the paper lMHL comes from).  The reference has no such report.
  *  ctx       context letters in both cases ("Zz", "XxZz", ...); D = max_neighbours, 1 .. 16.
