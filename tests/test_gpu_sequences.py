@@ -9,8 +9,20 @@ and fits, and every tile of the absolute grid yields as many rows as then.  The 
 operations of their own, each checked as in test_gpu_fuzz_reports.py: the heterogeneity report (whose own CX report keeps
 or replaces the direct-mode record: Slot.het, with the capacity the library reports afterwards and the `written` of the
 next C-level CX call against it), base frequencies, and the multi-target pattern tables and summaries, which keep
-scratch groups and hash tables on the batch.  Bounded by a list of seeds; a failure names its seed and step."""
+scratch groups and hash tables on the batch.  The linkage report and the heterogeneity comparison share the het_* buffers
+of the batch with the heterogeneity report, at other sizes, and their own CX reports treat the record as its own does
+(Slot.het again).  `link` remembers its restated pair table on the slot as the batch's live linkage report until an
+operation on the slot ends it: any CX, lMHL, heterogeneity or linkage report, either side of a comparison, or a reopen;
+thresholding, beta, base frequencies and the pattern calls leave it alone (linkage.hip and include/epihip.h: blocks_dev
+needs the last report on the batch to be a linkage report).  `blocks_late` asks for the blocks through the C entry points
+with fresh thresholds, twice where the report is live: the blocks of the remembered table, however many operations on
+other batches lie between, and the pair table still that one; or a call sequence error.  `cmp` compares two slots, mostly
+the first batch and its sibling (the last slot), in a drawn order: the record of both slots is modelled, the second
+batch first as the library runs them, and whatever comes next on either slot is checked as always, so a site table or a
+counter that the comparison left on the wrong batch shows there.  Bounded by a list of seeds; a failure names its seed
+and step."""
 import collections
+import ctypes as C
 
 import numpy as np
 import pytest
@@ -21,19 +33,20 @@ import test_extract_patterns as TP
 import test_gpu_cx_direct as D
 import test_gpu_fuzz as F
 import test_gpu_fuzz_reports as R
+import test_gpu_linkage as LK
 from oracle import oracle as orc
 
 pytestmark = pytest.mark.gpu
 
-SEEDS = list(range(5000, 5060))
-GROUPS = 6
+SEEDS = list(range(5000, 5080))
+GROUPS = 16
 CX_LETTERS = ("Z", "ZZ", "Zz", "X", "ZX", "ZXH", "H")
 NAMED = ("CG", "CHG", "CHH", "CxG", "CX")
 MHL_CTX = ("Zz", "Xx", "Hh", "ZzXx", "ZzXxHh")
 PASSES = ("none", "oracle", "random", "false", "na")
 MAKERS = ("arrays", "pinned", "device", "zero_copy")
-OPS = (("cx_c", 8), ("cx_py", 2), ("fused_py", 2), ("gcr", 1), ("mhl", 2), ("thr", 1), ("beta", 1), ("pat", 1), ("reopen", 1),
-       ("het", 2), ("freqs", 1), ("pat_multi", 1), ("summ", 1))
+OPS = (("cx_c", 10), ("cx_py", 2), ("fused_py", 2), ("gcr", 1), ("mhl", 2), ("thr", 1), ("beta", 1), ("pat", 1), ("reopen", 1),
+       ("het", 2), ("freqs", 1), ("pat_multi", 1), ("summ", 1), ("link", 2), ("blocks_late", 2), ("cmp", 2))
 NA = -2 ** 31
 # Paths over the whole seed list: C-level CX calls (`written` asserted) and Python-level ones (py_: tables only).  pool:
 # no record with these contexts yet; fallback: a direct launch in which some tile's count differed, the new row count
@@ -41,8 +54,18 @@ NA = -2 ** 31
 # het_replaces / het_keeps: a heterogeneity report whose own CX report replaced the record / met one with its contexts and
 # left it alone; direct_after_het: a C-level direct launch on a record that a heterogeneity report was the last to touch
 # (kept or made; repeated launches count); direct_after_het_replaces: such a launch on a record that the report MADE.
+# link_replaces / link_keeps: the same for the CX report under a linkage report; direct_after_link: a C-level direct launch on
+# a record that a linkage report was the last to touch.  blocks_late_live: blocks computed, perhaps many operations on other
+# batches later, from the counters of a linkage report that no operation on its batch has ended; blocks_late_refused: asked
+# for on a batch whose last report is no linkage report (a call sequence error).  cmp_pair: a comparison of the first batch
+# with its sibling, either order; cmp_self: of a batch with itself (its second CX report meets the record that the first one
+# made); cmp_b_replaces: the CX report on the SECOND batch of a comparison replaced that batch's record;
+# direct_after_cmp_on_b: a C-level direct launch on a record that a comparison, with the batch as its second, was the last
+# to touch.
 MIN_PATHS = {"pool": 150, "direct": 100, "fallback_above": 8, "fallback_below": 8, "py_direct": 40, "py_fallback_above": 5,
-             "het_replaces": 5, "het_keeps": 5, "direct_after_het": 5, "direct_after_het_replaces": 5}
+             "het_replaces": 5, "het_keeps": 5, "direct_after_het": 5, "direct_after_het_replaces": 5,
+             "link_replaces": 5, "link_keeps": 5, "direct_after_link": 5, "blocks_late_live": 5, "blocks_late_refused": 5,
+             "cmp_pair": 5, "cmp_self": 5, "cmp_b_replaces": 5, "direct_after_cmp_on_b": 5}
 RAN = {}                                               # group -> its path counts (this session)
 
 
@@ -84,8 +107,10 @@ class Slot:
         t = self.t
         self.maker = maker
         self.rec = None                                # (context mask, per-tile counts, row count) of the kept record
-        self.after_het = False                         # a heterogeneity report was the last call to keep or replace it
+        # "het", "link", "cmp_a", "cmp_b": the report whose own CX report was the last call to keep or replace the record
+        self.after = None
         self.het_made = False                          # the record is one that a heterogeneity report made
+        self.link = None                               # (call, restated pair table) of the linkage report the batch holds
         nb = int(t["off"][-1])
         if maker == "arrays":
             self.bam = ea.ProcessedBam.from_arrays(t["xm"], t["off"], t["rname"], t["strand"], t["start"])
@@ -113,22 +138,23 @@ class Slot:
             path = "pool_again"                        # same contexts, but pile-ups or an empty kept table: the record stays
         if self.n > 0 and path in ("pool", "fallback_above", "fallback_below"):
             self.rec = (mask, counts, nrow)
-            self.after_het = self.het_made = False
+            self.after, self.het_made = None, False
         return path, cap
 
-    def het(self, letters, sites, T):
-        """What a heterogeneity report does to the record: its own CX report is a pool report without caller columns, for the
+    def het(self, letters, sites, T, by="het"):
+        """What a heterogeneity report does to the record (a linkage report and either side of a comparison do the same: all
+        go through het_cx_sites; `by` names which): its own CX report is a pool report without caller columns, for the
         upper-case letters of its context, all rows passing (`sites`: that table).  A record with the same contexts stays
         as it is, also one made under another pass vector (cx_keep_offsets); any other is replaced by this table's tile
         counts and row count.  -> the path's name"""
         mask = ctx_mask(letters)
         if self.n == 0:
             return "het_empty"
-        self.after_het = True
+        self.after = by
         if self.rec is not None and self.rec[0] == mask:
             return "het_keeps"
         self.rec = (mask, D.tile_counts(sites, T), int(sites["pos"].size))
-        self.het_made = True
+        self.het_made = by == "het"
         return "het_replaces"
 
 
@@ -136,7 +162,30 @@ def make_slots(ea, rng, seed):
     ts = [F.make_batch(rng, seed * 7 + k)[1] for k in range(int(rng.integers(2, 4)))]
     ts.append(synth_np.random_templates(rng, int(rng.integers(50, 3000)), 0, int(rng.integers(20, 500)), int(rng.integers(1, 4)),
                                         int(rng.integers(200, 20000)), p_garbage=float(rng.choice([0.02, 0.1, 0.3]))))
+    ts.append(R.sibling(rng, ts[0]))                    # the last slot: a second sample of the first batch's library
     return [Slot(ea, t, MAKERS[(seed + k) % len(MAKERS)]) for k, t in enumerate(ts)]
+
+
+def blocks_late(ea, s, bcall):
+    """epi_batch_linkage_blocks_dev on the slot and what it must give: the blocks of the linkage report the batch holds (and
+    the pair table untouched), or a call sequence error from it and from the blocks' fetch -> the path's name"""
+    import torch
+    lib, api = ea._lib.load(), ea.api
+    nb = C.c_int64(-1)
+    rc = lib.epi_batch_linkage_blocks_dev(s.bam.batch(), bcall[0], bcall[1], api._stream(s.bam.device), C.byref(nb))
+    if s.link is None:
+        ic = list(torch.empty((5, 8), dtype=torch.int32, device="cuda:%d" % s.bam.device).unbind(0))
+        dc = list(torch.empty((1, 8), dtype=torch.float64, device="cuda:%d" % s.bam.device).unbind(0))
+        assert rc == ea._lib.EPI_ERR_STATE and nb.value == 0, ("blocks without a linkage report", rc, nb.value)
+        assert lib.epi_batch_linkage_blocks_fetch_dev(s.bam.batch(), api._ptr_array(ic), api._ptr_array(dc), None) == ea._lib.EPI_ERR_STATE
+        return "blocks_late_refused"
+    call, want = s.link
+    wb = R.blocks_want(want, bcall)
+    assert (rc, nb.value) == (ea._lib.EPI_OK, wb["start"].size), ("blocks of the live linkage report", rc, nb.value, wb["start"].size)
+    got = api._fetch_table(s.bam, lib.epi_batch_linkage_blocks_fetch_dev, nb.value, 5, api.BLOCK_COLUMNS, False)
+    LK.assert_table(got, wb, LK.BLOCK_INT_COLS, LK.BLOCK_FLOAT_COLS, ("late blocks",) + tuple(call) + tuple(bcall))
+    LK.assert_same(R.fetch_pairs(ea, s.bam, int(want["pos"].size)), want, ("pairs after late blocks",) + tuple(call))
+    return "blocks_late_live"
 
 
 def pick_pass(rng, s, kind, c4=None, thr=None):
@@ -177,11 +226,15 @@ def run_seed(ea, seed, paths):
     nsteps = int(rng.integers(15, 26))
     try:
         for step in range(nsteps):
-            # the garbage batch (last) 40 % of the time: only its reads change a tile's row count with `pass`
-            k = len(slots) - 1 if rng.random() < 0.4 else int(rng.integers(0, len(slots) - 1))
+            # the garbage batch (last but one) 40 % of the time: only its reads change a tile's row count with `pass`
+            k = len(slots) - 2 if rng.random() < 0.4 else int(rng.choice([q for q in range(len(slots)) if q != len(slots) - 2]))
             s = slots[k]
             t = s.t
             op = str(rng.choice(ops, p=weights))
+            live = [q for q in range(len(slots)) if slots[q].link is not None]
+            if op == "blocks_late" and live and rng.random() < 0.6:   # a batch that holds a linkage report, however long ago
+                k = int(rng.choice(live))
+                s, t = slots[k], slots[k].t
             c4 = H.cls4(str(rng.choice(NAMED)))
             thr = (int(rng.choice(F.MN)), float(rng.choice(F.MB)), float(rng.choice(F.MO)))
             what = (step, op, k, s.maker)
@@ -207,7 +260,8 @@ def run_seed(ea, seed, paths):
                     p = pick_pass(rng, s, pk, c4, thr)
                     want = orc.cx_report(t["xm"], t["off"], t["rname"], t["strand"], t["start"], p, letters)
                     T = lib.epi_cx_tile_positions(letters.encode())
-                    after_het, het_made = s.after_het, s.het_made
+                    after, het_made = s.after, s.het_made
+                    s.link = None
                     path, cap = s.predict(letters, want, T)
                     what += (letters, pk, fused, thr, path)
                     assert D.capacity(ea, s.bam, letters) == cap, ("capacity", cap)
@@ -217,8 +271,10 @@ def run_seed(ea, seed, paths):
                         H.assert_reports_equal(got, want)
                         assert written == (path == "direct"), ("written", written)
                         paths[path] += 1
-                        paths["direct_after_het"] += path == "direct" and after_het
-                        paths["direct_after_het_replaces"] += path == "direct" and het_made
+                        paths["direct_after_het"] += path == "direct" and after == "het"
+                        paths["direct_after_link"] += path == "direct" and after == "link"
+                        paths["direct_after_cmp_on_b"] += path == "direct" and after == "cmp_b"
+                        paths["direct_after_het_replaces"] += path == "direct" and het_made and after == "het"
                     else:
                         H.dirty_allocator(s.bam)
                         if op == "cx_py":
@@ -236,6 +292,7 @@ def run_seed(ea, seed, paths):
                     hmax, hmin = int(rng.choice([0, 0, 1, 3, 50])), int(rng.choice([0, 0, 2, 5]))
                     moo = float(rng.choice([0.1, 0.0, 1.0, float("nan"), -0.5]))
                     what += (hctx, hmax, hmin, moo)
+                    s.link = None
                     H.assert_reports_equal(cpu(ea.rcpp_mhl_report(s.bam, hctx, hmax, hmin, moo, as_device=bool(rng.random() < 0.3))),
                                            orc.mhl_report(t["xm"], t["off"], t["rname"], t["strand"], t["start"], hctx, hmax, hmin, moo),
                                            float_cols=("length", "lmhl"))
@@ -281,6 +338,7 @@ def run_seed(ea, seed, paths):
                         continue
                     hp = s.het(letters, want["sites"], lib.epi_cx_tile_positions(letters.encode()))
                     what += (hp,)
+                    s.link = None
                     R.check_het(ea, s.bam, t, call, want)
                     assert D.capacity(ea, s.bam, letters) == (s.rec[2] if s.n else -1), ("capacity after het", s.rec and s.rec[2])
                     paths[hp] += 1
@@ -295,6 +353,65 @@ def run_seed(ea, seed, paths):
                     p = R.draw_patterns(rng, t)
                     what += tuple(p[q] for q in ("targets", "mo", "ctx", "freq", "clip", "ro", "hl", "bin"))
                     (R.check_multi if op == "pat_multi" else R.check_summ)(ea, s.bam, t, p)
+                elif op == "link":
+                    name = named_of(last[k][0]) if k in last and rng.random() < 0.6 else None    # the CX ops' coin, as for het
+                    call, _ = R.draw_link(rng, t, ctx=name)
+                    letters = H.CONTEXT_TO_BASES[call[0]]["ctx_meth"]
+                    what += call
+                    want = R.link_want(t, call)
+                    if want is None:
+                        paths["link_skipped"] += 1
+                        continue
+                    lp = s.het(letters, want["sites"], lib.epi_cx_tile_positions(letters.encode()), by="link").replace("het_", "link_")
+                    what += (lp,)
+                    s.link = None
+                    R.check_link(ea, s.bam, t, call, want)
+                    assert D.capacity(ea, s.bam, letters) == (s.rec[2] if s.n else -1), ("capacity after link", s.rec and s.rec[2])
+                    s.link = (call, want)
+                    paths[lp] += 1
+                    last[k] = (letters, "none", H.cls4(call[0]), thr)
+                elif op == "blocks_late":
+                    # twice with fresh thresholds where the report is live: the second call finds the first one's block lengths
+                    for _ in range(1 if s.link is None else 2):
+                        bcall = (float(rng.choice(R.MIN_R2)), int(rng.choice(R.MIN_SITES)))
+                        what += bcall
+                        bp = blocks_late(ea, s, bcall)
+                    paths[bp] += 1
+                elif op == "cmp":
+                    sib = len(slots) - 1
+                    if rng.random() < 0.7:                 # the first batch and its sibling
+                        ka, kb = 0, sib
+                    elif rng.random() < 1 / 3:             # the slot itself
+                        ka, kb = k, k
+                    else:                                  # any other slot: usually no common site
+                        ka, kb = k, int(rng.choice([q for q in range(len(slots)) if q != k]))
+                    if rng.random() < 0.5:
+                        ka, kb = kb, ka
+                    sa, sb = slots[ka], slots[kb]
+                    name = named_of(last[ka][0]) if ka in last and rng.random() < 0.6 else None
+                    call = R.draw_het(rng, sa.t, ctx=name)
+                    letters = H.CONTEXT_TO_BASES[call[0]]["ctx_meth"]
+                    what += (ka, kb, sb.maker) + call
+                    want = R.cmp_want(sa.t, sb.t, call)
+                    if want is None:
+                        paths["cmp_skipped"] += 1
+                        continue
+                    # the library runs the second batch's CX report first; with one slot on both sides its second report meets
+                    # the record that the first one made
+                    T = lib.epi_cx_tile_positions(letters.encode())
+                    pb = sb.het(letters, want["sites_b"], T, by="cmp_b")
+                    pa = sa.het(letters, want["sites_a"], T, by="cmp_a")
+                    what += (pb, pa)
+                    assert ka != kb or pa == "het_keeps"
+                    sa.link = sb.link = None
+                    R.check_cmp(ea, sa.bam, sb.bam, sa.t, sb.t, call, want)
+                    for q in (sa, sb):
+                        assert D.capacity(ea, q.bam, letters) == (q.rec[2] if q.n else -1), ("capacity after cmp", q.maker, q.rec and q.rec[2])
+                    paths["cmp_pair"] += {ka, kb} == {0, sib}
+                    paths["cmp_self"] += ka == kb
+                    paths["cmp_b_replaces"] += pb == "het_replaces"
+                    paths["cmp"] += 1
+                    last[ka] = last[kb] = (letters, "none", H.cls4(call[0]), thr)
                 else:                                      # reopen: a fresh batch of the same rows, maybe another constructor
                     s.bam.close()
                     last.pop(k, None)
