@@ -525,6 +525,132 @@ def rcpp_linkage_blocks(df, ctx, max_neighbours, max_distance, max_ooctx_meth_fr
     return _fetch_table(bam, lib.epi_batch_linkage_blocks_fetch_dev, nblock.value, 5, BLOCK_COLUMNS, as_device)
 
 
+CX_COLUMNS = ("rname", "strand", "pos", "context", "meth", "unmeth")
+CX_COMPARE_COLUMNS = ("rname", "strand", "pos", "context", "meth_a", "unmeth_a", "meth_b", "unmeth_b", "beta_a", "beta_b", "delta_beta", "p")
+DMR_COLUMNS = ("rname", "start", "end", "nsites", "direction", "beta_a", "beta_b", "delta_beta", "mean_delta_beta", "p")
+
+
+def _device_columns(rep, names, what):
+    """The named columns of a device Report (int32 ones first, then float64 ones): contiguous tensors, all on one GPU."""
+    torch = _torch()
+    cols = []
+    for i, k in enumerate(names):
+        if k not in rep or not isinstance(rep[k], torch.Tensor) or not rep[k].is_cuda:
+            raise TypeError("%s: expected a device Report (as_device=True) with the column '%s'" % (what, k))
+        cols.append(rep[k].contiguous())
+        if cols[i].dtype not in (torch.int32, torch.float64) or cols[i].shape != cols[0].shape or cols[i].device != cols[0].device:
+            raise TypeError("%s: column '%s' does not fit the table (int32 / float64 columns of one length on one device)" % (what, k))
+    return cols
+
+
+def _table_to_host(rep, as_device):
+    if as_device:
+        return rep
+    out = Report({k: v.cpu().numpy() for k, v in rep.items()}, rep.levels["rname"])
+    out.__dict__.update({k: v for k, v in rep.__dict__.items() if k != "levels"})
+    return out
+
+
+def rcpp_cx_compare(rep_a, rep_b, min_coverage=1, as_device=False):
+    """Two device cytosine reports (rcpp_cx_report / generateCytosineReport with as_device=True) against each other per
+    cytosine both have (include/epihip.h, epi_cx_compare_dev): rname, strand, pos, context, meth_a, unmeth_a, meth_b,
+    unmeth_b (int32), beta_a, beta_b, delta_beta = beta_b - beta_a and the two-sided Fisher exact p of (meth_a unmeth_a /
+    meth_b unmeth_b) (float64), for the common sites covered min_coverage times in either.  Both reports under one
+    sequence dictionary (differing `levels`: ValueError), on one device, rows ascending in (rname, pos, strand).  The
+    Report carries rep_a's levels and `ncommon`, the number of common sites."""
+    min_coverage = _whole_number(min_coverage, "min.coverage", 0, 2 ** 31 - 1)
+    if rep_a.levels["rname"] != rep_b.levels["rname"]:
+        raise ValueError("the two reports have different sequence names (levels): their rname codes cannot be compared")
+    torch = _torch()
+    lib = _lib.load()
+    a, b = _device_columns(rep_a, CX_COLUMNS, "rcpp_cx_compare"), _device_columns(rep_b, CX_COLUMNS, "rcpp_cx_compare")
+    if a[0].device != b[0].device:
+        raise ValueError("the two reports are on different devices (%s and %s)" % (a[0].device, b[0].device))
+    dev = a[0].device
+    na, nb = int(a[0].numel()), int(b[0].numel())
+    cap = min(na, nb)
+    icols = list(torch.empty((8, cap), dtype=torch.int32, device=dev).unbind(0))
+    dcols = list(torch.empty((4, cap), dtype=torch.float64, device=dev).unbind(0))
+    ncommon, nrow = C.c_int64(0), C.c_int64(0)
+    _lib.check(lib.epi_cx_compare_dev(_engine(dev.index), _ptr_array(a), na, _ptr_array(b), nb, min_coverage, _ptr_array(icols),
+                                      _ptr_array(dcols), cap, _stream(dev.index), C.byref(ncommon), C.byref(nrow)))
+    rep = Report(dict(zip(CX_COMPARE_COLUMNS, [c[:nrow.value] for c in icols + dcols])), rep_a.levels["rname"])
+    rep.ncommon = ncommon.value
+    return _table_to_host(rep, as_device)
+
+
+def _region_args(max_p, min_delta_beta, max_gap, min_sites):
+    for value, name in ((max_p, "max.p"), (min_delta_beta, "min.delta.beta")):
+        if isinstance(value, bool) or not 0 <= value <= 1:
+            raise ValueError("'%s' should be a number from 0 to 1" % name)
+    return float(max_p), float(min_delta_beta), _whole_number(max_gap, "max.gap", 0, 2 ** 31 - 1), _whole_number(min_sites, "min.sites", 1, 2 ** 31 - 1)
+
+
+def rcpp_cx_compare_regions(rep, max_p=0.05, min_delta_beta=0.1, max_gap=500, min_sites=3, as_device=False):
+    """The differentially methylated regions of a device comparison table (rcpp_cx_compare with as_device=True;
+    include/epihip.h, epi_cx_compare_regions_dev): maximal runs of at least min_sites consecutive rows with p <= max_p and
+    |delta_beta| >= min_delta_beta, of one direction and sequence, neighbours at most max_gap apart.  rname, start, end,
+    nsites, direction (int32), the pooled beta_a, beta_b and delta_beta, mean_delta_beta and the Fisher p of the pooled
+    table (float64)."""
+    max_p, min_delta_beta, max_gap, min_sites = _region_args(max_p, min_delta_beta, max_gap, min_sites)
+    torch = _torch()
+    lib = _lib.load()
+    cols = _device_columns(rep, CX_COMPARE_COLUMNS, "rcpp_cx_compare_regions")
+    dev = cols[0].device
+    n = int(cols[0].numel())
+    cap = n // min_sites                                   # (runs do not overlap)
+    icols = list(torch.empty((5, cap), dtype=torch.int32, device=dev).unbind(0))
+    dcols = list(torch.empty((5, cap), dtype=torch.float64, device=dev).unbind(0))
+    nregion = C.c_int64(0)
+    _lib.check(lib.epi_cx_compare_regions_dev(_engine(dev.index), _ptr_array(cols[:8]), _ptr_array(cols[8:]), n, max_p, min_delta_beta,
+                                              max_gap, min_sites, _ptr_array(icols), _ptr_array(dcols), cap, _stream(dev.index),
+                                              C.byref(nregion)))
+    out = Report(dict(zip(DMR_COLUMNS, [c[:nregion.value] for c in icols + dcols])), rep.levels["rname"])
+    return _table_to_host(out, as_device)
+
+
+def _fisher_cells(x, name):
+    """One cell of the tables as int32: a device tensor stays on its device; NaN in a float array-like is NA."""
+    torch = _torch()
+    if isinstance(x, torch.Tensor):
+        if x.dtype.is_floating_point or x.dtype.is_complex:
+            raise ValueError("'%s' should hold integers" % name)
+        return x.reshape(-1)
+    v = np.asarray(x).reshape(-1)
+    if v.dtype.kind == "f":
+        nan = np.isnan(v)
+        w = np.where(nan, 0.0, v)
+        if np.any(w != np.floor(w)):
+            raise ValueError("'%s' should hold integers" % name)
+        v = np.where(nan, float(NA_INTEGER), w)
+    elif v.dtype.kind not in "iub":
+        raise ValueError("'%s' should hold integers" % name)
+    if v.size and (v.min() < NA_INTEGER or v.max() > 2 ** 31 - 1):
+        raise ValueError("'%s' should hold 32-bit integers" % name)
+    return np.ascontiguousarray(v.astype(np.int32))
+
+
+def fisherExact(a, b, c, d, as_device=False):
+    """Two-sided Fisher exact p-values of the 2x2 tables (a[i] b[i] / c[i] d[i]) on the GPU (epi_fisher_exact_dev): the
+    definition of rcpp_fep, one thread per table.  a, b, c, d: array-likes or device tensors of integers, one length; a
+    negative cell (NA) gives NaN.  Returns float64, a device tensor with as_device."""
+    cells = [_fisher_cells(x, k) for x, k in zip((a, b, c, d), "abcd")]
+    n = int(cells[0].shape[0])
+    if any(int(x.shape[0]) != n for x in cells):
+        raise ValueError("'a', 'b', 'c' and 'd' should have one length")
+    torch = _torch()
+    lib = _lib.load()
+    on_dev = [x.device for x in cells if isinstance(x, torch.Tensor) and x.is_cuda]
+    index = on_dev[0].index if on_dev else None
+    eng = _engine(index)
+    index = lib.epi_engine_device(eng)
+    dev = "cuda:%d" % index
+    cells = [(x if isinstance(x, torch.Tensor) else torch.from_numpy(x)).to(device=dev, dtype=torch.int32).contiguous() for x in cells]
+    p = torch.empty(n, dtype=torch.float64, device=dev)
+    _lib.check(lib.epi_fisher_exact_dev(eng, *[C.c_void_p(x.data_ptr()) for x in cells], n, C.c_void_p(p.data_ptr()), _stream(index)))
+    return p if as_device else p.cpu().numpy()
+
+
 PATTERN_LEVELS = ("NA1", "H", "A", "C", "NA5", "X", "Z", "NA8", "NA9", "h", "G", "T", "N", "x", "z", "NA16")   # :192-195
 NA_INTEGER = -2 ** 31
 
@@ -782,6 +908,63 @@ def generateHaplotypeBlocks(bam, report_file=None, linkage_context=None, max_nei
                               min_reads, min_r2, min_sites, as_device=as_device)
     if report_file is None:
         return rep
+    writeReport(rep, report_file, gzip)
+    return None
+
+
+def _cytosine_comparison(bam_a, bam_b, threshold_reads, threshold_context, min_context_sites, min_context_beta, max_outofcontext_beta,
+                         report_context, min_coverage, preprocess_args):
+    """The device comparison table of compareCytosineReports; every argument is checked before a file is opened."""
+    threshold_context = _match_arg(threshold_context, _CTX_CHOICES, "threshold.context")
+    report_context = threshold_context if report_context is None else _match_arg(report_context, _CTX_CHOICES, "report.context")
+    min_coverage = _whole_number(min_coverage, "min.coverage", 0, 2 ** 31 - 1)
+    bam_a = preprocessBam(bam_a, **preprocess_args)
+    bam_b = preprocessBam(bam_b, **preprocess_args)
+    if bam_a.levels != bam_b.levels:
+        raise ValueError("the two inputs have different sequence names (levels): their rname codes cannot be compared")
+    bam_a.batch()
+    bam_b.batch(bam_a.device)
+    if bam_b.device != bam_a.device:
+        raise ValueError("the two inputs are on different devices (%s and %s)" % (bam_a.device, bam_b.device))
+    reps = [generateCytosineReport(bam, None, threshold_reads, threshold_context, min_context_sites, min_context_beta,
+                                   max_outofcontext_beta, report_context, as_device=True) for bam in (bam_a, bam_b)]
+    return rcpp_cx_compare(reps[0], reps[1], min_coverage, as_device=True)
+
+
+def compareCytosineReports(bam_a, bam_b, report_file=None, threshold_reads=True, threshold_context=None, min_context_sites=2,
+                           min_context_beta=0.5, max_outofcontext_beta=0.1, report_context=None, min_coverage=1, gzip=False,
+                           verbose=False, as_device=False, **preprocess_args):
+    """Two samples against each other per cytosine: the tables generateCytosineReport gives for either input with these
+    arguments, joined on the device over the cytosines both have (same position, strand and context) and that are covered
+    at least min_coverage times in either.  Columns: rname, strand, pos, context, meth_a, unmeth_a, meth_b, unmeth_b,
+    beta_a, beta_b, delta_beta (b minus a) and p, the two-sided Fisher exact p-value of (meth_a unmeth_a / meth_b unmeth_b);
+    no p-value is adjusted for the number of tests.  Both inputs go through preprocessBam with the same preprocess_args
+    and must have the same sequence names.  The Report's `ncommon` is the number of common cytosines.  The reference has
+    no such report."""
+    rep = _cytosine_comparison(bam_a, bam_b, threshold_reads, threshold_context, min_context_sites, min_context_beta,
+                               max_outofcontext_beta, report_context, min_coverage, preprocess_args)
+    if report_file is None:
+        return _table_to_host(rep, as_device)
+    writeReport(rep, report_file, gzip)
+    return None
+
+
+def generateDmrReport(bam_a, bam_b, report_file=None, threshold_reads=True, threshold_context=None, min_context_sites=2,
+                      min_context_beta=0.5, max_outofcontext_beta=0.1, report_context=None, min_coverage=1, gzip=False,
+                      verbose=False, as_device=False, max_p=0.05, min_delta_beta=0.1, max_gap=500, min_sites=3, **preprocess_args):
+    """Differentially methylated regions between two samples: the comparison of compareCytosineReports with the same
+    arguments, and of its rows the maximal runs of at least `min_sites` consecutive cytosines (both strands, in table
+    order) with p <= max_p and |delta_beta| >= min_delta_beta that change in one direction, lie on one sequence and whose
+    neighbours are at most `max_gap` bases apart.  Columns: rname, start, end, nsites, direction (+1: b above a, -1),
+    beta_a, beta_b and delta_beta of the region's pooled counts, mean_delta_beta of its cytosines and p, the Fisher exact
+    p-value of the pooled table.  The Report's `ncommon` is the number of common cytosines."""
+    args = _region_args(max_p, min_delta_beta, max_gap, min_sites)
+    cmp_ = _cytosine_comparison(bam_a, bam_b, threshold_reads, threshold_context, min_context_sites, min_context_beta,
+                                max_outofcontext_beta, report_context, min_coverage, preprocess_args)
+    rep = rcpp_cx_compare_regions(cmp_, *args, as_device=True)
+    rep.ncommon = cmp_.ncommon
+    if report_file is None:
+        return _table_to_host(rep, as_device)
     writeReport(rep, report_file, gzip)
     return None
 

@@ -552,6 +552,55 @@ int epi_batch_linkage_blocks_dev(epi_batch *b, double min_r2, int32_t min_sites,
 int epi_batch_linkage_blocks_fetch_dev(epi_batch *b, int32_t *const d_icols[5], double *const d_dcols[1], void *stream);
 int epi_linkage_counter_bytes(int64_t nsites, int max_neighbours, int64_t *bytes_out);
 
+/* epi_fisher_exact on the device: d_p[i] = the two-sided Fisher exact p-value of the table (d_a[i] d_b[i] / d_c[i] d_d[i]),
+ * by the definition and the arithmetic of epi_fisher_exact (csrc/fisher_math.hpp is compiled into both): P(k) in Loader's
+ * saddle-point form, a table as extreme when P(k) <= P(a) (1 + 1e-7), the tails found by bisection and summed outwards by
+ * the ratio recurrence until a term no longer changes the sum, the result clamped at 1; a negative cell (NA included): NaN;
+ * degenerate margins (one table only): exactly 1.0.  One thread per table performs the host's operations in the host's
+ * order, so no launch shape enters a result; against the host the results differ by what the device's lgamma / log / exp
+ * differ from the host's (a few ulp, scaled by the size of the exponent).  All pointers are device memory of e's device;
+ * the kernel is queued on `stream`, nothing is synchronised.  n == 0: nothing is done. */
+int epi_fisher_exact_dev(epi_engine *e, const int32_t *d_a, const int32_t *d_b, const int32_t *d_c, const int32_t *d_d,
+                         int64_t n, double *d_p, void *stream);
+
+/* Cytosine report comparison: two CX tables against each other per cytosine (tumour against normal), and the regions over
+ * which they differ.  The reference has no such report.  Both calls are stateless: they read device columns of the caller,
+ * write device columns of the caller, hold their scratch for the length of the call and touch no batch and no batch's
+ * report state.  Both synchronise `stream`.
+ *  Inputs    d_a (na rows), d_b (nb rows): CX tables as epi_batch_cx_fetch_dev writes them (rname, strand, pos, context,
+ *            meth, unmeth), thresholded or not, of any batches of e's device.  rname codes are compared as integers (both
+ *            tables under one sequence dictionary).  Precondition, checked on the device: the rows of each table strictly
+ *            ascend in (rname, pos, strand) -- the CX row order whenever the batch's rname codes ascend.  Otherwise
+ *            EPI_ERR_ARG, and nothing is written.
+ *  Common    a row of a is common when b has a row with the same rname, strand, pos AND context code (the rule of
+ *            epi_batch_heterogeneity_compare_dev: a position whose majority context differs is not common).
+ *            *ncommon_out = their number.
+ *  Rows      a common site is reported when meth_a + unmeth_a >= max(min_coverage, 1) and meth_b + unmeth_b >=
+ *            max(min_coverage, 1), in a's row order.  *nrow_out = their number.
+ *  Columns   eight int32: rname, strand, pos, context, meth_a, unmeth_a, meth_b, unmeth_b.  Four double: beta_a = meth_a /
+ *            (meth_a + unmeth_a), beta_b likewise (one IEEE division of integers each), delta_beta = beta_b - beta_a, p = the
+ *            two-sided Fisher p-value of (meth_a unmeth_a / meth_b unmeth_b) as epi_fisher_exact_dev computes it.
+ *  Capacity  the columns hold `cap` rows.  cap < *nrow_out: EPI_ERR_ARG, nothing is written, *nrow_out is the count
+ *            needed.  cap >= min(na, nb) always suffices.  na == 0 or nb == 0: an empty report.
+ *  Regions   (epi_cx_compare_regions_dev, on the n rows of such a table; max_p and min_delta_beta in [0, 1], max_gap >= 0,
+ *            min_sites >= 1, else EPI_ERR_ARG)  row i is significant when p[i] <= max_p and |delta_beta[i]| >= min_delta_beta
+ *            and delta_beta[i] != 0; NaN is never significant; its direction is the sign of delta_beta.  A region is a
+ *            maximal run of consecutive table rows, both strands in table order, that are all significant, of one direction
+ *            and one rname, with pos[i + 1] - pos[i] <= max_gap between neighbours; a row that is not significant ends the
+ *            run.  Runs of at least min_sites rows are reported, in table order.  Five int32: rname, start = pos of the
+ *            first row, end = pos of the last, nsites, direction (+1: b above a, -1).  Five double: beta_a and beta_b pooled
+ *            as sum(meth) / sum(meth + unmeth) with 64-bit integer sums, delta_beta = pooled b - a, mean_delta_beta = the
+ *            mean of the rows' delta_beta, summed in ascending row order by one thread, p = the Fisher test of the pooled
+ *            table (64-bit cells).  Capacity as above (*nregion_out: the count needed).  No p-value is adjusted for the
+ *            number of tests. */
+int epi_cx_compare_dev(epi_engine *e, const int32_t *const d_a[6], int64_t na, const int32_t *const d_b[6], int64_t nb,
+                       int32_t min_coverage, int32_t *const d_icols[8], double *const d_dcols[4], int64_t cap,
+                       void *stream, int64_t *ncommon_out, int64_t *nrow_out);
+int epi_cx_compare_regions_dev(epi_engine *e, const int32_t *const d_icols[8], const double *const d_dcols[4], int64_t n,
+                               double max_p, double min_delta_beta, int32_t max_gap, int32_t min_sites,
+                               int32_t *const d_ricols[5], double *const d_rdcols[5], int64_t cap, void *stream,
+                               int64_t *nregion_out);
+
 /* rcpp_extract_patterns (src/rcpp_extract_patterns.cpp:26-211; caller .getPatterns, R/internal.R:683-714):
  * methylation patterns of the reads overlapping one target.  Library-owned host table: per pattern strand, start,
  * end, nbase, beta, the FNV-1a hash the R side prints as 16 hex digits ("pattern"), the ordered column positions
