@@ -25,6 +25,7 @@ CONTEXT_TO_BASES = {
 }
 STRAND_LEVELS = ("+", "-")                                            # src/rcpp_read_bam.cpp:175
 CONTEXT_LEVELS = ("NA1", "CHH", "NA3", "NA4", "NA5", "CHG", "CG")     # src/rcpp_cx_report.cpp:150-152
+CX_COLUMNS = ("rname", "strand", "pos", "context", "meth", "unmeth")
 
 _engines = {}
 
@@ -345,10 +346,9 @@ def rcpp_cx_report(df, pass_, ctx, as_device=False):
     cols = _cx_columns(bam, ctx, lambda cols, cap, nrow, written: _lib.check(lib.epi_batch_cx_report_into_dev(
         b, C.c_void_p(p.data_ptr()) if p is not None and bam.n else None, _lib.enc(ctx), cols, cap, _stream(bam.device),
         C.byref(nrow), C.byref(written))))
-    names = ("rname", "strand", "pos", "context", "meth", "unmeth")
     if not as_device:
         cols = [c.cpu().numpy() for c in cols]
-    return Report(dict(zip(names, cols)), bam.levels)
+    return Report(dict(zip(CX_COLUMNS, cols)), bam.levels)
 
 
 def cytosine_report_fused(df, ctx_meth, ctx_unmeth, ooctx_meth, ooctx_unmeth, min_n_ctx, min_ctx_meth_frac,
@@ -367,36 +367,50 @@ def cytosine_report_fused(df, ctx_meth, ctx_unmeth, ooctx_meth, ooctx_unmeth, mi
         float(min_ctx_meth_frac), float(max_ooctx_meth_frac), _lib.enc(ctx),
         C.c_void_p(pass_out.data_ptr()) if pass_out is not None else None, cols, cap, _stream(bam.device),
         C.byref(nrow), C.byref(written))))
-    names = ("rname", "strand", "pos", "context", "meth", "unmeth")
     if not as_device:
         cols = [c.cpu().numpy() for c in cols]
-    rep = Report(dict(zip(names, cols)), bam.levels)
+    rep = Report(dict(zip(CX_COLUMNS, cols)), bam.levels)
     if return_pass:
         p = pass_out[:bam.n]
         return rep, (p if as_device else p.cpu().numpy().astype(bool))
     return rep
 
 
-def rcpp_mhl_report(df, ctx, hmax, hmin, max_ooctx_meth_frac, as_device=False):
-    """src/rcpp_mhl_report.cpp:46-228 -> rname,strand,pos,context,coverage (int32), length,lmhl (float64)."""
+def _fetch_table(bam, fetch, n, nint, names, as_device, extra=()):
+    """The columns of a finished report of n rows, nint int32 ones then float64 ones, through the library's `fetch`;
+    `extra`: further device tensors (or None) that it takes between the columns and the stream."""
     torch = _torch()
-    lib = _lib.load()
-    bam = _as_bam(df)
-    b = bam.batch()
     dev = "cuda:%d" % bam.device
-    nrow = C.c_int64(0)
-    _lib.check(lib.epi_batch_mhl_report_dev(b, _lib.enc(ctx), int(hmax), int(hmin), float(max_ooctx_meth_frac),
-                                            _stream(bam.device), C.byref(nrow)))
-    n = nrow.value
-    icols = list(torch.empty((5, n), dtype=torch.int32, device=dev).unbind(0))
-    dcols = list(torch.empty((2, n), dtype=torch.float64, device=dev).unbind(0))
+    icols = list(torch.empty((nint, n), dtype=torch.int32, device=dev).unbind(0))
+    dcols = list(torch.empty((len(names) - nint, n), dtype=torch.float64, device=dev).unbind(0))
     if n:
-        _lib.check(lib.epi_batch_mhl_fetch_dev(b, _ptr_array(icols), _ptr_array(dcols), _stream(bam.device)))
+        _lib.check(fetch(bam.batch(), _ptr_array(icols), _ptr_array(dcols),
+                         *[C.c_void_p(t.data_ptr()) if t is not None else None for t in extra], _stream(bam.device)))
     cols = icols + dcols
     if not as_device:
         cols = [c.cpu().numpy() for c in cols]
-    names = ("rname", "strand", "pos", "context", "coverage", "length", "lmhl")
     return Report(dict(zip(names, cols)), bam.levels)
+
+
+def _pattern_counts(bam, n, k, with_counts, sides=1):
+    """The [n, 2^k] int32 histograms a heterogeneity fetch fills, one per side (None without with_counts)."""
+    torch = _torch()
+    return [torch.empty((n, 1 << int(k)), dtype=torch.int32, device="cuda:%d" % bam.device) if with_counts else None
+            for _ in range(sides)]
+
+
+MHL_COLUMNS = ("rname", "strand", "pos", "context", "coverage", "length", "lmhl")
+HETEROGENEITY_COLUMNS = ("rname", "strand", "pos", "end", "context", "nreads", "npatterns", "beta", "epipolymorphism", "entropy", "pdr")
+
+
+def rcpp_mhl_report(df, ctx, hmax, hmin, max_ooctx_meth_frac, as_device=False):
+    """src/rcpp_mhl_report.cpp:46-228 -> rname,strand,pos,context,coverage (int32), length,lmhl (float64)."""
+    lib = _lib.load()
+    bam = _as_bam(df)
+    nrow = C.c_int64(0)
+    _lib.check(lib.epi_batch_mhl_report_dev(bam.batch(), _lib.enc(ctx), int(hmax), int(hmin), float(max_ooctx_meth_frac),
+                                            _stream(bam.device), C.byref(nrow)))
+    return _fetch_table(bam, lib.epi_batch_mhl_fetch_dev, nrow.value, 5, MHL_COLUMNS, as_device)
 
 
 def rcpp_heterogeneity_report(df, ctx, k, max_ooctx_meth_frac, min_reads=1, max_window_span=0, as_device=False,
@@ -405,36 +419,33 @@ def rcpp_heterogeneity_report(df, ctx, k, max_ooctx_meth_frac, min_reads=1, max_
     epi_batch_heterogeneity_report_dev): rname, strand, pos, end, context, nreads, npatterns (int32), beta, epipolymorphism,
     entropy, pdr (float64).  ctx: context letters in both cases, as for rcpp_mhl_report.  with_counts: the Report's
     `counts` attribute holds the [nrow, 2^k] int32 pattern histogram of the reported windows."""
-    torch = _torch()
     lib = _lib.load()
     bam = _as_bam(df)
-    b = bam.batch()
-    dev = "cuda:%d" % bam.device
     nrow = C.c_int64(0)
-    _lib.check(lib.epi_batch_heterogeneity_report_dev(b, _lib.enc(ctx), int(k), float(max_ooctx_meth_frac), int(min_reads),
+    _lib.check(lib.epi_batch_heterogeneity_report_dev(bam.batch(), _lib.enc(ctx), int(k), float(max_ooctx_meth_frac), int(min_reads),
                                                       int(max_window_span), _stream(bam.device), C.byref(nrow)))
-    n = nrow.value
-    icols = list(torch.empty((7, n), dtype=torch.int32, device=dev).unbind(0))
-    dcols = list(torch.empty((4, n), dtype=torch.float64, device=dev).unbind(0))
-    counts = torch.empty((n, 1 << int(k)), dtype=torch.int32, device=dev) if with_counts else None
-    if n:
-        _lib.check(lib.epi_batch_heterogeneity_fetch_dev(b, _ptr_array(icols), _ptr_array(dcols),
-                                                         C.c_void_p(counts.data_ptr()) if with_counts else None,
-                                                         _stream(bam.device)))
-    cols = icols + dcols
-    if not as_device:
-        cols = [c.cpu().numpy() for c in cols]
-        counts = counts.cpu().numpy() if with_counts else None
-    names = ("rname", "strand", "pos", "end", "context", "nreads", "npatterns", "beta", "epipolymorphism", "entropy", "pdr")
-    rep = Report(dict(zip(names, cols)), bam.levels)
+    counts = _pattern_counts(bam, nrow.value, k, with_counts)
+    rep = _fetch_table(bam, lib.epi_batch_heterogeneity_fetch_dev, nrow.value, 7, HETEROGENEITY_COLUMNS, as_device, counts)
     if with_counts:
-        rep.counts = counts
+        rep.counts, = counts if as_device else [c.cpu().numpy() for c in counts]
     return rep
 
 
 HETEROGENEITY_COMPARE_COLUMNS = ("rname", "strand", "pos", "end", "context", "nreads_a", "nreads_b", "npatterns_a", "npatterns_b", "df",
                                  "beta_a", "beta_b", "entropy_a", "entropy_b", "epipolymorphism_a", "epipolymorphism_b", "pdr_a", "pdr_b",
                                  "delta_beta", "delta_entropy", "jsd", "tvd", "g")
+
+
+def _batch_pair(bam_a, bam_b):
+    """The batches of two inputs that are compared: one sequence dictionary (checked before anything is uploaded), then
+    both on the device of the first."""
+    if bam_a.levels != bam_b.levels:
+        raise ValueError("the two inputs have different sequence names (levels): their rname codes cannot be compared")
+    a = bam_a.batch()
+    b = bam_b.batch(bam_a.device)
+    if bam_b.device != bam_a.device:
+        raise ValueError("the two inputs are on different devices (%s and %s)" % (bam_a.device, bam_b.device))
+    return a, b
 
 
 def rcpp_heterogeneity_compare(df_a, df_b, ctx, k, max_ooctx_meth_frac, min_reads=1, max_window_span=0, as_device=False,
@@ -446,34 +457,16 @@ def rcpp_heterogeneity_compare(df_a, df_b, ctx, k, max_ooctx_meth_frac, min_read
     levels and `ncommon`, the number of common sites; with_counts: `counts_a` and `counts_b` hold the [nrow, 2^k] int32
     pattern histograms of the reported windows."""
     bam_a, bam_b = _as_bam(df_a), _as_bam(df_b)
-    if bam_a.levels != bam_b.levels:
-        raise ValueError("the two inputs have different sequence names (levels): their rname codes cannot be compared")
-    torch = _torch()
-    lib = _lib.load()
-    a = bam_a.batch()
-    b = bam_b.batch(bam_a.device)
-    if bam_b.device != bam_a.device:
-        raise ValueError("the two inputs are on different devices (%s and %s)" % (bam_a.device, bam_b.device))
-    dev = "cuda:%d" % bam_a.device
+    a, b = _batch_pair(bam_a, bam_b)
     ncommon, nrow = C.c_int64(0), C.c_int64(0)
+    lib = _lib.load()
     _lib.check(lib.epi_batch_heterogeneity_compare_dev(a, b, _lib.enc(ctx), int(k), float(max_ooctx_meth_frac), int(min_reads),
                                                        int(max_window_span), _stream(bam_a.device), C.byref(ncommon), C.byref(nrow)))
-    n = nrow.value
-    icols = list(torch.empty((10, n), dtype=torch.int32, device=dev).unbind(0))
-    dcols = list(torch.empty((13, n), dtype=torch.float64, device=dev).unbind(0))
-    counts = [torch.empty((n, 1 << int(k)), dtype=torch.int32, device=dev) for _ in range(2)] if with_counts else [None, None]
-    if n:
-        _lib.check(lib.epi_batch_heterogeneity_compare_fetch_dev(a, _ptr_array(icols), _ptr_array(dcols),
-                                                                 *[C.c_void_p(c.data_ptr()) if with_counts else None for c in counts],
-                                                                 _stream(bam_a.device)))
-    cols = icols + dcols
-    if not as_device:
-        cols = [c.cpu().numpy() for c in cols]
-        counts = [c.cpu().numpy() if with_counts else None for c in counts]
-    rep = Report(dict(zip(HETEROGENEITY_COMPARE_COLUMNS, cols)), bam_a.levels)
+    counts = _pattern_counts(bam_a, nrow.value, k, with_counts, sides=2)
+    rep = _fetch_table(bam_a, lib.epi_batch_heterogeneity_compare_fetch_dev, nrow.value, 10, HETEROGENEITY_COMPARE_COLUMNS, as_device, counts)
     rep.ncommon = ncommon.value
     if with_counts:
-        rep.counts_a, rep.counts_b = counts
+        rep.counts_a, rep.counts_b = counts if as_device else [c.cpu().numpy() for c in counts]
     return rep
 
 
@@ -489,20 +482,6 @@ def _linkage_run(bam, ctx, max_neighbours, max_distance, max_ooctx_meth_frac, mi
                                                         float(max_ooctx_meth_frac), int(min_reads), _stream(bam.device),
                                                         C.byref(nrow)))
     return nrow.value
-
-
-def _fetch_table(bam, fetch, n, nint, names, as_device):
-    """The columns of a finished report, nint int32 ones then float64 ones, through the library's `fetch`."""
-    torch = _torch()
-    dev = "cuda:%d" % bam.device
-    icols = list(torch.empty((nint, n), dtype=torch.int32, device=dev).unbind(0))
-    dcols = list(torch.empty((len(names) - nint, n), dtype=torch.float64, device=dev).unbind(0))
-    if n:
-        _lib.check(fetch(bam.batch(), _ptr_array(icols), _ptr_array(dcols), _stream(bam.device)))
-    cols = icols + dcols
-    if not as_device:
-        cols = [c.cpu().numpy() for c in cols]
-    return Report(dict(zip(names, cols)), bam.levels)
 
 
 def rcpp_linkage_report(df, ctx, max_neighbours, max_distance, max_ooctx_meth_frac, min_reads=1, as_device=False):
@@ -525,7 +504,6 @@ def rcpp_linkage_blocks(df, ctx, max_neighbours, max_distance, max_ooctx_meth_fr
     return _fetch_table(bam, lib.epi_batch_linkage_blocks_fetch_dev, nblock.value, 5, BLOCK_COLUMNS, as_device)
 
 
-CX_COLUMNS = ("rname", "strand", "pos", "context", "meth", "unmeth")
 CX_COMPARE_COLUMNS = ("rname", "strand", "pos", "context", "meth_a", "unmeth_a", "meth_b", "unmeth_b", "beta_a", "beta_b", "delta_beta", "p")
 DMR_COLUMNS = ("rname", "start", "end", "nsites", "direction", "beta_a", "beta_b", "delta_beta", "mean_delta_beta", "p")
 
@@ -770,6 +748,15 @@ def rcpp_summarise_patterns_multi(df, targets, min_overlap, ctx, min_ctx_freq, c
 
 # ---- exported R API ------------------------------------------------------------------------------
 
+def _deliver(rep, report_file, gzip, as_device=True):
+    """The end of every report function: the report itself (a device table comes to the host unless as_device), or with a
+    report_file the report written there and None."""
+    if report_file is None:
+        return _table_to_host(rep, as_device)
+    writeReport(rep, report_file, gzip)
+    return None
+
+
 def _match_arg(value, choices, name):
     if value is None:
         return choices[0]                       # match.arg: first choice is the default
@@ -795,10 +782,7 @@ def generateCytosineReport(bam, report_file=None, threshold_reads=True, threshol
                                     CONTEXT_TO_BASES[report_context]["ctx_meth"], as_device=as_device)
     else:                                       # pass <- rep(TRUE, nrow(bam)), :193-195
         rep = rcpp_cx_report(bam, None, CONTEXT_TO_BASES[report_context]["ctx_meth"], as_device=as_device)
-    if report_file is None:
-        return rep
-    writeReport(rep, report_file, gzip)
-    return None
+    return _deliver(rep, report_file, gzip)
 
 
 def generateMhlReport(bam, report_file=None, haplotype_context=None, max_haplotype_window=0,
@@ -810,10 +794,7 @@ def generateMhlReport(bam, report_file=None, haplotype_context=None, max_haploty
     c = CONTEXT_TO_BASES[haplotype_context]
     rep = rcpp_mhl_report(bam, c["ctx_meth"] + c["ctx_unmeth"], max_haplotype_window, min_haplotype_length,
                           max_outofcontext_beta, as_device=as_device)
-    if report_file is None:
-        return rep
-    writeReport(rep, report_file, gzip)
-    return None
+    return _deliver(rep, report_file, gzip)
 
 
 def generateHeterogeneityReport(bam, report_file=None, window_context=None, window_sites=4, min_reads=1, max_window_span=0,
@@ -824,16 +805,12 @@ def generateHeterogeneityReport(bam, report_file=None, window_context=None, wind
     the reads those generateMhlReport keeps under max_outofcontext_beta; windows with fewer than min_reads reads, or
     (max_window_span > 0) spanning more than max_window_span bases, are left out.  The reference has no such report."""
     window_context = _match_arg(window_context, _CTX_CHOICES, "window.context")
-    if isinstance(window_sites, bool) or int(window_sites) != window_sites or not 2 <= int(window_sites) <= 6:
-        raise ValueError("'window.sites' should be an integer from 2 to 6")
+    window_sites = _whole_number(window_sites, "window.sites", 2, 6)
     bam = preprocessBam(bam, **preprocess_args)
     c = CONTEXT_TO_BASES[window_context]
-    rep = rcpp_heterogeneity_report(bam, c["ctx_meth"] + c["ctx_unmeth"], int(window_sites), max_outofcontext_beta,
+    rep = rcpp_heterogeneity_report(bam, c["ctx_meth"] + c["ctx_unmeth"], window_sites, max_outofcontext_beta,
                                     min_reads, max_window_span, as_device=as_device)
-    if report_file is None:
-        return rep
-    writeReport(rep, report_file, gzip)
-    return None
+    return _deliver(rep, report_file, gzip)
 
 
 def compareHeterogeneity(bam_a, bam_b, report_file=None, window_context=None, window_sites=4, min_reads=1, max_window_span=0,
@@ -848,17 +825,13 @@ def compareHeterogeneity(bam_a, bam_b, report_file=None, window_context=None, wi
     preprocessBam with the same preprocess_args and must have the same sequence names.  The Report's `ncommon` is the
     number of common sites.  The reference has no such report."""
     window_context = _match_arg(window_context, _CTX_CHOICES, "window.context")
-    if isinstance(window_sites, bool) or int(window_sites) != window_sites or not 2 <= int(window_sites) <= 6:
-        raise ValueError("'window.sites' should be an integer from 2 to 6")
+    window_sites = _whole_number(window_sites, "window.sites", 2, 6)
     bam_a = preprocessBam(bam_a, **preprocess_args)
     bam_b = preprocessBam(bam_b, **preprocess_args)
     c = CONTEXT_TO_BASES[window_context]
-    rep = rcpp_heterogeneity_compare(bam_a, bam_b, c["ctx_meth"] + c["ctx_unmeth"], int(window_sites), max_outofcontext_beta,
+    rep = rcpp_heterogeneity_compare(bam_a, bam_b, c["ctx_meth"] + c["ctx_unmeth"], window_sites, max_outofcontext_beta,
                                      min_reads, max_window_span, as_device=as_device)
-    if report_file is None:
-        return rep
-    writeReport(rep, report_file, gzip)
-    return None
+    return _deliver(rep, report_file, gzip)
 
 
 def _whole_number(value, name, lo, hi=None):
@@ -885,10 +858,7 @@ def generateLinkageReport(bam, report_file=None, linkage_context=None, max_neigh
     c = CONTEXT_TO_BASES[linkage_context]
     rep = rcpp_linkage_report(bam, c["ctx_meth"] + c["ctx_unmeth"], max_neighbours, max_distance, max_outofcontext_beta,
                               min_reads, as_device=as_device)
-    if report_file is None:
-        return rep
-    writeReport(rep, report_file, gzip)
-    return None
+    return _deliver(rep, report_file, gzip)
 
 
 def generateHaplotypeBlocks(bam, report_file=None, linkage_context=None, max_neighbours=4, max_distance=0, min_reads=10,
@@ -906,10 +876,7 @@ def generateHaplotypeBlocks(bam, report_file=None, linkage_context=None, max_nei
     c = CONTEXT_TO_BASES[linkage_context]
     rep = rcpp_linkage_blocks(bam, c["ctx_meth"] + c["ctx_unmeth"], max_neighbours, max_distance, max_outofcontext_beta,
                               min_reads, min_r2, min_sites, as_device=as_device)
-    if report_file is None:
-        return rep
-    writeReport(rep, report_file, gzip)
-    return None
+    return _deliver(rep, report_file, gzip)
 
 
 def _cytosine_comparison(bam_a, bam_b, threshold_reads, threshold_context, min_context_sites, min_context_beta, max_outofcontext_beta,
@@ -920,12 +887,7 @@ def _cytosine_comparison(bam_a, bam_b, threshold_reads, threshold_context, min_c
     min_coverage = _whole_number(min_coverage, "min.coverage", 0, 2 ** 31 - 1)
     bam_a = preprocessBam(bam_a, **preprocess_args)
     bam_b = preprocessBam(bam_b, **preprocess_args)
-    if bam_a.levels != bam_b.levels:
-        raise ValueError("the two inputs have different sequence names (levels): their rname codes cannot be compared")
-    bam_a.batch()
-    bam_b.batch(bam_a.device)
-    if bam_b.device != bam_a.device:
-        raise ValueError("the two inputs are on different devices (%s and %s)" % (bam_a.device, bam_b.device))
+    _batch_pair(bam_a, bam_b)
     reps = [generateCytosineReport(bam, None, threshold_reads, threshold_context, min_context_sites, min_context_beta,
                                    max_outofcontext_beta, report_context, as_device=True) for bam in (bam_a, bam_b)]
     return rcpp_cx_compare(reps[0], reps[1], min_coverage, as_device=True)
@@ -943,10 +905,7 @@ def compareCytosineReports(bam_a, bam_b, report_file=None, threshold_reads=True,
     no such report."""
     rep = _cytosine_comparison(bam_a, bam_b, threshold_reads, threshold_context, min_context_sites, min_context_beta,
                                max_outofcontext_beta, report_context, min_coverage, preprocess_args)
-    if report_file is None:
-        return _table_to_host(rep, as_device)
-    writeReport(rep, report_file, gzip)
-    return None
+    return _deliver(rep, report_file, gzip, as_device)
 
 
 def generateDmrReport(bam_a, bam_b, report_file=None, threshold_reads=True, threshold_context=None, min_context_sites=2,
@@ -963,10 +922,7 @@ def generateDmrReport(bam_a, bam_b, report_file=None, threshold_reads=True, thre
                                 max_outofcontext_beta, report_context, min_coverage, preprocess_args)
     rep = rcpp_cx_compare_regions(cmp_, *args, as_device=True)
     rep.ncommon = cmp_.ncommon
-    if report_file is None:
-        return _table_to_host(rep, as_device)
-    writeReport(rep, report_file, gzip)
-    return None
+    return _deliver(rep, report_file, gzip, as_device)
 
 
 def writeReport(report, report_file, gzip=False, nthreads=None):

@@ -80,6 +80,41 @@ struct DevBuf {
 
 struct ProfEntry { double ms = 0; int64_t n = 0; };
 
+// ---- state of the reports that count over the per-strand site table -------------
+// The scalars their kernels and the host exchange (SiteReportState::scal holds one, 64 bytes allocated; kernels take
+// `&sc->field`, as with Scalars)
+struct SiteScalars {
+  uint32_t nplus;          // '+' sites of the table: its '-' part starts here
+  uint32_t nrow;           // reported rows: windows, pairs
+  uint32_t nblock;         // haplotype blocks
+  uint32_t ncommon;        // comparison: sites both batches have
+};
+
+// What the heterogeneity report (heterogeneity.hip), the linkage report and its blocks (linkage.hip) and the heterogeneity
+// comparison (het_compare.hip, on its first batch) keep on a batch: the site table, the counters over it, which rows are
+// reported and where, and the arguments of the last report that its fetch needs.  het_common.hpp has the data path.
+struct SiteReportState {
+  DevBuf cx;               // the site table in CX row order: the un-thresholded CX report's six columns, [6][nsite]
+  DevBuf rank;             // [nsite] '+' rows in front of a CX row
+  DevBuf key, sctx;        // [nsite] the table split per strand: 64-bit search key and context code of a site
+  DevBuf counts;           // [nsite][2^k] pattern counters, or [nsite][D][4] pair counters
+  DevBuf flag, out;        // keep flag and output row: [nsite] per window start, [nsite][D] per pair
+  DevBuf scal;             // SiteScalars
+  DevBuf back, blen, bmean;       // blocks, by table ordinal: leading linked pairs behind a site; length and mean r^2 at a block's first site
+  DevBuf bflag, bout;             // ... by CX row: a block starts here, its output row
+  DevBuf cx_all, counts_b;        // comparison: a's CX table before the common one is compacted from it; the counters of b's rows
+  int64_t nsite = 0;       // sites of the table the last report counted over (0: it reported nothing, no table is kept)
+  int32_t k = 0, D = 0;    // window size / neighbours of the last report
+  uint32_t min_reads = 1;
+  int64_t max_span = 0, max_dist = 0;
+  bool blocks = false;     // epi_batch_linkage_blocks_dev has run on the last linkage report ...
+  int64_t nblock = 0;      // ... and found this many
+  SiteScalars *scalars() const { return scal.as<SiteScalars>(); }
+  void release() {
+    for (DevBuf *d : {&cx, &rank, &key, &sctx, &counts, &flag, &out, &scal, &back, &blen, &bmean, &bflag, &bout, &cx_all, &counts_b}) d->release();
+  }
+};
+
 // ---- per-read class counting shared by the per-read kernels and the fused CX tile kernel (per_read.hip) ----------
 struct ClassLut { uint32_t lo0, lo1, hi0, hi1; };   // one byte per code: codes 0-3, 4-7, 8-11, 12-15
 
@@ -229,26 +264,9 @@ struct epi_batch {
   int32_t thr_tab_len = -1;
   epi::ThrParams thr_tab_prm = {0, 0.0, 0.0};
   size_t pool_cap2 = 0;     // rows that fit pool_d/pool_e (lMHL doubles)
-  // heterogeneity report (heterogeneity.hip): its own copy of the site table (the CX report's six columns), the '+' rank of
-  // every site, the per-strand search table (key, context), the pattern counters [site][2^k], the keep flags and output
-  // rows of the windows, two scalars ('+' sites, reported rows); and what the fetch needs to know of the last report
-  epi::DevBuf het_cx, het_rank, het_flag, het_key, het_sctx, het_counts, het_out, het_scal;
-  int64_t het_nsite = 0, het_max_span = 0;
-  int32_t het_k = 0;
-  uint32_t het_min_reads = 1;
-  // linkage report (linkage.hip): the site table and the counters [site][D][4], keep flags and output rows [site][D] live in
-  // the heterogeneity report's buffers (one report is live on a batch at a time; het_scal[2]: blocks); its own are the
-  // blocks': leading linked pairs behind a site, block length and mean r^2 at a block's first site (by table ordinal),
-  // and the blocks' flags and output rows by CX row
-  epi::DevBuf link_back, link_blen, link_bmean, link_bflag, link_bout;
-  int32_t link_D = 0;
-  uint32_t link_min_reads = 1;
-  int64_t link_max_dist = 0, link_nblock = 0;
-  bool link_blocks = false;                    // epi_batch_linkage_blocks_dev has run on the last linkage report
-  // heterogeneity comparison (het_compare.hip), all on its first batch a: the common site table and what follows from it
-  // live in a's heterogeneity buffers (het_counts: a's side, het_scal[3]: common sites); its own are a's un-intersected
-  // CX table, which the common one is compacted from, and the counters of the second batch's rows
-  epi::DevBuf cmp_cx, cmp_counts_b;
+  // the heterogeneity report, the linkage report with its blocks and the heterogeneity comparison (het_common.hpp): the
+  // site table they count over and what the last of them left for its fetch; one of them is live on a batch at a time
+  epi::SiteReportState sites;
 
   // state of the last report (for fetch)
   epi::ReportKind last_kind = epi::KIND_NONE;

@@ -1,8 +1,10 @@
 // What the heterogeneity report (heterogeneity.hip), the linkage report (linkage.hip) and the heterogeneity comparison
 // (het_compare.hip) share: the per-strand site table of the batch's un-thresholded CX report, the read rule, a row's site
-// range in that table and its call at a site.  All count on the same data path (heterogeneity.hip has its description);
-// the reports differ in what a row adds to, the comparison counts two batches with the heterogeneity report's kernel on
-// the sites both have.
+// range in that table and its call at a site; the device view of the table that the kernels behind the counting take, the
+// step from keep flags to output rows, the per-sample metrics of a histogram and the checks of the entry points.  All
+// count on the same data path (heterogeneity.hip has its description) and keep their state in one place, epi_batch::sites
+// (SiteReportState, common.hpp); the reports differ in what a row adds to, the comparison counts two batches with the
+// heterogeneity report's kernel on the sites both have.
 #pragma once
 #include "common.hpp"
 #include <string.h>
@@ -38,16 +40,23 @@ __device__ __forceinline__ int32_t het_key_pos(unsigned long long key) {
 // at most G entries is probed whole.  log_{G+1} dependent loads instead of log_2: 6 instead of 22 for 3.5 M sites and 16
 // lanes, and the loads are what the kernel waits for.  Every lane of the wave calls this together; the lanes of a group pass
 // the same a, b and key (a = b: nothing to search).
+// the bits of group `grp` (G lanes) in the wave's ballot of pred, lane `sub` of the group at bit `sub` (pred: an int, as
+// __ballot takes it)
+template <int G>
+__device__ __forceinline__ unsigned long long group_ballot(int pred, uint32_t grp) {
+  const unsigned long long gmask = G == 64 ? ~0ull : ((1ull << (G % 64)) - 1ull);
+  return (__ballot(pred) >> (grp * G)) & gmask;
+}
+
 template <int G>
 __device__ __forceinline__ uint32_t het_lower_bound(const unsigned long long *__restrict__ keys, uint32_t a, uint32_t b,
                                                     unsigned long long key, uint32_t sub, uint32_t grp) {
-  const unsigned long long gmask = G == 64 ? ~0ull : ((1ull << (G % 64)) - 1ull);
   while (__ballot(a < b) != 0ull) {
     const uint32_t span = b - a;
     const bool last = span <= (uint32_t)G;
     const uint32_t m = last ? a + sub : a + (uint32_t)(((uint64_t)span * (sub + 1u)) / (uint32_t)(G + 1));
     const bool below = m < b && keys[m] < key;
-    const uint32_t cnt = (uint32_t)__popcll((__ballot(below) >> (grp * G)) & gmask);
+    const uint32_t cnt = (uint32_t)__popcll(group_ballot<G>(below, grp));
     if (last) {
       a = b = a + cnt;
     } else {
@@ -119,13 +128,18 @@ struct HetRow {
   }
 };
 
-// What the kernels behind the counting see (heterogeneity.hip, het_compare.hip): the site table in CX row order, the
-// per-strand table and the counters of the windows
-struct HetFinish {
+// The site table as the kernels behind the counting see it: in CX row order, split per strand, and the counters over it.
+// (Its row count N is the first member of the structs that derive from it: a 32-bit member at the end of this one would
+// move what follows it in their kernel arguments by the padding behind it.)
+struct SiteView {
   const int32_t *rname, *strand, *pos, *context;   // the CX table
   const uint32_t *rank, *n1;
   const unsigned long long *key;
   const uint32_t *counts;
+};
+
+// ... with the windows of a heterogeneity report or a comparison (heterogeneity.hip, het_compare.hip)
+struct HetFinish : SiteView {
   uint32_t N;
   int32_t k;
   uint32_t min_reads;
@@ -145,26 +159,70 @@ __device__ __forceinline__ const uint32_t *het_window(const HetFinish &f, uint32
   return f.counts + ((size_t)g << f.k);
 }
 
+// What one histogram c[2^k] says of its sample.  The bin sums run over the bins in ascending order inside one thread; hist,
+// when given, receives the histogram as a row of int32.
+struct HetMetrics {
+  uint64_t n;
+  int32_t npatterns;
+  double beta, epipoly, entropy, pdr;
+};
+__device__ __forceinline__ HetMetrics het_metrics(const uint32_t *c, int k, int32_t *hist) {
+  const int nb = 1 << k;
+  uint64_t n = 0, nmeth = 0;
+  int32_t npat = 0;
+  for (int b = 0; b < nb; b++) { const uint32_t v = c[b]; n += v; nmeth += (uint64_t)v * (uint32_t)__popc(b); npat += v ? 1 : 0; }
+  const double dn = (double)n;
+  double sq = 0.0, ent = 0.0;
+  for (int b = 0; b < nb; b++) {                              // ascending bins
+    const uint32_t v = c[b];
+    if (hist) hist[b] = (int32_t)v;
+    if (!v) continue;
+    const double pb = (double)v / dn;
+    sq += pb * pb;
+    ent += pb * log2(pb);
+  }
+  HetMetrics m;
+  m.n = n; m.npatterns = npat;
+  m.beta = (double)nmeth / (dn * (double)k);
+  m.epipoly = 1.0 - sq;
+  m.entropy = -ent / (double)k;
+  m.pdr = 1.0 - (double)((uint64_t)c[0] + c[nb - 1]) / dn;
+  return m;
+}
+
 constexpr int kHetMinK = 2, kHetMaxK = 6;
 // bytes of counters (nsites * 2^k * 4) of a heterogeneity report or of one side of a comparison, or -1 when a report
 // refuses them: above 4 GiB, or sites beyond 32-bit ordinals
 int64_t het_counter_bytes(int64_t nsites, int k);
 
-// Host side (heterogeneity.hip).  het_cx_sites: the un-thresholded CX report of the upper-case letters of ctx, as
-// epi_batch_cx_report_dev(b, NULL, those) runs it; refuses a batch set up for a sharded report (`who` names the caller in
-// the message) and leaves last_kind = KIND_NONE.  het_site_table: that report's six columns fetched into het_cx, every
-// row's '+' rank in het_rank, the per-strand table in het_key / het_sctx and the '+' site count in het_scal[0]
-// (het_scal[1] is the caller's); nsite >= 1.  het_flag holds nsite scratch words afterwards.  Its two halves on their
-// own: het_cx_fetch brings the six columns into `cx` ([6][nsite]), het_strand_table makes rank, key, context and '+'
-// count from a table of nsite rows that is in het_cx already (its first four columns, [.][nsite]).
+// Host side (heterogeneity.hip); `sites` is epi_batch::sites.  het_cx_sites: the un-thresholded CX report of the upper-case
+// letters of ctx, as epi_batch_cx_report_dev(b, NULL, those) runs it; refuses a batch set up for a sharded report (`who`
+// names the caller in the message) and leaves last_kind = KIND_NONE.  het_site_table: that report's six columns fetched
+// into sites.cx, every row's '+' rank in sites.rank, the per-strand table in sites.key / sites.sctx and the '+' site count
+// in the scalar nplus; nsite >= 1.  sites.flag holds nsite scratch words afterwards.  Its two halves on their own:
+// het_cx_fetch brings the six columns into `cx` ([6][nsite]), het_strand_table makes rank, key, context and '+' count from
+// a table of nsite rows that is in sites.cx already (its first four columns, [.][nsite]).
 int het_cx_sites(epi_batch *b, const char *ctx, hipStream_t s, const char *who, int64_t *nsite);
 int het_cx_fetch(epi_batch *b, int64_t nsite, hipStream_t s, DevBuf &cx);
 int het_strand_table(epi_batch *b, int64_t nsite, hipStream_t s);
 int het_site_table(epi_batch *b, int64_t nsite, hipStream_t s);
 // the rows, the table and the read rule's masks for the contexts of ctx_mask
 void het_rows_args(const epi_batch *b, uint32_t ctx_mask, double max_oo, HetRows &a);
-// the site table, window size, thresholds and counters (het_counts) of the last report on b
+// the site table of b and its counters; returns its rows (sites.nsite)
+uint32_t site_view_args(const epi_batch *b, SiteView &v);
+// ... with window size and thresholds of the last report on b
 void het_finish_args(const epi_batch *b, HetFinish &f);
+// Which rows are reported, and where: the exclusive scan of the n keep flags into off, their total into `total` (a field
+// of b's SiteScalars) and from there to the host -- the step's one synchronisation.  A profiling range `prof` that the
+// caller has open around its keep kernel ends behind the scan.
+int site_rows(epi_batch *b, const uint32_t *flag, int64_t n, uint32_t *off, uint32_t *total, hipStream_t s, int64_t *count,
+              const char *prof = nullptr);
+// k and max_window_span as a report and a comparison take them (`who`: the entry point, for the message)
+int het_check_window(const char *who, int k, int32_t max_window_span);
+// What a fetch entry point `who` does first: its arguments, the report on b (`kind`; blocks: those of the linkage report),
+// the ni + nd columns, the device and the stream.  *nrow = 0: nothing to write.
+int site_fetch_begin(const char *who, epi_batch *b, ReportKind kind, bool blocks, int32_t *const *icols, int ni, double *const *dcols,
+                     int nd, void *stream, hipStream_t *s, int64_t *nrow);
 // k_het_count<16> or <64> (heterogeneity.hip): the rows of `a` add to counts [a.N << k], which the caller has zeroed;
 // nb_rows and wide are het_count_blocks' of the batch the rows are of
 int het_count_launch(const HetRows &a, int k, uint32_t *counts, int64_t nb_rows, bool wide, hipStream_t s);

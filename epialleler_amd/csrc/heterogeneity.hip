@@ -6,7 +6,7 @@
 //
 // Data path, all on the report's stream:
 // The site table, the read rule and a row's walk over its sites are shared with the linkage report (het_common.hpp).
-//  (a) the un-thresholded CX report of the batch, fetched into het_cx (six columns of N rows, in (rname, pos, strand)
+//  (a) the un-thresholded CX report of the batch, fetched into sites.cx (six columns of N rows, in (rname, pos, strand)
 //      order).  A scan over "strand is +" gives every row its ordinal in a table split per strand: '+' sites at
 //      [0, n1), '-' sites at [n1, N), each sorted by (rname, pos).  k_het_sites writes that table: a 64-bit key
 //      (rname << 32) + (pos + 2^31) to search in, and the site's context code.
@@ -16,8 +16,10 @@
 //      the k bits that end at it (the previous round's last k - 1 bits carried over) and, when all k are valid, adds 1
 //      to counts[first site of the window][pattern].  Windows never leave the row's (rname, strand): [lo, hi) does not.
 //  (c) k_het_keep (a thread per CX row = per window start): n, min_reads, the span cap -> a flag; util.hip's scan turns
-//      the flags into output rows; k_het_emit (at fetch) computes the metrics into the caller's columns.  The bin sums
-//      run over the bins in ascending order inside one thread: no launch shape enters the result.
+//      the flags into output rows (site_rows); k_het_emit (at fetch) writes het_metrics of the window's histogram into
+//      the caller's columns.  The bin sums run over the bins in ascending order inside one thread: no launch shape
+//      enters the result.
+// The state all of this leaves on the batch is epi_batch::sites (SiteReportState, common.hpp).
 //
 // Contention.  Rows arrive sorted by (rname, start): on a deep amplicon the rows of a wave share their windows and mostly
 // their pattern.  With 16-lane groups the four rows of a wave walk the same sites when they start together, so lane j
@@ -61,14 +63,13 @@ __global__ __launch_bounds__(HET_WG) void k_het_count(HetArgs a) {
   const uint32_t lo = r.lo, hi = r.hi;
 
   const int k = a.k;
-  const unsigned long long gmask = G == 64 ? ~0ull : ((1ull << (G % 64)) - 1ull);
   const uint32_t full = (1u << k) - 1u;
   unsigned long long carry_v = 0, carry_m = 0;               // the k - 1 sites in front of this round, oldest at bit 0
   for (uint32_t base = lo; __ballot(base < hi) != 0ull; base += G) {
     const uint32_t g = base + sub;
     bool valid, meth;
     r.call(a, g, valid, meth);
-    const unsigned long long sv = (__ballot(valid) >> (grp * G)) & gmask, sm = (__ballot(meth) >> (grp * G)) & gmask;
+    const unsigned long long sv = group_ballot<G>(valid, grp), sm = group_ballot<G>(meth, grp);
     // the k sites that end at this lane's: from this round, and from the carry for the first k - 1 lanes
     const int back = k - 1;
     unsigned long long wv, wm;
@@ -127,41 +128,68 @@ __global__ __launch_bounds__(HET_WG) void k_het_emit(HetFinish f, const uint32_t
   int32_t end = 0;
   const uint32_t *c = het_window(f, i, &end);
   if (!c) return;
-  const int nb = 1 << f.k;
   const uint32_t r = out_off[i];
-  uint64_t n = 0, nmeth = 0;
-  int32_t npat = 0;
-  for (int b = 0; b < nb; b++) { const uint32_t v = c[b]; n += v; nmeth += (uint64_t)v * (uint32_t)__popc(b); npat += v ? 1 : 0; }
-  const double dn = (double)n;
-  double sq = 0.0, ent = 0.0;
-  for (int b = 0; b < nb; b++) {                              // ascending bins
-    const uint32_t v = c[b];
-    if (o.counts) o.counts[(size_t)r * nb + b] = (int32_t)v;
-    if (!v) continue;
-    const double pb = (double)v / dn;
-    sq += pb * pb;
-    ent += pb * log2(pb);
-  }
+  const HetMetrics m = het_metrics(c, f.k, o.counts ? o.counts + ((size_t)r << f.k) : nullptr);
   o.rname[r] = f.rname[i]; o.strand[r] = f.strand[i]; o.pos[r] = f.pos[i]; o.end[r] = end; o.context[r] = f.context[i];
-  o.nreads[r] = (int32_t)n; o.npatterns[r] = npat;
-  o.beta[r] = (double)nmeth / (dn * (double)f.k);
-  o.epipoly[r] = 1.0 - sq;
-  o.entropy[r] = -ent / (double)f.k;
-  o.pdr[r] = 1.0 - (double)((uint64_t)c[0] + c[nb - 1]) / dn;
+  o.nreads[r] = (int32_t)m.n; o.npatterns[r] = m.npatterns;
+  o.beta[r] = m.beta; o.epipoly[r] = m.epipoly; o.entropy[r] = m.entropy; o.pdr[r] = m.pdr;
+}
+
+uint32_t site_view_args(const epi_batch *b, SiteView &v) {
+  const SiteReportState &t = b->sites;
+  const int32_t *cx = t.cx.as<int32_t>();
+  const size_t N = (size_t)t.nsite;
+  v.rname = cx; v.strand = cx + N; v.pos = cx + 2 * N; v.context = cx + 3 * N;
+  v.rank = t.rank.as<uint32_t>();
+  v.n1 = &t.scalars()->nplus;
+  v.key = t.key.as<unsigned long long>();
+  v.counts = t.counts.as<uint32_t>();
+  return (uint32_t)N;
 }
 
 void het_finish_args(const epi_batch *b, HetFinish &f) {
-  const int32_t *cx = b->het_cx.as<int32_t>();
-  const size_t N = (size_t)b->het_nsite;
-  f.rname = cx; f.strand = cx + N; f.pos = cx + 2 * N; f.context = cx + 3 * N;
-  f.rank = b->het_rank.as<uint32_t>();
-  f.n1 = b->het_scal.as<uint32_t>();
-  f.key = b->het_key.as<unsigned long long>();
-  f.counts = b->het_counts.as<uint32_t>();
-  f.N = (uint32_t)N;
-  f.k = b->het_k;
-  f.min_reads = b->het_min_reads;
-  f.max_span = b->het_max_span;
+  f.N = site_view_args(b, f);
+  f.k = b->sites.k;
+  f.min_reads = b->sites.min_reads;
+  f.max_span = b->sites.max_span;
+}
+
+int site_rows(epi_batch *b, const uint32_t *flag, int64_t n, uint32_t *off, uint32_t *total, hipStream_t s, int64_t *count,
+              const char *prof) {
+  const int rc = scan_exclusive_u32(flag, off, n, total, b->scan_tmp, s);
+  if (prof) prof_end(prof, s);
+  EPI_HIP(hipGetLastError());
+  EPI_TRY(rc);
+  // (the reported rows come back with the '+' count in front of them, 8 bytes; blocks and common sites alone, 4)
+  SiteScalars *sc = b->sites.scalars();
+  const uint32_t *first = total == &sc->nrow ? &sc->nplus : total;
+  uint32_t h[2] = {0, 0};
+  EPI_TRY(read_scalars(b, s, first, (size_t)(total - first + 1) * 4, h));
+  *count = h[total - first];
+  return EPI_OK;
+}
+
+int het_check_window(const char *who, int k, int32_t max_window_span) {
+  if (k < kHetMinK || k > kHetMaxK) return fail(EPI_ERR_ARG, "%s: k = %d, windows hold %d to %d sites", who, k, kHetMinK, kHetMaxK);
+  if (max_window_span < 0) return fail(EPI_ERR_ARG, "%s: negative max_window_span", who);
+  return EPI_OK;
+}
+
+int site_fetch_begin(const char *who, epi_batch *b, ReportKind kind, bool blocks, int32_t *const *icols, int ni, double *const *dcols,
+                     int nd, void *stream, hipStream_t *s, int64_t *nrow) {
+  *nrow = 0;
+  if (!b || !icols || !dcols) return fail(EPI_ERR_ARG, "%s: NULL argument", who);
+  const char *what = blocks ? "epi_batch_linkage_blocks_dev" : kind == KIND_HET ? "heterogeneity report" : kind == KIND_LINK ? "linkage report"
+                                                                                                          : "heterogeneity comparison";
+  if (b->last_kind != kind || (blocks && !b->sites.blocks)) return fail(EPI_ERR_STATE, "%s: no finished %s on this batch", who, what);
+  const int64_t n = blocks ? b->sites.nblock : b->last_nrow;
+  if (n == 0) return EPI_OK;
+  for (int i = 0; i < ni; i++) if (!icols[i]) return fail(EPI_ERR_ARG, "%s: NULL column", who);
+  for (int i = 0; i < nd; i++) if (!dcols[i]) return fail(EPI_ERR_ARG, "%s: NULL column", who);
+  EPI_HIP(hipSetDevice(b->eng->device));
+  *s = pick_stream(b, stream);
+  *nrow = n;
+  return EPI_OK;
 }
 
 int het_cx_sites(epi_batch *b, const char *ctx, hipStream_t s, const char *who, int64_t *nsite) {
@@ -197,25 +225,26 @@ int het_strand_table(epi_batch *b, int64_t nsite, hipStream_t s) {
   const size_t N = (size_t)nsite;
   const int64_t nb_sites = ((int64_t)N + HET_WG - 1) / HET_WG;
   EPI_TRY(check_grid(nb_sites, HET_WG, "heterogeneity site kernels"));
-  EPI_TRY(b->het_rank.ensure(N * 4));
-  EPI_TRY(b->het_flag.ensure(N * 4));
-  EPI_TRY(b->het_key.ensure(N * 8));
-  EPI_TRY(b->het_sctx.ensure(N));
-  EPI_TRY(b->het_scal.ensure(64));
-  const int32_t *cx = b->het_cx.as<int32_t>();
-  uint32_t *scal = b->het_scal.as<uint32_t>();             // [0] '+' sites, [1] reported rows
-  uint32_t *flag = b->het_flag.as<uint32_t>(), *rank = b->het_rank.as<uint32_t>();
+  SiteReportState &t = b->sites;
+  EPI_TRY(t.rank.ensure(N * 4));
+  EPI_TRY(t.flag.ensure(N * 4));
+  EPI_TRY(t.key.ensure(N * 8));
+  EPI_TRY(t.sctx.ensure(N));
+  EPI_TRY(t.scal.ensure(64));
+  const int32_t *cx = t.cx.as<int32_t>();
+  uint32_t *nplus = &t.scalars()->nplus;
+  uint32_t *flag = t.flag.as<uint32_t>(), *rank = t.rank.as<uint32_t>();
   hipLaunchKernelGGL(k_het_strand_flag, dim3((unsigned)nb_sites), dim3(HET_WG), 0, s, cx + N, (uint32_t)N, flag);
-  EPI_TRY(scan_exclusive_u32(flag, rank, (int64_t)N, &scal[0], b->scan_tmp, s));
-  hipLaunchKernelGGL(k_het_sites, dim3((unsigned)nb_sites), dim3(HET_WG), 0, s, cx, cx + N, cx + 2 * N, cx + 3 * N, rank, &scal[0],
-                     (uint32_t)N, b->het_key.as<unsigned long long>(), b->het_sctx.as<uint8_t>());
+  EPI_TRY(scan_exclusive_u32(flag, rank, (int64_t)N, nplus, b->scan_tmp, s));
+  hipLaunchKernelGGL(k_het_sites, dim3((unsigned)nb_sites), dim3(HET_WG), 0, s, cx, cx + N, cx + 2 * N, cx + 3 * N, rank, nplus,
+                     (uint32_t)N, t.key.as<unsigned long long>(), t.sctx.as<uint8_t>());
   EPI_HIP(hipGetLastError());
   return EPI_OK;
 }
 
 int het_site_table(epi_batch *b, int64_t nsite, hipStream_t s) {
   EPI_TRY(check_grid((nsite + HET_WG - 1) / HET_WG, HET_WG, "heterogeneity site kernels"));
-  EPI_TRY(het_cx_fetch(b, nsite, s, b->het_cx));
+  EPI_TRY(het_cx_fetch(b, nsite, s, b->sites.cx));
   return het_strand_table(b, nsite, s);
 }
 
@@ -238,8 +267,8 @@ int het_count_launch(const HetRows &rows, int k, uint32_t *counts, int64_t nb_ro
 
 void het_rows_args(const epi_batch *b, uint32_t ctx_mask, double max_oo, HetRows &a) {
   a.xm = b->xm; a.off = b->off; a.len = b->len; a.rname = b->rname; a.strand = b->strand; a.start = b->start; a.n = b->n;
-  a.key = b->het_key.as<unsigned long long>(); a.sctx = b->het_sctx.as<uint8_t>(); a.n1 = b->het_scal.as<uint32_t>();
-  a.N = (uint32_t)b->het_nsite;
+  a.key = b->sites.key.as<unsigned long long>(); a.sctx = b->sites.sctx.as<uint8_t>(); a.n1 = &b->sites.scalars()->nplus;
+  a.N = (uint32_t)b->sites.nsite;
   a.oom_mask = ((1u << 2) | (1u << 5) | (1u << 6) | (1u << 7)) & ~ctx_mask;           // rcpp_mhl_report.cpp:176-177
   a.oou_mask = ((1u << 10) | (1u << 13) | (1u << 14) | (1u << 15)) & ~ctx_mask;
   a.max_oo = max_oo;
@@ -247,13 +276,14 @@ void het_rows_args(const epi_batch *b, uint32_t ctx_mask, double max_oo, HetRows
 
 static int het_report(epi_batch *b, const char *ctx, int k, double max_oo, int32_t min_reads, int32_t max_span, hipStream_t s,
                       int64_t *nrow_out) {
+  SiteReportState &t = b->sites;
   // (a) the site table
   int64_t nsite = 0;
   EPI_TRY(het_cx_sites(b, ctx, s, "epi_batch_heterogeneity_report_dev", &nsite));
-  b->het_nsite = nsite; b->het_k = k;
-  b->het_min_reads = (uint32_t)(min_reads > 1 ? min_reads : 1);
-  b->het_max_span = max_span;
-  if (nsite < k) { b->last_kind = KIND_HET; b->last_nrow = 0; b->het_nsite = 0; return EPI_OK; }
+  t.nsite = nsite; t.k = k;
+  t.min_reads = (uint32_t)(min_reads > 1 ? min_reads : 1);
+  t.max_span = max_span;
+  if (nsite < k) { b->last_kind = KIND_HET; b->last_nrow = 0; t.nsite = 0; return EPI_OK; }
   if (het_counter_bytes(nsite, k) < 0)
     return fail(EPI_ERR_ARG, "epi_batch_heterogeneity_report_dev: %lld sites x %d patterns need %lld bytes of counters, above the cap of %lld",
                 (long long)nsite, 1 << k, (long long)((nsite << k) * 4), (long long)kHetCountsCap);
@@ -263,16 +293,15 @@ static int het_report(epi_batch *b, const char *ctx, int k, double max_oo, int32
   const int64_t nb_rows = het_count_blocks(b, &wide);
   EPI_TRY(check_grid(nb_rows, HET_WG, "heterogeneity counting kernel"));
   EPI_TRY(het_site_table(b, nsite, s));
-  EPI_TRY(b->het_counts.ensure((N << k) * 4));
-  uint32_t *scal = b->het_scal.as<uint32_t>();             // [0] '+' sites, [1] reported rows
-  uint32_t *flag = b->het_flag.as<uint32_t>();
+  EPI_TRY(t.counts.ensure((N << k) * 4));
+  uint32_t *flag = t.flag.as<uint32_t>();
 
   // (b) the histograms
-  EPI_HIP(hipMemsetAsync(b->het_counts.p, 0, (N << k) * 4, s));
+  EPI_HIP(hipMemsetAsync(t.counts.p, 0, (N << k) * 4, s));
   HetRows a;
   het_rows_args(b, ctx_mask_of(ctx), max_oo, a);
   prof_begin("het_count", s);
-  const int rc_count = het_count_launch(a, k, b->het_counts.as<uint32_t>(), nb_rows, wide, s);
+  const int rc_count = het_count_launch(a, k, t.counts.as<uint32_t>(), nb_rows, wide, s);
   prof_end("het_count", s);
   EPI_TRY(rc_count);
 
@@ -281,13 +310,10 @@ static int het_report(epi_batch *b, const char *ctx, int k, double max_oo, int32
   het_finish_args(b, f);
   hipLaunchKernelGGL(k_het_keep, dim3((unsigned)nb_sites), dim3(HET_WG), 0, s, f, flag);
   EPI_HIP(hipGetLastError());
-  EPI_TRY(b->het_out.ensure(N * 4));
-  EPI_TRY(scan_exclusive_u32(flag, b->het_out.as<uint32_t>(), (int64_t)N, &scal[1], b->scan_tmp, s));
-  uint32_t h[2];
-  EPI_TRY(read_scalars(b, s, scal, sizeof(h), h));
+  EPI_TRY(t.out.ensure(N * 4));
+  EPI_TRY(site_rows(b, flag, (int64_t)N, t.out.as<uint32_t>(), &t.scalars()->nrow, s, nrow_out));
   b->last_kind = KIND_HET;
-  b->last_nrow = h[1];
-  *nrow_out = h[1];
+  b->last_nrow = *nrow_out;
   return EPI_OK;
 }
 
@@ -314,9 +340,7 @@ int epi_batch_heterogeneity_report_dev(epi_batch *b, const char *ctx, int k, dou
                                        int32_t max_window_span, void *stream, int64_t *nrow_out) {
   if (!b || !ctx || !nrow_out) return fail(EPI_ERR_ARG, "epi_batch_heterogeneity_report_dev: NULL argument");
   *nrow_out = 0;
-  if (k < kHetMinK || k > kHetMaxK)
-    return fail(EPI_ERR_ARG, "epi_batch_heterogeneity_report_dev: k = %d, windows hold %d to %d sites", k, kHetMinK, kHetMaxK);
-  if (max_window_span < 0) return fail(EPI_ERR_ARG, "epi_batch_heterogeneity_report_dev: negative max_window_span");
+  EPI_TRY(het_check_window("epi_batch_heterogeneity_report_dev", k, max_window_span));
   b->last_kind = KIND_NONE;
   EPI_HIP(hipSetDevice(b->eng->device));
   return het_report(b, ctx, k, max_ooctx_meth_frac, min_reads, max_window_span, pick_stream(b, stream), nrow_out);
@@ -324,13 +348,10 @@ int epi_batch_heterogeneity_report_dev(epi_batch *b, const char *ctx, int k, dou
 
 int epi_batch_heterogeneity_fetch_dev(epi_batch *b, int32_t *const d_icols[7], double *const d_dcols[4], int32_t *d_counts,
                                       void *stream) {
-  if (!b || !d_icols || !d_dcols) return fail(EPI_ERR_ARG, "epi_batch_heterogeneity_fetch_dev: NULL argument");
-  if (b->last_kind != KIND_HET) return fail(EPI_ERR_STATE, "epi_batch_heterogeneity_fetch_dev: no finished heterogeneity report on this batch");
-  if (b->last_nrow == 0) return EPI_OK;
-  for (int i = 0; i < 7; i++) if (!d_icols[i]) return fail(EPI_ERR_ARG, "epi_batch_heterogeneity_fetch_dev: NULL column");
-  for (int i = 0; i < 4; i++) if (!d_dcols[i]) return fail(EPI_ERR_ARG, "epi_batch_heterogeneity_fetch_dev: NULL column");
-  EPI_HIP(hipSetDevice(b->eng->device));
-  hipStream_t s = pick_stream(b, stream);
+  hipStream_t s = nullptr;
+  int64_t nrow = 0;
+  EPI_TRY(site_fetch_begin("epi_batch_heterogeneity_fetch_dev", b, KIND_HET, false, d_icols, 7, d_dcols, 4, stream, &s, &nrow));
+  if (nrow == 0) return EPI_OK;
   HetFinish f;
   het_finish_args(b, f);
   HetOut o;
@@ -340,7 +361,7 @@ int epi_batch_heterogeneity_fetch_dev(epi_batch *b, int32_t *const d_icols[7], d
   o.counts = d_counts;
   const unsigned nb = (unsigned)(((int64_t)f.N + HET_WG - 1) / HET_WG);
   prof_begin("het_emit", s);
-  hipLaunchKernelGGL(k_het_emit, dim3(nb), dim3(HET_WG), 0, s, f, b->het_flag.as<uint32_t>(), b->het_out.as<uint32_t>(), o);
+  hipLaunchKernelGGL(k_het_emit, dim3(nb), dim3(HET_WG), 0, s, f, b->sites.flag.as<uint32_t>(), b->sites.out.as<uint32_t>(), o);
   prof_end("het_emit", s);
   EPI_HIP(hipGetLastError());
   return EPI_OK;

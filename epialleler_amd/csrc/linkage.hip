@@ -8,12 +8,14 @@
 //      d = 1 .. D in the round's valid / methylated masks (the previous round's last D bits carried over for the first
 //      lanes; D <= 16 <= G: one previous round suffices) and adds 1 to counts[((g - d) D + d - 1) 4 + p] for every called
 //      site it finds, p = meth(s_{g-d}) + 2 meth(s_g).  What lies between the two sites does not matter.
-//  (c) k_link_keep (a thread per CX row and d): n, min_reads, the distance cap -> a flag; util.hip's scan; k_link_emit
-//      (at fetch) writes the pair's row and metrics.
+//  (c) k_link_keep (a thread per CX row and d): n, min_reads, the distance cap -> a flag; util.hip's scan (site_rows);
+//      k_link_emit (at fetch) writes the pair's row and metrics.
 //  (d) blocks, from the counters (nothing is read back from the emitted table): k_link_back (a thread per site) counts
 //      the leading linked pairs behind a site; k_link_blocks (a thread per run head: a strand's first site or a site with
 //      back = 0) walks greedily to the next run head and leaves every block's length and mean r^2 at its first site;
 //      k_link_block_flag, the scan and k_link_block_emit bring them into CX row order.
+// The site table, the counters [site][D][4], the keep flags and output rows [site][D] and the blocks' buffers are those of
+// epi_batch::sites (SiteReportState, common.hpp), where every report of this family keeps its state.
 // Every metric is computed by one thread from the four integers of its pair: no launch shape enters a result.
 //
 // Contention.  As in k_het_count the four rows of a wave of 16-lane groups walk the same sites when they start together
@@ -50,14 +52,13 @@ __global__ __launch_bounds__(HET_WG) void k_link_count(LinkArgs a) {
   const uint32_t lo = r.lo, hi = r.hi;
 
   const int D = a.D;
-  const unsigned long long gmask = G == 64 ? ~0ull : ((1ull << (G % 64)) - 1ull);
   const uint32_t dmask = (1u << D) - 1u;
   uint32_t carry_v = 0, carry_m = 0;                         // the D sites in front of this round, oldest at bit 0
   for (uint32_t base = lo; __ballot(base < hi) != 0ull; base += G) {
     const uint32_t g = base + sub;
     bool valid, meth;
     r.call(a, g, valid, meth);
-    const unsigned long long sv = (__ballot(valid) >> (grp * G)) & gmask, sm = (__ballot(meth) >> (grp * G)) & gmask;
+    const unsigned long long sv = group_ballot<G>(valid, grp), sm = group_ballot<G>(meth, grp);
     // the D + 1 sites that end at this lane's: bit D is its own, bit D - d the site d behind it
     uint32_t wv, wm;
     if ((int)sub >= D) { wv = (uint32_t)(sv >> (sub - D)); wm = (uint32_t)(sm >> (sub - D)); }
@@ -103,11 +104,7 @@ __global__ __launch_bounds__(HET_WG) void k_link_count(LinkArgs a) {
   }
 }
 
-struct LinkFinish {
-  const int32_t *rname, *strand, *pos, *context;   // the CX table
-  const uint32_t *rank, *n1;
-  const unsigned long long *key;
-  const uint32_t *counts;
+struct LinkFinish : SiteView {
   uint32_t N;
   int32_t D;
   uint32_t min_reads;
@@ -269,29 +266,23 @@ __global__ __launch_bounds__(HET_WG) void k_link_block_emit(LinkFinish f, const 
 }
 
 static void link_finish_args(const epi_batch *b, LinkFinish &f) {
-  const int32_t *cx = b->het_cx.as<int32_t>();
-  const size_t N = (size_t)b->het_nsite;
-  f.rname = cx; f.strand = cx + N; f.pos = cx + 2 * N; f.context = cx + 3 * N;
-  f.rank = b->het_rank.as<uint32_t>();
-  f.n1 = b->het_scal.as<uint32_t>();
-  f.key = b->het_key.as<unsigned long long>();
-  f.counts = b->het_counts.as<uint32_t>();
-  f.N = (uint32_t)N;
-  f.D = b->link_D;
-  f.min_reads = b->link_min_reads;
-  f.max_dist = b->link_max_dist;
+  f.N = site_view_args(b, f);
+  f.D = b->sites.D;
+  f.min_reads = b->sites.min_reads;
+  f.max_dist = b->sites.max_dist;
 }
 
 static int link_report(epi_batch *b, const char *ctx, int D, int32_t max_dist, double max_oo, int32_t min_reads, hipStream_t s,
                        int64_t *nrow_out) {
+  SiteReportState &t = b->sites;
   // (a) the site table
   int64_t nsite = 0;
   EPI_TRY(het_cx_sites(b, ctx, s, "epi_batch_linkage_report_dev", &nsite));
-  b->het_nsite = nsite; b->link_D = D;
-  b->link_min_reads = (uint32_t)(min_reads > 1 ? min_reads : 1);
-  b->link_max_dist = max_dist;
-  b->link_blocks = false; b->link_nblock = 0;
-  if (nsite < 2) { b->last_kind = KIND_LINK; b->last_nrow = 0; b->het_nsite = 0; return EPI_OK; }
+  t.nsite = nsite; t.D = D;
+  t.min_reads = (uint32_t)(min_reads > 1 ? min_reads : 1);
+  t.max_dist = max_dist;
+  t.blocks = false; t.nblock = 0;
+  if (nsite < 2) { b->last_kind = KIND_LINK; b->last_nrow = 0; t.nsite = 0; return EPI_OK; }
   const int64_t cbytes = link_counter_bytes(nsite, D);
   if (cbytes < 0)
     return fail(EPI_ERR_ARG, "epi_batch_linkage_report_dev: %lld sites x %d neighbours need %lld bytes of counters, above the cap of %lld",
@@ -303,18 +294,17 @@ static int link_report(epi_batch *b, const char *ctx, int D, int32_t max_dist, d
   EPI_TRY(check_grid(nb_pairs, HET_WG, "linkage pair kernels"));
   EPI_TRY(check_grid(nb_rows, HET_WG, "linkage counting kernel"));
   EPI_TRY(het_site_table(b, nsite, s));
-  EPI_TRY(b->het_counts.ensure((size_t)cbytes));
-  EPI_TRY(b->het_flag.ensure(ND * 4));                       // (the site table is done with its N words)
-  EPI_TRY(b->het_out.ensure(ND * 4));
-  uint32_t *scal = b->het_scal.as<uint32_t>();               // [0] '+' sites, [1] reported pairs, [2] blocks
-  uint32_t *flag = b->het_flag.as<uint32_t>();
+  EPI_TRY(t.counts.ensure((size_t)cbytes));
+  EPI_TRY(t.flag.ensure(ND * 4));                            // (the site table is done with its N words)
+  EPI_TRY(t.out.ensure(ND * 4));
+  uint32_t *flag = t.flag.as<uint32_t>();
 
   // (b) the 2 x 2 tables
-  EPI_HIP(hipMemsetAsync(b->het_counts.p, 0, (size_t)cbytes, s));
+  EPI_HIP(hipMemsetAsync(t.counts.p, 0, (size_t)cbytes, s));
   LinkArgs a;
   het_rows_args(b, ctx_mask_of(ctx), max_oo, a);
   a.D = D;
-  a.counts = b->het_counts.as<uint32_t>();
+  a.counts = t.counts.as<uint32_t>();
   prof_begin("link_count", s);
   if (wide) hipLaunchKernelGGL((k_link_count<64>), dim3((unsigned)nb_rows), dim3(HET_WG), 0, s, a);
   else hipLaunchKernelGGL((k_link_count<16>), dim3((unsigned)nb_rows), dim3(HET_WG), 0, s, a);
@@ -326,41 +316,35 @@ static int link_report(epi_batch *b, const char *ctx, int D, int32_t max_dist, d
   link_finish_args(b, f);
   hipLaunchKernelGGL(k_link_keep, dim3((unsigned)nb_pairs), dim3(HET_WG), 0, s, f, flag);
   EPI_HIP(hipGetLastError());
-  EPI_TRY(scan_exclusive_u32(flag, b->het_out.as<uint32_t>(), (int64_t)ND, &scal[1], b->scan_tmp, s));
-  uint32_t h[2];
-  EPI_TRY(read_scalars(b, s, scal, sizeof(h), h));
+  EPI_TRY(site_rows(b, flag, (int64_t)ND, t.out.as<uint32_t>(), &t.scalars()->nrow, s, nrow_out));
   b->last_kind = KIND_LINK;
-  b->last_nrow = h[1];
-  *nrow_out = h[1];
+  b->last_nrow = *nrow_out;
   return EPI_OK;
 }
 
+// (d) the blocks of the last linkage report on b
 static int link_blocks(epi_batch *b, double min_r2, int32_t min_sites, hipStream_t s, int64_t *nblock_out) {
-  b->link_blocks = false; b->link_nblock = 0;
-  const size_t N = (size_t)b->het_nsite;
-  if (N == 0) { b->link_blocks = true; return EPI_OK; }
+  SiteReportState &t = b->sites;
+  t.blocks = false; t.nblock = 0;
+  const size_t N = (size_t)t.nsite;
+  if (N == 0) { t.blocks = true; return EPI_OK; }
   const unsigned nb = (unsigned)(((int64_t)N + HET_WG - 1) / HET_WG);
-  EPI_TRY(b->link_back.ensure(N));
-  EPI_TRY(b->link_blen.ensure(N * 4));
-  EPI_TRY(b->link_bmean.ensure(N * 8));
-  EPI_TRY(b->link_bflag.ensure(N * 4));
-  EPI_TRY(b->link_bout.ensure(N * 4));
+  EPI_TRY(t.back.ensure(N));
+  EPI_TRY(t.blen.ensure(N * 4));
+  EPI_TRY(t.bmean.ensure(N * 8));
+  EPI_TRY(t.bflag.ensure(N * 4));
+  EPI_TRY(t.bout.ensure(N * 4));
   LinkFinish f;
   link_finish_args(b, f);
-  uint32_t *scal = b->het_scal.as<uint32_t>();
-  uint32_t *blen = b->link_blen.as<uint32_t>(), *flag = b->link_bflag.as<uint32_t>();
+  uint32_t *blen = t.blen.as<uint32_t>(), *flag = t.bflag.as<uint32_t>();
   EPI_HIP(hipMemsetAsync(blen, 0, N * 4, s));
-  hipLaunchKernelGGL(k_link_back, dim3(nb), dim3(HET_WG), 0, s, f, min_r2, b->link_back.as<uint8_t>());
-  hipLaunchKernelGGL(k_link_blocks, dim3(nb), dim3(HET_WG), 0, s, f, min_r2, min_sites, b->link_back.as<uint8_t>(), blen,
-                     b->link_bmean.as<double>());
+  hipLaunchKernelGGL(k_link_back, dim3(nb), dim3(HET_WG), 0, s, f, min_r2, t.back.as<uint8_t>());
+  hipLaunchKernelGGL(k_link_blocks, dim3(nb), dim3(HET_WG), 0, s, f, min_r2, min_sites, t.back.as<uint8_t>(), blen, t.bmean.as<double>());
   hipLaunchKernelGGL(k_link_block_flag, dim3(nb), dim3(HET_WG), 0, s, f, blen, flag);
   EPI_HIP(hipGetLastError());
-  EPI_TRY(scan_exclusive_u32(flag, b->link_bout.as<uint32_t>(), (int64_t)N, &scal[2], b->scan_tmp, s));
-  uint32_t h = 0;
-  EPI_TRY(read_scalars(b, s, &scal[2], sizeof(h), &h));
-  b->link_blocks = true;
-  b->link_nblock = h;
-  *nblock_out = h;
+  EPI_TRY(site_rows(b, flag, (int64_t)N, t.bout.as<uint32_t>(), &t.scalars()->nblock, s, nblock_out));
+  t.blocks = true;
+  t.nblock = *nblock_out;
   return EPI_OK;
 }
 
@@ -396,13 +380,10 @@ int epi_batch_linkage_report_dev(epi_batch *b, const char *ctx, int max_neighbou
 }
 
 int epi_batch_linkage_fetch_dev(epi_batch *b, int32_t *const d_icols[11], double *const d_dcols[3], void *stream) {
-  if (!b || !d_icols || !d_dcols) return fail(EPI_ERR_ARG, "epi_batch_linkage_fetch_dev: NULL argument");
-  if (b->last_kind != KIND_LINK) return fail(EPI_ERR_STATE, "epi_batch_linkage_fetch_dev: no finished linkage report on this batch");
-  if (b->last_nrow == 0) return EPI_OK;
-  for (int i = 0; i < 11; i++) if (!d_icols[i]) return fail(EPI_ERR_ARG, "epi_batch_linkage_fetch_dev: NULL column");
-  for (int i = 0; i < 3; i++) if (!d_dcols[i]) return fail(EPI_ERR_ARG, "epi_batch_linkage_fetch_dev: NULL column");
-  EPI_HIP(hipSetDevice(b->eng->device));
-  hipStream_t s = pick_stream(b, stream);
+  hipStream_t s = nullptr;
+  int64_t nrow = 0;
+  EPI_TRY(site_fetch_begin("epi_batch_linkage_fetch_dev", b, KIND_LINK, false, d_icols, 11, d_dcols, 3, stream, &s, &nrow));
+  if (nrow == 0) return EPI_OK;
   LinkFinish f;
   link_finish_args(b, f);
   LinkOut o;
@@ -410,7 +391,7 @@ int epi_batch_linkage_fetch_dev(epi_batch *b, int32_t *const d_icols[11], double
   o.neighbour = d_icols[5]; o.nreads = d_icols[6]; o.uu = d_icols[7]; o.mu = d_icols[8]; o.um = d_icols[9]; o.mm = d_icols[10];
   o.cov = d_dcols[0]; o.r2 = d_dcols[1]; o.dprime = d_dcols[2];
   const unsigned nb = (unsigned)(((int64_t)f.N * f.D + HET_WG - 1) / HET_WG);
-  hipLaunchKernelGGL(k_link_emit, dim3(nb), dim3(HET_WG), 0, s, f, b->het_flag.as<uint32_t>(), b->het_out.as<uint32_t>(), o);
+  hipLaunchKernelGGL(k_link_emit, dim3(nb), dim3(HET_WG), 0, s, f, b->sites.flag.as<uint32_t>(), b->sites.out.as<uint32_t>(), o);
   EPI_HIP(hipGetLastError());
   return EPI_OK;
 }
@@ -426,22 +407,18 @@ int epi_batch_linkage_blocks_dev(epi_batch *b, double min_r2, int32_t min_sites,
 }
 
 int epi_batch_linkage_blocks_fetch_dev(epi_batch *b, int32_t *const d_icols[5], double *const d_dcols[1], void *stream) {
-  if (!b || !d_icols || !d_dcols) return fail(EPI_ERR_ARG, "epi_batch_linkage_blocks_fetch_dev: NULL argument");
-  if (b->last_kind != KIND_LINK || !b->link_blocks)
-    return fail(EPI_ERR_STATE, "epi_batch_linkage_blocks_fetch_dev: no finished epi_batch_linkage_blocks_dev on this batch");
-  if (b->link_nblock == 0) return EPI_OK;
-  for (int i = 0; i < 5; i++) if (!d_icols[i]) return fail(EPI_ERR_ARG, "epi_batch_linkage_blocks_fetch_dev: NULL column");
-  if (!d_dcols[0]) return fail(EPI_ERR_ARG, "epi_batch_linkage_blocks_fetch_dev: NULL column");
-  EPI_HIP(hipSetDevice(b->eng->device));
-  hipStream_t s = pick_stream(b, stream);
+  hipStream_t s = nullptr;
+  int64_t nblock = 0;
+  EPI_TRY(site_fetch_begin("epi_batch_linkage_blocks_fetch_dev", b, KIND_LINK, true, d_icols, 5, d_dcols, 1, stream, &s, &nblock));
+  if (nblock == 0) return EPI_OK;
   LinkFinish f;
   link_finish_args(b, f);
   LinkBlockOut o;
   o.rname = d_icols[0]; o.strand = d_icols[1]; o.start = d_icols[2]; o.end = d_icols[3]; o.nsites = d_icols[4];
   o.mean_r2 = d_dcols[0];
   const unsigned nb = (unsigned)(((int64_t)f.N + HET_WG - 1) / HET_WG);
-  hipLaunchKernelGGL(k_link_block_emit, dim3(nb), dim3(HET_WG), 0, s, f, b->link_blen.as<uint32_t>(), b->link_bmean.as<double>(),
-                     b->link_bflag.as<uint32_t>(), b->link_bout.as<uint32_t>(), o);
+  hipLaunchKernelGGL(k_link_block_emit, dim3(nb), dim3(HET_WG), 0, s, f, b->sites.blen.as<uint32_t>(), b->sites.bmean.as<double>(),
+                     b->sites.bflag.as<uint32_t>(), b->sites.bout.as<uint32_t>(), o);
   EPI_HIP(hipGetLastError());
   return EPI_OK;
 }
