@@ -179,6 +179,7 @@ _SIGS = {
                                      C.POINTER(_I64), C.POINTER(_I64)]),
     "epi_cx_compare_regions_dev": (C.c_int, [_VP, C.POINTER(_VP), C.POINTER(_VP), _I64, _F64, _F64, _I32, _I32, C.POINTER(_VP),
                                              C.POINTER(_VP), _I64, _VP, C.POINTER(_I64)]),
+    "epi_p_adjust_dev": (C.c_int, [_VP, _VP, _I64, _I32, _I64, _VP, _VP, _VP, C.POINTER(_I64)]),
     "epi_tile_positions": (C.c_int, []),
     "epi_cx_tile_positions": (C.c_int, [_CS]),
     "epi_batch_tile_key_range": (C.c_int, [_VP, _VP, C.POINTER(_I64), C.POINTER(_I64)]),

@@ -557,23 +557,24 @@ def rcpp_cx_compare(rep_a, rep_b, min_coverage=1, as_device=False):
     return _table_to_host(rep, as_device)
 
 
-def _region_args(max_p, min_delta_beta, max_gap, min_sites):
-    for value, name in ((max_p, "max.p"), (min_delta_beta, "min.delta.beta")):
+def _region_args(max_p, min_delta_beta, max_gap, min_sites, p_name="max.p"):
+    for value, name in ((max_p, p_name), (min_delta_beta, "min.delta.beta")):
         if isinstance(value, bool) or not 0 <= value <= 1:
             raise ValueError("'%s' should be a number from 0 to 1" % name)
     return float(max_p), float(min_delta_beta), _whole_number(max_gap, "max.gap", 0, 2 ** 31 - 1), _whole_number(min_sites, "min.sites", 1, 2 ** 31 - 1)
 
 
-def rcpp_cx_compare_regions(rep, max_p=0.05, min_delta_beta=0.1, max_gap=500, min_sites=3, as_device=False):
+def rcpp_cx_compare_regions(rep, max_p=0.05, min_delta_beta=0.1, max_gap=500, min_sites=3, as_device=False, significance="p"):
     """The differentially methylated regions of a device comparison table (rcpp_cx_compare with as_device=True;
     include/epihip.h, epi_cx_compare_regions_dev): maximal runs of at least min_sites consecutive rows with p <= max_p and
     |delta_beta| >= min_delta_beta, of one direction and sequence, neighbours at most max_gap apart.  rname, start, end,
     nsites, direction (int32), the pooled beta_a, beta_b and delta_beta, mean_delta_beta and the Fisher p of the pooled
-    table (float64)."""
+    table (float64).  significance="q": the table's `q` column (adjustReport) is what max_p is tested against."""
     max_p, min_delta_beta, max_gap, min_sites = _region_args(max_p, min_delta_beta, max_gap, min_sites)
+    significance = _match_arg(significance, ("p", "q"), "significance")
     torch = _torch()
     lib = _lib.load()
-    cols = _device_columns(rep, CX_COMPARE_COLUMNS, "rcpp_cx_compare_regions")
+    cols = _device_columns(rep, CX_COMPARE_COLUMNS[:-1] + (significance,), "rcpp_cx_compare_regions")
     dev = cols[0].device
     n = int(cols[0].numel())
     cap = n // min_sites                                   # (runs do not overlap)
@@ -627,6 +628,84 @@ def fisherExact(a, b, c, d, as_device=False):
     p = torch.empty(n, dtype=torch.float64, device=dev)
     _lib.check(lib.epi_fisher_exact_dev(eng, *[C.c_void_p(x.data_ptr()) for x in cells], n, C.c_void_p(p.data_ptr()), _stream(index)))
     return p if as_device else p.cpu().numpy()
+
+
+P_ADJUST_METHODS = ("holm", "hochberg", "bonferroni", "BH", "BY", "fdr", "none")          # R's p.adjust.methods without hommel
+_P_ADJUST_CODES = {"none": 0, "bonferroni": 1, "holm": 2, "hochberg": 3, "BH": 4, "fdr": 4, "BY": 5}   # EPI_PADJ_*
+
+
+def _p_adjust_args(method, n_tests, name="method"):
+    """(EPI_PADJ_* code, n_tests or 0) of a p.adjust method and R's p.adjust(n =)."""
+    method = _match_arg(method, P_ADJUST_METHODS, name)
+    if n_tests is not None:
+        try:
+            n_tests = _whole_number(n_tests, "n.tests", 1, 2 ** 31 - 1)
+        except (TypeError, OverflowError, ValueError):
+            raise ValueError("'n.tests' should be an integer from 1 to %d" % (2 ** 31 - 1))
+    return _P_ADJUST_CODES[method], n_tests or 0
+
+
+def _p_values(p, name):
+    """A column of p-values as flat float64: a device tensor stays on its device."""
+    torch = _torch()
+    if isinstance(p, torch.Tensor):
+        if not p.dtype.is_floating_point:
+            raise ValueError("'%s' should hold floating-point numbers" % name)
+        return p.reshape(-1)
+    try:
+        v = np.asarray(p)
+        if v.dtype.kind not in "fiu":
+            raise TypeError
+        return np.ascontiguousarray(v.reshape(-1), np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("'%s' should hold numbers" % name)
+
+
+def _p_adjust(p, code, n_tests):
+    """epi_p_adjust_dev on a flat column (_p_values): q, a device tensor."""
+    torch = _torch()
+    lib = _lib.load()
+    index = p.device.index if isinstance(p, torch.Tensor) and p.is_cuda else None
+    eng = _engine(index)
+    index = lib.epi_engine_device(eng)
+    dev = "cuda:%d" % index
+    p = (p if isinstance(p, torch.Tensor) else torch.from_numpy(p)).to(device=dev, dtype=torch.float64).contiguous()
+    n = int(p.shape[0])
+    q = torch.empty(n, dtype=torch.float64, device=dev)
+    m = C.c_int64(0)
+    _lib.check(lib.epi_p_adjust_dev(eng, C.c_void_p(p.data_ptr()), n, code, n_tests, C.c_void_p(q.data_ptr()), None, _stream(index),
+                                    C.byref(m)))
+    return q
+
+
+def adjustPValues(p, method="BH", n_tests=None, as_device=False):
+    """R's p.adjust on the GPU (include/epihip.h, epi_p_adjust_dev): the p-values adjusted for the number of tests by
+    `method`, one of "holm", "hochberg", "bonferroni", "BH", "BY", "fdr" (= "BH") and "none"; `hommel` is not built.  p: an
+    array-like or a device tensor of floats; NaN is NA, stays NaN and is not counted as a test; any other value outside
+    [0, 1] is an error.  n_tests: R's `n`, the number of tests when it is larger than the number of p-values given.
+    Returns float64 of p's length, a device tensor with as_device."""
+    code, n_tests = _p_adjust_args(method, n_tests)
+    q = _p_adjust(_p_values(p, "p"), code, n_tests)
+    return q if as_device else q.cpu().numpy()
+
+
+def adjustReport(report, method="BH", column="p", name="q", n_tests=None):
+    """The Report with one more float64 column `name`: its `column` adjusted by adjustPValues over the table's rows -- a
+    device tensor when `column` is one, else numpy.  For the tables of compareCytosineReports and generateDmrReport (p)
+    and of generateVcfReport ("FEp+", "FEp-").  Levels and attributes such as `ncommon` are kept."""
+    code, n_tests = _p_adjust_args(method, n_tests)
+    if not isinstance(report, Report) or not isinstance(column, str) or column not in report:
+        raise ValueError("'report' should be a Report with the column %r" % (column,))
+    if not isinstance(name, str) or not name or name in report:
+        raise ValueError("'name' should be the name of a column the report does not have yet")
+    p = _p_values(report[column], column)
+    on_device = hasattr(report[column], "is_cuda")
+    q = _p_adjust(p, code, n_tests)
+    out = Report(dict(report), report.levels["rname"])
+    out.__dict__.update({k: v for k, v in report.__dict__.items() if k != "levels"})
+    out.levels = dict(report.levels)
+    out[name] = q if on_device else q.cpu().numpy()
+    return out
 
 
 PATTERN_LEVELS = ("NA1", "H", "A", "C", "NA5", "X", "Z", "NA8", "NA9", "h", "G", "T", "N", "x", "z", "NA16")   # :192-195
@@ -900,7 +979,7 @@ def compareCytosineReports(bam_a, bam_b, report_file=None, threshold_reads=True,
     arguments, joined on the device over the cytosines both have (same position, strand and context) and that are covered
     at least min_coverage times in either.  Columns: rname, strand, pos, context, meth_a, unmeth_a, meth_b, unmeth_b,
     beta_a, beta_b, delta_beta (b minus a) and p, the two-sided Fisher exact p-value of (meth_a unmeth_a / meth_b unmeth_b);
-    no p-value is adjusted for the number of tests.  Both inputs go through preprocessBam with the same preprocess_args
+    no p-value is adjusted for the number of tests (adjustReport does that).  Both inputs go through preprocessBam with the same preprocess_args
     and must have the same sequence names.  The Report's `ncommon` is the number of common cytosines.  The reference has
     no such report."""
     rep = _cytosine_comparison(bam_a, bam_b, threshold_reads, threshold_context, min_context_sites, min_context_beta,
@@ -921,6 +1000,24 @@ def generateDmrReport(bam_a, bam_b, report_file=None, threshold_reads=True, thre
     cmp_ = _cytosine_comparison(bam_a, bam_b, threshold_reads, threshold_context, min_context_sites, min_context_beta,
                                 max_outofcontext_beta, report_context, min_coverage, preprocess_args)
     rep = rcpp_cx_compare_regions(cmp_, *args, as_device=True)
+    rep.ncommon = cmp_.ncommon
+    return _deliver(rep, report_file, gzip, as_device)
+
+
+def generateAdjustedDmrReport(bam_a, bam_b, report_file=None, threshold_reads=True, threshold_context=None, min_context_sites=2,
+                              min_context_beta=0.5, max_outofcontext_beta=0.1, report_context=None, min_coverage=1, gzip=False,
+                              verbose=False, as_device=False, max_q=0.05, min_delta_beta=0.1, max_gap=500, min_sites=3,
+                              p_adjust="BH", **preprocess_args):
+    """generateDmrReport on adjusted p-values: the comparison of compareCytosineReports with the same arguments, its p
+    adjusted over its rows by `p_adjust` (adjustPValues' methods) into q, and the regions of generateDmrReport formed on
+    q <= max_q.  Columns: generateDmrReport's, and q: the regions' pooled p adjusted over the reported regions by the same
+    method.  The Report's `ncommon` is the number of common cytosines."""
+    args = _region_args(max_q, min_delta_beta, max_gap, min_sites, "max.q")
+    _p_adjust_args(p_adjust, None, "p.adjust")
+    cmp_ = _cytosine_comparison(bam_a, bam_b, threshold_reads, threshold_context, min_context_sites, min_context_beta,
+                                max_outofcontext_beta, report_context, min_coverage, preprocess_args)
+    rep = rcpp_cx_compare_regions(adjustReport(cmp_, p_adjust), *args, as_device=True, significance="q")
+    rep = adjustReport(rep, p_adjust)
     rep.ncommon = cmp_.ncommon
     return _deliver(rep, report_file, gzip, as_device)
 

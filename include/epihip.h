@@ -591,8 +591,8 @@ int epi_fisher_exact_dev(epi_engine *e, const int32_t *d_a, const int32_t *d_b, 
  *            first row, end = pos of the last, nsites, direction (+1: b above a, -1).  Five double: beta_a and beta_b pooled
  *            as sum(meth) / sum(meth + unmeth) with 64-bit integer sums, delta_beta = pooled b - a, mean_delta_beta = the
  *            mean of the rows' delta_beta, summed in ascending row order by one thread, p = the Fisher test of the pooled
- *            table (64-bit cells).  Capacity as above (*nregion_out: the count needed).  No p-value is adjusted for the
- *            number of tests. */
+ *            table (64-bit cells).  Capacity as above (*nregion_out: the count needed).  Neither call adjusts a p-value for
+ *            the number of tests: epi_p_adjust_dev (below) does that, for a table's p column or a region table's. */
 int epi_cx_compare_dev(epi_engine *e, const int32_t *const d_a[6], int64_t na, const int32_t *const d_b[6], int64_t nb,
                        int32_t min_coverage, int32_t *const d_icols[8], double *const d_dcols[4], int64_t cap,
                        void *stream, int64_t *ncommon_out, int64_t *nrow_out);
@@ -600,6 +600,38 @@ int epi_cx_compare_regions_dev(epi_engine *e, const int32_t *const d_icols[8], c
                                double max_p, double min_delta_beta, int32_t max_gap, int32_t min_sites,
                                int32_t *const d_ricols[5], double *const d_rdcols[5], int64_t cap, void *stream,
                                int64_t *nregion_out);
+
+/* Multiple-testing correction of a column of p-values on the device: R's p.adjust without `hommel`.  The reference has no
+ * such call.  Stateless, like epi_cx_compare_dev: it reads and writes device columns of the caller, holds its scratch
+ * (about 24 bytes per row for the sort's two buffers and 8 bytes per row of terms) for the length of the call, touches no
+ * batch and synchronises `stream`.
+ *  Values    d_p holds n doubles.  NaN is NA: the row is not a test and its q is NaN.  -0.0 counts as 0.0.  Any other value
+ *            outside [0, 1] (negative, above 1, +-inf): EPI_ERR_ARG, and nothing is written; the check runs on the device.
+ *            m = the number of values that are not NaN, returned in *nvalid_out.  N = n_tests when n_tests > 0, and then
+ *            n_tests >= m, else EPI_ERR_ARG (R's p.adjust(n =)); otherwise N = m.  n == 0 or m == 0: nothing is computed, q
+ *            is all NaN.  n >= 2^31 or n_tests >= 2^31: EPI_ERR_ARG.  d_q == d_p (in place) is allowed.
+ *  Order     d_order (may be NULL) receives n entries: d_order[r] is the row with ascending rank r, in the stable ascending
+ *            order of p with NaN last -- numpy's argsort(p, kind="stable").
+ *  Methods   s_r: the r-th smallest valid p, r = 1 .. m.  All arithmetic is fp64, each term in exactly this operation order:
+ *              EPI_PADJ_NONE        t_r = s_r
+ *              EPI_PADJ_BONFERRONI  t_r = N * s_r
+ *              EPI_PADJ_HOLM        t_r = max over j <= r of (N + 1 - j) * s_j
+ *              EPI_PADJ_HOCHBERG    t_r = min over j >= r of (N + 1 - j) * s_j
+ *              EPI_PADJ_BH          t_r = min over j >= r of (N / j) * s_j
+ *              EPI_PADJ_BY          t_r = min over j >= r of ((c * N) / j) * s_j, c = the sum over k = 1 .. N of 1.0 / k,
+ *                                   summed in ascending k in fp64 by this function on the host, once per call
+ *            and q = min(1, t_r), written to the row the rank came from.  N + 1 - j is an integer, converted exactly; every
+ *            term is one correctly rounded division and / or multiplication (the library is built without fast-math and
+ *            without contraction), minimum and maximum are exact: no launch shape and no order among equal values enters a
+ *            result, and results compare bit for bit with a sequential evaluation. */
+#define EPI_PADJ_NONE        0
+#define EPI_PADJ_BONFERRONI  1
+#define EPI_PADJ_HOLM        2
+#define EPI_PADJ_HOCHBERG    3
+#define EPI_PADJ_BH          4
+#define EPI_PADJ_BY          5
+int epi_p_adjust_dev(epi_engine *e, const double *d_p, int64_t n, int32_t method, int64_t n_tests, double *d_q,
+                     int32_t *d_order, void *stream, int64_t *nvalid_out);
 
 /* rcpp_extract_patterns (src/rcpp_extract_patterns.cpp:26-211; caller .getPatterns, R/internal.R:683-714):
  * methylation patterns of the reads overlapping one target.  Library-owned host table: per pattern strand, start,
