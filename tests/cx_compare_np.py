@@ -1,7 +1,9 @@
 """Plain restatements (loops and numpy) of the cytosine report comparison and its regions as include/epihip.h defines them
 (epi_cx_compare_dev, epi_cx_compare_regions_dev), the hand-written tables and the Fisher tables the tests of both share.
-The p-values of the restatement are the host epi_fisher_exact's, which test_vcf_host.py pins against scipy.  Test
-infrastructure only; treat what the functions return as read-only."""
+The p-values of the restatement are the host epi_fisher_exact's, which test_vcf_host.py pins against scipy (cells below
+30 000) and test_cx_compare_host.py against exact_fisher, the same rule in exact fractions or 60-digit arithmetic (cells up
+to 2^31 - 1); pooled cells of a region that pass int32 take exact_fisher's p.  Test infrastructure only; treat what the
+functions return as read-only."""
 import fractions
 import functools
 
@@ -59,8 +61,43 @@ def join_np(a, b, min_coverage=1):
     return out
 
 
+def pack_key(t):
+    """(rname, pos, strand) of a CX table as one uint64 that sorts as the triple does: 31 + 31 + 2 bits."""
+    r, p, s = (np.asarray(t[k], np.int64) for k in ("rname", "pos", "strand"))
+    assert r.size == 0 or (min(r.min(), p.min(), s.min()) >= 0 and s.max() < 4)
+    return (r.astype(np.uint64) << np.uint64(33)) | (p.astype(np.uint64) << np.uint64(2)) | s.astype(np.uint64)
+
+
+def join_vec(a, b, min_coverage=1):
+    """join_np without the loop (np.searchsorted on pack_key), for tables of a million rows; both tables sorted.  Equal
+    tables have equal p: the host Fisher test runs once per distinct table."""
+    ka, kb = pack_key(a), pack_key(b)
+    j = np.minimum(np.searchsorted(kb, ka), max(kb.size - 1, 0))
+    if kb.size:
+        common = (kb[j] == ka) & (np.asarray(b["context"])[j] == np.asarray(a["context"]))
+    else:
+        common = np.zeros(ka.size, bool)
+    lo = max(int(min_coverage), 1)
+    i = np.flatnonzero(common)
+    j = j[i]
+    cells = np.stack([np.asarray(t[k], np.int64)[x] for t, x in ((a, i), (b, j)) for k in ("meth", "unmeth")], 1).reshape(-1, 4)
+    keep = (cells[:, 0] + cells[:, 1] >= lo) & (cells[:, 2] + cells[:, 3] >= lo)
+    i, cells = i[keep], cells[keep]
+    out = {k: np.asarray(a[k])[i].astype(np.int32) for k in CX[:4]}
+    out.update({k: cells[:, c].astype(np.int32) for c, k in enumerate(CMP_INT[4:])})
+    with np.errstate(invalid="ignore", divide="ignore"):
+        out["beta_a"] = cells[:, 0].astype(np.float64) / (cells[:, 0] + cells[:, 1]).astype(np.float64)
+        out["beta_b"] = cells[:, 2].astype(np.float64) / (cells[:, 2] + cells[:, 3]).astype(np.float64)
+    out["delta_beta"] = out["beta_b"] - out["beta_a"]
+    distinct, inverse = np.unique(cells, axis=0, return_inverse=True)
+    out["p"] = host_fisher(*distinct.T)[inverse.reshape(-1)] if cells.size else np.zeros(0, np.float64)
+    out["ncommon"] = int(common.sum())
+    return out
+
+
 def regions_np(t, max_p, min_delta_beta, max_gap, min_sites):
-    """The regions of the comparison table t (dict of the ten columns, `cells`: the pooled tables); one sequential pass."""
+    """The regions of the comparison table t (dict of the ten columns, `cells`: the pooled tables); one sequential pass.
+    p is the host epi_fisher_exact's where the pooled cells fit int32 and exact_fisher's, rounded to a double, elsewhere."""
     n = t["pos"].size
     delta, p = np.asarray(t["delta_beta"], np.float64), np.asarray(t["p"], np.float64)
 
@@ -95,7 +132,9 @@ def regions_np(t, max_p, min_delta_beta, max_gap, min_sites):
         beta_a, beta_b = np.float64(ma) / np.float64(ma + ua), np.float64(mb) / np.float64(mb + ub)
         flt[r, :4] = (beta_a, beta_b, beta_b - beta_a, np.float64(total) / np.float64(j - i))
         cells[r] = (ma, ua, mb, ub)
-    flt[:, 4] = host_fisher(*cells.T) if len(runs) else 0.0
+    wide = (cells >= 2 ** 31).any(axis=1)                  # a pooled cell beyond int32: the host entry point cannot take it
+    flt[~wide, 4] = host_fisher(*cells[~wide].T) if np.any(~wide) else 0.0
+    flt[wide, 4] = [float(exact_fisher(*row)) for row in cells[wide].tolist()]
     out = {k: ints[:, i].astype(np.int32) for i, k in enumerate(DMR_INT)}
     out.update({k: flt[:, i].copy() for i, k in enumerate(DMR_FLOAT)})
     out["cells"] = cells                                   # the pooled tables (not a column of the report)
@@ -241,6 +280,99 @@ def tie_band_distance(table, exact_below=400):
     return float(min(abs(ratio(k) - mpband) for k in near if lo <= k <= hi))
 
 
+# Tables with cells near 2^31 on both sides: x / n of dbinom_raw is within 1e-9 of 1 there.  Kept out of LARGE_TABLES
+# (the `fisher_cases` of the device-against-host tests stay as they are).
+NEAR_INT32_TABLES = np.asarray([(2 ** 31 - 1, 3, 5, 4), (2 ** 31 - 1, 7, 2147483548, 19), (2000000000, 1000, 1999990000, 1300)], np.int64)
+
+
+def exact_fisher(a, b, c, d, exact_below=400):
+    """The two-sided Fisher p of (a b / c d) by the rule of csrc/fisher_math.hpp, sum of P(k) over P(k) <= P(a) (1 + 1e-7),
+    as a 60-digit mpmath number; cells of any size.  A range hi - lo of at most exact_below: exact fractions throughout.
+    Else P(a) from loggamma and the ratio recurrence outwards from a in both directions, past the mode, until a term is
+    below 1e-45 of P(a) (what is left out is below 1e-45 of p per term, P being log-concave).  When even
+    (hi - lo + 1) P(a) (1 + 1e-7), which bounds p from above, is below 1e-400 the result is 0: no double holds it, and
+    walking from a to the mode could take 2^32 steps."""
+    import mpmath
+    mp = mpmath.mp.clone()
+    mp.dps = 60
+    a, b, c, d = int(a), int(b), int(c), int(d)
+    assert min(a, b, c, d) >= 0
+    n1, n2, m = a + b, c + d, a + c
+    lo, hi = max(0, m - n2), min(m, n1)
+    if lo == hi:
+        return mp.mpf(1)
+    band = fractions.Fraction(10 ** 7 + 1, 10 ** 7)
+    if hi - lo <= exact_below:
+        r = _ratios_exact(n1, n2, m, lo, hi, a)
+        p = sum(v for v in r.values() if v <= band) / sum(r.values())
+        return mp.mpf(p.numerator) / mp.mpf(p.denominator)
+
+    def logc(n, k):
+        return mp.loggamma(n + 1) - mp.loggamma(k + 1) - mp.loggamma(n - k + 1)
+
+    log_pa = logc(n1, a) + logc(n2, m - a) - logc(n1 + n2, m)
+    mpband = mp.mpf(band.numerator) / band.denominator
+    if log_pa + mp.log((hi - lo + 1) * mpband) < mp.log(mp.mpf(10)) * -400:
+        return mp.mpf(0)
+    stop = mp.mpf(10) ** -45
+    total = mp.mpf(1)                                        # k = a itself
+    r, x = mp.mpf(1), a
+    while x < hi and r >= stop:
+        r = r * ((n1 - x) * (m - x)) / ((x + 1) * (n2 - m + x + 1))
+        x += 1
+        if r <= mpband:
+            total += r
+    r, x = mp.mpf(1), a
+    while x > lo and r >= stop:
+        r = r * (x * (n2 - m + x)) / ((n1 - x + 1) * (m - x + 1))
+        x -= 1
+        if r <= mpband:
+            total += r
+    return total * mp.exp(log_pa)
+
+
+def exact_rel_error(got, exact):
+    """|got - exact| / exact of a double against an exact_fisher value, as a float."""
+    return float(abs(type(exact)(float(got)) - exact) / exact)
+
+
+def exact_cases():
+    """The tables compared with exact arithmetic: LARGE_TABLES, NEAR_INT32_TABLES and every 7th of small_tables()."""
+    return np.concatenate([LARGE_TABLES.astype(np.int64), NEAR_INT32_TABLES, small_tables()[::7].astype(np.int64)])
+
+
+EXACT_EXCLUDED = [(2000, 0, 0, 2000), (0, 5000, 5000, 0), (900, 0, 1, 900), (1000000, 3, 5, 1000000)]   # exact p below 1e-280
+
+
+@functools.lru_cache(maxsize=None)
+def exact_values():
+    """(tables, exact_fisher of each, compared: exact p at least 1e-280) of exact_cases(); computed once, about a second."""
+    t = exact_cases()
+    exact = [exact_fisher(*row) for row in t.tolist()]
+    return t, exact, np.asarray([e >= 1e-280 for e in exact])
+
+
+def worst_exact_error(p, what):
+    """The largest relative error of the doubles p against exact_values() over the compared tables, printed, with its
+    table; exactly 1.0 is required on degenerate margins."""
+    t, exact, compared = exact_values()
+    assert [tuple(row) for row in t[~compared].tolist()] == EXACT_EXCLUDED
+    p = np.asarray(p, np.float64)
+    assert p.shape == (len(t),) and np.all(p[degenerate(t)] == 1.0) and np.all(p[~compared] < 1e-279)
+    rel = np.asarray([exact_rel_error(v, e) if c else 0.0 for v, e, c in zip(p, exact, compared)])
+    worst = int(rel.argmax())
+    print("largest relative error of the %s p against exact arithmetic over %d tables: %.3e at %s" %
+          (what, int(compared.sum()), rel[worst], tuple(t[worst].tolist())))
+    return rel, t
+
+
+# The largest relative error of the host epi_fisher_exact against exact_fisher over exact_cases(), as
+# test_cx_compare_host.py::test_fisher_host_against_exact_arithmetic prints it: at (480, 20, 100, 300), p = 9e-122.  The
+# bound is 8 times that, the margin of the device-against-host RTOL.
+EXACT_MEASURED_REL = 1.003e-13
+EXACT_RTOL = 8 * EXACT_MEASURED_REL
+
+
 def compare_p(got, want, tables, rtol):
     """Device p-values against the host's: NaN where the host has NaN, exactly 1.0 on degenerate margins, exactly equal
     where the host has 0.0, within 1e-300 absolute in the denormal range and within rtol relative elsewhere.  Returns
@@ -309,3 +441,75 @@ def random_comparison(rng, n, run_mean=6):
         out[k] = cells[:, i].astype(np.int32)
     out.update(beta_a=beta_a, beta_b=beta_a + delta, delta_beta=delta, p=p)
     return out
+
+
+def random_cx_vec(rng, n, npos, nrname=3, depth=40):
+    """random_cx without the loop: n distinct keys of nrname x npos positions x 2 strands, drawn at once."""
+    code = np.sort(rng.choice(nrname * npos * 2, n, replace=False))
+    out = {"rname": 1 + code // (2 * npos), "strand": 1 + code % 2, "pos": 1 + code // 2 % npos,
+           "context": np.where(rng.random(n) < 0.05, 5, 6), "meth": rng.integers(0, depth, n), "unmeth": rng.integers(0, depth, n)}
+    return {k: np.ascontiguousarray(out[k]).astype(np.int32) for k in CX}
+
+
+def stretches_comparison(rng, stretches):
+    """A comparison table on one rname made of (length, state) stretches: state +1 / -1 rows are significant in that
+    direction (p = 0.01), state 0 rows are not (p = 0.5, delta_beta 0); neighbours 1 .. 29 bases apart."""
+    n = sum(ln for ln, _ in stretches)
+    state = np.concatenate([np.full(ln, st, np.int64) for ln, st in stretches]) if stretches else np.zeros(0, np.int64)
+    cells = rng.integers(0, 50, (n, 4)) + 1
+    out = {"rname": np.ones(n, np.int32), "strand": rng.integers(1, 3, n).astype(np.int32),
+           "pos": (100 + np.cumsum(rng.integers(1, 30, n))).astype(np.int32), "context": np.full(n, 6, np.int32)}
+    for i, k in enumerate(CMP_INT[4:]):
+        out[k] = cells[:, i].astype(np.int32)
+    beta_a = cells[:, 0] / (cells[:, 0] + cells[:, 1])
+    delta = state * rng.uniform(0.2, 0.9, n)
+    out.update(beta_a=beta_a, beta_b=beta_a + delta, delta_beta=delta, p=np.where(state == 0, 0.5, 0.01))
+    return out
+
+
+# Stretches around min_sites = 300 and 5000, longer than a workgroup (256 rows) and than a scan block (4096): the flag
+# walk of a run's first row crosses both.  Directions alternate, so no two stretches merge.
+LONG_STRETCHES = [(ln, (1, -1, 0)[i % 3]) for i, ln in enumerate(
+    (250, 5000, 40, 299, 300, 7, 4999, 301, 1, 6000, 256, 3, 4097, 5001, 9, 700, 298, 2))]
+LONG_MIN_SITES = (300, 5000)
+
+
+def long_stretches_table():
+    return stretches_comparison(np.random.default_rng(23), LONG_STRETCHES)
+
+
+# ---- pooled cells beyond int32 -------------------------------------------------------------------------------------------
+
+M31 = 2 ** 31 - 1
+
+
+def wide_tables():
+    """Hand-made comparison tables whose runs pool 2 to 4 rows with meth_a / meth_b near 2^31 - 1: pooled sums of about
+    4.3e9 and 6.4e9 (and 8.6e9), unmeth_* small, so that hi - lo of the pooled table stays below 40 and exact_fisher is
+    exact fractions.  Each table ends with a run whose pooled table is degenerate (unmeth_* all 0: p is exactly 1) and a
+    run that is (3 M31, 0 / 0, 3 M31): p = 1 / C(6 M31, 3 M31) underflows to exactly 0.  name -> (table, regions_np
+    arguments).  delta_beta and p of the rows are set by hand, as a region pass reads them."""
+    def table(runs):
+        # runs of (delta_beta, [(meth_a, unmeth_a, meth_b, unmeth_b), ...]); one insignificant row between two runs
+        rows = []
+        for delta, cells in runs:
+            rows += [(delta, 0.01) + c for c in cells] + [(0.0, 0.5, 5, 5, 5, 5)]
+        n = len(rows)
+        m = np.asarray([r[2:] for r in rows], np.int64)
+        t = {"rname": np.ones(n, np.int32), "strand": np.asarray([1 + i % 2 for i in range(n)], np.int32),
+             "pos": np.arange(10, 10 + 7 * n, 7, dtype=np.int32), "context": np.full(n, 6, np.int32)}
+        t.update({k: m[:, i].astype(np.int32) for i, k in enumerate(CMP_INT[4:])})
+        with np.errstate(invalid="ignore", divide="ignore"):
+            t.update(beta_a=m[:, 0] / (m[:, 0] + m[:, 1]), beta_b=m[:, 2] / (m[:, 2] + m[:, 3]))
+        t.update(delta_beta=np.asarray([r[0] for r in rows], np.float64), p=np.asarray([r[1] for r in rows], np.float64))
+        return t
+
+    tail = [(0.3, [(M31, 0, M31 - 5, 0), (M31 - 1, 0, M31, 0), (M31, 0, M31, 0)]),     # degenerate: exactly 1
+            (-0.9, [(M31, 0, 0, M31)] * 3)]                                            # underflow: exactly 0
+    return {
+        "two_and_three_rows": (table([(0.3, [(M31, 3, M31 - 100, 11), (M31 - 7, 2, M31, 9)]),
+                                      (-0.4, [(M31, 9, M31, 1), (M31 - 1, 12, M31 - 2, 0), (M31, 8, M31 - 3, 2)])] + tail), (0.05, 0.1, 50, 2)),
+        "four_rows_and_a_one_sided_run": (table([(0.2, [(M31, 1, M31, 6), (M31, 0, M31, 9), (M31, 2, M31, 5), (M31 - 9, 3, M31, 7)]),
+                                                 (-0.2, [(M31, 5, 17, 0), (M31, 7, 4, 1), (M31, 6, 9, 0)]),      # meth_a alone is wide
+                                                 (0.5, [(9, 1, M31, 2), (11, 0, M31, 0), (5, 1, M31, 1)])] + tail), (0.05, 0.1, 50, 3)),
+    }

@@ -1,8 +1,9 @@
 """compareCytosineReports / generateDmrReport / fisherExact on the host side: the exported symbols, the functions' signatures,
 argument checks before any I/O, the sequence-name check before anything touches a device, the loud failure without a
 device (join, Fisher test and regions run on the GPU; there is no CPU path), the numpy restatement the GPU tests compare
-against on a hand-written table (tests/cx_compare_np.py), and that none of the Fisher tables of the GPU test sits so close
-to the tie band that a few ulp in P could move a table from one side to the other."""
+against on a hand-written table (tests/cx_compare_np.py), that none of the Fisher tables of the GPU test sits so close
+to the tie band that a few ulp in P could move a table from one side to the other, the host Fisher test against exact
+arithmetic, and the restatements and tables that test_gpu_cx_compare_seams.py relies on."""
 import ctypes as C
 import inspect
 import os
@@ -199,3 +200,85 @@ def test_fisher_host_values_of_the_listed_tables():
     assert large[(2000, 0, 0, 2000)] == 0.0 and large[(0, 5000, 5000, 0)] == 0.0
     assert large[(37, 37, 37, 37)] == 1.0 and 0 < large[(2 ** 31 - 1, 3, 5, 4)] < 1 and 0 < large[(1000000, 999000, 998500, 1000000)] < 1
     assert p[np.flatnonzero((t == (3, 1, 1, 3)).all(axis=1))[0]] == pytest.approx(X.KAT_P_3113, rel=1e-12)
+
+
+def test_fisher_host_against_exact_arithmetic():
+    """The host epi_fisher_exact against a 60-digit sum by the same rule (cx_compare_np.exact_fisher: exact fractions for a
+    range of at most 400 tables, loggamma and the ratio recurrence beyond) on LARGE_TABLES, three tables with cells near
+    2^31 and every 7th table with cells 0 .. 6.  Device and host share fisher_math.hpp, so this is the one place where a
+    mistake in the header shows; the scipy pin of test_vcf_host.py stops at cells of 30 000.  Four tables whose exact p is
+    below 1e-280 are left out, as there.  Measured: largest relative error 1.002e-13, at (480, 20, 100, 300) with
+    p = 9.06e-122 (the exponent scales it); the near-2^31 tables are at 4.9e-15, 7.1e-16 and 2.5e-15.  The bound is 8 times
+    the measured figure, 8.02e-13.  With log1p(-x / n) in dbinom_raw's lf, as it was, the near-2^31 tables were off by
+    2.1e-9, 1.2e-9 and 1.0e-10."""
+    t, _, _ = X.exact_values()
+    rel, t = X.worst_exact_error(X.host_fisher(*t.T), "host")
+    for row in X.NEAR_INT32_TABLES.tolist():
+        i = int(np.flatnonzero((t == row).all(axis=1))[-1])
+        print("  %s: %.3e" % (tuple(row), rel[i]))
+        assert rel[i] <= X.EXACT_RTOL, (row, rel[i])
+    assert rel.max() <= X.EXACT_RTOL, (rel.max(), t[int(rel.argmax())].tolist())
+
+
+def test_exact_fisher_on_known_values():
+    """The reference itself: the hand-computed (3 1 / 1 3), both of its paths on one table, its zero and its one."""
+    assert float(X.exact_fisher(3, 1, 1, 3)) == pytest.approx(X.KAT_P_3113, rel=1e-15)
+    for row in ((200, 100, 90, 250), (12, 1, 3, 11), (600, 700, 800, 500)):
+        by_fractions, by_loggamma = X.exact_fisher(*row, exact_below=10 ** 9), X.exact_fisher(*row, exact_below=0)
+        assert abs(by_loggamma / by_fractions - 1) < 1e-40
+    assert X.exact_fisher(0, 4, 0, 8) == 1 and X.exact_fisher(37, 37, 37, 37) == 1
+    assert X.exact_fisher(3 * X.M31, 0, 0, 3 * X.M31) == 0 and X.exact_fisher(2000, 0, 0, 2000) == 0
+    assert all(X.tie_band_distance(row) > 1e-9 for row in X.NEAR_INT32_TABLES)
+
+
+def test_vectorised_join_equals_the_loop():
+    """join_vec (searchsorted on a packed key, one Fisher test per distinct table), which the million-row GPU test compares
+    with, against join_np on tables small enough for the loop."""
+    rng = np.random.default_rng(41)
+    empty = X.cx_table([])
+    edge = X.cx_table([(0, 0, 0, 6, 1, 2), (X.M31, 1, X.M31, 6, X.M31, X.M31), (X.M31, 2, X.M31, 5, 0, 0)])
+    pairs = [(X.KAT_A, X.KAT_B), (X.KAT_B, X.KAT_A), (empty, X.KAT_A), (X.KAT_A, empty), (empty, empty), (edge, edge), (X.KAT_A, edge),
+             (X.random_cx(rng, 1003, 400), X.random_cx(rng, 997, 400)), (X.random_cx_vec(rng, 4097, 3000, depth=7), X.random_cx_vec(rng, 700, 3000, depth=7))]
+    for a, b in pairs:
+        assert X.is_sorted(a) and X.is_sorted(b)
+        for min_coverage in (0, 1, 6, 25, X.M31):
+            want, got = X.join_np(a, b, min_coverage), X.join_vec(a, b, min_coverage)
+            assert got["ncommon"] == want["ncommon"]
+            for k in X.CMP_INT + X.CMP_FLOAT:
+                assert got[k].dtype == want[k].dtype and np.array_equal(got[k], want[k], equal_nan=True), k
+    assert X.join_vec(edge, edge, X.M31)["pos"].tolist() == [X.M31]          # coverage 2^32 - 2 is not wrapped
+
+
+def test_long_stretches_have_what_the_gpu_test_needs():
+    """The table of the min_sites = 300 and 5000 test: at least 3 regions reported and at least 3 runs too short for each."""
+    t = X.long_stretches_table()
+    runs = X.regions_np(t, 0.05, 0.1, 50, 1)
+    assert sorted(runs["nsites"].tolist()) == sorted(ln for ln, st in X.LONG_STRETCHES if st)
+    for min_sites in X.LONG_MIN_SITES:
+        r = X.regions_np(t, 0.05, 0.1, 50, min_sites)
+        assert r["rname"].size >= 3 and runs["rname"].size - r["rname"].size >= 3
+        assert r["nsites"].tolist() == [v for v in runs["nsites"].tolist() if v >= min_sites]
+    starts = np.cumsum([0] + [ln for ln, _ in X.LONG_STRETCHES])
+    assert len(set((starts // 256).tolist())) > 10 and len(set((starts // 4096).tolist())) > 5
+
+
+def test_restatement_on_pooled_cells_beyond_int32():
+    """regions_np on the hand-made wide tables: pooled cells of 2^31 and more, p from exact_fisher there, exactly 1 on the
+    degenerate run and exactly 0 on the run whose p underflows; a region that fits int32 keeps the host's p."""
+    seen = set()
+    for name, (t, args) in sorted(X.wide_tables().items()):
+        r = X.regions_np(t, *args)
+        cells = r["cells"]
+        assert cells.dtype == np.int64 and cells.shape[0] >= 4 and np.all(cells.max(axis=1) >= 2 ** 31)
+        assert 2 <= r["nsites"].min() and r["nsites"].max() <= 4
+        assert r["p"][-2] == 1.0 and bool(X.degenerate(cells)[-2]) and r["p"][-1] == 0.0
+        assert np.all((r["p"][:-2] > 1e-30) & (r["p"][:-2] < 1))
+        n1, n2, m = cells[:, 0] + cells[:, 1], cells[:, 2] + cells[:, 3], cells[:, 0] + cells[:, 2]
+        assert np.all((np.minimum(m, n1) - np.maximum(0, m - n2))[:-1] < 40)
+        assert r["beta_a"][0] == cells[0, 0] / (cells[0, 0] + cells[0, 1])
+        seen.update(np.rint(cells.max(axis=1) / X.M31).astype(int).tolist())
+    assert seen == {2, 3, 4}                               # pooled sums of about 4.3e9, 6.4e9 and 8.6e9
+    # below 2^31 nothing changes: the host's p, bit for bit
+    small = X.random_comparison(np.random.default_rng(5), 300)
+    r = X.regions_np(small, 0.05, 0.1, 300, 1)
+    assert np.array_equal(r["p"], X.host_fisher(*r["cells"].T))

@@ -5,11 +5,16 @@ division or subtraction of integers each) and mean_delta_beta (a sequential sum 
 
 p compares with the host epi_fisher_exact: NaN where it has NaN, exactly 1.0 on degenerate margins, exactly equal where it
 returns 0.0, within 1e-300 absolute in the denormal range, and elsewhere within RTOL relative.  Device and host run the
-same operations in the same order (csrc/fisher_math.hpp); what differs is lgamma / log / log1p / exp, by ulps that the size
+same operations in the same order (csrc/fisher_math.hpp); what differs is lgamma / log / exp, by ulps that the size
 of the exponent scales.  RTOL is 8 times the largest relative difference measured over the tables of
-test_fisher_kernel_against_the_host on an MI355X (profiles/cx_compare.txt): measured 1.405e-14, RTOL = 1.124e-13.  A
+test_fisher_kernel_against_the_host on an MI355X (profiles/cx_compare.txt): measured 1.405e-14, RTOL = 1.124e-13 (measured
+again, and the same, after dbinom_raw's lf became log((n - x) / n)).  A
 difference above 1e-9 would be a wrong port, not an imprecise one (the tie band is 1e-7 wide;
-test_cx_compare_host.py::test_fisher_tables_stay_clear_of_the_tie_band shows no table of the list can change sides)."""
+test_cx_compare_host.py::test_fisher_tables_stay_clear_of_the_tie_band shows no table of the list can change sides).
+What the shared header itself gets wrong shows in neither side of this comparison: test_gpu_cx_compare_seams.py and
+test_cx_compare_host.py hold both against exact arithmetic.
+
+The last three tests run the calls in sequence on the `samples` fixture: they keep no state and leave no report changed."""
 import ctypes as C
 
 import numpy as np
@@ -61,12 +66,12 @@ def assert_join_equal(got, want):
     X.compare_p(got["p"], want["p"], np.stack([want[k] for k in X.CMP_INT[4:]], 1), RTOL)
 
 
-def assert_regions_equal(got, want):
+def assert_regions_equal(got, want, rtol=RTOL):
     for k in X.DMR_INT:
         assert got[k].dtype == np.int32 and np.array_equal(got[k], want[k]), k
     for k in ("beta_a", "beta_b", "delta_beta", "mean_delta_beta"):
         assert np.array_equal(bits(got[k]), bits(want[k])), k
-    X.compare_p(got["p"], want["p"], want["cells"], RTOL)
+    X.compare_p(got["p"], want["p"], want["cells"], rtol)
 
 
 # ---- the Fisher kernel ---------------------------------------------------------------------------------------------------
@@ -360,3 +365,98 @@ def test_end_to_end(ea, samples, tmp_path, threshold_reads):
     for x, (cx, het) in zip((a, b), before):
         H.assert_reports_equal(ea.generateHeterogeneityReport(x, window_sites=3), het, float_cols=("beta", "epipolymorphism", "entropy", "pdr"))
         H.assert_reports_equal(ea.generateCytosineReport(x, **cx_kw), cx)
+
+
+# ---- calls in sequence -----------------------------------------------------------------------------------------------------
+
+def _assert_bitwise(got, want):
+    assert list(got) == list(want) and got.ncommon == want.ncommon
+    for k in got:
+        assert got[k].dtype == want[k].dtype and np.array_equal(got[k].view(np.uint8), want[k].view(np.uint8)), k
+
+
+def test_joins_in_sequence_keep_no_state(ea, samples):
+    """The calls are stateless and give their scratch back: a join of 70 001 x 65 537 rows, a join of 6 x 7 rows at once,
+    and the large one again give what they give alone, bit for bit; so do the samples' comparison and a small join."""
+    rng = np.random.default_rng(17)
+    big_a, big_b = X.random_cx_vec(rng, 70001, 15000), X.random_cx_vec(rng, 65537, 15000)
+    first = gpu_join(ea, big_a, big_b, 3)
+    small = gpu_join(ea, BASE, OTHER, 1)
+    again = gpu_join(ea, big_a, big_b, 3)
+    assert first.nrow > 30000 and small.nrow == 3
+    _assert_bitwise(again, first)
+    assert_join_equal(small, X.join_np(BASE, OTHER, 1))
+    assert_join_equal(first, X.join_vec(big_a, big_b, 3))
+    a, b = samples
+    kw = dict(threshold_reads=False, min_coverage=4)
+    alone = ea.compareCytosineReports(a, b, **kw)
+    gpu_join(ea, big_a, big_b, 3)
+    after_big = ea.compareCytosineReports(a, b, **kw)
+    gpu_join(ea, BASE, OTHER, 1)
+    _assert_bitwise(after_big, alone)
+    _assert_bitwise(ea.compareCytosineReports(a, b, **kw), alone)
+
+
+def test_a_sample_against_itself_and_swapped(ea, samples):
+    """(a, a): every table is (m u / m u), p is exactly 1.0 and delta_beta +0.0.  (b, a) against (a, b): the same rows with
+    the two sides exchanged, delta_beta negated bit for bit (0.0 - x: equal betas give +0.0 either way), p within RTOL and
+    not bitwise, the table being transposed."""
+    a, b = samples
+    kw = dict(threshold_reads=False, min_coverage=4)
+    same = ea.compareCytosineReports(a, a, **kw)
+    assert same.nrow > 100 and same.ncommon == ea.generateCytosineReport(a, threshold_reads=False).nrow
+    assert np.all(same["p"] == 1.0) and np.all(bits(same["delta_beta"]) == 0)
+    assert np.array_equal(same["meth_a"], same["meth_b"]) and np.array_equal(same["unmeth_a"], same["unmeth_b"])
+    assert np.array_equal(bits(same["beta_a"]), bits(same["beta_b"]))
+    ab, ba = ea.compareCytosineReports(a, b, **kw), ea.compareCytosineReports(b, a, **kw)
+    assert ab.nrow > 100 and ab.ncommon == ba.ncommon
+    for k in ("rname", "strand", "pos", "context"):
+        assert np.array_equal(ab[k], ba[k]), k
+    for k in ("meth", "unmeth", "beta"):
+        assert np.array_equal(ab[k + "_a"].view(np.uint8), ba[k + "_b"].view(np.uint8)), k
+        assert np.array_equal(ab[k + "_b"].view(np.uint8), ba[k + "_a"].view(np.uint8)), k
+    assert np.array_equal(bits(ba["delta_beta"]), bits(0.0 - ab["delta_beta"]))
+    X.compare_p(ba["p"], ab["p"], np.stack([ab[k] for k in X.CMP_INT[4:]], 1), RTOL)
+
+
+def test_comparison_calls_between_other_reports(ea, samples):
+    """adjustReport and the regions interleaved with the cytosine, heterogeneity and linkage reports of both batches: those
+    are what they were before, and the comparison is what it is alone."""
+    a, b = samples
+    het_floats, link_floats = ("beta", "epipolymorphism", "entropy", "pdr"), ("cov", "r2", "dprime")
+
+    def others(x):
+        return (ea.generateCytosineReport(x, threshold_reads=False), ea.generateHeterogeneityReport(x, window_sites=3),
+                ea.generateLinkageReport(x, max_neighbours=2))
+
+    def check(x, before):
+        cx, het, link = others(x)
+        H.assert_reports_equal(cx, before[0])
+        H.assert_reports_equal(het, before[1], float_cols=het_floats)
+        H.assert_reports_equal(link, before[2], float_cols=link_floats)
+
+    before = [others(x) for x in (a, b)]
+    assert all(r.nrow > 50 for pair in before for r in pair)
+    kw = dict(threshold_reads=False, min_coverage=4)
+    want = X.join_np(before[0][0], before[1][0], 4)
+    want_r = X.regions_np(want, 0.05, 0.2, 30, 3)
+    assert want_r["rname"].size >= 1
+    table = ea.compareCytosineReports(a, b, as_device=True, **kw)
+    check(a, before[0])
+    adjusted = ea.adjustReport(table, "BH")
+    check(b, before[1])
+    regions = ea.rcpp_cx_compare_regions(adjusted, 0.05, 0.2, 30, 3)
+    ea.generateLinkageReport(a, max_neighbours=2)
+    on_q = ea.rcpp_cx_compare_regions(adjusted, 0.2, 0.2, 30, 3, significance="q")
+    check(a, before[0])
+    check(b, before[1])
+    assert_regions_equal(regions, want_r)
+    host = ea.Report({k: v.cpu().numpy() for k, v in table.items()}, table.levels["rname"])
+    host.ncommon = table.ncommon
+    assert_join_equal(host, want)
+    assert np.array_equal(bits(adjusted["q"].cpu().numpy()), bits(ea.adjustPValues(table["p"].cpu().numpy(), "BH")))
+    again = ea.rcpp_cx_compare_regions(ea.adjustReport(ea.compareCytosineReports(a, b, as_device=True, **kw), "BH"), 0.2, 0.2, 30, 3,
+                                       significance="q")
+    assert on_q.nrow >= 1 and list(on_q) == list(again)
+    for k in on_q:
+        assert np.array_equal(on_q[k].view(np.uint8), again[k].view(np.uint8)), k
