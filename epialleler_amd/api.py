@@ -504,6 +504,22 @@ def rcpp_linkage_blocks(df, ctx, max_neighbours, max_distance, max_ooctx_meth_fr
     return _fetch_table(bam, lib.epi_batch_linkage_blocks_fetch_dev, nblock.value, 5, BLOCK_COLUMNS, as_device)
 
 
+FDRP_COLUMNS = ("rname", "strand", "pos", "context", "coverage", "nreads", "npairs", "ndiscordant", "fdrp", "qfdrp")
+
+
+def rcpp_fdrp_report(df, ctx, flank_sites, max_reads, min_overlap, max_distance, max_ooctx_meth_frac, min_reads=2, as_device=False):
+    """Per site of the un-thresholded cytosine report, over the pairs of reads that have a call there (include/epihip.h,
+    epi_batch_fdrp_report_dev): rname, strand, pos, context, coverage, nreads, npairs, ndiscordant (int32), fdrp, qfdrp
+    (float64).  ctx: context letters in both cases, as for rcpp_mhl_report."""
+    lib = _lib.load()
+    bam = _as_bam(df)
+    nrow = C.c_int64(0)
+    _lib.check(lib.epi_batch_fdrp_report_dev(bam.batch(), _lib.enc(ctx), int(flank_sites), int(max_reads), int(min_overlap),
+                                             int(max_distance), float(max_ooctx_meth_frac), int(min_reads), _stream(bam.device),
+                                             C.byref(nrow)))
+    return _fetch_table(bam, lib.epi_batch_fdrp_fetch_dev, nrow.value, 8, FDRP_COLUMNS, as_device)
+
+
 CX_COMPARE_COLUMNS = ("rname", "strand", "pos", "context", "meth_a", "unmeth_a", "meth_b", "unmeth_b", "beta_a", "beta_b", "delta_beta", "p")
 DMR_COLUMNS = ("rname", "start", "end", "nsites", "direction", "beta_a", "beta_b", "delta_beta", "mean_delta_beta", "p")
 
@@ -955,6 +971,31 @@ def generateHaplotypeBlocks(bam, report_file=None, linkage_context=None, max_nei
     c = CONTEXT_TO_BASES[linkage_context]
     rep = rcpp_linkage_blocks(bam, c["ctx_meth"] + c["ctx_unmeth"], max_neighbours, max_distance, max_outofcontext_beta,
                               min_reads, min_r2, min_sites, as_device=as_device)
+    return _deliver(rep, report_file, gzip)
+
+
+def generateFdrpReport(bam, report_file=None, fdrp_context=None, flank_sites=8, max_reads=40, min_overlap=1, max_distance=0,
+                       min_reads=2, max_outofcontext_beta=0.1, gzip=False, verbose=False, as_device=False, **preprocess_args):
+    """FDRP and qFDRP (Scherer et al. 2020, the WSH package) per cytosine of `fdrp_context`: over the pairs of reads that
+    have a call at the cytosine, the fraction of pairs whose calls differ anywhere in the window of `flank_sites` (0 to 31)
+    cytosines on either side (fdrp), and the mean over the pairs of the share of differing calls among the window's
+    cytosines both reads call (qfdrp).  A pair counts when both reads call at least `min_overlap` cytosines of the window;
+    with max_distance > 0 the window holds only cytosines within that many bases.  At most `max_reads` (2 to 64; WSH's
+    sample size of 40 by default) reads per cytosine are compared: those at evenly spaced ranks of the covering reads,
+    not a random draw as in WSH -- and over a window of cytosines, not over the reads' whole overlap.  The sites are those of
+    generateCytosineReport(threshold_reads=False, report_context=fdrp_context), the reads those generateMhlReport keeps
+    under max_outofcontext_beta; cytosines with fewer than max(min_reads, 2) compared reads or without a counted pair are
+    left out.  Columns: rname, strand, pos, context, coverage, nreads, npairs, ndiscordant, fdrp, qfdrp
+    (include/epihip.h has the definitions).  The reference has no such report."""
+    fdrp_context = _match_arg(fdrp_context, _CTX_CHOICES, "fdrp.context")
+    flank_sites = _whole_number(flank_sites, "flank.sites", 0, 31)
+    max_reads = _whole_number(max_reads, "max.reads", 2, 64)
+    min_overlap = _whole_number(min_overlap, "min.overlap", 1, 2 * flank_sites + 1)
+    max_distance = _whole_number(max_distance, "max.distance", 0)
+    bam = preprocessBam(bam, **preprocess_args)
+    c = CONTEXT_TO_BASES[fdrp_context]
+    rep = rcpp_fdrp_report(bam, c["ctx_meth"] + c["ctx_unmeth"], flank_sites, max_reads, min_overlap, max_distance,
+                           max_outofcontext_beta, min_reads, as_device=as_device)
     return _deliver(rep, report_file, gzip)
 
 

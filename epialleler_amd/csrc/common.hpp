@@ -88,10 +88,14 @@ struct SiteScalars {
   uint32_t nrow;           // reported rows: windows, pairs
   uint32_t nblock;         // haplotype blocks
   uint32_t ncommon;        // comparison: sites both batches have
+  uint32_t nwords;         // FDRP: 64-bit words of the rows' packed calls
+  uint32_t unused;
+  unsigned long long ncalls;   // FDRP: calls of the kept rows = (site, row) pairs of the index (zeroed by the report)
 };
+static_assert(sizeof(SiteScalars) == 32 && offsetof(SiteScalars, ncalls) == 24, "SiteScalars layout");
 
-// What the heterogeneity report (heterogeneity.hip), the linkage report and its blocks (linkage.hip) and the heterogeneity
-// comparison (het_compare.hip, on its first batch) keep on a batch: the site table, the counters over it, which rows are
+// What the heterogeneity report (heterogeneity.hip), the linkage report and its blocks (linkage.hip), the heterogeneity
+// comparison (het_compare.hip, on its first batch) and the FDRP report (fdrp.hip) keep on a batch: the site table, the counters over it, which rows are
 // reported and where, and the arguments of the last report that its fetch needs.  het_common.hpp has the data path.
 struct SiteReportState {
   DevBuf cx;               // the site table in CX row order: the un-thresholded CX report's six columns, [6][nsite]
@@ -103,15 +107,24 @@ struct SiteReportState {
   DevBuf back, blen, bmean;       // blocks, by table ordinal: leading linked pairs behind a site; length and mean r^2 at a block's first site
   DevBuf bflag, bout;             // ... by CX row: a block starts here, its output row
   DevBuf cx_all, counts_b;        // comparison: a's CX table before the common one is compacted from it; the counters of b's rows
+  // FDRP (fdrp.hip): the site -> rows index and the rows' packed calls
+  DevBuf frow;             // [6][n rows] u32: first site, sites, calls and words of a row; its first pair and first word (scans)
+  DevBuf fbits;            // [2][nwords] u64: the rows' calls, bit j of a row = its site lo + j: valid, then methylated
+  DevBuf fpair;            // the (site, row) pairs and the sort's scratch; sorted: rows of site g at [site_off[g], site_end[g])
+  DevBuf fsite;            // [2][nsite] u32 site_off, site_end
+  const uint32_t *fdrp_rows = nullptr;   // [ncalls] the sorted rows inside fpair
   int64_t nsite = 0;       // sites of the table the last report counted over (0: it reported nothing, no table is kept)
   int32_t k = 0, D = 0;    // window size / neighbours of the last report
+  int32_t W = 0, max_rows = 0, min_overlap = 0;   // FDRP: flanking sites, rows used per site, overlap a pair needs
   uint32_t min_reads = 1;
   int64_t max_span = 0, max_dist = 0;
   bool blocks = false;     // epi_batch_linkage_blocks_dev has run on the last linkage report ...
   int64_t nblock = 0;      // ... and found this many
   SiteScalars *scalars() const { return scal.as<SiteScalars>(); }
   void release() {
-    for (DevBuf *d : {&cx, &rank, &key, &sctx, &counts, &flag, &out, &scal, &back, &blen, &bmean, &bflag, &bout, &cx_all, &counts_b}) d->release();
+    for (DevBuf *d : {&cx, &rank, &key, &sctx, &counts, &flag, &out, &scal, &back, &blen, &bmean, &bflag, &bout, &cx_all, &counts_b,
+                      &frow, &fbits, &fpair, &fsite})
+      d->release();
   }
 };
 
@@ -193,6 +206,7 @@ enum ReportKind {
   KIND_HET = 6,             // finished heterogeneity report
   KIND_LINK = 7,            // finished linkage report
   KIND_HETCMP = 8,          // finished heterogeneity comparison (on its first batch; the second is left at KIND_NONE)
+  KIND_FDRP = 9,            // finished FDRP report
 };
 }  // namespace epi
 
@@ -397,6 +411,14 @@ int stage_send(epi_engine *eng, int k, void *d_dst, size_t bytes);
 int scan_exclusive_u32(const uint32_t *d_in, uint32_t *d_out, int64_t n, uint32_t *d_total,
                        DevBuf &tmp, hipStream_t s);
 int scan_block_sums_inplace(uint32_t *d_bsum, int64_t nb, uint32_t *d_total, hipStream_t s);
+
+// Stable LSD radix sort of n (64-bit key, 32-bit value) pairs, n < 2^32 (p_adjust.hip has the kernels).  One pass per set bit
+// d of `bytes` (key byte d, least significant first); the pairs start in key[0] / row[0] and bounce between the two buffer
+// pairs, *cur = the one that holds the result.  table and off: radix_sort_blocks(n) * 256 words each; scan_tmp: the
+// scratch of the scan over the table.  Everything is queued on s, nothing is synchronised.
+int64_t radix_sort_blocks(int64_t n);
+int radix_sort_pairs(uint64_t *const key[2], uint32_t *const row[2], uint32_t n, uint32_t bytes, uint32_t *table, uint32_t *off,
+                     DevBuf &scan_tmp, hipStream_t s, int *cur);
 
 // tile index (tiles.hip)
 // queue k_row_stats for a new batch (no sync, no error: per-read functions accept unsorted rows)

@@ -180,7 +180,7 @@ int site_fetch_begin(const char *who, epi_batch *b, ReportKind kind, bool blocks
   *nrow = 0;
   if (!b || !icols || !dcols) return fail(EPI_ERR_ARG, "%s: NULL argument", who);
   const char *what = blocks ? "epi_batch_linkage_blocks_dev" : kind == KIND_HET ? "heterogeneity report" : kind == KIND_LINK ? "linkage report"
-                                                                                                          : "heterogeneity comparison";
+                                                                                     : kind == KIND_FDRP ? "FDRP report" : "heterogeneity comparison";
   if (b->last_kind != kind || (blocks && !b->sites.blocks)) return fail(EPI_ERR_STATE, "%s: no finished %s on this batch", who, what);
   const int64_t n = blocks ? b->sites.nblock : b->last_nrow;
   if (n == 0) return EPI_OK;

@@ -11,8 +11,9 @@
 //           digits is the wave's running count of that digit (one lane per digit stores it, plain LDS stores) plus the
 //           number of lower lanes of the match mask (eight ballots).  No rank comes from what an LDS atomic returns.  The
 //           tile is put into digit order in LDS (keys, then rows, in one 32 KB buffer) and stored from there, so that a
-//           wave's stores run along the digits' runs instead of 64 ways apart.
-//  Terms    k_padj_terms: t_r of the method, in the header's operation order, from the sorted keys; then a device-wide
+//           wave's stores run along the digits' runs instead of 64 ways apart.  The per-byte launch sequence is
+//           radix_sort_pairs (common.hpp), which the FDRP report's site -> rows index (fdrp.hip) calls as well.
+//  Terms   k_padj_terms: t_r of the method, in the header's operation order, from the sorted keys; then a device-wide
 //           inclusive scan of doubles under min or max (k_dscan_reduce, k_dscan_carry, k_dscan_apply: reduce-then-scan as
 //           util.hip's three launches; min and max are exact and associative, so no launch shape enters a result), walking
 //           the ranks downwards for the suffix minimum.
@@ -213,6 +214,32 @@ __global__ __launch_bounds__(PADJ_WG) void k_padj_sort_scatter(const uint64_t *_
   }
 }
 
+int64_t radix_sort_blocks(int64_t n) { return (n + PADJ_SORT_TILE - 1) / PADJ_SORT_TILE; }
+
+int radix_sort_pairs(uint64_t *const key[2], uint32_t *const row[2], uint32_t n, uint32_t bytes, uint32_t *table, uint32_t *off,
+                     DevBuf &scan_tmp, hipStream_t s, int *cur_out) {
+  const int64_t nblk = radix_sort_blocks((int64_t)n);
+  int cur = 0;
+  for (int d = 0; d < 8; d++) {
+    if (!((bytes >> d) & 1u)) continue;
+    prof_begin("padj_hist", s);
+    hipLaunchKernelGGL(k_padj_hist, dim3((unsigned)nblk), dim3(PADJ_WG), 0, s, key[cur], n, 8 * d, (uint32_t)nblk, table);
+    prof_end("padj_hist", s);
+    prof_begin("padj_table_scan", s);
+    const int rc = scan_exclusive_u32(table, off, nblk * 256, nullptr, scan_tmp, s);
+    prof_end("padj_table_scan", s);
+    EPI_TRY(rc);
+    prof_begin("padj_sort_scatter", s);
+    hipLaunchKernelGGL(k_padj_sort_scatter, dim3((unsigned)nblk), dim3(PADJ_WG), 0, s, key[cur], row[cur], n, 8 * d, (uint32_t)nblk,
+                       off, key[cur ^ 1], row[cur ^ 1]);
+    prof_end("padj_sort_scatter", s);
+    cur ^= 1;
+  }
+  EPI_HIP(hipGetLastError());
+  *cur_out = cur;
+  return EPI_OK;
+}
+
 // ---- terms -----------------------------------------------------------------------------------------------------------------
 
 struct PadjTerms {
@@ -406,23 +433,10 @@ static int p_adjust(epi_engine *e, const double *d_p, int64_t n, int32_t method,
   if (n_tests > 0 && n_tests < m) return fail(EPI_ERR_ARG, "%s: n_tests = %lld, below the %lld p-values that are not NA", who, (long long)n_tests, (long long)m);
   const int64_t N = n_tests > 0 ? n_tests : m;
 
+  uint32_t bytes = 0;
+  for (int d = 0; d < 8; d++) if (!h.skip[d]) bytes |= 1u << d;
   int cur = 0;
-  for (int d = 0; d < 8; d++) {
-    if (h.skip[d]) continue;
-    prof_begin("padj_hist", s);
-    hipLaunchKernelGGL(k_padj_hist, dim3((unsigned)nblk_sort), dim3(PADJ_WG), 0, s, key[cur], un, 8 * d, (uint32_t)nblk_sort, table);
-    prof_end("padj_hist", s);
-    prof_begin("padj_table_scan", s);
-    const int rc = scan_exclusive_u32(table, off, nblk_sort * 256, nullptr, scan_tmp, s);
-    prof_end("padj_table_scan", s);
-    EPI_TRY(rc);
-    prof_begin("padj_sort_scatter", s);
-    hipLaunchKernelGGL(k_padj_sort_scatter, dim3((unsigned)nblk_sort), dim3(PADJ_WG), 0, s, key[cur], row[cur], un, 8 * d, (uint32_t)nblk_sort,
-                       off, key[cur ^ 1], row[cur ^ 1]);
-    prof_end("padj_sort_scatter", s);
-    cur ^= 1;
-  }
-  EPI_HIP(hipGetLastError());
+  EPI_TRY(radix_sort_pairs(key, row, un, bytes, table, off, scan_tmp, s, &cur));
 
   const uint32_t um = (uint32_t)m;
   if (m > 0) {

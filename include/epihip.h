@@ -552,6 +552,47 @@ int epi_batch_linkage_blocks_dev(epi_batch *b, double min_r2, int32_t min_sites,
 int epi_batch_linkage_blocks_fetch_dev(epi_batch *b, int32_t *const d_icols[5], double *const d_dcols[1], void *stream);
 int epi_linkage_counter_bytes(int64_t nsites, int max_neighbours, int64_t *bytes_out);
 
+/* FDRP report: the fraction of discordant read pairs (FDRP) and its quantitative form (qFDRP, the mean normalised Hamming
+ * distance of read pairs) per cytosine, the two within-sample heterogeneity scores of the WSH package (Scherer et al.
+ * 2020).  The reference has no such report.  Where every other score of this family is a sum over reads, these are sums
+ * over PAIRS of reads that cover a site.
+ *  ctx       context letters in both cases ("Zz", "XxZz", ...), as for the lMHL report; W = flank_sites, 0 .. 31;
+ *            m = max_reads, 2 .. 64; min_overlap, 1 .. 2W + 1; max_distance >= 0; max_ooctx_meth_frac and min_reads as for
+ *            the heterogeneity report.  Anything out of range: EPI_ERR_ARG before any work.
+ *  Sites, calls and kept rows: exactly as for the heterogeneity report above -- the rows of the un-thresholded CX report of
+ *            the whole batch, ordered by pos per (rname, strand); a call where (x & 7) == the site's context code,
+ *            methylated when x < 8; the lMHL read rule with hmin = 0 and max_ooctx_meth_frac.
+ *  Coverage  c of site g = the kept rows with a call at g.
+ *  Selection the rows that cover g, listed in ascending batch row index: all of them when c <= m, otherwise the m rows at
+ *            ranks floor(j c / m), j = 0 .. m - 1, of that list (the product in 64 bits).  nreads = min(c, m).  The choice is
+ *            deterministic, spread over the whole list, and depends on neither launch shape nor atomic order.
+ *  Window    of g: the sites g - W .. g + W of g's (rname, strand) segment of the table, clipped at the segment's ends; with
+ *            max_distance > 0 only those whose position is within max_distance bases of g's.  g itself is always in it.
+ *  Pairs     (a, b) of used rows, a < b in list order.  o = the window sites at which both rows have a call (o >= 1: both
+ *            call g), h = those of them at which the two calls differ.  The pair counts when o >= min_overlap; then
+ *            npairs += 1, ndiscordant += (h > 0), H[o] += h.
+ *  Scores    float64: fdrp = ndiscordant / npairs; qfdrp = (sum over o = 1 .. 2W + 1 of H[o] / o) / npairs, every integer
+ *            H[o] divided by o and the terms added in ascending o by one thread.  No launch shape enters a result: a
+ *            restatement that performs the same IEEE operations in the same order agrees bit for bit.
+ *  Rows      a site is reported when nreads >= max(min_reads, 2) and npairs >= 1, in CX row order.
+ *  Columns   eight int32 (rname, strand, pos, context, coverage, nreads, npairs, ndiscordant) and two double (fdrp, qfdrp).
+ * Two deviations from WSH are deliberate.  The reads of a deep site are SELECTED DETERMINISTICALLY (evenly spaced ranks)
+ * where WSH draws 40 at random: a report is reproducible.  And two reads are compared over a WINDOW OF SITES around the
+ * cytosine where WSH compares them over their whole overlap in bases: with long reads the whole overlap makes nearly every
+ * pair discordant, and the score of a site would depend on the read length.
+ * Steps and state as for the heterogeneity report: report_dev runs the report (synchronises `stream`), fetch_dev writes the
+ * rows.  Only epi_batch_fdrp_fetch_dev may follow the report: it after any other report, or another report's fetch after
+ * this one, is EPI_ERR_STATE.  The CX report inside leaves the direct-mode record exactly as
+ * epi_batch_cx_report_dev(b, NULL, the upper-case letters of ctx) would.  The report lists one (site, row) pair per call
+ * of a kept row and sorts the list by site; the list holds fewer than 2^32 pairs (the sort's indices are 32-bit), more is
+ * EPI_ERR_ARG before the list is allocated.  epi_fdrp_pair_bytes is that check on its own: *bytes_out = the bytes of the
+ * two (key, row) buffers, 24 per call, or EPI_ERR_ARG for ncalls < 0 or ncalls >= 2^32.  Single GPU only: the sharded form
+ * is not built (a batch with shared tiles attached: EPI_ERR_STATE). */
+int epi_batch_fdrp_report_dev(epi_batch *b, const char *ctx, int flank_sites, int max_reads, int min_overlap, int32_t max_distance,
+                              double max_ooctx_meth_frac, int32_t min_reads, void *stream, int64_t *nrow_out);
+int epi_batch_fdrp_fetch_dev(epi_batch *b, int32_t *const d_icols[8], double *const d_dcols[2], void *stream);
+int epi_fdrp_pair_bytes(int64_t ncalls, int64_t *bytes_out);
+
 /* epi_fisher_exact on the device: d_p[i] = the two-sided Fisher exact p-value of the table (d_a[i] d_b[i] / d_c[i] d_d[i]),
  * by the definition and the arithmetic of epi_fisher_exact (csrc/fisher_math.hpp is compiled into both): P(k) in Loader's
  * saddle-point form, a table as extreme when P(k) <= P(a) (1 + 1e-7), the tails found by bisection and summed outwards by
