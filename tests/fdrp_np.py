@@ -24,6 +24,9 @@ def _popcount(x):
     return bin(x).count("1")
 
 
+_bit_count = getattr(int, "bit_count", _popcount)          # (restate_indexed: three times as fast where Python has it)
+
+
 def selected_ranks(c, m):
     """Ranks (in the list of the c covering rows) of the rows that are used."""
     return list(range(c)) if c <= m else [(j * c) // m for j in range(m)]
@@ -81,6 +84,90 @@ def restate(t, ctx, flank_sites=8, max_reads=40, min_overlap=1, max_distance=0, 
                 both = sel[a][1] & sel[b][1] & win
                 o = _popcount(both)
                 h = _popcount((sel[a][2] ^ sel[b][2]) & both)
+                if o >= min_overlap:
+                    npairs += 1
+                    ndisc += 1 if h > 0 else 0
+                    Hh[o] += h
+        if nreads < max(min_reads, 2) or npairs < 1:
+            continue
+        q = np.float64(0.0)
+        for o in range(1, 2 * W + 2):
+            q = q + np.float64(Hh[o]) / np.float64(o)
+        for name in ("rname", "strand", "pos", "context"):
+            out[name].append(int(sites[name][i]))
+        out["coverage"].append(c); out["nreads"].append(nreads); out["npairs"].append(npairs); out["ndiscordant"].append(ndisc)
+        out["fdrp"].append(np.float64(ndisc) / np.float64(npairs))
+        out["qfdrp"].append(q / np.float64(npairs))
+        used.append([q_[0] for q_ in sel])
+    res = {q: np.asarray(out[q], np.int32) for q in INT_COLS}
+    res.update({q: np.asarray(out[q], np.float64) for q in FLOAT_COLS})
+    res["sites"] = sites
+    res["used"] = used
+    return res
+
+
+def restate_indexed(t, ctx, flank_sites=8, max_reads=40, min_overlap=1, max_distance=0, max_oo=0.1, min_reads=2):
+    """restate for large tables: the same definitions in the same loops, but the rows that cover a site are looked up in a
+    list per site that is filled while the rows are walked (restate scans every row of the segment per site: 48 s for
+    65 000 sites on one sequence), and a row's calls are two integers whose bit 0 is the row's OWN first site, so that no
+    integer is as long as the segment.  Rows are walked in ascending batch row: every site's list is in that order.
+    test_fdrp_host.py shows the two equal, column for column and in `used`."""
+    W, m = int(flank_sites), int(max_reads)
+    c_ = H.CONTEXT_TO_BASES[ctx]
+    sites = site_table(t, ctx)
+    n = t["off"].size - 1
+    xm = np.asarray(t["xm"], np.uint8)
+    keep = H.mhl_keep_np(xm, t["off"], c_["ctx_meth"] + c_["ctx_unmeth"], 0, max_oo) if n else np.zeros(0, bool)
+    N = sites["pos"].size
+    out = {q: [] for q in INT_COLS + FLOAT_COLS}
+    used = []
+    segs = {}
+    for r in np.unique(sites["rname"]):
+        for s in (1, 2):
+            cxrows = np.flatnonzero((sites["rname"] == r) & (sites["strand"] == s))
+            P = sites["pos"][cxrows].astype(np.int64)
+            assert np.all(np.diff(P) > 0)
+            code = sites["context"][cxrows].tolist()
+            Pl = P.tolist()
+            cover = [[] for _ in Pl]                        # per site: (batch row, its first site, valid bits, methylated bits)
+            for x in np.flatnonzero((t["rname"] == r) & (t["strand"] == s) & keep):
+                st, o0, o1 = int(t["start"][x]), int(t["off"][x]), int(t["off"][x + 1])
+                a, b = int(np.searchsorted(P, st)), int(np.searchsorted(P, st + (o1 - o0)))
+                row = xm[o0:o1].tolist()
+                v = mm = 0
+                for j in range(a, b):
+                    nib = row[Pl[j] - st] & 15
+                    if (nib & 7) == code[j]:
+                        v |= 1 << (j - a)
+                        if nib < 8:
+                            mm |= 1 << (j - a)
+                entry = (int(x), a, v, mm)
+                for j in range(a, b):
+                    if (v >> (j - a)) & 1:
+                        cover[j].append(entry)
+            segs[(int(r), s)] = (P, Pl, {p: j for j, p in enumerate(Pl)}, cover)
+    for i in range(N):
+        P, Pl, where, cover = segs[(int(sites["rname"][i]), int(sites["strand"][i]))]
+        j = where[int(sites["pos"][i])]
+        c = len(cover[j])
+        sel = [cover[j][k] for k in selected_ranks(c, m)]
+        nreads = len(sel)
+        w0 = max(0, j - W)
+        win = 0                                             # bit 0 = site w0
+        for w in range(w0, min(len(Pl), j + W + 1)):
+            if max_distance == 0 or abs(Pl[w] - Pl[j]) <= max_distance:
+                win |= 1 << (w - w0)
+        # the selected rows' calls inside the window, bit 0 = site w0
+        vs = [((q[2] >> (w0 - q[1])) if w0 >= q[1] else (q[2] << (q[1] - w0))) & win for q in sel]
+        ms = [((q[3] >> (w0 - q[1])) if w0 >= q[1] else (q[3] << (q[1] - w0))) & win for q in sel]
+        npairs = ndisc = 0
+        Hh = [0] * (2 * W + 2)
+        for a in range(nreads):
+            va, ma = vs[a], ms[a]
+            for b in range(a + 1, nreads):
+                both = va & vs[b]
+                o = _bit_count(both)
+                h = _bit_count((ma ^ ms[b]) & both)
                 if o >= min_overlap:
                     npairs += 1
                     ndisc += 1 if h > 0 else 0

@@ -145,3 +145,105 @@ def test_selection_ranks():
     assert r[0] == 0 and r[-1] == 63 and len(set(r)) == 64
     r = fdrp_np.selected_ranks(100, 40)
     assert r == [(5 * j) // 2 for j in range(40)] and len(set(r)) == 40
+
+
+# ---- the indexed restatement, the seam batches and what the fuzz list reaches (no GPU) -------------------------------------------
+
+def same_restatement(a, b, label):
+    for q in fdrp_np.INT_COLS + fdrp_np.FLOAT_COLS:
+        assert a[q].dtype == b[q].dtype and np.array_equal(a[q], b[q]), (label, q)
+    assert a["used"] == b["used"], (label, "used")
+    for q in a["sites"]:
+        assert np.array_equal(a["sites"][q], b["sites"][q]), (label, "sites", q)
+
+
+def test_indexed_restatement_equals_the_loop():
+    """fdrp_np.restate_indexed (the covering rows of a site looked up, a row's calls counted from the row's first site)
+    against fdrp_np.restate, column for column and in `used`: on the batches of test_gpu_fdrp.py with their arguments, on
+    its five fuzz seeds and on five batches of the fuzz generator with the calls test_gpu_fuzz_fdrp.py draws for them"""
+    import test_gpu_fdrp as TF
+    import test_gpu_fuzz_fdrp as FF
+    rng = np.random.default_rng
+    cases = [("by hand", H.templates_from_xm(["Z.Z.Z", "Z.z.Z", "z.z.Z", "..Z.z"], [1, 1, 1, 1], [1, 1, 1, 1]), "CG", dict(flank_sites=1)),
+             ("selection 100 / 7", TF.selection_batch(100), "CG", dict(max_reads=7)),
+             ("selection 65 / 64", TF.selection_batch(65), "CG", dict(max_reads=64)),
+             ("packing", TF.packing_batch(17), "CG", dict(flank_sites=31, max_reads=64)),
+             ("packing, long rows", TF.packing_batch(19, step=9), "CG", dict(flank_sites=5, max_reads=9, min_overlap=3)),
+             ("segments", TF.ragged(rng(29), 240, span=40, lmin=6, lmax=30, rnames=(1, 2), p_site=0.8), "CG", dict(flank_sites=3, max_reads=64)),
+             ("gaps", TF.ragged(rng(31), 160, span=50, lmin=6, lmax=40, p_site=0.95, p_gap=0.25, other="xh-", p_other=0.3), "CG",
+              dict(flank_sites=4, max_reads=64, min_overlap=5)),
+             ("max_distance", TF.ragged(rng(37), 120, span=40, lmin=10, lmax=40, p_site=0.9), "CG", dict(flank_sites=4, max_reads=64, max_distance=4)),
+             ("min_reads", TF.ragged(rng(41), 60, span=80, lmin=6, lmax=30, p_site=0.8), "CG", dict(flank_sites=3, max_reads=5, min_reads=3)),
+             ("no kept row", H.templates_from_xm(["Z.z.HH", "z.Z.HH"], [1, 1], [1, 1]), "CG", {}),
+             ("empty", H.templates_from_xm([], [], []), "CG", {})]
+    names = {"W": "flank_sites", "m": "max_reads"}
+    for seed in TF.FUZZ_SEEDS:
+        t, ctx, kw = TF.fuzz_case(seed)
+        cases.append(("fuzz %d" % seed, t, ctx, {names.get(k, k): v for k, v in kw.items()}))
+    for seed in (1003, 1007, 1028, 1033, 9004):             # a pile, three sequences, long rows, flank_sites = 0, garbage and empty rows
+        kind, t, calls = FF.plan(seed)
+        cases.append(("fuzz batch %d" % seed, t, calls[0][0], dict(zip(("flank_sites", "max_reads", "min_overlap", "max_distance", "max_oo", "min_reads"),
+                                                                      calls[0][1:]))))
+    nonempty = 0
+    for label, t, ctx, kw in cases:
+        a, b = fdrp_np.restate(t, ctx, **kw), fdrp_np.restate_indexed(t, ctx, **kw)
+        same_restatement(a, b, label)
+        nonempty += a["pos"].size > 0
+    assert nonempty >= len(cases) - 3
+
+
+def test_seam_batches_hold_what_they_are_built_for():
+    """The counts that test_gpu_fdrp_seams.py pins, on the cases whose restatement is quick (each *_want asserts its own:
+    the site count, the coverage, the first and the last ordinal, the pair count, the deep site, the top of int32)"""
+    import test_gpu_fdrp_seams as S
+    for N in (1, 2, 256, 257):
+        t, want = S.table_want(N, 8, 40)
+        assert want["pos"].size == N
+    for n in (4095, 4096, 4097):
+        t, want = S.rows_want(n, False, 8, 40)
+        assert t["start"].size == n and int(t["off"][-1]) <= 512 * n
+    t, want = S.rows_want(5, True, 8, 40)
+    assert int(t["off"][-1]) > 512 * 5 and want["pos"].size > 50
+    for nc in (4095, 4096, 4097, 8193):
+        S.pairs_want(nc)
+    t, want, i = S.deep_want(4097, 40)
+    assert want["coverage"][i] == 4097
+    for which in ("pos", "rname"):
+        S.end_want(which, 3)
+
+
+def test_fuzz_fdrp_inputs_cover_the_shapes():
+    """What the calls of test_gpu_fuzz_fdrp.py reach, from the restatement alone"""
+    import test_gpu_fuzz_fdrp as FF
+    TOP = 2 ** 31 - 1
+    n = dict.fromkeys(("calls", "skipped", "discordant", "deep", "high", "long_row", "wide", "three_both", "capped"), 0)
+    Ws, ms = set(), set()
+    for seed in FF.SEEDS:
+        kind, t, calls = FF.plan(seed)
+        L = np.diff(t["off"])
+        for call in calls:
+            ctx, W, m, min_overlap, max_distance, max_oo, min_reads = call
+            assert ctx in H.CONTEXT_TO_BASES and 0 <= W <= 31 and 2 <= m <= 64 and 1 <= min_overlap <= 2 * W + 1
+            assert max_distance in FF.MAX_DISTANCE and 0 <= min_reads <= 5
+            n["calls"] += 1
+            Ws.add(W); ms.add(m)
+            want = FF.fdrp_want(t, call)
+            if want is None:
+                n["skipped"] += 1
+                continue
+            nrow = want["pos"].size
+            n["discordant"] += bool(nrow and want["ndiscordant"].max() > 0)
+            n["deep"] += bool(nrow and want["coverage"].max() >= 256)
+            n["high"] += bool(nrow and want["pos"].max() > TOP - 1000)
+            n["long_row"] += bool(L.max() > 4000)
+            n["wide"] += bool(int(t["off"][-1]) > 512 * L.size)
+            n["three_both"] += bool(np.unique(t["rname"]).size == 3 and np.unique(want["rname"]).size == 3 and set(want["strand"].tolist()) >= {1, 2})
+            n["capped"] += bool(nrow and np.any(want["nreads"] < want["coverage"]))
+    print("FDRP calls %(calls)d: %(discordant)d with a discordant pair, %(deep)d with a site of 256 rows or more, %(high)d with a pos above "
+          "2^31 - 1000, %(long_row)d on a batch with a row above 4000 bytes, %(wide)d on a batch with a mean row above 512 bytes, "
+          "%(three_both)d on three sequences with both strands, %(capped)d with nreads < coverage, %(skipped)d skipped for size" % n,
+          "flank_sites drawn %s, max_reads drawn %s" % (sorted(Ws), sorted(ms)))
+    assert 20 * n["skipped"] <= n["calls"]
+    assert 3 * n["discordant"] >= 2 * n["calls"]
+    assert n["deep"] >= 1 and n["high"] >= 1 and n["long_row"] >= 1 and n["wide"] >= 1 and n["three_both"] >= 1 and n["capped"] >= 1
+    assert {0, 31} <= Ws and {2, 64} <= ms

@@ -312,8 +312,11 @@ def test_bad_arguments_at_the_c_level(ea):
 
 # ---- fuzz ------------------------------------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("seed", [1, 2, 3, 4, 5])
-def test_fuzz(ea, seed):
+FUZZ_SEEDS = (1, 2, 3, 4, 5)
+
+
+def fuzz_case(seed):
+    """(templates, context, the arguments) of a seed"""
     rng = np.random.default_rng(1000 + seed)
     t = ragged(rng, int(rng.integers(200, 400)), span=int(rng.integers(30, 200)), lmin=1, lmax=int(rng.integers(30, 200)),
                rnames=(1, 2, 3)[:int(rng.integers(1, 4))], p_site=float(rng.uniform(0.7, 1.0)), p_meth=float(rng.uniform(0.1, 0.9)),
@@ -323,7 +326,13 @@ def test_fuzz(ea, seed):
     widest = 2 * min(W, max_distance // 2 if max_distance else W) + 1          # sites of a window (every other position is one)
     kw = dict(W=W, m=int(rng.integers(2, 65)), min_overlap=int(rng.integers(1, min(widest, 6) + 1)), max_distance=max_distance,
               min_reads=int(rng.integers(0, 6)), max_oo=float(rng.choice([0.1, 0.5, 1.0])))
-    check(ea, t, ctx=str(rng.choice(["CG", "CG", "CX"])), **kw)
+    return t, str(rng.choice(["CG", "CG", "CX"])), kw
+
+
+@pytest.mark.parametrize("seed", FUZZ_SEEDS)
+def test_fuzz(ea, seed):
+    t, ctx, kw = fuzz_case(seed)
+    check(ea, t, ctx=ctx, **kw)
 
 
 # ---- call sequences on one batch ---------------------------------------------------------------------------------------------------
@@ -383,6 +392,160 @@ def test_adjust_p_values_is_untouched(ea):
     check(ea, t, W=31, m=64)
     for meth, q in before.items():
         assert np.asarray(ea.adjustPValues(p, method=meth)).tobytes() == q.tobytes(), meth
+
+
+# ---- call sequences that regrow, reuse and share the index buffers -------------------------------------------------------------------
+
+def report_dev(ea, bam, ctx, W, m, min_overlap=1, max_distance=0, max_oo=0.1, min_reads=2, stream=None):
+    """epi_batch_fdrp_report_dev on its own -> the table's rows"""
+    from epialleler_amd import _lib
+    c = H.CONTEXT_TO_BASES[ctx]
+    nrow = C.c_int64(0)
+    _lib.check(_lib.load().epi_batch_fdrp_report_dev(bam.batch(), (c["ctx_meth"] + c["ctx_unmeth"]).encode(), W, m, min_overlap, max_distance,
+                                                     max_oo, min_reads, stream, C.byref(nrow)))
+    return nrow.value
+
+
+def fetch_dev(ea, bam, nrow):
+    """epi_batch_fdrp_fetch_dev on its own (on torch's current stream)"""
+    from epialleler_amd import _lib, api
+    return api._fetch_table(bam, _lib.load().epi_batch_fdrp_fetch_dev, nrow, 8, api.FDRP_COLUMNS, False)
+
+
+def other_contexts_batch(seed, nrow=250):
+    return ragged(np.random.default_rng(seed), nrow, span=80, lmin=6, lmax=60, rnames=(1, 2), p_site=0.8, p_gap=0.1, other="hH", p_other=0.5)
+
+
+def test_changing_contexts_on_one_batch(ea):
+    """CG, CX, CHH, then CG again on one batch: tables of other sizes over the same index buffers"""
+    t = other_contexts_batch(67)
+    bam = as_bam(ea, t)
+    sizes = []
+    for ctx in ("CG", "CX", "CHH", "CG"):
+        want = fdrp_np.restate(t, ctx, flank_sites=4, max_reads=16, max_oo=1.0)
+        assert want["pos"].size > 20 and want["ndiscordant"].max() > 0
+        assert_same(gpu_report(ea, bam, ctx, W=4, m=16, max_oo=1.0), want, ctx)
+        sizes.append(int(want["sites"]["pos"].size))
+    assert len(set(sizes)) == 3
+
+
+def test_a_small_table_after_a_large_one_and_back(ea):
+    """The 65537-site batch of test_gpu_fdrp_seams.py with four rows of a further sequence that hold the batch's only CHH
+    calls: 3 sites, 65537 sites (every index buffer regrown), 3 sites (reused by a smaller call), 65537 sites"""
+    import test_gpu_fdrp_seams as S
+    big = S.table_batch(65537)
+    tail = H.templates_from_xm(["H.h.H", "h.H.h", "H.H.h", "h.h.H"], [1, 1, 1, 1], [1, 1, 1, 1], [9, 9, 9, 9])
+    t = {"xm": np.concatenate((big["xm"], tail["xm"])), "off": np.concatenate((big["off"], big["off"][-1] + tail["off"][1:]))}
+    for q in ("rname", "strand", "start"):
+        t[q] = np.concatenate((big[q], tail[q]))
+    want_big = fdrp_np.restate_indexed(t, "CG", flank_sites=8, max_reads=40)
+    want_small = fdrp_np.restate(t, "CHH", flank_sites=1, max_reads=3, max_oo=1.0)
+    assert want_big["sites"]["pos"].size == 65537 == want_big["pos"].size
+    assert want_small["sites"]["pos"].size == 3 == want_small["pos"].size and want_small["ndiscordant"].min() > 0
+    bam = as_bam(ea, t)
+    for _ in range(2):
+        assert_same(gpu_report(ea, bam, "CHH", W=1, m=3, max_oo=1.0), want_small, "3 sites")
+        assert_same(gpu_report(ea, bam, "CG", W=8, m=40), want_big, "65537 sites")
+
+
+def test_after_an_empty_report(ea):
+    """An empty table with its fetch, then a table with rows, on one batch: empty because no site has min_reads rows (the
+    whole report runs), and empty because the read rule drops every row (the report ends after its first step)"""
+    import torch
+    from epialleler_amd import _lib, api
+    rng = np.random.default_rng(71)
+    xms, starts = [], []
+    for _ in range(150):
+        st = int(rng.integers(1, 60))
+        xms.append(random_xm(rng, int(rng.integers(8, 50)), p_site=0.85, phase=st % 2) + "H")
+        starts.append(st)
+    t = H.templates_from_xm(xms, starts, [1] * 150)
+    bam = as_bam(ea, t)
+    lib, b = _lib.load(), bam.batch()
+    ic = list(torch.empty((8, 0), dtype=torch.int32, device="cuda").unbind(0))
+    dc = list(torch.empty((2, 0), dtype=torch.float64, device="cuda").unbind(0))
+    want = fdrp_np.restate(t, "CG", flank_sites=6, max_reads=5, max_oo=1.0)
+    assert want["pos"].size > 20 and want["ndiscordant"].max() > 0
+    for empty in (dict(min_reads=9, max_oo=1.0), dict(max_oo=0.0), dict(min_reads=9, max_oo=1.0)):
+        assert fdrp_np.restate(t, "CG", flank_sites=6, max_reads=5, **empty)["pos"].size == 0
+        assert report_dev(ea, bam, "CG", 6, 5, **empty) == 0
+        assert lib.epi_batch_fdrp_fetch_dev(b, api._ptr_array(ic), api._ptr_array(dc), None) == _lib.EPI_OK
+        assert_same(gpu_report(ea, bam, "CG", W=6, m=5, max_oo=1.0), want, str(empty))
+
+
+def test_two_batches_interleaved(ea):
+    """report A, report B, fetch A, fetch B: every batch has its own index"""
+    ta, tb = other_contexts_batch(73, 300), other_contexts_batch(79, 90)
+    a, b = as_bam(ea, ta), as_bam(ea, tb)
+    wa = fdrp_np.restate(ta, "CG", flank_sites=8, max_reads=40, max_oo=1.0)
+    wb = fdrp_np.restate(tb, "CX", flank_sites=2, max_reads=7, max_oo=1.0)
+    assert min(wa["pos"].size, wb["pos"].size) > 20 and wa["pos"].size != wb["pos"].size
+    for _ in range(2):
+        na = report_dev(ea, a, "CG", 8, 40, max_oo=1.0)
+        nb = report_dev(ea, b, "CX", 2, 7, max_oo=1.0)
+        assert_same(fetch_dev(ea, a, na), wa, "A")
+        assert_same(fetch_dev(ea, b, nb), wb, "B")
+        nb = report_dev(ea, b, "CX", 2, 7, max_oo=1.0)
+        na = report_dev(ea, a, "CG", 8, 40, max_oo=1.0)
+        assert_same(fetch_dev(ea, a, na), wa, "A after B")
+        assert_same(fetch_dev(ea, b, nb), wb, "B before A")
+
+
+def test_on_a_side_stream(ea):
+    """The report and the fetch queued through the C entry points on a stream that is not the default one"""
+    import torch
+    t = packing_batch(83)
+    want = fdrp_np.restate(t, "CG", flank_sites=31, max_reads=64)
+    s = torch.cuda.Stream()
+    assert s.cuda_stream != torch.cuda.default_stream().cuda_stream
+    with torch.cuda.stream(s):
+        bam = as_bam(ea, t)
+        nrow = report_dev(ea, bam, "CG", 31, 64, stream=C.c_void_p(s.cuda_stream))
+        got = fetch_dev(ea, bam, nrow)
+    s.synchronize()
+    assert got.nrow > 0
+    assert_same(got, want)
+    assert_same(gpu_report(ea, bam, "CG", W=31, m=64), want, "then on the default stream")
+
+
+def test_a_batch_set_up_for_a_sharded_report_is_refused(ea):
+    """Shared tiles attached (the setup of test_gpu_sharded.py's single-rank worker): EPI_ERR_STATE, and the batch still
+    serves the sharded CX report and, once that has detached the tiles, this report"""
+    from epialleler_amd import _lib, distributed as D
+    t = H.bam("amplicon010meth.bam")
+    bam = as_bam(ea, t, t.get("levels"))
+    eng = D.HipShardEngine(bam)
+    first, last = eng.key_range()
+    keys = np.array([k for k in range(first, first + 4) if (k >> 32) == (first >> 32) and k <= last], dtype=np.int64)
+    owned = np.ones(keys.size, dtype=np.int32)
+    assert keys.size > 0
+    eng._attach_cx_slab(keys, owned, "Z")
+    nrow = C.c_int64(7)
+    assert _lib.load().epi_batch_fdrp_report_dev(bam.batch(), b"Zz", 8, 40, 1, 0, 0.1, 2, None, C.byref(nrow)) == _lib.EPI_ERR_STATE
+    assert nrow.value == 0 and b"sharded" in _lib.load().epi_last_error()
+    slab = eng.cx_accumulate(None, "Z", keys, owned)
+    assert int(slab.abs().sum()) > 0
+    cols = eng.cx_finish("Z")
+    sites = fdrp_np.site_table(t, "CG")
+    for i, q in enumerate(("rname", "strand", "pos", "context", "meth", "unmeth")):
+        assert np.array_equal(cols[i].cpu().numpy(), sites[q]), q
+    want = fdrp_np.restate(t, "CG")
+    assert want["pos"].size > 0
+    assert_same(gpu_report(ea, bam, "CG"), want)
+
+
+def test_adjust_p_values_between_report_and_fetch(ea):
+    """adjustPValues on 70 000 values (18 sorting tiles, its own pass plan) between this report and its fetch, on one engine"""
+    import padjust_np
+    p = np.random.default_rng(89).random(70000)
+    t = other_contexts_batch(97, 300)
+    want = fdrp_np.restate(t, "CG", flank_sites=8, max_reads=40, max_oo=1.0)
+    assert want["pos"].size > 20
+    bam = as_bam(ea, t)
+    nrow = report_dev(ea, bam, "CG", 8, 40, max_oo=1.0)
+    q = np.asarray(ea.adjustPValues(p, method="BH"))
+    assert_same(fetch_dev(ea, bam, nrow), want)
+    np.testing.assert_array_equal(q, padjust_np.adjust_np(p, "BH")[0])
 
 
 # ---- delivery ----------------------------------------------------------------------------------------------------------------------
