@@ -211,6 +211,7 @@ _SIGS = {
     "epi_prof_enable": (None, [C.c_int]),
     "epi_prof_get": (C.c_int, [_CS, C.POINTER(_F64), C.POINTER(_I64)]),
     "epi_prof_reset": (None, []),
+    "epi_device_allocations": (C.c_int, [C.POINTER(_I64), C.POINTER(_I64)]),
     "epi_options_reload": (None, []),
 }
 

@@ -93,10 +93,6 @@ int assemble_templates(epi_engine *eng, const uint8_t *d_arena, const AsmTpl *tp
   const int64_t nblk = (ntpl + kWaves - 1) / kWaves;
   EPI_TRY(check_grid(nblk, 256, "preprocessBam"));
   DevBuf d_tpl, d_rec, d_out, d_q;
-  struct Release {
-    DevBuf *b[4];
-    ~Release() { for (DevBuf *x : b) x->release(); }
-  } rel{{&d_tpl, &d_rec, &d_out, &d_q}};
   EPI_TRY(d_tpl.ensure((size_t)ntpl * sizeof(AsmTpl)));
   EPI_TRY(d_rec.ensure((size_t)(nrec > 0 ? nrec : 1) * sizeof(AsmRec)));
   EPI_TRY(d_out.ensure((size_t)nbytes));

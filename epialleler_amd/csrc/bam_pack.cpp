@@ -1193,7 +1193,7 @@ struct BamJob {
   int stage_k = 0;
 #ifndef EPI_HOST_ONLY
   DevBuf arena;                                              // sized by the file's inflated bytes: a kept record's inputs are
-  ~BamJob() { arena.release(); }                             // smaller than the record
+                                                             // smaller than the record
 #endif
   std::vector<AsmRec> arec;                                  // kept records in merge order, template after template
   std::vector<int64_t> tpl_lo;                               // per template: its first record in arec (n + 1 entries)

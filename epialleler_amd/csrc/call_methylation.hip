@@ -93,7 +93,6 @@ __global__ __launch_bounds__(256) void k_call_xm(const CallRec *__restrict__ rec
 
 }  // namespace
 
-CallWork::~CallWork() { recs.release(); cig.release(); seq.release(); ref.release(); xm.release(); }
 
 int call_methylation_window(epi_engine *eng, epi_genome *g, CallWork &wk, const CallRec *recs, int64_t nrec,
                             const uint32_t *cigar, int64_t ncig, const uint8_t *seq, int64_t nseq, int64_t nxm,

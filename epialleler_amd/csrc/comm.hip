@@ -185,7 +185,6 @@ void epi_comm_free(epi_comm *c) {
   if (!c) return;
   (void)hipSetDevice(c->eng->device);
   if (c->nccl) (void)rccl().CommDestroy(c->nccl);
-  c->d_gather.release();
   delete c;
 }
 
@@ -206,7 +205,7 @@ int epi_batch_cytosine_report_sharded(epi_batch *b, epi_comm *c, const char *ctx
   const int T = epi_cx_tile_positions(ctx);
   // 1, 2: shared tiles -- a property of the shards, the tile grid and the communicator: exchanged once, remembered on the batch
   epi_shard_plan *plan = nullptr;
-  for (auto &p : b->shard_plans) if (p->comm_serial == c->serial && p->T == T && p->kind == 0) plan = p.get();
+  for (auto &p : b->shard.plans) if (p->comm_serial == c->serial && p->T == T && p->kind == 0) plan = p.get();
   if (!plan) {
     int64_t mine[2] = {0, -1};
     EPI_TRY(epi_batch_tile_key_range_for(b, T, s, &mine[0], &mine[1]));
@@ -219,17 +218,17 @@ int epi_batch_cytosine_report_sharded(epi_batch *b, epi_comm *c, const char *ctx
     else EPI_TRY(shared_keys_of(all, c->world, &np->keys, &owner));
     np->owned.resize(owner.size());
     for (size_t i = 0; i < owner.size(); i++) np->owned[i] = owner[i] == c->rank ? 1 : 0;
-    b->shard_plans.push_back(std::move(np));
-    plan = b->shard_plans.back().get();
+    b->shard.plans.push_back(std::move(np));
+    plan = b->shard.plans.back().get();
   }
   const int32_t nshared = (int32_t)plan->keys.size();
   // 3: accumulate (shared tiles into the slab)
   const size_t slab_bytes = (size_t)nshared * kCxPlanes * T * 4;
   if (nshared > 0) {
-    EPI_TRY(b->own_slab.ensure(slab_bytes));
-    EPI_HIP(hipMemsetAsync(b->own_slab.p, 0, slab_bytes, s));
+    EPI_TRY(b->shard.own_slab.ensure(slab_bytes));
+    EPI_HIP(hipMemsetAsync(b->shard.own_slab.p, 0, slab_bytes, s));
   }
-  EPI_TRY(epi_batch_cx_set_shared(b, plan->keys.data(), plan->owned.data(), nshared, nshared ? b->own_slab.as<int32_t>() : nullptr));
+  EPI_TRY(epi_batch_cx_set_shared(b, plan->keys.data(), plan->owned.data(), nshared, nshared ? b->shard.own_slab.as<int32_t>() : nullptr));
   int rc;
   int64_t nrow = 0;
   auto first_half = [&]() {
@@ -241,13 +240,13 @@ int epi_batch_cytosine_report_sharded(epi_batch *b, epi_comm *c, const char *ctx
   // ONE host synchronisation per report where the batch allows it (an earlier report found no ultra-deep tile the host
   // would have to finish before the slab travels): the first half only queues its kernels, the all-reduce and the owners'
   // emit are queued behind them, and everything is read back and checked once, in the second half.
-  b->cx_defer = true;
+  b->cx.defer = true;
   rc = first_half();
-  b->cx_defer = false;
+  b->cx.defer = false;
   if (rc == EPI_OK && nshared > 0) {
     // 4: the one data-path collective, queued on the report's stream behind the tile kernels
     if (c->nccl) {
-      const ncclResult_t r = rccl().AllReduce(b->own_slab.p, b->own_slab.p, slab_bytes / 4, ncclInt32, ncclSum, c->nccl, s);
+      const ncclResult_t r = rccl().AllReduce(b->shard.own_slab.p, b->shard.own_slab.p, slab_bytes / 4, ncclInt32, ncclSum, c->nccl, s);
       if (r != ncclSuccess) rc = fail(EPI_ERR_HIP, "ncclAllReduce failed: %s", rccl().GetErrorString(r));
       c->last_bytes = (int64_t)slab_bytes;
     }
@@ -256,11 +255,11 @@ int epi_batch_cytosine_report_sharded(epi_batch *b, epi_comm *c, const char *ctx
     if (rc == EPI_RETRY_POOL) {
       // (deferred synchronisation only) the row pool was too small: the first half again, with its own synchronisation --
       // it grows the pool -- into a scratch slab; the shared tiles are then emitted from the slab that is already reduced
-      rc = b->own_slab2.ensure(slab_bytes);
-      if (rc == EPI_OK && hipMemsetAsync(b->own_slab2.p, 0, slab_bytes, s) != hipSuccess) rc = fail(EPI_ERR_HIP, "hipMemsetAsync failed");
-      if (rc == EPI_OK) rc = epi_batch_cx_set_shared(b, plan->keys.data(), plan->owned.data(), nshared, b->own_slab2.as<int32_t>());
+      rc = b->shard.own_slab2.ensure(slab_bytes);
+      if (rc == EPI_OK && hipMemsetAsync(b->shard.own_slab2.p, 0, slab_bytes, s) != hipSuccess) rc = fail(EPI_ERR_HIP, "hipMemsetAsync failed");
+      if (rc == EPI_OK) rc = epi_batch_cx_set_shared(b, plan->keys.data(), plan->owned.data(), nshared, b->shard.own_slab2.as<int32_t>());
       if (rc == EPI_OK) rc = first_half();
-      if (rc == EPI_OK) rc = epi_batch_cx_set_shared(b, plan->keys.data(), plan->owned.data(), nshared, b->own_slab.as<int32_t>());
+      if (rc == EPI_OK) rc = epi_batch_cx_set_shared(b, plan->keys.data(), plan->owned.data(), nshared, b->shard.own_slab.as<int32_t>());
       if (rc == EPI_OK) rc = epi_batch_cx_finish_shared(b, ctx, s, &nrow);
     }
   }
@@ -282,7 +281,7 @@ int epi_batch_mhl_report_sharded(epi_batch *b, epi_comm *c, const char *ctx, int
   // itself (two strings with the same letters' indices, "Zz" and "[[", may still differ in that decision)
   const int kind = 1;
   epi_shard_plan *plan = nullptr;
-  for (auto &p : b->shard_plans) if (p->comm_serial == c->serial && p->kind == kind && p->ctx == ctx) plan = p.get();
+  for (auto &p : b->shard.plans) if (p->comm_serial == c->serial && p->kind == kind && p->ctx == ctx) plan = p.get();
   if (!plan) {
     // both tile grids' ranges and whether this rank's rows allow the one-pass kernel: one all-gather decides path and tiles
     int32_t ok = 0;
@@ -304,31 +303,31 @@ int epi_batch_mhl_report_sharded(epi_batch *b, epi_comm *c, const char *ctx, int
     else EPI_TRY(shared_keys_of(ranges, c->world, &np->keys, &owner));
     np->owned.resize(owner.size());
     for (size_t i = 0; i < owner.size(); i++) np->owned[i] = owner[i] == c->rank ? 1 : 0;
-    b->shard_plans.push_back(std::move(np));
-    plan = b->shard_plans.back().get();
+    b->shard.plans.push_back(std::move(np));
+    plan = b->shard.plans.back().get();
   }
   const int32_t nshared = (int32_t)plan->keys.size();
   const int T = plan->T;
   const size_t cnt_bytes = plan->fused ? (size_t)nshared * 4 * T * 4 : (size_t)nshared * 16 * T * 4;
   const size_t sum_bytes = plan->fused ? (size_t)nshared * 6 * T * 8 : (size_t)nshared * (size_t)epi_mhl_slab_sums() * 8;
   if (nshared > 0) {
-    EPI_TRY(b->own_slab.ensure(cnt_bytes));
-    EPI_TRY(b->own_slab2.ensure(sum_bytes));
-    EPI_HIP(hipMemsetAsync(b->own_slab.p, 0, cnt_bytes, s));
-    EPI_HIP(hipMemsetAsync(b->own_slab2.p, 0, sum_bytes, s));
+    EPI_TRY(b->shard.own_slab.ensure(cnt_bytes));
+    EPI_TRY(b->shard.own_slab2.ensure(sum_bytes));
+    EPI_HIP(hipMemsetAsync(b->shard.own_slab.p, 0, cnt_bytes, s));
+    EPI_HIP(hipMemsetAsync(b->shard.own_slab2.p, 0, sum_bytes, s));
   }
   if (plan->fused)
-    EPI_TRY(epi_batch_mhl_set_shared_fused(b, plan->keys.data(), plan->owned.data(), nshared, nshared ? b->own_slab.as<int32_t>() : nullptr,
-                                           nshared ? b->own_slab2.as<int64_t>() : nullptr));
+    EPI_TRY(epi_batch_mhl_set_shared_fused(b, plan->keys.data(), plan->owned.data(), nshared, nshared ? b->shard.own_slab.as<int32_t>() : nullptr,
+                                           nshared ? b->shard.own_slab2.as<int64_t>() : nullptr));
   else
-    EPI_TRY(epi_batch_mhl_set_shared(b, plan->keys.data(), plan->owned.data(), nshared, nshared ? b->own_slab.as<int32_t>() : nullptr,
-                                     nshared ? b->own_slab2.as<int64_t>() : nullptr));
+    EPI_TRY(epi_batch_mhl_set_shared(b, plan->keys.data(), plan->owned.data(), nshared, nshared ? b->shard.own_slab.as<int32_t>() : nullptr,
+                                     nshared ? b->shard.own_slab2.as<int64_t>() : nullptr));
   int64_t nrow = 0;
   int rc = epi_batch_mhl_report_dev(b, ctx, hmax, hmin, max_ooctx_meth_frac, s, &nrow);
   if (rc == EPI_OK && nshared > 0) {
     if (c->nccl) {
-      ncclResult_t r = rccl().AllReduce(b->own_slab.p, b->own_slab.p, cnt_bytes / 4, ncclInt32, ncclSum, c->nccl, s);
-      if (r == ncclSuccess) r = rccl().AllReduce(b->own_slab2.p, b->own_slab2.p, sum_bytes / 8, ncclInt64, ncclSum, c->nccl, s);
+      ncclResult_t r = rccl().AllReduce(b->shard.own_slab.p, b->shard.own_slab.p, cnt_bytes / 4, ncclInt32, ncclSum, c->nccl, s);
+      if (r == ncclSuccess) r = rccl().AllReduce(b->shard.own_slab2.p, b->shard.own_slab2.p, sum_bytes / 8, ncclInt64, ncclSum, c->nccl, s);
       if (r != ncclSuccess) rc = fail(EPI_ERR_HIP, "ncclAllReduce failed: %s", rccl().GetErrorString(r));
       c->last_bytes = (int64_t)(cnt_bytes + sum_bytes);
     }

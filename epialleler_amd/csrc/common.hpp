@@ -70,12 +70,26 @@ static_assert(offsetof(Scalars, ntiles) == 0 && offsetof(Scalars, cursor) == 4 &
               offsetof(Scalars, pat_total) == 60 && sizeof(Scalars) == 64, "Scalars layout");
 
 // ---- device buffers that grow on demand --------------------------------------
+// A DevBuf owns its allocation: move-only, freed by its destructor (engine.hip; release() frees early).  The device of
+// the allocation must be current when it goes.  view() is the non-owning form -- a piece of somebody else's allocation
+// for a callee that takes a DevBuf: never freed, never counted, and ensure() beyond its size is an error.
 struct DevBuf {
   void *p = nullptr;
   size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf &) = delete; DevBuf &operator=(const DevBuf &) = delete;
+  DevBuf(DevBuf &&o) noexcept { *this = static_cast<DevBuf &&>(o); }
+  DevBuf &operator=(DevBuf &&o) noexcept {                    // the moved-from buffer is left empty
+    if (this != &o) { release(); p = o.p; cap = o.cap; owned = o.owned; o.p = nullptr; o.cap = 0; o.owned = true; }
+    return *this;
+  }
+  ~DevBuf();
+  static DevBuf view(void *p, size_t bytes) { DevBuf v; v.p = p; v.cap = bytes; v.owned = false; return v; }
   int ensure(size_t bytes);   // keeps contents only if no growth is needed
   void release();
   template <class T> T *as() const { return reinterpret_cast<T *>(p); }
+ private:
+  bool owned = true;
 };
 
 struct ProfEntry { double ms = 0; int64_t n = 0; };
@@ -121,11 +135,6 @@ struct SiteReportState {
   bool blocks = false;     // epi_batch_linkage_blocks_dev has run on the last linkage report ...
   int64_t nblock = 0;      // ... and found this many
   SiteScalars *scalars() const { return scal.as<SiteScalars>(); }
-  void release() {
-    for (DevBuf *d : {&cx, &rank, &key, &sctx, &counts, &flag, &out, &scal, &back, &blen, &bmean, &bflag, &bout, &cx_all, &counts_b,
-                      &frow, &fbits, &fpair, &fsite})
-      d->release();
-  }
 };
 
 // ---- per-read class counting shared by the per-read kernels and the fused CX tile kernel (per_read.hip) ----------
@@ -208,6 +217,76 @@ enum ReportKind {
   KIND_HETCMP = 8,          // finished heterogeneity comparison (on its first batch; the second is left at KIND_NONE)
   KIND_FDRP = 9,            // finished FDRP report
 };
+
+// ---- what a batch keeps besides its rows, one struct per owner (who owns a device buffer) ----------------------
+// The tile index (tiles.hip).  The tile table is a function of (rname, start, longest row, tile size, shared keys): while the
+// batch owns its columns the table of the last build is still valid for the same tile size and keys, and build_tiles skips the pass.
+struct TileIndex {
+  DevBuf tiles, nt_dev;                         // nt_dev: the tile count as the index pass left it in Scalars::ntiles
+  struct { int32_t T = 0, nt = 0, lmax = 0; std::vector<int64_t> shared; } built;   // what `tiles` was built for (T = 0: nothing)
+  // tile counts of this (immutable) batch by tile size, as found by earlier calls, and the index build's scanned per-block counts
+  struct { int32_t T = 0, nt = 0, lmax = 0; DevBuf bsum; } hint[4];
+  void forget() { for (auto &h : hint) h.T = 0; built.T = 0; }   // the rows changed: nothing remembered holds any more
+};
+
+// Row pool of a report: a slot per tile + an overflow region (the scheme: tiles.hip, with layout_pool).  Each report's
+// bind function names what it keeps in a .. f.
+struct RowPool {
+  DevBuf tile_nrow, tile_base, tile_out;
+  DevBuf key, a, b, c, d, e, f;
+  size_t row_cap = 0, row_cap2 = 0;             // rows that fit key / a / b; rows that fit d / e (lMHL doubles)
+  DevBuf heavy_list, heavy_slab, heavy_sums;    // ultra-deep tiles: ids and dense counters (+ lMHL sums)
+};
+
+struct CxState {                                // cx_report.hip
+  uint32_t slot_cg = 0, slot_wide = 0;          // pool rows per tile slot: CpG-only reports / reports with CHG, CHH (adapted per call)
+  uint32_t last_slot = 0, last_ovf = 0;         // layout of the last CX report (the sharded second half emits into it)
+  int last_np = 0; uint32_t last_ctx_of_plane = 0;   // ... its number of reported contexts and their codes
+  // CX reports written straight into the caller's columns (direct mode): the tile offsets and row counts of the last
+  // pool report, for its context mask (key = mask | 1 << 31; 0: none), tile size and tile count
+  struct { DevBuf off, cnt; uint32_t key = 0; int32_t T = 0, nt = 0; int64_t nrow = 0; } kept;
+  // One host synchronisation for a sharded CX report (comm.hip): with `defer` set the first half queues its kernels and
+  // returns without reading anything back; the second half reads and checks everything at once.  Allowed only when an
+  // earlier report on this (immutable) batch and tile size found no ultra-deep tile that the host would have to finish
+  // before the slab may travel (noheavy_T / _rows: the tile size and threshold that was observed for).
+  bool defer = false, deferred = false; uint32_t def_heavy_done = 0; int32_t noheavy_T = 0, noheavy_rows = 0;
+  DevBuf deep_list;                             // tiles the lean kernel hands to the general one
+  DevBuf pass_tmp;                              // pass flags when thresholding could not be fused and the caller wants none
+  DevBuf thr_tab;                               // fused thresholding: decision table for thr_tab_prm over totals 0..thr_tab_len
+  int32_t thr_tab_len = -1; ThrParams thr_tab_prm = {0, 0.0, 0.0};
+};
+
+struct MhlState {                               // mhl_report.hip, mhl_fused.hip
+  DevBuf m, h, blk, cont, cur;                  // pass 1: stretch records, per-read info, record table, block carries
+  size_t rec_cap = 0;                           // records that fit m
+  uint32_t slot = 0, last_slot = 0, last_ovf = 0, ctx_mask = 0;   // pool rows per tile slot and the last report's layout, as for CX; its contexts
+  DevBuf keep_tab;                              // fused lMHL: passing out-of-context counts per total (k_mhl_keep_table)
+  int32_t keep_len = -1; double keep_oo = 0.0;
+  uint32_t fused_slot = 0;                      // `slot` of the fused kernel (1024-position tiles)
+  bool prefer_wide = false;                     // most tiles of the last fused lMHL report needed the u64 sums: start with that variant
+  uint32_t prefer_wide_H = 0;                   // ... learned for this haplotype clamp H (the sums shrink with H: a smaller one probes the fast variant again)
+  bool prefer_fold = false;                     // ... many held more than 255 rows: use the kernel with the folded call counters
+  DevBuf fold_slab;                             // call counters of tiles over 255 rows (kernels built without the LDS fold array)
+};
+
+// multi-GPU shared tiles (comm.hip): which tiles dump their raw sums into a slab, and the slab(s) attached for them
+enum SlabKind { SLAB_NONE, SLAB_CX, SLAB_MHL, SLAB_MHL_FUSED };   // _MHL: k_mhl_tiles' layout; _MHL_FUSED: the fused kernel's (mhl_common.hpp)
+struct ShardState {
+  std::vector<int64_t> keys, dev_keys;          // dev_*: what d_keys / d_owned currently hold
+  std::vector<int32_t> owned, dev_owned;
+  DevBuf d_keys, d_owned, d_slot_tile;
+  DevBuf own_slab, own_slab2;                   // the slabs of the library's own sharded entry points
+  std::vector<std::shared_ptr<epi_shard_plan>> plans;
+  SlabKind kind = SLAB_NONE;                    // what is attached (the caller's memory) ...
+  int32_t *d_slab = nullptr;                    // ... SLAB_CX
+  int32_t *d_mhl_cnt_slab = nullptr;            // ... SLAB_MHL, SLAB_MHL_FUSED: counters and 64-bit sums
+  int64_t *d_mhl_sum_slab = nullptr;
+};
+
+struct PatternStats {
+  int64_t extract_groups = 0, extract_pairs = 0, extract_scratch = 0;        // last epi_batch_extract_patterns_multi: groups, pairs, peak scratch bytes
+  int64_t summarise_groups = 0, summarise_pairs = 0, summarise_fallback = 0; // last epi_batch_summarise_patterns_multi: groups, pairs, targets grouped on the host
+};
 }  // namespace epi
 
 struct epi_batch {
@@ -226,89 +305,41 @@ struct epi_batch {
   int congruent = 0;         // 0: rows as the caller laid them out; 4 / 16: off[x] = start[x] modulo this
   bool cols_owned = false;   // every column is the batch's own copy (uploaded, or adopted and realigned): nobody can change a row
   epi::DevBuf own_xm, own_off, own_len, own_rname, own_strand, own_start;
-
-  // reusable workspace
   epi::DevBuf stats;        // RowStats of the batch (k_row_stats, queued once at creation)
   bool stats_queued = false, stats_host = false;
   hipEvent_t stats_done = nullptr;          // recorded behind k_row_stats on the stream it was queued on
   epi::RowStats h_stats = {};   // host copy, fetched by the first report call (which raises the errors)
-  epi::DevBuf scan_tmp;
-  epi::DevBuf tiles, tile_nrow, tile_base, tile_out;
-  epi::DevBuf pool_key, pool_a, pool_b, pool_c, pool_d, pool_e, pool_f;
-  epi::DevBuf misc;         // epi::Scalars (256 bytes allocated)
-  epi::DevBuf mhl_m, mhl_h, mhl_blk, mhl_cont, mhl_cur;   // lMHL pass 1: stretch records, per-read info, record table, block carries
-  size_t mhl_rec_cap = 0;   // records that fit mhl_m
-  epi::DevBuf heavy_list, heavy_slab, heavy_sums;   // ultra-deep tiles: ids and dense counters (+ lMHL sums)
-  epi::DevBuf deep_list;                            // CX report: tiles the lean kernel hands to the general one
-  epi::DevBuf diag;                     // check / timing builds only
-  size_t pool_cap = 0;      // rows that fit pool_key/pool_a/pool_b
-  uint32_t cx_slot_cg = 0, cx_slot_wide = 0;   // pool rows per tile slot: CpG-only reports / reports with CHG, CHH (adapted per call)
-  uint32_t mhl_slot = 0, mhl_last_slot = 0, mhl_last_ovf = 0;   // the same for the lMHL report
-  uint32_t mhlf_slot = 0;                      // ... and its fused kernel (1024-position tiles)
-  bool mhlf_prefer_wide = false;               // most tiles of the last fused lMHL report needed the u64 sums: start with that variant
-  uint32_t mhlf_prefer_wide_H = 0;             // ... learned for this haplotype clamp H (the sums shrink with H: a smaller one probes the fast variant again)
-  bool mhlf_prefer_fold = false;               // ... many held more than 255 rows: use the kernel with the folded call counters
-  epi::DevBuf mhlf_fold_slab;                  // call counters of tiles over 255 rows (kernels built without the LDS fold array)
-  bool mhl_shared_fused = false;               // the lMHL slabs attached are in the fused kernel's layout (mhl_common.hpp)
-  uint32_t cx_last_slot = 0, cx_last_ovf = 0;  // layout of the last CX report (the sharded second half emits into it)
-  // CX reports written straight into the caller's columns (cx_report.hip, direct mode): the tile offsets and row counts
-  // of the last pool report, for its context mask (key = mask | 1 << 31; 0: none), tile size and tile count
-  epi::DevBuf cx_prev_off, cx_prev_cnt;
-  uint32_t cx_prev_key = 0;
-  int32_t cx_prev_T = 0, cx_prev_nt = 0;
-  int64_t cx_prev_nrow = 0;
-  // One host synchronisation for a sharded CX report (comm.hip): with cx_defer set the first half queues its kernels and
-  // returns without reading anything back; the second half reads and checks everything at once.  Allowed only when an
-  // earlier report on this (immutable) batch and tile size found no ultra-deep tile that the host would have to finish
-  // before the slab may travel (cx_noheavy_T / _rows: the tile size and threshold that was observed for).
-  bool cx_defer = false, cx_deferred = false;
-  uint32_t cx_def_heavy_done = 0;
-  int32_t cx_noheavy_T = 0, cx_noheavy_rows = 0;
-  int cx_last_np = 0;                          // ... its number of reported contexts and their codes
-  uint32_t cx_last_ctx_of_plane = 0;
-  epi::DevBuf pass_tmp;                        // pass flags when thresholding could not be fused and the caller wants none
-  epi::DevBuf host_io;                         // device side of the host-pointer calls (pass flags / per-read beta)
-  epi::DevBuf bf_flag;                         // base frequencies: the sites' sortedness verdict (base_freqs.hip)
-  int64_t patm_groups = 0, patm_pairs = 0, patm_scratch = 0;   // last epi_batch_extract_patterns_multi: groups, pairs, peak scratch bytes
-  int64_t pats_groups = 0, pats_pairs = 0, pats_fallback = 0;  // last epi_batch_summarise_patterns_multi: groups, pairs, targets grouped on the host
-  epi::DevBuf mhl_keep_tab;                    // fused lMHL: passing out-of-context counts per total (k_mhl_keep_table)
-  int32_t mhl_keep_len = -1;
-  double mhl_keep_oo = 0.0;
-  epi::DevBuf thr_tab;                         // fused thresholding: decision table for thr_tab_prm over totals 0..thr_tab_len
-  int32_t thr_tab_len = -1;
-  epi::ThrParams thr_tab_prm = {0, 0.0, 0.0};
-  size_t pool_cap2 = 0;     // rows that fit pool_d/pool_e (lMHL doubles)
+
+  epi::TileIndex tix;
+  epi::RowPool pool;
+  epi::CxState cx;
+  epi::MhlState mhl;
+  epi::ShardState shard;
+  epi::PatternStats pat;
   // the heterogeneity report, the linkage report with its blocks and the heterogeneity comparison (het_common.hpp): the
   // site table they count over and what the last of them left for its fetch; one of them is live on a batch at a time
   epi::SiteReportState sites;
+
+  // workspace every report shares
+  epi::DevBuf scan_tmp;
+  epi::DevBuf misc;         // epi::Scalars (256 bytes allocated)
+  epi::DevBuf diag;         // check / timing builds only
+  epi::DevBuf host_io;      // device side of the host-pointer calls (pass flags / per-read beta)
+  epi::DevBuf bf_flag;      // base frequencies: the sites' sortedness verdict (base_freqs.hip)
 
   // state of the last report (for fetch)
   epi::ReportKind last_kind = epi::KIND_NONE;
   int64_t last_nrow = 0;
   int32_t last_ntiles = 0;
-  int32_t tile_hint_T[4] = {0, 0, 0, 0};    // tile counts of this (immutable) batch by tile size, as found by earlier calls
-  int32_t tile_hint_nt[4] = {0, 0, 0, 0};
-  int32_t tile_hint_lmax[4] = {0, 0, 0, 0};
-  epi::DevBuf tile_bsum[4];                  // ... and the scanned per-block tile counts of the index build
-  // The tile table itself is a function of (rname, start, longest row, tile size, shared keys): while the batch owns its
-  // columns the table of the last build is still valid for the same tile size and keys, and build_tiles skips the pass.
-  int32_t tiles_T = 0, tiles_nt = 0, tiles_lmax = 0;
-  std::vector<int64_t> tiles_shared;
-  epi::DevBuf tiles_nt_dev;                  // the tile count as the index pass left it in Scalars::ntiles
-
-  // multi-GPU shared tiles
-  std::vector<int64_t> shared_keys;
-  std::vector<int32_t> shared_owned;
-  std::vector<int64_t> dev_shared_keys;      // what d_shared_keys / d_shared_owned currently hold
-  std::vector<int32_t> dev_shared_owned;
-  epi::DevBuf d_shared_keys, d_shared_owned, d_slot_tile;
-  int32_t *d_slab = nullptr;
-  epi::DevBuf own_slab, own_slab2;       // the slabs of the library's own sharded entry points (comm.hip)
-  std::vector<std::shared_ptr<epi_shard_plan>> shard_plans;
-  int32_t *d_mhl_cnt_slab = nullptr;     // lMHL shared tiles: counters and 64-bit sums
-  int64_t *d_mhl_sum_slab = nullptr;
-  uint32_t mhl_ctx_mask = 0;
 };
+
+// Somebody else may have changed the rows of this batch (a tile count remembered for it no longer holds): forget
+// everything that was derived from row contents.
+inline void batch_rows_changed(epi_batch *b) {
+  b->tix.forget();
+  b->cx.kept.key = 0;
+  b->cx.noheavy_T = 0;
+}
 
 namespace epi {
 
@@ -367,10 +398,7 @@ struct CallRec {
   uint8_t pad[6];
 };
 static_assert(sizeof(CallRec) == 48, "CallRec layout");
-struct CallWork {      // device buffers of the windows, grown on demand
-  DevBuf recs, cig, seq, ref, xm;
-  ~CallWork();
-};
+struct CallWork { DevBuf recs, cig, seq, ref, xm; };   // device buffers of the windows, grown on demand
 int call_methylation_window(epi_engine *eng, epi_genome *g, CallWork &wk, const CallRec *recs, int64_t nrec,
                             const uint32_t *cigar, int64_t ncig, const uint8_t *seq, int64_t nseq, int64_t nxm,
                             CallForm form, uint8_t *xm_out);
@@ -436,6 +464,8 @@ int layout_copy_range(const uint8_t *src, int64_t c0, int64_t c1, const int64_t 
 // `hinted` (may be null): the caller accepts a tile count remembered from an earlier call on this batch and tile size
 // (no host round trip in the middle of the index build) and verifies it against Scalars::ntiles at its own synchronisation.
 int build_tiles(epi_batch *b, hipStream_t s, int32_t tile_positions, RowStats *h_stats, int32_t *ntiles_out, bool *hinted = nullptr);
+// the key bookkeeping and uploads of the *_set_shared entry points (tiles.hip)
+int attach_shared(epi_batch *b, const int64_t *h_keys, const int32_t *h_owned, int32_t nshared);
 
 // Row pool of a report: a slot per tile + an overflow region (the scheme: tiles.hip, with layout_pool)
 struct PoolLayout {

@@ -186,10 +186,7 @@ __global__ __launch_bounds__(CXC_WG) void k_reg_emit(RegIn t, const uint32_t *__
 
 // ---- host --------------------------------------------------------------------------------------------------------------
 
-struct Scratch {                        // released when the call returns, as assemble_templates' buffers are
-  DevBuf flag, off, brow, scal, scan_tmp;
-  ~Scratch() { flag.release(); off.release(); brow.release(); scal.release(); scan_tmp.release(); }
-};
+struct Scratch { DevBuf flag, off, brow, scal, scan_tmp; };   // (goes when the call returns)
 
 static int read_words(epi_engine *e, hipStream_t s, const uint32_t *d_src, int nwords, uint32_t *h_dst) {   // one synchronisation
   EPI_HIP(hipMemcpyAsync(e->h_scalars, d_src, (size_t)nwords * 4, hipMemcpyDeviceToHost, s));

@@ -1415,11 +1415,11 @@ static void launch_cx_emit_slab(int np, int nshared, hipStream_t s, const Cx2Arg
 }
 
 static int ensure_pool(epi_batch *b, size_t rows) {
-  if (rows <= b->pool_cap && b->pool_key.p) return EPI_OK;
-  EPI_TRY(b->pool_key.ensure(rows * 4));
-  EPI_TRY(b->pool_a.ensure(rows * 4));
-  EPI_TRY(b->pool_b.ensure(rows * 4));
-  b->pool_cap = rows;
+  if (rows <= b->pool.row_cap && b->pool.key.p) return EPI_OK;
+  EPI_TRY(b->pool.key.ensure(rows * 4));
+  EPI_TRY(b->pool.a.ensure(rows * 4));
+  EPI_TRY(b->pool.b.ensure(rows * 4));
+  b->pool.row_cap = rows;
   return EPI_OK;
 }
 
@@ -1490,7 +1490,7 @@ static bool make_fused_lut(const CxThreshold &t, uint32_t ctx_of_plane, int np, 
 
 // Direct mode: rows of the report whose tile offsets the batch keeps (cx_prev_*) if it had these contexts, else -1.
 static int64_t cx_recorded_nrow(const epi_batch *b, uint32_t ctx_mask) {
-  return b->cx_prev_key == (ctx_mask | 0x80000000u) ? b->cx_prev_nrow : -1;
+  return b->cx.kept.key == (ctx_mask | 0x80000000u) ? b->cx.kept.nrow : -1;
 }
 
 // What one report call has decided before it queues a tile kernel.
@@ -1511,7 +1511,7 @@ struct CxPlan {
 // A remembered tile count that the index pass could not confirm: the rows were changed under the batch.
 static int cx_check_tile_count(epi_batch *b, bool hinted, uint32_t counted, int32_t nt) {
   if (!hinted || counted == (uint32_t)nt) return EPI_OK;
-  for (int i = 0; i < 4; i++) b->tile_hint_T[i] = 0;
+  batch_rows_changed(b);
   return fail(EPI_ERR_STATE, "the rows of this batch changed since an earlier report (tile count %u, was %d)", counted, nt);
 }
 
@@ -1529,23 +1529,23 @@ static int cx_setup_threshold(epi_batch *b, const CxThreshold &thr, const RowSta
     a.fill4 = fill4;
     a.pass_out = d_pass_out;
     // (field by field: the caller's struct may carry padding; doubles bitwise, so that a NaN threshold compares equal to itself)
-    const bool same = b->thr_tab_len == st.max_len && b->thr_tab_prm.min_n_ctx == thr.prm.min_n_ctx &&
-                      memcmp(&b->thr_tab_prm.min_ctx_meth_frac, &thr.prm.min_ctx_meth_frac, sizeof(double)) == 0 &&
-                      memcmp(&b->thr_tab_prm.max_ooctx_meth_frac, &thr.prm.max_ooctx_meth_frac, sizeof(double)) == 0;
+    const bool same = b->cx.thr_tab_len == st.max_len && b->cx.thr_tab_prm.min_n_ctx == thr.prm.min_n_ctx &&
+                      memcmp(&b->cx.thr_tab_prm.min_ctx_meth_frac, &thr.prm.min_ctx_meth_frac, sizeof(double)) == 0 &&
+                      memcmp(&b->cx.thr_tab_prm.max_ooctx_meth_frac, &thr.prm.max_ooctx_meth_frac, sizeof(double)) == 0;
     if (!same) {
-      EPI_TRY(b->thr_tab.ensure((size_t)(st.max_len + 1) * 4));
-      hipLaunchKernelGGL(k_thr_table, dim3((unsigned)(st.max_len / 256 + 1)), dim3(256), 0, s, thr.prm, st.max_len, b->thr_tab.as<uint32_t>());
+      EPI_TRY(b->cx.thr_tab.ensure((size_t)(st.max_len + 1) * 4));
+      hipLaunchKernelGGL(k_thr_table, dim3((unsigned)(st.max_len / 256 + 1)), dim3(256), 0, s, thr.prm, st.max_len, b->cx.thr_tab.as<uint32_t>());
       EPI_HIP(hipGetLastError());
-      b->thr_tab_len = st.max_len;
-      memset(&b->thr_tab_prm, 0, sizeof(ThrParams));
-      b->thr_tab_prm.min_n_ctx = thr.prm.min_n_ctx;
-      b->thr_tab_prm.min_ctx_meth_frac = thr.prm.min_ctx_meth_frac;
-      b->thr_tab_prm.max_ooctx_meth_frac = thr.prm.max_ooctx_meth_frac;
+      b->cx.thr_tab_len = st.max_len;
+      memset(&b->cx.thr_tab_prm, 0, sizeof(ThrParams));
+      b->cx.thr_tab_prm.min_n_ctx = thr.prm.min_n_ctx;
+      b->cx.thr_tab_prm.min_ctx_meth_frac = thr.prm.min_ctx_meth_frac;
+      b->cx.thr_tab_prm.max_ooctx_meth_frac = thr.prm.max_ooctx_meth_frac;
     }
-    a.thr_tab = b->thr_tab.as<uint32_t>();
+    a.thr_tab = b->cx.thr_tab.as<uint32_t>();
   } else if (b->n > 0) {
     int32_t *dst = d_pass_out;
-    if (!dst) { EPI_TRY(b->pass_tmp.ensure((size_t)b->n * 4)); dst = b->pass_tmp.as<int32_t>(); }
+    if (!dst) { EPI_TRY(b->cx.pass_tmp.ensure((size_t)b->n * 4)); dst = b->cx.pass_tmp.as<int32_t>(); }
     EPI_TRY(epi_batch_threshold_reads_dev(b, thr.cls[0], thr.cls[1], thr.cls[2] ? thr.cls[2] : "", thr.cls[3] ? thr.cls[3] : "",
                                           thr.prm.min_n_ctx, thr.prm.min_ctx_meth_frac, thr.prm.max_ooctx_meth_frac, dst, s));
     *d_pass = dst;
@@ -1555,30 +1555,30 @@ static int cx_setup_threshold(epi_batch *b, const CxThreshold &thr, const RowSta
 
 // The remembered slot size of the row pool (layout_pool, tiles.hip): it starts at a typical density of reported cytosines
 // (CpG ~6 % of the (pos,strand) cells of a tile, all contexts ~40 %) and is doubled by cx_report_impl.
-static uint32_t &cx_slot_state(epi_batch *b, uint32_t ctx_mask) { return (ctx_mask & ~(1u << 7)) ? b->cx_slot_wide : b->cx_slot_cg; }
+static uint32_t &cx_slot_state(epi_batch *b, uint32_t ctx_mask) { return (ctx_mask & ~(1u << 7)) ? b->cx.slot_wide : b->cx.slot_cg; }
 
 static int cx_layout_pool(epi_batch *b, uint32_t ctx_mask, CxPlan &p) {
   uint32_t &slot_state = cx_slot_state(b, ctx_mask);
   if (!slot_state) slot_state = (ctx_mask & ~(1u << 7)) ? (uint32_t)(3 * p.T) / 4 : (uint32_t)p.T / 8;
   EPI_TRY(layout_pool(b, slot_state, p.T, p.nt, p.headroom, options().cx_slot, ensure_pool, &p.pool));   // test hook (EPIHIP_CX_SLOT)
-  b->cx_last_slot = p.pool.slot;
-  b->cx_last_ovf = (uint32_t)p.pool.ovf_base;
+  b->cx.last_slot = p.pool.slot;
+  b->cx.last_ovf = (uint32_t)p.pool.ovf_base;
   return EPI_OK;
 }
 
 // The batch's tile table, row pool (as it is now: a regrown pool is bound again) and the layout of its last report
 static void cx_bind_pool(const epi_batch *b, Cx2Args &a) {
-  a.tiles = b->tiles.as<Tile>();
+  a.tiles = b->tix.tiles.as<Tile>();
   a.cursor = &report_scalars(b)->cursor;
-  a.tile_nrow = b->tile_nrow.as<uint32_t>();
-  a.tile_base = b->tile_base.as<uint32_t>();
-  a.slab = b->d_slab;
-  a.pool_key = b->pool_key.as<uint32_t>();
-  a.pool_meth = b->pool_a.as<uint32_t>();
-  a.pool_unmeth = b->pool_b.as<uint32_t>();
-  a.pool_cap = (uint32_t)(b->pool_cap > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : b->pool_cap);
-  a.slot_rows = b->cx_last_slot;
-  a.ovf_base = b->cx_last_ovf;
+  a.tile_nrow = b->pool.tile_nrow.as<uint32_t>();
+  a.tile_base = b->pool.tile_base.as<uint32_t>();
+  a.slab = b->shard.d_slab;
+  a.pool_key = b->pool.key.as<uint32_t>();
+  a.pool_meth = b->pool.a.as<uint32_t>();
+  a.pool_unmeth = b->pool.b.as<uint32_t>();
+  a.pool_cap = (uint32_t)(b->pool.row_cap > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : b->pool.row_cap);
+  a.slot_rows = b->cx.last_slot;
+  a.ovf_base = b->cx.last_ovf;
 }
 
 // Everything else the tile kernels of this report read: the rows, the heavy-tile thresholds and lists, the deep list.
@@ -1592,14 +1592,14 @@ static int cx_fill_args(epi_batch *b, const CxPlan &p, const int32_t *d_pass, hi
   if (a.heavy_rows > 16384) a.heavy_rows = 16384;          // u16 pairs and the packed coverage halves: a base adds at most 2
   a.heavy_chunk = a.heavy_rows / 4 > 64 ? a.heavy_rows / 4 : 64;
   if (a.heavy_chunk > 256) a.heavy_chunk = 256;            // (a 20 000-row pile-up is then 80 work items, not 5)
-  EPI_TRY(b->heavy_list.ensure((size_t)p.nt * 4));
-  a.heavy_list = b->heavy_list.as<uint32_t>();
+  EPI_TRY(b->pool.heavy_list.ensure((size_t)p.nt * 4));
+  a.heavy_list = b->pool.heavy_list.as<uint32_t>();
   a.heavy_count = &sc->heavy_count;
   a.heavy_max = &sc->heavy_max;
   a.heavy_slab = nullptr;
   if (p.per_tile) {
-    EPI_TRY(b->deep_list.ensure((size_t)p.nt * 4));
-    a.deep_list = b->deep_list.as<uint32_t>();
+    EPI_TRY(b->cx.deep_list.ensure((size_t)p.nt * 4));
+    a.deep_list = b->cx.deep_list.as<uint32_t>();
     a.deep_count = &sc->deep_count;
   }
   a.nrows = b->n;
@@ -1636,8 +1636,8 @@ static int cx_queue_attempt(epi_batch *b, const CxPlan &p, Cx2Args &a, hipStream
   // them are split, reduced and emitted by fixed-grid launches queued right here -- no host round trip for one pile-up
   // in a WGS batch; a larger number is finished by cx_finish_pool_run, once the count is known.
   if (p.chained) {
-    EPI_TRY(b->heavy_slab.ensure((size_t)CX_HEAVY_CAP * kCxPlanes * p.T * 4));
-    a.heavy_slab = b->heavy_slab.as<int32_t>();
+    EPI_TRY(b->pool.heavy_slab.ensure((size_t)CX_HEAVY_CAP * kCxPlanes * p.T * 4));
+    a.heavy_slab = b->pool.heavy_slab.as<int32_t>();
     a.heavy_first = 0;
     EPI_HIP(hipMemsetAsync(a.heavy_slab, 0, (size_t)CX_HEAVY_CAP * kCxPlanes * p.T * 4, s));
     prof_begin("cx_heavy", s);
@@ -1653,23 +1653,23 @@ static int cx_queue_attempt(epi_batch *b, const CxPlan &p, Cx2Args &a, hipStream
 // ceil(rows / chunk) workgroups, reduce in HBM, emit, rescan, read again.
 static int cx_finish_pool_run(epi_batch *b, const CxPlan &p, Cx2Args &a, hipStream_t s, int attempt, Scalars *host, bool *host_heavy) {
   Scalars *sc = report_scalars(b);
-  EPI_TRY(scan_exclusive_u32(a.tile_nrow, b->tile_out.as<uint32_t>(), p.nt, &sc->rows, b->scan_tmp, s));
+  EPI_TRY(scan_exclusive_u32(a.tile_nrow, b->pool.tile_out.as<uint32_t>(), p.nt, &sc->rows, b->scan_tmp, s));
   EPI_TRY(read_report_scalars(b, s, host));
   EPI_TRY(cx_check_tile_count(b, p.nt_hinted, host->ntiles, p.nt));
   const uint32_t heavy_done = p.chained ? CX_HEAVY_CAP : 0u;
   if (host->heavy_count > heavy_done) {
     *host_heavy = true;
-    b->cx_noheavy_T = 0;
+    b->cx.noheavy_T = 0;
     const uint32_t nheavy = host->heavy_count - heavy_done, nchunks = (host->heavy_max + (uint32_t)a.heavy_chunk - 1) / (uint32_t)a.heavy_chunk;
     a.heavy_first = (int)heavy_done;
-    EPI_TRY(b->heavy_slab.ensure((size_t)nheavy * kCxPlanes * p.T * 4));
-    a.heavy_slab = b->heavy_slab.as<int32_t>();
+    EPI_TRY(b->pool.heavy_slab.ensure((size_t)nheavy * kCxPlanes * p.T * 4));
+    a.heavy_slab = b->pool.heavy_slab.as<int32_t>();
     EPI_HIP(hipMemsetAsync(a.heavy_slab, 0, (size_t)nheavy * kCxPlanes * p.T * 4, s));
     prof_begin("cx_heavy", s);
     launch_cx(true, p.np, p.fused, p.lean, p.shape_heavy, p.nt, dim3(nchunks, nheavy), s, a);
     prof_end("cx_heavy", s);
     EPI_HIP(hipGetLastError());
-    EPI_TRY(scan_exclusive_u32(a.tile_nrow, b->tile_out.as<uint32_t>(), p.nt, &sc->rows, b->scan_tmp, s));
+    EPI_TRY(scan_exclusive_u32(a.tile_nrow, b->pool.tile_out.as<uint32_t>(), p.nt, &sc->rows, b->scan_tmp, s));
     EPI_TRY(read_report_scalars(b, s, host));
   }
 #ifdef EPI_CHECK
@@ -1687,15 +1687,15 @@ static int cx_finish_pool_run(epi_batch *b, const CxPlan &p, Cx2Args &a, hipStre
 // Keeps this pool report's tile offsets for the next report with these contexts (device copies; the pool and the row counts
 // are the next report's to overwrite)
 static int cx_keep_offsets(epi_batch *b, uint32_t ctx_mask, const CxPlan &p, uint32_t nrow, hipStream_t s) {
-  if (b->cx_prev_key == (ctx_mask | 0x80000000u) && b->cx_prev_T == p.T && b->cx_prev_nt == p.nt) return EPI_OK;
-  EPI_TRY(b->cx_prev_off.ensure((size_t)p.nt * 4));
-  EPI_TRY(b->cx_prev_cnt.ensure((size_t)p.nt * 4));
-  EPI_HIP(hipMemcpyAsync(b->cx_prev_off.p, b->tile_out.p, (size_t)p.nt * 4, hipMemcpyDeviceToDevice, s));
-  EPI_HIP(hipMemcpyAsync(b->cx_prev_cnt.p, b->tile_nrow.p, (size_t)p.nt * 4, hipMemcpyDeviceToDevice, s));
-  b->cx_prev_key = ctx_mask | 0x80000000u;
-  b->cx_prev_T = p.T;
-  b->cx_prev_nt = p.nt;
-  b->cx_prev_nrow = nrow;
+  if (b->cx.kept.key == (ctx_mask | 0x80000000u) && b->cx.kept.T == p.T && b->cx.kept.nt == p.nt) return EPI_OK;
+  EPI_TRY(b->cx.kept.off.ensure((size_t)p.nt * 4));
+  EPI_TRY(b->cx.kept.cnt.ensure((size_t)p.nt * 4));
+  EPI_HIP(hipMemcpyAsync(b->cx.kept.off.p, b->pool.tile_out.p, (size_t)p.nt * 4, hipMemcpyDeviceToDevice, s));
+  EPI_HIP(hipMemcpyAsync(b->cx.kept.cnt.p, b->pool.tile_nrow.p, (size_t)p.nt * 4, hipMemcpyDeviceToDevice, s));
+  b->cx.kept.key = ctx_mask | 0x80000000u;
+  b->cx.kept.T = p.T;
+  b->cx.kept.nt = p.nt;
+  b->cx.kept.nrow = nrow;
   return EPI_OK;
 }
 
@@ -1731,16 +1731,16 @@ static int cx_report_impl(epi_batch *b, const int32_t *d_pass, const CxThreshold
   if (thr) EPI_TRY(cx_setup_threshold(b, *thr, st, p, d_pass_out, s, a, &d_pass));
   if (p.nt == 0 || p.np == 0) {                            // no rows, or a context string without H/X/Z: an empty table
     // (a rank of a sharded run without rows still takes part in the exchange: its second half returns the empty table)
-    b->last_kind = !b->shared_keys.empty() && b->d_slab ? KIND_CX_SHARED : KIND_CX; b->last_nrow = 0; b->last_ntiles = 0;
+    b->last_kind = b->shard.kind == SLAB_CX ? KIND_CX_SHARED : KIND_CX; b->last_nrow = 0; b->last_ntiles = 0;
     return EPI_OK;
   }
   const int T = p.T, np = p.np;
   const int32_t nt = p.nt;
 
-  EPI_TRY(b->tile_nrow.ensure((size_t)nt * 4));
-  EPI_TRY(b->tile_base.ensure((size_t)nt * 4));
-  EPI_TRY(b->tile_out.ensure((size_t)(nt + 1) * 4));
-  p.nshared = (int32_t)b->shared_keys.size();
+  EPI_TRY(b->pool.tile_nrow.ensure((size_t)nt * 4));
+  EPI_TRY(b->pool.tile_base.ensure((size_t)nt * 4));
+  EPI_TRY(b->pool.tile_out.ensure((size_t)(nt + 1) * 4));
+  p.nshared = (int32_t)b->shard.keys.size();
   p.headroom = p.nshared > 0 ? (size_t)p.nshared * 2 * T : 0;
   EPI_TRY(cx_layout_pool(b, ctx_mask, p));
   // Single-context reports run the LEAN kernel (u8 counters, no folds).  Where a position may be covered by more than
@@ -1752,22 +1752,22 @@ static int cx_report_impl(epi_batch *b, const int32_t *d_pass, const CxThreshold
   // the heavy-tile kernel is the general one (three chunks per lane)
   p.shape = np > 1 ? pick_cxp_group(st) * 8 : pick_cx_shape(st, T, p.fused, p.lean);
   p.shape_heavy = np > 1 ? p.shape : pick_cx_shape(st, T, p.fused, false);
-  b->cx_last_np = np;
-  b->cx_last_ctx_of_plane = a.ctx_of_plane;
+  b->cx.last_np = np;
+  b->cx.last_ctx_of_plane = a.ctx_of_plane;
   EPI_TRY(check_grid(((int64_t)nt + 7) / 8 * 8, np == 1 && p.lean ? cx2_wg<true>() : CX_WG, "CX tile kernel"));
   EPI_TRY(cx_fill_args(b, p, d_pass, s, a));
-  b->cx_deferred = false;
+  b->cx.deferred = false;
 
   // Direct mode, at most once and in front of the pool runs: the rows go straight into the caller's columns and the one
   // synchronisation brings back the number of tiles whose row count differed from the kept one (Scalars::cursor: no pool).
   const int64_t rec = cx_recorded_nrow(b, ctx_mask);
   bool direct = d_cols && cap > 0 && cap <= 0x7FFFFFFF && rec >= 0 && rec <= cap && st.deep == 0 && p.nshared == 0 && options().cx_direct &&
-                b->cx_prev_T == T && b->cx_prev_nt == nt;
+                b->cx.kept.T == T && b->cx.kept.nt == nt;
   for (int i = 0; direct && i < 6; i++) if (!d_cols[i]) direct = false;
   if (direct) {
     Cx2Args d = a;
-    d.prev_off = b->cx_prev_off.as<uint32_t>();
-    d.prev_nrow = b->cx_prev_cnt.as<uint32_t>();
+    d.prev_off = b->cx.kept.off.as<uint32_t>();
+    d.prev_nrow = b->cx.kept.cnt.as<uint32_t>();
     d.mismatch = d.cursor;
     for (int i = 0; i < 6; i++) d.out[i] = d_cols[i];
     d.out_cap = cap;
@@ -1779,11 +1779,11 @@ static int cx_report_impl(epi_batch *b, const int32_t *d_pass, const CxThreshold
     if (host.cursor == 0) {
       b->last_kind = KIND_NONE;                                    // (nothing to fetch: the rows are where the caller wants them)
       b->last_nrow = 0;
-      *nrow_out = b->cx_prev_nrow;
+      *nrow_out = b->cx.kept.nrow;
       if (written) *written = 1;
       return EPI_OK;
     }
-    b->cx_prev_key = 0;                                    // the rows of this batch changed: the table from the pool, whose offsets are kept instead
+    b->cx.kept.key = 0;                                    // the rows of this batch changed: the table from the pool, whose offsets are kept instead
   }
 
   // Pool runs: at most two, the second with a pool regrown to the size the first one asked for.
@@ -1792,12 +1792,12 @@ static int cx_report_impl(epi_batch *b, const int32_t *d_pass, const CxThreshold
   for (int run = 0;; run++) {
     cx_bind_pool(b, a);
     EPI_TRY(cx_queue_attempt(b, p, a, s, direct || run > 0));
-    if (run == 0 && b->cx_defer && p.nshared > 0 && p.nt_hinted && b->cx_noheavy_T == T && b->cx_noheavy_rows == a.heavy_rows) {
+    if (run == 0 && b->cx.defer && p.nshared > 0 && p.nt_hinted && b->cx.noheavy_T == T && b->cx.noheavy_rows == a.heavy_rows) {
       // sharded report with one host synchronisation: nothing is read back here; epi_batch_cx_finish_shared checks the tile
       // count, the heavy-tile count and the pool at its own synchronisation (comm.hip reruns the first half into a scratch
       // slab if the pool turns out too small)
-      b->cx_deferred = true;
-      b->cx_def_heavy_done = p.chained ? CX_HEAVY_CAP : 0u;
+      b->cx.deferred = true;
+      b->cx.def_heavy_done = p.chained ? CX_HEAVY_CAP : 0u;
       b->last_kind = KIND_CX_SHARED;
       return EPI_OK;
     }
@@ -1806,12 +1806,12 @@ static int cx_report_impl(epi_batch *b, const int32_t *d_pass, const CxThreshold
     if (run == 1) return fail(EPI_ERR_STATE, "row pool overflow after regrow");
     EPI_TRY(ensure_pool(b, p.pool.ovf_base + host.cursor + (host.cursor >> 4) + 1024 + p.headroom));   // exact need is known now: rerun once
     if (p.nshared > 0)   // the rerun adds into the slab again
-      EPI_HIP(hipMemsetAsync(b->d_slab, 0, (size_t)p.nshared * kCxPlanes * T * 4, s));
+      EPI_HIP(hipMemsetAsync(b->shard.d_slab, 0, (size_t)p.nshared * kCxPlanes * T * 4, s));
   }
   uint32_t &slot_state = cx_slot_state(b, ctx_mask);
   if (host.cursor > host.rows / 8 && slot_state < (uint32_t)(2 * T)) slot_state *= 2;   // too many tiles outgrew their slot
   // (no ultra-deep tile was left for the host to finish: a later sharded report on this batch may defer its synchronisation)
-  if (!host_heavy) { b->cx_noheavy_T = T; b->cx_noheavy_rows = a.heavy_rows; }
+  if (!host_heavy) { b->cx.noheavy_T = T; b->cx.noheavy_rows = a.heavy_rows; }
   if (p.nshared > 0) { b->last_kind = KIND_CX_SHARED; return EPI_OK; }   // caller continues with epi_batch_cx_finish_shared
   b->last_kind = KIND_CX;
   b->last_nrow = host.rows;
@@ -1886,19 +1886,19 @@ int epi_batch_cx_finish_shared(epi_batch *b, const char *ctx, void *stream, int6
   Cx2Args a;
   memset(&a, 0, sizeof(a));
   cx_bind_pool(b, a);
-  a.ctx_of_plane = b->cx_last_ctx_of_plane;
-  launch_cx_emit_slab(b->cx_last_np, (int)b->shared_keys.size(), s, a, b->d_shared_owned.as<int32_t>(),
-                      b->d_slot_tile.as<int32_t>());
+  a.ctx_of_plane = b->cx.last_ctx_of_plane;
+  launch_cx_emit_slab(b->cx.last_np, (int)b->shard.keys.size(), s, a, b->shard.d_owned.as<int32_t>(),
+                      b->shard.d_slot_tile.as<int32_t>());
   EPI_HIP(hipGetLastError());
-  EPI_TRY(scan_exclusive_u32(a.tile_nrow, b->tile_out.as<uint32_t>(), nt, &report_scalars(b)->rows, b->scan_tmp, s));
+  EPI_TRY(scan_exclusive_u32(a.tile_nrow, b->pool.tile_out.as<uint32_t>(), nt, &report_scalars(b)->rows, b->scan_tmp, s));
   Scalars host;                                             // overflow rows handed out, total rows: one sync
   EPI_TRY(read_report_scalars(b, s, &host));
-  if (b->cx_deferred) {
+  if (b->cx.deferred) {
     // the first half read nothing back: its checks happen here, with the report's only synchronisation
-    b->cx_deferred = false;
+    b->cx.deferred = false;
     EPI_TRY(cx_check_tile_count(b, true, host.ntiles, nt));
-    if (host.heavy_count > b->cx_def_heavy_done) {
-      b->cx_noheavy_T = 0;
+    if (host.heavy_count > b->cx.def_heavy_done) {
+      batch_rows_changed(b);
       return fail(EPI_ERR_STATE, "ultra-deep tiles appeared in a batch that had none (%u): the rows of this batch changed", host.heavy_count);
     }
     if ((size_t)a.ovf_base + host.cursor > a.pool_cap) {      // (the cursor has served the shared tiles' rows as well by now)
@@ -1919,31 +1919,10 @@ int epi_batch_cx_finish_shared(epi_batch *b, const char *ctx, void *stream, int6
 
 int epi_batch_cx_set_shared(epi_batch *b, const int64_t *h_keys, const int32_t *h_owned, int32_t nshared,
                             int32_t *d_slab) {
-  if (!b || nshared < 0 || (nshared > 0 && (!h_keys || !h_owned || !d_slab)))
-    return fail(EPI_ERR_ARG, "epi_batch_cx_set_shared: bad arguments");
-  for (int32_t i = 1; i < nshared; i++)
-    if (h_keys[i - 1] >= h_keys[i]) return fail(EPI_ERR_ARG, "epi_batch_cx_set_shared: keys must be strictly increasing");
-  EPI_HIP(hipSetDevice(b->eng->device));
-  b->shared_keys.assign(h_keys, h_keys + nshared);
-  b->shared_owned.assign(h_owned, h_owned + nshared);
-  // a sharded run attaches the same keys for every report: skip the copies when the device already holds them
-  if (nshared > 0 && b->dev_shared_keys == b->shared_keys && b->dev_shared_owned == b->shared_owned) {
-    b->d_slab = d_slab;
-    b->d_mhl_cnt_slab = nullptr;
-    b->d_mhl_sum_slab = nullptr;
-    return EPI_OK;
-  }
-  b->d_slab = nshared > 0 ? d_slab : nullptr;
-  b->d_mhl_cnt_slab = nullptr;
-  b->d_mhl_sum_slab = nullptr;
-  if (nshared > 0) {
-    EPI_TRY(b->d_shared_keys.ensure((size_t)nshared * 8));
-    EPI_TRY(b->d_shared_owned.ensure((size_t)nshared * 4));
-    EPI_HIP(hipMemcpy(b->d_shared_keys.p, h_keys, (size_t)nshared * 8, hipMemcpyHostToDevice));
-    EPI_HIP(hipMemcpy(b->d_shared_owned.p, h_owned, (size_t)nshared * 4, hipMemcpyHostToDevice));
-    b->dev_shared_keys = b->shared_keys;
-    b->dev_shared_owned = b->shared_owned;
-  }
+  if (nshared > 0 && !d_slab) return fail(EPI_ERR_ARG, "epi_batch_cx_set_shared: bad arguments");
+  EPI_TRY(attach_shared(b, h_keys, h_owned, nshared));
+  b->shard.kind = nshared > 0 ? SLAB_CX : SLAB_NONE;
+  b->shard.d_slab = nshared > 0 ? d_slab : nullptr;
   return EPI_OK;
 }
 
@@ -1962,8 +1941,8 @@ int epi_batch_tile_key_range_for(epi_batch *b, int tile_positions, void *stream,
   EPI_TRY(build_tiles(b, s, T, &st, &nt));
   if (nt == 0) return EPI_OK;
   Tile t0, t1;
-  EPI_TRY(read_scalars(b, s, b->tiles.as<Tile>(), sizeof(Tile), &t0));
-  EPI_TRY(read_scalars(b, s, b->tiles.as<Tile>() + (nt - 1), sizeof(Tile), &t1));
+  EPI_TRY(read_scalars(b, s, b->tix.tiles.as<Tile>(), sizeof(Tile), &t0));
+  EPI_TRY(read_scalars(b, s, b->tix.tiles.as<Tile>() + (nt - 1), sizeof(Tile), &t1));
   auto key = [T](const Tile &t) { return ((int64_t)t.rname << 32) | (int64_t)(uint32_t)((t.pos0 + kPosBias) / T); };
   *first_key = key(t0);
   *last_key = key(t1);
@@ -1979,9 +1958,9 @@ int epi_batch_cx_fetch_dev(epi_batch *b, int32_t *const d_cols[6], void *stream)
   hipStream_t s = pick_stream(b, stream);
   const unsigned nb = (unsigned)((b->last_ntiles + 3) / 4);
   prof_begin("gather", s);
-  hipLaunchKernelGGL(k_cx_gather, dim3(nb), dim3(256), 0, s, b->tiles.as<Tile>(), b->tile_out.as<uint32_t>(),
-                     b->tile_nrow.as<uint32_t>(), b->tile_base.as<uint32_t>(), b->last_ntiles, b->pool_key.as<uint32_t>(),
-                     b->pool_a.as<uint32_t>(), b->pool_b.as<uint32_t>(), d_cols[0], d_cols[1], d_cols[2], d_cols[3],
+  hipLaunchKernelGGL(k_cx_gather, dim3(nb), dim3(256), 0, s, b->tix.tiles.as<Tile>(), b->pool.tile_out.as<uint32_t>(),
+                     b->pool.tile_nrow.as<uint32_t>(), b->pool.tile_base.as<uint32_t>(), b->last_ntiles, b->pool.key.as<uint32_t>(),
+                     b->pool.a.as<uint32_t>(), b->pool.b.as<uint32_t>(), d_cols[0], d_cols[1], d_cols[2], d_cols[3],
                      d_cols[4], d_cols[5]);
   prof_end("gather", s);
   EPI_HIP(hipGetLastError());
@@ -1995,8 +1974,8 @@ int epi_batch_cx_fetch_host(epi_batch *b, int32_t *const h_cols[6], void *stream
   if (nrow == 0) return EPI_OK;
   EPI_HIP(hipSetDevice(b->eng->device));
   hipStream_t s = pick_stream(b, stream);
-  EPI_TRY(b->pool_c.ensure((size_t)nrow * 4 * 6));
-  int32_t *d = b->pool_c.as<int32_t>();
+  EPI_TRY(b->pool.c.ensure((size_t)nrow * 4 * 6));
+  int32_t *d = b->pool.c.as<int32_t>();
   int32_t *cols[6];
   for (int i = 0; i < 6; i++) cols[i] = d + (int64_t)i * nrow;
   EPI_TRY(epi_batch_cx_fetch_dev(b, cols, s));

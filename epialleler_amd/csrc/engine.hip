@@ -7,6 +7,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <atomic>
 #include <condition_variable>
 #include <mutex>
 #include <thread>
@@ -14,21 +15,27 @@
 
 namespace epi {
 
+// owned DevBuf allocations that are live, and their bytes (epi_device_allocations)
+static std::atomic<int64_t> g_dev_live{0}, g_dev_bytes{0};
+
 int DevBuf::ensure(size_t bytes) {
   if (bytes <= cap && p) return EPI_OK;
+  if (!owned) return fail(EPI_ERR_STATE, "device buffer view of %zu bytes asked for %zu", cap, bytes);
   if (bytes == 0) bytes = 16;
   size_t want = bytes + (bytes >> 3) + 256;   // a little slack so steady-state calls never reallocate
-  if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
+  release();
   EPI_HIP(hipMalloc(&p, want));
   cap = want;
+  g_dev_live += 1; g_dev_bytes += (int64_t)want;
   return EPI_OK;
 }
 
 void DevBuf::release() {
-  if (p) (void)hipFree(p);
-  p = nullptr;
-  cap = 0;
+  if (p && owned) { (void)hipFree(p); g_dev_live -= 1; g_dev_bytes -= (int64_t)cap; }
+  p = nullptr; cap = 0; owned = true;
 }
+
+DevBuf::~DevBuf() { release(); }
 
 // A NULL `stream` is the HIP null stream (what torch's default stream is), NOT the engine's
 // private stream: work must stay ordered with whatever the caller queued before.
@@ -111,6 +118,12 @@ void epi_prof_reset(void) {
   std::lock_guard<std::mutex> lk(g_prof_mu);
   prof_drain();
   g_prof.clear();
+}
+
+int epi_device_allocations(int64_t *live, int64_t *bytes) {
+  if (live) *live = g_dev_live.load();
+  if (bytes) *bytes = g_dev_bytes.load();
+  return EPI_OK;
 }
 
 int epi_engine_create(int device, epi_engine **out) {
@@ -234,6 +247,18 @@ static bool is_pinned_host(const void *h_src) {
   return at.type == hipMemoryTypeHost;
 }
 
+static int ensure_staging(epi_engine *eng) {                // the two pinned staging buffers, on first use
+  const size_t chunk = 64u << 20;
+  if (!eng->pinned[0]) {
+    for (int i = 0; i < 2; i++) {
+      EPI_HIP(hipHostMalloc(&eng->pinned[i], chunk, hipHostMallocDefault));
+      EPI_HIP(hipEventCreateWithFlags(&eng->pinned_done[i], hipEventDisableTiming));
+    }
+    eng->pinned_bytes = chunk;
+  }
+  return EPI_OK;
+}
+
 static int staged_upload(epi_engine *eng, void *d_dst, const void *h_src, size_t bytes) {
   const size_t stage = 64u << 20;                          // the pinned staging buffers
   size_t chunk = stage;
@@ -243,13 +268,7 @@ static int staged_upload(epi_engine *eng, void *d_dst, const void *h_src, size_t
     EPI_HIP(hipMemcpyAsync(d_dst, h_src, bytes, hipMemcpyHostToDevice, eng->copy_stream));
     return EPI_OK;
   }
-  if (!eng->pinned[0]) {
-    for (int i = 0; i < 2; i++) {
-      EPI_HIP(hipHostMalloc(&eng->pinned[i], stage, hipHostMallocDefault));
-      EPI_HIP(hipEventCreateWithFlags(&eng->pinned_done[i], hipEventDisableTiming));
-    }
-    eng->pinned_bytes = stage;
-  }
+  EPI_TRY(ensure_staging(eng));
   for (int i = 0; i < 2; i++) EPI_HIP(hipEventSynchronize(eng->pinned_done[i]));   // (a device-to-host copy may have used them)
   size_t done = 0;
   int k = 0;
@@ -295,13 +314,7 @@ static int upload_rows_congruent(epi_engine *eng, const uint8_t *h_xm, const int
     if (!eng->up_done[i]) EPI_HIP(hipEventCreateWithFlags(&eng->up_done[i], hipEventDisableTiming));
     if (!eng->stage_free[i]) EPI_HIP(hipEventCreateWithFlags(&eng->stage_free[i], hipEventDisableTiming));
   }
-  if (!pinned_src && !eng->pinned[0]) {
-    for (int i = 0; i < 2; i++) {
-      EPI_HIP(hipHostMalloc(&eng->pinned[i], 64u << 20, hipHostMallocDefault));
-      EPI_HIP(hipEventCreateWithFlags(&eng->pinned_done[i], hipEventDisableTiming));
-    }
-    eng->pinned_bytes = 64u << 20;
-  }
+  if (!pinned_src) EPI_TRY(ensure_staging(eng));
   if (!pinned_src) for (int i = 0; i < 2; i++) EPI_HIP(hipEventSynchronize(eng->pinned_done[i]));
   const int g = layout_group(nbytes, n);
   int k = 0;
@@ -334,18 +347,6 @@ static int upload_rows_congruent(epi_engine *eng, const uint8_t *h_xm, const int
 }  // extern "C"
 
 namespace epi {
-
-static int ensure_staging(epi_engine *eng) {
-  const size_t chunk = 64u << 20;
-  if (!eng->pinned[0]) {
-    for (int i = 0; i < 2; i++) {
-      EPI_HIP(hipHostMalloc(&eng->pinned[i], chunk, hipHostMallocDefault));
-      EPI_HIP(hipEventCreateWithFlags(&eng->pinned_done[i], hipEventDisableTiming));
-    }
-    eng->pinned_bytes = chunk;
-  }
-  return EPI_OK;
-}
 
 int stage_buffer(epi_engine *eng, int k, uint8_t **buf, size_t *cap) {
   EPI_TRY(ensure_staging(eng));
@@ -426,6 +427,51 @@ int copy_to_host(epi_engine *eng, void *h_dst, const void *d_src, size_t bytes, 
 
 }  // namespace epi
 
+// The columns and rows of a new batch onto the device (epi_batch_upload synchronises both streams before a failed batch goes)
+static int upload_columns(epi_engine *e, epi_batch *b, const uint8_t *xm, const int64_t *off, const int32_t *rname,
+                          const int32_t *strand, const int32_t *start) {
+  const int64_t n = b->n, nbytes = b->nbytes;
+  const int modulus = (n > 0 && nbytes > 0) ? options().realign : 0;   // EPIHIP_REALIGN=0: rows stay as uploaded
+  const struct { DevBuf &d; const void *h; size_t bytes, room; } cols[4] = {
+      {b->own_off, off, (size_t)(n + 1) * 8, 0}, {b->own_rname, rname, (size_t)n * 4, 4}, {b->own_strand, strand, (size_t)n * 4, 4},
+      {b->own_start, start, (size_t)n * 4, 4}};
+  for (const auto &c : cols) EPI_TRY(c.d.ensure(c.bytes + c.room));
+  for (const auto &c : cols) if (c.bytes) EPI_TRY(staged_upload(e, c.d.p, c.h, c.bytes));
+  b->off = b->own_off.as<int64_t>();
+  b->rname = b->own_rname.as<int32_t>();
+  b->strand = b->own_strand.as<int32_t>();
+  b->start = b->own_start.as<int32_t>();
+  // row lengths and statistics behind the columns, on the copy stream (the first report reads the verdict)
+  EPI_TRY(launch_row_stats(b, e->copy_stream));
+  if (modulus) {
+    // The batch owns its arena: rows go where the tile kernels read them fastest -- at offsets congruent to their start
+    // position (layout.hip) -- while the bytes arrive.  The offsets need the columns only.
+    DevBuf new_off;
+    unsigned long long h_end = 0; uint32_t head = 0;
+    EPI_TRY(layout_offsets(b, modulus, e->copy_stream, &new_off, &h_end, &head));
+    const size_t cap = ((size_t)h_end + 15) / 16 * 16 + 64;
+    EPI_TRY(b->own_xm.ensure(cap));
+    uint8_t *arena = b->own_xm.as<uint8_t>();
+    if ((head && hipMemsetAsync(arena, 0xFB, head, e->aux_stream) != hipSuccess) ||
+        hipMemsetAsync(arena + h_end, 0xFB, cap - (size_t)h_end, e->aux_stream) != hipSuccess) return fail(EPI_ERR_HIP, "memset failed");
+    EPI_TRY(upload_rows_congruent(e, xm, off, n, nbytes, b->off, b->len, new_off.as<int64_t>(), arena));
+    if (hipStreamSynchronize(e->copy_stream) != hipSuccess || hipStreamSynchronize(e->aux_stream) != hipSuccess)
+      return fail(EPI_ERR_HIP, "upload failed: %s", hipGetErrorName(hipGetLastError()));
+    std::swap(b->own_off, new_off);                        // (new_off takes the uploaded offsets with it: nothing reads them any more)
+    b->off = b->own_off.as<int64_t>();
+    b->nbytes = (int64_t)h_end;
+    b->congruent = modulus;
+  } else {
+    const size_t cap = ((size_t)nbytes + 15) / 16 * 16 + 64;
+    EPI_TRY(b->own_xm.ensure(cap));
+    if (hipMemsetAsync(static_cast<char *>(b->own_xm.p) + nbytes, 0xFB, cap - nbytes, e->copy_stream) != hipSuccess)
+      return fail(EPI_ERR_HIP, "memset failed");
+    if (nbytes) EPI_TRY(staged_upload(e, b->own_xm.p, xm, (size_t)nbytes));
+    if (hipStreamSynchronize(e->copy_stream) != hipSuccess) return fail(EPI_ERR_HIP, "upload failed: %s", hipGetErrorName(hipGetLastError()));
+  }
+  return EPI_OK;
+}
+
 extern "C" {
 
 int epi_batch_upload(epi_engine *e, const uint8_t *xm, const int64_t *off, const int32_t *rname,
@@ -444,56 +490,7 @@ int epi_batch_upload(epi_engine *e, const uint8_t *xm, const int64_t *off, const
   b->n = n;
   b->nbytes = nbytes;
   b->owns = true;
-  int rc = EPI_OK;
-  const int modulus = (n > 0 && nbytes > 0) ? options().realign : 0;   // EPIHIP_REALIGN=0: rows stay as uploaded
-  DevBuf new_off;
-  do {
-    if ((rc = b->own_off.ensure((size_t)(n + 1) * 8))) break;
-    if ((rc = b->own_rname.ensure((size_t)n * 4 + 4))) break;
-    if ((rc = b->own_strand.ensure((size_t)n * 4 + 4))) break;
-    if ((rc = b->own_start.ensure((size_t)n * 4 + 4))) break;
-    if ((rc = staged_upload(e, b->own_off.p, off, (size_t)(n + 1) * 8))) break;
-    if (n) {
-      if ((rc = staged_upload(e, b->own_rname.p, rname, (size_t)n * 4))) break;
-      if ((rc = staged_upload(e, b->own_strand.p, strand, (size_t)n * 4))) break;
-      if ((rc = staged_upload(e, b->own_start.p, start, (size_t)n * 4))) break;
-    }
-    b->off = b->own_off.as<int64_t>();
-    b->rname = b->own_rname.as<int32_t>();
-    b->strand = b->own_strand.as<int32_t>();
-    b->start = b->own_start.as<int32_t>();
-    // row lengths and statistics behind the columns, on the copy stream (the first report reads the verdict)
-    if ((rc = launch_row_stats(b, e->copy_stream))) break;
-    if (modulus) {
-      // The batch owns its arena: rows go where the tile kernels read them fastest -- at offsets congruent to their start
-      // position (layout.hip) -- while the bytes arrive.  The offsets need the columns only.
-      unsigned long long h_end = 0;
-      uint32_t head = 0;
-      if ((rc = layout_offsets(b, modulus, e->copy_stream, &new_off, &h_end, &head))) break;
-      const size_t cap = ((size_t)h_end + 15) / 16 * 16 + 64;
-      if ((rc = b->own_xm.ensure(cap))) break;
-      uint8_t *arena = b->own_xm.as<uint8_t>();
-      if ((head && hipMemsetAsync(arena, 0xFB, head, e->aux_stream) != hipSuccess) ||
-          hipMemsetAsync(arena + h_end, 0xFB, cap - (size_t)h_end, e->aux_stream) != hipSuccess) { rc = fail(EPI_ERR_HIP, "memset failed"); break; }
-      if ((rc = upload_rows_congruent(e, xm, off, n, nbytes, b->off, b->len, new_off.as<int64_t>(), arena))) break;
-      if (hipStreamSynchronize(e->copy_stream) != hipSuccess || hipStreamSynchronize(e->aux_stream) != hipSuccess) {
-        rc = fail(EPI_ERR_HIP, "upload failed: %s", hipGetErrorName(hipGetLastError())); break;
-      }
-      std::swap(b->own_off, new_off);
-      b->off = b->own_off.as<int64_t>();
-      b->nbytes = (int64_t)h_end;
-      b->congruent = modulus;
-    } else {
-      const size_t cap = ((size_t)nbytes + 15) / 16 * 16 + 64;
-      if ((rc = b->own_xm.ensure(cap))) break;
-      if (hipMemsetAsync(static_cast<char *>(b->own_xm.p) + nbytes, 0xFB, cap - nbytes, e->copy_stream) != hipSuccess) {
-        rc = fail(EPI_ERR_HIP, "memset failed"); break;
-      }
-      if (nbytes && (rc = staged_upload(e, b->own_xm.p, xm, (size_t)nbytes))) break;
-      if (hipStreamSynchronize(e->copy_stream) != hipSuccess) { rc = fail(EPI_ERR_HIP, "upload failed: %s", hipGetErrorName(hipGetLastError())); break; }
-    }
-  } while (0);
-  new_off.release();
+  const int rc = upload_columns(e, b, xm, off, rname, strand, start);
   if (rc) {
     (void)hipStreamSynchronize(e->copy_stream); (void)hipStreamSynchronize(e->aux_stream);   // nothing of the batch is in flight when it goes
     epi_batch_free(b);
@@ -539,12 +536,6 @@ int epi_batch_adopt(epi_engine *e, const uint8_t *d_xm, int64_t xm_capacity, int
 void epi_batch_free(epi_batch *b) {
   if (!b) return;
   (void)hipSetDevice(b->eng->device);
-  DevBuf *bufs[] = {&b->own_xm, &b->own_off, &b->own_len, &b->own_rname, &b->own_strand, &b->own_start, &b->stats,
-                    &b->scan_tmp, &b->tiles, &b->tile_nrow, &b->tile_base,
-                    &b->tile_out, &b->pool_key, &b->pool_a, &b->pool_b, &b->pool_c, &b->pool_d, &b->pool_e, &b->pool_f,
-                    &b->misc, &b->mhl_m, &b->mhl_h, &b->mhl_blk, &b->mhl_cont, &b->mhl_cur, &b->d_shared_keys, &b->d_shared_owned, &b->heavy_list, &b->heavy_slab, &b->heavy_sums, &b->deep_list, &b->mhlf_fold_slab, &b->diag, &b->d_slot_tile, &b->pass_tmp, &b->thr_tab, &b->mhl_keep_tab, &b->host_io, &b->tile_bsum[0], &b->tile_bsum[1], &b->tile_bsum[2], &b->tile_bsum[3], &b->own_slab, &b->own_slab2, &b->tiles_nt_dev, &b->cx_prev_off, &b->cx_prev_cnt};
-  for (DevBuf *d : bufs) d->release();
-  b->sites.release();
   if (b->stats_done) (void)hipEventDestroy(b->stats_done);
   delete b;
 }

@@ -167,22 +167,17 @@ int layout_offsets(epi_batch *b, int modulus, hipStream_t s, DevBuf *new_off, un
   const int64_t nb = (n + LY_ROWS - 1) / LY_ROWS;
   const uint32_t am = (uint32_t)modulus - 1u;
   DevBuf tmp;
-  int rc = EPI_OK;
-  do {
-    if ((rc = tmp.ensure((size_t)(nb + 2) * 8))) break;
-    if ((rc = new_off->ensure((size_t)(n + 1) * 8))) break;
-    unsigned long long *bsum = tmp.as<unsigned long long>(), *d_end = bsum + nb;
-    int32_t first_start = 0;
-    if ((rc = read_scalars(b, s, b->start, 4, &first_start))) break;
-    *head = (uint32_t)first_start & am;
-    hipLaunchKernelGGL(k_ly_sums, dim3((unsigned)nb), dim3(256), 0, s, b->start, b->len, n, am, bsum);
-    hipLaunchKernelGGL(k_ly_scan, dim3(1), dim3(256), 0, s, bsum, nb, (unsigned long long)*head, d_end);
-    hipLaunchKernelGGL(k_ly_offsets, dim3((unsigned)nb), dim3(256), 0, s, b->start, b->len, n, am, bsum, d_end, new_off->as<int64_t>());
-    if (hipGetLastError() != hipSuccess) { rc = fail(EPI_ERR_HIP, "layout: launch failed"); break; }
-    if ((rc = read_scalars(b, s, d_end, 8, h_end))) break;   // (synchronises: tmp may go)
-  } while (0);
-  tmp.release();
-  return rc;
+  EPI_TRY(tmp.ensure((size_t)(nb + 2) * 8));
+  EPI_TRY(new_off->ensure((size_t)(n + 1) * 8));
+  unsigned long long *bsum = tmp.as<unsigned long long>(), *d_end = bsum + nb;
+  int32_t first_start = 0;
+  EPI_TRY(read_scalars(b, s, b->start, 4, &first_start));
+  *head = (uint32_t)first_start & am;
+  hipLaunchKernelGGL(k_ly_sums, dim3((unsigned)nb), dim3(256), 0, s, b->start, b->len, n, am, bsum);
+  hipLaunchKernelGGL(k_ly_scan, dim3(1), dim3(256), 0, s, bsum, nb, (unsigned long long)*head, d_end);
+  hipLaunchKernelGGL(k_ly_offsets, dim3((unsigned)nb), dim3(256), 0, s, b->start, b->len, n, am, bsum, d_end, new_off->as<int64_t>());
+  if (hipGetLastError() != hipSuccess) return fail(EPI_ERR_HIP, "layout: launch failed");
+  return read_scalars(b, s, d_end, 8, h_end);                // (synchronises: tmp may go)
 }
 
 int realign_batch(epi_batch *b, int modulus, hipStream_t s) {
@@ -192,43 +187,39 @@ int realign_batch(epi_batch *b, int modulus, hipStream_t s) {
   if (b->last_kind != KIND_NONE) return fail(EPI_ERR_STATE, "epi_batch_realign: call it before the first report on the batch");
   EPI_HIP(hipStreamWaitEvent(s, b->stats_done, 0));       // len[] is written by k_row_stats, possibly on another stream
   DevBuf new_off, new_xm;
-  int rc = EPI_OK;
-  do {
-    unsigned long long h_end = 0;
-    uint32_t head = 0;
-    if ((rc = layout_offsets(b, modulus, s, &new_off, &h_end, &head))) break;
-    const size_t cap = ((size_t)h_end + 15) / 16 * 16 + 64;
-    if ((rc = new_xm.ensure(cap))) break;
-    uint8_t *dst = new_xm.as<uint8_t>();
-    if (head && hipMemsetAsync(dst, 0xFB, head, s) != hipSuccess) { rc = fail(EPI_ERR_HIP, "realign: memset failed"); break; }
-    if (hipMemsetAsync(dst + h_end, 0xFB, cap - (size_t)h_end, s) != hipSuccess) { rc = fail(EPI_ERR_HIP, "realign: memset failed"); break; }
-    if ((rc = layout_copy_range(b->xm, 0, INT64_MAX, b->off, b->len, new_off.as<int64_t>(), 0, b->n, layout_group(b->nbytes, b->n), dst, s))) break;
-    // the old arena may be freed (an uploaded batch) or handed back to its owner (an adopted one) when this returns
-    if (hipStreamSynchronize(s) != hipSuccess) { rc = fail(EPI_ERR_HIP, "realign: %s", hipGetErrorName(hipGetLastError())); break; }
-    if (!b->owns) {
-      // an adopted batch: the three small columns become the batch's own as well -- from here on nobody else can change a
-      // row, and what is derived from the rows alone (the tile table, tiles.hip) stays valid between reports
-      const size_t cb = (size_t)b->n * 4;
-      if ((rc = b->own_rname.ensure(cb + 4)) || (rc = b->own_strand.ensure(cb + 4)) || (rc = b->own_start.ensure(cb + 4))) break;
-      if (hipMemcpyAsync(b->own_rname.p, b->rname, cb, hipMemcpyDeviceToDevice, s) != hipSuccess ||
-          hipMemcpyAsync(b->own_strand.p, b->strand, cb, hipMemcpyDeviceToDevice, s) != hipSuccess ||
-          hipMemcpyAsync(b->own_start.p, b->start, cb, hipMemcpyDeviceToDevice, s) != hipSuccess ||
-          hipStreamSynchronize(s) != hipSuccess) { rc = fail(EPI_ERR_HIP, "realign: column copy failed"); break; }
-      b->rname = b->own_rname.as<int32_t>();
-      b->strand = b->own_strand.as<int32_t>();
-      b->start = b->own_start.as<int32_t>();
-      b->owns = true;
-    }
-    std::swap(b->own_xm, new_xm);
-    std::swap(b->own_off, new_off);
-    b->xm = b->own_xm.as<uint8_t>();
-    b->off = b->own_off.as<int64_t>();
-    b->nbytes = (int64_t)h_end;
-    b->congruent = modulus;
-    b->cols_owned = true;
-  } while (0);
-  new_off.release(); new_xm.release();                    // (after the swap: the batch's previous own buffers, if it had any)
-  return rc;
+  unsigned long long h_end = 0; uint32_t head = 0;
+  EPI_TRY(layout_offsets(b, modulus, s, &new_off, &h_end, &head));
+  const size_t cap = ((size_t)h_end + 15) / 16 * 16 + 64;
+  EPI_TRY(new_xm.ensure(cap));
+  uint8_t *dst = new_xm.as<uint8_t>();
+  if (head && hipMemsetAsync(dst, 0xFB, head, s) != hipSuccess) return fail(EPI_ERR_HIP, "realign: memset failed");
+  if (hipMemsetAsync(dst + h_end, 0xFB, cap - (size_t)h_end, s) != hipSuccess) return fail(EPI_ERR_HIP, "realign: memset failed");
+  EPI_TRY(layout_copy_range(b->xm, 0, INT64_MAX, b->off, b->len, new_off.as<int64_t>(), 0, b->n, layout_group(b->nbytes, b->n), dst, s));
+  // The old arena may be handed back to its owner (an adopted batch) when this returns, or freed (an uploaded one): new_off / new_xm
+  // hold the batch's previous buffers after the swaps below and free them on return.  This synchronisation makes that safe.
+  if (hipStreamSynchronize(s) != hipSuccess) return fail(EPI_ERR_HIP, "realign: %s", hipGetErrorName(hipGetLastError()));
+  if (!b->owns) {
+    // an adopted batch: the three small columns become the batch's own as well -- from here on nobody else can change a
+    // row, and what is derived from the rows alone (the tile table, tiles.hip) stays valid between reports
+    const size_t cb = (size_t)b->n * 4;
+    for (DevBuf *d : {&b->own_rname, &b->own_strand, &b->own_start}) EPI_TRY(d->ensure(cb + 4));
+    if (hipMemcpyAsync(b->own_rname.p, b->rname, cb, hipMemcpyDeviceToDevice, s) != hipSuccess ||
+        hipMemcpyAsync(b->own_strand.p, b->strand, cb, hipMemcpyDeviceToDevice, s) != hipSuccess ||
+        hipMemcpyAsync(b->own_start.p, b->start, cb, hipMemcpyDeviceToDevice, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess) return fail(EPI_ERR_HIP, "realign: column copy failed");
+    b->rname = b->own_rname.as<int32_t>();
+    b->strand = b->own_strand.as<int32_t>();
+    b->start = b->own_start.as<int32_t>();
+    b->owns = true;
+  }
+  std::swap(b->own_xm, new_xm);
+  std::swap(b->own_off, new_off);
+  b->xm = b->own_xm.as<uint8_t>();
+  b->off = b->own_off.as<int64_t>();
+  b->nbytes = (int64_t)h_end;
+  b->congruent = modulus;
+  b->cols_owned = true;
+  return EPI_OK;
 }
 
 }  // namespace epi

@@ -199,18 +199,18 @@ inline uint32_t mhl_pool_cap(const epi_batch *b) { return (uint32_t)(mhl_pool_ro
 // the argument struct of either path (MhlArgs, MhlFArgs: the members have the same names)
 template <class Args>
 inline void mhl_bind_pool(const epi_batch *b, Args &a) {
-  a.tiles = b->tiles.as<Tile>();
+  a.tiles = b->tix.tiles.as<Tile>();
   a.cursor = &report_scalars(b)->cursor;
-  a.tile_nrow = b->tile_nrow.as<uint32_t>();
-  a.tile_base = b->tile_base.as<uint32_t>();
-  a.pool_key = b->pool_key.as<uint32_t>();
-  a.pool_cov = b->pool_a.as<uint32_t>();
-  a.pool_hs = b->pool_d.as<unsigned long long>();
-  a.pool_nu = b->pool_e.as<unsigned long long>();
-  a.pool_de = b->pool_f.as<unsigned long long>();
+  a.tile_nrow = b->pool.tile_nrow.as<uint32_t>();
+  a.tile_base = b->pool.tile_base.as<uint32_t>();
+  a.pool_key = b->pool.key.as<uint32_t>();
+  a.pool_cov = b->pool.a.as<uint32_t>();
+  a.pool_hs = b->pool.d.as<unsigned long long>();
+  a.pool_nu = b->pool.e.as<unsigned long long>();
+  a.pool_de = b->pool.f.as<unsigned long long>();
   a.pool_cap = mhl_pool_cap(b);
-  a.slot_rows = b->mhl_last_slot;
-  a.ovf_base = b->mhl_last_ovf;
+  a.slot_rows = b->mhl.last_slot;
+  a.ovf_base = b->mhl.last_ovf;
 }
 
 // ---- the fused path (mhl_fused.hip) --------------------------------------------------------------------------------------

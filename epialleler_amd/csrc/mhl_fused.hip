@@ -978,14 +978,14 @@ struct MhlfPlan {
 
 // Decision table over 0 .. longest row; kept while max_oo does not change (bitwise: a NaN compares equal to itself)
 static int mhlf_keep_table(epi_batch *b, int32_t max_len, double max_oo, hipStream_t s, MhlFArgs &a) {
-  if (b->mhl_keep_len != max_len || memcmp(&b->mhl_keep_oo, &max_oo, sizeof(double)) != 0) {
-    EPI_TRY(b->mhl_keep_tab.ensure((size_t)(max_len + 1) * 4));
-    hipLaunchKernelGGL(k_mhl_keep_table, dim3((unsigned)(max_len / 256 + 1)), dim3(256), 0, s, max_oo, max_len, b->mhl_keep_tab.as<uint32_t>());
+  if (b->mhl.keep_len != max_len || memcmp(&b->mhl.keep_oo, &max_oo, sizeof(double)) != 0) {
+    EPI_TRY(b->mhl.keep_tab.ensure((size_t)(max_len + 1) * 4));
+    hipLaunchKernelGGL(k_mhl_keep_table, dim3((unsigned)(max_len / 256 + 1)), dim3(256), 0, s, max_oo, max_len, b->mhl.keep_tab.as<uint32_t>());
     EPI_HIP(hipGetLastError());
-    b->mhl_keep_len = max_len;
-    b->mhl_keep_oo = max_oo;
+    b->mhl.keep_len = max_len;
+    b->mhl.keep_oo = max_oo;
   }
-  a.keep_tab = b->mhl_keep_tab.as<uint32_t>();
+  a.keep_tab = b->mhl.keep_tab.as<uint32_t>();
   return EPI_OK;
 }
 
@@ -994,13 +994,13 @@ static int mhlf_keep_table(epi_batch *b, int32_t max_len, double max_oo, hipStre
 // (MHLF_FOLD_SLOTS of them; a tile that finds none left goes to the WIDE variant with the other deep tiles).  Batches whose
 // tiles average well below 255 rows start there; one that runs out of slots switches the batch over.
 static int mhlf_pick_fold(epi_batch *b, MhlfPlan &p, MhlFArgs &a) {
-  p.fold = options().mhlf_fold >= 0 ? options().mhlf_fold != 0 : (b->mhlf_prefer_fold || (double)b->n > 150.0 * (double)p.nt);
+  p.fold = options().mhlf_fold >= 0 ? options().mhlf_fold != 0 : (b->mhl.prefer_fold || (double)b->n > 150.0 * (double)p.nt);
   p.fold_slots = options().mhlf_fold_slots >= 0 && (uint32_t)options().mhlf_fold_slots < MHLF_FOLD_SLOTS
                      ? (uint32_t)options().mhlf_fold_slots : MHLF_FOLD_SLOTS;   // (test hook: fewer)
   a.fold_cursor = &report_scalars(b)->fold_cursor;
   if (!p.fold) {
-    EPI_TRY(b->mhlf_fold_slab.ensure((size_t)MHLF_FOLD_SLOTS * 2 * MHLF_T * 4));
-    a.fold_slab = b->mhlf_fold_slab.as<uint32_t>();
+    EPI_TRY(b->mhl.fold_slab.ensure((size_t)MHLF_FOLD_SLOTS * 2 * MHLF_T * 4));
+    a.fold_slab = b->mhl.fold_slab.as<uint32_t>();
     a.fold_slots = p.fold_slots;
   }
   return EPI_OK;
@@ -1015,11 +1015,11 @@ static int mhlf_fill_args(epi_batch *b, uint32_t ctx_mask, uint32_t H, int hmin,
   a.lut2 = make_mhlf_lut2(ctx_mask);
   a.hmin = (int32_t)hmin; a.H = H; a.ctx = k;
   a.deep_count = &report_scalars(b)->heavy_count;          // (this kernel's deep tiles share the heavy tiles' counter)
-  a.deep_list = b->heavy_list.as<uint32_t>();
+  a.deep_list = b->pool.heavy_list.as<uint32_t>();
   a.max_rows = MHLF_FAST_ROWS;
   if (options().heavy_rows > 0 && options().heavy_rows < a.max_rows) a.max_rows = options().heavy_rows;   // test hook (EPIHIP_HEAVY_ROWS)
-  a.slab_cnt = b->d_mhl_cnt_slab;
-  a.slab_sum = reinterpret_cast<unsigned long long *>(b->d_mhl_sum_slab);
+  a.slab_cnt = b->shard.d_mhl_cnt_slab;
+  a.slab_sum = reinterpret_cast<unsigned long long *>(b->shard.d_mhl_sum_slab);
   a.nrows = b->n;
 #ifdef EPI_CHECK
   EPI_TRY(mhl_check_begin(b, s, &a.dbg));
@@ -1030,11 +1030,11 @@ static int mhlf_fill_args(epi_batch *b, uint32_t ctx_mask, uint32_t H, int hmin,
 // What a finished attempt teaches the batch for its next report
 static void mhlf_learn(epi_batch *b, const MhlfPlan &p, uint32_t H, uint32_t ndeep, uint32_t fold_asked) {
   if (ndeep > 0) {
-    b->mhlf_prefer_wide = ndeep > (uint32_t)p.nt / 2;      // most tiles needed the wide sums: start there next time
-    b->mhlf_prefer_wide_H = H;
+    b->mhl.prefer_wide = ndeep > (uint32_t)p.nt / 2;      // most tiles needed the wide sums: start there next time
+    b->mhl.prefer_wide_H = H;
   }
   // (rows per tile are a property of the immutable batch, not of the report's parameters: this one may stay)
-  if (!p.fold && fold_asked > p.fold_slots / 2) b->mhlf_prefer_fold = true;   // many tiles over 255 rows: LDS fold array next time
+  if (!p.fold && fold_asked > p.fold_slots / 2) b->mhl.prefer_fold = true;   // many tiles over 255 rows: LDS fold array next time
 }
 
 // One attempt at all tiles: the fast variant (or the WIDE one where the batch has learned to start there), the tiles' row
@@ -1056,14 +1056,14 @@ static int mhlf_attempt(epi_batch *b, const MhlfPlan &p, MhlFArgs &a, uint32_t H
   // (the preference was learned for one H: S(min(h, H)) shrinks with H, so a report with a smaller H starts on the fast
   //  variant again, which lists the tiles that still need the wide sums)
   const unsigned grid = (unsigned)(((nt + 7) / 8) * 8);
-  if (b->mhlf_prefer_wide && H >= b->mhlf_prefer_wide_H) launch_mhl_fused<true>(p.shape_wide, grid, nt, s, a);
+  if (b->mhl.prefer_wide && H >= b->mhl.prefer_wide_H) launch_mhl_fused<true>(p.shape_wide, grid, nt, s, a);
   else launch_mhl_fused<false>(p.shape, grid, nt, s, a, p.fold);
   prof_end("mhl_tiles", s);
   EPI_HIP(hipGetLastError());
-  EPI_TRY(scan_exclusive_u32(a.tile_nrow, b->tile_out.as<uint32_t>(), nt, &sc->rows, b->scan_tmp, s));
+  EPI_TRY(scan_exclusive_u32(a.tile_nrow, b->pool.tile_out.as<uint32_t>(), nt, &sc->rows, b->scan_tmp, s));
   EPI_TRY(read_report_scalars(b, s, host));
   if (p.nt_hinted && host->ntiles != (uint32_t)nt) {
-    for (int i = 0; i < 4; i++) b->tile_hint_T[i] = 0;
+    batch_rows_changed(b);
     return fail(EPI_ERR_STATE, "the rows of this batch changed since an earlier report (tile count %u, was %d)", host->ntiles, nt);
   }
   const uint32_t ndeep = host->heavy_count, fold_asked = host->fold_cursor;
@@ -1073,7 +1073,7 @@ static int mhlf_attempt(epi_batch *b, const MhlfPlan &p, MhlFArgs &a, uint32_t H
     launch_mhl_fused<true>(p.shape_wide, ndeep, (int)ndeep, s, a);
     prof_end("mhl_deep", s);
     EPI_HIP(hipGetLastError());
-    EPI_TRY(scan_exclusive_u32(a.tile_nrow, b->tile_out.as<uint32_t>(), nt, &sc->rows, b->scan_tmp, s));
+    EPI_TRY(scan_exclusive_u32(a.tile_nrow, b->pool.tile_out.as<uint32_t>(), nt, &sc->rows, b->scan_tmp, s));
     EPI_TRY(read_report_scalars(b, s, host));
   }
   mhlf_learn(b, p, H, ndeep, fold_asked);
@@ -1090,8 +1090,8 @@ int mhl_fused_report(epi_batch *b, uint32_t ctx_mask, uint32_t H, int hmin, doub
                      int64_t *nrow_out, bool *done) {
   *done = false;
   MhlfPlan p = {};
-  p.nshared = (int32_t)b->shared_keys.size();
-  if (p.nshared > 0 && !b->mhl_shared_fused) return EPI_OK;  // the slabs attached are the two-kernel path's
+  p.nshared = (int32_t)b->shard.keys.size();
+  if (p.nshared > 0 && b->shard.kind != SLAB_MHL_FUSED) return EPI_OK;  // the slabs attached are the two-kernel path's
   RowStats st;
   EPI_TRY(build_tiles(b, s, MHLF_T, &st, &p.nt, &p.nt_hinted));   // (a remembered tile count is verified at the attempt's synchronisation)
   if (!mhl_fused_eligible(ctx_mask, st)) {
@@ -1102,13 +1102,13 @@ int mhl_fused_report(epi_batch *b, uint32_t ctx_mask, uint32_t H, int hmin, doub
   p.shape = pick_mhlf_shape_hist(st, b->n, p.nt, MHLF_T);
   b->last_ntiles = p.nt;
   if (p.nt == 0) { b->last_kind = p.nshared > 0 ? KIND_MHLF_SHARED : KIND_MHL; b->last_nrow = 0; *done = true; return EPI_OK; }
-  EPI_TRY(b->tile_nrow.ensure((size_t)p.nt * 4));
-  EPI_TRY(b->tile_base.ensure((size_t)p.nt * 4));
-  EPI_TRY(b->tile_out.ensure((size_t)(p.nt + 1) * 4));
-  EPI_TRY(b->heavy_list.ensure((size_t)p.nt * 4));        // the deep list
+  EPI_TRY(b->pool.tile_nrow.ensure((size_t)p.nt * 4));
+  EPI_TRY(b->pool.tile_base.ensure((size_t)p.nt * 4));
+  EPI_TRY(b->pool.tile_out.ensure((size_t)(p.nt + 1) * 4));
+  EPI_TRY(b->pool.heavy_list.ensure((size_t)p.nt * 4));        // the deep list
   p.headroom = p.nshared > 0 ? (size_t)p.nshared * 2 * MHLF_T : 0;
-  EPI_TRY(mhl_layout_pool(b, b->mhlf_slot, MHLF_T, p.nt, p.headroom, &p.pool));   // (a slot size of its own: these tiles have MHLF_T positions)
-  b->mhl_ctx_mask = ctx_mask;
+  EPI_TRY(mhl_layout_pool(b, b->mhl.fused_slot, MHLF_T, p.nt, p.headroom, &p.pool));   // (a slot size of its own: these tiles have MHLF_T positions)
+  b->mhl.ctx_mask = ctx_mask;
   MhlFArgs a{};
   EPI_TRY(mhlf_keep_table(b, st.max_len, max_oo, s, a));
   EPI_TRY(mhlf_pick_fold(b, p, a));
@@ -1123,7 +1123,7 @@ int mhl_fused_report(epi_batch *b, uint32_t ctx_mask, uint32_t H, int hmin, doub
     if (attempt == 1) return fail(EPI_ERR_STATE, "row pool overflow after regrow");
     EPI_TRY(ensure_mhl_pool(b, p.pool.ovf_base + host.cursor + (host.cursor >> 4) + 1024 + p.headroom));
   }
-  if (host.cursor > host.rows / 8 && b->mhlf_slot < 2u * MHLF_T) b->mhlf_slot *= 2;   // too many tiles outgrew their slot
+  if (host.cursor > host.rows / 8 && b->mhl.fused_slot < 2u * MHLF_T) b->mhl.fused_slot *= 2;   // too many tiles outgrew their slot
   *done = true;
   if (p.nshared > 0) { b->last_kind = KIND_MHLF_SHARED; return EPI_OK; }    // caller continues with epi_batch_mhl_finish_shared
   b->last_kind = KIND_MHL;
@@ -1134,14 +1134,14 @@ int mhl_fused_report(epi_batch *b, uint32_t ctx_mask, uint32_t H, int hmin, doub
 
 // Second half of a sharded lMHL report on the fused path: the slabs have been sum-reduced across ranks.
 int mhl_fused_finish_shared(epi_batch *b, hipStream_t s, int64_t *nrow_out) {
-  if (b->last_ntiles > 0 && !b->shared_keys.empty()) {
+  if (b->last_ntiles > 0 && !b->shard.keys.empty()) {
     MhlFArgs a{};
     mhl_bind_pool(b, a);
-    a.ctx = mhl_single_context(b->mhl_ctx_mask);
-    a.slab_cnt = b->d_mhl_cnt_slab;
-    a.slab_sum = reinterpret_cast<unsigned long long *>(b->d_mhl_sum_slab);
-    hipLaunchKernelGGL(k_mhlf_emit_slab, dim3((unsigned)b->shared_keys.size()), dim3(MHLF_WG), 0, s, a, b->d_shared_owned.as<int32_t>(),
-                       b->d_slot_tile.as<int32_t>());
+    a.ctx = mhl_single_context(b->mhl.ctx_mask);
+    a.slab_cnt = b->shard.d_mhl_cnt_slab;
+    a.slab_sum = reinterpret_cast<unsigned long long *>(b->shard.d_mhl_sum_slab);
+    hipLaunchKernelGGL(k_mhlf_emit_slab, dim3((unsigned)b->shard.keys.size()), dim3(MHLF_WG), 0, s, a, b->shard.d_owned.as<int32_t>(),
+                       b->shard.d_slot_tile.as<int32_t>());
     EPI_HIP(hipGetLastError());
     return mhl_finish_rows(b, s, nrow_out);
   }

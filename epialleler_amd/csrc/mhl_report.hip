@@ -878,20 +878,20 @@ __global__ __launch_bounds__(256) void k_mhl_gather(const Tile *__restrict__ til
   }
 }
 
-size_t mhl_pool_rows(const epi_batch *b) { return b->pool_cap < b->pool_cap2 ? b->pool_cap : b->pool_cap2; }
+size_t mhl_pool_rows(const epi_batch *b) { return b->pool.row_cap < b->pool.row_cap2 ? b->pool.row_cap : b->pool.row_cap2; }
 
 int ensure_mhl_pool(epi_batch *b, size_t rows) {
-  if (rows > b->pool_cap || !b->pool_key.p) {
-    EPI_TRY(b->pool_key.ensure(rows * 4));
-    EPI_TRY(b->pool_a.ensure(rows * 4));
-    EPI_TRY(b->pool_b.ensure(rows * 4));
-    b->pool_cap = rows;
+  if (rows > b->pool.row_cap || !b->pool.key.p) {
+    EPI_TRY(b->pool.key.ensure(rows * 4));
+    EPI_TRY(b->pool.a.ensure(rows * 4));
+    EPI_TRY(b->pool.b.ensure(rows * 4));
+    b->pool.row_cap = rows;
   }
-  if (rows > b->pool_cap2 || !b->pool_d.p) {
-    EPI_TRY(b->pool_d.ensure(rows * 8));
-    EPI_TRY(b->pool_e.ensure(rows * 8));
-    EPI_TRY(b->pool_f.ensure(rows * 8));
-    b->pool_cap2 = rows;
+  if (rows > b->pool.row_cap2 || !b->pool.d.p) {
+    EPI_TRY(b->pool.d.ensure(rows * 8));
+    EPI_TRY(b->pool.e.ensure(rows * 8));
+    EPI_TRY(b->pool.f.ensure(rows * 8));
+    b->pool.row_cap2 = rows;
   }
   return EPI_OK;
 }
@@ -987,14 +987,14 @@ struct MhlPlan {
 
 // Pass 1 workspace: per-read info, record table, records (grown on demand like the row pool), allocation cursors
 static int mhl_pass1_workspace(epi_batch *b, const MhlPlan &p) {
-  EPI_TRY(b->mhl_h.ensure((size_t)b->n * 16));
-  EPI_TRY(b->mhl_blk.ensure(p.nblkrec * 8));
-  if (p.multi) EPI_TRY(b->mhl_cont.ensure(p.nblkrec * 4));
-  if (b->mhl_rec_cap == 0) {
-    b->mhl_rec_cap = (size_t)b->nbytes / 48 + (size_t)b->n + 64 * MHL_REGIONS;
-    EPI_TRY(b->mhl_m.ensure(b->mhl_rec_cap * sizeof(MhlRec)));
+  EPI_TRY(b->mhl.h.ensure((size_t)b->n * 16));
+  EPI_TRY(b->mhl.blk.ensure(p.nblkrec * 8));
+  if (p.multi) EPI_TRY(b->mhl.cont.ensure(p.nblkrec * 4));
+  if (b->mhl.rec_cap == 0) {
+    b->mhl.rec_cap = (size_t)b->nbytes / 48 + (size_t)b->n + 64 * MHL_REGIONS;
+    EPI_TRY(b->mhl.m.ensure(b->mhl.rec_cap * sizeof(MhlRec)));
   }
-  return b->mhl_cur.ensure((size_t)MHL_REGIONS * MHL_CUR_STRIDE * 8);
+  return b->mhl.cur.ensure((size_t)MHL_REGIONS * MHL_CUR_STRIDE * 8);
 }
 
 // Row pool (layout_pool, tiles.hip) of either path, for its tiles of T positions and from its own remembered slot size:
@@ -1002,8 +1002,8 @@ static int mhl_pass1_workspace(epi_batch *b, const MhlPlan &p) {
 int mhl_layout_pool(epi_batch *b, uint32_t &slot_state, int T, int32_t nt, size_t headroom, PoolLayout *l) {
   if (!slot_state) slot_state = (uint32_t)T / 8;
   EPI_TRY(layout_pool(b, slot_state, T, nt, headroom, options().mhl_slot, ensure_mhl_pool, l));   // test hook (EPIHIP_MHL_SLOT)
-  b->mhl_last_slot = l->slot;
-  b->mhl_last_ovf = (uint32_t)l->ovf_base;
+  b->mhl.last_slot = l->slot;
+  b->mhl.last_ovf = (uint32_t)l->ovf_base;
   return EPI_OK;
 }
 
@@ -1015,15 +1015,15 @@ static int mhl_fill_args(epi_batch *b, MhlPlan &p, uint32_t ctx_mask, uint32_t H
   ra.xm = b->xm; ra.off = b->off; ra.len = b->len; ra.n = b->n;
   ra.lut = make_mhl_lut(ctx_mask);
   ra.hmin = (int32_t)hmin; ra.max_oo = max_oo;
-  ra.rowinfo = b->mhl_h.as<int4>();
-  ra.blkrec = b->mhl_blk.as<uint2>();
-  ra.rec_cursor = b->mhl_cur.as<unsigned long long>();
-  ra.cont = p.multi ? b->mhl_cont.as<uint32_t>() : nullptr;
+  ra.rowinfo = b->mhl.h.as<int4>();
+  ra.blkrec = b->mhl.blk.as<uint2>();
+  ra.rec_cursor = b->mhl.cur.as<unsigned long long>();
+  ra.cont = p.multi ? b->mhl.cont.as<uint32_t>() : nullptr;
   ra.max_h = &sc->max_h;
 
   a.c.xm = b->xm; a.c.off = b->off; a.c.len = b->len; a.c.start = b->start; a.c.strand = b->strand; a.c.pass = nullptr;
-  a.rowinfo = b->mhl_h.as<int4>();
-  a.blkrec = b->mhl_blk.as<uint2>();
+  a.rowinfo = b->mhl.h.as<int4>();
+  a.blkrec = b->mhl.blk.as<uint2>();
   a.multi = p.multi ? 1 : 0;
 #ifdef EPI_MHL_CHECK
   EPI_TRY(mhl_check_begin(b, s, &a.dbg));
@@ -1034,12 +1034,12 @@ static int mhl_fill_args(epi_batch *b, MhlPlan &p, uint32_t ctx_mask, uint32_t H
   if (options().heavy_rows > 0) p.heavy_rows = options().heavy_rows;   // test hook (EPIHIP_HEAVY_ROWS)
   if (p.heavy_rows > 32767) p.heavy_rows = 32767;          // k_mhl_tiles' packed u16 counters: a base adds at most 2 (the
                                                            // CX kernels cap at 16384, cx_report.hip)
-  EPI_TRY(b->heavy_list.ensure((size_t)p.nt * 4));
-  a.heavy_list = b->heavy_list.as<uint32_t>();
+  EPI_TRY(b->pool.heavy_list.ensure((size_t)p.nt * 4));
+  a.heavy_list = b->pool.heavy_list.as<uint32_t>();
   a.heavy_count = &sc->heavy_count;
   a.heavy_max = &sc->heavy_max;
-  a.shared_cnt = reinterpret_cast<uint32_t *>(b->d_mhl_cnt_slab);
-  a.shared_sums = reinterpret_cast<unsigned long long *>(b->d_mhl_sum_slab);
+  a.shared_cnt = reinterpret_cast<uint32_t *>(b->shard.d_mhl_cnt_slab);
+  a.shared_sums = reinterpret_cast<unsigned long long *>(b->shard.d_mhl_sum_slab);
   return EPI_OK;
 }
 
@@ -1047,8 +1047,8 @@ static int mhl_fill_args(epi_batch *b, MhlPlan &p, uint32_t ctx_mask, uint32_t H
 // *rec_used: records the fullest region asked for -- more than a region holds: mhl_regrow_records, then pass 1 again.
 static int mhl_pass1(epi_batch *b, const MhlPlan &p, RowsArgs &ra, hipStream_t s, Scalars *host, unsigned long long *rec_used) {
   Scalars *sc = report_scalars(b);
-  ra.recs = b->mhl_m.as<MhlRec>();
-  ra.rec_cap = (uint32_t)b->mhl_rec_cap;
+  ra.recs = b->mhl.m.as<MhlRec>();
+  ra.rec_cap = (uint32_t)b->mhl.rec_cap;
   EPI_HIP(hipMemsetAsync(ra.rec_cursor, 0, (size_t)MHL_REGIONS * MHL_CUR_STRIDE * 8, s));
   EPI_HIP(hipMemsetAsync(ra.max_h, 0, 4, s));
   prof_begin("mhl_rows", s);
@@ -1079,8 +1079,8 @@ static int mhl_pass1(epi_batch *b, const MhlPlan &p, RowsArgs &ra, hipStream_t s
 static int mhl_regrow_records(epi_batch *b, unsigned long long rec_used) {
   const unsigned long long want = (rec_used + rec_used / 16 + 64) * MHL_REGIONS;
   if (want > 0xFFFFFFF0ull) return fail(EPI_ERR_NOMEM, "too many methylated stretches in one batch (%llu)", want);
-  b->mhl_rec_cap = (size_t)want;
-  return b->mhl_m.ensure(b->mhl_rec_cap * sizeof(MhlRec));
+  b->mhl.rec_cap = (size_t)want;
+  return b->mhl.m.ensure(b->mhl.rec_cap * sizeof(MhlRec));
 }
 
 // u32 LDS sums if no position of a tile (or heavy-tile chunk) can reach 2^31: rows x (the largest value a read can add:
@@ -1111,24 +1111,24 @@ static int mhl_pass2(epi_batch *b, const MhlPlan &p, MhlArgs &a, hipStream_t s, 
   if (p.narrow) launch_mhl_tiles<uint32_t>(p.tg, nt, s, a); else launch_mhl_tiles<unsigned long long>(p.tg, nt, s, a);
   prof_end("mhl_tiles", s);
   EPI_HIP(hipGetLastError());
-  EPI_TRY(scan_exclusive_u32(a.tile_nrow, b->tile_out.as<uint32_t>(), nt, &sc->rows, b->scan_tmp, s));
+  EPI_TRY(scan_exclusive_u32(a.tile_nrow, b->pool.tile_out.as<uint32_t>(), nt, &sc->rows, b->scan_tmp, s));
 #ifdef EPI_MHL_CHECK
   EPI_TRY(mhl_check_end(b, a.dbg, "lMHL", nt, attempt));
 #endif
   EPI_TRY(read_report_scalars(b, s, host));
   if (host->heavy_count > 0) {
     const uint32_t nheavy = host->heavy_count, nchunks = (host->heavy_max + (uint32_t)a.heavy_chunk - 1) / (uint32_t)a.heavy_chunk;
-    EPI_TRY(b->heavy_slab.ensure((size_t)nheavy * 16 * MHL_T * 4));
-    EPI_TRY(b->heavy_sums.ensure((size_t)nheavy * MHL_NSUM * 8));
-    a.heavy_cnt = b->heavy_slab.as<uint32_t>();
-    a.heavy_sums = b->heavy_sums.as<unsigned long long>();
+    EPI_TRY(b->pool.heavy_slab.ensure((size_t)nheavy * 16 * MHL_T * 4));
+    EPI_TRY(b->pool.heavy_sums.ensure((size_t)nheavy * MHL_NSUM * 8));
+    a.heavy_cnt = b->pool.heavy_slab.as<uint32_t>();
+    a.heavy_sums = b->pool.heavy_sums.as<unsigned long long>();
     EPI_HIP(hipMemsetAsync(a.heavy_cnt, 0, (size_t)nheavy * 16 * MHL_T * 4, s));
     EPI_HIP(hipMemsetAsync(a.heavy_sums, 0, (size_t)nheavy * MHL_NSUM * 8, s));
     prof_begin("mhl_heavy", s);
     if (p.narrow) launch_mhl_heavy<uint32_t>(p.tg, nheavy, nchunks, s, a); else launch_mhl_heavy<unsigned long long>(p.tg, nheavy, nchunks, s, a);
     prof_end("mhl_heavy", s);
     EPI_HIP(hipGetLastError());
-    EPI_TRY(scan_exclusive_u32(a.tile_nrow, b->tile_out.as<uint32_t>(), nt, &sc->rows, b->scan_tmp, s));
+    EPI_TRY(scan_exclusive_u32(a.tile_nrow, b->pool.tile_out.as<uint32_t>(), nt, &sc->rows, b->scan_tmp, s));
     EPI_TRY(read_report_scalars(b, s, host));
   }
   return EPI_OK;
@@ -1152,7 +1152,7 @@ static int mhl_report_impl(epi_batch *b, uint32_t ctx_mask, uint32_t H, int hmin
   EPI_TRY(build_tiles(b, s, kMhlTile, &st, &p.nt));
   b->last_ntiles = p.nt;
   if (p.nt == 0) {                                         // (a rank of a sharded run without rows still takes part in the exchange)
-    b->last_kind = !b->shared_keys.empty() && b->d_mhl_cnt_slab ? KIND_MHL_SHARED : KIND_MHL; b->last_nrow = 0;
+    b->last_kind = b->shard.kind == SLAB_MHL ? KIND_MHL_SHARED : KIND_MHL; b->last_nrow = 0;
     return EPI_OK;
   }
   p.gc = pick_mhl_group(st.max_len);
@@ -1160,23 +1160,23 @@ static int mhl_report_impl(epi_batch *b, uint32_t ctx_mask, uint32_t H, int hmin
   p.nblkrec = p.multi ? (size_t)(b->nbytes >> MHL_BLK_SHIFT) + 2 * (size_t)b->n + 2 : 1;
   p.tg = pick_mhl_tile_group(st.max_len);
   EPI_TRY(mhl_pass1_workspace(b, p));
-  EPI_TRY(b->tile_nrow.ensure((size_t)p.nt * 4));
-  EPI_TRY(b->tile_base.ensure((size_t)p.nt * 4));
-  EPI_TRY(b->tile_out.ensure((size_t)(p.nt + 1) * 4));
+  EPI_TRY(b->pool.tile_nrow.ensure((size_t)p.nt * 4));
+  EPI_TRY(b->pool.tile_base.ensure((size_t)p.nt * 4));
+  EPI_TRY(b->pool.tile_out.ensure((size_t)(p.nt + 1) * 4));
   RowsArgs ra{};
   MhlArgs a{};
   EPI_TRY(mhl_fill_args(b, p, ctx_mask, H, hmin, max_oo, s, ra, a));
-  p.nshared = (int32_t)b->shared_keys.size();
+  p.nshared = (int32_t)b->shard.keys.size();
   if (p.nshared > 0 && (!a.shared_cnt || !a.shared_sums)) return fail(EPI_ERR_STATE, "shared tiles set without lMHL slabs (use epi_batch_mhl_set_shared)");
   p.headroom = p.nshared > 0 ? (size_t)p.nshared * 2 * MHL_T : 0;
-  EPI_TRY(mhl_layout_pool(b, b->mhl_slot, MHL_T, p.nt, p.headroom, &p.pool));
-  b->mhl_ctx_mask = ctx_mask;
+  EPI_TRY(mhl_layout_pool(b, b->mhl.slot, MHL_T, p.nt, p.headroom, &p.pool));
+  b->mhl.ctx_mask = ctx_mask;
 
   Scalars host;
   for (int attempt = 0;; attempt++) {
     unsigned long long rec_used = 0;
     EPI_TRY(mhl_pass1(b, p, ra, s, &host, &rec_used));
-    if (rec_used > b->mhl_rec_cap / MHL_REGIONS) {
+    if (rec_used > b->mhl.rec_cap / MHL_REGIONS) {
       if (attempt == 2) return fail(EPI_ERR_STATE, "stretch record overflow after regrow");
       EPI_TRY(mhl_regrow_records(b, rec_used));
       continue;
@@ -1189,7 +1189,7 @@ static int mhl_report_impl(epi_batch *b, uint32_t ctx_mask, uint32_t H, int hmin
     if (attempt == 2) return fail(EPI_ERR_STATE, "row pool overflow after regrow");
     EPI_TRY(mhl_regrow_pool(b, p, a, host.cursor, s));
   }
-  if (host.cursor > host.rows / 8 && b->mhl_slot < 2u * MHL_T) b->mhl_slot *= 2;   // too many tiles outgrew their slot
+  if (host.cursor > host.rows / 8 && b->mhl.slot < 2u * MHL_T) b->mhl.slot *= 2;   // too many tiles outgrew their slot
   if (p.nshared > 0) { b->last_kind = KIND_MHL_SHARED; return EPI_OK; }     // caller continues with epi_batch_mhl_finish_shared
   b->last_kind = KIND_MHL;
   b->last_nrow = host.rows;
@@ -1199,11 +1199,11 @@ static int mhl_report_impl(epi_batch *b, uint32_t ctx_mask, uint32_t H, int hmin
 
 int mhl_finish_rows(epi_batch *b, hipStream_t s, int64_t *nrow_out) {
   Scalars *sc = report_scalars(b);
-  EPI_TRY(scan_exclusive_u32(b->tile_nrow.as<uint32_t>(), b->tile_out.as<uint32_t>(), b->last_ntiles, &sc->rows, b->scan_tmp, s));
+  EPI_TRY(scan_exclusive_u32(b->pool.tile_nrow.as<uint32_t>(), b->pool.tile_out.as<uint32_t>(), b->last_ntiles, &sc->rows, b->scan_tmp, s));
   Scalars host;
   EPI_TRY(read_report_scalars(b, s, &host));
   // cannot overflow: the first half kept 2 T rows per shared tile free
-  if ((size_t)b->mhl_last_ovf + host.cursor > mhl_pool_cap(b)) return fail(EPI_ERR_STATE, "row pool overflow in sharded lMHL report");
+  if ((size_t)b->mhl.last_ovf + host.cursor > mhl_pool_cap(b)) return fail(EPI_ERR_STATE, "row pool overflow in sharded lMHL report");
   b->last_kind = KIND_MHL;
   b->last_nrow = host.rows;
   *nrow_out = host.rows;
@@ -1234,17 +1234,19 @@ int epi_batch_mhl_report_dev(epi_batch *b, const char *ctx, int hmax, int hmin, 
 int epi_mhl_tile_positions(void) { return MHL_T; }
 int epi_mhl_slab_sums(void) { return MHL_NSUM; }
 
+static int mhl_set_shared(epi_batch *b, const int64_t *h_keys, const int32_t *h_owned, int32_t nshared, int32_t *d_cnt_slab,
+                          int64_t *d_sum_slab, SlabKind kind) {
+  if (nshared > 0 && (!d_cnt_slab || !d_sum_slab)) return fail(EPI_ERR_ARG, "epi_batch_mhl_set_shared: NULL slab");
+  EPI_TRY(attach_shared(b, h_keys, h_owned, nshared));
+  b->shard.kind = nshared > 0 ? kind : SLAB_NONE;
+  b->shard.d_mhl_cnt_slab = nshared > 0 ? d_cnt_slab : nullptr;
+  b->shard.d_mhl_sum_slab = nshared > 0 ? d_sum_slab : nullptr;
+  return EPI_OK;
+}
+
 int epi_batch_mhl_set_shared(epi_batch *b, const int64_t *h_keys, const int32_t *h_owned, int32_t nshared,
                              int32_t *d_cnt_slab, int64_t *d_sum_slab) {
-  if (nshared > 0 && (!d_cnt_slab || !d_sum_slab)) return fail(EPI_ERR_ARG, "epi_batch_mhl_set_shared: NULL slab");
-  // same key/owner bookkeeping as the CX report (the slot of a tile is assigned when the tile table is built)
-  int32_t dummy = 0;
-  EPI_TRY(epi_batch_cx_set_shared(b, h_keys, h_owned, nshared, nshared > 0 ? &dummy : nullptr));
-  b->d_slab = nullptr;
-  b->d_mhl_cnt_slab = nshared > 0 ? d_cnt_slab : nullptr;
-  b->d_mhl_sum_slab = nshared > 0 ? d_sum_slab : nullptr;
-  b->mhl_shared_fused = false;
-  return EPI_OK;
+  return mhl_set_shared(b, h_keys, h_owned, nshared, d_cnt_slab, d_sum_slab, SLAB_MHL);
 }
 
 int epi_mhl_fused_tile_positions(void) { return MHLF_T; }
@@ -1262,9 +1264,7 @@ int epi_batch_mhl_fused_ok(epi_batch *b, const char *ctx, void *stream, int32_t 
 
 int epi_batch_mhl_set_shared_fused(epi_batch *b, const int64_t *h_keys, const int32_t *h_owned, int32_t nshared,
                                    int32_t *d_cnt_slab, int64_t *d_sum_slab) {
-  EPI_TRY(epi_batch_mhl_set_shared(b, h_keys, h_owned, nshared, d_cnt_slab, d_sum_slab));
-  b->mhl_shared_fused = nshared > 0;
-  return EPI_OK;
+  return mhl_set_shared(b, h_keys, h_owned, nshared, d_cnt_slab, d_sum_slab, SLAB_MHL_FUSED);
 }
 
 // Second half of a sharded lMHL report: the slabs have been sum-reduced across ranks.
@@ -1278,11 +1278,11 @@ int epi_batch_mhl_finish_shared(epi_batch *b, void *stream, int64_t *nrow_out) {
   if (b->last_ntiles == 0) { b->last_kind = KIND_MHL; b->last_nrow = 0; *nrow_out = 0; return EPI_OK; }   // this rank holds no rows: owns no tile
   MhlArgs a{};
   mhl_bind_pool(b, a);
-  a.ctx_mask = b->mhl_ctx_mask;
-  a.shared_cnt = reinterpret_cast<uint32_t *>(b->d_mhl_cnt_slab);
-  a.shared_sums = reinterpret_cast<unsigned long long *>(b->d_mhl_sum_slab);
-  hipLaunchKernelGGL((k_mhl_emit_slab<MHL_WG>), dim3((unsigned)b->shared_keys.size()), dim3(MHL_WG), 0, s, a,
-                     b->d_shared_owned.as<int32_t>(), b->d_slot_tile.as<int32_t>());
+  a.ctx_mask = b->mhl.ctx_mask;
+  a.shared_cnt = reinterpret_cast<uint32_t *>(b->shard.d_mhl_cnt_slab);
+  a.shared_sums = reinterpret_cast<unsigned long long *>(b->shard.d_mhl_sum_slab);
+  hipLaunchKernelGGL((k_mhl_emit_slab<MHL_WG>), dim3((unsigned)b->shard.keys.size()), dim3(MHL_WG), 0, s, a,
+                     b->shard.d_owned.as<int32_t>(), b->shard.d_slot_tile.as<int32_t>());
   EPI_HIP(hipGetLastError());
   return mhl_finish_rows(b, s, nrow_out);
 }
@@ -1297,10 +1297,10 @@ int epi_batch_mhl_fetch_dev(epi_batch *b, int32_t *const d_icols[5], double *con
   hipStream_t s = pick_stream(b, stream);
   const unsigned nb = (unsigned)((b->last_ntiles + 3) / 4);
   prof_begin("gather", s);
-  hipLaunchKernelGGL(k_mhl_gather, dim3(nb), dim3(256), 0, s, b->tiles.as<Tile>(), b->tile_out.as<uint32_t>(),
-                     b->tile_nrow.as<uint32_t>(), b->tile_base.as<uint32_t>(), b->last_ntiles, b->pool_key.as<uint32_t>(),
-                     b->pool_a.as<uint32_t>(), b->pool_d.as<unsigned long long>(), b->pool_e.as<unsigned long long>(),
-                     b->pool_f.as<unsigned long long>(), d_icols[0], d_icols[1],
+  hipLaunchKernelGGL(k_mhl_gather, dim3(nb), dim3(256), 0, s, b->tix.tiles.as<Tile>(), b->pool.tile_out.as<uint32_t>(),
+                     b->pool.tile_nrow.as<uint32_t>(), b->pool.tile_base.as<uint32_t>(), b->last_ntiles, b->pool.key.as<uint32_t>(),
+                     b->pool.a.as<uint32_t>(), b->pool.d.as<unsigned long long>(), b->pool.e.as<unsigned long long>(),
+                     b->pool.f.as<unsigned long long>(), d_icols[0], d_icols[1],
                      d_icols[2], d_icols[3], d_icols[4], d_dcols[0], d_dcols[1]);
   prof_end("gather", s);
   EPI_HIP(hipGetLastError());
@@ -1314,8 +1314,8 @@ int epi_batch_mhl_fetch_host(epi_batch *b, int32_t *const h_icols[5], double *co
   if (nrow == 0) return EPI_OK;
   EPI_HIP(hipSetDevice(b->eng->device));
   hipStream_t s = pick_stream(b, stream);
-  EPI_TRY(b->pool_c.ensure((size_t)nrow * (8 * 2 + 4 * 5) + 64));
-  double *dd = b->pool_c.as<double>();
+  EPI_TRY(b->pool.c.ensure((size_t)nrow * (8 * 2 + 4 * 5) + 64));
+  double *dd = b->pool.c.as<double>();
   double *dc[2] = {dd, dd + nrow};
   int32_t *di = reinterpret_cast<int32_t *>(dd + 2 * nrow);
   int32_t *ic[5];

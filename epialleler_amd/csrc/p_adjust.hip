@@ -390,7 +390,6 @@ __global__ __launch_bounds__(PADJ_WG) void k_padj_scatter(const uint32_t *__rest
 struct PadjScratch {                    // one allocation, released when the call returns; the buffers are pieces of it
   DevBuf arena;
   size_t used = 0;
-  ~PadjScratch() { arena.release(); }
   size_t reserve(size_t bytes) { const size_t at = used; used += (bytes + 255) & ~(size_t)255; return at; }
   template <class T> T *at(size_t off) const { return reinterpret_cast<T *>(arena.as<char>() + off); }
 };
@@ -412,9 +411,7 @@ static int p_adjust(epi_engine *e, const double *d_p, int64_t n, int32_t method,
   uint32_t *const row[2] = {w.at<uint32_t>(o_row[0]), w.at<uint32_t>(o_row[1])};
   double *const terms = w.at<double>(o_terms);
   uint32_t *const table = w.at<uint32_t>(o_table), *const off = w.at<uint32_t>(o_off);
-  DevBuf scan_tmp, agg;                                       // (views: never grown, never released)
-  scan_tmp.p = w.at<void>(o_scan); scan_tmp.cap = (size_t)nblk_scan * 4;
-  agg.p = w.at<void>(o_agg); agg.cap = (size_t)nblk_dscan * 8;
+  DevBuf scan_tmp = DevBuf::view(w.at<void>(o_scan), (size_t)nblk_scan * 4), agg = DevBuf::view(w.at<void>(o_agg), (size_t)nblk_dscan * 8);
   PadjScalars *sc = w.at<PadjScalars>(o_scal);
   uint32_t *ghist = reinterpret_cast<uint32_t *>(sc + 1);
   EPI_HIP(hipMemsetAsync(sc, 0, sizeof(PadjScalars) + 8 * 256 * 4, s));

@@ -412,7 +412,6 @@ struct PatmScratch {
     for (const DevBuf &d : buf) v += d.cap;
     if (v > peak) peak = v;
   }
-  ~PatmScratch() { for (DevBuf &d : buf) d.release(); }
 };
 
 struct PatmStats { int64_t groups = 0, pairs = 0, scratch = 0, fallback = 0; };
@@ -1040,12 +1039,12 @@ int epi_batch_extract_patterns_multi(epi_batch *b, int32_t ntargets, const int32
                                      epi_pattern_table *out) {
   if (ntargets > 0 && out) memset(out, 0, (size_t)ntargets * sizeof(*out));
   EPI_TRY(patm_check_args("epi_batch_extract_patterns_multi", b, ntargets, target_rname, target_start, target_end, ctx, hlght, hlght_off, out));
-  b->patm_groups = 0; b->patm_pairs = 0; b->patm_scratch = 0;
+  b->pat.extract_groups = 0; b->pat.extract_pairs = 0; b->pat.extract_scratch = 0;
   if (ntargets == 0 || b->n == 0) return EPI_OK;
   PatmStats st;
   const int rc = patm_run(b, ntargets, target_rname, target_start, target_end, min_overlap, ctx, min_ctx_freq, clip, reverse_offset,
                           hlght, hlght_off, stream, out, nullptr, st);
-  b->patm_groups = st.groups; b->patm_pairs = st.pairs; b->patm_scratch = st.scratch;
+  b->pat.extract_groups = st.groups; b->pat.extract_pairs = st.pairs; b->pat.extract_scratch = st.scratch;
   if (rc != EPI_OK)
     for (int32_t t = 0; t < ntargets; t++) epi_pattern_table_free(out + t);
   return rc;
@@ -1063,12 +1062,12 @@ int epi_batch_summarise_patterns_multi(epi_batch *b, int32_t ntargets, const int
                                        void *stream, epi_pattern_summary *out) {
   if (ntargets > 0 && out) memset(out, 0, (size_t)ntargets * sizeof(*out));
   EPI_TRY(patm_check_args("epi_batch_summarise_patterns_multi", b, ntargets, target_rname, target_start, target_end, ctx, hlght, hlght_off, out));
-  b->pats_groups = 0; b->pats_pairs = 0; b->pats_fallback = 0;
+  b->pat.summarise_groups = 0; b->pat.summarise_pairs = 0; b->pat.summarise_fallback = 0;
   if (ntargets == 0 || b->n == 0) return EPI_OK;
   PatmStats st;
   const int rc = patm_run(b, ntargets, target_rname, target_start, target_end, min_overlap, ctx, min_ctx_freq, clip, reverse_offset,
                           hlght, hlght_off, stream, nullptr, out, st);
-  b->pats_groups = st.groups; b->pats_pairs = st.pairs; b->pats_fallback = st.fallback;
+  b->pat.summarise_groups = st.groups; b->pat.summarise_pairs = st.pairs; b->pat.summarise_fallback = st.fallback;
   if (rc != EPI_OK)
     for (int32_t t = 0; t < ntargets; t++) epi_pattern_summary_free(out + t);
   return rc;
@@ -1076,17 +1075,17 @@ int epi_batch_summarise_patterns_multi(epi_batch *b, int32_t ntargets, const int
 
 int epi_batch_summarise_patterns_stats(epi_batch *b, int64_t *groups, int64_t *pairs, int64_t *fallback_targets) {
   if (!b) return fail(EPI_ERR_ARG, "epi_batch_summarise_patterns_stats: batch is NULL");
-  if (groups) *groups = b->pats_groups;
-  if (pairs) *pairs = b->pats_pairs;
-  if (fallback_targets) *fallback_targets = b->pats_fallback;
+  if (groups) *groups = b->pat.summarise_groups;
+  if (pairs) *pairs = b->pat.summarise_pairs;
+  if (fallback_targets) *fallback_targets = b->pat.summarise_fallback;
   return EPI_OK;
 }
 
 int epi_batch_extract_patterns_multi_stats(epi_batch *b, int64_t *groups, int64_t *pairs, int64_t *scratch_bytes) {
   if (!b) return fail(EPI_ERR_ARG, "epi_batch_extract_patterns_multi_stats: batch is NULL");
-  if (groups) *groups = b->patm_groups;
-  if (pairs) *pairs = b->patm_pairs;
-  if (scratch_bytes) *scratch_bytes = b->patm_scratch;
+  if (groups) *groups = b->pat.extract_groups;
+  if (pairs) *pairs = b->pat.extract_pairs;
+  if (scratch_bytes) *scratch_bytes = b->pat.extract_scratch;
   return EPI_OK;
 }
 

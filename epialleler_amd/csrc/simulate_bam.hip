@@ -396,9 +396,7 @@ struct SimState {
   void *pinned[2] = {nullptr, nullptr};
   std::thread writer;
   ~SimState() {
-    if (writer.joinable()) writer.join();
-    for (auto &b : bufs) b.release();
-    cols.release(); sizes.release(); err.release(); bad.release(); off.release(); scan_tmp.release(); win.release();
+    if (writer.joinable()) writer.join();                  // first: the writer reads the pinned buffers; the device buffers go after this body
     for (void *p : pinned) if (p) (void)hipHostFree(p);
   }
 };

@@ -260,6 +260,29 @@ int fetch_row_stats(epi_batch *b, hipStream_t s) {
   return EPI_OK;
 }
 
+// The shared tile keys of a sharded report and which of them this rank owns (keys strictly increasing; nshared = 0: none), with
+// no slab attached: what every *_set_shared entry point does first.  A tile's slot is assigned when the tile table is built.
+int attach_shared(epi_batch *b, const int64_t *h_keys, const int32_t *h_owned, int32_t nshared) {
+  if (!b || nshared < 0 || (nshared > 0 && (!h_keys || !h_owned)))
+    return fail(EPI_ERR_ARG, "epi_batch_cx_set_shared: bad arguments");
+  for (int32_t i = 1; i < nshared; i++)
+    if (h_keys[i - 1] >= h_keys[i]) return fail(EPI_ERR_ARG, "epi_batch_cx_set_shared: keys must be strictly increasing");
+  EPI_HIP(hipSetDevice(b->eng->device));
+  ShardState &sh = b->shard;
+  sh.keys.assign(h_keys, h_keys + nshared);
+  sh.owned.assign(h_owned, h_owned + nshared);
+  sh.kind = SLAB_NONE; sh.d_slab = nullptr; sh.d_mhl_cnt_slab = nullptr; sh.d_mhl_sum_slab = nullptr;
+  // a sharded run attaches the same keys for every report: skip the copies when the device already holds them
+  if (nshared == 0 || (sh.dev_keys == sh.keys && sh.dev_owned == sh.owned)) return EPI_OK;
+  EPI_TRY(sh.d_keys.ensure((size_t)nshared * 8));
+  EPI_TRY(sh.d_owned.ensure((size_t)nshared * 4));
+  EPI_HIP(hipMemcpy(sh.d_keys.p, h_keys, (size_t)nshared * 8, hipMemcpyHostToDevice));
+  EPI_HIP(hipMemcpy(sh.d_owned.p, h_owned, (size_t)nshared * 4, hipMemcpyHostToDevice));
+  sh.dev_keys = sh.keys;
+  sh.dev_owned = sh.owned;
+  return EPI_OK;
+}
+
 // Validated row statistics (errors for bad offsets / strands / unsorted rows) + the tile table for tiles of T
 // positions.  One host synchronisation per call (the tile count); the statistics come back with the first one.
 int build_tiles(epi_batch *b, hipStream_t s, int32_t T, RowStats *h, int32_t *ntiles_out, bool *hinted) {
@@ -282,41 +305,41 @@ int build_tiles(epi_batch *b, hipStream_t s, int32_t T, RowStats *h, int32_t *nt
   const int64_t nb = (b->n + TB_ROWS - 1) / TB_ROWS;
   EPI_TRY(check_grid(nb, TB_THREADS, "tile index"));
   int slot = -1;
-  for (int i = 0; i < 4; i++) if (b->tile_hint_T[i] == T) slot = i;
+  for (int i = 0; i < 4; i++) if (b->tix.hint[i].T == T) slot = i;
   const int use_hint = options().tile_hint;                // EPIHIP_TILE_HINT=0: every call counts, scans and asks (A/B runs, tests)
-  auto remember_table = [&](uint32_t nt) -> int {            // (after the pass that filled b->tiles)
-    b->tiles_T = 0;
+  auto remember_table = [&](uint32_t nt) -> int {            // (after the pass that filled b->tix.tiles)
+    b->tix.built.T = 0;
     if (!b->cols_owned) return EPI_OK;
-    EPI_TRY(b->tiles_nt_dev.ensure(4));
-    EPI_HIP(hipMemcpyAsync(b->tiles_nt_dev.p, &sc->ntiles, 4, hipMemcpyDeviceToDevice, s));
-    b->tiles_T = T; b->tiles_nt = (int32_t)nt; b->tiles_lmax = lmax; b->tiles_shared = b->shared_keys;
+    EPI_TRY(b->tix.nt_dev.ensure(4));
+    EPI_HIP(hipMemcpyAsync(b->tix.nt_dev.p, &sc->ntiles, 4, hipMemcpyDeviceToDevice, s));
+    b->tix.built.T = T; b->tix.built.nt = (int32_t)nt; b->tix.built.lmax = lmax; b->tix.built.shared = b->shard.keys;
     return EPI_OK;
   };
-  if (use_hint && hinted && b->cols_owned && b->tiles_T == T && b->tiles_lmax == lmax && b->tiles_shared == b->shared_keys) {
+  if (use_hint && hinted && b->cols_owned && b->tix.built.T == T && b->tix.built.lmax == lmax && b->tix.built.shared == b->shard.keys) {
     // the batch owns its columns and the table of the last build was made for this tile size and these shared keys: it is
     // still there (tiles, d_slot_tile); sc->ntiles gets the count the pass had left, which the caller compares as always
-    hipLaunchKernelGGL(k_misc_reset, dim3(1), dim3(64), 0, s, sc, b->tiles_nt_dev.as<uint32_t>());   // (one launch instead of three copies)
+    hipLaunchKernelGGL(k_misc_reset, dim3(1), dim3(64), 0, s, sc, b->tix.nt_dev.as<uint32_t>());   // (one launch instead of three copies)
     EPI_HIP(hipGetLastError());
     *hinted = true;
-    *ntiles_out = b->tiles_nt;
+    *ntiles_out = b->tix.built.nt;
     return EPI_OK;
   }
-  if (use_hint && hinted && slot >= 0 && b->tile_hint_lmax[slot] == lmax) {
+  if (use_hint && hinted && slot >= 0 && b->tix.hint[slot].lmax == lmax) {
     // The tile count and the per-block offsets are functions of the batch's rows and T alone: with those of an earlier
     // call the table is allocated up front and filled by ONE pass that verifies them block by block; the caller
     // compares sc->ntiles with the count when it next synchronises anyway.
-    const uint32_t nt = (uint32_t)b->tile_hint_nt[slot];
-    EPI_TRY(b->tiles.ensure((size_t)nt * sizeof(Tile)));
-    const int32_t nshared = (int32_t)b->shared_keys.size();
+    const uint32_t nt = (uint32_t)b->tix.hint[slot].nt;
+    EPI_TRY(b->tix.tiles.ensure((size_t)nt * sizeof(Tile)));
+    const int32_t nshared = (int32_t)b->shard.keys.size();
     if (nshared > 0) {
-      EPI_TRY(b->d_slot_tile.ensure((size_t)nshared * 4));
-      EPI_HIP(hipMemsetAsync(b->d_slot_tile.p, 0xFF, (size_t)nshared * 4, s));
+      EPI_TRY(b->shard.d_slot_tile.ensure((size_t)nshared * 4));
+      EPI_HIP(hipMemsetAsync(b->shard.d_slot_tile.p, 0xFF, (size_t)nshared * 4, s));
     }
     EPI_HIP(hipMemsetAsync(&sc->ntiles, 0, 4, s));
     prof_begin("tile_index", s);
     hipLaunchKernelGGL((k_tile_pass<true, true>), dim3((unsigned)nb), dim3(TB_THREADS), 0, s, b->start, b->rname, b->n, lmax, sh,
-                       b->tile_bsum[slot].as<uint32_t>(), b->tiles.as<Tile>(), b->d_shared_keys.as<int64_t>(), nshared,
-                       b->d_slot_tile.as<int32_t>(), sc, (int64_t)nt);
+                       b->tix.hint[slot].bsum.as<uint32_t>(), b->tix.tiles.as<Tile>(), b->shard.d_keys.as<int64_t>(), nshared,
+                       b->shard.d_slot_tile.as<int32_t>(), sc, (int64_t)nt);
     prof_end("tile_index", s);
     EPI_HIP(hipGetLastError());
     EPI_TRY(remember_table(nt));
@@ -324,7 +347,7 @@ int build_tiles(epi_batch *b, hipStream_t s, int32_t T, RowStats *h, int32_t *nt
     *ntiles_out = (int32_t)nt;
     return EPI_OK;
   }
-  b->tiles_T = 0;
+  b->tix.built.T = 0;
   EPI_TRY(b->scan_tmp.ensure((size_t)nb * 4));
   uint32_t *bsum = b->scan_tmp.as<uint32_t>();
   hipLaunchKernelGGL((k_tile_pass<false>), dim3((unsigned)nb), dim3(TB_THREADS), 0, s, b->start, b->rname, b->n, lmax, sh, bsum,
@@ -334,21 +357,21 @@ int build_tiles(epi_batch *b, hipStream_t s, int32_t T, RowStats *h, int32_t *nt
   uint32_t nt = 0;
   EPI_TRY(read_scalars(b, s, &sc->ntiles, 4, &nt));
   if (nt <= 0x7FFFFFF0u) {                                 // remember count and block offsets for the one-pass path above
-    for (int i = 0; i < 4 && slot < 0; i++) if (b->tile_hint_T[i] == 0) slot = i;
-    if (slot >= 0 && b->tile_bsum[slot].ensure((size_t)nb * 4) == EPI_OK &&
-        hipMemcpyAsync(b->tile_bsum[slot].p, bsum, (size_t)nb * 4, hipMemcpyDeviceToDevice, s) == hipSuccess) {
-      b->tile_hint_T[slot] = T; b->tile_hint_nt[slot] = (int32_t)nt; b->tile_hint_lmax[slot] = lmax;
+    for (int i = 0; i < 4 && slot < 0; i++) if (b->tix.hint[i].T == 0) slot = i;
+    if (slot >= 0 && b->tix.hint[slot].bsum.ensure((size_t)nb * 4) == EPI_OK &&
+        hipMemcpyAsync(b->tix.hint[slot].bsum.p, bsum, (size_t)nb * 4, hipMemcpyDeviceToDevice, s) == hipSuccess) {
+      b->tix.hint[slot].T = T; b->tix.hint[slot].nt = (int32_t)nt; b->tix.hint[slot].lmax = lmax;
     }
   }
   if (nt > 0x7FFFFFF0u) return fail(EPI_ERR_ARG, "too many tiles (%u)", nt);
-  EPI_TRY(b->tiles.ensure((size_t)nt * sizeof(Tile)));
-  const int32_t nshared = (int32_t)b->shared_keys.size();
+  EPI_TRY(b->tix.tiles.ensure((size_t)nt * sizeof(Tile)));
+  const int32_t nshared = (int32_t)b->shard.keys.size();
   if (nshared > 0) {   // slot -> this rank's tile index (-1: this rank has no rows near that tile)
-    EPI_TRY(b->d_slot_tile.ensure((size_t)nshared * 4));
-    EPI_HIP(hipMemsetAsync(b->d_slot_tile.p, 0xFF, (size_t)nshared * 4, s));
+    EPI_TRY(b->shard.d_slot_tile.ensure((size_t)nshared * 4));
+    EPI_HIP(hipMemsetAsync(b->shard.d_slot_tile.p, 0xFF, (size_t)nshared * 4, s));
   }
   hipLaunchKernelGGL((k_tile_pass<true>), dim3((unsigned)nb), dim3(TB_THREADS), 0, s, b->start, b->rname, b->n, lmax, sh, bsum,
-                     b->tiles.as<Tile>(), b->d_shared_keys.as<int64_t>(), nshared, b->d_slot_tile.as<int32_t>(), sc, (int64_t)nt);
+                     b->tix.tiles.as<Tile>(), b->shard.d_keys.as<int64_t>(), nshared, b->shard.d_slot_tile.as<int32_t>(), sc, (int64_t)nt);
   EPI_HIP(hipGetLastError());
   EPI_TRY(remember_table(nt));
   *ntiles_out = (int32_t)nt;
@@ -374,7 +397,7 @@ int layout_pool(epi_batch *b, uint32_t slot, int T, int32_t nt, size_t headroom,
     const size_t ovf = (ovf_base >> 4) > 65536 ? (ovf_base >> 4) : 65536;
     const int rc = reserve(b, ovf_base + ovf + headroom);
     if (rc == EPI_OK) break;
-    b->pool_cap = 0; b->pool_cap2 = 0;                     // (a failed growth has released the old buffers; pool_cap2: lMHL's 64-bit columns)
+    b->pool.row_cap = 0; b->pool.row_cap2 = 0;                     // (a failed growth has released the old buffers; row_cap2: lMHL's 64-bit columns)
     if (!slot) return rc;
     slot = 0;
     ovf_base = 0;

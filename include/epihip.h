@@ -863,6 +863,10 @@ void epi_prof_enable(int on);
 /* name: "cx_tiles", "threshold", "mhl_tiles", ...; returns accumulated ms and launch count since reset */
 int epi_prof_get(const char *name, double *ms_total, int64_t *launches);
 void epi_prof_reset(void);
+/* Test hook.  The device allocations the library owns right now, process-wide, and their bytes: every buffer of a batch,
+ * a communicator or a call's scratch (not the engines' staging buffers).  A call that has returned holds none of its
+ * scratch any more, and a batch or communicator that has been freed holds nothing: tests pin ownership with this. */
+int epi_device_allocations(int64_t *live, int64_t *bytes);
 
 /* Test hook.  The library's environment switches (EPIHIP_*: result-neutral hooks that steer a call onto a rarely
  * taken path) are read once per process; this re-reads them. */
