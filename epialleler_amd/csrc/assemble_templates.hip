@@ -1,8 +1,8 @@
 // preprocessBam(mates = "anywhere"): each template's merged row, built in its final output slot.
 //
-// The reader (bam_pack.cpp) has paired the records through their QNAMEs, uploaded every kept record's CIGAR ops, packed
-// query bytes (nt16 << 4) | ctx and QUAL to a device arena, and at the end of the file ordered each template's records
-// (READ1 before READ2, ties in file order), computed its start, width and trims and sorted the rows.  What is left is the
+// The host (bam_pack.cpp; the uploads: bam_device.cpp) has paired the records through their QNAMEs, uploaded every kept
+// record's CIGAR ops, packed query bytes (nt16 << 4) | ctx and QUAL to a device arena, and at the end of the file ordered
+// each template's records (READ1 before READ2, ties in file order), computed its start, width and trims and sorted the rows.  What is left is the
 // byte work of the reference's template merge (src/rcpp_read_bam.cpp:84-151, pack_pe in bam_pack.cpp):
 //   every position starts at quality q0 and byte 0xFB; the records are applied in merge order, and a query base of an
 //   M / = / X op replaces the position's byte when its quality is strictly higher than the position's (a tie keeps the

@@ -6,586 +6,25 @@
 //   rcpp_read_bam_single      src/rcpp_read_bam.cpp:199-343
 //   rcpp_read_bam_mm_single   src/rcpp_read_bam.cpp:364-579  (long-read MM/ML alignments: pack_mm below)
 //   .readBam (templid, sort)  R/internal.R:154-199
-// without HTSlib: BGZF is a series of gzip members whose compressed size is in the
-// BC extra field (SAM spec 4.1), so the blocks are located without inflating (the file is
-// mmap-ed) and inflated in parallel by worker threads, window by window (a record or template
-// that straddles a window seam is carried over); BAM records have a fixed layout (SAM spec 4.2)
-// and are validated before use.  The packed byte per reference position is
-// (nt16 << 4) | ctx_to_idx(XM) (src/epialleleR.h:28-35), filler 0xFB (N,'-').
+// without HTSlib: the file comes as windows of parsed records from the reader (bam_reader.hpp), the records
+// callMethylation would call from bam_call.hpp, and what runs on the device goes through bam_device.hpp.  The packed
+// byte per reference position is (nt16 << 4) | ctx_to_idx(XM) (src/epialleleR.h:28-35), filler 0xFB (N,'-').
 // Output is what the GPU engine consumes: one contiguous byte stream in (rname,start)
-// order + offsets + int32 columns, allocated with hipHostMalloc when a HIP device is
-// usable (so it can be streamed to HBM with hipMemcpyAsync) and with malloc otherwise.
-#include <hip/hip_runtime.h>
-#include <zlib.h>
-#include <dlfcn.h>
+// order + offsets + int32 columns, page-locked when a HIP device is usable (so it can be
+// streamed to HBM with hipMemcpyAsync) and from malloc otherwise.
 #include <stdio.h>
 #include <limits.h>
-#include <fcntl.h>
-#include <stdlib.h>
-#include <string.h>
-#include <sys/mman.h>
-#include <sys/stat.h>
-#include <unistd.h>
 #include <algorithm>
 #include <deque>
-#include <new>
-#include <atomic>
 #include <numeric>
-#include <string>
-#include <thread>
-#include <chrono>
-#include <vector>
-#include "common.hpp"
+#include "bam_reader.hpp"
+#include "bam_call.hpp"
+#include "bam_device.hpp"
 
 using namespace epi;
+using namespace epi::bam;
 
 namespace {
-
-// Large host buffers (the inflated window, the packed bytes of a thread, the record index): 2 MiB-aligned and advised
-// as huge pages -- a first touch then faults 2 MiB at a time instead of 4 KiB (hundreds of thousands of faults per file
-// from 16 threads otherwise).  Released with free().
-inline void *big_malloc(size_t bytes) {
-  constexpr size_t HUGE = (size_t)2 << 20;
-  if (bytes >= 4 * HUGE && !epi::options().no_hugepage) {
-    const size_t r = (bytes + HUGE - 1) & ~(HUGE - 1);
-    void *p = aligned_alloc(HUGE, r);
-    if (p) { (void)madvise(p, r, MADV_HUGEPAGE); return p; }
-  }
-  return malloc(bytes);
-}
-template <class T> struct BigAlloc {
-  using value_type = T;
-  BigAlloc() = default;
-  template <class U> BigAlloc(const BigAlloc<U> &) {}
-  T *allocate(size_t n) { void *p = big_malloc(n * sizeof(T)); if (!p) throw std::bad_alloc(); return static_cast<T *>(p); }
-  void deallocate(T *p, size_t) { free(p); }
-  template <class U> bool operator==(const BigAlloc<U> &) const { return true; }
-  template <class U> bool operator!=(const BigAlloc<U> &) const { return false; }
-};
-
-struct Block {
-  size_t cpos, clen; size_t upos, ulen;                     // compressed payload / uncompressed placement
-  // what the inflating thread found when it walked the block's bytes as a chain of BAM records starting at the block's
-  // first byte: their number, and whether the chain ends exactly at the block's end.  (HTSlib never lets a record
-  // straddle two blocks unless it is larger than one, so this is the true chain nearly always -- the index uses it
-  // only where the true chain does arrive at the block's first byte.)
-  uint32_t spec_n = 0;
-  bool spec_ok = false;
-};
-
-inline uint32_t rd32(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
-inline uint16_t rd16(const uint8_t *p) { return (uint16_t)(p[0] | (p[1] << 8)); }
-
-// The compressed file, memory-mapped (read into a buffer where mmap is not possible): nothing of it is copied.
-struct FileView {
-  const uint8_t *p = nullptr;
-  size_t n = 0;
-  bool mapped = false;
-  std::vector<uint8_t> own;
-  ~FileView() { if (mapped && p) munmap(const_cast<uint8_t *>(p), n); }
-};
-
-int open_file(const char *path, FileView &v) {
-  const int fd = open(path, O_RDONLY);
-  if (fd < 0) return fail(EPI_ERR_ARG, "Unable to open BAM file for reading");   // src/rcpp_read_bam.cpp:34
-  struct stat st;
-  if (fstat(fd, &st) != 0 || st.st_size < 0) { close(fd); return fail(EPI_ERR_ARG, "Unable to read BAM file"); }
-  v.n = (size_t)st.st_size;
-  if (v.n == 0) { close(fd); return EPI_OK; }
-  void *m = mmap(nullptr, v.n, PROT_READ, MAP_PRIVATE, fd, 0);
-  if (m != MAP_FAILED) { v.p = static_cast<const uint8_t *>(m); v.mapped = true; close(fd); return EPI_OK; }
-  v.own.resize(v.n);
-  size_t got = 0;
-  while (got < v.n) {
-    const ssize_t k = read(fd, v.own.data() + got, v.n - got);
-    if (k <= 0) break;
-    got += (size_t)k;
-  }
-  close(fd);
-  if (got != v.n) return fail(EPI_ERR_ARG, "Unable to read BAM file");
-  v.p = v.own.data();
-  return EPI_OK;
-}
-
-// Locate the BGZF blocks (no inflation).
-int bgzf_scan(const uint8_t *in, size_t n, std::vector<Block> &blocks) {
-  size_t p = 0;
-  while (p + 18 <= n) {
-    const uint8_t *h = in + p;
-    if (h[0] != 0x1f || h[1] != 0x8b || h[2] != 8 || !(h[3] & 4)) return fail(EPI_ERR_ARG, "not a BGZF/BAM file");
-    const unsigned xlen = rd16(h + 10);
-    size_t q = p + 12;
-    const size_t xend = p + 12 + xlen;
-    int bsize = -1;
-    while (q + 4 <= xend && xend <= n) {
-      const unsigned slen = rd16(in + q + 2);
-      if (in[q] == 'B' && in[q + 1] == 'C' && slen == 2 && q + 6 <= xend) bsize = rd16(in + q + 4);
-      q += 4 + slen;
-    }
-    if (bsize < 0 || p + (size_t)bsize + 1 > n) return fail(EPI_ERR_ARG, "truncated BGZF block");
-    const size_t blen = (size_t)bsize + 1;
-    if (blen < (xend - p) + 8) return fail(EPI_ERR_ARG, "corrupt BGZF block");
-    Block b;
-    b.cpos = xend;
-    b.clen = blen - (xend - p) - 8;
-    b.ulen = rd32(in + p + blen - 4);
-    b.upos = 0;
-    if (b.ulen > 65536) return fail(EPI_ERR_ARG, "corrupt BGZF block");
-    blocks.push_back(b);
-    p += blen;
-  }
-  if (p != n) return fail(EPI_ERR_ARG, "truncated BGZF block");
-  return EPI_OK;
-}
-
-// libdeflate (its shared library ships with the image; 2-3x zlib's inflate rate) is used when it can be loaded at run
-// time -- no headers needed for its three-call ABI -- and zlib otherwise.  Both produce the same bytes or an error.
-struct FastInflate {
-  void *(*alloc)() = nullptr;
-  int (*run)(void *, const void *, size_t, void *, size_t, size_t *) = nullptr;
-  void (*release)(void *) = nullptr;
-  FastInflate() {
-    if (epi::options().no_libdeflate) return;
-    void *h = dlopen("libdeflate.so.0", RTLD_NOW | RTLD_LOCAL);
-    if (!h) return;
-    alloc = reinterpret_cast<void *(*)()>(dlsym(h, "libdeflate_alloc_decompressor"));
-    run = reinterpret_cast<int (*)(void *, const void *, size_t, void *, size_t, size_t *)>(dlsym(h, "libdeflate_deflate_decompress"));
-    release = reinterpret_cast<void (*)(void *)>(dlsym(h, "libdeflate_free_decompressor"));
-    if (!alloc || !run || !release) { alloc = nullptr; run = nullptr; release = nullptr; }
-  }
-  bool ok() const { return run != nullptr; }
-};
-const FastInflate &fast_inflate() { static const FastInflate f; return f; }
-
-// Inflate blocks [b0, b1) to out + their upos, in parallel.
-int bgzf_inflate_range(const uint8_t *in, std::vector<Block> &blocks, size_t b0, size_t b1, uint8_t *out, int nthreads) {
-  std::atomic<size_t> next(b0);
-  std::atomic<int> bad(0);
-  auto walk = [&](Block &b) {                                // (the bytes are still in this core's cache)
-    const uint8_t *q = out + b.upos;
-    size_t p = 0;
-    uint32_t n = 0;
-    while (p + 4 <= b.ulen) {
-      const size_t bs = rd32(q + p);
-      if (p + 4 + bs > b.ulen) break;
-      p += 4 + bs;
-      n++;
-    }
-    b.spec_n = n;
-    b.spec_ok = p == b.ulen;
-  };
-  auto work = [&]() {
-    const FastInflate &fi = fast_inflate();
-    if (fi.ok()) {
-      void *d = fi.alloc();
-      if (d) {
-        for (;;) {
-          const size_t i = next.fetch_add(1);
-          if (i >= b1) break;
-          Block &b = blocks[i];
-          b.spec_n = 0; b.spec_ok = false;
-          if (b.ulen == 0) continue;
-          size_t got = 0;
-          if (fi.run(d, in + b.cpos, b.clen, out + b.upos, b.ulen, &got) != 0 || got != b.ulen) bad = 1;
-          else walk(b);
-        }
-        fi.release(d);
-        return;
-      }
-    }
-    z_stream zs;                                             // one stream per thread, reset per block (an init / end pair per
-    memset(&zs, 0, sizeof(zs));                              // block allocates and frees its state and window every 64 KiB)
-    if (inflateInit2(&zs, -15) != Z_OK) { bad = 1; return; }
-    for (;;) {
-      const size_t i = next.fetch_add(1);
-      if (i >= b1) break;
-      Block &b = blocks[i];
-      b.spec_n = 0; b.spec_ok = false;
-      if (b.ulen == 0) continue;
-      if (inflateReset(&zs) != Z_OK) { bad = 1; continue; }
-      zs.next_in = const_cast<Bytef *>(in + b.cpos);
-      zs.avail_in = (uInt)b.clen;
-      zs.next_out = out + b.upos;
-      zs.avail_out = (uInt)b.ulen;
-      const int rc = inflate(&zs, Z_FINISH);
-      if (rc != Z_STREAM_END || zs.avail_out != 0) bad = 1;
-      else walk(b);
-    }
-    inflateEnd(&zs);
-  };
-  int nt = nthreads > 0 ? nthreads : 1;
-  if ((size_t)nt > b1 - b0) nt = b1 > b0 ? (int)(b1 - b0) : 1;
-  std::vector<std::thread> th;
-  for (int t = 1; t < nt; t++) th.emplace_back(work);
-  work();
-  for (auto &t : th) t.join();
-  if (bad) return fail(EPI_ERR_ARG, "corrupt BGZF block");
-  return EPI_OK;
-}
-
-inline double tnow() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
-// the caller's nthreads -> threads of the host loops below (the inflate takes nthreads as given)
-inline size_t thread_cap(int nthreads) { return nthreads > 1 ? (size_t)(nthreads > 16 ? 16 : nthreads) : 1; }
-
-// [0, n) in K nearly equal ranges: the K + 1 cut points
-inline std::vector<size_t> even_cuts(size_t n, size_t K) {
-  std::vector<size_t> cut(K + 1);
-  for (size_t k = 0; k <= K; k++) cut[k] = n * k / K;
-  return cut;
-}
-
-// Runs f(k, cut[k], cut[k + 1]) for every part k: part 0 here, the others on a thread each.  Nothing unwinds out of a
-// thread, and the first part's error wins (by part, not by time; the message is thread-local, so each part keeps its own).
-template <class F>
-int fan_out(const std::vector<size_t> &cut, const char *who, const char *what, F &&f) {
-  const size_t K = cut.size() - 1;
-  std::vector<int> rcs(K, EPI_OK);
-  std::vector<std::string> msgs(K);
-  auto run = [&](size_t k) {
-    try {
-      rcs[k] = f(k, cut[k], cut[k + 1]);
-    } catch (const std::bad_alloc &) {
-      rcs[k] = fail(EPI_ERR_NOMEM, "%s: out of host memory", who);
-    } catch (...) {
-      rcs[k] = fail(EPI_ERR_ARG, "%s: unexpected failure while %s", who, what);
-    }
-    if (rcs[k] != EPI_OK) msgs[k] = epi_last_error();
-  };
-  std::vector<std::thread> th;
-  for (size_t k = 1; k < K; k++) th.emplace_back(run, k);
-  run(0);
-  for (auto &t : th) t.join();
-  for (size_t k = 0; k < K; k++)
-    if (rcs[k] != EPI_OK) return fail(rcs[k], "%s", msgs[k].c_str());
-  return EPI_OK;
-}
-
-// f(lo, hi) over K even ranges of [0, n) (one thread below 4096 items)
-template <class F>
-int parallel_ranges(size_t K, size_t n, const char *who, F &&f) {
-  return fan_out(even_cuts(n, n < 4096 ? 1 : K), who, "processing records", [&](size_t, size_t lo, size_t hi) { return f(lo, hi); });
-}
-
-struct Rec {                 // one BAM alignment record, pointing into the inflated stream
-  int32_t tid, pos, mtid, mpos, isize, l_seq;
-  uint32_t n_cigar;
-  uint16_t flag;
-  uint8_t mapq;
-  const char *qname;
-  const uint8_t *cigar, *seq, *qual, *aux, *end;
-};
-
-// One record of the inflated stream -> Rec, with the structural checks HTSlib's bam_read1 makes (sizes consistent
-// with block_size, NUL-terminated name); false: the record is not well-formed.
-bool parse_record(const uint8_t *b, uint32_t bs, Rec *r) {
-  if (bs < 32) return false;
-  r->tid = (int32_t)rd32(b); r->pos = (int32_t)rd32(b + 4);
-  const uint32_t l_qname = b[8];
-  r->mapq = b[9];
-  r->n_cigar = rd16(b + 12); r->flag = rd16(b + 14);
-  r->l_seq = (int32_t)rd32(b + 16); r->mtid = (int32_t)rd32(b + 20); r->mpos = (int32_t)rd32(b + 24); r->isize = (int32_t)rd32(b + 28);
-  if (l_qname < 1 || r->l_seq < 0) return false;
-  const uint64_t need = 32ull + l_qname + 4ull * r->n_cigar + ((uint64_t)r->l_seq + 1) / 2 + (uint64_t)r->l_seq;
-  if (need > bs) return false;
-  r->qname = (const char *)b + 32;
-  if (b[32 + l_qname - 1] != 0) return false;
-  r->cigar = b + 32 + l_qname;
-  r->seq = r->cigar + 4 * (size_t)r->n_cigar;
-  r->qual = r->seq + ((size_t)r->l_seq + 1) / 2;
-  r->aux = r->qual + (size_t)r->l_seq;
-  r->end = b + bs;
-  return true;
-}
-
-// The aux field (tag, type, value: SAM spec 4.2.4) at p, p + 3 <= end: the byte after its value, or NULL where the field
-// is malformed (a string without its NUL, an array header cut short, an unknown type).  Values of fixed size and array
-// elements may run past `end`: the walkers below stop there by their loop condition.
-inline const uint8_t *aux_value_end(const uint8_t *p, const uint8_t *end) {
-  const uint8_t *v = p + 3;
-  switch ((char)p[2]) {
-    case 'A': case 'c': case 'C': return v + 1;
-    case 's': case 'S': return v + 2;
-    case 'i': case 'I': case 'f': return v + 4;
-    case 'Z': case 'H': {
-      const uint8_t *e = (const uint8_t *)memchr(v, 0, (size_t)(end - v));
-      return e ? e + 1 : nullptr;
-    }
-    case 'B': {
-      if (v + 5 > end) return nullptr;
-      const char sub = (char)v[0];
-      const size_t es = (sub == 'c' || sub == 'C') ? 1 : (sub == 's' || sub == 'S') ? 2 : 4;
-      return v + 5 + (size_t)rd32(v + 1) * es;
-    }
-    default: return nullptr;
-  }
-}
-
-// bam_aux_get for Z-typed tags: pointer to the first character, or NULL.  *present: the tag is there (with a NULL
-// result: not as a string).  A tag at or behind a malformed field is absent.
-const char *aux_z(const Rec &r, char a, char b, bool *present) {
-  *present = false;
-  for (const uint8_t *p = r.aux; p + 3 <= r.end;) {
-    const uint8_t *next = aux_value_end(p, r.end);
-    if (!next) return nullptr;
-    if ((char)p[0] == a && (char)p[1] == b) {
-      *present = true;
-      return p[2] == 'Z' || p[2] == 'H' ? (const char *)p + 3 : nullptr;
-    }
-    p = next;
-  }
-  return nullptr;
-}
-
-bool has_tag(const Rec &r, char a, char b) { bool pr; (void)aux_z(r, a, b, &pr); return pr; }
-
-// bam_aux_get for B-typed (array) tags: element type, count and a pointer to the first element; false if absent.  Every
-// array on the way, the tag's own included, must lie inside the record.
-bool aux_b(const Rec &r, char a, char b, char *sub, uint32_t *count, const uint8_t **data) {
-  for (const uint8_t *p = r.aux; p + 3 <= r.end;) {
-    const uint8_t *next = aux_value_end(p, r.end);
-    if (!next || (p[2] == 'B' && next > r.end)) return false;
-    if ((char)p[0] == a && (char)p[1] == b) {
-      if (p[2] != 'B') return false;
-      *sub = (char)p[3]; *count = rd32(p + 4); *data = p + 8;
-      return true;
-    }
-    p = next;
-  }
-  return false;
-}
-
-// bam_aux_get: the tag's type byte, or NULL when the record has no such tag (or its aux data is malformed before it;
-// the tag's own field is not looked at)
-const uint8_t *aux_find(const Rec &r, char a, char b) {
-  for (const uint8_t *p = r.aux; p && p + 3 <= r.end; p = aux_value_end(p, r.end))
-    if ((char)p[0] == a && (char)p[1] == b) return p + 2;
-  return nullptr;
-}
-
-// whether a walk over the record's aux fields (as aux_z makes it) ends exactly at the record's end: tags appended to
-// the record are then found by a later walk, otherwise they lie beyond a malformed field and are not
-bool aux_clean(const Rec &r) {
-  const uint8_t *p = r.aux;
-  while (p && p + 3 <= r.end) p = aux_value_end(p, r.end);
-  return p == r.end;
-}
-
-// query bases (M I S = X) and reference bases (M D N = X) the CIGAR consumes; *bad_op: it holds an operation that BAM
-// does not define (the lengths then leave it out)
-inline void cigar_lens(const Rec &r, uint64_t *qlen, uint64_t *rlen, bool *bad_op) {
-  uint64_t q = 0, d = 0;
-  bool bad = false;
-  for (uint32_t i = 0; i < r.n_cigar; i++) {
-    const uint32_t c = rd32(r.cigar + 4 * i), op = c & 0xF, len = c >> 4;
-    if (op == 0 || op == 1 || op == 4 || op == 7 || op == 8) q += len;
-    if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) d += len;
-    bad |= op > 9;
-  }
-  *qlen = q; *rlen = d; *bad_op = bad;
-}
-
-// the window of inflated bytes: grown without clearing it (std::vector::resize would zero-fill hundreds of megabytes on
-// one thread before every inflate)
-struct RawBuf {
-  uint8_t *p = nullptr;
-  size_t n = 0, cap = 0;
-  ~RawBuf() { free(p); }
-  uint8_t *data() { return p; }
-  size_t size() const { return n; }
-  uint8_t &operator[](size_t i) { return p[i]; }
-  void resize(size_t m) {                                 // keeps the first n bytes (the carry)
-    if (m > cap) {
-      uint8_t *q = static_cast<uint8_t *>(big_malloc(m));
-      if (!q) throw std::bad_alloc();
-      if (n) memcpy(q, p, n);
-      free(p);
-      p = q; cap = m;
-    }
-    n = m;
-  }
-  void release() { free(p); p = nullptr; n = cap = 0; }
-};
-
-struct RecBuf {                                             // a window's records (not value-initialised: 80 bytes x millions)
-  Rec *p = nullptr;
-  size_t n = 0, cap = 0;
-  ~RecBuf() { free(p); }
-  size_t size() const { return n; }
-  void clear() { n = 0; }
-  Rec &operator[](size_t i) { return p[i]; }
-  const Rec &operator[](size_t i) const { return p[i]; }
-  const Rec *begin() const { return p; }
-  const Rec *end() const { return p + n; }
-  void resize_uninit(size_t m) {
-    if (m > cap) {
-      free(p);
-      p = static_cast<Rec *>(big_malloc((m + m / 8 + 16) * sizeof(Rec)));
-      if (!p) { cap = 0; n = 0; throw std::bad_alloc(); }
-      cap = m + m / 8 + 16;
-    }
-    n = m;
-  }
-};
-
-// The file as windows of inflated data (the reference streams records through HTSlib).  next() inflates a run of BGZF
-// blocks behind what the last window left over, then indexes and parses the complete records; the caller takes records
-// [0, r_end) and consume(r_end) carries the rest (a record cut by the window, or the records of a template whose mate is
-// still to come) over to the next window.  keep_all() carries everything instead: the next window is this one and more.
-class BamWindows {
- public:
-  FileView file;                                             // the compressed file ...
-  std::vector<Block> blocks;                                 // ... and its BGZF blocks
-  std::vector<std::string> names;                            // the header's reference sequences ...
-  std::vector<int64_t> lens;                                 // ... and their lengths (the genome check)
-  RecBuf recs;                                               // the window's complete records
-  double t_inflate = 0, t_parse = 0;                         // seconds spent so far (EPIHIP_BAM_TIMING)
-
-  // window_kib 0: default_window bytes.  hdr_msg: the caller's words for a header that cannot be read.
-  int open(const char *path, int32_t window_kib, size_t default_window, int nthreads, const char *hdr_msg) {
-    window_ = window_kib > 0 ? (size_t)window_kib * 1024 : default_window;
-    nthreads_ = nthreads;
-    hdr_msg_ = hdr_msg;
-    EPI_TRY(open_file(path, file));
-    return bgzf_scan(file.p, file.n, blocks);
-  }
-  size_t inflated_size() const {
-    size_t total = 0;
-    for (const Block &b : blocks) total += b.ulen;
-    return total;
-  }
-
-  // *final: the file's last block is in (what the window leaves over then is an error, or the caller's to take)
-  int next(bool *final) {
-    for (;;) {
-      double tw = tnow();
-      const size_t b0 = bi_;                                 // first block inflated into this window
-      size_t add = 0;
-      while (bi_ < blocks.size() && (bi_ == b0 || add + blocks[bi_].ulen <= window_)) { blocks[bi_].upos = carry_ + add; add += blocks[bi_].ulen; bi_++; }
-      *final = bi_ == blocks.size();
-      buf_.resize(carry_ + add);
-      EPI_TRY(bgzf_inflate_range(file.p, blocks, b0, bi_, buf_.data(), nthreads_));
-      t_inflate += tnow() - tw;
-      tw = tnow();
-      if (!header_done_) {
-        bool complete = false;
-        EPI_TRY(parse_header(&complete));
-        if (!complete) {
-          if (*final) return fail(EPI_ERR_ARG, "%s", hdr_msg_);
-          keep_all();                                        // the header is longer than a window: read on
-          continue;
-        }
-        header_done_ = true;
-      }
-      std::vector<Span> spans;
-      const size_t nrec = index_records(b0, spans);
-      EPI_TRY(parse_records(spans, nrec));
-      if (*final && end_ != buf_.size()) return fail(EPI_ERR_ARG, "truncated BAM record");
-      t_parse += tnow() - tw;
-      return EPI_OK;
-    }
-  }
-  // for the caller that needs more records at once than the window gave: fewer than .checkBam's 1024, or one template
-  // that fills the window
-  void keep_all() { carry_ = buf_.size(); }
-  void consume(size_t r_end) {
-    const size_t keep_from = r_end < recs.size() ? roff_[r_end] : end_;
-    carry_ = buf_.size() - keep_from;
-    if (carry_) memmove(buf_.data(), buf_.data() + keep_from, carry_);
-    hdr_end_ = 0;                                            // (the header is gone from the buffer)
-    recs.clear();
-  }
-  const uint8_t *record(size_t i) { return buf_.data() + roff_[i]; }   // record i as the file has it, from its block_size
-  const uint8_t *header() { return buf_.data(); }           // the header as the file has it: until the first consume()
-  size_t header_size() const { return hdr_end_; }
-  void release() { buf_.release(); }                         // after the last window
-
- private:
-  struct Span { size_t p; uint32_t n; };                    // n records starting at byte p (a block, or a single record)
-
-  // BAM header: magic, text, reference names and lengths.  *complete: all of it is in the buffer, up to hdr_end_.
-  int parse_header(bool *complete) {
-    *complete = false;
-    if (buf_.size() < 12) return EPI_OK;
-    if (memcmp(buf_.data(), "BAM\1", 4) != 0) return fail(EPI_ERR_ARG, "%s", hdr_msg_);
-    size_t q = 8 + (size_t)rd32(buf_.data() + 4);
-    if (q + 4 > buf_.size()) return EPI_OK;
-    const uint32_t n_ref = rd32(buf_.data() + q);
-    q += 4;
-    names.clear(); lens.clear();
-    for (uint32_t i = 0; i < n_ref; i++) {
-      if (q + 4 > buf_.size()) return EPI_OK;
-      const uint32_t l = rd32(buf_.data() + q);
-      if (q + 4 + (size_t)l + 4 > buf_.size()) return EPI_OK;
-      if (l == 0 || buf_[q + 4 + l - 1] != 0) return fail(EPI_ERR_ARG, "%s", hdr_msg_);
-      names.emplace_back((const char *)buf_.data() + q + 4);
-      lens.push_back((int64_t)rd32(buf_.data() + q + 4 + l));
-      q += 4 + (size_t)l + 4;
-    }
-    hdr_end_ = q;
-    *complete = true;
-    return EPI_OK;
-  }
-
-  // Index of the complete records of the window.  The chain of block sizes is followed from the first record; wherever
-  // it arrives exactly at the first byte of a BGZF block whose own walk (done by the thread that inflated it) ended
-  // exactly at the block's end, the block's records are taken as a whole -- they are enumerated and parsed by all
-  // threads in parse_records -- so the serial part is one step per block, not per record.
-  size_t index_records(size_t kb, std::vector<Span> &spans) {
-    size_t p = hdr_end_, nrec = 0;
-    for (;;) {
-      while (kb < bi_ && blocks[kb].upos < p) kb++;
-      if (kb < bi_ && blocks[kb].upos == p && blocks[kb].spec_ok && blocks[kb].spec_n > 0) {
-        spans.push_back({p, blocks[kb].spec_n});
-        nrec += blocks[kb].spec_n;
-        p += blocks[kb].ulen;
-        continue;
-      }
-      if (p + 4 > buf_.size()) break;
-      const uint32_t bs = rd32(buf_.data() + p);
-      if (p + 4 + (size_t)bs > buf_.size()) break;           // cut by the window (or by the end of the file)
-      spans.push_back({p, 1u});
-      nrec++;
-      p += 4 + (size_t)bs;
-    }
-    end_ = p;
-    return nrec;
-  }
-
-  int parse_records(const std::vector<Span> &spans, size_t nrec) {
-    recs.resize_uninit(nrec);
-    roff_.resize(nrec);
-    std::vector<size_t> base(spans.size() + 1, 0);
-    for (size_t i = 0; i < spans.size(); i++) base[i + 1] = base[i] + spans[i].n;
-    std::atomic<size_t> next(0);
-    const size_t K = nrec < 4096 ? 1 : thread_cap(nthreads_);
-    // (a part is a thread here, not a range: each takes a few spans at a time until none is left)
-    return fan_out(even_cuts(K, K), "epi_preprocess_bam", "reading records", [&](size_t, size_t, size_t) -> int {
-      for (;;) {
-        const size_t i0 = next.fetch_add(16);
-        if (i0 >= spans.size()) return EPI_OK;
-        const size_t i1 = i0 + 16 < spans.size() ? i0 + 16 : spans.size();
-        for (size_t i = i0; i < i1; i++) {
-          size_t q = spans[i].p;
-          for (size_t j = base[i]; j < base[i + 1]; j++) {
-            const uint8_t *rp = buf_.data() + q;
-            const uint32_t bs = rd32(rp);
-            roff_[j] = q;
-            if (!parse_record(rp + 4, bs, &recs[j])) return fail(EPI_ERR_ARG, "corrupt BAM record");
-            q += 4 + (size_t)bs;
-          }
-        }
-      }
-    });
-  }
-
-  RawBuf buf_;                                               // [carry | the window's blocks]
-  std::vector<size_t> roff_;                                 // offsets of the window's records in buf_
-  size_t window_ = 0, carry_ = 0, bi_ = 0, hdr_end_ = 0, end_ = 0;   // end_: the byte after the last complete record
-  int nthreads_ = 1;
-  const char *hdr_msg_ = "";
-  bool header_done_ = false;
-};
 
 inline uint8_t ctx_idx(char c) { return (uint8_t)ctx_to_idx((unsigned char)c); }
 inline uint8_t seqi_shifted(const uint8_t *s, uint32_t i) { return (uint8_t)((s[i >> 1] << ((i & 1) << 2)) & 0xF0); }   // epialleleR.h:32
@@ -674,6 +113,18 @@ inline char ctx_reverse(int b0, int b1, int b2) {                // G at i with 
   if (b2 != 7 || !tri_ok(b0) || !tri_ok(b1)) return '.';
   return b1 == 3 ? 'z' : b0 == 3 ? 'x' : 'h';
 }
+
+// big_malloc as a standard allocator, for the packed bytes of a thread.  (Here and not next to big_malloc: with a type of
+// this unit's own for its allocator the vector's members have internal linkage, and push_row's insert is inlined.)
+template <class T> struct BigAlloc {
+  using value_type = T;
+  BigAlloc() = default;
+  template <class U> BigAlloc(const BigAlloc<U> &) {}
+  T *allocate(size_t n) { void *p = big_malloc(n * sizeof(T)); if (!p) throw std::bad_alloc(); return static_cast<T *>(p); }
+  void deallocate(T *p, size_t) { free(p); }
+  template <class U> bool operator==(const BigAlloc<U> &) const { return true; }
+  template <class U> bool operator!=(const BigAlloc<U> &) const { return false; }
+};
 
 struct Packed {
   std::vector<int32_t> rname, strand, start;
@@ -769,119 +220,6 @@ class QnameMap {
   std::vector<size_t> off_;        // per id: its key in names_
   std::vector<char> names_;
 };
-
-// ---- callMethylation's call set (rcpp_call_methylation_genome, src/rcpp_call_methylation.cpp:27-177, with
-// .callMethylation's tag choice, R/internal.R:405-432): which records are called and what the GPU needs for them.
-// Shared by callMethylation (BAM out, call_impl below) and preprocessBam with a genome (preprocess_impl), so that the
-// second sees exactly the records, strand letters and errors the first would have produced. ----------------------
-enum StrandTag { TAG_XG = 0, TAG_YD = 1, TAG_ZS = 2 };
-
-// .callMethylation (R/internal.R:412-423): the strand tag from the first 1024 records; force_tag ("XG" / "YD" / "ZS")
-// skips the look (rcpp_call_methylation_genome's own contract)
-int call_choose_tag(const Rec *recs, size_t nrec, const char *force_tag, StrandTag *tag) {
-  bool tXG = false, tYD = false, tZS = false;
-  for (size_t i = 0; i < nrec && i < 1024; i++) {
-    tXG |= aux_find(recs[i], 'X', 'G') != nullptr;
-    tYD |= aux_find(recs[i], 'Y', 'D') != nullptr;
-    tZS |= aux_find(recs[i], 'Z', 'S') != nullptr;
-  }
-  if (force_tag) *tag = strcmp(force_tag, "XG") == 0 ? TAG_XG : strcmp(force_tag, "YD") == 0 ? TAG_YD : TAG_ZS;
-  else if (nrec == 0) return fail(EPI_ERR_ARG, "Empty file provided! Exiting");
-  else if (tXG) *tag = TAG_XG;
-  else if (tYD) *tag = TAG_YD;
-  else if (tZS) *tag = TAG_ZS;
-  else return fail(EPI_ERR_ARG, "Unable to call methylation: neither of XG/YD/ZS tags is present (genome strand unknown).\nExiting");
-  return EPI_OK;
-}
-
-// the header's reference sequences must be the genome's, by name and length (src/rcpp_call_methylation.cpp:41-72)
-int call_check_genome(epi_genome *g, const std::vector<std::string> &names, const std::vector<int64_t> &lens) {
-  const int32_t ng = epi_genome_count(g);
-  for (size_t i = 0; i < names.size(); i++)
-    if ((int32_t)i >= ng || epi_genome_length(g, (int32_t)i) != lens[i] || names[i] != epi_genome_name(g, (int32_t)i))
-      return fail(EPI_ERR_ARG, "BAM reference sequence doesn't match the provided genome sequence");
-  return EPI_OK;
-}
-
-struct CallSet {                      // the records of one window to call
-  std::vector<uint8_t> call;          // per record: 1 = call it
-  std::vector<uint8_t> s_meth, s_conv;
-  std::vector<int64_t> call_idx;      // per called record of the packed range: its index among the called ones
-  std::vector<CallRec> crec;
-  std::vector<uint32_t> cigar;
-  std::vector<uint8_t> seq;
-  std::vector<uint8_t> xm;            // the GPU's output: l_seq bytes per called record, at its xm_off
-  int64_t ncig = 0, nseq = 0, nxm = 0;
-};
-
-// Which of recs[0, n) are called (mapped, carrying the strand tag, no XM: :84-89), their strand letters (the tag's first
-// two characters, or the strand YD / ZS names: :92-97), and the checks that keep every access in bounds (DESIGN.md
-// section 2: the reference reads out of bounds here).  A called record grows by the XG tag (YD / ZS input) and XM.
-int call_select(const Rec *recs, size_t n, StrandTag tag, const std::vector<std::string> &names,
-                const std::vector<int64_t> &lens, size_t K, const char *who, CallSet &S) {
-  const char t0 = tag == TAG_XG ? 'X' : tag == TAG_YD ? 'Y' : 'Z', t1 = tag == TAG_XG ? 'G' : tag == TAG_YD ? 'D' : 'S';
-  S.call.resize(n); S.s_meth.resize(n); S.s_conv.resize(n);
-  return parallel_ranges(K, n, who, [&](size_t lo, size_t hi) -> int {
-    for (size_t i = lo; i < hi; i++) {
-      const Rec &r = recs[i];
-      S.call[i] = 0;
-      const uint8_t *st = aux_find(r, t0, t1);
-      if ((r.flag & 4) || !st || aux_find(r, 'X', 'M')) continue;          // written unchanged
-      // the strand tag's first two characters (bam_aux_get's pointer [1] and [2])
-      const uint8_t c1 = st + 1 < r.end ? st[1] : 0, c2 = st + 2 < r.end ? st[2] : 0;
-      if (tag == TAG_XG) { S.s_meth[i] = c1; S.s_conv[i] = c2; }
-      else {
-        const bool ga = tag == TAG_YD ? c1 == 'r' : c1 == '-';
-        S.s_meth[i] = ga ? 'G' : 'C'; S.s_conv[i] = ga ? 'A' : 'T';
-      }
-      if (r.tid < 0 || (size_t)r.tid >= names.size()) return fail(EPI_ERR_ARG, "corrupt BAM record %s: reference id out of range", r.qname);
-      if (r.pos < 0) return fail(EPI_ERR_ARG, "corrupt BAM record %s: position out of range", r.qname);
-      uint64_t qlen, rlen;
-      bool bad_op;
-      cigar_lens(r, &qlen, &rlen, &bad_op);
-      if (bad_op) return fail(EPI_ERR_ARG, "Unknown CIGAR operation for BAM entry %s", r.qname);
-      if (qlen != (uint64_t)r.l_seq) return fail(EPI_ERR_ARG, "corrupt BAM record %s: CIGAR does not match the sequence length", r.qname);
-      if ((uint64_t)r.pos + rlen > (uint64_t)lens[(size_t)r.tid])
-        return fail(EPI_ERR_ARG, "corrupt BAM record %s: alignment runs past the end of reference sequence %s", r.qname, names[(size_t)r.tid].c_str());
-      const uint64_t bs = (uint64_t)(r.end - (const uint8_t *)r.qname) + 32;   // block_size (the name follows 32 fixed bytes)
-      if (bs + (tag == TAG_XG ? 0 : 6) + 4 + (uint64_t)r.l_seq > 0x7FFFFFFFull)
-        return fail(EPI_ERR_ARG, "corrupt BAM record %s: record too large", r.qname);
-      S.call[i] = 1;
-    }
-    return EPI_OK;
-  });
-}
-
-// the CallRec, CIGAR and SEQ inputs of the called records among recs[0, n) (n: at most call_select's range)
-int call_pack_inputs(const Rec *recs, size_t n, size_t K, const char *who, CallSet &S) {
-  S.call_idx.resize(n);
-  S.crec.clear();
-  int64_t ncig = 0, nseq = 0, nxm = 0;
-  for (size_t i = 0; i < n; i++) {
-    if (!S.call[i]) continue;
-    const Rec &r = recs[i];
-    CallRec c;
-    memset(&c, 0, sizeof(c));
-    c.cig_off = ncig; c.seq_off = nseq; c.xm_off = nxm;
-    c.tid = r.tid; c.pos = r.pos; c.l_seq = r.l_seq; c.n_cig = (int32_t)r.n_cigar;
-    c.s_meth = S.s_meth[i]; c.s_conv = S.s_conv[i];
-    S.call_idx[i] = (int64_t)S.crec.size();
-    S.crec.push_back(c);
-    ncig += r.n_cigar; nseq += ((int64_t)r.l_seq + 1) / 2; nxm += r.l_seq;
-  }
-  S.ncig = ncig; S.nseq = nseq; S.nxm = nxm;
-  S.cigar.resize((size_t)ncig); S.seq.resize((size_t)nseq); S.xm.resize((size_t)nxm);
-  return parallel_ranges(K, n, who, [&](size_t lo, size_t hi) -> int {
-    for (size_t i = lo; i < hi; i++) {
-      if (!S.call[i]) continue;
-      const Rec &r = recs[i];
-      const CallRec &c = S.crec[(size_t)S.call_idx[i]];
-      if (r.n_cigar) memcpy(S.cigar.data() + c.cig_off, r.cigar, 4 * (size_t)r.n_cigar);
-      if (r.l_seq) memcpy(S.seq.data() + c.seq_off, r.seq, ((size_t)r.l_seq + 1) / 2);
-    }
-    return EPI_OK;
-  });
-}
 
 // ---- .readBam: skip flags (R/internal.R:173-177) and the packers ----
 struct PackCtx {                      // what the packers read of the call's options and of the file; never written by them
@@ -1073,29 +411,10 @@ int pack_se(const PackCtx &c, const Rec *recs, size_t r_lo, size_t r_hi, Packed 
   return EPI_OK;
 }
 
-// The output bytes go to page-locked memory (the upload DMAs straight from it).  Pinning ~100 MB takes tens of
-// milliseconds, so it starts when the file is opened, next to the inflate / pack work, sized by an estimate (a base is at
-// least 2.5 bytes of record: half a byte of SEQ, QUAL, XM); a template set that turns out larger is allocated at the end
-// instead.
-struct PinAhead {
-  std::thread th;
-  void *p = nullptr;
-  size_t cap = 0;
-  bool ok = false;
-  ~PinAhead() { release(); }
-  void wait() { if (th.joinable()) th.join(); }
-  void release() {
-    wait();
-#ifndef EPI_HOST_ONLY
-    if (ok && p) (void)hipHostFree(p);
-#endif
-    p = nullptr; ok = false;
-  }
-};
-
-#ifndef EPI_HOST_ONLY
-// template bytes per inflated byte, sampled from the file's first records (sum of l_seq over sum of record sizes: a
-// PE150 Bismark / DRAGEN file gives ~0.35, where the worst-case bound is 0.4); 0.5 when the sample cannot be read
+// The output buffer pinned ahead (PinAhead, bam_device.hpp) is sized by an estimate (a base is at least 2.5 bytes of
+// record: half a byte of SEQ, QUAL, XM): template bytes per inflated byte, sampled from the file's first records (sum of
+// l_seq over sum of record sizes: a PE150 Bismark / DRAGEN file gives ~0.35, where the worst-case bound is 0.4); 0.5 when
+// the sample cannot be read
 double pin_ratio_sample(const BamWindows &win) {
   std::vector<Block> head;
   size_t up = 0;
@@ -1117,20 +436,11 @@ double pin_ratio_sample(const BamWindows &win) {
 }
 
 // the buffer pinned ahead: the file's inflated size times the sampled ratio plus 15 % (files below 8 MiB: none)
-void pin_ahead_start(const BamWindows &win, PinAhead &pin) {
+void pin_ahead(const BamWindows &win, PinAhead &pin) {
   const size_t total = win.inflated_size();
   if (total < ((size_t)8 << 20)) return;
-  pin.cap = ((size_t)((double)total * pin_ratio_sample(win) * 1.15) + ((size_t)1 << 20) + 15) / 16 * 16;
-  int cur_dev = -1;                                          // the caller's device, not device 0: every rank of a multi-GPU job pins under its own GPU
-  if (hipGetDevice(&cur_dev) != hipSuccess) { (void)hipGetLastError(); cur_dev = -1; }
-  pin.th = std::thread([&pin, cur_dev]() {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0 && (cur_dev < 0 || hipSetDevice(cur_dev) == hipSuccess) &&
-        hipHostMalloc(&pin.p, pin.cap, hipHostMallocDefault) == hipSuccess) pin.ok = true;
-    else (void)hipGetLastError();
-  });
+  pin_ahead_start(pin, ((size_t)((double)total * pin_ratio_sample(win) * 1.15) + ((size_t)1 << 20) + 15) / 16 * 16);
 }
-#endif
 
 // mates = "anywhere": a kept record of paired-end input, wherever its mate is.  Its QNAME is kept once per template (in
 // the job's qmap); its CIGAR ops, packed query bytes and qualities go to the device arena at aoff, 4 * n_cig + 2 * l_seq
@@ -1172,9 +482,7 @@ struct BamJob {
   // with a genome: the window's records to call
   CallSet CS;
   int64_t ncalled = 0;
-#ifndef EPI_HOST_ONLY
-  CallWork wk;
-#endif
+  DeviceStatePtr dev = device_state_new();                   // the GPU's buffers of the windows to call, and the arena below
   // the templates, in file order
   Packed P;                                                  // the small columns of all templates (the bytes stay in `segs`)
   std::deque<Packed> segs;                                   // what the packing threads produced, kept until the ordered copy
@@ -1189,12 +497,8 @@ struct BamJob {
   std::vector<const char *> wk_xm;
   std::vector<uint32_t> wk_span, wk_ri;
   std::vector<uint64_t> wk_hash;
-  size_t arena_used = 0;
-  int stage_k = 0;
-#ifndef EPI_HOST_ONLY
-  DevBuf arena;                                              // sized by the file's inflated bytes: a kept record's inputs are
-                                                             // smaller than the record
-#endif
+  size_t arena_used = 0;                                     // of the device arena (dev), which is sized by the file's inflated
+  int stage_k = 0;                                           // bytes: a kept record's inputs are smaller than the record
   std::vector<AsmRec> arec;                                  // kept records in merge order, template after template
   std::vector<int64_t> tpl_lo;                               // per template: its first record in arec (n + 1 entries)
   // the output
@@ -1250,12 +554,7 @@ int check_bam(BamJob &J) {
   if (J.paired && !sorted && !J.anyorder) return fail(EPI_ERR_ARG, "BAM file seems to be paired-end but not sorted by name! Please sort using 'samtools sort -n -o out.bam in.bam'. Exiting");
   if (J.opt.paired >= 0 && (J.opt.paired != 0) != J.paired) return fail(EPI_ERR_ARG, "Expected endness is different from detected! Exiting");
   J.asm_mode = J.anyorder && J.paired && !J.tMM;
-#ifndef EPI_HOST_ONLY
-  if (J.asm_mode) {
-    EPI_HIP(hipSetDevice(J.eng->device));
-    EPI_TRY(J.arena.ensure(J.win.inflated_size()));
-  }
-#endif
+  if (J.asm_mode) EPI_TRY(arena_reserve(J.dev.get(), J.eng, J.win.inflated_size()));
   return EPI_OK;
 }
 
@@ -1266,13 +565,9 @@ int call_window(BamJob &J, size_t r_end) {
   EPI_TRY(call_pack_inputs(J.win.recs.begin(), r_end, J.KT, "epi_preprocess_bam", CS));
   const int64_t ncall = (int64_t)CS.crec.size();
   J.ncalled += ncall;
-#ifndef EPI_HOST_ONLY
   if (!J.tMM)                                                // (the MM/ML packer reads no XG / XM)
-    EPI_TRY(call_methylation_window(J.eng, J.genome, J.wk, CS.crec.data(), ncall, CS.cigar.data(), CS.ncig, CS.seq.data(),
-                                    CS.nseq, CS.nxm, CALL_PACKED, CS.xm.data()));
-#else
-  return fail(EPI_ERR_NODEVICE, "epi_preprocess_bam_genome: this build has no device code");
-#endif
+    EPI_TRY(device_call_window(J.dev.get(), J.eng, J.genome, CS.crec.data(), ncall, CS.cigar.data(), CS.ncig, CS.seq.data(),
+                               CS.nseq, CS.nxm, CALL_PACKED, CS.xm.data()));
   J.t_call += tnow() - t0;
   return EPI_OK;
 }
@@ -1311,13 +606,12 @@ int pack_window(BamJob &J, size_t r_end) {
   return EPI_OK;
 }
 
-#ifndef EPI_HOST_ONLY
 // mates = "anywhere": the inputs of kept records [k0, kept.size()), all of this window, go to the device arena through
 // the engine's two pinned staging buffers: filled by the threads while the copy stream drains the other one
 int upload_kept(BamJob &J, size_t k0, size_t wbytes) {
   const RecBuf &recs = J.win.recs;
   const std::vector<Kept> &kept = J.kept;
-  if (J.arena_used + wbytes > J.arena.cap) return fail(EPI_ERR_STATE, "epi_preprocess_bam_anyorder: device arena too small");
+  if (J.arena_used + wbytes > arena_capacity(J.dev.get())) return fail(EPI_ERR_STATE, "epi_preprocess_bam_anyorder: device arena too small");
   auto fill = [&](size_t i, uint8_t *o) {                   // kept record k0 + i -> its arena bytes at o
     const Rec &r = recs[J.wk_ri[i]];
     if (r.n_cigar) memcpy(o, r.cigar, 4 * (size_t)r.n_cigar);
@@ -1329,13 +623,13 @@ int upload_kept(BamJob &J, size_t k0, size_t wbytes) {
   for (size_t i = 0; i < nk;) {
     uint8_t *st;
     size_t cap;
-    EPI_TRY(stage_buffer(J.eng, J.stage_k, &st, &cap));
+    EPI_TRY(arena_stage(J.eng, J.stage_k, &st, &cap));
     size_t j = i, bytes = 0;
     while (j < nk && bytes + kept_bytes(kept[k0 + j]) <= cap) bytes += kept_bytes(kept[k0 + j++]);
     if (j == i) {                                           // one record larger than a staging buffer: a copy of its own
       std::vector<uint8_t> big(kept_bytes(kept[k0 + i]));
       fill(i, big.data());
-      EPI_HIP(hipMemcpy(J.arena.as<uint8_t>() + kept[k0 + i].aoff, big.data(), big.size(), hipMemcpyHostToDevice));
+      EPI_TRY(arena_write(J.dev.get(), kept[k0 + i].aoff, big.data(), big.size()));
       i++;
       continue;
     }
@@ -1344,13 +638,12 @@ int upload_kept(BamJob &J, size_t k0, size_t wbytes) {
       for (size_t x = i + lo; x < i + hi; x++) fill(x, st + (kept[k0 + x].aoff - a0));
       return EPI_OK;
     }));
-    EPI_TRY(stage_send(J.eng, J.stage_k, J.arena.as<uint8_t>() + a0, bytes));
+    EPI_TRY(arena_send(J.dev.get(), J.eng, J.stage_k, a0, bytes));
     J.stage_k ^= 1;
     i = j;
   }
   return EPI_OK;
 }
-#endif
 
 // mates = "anywhere": the window's records [0, nrec): which are kept (pack_pe's filters and checks), their template ids,
 // and their inputs queued for upload
@@ -1395,11 +688,7 @@ int collect_window(BamJob &J, size_t nrec) {
   }
   const double t1 = tnow();
   J.t_pair += t1 - t0;
-#ifndef EPI_HOST_ONLY
   EPI_TRY(upload_kept(J, k0, wbytes));
-#else
-  (void)k0;
-#endif
   J.arena_used += wbytes;
   J.t_upload += tnow() - t1;
   return EPI_OK;
@@ -1487,9 +776,6 @@ int allocate_output(BamJob &J) {
   for (size_t i = 0; i < n; i++) nbytes += (size_t)J.len[i];
   size_t cap = (nbytes + 15) / 16 * 16 + 64;
   void *xmp = nullptr;
-#ifdef EPI_HOST_ONLY
-  xmp = malloc(cap); out->pinned = 0;                      // host-only sanitizer build (`make asan`)
-#else
   PinAhead &pin = J.pin;
   pin.wait();
   // the buffer pinned while the file was being read -- unless it turned out too small, or more than a quarter larger
@@ -1499,11 +785,9 @@ int allocate_output(BamJob &J) {
     pin.p = nullptr; pin.ok = false;
   } else {
     pin.release();
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0 && hipHostMalloc(&xmp, cap, hipHostMallocDefault) == hipSuccess) out->pinned = 1;
-    else { (void)hipGetLastError(); xmp = malloc(cap); out->pinned = 0; }
+    if (pinned_alloc(cap, &xmp)) out->pinned = 1;
+    else { xmp = malloc(cap); out->pinned = 0; }
   }
-#endif
   out->xm = (uint8_t *)xmp;
   out->off = (int64_t *)malloc((n + 1) * sizeof(int64_t));
   out->rname = (int32_t *)malloc((n + 1) * sizeof(int32_t));
@@ -1537,7 +821,6 @@ int copy_ordered(BamJob &J) {
 
 // mates = "anywhere": the rows, merged on the GPU in their output slots
 int assemble_on_gpu(BamJob &J) {
-#ifndef EPI_HOST_ONLY
   const size_t n = J.order.size();
   std::vector<AsmTpl> tpl(n);
   int64_t qbytes = 0;
@@ -1548,19 +831,14 @@ int assemble_on_gpu(BamJob &J) {
     x.q_off = 0;
     if (J.len[t] > kAsmLdsWidth) { x.q_off = qbytes; qbytes += J.len[t]; }
   }
-  const double t0 = tnow();
-  EPI_HIP(hipStreamSynchronize(J.eng->copy_stream));         // (the arena's last uploads)
-  J.t_upload += tnow() - t0;
   const uint8_t q0 = (uint8_t)(J.ctx.min_baseq - (J.ctx.min_baseq > 0 ? 1 : 0));   // src/rcpp_read_bam.cpp:30,57
-  double t_kernel = 0, t_d2h = 0;
-  EPI_TRY(assemble_templates(J.eng, J.arena.as<uint8_t>(), tpl.data(), (int64_t)n, J.arec.data(), (int64_t)J.arec.size(), q0,
-                             J.ctx.trim5, J.nbytes, qbytes, J.out->xm, &t_kernel, &t_d2h));
+  double t_sync = 0, t_kernel = 0, t_d2h = 0;
+  EPI_TRY(arena_assemble(J.dev.get(), J.eng, tpl.data(), (int64_t)n, J.arec.data(), (int64_t)J.arec.size(), q0, J.ctx.trim5,
+                         J.nbytes, qbytes, J.out->xm, &t_sync, &t_kernel, &t_d2h));
+  J.t_upload += t_sync;
   if (J.timing)
     fprintf(stderr, "[bam] (anywhere: inflate %.3f s, parse %.3f s, pairing %.3f s, upload %.3f s, grouping %.3f s, "
                     "kernel %.3f s, D2H %.3f s)\n", J.win.t_inflate, J.win.t_parse, J.t_pair, J.t_upload, J.t_group, t_kernel, t_d2h);
-#else
-  (void)J;
-#endif
   return EPI_OK;
 }
 
@@ -1608,9 +886,7 @@ int preprocess_impl(const char *path, const epi_bam_options *opt_in, epi_templat
   BamWindows &win = J.win;
   // with a genome, the header messages are callMethylation's: it reads the file first
   EPI_TRY(win.open(path, J.opt.window_kib, (size_t)256 << 20, J.opt.nthreads, genome ? "Unable to read input BAM header" : "Unable to read BAM header"));
-#ifndef EPI_HOST_ONLY
-  pin_ahead_start(win, J.pin);
-#endif
+  pin_ahead(win, J.pin);
   bool checked = false;
   for (;;) {
     bool final;
@@ -1672,128 +948,13 @@ int preprocess_entry(const char *path, const epi_bam_options *opt_in, epi_templa
   return rc;
 }
 
-// ---- callMethylation: BAM in, BAM out (rcpp_call_methylation_genome, src/rcpp_call_methylation.cpp:27-177, with
-// .callMethylation's tag choice, R/internal.R:405-432) ------------------------------------------------------------------
-// The file goes through the reader's windows (block scan, parallel inflate and parse_record).  Per window the
-// host picks the records to call (mapped, carrying the strand tag, no XM yet), checks them and packs their CIGAR and
-// SEQ; the GPU computes their XM bytes (call_methylation.hip); the records are then written out in input order -- the
-// called ones with XG (when the tag was YD or ZS) and XM appended -- and deflated into BGZF blocks by `nthreads`
-// threads.  Host memory is bounded by the window (inflated bytes, the records written out, the packed call inputs).
-#ifndef EPI_HOST_ONLY
-struct Window {                       // what one window's records turn into
-  std::vector<uint64_t> out_off;      // per record: where its output starts (n + 1 entries)
-  std::vector<uint8_t> out;
-};
-
-// the window's records, in input order, with the new tags appended (bam_aux_append / bam_aux_update_str)
-int call_splice(BamWindows &win, const CallSet &S, StrandTag tag, size_t K, Window &W) {
-  const size_t nrec = win.recs.size();
-  W.out.resize((size_t)W.out_off[nrec]);
-  return parallel_ranges(K, nrec, "epi_call_methylation", [&](size_t lo, size_t hi) -> int {
-    for (size_t i = lo; i < hi; i++) {
-      const uint8_t *src = win.record(i);
-      const uint32_t bs = rd32(src);
-      uint8_t *o = W.out.data() + W.out_off[i];
-      if (!S.call[i]) { memcpy(o, src, 4 + (size_t)bs); continue; }
-      const uint64_t nb = W.out_off[i + 1] - W.out_off[i] - 4;
-      o[0] = (uint8_t)nb; o[1] = (uint8_t)(nb >> 8); o[2] = (uint8_t)(nb >> 16); o[3] = (uint8_t)(nb >> 24);
-      memcpy(o + 4, src + 4, bs);
-      o += 4 + (size_t)bs;
-      if (tag != TAG_XG) {
-        const bool ga = S.s_meth[i] == 'G';
-        const uint8_t xg[6] = {'X', 'G', 'Z', (uint8_t)(ga ? 'G' : 'C'), (uint8_t)(ga ? 'A' : 'T'), 0};
-        memcpy(o, xg, 6);
-        o += 6;
-      }
-      o[0] = 'X'; o[1] = 'M'; o[2] = 'Z';
-      const Rec &r = win.recs[i];
-      if (r.l_seq) memcpy(o + 3, S.xm.data() + S.crec[(size_t)S.call_idx[i]].xm_off, (size_t)r.l_seq);
-      o[3 + r.l_seq] = 0;
-    }
-    return EPI_OK;
-  });
-}
-
-int call_impl(epi_engine *eng, const char *in_path, const char *out_path, epi_genome *g, const char *force_tag,
-              int nthreads, int32_t window_kib, int64_t *nrecs_out, int64_t *ncalled_out) {
-  BamWindows win;
-  EPI_TRY(win.open(in_path, window_kib, (size_t)64 << 20, nthreads, "Unable to read input BAM header"));
-  const size_t K = thread_cap(nthreads);
-  bool checked = false;
-  StrandTag tag = TAG_XG;
-  BgzfWriter out;
-  CallWork wk;
-  CallSet S;
-  Window W;
-  int64_t nrecs = 0, ncalled = 0;
-  // phase times (EPIHIP_BAM_TIMING, as for the reader): inflate + index, host preparation, GPU, splice, deflate + write
-  const bool timing = epi::options().bam_timing != 0;
-  double t_phase[5] = {0, 0, 0, 0, 0}, t_mark = tnow();
-  auto lap = [&](int k) { const double t = tnow(); t_phase[k] += t - t_mark; t_mark = t; };
-
-  for (;;) {
-    bool final;
-    EPI_TRY(win.next(&final));
-    const Rec *recs = win.recs.begin();
-    const size_t nrec = win.recs.size();
-    lap(0);
-    if (!checked) {
-      if (nrec < 1024 && !final) { win.keep_all(); continue; }   // .checkBam looks at the first 1024 records
-      EPI_TRY(call_choose_tag(recs, nrec, force_tag, &tag));
-      // ---- the output and the header check (src/rcpp_call_methylation.cpp:41-72) ----
-      EPI_TRY(out.open(out_path));
-      EPI_TRY(call_check_genome(g, win.names, win.lens));
-      EPI_TRY(out.write(win.header(), win.header_size(), nthreads));   // the input header, verbatim
-      checked = true;
-    }
-    // ---- which records are called, and how large each one is written out ----
-    EPI_TRY(call_select(recs, nrec, tag, win.names, win.lens, K, "epi_call_methylation", S));
-    W.out_off.resize(nrec + 1);
-    W.out_off[0] = 0;
-    for (size_t i = 0; i < nrec; i++) {
-      const uint64_t bs = rd32(win.record(i));
-      W.out_off[i + 1] = W.out_off[i] + 4 + bs + (S.call[i] ? (tag == TAG_XG ? 0 : 6) + 4 + (uint64_t)recs[i].l_seq : 0);
-    }
-    // ---- the packed inputs of the called records ----
-    EPI_TRY(call_pack_inputs(recs, nrec, K, "epi_call_methylation", S));
-    const int64_t ncall = (int64_t)S.crec.size();
-    lap(1);
-    // ---- the GPU: XM of every called record ----
-    EPI_TRY(call_methylation_window(eng, g, wk, S.crec.data(), ncall, S.cigar.data(), S.ncig, S.seq.data(), S.nseq, S.nxm,
-                                    CALL_XM, S.xm.data()));
-    lap(2);
-    EPI_TRY(call_splice(win, S, tag, K, W));
-    lap(3);
-    EPI_TRY(out.write(W.out.data(), W.out.size(), nthreads));
-    lap(4);
-    nrecs += (int64_t)nrec;
-    ncalled += ncall;
-    win.consume(nrec);
-    if (final) break;
-  }
-  if (!checked) return fail(EPI_ERR_ARG, "Empty file provided! Exiting");
-  EPI_TRY(out.close());
-  lap(4);
-  if (timing)
-    fprintf(stderr, "[call] inflate+index %.3f s  prepare %.3f s  gpu %.3f s  splice %.3f s  deflate+write %.3f s\n",
-            t_phase[0], t_phase[1], t_phase[2], t_phase[3], t_phase[4]);
-  *nrecs_out = nrecs;
-  *ncalled_out = ncalled;
-  return EPI_OK;
-}
-#endif  // EPI_HOST_ONLY
-
 }  // namespace
 
 extern "C" {
 
 void epi_templates_free(epi_templates *t) {
   if (!t) return;
-#ifdef EPI_HOST_ONLY
-  free(t->xm);                                             // (sanitizer build: no HIP runtime, the bytes came from malloc)
-#else
-  if (t->xm) { if (t->pinned) (void)hipHostFree(t->xm); else free(t->xm); }
-#endif
+  if (t->xm) { if (t->pinned) pinned_free(t->xm); else free(t->xm); }
   free(t->off); free(t->rname); free(t->strand); free(t->start);
   if (t->target_names) { for (int32_t i = 0; i < t->n_targets; i++) free(t->target_names[i]); free(t->target_names); }
   memset(t, 0, sizeof(*t));
@@ -1810,97 +971,15 @@ int epi_preprocess_bam_genome(epi_engine *eng, const char *path, const epi_bam_o
   if (!path || !out || !g || !ncalled) return fail(EPI_ERR_ARG, "epi_preprocess_bam_genome: NULL argument");
   memset(out, 0, sizeof(*out));
   *ncalled = 0;
-#ifdef EPI_HOST_ONLY
-  (void)eng; (void)opt_in;
-  return fail(EPI_ERR_NODEVICE, "epi_preprocess_bam_genome: the calls are made on the GPU; this build has no device code");
-#else
-  if (!eng) EPI_TRY(epi_default_engine(&eng));               // no device: fails here, before the file is read
+  EPI_TRY(device_engine(&eng, "epi_preprocess_bam_genome: the calls are made on the GPU"));   // no device: fails here, before the file is read
   return preprocess_entry(path, opt_in, out, eng, g, ncalled, false);
-#endif
 }
 
 int epi_preprocess_bam_anyorder(epi_engine *eng, const char *path, const epi_bam_options *opt_in, epi_templates *out) {
   if (!path || !out) return fail(EPI_ERR_ARG, "epi_preprocess_bam_anyorder: NULL argument");
   memset(out, 0, sizeof(*out));
-#ifdef EPI_HOST_ONLY
-  (void)eng; (void)opt_in;
-  return fail(EPI_ERR_NODEVICE, "epi_preprocess_bam_anyorder: templates are assembled on the GPU; this build has no device code");
-#else
-  if (!eng) EPI_TRY(epi_default_engine(&eng));               // no device: fails here, before the file is read
+  EPI_TRY(device_engine(&eng, "epi_preprocess_bam_anyorder: templates are assembled on the GPU"));   // (as above)
   return preprocess_entry(path, opt_in, out, eng, nullptr, nullptr, true);
-#endif
 }
-
-#ifndef EPI_HOST_ONLY
-int epi_call_methylation_windowed(epi_engine *eng, const char *in_path, const char *out_path, epi_genome *g, const char *tag,
-                                  int nthreads, int32_t window_kib, int64_t *nrecs, int64_t *ncalled) {
-  if (!in_path || !out_path || !g || !nrecs || !ncalled) return fail(EPI_ERR_ARG, "epi_call_methylation: NULL argument");
-  if (tag && strcmp(tag, "XG") != 0 && strcmp(tag, "YD") != 0 && strcmp(tag, "ZS") != 0)
-    return fail(EPI_ERR_ARG, "epi_call_methylation: tag must be XG, YD or ZS");
-  *nrecs = 0; *ncalled = 0;
-  if (!eng) EPI_TRY(epi_default_engine(&eng));               // no device: fails here, before any file is touched
-  int rc;
-  bool wrote = false;
-  try {
-    struct stat st;
-    wrote = !(*out_path && stat(out_path, &st) == 0);        // (a partial output is removed only if this call created it)
-    rc = call_impl(eng, in_path, out_path, g, tag, nthreads, window_kib, nrecs, ncalled);
-  } catch (const std::bad_alloc &) {
-    rc = fail(EPI_ERR_NOMEM, "epi_call_methylation: out of host memory");
-  } catch (...) {
-    rc = fail(EPI_ERR_ARG, "epi_call_methylation: unexpected failure while reading %s", in_path);
-  }
-  if (rc != EPI_OK) {
-    *nrecs = 0; *ncalled = 0;
-    if (wrote && *out_path) (void)unlink(out_path);
-  }
-  return rc;
-}
-
-int epi_call_methylation(epi_engine *eng, const char *in_path, const char *out_path, epi_genome *g, int nthreads,
-                         int64_t *nrecs, int64_t *ncalled) {
-  return epi_call_methylation_windowed(eng, in_path, out_path, g, nullptr, nthreads, 0, nrecs, ncalled);
-}
-#endif  // EPI_HOST_ONLY
 
 }  // extern "C"
-
-
-// ---- whole-file inflate for the other host readers (vcf_reader.cpp) ----------------------------------------------
-// BGZF through the same block scan and parallel inflate as the BAM reader; a gzip file that is not BGZF through zlib
-// (any number of members); anything else is returned as it is.
-int epi::read_text_file(const char *path, std::vector<uint8_t> &out, int nthreads) {
-  out.clear();
-  FileView file;
-  if (open_file(path, file) != EPI_OK) return fail(EPI_ERR_ARG, "Unable to open file for reading: %s", path);
-  if (file.n < 2 || file.p[0] != 0x1f || file.p[1] != 0x8b) { out.assign(file.p, file.p + file.n); return EPI_OK; }
-  std::vector<Block> blocks;
-  if (bgzf_scan(file.p, file.n, blocks) == EPI_OK) {
-    size_t u = 0;
-    for (Block &b : blocks) { b.upos = u; u += b.ulen; }
-    out.resize(u);
-    return bgzf_inflate_range(file.p, blocks, 0, blocks.size(), out.data(), nthreads);
-  }
-  z_stream zs;
-  memset(&zs, 0, sizeof(zs));
-  if (inflateInit2(&zs, 15 + 32) != Z_OK) return fail(EPI_ERR_NOMEM, "inflateInit2 failed");
-  zs.next_in = const_cast<Bytef *>(file.p);
-  zs.avail_in = (uInt)file.n;                                // (a gzip file that is not BGZF: small, below 4 GiB)
-  uint8_t buf[1 << 16];
-  int rc = Z_OK;
-  for (;;) {
-    zs.next_out = buf;
-    zs.avail_out = sizeof(buf);
-    rc = inflate(&zs, Z_NO_FLUSH);
-    out.insert(out.end(), buf, buf + (sizeof(buf) - zs.avail_out));
-    if (rc == Z_STREAM_END) {
-      if (zs.avail_in == 0) break;
-      if (inflateReset(&zs) != Z_OK) { rc = Z_DATA_ERROR; break; }   // the next member
-      continue;
-    }
-    if (rc != Z_OK) break;
-  }
-  inflateEnd(&zs);
-  if (rc != Z_STREAM_END) return fail(EPI_ERR_ARG, "corrupt gzip file: %s", path);
-  return EPI_OK;
-}

@@ -14,8 +14,8 @@
 //                    case otherwise.  Two output forms of one kernel: the XM letter (callMethylation, BAM out) or the
 //                    reader's packed template byte (nt16 << 4) | ctx_to_idx(XM) (preprocessBam with a genome), which is
 //                    what bam_pack.cpp's packed_bytes() makes of SEQ and the XM letter.
-// The kernel boundary orders the scratch writes of the first before the reads of the second.  The host (bam_pack.cpp)
-// has checked every record it hands over: the contig exists, the CIGAR consumes exactly l_seq query bases and the
+// The kernel boundary orders the scratch writes of the first before the reads of the second.  The host (call_select in
+// bam_call.cpp) has checked every record it hands over: the contig exists, the CIGAR consumes exactly l_seq query bases and the
 // aligned span lies inside the contig; the kernels still keep every genome read inside its contig.
 #include "common.hpp"
 #include "cigar_walk.hpp"
