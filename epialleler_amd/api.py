@@ -520,6 +520,37 @@ def rcpp_fdrp_report(df, ctx, flank_sites, max_reads, min_overlap, max_distance,
     return _fetch_table(bam, lib.epi_batch_fdrp_fetch_dev, nrow.value, 8, FDRP_COLUMNS, as_device)
 
 
+REGION_COLUMNS = ("rname", "start", "end", "nreads", "nlong", "kreads", "tbase", "mbase", "cbase", "ndiscordant",
+                  "nmethylated", "n_u", "n_x", "n_m", "maxsites", "beta", "pdr", "chalm", "mcr", "mbs", "mhl")
+
+
+def rcpp_region_report(df, regions, ctx, min_sites, max_sites, reverse_offset, u_max, m_min, max_ooctx_meth_frac, as_device=False):
+    """One row per region, in the order given, from the calls that the kept rows have inside it (include/epihip.h,
+    epi_batch_region_report_dev): rname, start, end, nreads, nlong, kreads, tbase, mbase, cbase, ndiscordant, nmethylated,
+    n_u, n_x, n_m, maxsites (int32), beta, pdr, chalm, mcr, mbs, mhl (float64).  regions: (rname codes, start, end), three
+    integer sequences, numpy arrays or device tensors of one length (1-based closed ranges; a code that no row has, NA
+    included, gives a row of zero counts).  ctx: context letters in both cases, as for rcpp_mhl_report."""
+    torch = _torch()
+    lib = _lib.load()
+    bam = _as_bam(df)
+    b = bam.batch()
+    dev = "cuda:%d" % bam.device
+    cols3 = [r.to(device=dev, dtype=torch.int32).contiguous() if isinstance(r, torch.Tensor)
+             else torch.from_numpy(np.ascontiguousarray(np.asarray(r, np.int64).astype(np.int32))).to(dev) for r in regions]
+    if len(cols3) != 3 or any(c.dim() != 1 or c.numel() != cols3[0].numel() for c in cols3):
+        raise ValueError("regions: expected (rname codes, start, end), three sequences of one length")
+    n = int(cols3[0].numel())
+    icols = list(torch.empty((15, n), dtype=torch.int32, device=dev).unbind(0))
+    dcols = list(torch.empty((6, n), dtype=torch.float64, device=dev).unbind(0))
+    _lib.check(lib.epi_batch_region_report_dev(b, *[C.c_void_p(c.data_ptr()) if n else None for c in cols3], n, _lib.enc(ctx), int(min_sites),
+                                               int(max_sites), int(reverse_offset), float(u_max), float(m_min), float(max_ooctx_meth_frac),
+                                               _ptr_array(icols), _ptr_array(dcols), _stream(bam.device)))
+    cols = icols + dcols
+    if not as_device:
+        cols = [c.cpu().numpy() for c in cols]
+    return Report(dict(zip(REGION_COLUMNS, cols)), bam.levels)
+
+
 CX_COMPARE_COLUMNS = ("rname", "strand", "pos", "context", "meth_a", "unmeth_a", "meth_b", "unmeth_b", "beta_a", "beta_b", "delta_beta", "p")
 DMR_COLUMNS = ("rname", "start", "end", "nsites", "direction", "beta_a", "beta_b", "delta_beta", "mean_delta_beta", "p")
 

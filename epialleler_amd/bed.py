@@ -10,9 +10,9 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .api import (CONTEXT_TO_BASES, Report, _CTX_CHOICES, _as_bam, _match_arg, _stream, preprocessBam,
-                  rcpp_extract_patterns, rcpp_extract_patterns_multi, rcpp_get_xm_beta, rcpp_summarise_patterns_multi,
-                  rcpp_threshold_reads, writeReport)
+from .api import (CONTEXT_TO_BASES, Report, _CTX_CHOICES, _as_bam, _deliver, _match_arg, _stream, _whole_number, preprocessBam,
+                  rcpp_extract_patterns, rcpp_extract_patterns_multi, rcpp_get_xm_beta, rcpp_region_report,
+                  rcpp_summarise_patterns_multi, rcpp_threshold_reads, writeReport)
 
 NA_INTEGER = -2 ** 31
 
@@ -280,6 +280,54 @@ def summarisePatterns(bam, bed, bed_rows=None, zero_based_bed=False, match_min_o
     reps = rcpp_summarise_patterns_multi(bam, targets, match_min_overlap, ctx, min_context_freq, clip_patterns, offset, hl,
                                          (cb["ctx_meth"], cb["ctx_unmeth"]))
     return _pattern_reports(bam, bed, rows, keep, reps)
+
+
+def generateRegionReport(bam, bed, report_file=None, zero_based_bed=False, region_context=None, min_sites=4, max_sites=64,
+                         strand_offset=None, uxm_thresholds=(0.25, 0.75), max_outofcontext_beta=0.1, gzip=False, verbose=False,
+                         as_device=False, **preprocess_args):
+    """Read-level methylation statistics per region: one row per region of `bed`, in its order.  A read's calls in a region
+    are its cytosines of `region_context` whose position (less `strand_offset` on the reverse strand: 1 for CG, 2 for CHG,
+    else 0, as in extractPatterns) lies inside; the reads are those generateMhlReport keeps under max_outofcontext_beta.
+    Reads with 1 to `max_sites` (1 to 256) calls are counted, those with at least `min_sites` (1 to max_sites) are the
+    k-reads; a read with more than max_sites calls is counted in nlong only.  Columns: rname, start, end, nreads, nlong,
+    kreads, tbase, mbase, cbase, ndiscordant, nmethylated, n_u, n_x, n_m, maxsites (int32); beta (mean methylation), pdr
+    (share of k-reads with both states), chalm (share of k-reads with a methylated call), mcr (unmethylated calls on reads
+    with a methylated one, over all calls), mbs (methylation block score), mhl (methylated haplotype load, Guo et al.
+    2017) (float64).  n_u / n_x / n_m split the k-reads by their methylated share m / n at uxm_thresholds = (u_max, m_min):
+    m <= u_max n, m >= m_min n, and the rest.  A region nothing falls on has zero counts and NaN ratios; regions may
+    overlap, repeat and come in any order.  bed: a path, a Bed, "chr:start-end", or a Report with rname, start and end
+    columns (generateHaplotypeBlocks, generateDmrReport; on the host or on the device) whose rname codes are used as they
+    are and whose strand is ignored.  include/epihip.h has the definitions.  The reference has no such report."""
+    region_context = _match_arg(region_context, _CTX_CHOICES, "region.context")
+    max_sites = _whole_number(max_sites, "max.sites", 1, 256)
+    min_sites = _whole_number(min_sites, "min.sites", 1, max_sites)
+    if strand_offset is None:
+        strand_offset = {"CG": 1, "CHG": 2, "CHH": 0, "CxG": 0, "CX": 0}[region_context]
+    strand_offset = _whole_number(strand_offset, "strand.offset", 0, 2 ** 31 - 1)
+    try:
+        u_max, m_min = (float(v) for v in uxm_thresholds)
+        ok = 0 <= u_max < m_min <= 1
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError("'uxm.thresholds' should be two numbers (u_max, m_min) with 0 <= u_max < m_min <= 1")
+    from_report = isinstance(bed, Report)
+    if from_report:
+        for k in ("rname", "start", "end"):
+            if k not in bed:
+                raise ValueError("'bed' should be a BED file, a Bed, \"chr:start-end\" or a Report with rname, start and end columns")
+    else:
+        bed = _pattern_bed(bed, zero_based_bed)
+    bam = _as_bam(preprocessBam(bam, **preprocess_args))
+    if from_report:
+        regions = (bed["rname"], bed["start"], bed["end"])
+    else:
+        code = {c: i + 1 for i, c in enumerate(bam.levels or ())}
+        regions = ([code.get(c, NA_INTEGER) for c in bed.chrom], bed.start, bed.end)   # factor(seqnames, levels=levels(rname))
+    c = CONTEXT_TO_BASES[region_context]
+    rep = rcpp_region_report(bam, regions, c["ctx_meth"] + c["ctx_unmeth"], min_sites, max_sites, strand_offset, u_max, m_min,
+                             max_outofcontext_beta, as_device=True)
+    return _deliver(rep, report_file, gzip, as_device)
 
 
 def selectPatterns(summary, order_by="beta", beta_range=(0, 1), nbins=10, npatterns_per_bin=2):

@@ -503,6 +503,7 @@ struct Options {
   int no_libdeflate = 0;     // EPIHIP_NO_LIBDEFLATE zlib's inflate for the BGZF blocks although libdeflate.so.0 can be loaded
   int pat_hash_bits = 0;         // EPIHIP_PAT_HASH_BITS=<k>  epi_batch_summarise_patterns_multi groups by the low k bits of the hash (1-63; else all 64)
   int64_t pat_group_bytes = 0;   // EPIHIP_PAT_GROUP_BYTES=<bytes>  scratch cap of a group of targets in epi_batch_extract_patterns_multi (0: 256 MiB)
+  int64_t rgn_group_bytes = 0;   // EPIHIP_RGN_GROUP_BYTES=<bytes>  counter cap of a group of regions in epi_batch_region_report_dev (0: 256 MiB)
   int64_t upload_piece = 0; // EPIHIP_UPLOAD_PIECE=<bytes>  piece size of the host-to-device copies of epi_batch_upload (0: by the
                              //                      source; at most 64 MiB from pageable memory, the size of the pinned staging buffers)
 };

@@ -61,6 +61,8 @@ static void read_options() {
   if (const char *e = getenv("EPIHIP_PAT_GROUP_BYTES")) o.pat_group_bytes = strtoll(e, nullptr, 10);
   if (o.pat_group_bytes < 0) o.pat_group_bytes = 0;
   geti("EPIHIP_PAT_HASH_BITS", &o.pat_hash_bits);
+  if (const char *e = getenv("EPIHIP_RGN_GROUP_BYTES")) o.rgn_group_bytes = strtoll(e, nullptr, 10);
+  if (o.rgn_group_bytes < 0) o.rgn_group_bytes = 0;
   g_options = o;
 }
 

@@ -593,6 +593,47 @@ int epi_batch_fdrp_report_dev(epi_batch *b, const char *ctx, int flank_sites, in
 int epi_batch_fdrp_fetch_dev(epi_batch *b, int32_t *const d_icols[8], double *const d_dcols[2], void *stream);
 int epi_fdrp_pair_bytes(int64_t ncalls, int64_t *bytes_out);
 
+/* Region report: read-level statistics per region of a list -- the methylated haplotype load of Guo et al. 2017 and the
+ * per-interval metrics of the mHap tool-chain (mean methylation, PDR, CHALM, MCR, MBS) with the U / X / M read fractions.
+ * The reference has no such report.  The other read-level reports are keyed by a cytosine or a window of k cytosines; this
+ * one is keyed by the caller's regions: d_chr / d_start / d_end are nregions device int32 (rname factor codes, 1-based
+ * closed ranges), in any order, overlapping and repeated as the caller likes; a code no row has (INT32_MIN for NA) gives a
+ * row of zero counts.
+ *  ctx       context letters in both cases, as for the lMHL report.  1 <= min_sites <= max_sites <= 256;
+ *            reverse_offset >= 0; 0 <= u_max < m_min <= 1.  Anything out of range, or a NULL pointer: EPI_ERR_ARG with a
+ *            message that names the argument, before any work.
+ *  Kept rows the lMHL read rule with hmin = 0 and max_ooctx_meth_frac over the whole row, as for the heterogeneity report.
+ *  Calls     of a kept row x in region [start, end] on its rname: its bytes whose context code is one of ctx's and whose
+ *            position start[x] + i - (strand[x] == 2 ? reverse_offset : 0) lies in [start, end], in row order; n of them,
+ *            m methylated (codes 2, 5, 6, 7), r_1 .. r_q the lengths of the maximal runs of methylated calls.  The row is
+ *            counted when 1 <= n <= max_sites and a k-read when also n >= min_sites.
+ *  Columns   one row per region, in input order.  Fifteen int32: rname, start, end (as given), nreads (rows with n >= 1),
+ *            nlong (rows with n > max_sites: in nreads and nowhere else), kreads, tbase = sum n, mbase = sum m, cbase =
+ *            sum (n - m) over rows with m >= 1 (the three over counted rows), ndiscordant (k-reads with 0 < m < n),
+ *            nmethylated (k-reads with m >= 1), n_u (k-reads with (double)m <= u_max * (double)n), n_x, n_m (of the rest,
+ *            those with (double)m >= m_min * (double)n; n_x is what remains), maxsites (the largest n of a counted row).
+ *            Six double: beta = mbase / tbase, pdr = ndiscordant / kreads, chalm = nmethylated / kreads, mcr = cbase / tbase,
+ *            mbs = (sum_{n = min_sites}^{maxsites} S2[n] / (n n)) / kreads in ascending n, S2[n] = sum over k-reads with n sites
+ *            of sum_j r_j^2, and mhl = (sum_{l = 1}^{maxsites} l (M[l] / T[l])) / (sum_{l = 1}^{maxsites} l) in ascending l,
+ *            M[l] = sum over counted rows and runs of max(0, r_j - l + 1), T[l] = sum over counted rows of max(0, n - l + 1).
+ *            Every sum is an integer, every ratio one fp64 evaluation per region in the order written (csrc/region_report.hip
+ *            has the definitions in full); a zero denominator gives NaN.  The device counts in 64 bits: a count above
+ *            2^31 - 1 is EPI_ERR_ARG with the region's index, not a wrapped number.
+ * The call is stateless with respect to the batch: it writes the caller's columns, keeps nothing, and its scratch goes with
+ * it on every return path (epi_device_allocations reads the same before and after).  It needs no other report and disturbs
+ * none.  The rows must be sorted by (rname, start): otherwise EPI_ERR_UNSORTED, and nothing is written.  nregions == 0:
+ * EPI_OK, nothing is touched; an empty batch: every region gets its row of zeros.  Synchronises `stream` twice (the
+ * candidate rows of the regions; the overflow verdict).  Memory: consecutive regions form a group while their counters and
+ * bookkeeping stay under 256 MiB (test hook EPIHIP_RGN_GROUP_BYTES; a region above the cap runs alone);
+ * epi_region_counter_bytes gives the counters of nregions regions, nregions * (3 max_sites + 16) * 8, or EPI_ERR_ARG outside
+ * 0 <= nregions < 2^31, 1 <= max_sites <= 256.  Single GPU only: the counters are additive over row shards, the sharded form
+ * is not built. */
+int epi_batch_region_report_dev(epi_batch *b, const int32_t *d_chr, const int32_t *d_start, const int32_t *d_end, int32_t nregions,
+                                const char *ctx, int32_t min_sites, int32_t max_sites, int32_t reverse_offset,
+                                double u_max, double m_min, double max_ooctx_meth_frac,
+                                int32_t *const d_icols[15], double *const d_dcols[6], void *stream);
+int epi_region_counter_bytes(int64_t nregions, int32_t max_sites, int64_t *bytes_out);
+
 /* epi_fisher_exact on the device: d_p[i] = the two-sided Fisher exact p-value of the table (d_a[i] d_b[i] / d_c[i] d_d[i]),
  * by the definition and the arithmetic of epi_fisher_exact (csrc/fisher_math.hpp is compiled into both): P(k) in Loader's
  * saddle-point form, a table as extreme when P(k) <= P(a) (1 + 1e-7), the tails found by bisection and summed outwards by
