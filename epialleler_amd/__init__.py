@@ -17,5 +17,6 @@ from .bed import (Bed, Ecdf, extractPatterns, extractPatternsBed, generateAmplic
                   generateBedReport, generateCaptureReport, generateRegionReport, readBed, selectPatterns, summarisePatterns)
 from .genome import Genome, callMethylation, preprocessGenome, rcpp_call_methylation_genome, rcpp_read_genome  # noqa: F401
 from .simulate import rcpp_simulate_bam, simulateBam  # noqa: F401
-from .vcf import Vcf, generateVcfReport, rcpp_fep, rcpp_get_base_freqs, readVcf  # noqa: F401
+from .vcf import (ASM_COLUMNS, ASM_SNV_COLUMNS, Vcf, allele_masks, generateAsmReport, generateAsmSnvReport, generateVcfReport,  # noqa: F401
+                  rcpp_asm_report, rcpp_fep, rcpp_get_base_freqs, readVcf)
 from ._lib import EpihipError  # noqa: F401

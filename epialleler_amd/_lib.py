@@ -180,6 +180,10 @@ _SIGS = {
     "epi_batch_region_report_dev": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _CS, _I32, _I32, _I32, _F64, _F64, _F64, C.POINTER(_VP), C.POINTER(_VP),
                                               _VP]),
     "epi_region_counter_bytes": (C.c_int, [_I64, _I32, C.POINTER(_I64)]),
+    "epi_batch_asm_report_dev": (C.c_int, [_VP, _VP, _VP, _VP, _I64, _CS, _I32, _I32, _F64, C.POINTER(_VP), C.POINTER(_VP), _VP,
+                                           C.POINTER(_I64)]),
+    "epi_batch_asm_fetch_dev": (C.c_int, [_VP, C.POINTER(_VP), C.POINTER(_VP), _VP]),
+    "epi_asm_event_bytes": (C.c_int, [_I64, C.POINTER(_I64)]),
     "epi_fisher_exact_dev": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _I64, _VP, _VP]),
     "epi_cx_compare_dev": (C.c_int, [_VP, C.POINTER(_VP), _I64, C.POINTER(_VP), _I64, _I32, C.POINTER(_VP), C.POINTER(_VP), _I64, _VP,
                                      C.POINTER(_I64), C.POINTER(_I64)]),

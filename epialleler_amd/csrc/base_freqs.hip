@@ -14,6 +14,7 @@
 // Rows with a strand other than 1 / 2 (the placeholder template of an empty paired-end file has 0) are skipped.
 #include <string.h>
 #include "common.hpp"
+#include "site_search.hpp"
 
 namespace epi {
 
@@ -21,40 +22,7 @@ constexpr int BF_ROWS = 256;          // rows (= threads) per workgroup
 constexpr int BF_CAP = 256;           // window sites counted in LDS: 20 u32 each
 constexpr int BF_COLS = 20;
 
-// (rname, pos) as one monotone 64-bit key
-__device__ __forceinline__ int64_t site_key(int32_t c, int32_t p) { return (int64_t)c * 4294967296LL + ((int64_t)p + 2147483648LL); }
-
-// first i in [0, n) with key(chr[i], pos[i]) >= q, by the whole wavefront (uniform result): every step the 64 lanes probe
-// 64 evenly spaced sites and the count of those below q narrows the range to one stride
-__device__ int64_t wave_lower_bound(const int32_t *__restrict__ chr, const int32_t *__restrict__ pos, int64_t n, int64_t q) {
-  const int lane = threadIdx.x & 63;
-  int64_t a = 0, b = n;
-  while (b > a) {
-    const int64_t s = (b - a + 63) / 64;
-    const int64_t p = a + (int64_t)lane * s;
-    const bool less = p < b && site_key(chr[p], pos[p]) < q;
-    const int c = __popcll(__ballot(less));
-    if (c == 0) break;                               // site a is already >= q
-    const int64_t next = a + (int64_t)c * s;
-    a = a + (int64_t)(c - 1) * s + 1;
-    b = next < b ? next : b;
-  }
-  return a;
-}
-
-// sequential lower bound over a sorted key array
-__device__ __forceinline__ int32_t lds_lower_bound(const int64_t *k, int32_t n, int64_t q) {
-  int32_t a = 0, b = n;
-  while (a < b) { const int32_t m = (a + b) >> 1; if (k[m] < q) a = m + 1; else b = m; }
-  return a;
-}
-__device__ __forceinline__ int64_t glb_lower_bound(const int32_t *chr, const int32_t *pos, int64_t a, int64_t b, int64_t q) {
-  while (a < b) { const int64_t m = (a + b) >> 1; if (site_key(chr[m], pos[m]) < q) a = m + 1; else b = m; }
-  return a;
-}
-
-// seq_nt16_int: A C G T (nt16 1 2 4 8) -> 0 1 2 3, every other code -> 4 (N), one nibble per code
-constexpr uint64_t kNt16Int = 0x4444444344424104ULL;
+// site_key, wave_lower_bound, lds_lower_bound, glb_lower_bound and kNt16Int: site_search.hpp (shared with asm_report.hip)
 
 __global__ __launch_bounds__(BF_ROWS) void k_base_freqs(const uint8_t *__restrict__ xm, const int64_t *__restrict__ off,
                                                         const int32_t *__restrict__ len, const int32_t *__restrict__ rname,

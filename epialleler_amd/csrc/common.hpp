@@ -283,6 +283,16 @@ struct ShardState {
   int64_t *d_mhl_sum_slab = nullptr;
 };
 
+// The pair table of the last allele-specific methylation report (asm_report.hip): one piece per group of sites, in site
+// order.  Nothing else on the batch reads or writes it; it goes with the batch.
+struct AsmState {
+  std::vector<DevBuf> piece;                    // [10][rows] int32: the pair rows' integer columns
+  std::vector<int64_t> rows;                    // rows of every piece
+  int64_t npair = 0;
+  bool reported = false;                        // a report has run: a fetch has a table (possibly empty) to write
+  void clear() { piece.clear(); rows.clear(); npair = 0; reported = false; }
+};
+
 struct PatternStats {
   int64_t extract_groups = 0, extract_pairs = 0, extract_scratch = 0;        // last epi_batch_extract_patterns_multi: groups, pairs, peak scratch bytes
   int64_t summarise_groups = 0, summarise_pairs = 0, summarise_fallback = 0; // last epi_batch_summarise_patterns_multi: groups, pairs, targets grouped on the host
@@ -316,6 +326,7 @@ struct epi_batch {
   epi::MhlState mhl;
   epi::ShardState shard;
   epi::PatternStats pat;
+  epi::AsmState asmr;
   // the heterogeneity report, the linkage report with its blocks and the heterogeneity comparison (het_common.hpp): the
   // site table they count over and what the last of them left for its fetch; one of them is live on a batch at a time
   epi::SiteReportState sites;
@@ -504,6 +515,7 @@ struct Options {
   int pat_hash_bits = 0;         // EPIHIP_PAT_HASH_BITS=<k>  epi_batch_summarise_patterns_multi groups by the low k bits of the hash (1-63; else all 64)
   int64_t pat_group_bytes = 0;   // EPIHIP_PAT_GROUP_BYTES=<bytes>  scratch cap of a group of targets in epi_batch_extract_patterns_multi (0: 256 MiB)
   int64_t rgn_group_bytes = 0;   // EPIHIP_RGN_GROUP_BYTES=<bytes>  counter cap of a group of regions in epi_batch_region_report_dev (0: 256 MiB)
+  int64_t asm_group_bytes = 0;   // EPIHIP_ASM_GROUP_BYTES=<bytes>  event cap of a group of sites in epi_batch_asm_report_dev (0: 256 MiB)
   int64_t upload_piece = 0; // EPIHIP_UPLOAD_PIECE=<bytes>  piece size of the host-to-device copies of epi_batch_upload (0: by the
                              //                      source; at most 64 MiB from pageable memory, the size of the pinned staging buffers)
 };

@@ -63,6 +63,8 @@ static void read_options() {
   geti("EPIHIP_PAT_HASH_BITS", &o.pat_hash_bits);
   if (const char *e = getenv("EPIHIP_RGN_GROUP_BYTES")) o.rgn_group_bytes = strtoll(e, nullptr, 10);
   if (o.rgn_group_bytes < 0) o.rgn_group_bytes = 0;
+  if (const char *e = getenv("EPIHIP_ASM_GROUP_BYTES")) o.asm_group_bytes = strtoll(e, nullptr, 10);
+  if (o.asm_group_bytes < 0) o.asm_group_bytes = 0;
   g_options = o;
 }
 

@@ -1,4 +1,5 @@
-"""generateVcfReport: base frequencies and Fisher exact tests at the SNVs of a VCF file.
+"""generateVcfReport: base frequencies and Fisher exact tests at the SNVs of a VCF file; generateAsmReport and
+generateAsmSnvReport: allele-specific methylation at those SNVs (no reference counterpart; at the end of this file).
 Mirrors R/generateVcfReport.R, .readVcf (R/internal.R:230-267) and .getBaseFreqReport (R/internal.R:611-676), with the
 Rcpp exports rcpp_get_base_freqs (src/rcpp_get_base_freqs.cpp) and rcpp_fep (src/rcpp_fep.cpp).  The VCF is parsed by
 the library (epi_read_vcf), the per-site tallies run on the GPU (epi_batch_base_freqs_dev) and the Fisher tests on the
@@ -13,8 +14,8 @@ import os
 import numpy as np
 
 from . import _lib
-from .api import CONTEXT_TO_BASES, Report, _CTX_CHOICES, _as_bam, _pass_tensor, _stream, preprocessBam, \
-    rcpp_threshold_reads, writeReport
+from .api import CONTEXT_TO_BASES, Report, _CTX_CHOICES, _as_bam, _deliver, _fetch_table, _match_arg, _pass_tensor, _ptr_array, \
+    _stream, _table_to_host, _whole_number, preprocessBam, rcpp_threshold_reads, writeReport
 from .bed import Bed, readBed
 
 NA_INTEGER = -2 ** 31
@@ -259,3 +260,141 @@ def generateVcfReport(bam, vcf, vcf_style=None, bed=None, report_file=None, zero
         return rep
     writeReport(rep, report_file, gzip)
     return None
+
+
+# ---- allele-specific methylation -----------------------------------------------------------------
+
+_ASM_PAIR_DEVICE = ("snv", "rname", "snv_pos", "strand", "pos", "context", "meth_ref", "unmeth_ref", "meth_alt", "unmeth_alt",
+                    "beta_ref", "beta_alt", "delta_beta", "p")
+_ASM_SNV_DEVICE = ("rname", "pos", "reads_ref", "reads_alt", "reads_other", "npairs", "meth_ref", "unmeth_ref", "meth_alt",
+                   "unmeth_alt", "beta_ref", "beta_alt", "delta_beta", "p")
+ASM_COLUMNS = ("name", "REF", "ALT") + _ASM_PAIR_DEVICE
+ASM_SNV_COLUMNS = ("name", "REF", "ALT") + _ASM_SNV_DEVICE
+_BASE_BIT = {"A": 1, "C": 2, "G": 4, "T": 8}                 # 1 << seq_nt16_int
+
+
+def allele_masks(ref, alt):
+    """The site_alleles of epi_batch_asm_report_dev (include/epihip.h) from _ALLELE_TABLE: per (REF, ALT) four 4-bit masks
+    over A, C, G, T -- bits 0-3 the bases read as REF on '+' rows, 4-7 as ALT on '+', 8-11 REF on '-', 12-15 ALT on '-'
+    (zero where the strand cannot tell the alleles apart after bisulfite conversion).  A pair that is not in the table
+    gets 0 everywhere.  Returns int32."""
+    ref = np.asarray(ref).astype("U1").reshape(-1)
+    alt = np.asarray(alt).astype("U1").reshape(-1)
+    if ref.shape != alt.shape:
+        raise ValueError("REF and ALT must have the same length")
+    out = np.zeros(ref.size, np.int32)
+    for (r, a), bases in _ALLELE_TABLE.items():
+        mask = 0
+        for shift, bs in ((0, bases[0]), (8, bases[2]), (4, bases[4]), (12, bases[6])):     # M+Ref, M-Ref, M+Alt, M-Alt
+            mask |= sum(_BASE_BIT[x] for x in (bs or "")) << shift
+        out[(ref == r) & (alt == a)] = mask
+    return out
+
+
+def rcpp_asm_report(df, site_chr, site_pos, site_alleles, ctx, max_distance, min_coverage, max_ooctx_meth_frac, as_device=False):
+    """Allele-specific methylation per (SNV, cytosine) and per SNV (include/epihip.h, epi_batch_asm_report_dev) ->
+    (pairs, snvs), two Reports.  pairs: snv, rname, snv_pos, strand, pos, context, meth_ref, unmeth_ref, meth_alt,
+    unmeth_alt (int32), beta_ref, beta_alt, delta_beta, p (float64), in (rname, snv_pos, snv, pos, strand, context) order.  snvs:
+    one row per site, in the order given: rname, pos, reads_ref, reads_alt, reads_other, npairs and the four cells summed over
+    the site's pair rows (int32), the pooled beta_ref, beta_alt, delta_beta, p (float64).  site_chr: rname factor codes
+    (NA_INTEGER: a row of zero counts and NaN), site_alleles: allele_masks(); the sites in any order -- NA is dropped and the
+    rest are sorted for the device, `snv` indexes the order given.  ctx: context letters in both cases, as for
+    rcpp_mhl_report."""
+    import torch
+    lib = _lib.load()
+    bam = _as_bam(df)
+    b = bam.batch()
+    dev = "cuda:%d" % bam.device
+    chr_ = np.ascontiguousarray(np.asarray(site_chr, np.int64).astype(np.int32)).reshape(-1)
+    pos = np.ascontiguousarray(np.asarray(site_pos, np.int64).astype(np.int32)).reshape(-1)
+    masks = np.ascontiguousarray(np.asarray(site_alleles, np.int64).astype(np.int32)).reshape(-1)
+    if not chr_.shape == pos.shape == masks.shape:
+        raise ValueError("site seqnames, positions and alleles must have the same length")
+    nsite = int(chr_.size)
+    idx = np.flatnonzero(chr_ != NA_INTEGER)
+    idx = idx[np.lexsort((pos[idx], chr_[idx]))]                 # (code, pos), stable
+    m = int(idx.size)
+    d_sites = [torch.from_numpy(a[idx]).to(dev) for a in (chr_, pos, masks)]
+    icols = list(torch.empty((10, m), dtype=torch.int32, device=dev).unbind(0))
+    dcols = list(torch.empty((4, m), dtype=torch.float64, device=dev).unbind(0))
+    npair = C.c_int64(0)
+    _lib.check(lib.epi_batch_asm_report_dev(b, *[C.c_void_p(t.data_ptr()) if m else None for t in d_sites], m, _lib.enc(ctx),
+                                            int(max_distance), int(min_coverage), float(max_ooctx_meth_frac),
+                                            _ptr_array(icols), _ptr_array(dcols), _stream(bam.device), C.byref(npair)))
+    pairs = _fetch_table(bam, lib.epi_batch_asm_fetch_dev, npair.value, 10, _ASM_PAIR_DEVICE, True)
+    d_idx = torch.from_numpy(idx).to(dev)
+    pairs["snv"] = d_idx[pairs["snv"].long()].to(torch.int32)    # the caller's order
+    # the SNV rows in the caller's order: an NA site keeps its code and position, counts nothing and has no ratio
+    full_i = torch.zeros((10, nsite), dtype=torch.int32, device=dev)
+    full_i[0] = torch.from_numpy(chr_).to(dev)
+    full_i[1] = torch.from_numpy(pos).to(dev)
+    full_d = torch.full((4, nsite), float("nan"), dtype=torch.float64, device=dev)
+    if m:
+        full_i[:, d_idx] = torch.stack(icols)
+        full_d[:, d_idx] = torch.stack(dcols)
+    snvs = Report(dict(zip(_ASM_SNV_DEVICE, list(full_i.unbind(0)) + list(full_d.unbind(0)))), bam.levels)
+    return _table_to_host(pairs, as_device), _table_to_host(snvs, as_device)
+
+
+def _asm_tables(bam, vcf, vcf_style, bed, zero_based_bed, asm_context, max_distance, min_coverage, max_outofcontext_beta,
+                as_device, preprocess_args):
+    """What generateAsmReport and generateAsmSnvReport share: the arguments, the VCF as generateVcfReport reads and styles
+    it, and both tables with name, REF and ALT of the Vcf in front (host tables only)."""
+    asm_context = _match_arg(asm_context, _CTX_CHOICES, "asm.context")
+    max_distance = _whole_number(max_distance, "max.distance", 0, 2 ** 31 - 1)
+    min_coverage = _whole_number(min_coverage, "min.coverage", 0, 2 ** 31 - 1)
+    if not isinstance(vcf, Vcf):
+        vcf = readVcf(vcf, vcf_style=vcf_style, bed=bed, zero_based_bed=zero_based_bed)
+    bam = _as_bam(preprocessBam(bam, **preprocess_args))
+    vcf = vcf.subset(np.lexsort((vcf.pos, vcf.chrom)))           # sort(rowRanges), as .getBaseFreqReport
+    levels = list(bam.levels) if bam.levels is not None else []
+    code_of = {s: i + 1 for i, s in enumerate(levels)}
+    lev_code = np.asarray([code_of.get(s, NA_INTEGER) for s in vcf.levels] or [NA_INTEGER], np.int32)
+    seq = lev_code[vcf.chrom] if len(vcf) else np.zeros(0, np.int32)
+    if not (seq != NA_INTEGER).any():
+        raise ValueError("Looks like seqlevels styles of BAM and VCF don't match. "
+                         "Please provide VCF as an object with correct seqlevels.")
+    c = CONTEXT_TO_BASES[asm_context]
+    pairs, snvs = rcpp_asm_report(bam, seq, vcf.pos, allele_masks(vcf.ref, vcf.alt), c["ctx_meth"] + c["ctx_unmeth"],
+                                  max_distance, min_coverage, max_outofcontext_beta, as_device=as_device)
+    if as_device:
+        return pairs, snvs
+    s = pairs["snv"]
+    front = lambda sel: {"name": vcf.names[sel], "REF": vcf.ref.astype(object)[sel], "ALT": vcf.alt.astype(object)[sel]}
+    out = []
+    for rep, sel in ((pairs, s), (snvs, slice(None))):
+        cols = front(sel)
+        cols.update(rep)
+        out.append(Report(cols, rep.levels["rname"]))
+    return out
+
+
+def generateAsmReport(bam, vcf, vcf_style=None, bed=None, report_file=None, zero_based_bed=False, asm_context=None,
+                      max_distance=0, min_coverage=1, max_outofcontext_beta=0.1, gzip=False, verbose=False, as_device=False,
+                      **preprocess_args):
+    """Allele-specific methylation per (SNV, cytosine): for every SNV of `vcf` and every cytosine of `asm_context` on the reads
+    that cover the SNV, the methylated / unmethylated calls of the reads that carry the reference allele against those of the
+    reads that carry the alternative one (meth_ref, unmeth_ref, meth_alt, unmeth_alt), their betas, delta_beta = beta_alt -
+    beta_ref and the two-sided Fisher exact p (what CGmapTools asm, MethPipe allelicmeth and DAMEfinder's SNP mode report).
+    A read's allele is its base at the SNV, read bisulfite-aware (R/internal.R:642-666: C>T is told apart on '-' reads only,
+    G>A on '+' reads only); reads without an allele there, and reads that generateMhlReport drops under
+    max_outofcontext_beta, count nowhere.  Cytosines more than max_distance bases from the SNV (0: no limit) and those with
+    fewer than max(min_coverage, 1) calls on either allele are left out.  vcf, vcf_style, bed, zero_based_bed: as for
+    generateVcfReport.  Columns: ASM_COLUMNS -- name, REF, ALT of the SNV, snv (its row in the sorted VCF), rname, snv_pos,
+    strand, pos, context, the four cells, beta_ref, beta_alt, delta_beta, p; with as_device the numeric columns alone, as
+    device tensors.  Composes with adjustReport(rep, column="p").  The reference has no such report."""
+    pairs, _ = _asm_tables(bam, vcf, vcf_style, bed, zero_based_bed, asm_context, max_distance, min_coverage, max_outofcontext_beta,
+                           as_device, preprocess_args)
+    return _deliver(pairs, report_file, gzip)
+
+
+def generateAsmSnvReport(bam, vcf, vcf_style=None, bed=None, report_file=None, zero_based_bed=False, asm_context=None,
+                         max_distance=0, min_coverage=1, max_outofcontext_beta=0.1, gzip=False, verbose=False, as_device=False,
+                         **preprocess_args):
+    """generateAsmReport pooled per SNV: one row per SNV of the sorted VCF with the reads that carry either allele or
+    neither (reads_ref, reads_alt, reads_other), the number of its cytosines in generateAsmReport's table (npairs), the four
+    cells summed over them, the pooled betas, delta_beta and the Fisher exact p of the pooled table (NaN ratios where a
+    denominator is zero).  Same arguments.  Columns: ASM_SNV_COLUMNS; with as_device the numeric columns alone."""
+    _, snvs = _asm_tables(bam, vcf, vcf_style, bed, zero_based_bed, asm_context, max_distance, min_coverage, max_outofcontext_beta,
+                          as_device, preprocess_args)
+    return _deliver(snvs, report_file, gzip)

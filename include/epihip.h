@@ -634,6 +634,58 @@ int epi_batch_region_report_dev(epi_batch *b, const int32_t *d_chr, const int32_
                                 int32_t *const d_icols[15], double *const d_dcols[6], void *stream);
 int epi_region_counter_bytes(int64_t nregions, int32_t max_sites, int64_t *bytes_out);
 
+/* Allele-specific methylation report: does methylation differ between the two alleles of a heterozygous SNV?  Per (SNV,
+ * cytosine) the calls of the reads that carry the reference allele against those of the reads that carry the alternative
+ * one, with a Fisher exact test, and the same pooled per SNV (what CGmapTools asm, MethPipe allelicmeth and DAMEfinder's SNP
+ * mode report).  The reference has no such report.  The packed byte holds the base (nt16 << 4) next to the call, so a row
+ * says both which allele it carries and what it calls.
+ *  Inputs    a resident batch; nsite sites as device int32 d_site_chr (rname factor codes, INT32_MIN = NA), d_site_pos
+ *            (1-based) and d_site_alleles.  The sites are sorted by (code, pos), equal keys allowed (multi-ALT records) and NA
+ *            codes (which sort first) included: the precondition of epi_batch_base_freqs_dev, and its EPI_ERR_UNSORTED.
+ *  Alleles   d_site_alleles packs four 4-bit masks over the bases A, C, G, T (bit = seq_nt16_int, 0 .. 3): bits 0-3 REF on
+ *            '+' rows, 4-7 ALT on '+', 8-11 REF on '-', 12-15 ALT on '-' -- bisulfite-aware, so C>T reads as REF = C, ALT = T
+ *            on '-' and as nothing on '+'.  A zero mask: the strand cannot tell the alleles apart.  A bit above 15, or REF
+ *            and ALT of one strand sharing a bit: EPI_ERR_ARG naming the site, before any counting.
+ *  Kept rows the lMHL read rule with hmin = 0 and max_ooctx_meth_frac over the whole row, as for the heterogeneity and
+ *            region reports; the strand must be 1 or 2, the length positive.
+ *  Allele    a kept row x covers site s when rname[x] == site_chr[s] and start[x] <= site_pos[s] <= start[x] + len[x] - 1 (no
+ *            row covers an NA site).  Its base there is seq_nt16_int[byte >> 4]; its allele is 0 when the base's bit is in its
+ *            strand's REF mask, 1 when in the ALT mask, none otherwise (N, the 0xF? filler between mates, a third base, an
+ *            uninformative strand).
+ *  Events    for a covering row with an allele, every byte of the row whose context code is one of ctx's (letters in both
+ *            cases, as for the lMHL report), at position q = start[x] + i with q != site_pos[s] and, when max_distance > 0,
+ *            |q - site_pos[s]| <= max_distance (0: no limit, as in the linkage report): one event (s, strand, q, context code =
+ *            code & 7, allele, methylated = codes 2, 5, 6, 7).
+ *  Pair rows events grouped by (s, q, strand, context code), four cells meth_ref, unmeth_ref, meth_alt, unmeth_alt; reported
+ *            when meth_ref + unmeth_ref >= max(min_coverage, 1) and the same holds for alt, in ascending (s, q, strand,
+ *            context).  Ten int32 columns: snv (index into the site list as given), rname, snv_pos, strand, pos, context and
+ *            the four cells.  Four double: beta_ref, beta_alt (one IEEE division of integers each), delta_beta = beta_alt -
+ *            beta_ref, p = the two-sided Fisher p-value of (meth_ref unmeth_ref / meth_alt unmeth_alt) as
+ *            epi_fisher_exact_dev computes it, one thread per row.
+ *  SNV rows  one per site, in input order.  Ten int32: rname, pos (as given), reads_ref, reads_alt, reads_other (kept covering
+ *            rows by allele / without one), npairs (the site's reported pair rows), meth_ref, unmeth_ref, meth_alt, unmeth_alt
+ *            summed over the site's REPORTED pair rows (the SNV table is a group-by of the pair table).  Four double: beta_ref,
+ *            beta_alt, delta_beta and p from the pooled cells; a zero denominator gives NaN (p of an all-zero table is 1).  An
+ *            NA site: zero counts, four NaN.  The device sums in 64 bits: a sum above 2^31 - 1 is EPI_ERR_ARG with the site's
+ *            index.  (csrc/asm_report.hip has the definitions in full.)
+ * epi_batch_asm_report_dev writes the SNV columns and *npair_out and keeps the pair table on the batch in a state of its own:
+ * it touches neither last_kind nor any other report's state, so a CX, lMHL, heterogeneity, linkage or FDRP report fetched
+ * after it reads what it read before; the table goes with the batch (epi_device_allocations reads the same after
+ * epi_batch_free as before the upload) and the call's scratch on every return path.  epi_batch_asm_fetch_dev writes the pair
+ * table's columns (*npair_out rows each); before any report: EPI_ERR_STATE.  nsite == 0: EPI_OK and an empty pair table; an
+ * empty batch: zero pair rows and SNV rows of zero counts.  Rows not sorted by (rname, start): EPI_ERR_UNSORTED, nothing
+ * written.  max_distance < 0, min_coverage < 0, nsite outside 0 .. 2^31 - 1 or a NULL pointer: EPI_ERR_ARG naming the argument,
+ * before any work.  The report synchronises `stream` (site checks, event counts, once per group of sites, overflow verdict).
+ * Memory: consecutive sites form a group while their events, 24 bytes each with the sort's second buffers, stay under 256 MiB
+ * (test hook EPIHIP_ASM_GROUP_BYTES; a site above the cap runs alone; a single site with more than 2^31 - 1 events is
+ * EPI_ERR_ARG); epi_asm_event_bytes gives the bytes of nevents events, 24 nevents, or EPI_ERR_ARG outside 0 <= nevents < 2^32.
+ * Single GPU only: the cells are additive over row shards, the sharded form is not built. */
+int epi_batch_asm_report_dev(epi_batch *b, const int32_t *d_site_chr, const int32_t *d_site_pos, const int32_t *d_site_alleles,
+                             int64_t nsite, const char *ctx, int32_t max_distance, int32_t min_coverage, double max_ooctx_meth_frac,
+                             int32_t *const d_snv_icols[10], double *const d_snv_dcols[4], void *stream, int64_t *npair_out);
+int epi_batch_asm_fetch_dev(epi_batch *b, int32_t *const d_icols[10], double *const d_dcols[4], void *stream);
+int epi_asm_event_bytes(int64_t nevents, int64_t *bytes_out);
+
 /* epi_fisher_exact on the device: d_p[i] = the two-sided Fisher exact p-value of the table (d_a[i] d_b[i] / d_c[i] d_d[i]),
  * by the definition and the arithmetic of epi_fisher_exact (csrc/fisher_math.hpp is compiled into both): P(k) in Loader's
  * saddle-point form, a table as extreme when P(k) <= P(a) (1 + 1e-7), the tails found by bisection and summed outwards by
