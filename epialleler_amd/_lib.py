@@ -190,6 +190,11 @@ _SIGS = {
     "epi_cx_compare_regions_dev": (C.c_int, [_VP, C.POINTER(_VP), C.POINTER(_VP), _I64, _F64, _F64, _I32, _I32, C.POINTER(_VP),
                                              C.POINTER(_VP), _I64, _VP, C.POINTER(_I64)]),
     "epi_p_adjust_dev": (C.c_int, [_VP, _VP, _I64, _I32, _I64, _VP, _VP, _VP, C.POINTER(_I64)]),
+    "epi_dist_tail": (C.c_int, [_I32, _VP, _VP, _I64, _VP]),
+    "epi_dist_tail_dev": (C.c_int, [_VP, _I32, _VP, _VP, _I64, _VP, _VP]),
+    "epi_cx_groups_dev": (C.c_int, [_VP, C.POINTER(_VP), C.POINTER(_I64), _I32, _I32, _I32, _I32, _I32, _I32, C.POINTER(_VP), C.POINTER(_VP),
+                                    _I64, _VP, C.POINTER(_I64), C.POINTER(_I64)]),
+    "epi_cx_groups_scratch_bytes": (C.c_int, [_I64, C.POINTER(_I64)]),
     "epi_tile_positions": (C.c_int, []),
     "epi_cx_tile_positions": (C.c_int, [_CS]),
     "epi_batch_tile_key_range": (C.c_int, [_VP, _VP, C.POINTER(_I64), C.POINTER(_I64)]),

@@ -677,6 +677,110 @@ def fisherExact(a, b, c, d, as_device=False):
     return p if as_device else p.cpu().numpy()
 
 
+def _tail_values(x, name):
+    """A column of statistics or degrees of freedom as flat float64: a device tensor stays on its device."""
+    torch = _torch()
+    if isinstance(x, torch.Tensor):
+        if x.dtype.is_complex or x.dtype == torch.bool:
+            raise ValueError("'%s' should hold numbers" % name)
+        return x.reshape(-1)
+    try:
+        v = np.asarray(x)
+        if v.dtype.kind not in "fiu":
+            raise TypeError
+        return np.ascontiguousarray(v.reshape(-1), np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("'%s' should hold numbers" % name)
+
+
+def _dist_tail(kind, x, df, names, as_device):
+    """epi_dist_tail_dev over x and df (df of x's length or one value)."""
+    x, df = _tail_values(x, names[0]), _tail_values(df, names[1])
+    n = int(x.shape[0])
+    if int(df.shape[0]) not in (1, n):
+        raise ValueError("'%s' should be one number or have the length of '%s'" % (names[1], names[0]))
+    torch = _torch()
+    lib = _lib.load()
+    on_dev = [v.device for v in (x, df) if isinstance(v, torch.Tensor) and v.is_cuda]
+    index = on_dev[0].index if on_dev else None
+    eng = _engine(index)
+    index = lib.epi_engine_device(eng)
+    dev = "cuda:%d" % index
+    x, df = [(v if isinstance(v, torch.Tensor) else torch.from_numpy(v)).to(device=dev, dtype=torch.float64) for v in (x, df)]
+    if int(df.shape[0]) != n:
+        df = df.expand(n)
+    x, df = x.contiguous(), df.contiguous()
+    p = torch.empty(n, dtype=torch.float64, device=dev)
+    _lib.check(lib.epi_dist_tail_dev(eng, kind, C.c_void_p(x.data_ptr()), C.c_void_p(df.data_ptr()), n, C.c_void_p(p.data_ptr()), _stream(index)))
+    return p if as_device else p.cpu().numpy()
+
+
+def chisqPValues(stat, df, as_device=False):
+    """Upper tail probabilities of the chi-square distribution on the GPU (include/epihip.h, epi_dist_tail_dev with
+    EPI_DIST_CHISQ): P(X >= stat) with df degrees of freedom, R's pchisq(stat, df, lower.tail = FALSE) -- the p-value of a
+    likelihood-ratio statistic such as compareHeterogeneity's g with its df.  stat, df: array-likes or device tensors of
+    numbers; df one value or of stat's length, from above 0 to 1e4.  A negative or NaN stat, or a df outside the range, gives
+    NaN.  Returns float64, a device tensor with as_device."""
+    return _dist_tail(0, stat, df, ("stat", "df"), as_device)
+
+
+def tTestPValues(t, df, as_device=False):
+    """Two-sided tail probabilities of Student's t distribution on the GPU (epi_dist_tail_dev with EPI_DIST_T2):
+    P(|T| >= |t|) with df degrees of freedom, R's 2 * pt(-abs(t), df).  t of either sign; otherwise as chisqPValues."""
+    return _dist_tail(1, t, df, ("t", "df"), as_device)
+
+
+GROUP_COMPARE_COLUMNS = ("rname", "strand", "pos", "context", "meth_a", "unmeth_a", "meth_b", "unmeth_b", "nsamples_a", "nsamples_b",
+                         "beta_a", "beta_b", "delta_beta", "mean_beta_a", "mean_beta_b", "var_a", "var_b", "stat", "df", "phi", "p")
+GROUP_TESTS = ("lrt", "lrt_mn", "welch", "fisher")
+_GROUP_TEST_CODES = {"fisher": 0, "lrt": 1, "lrt_mn": 2, "welch": 3}                      # EPI_CXG_*
+_GROUP_MAX = 32
+
+
+def _group_min_samples(value, size, name):
+    return size if value is None else _whole_number(value, name, 1, size)
+
+
+def rcpp_cx_compare_groups(reps_a, reps_b, min_coverage=1, min_samples_a=None, min_samples_b=None, test="lrt", as_device=False):
+    """Two groups of device cytosine reports (lists of rcpp_cx_report / generateCytosineReport tables with as_device=True)
+    against each other per cytosine (include/epihip.h, epi_cx_groups_dev, has the definitions): a sample counts at a
+    cytosine when it covers it min_coverage times, and the cytosines at which min_samples_a samples of a and min_samples_b
+    of b count (None: every sample of the group) are reported with GROUP_COMPARE_COLUMNS -- the counts pooled over the
+    counting samples, nsamples_a, nsamples_b, the pooled betas and their difference, mean and variance of the samples' betas
+    and stat, df, phi, p of `test`: "fisher" (the pooled table), "lrt" (binomial logistic regression, chi-square), "lrt_mn"
+    (the same with McCullagh-Nelder overdispersion, F test) or "welch" (t-test on the samples' betas).  1 to 32 reports a
+    side, under one sequence dictionary and on one device (else ValueError, before the device is touched).  The Report
+    carries the first report's levels and `nsites`, the cytosines at which any sample counts."""
+    min_coverage = _whole_number(min_coverage, "min.coverage", 0, 2 ** 31 - 1)
+    test = _match_arg(test, GROUP_TESTS, "test")
+    reps_a, reps_b = list(reps_a), list(reps_b)
+    for reps, name in ((reps_a, "reps_a"), (reps_b, "reps_b")):
+        if not 1 <= len(reps) <= _GROUP_MAX:
+            raise ValueError("'%s' should hold 1 to %d reports" % (name, _GROUP_MAX))
+    min_samples_a = _group_min_samples(min_samples_a, len(reps_a), "min.samples.a")
+    min_samples_b = _group_min_samples(min_samples_b, len(reps_b), "min.samples.b")
+    reps = reps_a + reps_b
+    if any(r.levels["rname"] != reps[0].levels["rname"] for r in reps):
+        raise ValueError("the reports have different sequence names (levels): their rname codes cannot be compared")
+    tabs = [_device_columns(r, CX_COLUMNS, "rcpp_cx_compare_groups") for r in reps]
+    dev = tabs[0][0].device
+    if any(t[0].device != dev for t in tabs):
+        raise ValueError("the reports are on different devices")
+    torch = _torch()
+    lib = _lib.load()
+    nrows = [int(t[0].numel()) for t in tabs]
+    cap = sum(nrows) // (min_samples_a + min_samples_b)
+    icols = list(torch.empty((10, cap), dtype=torch.int32, device=dev).unbind(0))
+    dcols = list(torch.empty((11, cap), dtype=torch.float64, device=dev).unbind(0))
+    nsite, nrow = C.c_int64(0), C.c_int64(0)
+    _lib.check(lib.epi_cx_groups_dev(_engine(dev.index), _ptr_array([c for t in tabs for c in t]), (C.c_int64 * len(nrows))(*nrows), len(reps_a),
+                                     len(reps_b), min_coverage, min_samples_a, min_samples_b, _GROUP_TEST_CODES[test], _ptr_array(icols),
+                                     _ptr_array(dcols), cap, _stream(dev.index), C.byref(nsite), C.byref(nrow)))
+    rep = Report(dict(zip(GROUP_COMPARE_COLUMNS, [c[:nrow.value] for c in icols + dcols])), reps[0].levels["rname"])
+    rep.nsites = nsite.value
+    return _table_to_host(rep, as_device)
+
+
 P_ADJUST_METHODS = ("holm", "hochberg", "bonferroni", "BH", "BY", "fdr", "none")          # R's p.adjust.methods without hommel
 _P_ADJUST_CODES = {"none": 0, "bonferroni": 1, "holm": 2, "hochberg": 3, "BH": 4, "fdr": 4, "BY": 5}   # EPI_PADJ_*
 
@@ -946,7 +1050,7 @@ def compareHeterogeneity(bam_a, bam_b, report_file=None, window_context=None, wi
     same position, strand and context): what generateHeterogeneityReport gives for either sample on these windows
     (columns *_a, *_b), delta_beta and delta_entropy (b minus a), the Jensen-Shannon divergence of the two epiallele
     histograms in bits (jsd), their total variation distance (tvd) and the likelihood-ratio statistic g of the 2 x 2^k
-    table with its degrees of freedom df (no p-value is computed).  Windows with fewer than min_reads reads in either
+    table with its degrees of freedom df (chisqPValues(g, df) gives its p-value).  Windows with fewer than min_reads reads in either
     sample, or (max_window_span > 0) spanning more than max_window_span bases, are left out.  Both inputs go through
     preprocessBam with the same preprocess_args and must have the same sequence names.  The Report's `ncommon` is the
     number of common sites.  The reference has no such report."""
@@ -1091,6 +1195,82 @@ def generateAdjustedDmrReport(bam_a, bam_b, report_file=None, threshold_reads=Tr
     rep = rcpp_cx_compare_regions(adjustReport(cmp_, p_adjust), *args, as_device=True, significance="q")
     rep = adjustReport(rep, p_adjust)
     rep.ncommon = cmp_.ncommon
+    return _deliver(rep, report_file, gzip, as_device)
+
+
+def _group_comparison(bams_a, bams_b, threshold_reads, threshold_context, min_context_sites, min_context_beta, max_outofcontext_beta,
+                      report_context, min_coverage, min_samples, test, preprocess_args):
+    """The device table of compareCytosineGroups; every argument is checked before a file is opened."""
+    threshold_context = _match_arg(threshold_context, _CTX_CHOICES, "threshold.context")
+    report_context = threshold_context if report_context is None else _match_arg(report_context, _CTX_CHOICES, "report.context")
+    min_coverage = _whole_number(min_coverage, "min.coverage", 0, 2 ** 31 - 1)
+    test = _match_arg(test, GROUP_TESTS, "test")
+    if isinstance(bams_a, (str, bytes, ProcessedBam, dict)) or isinstance(bams_b, (str, bytes, ProcessedBam, dict)):
+        raise ValueError("'bams.a' and 'bams.b' should be lists of 1 to %d inputs" % _GROUP_MAX)
+    bams_a, bams_b = list(bams_a), list(bams_b)
+    for bams, name in ((bams_a, "bams.a"), (bams_b, "bams.b")):
+        if not 1 <= len(bams) <= _GROUP_MAX:
+            raise ValueError("'%s' should be a list of 1 to %d inputs" % (name, _GROUP_MAX))
+    if min_samples is None or isinstance(min_samples, (int, float, np.integer, np.floating)):
+        min_samples = (min_samples, min_samples)
+    if len(min_samples) != 2:
+        raise ValueError("'min.samples' should be an integer or a pair of integers")
+    min_a = _group_min_samples(min_samples[0], len(bams_a), "min.samples")
+    min_b = _group_min_samples(min_samples[1], len(bams_b), "min.samples")
+    given = [b for b in bams_a + bams_b if isinstance(b, ProcessedBam)]
+    if any(b.levels != given[0].levels for b in given):
+        raise ValueError("the inputs have different sequence names (levels): their rname codes cannot be compared")
+    reps = []
+    for bam in bams_a + bams_b:                       # one batch at a time: only the samples' device tables stay
+        pb = preprocessBam(bam, **preprocess_args)
+        if reps and pb.levels != reps[0].levels["rname"]:
+            raise ValueError("the inputs have different sequence names (levels): their rname codes cannot be compared")
+        reps.append(generateCytosineReport(pb, None, threshold_reads, threshold_context, min_context_sites, min_context_beta,
+                                           max_outofcontext_beta, report_context, as_device=True))
+        if pb is not bam:
+            pb.close()
+    return rcpp_cx_compare_groups(reps[:len(bams_a)], reps[len(bams_a):], min_coverage, min_a, min_b, test, as_device=True)
+
+
+def compareCytosineGroups(bams_a, bams_b, report_file=None, threshold_reads=True, threshold_context=None, min_context_sites=2,
+                          min_context_beta=0.5, max_outofcontext_beta=0.1, report_context=None, min_coverage=1, min_samples=None,
+                          test="lrt", gzip=False, verbose=False, as_device=False, **preprocess_args):
+    """Two groups of samples (replicates) against each other per cytosine: the tables generateCytosineReport gives for every
+    input with these arguments, joined on the device.  A sample counts at a cytosine (same position, strand and context)
+    when it covers it at least min_coverage times; cytosines at which at least min_samples samples of either group count (an
+    integer or a pair for a and b; None: every sample) are reported.  Columns: GROUP_COMPARE_COLUMNS -- rname, strand, pos,
+    context, the counts pooled over the counting samples (meth_a, unmeth_a, meth_b, unmeth_b), nsamples_a, nsamples_b,
+    beta_a, beta_b and delta_beta (b minus a) of the pooled counts, mean_beta_* and var_* of the samples' betas, and stat,
+    df, phi, p of `test`: "lrt", the likelihood-ratio test of the two-group binomial logistic regression (chi-square, 1 df);
+    "lrt_mn", the same deviance divided by the McCullagh-Nelder overdispersion phi, F test with nsamples - 2 df (the idea
+    of methylKit's overdispersion = "MN", test = "F"; parity with it is not claimed); "welch", Welch's t-test on the
+    samples' betas; "fisher", the Fisher exact test of the pooled table, which takes replicate spread for signal (with one
+    sample a side it is compareCytosineReports).  No p-value is adjusted for the number of tests (adjustReport does that).
+    Inputs: 1 to 32 a side, paths or preprocessBam results under one sequence dictionary; an input given as a path is read,
+    reported and its batch dropped before the next is read.  The Report's `nsites` is the number of cytosines at which any
+    sample counts.  The reference has no such report."""
+    rep = _group_comparison(bams_a, bams_b, threshold_reads, threshold_context, min_context_sites, min_context_beta,
+                            max_outofcontext_beta, report_context, min_coverage, min_samples, test, preprocess_args)
+    return _deliver(rep, report_file, gzip, as_device)
+
+
+def generateGroupDmrReport(bams_a, bams_b, report_file=None, threshold_reads=True, threshold_context=None, min_context_sites=2,
+                           min_context_beta=0.5, max_outofcontext_beta=0.1, report_context=None, min_coverage=1, min_samples=None,
+                           test="lrt", gzip=False, verbose=False, as_device=False, max_q=0.05, min_delta_beta=0.1, max_gap=500,
+                           min_sites=3, p_adjust="BH", **preprocess_args):
+    """Differentially methylated regions between two groups of samples, by generateAdjustedDmrReport's sequence: the
+    table of compareCytosineGroups with the same arguments, its p adjusted over its rows by `p_adjust` into q, the regions
+    of generateDmrReport formed on q <= max_q and |delta_beta| >= min_delta_beta of the pooled betas, and the regions' p
+    adjusted over the reported regions into q.  The regions' own p stays the Fisher exact test of the region's pooled
+    counts, whatever `test` is: a replicate-aware regional test is not built.  Columns: generateAdjustedDmrReport's.  The
+    Report's `nsites` is compareCytosineGroups'."""
+    args = _region_args(max_q, min_delta_beta, max_gap, min_sites, "max.q")
+    _p_adjust_args(p_adjust, None, "p.adjust")
+    cmp_ = _group_comparison(bams_a, bams_b, threshold_reads, threshold_context, min_context_sites, min_context_beta,
+                             max_outofcontext_beta, report_context, min_coverage, min_samples, test, preprocess_args)
+    rep = rcpp_cx_compare_regions(adjustReport(cmp_, p_adjust), *args, as_device=True, significance="q")
+    rep = adjustReport(rep, p_adjust)
+    rep.nsites = cmp_.nsites
     return _deliver(rep, report_file, gzip, as_device)
 
 

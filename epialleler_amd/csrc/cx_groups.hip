@@ -1,0 +1,378 @@
+// Two groups of cytosine reports against each other per site, with replicates, and the distribution tails the tests need
+// (include/epihip.h, epi_cx_groups_dev and epi_dist_tail_dev, has the definitions).  No reference interface is replaced.
+// Stateless like cx_compare.hip: the call reads the caller's columns, takes its scratch for the length of the call and
+// touches no batch.  All on the call's stream:
+//  Tails    k_dist_tail: a thread per value runs dist_math.hpp's tail_of -- the host's arithmetic in the host's order.
+//  Keys     k_cxg_key, one launch per sample: a thread per row checks the row against its predecessor ((rname, pos, strand)
+//           strictly ascending, as k_cxc_sorted does) and its fields against the key's ranges, and writes the row's 64-bit
+//           key, its index in the concatenation of the tables (a's first) as the sort's value, and its two counts.
+//  Sort     radix_sort_pairs (p_adjust.hip) over the key's seven bytes.  The sort is stable, so a run of equal keys -- a site
+//           -- lists its samples in sample order; a table has a key once, so a run has at most 64 entries.
+//  Sites    k_cxg_flag: the thread of a run's first entry walks the run, counts the samples that count in either group and
+//           flags the site as reported; pooled coverage beyond int32 at a reported site raises the overflow flag.  util.hip's
+//           scan over the flags; ONE read of {unsorted, bad row / overflow, sites, rows}.
+//  Rows     only when order, ranges, coverage and capacity hold: k_cxg_emit, the thread of a reported run's first entry walks
+//           the run twice (sums and mean; then squared deviations and X2, which need the mean and the pooled beta) and writes
+//           the site's 21 columns.  The samples' betas are recomputed in the second walk instead of being kept: no array, no
+//           scratch memory.  The test is a kernel argument, one branch per site.
+// The sort always runs its seven passes: which of the key's upper bytes are empty is known on the device only, and a second
+// read-back to learn it would cost the synchronisation the one read above avoids.
+#include <string.h>
+#include "common.hpp"
+#include "fisher_math.hpp"
+#include "dist_math.hpp"
+
+namespace epi {
+
+constexpr int CXG_WG = 256;
+constexpr int CXG_MAX_GROUP = 32;                             // samples a side
+constexpr int CXG_MAX_RUN = 2 * CXG_MAX_GROUP;                // entries of a site: one per sample
+constexpr uint32_t CXG_KEY_BYTES = 0x7Fu;                     // the key's 56 bits
+constexpr uint32_t CXG_BAD_ROW = 1u, CXG_BAD_POOLED = 2u;     // bits of CxgScalars::bad
+
+struct CxgScalars {                                           // what the kernels and the host exchange (64 bytes allocated)
+  uint32_t unsorted;       // 1 + the last table found out of order (0: none)
+  uint32_t bad;            // CXG_BAD_ROW: a field outside the key's ranges or a negative count; CXG_BAD_POOLED: pooled coverage
+  uint32_t nsite;          // sites at which a sample counts
+  uint32_t nrow;           // reported sites
+};
+
+// ---- tails -------------------------------------------------------------------------------------------------------------
+
+__global__ __launch_bounds__(CXG_WG) void k_dist_tail(int32_t kind, const double *__restrict__ x, const double *__restrict__ df, int64_t n,
+                                                      double *__restrict__ p) {
+  const int64_t i = (int64_t)blockIdx.x * CXG_WG + threadIdx.x;
+  if (i >= n) return;
+  p[i] = dist::tail_of(kind, x[i], df[i]);
+}
+
+// ---- keys --------------------------------------------------------------------------------------------------------------
+
+struct CxgTab {                        // one sample's CX table and where its rows go in the concatenation
+  const int32_t *rname, *strand, *pos, *context, *meth, *unmeth;
+  uint32_t n, base, index;
+};
+
+struct CxgRows {                       // [total] each
+  uint64_t *key;
+  uint32_t *val;
+  int32_t *meth, *unmeth;
+};
+
+__global__ __launch_bounds__(CXG_WG) void k_cxg_key(CxgTab t, CxgRows o, CxgScalars *__restrict__ sc) {
+  const uint32_t i = blockIdx.x * (uint32_t)CXG_WG + threadIdx.x;
+  if (i >= t.n) return;
+  const int32_t rname = t.rname[i], pos = t.pos[i], strand = t.strand[i], ctx = t.context[i], m = t.meth[i], u = t.unmeth[i];
+  if (i > 0) {
+    const int32_t r0 = t.rname[i - 1], p0 = t.pos[i - 1], s0 = t.strand[i - 1];
+    const bool above = r0 != rname ? r0 < rname : p0 != pos ? p0 < pos : s0 < strand;
+    if (!above) atomicMax(&sc->unsorted, t.index + 1u);
+  }
+  if (rname < 0 || rname > EPI_CXG_MAX_RNAME || pos < 0 || strand < 1 || strand > 2 || ctx < 0 || ctx > 7 || m < 0 || u < 0)
+    atomicOr(&sc->bad, CXG_BAD_ROW);
+  const uint32_t g = t.base + i;
+  o.key[g] = ((uint64_t)(uint32_t)rname & (uint64_t)EPI_CXG_MAX_RNAME) << 35 | ((uint64_t)(uint32_t)pos & 0x7FFFFFFFull) << 4 |
+             (uint64_t)((uint32_t)(strand - 1) & 1u) << 3 | (uint64_t)((uint32_t)ctx & 7u);
+  o.val[g] = g;
+  o.meth[g] = m;
+  o.unmeth[g] = u;
+}
+
+// ---- sites -------------------------------------------------------------------------------------------------------------
+
+struct CxgSorted {                     // the sorted pairs, the rows' counts (by concatenation index) and the call's arguments
+  const uint64_t *key;
+  const uint32_t *val;
+  const int32_t *meth, *unmeth;
+  uint32_t n;                          // rows of all samples
+  uint32_t first_b;                    // concatenation index of b's first row: a value below it is a row of a
+  int32_t min_cov, min_a, min_b, test;
+};
+
+// entries of the run that starts at sorted entry j (at most CXG_MAX_RUN: more means a table had a key twice, which the
+// order check has flagged)
+__device__ __forceinline__ uint32_t cxg_run(const CxgSorted &t, uint32_t j) {
+  const uint64_t k = t.key[j];
+  uint32_t len = 1;
+  while (len < (uint32_t)CXG_MAX_RUN && j + len < t.n && t.key[j + len] == k) len++;
+  return len;
+}
+
+__global__ __launch_bounds__(CXG_WG) void k_cxg_flag(CxgSorted t, uint32_t *__restrict__ flag, CxgScalars *__restrict__ sc) {
+  const uint32_t j = blockIdx.x * (uint32_t)CXG_WG + threadIdx.x;
+  uint32_t site = 0;
+  if (j < t.n) {
+    uint32_t rep = 0;
+    if (j == 0 || t.key[j - 1] != t.key[j]) {
+      const uint32_t len = cxg_run(t, j);
+      int32_t na = 0, nb = 0;
+      int64_t cov_a = 0, cov_b = 0;
+      for (uint32_t e = 0; e < len; e++) {
+        const uint32_t v = t.val[j + e];
+        if (v >= t.n) continue;
+        const int64_t cov = (int64_t)t.meth[v] + (int64_t)t.unmeth[v];
+        if (cov < (int64_t)t.min_cov) continue;
+        if (v < t.first_b) { na++; cov_a += cov; } else { nb++; cov_b += cov; }
+      }
+      site = na + nb > 0 ? 1u : 0u;
+      rep = na >= t.min_a && nb >= t.min_b ? 1u : 0u;
+      if (rep && (cov_a > 0x7FFFFFFFLL || cov_b > 0x7FFFFFFFLL)) atomicOr(&sc->bad, CXG_BAD_POOLED);
+    }
+    flag[j] = rep;
+  }
+  const uint32_t wsum = wave_sum_u32(site);                  // (every lane of the wave is here)
+  if ((threadIdx.x & 63) == 0 && wsum) atomicAdd(&sc->nsite, wsum);
+}
+
+// ---- rows --------------------------------------------------------------------------------------------------------------
+
+struct CxgOut {
+  int32_t *icol[10];                   // rname, strand, pos, context, meth_a, unmeth_a, meth_b, unmeth_b, nsamples_a, nsamples_b
+  double *dcol[11];                    // beta_a, beta_b, delta_beta, mean_beta_a, mean_beta_b, var_a, var_b, stat, df, phi, p
+  uint32_t nrow;
+};
+
+__device__ __forceinline__ double cxg_dev_term(double x, double e) { return x == 0.0 ? e : fisher::bd0(x, e); }
+
+__global__ __launch_bounds__(CXG_WG) void k_cxg_emit(CxgSorted t, const uint32_t *__restrict__ flag, const uint32_t *__restrict__ off, CxgOut o) {
+  const uint32_t j = blockIdx.x * (uint32_t)CXG_WG + threadIdx.x;
+  if (j >= t.n || !flag[j]) return;
+  const uint32_t r = off[j];
+  if (r >= o.nrow) return;
+  const double nan = __builtin_nan("");
+  const uint32_t len = cxg_run(t, j);
+  // first walk: pooled counts and the sums of the samples' betas, in sample order
+  int64_t Ma = 0, Ua = 0, Mb = 0, Ub = 0;
+  int32_t cnt_a = 0, cnt_b = 0;
+  double sum_a = 0.0, sum_b = 0.0;
+  for (uint32_t e = 0; e < len; e++) {
+    const uint32_t v = t.val[j + e];
+    if (v >= t.n) continue;
+    const int64_t m = t.meth[v], u = t.unmeth[v];
+    if (m + u < (int64_t)t.min_cov) continue;
+    const double beta = (double)m / (double)(m + u);
+    if (v < t.first_b) { Ma += m; Ua += u; cnt_a++; sum_a += beta; } else { Mb += m; Ub += u; cnt_b++; sum_b += beta; }
+  }
+  const double Na = (double)(Ma + Ua), Nb = (double)(Mb + Ub);
+  const double beta_a = (double)Ma / Na, beta_b = (double)Mb / Nb;
+  const double mean_a = sum_a / (double)cnt_a, mean_b = sum_b / (double)cnt_b;
+  // second walk: squared deviations from the group's mean, and the Pearson statistic around the group's pooled beta
+  double ss_a = 0.0, ss_b = 0.0, X2 = 0.0;
+  for (uint32_t e = 0; e < len; e++) {
+    const uint32_t v = t.val[j + e];
+    if (v >= t.n) continue;
+    const int64_t m = t.meth[v], u = t.unmeth[v];
+    if (m + u < (int64_t)t.min_cov) continue;
+    const bool in_a = v < t.first_b;
+    const double dm = (double)m, dn = (double)(m + u);
+    const double dev = dm / dn - (in_a ? mean_a : mean_b);
+    if (in_a) ss_a += dev * dev; else ss_b += dev * dev;
+    const double ph = in_a ? beta_a : beta_b;
+    const double ex = dn * ph, den = ex * (1.0 - ph), res = dm - ex;
+    if (den != 0.0) X2 += res * res / den;
+  }
+  const double var_a = cnt_a >= 2 ? ss_a / (double)(cnt_a - 1) : nan, var_b = cnt_b >= 2 ? ss_b / (double)(cnt_b - 1) : nan;
+
+  double stat = nan, df = nan, phi = nan, p = nan;
+  if (t.test == EPI_CXG_FISHER) {
+    p = fisher::fisher_two_sided(Ma, Ua, Mb, Ub);
+  } else if (t.test == EPI_CXG_WELCH) {
+    if (cnt_a >= 2 && cnt_b >= 2) {
+      const double va = var_a / (double)cnt_a, vb = var_b / (double)cnt_b, s2 = va + vb;
+      if (s2 != 0.0) {
+        stat = (mean_b - mean_a) / sqrt(s2);
+        df = s2 * s2 / (va * va / (double)(cnt_a - 1) + vb * vb / (double)(cnt_b - 1));
+        p = dist::tail_of(EPI_DIST_T2, stat, df);
+      }
+    }
+  } else {
+    const double N = (double)(Ma + Ua + Mb + Ub);
+    const double p0 = (double)(Ma + Mb) / N, q0 = (double)(Ua + Ub) / N;
+    const double G = 2.0 * (((cxg_dev_term((double)Ma, Na * p0) + cxg_dev_term((double)Ua, Na * q0)) + cxg_dev_term((double)Mb, Nb * p0)) +
+                            cxg_dev_term((double)Ub, Nb * q0));
+    if (t.test == EPI_CXG_LRT) {
+      stat = G; df = 1.0;
+      p = dist::tail_of(EPI_DIST_CHISQ, G, 1.0);
+    } else {
+      const int32_t n = cnt_a + cnt_b;
+      df = (double)(n - 2);
+      if (n > 2) {
+        const double over = X2 / df;
+        phi = over > 1.0 ? over : 1.0;
+        stat = G / phi;
+        p = dist::tail_of(EPI_DIST_F1, stat, df);
+      }
+    }
+  }
+
+  const uint64_t k = t.key[j];
+  o.icol[0][r] = (int32_t)(k >> 35); o.icol[1][r] = (int32_t)((k >> 3) & 1u) + 1; o.icol[2][r] = (int32_t)((k >> 4) & 0x7FFFFFFFull);
+  o.icol[3][r] = (int32_t)(k & 7u);
+  o.icol[4][r] = (int32_t)Ma; o.icol[5][r] = (int32_t)Ua; o.icol[6][r] = (int32_t)Mb; o.icol[7][r] = (int32_t)Ub;
+  o.icol[8][r] = cnt_a; o.icol[9][r] = cnt_b;
+  o.dcol[0][r] = beta_a; o.dcol[1][r] = beta_b; o.dcol[2][r] = beta_b - beta_a;
+  o.dcol[3][r] = mean_a; o.dcol[4][r] = mean_b; o.dcol[5][r] = var_a; o.dcol[6][r] = var_b;
+  o.dcol[7][r] = stat; o.dcol[8][r] = df; o.dcol[9][r] = phi; o.dcol[10][r] = p;
+}
+
+// ---- host --------------------------------------------------------------------------------------------------------------
+
+// the call's scratch for n rows: two key buffers and four 32-bit arrays (two value buffers, two counts), the sort's two
+// digit tables, the scan's block sums (over the rows' flags; the tables' are fewer) and the scalars
+static int64_t cxg_scratch_bytes(int64_t n) {
+  if (n < 0 || n >= (1LL << 32)) return -1;
+  if (n == 0) return 0;
+  return 32 * n + radix_sort_blocks(n) * 256 * 4 * 2 + (n + 4095) / 4096 * 4 + 64;
+}
+
+struct CxgCall {
+  const int32_t *const *tabs;
+  const int64_t *nrows;
+  int32_t n_a, n_b, min_cov, min_a, min_b, test;
+  int32_t *const *icols;
+  double *const *dcols;
+  int64_t cap, total;
+};
+
+static int cx_groups(epi_engine *e, const CxgCall &c, hipStream_t s, int64_t *nsite_out, int64_t *nrow_out) {
+  const char *who = "epi_cx_groups_dev";
+  const int64_t n = c.total, nblk = (n + CXG_WG - 1) / CXG_WG, nsort = radix_sort_blocks(n);
+  EPI_TRY(check_grid(nblk, CXG_WG, "cytosine group comparison kernels"));
+  DevBuf d_rows, d_tab, d_scal, scan_tmp;                     // (go when the call returns)
+  EPI_TRY(d_rows.ensure((size_t)n * 32));
+  EPI_TRY(d_tab.ensure((size_t)nsort * 256 * 4 * 2));
+  EPI_TRY(d_scal.ensure(64));
+  EPI_TRY(scan_tmp.ensure((size_t)nsort * 4));                // (the larger of the two scans: no growth between the kernels)
+  char *rp = d_rows.as<char>();
+  uint64_t *const key[2] = {reinterpret_cast<uint64_t *>(rp), reinterpret_cast<uint64_t *>(rp + (size_t)n * 8)};
+  uint32_t *const val[2] = {reinterpret_cast<uint32_t *>(rp + (size_t)n * 16), reinterpret_cast<uint32_t *>(rp + (size_t)n * 20)};
+  CxgRows rows;
+  rows.key = key[0]; rows.val = val[0];
+  rows.meth = reinterpret_cast<int32_t *>(rp + (size_t)n * 24); rows.unmeth = reinterpret_cast<int32_t *>(rp + (size_t)n * 28);
+  CxgScalars *sc = d_scal.as<CxgScalars>();
+  EPI_HIP(hipMemsetAsync(sc, 0, 64, s));
+
+  prof_begin("cxg_key", s);
+  int64_t base = 0, first_b = 0;
+  for (int k = 0; k < c.n_a + c.n_b; k++) {
+    if (k == c.n_a) first_b = base;
+    const int64_t nk = c.nrows[k];
+    if (nk == 0) continue;
+    CxgTab t;
+    const int32_t *const *d = c.tabs + 6 * k;
+    t.rname = d[0]; t.strand = d[1]; t.pos = d[2]; t.context = d[3]; t.meth = d[4]; t.unmeth = d[5];
+    t.n = (uint32_t)nk; t.base = (uint32_t)base; t.index = (uint32_t)k;
+    hipLaunchKernelGGL(k_cxg_key, dim3((unsigned)((nk + CXG_WG - 1) / CXG_WG)), dim3(CXG_WG), 0, s, t, rows, sc);
+    base += nk;
+  }
+  prof_end("cxg_key", s);
+  EPI_HIP(hipGetLastError());
+
+  int cur = 0;
+  prof_begin("cxg_sort", s);
+  const int rc_sort = radix_sort_pairs(key, val, (uint32_t)n, CXG_KEY_BYTES, d_tab.as<uint32_t>(), d_tab.as<uint32_t>() + (size_t)nsort * 256, scan_tmp, s, &cur);
+  prof_end("cxg_sort", s);
+  EPI_TRY(rc_sort);
+
+  CxgSorted t;
+  t.key = key[cur]; t.val = val[cur]; t.meth = rows.meth; t.unmeth = rows.unmeth;
+  t.n = (uint32_t)n; t.first_b = (uint32_t)first_b;
+  t.min_cov = c.min_cov > 1 ? c.min_cov : 1; t.min_a = c.min_a; t.min_b = c.min_b; t.test = c.test;
+  uint32_t *flag = reinterpret_cast<uint32_t *>(key[cur ^ 1]), *off = flag + n;     // (the sort's other key buffer is free now)
+  prof_begin("cxg_flag", s);
+  hipLaunchKernelGGL(k_cxg_flag, dim3((unsigned)nblk), dim3(CXG_WG), 0, s, t, flag, sc);
+  const int rc_scan = scan_exclusive_u32(flag, off, n, &sc->nrow, scan_tmp, s);
+  prof_end("cxg_flag", s);
+  EPI_HIP(hipGetLastError());
+  EPI_TRY(rc_scan);
+
+  CxgScalars h;                                               // the one synchronisation before anything is written
+  EPI_HIP(hipMemcpyAsync(e->h_scalars, sc, sizeof(h), hipMemcpyDeviceToHost, s));
+  EPI_HIP(hipStreamSynchronize(s));
+  memcpy(&h, e->h_scalars, sizeof(h));
+  if (h.unsorted)
+    return fail(EPI_ERR_ARG, "%s: the rows of table %u (counting a's, then b's, from 0) are not strictly ascending in (rname, pos, strand)", who, h.unsorted - 1u);
+  if (h.bad & CXG_BAD_ROW)
+    return fail(EPI_ERR_ARG, "%s: a row has an rname code outside 0 .. %d, a negative pos, a strand other than 1 and 2, a context code outside 0 .. 7 or a negative count",
+                who, EPI_CXG_MAX_RNAME);
+  *nsite_out = h.nsite;
+  *nrow_out = h.nrow;
+  if (h.bad & CXG_BAD_POOLED)
+    return fail(EPI_ERR_ARG, "%s: a group's pooled meth + unmeth at a reported site exceeds 2^31 - 1, which an int32 column cannot hold", who);
+  if ((int64_t)h.nrow > c.cap) return fail(EPI_ERR_ARG, "%s: %lld rows to write, room for %lld", who, (long long)h.nrow, (long long)c.cap);
+  if (h.nrow == 0) return EPI_OK;
+  CxgOut o;
+  for (int i = 0; i < 10; i++) { if (!c.icols || !c.icols[i]) return fail(EPI_ERR_ARG, "%s: NULL column", who); o.icol[i] = c.icols[i]; }
+  for (int i = 0; i < 11; i++) { if (!c.dcols || !c.dcols[i]) return fail(EPI_ERR_ARG, "%s: NULL column", who); o.dcol[i] = c.dcols[i]; }
+  o.nrow = h.nrow;
+  prof_begin("cxg_emit", s);
+  hipLaunchKernelGGL(k_cxg_emit, dim3((unsigned)nblk), dim3(CXG_WG), 0, s, t, flag, off, o);
+  prof_end("cxg_emit", s);
+  EPI_HIP(hipGetLastError());
+  EPI_HIP(hipStreamSynchronize(s));                           // (the scratch goes back when this returns)
+  return EPI_OK;
+}
+
+}  // namespace epi
+
+using namespace epi;
+
+extern "C" {
+
+int epi_dist_tail_dev(epi_engine *e, int32_t kind, const double *d_x, const double *d_df, int64_t n, double *d_p, void *stream) {
+  const char *who = "epi_dist_tail_dev";
+  if (!e) return fail(EPI_ERR_ARG, "%s: NULL engine", who);
+  if (kind < EPI_DIST_CHISQ || kind > EPI_DIST_F1) return fail(EPI_ERR_ARG, "%s: kind = %d, one of EPI_DIST_CHISQ, EPI_DIST_T2, EPI_DIST_F1", who, kind);
+  if (n < 0 || (n > 0 && (!d_x || !d_df || !d_p))) return fail(EPI_ERR_ARG, "%s: bad arguments", who);
+  if (n == 0) return EPI_OK;
+  const int64_t nb = (n + CXG_WG - 1) / CXG_WG;
+  EPI_TRY(check_grid(nb, CXG_WG, "distribution tail kernel"));
+  EPI_HIP(hipSetDevice(e->device));
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  prof_begin("dist_tail", s);
+  hipLaunchKernelGGL(k_dist_tail, dim3((unsigned)nb), dim3(CXG_WG), 0, s, kind, d_x, d_df, n, d_p);
+  prof_end("dist_tail", s);
+  EPI_HIP(hipGetLastError());
+  return EPI_OK;
+}
+
+int epi_cx_groups_scratch_bytes(int64_t total_rows, int64_t *bytes_out) {
+  if (!bytes_out) return fail(EPI_ERR_ARG, "epi_cx_groups_scratch_bytes: NULL argument");
+  *bytes_out = 0;
+  const int64_t bytes = cxg_scratch_bytes(total_rows);
+  if (bytes < 0) return fail(EPI_ERR_ARG, "epi_cx_groups_scratch_bytes: %lld rows, the samples hold 0 to 2^32 - 1 together", (long long)total_rows);
+  *bytes_out = bytes;
+  return EPI_OK;
+}
+
+int epi_cx_groups_dev(epi_engine *e, const int32_t *const *d_tabs, const int64_t *nrows, int32_t n_a, int32_t n_b, int32_t min_coverage,
+                      int32_t min_samples_a, int32_t min_samples_b, int32_t test, int32_t *const d_icols[10], double *const d_dcols[11],
+                      int64_t cap, void *stream, int64_t *nsite_out, int64_t *nrow_out) {
+  const char *who = "epi_cx_groups_dev";
+  if (!e || !nsite_out || !nrow_out) return fail(EPI_ERR_ARG, "%s: NULL argument", who);
+  *nsite_out = 0; *nrow_out = 0;
+  if (n_a < 1 || n_a > CXG_MAX_GROUP || n_b < 1 || n_b > CXG_MAX_GROUP)
+    return fail(EPI_ERR_ARG, "%s: %d and %d samples, a group holds 1 to %d", who, n_a, n_b, CXG_MAX_GROUP);
+  if (min_samples_a < 1 || min_samples_a > n_a || min_samples_b < 1 || min_samples_b > n_b)
+    return fail(EPI_ERR_ARG, "%s: min_samples_a = %d and min_samples_b = %d, each from 1 to its group's size (%d, %d)", who, min_samples_a,
+                min_samples_b, n_a, n_b);
+  if (test < EPI_CXG_FISHER || test > EPI_CXG_WELCH) return fail(EPI_ERR_ARG, "%s: test = %d, one of EPI_CXG_FISHER, LRT, LRT_MN, WELCH", who, test);
+  if (!d_tabs || !nrows) return fail(EPI_ERR_ARG, "%s: NULL argument", who);
+  if (cap < 0) return fail(EPI_ERR_ARG, "%s: negative capacity", who);
+  int64_t total = 0;
+  for (int k = 0; k < n_a + n_b; k++) {
+    if (nrows[k] < 0 || nrows[k] >= (1LL << 32)) return fail(EPI_ERR_ARG, "%s: table %d has %lld rows", who, k, (long long)nrows[k]);
+    total += nrows[k];
+    if (nrows[k] > 0)
+      for (int i = 0; i < 6; i++) if (!d_tabs[6 * k + i]) return fail(EPI_ERR_ARG, "%s: NULL column in table %d", who, k);
+  }
+  if (total >= (1LL << 32)) return fail(EPI_ERR_ARG, "%s: %lld rows in all, the samples hold fewer than 2^32 together", who, (long long)total);
+  if (total == 0) return EPI_OK;
+  EPI_HIP(hipSetDevice(e->device));
+  CxgCall c;
+  c.tabs = d_tabs; c.nrows = nrows; c.n_a = n_a; c.n_b = n_b; c.min_cov = min_coverage; c.min_a = min_samples_a; c.min_b = min_samples_b;
+  c.test = test; c.icols = d_icols; c.dcols = d_dcols; c.cap = cap; c.total = total;
+  return cx_groups(e, c, reinterpret_cast<hipStream_t>(stream), nsite_out, nrow_out);
+}
+
+}  // extern "C"

@@ -28,15 +28,19 @@ namespace fisher {
 constexpr double kRelTol = 1e-7;
 constexpr double kLn2Pi = 1.837877066409345483560659472811;   // log(2 pi)
 
-// stirlerr(n) = log(n!) - log(sqrt(2 pi n) (n / e)^n)
-EPI_FISHER_HD static double stirlerr(double n) {
-  if (n <= 15.0) return lgamma(n + 1.0) - (n + 0.5) * log(n) + n - 0.5 * kLn2Pi;
+// stirlerr(n) = log(n!) - log(sqrt(2 pi n) (n / e)^n): its series, n > 15 (dist_math.hpp calls this half alone)
+EPI_FISHER_HD static double stirlerr_series(double n) {
   const double S0 = 1.0 / 12, S1 = 1.0 / 360, S2 = 1.0 / 1260, S3 = 1.0 / 1680, S4 = 1.0 / 1188;
   const double nn = n * n;
   if (n > 500) return (S0 - S1 / nn) / n;
   if (n > 80) return (S0 - (S1 - S2 / nn) / nn) / n;
   if (n > 35) return (S0 - (S1 - (S2 - S3 / nn) / nn) / nn) / n;
   return (S0 - (S1 - (S2 - (S3 - S4 / nn) / nn) / nn) / nn) / n;
+}
+
+EPI_FISHER_HD static double stirlerr(double n) {
+  if (n <= 15.0) return lgamma(n + 1.0) - (n + 0.5) * log(n) + n - 0.5 * kLn2Pi;
+  return stirlerr_series(n);
 }
 
 // deviance term x log(x / np) + np - x, accurately also when x is close to np
@@ -81,8 +85,8 @@ struct Hyper {
   EPI_FISHER_HD double down(double k) const { return k * (n2 - m + k) / ((n1 - k + 1) * (m - k + 1)); }    // P(k - 1) / P(k)
 };
 
-// non-negative cells (the callers turn a negative one into NaN)
-EPI_FISHER_HD static double fisher_two_sided(int64_t a, int64_t b, int64_t c, int64_t d) {
+// non-negative cells (the callers turn a negative one into NaN); dist.cpp includes this header for stirlerr and bd0 alone
+[[maybe_unused]] EPI_FISHER_HD static double fisher_two_sided(int64_t a, int64_t b, int64_t c, int64_t d) {
   const int64_t n1 = a + b, n2 = c + d, m = a + c, n = n1 + n2;
   const int64_t lo = m - n2 > 0 ? m - n2 : 0, hi = m < n1 ? m : n1;
   if (lo == hi) return 1.0;

@@ -767,6 +767,90 @@ int epi_cx_compare_regions_dev(epi_engine *e, const int32_t *const d_icols[8], c
 int epi_p_adjust_dev(epi_engine *e, const double *d_p, int64_t n, int32_t method, int64_t n_tests, double *d_q,
                      int32_t *d_order, void *stream, int64_t *nvalid_out);
 
+/* Tail probabilities of the chi-square, Student and F(1, df) distributions.  The reference has no such call.  One copy of
+ * the arithmetic (csrc/dist_math.hpp, which has the formulas) is compiled into the host function and the device kernel,
+ * without fast-math and without contraction.
+ *  Kinds     EPI_DIST_CHISQ  p = P(X >= x), X chi-square with df degrees of freedom: Q(df / 2, x / 2), the regularised upper
+ *                            incomplete gamma function (series below x / 2 < df / 2 + 1, continued fraction above it,
+ *                            erfc(sqrt(x / 2)) at df == 1).
+ *            EPI_DIST_T2     x is a Student statistic t, of either sign; p = P(|T| >= |t|) = I_{df / (df + t^2)}(df / 2, 1 / 2),
+ *                            the regularised incomplete beta function (continued fraction with the symmetric swap).
+ *            EPI_DIST_F1     x is an F statistic with 1 and df degrees of freedom; p = P(F >= x) = I_{df / (df + x)}(df / 2, 1 / 2).
+ *  Domain    df finite, 0 < df <= 1e4.  x >= 0 (EPI_DIST_T2: any t).  x == 0 gives 1, +inf (EPI_DIST_T2: either inf) gives
+ *            0.  NaN, a negative x, or a df outside the range: NaN.  No loop depends on convergence alone: each has a fixed
+ *            bound derived from the domain, and a tail that has not converged there is NaN (none does on the domain).
+ *  Accuracy  against 50-digit arithmetic on the grid and the random points of tests/test_dist_host.py the host's largest
+ *            relative error is 6.4e-13 where the exact value is at least 1e-300 (EPI_DIST_T2 at t = 2, df = 1e4, just below the
+ *            swap, where the direct fraction's denominators cancel; the chi-square tail's is 1.1e-13, at p = 4e-249, about
+ *            1e-16 times the size of the exponent); below 1e-300 the result is between 0 and 1e-300.  The device differs from the host by
+ *            what its lgamma / log / exp / erfc differ (DESIGN 4.18 has the measured figure).
+ * epi_dist_tail is host code and needs no device.  epi_dist_tail_dev: all pointers are device memory of e's device, one
+ * thread per value performs the host's operations in the host's order, so no launch shape enters a result; the kernel is
+ * queued on `stream`, nothing is synchronised.  n == 0: nothing is done.  A kind other than the three, n < 0 or a NULL
+ * pointer with n > 0: EPI_ERR_ARG. */
+#define EPI_DIST_CHISQ 0
+#define EPI_DIST_T2    1
+#define EPI_DIST_F1    2
+int epi_dist_tail(int32_t kind, const double *x, const double *df, int64_t n, double *p_out);
+int epi_dist_tail_dev(epi_engine *e, int32_t kind, const double *d_x, const double *d_df, int64_t n, double *d_p, void *stream);
+
+/* Two groups of cytosine reports against each other per cytosine: replicate-aware differential methylation.  The reference
+ * has no such report.  Stateless, like epi_cx_compare_dev: the call reads device columns of the caller, writes device columns
+ * of the caller, holds its scratch for the length of the call (epi_device_allocations reads the same after it as before,
+ * on every return path) and touches no batch.  It synchronises `stream`, once before anything is written.
+ *  Inputs    d_tabs: (n_a + n_b) * 6 device pointers (the array itself is host memory), the six CX columns (rname, strand, pos,
+ *            context, meth, unmeth) of each sample, group a's samples first; nrows[k]: the rows of sample k.  n_a and n_b from
+ *            1 to 32, the rows of all samples together below 2^32.  Precondition, checked on the device: the rows of every
+ *            table strictly ascend in (rname, pos, strand); otherwise EPI_ERR_ARG naming a table, and nothing is written.
+ *  Key       one 64-bit key per row: rname << 35 | pos << 4 | (strand - 1) << 3 | context.  rname codes from 0 to
+ *            EPI_CXG_MAX_RNAME = 2^21 - 1, pos from 0 to 2^31 - 1, strand 1 or 2, context codes from 0 to 7, meth and unmeth not
+ *            negative: anything else in any row is EPI_ERR_ARG, and nothing is written.
+ *  Sites     a site is a distinct (rname, pos, strand, context) over all tables.  Sample k counts at a site when it has that
+ *            row with meth + unmeth >= max(min_coverage, 1).  *nsite_out = the sites at which at least one sample counts.  A
+ *            site is reported when at least min_samples_a samples of a and min_samples_b samples of b count (each minimum
+ *            from 1 to its group's size, else EPI_ERR_ARG), in ascending (rname, pos, strand, context).  *nrow_out = their
+ *            number.
+ *  Columns   ten int32: rname, strand, pos, context, meth_a, unmeth_a, meth_b, unmeth_b (M_g, U_g: sums over the counting
+ *            samples of the group), nsamples_a, nsamples_b (n_a', n_b': the counting samples).  If N_g = M_g + U_g of a reported
+ *            site exceeds 2^31 - 1: EPI_ERR_ARG, nothing is written.  Eleven double: beta_a = M_a / N_a, beta_b (one IEEE
+ *            division of integers each), delta_beta = beta_b - beta_a; mean_beta_g = (sum in sample order of beta_i = m_i /
+ *            (m_i + u_i)) / n_g'; var_g = (sum in sample order of (beta_i - mean_beta_g)^2) / (n_g' - 1), NaN when n_g' < 2;
+ *            stat, df, phi, p by `test`:
+ *  Tests     with p0 = (M_a + M_b) / (N_a + N_b), q0 = (U_a + U_b) / (N_a + N_b), n = n_a' + n_b', d(x, e) = e when x == 0 and
+ *            else csrc/fisher_math.hpp's deviance term bd0(x, e) = x log(x / e) + e - x,
+ *            G = 2 (((d(M_a, N_a p0) + d(U_a, N_a q0)) + d(M_b, N_b p0)) + d(U_b, N_b q0)), every term >= 0:
+ *              EPI_CXG_FISHER  p = the two-sided Fisher p-value of (M_a U_a / M_b U_b) as epi_fisher_exact_dev computes it;
+ *                              stat, df, phi NaN.  With one sample a side the table is epi_cx_compare_dev's.
+ *              EPI_CXG_LRT     the likelihood-ratio test of the two-group binomial logistic regression: stat = G, df = 1, phi
+ *                              NaN, p = EPI_DIST_CHISQ of (G, 1).  M = 0 or U = 0 in both groups: G = 0 and p = 1 exactly.
+ *              EPI_CXG_LRT_MN  the same deviance with McCullagh-Nelder overdispersion and an F test: X2 = the sum, over a's
+ *                              counting samples and then b's, in sample order, of (m_i - n_i ph_g)^2 / ((n_i ph_g) (1 - ph_g))
+ *                              with n_i = m_i + u_i, ph_g = M_g / N_g, a term with a zero denominator being 0; phi = max(1, X2 /
+ *                              (n - 2)), stat = G / phi, df = n - 2, p = EPI_DIST_F1 of (stat, df).  n <= 2: df = n - 2 and
+ *                              stat, phi, p NaN.
+ *              EPI_CXG_WELCH   Welch's t-test on the samples' betas: v_g = var_g / n_g', s2 = v_a + v_b, stat = (mean_beta_b -
+ *                              mean_beta_a) / sqrt(s2), df = s2^2 / (v_a^2 / (n_a' - 1) + v_b^2 / (n_b' - 1)), p = EPI_DIST_T2 of
+ *                              (stat, df); phi NaN.  n_a' < 2, n_b' < 2 or s2 == 0: stat, df, p NaN.
+ *            One thread per reported site performs these operations in this order: no launch shape enters a result, and the
+ *            integer columns, the betas, means, variances, phi and Welch's stat and df compare bit for bit with a sequential
+ *            evaluation in IEEE double; G and p differ by what the device's log / exp / lgamma / erfc differ from the host's.
+ *  Capacity  the columns hold `cap` rows.  cap < *nrow_out: EPI_ERR_ARG, nothing is written, *nrow_out is the count needed.
+ *            (rows of all samples) / (min_samples_a + min_samples_b) always suffices.  No rows at all: an empty report.
+ *  Memory    32 bytes per input row (two key and two value buffers of the sort, the rows' two counts) and the sort's digit
+ *            tables; epi_cx_groups_scratch_bytes gives the figure for total_rows rows, 0 for none, or EPI_ERR_ARG outside
+ *            0 <= total_rows < 2^32 (it needs no device).
+ * No covariates, no beta-binomial shrinkage, no sharded form. */
+#define EPI_CXG_FISHER 0
+#define EPI_CXG_LRT    1
+#define EPI_CXG_LRT_MN 2
+#define EPI_CXG_WELCH  3
+#define EPI_CXG_MAX_RNAME 2097151
+int epi_cx_groups_dev(epi_engine *e, const int32_t *const *d_tabs, const int64_t *nrows, int32_t n_a, int32_t n_b,
+                      int32_t min_coverage, int32_t min_samples_a, int32_t min_samples_b, int32_t test,
+                      int32_t *const d_icols[10], double *const d_dcols[11], int64_t cap, void *stream, int64_t *nsite_out,
+                      int64_t *nrow_out);
+int epi_cx_groups_scratch_bytes(int64_t total_rows, int64_t *bytes_out);
+
 /* rcpp_extract_patterns (src/rcpp_extract_patterns.cpp:26-211; caller .getPatterns, R/internal.R:683-714):
  * methylation patterns of the reads overlapping one target.  Library-owned host table: per pattern strand, start,
  * end, nbase, beta, the FNV-1a hash the R side prints as 16 hex digits ("pattern"), the ordered column positions
