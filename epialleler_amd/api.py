@@ -53,6 +53,23 @@ def _stream(device):
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
+def _engine_of(values):
+    """(engine, device index, device string) of a call over `values` (array-likes or tensors): the device of the first CUDA
+    tensor among them, else the default engine's."""
+    torch = _torch()
+    on_dev = [v.device for v in values if isinstance(v, torch.Tensor) and v.is_cuda]
+    eng = _engine(on_dev[0].index if on_dev else None)
+    index = _lib.load().epi_engine_device(eng)
+    return eng, index, "cuda:%d" % index
+
+
+def _table_cols(nint, ndbl, n, dev):
+    """The columns of a table of n rows on `dev`, nint int32 ones and ndbl float64 ones: one allocation per type."""
+    torch = _torch()
+    return (list(torch.empty((nint, n), dtype=torch.int32, device=dev).unbind(0)),
+            list(torch.empty((ndbl, n), dtype=torch.float64, device=dev).unbind(0)))
+
+
 class Report(dict):
     """A report table: dict of equal-length numpy (or torch) columns plus factor levels,
     the analogue of the data.table the reference returns."""
@@ -379,10 +396,7 @@ def cytosine_report_fused(df, ctx_meth, ctx_unmeth, ooctx_meth, ooctx_unmeth, mi
 def _fetch_table(bam, fetch, n, nint, names, as_device, extra=()):
     """The columns of a finished report of n rows, nint int32 ones then float64 ones, through the library's `fetch`;
     `extra`: further device tensors (or None) that it takes between the columns and the stream."""
-    torch = _torch()
-    dev = "cuda:%d" % bam.device
-    icols = list(torch.empty((nint, n), dtype=torch.int32, device=dev).unbind(0))
-    dcols = list(torch.empty((len(names) - nint, n), dtype=torch.float64, device=dev).unbind(0))
+    icols, dcols = _table_cols(nint, len(names) - nint, n, "cuda:%d" % bam.device)
     if n:
         _lib.check(fetch(bam.batch(), _ptr_array(icols), _ptr_array(dcols),
                          *[C.c_void_p(t.data_ptr()) if t is not None else None for t in extra], _stream(bam.device)))
@@ -540,8 +554,7 @@ def rcpp_region_report(df, regions, ctx, min_sites, max_sites, reverse_offset, u
     if len(cols3) != 3 or any(c.dim() != 1 or c.numel() != cols3[0].numel() for c in cols3):
         raise ValueError("regions: expected (rname codes, start, end), three sequences of one length")
     n = int(cols3[0].numel())
-    icols = list(torch.empty((15, n), dtype=torch.int32, device=dev).unbind(0))
-    dcols = list(torch.empty((6, n), dtype=torch.float64, device=dev).unbind(0))
+    icols, dcols = _table_cols(15, 6, n, dev)
     _lib.check(lib.epi_batch_region_report_dev(b, *[C.c_void_p(c.data_ptr()) if n else None for c in cols3], n, _lib.enc(ctx), int(min_sites),
                                                int(max_sites), int(reverse_offset), float(u_max), float(m_min), float(max_ooctx_meth_frac),
                                                _ptr_array(icols), _ptr_array(dcols), _stream(bam.device)))
@@ -594,8 +607,7 @@ def rcpp_cx_compare(rep_a, rep_b, min_coverage=1, as_device=False):
     dev = a[0].device
     na, nb = int(a[0].numel()), int(b[0].numel())
     cap = min(na, nb)
-    icols = list(torch.empty((8, cap), dtype=torch.int32, device=dev).unbind(0))
-    dcols = list(torch.empty((4, cap), dtype=torch.float64, device=dev).unbind(0))
+    icols, dcols = _table_cols(8, 4, cap, dev)
     ncommon, nrow = C.c_int64(0), C.c_int64(0)
     _lib.check(lib.epi_cx_compare_dev(_engine(dev.index), _ptr_array(a), na, _ptr_array(b), nb, min_coverage, _ptr_array(icols),
                                       _ptr_array(dcols), cap, _stream(dev.index), C.byref(ncommon), C.byref(nrow)))
@@ -625,8 +637,7 @@ def rcpp_cx_compare_regions(rep, max_p=0.05, min_delta_beta=0.1, max_gap=500, mi
     dev = cols[0].device
     n = int(cols[0].numel())
     cap = n // min_sites                                   # (runs do not overlap)
-    icols = list(torch.empty((5, cap), dtype=torch.int32, device=dev).unbind(0))
-    dcols = list(torch.empty((5, cap), dtype=torch.float64, device=dev).unbind(0))
+    icols, dcols = _table_cols(5, 5, cap, dev)
     nregion = C.c_int64(0)
     _lib.check(lib.epi_cx_compare_regions_dev(_engine(dev.index), _ptr_array(cols[:8]), _ptr_array(cols[8:]), n, max_p, min_delta_beta,
                                               max_gap, min_sites, _ptr_array(icols), _ptr_array(dcols), cap, _stream(dev.index),
@@ -666,11 +677,7 @@ def fisherExact(a, b, c, d, as_device=False):
         raise ValueError("'a', 'b', 'c' and 'd' should have one length")
     torch = _torch()
     lib = _lib.load()
-    on_dev = [x.device for x in cells if isinstance(x, torch.Tensor) and x.is_cuda]
-    index = on_dev[0].index if on_dev else None
-    eng = _engine(index)
-    index = lib.epi_engine_device(eng)
-    dev = "cuda:%d" % index
+    eng, index, dev = _engine_of(cells)
     cells = [(x if isinstance(x, torch.Tensor) else torch.from_numpy(x)).to(device=dev, dtype=torch.int32).contiguous() for x in cells]
     p = torch.empty(n, dtype=torch.float64, device=dev)
     _lib.check(lib.epi_fisher_exact_dev(eng, *[C.c_void_p(x.data_ptr()) for x in cells], n, C.c_void_p(p.data_ptr()), _stream(index)))
@@ -701,11 +708,7 @@ def _dist_tail(kind, x, df, names, as_device):
         raise ValueError("'%s' should be one number or have the length of '%s'" % (names[1], names[0]))
     torch = _torch()
     lib = _lib.load()
-    on_dev = [v.device for v in (x, df) if isinstance(v, torch.Tensor) and v.is_cuda]
-    index = on_dev[0].index if on_dev else None
-    eng = _engine(index)
-    index = lib.epi_engine_device(eng)
-    dev = "cuda:%d" % index
+    eng, index, dev = _engine_of((x, df))
     x, df = [(v if isinstance(v, torch.Tensor) else torch.from_numpy(v)).to(device=dev, dtype=torch.float64) for v in (x, df)]
     if int(df.shape[0]) != n:
         df = df.expand(n)
@@ -770,8 +773,7 @@ def rcpp_cx_compare_groups(reps_a, reps_b, min_coverage=1, min_samples_a=None, m
     lib = _lib.load()
     nrows = [int(t[0].numel()) for t in tabs]
     cap = sum(nrows) // (min_samples_a + min_samples_b)
-    icols = list(torch.empty((10, cap), dtype=torch.int32, device=dev).unbind(0))
-    dcols = list(torch.empty((11, cap), dtype=torch.float64, device=dev).unbind(0))
+    icols, dcols = _table_cols(10, 11, cap, dev)
     nsite, nrow = C.c_int64(0), C.c_int64(0)
     _lib.check(lib.epi_cx_groups_dev(_engine(dev.index), _ptr_array([c for t in tabs for c in t]), (C.c_int64 * len(nrows))(*nrows), len(reps_a),
                                      len(reps_b), min_coverage, min_samples_a, min_samples_b, _GROUP_TEST_CODES[test], _ptr_array(icols),
@@ -816,10 +818,7 @@ def _p_adjust(p, code, n_tests):
     """epi_p_adjust_dev on a flat column (_p_values): q, a device tensor."""
     torch = _torch()
     lib = _lib.load()
-    index = p.device.index if isinstance(p, torch.Tensor) and p.is_cuda else None
-    eng = _engine(index)
-    index = lib.epi_engine_device(eng)
-    dev = "cuda:%d" % index
+    eng, index, dev = _engine_of((p,))
     p = (p if isinstance(p, torch.Tensor) else torch.from_numpy(p)).to(device=dev, dtype=torch.float64).contiguous()
     n = int(p.shape[0])
     q = torch.empty(n, dtype=torch.float64, device=dev)

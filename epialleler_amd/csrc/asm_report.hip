@@ -55,7 +55,7 @@
 //      with cell = 2 allele + (methylated ? 0 : 1), R = the longest row (or D + 1 when that is smaller) and S = 6 + the bits of
 //      2 R.  A unit batch reserves its events' places with one atomic add of the workgroup on the group's cursor; where an
 //      event lands does not matter, the sort puts it in place and equal keys are only counted.
-//  (e) radix_sort_pairs (p_adjust.hip) over the key bytes in use.
+//  (e) radix_sort.hip's sort, in a SortPairs workspace, over the key bytes in use.
 //  (f) k_asm_mark: a thread per event; the first event of a (site, q, strand, context) run finds the ends of the run's four
 //      cell runs by galloping search -- the cells are lengths of runs of equal keys, no counter array and no atomics -- and
 //      flags the run when both alleles have mc calls.  util.hip's scan turns the flags into output rows; their number comes to
@@ -70,7 +70,7 @@
 #include <math.h>
 #include <string.h>
 #include <vector>
-#include "common.hpp"
+#include "radix_sort.hpp"
 #include "site_search.hpp"
 #include "fisher_math.hpp"
 
@@ -79,7 +79,6 @@ namespace epi {
 constexpr int ASM_WG = 256;                         // rows (= threads) per workgroup of the walk
 constexpr int ASM_CAP = 256;                        // window sites counted in LDS
 constexpr int64_t kAsmGroupBytes = 256LL << 20;
-constexpr int64_t kAsmEventBytes = 24;              // two 64-bit keys and two 32-bit values per event
 constexpr uint32_t kAsmNoSite = 0xFFFFFFFFu;
 
 struct AsmScalars {                                 // what the kernels and the host exchange (64 bytes allocated)
@@ -495,7 +494,7 @@ __global__ __launch_bounds__(ASM_WG) void k_asm_fetch(const int32_t *__restrict_
 
 // ---- host -------------------------------------------------------------------------------------------------------------------
 
-static int64_t asm_event_bytes(int64_t nevents) { return nevents < 0 || nevents >= (1LL << 32) ? -1 : nevents * kAsmEventBytes; }
+static int64_t asm_event_bytes(int64_t nevents) { return nevents < 0 || nevents >= (1LL << 32) ? -1 : (int64_t)SortPairs::pair_bytes((size_t)nevents); }
 
 struct AsmCall {
   const int32_t *d_chr, *d_pos, *d_all;
@@ -506,35 +505,43 @@ struct AsmCall {
   AsmCols snv;
 };
 
-static int asm_report(epi_batch *b, const AsmCall &c, hipStream_t s, int64_t *npair_out) {
-  const char *who = "epi_batch_asm_report_dev";
-  AsmState &st = b->asmr;
-  st.clear();
-  const int64_t ns = c.nsite;
-  DevBuf d_sc, d_cnt, d_keep, d_ev, d_tab;                    // the call's scratch: goes with it on every return path
-  EPI_TRY(d_sc.ensure(64));
-  AsmScalars *sc = d_sc.as<AsmScalars>();
-  EPI_HIP(hipMemsetAsync(sc, 0, 64, s));
-  EPI_HIP(hipMemsetAsync(&sc->bad_site, 0xFF, 4, s));
-  const int64_t nb_sites = (ns + 255) / 256;
-  EPI_TRY(check_grid(nb_sites, 256, who));
+struct AsmWork {                                    // the call's scratch (goes with it on every return path) and what its steps share
+  DevBuf d_sc, d_cnt, d_keep, d_ev;
+  AsmScalars *sc = nullptr;
+  unsigned long long *d_events = nullptr, *d_pooled = nullptr;   // the sites' counters: events [ns] and pooled cells [4][ns] in 64 bits,
+  uint32_t *d_reads = nullptr, *d_npairs = nullptr;              // ... reads [3][ns] and pair rows [ns] in 32
+  AsmArgs a;                                        // the walk over all sites
+  uint32_t qbits = 1;                               // q - site_pos + R < 2 R < 2^qbits
+  int64_t nb_walk = 0;
+};
 
-  // (a) the sites
-  hipLaunchKernelGGL(k_asm_check_sites, dim3((unsigned)nb_sites), dim3(256), 0, s, c.d_chr, c.d_pos, c.d_all, ns, sc);
+// (a) the sites' order and masks (first synchronisation), then their zeroed counters
+static int asm_sites(epi_batch *b, const AsmCall &c, AsmWork &w, hipStream_t s) {
+  const char *who = "epi_batch_asm_report_dev";
+  const int64_t ns = c.nsite, nb_sites = (ns + 255) / 256;
+  EPI_TRY(w.d_sc.ensure(64));
+  w.sc = w.d_sc.as<AsmScalars>();
+  EPI_HIP(hipMemsetAsync(w.sc, 0, 64, s));
+  EPI_HIP(hipMemsetAsync(&w.sc->bad_site, 0xFF, 4, s));
+  EPI_TRY(check_grid(nb_sites, 256, who));
+  hipLaunchKernelGGL(k_asm_check_sites, dim3((unsigned)nb_sites), dim3(256), 0, s, c.d_chr, c.d_pos, c.d_all, ns, w.sc);
   EPI_HIP(hipGetLastError());
   AsmScalars h;
-  EPI_TRY(read_scalars(b, s, sc, sizeof(h), &h));
+  EPI_TRY(read_scalars(b, s, w.sc, sizeof(h), &h));
   if (h.bad_site != kAsmNoSite)
     return fail(EPI_ERR_ARG, "%s: d_site_alleles of site %u has a bit above 15, or REF and ALT of one strand share a base", who, h.bad_site);
   if (h.unsorted) return fail(EPI_ERR_UNSORTED, "VCF sites are not sorted by (seqnames, start)");
+  EPI_TRY(w.d_cnt.ensure((size_t)ns * 56));
+  EPI_HIP(hipMemsetAsync(w.d_cnt.p, 0, (size_t)ns * 56, s));
+  w.d_events = w.d_cnt.as<unsigned long long>(); w.d_pooled = w.d_events + ns;
+  w.d_reads = reinterpret_cast<uint32_t *>(w.d_pooled + 4 * ns); w.d_npairs = w.d_reads + 3 * ns;
+  return EPI_OK;
+}
 
-  // the sites' counters: events [ns] and pooled cells [4][ns] in 64 bits, reads [3][ns] and pair rows [ns] in 32
-  EPI_TRY(d_cnt.ensure((size_t)ns * 56));
-  EPI_HIP(hipMemsetAsync(d_cnt.p, 0, (size_t)ns * 56, s));
-  unsigned long long *d_events = d_cnt.as<unsigned long long>(), *d_pooled = d_events + ns;
-  uint32_t *d_reads = reinterpret_cast<uint32_t *>(d_pooled + 4 * ns), *d_npairs = d_reads + 3 * ns;
-
-  int64_t npair = 0;
+// (b), (c) the read rule, then alleles, read counters and the events of every site: h_ev (second synchronisation), left
+// empty when the batch has no byte to walk
+static int asm_count(epi_batch *b, const AsmCall &c, AsmWork &w, hipStream_t s, std::vector<unsigned long long> &h_ev) {
+  const char *who = "epi_batch_asm_report_dev";
   int64_t lmax = 0;
   if (b->n > 0) {
     EPI_TRY(fetch_row_stats(b, s));
@@ -542,121 +549,152 @@ static int asm_report(epi_batch *b, const AsmCall &c, hipStream_t s, int64_t *np
     if (b->h_stats.unsorted) return fail(EPI_ERR_UNSORTED, "PRE-SORTED DATASET IS A REQUIREMENT: rows are not sorted by (rname, start)");
     lmax = b->h_stats.max_len;
   }
-  if (lmax > 0) {
-    AsmArgs a;
-    a.xm = b->xm; a.off = b->off; a.len = b->len; a.rname = b->rname; a.strand = b->strand; a.start = b->start; a.n = b->n;
-    a.lut = asm_make_lut(ctx_mask_of(c.ctx));
-    a.max_dist = c.max_dist;
-    const int64_t R = c.max_dist > 0 && (int64_t)c.max_dist + 1 < lmax ? (int64_t)c.max_dist + 1 : lmax;
-    a.R = (int32_t)R;
-    uint32_t qbits = 1;
-    while ((2 * R) >> qbits) qbits++;                         // q - site_pos + R < 2 R < 2^qbits
-    a.sshift = 6u + qbits;
-    a.reads = d_reads; a.events = d_events;
-    a.key = nullptr; a.cap = 0; a.sc = sc;
+  if (lmax == 0) return EPI_OK;
+  AsmArgs &a = w.a;
+  a.xm = b->xm; a.off = b->off; a.len = b->len; a.rname = b->rname; a.strand = b->strand; a.start = b->start; a.n = b->n;
+  a.lut = asm_make_lut(ctx_mask_of(c.ctx));
+  a.max_dist = c.max_dist;
+  const int64_t R = c.max_dist > 0 && (int64_t)c.max_dist + 1 < lmax ? (int64_t)c.max_dist + 1 : lmax;
+  a.R = (int32_t)R;
+  while ((2 * R) >> w.qbits) w.qbits++;
+  a.sshift = 6u + w.qbits;
+  a.reads = w.d_reads; a.events = w.d_events;
+  a.key = nullptr; a.cap = 0; a.sc = w.sc;
 
-    // (b) the read rule
-    EPI_TRY(d_keep.ensure((size_t)b->n));
-    a.keep = d_keep.as<uint8_t>();
-    const int64_t nb_rule = (b->n + ASM_WG / 16 - 1) / (ASM_WG / 16), nb_walk = (b->n + ASM_WG - 1) / ASM_WG;
-    EPI_TRY(check_grid(nb_rule, ASM_WG, who));
-    EPI_TRY(check_grid(nb_walk, ASM_WG, who));
-    prof_begin("asm_rows", s);
-    hipLaunchKernelGGL(k_asm_rows, dim3((unsigned)nb_rule), dim3(ASM_WG), 0, s, b->xm, b->off, b->len, b->rname, b->strand, b->n, a.lut,
-                       c.max_oo, d_keep.as<uint8_t>());
-    prof_end("asm_rows", s);
-    EPI_HIP(hipGetLastError());
+  EPI_TRY(w.d_keep.ensure((size_t)b->n));
+  a.keep = w.d_keep.as<uint8_t>();
+  const int64_t nb_rule = (b->n + ASM_WG / 16 - 1) / (ASM_WG / 16);
+  w.nb_walk = (b->n + ASM_WG - 1) / ASM_WG;
+  EPI_TRY(check_grid(nb_rule, ASM_WG, who));
+  EPI_TRY(check_grid(w.nb_walk, ASM_WG, who));
+  prof_begin("asm_rows", s);
+  hipLaunchKernelGGL(k_asm_rows, dim3((unsigned)nb_rule), dim3(ASM_WG), 0, s, b->xm, b->off, b->len, b->rname, b->strand, b->n, a.lut,
+                     c.max_oo, w.d_keep.as<uint8_t>());
+  prof_end("asm_rows", s);
+  EPI_HIP(hipGetLastError());
 
-    // (c) alleles, read counters and the events of every site
-    a.s_chr = c.d_chr; a.s_pos = c.d_pos; a.s_all = c.d_all; a.nsite = ns;
-    prof_begin("asm_count", s);
-    hipLaunchKernelGGL((k_asm_walk<false>), dim3((unsigned)nb_walk), dim3(ASM_WG), 0, s, a);
-    prof_end("asm_count", s);
-    EPI_HIP(hipGetLastError());
-    std::vector<unsigned long long> h_ev((size_t)ns);
-    EPI_TRY(copy_to_host(b->eng, h_ev.data(), d_events, (size_t)ns * 8, s));
+  a.s_chr = c.d_chr; a.s_pos = c.d_pos; a.s_all = c.d_all; a.nsite = c.nsite;
+  prof_begin("asm_count", s);
+  hipLaunchKernelGGL((k_asm_walk<false>), dim3((unsigned)w.nb_walk), dim3(ASM_WG), 0, s, a);
+  prof_end("asm_count", s);
+  EPI_HIP(hipGetLastError());
+  h_ev.resize((size_t)c.nsite);
+  return copy_to_host(b->eng, h_ev.data(), w.d_events, (size_t)c.nsite * 8, s);
+}
 
-    // (d) - (f) group by group
-    const int64_t cap_bytes = options().asm_group_bytes > 0 ? options().asm_group_bytes : kAsmGroupBytes;
-    const int64_t max_sites = 1LL << (58u - qbits < 31u ? 58u - qbits : 31u);
-    for (int64_t ga = 0; ga < ns;) {
-      unsigned long long ne = h_ev[ga];
-      int64_t gb = ga + 1;
-      while (gb < ns && gb - ga < max_sites && ne + h_ev[gb] <= 0x7FFFFFFFull && (int64_t)(ne + h_ev[gb]) * kAsmEventBytes <= cap_bytes)
-        ne += h_ev[gb++];
-      if (ne > 0x7FFFFFFFull)
-        return fail(EPI_ERR_ARG, "%s: site %lld has %llu events, a site is sorted with at most 2^31 - 1", who, (long long)ga, ne);
-      const int64_t ng = gb - ga;
-      if (ne > 0) {
-        const size_t n = (size_t)ne;
-        const auto pad = [](size_t v) { return (v + 255) & ~(size_t)255; };
-        const size_t o_key1 = pad(n * 8), o_val0 = o_key1 + pad(n * 8), o_val1 = o_val0 + pad(n * 4);
-        const int64_t nblk = radix_sort_blocks((int64_t)n), nb_ev = ((int64_t)n + ASM_WG - 1) / ASM_WG;
-        EPI_TRY(check_grid(nb_ev, ASM_WG, who));
-        EPI_TRY(d_ev.ensure(o_val1 + pad(n * 4)));
-        EPI_TRY(d_tab.ensure((size_t)nblk * 256 * 4 * 2));
-        char *ep = d_ev.as<char>();
-        uint64_t *const key[2] = {reinterpret_cast<uint64_t *>(ep), reinterpret_cast<uint64_t *>(ep + o_key1)};
-        uint32_t *const val[2] = {reinterpret_cast<uint32_t *>(ep + o_val0), reinterpret_cast<uint32_t *>(ep + o_val1)};
-        EPI_HIP(hipMemsetAsync(val[0], 0, n * 4, s));         // (the sort moves a value with every key; the report has none)
-        EPI_HIP(hipMemsetAsync(&sc->overflow, 0, 16, s));     // overflow, nkept, cursor
-        a.s_chr = c.d_chr + ga; a.s_pos = c.d_pos + ga; a.s_all = c.d_all + ga; a.nsite = ng;
-        a.key = key[0]; a.cap = n;
-        prof_begin("asm_emit", s);
-        hipLaunchKernelGGL((k_asm_walk<true>), dim3((unsigned)nb_walk), dim3(ASM_WG), 0, s, a);
-        prof_end("asm_emit", s);
-        EPI_HIP(hipGetLastError());
+// (d) the grouping rule: the sites from ga on that form the next group -- while their events' (key, value) buffers stay under
+// cap_bytes, they are at most max_sites and their events at most 2^31 - 1; a site beyond a limit runs alone (and beyond the
+// last one is the caller's error).  Returns the group's end, *ne_out its events.
+static int64_t asm_group_end(const std::vector<unsigned long long> &ev, int64_t ga, int64_t max_sites, int64_t cap_bytes,
+                             unsigned long long *ne_out) {
+  const int64_t ns = (int64_t)ev.size();
+  unsigned long long ne = ev[ga];
+  int64_t gb = ga + 1;
+  while (gb < ns && gb - ga < max_sites && ne + ev[gb] <= 0x7FFFFFFFull && (int64_t)SortPairs::pair_bytes((size_t)(ne + ev[gb])) <= cap_bytes)
+    ne += ev[gb++];
+  *ne_out = ne;
+  return gb;
+}
 
-        // (e) the key bytes in use
-        const uint64_t maxkey = ((uint64_t)(ng - 1) << a.sshift) | ((1ull << a.sshift) - 1ull);
-        uint32_t bytes = 0;
-        for (int d = 0; d < 8; d++) if (maxkey >> (8 * d)) bytes |= 1u << d;
-        int cur = 0;
-        prof_begin("asm_sort", s);
-        const int rc_sort = radix_sort_pairs(key, val, (uint32_t)n, bytes, d_tab.as<uint32_t>(), d_tab.as<uint32_t>() + (size_t)nblk * 256, b->scan_tmp, s, &cur);
-        prof_end("asm_sort", s);
-        EPI_TRY(rc_sort);
+// (f) the group's reported runs: a piece of the pair table of nkept rows and their cells added to the sites' pooled sums
+static int asm_piece(epi_batch *b, const AsmCall &c, const AsmWork &w, const SortPairs &sort, size_t n, int64_t ga, uint32_t nkept,
+                     hipStream_t s) {
+  AsmState &st = b->asmr;
+  st.piece.emplace_back();
+  st.rows.push_back(0);                                       // (the piece is counted once it is written)
+  EPI_TRY(st.piece.back().ensure((size_t)nkept * 40));
+  AsmWrite wr;
+  wr.key = sort.keys(); wr.flag = sort.spare<uint32_t>(); wr.out = wr.flag + n; wr.n = (uint32_t)n; wr.nrow = nkept;
+  wr.piece = st.piece.back().as<int32_t>();
+  wr.s_chr = c.d_chr; wr.s_pos = c.d_pos; wr.site0 = ga; wr.nsite = c.nsite;
+  wr.sshift = w.a.sshift; wr.R = w.a.R;
+  wr.pooled = w.d_pooled; wr.npairs = w.d_npairs;
+  prof_begin("asm_reduce", s);
+  hipLaunchKernelGGL(k_asm_write, dim3((unsigned)((n + ASM_WG - 1) / ASM_WG)), dim3(ASM_WG), 0, s, wr);
+  prof_end("asm_reduce", s);
+  EPI_HIP(hipGetLastError());
+  st.rows.back() = nkept;
+  return EPI_OK;
+}
 
-        // (f) which runs are reported, and where (flags and rows in the sort's other key buffer)
-        uint32_t *flag = reinterpret_cast<uint32_t *>(key[cur ^ 1]), *out = flag + n;
-        prof_begin("asm_reduce", s);
-        hipLaunchKernelGGL(k_asm_mark, dim3((unsigned)nb_ev), dim3(ASM_WG), 0, s, key[cur], (uint32_t)n, (uint32_t)(c.min_cov > 1 ? c.min_cov : 1), flag);
-        const int rc_scan = scan_exclusive_u32(flag, out, (int64_t)n, &sc->nkept, b->scan_tmp, s);
-        prof_end("asm_reduce", s);
-        EPI_TRY(rc_scan);
-        EPI_HIP(hipGetLastError());
-        EPI_TRY(read_scalars(b, s, sc, sizeof(h), &h));
-        if (h.overflow || h.cursor != ne)
-          return fail(EPI_ERR_STATE, "%s: sites %lld to %lld counted %llu events and wrote %llu", who, (long long)ga, (long long)gb - 1, ne, h.cursor);
-        if (h.nkept) {
-          st.piece.emplace_back();
-          st.rows.push_back(0);                               // (the piece is counted once it is written)
-          EPI_TRY(st.piece.back().ensure((size_t)h.nkept * 40));
-          AsmWrite wr;
-          wr.key = key[cur]; wr.flag = flag; wr.out = out; wr.n = (uint32_t)n; wr.nrow = h.nkept;
-          wr.piece = st.piece.back().as<int32_t>();
-          wr.s_chr = c.d_chr; wr.s_pos = c.d_pos; wr.site0 = ga; wr.nsite = ns;
-          wr.sshift = a.sshift; wr.R = a.R;
-          wr.pooled = d_pooled; wr.npairs = d_npairs;
-          prof_begin("asm_reduce", s);
-          hipLaunchKernelGGL(k_asm_write, dim3((unsigned)nb_ev), dim3(ASM_WG), 0, s, wr);
-          prof_end("asm_reduce", s);
-          EPI_HIP(hipGetLastError());
-          st.rows.back() = h.nkept;
-          npair += h.nkept;
-        }
-      }
-      ga = gb;
-    }
-  }
+// (d) - (f) one group: sites [ga, gb) with ne > 0 events; the group's synchronisation
+static int asm_group(epi_batch *b, const AsmCall &c, AsmWork &w, int64_t ga, int64_t gb, unsigned long long ne, hipStream_t s,
+                     int64_t *npair) {
+  const char *who = "epi_batch_asm_report_dev";
+  const size_t n = (size_t)ne;
+  const int64_t ng = gb - ga, nb_ev = ((int64_t)n + ASM_WG - 1) / ASM_WG;
+  EPI_TRY(check_grid(nb_ev, ASM_WG, who));
+  EPI_TRY(w.d_ev.ensure(SortPairs::bytes(n)));
+  SortPairs sort(w.d_ev.p, n);
+  EPI_HIP(hipMemsetAsync(sort.vals_in(), 0, n * 4, s));       // (the sort moves a value with every key; the report has none)
+  EPI_HIP(hipMemsetAsync(&w.sc->overflow, 0, 16, s));         // overflow, nkept, cursor
+  AsmArgs a = w.a;                                            // the walk over the group's sites
+  a.s_chr = c.d_chr + ga; a.s_pos = c.d_pos + ga; a.s_all = c.d_all + ga; a.nsite = ng;
+  a.key = sort.keys_in(); a.cap = n;
+  prof_begin("asm_emit", s);
+  hipLaunchKernelGGL((k_asm_walk<true>), dim3((unsigned)w.nb_walk), dim3(ASM_WG), 0, s, a);
+  prof_end("asm_emit", s);
+  EPI_HIP(hipGetLastError());
 
-  // (g) the SNV rows
+  // (e) the key bytes in use
+  const uint64_t maxkey = ((uint64_t)(ng - 1) << a.sshift) | ((1ull << a.sshift) - 1ull);
+  uint32_t bytes = 0;
+  for (int d = 0; d < 8; d++) if (maxkey >> (8 * d)) bytes |= 1u << d;
+  prof_begin("asm_sort", s);
+  const int rc_sort = sort.sort(bytes, b->scan_tmp, s);
+  prof_end("asm_sort", s);
+  EPI_TRY(rc_sort);
+
+  // (f) which runs are reported, and where (flags and rows in the sort's spare buffer)
+  uint32_t *flag = sort.spare<uint32_t>(), *out = flag + n;
+  prof_begin("asm_reduce", s);
+  hipLaunchKernelGGL(k_asm_mark, dim3((unsigned)nb_ev), dim3(ASM_WG), 0, s, sort.keys(), (uint32_t)n, (uint32_t)(c.min_cov > 1 ? c.min_cov : 1), flag);
+  const int rc_scan = scan_exclusive_u32(flag, out, (int64_t)n, &w.sc->nkept, b->scan_tmp, s);
+  prof_end("asm_reduce", s);
+  EPI_TRY(rc_scan);
+  EPI_HIP(hipGetLastError());
+  AsmScalars h;
+  EPI_TRY(read_scalars(b, s, w.sc, sizeof(h), &h));
+  if (h.overflow || h.cursor != ne)
+    return fail(EPI_ERR_STATE, "%s: sites %lld to %lld counted %llu events and wrote %llu", who, (long long)ga, (long long)gb - 1, ne, h.cursor);
+  if (h.nkept) EPI_TRY(asm_piece(b, c, w, sort, n, ga, h.nkept, s));
+  *npair += h.nkept;
+  return EPI_OK;
+}
+
+// (g) the SNV rows; the overflow verdict is the last synchronisation
+static int asm_snv_rows(epi_batch *b, const AsmCall &c, const AsmWork &w, hipStream_t s) {
+  const char *who = "epi_batch_asm_report_dev";
   prof_begin("asm_snv", s);
-  hipLaunchKernelGGL(k_asm_snv, dim3((unsigned)nb_sites), dim3(ASM_WG), 0, s, c.d_chr, c.d_pos, ns, d_reads, d_npairs, d_pooled, c.snv, sc);
+  hipLaunchKernelGGL(k_asm_snv, dim3((unsigned)((c.nsite + 255) / 256)), dim3(ASM_WG), 0, s, c.d_chr, c.d_pos, c.nsite, w.d_reads, w.d_npairs,
+                     w.d_pooled, c.snv, w.sc);
   prof_end("asm_snv", s);
   EPI_HIP(hipGetLastError());
-  EPI_TRY(read_scalars(b, s, sc, sizeof(h), &h));
+  AsmScalars h;
+  EPI_TRY(read_scalars(b, s, w.sc, sizeof(h), &h));
   if (h.bad_sum) return fail(EPI_ERR_ARG, "%s: site %u has a count above 2^31 - 1, which an int32 column cannot hold", who, h.bad_sum - 1u);
+  return EPI_OK;
+}
+
+static int asm_report(epi_batch *b, const AsmCall &c, hipStream_t s, int64_t *npair_out) {
+  const char *who = "epi_batch_asm_report_dev";
+  AsmState &st = b->asmr;
+  st.clear();
+  AsmWork w;
+  EPI_TRY(asm_sites(b, c, w, s));
+  std::vector<unsigned long long> h_ev;
+  EPI_TRY(asm_count(b, c, w, s, h_ev));
+  const int64_t cap_bytes = options().asm_group_bytes > 0 ? options().asm_group_bytes : kAsmGroupBytes;
+  const int64_t max_sites = 1LL << (58u - w.qbits < 31u ? 58u - w.qbits : 31u);
+  int64_t npair = 0;
+  for (int64_t ga = 0, gb = 0; ga < (int64_t)h_ev.size(); ga = gb) {
+    unsigned long long ne = 0;
+    gb = asm_group_end(h_ev, ga, max_sites, cap_bytes, &ne);
+    if (ne > 0x7FFFFFFFull)
+      return fail(EPI_ERR_ARG, "%s: site %lld has %llu events, a site is sorted with at most 2^31 - 1", who, (long long)ga, ne);
+    if (ne > 0) EPI_TRY(asm_group(b, c, w, ga, gb, ne, s, &npair));
+  }
+  EPI_TRY(asm_snv_rows(b, c, w, s));
   st.npair = npair;
   st.reported = true;
   *npair_out = npair;

@@ -126,7 +126,6 @@ struct SiteReportState {
   DevBuf fbits;            // [2][nwords] u64: the rows' calls, bit j of a row = its site lo + j: valid, then methylated
   DevBuf fpair;            // the (site, row) pairs and the sort's scratch; sorted: rows of site g at [site_off[g], site_end[g])
   DevBuf fsite;            // [2][nsite] u32 site_off, site_end
-  const uint32_t *fdrp_rows = nullptr;   // [ncalls] the sorted rows inside fpair
   int64_t nsite = 0;       // sites of the table the last report counted over (0: it reported nothing, no table is kept)
   int32_t k = 0, D = 0;    // window size / neighbours of the last report
   int32_t W = 0, max_rows = 0, min_overlap = 0;   // FDRP: flanking sites, rows used per site, overlap a pair needs
@@ -361,7 +360,8 @@ hipStream_t pick_stream(epi_batch *b, void *stream);
 struct CopyPart { void *dst; const void *src; size_t bytes; };
 int copy_parts_to_host(epi_engine *eng, const CopyPart *parts, int nparts, hipStream_t s);
 int copy_to_host(epi_engine *eng, void *h_dst, const void *d_src, size_t bytes, hipStream_t s);
-int read_scalars(epi_batch *b, hipStream_t s, const void *d_src, size_t bytes, void *h_dst);  // sync D2H of a few bytes
+int read_scalars(epi_engine *e, hipStream_t s, const void *d_src, size_t bytes, void *h_dst);  // sync D2H of a few bytes
+int read_scalars(epi_batch *b, hipStream_t s, const void *d_src, size_t bytes, void *h_dst);   // ... on the batch's engine
 inline Scalars *report_scalars(const epi_batch *b) { return b->misc.as<Scalars>(); }
 inline int read_report_scalars(epi_batch *b, hipStream_t s, Scalars *h) {                   // the whole block, one sync
   return read_scalars(b, s, report_scalars(b), sizeof(Scalars), h);
@@ -450,14 +450,6 @@ int stage_send(epi_engine *eng, int k, void *d_dst, size_t bytes);
 int scan_exclusive_u32(const uint32_t *d_in, uint32_t *d_out, int64_t n, uint32_t *d_total,
                        DevBuf &tmp, hipStream_t s);
 int scan_block_sums_inplace(uint32_t *d_bsum, int64_t nb, uint32_t *d_total, hipStream_t s);
-
-// Stable LSD radix sort of n (64-bit key, 32-bit value) pairs, n < 2^32 (p_adjust.hip has the kernels).  One pass per set bit
-// d of `bytes` (key byte d, least significant first); the pairs start in key[0] / row[0] and bounce between the two buffer
-// pairs, *cur = the one that holds the result.  table and off: radix_sort_blocks(n) * 256 words each; scan_tmp: the
-// scratch of the scan over the table.  Everything is queued on s, nothing is synchronised.
-int64_t radix_sort_blocks(int64_t n);
-int radix_sort_pairs(uint64_t *const key[2], uint32_t *const row[2], uint32_t n, uint32_t bytes, uint32_t *table, uint32_t *off,
-                     DevBuf &scan_tmp, hipStream_t s, int *cur);
 
 // tile index (tiles.hip)
 // queue k_row_stats for a new batch (no sync, no error: per-read functions accept unsorted rows)

@@ -4,7 +4,7 @@
 // touch no batch.  All on the call's stream:
 //  Fisher   k_fisher: a thread per table runs fisher_math.hpp's fisher_two_sided -- the host's arithmetic, in the host's
 //           order, inside one thread: no LDS, no cross-lane work, no launch shape in a result.
-//  Sites    k_cxc_sorted (both tables: every row above its predecessor in (rname, pos, strand)); k_cxc_match: a thread per
+//  Sites    k_cxc_sorted (both tables: every row above its predecessor, cx_table.hpp's order); k_cxc_match: a thread per
 //           row of a searches b (binary, on the same key) and flags the row as common when b has the key with the same
 //           context code, and as reported when both sides have the coverage; util.hip's scan over the reported flags; one
 //           read of {unsorted a, unsorted b, common, reported}; then, and only when the order and the capacity hold,
@@ -13,8 +13,7 @@
 //           apart; k_reg_flag: a thread per row decides whether a run starts there and walks at most min_sites rows of it to
 //           see whether it is reported; the scan; k_reg_emit: the thread of a reported run's first row walks the run once,
 //           summing in ascending row order (a table that is one long run is walked by one thread).
-#include <string.h>
-#include "common.hpp"
+#include "cx_table.hpp"
 #include "fisher_math.hpp"
 
 namespace epi {
@@ -48,32 +47,10 @@ static int fisher_launch(const int32_t *a, const int32_t *b, const int32_t *c, c
 
 // ---- sites -------------------------------------------------------------------------------------------------------------
 
-struct CxTab {                         // a CX table: rname, strand, pos, context, meth, unmeth
-  const int32_t *rname, *strand, *pos, *context, *meth, *unmeth;
-  uint32_t n;
-};
-
-static CxTab cx_tab(const int32_t *const d[6], int64_t n) {
-  CxTab t;
-  t.rname = d[0]; t.strand = d[1]; t.pos = d[2]; t.context = d[3]; t.meth = d[4]; t.unmeth = d[5];
-  t.n = (uint32_t)n;
-  return t;
-}
-
-// row i of t against the key (rname, pos, strand): < 0, 0, > 0
-__device__ __forceinline__ int cxc_cmp(const CxTab &t, uint32_t i, int32_t rname, int32_t pos, int32_t strand) {
-  const int32_t r = t.rname[i];
-  if (r != rname) return r < rname ? -1 : 1;
-  const int32_t p = t.pos[i];
-  if (p != pos) return p < pos ? -1 : 1;
-  const int32_t s = t.strand[i];
-  return s < strand ? -1 : s > strand ? 1 : 0;
-}
-
 __global__ __launch_bounds__(CXC_WG) void k_cxc_sorted(CxTab t, uint32_t *__restrict__ unsorted) {
   const uint32_t i = blockIdx.x * (uint32_t)CXC_WG + threadIdx.x;
   if (i == 0 || i >= t.n) return;
-  if (cxc_cmp(t, i - 1, t.rname[i], t.pos[i], t.strand[i]) >= 0) atomicOr(unsorted, 1u);
+  if (!cx_above(t, i)) atomicOr(unsorted, 1u);
 }
 
 __device__ __forceinline__ bool cxc_covered(int32_t meth, int32_t unmeth, int32_t min_cov) {
@@ -90,9 +67,9 @@ __global__ __launch_bounds__(CXC_WG) void k_cxc_match(CxTab a, CxTab b, int32_t 
     uint32_t lo = 0, hi = b.n;
     while (lo < hi) {
       const uint32_t mid = lo + (hi - lo) / 2u;
-      if (cxc_cmp(b, mid, rname, pos, strand) < 0) lo = mid + 1u; else hi = mid;
+      if (cx_cmp(b, mid, rname, pos, strand) < 0) lo = mid + 1u; else hi = mid;
     }
-    common = lo < b.n && cxc_cmp(b, lo, rname, pos, strand) == 0 && b.context[lo] == a.context[i] ? 1u : 0u;
+    common = lo < b.n && cx_cmp(b, lo, rname, pos, strand) == 0 && b.context[lo] == a.context[i] ? 1u : 0u;
     const bool rep = common && cxc_covered(a.meth[i], a.unmeth[i], min_cov) && cxc_covered(b.meth[lo], b.unmeth[lo], min_cov);
     keep[i] = rep ? 1u : 0u;
     brow[i] = lo;
@@ -188,13 +165,6 @@ __global__ __launch_bounds__(CXC_WG) void k_reg_emit(RegIn t, const uint32_t *__
 
 struct Scratch { DevBuf flag, off, brow, scal, scan_tmp; };   // (goes when the call returns)
 
-static int read_words(epi_engine *e, hipStream_t s, const uint32_t *d_src, int nwords, uint32_t *h_dst) {   // one synchronisation
-  EPI_HIP(hipMemcpyAsync(e->h_scalars, d_src, (size_t)nwords * 4, hipMemcpyDeviceToHost, s));
-  EPI_HIP(hipStreamSynchronize(s));
-  memcpy(h_dst, e->h_scalars, (size_t)nwords * 4);
-  return EPI_OK;
-}
-
 static int cx_compare(epi_engine *e, const int32_t *const d_a[6], int64_t na, const int32_t *const d_b[6], int64_t nb, int32_t min_coverage,
                       int32_t *const d_icols[8], double *const d_dcols[4], int64_t cap, hipStream_t s, int64_t *ncommon_out,
                       int64_t *nrow_out) {
@@ -220,7 +190,7 @@ static int cx_compare(epi_engine *e, const int32_t *const d_a[6], int64_t na, co
   EPI_HIP(hipGetLastError());
   EPI_TRY(rc_scan);
   uint32_t h[4];
-  EPI_TRY(read_words(e, s, scal, 4, h));
+  EPI_TRY(read_scalars(e, s, scal, sizeof(h), h));
   if (h[0] || h[1])
     return fail(EPI_ERR_ARG, "%s: the rows of the %s table are not strictly ascending in (rname, pos, strand)", who, h[0] ? "first" : "second");
   *ncommon_out = h[2];
@@ -267,7 +237,7 @@ static int cx_regions(epi_engine *e, const int32_t *const d_icols[8], const doub
   EPI_HIP(hipGetLastError());
   EPI_TRY(rc_scan);
   uint32_t h = 0;
-  EPI_TRY(read_words(e, s, scal, 1, &h));
+  EPI_TRY(read_scalars(e, s, scal, sizeof(h), &h));
   *nregion_out = h;
   if ((int64_t)h > cap) return fail(EPI_ERR_ARG, "%s: %lld regions to write, room for %lld", who, (long long)h, (long long)cap);
   if (h == 0) return EPI_OK;

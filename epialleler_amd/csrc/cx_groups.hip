@@ -3,10 +3,10 @@
 // Stateless like cx_compare.hip: the call reads the caller's columns, takes its scratch for the length of the call and
 // touches no batch.  All on the call's stream:
 //  Tails    k_dist_tail: a thread per value runs dist_math.hpp's tail_of -- the host's arithmetic in the host's order.
-//  Keys     k_cxg_key, one launch per sample: a thread per row checks the row against its predecessor ((rname, pos, strand)
-//           strictly ascending, as k_cxc_sorted does) and its fields against the key's ranges, and writes the row's 64-bit
+//  Keys     k_cxg_key, one launch per sample: a thread per row checks the row against its predecessor (cx_table.hpp's order,
+//           the one k_cxc_sorted checks) and its fields against the key's ranges, and writes the row's 64-bit
 //           key, its index in the concatenation of the tables (a's first) as the sort's value, and its two counts.
-//  Sort     radix_sort_pairs (p_adjust.hip) over the key's seven bytes.  The sort is stable, so a run of equal keys -- a site
+//  Sort     radix_sort.hip's sort, in a SortPairs workspace, over the key's seven bytes.  The sort is stable, so a run of equal keys -- a site
 //           -- lists its samples in sample order; a table has a key once, so a run has at most 64 entries.
 //  Sites    k_cxg_flag: the thread of a run's first entry walks the run, counts the samples that count in either group and
 //           flags the site as reported; pooled coverage beyond int32 at a reported site raises the overflow flag.  util.hip's
@@ -17,8 +17,8 @@
 //           scratch memory.  The test is a kernel argument, one branch per site.
 // The sort always runs its seven passes: which of the key's upper bytes are empty is known on the device only, and a second
 // read-back to learn it would cost the synchronisation the one read above avoids.
-#include <string.h>
-#include "common.hpp"
+#include "cx_table.hpp"
+#include "radix_sort.hpp"
 #include "fisher_math.hpp"
 #include "dist_math.hpp"
 
@@ -48,29 +48,21 @@ __global__ __launch_bounds__(CXG_WG) void k_dist_tail(int32_t kind, const double
 
 // ---- keys --------------------------------------------------------------------------------------------------------------
 
-struct CxgTab {                        // one sample's CX table and where its rows go in the concatenation
-  const int32_t *rname, *strand, *pos, *context, *meth, *unmeth;
-  uint32_t n, base, index;
-};
-
 struct CxgRows {                       // [total] each
   uint64_t *key;
   uint32_t *val;
   int32_t *meth, *unmeth;
 };
 
-__global__ __launch_bounds__(CXG_WG) void k_cxg_key(CxgTab t, CxgRows o, CxgScalars *__restrict__ sc) {
+// one sample's table; base: where its rows go in the concatenation, index: the sample
+__global__ __launch_bounds__(CXG_WG) void k_cxg_key(CxTab t, uint32_t base, uint32_t index, CxgRows o, CxgScalars *__restrict__ sc) {
   const uint32_t i = blockIdx.x * (uint32_t)CXG_WG + threadIdx.x;
   if (i >= t.n) return;
   const int32_t rname = t.rname[i], pos = t.pos[i], strand = t.strand[i], ctx = t.context[i], m = t.meth[i], u = t.unmeth[i];
-  if (i > 0) {
-    const int32_t r0 = t.rname[i - 1], p0 = t.pos[i - 1], s0 = t.strand[i - 1];
-    const bool above = r0 != rname ? r0 < rname : p0 != pos ? p0 < pos : s0 < strand;
-    if (!above) atomicMax(&sc->unsorted, t.index + 1u);
-  }
+  if (i > 0 && !cx_above(t, i)) atomicMax(&sc->unsorted, index + 1u);
   if (rname < 0 || rname > EPI_CXG_MAX_RNAME || pos < 0 || strand < 1 || strand > 2 || ctx < 0 || ctx > 7 || m < 0 || u < 0)
     atomicOr(&sc->bad, CXG_BAD_ROW);
-  const uint32_t g = t.base + i;
+  const uint32_t g = base + i;
   o.key[g] = ((uint64_t)(uint32_t)rname & (uint64_t)EPI_CXG_MAX_RNAME) << 35 | ((uint64_t)(uint32_t)pos & 0x7FFFFFFFull) << 4 |
              (uint64_t)((uint32_t)(strand - 1) & 1u) << 3 | (uint64_t)((uint32_t)ctx & 7u);
   o.val[g] = g;
@@ -217,12 +209,12 @@ __global__ __launch_bounds__(CXG_WG) void k_cxg_emit(CxgSorted t, const uint32_t
 
 // ---- host --------------------------------------------------------------------------------------------------------------
 
-// the call's scratch for n rows: two key buffers and four 32-bit arrays (two value buffers, two counts), the sort's two
-// digit tables, the scan's block sums (over the rows' flags; the tables' are fewer) and the scalars
+// the call's scratch for n rows: the sort's workspace, the rows' two counts, the scan's block sums (over the rows' flags; the
+// tables' are fewer) and the scalars
 static int64_t cxg_scratch_bytes(int64_t n) {
   if (n < 0 || n >= (1LL << 32)) return -1;
   if (n == 0) return 0;
-  return 32 * n + radix_sort_blocks(n) * 256 * 4 * 2 + (n + 4095) / 4096 * 4 + 64;
+  return (int64_t)SortPairs::bytes((size_t)n) + 8 * n + (n + 4095) / 4096 * 4 + 64;
 }
 
 struct CxgCall {
@@ -236,19 +228,16 @@ struct CxgCall {
 
 static int cx_groups(epi_engine *e, const CxgCall &c, hipStream_t s, int64_t *nsite_out, int64_t *nrow_out) {
   const char *who = "epi_cx_groups_dev";
-  const int64_t n = c.total, nblk = (n + CXG_WG - 1) / CXG_WG, nsort = radix_sort_blocks(n);
+  const int64_t n = c.total, nblk = (n + CXG_WG - 1) / CXG_WG;
   EPI_TRY(check_grid(nblk, CXG_WG, "cytosine group comparison kernels"));
-  DevBuf d_rows, d_tab, d_scal, scan_tmp;                     // (go when the call returns)
-  EPI_TRY(d_rows.ensure((size_t)n * 32));
-  EPI_TRY(d_tab.ensure((size_t)nsort * 256 * 4 * 2));
+  DevBuf d_rows, d_scal, scan_tmp;                            // (go when the call returns)
+  EPI_TRY(d_rows.ensure(SortPairs::bytes((size_t)n) + (size_t)n * 8));   // the sort's workspace, then the two counts
   EPI_TRY(d_scal.ensure(64));
-  EPI_TRY(scan_tmp.ensure((size_t)nsort * 4));                // (the larger of the two scans: no growth between the kernels)
-  char *rp = d_rows.as<char>();
-  uint64_t *const key[2] = {reinterpret_cast<uint64_t *>(rp), reinterpret_cast<uint64_t *>(rp + (size_t)n * 8)};
-  uint32_t *const val[2] = {reinterpret_cast<uint32_t *>(rp + (size_t)n * 16), reinterpret_cast<uint32_t *>(rp + (size_t)n * 20)};
+  EPI_TRY(scan_tmp.ensure((size_t)((n + 4095) / 4096 * 4)));              // (the larger of the two scans: no growth between the kernels)
+  SortPairs sort(d_rows.p, (size_t)n);
   CxgRows rows;
-  rows.key = key[0]; rows.val = val[0];
-  rows.meth = reinterpret_cast<int32_t *>(rp + (size_t)n * 24); rows.unmeth = reinterpret_cast<int32_t *>(rp + (size_t)n * 28);
+  rows.key = sort.keys_in(); rows.val = sort.vals_in();
+  rows.meth = reinterpret_cast<int32_t *>(d_rows.as<char>() + SortPairs::bytes((size_t)n)); rows.unmeth = rows.meth + n;
   CxgScalars *sc = d_scal.as<CxgScalars>();
   EPI_HIP(hipMemsetAsync(sc, 0, 64, s));
 
@@ -258,27 +247,23 @@ static int cx_groups(epi_engine *e, const CxgCall &c, hipStream_t s, int64_t *ns
     if (k == c.n_a) first_b = base;
     const int64_t nk = c.nrows[k];
     if (nk == 0) continue;
-    CxgTab t;
-    const int32_t *const *d = c.tabs + 6 * k;
-    t.rname = d[0]; t.strand = d[1]; t.pos = d[2]; t.context = d[3]; t.meth = d[4]; t.unmeth = d[5];
-    t.n = (uint32_t)nk; t.base = (uint32_t)base; t.index = (uint32_t)k;
-    hipLaunchKernelGGL(k_cxg_key, dim3((unsigned)((nk + CXG_WG - 1) / CXG_WG)), dim3(CXG_WG), 0, s, t, rows, sc);
+    hipLaunchKernelGGL(k_cxg_key, dim3((unsigned)((nk + CXG_WG - 1) / CXG_WG)), dim3(CXG_WG), 0, s, cx_tab(c.tabs + 6 * k, nk), (uint32_t)base,
+                       (uint32_t)k, rows, sc);
     base += nk;
   }
   prof_end("cxg_key", s);
   EPI_HIP(hipGetLastError());
 
-  int cur = 0;
   prof_begin("cxg_sort", s);
-  const int rc_sort = radix_sort_pairs(key, val, (uint32_t)n, CXG_KEY_BYTES, d_tab.as<uint32_t>(), d_tab.as<uint32_t>() + (size_t)nsort * 256, scan_tmp, s, &cur);
+  const int rc_sort = sort.sort(CXG_KEY_BYTES, scan_tmp, s);
   prof_end("cxg_sort", s);
   EPI_TRY(rc_sort);
 
   CxgSorted t;
-  t.key = key[cur]; t.val = val[cur]; t.meth = rows.meth; t.unmeth = rows.unmeth;
+  t.key = sort.keys(); t.val = sort.vals(); t.meth = rows.meth; t.unmeth = rows.unmeth;
   t.n = (uint32_t)n; t.first_b = (uint32_t)first_b;
   t.min_cov = c.min_cov > 1 ? c.min_cov : 1; t.min_a = c.min_a; t.min_b = c.min_b; t.test = c.test;
-  uint32_t *flag = reinterpret_cast<uint32_t *>(key[cur ^ 1]), *off = flag + n;     // (the sort's other key buffer is free now)
+  uint32_t *flag = sort.spare<uint32_t>(), *off = flag + n;
   prof_begin("cxg_flag", s);
   hipLaunchKernelGGL(k_cxg_flag, dim3((unsigned)nblk), dim3(CXG_WG), 0, s, t, flag, sc);
   const int rc_scan = scan_exclusive_u32(flag, off, n, &sc->nrow, scan_tmp, s);
@@ -287,9 +272,7 @@ static int cx_groups(epi_engine *e, const CxgCall &c, hipStream_t s, int64_t *ns
   EPI_TRY(rc_scan);
 
   CxgScalars h;                                               // the one synchronisation before anything is written
-  EPI_HIP(hipMemcpyAsync(e->h_scalars, sc, sizeof(h), hipMemcpyDeviceToHost, s));
-  EPI_HIP(hipStreamSynchronize(s));
-  memcpy(&h, e->h_scalars, sizeof(h));
+  EPI_TRY(read_scalars(e, s, sc, sizeof(h), &h));
   if (h.unsorted)
     return fail(EPI_ERR_ARG, "%s: the rows of table %u (counting a's, then b's, from 0) are not strictly ascending in (rname, pos, strand)", who, h.unsorted - 1u);
   if (h.bad & CXG_BAD_ROW)

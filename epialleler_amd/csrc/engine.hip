@@ -44,13 +44,14 @@ hipStream_t pick_stream(epi_batch *b, void *stream) {
   return reinterpret_cast<hipStream_t>(stream);
 }
 
-int read_scalars(epi_batch *b, hipStream_t s, const void *d_src, size_t bytes, void *h_dst) {
+int read_scalars(epi_engine *e, hipStream_t s, const void *d_src, size_t bytes, void *h_dst) {
   if (bytes > 512) return fail(EPI_ERR_ARG, "read_scalars: too large");
-  EPI_HIP(hipMemcpyAsync(b->eng->h_scalars, d_src, bytes, hipMemcpyDeviceToHost, s));
+  EPI_HIP(hipMemcpyAsync(e->h_scalars, d_src, bytes, hipMemcpyDeviceToHost, s));
   EPI_HIP(hipStreamSynchronize(s));
-  memcpy(h_dst, b->eng->h_scalars, bytes);
+  memcpy(h_dst, e->h_scalars, bytes);
   return EPI_OK;
 }
+int read_scalars(epi_batch *b, hipStream_t s, const void *d_src, size_t bytes, void *h_dst) { return read_scalars(b->eng, s, d_src, bytes, h_dst); }
 
 // ---- profiling ----------------------------------------------------------------
 static bool g_prof_on = false;

@@ -14,7 +14,7 @@
 //      lo + j: valid, methylated), and every call writes one (key = site, value = row) pair at the row's first pair + the
 //      calls of the row in front of this one (the count of the earlier rounds + the lower lanes of the ballot): no place
 //      comes from what an atomic returns.
-//  (d) radix_sort_pairs (p_adjust.hip's stable LSD sort) over the bytes that N - 1 occupies.  The pairs are written in
+//  (d) radix_sort.hip's stable LSD sort, in a SortPairs workspace, over the bytes that N - 1 occupies.  The pairs are written in
 //      ascending row order, the sort is stable: the rows of site g are then a run in ascending row index.  k_fdrp_bounds
 //      (a thread per pair) writes where the run of a site starts and ends; its length is the site's coverage.
 //  (e) k_fdrp_pairs: a wavefront per site.  Lane j takes the j-th selected row and shifts the row's packed calls of the
@@ -29,6 +29,7 @@
 // State: epi_batch::sites (SiteReportState, common.hpp); frow, fbits, fpair and fsite are this report's and stay on the
 // batch with the table: the site -> rows index.
 #include "het_common.hpp"
+#include "radix_sort.hpp"
 
 namespace epi {
 
@@ -272,7 +273,7 @@ static void fdrp_finish_args(const epi_batch *b, FdrpFinish &f) {
 }
 
 // bytes of the two (key, row) buffers of ncalls pairs, or -1 when the sort's 32-bit indices cannot hold them
-static int64_t fdrp_pair_bytes(int64_t ncalls) { return ncalls < 0 || ncalls >= (1LL << 32) ? -1 : ncalls * 24; }
+static int64_t fdrp_pair_bytes(int64_t ncalls) { return ncalls < 0 || ncalls >= (1LL << 32) ? -1 : (int64_t)SortPairs::pair_bytes((size_t)ncalls); }
 
 static int fdrp_empty(epi_batch *b) { b->last_kind = KIND_FDRP; b->last_nrow = 0; b->sites.nsite = 0; return EPI_OK; }
 
@@ -286,7 +287,6 @@ static int fdrp_report(epi_batch *b, const char *ctx, int W, int m, int min_over
   t.nsite = nsite; t.W = W; t.max_rows = m; t.min_overlap = min_overlap;
   t.min_reads = (uint32_t)(min_reads > 2 ? min_reads : 2);
   t.max_dist = max_dist;
-  t.fdrp_rows = nullptr;
   if (nsite == 0 || b->n == 0) return fdrp_empty(b);
   if (nsite >= (1LL << 31)) return fail(EPI_ERR_ARG, "%s: %lld sites, beyond 32-bit ordinals", who, (long long)nsite);
   if (b->nbytes / 64 + b->n >= (1LL << 32)) return fail(EPI_ERR_ARG, "%s: the rows' packed calls need 2^32 words or more", who);
@@ -326,23 +326,18 @@ static int fdrp_report(epi_batch *b, const char *ctx, int W, int m, int min_over
   if (pbytes < 0)
     return fail(EPI_ERR_ARG, "%s: %llu calls, the site -> rows index holds fewer than 2^32 pairs", who, h.ncalls);
   const size_t nc = (size_t)h.ncalls, nw = h.nwords;
-  const int64_t nblk_sort = radix_sort_blocks((int64_t)nc), nb_pairs = ((int64_t)nc + HET_WG - 1) / HET_WG;
+  const int64_t nb_pairs = ((int64_t)nc + HET_WG - 1) / HET_WG;
   EPI_TRY(check_grid(nb_pairs, HET_WG, "FDRP index kernels"));
 
   // (c) the packed calls and the (site, row) pairs
-  const auto pad = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t o_key1 = pad(nc * 8), o_row0 = o_key1 + pad(nc * 8), o_row1 = o_row0 + pad(nc * 4), o_table = o_row1 + pad(nc * 4);
-  const size_t o_off = o_table + pad((size_t)nblk_sort * 256 * 4), p_end = o_off + pad((size_t)nblk_sort * 256 * 4);
-  EPI_TRY(t.fpair.ensure(p_end));
+  EPI_TRY(t.fpair.ensure(SortPairs::bytes(nc)));
   EPI_TRY(t.fbits.ensure(nw * 16));
   EPI_TRY(t.fsite.ensure(N * 8));
   EPI_TRY(t.counts.ensure(N * sizeof(FdrpSite)));
   EPI_TRY(t.out.ensure(N * 4));
-  char *fp = t.fpair.as<char>();
-  uint64_t *const key[2] = {reinterpret_cast<uint64_t *>(fp), reinterpret_cast<uint64_t *>(fp + o_key1)};
-  uint32_t *const row[2] = {reinterpret_cast<uint32_t *>(fp + o_row0), reinterpret_cast<uint32_t *>(fp + o_row1)};
+  SortPairs sort(t.fpair.p, nc);
   a.valid = t.fbits.as<uint64_t>(); a.meth = a.valid + nw;
-  a.pkey = key[0]; a.prow = row[0];
+  a.pkey = sort.keys_in(); a.prow = sort.vals_in();
   prof_begin("fdrp_fill", s);
   if (wide) hipLaunchKernelGGL((k_fdrp_fill<64>), dim3((unsigned)nb_rows), dim3(HET_WG), 0, s, a);
   else hipLaunchKernelGGL((k_fdrp_fill<16>), dim3((unsigned)nb_rows), dim3(HET_WG), 0, s, a);
@@ -352,20 +347,17 @@ static int fdrp_report(epi_batch *b, const char *ctx, int W, int m, int min_over
   // (d) the rows of a site, in ascending row index
   uint32_t bytes = 0;
   for (int d = 0; d < 4; d++) if ((N - 1) >> (8 * d)) bytes |= 1u << d;
-  int cur = 0;
-  EPI_TRY(radix_sort_pairs(key, row, (uint32_t)nc, bytes, reinterpret_cast<uint32_t *>(fp + o_table), reinterpret_cast<uint32_t *>(fp + o_off),
-                           b->scan_tmp, s, &cur));
-  t.fdrp_rows = row[cur];
+  EPI_TRY(sort.sort(bytes, b->scan_tmp, s));
   uint32_t *site_off = t.fsite.as<uint32_t>(), *site_end = site_off + N;
   EPI_HIP(hipMemsetAsync(site_off, 0, N * 8, s));
   prof_begin("fdrp_bounds", s);
-  hipLaunchKernelGGL(k_fdrp_bounds, dim3((unsigned)nb_pairs), dim3(HET_WG), 0, s, key[cur], (uint32_t)nc, (uint32_t)N, site_off, site_end);
+  hipLaunchKernelGGL(k_fdrp_bounds, dim3((unsigned)nb_pairs), dim3(HET_WG), 0, s, sort.keys(), (uint32_t)nc, (uint32_t)N, site_off, site_end);
   prof_end("fdrp_bounds", s);
 
   // (e) the pairs of every site
   FdrpPairArgs p;
   p.key = t.key.as<unsigned long long>(); p.n1 = &sc->nplus; p.N = (uint32_t)N;
-  p.site_off = site_off; p.site_end = site_end; p.rows = row[cur];
+  p.site_off = site_off; p.site_end = site_end; p.rows = sort.vals();
   p.row_lo = a.row_lo; p.row_ns = a.row_ns; p.word_off = word_off;
   p.valid = a.valid; p.meth = a.meth;
   p.out = t.counts.as<FdrpSite>();

@@ -5,21 +5,14 @@
 //           [0, 1]; NaN: ~0, behind everything), its value the row.  The same pass ORs the range flag, counts the valid
 //           rows (one add per wave) and fills the histograms of all eight key bytes (per workgroup in LDS, then one add per
 //           occupied bin); k_padj_plan marks the bytes in which every key agrees: their passes are skipped.
-//  Sort     least significant byte first, per byte that is left: k_padj_hist (a workgroup's tile of 4096 keys -> its column of
-//           the [digit][workgroup] table), util.hip's scan over the table, k_padj_sort_scatter.  The scatter is STABLE: a
-//           wave owns 1024 consecutive keys of the tile and takes them 64 at a time; a key's rank among the wave's equal
-//           digits is the wave's running count of that digit (one lane per digit stores it, plain LDS stores) plus the
-//           number of lower lanes of the match mask (eight ballots).  No rank comes from what an LDS atomic returns.  The
-//           tile is put into digit order in LDS (keys, then rows, in one 32 KB buffer) and stored from there, so that a
-//           wave's stores run along the digits' runs instead of 64 ways apart.  The per-byte launch sequence is
-//           radix_sort_pairs (common.hpp), which the FDRP report's site -> rows index (fdrp.hip) calls as well.
+//  Sort     least significant byte first, per byte that is left: radix_sort.hip's stable LSD sort, in a SortPairs workspace
+//           (radix_sort.hpp) that is one piece of the call's arena.
 //  Terms   k_padj_terms: t_r of the method, in the header's operation order, from the sorted keys; then a device-wide
 //           inclusive scan of doubles under min or max (k_dscan_reduce, k_dscan_carry, k_dscan_apply: reduce-then-scan as
 //           util.hip's three launches; min and max are exact and associative, so no launch shape enters a result), walking
 //           the ranks downwards for the suffix minimum.
 //  Scatter  k_padj_scatter: q[order[r]] = min(1, t_r), NaN for the ranks of the NaN rows; order[r] to the caller.
-#include <string.h>
-#include "common.hpp"
+#include "radix_sort.hpp"
 
 namespace epi {
 
@@ -27,9 +20,6 @@ constexpr int PADJ_WG = 256;
 constexpr int PADJ_WAVES = PADJ_WG / 64;
 constexpr int PADJ_KEY_ITEMS = 8;                              // rows per thread of k_padj_keys
 constexpr int PADJ_KEY_TILE = PADJ_WG * PADJ_KEY_ITEMS;
-constexpr int PADJ_SORT_ITEMS = 16;                            // keys per thread of a sorting pass
-constexpr int PADJ_WAVE_KEYS = 64 * PADJ_SORT_ITEMS;           // consecutive keys a wave owns
-constexpr int PADJ_SORT_TILE = PADJ_WG * PADJ_SORT_ITEMS;      // 4096 keys per workgroup
 constexpr int DSCAN_ITEMS = 4;                                 // consecutive terms per thread of the double scan
 constexpr int DSCAN_BLOCK = PADJ_WG * DSCAN_ITEMS;
 constexpr uint64_t PADJ_NAN_KEY = ~0ull;
@@ -43,17 +33,6 @@ struct PadjScalars {                   // 64 bytes in front of the eight global 
 static_assert(sizeof(PadjScalars) == 64, "PadjScalars layout");
 
 // ---- keys ----------------------------------------------------------------------------------------------------------------
-
-// one LDS add per lane, or one per wave when every active lane holds the same bin (the exponent bytes of a p-value column)
-__device__ __forceinline__ void hist_add(uint32_t *hist, uint32_t bin, bool active, uint64_t amask) {
-  if (amask == 0) return;                                                     // (uniform)
-  const uint32_t first = (uint32_t)__builtin_amdgcn_readlane((int)bin, __ffsll((unsigned long long)amask) - 1);
-  if (__all(!active || bin == first)) {
-    if ((threadIdx.x & 63) == 0) atomicAdd(&hist[first], (uint32_t)__popcll(amask));
-  } else if (active) {
-    atomicAdd(&hist[bin], 1u);
-  }
-}
 
 __global__ __launch_bounds__(PADJ_WG) void k_padj_keys(const double *__restrict__ p, uint32_t n, uint64_t *__restrict__ key,
                                                        uint32_t *__restrict__ row, PadjScalars *__restrict__ sc,
@@ -103,141 +82,6 @@ __global__ __launch_bounds__(PADJ_WG) void k_padj_plan(const uint32_t *__restric
     const int occupied = __syncthreads_count(ghist[d * 256 + threadIdx.x] != 0u);
     if (threadIdx.x == 0) sc->skip[d] = occupied <= 1 ? 1u : 0u;
   }
-}
-
-// ---- one pass of the sort --------------------------------------------------------------------------------------------------
-
-// table[digit * nblk + workgroup] = keys of the workgroup's tile with that digit
-__global__ __launch_bounds__(PADJ_WG) void k_padj_hist(const uint64_t *__restrict__ key, uint32_t n, int shift, uint32_t nblk,
-                                                       uint32_t *__restrict__ table) {
-  __shared__ uint32_t s_hist[256];
-  s_hist[threadIdx.x] = 0;
-  __syncthreads();
-  const uint32_t base = blockIdx.x * (uint32_t)PADJ_SORT_TILE + (threadIdx.x >> 6) * (uint32_t)PADJ_WAVE_KEYS + (threadIdx.x & 63);
-#pragma unroll
-  for (int i = 0; i < PADJ_SORT_ITEMS; i++) {
-    const uint32_t r = base + (uint32_t)i * 64u;
-    const bool active = r < n;
-    const uint32_t d = active ? (uint32_t)(key[r] >> shift) & 255u : 0u;
-    hist_add(s_hist, d, active, __ballot(active));
-  }
-  __syncthreads();
-  table[(size_t)threadIdx.x * nblk + blockIdx.x] = s_hist[threadIdx.x];
-}
-
-// off[digit * nblk + workgroup]: the exclusive scan of the table = where the workgroup's first key of that digit goes
-__global__ __launch_bounds__(PADJ_WG) void k_padj_sort_scatter(const uint64_t *__restrict__ key_in, const uint32_t *__restrict__ row_in,
-                                                               uint32_t n, int shift, uint32_t nblk, const uint32_t *__restrict__ off,
-                                                               uint64_t *__restrict__ key_out, uint32_t *__restrict__ row_out) {
-  __shared__ uint32_t s_cnt[PADJ_WAVES][256];       // per wave: keys of a digit seen so far; then: where in the tile its next key of the digit goes
-  __shared__ uint64_t s_stage[PADJ_SORT_TILE];      // the tile's keys in digit order; then, as u32, its rows
-  __shared__ uint32_t s_goff[256], s_wsum[PADJ_WAVES];
-  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int w = 0; w < PADJ_WAVES; w++) s_cnt[w][threadIdx.x] = 0;
-  __syncthreads();
-  const uint32_t base = blockIdx.x * (uint32_t)PADJ_SORT_TILE + wave * (uint32_t)PADJ_WAVE_KEYS + lane;
-  const uint64_t below = (1ull << lane) - 1ull;
-  uint64_t k[PADJ_SORT_ITEMS];
-  uint32_t v[PADJ_SORT_ITEMS], rank[PADJ_SORT_ITEMS];
-#pragma unroll
-  for (int i = 0; i < PADJ_SORT_ITEMS; i++) {
-    const uint32_t r = base + (uint32_t)i * 64u;
-    const bool active = r < n;
-    k[i] = active ? key_in[r] : 0ull;
-    v[i] = active ? row_in[r] : 0u;
-  }
-#pragma unroll
-  for (int i = 0; i < PADJ_SORT_ITEMS; i++) {
-    const bool active = base + (uint32_t)i * 64u < n;
-    const uint32_t d = (uint32_t)(k[i] >> shift) & 255u;
-    uint64_t same = __ballot(active);                                         // the active lanes that hold this lane's digit
-#pragma unroll
-    for (int b = 0; b < 8; b++) {
-      const bool bit = (d >> b) & 1u;
-      const uint64_t bal = __ballot(bit);
-      same &= bit ? bal : ~bal;
-    }
-    const uint32_t seen = s_cnt[wave][d];
-    rank[i] = seen + (uint32_t)__popcll(same & below);
-    __builtin_amdgcn_wave_barrier();                                          // every lane has read before one lane per digit writes
-    if (active && (same >> lane) == 1ull) s_cnt[wave][d] = rank[i] + 1u;      // the highest lane of the set: seen + |set|
-    __builtin_amdgcn_wave_barrier();
-  }
-  __syncthreads();
-  {                                                 // thread = digit: where the tile's run of the digit starts, the waves' shares in wave order
-    const uint32_t d = threadIdx.x;
-    uint32_t c[PADJ_WAVES], total = 0;
-    for (int w = 0; w < PADJ_WAVES; w++) { c[w] = s_cnt[w][d]; total += c[w]; }
-    const uint32_t inc = wave_scan_u32(total);
-    if (lane == 63) s_wsum[wave] = inc;
-    __syncthreads();
-    uint32_t start = inc - total;
-    for (uint32_t w = 0; w < wave; w++) start += s_wsum[w];
-    s_goff[d] = off[(size_t)d * nblk + blockIdx.x] - start;                   // (mod 2^32) + a key's place in the tile = its place in the output
-    uint32_t at = start;
-    for (int w = 0; w < PADJ_WAVES; w++) { s_cnt[w][d] = at; at += c[w]; }
-  }
-  __syncthreads();
-  // the tile in digit order through LDS, so that a wave's stores run along the digits' runs: first the keys, then the rows
-#pragma unroll
-  for (int i = 0; i < PADJ_SORT_ITEMS; i++) {
-    const bool active = base + (uint32_t)i * 64u < n;
-    rank[i] += s_cnt[wave][(uint32_t)(k[i] >> shift) & 255u];                 // the key's place in the tile
-    if (active && rank[i] < (uint32_t)PADJ_SORT_TILE) s_stage[rank[i]] = k[i];
-  }
-  __syncthreads();
-  const uint32_t tile0 = blockIdx.x * (uint32_t)PADJ_SORT_TILE;
-  const uint32_t count = n - tile0 < (uint32_t)PADJ_SORT_TILE ? n - tile0 : (uint32_t)PADJ_SORT_TILE;
-  uint32_t dst[PADJ_SORT_ITEMS];
-#pragma unroll
-  for (int i = 0; i < PADJ_SORT_ITEMS; i++) {
-    const uint32_t j = (uint32_t)i * PADJ_WG + threadIdx.x;
-    dst[i] = n;
-    if (j < count) {
-      const uint64_t kk = s_stage[j];
-      dst[i] = s_goff[(uint32_t)(kk >> shift) & 255u] + j;
-      if (dst[i] < n) key_out[dst[i]] = kk;
-    }
-  }
-  __syncthreads();
-  uint32_t *s_rows = reinterpret_cast<uint32_t *>(s_stage);
-#pragma unroll
-  for (int i = 0; i < PADJ_SORT_ITEMS; i++) {
-    const bool active = base + (uint32_t)i * 64u < n;
-    if (active && rank[i] < (uint32_t)PADJ_SORT_TILE) s_rows[rank[i]] = v[i];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < PADJ_SORT_ITEMS; i++) {
-    const uint32_t j = (uint32_t)i * PADJ_WG + threadIdx.x;
-    if (j < count && dst[i] < n) row_out[dst[i]] = s_rows[j];
-  }
-}
-
-int64_t radix_sort_blocks(int64_t n) { return (n + PADJ_SORT_TILE - 1) / PADJ_SORT_TILE; }
-
-int radix_sort_pairs(uint64_t *const key[2], uint32_t *const row[2], uint32_t n, uint32_t bytes, uint32_t *table, uint32_t *off,
-                     DevBuf &scan_tmp, hipStream_t s, int *cur_out) {
-  const int64_t nblk = radix_sort_blocks((int64_t)n);
-  int cur = 0;
-  for (int d = 0; d < 8; d++) {
-    if (!((bytes >> d) & 1u)) continue;
-    prof_begin("padj_hist", s);
-    hipLaunchKernelGGL(k_padj_hist, dim3((unsigned)nblk), dim3(PADJ_WG), 0, s, key[cur], n, 8 * d, (uint32_t)nblk, table);
-    prof_end("padj_hist", s);
-    prof_begin("padj_table_scan", s);
-    const int rc = scan_exclusive_u32(table, off, nblk * 256, nullptr, scan_tmp, s);
-    prof_end("padj_table_scan", s);
-    EPI_TRY(rc);
-    prof_begin("padj_sort_scatter", s);
-    hipLaunchKernelGGL(k_padj_sort_scatter, dim3((unsigned)nblk), dim3(PADJ_WG), 0, s, key[cur], row[cur], n, 8 * d, (uint32_t)nblk,
-                       off, key[cur ^ 1], row[cur ^ 1]);
-    prof_end("padj_sort_scatter", s);
-    cur ^= 1;
-  }
-  EPI_HIP(hipGetLastError());
-  *cur_out = cur;
-  return EPI_OK;
 }
 
 // ---- terms -----------------------------------------------------------------------------------------------------------------
@@ -398,32 +242,26 @@ static int p_adjust(epi_engine *e, const double *d_p, int64_t n, int32_t method,
                     hipStream_t s, int64_t *nvalid_out) {
   const char *who = "epi_p_adjust_dev";
   const uint32_t un = (uint32_t)n;
-  const int64_t nblk_key = (n + PADJ_KEY_TILE - 1) / PADJ_KEY_TILE, nblk_sort = (n + PADJ_SORT_TILE - 1) / PADJ_SORT_TILE;
-  const int64_t nblk_row = (n + PADJ_WG - 1) / PADJ_WG, nblk_scan = (nblk_sort * 256 + 4095) / 4096, nblk_dscan = (n + DSCAN_BLOCK - 1) / DSCAN_BLOCK;
+  const int64_t nblk_key = (n + PADJ_KEY_TILE - 1) / PADJ_KEY_TILE, nblk_row = (n + PADJ_WG - 1) / PADJ_WG;
+  const int64_t nblk_scan = ((int64_t)SortPairs::table_words((size_t)n) + 4095) / 4096, nblk_dscan = (n + DSCAN_BLOCK - 1) / DSCAN_BLOCK;
   EPI_TRY(check_grid(nblk_row, PADJ_WG, "p-value adjustment kernels"));
   PadjScratch w;
-  const size_t o_scal = w.reserve(sizeof(PadjScalars) + 8 * 256 * 4);
-  const size_t o_key[2] = {w.reserve((size_t)n * 8), w.reserve((size_t)n * 8)}, o_row[2] = {w.reserve((size_t)n * 4), w.reserve((size_t)n * 4)};
-  const size_t o_terms = w.reserve((size_t)n * 8), o_table = w.reserve((size_t)nblk_sort * 256 * 4), o_off = w.reserve((size_t)nblk_sort * 256 * 4);
-  const size_t o_scan = w.reserve((size_t)nblk_scan * 4), o_agg = w.reserve((size_t)nblk_dscan * 8);
+  const size_t o_scal = w.reserve(sizeof(PadjScalars) + 8 * 256 * 4), o_sort = w.reserve(SortPairs::bytes((size_t)n));
+  const size_t o_terms = w.reserve((size_t)n * 8), o_scan = w.reserve((size_t)nblk_scan * 4), o_agg = w.reserve((size_t)nblk_dscan * 8);
   EPI_TRY(w.arena.ensure(w.used));
-  uint64_t *const key[2] = {w.at<uint64_t>(o_key[0]), w.at<uint64_t>(o_key[1])};
-  uint32_t *const row[2] = {w.at<uint32_t>(o_row[0]), w.at<uint32_t>(o_row[1])};
+  SortPairs sort(w.at<void>(o_sort), (size_t)n);
   double *const terms = w.at<double>(o_terms);
-  uint32_t *const table = w.at<uint32_t>(o_table), *const off = w.at<uint32_t>(o_off);
   DevBuf scan_tmp = DevBuf::view(w.at<void>(o_scan), (size_t)nblk_scan * 4), agg = DevBuf::view(w.at<void>(o_agg), (size_t)nblk_dscan * 8);
   PadjScalars *sc = w.at<PadjScalars>(o_scal);
   uint32_t *ghist = reinterpret_cast<uint32_t *>(sc + 1);
   EPI_HIP(hipMemsetAsync(sc, 0, sizeof(PadjScalars) + 8 * 256 * 4, s));
   prof_begin("padj_keys", s);
-  hipLaunchKernelGGL(k_padj_keys, dim3((unsigned)nblk_key), dim3(PADJ_WG), 0, s, d_p, un, key[0], row[0], sc, ghist);
+  hipLaunchKernelGGL(k_padj_keys, dim3((unsigned)nblk_key), dim3(PADJ_WG), 0, s, d_p, un, sort.keys_in(), sort.vals_in(), sc, ghist);
   hipLaunchKernelGGL(k_padj_plan, dim3(1), dim3(PADJ_WG), 0, s, ghist, sc);
   prof_end("padj_keys", s);
   EPI_HIP(hipGetLastError());
   PadjScalars h;
-  EPI_HIP(hipMemcpyAsync(e->h_scalars, sc, sizeof(PadjScalars), hipMemcpyDeviceToHost, s));
-  EPI_HIP(hipStreamSynchronize(s));
-  memcpy(&h, e->h_scalars, sizeof(PadjScalars));
+  EPI_TRY(read_scalars(e, s, sc, sizeof(PadjScalars), &h));
   if (h.bad) return fail(EPI_ERR_ARG, "%s: a p-value is neither NA nor in [0, 1]", who);
   const int64_t m = h.nvalid;
   *nvalid_out = m;
@@ -432,8 +270,7 @@ static int p_adjust(epi_engine *e, const double *d_p, int64_t n, int32_t method,
 
   uint32_t bytes = 0;
   for (int d = 0; d < 8; d++) if (!h.skip[d]) bytes |= 1u << d;
-  int cur = 0;
-  EPI_TRY(radix_sort_pairs(key, row, un, bytes, table, off, scan_tmp, s, &cur));
+  EPI_TRY(sort.sort(bytes, scan_tmp, s));
 
   const uint32_t um = (uint32_t)m;
   if (m > 0) {
@@ -442,7 +279,7 @@ static int p_adjust(epi_engine *e, const double *d_p, int64_t n, int32_t method,
     if (method == EPI_PADJ_BY)
       for (int64_t k = 1; k <= N; k++) a.c += 1.0 / (double)k;
     prof_begin("padj_terms", s);
-    hipLaunchKernelGGL(k_padj_terms, dim3((um + PADJ_WG - 1) / PADJ_WG), dim3(PADJ_WG), 0, s, key[cur], a, terms);
+    hipLaunchKernelGGL(k_padj_terms, dim3((um + PADJ_WG - 1) / PADJ_WG), dim3(PADJ_WG), 0, s, sort.keys(), a, terms);
     prof_end("padj_terms", s);
     int rc = EPI_OK;
     prof_begin("padj_dscan", s);
@@ -453,7 +290,7 @@ static int p_adjust(epi_engine *e, const double *d_p, int64_t n, int32_t method,
     EPI_TRY(rc);
   }
   prof_begin("padj_scatter", s);
-  hipLaunchKernelGGL(k_padj_scatter, dim3((unsigned)nblk_row), dim3(PADJ_WG), 0, s, row[cur], terms, un, um, d_q, d_order);
+  hipLaunchKernelGGL(k_padj_scatter, dim3((unsigned)nblk_row), dim3(PADJ_WG), 0, s, sort.vals(), terms, un, um, d_q, d_order);
   prof_end("padj_scatter", s);
   EPI_HIP(hipGetLastError());
   EPI_HIP(hipStreamSynchronize(s));                           // (the scratch goes back when this returns)

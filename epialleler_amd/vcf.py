@@ -15,7 +15,7 @@ import numpy as np
 
 from . import _lib
 from .api import CONTEXT_TO_BASES, Report, _CTX_CHOICES, _as_bam, _deliver, _fetch_table, _match_arg, _pass_tensor, _ptr_array, \
-    _stream, _table_to_host, _whole_number, preprocessBam, rcpp_threshold_reads, writeReport
+    _stream, _table_cols, _table_to_host, _whole_number, preprocessBam, rcpp_threshold_reads, writeReport
 from .bed import Bed, readBed
 
 NA_INTEGER = -2 ** 31
@@ -315,8 +315,7 @@ def rcpp_asm_report(df, site_chr, site_pos, site_alleles, ctx, max_distance, min
     idx = idx[np.lexsort((pos[idx], chr_[idx]))]                 # (code, pos), stable
     m = int(idx.size)
     d_sites = [torch.from_numpy(a[idx]).to(dev) for a in (chr_, pos, masks)]
-    icols = list(torch.empty((10, m), dtype=torch.int32, device=dev).unbind(0))
-    dcols = list(torch.empty((4, m), dtype=torch.float64, device=dev).unbind(0))
+    icols, dcols = _table_cols(10, 4, m, dev)
     npair = C.c_int64(0)
     _lib.check(lib.epi_batch_asm_report_dev(b, *[C.c_void_p(t.data_ptr()) if m else None for t in d_sites], m, _lib.enc(ctx),
                                             int(max_distance), int(min_coverage), float(max_ooctx_meth_frac),

@@ -3,7 +3,7 @@ same batch in the same process -- the driver of profiles/fdrp_report.txt.
     python scratch/fdrp_profile.py cfg2 [rows]   the synthetic batch of bench.py's cfg2 (uniform starts, L = 300)
     python scratch/fdrp_profile.py deep          10^6 rows of 250 bytes on 25 sites
 Each: the whole call (median [min, max] of 9 repeats after one untimed call, stream synchronised, as_device) and every
-kernel of the call from HIP events around its launches (epi_prof; the sort's three kernels carry p_adjust.hip's labels and
+kernel of the call from HIP events around its launches (epi_prof; the sort's three kernels carry radix_sort.hip's labels and
 are summed over the passes), CG, the defaults (flank_sites 8, max_reads 40) and flank_sites 0 and 31, max_reads 64."""
 import ctypes as C
 import os
@@ -16,7 +16,7 @@ sys.path[:0] = [HERE]
 from heterogeneity_profile import deep_bam, ea, kernel_ms, lib, synth, timed  # noqa: E402
 
 sys.argv = argv
-LABELS = ("fdrp_mark", "fdrp_fill", "padj_hist", "padj_table_scan", "padj_sort_scatter", "fdrp_bounds", "fdrp_pairs", "fdrp_emit")
+LABELS = ("fdrp_mark", "fdrp_fill", "rsort_hist", "rsort_table_scan", "rsort_scatter", "fdrp_bounds", "fdrp_pairs", "fdrp_emit")
 
 
 def kernels_ms(fn, reps):

@@ -4,8 +4,8 @@ of the same device column -- the driver of profiles/p_adjust.txt.
     python scratch/p_adjust_profile.py [rows]     the pair of cx_compare_profile.py (2 x rows, 7.0 M table rows at the default)
 The two device paths are timed against each other in rounds of alternating order, 9 rounds after one untimed round, then the
 host path 9 times: median [min, max], stream synchronised.
-Kernels from the epi_prof labels "padj_keys" (keys + plan), "padj_hist", "padj_table_scan", "padj_sort_scatter" (each summed
-over the digit passes), "padj_terms", "padj_dscan", "padj_scatter"; 9 calls."""
+Kernels from the epi_prof labels "padj_keys" (keys + plan), "rsort_hist", "rsort_table_scan", "rsort_scatter" (radix_sort.hip; each
+summed over the digit passes), "padj_terms", "padj_dscan", "padj_scatter"; 9 calls."""
 import os
 import statistics
 import sys
@@ -72,7 +72,7 @@ if __name__ == "__main__":
     same = np.array_equal(q_dev.cpu().numpy().view(np.uint64), q_host.view(np.uint64))
     print("  device q against the restatement, bit for bit over %d rows: %s" % (n, "equal" if same else "DIFFERENT"))
     assert same
-    labels = ("padj_keys", "padj_hist", "padj_table_scan", "padj_sort_scatter", "padj_terms", "padj_dscan", "padj_scatter")
+    labels = ("padj_keys", "rsort_hist", "rsort_table_scan", "rsort_scatter", "padj_terms", "padj_dscan", "padj_scatter")
     for label in labels:
         print("  ... %-54s%s" % (label, kernel_ms(device, label, 9)))
     sys.stdout.flush()
@@ -95,5 +95,5 @@ if __name__ == "__main__":
             if rnd:
                 tu[i].append(ms)
     print("  uniform random column of %d rows (%d passes): adjustPValues %s; torch.sort(stable=True) %s" % (n, P.digit_passes(u.cpu().numpy()), fmt(tu[0]), fmt(tu[1])))
-    for label in ("padj_keys", "padj_hist", "padj_sort_scatter"):
+    for label in ("padj_keys", "rsort_hist", "rsort_scatter"):
         print("  ... %-54s%s" % (label, kernel_ms(fu, label, 9)))
