@@ -11,8 +11,8 @@
 //              seq_nt16_int, 0 .. 3): bits 0-3 REF on '+' rows, 4-7 ALT on '+', 8-11 REF on '-', 12-15 ALT on '-'.  A zero
 //              mask: the strand cannot tell the alleles apart.  A bit above 15, or REF and ALT of one strand sharing a bit,
 //              is an error.
-//  Kept rows   row x is kept by the lMHL read rule with hmin = 0 over the whole row (rcpp_mhl_report.cpp:172-179; the rule
-//              of het_common.hpp): o_m / (o_m + o_u) > max_oo drops it, o_m / o_u = its methylated (codes 2, 5, 6, 7) /
+//  Kept rows   row x is kept by the lMHL read rule with hmin = 0 over the whole row (rcpp_mhl_report.cpp:172-179; the verdict
+//              of xm_codes.hpp): o_m / (o_m + o_u) > max_oo drops it, o_m / o_u = its methylated (codes 2, 5, 6, 7) /
 //              unmethylated (10, 13, 14, 15) bytes whose code is not one of ctx's; 0 / 0 is NaN and keeps the row.  Its
 //              strand must be 1 or 2, its length positive, its rname not NA.
 //  Allele      a kept row x COVERS site s when rname[x] == site_chr[s] and start[x] <= site_pos[s] <= start[x] + len[x] - 1
@@ -94,34 +94,19 @@ static_assert(sizeof(AsmScalars) == 32 && offsetof(AsmScalars, cursor) == 16, "A
 
 // LUT byte of a code: bit 0 one of ctx's, bit 1 ... and methylated, bit 2 / 3 out-of-context methylated / unmethylated
 static ClassLut asm_make_lut(uint32_t ctx_mask) {
-  const uint32_t meth = (1u << 2) | (1u << 5) | (1u << 6) | (1u << 7), unmeth = (1u << 10) | (1u << 13) | (1u << 14) | (1u << 15);
-  uint32_t w[4] = {0, 0, 0, 0};
+  uint8_t f[16];
   for (uint32_t c = 0; c < 16; c++) {
-    uint32_t v = 0;
-    if ((ctx_mask >> c) & 1u) v |= 1u | (c < 8u ? 2u : 0u);
-    else v |= ((meth >> c) & 1u ? 4u : 0u) | ((unmeth >> c) & 1u ? 8u : 0u);
-    w[c >> 2] |= v << (8 * (c & 3u));
+    if ((ctx_mask >> c) & 1u) f[c] = 1u | (c < 8u ? 2u : 0u);
+    else f[c] = ((kXmMethMask >> c) & 1u ? 4u : 0u) | ((kXmUnmethMask >> c) & 1u ? 8u : 0u);
   }
-  ClassLut l;
-  l.lo0 = w[0]; l.lo1 = w[1]; l.hi0 = w[2]; l.hi1 = w[3];
-  return l;
+  return lut16_pack(f);
 }
-
-// the LUT bytes of the four codes (low nibbles) of a dword: codes 0-7 and 8-15 by one v_perm_b32 each, a third picks per byte
-__device__ __forceinline__ uint32_t asm_lut4(uint32_t w, const ClassLut &F) {
-  const uint32_t lo3 = w & 0x07070707u;
-  const uint32_t pick = ((w >> 1) & 0x04040404u) | 0x03020100u;
-  return __builtin_amdgcn_perm(__builtin_amdgcn_perm(F.hi1, F.hi0, lo3), __builtin_amdgcn_perm(F.lo1, F.lo0, lo3), pick);
-}
-
-// bit `bit` of the four LUT bytes of r as a 4-bit mask (byte j -> bit j): the products' bits do not meet, nothing carries
-__device__ __forceinline__ uint32_t asm_gather4(uint32_t r, int bit) { return (((r >> bit) & 0x01010101u) * 0x01020408u) >> 24; }
 
 // 16 bytes from p, of which the first `avail` belong to the row; the rest read as '.' (code 12: in no class)
 __device__ __forceinline__ uint4 asm_load16(const uint8_t *__restrict__ p, int64_t avail) {
   uint4 w;
   if (avail >= 16) { memcpy(&w, p, 16); return w; }
-  uint64_t lo = 0x0C0C0C0C0C0C0C0Cull, hi = lo;
+  uint64_t lo = ((uint64_t)kXmDot4 << 32) | kXmDot4, hi = lo;
   for (int j = 0; j < (int)avail; j++) {
     const uint64_t v = p[j];
     if (j < 8) lo = (lo & ~(0xFFull << (8 * j))) | (v << (8 * j));
@@ -153,14 +138,13 @@ __global__ __launch_bounds__(ASM_WG) void k_asm_rows(const uint8_t *__restrict__
   uint32_t om = 0, ou = 0;
   for (int64_t c = (int64_t)sub * 16; c < l; c += 256) {
     const uint4 w = asm_load16(p + c, (int64_t)l - c);
-    const uint32_t r0 = asm_lut4(w.x, F), r1 = asm_lut4(w.y, F), r2 = asm_lut4(w.z, F), r3 = asm_lut4(w.w, F);
+    const uint32_t r0 = lut16_pick(w.x, F), r1 = lut16_pick(w.y, F), r2 = lut16_pick(w.z, F), r3 = lut16_pick(w.w, F);
     om += (uint32_t)(__popc(r0 & 0x04040404u) + __popc(r1 & 0x04040404u) + __popc(r2 & 0x04040404u) + __popc(r3 & 0x04040404u));
     ou += (uint32_t)(__popc(r0 & 0x08080808u) + __popc(r1 & 0x08080808u) + __popc(r2 & 0x08080808u) + __popc(r3 & 0x08080808u));
   }
 #pragma unroll
   for (int d = 1; d < 16; d <<= 1) { om += __shfl_xor(om, d, 64); ou += __shfl_xor(ou, d, 64); }
-  const double frac = (double)om / (double)((uint64_t)om + ou);         // rcpp_mhl_report.cpp:178 (0 / 0 = NaN: kept)
-  if (have && sub == 0) keep[row] = l > 0 && !(frac > max_oo) ? 1 : 0;
+  if (have && sub == 0) keep[row] = read_rule_keeps(l, om, ou, max_oo) ? 1 : 0;
 }
 
 struct AsmArgs {
@@ -324,8 +308,8 @@ __global__ __launch_bounds__(ASM_WG) void k_asm_walk(AsmArgs a) {
         const uint32_t m0 = e0 <= 0 ? 0u : e0 >= 16 ? 16u : (uint32_t)e0, m1 = e1 <= 0 ? 0u : e1 >= 16 ? 16u : (uint32_t)e1;
         uint32_t rm = ((1u << m1) - 1u) & ~((1u << m0) - 1u);
         if (es >= 0 && es < 16) rm &= ~(1u << (uint32_t)es);              // q != site_pos
-        const uint32_t r0 = asm_lut4(w.x, a.lut), r1 = asm_lut4(w.y, a.lut), r2 = asm_lut4(w.z, a.lut), r3 = asm_lut4(w.w, a.lut);
-        elig = (asm_gather4(r0, 0) | (asm_gather4(r1, 0) << 4) | (asm_gather4(r2, 0) << 8) | (asm_gather4(r3, 0) << 12)) & rm;
+        const uint32_t r0 = lut16_pick(w.x, a.lut), r1 = lut16_pick(w.y, a.lut), r2 = lut16_pick(w.z, a.lut), r3 = lut16_pick(w.w, a.lut);
+        elig = (plane_nibble_mul(r0, 0) | (plane_nibble_mul(r1, 0) << 4) | (plane_nibble_mul(r2, 0) << 8) | (plane_nibble_mul(r3, 0) << 12)) & rm;
       }
       const uint32_t ne = (uint32_t)__popc(elig);
       if (!EMIT) {

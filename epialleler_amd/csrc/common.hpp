@@ -8,6 +8,7 @@
 #include <memory>
 #include <vector>
 #include "../../include/epihip.h"
+#include "xm_codes.hpp"
 
 namespace epi {
 
@@ -109,56 +110,41 @@ struct SiteScalars {
 static_assert(sizeof(SiteScalars) == 32 && offsetof(SiteScalars, ncalls) == 24, "SiteScalars layout");
 
 // What the heterogeneity report (heterogeneity.hip), the linkage report and its blocks (linkage.hip), the heterogeneity
-// comparison (het_compare.hip, on its first batch) and the FDRP report (fdrp.hip) keep on a batch: the site table, the counters over it, which rows are
-// reported and where, and the arguments of the last report that its fetch needs.  het_common.hpp has the data path.
+// comparison (het_compare.hip, on its first batch) and the FDRP report (fdrp.hip) keep on a batch, by owner: the site table
+// (site_table.hpp has its construction and the data path), the workspace over it that each of them reuses, and per report
+// what only its own fetch reads.  One of them is live on a batch at a time (last_kind).
 struct SiteReportState {
-  DevBuf cx;               // the site table in CX row order: the un-thresholded CX report's six columns, [6][nsite]
+  // the table (site_table.hip)
+  DevBuf cx;               // in CX row order: the un-thresholded CX report's six columns, [6][nsite]
   DevBuf rank;             // [nsite] '+' rows in front of a CX row
   DevBuf key, sctx;        // [nsite] the table split per strand: 64-bit search key and context code of a site
-  DevBuf counts;           // [nsite][2^k] pattern counters, or [nsite][D][4] pair counters
-  DevBuf flag, out;        // keep flag and output row: [nsite] per window start, [nsite][D] per pair
   DevBuf scal;             // SiteScalars
-  DevBuf back, blen, bmean;       // blocks, by table ordinal: leading linked pairs behind a site; length and mean r^2 at a block's first site
-  DevBuf bflag, bout;             // ... by CX row: a block starts here, its output row
-  DevBuf cx_all, counts_b;        // comparison: a's CX table before the common one is compacted from it; the counters of b's rows
-  // FDRP (fdrp.hip): the site -> rows index and the rows' packed calls
-  DevBuf frow;             // [6][n rows] u32: first site, sites, calls and words of a row; its first pair and first word (scans)
-  DevBuf fbits;            // [2][nwords] u64: the rows' calls, bit j of a row = its site lo + j: valid, then methylated
-  DevBuf fpair;            // the (site, row) pairs and the sort's scratch; sorted: rows of site g at [site_off[g], site_end[g])
-  DevBuf fsite;            // [2][nsite] u32 site_off, site_end
   int64_t nsite = 0;       // sites of the table the last report counted over (0: it reported nothing, no table is kept)
-  int32_t k = 0, D = 0;    // window size / neighbours of the last report
-  int32_t W = 0, max_rows = 0, min_overlap = 0;   // FDRP: flanking sites, rows used per site, overlap a pair needs
-  uint32_t min_reads = 1;
-  int64_t max_span = 0, max_dist = 0;
-  bool blocks = false;     // epi_batch_linkage_blocks_dev has run on the last linkage report ...
-  int64_t nblock = 0;      // ... and found this many
   SiteScalars *scalars() const { return scal.as<SiteScalars>(); }
+  // the workspace every report reuses
+  DevBuf counts;           // [nsite][2^k] pattern counters, [nsite][D][4] pair counters, or FDRP's [nsite] FdrpSite
+  DevBuf flag, out;        // keep flag and output row: [nsite] per window start or site, [nsite][D] per pair
+  uint32_t min_reads = 1;  // the last report's floor: each report writes its own and its keep kernel and fetch read it back
+  struct Het { int32_t k = 0; int64_t max_span = 0; } het;   // heterogeneity report and the comparison's windows: their size, the span cap
+  struct Link {            // linkage report and its blocks
+    int32_t D = 0; int64_t max_dist = 0;   // neighbours, the distance cap
+    bool blocks = false;   // epi_batch_linkage_blocks_dev has run on the last linkage report ...
+    int64_t nblock = 0;    // ... and found this many
+    DevBuf back, blen, bmean;     // blocks, by table ordinal: leading linked pairs behind a site; length and mean r^2 at a block's first site
+    DevBuf bflag, bout;           // ... by CX row: a block starts here, its output row
+  } link;
+  struct Cmp { DevBuf cx_all, counts_b; } cmp;   // comparison: a's CX table before the common one is compacted from it; the counters of b's rows
+  struct Fdrp {            // FDRP report: the site -> rows index and the rows' packed calls
+    int32_t W = 0, max_rows = 0, min_overlap = 0;   // flanking sites, rows used per site, overlap a pair needs
+    DevBuf frow;           // [6][n rows] u32: first site, sites, calls and words of a row; its first pair and first word (scans)
+    DevBuf fbits;          // [2][nwords] u64: the rows' calls, bit j of a row = its site lo + j: valid, then methylated
+    DevBuf fpair;          // the (site, row) pairs and the sort's scratch; sorted: rows of site g at [site_off[g], site_end[g])
+    DevBuf fsite;          // [2][nsite] u32 site_off, site_end
+  } fdrp;
 };
 
 // ---- per-read class counting shared by the per-read kernels and the fused CX tile kernel (per_read.hip) ----------
-struct ClassLut { uint32_t lo0, lo1, hi0, hi1; };   // one byte per code: codes 0-3, 4-7, 8-11, 12-15
-
-// The same table in the form two v_perm_b32 look up (lut16x in tile_common.hpp).  With a selector byte s, v_perm_b32 returns
-// byte s of its eight source bytes for s < 8, the sign of source byte 1 / 3 / 5 / 7 spread over the byte for s = 8 .. 11,
-// 0x00 for s = 12 and 0xFF for s >= 13.  So perm(low half, code) is the entry for codes 0 .. 7 and a constant per code
-// for 8 .. 15, perm(high half, code ^ 8) the other way round; the halves are stored XOR-ed with the constant the other
-// lookup returns, and the XOR of the two lookups is the entry for every code.
-inline ClassLut lut16_xor_form(const ClassLut &d) {
-  uint8_t D[16], L[8], H[8];
-  const uint32_t w[4] = {d.lo0, d.lo1, d.hi0, d.hi1};
-  for (int c = 0; c < 16; c++) D[c] = (uint8_t)(w[c >> 2] >> (8 * (c & 3)));
-  auto S = [](uint8_t x) { return (uint8_t)((x & 0x80u) ? 0xFFu : 0x00u); };
-  L[4] = D[4]; H[4] = D[12];
-  for (int j = 5; j < 8; j++) { L[j] = (uint8_t)~D[j]; H[j] = (uint8_t)~D[8 + j]; }
-  L[2] = D[2] ^ S(H[5]); L[3] = D[3] ^ S(H[7]); H[2] = D[10] ^ S(L[5]); H[3] = D[11] ^ S(L[7]);
-  L[1] = D[1] ^ S(H[3]); H[1] = D[9] ^ S(L[3]);
-  L[0] = D[0] ^ S(H[1]); H[0] = D[8] ^ S(L[1]);
-  auto pack = [](const uint8_t *b) { return (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16) | ((uint32_t)b[3] << 24); };
-  ClassLut x;
-  x.lo0 = pack(L); x.lo1 = pack(L + 4); x.hi0 = pack(H); x.hi1 = pack(H + 4);
-  return x;
-}
+// (ClassLut, the table the class strings become: xm_codes.hpp)
 struct ThrParams {                                   // rcpp_threshold_reads.cpp:15-23
   uint32_t min_n_ctx;
   double min_ctx_meth_frac, max_ooctx_meth_frac;
@@ -326,8 +312,8 @@ struct epi_batch {
   epi::ShardState shard;
   epi::PatternStats pat;
   epi::AsmState asmr;
-  // the heterogeneity report, the linkage report with its blocks and the heterogeneity comparison (het_common.hpp): the
-  // site table they count over and what the last of them left for its fetch; one of them is live on a batch at a time
+  // the heterogeneity report, the linkage report with its blocks, the heterogeneity comparison and the FDRP report: the
+  // site table they count over (site_table.hpp) and what the last of them left for its fetch
   epi::SiteReportState sites;
 
   // workspace every report shares
@@ -566,20 +552,11 @@ __host__ __device__ __forceinline__ uint64_t hash3(uint64_t seed, uint64_t strea
   return mix64(mix64(seed + stream * 0xD1B54A32D192ED03ull) ^ idx);
 }
 
-__host__ __device__ inline unsigned ctx_to_idx(unsigned char c) { return ((unsigned(c) + 2u) >> 2) & 15u; }   // src/epialleleR.h:28
-// the codes of a report's context string as a bit mask (rcpp_cx_report.cpp:88-91, rcpp_mhl_report.cpp:104-107)
-inline uint32_t ctx_mask_of(const char *ctx) {
-  uint32_t ctx_mask = 0;
-  for (const unsigned char *c = reinterpret_cast<const unsigned char *>(ctx); *c; c++) ctx_mask |= 1u << ctx_to_idx(*c);
-  return ctx_mask;
-}
-
 // A grid holds fewer than 2^32 threads (a larger one wraps silently): refuse instead.
 inline int check_grid(int64_t blocks, int threads, const char *what) {
   if (blocks < 0 || blocks > 0x7FFFFFFFLL || blocks * threads >= (1LL << 32))
     return fail(EPI_ERR_ARG, "%s: batch too large for one launch (%lld workgroups of %d threads)", what, (long long)blocks, threads);
   return EPI_OK;
 }
-
 
 }  // namespace epi

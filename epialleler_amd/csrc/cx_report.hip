@@ -143,13 +143,6 @@ template <int T, int NP, bool LEAN = false> struct Cx2Lds {
                                                  // (spill counts of 17 kernel shapes change, profiles/cx_host_refactor.txt)
 };
 
-// 16-entry byte LUT lookup of the four codes of a dword in two v_perm_b32 (X: the table in lut16_xor_form, common.hpp);
-// low8 = 0 or, for a lower-cased read, 0x08080808 (every byte takes the codes-8..15 half: c | 8, rcpp_cx_report.cpp:118,122)
-__device__ __forceinline__ uint32_t cx2_lut(uint32_t w, const ClassLut &X, uint32_t low8) {
-  const uint32_t sel = (w & 0x0F0F0F0Fu) | low8;
-  return __builtin_amdgcn_perm(X.lo1, X.lo0, sel) ^ __builtin_amdgcn_perm(X.hi1, X.hi0, sel ^ 0x08080808u);
-}
-
 template <int G>
 __device__ __forceinline__ uint32_t cx2_group_sum(uint32_t v) {     // over the G lanes of a row, every lane gets it
   v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, true);                  // quad_perm [1,0,3,2]
@@ -336,7 +329,7 @@ __device__ __forceinline__ void cx2_visit(const Cx2Args &a, Cx2Row &g, int32_t c
 #pragma unroll
     for (int u = 0; u < NU; u++) {
 #pragma unroll
-      for (int d = 0; d < 4; d++) w[u][d] = (EPI_CX_ABLATE & 4) ? w[u][d] : cx2_lut(w[u][d], a.lut_sx, 0u);
+      for (int d = 0; d < 4; d++) w[u][d] = (EPI_CX_ABLATE & 4) ? w[u][d] : lut16_xor(w[u][d], a.lut_sx, 0u);
       fl |= w[u][0] | w[u][1] | w[u][2] | w[u][3];
     }
     // The odd bits of a LUT byte are the flags of the skipped / doubled codes; they have to be masked off before three
@@ -441,7 +434,7 @@ __device__ __forceinline__ void cx2_visit(const Cx2Args &a, Cx2Row &g, int32_t c
         const bool inside = (uint32_t)(cb + u * G) < (uint32_t)C;
 #pragma unroll
         for (int d = 0; d < 4; d++) {
-          const uint32_t f = cx2_lut(w[u][d], a.lut_rx, pick0);
+          const uint32_t f = lut16_xor(w[u][d], a.lut_rx, pick0);
           const uint32_t sk = (f >> 6) & 0x01010101u, db = (f >> 7) & 0x01010101u;
           if ((sk | db) != 0u && inside) atomicAdd(cor + 4 * u * G + d, (unsigned long long)sk | ((unsigned long long)db << 32));
         }
@@ -456,7 +449,7 @@ __device__ __forceinline__ void cx2_visit(const Cx2Args &a, Cx2Row &g, int32_t c
       const bool inside = (uint32_t)(cb + u * G) < (uint32_t)C;      // (always: the visit stays inside the tile)
 #pragma unroll
       for (int d = 0; d < 4; d++) {
-        const uint32_t f = cx2_lut(w[u][d], a.lut_rx, pick0);
+        const uint32_t f = lut16_xor(w[u][d], a.lut_rx, pick0);
         w[u][d] = f;
         fl |= f;
 #pragma unroll
@@ -1261,11 +1254,6 @@ __global__ __launch_bounds__(256) void k_cx_gather(const Tile *__restrict__ tile
 // reach into two tiles, fuller rounds), 1024 with two or three contexts (their counters take 32 / 44 KiB).
 static int cx_tile_for(int np) { return np <= 1 ? CX_T1 : CXP_T; }
 
-// Lanes per row and 16-byte chunks per lane.  Whole rows (fused thresholding) must fit one visit of G * NU chunks
-// wherever they start inside their first chunk; so must the slice of a row inside a tile (at most T / 16 + 1 chunks).
-// The smallest G * NU that holds them wins: idle chunk slots cost the same VALU as used ones, and fewer lanes per row
-// are more rows per wavefront step (PE150: 20 chunks = 4 lanes x 5, against 8 x 3 = 24 slots).  Four to six chunks per
-// lane need ~80 VGPRs, which only the lean kernel's 256-thread workgroups have.  Returned as G * 8 + NU.
 // Lane shape (G lanes per row, NU chunks per lane) of the single-context tile kernels, as G * 8 + NU: the one with the least
 // expected work per row over the batch's length histogram (RowStats::len_hist).  A row of g * nu chunks or fewer is one visit
 // and costs ~ g * nu chunk slots + its share of the step's set-up (~ 2 g); a longer row is worked on in slices -- with fused
@@ -1436,16 +1424,10 @@ static int make_report_lut(uint32_t ctx_mask, ClassLut *lut, uint32_t *ctx_of_pl
     *ctx_of_plane |= k << (8 * np);
     np++;
   }
-  f[11] |= 0x40u;                                          // skipped (:123)
+  f[kXmSkip] |= 0x40u;                                     // skipped (:123)
   f[9] |= 0x80u;                                           // counts twice in the coverage (:126-127)
-  auto pack = [&](int b0) { return f[b0] | (f[b0 + 1] << 8) | (f[b0 + 2] << 16) | (f[b0 + 3] << 24); };
-  lut->lo0 = pack(0); lut->lo1 = pack(4); lut->hi0 = pack(8); lut->hi1 = pack(12);
+  *lut = lut16_pack(f);
   return np;
-}
-
-static uint32_t lut_byte(const ClassLut &l, int code) {
-  const uint32_t w = code < 4 ? l.lo0 : code < 8 ? l.lo1 : code < 12 ? l.hi0 : l.hi1;
-  return (w >> (8 * (code & 3))) & 255u;
 }
 
 struct CxThreshold {                      // fused thresholding request (null = use the pass vector)
@@ -1474,16 +1456,15 @@ static bool make_fused_lut(const CxThreshold &t, uint32_t ctx_of_plane, int np, 
     if (i == k) f[i] |= 0x04u;                             // methylated: n_m, and M for a passing read
     if (w[2][i]) f[i] |= 0x10u;
     if (w[3][i]) f[i] |= 0x40u;
-    if (i == 11) f[i] |= 0x02u;                            // skipped as is (:123) ...
+    if (i == kXmSkip) f[i] |= 0x02u;                           // skipped as is (:123) ...
     if (i == 9) f[i] |= 0x08u;                             // counts twice in the coverage (:126-127)
-    if ((i | 8u) == 11) f[i] |= 0x20u;                     // ... and when the read is lower-cased (c | 8, :122)
+    if ((i | 8u) == kXmSkip) f[i] |= 0x20u;                    // ... and when the read is lower-cased (c | 8, :122)
     if ((i | 8u) == 9) f[i] |= 0x80u;
   }
   int fill = -1;
   for (int c : {12, 8, 0, 4}) if (f[c] == 0) { fill = c; break; }
   if (fill < 0) return false;
-  auto pack = [&](int b0) { return f[b0] | (f[b0 + 1] << 8) | (f[b0 + 2] << 16) | (f[b0 + 3] << 24); };
-  lut->lo0 = pack(0); lut->lo1 = pack(4); lut->hi0 = pack(8); lut->hi1 = pack(12);
+  *lut = lut16_pack(f);
   *fill4 = 0x01010101u * (uint32_t)fill;
   return true;
 }
@@ -1723,7 +1704,7 @@ static int cx_report_impl(epi_batch *b, const int32_t *d_pass, const CxThreshold
   CxPlan p = {};
   p.np = make_report_lut(ctx_mask, &a.lut_r, &a.ctx_of_plane);
   a.lut_rx = lut16_xor_form(a.lut_r);
-  a.fill4 = 0x0C0C0C0Cu;                                   // '.': never a call, never skipped, also when lower-cased
+  a.fill4 = kXmDot4;                                       // '.': never a call, never skipped, also when lower-cased
   p.T = cx_tile_for(p.np);
   RowStats st;
   EPI_TRY(build_tiles(b, s, p.T, &st, &p.nt, &p.nt_hinted));

@@ -1,11 +1,11 @@
 // FDRP report: the fraction of discordant read pairs (FDRP) and the mean normalised Hamming distance of read pairs (qFDRP)
 // per cytosine, the two within-sample heterogeneity scores of the WSH package (Scherer et al. 2020; include/epihip.h,
 // epi_batch_fdrp_report_dev, has the definitions).  No reference interface is replaced.  Sites, calls and kept rows are the
-// heterogeneity report's (het_common.hpp); what is new is that rows are compared with each other, so the report first
+// heterogeneity report's (site_table.hpp); what is new is that rows are compared with each other, so the report first
 // builds an index from a site to the rows that have a call there.
 //
 // Data path, all on the report's stream:
-//  (a) the site table of the heterogeneity report: the un-thresholded CX report, split per strand (het_site_table).
+//  (a) the site table of the heterogeneity report: the un-thresholded CX report, split per strand (site_table).
 //  (b) k_fdrp_mark: a group of G lanes (16, or 64 for long rows) takes a row as in k_het_count and leaves the row's first
 //      site lo, its sites hi - lo, its calls and its words ceil((hi - lo) / 64); k_fdrp_sum_calls sums the calls of all rows
 //      in 64 bits.  Two scans give every row its first pair and its first word; the two totals come back to the host
@@ -28,15 +28,15 @@
 // launch shape or atomic order enters a result.
 // State: epi_batch::sites (SiteReportState, common.hpp); frow, fbits, fpair and fsite are this report's and stay on the
 // batch with the table: the site -> rows index.
-#include "het_common.hpp"
+#include "site_table.hpp"
 #include "radix_sort.hpp"
 
 namespace epi {
 
 constexpr int kFdrpMaxW = 31, kFdrpMaxRows = 64;
-constexpr int FDRP_WAVES = HET_WG / 64;
+constexpr int FDRP_WAVES = SITE_WG / 64;
 
-struct FdrpRowArgs : HetRows {
+struct FdrpRowArgs : SiteRows {
   uint32_t *row_lo, *row_ns, *row_nc, *row_nw;     // mark writes these ...
   unsigned long long *ncalls;
   const uint32_t *pair_off, *word_off;             // ... fill reads their scans
@@ -46,11 +46,11 @@ struct FdrpRowArgs : HetRows {
 };
 
 template <int G>
-__global__ __launch_bounds__(HET_WG) void k_fdrp_mark(FdrpRowArgs a) {
+__global__ __launch_bounds__(SITE_WG) void k_fdrp_mark(FdrpRowArgs a) {
   constexpr int GPW = 64 / G;
   const uint32_t lane = threadIdx.x & 63u, sub = lane % G, grp = lane / G;
-  const int64_t row = ((int64_t)blockIdx.x * (HET_WG / 64) + (threadIdx.x >> 6)) * GPW + grp;
-  const HetRow<G> r(a, row, sub, grp);
+  const int64_t row = ((int64_t)blockIdx.x * (SITE_WG / 64) + (threadIdx.x >> 6)) * GPW + grp;
+  const SiteRow<G> r(a, row, sub, grp);
   const uint32_t lo = r.lo, hi = r.hi;
   uint32_t nc = 0;
   for (uint32_t base = lo; __ballot(base < hi) != 0ull; base += G) {
@@ -68,12 +68,12 @@ __global__ __launch_bounds__(HET_WG) void k_fdrp_mark(FdrpRowArgs a) {
 // FDRP_SUM_ITEMS rows, a wave adds once.  (Not one add per wave of k_fdrp_mark: 2.5 M adds to one address for 10^7 rows
 // serialise in L2 at 12 ns each, 30 ms; profiles/fdrp_report.txt.)
 constexpr int FDRP_SUM_ITEMS = 16;
-__global__ __launch_bounds__(HET_WG) void k_fdrp_sum_calls(const uint32_t *__restrict__ row_nc, int64_t n, unsigned long long *__restrict__ ncalls) {
-  const int64_t base = (int64_t)blockIdx.x * (HET_WG * FDRP_SUM_ITEMS) + threadIdx.x;
+__global__ __launch_bounds__(SITE_WG) void k_fdrp_sum_calls(const uint32_t *__restrict__ row_nc, int64_t n, unsigned long long *__restrict__ ncalls) {
+  const int64_t base = (int64_t)blockIdx.x * (SITE_WG * FDRP_SUM_ITEMS) + threadIdx.x;
   unsigned long long sum = 0;
 #pragma unroll
   for (int i = 0; i < FDRP_SUM_ITEMS; i++) {
-    const int64_t r = base + (int64_t)i * HET_WG;
+    const int64_t r = base + (int64_t)i * SITE_WG;
     if (r < n) sum += row_nc[r];
   }
 #pragma unroll
@@ -82,11 +82,11 @@ __global__ __launch_bounds__(HET_WG) void k_fdrp_sum_calls(const uint32_t *__res
 }
 
 template <int G>
-__global__ __launch_bounds__(HET_WG) void k_fdrp_fill(FdrpRowArgs a) {
+__global__ __launch_bounds__(SITE_WG) void k_fdrp_fill(FdrpRowArgs a) {
   constexpr int GPW = 64 / G;
   const uint32_t lane = threadIdx.x & 63u, sub = lane % G, grp = lane / G;
-  const int64_t row = ((int64_t)blockIdx.x * (HET_WG / 64) + (threadIdx.x >> 6)) * GPW + grp;
-  const HetRow<G> r(a, row, sub, grp);
+  const int64_t row = ((int64_t)blockIdx.x * (SITE_WG / 64) + (threadIdx.x >> 6)) * GPW + grp;
+  const SiteRow<G> r(a, row, sub, grp);
   const uint32_t lo = r.lo, hi = r.hi;
   const size_t p0 = row < a.n ? a.pair_off[row] : 0u, w0 = row < a.n ? a.word_off[row] : 0u;
   const unsigned long long below = (1ull << sub) - 1ull;
@@ -115,9 +115,9 @@ __global__ __launch_bounds__(HET_WG) void k_fdrp_fill(FdrpRowArgs a) {
 }
 
 // sorted keys -> the run of every site that has one: [site_off, site_end); both are zero elsewhere (memset by the host)
-__global__ __launch_bounds__(HET_WG) void k_fdrp_bounds(const uint64_t *__restrict__ key, uint32_t n, uint32_t N,
+__global__ __launch_bounds__(SITE_WG) void k_fdrp_bounds(const uint64_t *__restrict__ key, uint32_t n, uint32_t N,
                                                         uint32_t *__restrict__ site_off, uint32_t *__restrict__ site_end) {
-  const uint32_t i = blockIdx.x * (uint32_t)HET_WG + threadIdx.x;
+  const uint32_t i = blockIdx.x * (uint32_t)SITE_WG + threadIdx.x;
   if (i >= n) return;
   const uint64_t k = key[i];
   if (k >= N) return;
@@ -159,7 +159,7 @@ __device__ __forceinline__ uint64_t wave_read_u64(uint64_t v, int l) {      // l
   return ((uint64_t)b << 32) | a;
 }
 
-__global__ __launch_bounds__(HET_WG) void k_fdrp_pairs(FdrpPairArgs a) {
+__global__ __launch_bounds__(SITE_WG) void k_fdrp_pairs(FdrpPairArgs a) {
   __shared__ uint32_t s_H[FDRP_WAVES][64];
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   s_H[wave][lane] = 0;
@@ -180,7 +180,7 @@ __global__ __launch_bounds__(HET_WG) void k_fdrp_pairs(FdrpPairArgs a) {
     bool ok = false;
     if ((int)lane < nwin && gi >= (int64_t)s0 && gi < (int64_t)s1) {
       const unsigned long long k = a.key[gi];
-      const int64_t d = (int64_t)het_key_pos(k) - (int64_t)het_key_pos(kg);
+      const int64_t d = (int64_t)table_key_pos(k) - (int64_t)table_key_pos(kg);
       ok = (k >> 32) == (kg >> 32) && (a.max_dist == 0 || (d <= a.max_dist && -d <= a.max_dist));
     }
     const uint64_t mask = __ballot(ok);
@@ -228,15 +228,15 @@ struct FdrpFinish : SiteView {
 };
 
 __device__ __forceinline__ bool fdrp_site(const FdrpFinish &f, uint32_t i, uint32_t *g_out, uint32_t *cov, uint32_t *nreads) {
-  const uint32_t g = het_ordinal(f.strand[i], i, f.rank[i], *f.n1);
+  const uint32_t g = site_ordinal(f.strand[i], i, f.rank[i], *f.n1);
   if (g >= f.N) return false;
   const uint32_t c = f.site_end[g] - f.site_off[g];
   *g_out = g; *cov = c; *nreads = c < (uint32_t)f.m ? c : (uint32_t)f.m;
   return true;
 }
 
-__global__ __launch_bounds__(HET_WG) void k_fdrp_keep(FdrpFinish f, uint32_t *__restrict__ flag) {
-  const uint32_t i = blockIdx.x * (uint32_t)HET_WG + threadIdx.x;
+__global__ __launch_bounds__(SITE_WG) void k_fdrp_keep(FdrpFinish f, uint32_t *__restrict__ flag) {
+  const uint32_t i = blockIdx.x * (uint32_t)SITE_WG + threadIdx.x;
   if (i >= f.N) return;
   uint32_t g, c, nr;
   flag[i] = fdrp_site(f, i, &g, &c, &nr) && nr >= f.min_reads && f.res[g].npairs >= 1u ? 1u : 0u;
@@ -247,9 +247,9 @@ struct FdrpOut {
   double *fdrp, *qfdrp;
 };
 
-__global__ __launch_bounds__(HET_WG) void k_fdrp_emit(FdrpFinish f, const uint32_t *__restrict__ flag, const uint32_t *__restrict__ out_off,
+__global__ __launch_bounds__(SITE_WG) void k_fdrp_emit(FdrpFinish f, const uint32_t *__restrict__ flag, const uint32_t *__restrict__ out_off,
                                                       FdrpOut o) {
-  const uint32_t i = blockIdx.x * (uint32_t)HET_WG + threadIdx.x;
+  const uint32_t i = blockIdx.x * (uint32_t)SITE_WG + threadIdx.x;
   if (i >= f.N || !flag[i]) return;
   uint32_t g, c, nr;
   if (!fdrp_site(f, i, &g, &c, &nr)) return;
@@ -265,9 +265,9 @@ __global__ __launch_bounds__(HET_WG) void k_fdrp_emit(FdrpFinish f, const uint32
 static void fdrp_finish_args(const epi_batch *b, FdrpFinish &f) {
   const SiteReportState &t = b->sites;
   f.N = site_view_args(b, f);
-  f.m = t.max_rows;
+  f.m = t.fdrp.max_rows;
   f.min_reads = t.min_reads;
-  f.site_off = t.fsite.as<uint32_t>();
+  f.site_off = t.fdrp.fsite.as<uint32_t>();
   f.site_end = f.site_off + f.N;
   f.res = t.counts.as<FdrpSite>();
 }
@@ -283,27 +283,26 @@ static int fdrp_report(epi_batch *b, const char *ctx, int W, int m, int min_over
   SiteReportState &t = b->sites;
   // (a) the site table
   int64_t nsite = 0;
-  EPI_TRY(het_cx_sites(b, ctx, s, who, &nsite));
-  t.nsite = nsite; t.W = W; t.max_rows = m; t.min_overlap = min_overlap;
+  EPI_TRY(site_cx_report(b, ctx, s, who, &nsite));
+  t.nsite = nsite; t.fdrp.W = W; t.fdrp.max_rows = m; t.fdrp.min_overlap = min_overlap;
   t.min_reads = (uint32_t)(min_reads > 2 ? min_reads : 2);
-  t.max_dist = max_dist;
   if (nsite == 0 || b->n == 0) return fdrp_empty(b);
   if (nsite >= (1LL << 31)) return fail(EPI_ERR_ARG, "%s: %lld sites, beyond 32-bit ordinals", who, (long long)nsite);
   if (b->nbytes / 64 + b->n >= (1LL << 32)) return fail(EPI_ERR_ARG, "%s: the rows' packed calls need 2^32 words or more", who);
   const size_t N = (size_t)nsite, n = (size_t)b->n;
-  const int64_t nb_sites = ((int64_t)N + HET_WG - 1) / HET_WG, nb_waves = ((int64_t)N + FDRP_WAVES - 1) / FDRP_WAVES;
+  const int64_t nb_sites = ((int64_t)N + SITE_WG - 1) / SITE_WG, nb_waves = ((int64_t)N + FDRP_WAVES - 1) / FDRP_WAVES;
   bool wide = false;
-  const int64_t nb_rows = het_count_blocks(b, &wide);
-  EPI_TRY(check_grid(nb_rows, HET_WG, "FDRP row kernels"));
-  EPI_TRY(check_grid(nb_waves, HET_WG, "FDRP pair kernel"));
-  EPI_TRY(het_site_table(b, nsite, s));
+  const int64_t nb_rows = site_count_blocks(b, &wide);
+  EPI_TRY(check_grid(nb_rows, SITE_WG, "FDRP row kernels"));
+  EPI_TRY(check_grid(nb_waves, SITE_WG, "FDRP pair kernel"));
+  EPI_TRY(site_table(b, nsite, s));
   SiteScalars *sc = t.scalars();
-  EPI_TRY(t.frow.ensure(n * 6 * 4));
+  EPI_TRY(t.fdrp.frow.ensure(n * 6 * 4));
 
   // (b) what every row holds
   FdrpRowArgs a;
-  het_rows_args(b, ctx_mask_of(ctx), max_oo, a);
-  uint32_t *fr = t.frow.as<uint32_t>();
+  site_rows_args(b, ctx_mask_of(ctx), max_oo, a);
+  uint32_t *fr = t.fdrp.frow.as<uint32_t>();
   a.row_lo = fr; a.row_ns = fr + n; a.row_nc = fr + 2 * n; a.row_nw = fr + 3 * n;
   uint32_t *pair_off = fr + 4 * n, *word_off = fr + 5 * n;
   a.pair_off = pair_off; a.word_off = word_off;
@@ -311,9 +310,9 @@ static int fdrp_report(epi_batch *b, const char *ctx, int W, int m, int min_over
   a.valid = a.meth = nullptr; a.pkey = nullptr; a.prow = nullptr;
   EPI_HIP(hipMemsetAsync(&sc->nwords, 0, 16, s));
   prof_begin("fdrp_mark", s);
-  if (wide) hipLaunchKernelGGL((k_fdrp_mark<64>), dim3((unsigned)nb_rows), dim3(HET_WG), 0, s, a);
-  else hipLaunchKernelGGL((k_fdrp_mark<16>), dim3((unsigned)nb_rows), dim3(HET_WG), 0, s, a);
-  hipLaunchKernelGGL(k_fdrp_sum_calls, dim3((unsigned)((n + HET_WG * FDRP_SUM_ITEMS - 1) / (HET_WG * FDRP_SUM_ITEMS))), dim3(HET_WG), 0, s,
+  if (wide) hipLaunchKernelGGL((k_fdrp_mark<64>), dim3((unsigned)nb_rows), dim3(SITE_WG), 0, s, a);
+  else hipLaunchKernelGGL((k_fdrp_mark<16>), dim3((unsigned)nb_rows), dim3(SITE_WG), 0, s, a);
+  hipLaunchKernelGGL(k_fdrp_sum_calls, dim3((unsigned)((n + SITE_WG * FDRP_SUM_ITEMS - 1) / (SITE_WG * FDRP_SUM_ITEMS))), dim3(SITE_WG), 0, s,
                      a.row_nc, (int64_t)n, a.ncalls);
   prof_end("fdrp_mark", s);
   EPI_HIP(hipGetLastError());
@@ -326,21 +325,21 @@ static int fdrp_report(epi_batch *b, const char *ctx, int W, int m, int min_over
   if (pbytes < 0)
     return fail(EPI_ERR_ARG, "%s: %llu calls, the site -> rows index holds fewer than 2^32 pairs", who, h.ncalls);
   const size_t nc = (size_t)h.ncalls, nw = h.nwords;
-  const int64_t nb_pairs = ((int64_t)nc + HET_WG - 1) / HET_WG;
-  EPI_TRY(check_grid(nb_pairs, HET_WG, "FDRP index kernels"));
+  const int64_t nb_pairs = ((int64_t)nc + SITE_WG - 1) / SITE_WG;
+  EPI_TRY(check_grid(nb_pairs, SITE_WG, "FDRP index kernels"));
 
   // (c) the packed calls and the (site, row) pairs
-  EPI_TRY(t.fpair.ensure(SortPairs::bytes(nc)));
-  EPI_TRY(t.fbits.ensure(nw * 16));
-  EPI_TRY(t.fsite.ensure(N * 8));
+  EPI_TRY(t.fdrp.fpair.ensure(SortPairs::bytes(nc)));
+  EPI_TRY(t.fdrp.fbits.ensure(nw * 16));
+  EPI_TRY(t.fdrp.fsite.ensure(N * 8));
   EPI_TRY(t.counts.ensure(N * sizeof(FdrpSite)));
   EPI_TRY(t.out.ensure(N * 4));
-  SortPairs sort(t.fpair.p, nc);
-  a.valid = t.fbits.as<uint64_t>(); a.meth = a.valid + nw;
+  SortPairs sort(t.fdrp.fpair.p, nc);
+  a.valid = t.fdrp.fbits.as<uint64_t>(); a.meth = a.valid + nw;
   a.pkey = sort.keys_in(); a.prow = sort.vals_in();
   prof_begin("fdrp_fill", s);
-  if (wide) hipLaunchKernelGGL((k_fdrp_fill<64>), dim3((unsigned)nb_rows), dim3(HET_WG), 0, s, a);
-  else hipLaunchKernelGGL((k_fdrp_fill<16>), dim3((unsigned)nb_rows), dim3(HET_WG), 0, s, a);
+  if (wide) hipLaunchKernelGGL((k_fdrp_fill<64>), dim3((unsigned)nb_rows), dim3(SITE_WG), 0, s, a);
+  else hipLaunchKernelGGL((k_fdrp_fill<16>), dim3((unsigned)nb_rows), dim3(SITE_WG), 0, s, a);
   prof_end("fdrp_fill", s);
   EPI_HIP(hipGetLastError());
 
@@ -348,10 +347,10 @@ static int fdrp_report(epi_batch *b, const char *ctx, int W, int m, int min_over
   uint32_t bytes = 0;
   for (int d = 0; d < 4; d++) if ((N - 1) >> (8 * d)) bytes |= 1u << d;
   EPI_TRY(sort.sort(bytes, b->scan_tmp, s));
-  uint32_t *site_off = t.fsite.as<uint32_t>(), *site_end = site_off + N;
+  uint32_t *site_off = t.fdrp.fsite.as<uint32_t>(), *site_end = site_off + N;
   EPI_HIP(hipMemsetAsync(site_off, 0, N * 8, s));
   prof_begin("fdrp_bounds", s);
-  hipLaunchKernelGGL(k_fdrp_bounds, dim3((unsigned)nb_pairs), dim3(HET_WG), 0, s, sort.keys(), (uint32_t)nc, (uint32_t)N, site_off, site_end);
+  hipLaunchKernelGGL(k_fdrp_bounds, dim3((unsigned)nb_pairs), dim3(SITE_WG), 0, s, sort.keys(), (uint32_t)nc, (uint32_t)N, site_off, site_end);
   prof_end("fdrp_bounds", s);
 
   // (e) the pairs of every site
@@ -363,7 +362,7 @@ static int fdrp_report(epi_batch *b, const char *ctx, int W, int m, int min_over
   p.out = t.counts.as<FdrpSite>();
   p.max_dist = max_dist; p.W = W; p.m = m; p.min_overlap = min_overlap;
   prof_begin("fdrp_pairs", s);
-  hipLaunchKernelGGL(k_fdrp_pairs, dim3((unsigned)nb_waves), dim3(HET_WG), 0, s, p);
+  hipLaunchKernelGGL(k_fdrp_pairs, dim3((unsigned)nb_waves), dim3(SITE_WG), 0, s, p);
   prof_end("fdrp_pairs", s);
   EPI_HIP(hipGetLastError());
 
@@ -371,7 +370,7 @@ static int fdrp_report(epi_batch *b, const char *ctx, int W, int m, int min_over
   FdrpFinish f;
   fdrp_finish_args(b, f);
   uint32_t *flag = t.flag.as<uint32_t>();
-  hipLaunchKernelGGL(k_fdrp_keep, dim3((unsigned)nb_sites), dim3(HET_WG), 0, s, f, flag);
+  hipLaunchKernelGGL(k_fdrp_keep, dim3((unsigned)nb_sites), dim3(SITE_WG), 0, s, f, flag);
   EPI_HIP(hipGetLastError());
   EPI_TRY(site_rows(b, flag, (int64_t)N, t.out.as<uint32_t>(), &sc->nrow, s, nrow_out));
   b->last_kind = KIND_FDRP;
@@ -412,7 +411,7 @@ int epi_batch_fdrp_report_dev(epi_batch *b, const char *ctx, int flank_sites, in
 int epi_batch_fdrp_fetch_dev(epi_batch *b, int32_t *const d_icols[8], double *const d_dcols[2], void *stream) {
   hipStream_t s = nullptr;
   int64_t nrow = 0;
-  EPI_TRY(site_fetch_begin("epi_batch_fdrp_fetch_dev", b, KIND_FDRP, false, d_icols, 8, d_dcols, 2, stream, &s, &nrow));
+  EPI_TRY(site_fetch_begin("epi_batch_fdrp_fetch_dev", b, KIND_FDRP, "FDRP report", false, d_icols, 8, d_dcols, 2, stream, &s, &nrow));
   if (nrow == 0) return EPI_OK;
   FdrpFinish f;
   fdrp_finish_args(b, f);
@@ -420,9 +419,9 @@ int epi_batch_fdrp_fetch_dev(epi_batch *b, int32_t *const d_icols[8], double *co
   o.rname = d_icols[0]; o.strand = d_icols[1]; o.pos = d_icols[2]; o.context = d_icols[3]; o.coverage = d_icols[4];
   o.nreads = d_icols[5]; o.npairs = d_icols[6]; o.ndiscordant = d_icols[7];
   o.fdrp = d_dcols[0]; o.qfdrp = d_dcols[1];
-  const unsigned nb = (unsigned)(((int64_t)f.N + HET_WG - 1) / HET_WG);
+  const unsigned nb = (unsigned)(((int64_t)f.N + SITE_WG - 1) / SITE_WG);
   prof_begin("fdrp_emit", s);
-  hipLaunchKernelGGL(k_fdrp_emit, dim3(nb), dim3(HET_WG), 0, s, f, b->sites.flag.as<uint32_t>(), b->sites.out.as<uint32_t>(), o);
+  hipLaunchKernelGGL(k_fdrp_emit, dim3(nb), dim3(SITE_WG), 0, s, f, b->sites.flag.as<uint32_t>(), b->sites.out.as<uint32_t>(), o);
   prof_end("fdrp_emit", s);
   EPI_HIP(hipGetLastError());
   return EPI_OK;

@@ -1,19 +1,19 @@
 // Heterogeneity comparison: the epiallele histograms of two batches a and b over the windows of the sites they have in
 // common, and what separates the two histograms of a window (include/epihip.h, epi_batch_heterogeneity_compare_dev, has the
 // definitions).  No reference interface is replaced.  The counting is the heterogeneity report's (heterogeneity.hip; the
-// shared parts are in het_common.hpp), twice, on one site table.  All on the call's stream:
+// shared parts are in site_table.hpp and het_common.hpp), twice, on one site table.  All on the call's stream:
 //  (a) b's site table as a heterogeneity report makes it (its CX report, fetched into b's sites.cx, split per strand into
 //      b's sites.key / sites.sctx); a's CX report, fetched into a's sites.cx_all.
 //  (b) k_hetcmp_match: a thread per CX row of a searches the part of b's table for its strand (binary, keys of one
 //      strand are sorted) and flags the row when b has the key with the same context code.  util.hip's scan, then
 //      k_hetcmp_compact writes the flagged rows' rname, strand, pos and context into a's sites.cx: the common table, in
-//      a's CX order.  het_strand_table turns it into the common per-strand table in a's sites.key / sites.sctx.
+//      a's CX order.  site_strand_table turns it into the common per-strand table in a's sites.key / sites.sctx.
 //  (c) k_het_count<16> / <64>, unchanged, once over a's rows into a's sites.counts and once over b's rows into a's
 //      sites.counts_b, both with the common table.  The lane shape follows the batch whose rows are counted.
 //  (d) k_hetcmp_keep (a thread per common site = per window start): n_a, n_b, min_reads, the span cap -> a flag; the scan;
 //      k_hetcmp_emit (at fetch) writes het_metrics of either histogram, as k_het_emit does, and the comparison
 //      metrics, every sum over the bins in ascending order inside one thread: no launch shape enters a result.
-// Everything the fetch needs is in a's sites; b keeps its own site table and is left as het_cx_sites leaves it (KIND_NONE).
+// Everything the fetch needs is in a's sites; b keeps its own site table and is left as site_cx_report leaves it (KIND_NONE).
 #include "het_common.hpp"
 
 namespace epi {
@@ -27,14 +27,14 @@ struct CmpMatch {
   uint32_t Nb;
 };
 
-__global__ __launch_bounds__(HET_WG) void k_hetcmp_match(CmpMatch m, uint32_t *__restrict__ flag) {
-  const uint32_t i = blockIdx.x * (uint32_t)HET_WG + threadIdx.x;
+__global__ __launch_bounds__(SITE_WG) void k_hetcmp_match(CmpMatch m, uint32_t *__restrict__ flag) {
+  const uint32_t i = blockIdx.x * (uint32_t)SITE_WG + threadIdx.x;
   if (i >= m.Na) return;
   const uint32_t n1 = *m.n1_b;
   const bool plus = m.strand[i] == 1;
   uint32_t lo = plus ? 0u : n1, hi = plus ? n1 : m.Nb;      // an empty part: nothing is searched, nothing is common
   const uint32_t end = hi;
-  const unsigned long long key = het_key(m.rname[i], (int64_t)m.pos[i]);
+  const unsigned long long key = table_key(m.rname[i], (int64_t)m.pos[i]);
   while (lo < hi) {
     const uint32_t mid = lo + (hi - lo) / 2u;
     if (m.key_b[mid] < key) lo = mid + 1u; else hi = mid;
@@ -43,9 +43,9 @@ __global__ __launch_bounds__(HET_WG) void k_hetcmp_match(CmpMatch m, uint32_t *_
 }
 
 // row i of a's table (columns of Na rows) to row off[i] of the common one (columns of Nc rows)
-__global__ __launch_bounds__(HET_WG) void k_hetcmp_compact(const int32_t *__restrict__ src, uint32_t Na, const uint32_t *__restrict__ flag,
+__global__ __launch_bounds__(SITE_WG) void k_hetcmp_compact(const int32_t *__restrict__ src, uint32_t Na, const uint32_t *__restrict__ flag,
                                                           const uint32_t *__restrict__ off, int32_t *__restrict__ dst, uint32_t Nc) {
-  const uint32_t i = blockIdx.x * (uint32_t)HET_WG + threadIdx.x;
+  const uint32_t i = blockIdx.x * (uint32_t)SITE_WG + threadIdx.x;
   if (i >= Na || !flag[i]) return;
   const uint32_t r = off[i];
   if (r >= Nc) return;
@@ -57,8 +57,8 @@ struct CmpFinish : HetFinish {          // counts: a's side
   const uint32_t *counts_b;
 };
 
-__global__ __launch_bounds__(HET_WG) void k_hetcmp_keep(CmpFinish f, uint32_t *__restrict__ flag) {
-  const uint32_t i = blockIdx.x * (uint32_t)HET_WG + threadIdx.x;
+__global__ __launch_bounds__(SITE_WG) void k_hetcmp_keep(CmpFinish f, uint32_t *__restrict__ flag) {
+  const uint32_t i = blockIdx.x * (uint32_t)SITE_WG + threadIdx.x;
   if (i >= f.N) return;
   int32_t end = 0;
   const uint32_t *ca = het_window(f, i, &end);
@@ -80,9 +80,9 @@ struct CmpOut {
   int32_t *counts[2];                   // [nrow][2^k] or null
 };
 
-__global__ __launch_bounds__(HET_WG) void k_hetcmp_emit(CmpFinish f, const uint32_t *__restrict__ flag, const uint32_t *__restrict__ out_off,
+__global__ __launch_bounds__(SITE_WG) void k_hetcmp_emit(CmpFinish f, const uint32_t *__restrict__ flag, const uint32_t *__restrict__ out_off,
                                                         CmpOut o) {
-  const uint32_t i = blockIdx.x * (uint32_t)HET_WG + threadIdx.x;
+  const uint32_t i = blockIdx.x * (uint32_t)SITE_WG + threadIdx.x;
   if (i >= f.N || !flag[i]) return;
   int32_t end = 0;
   const uint32_t *ca = het_window(f, i, &end);
@@ -135,7 +135,7 @@ __global__ __launch_bounds__(HET_WG) void k_hetcmp_emit(CmpFinish f, const uint3
 
 static void cmp_finish_args(const epi_batch *a, CmpFinish &f) {
   het_finish_args(a, f);
-  f.counts_b = a->sites.counts_b.as<uint32_t>();
+  f.counts_b = a->sites.cmp.counts_b.as<uint32_t>();
 }
 
 static int cmp_empty(epi_batch *a, int64_t ncommon, int64_t *ncommon_out) {
@@ -150,36 +150,36 @@ static int het_compare(epi_batch *a, epi_batch *b, const char *ctx, int k, doubl
   SiteReportState &t = a->sites;
   // (a) the two site tables: b's as a report of its own has it, a's in CX row order only
   int64_t nsite_b = 0, nsite_a = 0;
-  EPI_TRY(het_cx_sites(b, ctx, s, who, &nsite_b));
+  EPI_TRY(site_cx_report(b, ctx, s, who, &nsite_b));
   b->sites.nsite = 0;                                      // (b's buffers hold no report's table from here on)
   if (nsite_b > 0) {
     if (nsite_b >= (1LL << 31)) return fail(EPI_ERR_ARG, "%s: %lld sites in the second batch", who, (long long)nsite_b);
-    EPI_TRY(het_site_table(b, nsite_b, s));
+    EPI_TRY(site_table(b, nsite_b, s));
   }
-  EPI_TRY(het_cx_sites(a, ctx, s, who, &nsite_a));
-  t.nsite = 0; t.k = k;
+  EPI_TRY(site_cx_report(a, ctx, s, who, &nsite_a));
+  t.nsite = 0; t.het.k = k;
   t.min_reads = (uint32_t)(min_reads > 1 ? min_reads : 1);
-  t.max_span = max_span;
+  t.het.max_span = max_span;
   if (nsite_a == 0 || nsite_b == 0) return cmp_empty(a, 0, ncommon_out);
   if (nsite_a >= (1LL << 31)) return fail(EPI_ERR_ARG, "%s: %lld sites in the first batch", who, (long long)nsite_a);
   const size_t Na = (size_t)nsite_a;
-  const int64_t nb_a = ((int64_t)Na + HET_WG - 1) / HET_WG;
-  EPI_TRY(check_grid(nb_a, HET_WG, "heterogeneity comparison site kernels"));
-  EPI_TRY(het_cx_fetch(a, nsite_a, s, t.cx_all));
+  const int64_t nb_a = ((int64_t)Na + SITE_WG - 1) / SITE_WG;
+  EPI_TRY(check_grid(nb_a, SITE_WG, "heterogeneity comparison site kernels"));
+  EPI_TRY(site_cx_fetch(a, nsite_a, s, t.cmp.cx_all));
   EPI_TRY(t.flag.ensure(Na * 4));
   EPI_TRY(t.out.ensure(Na * 4));
   EPI_TRY(t.scal.ensure(64));
   uint32_t *flag = t.flag.as<uint32_t>(), *out = t.out.as<uint32_t>();
 
   // (b) the sites of a that b has too
-  const int32_t *cx_a = t.cx_all.as<int32_t>();
+  const int32_t *cx_a = t.cmp.cx_all.as<int32_t>();
   CmpMatch m;
   m.rname = cx_a; m.strand = cx_a + Na; m.pos = cx_a + 2 * Na; m.context = cx_a + 3 * Na;
   m.Na = (uint32_t)Na;
   m.key_b = b->sites.key.as<unsigned long long>(); m.sctx_b = b->sites.sctx.as<uint8_t>(); m.n1_b = &b->sites.scalars()->nplus;
   m.Nb = (uint32_t)nsite_b;
   prof_begin("hetcmp_intersect", s);
-  hipLaunchKernelGGL(k_hetcmp_match, dim3((unsigned)nb_a), dim3(HET_WG), 0, s, m, flag);
+  hipLaunchKernelGGL(k_hetcmp_match, dim3((unsigned)nb_a), dim3(SITE_WG), 0, s, m, flag);
   int64_t ncommon = 0;
   EPI_TRY(site_rows(a, flag, (int64_t)Na, out, &t.scalars()->ncommon, s, &ncommon, "hetcmp_intersect"));
   if (ncommon < k) return cmp_empty(a, ncommon, ncommon_out);
@@ -190,9 +190,9 @@ static int het_compare(epi_batch *a, epi_batch *b, const char *ctx, int k, doubl
   const size_t Nc = (size_t)ncommon;
   EPI_TRY(t.cx.ensure(Nc * 6 * 4));
   prof_begin("hetcmp_compact", s);
-  hipLaunchKernelGGL(k_hetcmp_compact, dim3((unsigned)nb_a), dim3(HET_WG), 0, s, cx_a, (uint32_t)Na, flag, out, t.cx.as<int32_t>(),
+  hipLaunchKernelGGL(k_hetcmp_compact, dim3((unsigned)nb_a), dim3(SITE_WG), 0, s, cx_a, (uint32_t)Na, flag, out, t.cx.as<int32_t>(),
                      (uint32_t)Nc);
-  const int rc_table = het_strand_table(a, ncommon, s);
+  const int rc_table = site_strand_table(a, ncommon, s);
   prof_end("hetcmp_compact", s);
   EPI_HIP(hipGetLastError());
   EPI_TRY(rc_table);
@@ -201,34 +201,34 @@ static int het_compare(epi_batch *a, epi_batch *b, const char *ctx, int k, doubl
 
   // (c) both batches' histograms over the common table
   bool wide_a = false, wide_b = false;
-  const int64_t nb_rows_a = het_count_blocks(a, &wide_a), nb_rows_b = het_count_blocks(b, &wide_b);
-  EPI_TRY(check_grid(nb_rows_a, HET_WG, "heterogeneity counting kernel"));
-  EPI_TRY(check_grid(nb_rows_b, HET_WG, "heterogeneity counting kernel"));
+  const int64_t nb_rows_a = site_count_blocks(a, &wide_a), nb_rows_b = site_count_blocks(b, &wide_b);
+  EPI_TRY(check_grid(nb_rows_a, SITE_WG, "heterogeneity counting kernel"));
+  EPI_TRY(check_grid(nb_rows_b, SITE_WG, "heterogeneity counting kernel"));
   EPI_TRY(t.counts.ensure((size_t)cbytes));
-  EPI_TRY(t.counts_b.ensure((size_t)cbytes));
+  EPI_TRY(t.cmp.counts_b.ensure((size_t)cbytes));
   EPI_HIP(hipMemsetAsync(t.counts.p, 0, (size_t)cbytes, s));
-  EPI_HIP(hipMemsetAsync(t.counts_b.p, 0, (size_t)cbytes, s));
+  EPI_HIP(hipMemsetAsync(t.cmp.counts_b.p, 0, (size_t)cbytes, s));
   const uint32_t ctx_mask = ctx_mask_of(ctx);
-  HetRows ra, rb;
-  het_rows_args(a, ctx_mask, max_oo, ra);
-  het_rows_args(b, ctx_mask, max_oo, rb);
+  SiteRows ra, rb;
+  site_rows_args(a, ctx_mask, max_oo, ra);
+  site_rows_args(b, ctx_mask, max_oo, rb);
   rb.key = ra.key; rb.sctx = ra.sctx; rb.n1 = ra.n1; rb.N = ra.N;     // b's rows, the common table
   prof_begin("hetcmp_count_a", s);
   const int rc_a = het_count_launch(ra, k, t.counts.as<uint32_t>(), nb_rows_a, wide_a, s);
   prof_end("hetcmp_count_a", s);
   EPI_TRY(rc_a);
   prof_begin("hetcmp_count_b", s);
-  const int rc_b = het_count_launch(rb, k, t.counts_b.as<uint32_t>(), nb_rows_b, wide_b, s);
+  const int rc_b = het_count_launch(rb, k, t.cmp.counts_b.as<uint32_t>(), nb_rows_b, wide_b, s);
   prof_end("hetcmp_count_b", s);
   EPI_TRY(rc_b);
 
   // (d) which windows are reported, and where
-  const int64_t nb_c = ((int64_t)Nc + HET_WG - 1) / HET_WG;
+  const int64_t nb_c = ((int64_t)Nc + SITE_WG - 1) / SITE_WG;
   CmpFinish f;
   cmp_finish_args(a, f);
-  flag = t.flag.as<uint32_t>();                              // (het_strand_table is done with its Nc words)
+  flag = t.flag.as<uint32_t>();                              // (site_strand_table is done with its Nc words)
   prof_begin("hetcmp_keep", s);
-  hipLaunchKernelGGL(k_hetcmp_keep, dim3((unsigned)nb_c), dim3(HET_WG), 0, s, f, flag);
+  hipLaunchKernelGGL(k_hetcmp_keep, dim3((unsigned)nb_c), dim3(SITE_WG), 0, s, f, flag);
   EPI_TRY(site_rows(a, flag, (int64_t)Nc, t.out.as<uint32_t>(), &t.scalars()->nrow, s, nrow_out, "hetcmp_keep"));
   a->last_kind = KIND_HETCMP;
   a->last_nrow = *nrow_out;
@@ -258,7 +258,7 @@ int epi_batch_heterogeneity_compare_fetch_dev(epi_batch *a, int32_t *const d_ico
                                               int32_t *d_counts_a, int32_t *d_counts_b, void *stream) {
   hipStream_t s = nullptr;
   int64_t nrow = 0;
-  EPI_TRY(site_fetch_begin("epi_batch_heterogeneity_compare_fetch_dev", a, KIND_HETCMP, false, d_icols, 10, d_dcols, 13, stream, &s,
+  EPI_TRY(site_fetch_begin("epi_batch_heterogeneity_compare_fetch_dev", a, KIND_HETCMP, "heterogeneity comparison", false, d_icols, 10, d_dcols, 13, stream, &s,
                            &nrow));
   if (nrow == 0) return EPI_OK;
   CmpFinish f;
@@ -271,9 +271,9 @@ int epi_batch_heterogeneity_compare_fetch_dev(epi_batch *a, int32_t *const d_ico
   }
   o.delta_beta = d_dcols[8]; o.delta_entropy = d_dcols[9]; o.jsd = d_dcols[10]; o.tvd = d_dcols[11]; o.g = d_dcols[12];
   o.counts[0] = d_counts_a; o.counts[1] = d_counts_b;
-  const unsigned nb = (unsigned)(((int64_t)f.N + HET_WG - 1) / HET_WG);
+  const unsigned nb = (unsigned)(((int64_t)f.N + SITE_WG - 1) / SITE_WG);
   prof_begin("hetcmp_emit", s);
-  hipLaunchKernelGGL(k_hetcmp_emit, dim3(nb), dim3(HET_WG), 0, s, f, a->sites.flag.as<uint32_t>(), a->sites.out.as<uint32_t>(), o);
+  hipLaunchKernelGGL(k_hetcmp_emit, dim3(nb), dim3(SITE_WG), 0, s, f, a->sites.flag.as<uint32_t>(), a->sites.out.as<uint32_t>(), o);
   prof_end("hetcmp_emit", s);
   EPI_HIP(hipGetLastError());
   return EPI_OK;

@@ -1,7 +1,7 @@
 // Linkage report: co-methylation of pairs of neighbouring sites over the reads that cover both -- the 2 x 2 table of
 // every pair (s_j, s_{j+d}), d = 1 .. D, its covariance, r^2 and D' -- and the methylation haplotype blocks that follow
 // from r^2 (Guo et al. 2017; include/epihip.h, epi_batch_linkage_report_dev, has the definitions).  No reference interface
-// is replaced.  The data path is the heterogeneity report's (heterogeneity.hip; the shared parts are in het_common.hpp):
+// is replaced.  The data path is the heterogeneity report's (heterogeneity.hip; the shared parts are in site_table.hpp):
 //  (a) the same site table: the un-thresholded CX report, split per strand, 64-bit keys and context codes.
 //  (b) k_link_count: a group of G lanes (16, or 64 for long rows) takes a row: the read rule, the (G + 1)-ary search for the
 //      row's site range [lo, hi), then G sites per round with the two ballots.  The lane at site g with a call looks back
@@ -22,7 +22,7 @@
 // (a deep amplicon).  Once per round every lane reads the base site and the two look-back windows of the lanes
 // sub + 16 m of the other groups; for each d the lanes that hold the same counter then add once, the lowest of them the
 // set's size.  Nine cross-lane reads per round whatever D is.
-#include "het_common.hpp"
+#include "site_table.hpp"
 
 namespace epi {
 
@@ -30,7 +30,7 @@ constexpr int kLinkMaxD = 16;
 constexpr int64_t kLinkCountsCap = 4LL << 30;         // bytes of counters (nsites * D * 16) a report may allocate
 static_assert(kLinkMaxD <= 16, "k_link_count<16> carries the bits of one previous round of 16 sites");
 
-struct LinkArgs : HetRows {
+struct LinkArgs : SiteRows {
   int32_t D;
   uint32_t *counts;                   // [N][D][4]: pair (g, d) at (g D + d - 1) 4, bins n_uu, n_mu, n_um, n_mm
 };
@@ -43,12 +43,12 @@ static int64_t link_counter_bytes(int64_t nsites, int D) {
 }
 
 template <int G>
-__global__ __launch_bounds__(HET_WG) void k_link_count(LinkArgs a) {
+__global__ __launch_bounds__(SITE_WG) void k_link_count(LinkArgs a) {
   static_assert(G >= kLinkMaxD, "the look-back reaches one previous round");
   constexpr int GPW = 64 / G;                                // groups per wave
   const uint32_t lane = threadIdx.x & 63u, sub = lane % G, grp = lane / G;
-  const int64_t row = ((int64_t)blockIdx.x * (HET_WG / 64) + (threadIdx.x >> 6)) * GPW + grp;
-  const HetRow<G> r(a, row, sub, grp);
+  const int64_t row = ((int64_t)blockIdx.x * (SITE_WG / 64) + (threadIdx.x >> 6)) * GPW + grp;
+  const SiteRow<G> r(a, row, sub, grp);
   const uint32_t lo = r.lo, hi = r.hi;
 
   const int D = a.D;
@@ -128,7 +128,7 @@ __device__ __forceinline__ bool link_pair(const LinkFinish &f, uint32_t g, int d
   const uint32_t *c = f.counts + (((size_t)g * (uint32_t)f.D + (uint32_t)(d - 1)) << 2);
   q.uu = c[0]; q.mu = c[1]; q.um = c[2]; q.mm = c[3];
   q.n = (uint64_t)q.uu + q.mu + q.um + q.mm;
-  q.pos = het_key_pos(k1); q.pos2 = het_key_pos(k2);
+  q.pos = table_key_pos(k1); q.pos2 = table_key_pos(k2);
   q.reported = q.n >= (uint64_t)f.min_reads && (f.max_dist == 0 || (int64_t)q.pos2 - (int64_t)q.pos <= f.max_dist);
   return true;
 }
@@ -151,13 +151,13 @@ __device__ __forceinline__ void link_metrics(const LinkPair &q, double *cov, dou
   else *dprime = 0.0;
 }
 
-__global__ __launch_bounds__(HET_WG) void k_link_keep(LinkFinish f, uint32_t *__restrict__ flag) {
-  const uint32_t t = blockIdx.x * (uint32_t)HET_WG + threadIdx.x;
+__global__ __launch_bounds__(SITE_WG) void k_link_keep(LinkFinish f, uint32_t *__restrict__ flag) {
+  const uint32_t t = blockIdx.x * (uint32_t)SITE_WG + threadIdx.x;
   const uint32_t D = (uint32_t)f.D;
   if (t >= f.N * D) return;                                  // N D <= 2^28 (the counter cap)
   const uint32_t i = t / D, d = t % D + 1u;
   LinkPair q;
-  const bool have = link_pair(f, het_ordinal(f.strand[i], i, f.rank[i], *f.n1), (int)d, q);
+  const bool have = link_pair(f, site_ordinal(f.strand[i], i, f.rank[i], *f.n1), (int)d, q);
   flag[t] = have && q.reported ? 1u : 0u;
 }
 
@@ -166,14 +166,14 @@ struct LinkOut {
   double *cov, *r2, *dprime;
 };
 
-__global__ __launch_bounds__(HET_WG) void k_link_emit(LinkFinish f, const uint32_t *__restrict__ flag, const uint32_t *__restrict__ out_off,
+__global__ __launch_bounds__(SITE_WG) void k_link_emit(LinkFinish f, const uint32_t *__restrict__ flag, const uint32_t *__restrict__ out_off,
                                                       LinkOut o) {
-  const uint32_t t = blockIdx.x * (uint32_t)HET_WG + threadIdx.x;
+  const uint32_t t = blockIdx.x * (uint32_t)SITE_WG + threadIdx.x;
   const uint32_t D = (uint32_t)f.D;
   if (t >= f.N * D || !flag[t]) return;
   const uint32_t i = t / D, d = t % D + 1u;
   LinkPair q;
-  if (!link_pair(f, het_ordinal(f.strand[i], i, f.rank[i], *f.n1), (int)d, q)) return;
+  if (!link_pair(f, site_ordinal(f.strand[i], i, f.rank[i], *f.n1), (int)d, q)) return;
   const uint32_t r = out_off[t];
   o.rname[r] = f.rname[i]; o.strand[r] = f.strand[i]; o.pos[r] = f.pos[i]; o.pos2[r] = q.pos2; o.context[r] = f.context[i];
   o.neighbour[r] = (int32_t)d; o.nreads[r] = (int32_t)q.n;
@@ -199,8 +199,8 @@ __device__ __forceinline__ bool link_linked(const LinkFinish &f, uint32_t g, int
 __device__ __forceinline__ uint32_t link_seg_start(const LinkFinish &f, uint32_t e) { const uint32_t n1 = *f.n1; return e < n1 ? 0u : n1; }
 
 // back[e]: the leading d = 1, 2, ... for which pair (e - d, d) is linked (a pair never leaves e's sequence and strand)
-__global__ __launch_bounds__(HET_WG) void k_link_back(LinkFinish f, double min_r2, uint8_t *__restrict__ back) {
-  const uint32_t e = blockIdx.x * (uint32_t)HET_WG + threadIdx.x;
+__global__ __launch_bounds__(SITE_WG) void k_link_back(LinkFinish f, double min_r2, uint8_t *__restrict__ back) {
+  const uint32_t e = blockIdx.x * (uint32_t)SITE_WG + threadIdx.x;
   if (e >= f.N) return;
   const uint32_t s0 = link_seg_start(f, e);
   int t = 0;
@@ -216,9 +216,9 @@ __device__ __forceinline__ bool link_strand_head(const LinkFinish &f, uint32_t e
 
 // A thread per run head walks its run [e, next run head): blocks are built greedily, a block's length and the mean of its
 // adjacent r^2 values (summed in ascending site order) go to its first site.  blen is zero elsewhere (memset by the host).
-__global__ __launch_bounds__(HET_WG) void k_link_blocks(LinkFinish f, double min_r2, int32_t min_sites, const uint8_t *__restrict__ back,
+__global__ __launch_bounds__(SITE_WG) void k_link_blocks(LinkFinish f, double min_r2, int32_t min_sites, const uint8_t *__restrict__ back,
                                                         uint32_t *__restrict__ blen, double *__restrict__ bmean) {
-  const uint32_t h = blockIdx.x * (uint32_t)HET_WG + threadIdx.x;
+  const uint32_t h = blockIdx.x * (uint32_t)SITE_WG + threadIdx.x;
   if (h >= f.N) return;
   if (back[h] != 0 && !link_strand_head(f, h)) return;
   const uint32_t n1 = *f.n1, seg_end = h < n1 ? n1 : f.N;
@@ -242,10 +242,10 @@ __global__ __launch_bounds__(HET_WG) void k_link_blocks(LinkFinish f, double min
   }
 }
 
-__global__ __launch_bounds__(HET_WG) void k_link_block_flag(LinkFinish f, const uint32_t *__restrict__ blen, uint32_t *__restrict__ flag) {
-  const uint32_t i = blockIdx.x * (uint32_t)HET_WG + threadIdx.x;
+__global__ __launch_bounds__(SITE_WG) void k_link_block_flag(LinkFinish f, const uint32_t *__restrict__ blen, uint32_t *__restrict__ flag) {
+  const uint32_t i = blockIdx.x * (uint32_t)SITE_WG + threadIdx.x;
   if (i >= f.N) return;
-  flag[i] = blen[het_ordinal(f.strand[i], i, f.rank[i], *f.n1)] ? 1u : 0u;
+  flag[i] = blen[site_ordinal(f.strand[i], i, f.rank[i], *f.n1)] ? 1u : 0u;
 }
 
 struct LinkBlockOut {
@@ -253,23 +253,23 @@ struct LinkBlockOut {
   double *mean_r2;
 };
 
-__global__ __launch_bounds__(HET_WG) void k_link_block_emit(LinkFinish f, const uint32_t *__restrict__ blen, const double *__restrict__ bmean,
+__global__ __launch_bounds__(SITE_WG) void k_link_block_emit(LinkFinish f, const uint32_t *__restrict__ blen, const double *__restrict__ bmean,
                                                             const uint32_t *__restrict__ flag, const uint32_t *__restrict__ out_off,
                                                             LinkBlockOut o) {
-  const uint32_t i = blockIdx.x * (uint32_t)HET_WG + threadIdx.x;
+  const uint32_t i = blockIdx.x * (uint32_t)SITE_WG + threadIdx.x;
   if (i >= f.N || !flag[i]) return;
-  const uint32_t g = het_ordinal(f.strand[i], i, f.rank[i], *f.n1), len = blen[g], r = out_off[i];
+  const uint32_t g = site_ordinal(f.strand[i], i, f.rank[i], *f.n1), len = blen[g], r = out_off[i];
   o.rname[r] = f.rname[i]; o.strand[r] = f.strand[i]; o.start[r] = f.pos[i];
-  o.end[r] = het_key_pos(f.key[g + len - 1u]);               // the walk stayed inside the strand part
+  o.end[r] = table_key_pos(f.key[g + len - 1u]);               // the walk stayed inside the strand part
   o.nsites[r] = (int32_t)len;
   o.mean_r2[r] = bmean[g];
 }
 
 static void link_finish_args(const epi_batch *b, LinkFinish &f) {
   f.N = site_view_args(b, f);
-  f.D = b->sites.D;
+  f.D = b->sites.link.D;
   f.min_reads = b->sites.min_reads;
-  f.max_dist = b->sites.max_dist;
+  f.max_dist = b->sites.link.max_dist;
 }
 
 static int link_report(epi_batch *b, const char *ctx, int D, int32_t max_dist, double max_oo, int32_t min_reads, hipStream_t s,
@@ -277,23 +277,23 @@ static int link_report(epi_batch *b, const char *ctx, int D, int32_t max_dist, d
   SiteReportState &t = b->sites;
   // (a) the site table
   int64_t nsite = 0;
-  EPI_TRY(het_cx_sites(b, ctx, s, "epi_batch_linkage_report_dev", &nsite));
-  t.nsite = nsite; t.D = D;
+  EPI_TRY(site_cx_report(b, ctx, s, "epi_batch_linkage_report_dev", &nsite));
+  t.nsite = nsite; t.link.D = D;
   t.min_reads = (uint32_t)(min_reads > 1 ? min_reads : 1);
-  t.max_dist = max_dist;
-  t.blocks = false; t.nblock = 0;
+  t.link.max_dist = max_dist;
+  t.link.blocks = false; t.link.nblock = 0;
   if (nsite < 2) { b->last_kind = KIND_LINK; b->last_nrow = 0; t.nsite = 0; return EPI_OK; }
   const int64_t cbytes = link_counter_bytes(nsite, D);
   if (cbytes < 0)
     return fail(EPI_ERR_ARG, "epi_batch_linkage_report_dev: %lld sites x %d neighbours need %lld bytes of counters, above the cap of %lld",
                 (long long)nsite, D, (long long)(nsite * D * 16), (long long)kLinkCountsCap);
   const size_t N = (size_t)nsite, ND = N * (size_t)D;
-  const int64_t nb_pairs = ((int64_t)ND + HET_WG - 1) / HET_WG;
+  const int64_t nb_pairs = ((int64_t)ND + SITE_WG - 1) / SITE_WG;
   bool wide = false;
-  const int64_t nb_rows = het_count_blocks(b, &wide);
-  EPI_TRY(check_grid(nb_pairs, HET_WG, "linkage pair kernels"));
-  EPI_TRY(check_grid(nb_rows, HET_WG, "linkage counting kernel"));
-  EPI_TRY(het_site_table(b, nsite, s));
+  const int64_t nb_rows = site_count_blocks(b, &wide);
+  EPI_TRY(check_grid(nb_pairs, SITE_WG, "linkage pair kernels"));
+  EPI_TRY(check_grid(nb_rows, SITE_WG, "linkage counting kernel"));
+  EPI_TRY(site_table(b, nsite, s));
   EPI_TRY(t.counts.ensure((size_t)cbytes));
   EPI_TRY(t.flag.ensure(ND * 4));                            // (the site table is done with its N words)
   EPI_TRY(t.out.ensure(ND * 4));
@@ -302,19 +302,19 @@ static int link_report(epi_batch *b, const char *ctx, int D, int32_t max_dist, d
   // (b) the 2 x 2 tables
   EPI_HIP(hipMemsetAsync(t.counts.p, 0, (size_t)cbytes, s));
   LinkArgs a;
-  het_rows_args(b, ctx_mask_of(ctx), max_oo, a);
+  site_rows_args(b, ctx_mask_of(ctx), max_oo, a);
   a.D = D;
   a.counts = t.counts.as<uint32_t>();
   prof_begin("link_count", s);
-  if (wide) hipLaunchKernelGGL((k_link_count<64>), dim3((unsigned)nb_rows), dim3(HET_WG), 0, s, a);
-  else hipLaunchKernelGGL((k_link_count<16>), dim3((unsigned)nb_rows), dim3(HET_WG), 0, s, a);
+  if (wide) hipLaunchKernelGGL((k_link_count<64>), dim3((unsigned)nb_rows), dim3(SITE_WG), 0, s, a);
+  else hipLaunchKernelGGL((k_link_count<16>), dim3((unsigned)nb_rows), dim3(SITE_WG), 0, s, a);
   prof_end("link_count", s);
   EPI_HIP(hipGetLastError());
 
   // (c) which pairs are reported, and where
   LinkFinish f;
   link_finish_args(b, f);
-  hipLaunchKernelGGL(k_link_keep, dim3((unsigned)nb_pairs), dim3(HET_WG), 0, s, f, flag);
+  hipLaunchKernelGGL(k_link_keep, dim3((unsigned)nb_pairs), dim3(SITE_WG), 0, s, f, flag);
   EPI_HIP(hipGetLastError());
   EPI_TRY(site_rows(b, flag, (int64_t)ND, t.out.as<uint32_t>(), &t.scalars()->nrow, s, nrow_out));
   b->last_kind = KIND_LINK;
@@ -325,26 +325,26 @@ static int link_report(epi_batch *b, const char *ctx, int D, int32_t max_dist, d
 // (d) the blocks of the last linkage report on b
 static int link_blocks(epi_batch *b, double min_r2, int32_t min_sites, hipStream_t s, int64_t *nblock_out) {
   SiteReportState &t = b->sites;
-  t.blocks = false; t.nblock = 0;
+  t.link.blocks = false; t.link.nblock = 0;
   const size_t N = (size_t)t.nsite;
-  if (N == 0) { t.blocks = true; return EPI_OK; }
-  const unsigned nb = (unsigned)(((int64_t)N + HET_WG - 1) / HET_WG);
-  EPI_TRY(t.back.ensure(N));
-  EPI_TRY(t.blen.ensure(N * 4));
-  EPI_TRY(t.bmean.ensure(N * 8));
-  EPI_TRY(t.bflag.ensure(N * 4));
-  EPI_TRY(t.bout.ensure(N * 4));
+  if (N == 0) { t.link.blocks = true; return EPI_OK; }
+  const unsigned nb = (unsigned)(((int64_t)N + SITE_WG - 1) / SITE_WG);
+  EPI_TRY(t.link.back.ensure(N));
+  EPI_TRY(t.link.blen.ensure(N * 4));
+  EPI_TRY(t.link.bmean.ensure(N * 8));
+  EPI_TRY(t.link.bflag.ensure(N * 4));
+  EPI_TRY(t.link.bout.ensure(N * 4));
   LinkFinish f;
   link_finish_args(b, f);
-  uint32_t *blen = t.blen.as<uint32_t>(), *flag = t.bflag.as<uint32_t>();
+  uint32_t *blen = t.link.blen.as<uint32_t>(), *flag = t.link.bflag.as<uint32_t>();
   EPI_HIP(hipMemsetAsync(blen, 0, N * 4, s));
-  hipLaunchKernelGGL(k_link_back, dim3(nb), dim3(HET_WG), 0, s, f, min_r2, t.back.as<uint8_t>());
-  hipLaunchKernelGGL(k_link_blocks, dim3(nb), dim3(HET_WG), 0, s, f, min_r2, min_sites, t.back.as<uint8_t>(), blen, t.bmean.as<double>());
-  hipLaunchKernelGGL(k_link_block_flag, dim3(nb), dim3(HET_WG), 0, s, f, blen, flag);
+  hipLaunchKernelGGL(k_link_back, dim3(nb), dim3(SITE_WG), 0, s, f, min_r2, t.link.back.as<uint8_t>());
+  hipLaunchKernelGGL(k_link_blocks, dim3(nb), dim3(SITE_WG), 0, s, f, min_r2, min_sites, t.link.back.as<uint8_t>(), blen, t.link.bmean.as<double>());
+  hipLaunchKernelGGL(k_link_block_flag, dim3(nb), dim3(SITE_WG), 0, s, f, blen, flag);
   EPI_HIP(hipGetLastError());
-  EPI_TRY(site_rows(b, flag, (int64_t)N, t.bout.as<uint32_t>(), &t.scalars()->nblock, s, nblock_out));
-  t.blocks = true;
-  t.nblock = *nblock_out;
+  EPI_TRY(site_rows(b, flag, (int64_t)N, t.link.bout.as<uint32_t>(), &t.scalars()->nblock, s, nblock_out));
+  t.link.blocks = true;
+  t.link.nblock = *nblock_out;
   return EPI_OK;
 }
 
@@ -382,7 +382,7 @@ int epi_batch_linkage_report_dev(epi_batch *b, const char *ctx, int max_neighbou
 int epi_batch_linkage_fetch_dev(epi_batch *b, int32_t *const d_icols[11], double *const d_dcols[3], void *stream) {
   hipStream_t s = nullptr;
   int64_t nrow = 0;
-  EPI_TRY(site_fetch_begin("epi_batch_linkage_fetch_dev", b, KIND_LINK, false, d_icols, 11, d_dcols, 3, stream, &s, &nrow));
+  EPI_TRY(site_fetch_begin("epi_batch_linkage_fetch_dev", b, KIND_LINK, "linkage report", false, d_icols, 11, d_dcols, 3, stream, &s, &nrow));
   if (nrow == 0) return EPI_OK;
   LinkFinish f;
   link_finish_args(b, f);
@@ -390,8 +390,8 @@ int epi_batch_linkage_fetch_dev(epi_batch *b, int32_t *const d_icols[11], double
   o.rname = d_icols[0]; o.strand = d_icols[1]; o.pos = d_icols[2]; o.pos2 = d_icols[3]; o.context = d_icols[4];
   o.neighbour = d_icols[5]; o.nreads = d_icols[6]; o.uu = d_icols[7]; o.mu = d_icols[8]; o.um = d_icols[9]; o.mm = d_icols[10];
   o.cov = d_dcols[0]; o.r2 = d_dcols[1]; o.dprime = d_dcols[2];
-  const unsigned nb = (unsigned)(((int64_t)f.N * f.D + HET_WG - 1) / HET_WG);
-  hipLaunchKernelGGL(k_link_emit, dim3(nb), dim3(HET_WG), 0, s, f, b->sites.flag.as<uint32_t>(), b->sites.out.as<uint32_t>(), o);
+  const unsigned nb = (unsigned)(((int64_t)f.N * f.D + SITE_WG - 1) / SITE_WG);
+  hipLaunchKernelGGL(k_link_emit, dim3(nb), dim3(SITE_WG), 0, s, f, b->sites.flag.as<uint32_t>(), b->sites.out.as<uint32_t>(), o);
   EPI_HIP(hipGetLastError());
   return EPI_OK;
 }
@@ -409,16 +409,16 @@ int epi_batch_linkage_blocks_dev(epi_batch *b, double min_r2, int32_t min_sites,
 int epi_batch_linkage_blocks_fetch_dev(epi_batch *b, int32_t *const d_icols[5], double *const d_dcols[1], void *stream) {
   hipStream_t s = nullptr;
   int64_t nblock = 0;
-  EPI_TRY(site_fetch_begin("epi_batch_linkage_blocks_fetch_dev", b, KIND_LINK, true, d_icols, 5, d_dcols, 1, stream, &s, &nblock));
+  EPI_TRY(site_fetch_begin("epi_batch_linkage_blocks_fetch_dev", b, KIND_LINK, "epi_batch_linkage_blocks_dev", true, d_icols, 5, d_dcols, 1, stream, &s, &nblock));
   if (nblock == 0) return EPI_OK;
   LinkFinish f;
   link_finish_args(b, f);
   LinkBlockOut o;
   o.rname = d_icols[0]; o.strand = d_icols[1]; o.start = d_icols[2]; o.end = d_icols[3]; o.nsites = d_icols[4];
   o.mean_r2 = d_dcols[0];
-  const unsigned nb = (unsigned)(((int64_t)f.N + HET_WG - 1) / HET_WG);
-  hipLaunchKernelGGL(k_link_block_emit, dim3(nb), dim3(HET_WG), 0, s, f, b->sites.blen.as<uint32_t>(), b->sites.bmean.as<double>(),
-                     b->sites.bflag.as<uint32_t>(), b->sites.bout.as<uint32_t>(), o);
+  const unsigned nb = (unsigned)(((int64_t)f.N + SITE_WG - 1) / SITE_WG);
+  hipLaunchKernelGGL(k_link_block_emit, dim3(nb), dim3(SITE_WG), 0, s, f, b->sites.link.blen.as<uint32_t>(), b->sites.link.bmean.as<double>(),
+                     b->sites.link.bflag.as<uint32_t>(), b->sites.link.bout.as<uint32_t>(), o);
   EPI_HIP(hipGetLastError());
   return EPI_OK;
 }

@@ -45,10 +45,6 @@ __device__ __forceinline__ Seg seg_combine(Seg left, Seg right) {   // state aft
   return r;
 }
 
-// nibble -> flags: 1 member (in context, methylated), 2 cut (in context, unmethylated), 4 skipped ('+'/'-'/filler, :187),
-// 8 / 16 out-of-context methylated / unmethylated (:176-177).  Built on the host from the context string.
-struct MhlLut { uint32_t lo0, lo1, hi0, hi1; };
-
 // Per-byte bit masks of the 16*C bytes a lane owns: u32 for C = 2, u64 for C = 3, 4.
 template <int C> struct MaskOf { using T = uint64_t; };
 template <> struct MaskOf<2> { using T = uint32_t; };
@@ -62,14 +58,6 @@ __device__ __forceinline__ int bm_msb(uint32_t x) { return 31 - __clz(x); }     
 __device__ __forceinline__ int bm_msb(uint64_t x) { return 63 - __clzll((long long)x); }
 template <class M> __device__ __forceinline__ M bm_below(int n) {                              // bits [0, n), 0 <= n <= width
   return n >= (int)(8 * sizeof(M)) ? ~(M)0 : (((M)1 << n) - (M)1);
-}
-
-// bit `bit` of the four bytes of f as a nibble
-__device__ __forceinline__ uint32_t plane_nibble(uint32_t f, int bit) {
-  uint32_t t = (f >> bit) & 0x01010101u;
-  t |= t >> 7;
-  t |= t >> 14;
-  return t & 0xFu;
 }
 
 // The 16*C bytes at g0 (16-byte aligned) of the row [rs,re), loaded (so that a caller can have the next chunk's loads
@@ -158,13 +146,12 @@ __device__ __forceinline__ ST mhl_wave_scan(ST v) {
   return v;
 }
 
-
 // ---- host helpers defined in mhl_report.hip ---------------------------------------------------------------------------
 size_t mhl_pool_rows(const epi_batch *b);
 int ensure_mhl_pool(epi_batch *b, size_t rows);
 int mhl_layout_pool(epi_batch *b, uint32_t &slot_state, int T, int32_t nt, size_t headroom, PoolLayout *l);
 int pick_mhl_group(int32_t max_len);             // lanes per read x chunks per lane as G * 8 + C (0: longer than 64 lanes cover)
-MhlLut make_mhl_lut(uint32_t ctx_mask);
+ClassLut make_mhl_lut(uint32_t ctx_mask);
 // Tail of the second half of a sharded report, either path: the tiles' row offsets, the one synchronisation, the pool
 // check, the finished report's state
 int mhl_finish_rows(epi_batch *b, hipStream_t s, int64_t *nrow_out);

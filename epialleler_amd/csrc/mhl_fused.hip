@@ -24,7 +24,7 @@
 //     (((pk & 7..7) ^ k..k) + 7..7: bit 3 of a nibble says "not this context"; the case bit of a code is its bit 3) -- plain
 //     two-operand VALU -- and ONE v_dot4 per plane and pair of dwords gathers the flags of eight bytes into a mask byte.
 //   * The out-of-context counts need no positions: 2-bit fields of a 16-entry byte LUT (two v_perm_b32 and an XOR,
-//     lut16_xor_form in common.hpp), summed field-wise and by v_sad_u8 (the per_read.hip scheme).
+//     lut16_xor_form in xm_codes.hpp), summed field-wise and by v_sad_u8 (the per_read.hip scheme).
 //   * Skipped ('+', '-', filler) and stray codes (nibbles 3, 4, 8, 9 alias the reference's sum / coverage slots) only raise
 //     a flag in the counting LUT; a lane that sees one builds that plane from the bytes it STILL HOLDS in registers
 //     (mhlf_eq_plane) -- nothing is reloaded.  The fast variant hands a tile with a stray code to the WIDE one.
@@ -88,7 +88,7 @@ struct MhlFArgs {
   int64_t xm_cap;                         // readable bytes behind xm
   const Tile *tiles;
   uint32_t k7;                            // the context's methylated code (2, 6 or 7) in every byte
-  MhlLut lut2;                            // counting LUT: bit 0 out-of-context methylated, bit 2 skipped (code 11), bit 4
+  ClassLut lut2;                          // counting LUT: bit 0 out-of-context methylated, bit 2 skipped (code 11), bit 4
                                           // out-of-context unmethylated, bit 6 stray (nibbles 3, 4, 8, 9)
   int32_t hmin;
   const uint32_t *keep_tab;               // [n] = passing out-of-context methylated counts for n out-of-context calls
@@ -234,23 +234,17 @@ __device__ __forceinline__ void mhlf_planes(const uint32_t (&ww)[4 * C], uint32_
   if constexpr (sizeof(M) == 8) { U |= (M)uhi << 32; N |= (M)nhi << 32; }
 }
 
-// 16-entry byte LUT lookup of the four codes of a dword in two v_perm_b32 (F: a table in lut16_xor_form, common.hpp)
-__device__ __forceinline__ uint32_t mhlf_lut4(uint32_t w, const MhlLut &F) {
-  const uint32_t sel = w & 0x0F0F0F0Fu;
-  return __builtin_amdgcn_perm(F.lo1, F.lo0, sel) ^ __builtin_amdgcn_perm(F.hi1, F.hi0, sel ^ 0x08080808u);
-}
-
 // Out-of-context counts of the lane and its rare-code flags: the LUT byte's bits 0, 2, 4, 6 are 2-bit fields (three
 // dwords add without a carry); fields 0 and 4 (the counts) go on as 4-bit fields (<= 12) into v_sad_u8, fields 2 and 6
 // (skipped, stray) are only OR-ed.  Returns oom | oou << 8 | (any skipped) << 16 | (any stray) << 24.
 template <int C>
-__device__ __forceinline__ uint32_t mhlf_counts(const uint32_t (&ww)[4 * C], const MhlLut &lut2) {
+__device__ __forceinline__ uint32_t mhlf_counts(const uint32_t (&ww)[4 * C], const ClassLut &lut2) {
   uint32_t E = 0, rare = 0, oom = 0, oou = 0;
 #pragma unroll
   for (int g = 0; g < (4 * C + 2) / 3; g++) {
     uint32_t t = 0;
 #pragma unroll
-    for (int k = 0; k < 3; k++) if (3 * g + k < 4 * C) t += mhlf_lut4(ww[3 * g + k], lut2);
+    for (int k = 0; k < 3; k++) if (3 * g + k < 4 * C) t += lut16_xor(ww[3 * g + k], lut2);
     E += t & 0x33333333u;
     rare |= t;
     if (g % 4 == 3 || g == (4 * C + 2) / 3 - 1) {
@@ -259,7 +253,7 @@ __device__ __forceinline__ uint32_t mhlf_counts(const uint32_t (&ww)[4 * C], con
       E = 0;
     }
   }
-  return oom | (oou << 8) | ((rare & 0x0C0C0C0Cu) ? 1u << 16 : 0u) | ((rare & 0xC0C0C0C0u) ? 1u << 24 : 0u);
+  return oom | (oou << 8) | ((rare & (0x03030303u << 2)) ? 1u << 16 : 0u) | ((rare & (0x03030303u << 6)) ? 1u << 24 : 0u);
 }
 
 // bit plane "code == c" (c: 4 bits) of the lane's bytes: t = (w ^ c) & 15 is 0 iff equal, t + 15 has bit 4 set iff not
@@ -856,23 +850,17 @@ __global__ __launch_bounds__(MHLF_WG) void k_mhlf_emit_slab(MhlFArgs a, const in
 // ---- host side -------------------------------------------------------------------------------------------------------
 
 // counting LUT of the fused kernel (MhlFArgs::lut2) for one context set (rcpp_mhl_report.cpp:104-107, :176-177, :187)
-static MhlLut make_mhlf_lut2(uint32_t ctx_mask) {
-  uint32_t w[4] = {0, 0, 0, 0};
+static ClassLut make_mhlf_lut2(uint32_t ctx_mask) {
+  uint8_t f[16];
   for (uint32_t code = 0; code < 16; code++) {
     const bool in = (ctx_mask >> code) & 1u;
-    uint32_t f = 0;
-    if (!in && ((0x00E4u >> code) & 1u)) f |= 1u;            // codes 2, 5, 6, 7 outside the context: methylated
-    if (!in && ((0xE400u >> code) & 1u)) f |= 16u;           // codes 10, 13, 14, 15: unmethylated
-    if (code == 11) f |= 4u;                                 // skipped (:187)
-    if (code == 3 || code == 4 || code == 8 || code == 9) f |= 64u;   // their counters are sums / the coverage slot (:190-194)
-    w[code >> 2] |= f << (8 * (code & 3));
+    f[code] = 0;
+    if (!in && ((kXmMethMask >> code) & 1u)) f[code] |= 1u;      // methylated outside the context
+    if (!in && ((kXmUnmethMask >> code) & 1u)) f[code] |= 16u;   // unmethylated
+    if (code == kXmSkip) f[code] |= 4u;                          // skipped (:187)
+    if (code == 3 || code == 4 || code == 8 || code == 9) f[code] |= 64u;   // their counters are sums / the coverage slot (:190-194)
   }
-  ClassLut d;
-  d.lo0 = w[0]; d.lo1 = w[1]; d.hi0 = w[2]; d.hi1 = w[3];
-  const ClassLut x = lut16_xor_form(d);                      // (the form mhlf_lut4 looks up)
-  MhlLut l;
-  l.lo0 = x.lo0; l.lo1 = x.lo1; l.hi0 = x.hi0; l.hi1 = x.hi1;
-  return l;
+  return lut16_xor_form(lut16_pack(f));                      // (the form lut16_xor looks up)
 }
 
 // Lane shape of the one-pass kernel as G * 100 + CA * 10 + CB: the smallest G * 16 * (CA + CB) that holds the longest row

@@ -37,18 +37,14 @@
 
 namespace epi {
 
-
-
 struct MhlRec { uint32_t first, last, m; };       // bytes [first,last] of the row; m = members of the stretch, 0 = counted run
-
-
 
 struct RowsArgs {
   const uint8_t *xm;
   const int64_t *off;                     // row r owns xm[off[r] .. off[r] + len[r])
   const int32_t *len;
   int64_t n;
-  MhlLut lut;
+  ClassLut lut;
   int32_t hmin;
   double max_oo;
   int4 *rowinfo;                          // per read: h or -1 (dropped), 1 if it has skipped bytes, (first record, records) of the read
@@ -61,8 +57,6 @@ struct RowsArgs {
   uint32_t *cont;                         // multi: members entering a block from the right
   uint32_t *max_h;                        // largest haplotype size among the kept reads (sizes the LDS sums of pass 2)
 };
-
-
 
 template <int C>
 __device__ __forceinline__ ChunkRaw<C> mhl_chunk_load(const uint8_t *__restrict__ xm, int64_t g0, bool live, int64_t rs, int64_t re) {
@@ -88,7 +82,7 @@ __device__ __forceinline__ ChunkRaw<C> mhl_chunk_load(const uint8_t *__restrict_
 
 // ... and turned into per-byte bit masks.
 template <int C>
-__device__ __forceinline__ Chunk<typename MaskOf<C>::T> mhl_chunk_masks(const ChunkRaw<C> &r, const MhlLut &lut) {
+__device__ __forceinline__ Chunk<typename MaskOf<C>::T> mhl_chunk_masks(const ChunkRaw<C> &r, const ClassLut &lut) {
   using M = typename MaskOf<C>::T;
   constexpr int W = 16 * C;
   Chunk<M> c = {0, 0, 0, 0, 0u, 0u};
@@ -108,10 +102,7 @@ __device__ __forceinline__ Chunk<typename MaskOf<C>::T> mhl_chunk_masks(const Ch
 #pragma unroll
     for (int h = 0; h < 2; h++) {
       const int d = 2 * e + h;
-      const uint32_t lo3 = r.ww[d] & 0x07070707u;           // low three bits of the codes; bit 3 picks the LUT half
-      const uint32_t pick = ((r.ww[d] >> 1) & 0x04040404u) | 0x03020100u;
-      uint32_t v = __builtin_amdgcn_perm(__builtin_amdgcn_perm(lut.hi1, lut.hi0, lo3),
-                                         __builtin_amdgcn_perm(lut.lo1, lut.lo0, lo3), pick);
+      uint32_t v = lut16_pick(r.ww[d], lut);
       if (edge) {
         int a = lo - 4 * d, b = hi - 4 * d;                   // valid bytes [a, b) of this dword
         a = a < 0 ? 0 : (a > 4 ? 4 : a);
@@ -146,11 +137,9 @@ __device__ __forceinline__ Chunk<typename MaskOf<C>::T> mhl_chunk_masks(const Ch
 
 template <int C>
 __device__ __forceinline__ Chunk<typename MaskOf<C>::T> mhl_chunk(const uint8_t *__restrict__ xm, int64_t g0, bool live,
-                                                                   int64_t rs, int64_t re, const MhlLut &lut) {
+                                                                   int64_t rs, int64_t re, const ClassLut &lut) {
   return mhl_chunk_masks<C>(mhl_chunk_load<C>(xm, g0, live, rs, re), lut);
 }
-
-
 
 // Span bytes of the chunk: bytes that have a member of their stretch at or before them AND at or after them
 // (segmented fills of the member bits, stopped by cuts; `enter` / `cont` = members of the open segment in the lanes
@@ -199,11 +188,8 @@ __device__ __forceinline__ void write_runs(M bits, bool stretch, const Chunk<M> 
 }
 
 __device__ __forceinline__ bool mhl_keep(uint32_t h, uint32_t oo_m, uint32_t oo_u, int32_t hmin, double max_oo) {
-  const double frac = (double)oo_m / (double)((uint64_t)oo_m + oo_u);      // :178 (0/0 = NaN -> kept)
-  return !((int)h < hmin || frac > max_oo);                                // :179
+  return !((int)h < hmin) && read_rule_keeps(1, oo_m, oo_u, max_oo);       // :179 (the row's length plays no part here)
 }
-
-
 
 // Reads that fit one block of G lanes x 16*C bytes (every read of a short-read batch): 256/G reads per workgroup.
 template <int G, int C>
@@ -952,21 +938,19 @@ int pick_mhl_group(int32_t max_len) {
   return best;
 }
 
-// nibble -> MhlLut flags for one context set (rcpp_mhl_report.cpp:104-107, :176-177, :187)
-MhlLut make_mhl_lut(uint32_t ctx_mask) {
-  uint32_t w[4] = {0, 0, 0, 0};
+// nibble -> flags for one context set (rcpp_mhl_report.cpp:104-107): 1 member (in context, methylated), 2 cut (in context,
+// unmethylated), 4 skipped ('+'/'-'/filler, :187), 8 / 16 out-of-context methylated / unmethylated (:176-177)
+ClassLut make_mhl_lut(uint32_t ctx_mask) {
+  uint8_t f[16];
   for (uint32_t code = 0; code < 16; code++) {
     const bool in = (ctx_mask >> code) & 1u;
-    uint32_t f = 0;
-    if (in) f |= code < 8 ? 1u : 2u;
-    if (code == 11) f |= 4u;
-    if (!in && ((0x00E4u >> code) & 1u)) f |= 8u;            // codes 2,5,6,7
-    if (!in && ((0xE400u >> code) & 1u)) f |= 16u;           // codes 10,13,14,15
-    w[code >> 2] |= f << (8 * (code & 3));
+    f[code] = 0;
+    if (in) f[code] |= code < 8 ? 1u : 2u;
+    if (code == kXmSkip) f[code] |= 4u;
+    if (!in && ((kXmMethMask >> code) & 1u)) f[code] |= 8u;
+    if (!in && ((kXmUnmethMask >> code) & 1u)) f[code] |= 16u;
   }
-  MhlLut l;
-  l.lo0 = w[0]; l.lo1 = w[1]; l.hi0 = w[2]; l.hi1 = w[3];
-  return l;
+  return lut16_pack(f);
 }
 
 // ---- the two-kernel report on the host ----------------------------------------------------------------------------------

@@ -24,15 +24,14 @@ namespace epi {
 #endif
 constexpr int PR_UN = EPI_PR_UN;   // 16-byte loads a lane keeps in flight
 
-struct Luts { ClassLut c[4]; };                     // weight bytes per class (ClassLut, ThrParams: common.hpp)
+struct Luts { ClassLut c[4]; };                     // weight bytes per class (ClassLut: xm_codes.hpp; ThrParams: common.hpp)
 
 static int make_lut(const char *s, ClassLut *out) {
   unsigned w[16] = {0};
   if (s) for (const unsigned char *c = reinterpret_cast<const unsigned char *>(s); *c; c++) w[ctx_to_idx(*c)]++;
   for (int i = 0; i < 16; i++)
     if (w[i] > 255) return fail(EPI_ERR_ARG, "context string repeats a letter more than 255 times");
-  auto pack = [&](int b) { return (uint32_t)(w[b] | (w[b + 1] << 8) | (w[b + 2] << 16) | (w[b + 3] << 24)); };
-  out->lo0 = pack(0); out->lo1 = pack(4); out->hi0 = pack(8); out->hi1 = pack(12);
+  *out = lut16_pack(w);
   return EPI_OK;
 }
 
@@ -42,9 +41,9 @@ __device__ __forceinline__ void acc_dword(uint32_t w, uint32_t mask, const Luts 
   acc[0] |= w & mask;                                   // timing experiment: loads only
   return;
 #endif
+  // lut16_pick (xm_codes.hpp) written out: the NCLS tables share one pair of selectors
   const uint32_t v = w & 0x0F0F0F0Fu;                 // unpack_ctx_idx, four codes
   const uint32_t lo3 = v & 0x07070707u;
-  // per byte: take the codes-8..15 lookup when bit 3 of the code is set (selector j + 4*bit3)
   const uint32_t pick = 0x03020100u | ((v >> 1) & 0x04040404u);
 #pragma unroll
   for (int k = 0; k < NCLS; k++) {
@@ -154,12 +153,6 @@ __global__ __launch_bounds__(256) void k_per_read(const uint8_t *__restrict__ xm
 constexpr int PW_NU = 3;     // 16-byte loads per lane and read
 constexpr int PW_RPG = 4;    // reads per lane group
 
-__device__ __forceinline__ uint32_t pw_lut(uint32_t w, const ClassLut &F) {
-  const uint32_t lo3 = w & 0x07070707u;
-  const uint32_t pick = ((w >> 1) & 0x04040404u) | 0x03020100u;
-  return __builtin_amdgcn_perm(__builtin_amdgcn_perm(F.hi1, F.hi0, lo3), __builtin_amdgcn_perm(F.lo1, F.lo0, lo3), pick);
-}
-
 // sum over the G lanes of a group (G <= 16: DPP inside a row of 16 lanes; 32, 64: two more shuffles)
 template <int G>
 __device__ __forceinline__ uint32_t pw_group_sum(uint32_t v) {
@@ -237,7 +230,7 @@ __global__ __launch_bounds__(256, (pw_waves<RPG>())) void k_per_read_wide(const 
       return;
 #endif
       const int g0 = k << 4;
-      uint32_t a = pw_lut(v.x, F), b = pw_lut(v.y, F), cc = pw_lut(v.z, F), d = pw_lut(v.w, F);
+      uint32_t a = lut16_pick(v.x, F), b = lut16_pick(v.y, F), cc = lut16_pick(v.z, F), d = lut16_pick(v.w, F);
       if (g0 < rs || g0 + 16 > re) {                    // first / last chunk of the read: mask foreign bytes
         a &= byte_range_mask32(rs - g0, re - g0);
         b &= byte_range_mask32(rs - g0 - 4, re - g0 - 4);
@@ -313,8 +306,7 @@ bool make_field_lut(const char *const cls[4], ClassLut *out) {
       f[i] |= w[i] << (2 * k);
     }
   }
-  auto pack = [&](int b) { return (uint32_t)(f[b] | (f[b + 1] << 8) | (f[b + 2] << 16) | (f[b + 3] << 24)); };
-  out->lo0 = pack(0); out->lo1 = pack(4); out->hi0 = pack(8); out->hi1 = pack(12);
+  *out = lut16_pack(f);
   return true;
 }
 

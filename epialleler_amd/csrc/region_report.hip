@@ -5,8 +5,8 @@
 // epi_batch_region_report_dev, has the interface.
 //
 // Definitions.  ctx: context letters in both cases; max_oo = max_ooctx_meth_frac.
-//  Kept rows   row x is kept by the lMHL read rule with hmin = 0 over the whole row (rcpp_mhl_report.cpp:172-179; the rule of
-//              het_common.hpp): o_m / (o_m + o_u) > max_oo drops it, o_m / o_u = its methylated (codes 2, 5, 6, 7) /
+//  Kept rows   row x is kept by the lMHL read rule with hmin = 0 over the whole row (rcpp_mhl_report.cpp:172-179; the verdict of
+//              xm_codes.hpp): o_m / (o_m + o_u) > max_oo drops it, o_m / o_u = its methylated (codes 2, 5, 6, 7) /
 //              unmethylated (10, 13, 14, 15) bytes whose code is not one of ctx's; 0 / 0 is NaN and keeps the row.
 //  Calls       of a kept row in region [start, end] on its rname: its bytes whose context code is one of ctx's letters and
 //              whose position start[x] + i - (strand == 2 ? reverse_offset : 0) lies in [start, end], in row order.
@@ -49,7 +49,7 @@
 //      does not fit int32 is reported, not wrapped.  The call's second synchronisation reads that verdict.
 #include "common.hpp"
 #include "pat_search.hpp"
-#include "het_common.hpp"
+#include "site_table.hpp"
 #include <math.h>
 #include <vector>
 
@@ -121,7 +121,7 @@ __device__ __forceinline__ void rgn_row(const RgnArgs &a, const RgnTarget &tg, i
   const uint32_t ulen = (uint32_t)len;                         // (unsigned: the step behind a row of 2^31 - 1 bytes does not wrap)
   for (uint32_t c = 0; __ballot(c < ulen) != 0ull; c += 4u * G) {
     const uint32_t my = c + 4u * sub;
-    uint32_t w = 0x0C0C0C0Cu;                                  // '.': in no class, no call
+    uint32_t w = kXmDot4;                                      // '.': in no class, no call
     if (my + 4u <= ulen) memcpy(&w, p + my, 4);
     else for (uint32_t j = 0; my + j < ulen; j++) w = (w & ~(0xFFu << (8 * j))) | ((uint32_t)p[my + j] << (8 * j));
     uint32_t vb = 0, mb = 0;
@@ -157,8 +157,7 @@ __device__ __forceinline__ void rgn_row(const RgnArgs &a, const RgnTarget &tg, i
   if (run) close_run();
 #pragma unroll
   for (int d = 1; d < G; d <<= 1) { om += __shfl_xor(om, d, 64); ou += __shfl_xor(ou, d, 64); }
-  const double frac = (double)om / (double)((uint64_t)om + ou);         // rcpp_mhl_report.cpp:178 (0 / 0 = NaN: kept)
-  if (!have || sub != 0 || frac > a.max_oo || n == 0) return;
+  if (!have || sub != 0 || !read_rule_keeps(1, om, ou, a.max_oo) || n == 0) return;   // (an empty row has n == 0)
   const uint32_t ms = (uint32_t)a.max_sites;
   add(RC_NREADS, 1u);
   if (n > ms) { add(RC_NLONG, 1u); return; }
@@ -311,11 +310,10 @@ static int rgn_report(epi_batch *b, const RgnCall &c, hipStream_t s) {
   a.xm = b->xm; a.off = b->off; a.len = b->len; a.strand = b->strand; a.start = b->start;
   a.stride = (uint32_t)(RGN_HDR + 3 * c.max_sites);
   a.ctx_mask = ctx_mask_of(c.ctx);
-  a.oom_mask = ((1u << 2) | (1u << 5) | (1u << 6) | (1u << 7)) & ~a.ctx_mask;           // rcpp_mhl_report.cpp:176-177
-  a.oou_mask = ((1u << 10) | (1u << 13) | (1u << 14) | (1u << 15)) & ~a.ctx_mask;
+  ooctx_masks(a.ctx_mask, &a.oom_mask, &a.oou_mask);
   a.min_sites = c.min_sites; a.max_sites = c.max_sites; a.reverse_offset = c.reverse_offset;
   a.u_max = c.u_max; a.m_min = c.m_min; a.max_oo = c.max_oo;
-  const bool wide = b->nbytes > kHetLongRow * b->n;           // long rows: a whole wave per pair
+  const bool wide = b->nbytes > kSiteLongRow * b->n;           // long rows: a whole wave per pair
   const int64_t ngrp = wide ? RGN_WG / 64 : RGN_WG / 16;      // pairs a workgroup walks at a time
 
   // (b) - (d) group by group

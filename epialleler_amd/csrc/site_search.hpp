@@ -5,7 +5,7 @@
 
 namespace epi {
 
-// (rname, pos) as one monotone 64-bit key
+// (rname, pos) as one monotone signed 64-bit key.  (Not site_table.hpp's unsigned table_key: they order a negative rname differently.)
 __device__ __forceinline__ int64_t site_key(int32_t c, int32_t p) { return (int64_t)c * 4294967296LL + ((int64_t)p + 2147483648LL); }
 
 // first i in [0, n) with key(chr[i], pos[i]) >= q, by the whole wavefront (uniform result): every step the 64 lanes probe

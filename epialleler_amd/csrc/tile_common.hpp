@@ -108,12 +108,9 @@ __device__ __forceinline__ RowSlice cx_row_slice(const RowCols &a, const Tile &t
 // wavefront always hit 32 different LDS banks.  Returns the stray-nibble flags (bits 6-7 of the LUT bytes).
 template <int T, int OFF, bool FIRST>
 __device__ __forceinline__ uint32_t cx_add_dword(uint32_t w, bool last, const RowSlice &m) {
-  const uint32_t lo3 = w & 0x07070707u;                  // low three bits of the four codes (unpack_ctx_idx)
-  // 16-entry byte LUT = two v_perm lookups (codes 0-7 / 8-15) + a third v_perm that picks, per byte,
-  // the second result when bit 3 of the code is set or the read is lower-cased (selector j + 4*bit3):
-  // no multiply, no masks
-  const uint32_t pick = ((w >> 1) & 0x04040404u) | m.pick0;
-  uint32_t s4 = __builtin_amdgcn_perm(__builtin_amdgcn_perm(kPkHi1, kPkHi0, lo3), __builtin_amdgcn_perm(kPkLo1, kPkLo0, lo3), pick);
+  // the codes' LUT bytes (unpack_ctx_idx); the second half for every byte when the read is lower-cased (m.pick0)
+  const ClassLut pk = {kPkLo0, kPkLo1, kPkHi0, kPkHi1};
+  uint32_t s4 = lut16_pick(w, pk, m.pick0);
   uint32_t vm = last ? m.mask_last : ~0u;
   if (FIRST) vm &= m.mask_first;
   s4 &= vm;

@@ -80,7 +80,7 @@ def test_fuzz_linkage_and_compare_inputs_cover_the_shapes():
             lk["high"] += bool(npair and want["pos2"].max() > TOP - 1000)
             lk["deep"] += bool(npair and want["nreads"].max() >= 256)
             lk["long_row"] += bool(L.max() > 4000)
-            lk["wide"] += bool(int(t["off"][-1]) > 512 * L.size)          # het_count_blocks: a whole wave takes a row
+            lk["wide"] += bool(int(t["off"][-1]) > 512 * L.size)          # site_count_blocks: a whole wave takes a row
             lk["three_both"] += bool(np.unique(t["rname"]).size >= 3 and set(np.unique(want["sites"]["strand"]).tolist()) >= {1, 2})
         ta, tb = t, p["sibling"]
         for call in p["cmp"]:

@@ -296,7 +296,7 @@ def test_deep_sites(ea, c, m):
 # ---- keys at the ends of int32 ---------------------------------------------------------------------------------------------------
 
 # The engine sets no limit on rname below int32 (epi_batch_upload takes any int32 column; the site table's key holds the
-# rname in its upper 32 bits, het_common.hpp): the largest rname is 2^31 - 1.
+# rname in its upper 32 bits, site_table.hpp): the largest rname is 2^31 - 1.
 MAX_RNAME = 2 ** 31 - 1
 
 

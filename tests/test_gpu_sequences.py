@@ -143,7 +143,7 @@ class Slot:
 
     def het(self, letters, sites, T, by="het"):
         """What a heterogeneity report does to the record (a linkage report and either side of a comparison do the same: all
-        go through het_cx_sites; `by` names which): its own CX report is a pool report without caller columns, for the
+        go through site_cx_report; `by` names which): its own CX report is a pool report without caller columns, for the
         upper-case letters of its context, all rows passing (`sites`: that table).  A record with the same contexts stays
         as it is, also one made under another pass vector (cx_keep_offsets); any other is replaced by this table's tile
         counts and row count.  -> the path's name"""
