@@ -12,6 +12,8 @@
 //     5. owners apply the rule to their shared tiles, rows are ordered: this rank's rows in table order.
 //   The rows of rank r precede those of rank r + 1 in the reference's table; fetch them with epi_batch_cx_fetch_* /
 //   epi_batch_mhl_fetch_* as after a single-GPU report.
+//   Steps 1 and 2 are shard_plan, steps 3 - 5 shard_exchange; an entry point supplies the values it gathers and how they
+//   become key ranges, its report's first half and its second half.
 //
 // librccl is loaded with dlopen on first use: the library itself (and every single-GPU caller) does not depend on it.
 #include "common.hpp"
@@ -131,12 +133,93 @@ void forced_keys(int64_t first, int64_t last, int n, std::vector<int64_t> *keys,
 
 struct epi_shard_plan {                         // what a (batch, tile grid, communicator) triple needs per report; remembered on the batch
   uint64_t comm_serial = 0;
-  int T = 0, kind = 0;                          // kind: 0 = CX, 1 = lMHL
+  SlabKind kind = SLAB_NONE;                    // the slabs its shared tiles add into (lMHL: whether all ranks can take the one-pass kernel)
+  int T = 0;                                    // positions per tile
   std::string ctx;                              // lMHL: the context string the plan was made for
   std::vector<int64_t> keys;
   std::vector<int32_t> owned;
-  bool fused = false;                           // lMHL: all ranks can take the one-pass kernel
 };
+
+namespace {
+
+// Steps 1, 2: the plan of this batch and communicator that `match` accepts, or a new one -- `mine` gives this rank's values,
+// one all-gather brings every rank's, `reduce` turns the gathered rows into the plan's kind and tile size and every rank's
+// (first, last) key range; shared keys and owners follow from the ranges.  Remembered on the batch.
+template <class Match, class Mine, class Reduce>
+int shard_plan(epi_batch *b, epi_comm *c, hipStream_t s, Match match, Mine mine, Reduce reduce, const epi_shard_plan **out) {
+  for (auto &p : b->shard.plans) if (p->comm_serial == c->serial && match(*p)) { *out = p.get(); return EPI_OK; }
+  std::vector<int64_t> vals, all, ranges((size_t)2 * c->world);
+  EPI_TRY(mine(vals));
+  EPI_TRY(all_gather_i64(c, vals.data(), (int)vals.size(), s, &all));
+  std::shared_ptr<epi_shard_plan> np(new epi_shard_plan());
+  np->comm_serial = c->serial;
+  reduce(all, np.get(), ranges.data());
+  std::vector<int32_t> owner;
+  if (c->world == 1 && c->test_shared > 0) forced_keys(ranges[0], ranges[1], c->test_shared, &np->keys, &owner);
+  else EPI_TRY(shared_keys_of(ranges, c->world, &np->keys, &owner));
+  np->owned.resize(owner.size());
+  for (size_t i = 0; i < owner.size(); i++) np->owned[i] = owner[i] == c->rank ? 1 : 0;
+  b->shard.plans.push_back(std::move(np));
+  *out = b->shard.plans.back().get();
+  return EPI_OK;
+}
+
+// Steps 3 - 5 for a plan: the library's slabs zeroed and attached; first_half(defer) runs the tile kernels as for a single GPU,
+// shared tiles into the slabs; the one data-path collective, ncclAllReduce(sum) of each slab, queued on the report's stream
+// behind them; second_half() has the owners emit their shared tiles and orders the rows.  Later single-GPU calls on this
+// batch emit every tile again: the slabs are detached on every way out.
+template <class First, class Second>
+int shard_exchange(epi_batch *b, epi_comm *c, const epi_shard_plan &plan, hipStream_t s, First first_half, Second second_half) {
+  ShardState &sh = b->shard;
+  const int32_t nshared = (int32_t)plan.keys.size();
+  const SlabShape shape = slab_shape(plan.kind, plan.T);
+  const size_t cnt_bytes = (size_t)nshared * shape.cnt * 4, sum_bytes = (size_t)nshared * shape.sum * 8;
+  auto attach = [&](const DevBuf &cnt) {
+    return attach_shared(b, plan.keys.data(), plan.owned.data(), nshared, plan.kind, cnt.as<int32_t>(), sum_bytes ? sh.lib_sum.as<int64_t>() : nullptr);
+  };
+  if (cnt_bytes) EPI_TRY(sh.lib_cnt.ensure(cnt_bytes));
+  if (sum_bytes) EPI_TRY(sh.lib_sum.ensure(sum_bytes));
+  int rc = attach(sh.lib_cnt);
+  if (rc == EPI_OK) rc = zero_shared_slabs(b, plan.T, s);
+  // ONE host synchronisation per CX report where the batch allows it (an earlier report found no ultra-deep tile the host
+  // would have to finish before the slab travels): the first half only queues its kernels, the all-reduce and the owners'
+  // emit are queued behind them, and everything is read back and checked once, in the second half.
+  if (rc == EPI_OK) rc = first_half(true);
+  if (rc == EPI_OK && nshared > 0) {
+    if (c->nccl) {
+      ncclResult_t r = rccl().AllReduce(sh.lib_cnt.p, sh.lib_cnt.p, cnt_bytes / 4, ncclInt32, ncclSum, c->nccl, s);
+      if (r == ncclSuccess && sum_bytes) r = rccl().AllReduce(sh.lib_sum.p, sh.lib_sum.p, sum_bytes / 8, ncclInt64, ncclSum, c->nccl, s);
+      if (r != ncclSuccess) rc = fail(EPI_ERR_HIP, "ncclAllReduce failed: %s", rccl().GetErrorString(r));
+      c->last_bytes = (int64_t)(cnt_bytes + sum_bytes);
+    }
+    if (rc == EPI_OK) rc = second_half();
+    if (rc == EPI_RETRY_POOL) {
+      // (deferred synchronisation only, so CX only) the row pool was too small: the first half again, with its own
+      // synchronisation -- it grows the pool -- into a scratch slab, the sum buffer a CX report leaves idle; the shared tiles
+      // are then emitted from the slab that is already reduced
+      rc = sum_bytes ? fail(EPI_ERR_STATE, "pool retry of a report whose sum slab is in use") : sh.lib_sum.ensure(cnt_bytes);
+      if (rc == EPI_OK) rc = attach(sh.lib_sum);
+      if (rc == EPI_OK) rc = zero_shared_slabs(b, plan.T, s);
+      if (rc == EPI_OK) rc = first_half(false);
+      if (rc == EPI_OK) rc = attach(sh.lib_cnt);
+      if (rc == EPI_OK) rc = second_half();
+    }
+  }
+  (void)attach_shared(b, nullptr, nullptr, 0, SLAB_NONE, nullptr, nullptr);   // detach
+  return rc;
+}
+
+// What both sharded entry points check and set up first
+int shard_begin(epi_batch *b, epi_comm *c, const char *ctx, int64_t *nrow_out, const char *who) {
+  if (!b || !c || !ctx || !nrow_out) return fail(EPI_ERR_ARG, "%s: NULL argument", who);
+  if (b->eng != c->eng) return fail(EPI_ERR_ARG, "%s: batch and communicator live on different engines", who);
+  EPI_HIP(hipSetDevice(b->eng->device));
+  *nrow_out = 0;
+  c->last_bytes = 0;
+  return EPI_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -196,145 +279,58 @@ void epi_comm_set_test_shared(epi_comm *c, int ntiles) { if (c) { c->test_shared
 int epi_batch_cytosine_report_sharded(epi_batch *b, epi_comm *c, const char *ctx_meth, const char *ctx_unmeth, const char *ooctx_meth,
                                       const char *ooctx_unmeth, uint32_t min_n_ctx, double min_ctx_meth_frac, double max_ooctx_meth_frac,
                                       const int32_t *d_pass, const char *ctx, int32_t *d_pass_out, void *stream, int64_t *nrow_out) {
-  if (!b || !c || !ctx || !nrow_out) return fail(EPI_ERR_ARG, "epi_batch_cytosine_report_sharded: NULL argument");
-  if (b->eng != c->eng) return fail(EPI_ERR_ARG, "epi_batch_cytosine_report_sharded: batch and communicator live on different engines");
-  EPI_HIP(hipSetDevice(b->eng->device));
+  EPI_TRY(shard_begin(b, c, ctx, nrow_out, "epi_batch_cytosine_report_sharded"));
   hipStream_t s = pick_stream(b, stream);
-  *nrow_out = 0;
-  c->last_bytes = 0;
   const int T = epi_cx_tile_positions(ctx);
-  // 1, 2: shared tiles -- a property of the shards, the tile grid and the communicator: exchanged once, remembered on the batch
-  epi_shard_plan *plan = nullptr;
-  for (auto &p : b->shard.plans) if (p->comm_serial == c->serial && p->T == T && p->kind == 0) plan = p.get();
-  if (!plan) {
-    int64_t mine[2] = {0, -1};
-    EPI_TRY(epi_batch_tile_key_range_for(b, T, s, &mine[0], &mine[1]));
-    std::vector<int64_t> all;
-    EPI_TRY(all_gather_i64(c, mine, 2, s, &all));
-    std::shared_ptr<epi_shard_plan> np(new epi_shard_plan());
-    np->comm_serial = c->serial; np->T = T; np->kind = 0;
-    std::vector<int32_t> owner;
-    if (c->world == 1 && c->test_shared > 0) forced_keys(mine[0], mine[1], c->test_shared, &np->keys, &owner);
-    else EPI_TRY(shared_keys_of(all, c->world, &np->keys, &owner));
-    np->owned.resize(owner.size());
-    for (size_t i = 0; i < owner.size(); i++) np->owned[i] = owner[i] == c->rank ? 1 : 0;
-    b->shard.plans.push_back(std::move(np));
-    plan = b->shard.plans.back().get();
-  }
-  const int32_t nshared = (int32_t)plan->keys.size();
-  // 3: accumulate (shared tiles into the slab)
-  const size_t slab_bytes = (size_t)nshared * kCxPlanes * T * 4;
-  if (nshared > 0) {
-    EPI_TRY(b->shard.own_slab.ensure(slab_bytes));
-    EPI_HIP(hipMemsetAsync(b->shard.own_slab.p, 0, slab_bytes, s));
-  }
-  EPI_TRY(epi_batch_cx_set_shared(b, plan->keys.data(), plan->owned.data(), nshared, nshared ? b->shard.own_slab.as<int32_t>() : nullptr));
-  int rc;
+  // shared tiles -- a property of the shards, the tile grid and the communicator: exchanged once, remembered on the batch
+  const epi_shard_plan *plan = nullptr;
+  EPI_TRY(shard_plan(b, c, s, [&](const epi_shard_plan &p) { return p.kind == SLAB_CX && p.T == T; },
+                     [&](std::vector<int64_t> &mine) { mine = {0, -1}; return epi_batch_tile_key_range_for(b, T, s, &mine[0], &mine[1]); },
+                     [&](const std::vector<int64_t> &all, epi_shard_plan *np, int64_t *ranges) {
+                       np->kind = SLAB_CX; np->T = T;
+                       std::copy(all.begin(), all.end(), ranges);
+                     }, &plan));
   int64_t nrow = 0;
-  auto first_half = [&]() {
-    if (ctx_meth)
-      return epi_batch_cytosine_report_dev(b, ctx_meth, ctx_unmeth, ooctx_meth, ooctx_unmeth, min_n_ctx, min_ctx_meth_frac, max_ooctx_meth_frac,
-                                           ctx, d_pass_out, s, &nrow);
-    return epi_batch_cx_report_dev(b, d_pass, ctx, s, &nrow);
-  };
-  // ONE host synchronisation per report where the batch allows it (an earlier report found no ultra-deep tile the host
-  // would have to finish before the slab travels): the first half only queues its kernels, the all-reduce and the owners'
-  // emit are queued behind them, and everything is read back and checked once, in the second half.
-  b->cx.defer = true;
-  rc = first_half();
-  b->cx.defer = false;
-  if (rc == EPI_OK && nshared > 0) {
-    // 4: the one data-path collective, queued on the report's stream behind the tile kernels
-    if (c->nccl) {
-      const ncclResult_t r = rccl().AllReduce(b->shard.own_slab.p, b->shard.own_slab.p, slab_bytes / 4, ncclInt32, ncclSum, c->nccl, s);
-      if (r != ncclSuccess) rc = fail(EPI_ERR_HIP, "ncclAllReduce failed: %s", rccl().GetErrorString(r));
-      c->last_bytes = (int64_t)slab_bytes;
-    }
-    // 5: owners emit their shared tiles; rows ordered
-    if (rc == EPI_OK) rc = epi_batch_cx_finish_shared(b, ctx, s, &nrow);
-    if (rc == EPI_RETRY_POOL) {
-      // (deferred synchronisation only) the row pool was too small: the first half again, with its own synchronisation --
-      // it grows the pool -- into a scratch slab; the shared tiles are then emitted from the slab that is already reduced
-      rc = b->shard.own_slab2.ensure(slab_bytes);
-      if (rc == EPI_OK && hipMemsetAsync(b->shard.own_slab2.p, 0, slab_bytes, s) != hipSuccess) rc = fail(EPI_ERR_HIP, "hipMemsetAsync failed");
-      if (rc == EPI_OK) rc = epi_batch_cx_set_shared(b, plan->keys.data(), plan->owned.data(), nshared, b->shard.own_slab2.as<int32_t>());
-      if (rc == EPI_OK) rc = first_half();
-      if (rc == EPI_OK) rc = epi_batch_cx_set_shared(b, plan->keys.data(), plan->owned.data(), nshared, b->shard.own_slab.as<int32_t>());
-      if (rc == EPI_OK) rc = epi_batch_cx_finish_shared(b, ctx, s, &nrow);
-    }
-  }
-  (void)epi_batch_cx_set_shared(b, nullptr, nullptr, 0, nullptr);     // later single-GPU calls on this batch emit every tile
-  if (rc != EPI_OK) return rc;
+  EPI_TRY(shard_exchange(b, c, *plan, s,
+                         [&](bool defer) {
+                           if (!ctx_meth) return cx_report_shared(b, d_pass, nullptr, nullptr, ctx, defer, s, &nrow);
+                           if (!ctx_unmeth) return fail(EPI_ERR_ARG, "epi_batch_cytosine_report_dev: bad arguments");
+                           const CxThreshold t = CxThreshold::of(ctx_meth, ctx_unmeth, ooctx_meth, ooctx_unmeth, min_n_ctx, min_ctx_meth_frac,
+                                                                 max_ooctx_meth_frac);
+                           return cx_report_shared(b, nullptr, &t, d_pass_out, ctx, defer, s, &nrow);
+                         },
+                         [&]() { return epi_batch_cx_finish_shared(b, ctx, s, &nrow); }));
   *nrow_out = nrow;
   return EPI_OK;
 }
 
 int epi_batch_mhl_report_sharded(epi_batch *b, epi_comm *c, const char *ctx, int hmax, int hmin, double max_ooctx_meth_frac, void *stream,
                                  int64_t *nrow_out) {
-  if (!b || !c || !ctx || !nrow_out) return fail(EPI_ERR_ARG, "epi_batch_mhl_report_sharded: NULL argument");
-  if (b->eng != c->eng) return fail(EPI_ERR_ARG, "epi_batch_mhl_report_sharded: batch and communicator live on different engines");
-  EPI_HIP(hipSetDevice(b->eng->device));
+  EPI_TRY(shard_begin(b, c, ctx, nrow_out, "epi_batch_mhl_report_sharded"));
   hipStream_t s = pick_stream(b, stream);
-  *nrow_out = 0;
-  c->last_bytes = 0;
   // the plan depends on the context string only through "can every rank take the one-pass kernel": keyed by the string
   // itself (two strings with the same letters' indices, "Zz" and "[[", may still differ in that decision)
-  const int kind = 1;
-  epi_shard_plan *plan = nullptr;
-  for (auto &p : b->shard.plans) if (p->comm_serial == c->serial && p->kind == kind && p->ctx == ctx) plan = p.get();
-  if (!plan) {
-    // both tile grids' ranges and whether this rank's rows allow the one-pass kernel: one all-gather decides path and tiles
-    int32_t ok = 0;
-    EPI_TRY(epi_batch_mhl_fused_ok(b, ctx, s, &ok));
-    int64_t mine[5] = {0, -1, 0, -1, ok};
-    EPI_TRY(epi_batch_tile_key_range_for(b, epi_mhl_tile_positions(), s, &mine[0], &mine[1]));
-    if (ok) EPI_TRY(epi_batch_tile_key_range_for(b, epi_mhl_fused_tile_positions(), s, &mine[2], &mine[3]));
-    std::vector<int64_t> all;
-    EPI_TRY(all_gather_i64(c, mine, 5, s, &all));
-    bool fused = true;
-    for (int r = 0; r < c->world; r++) fused = fused && all[5 * r + 4] != 0;
-    std::vector<int64_t> ranges((size_t)2 * c->world);
-    for (int r = 0; r < c->world; r++) { ranges[2 * r] = all[5 * r + (fused ? 2 : 0)]; ranges[2 * r + 1] = all[5 * r + (fused ? 3 : 1)]; }
-    std::shared_ptr<epi_shard_plan> np(new epi_shard_plan());
-    np->comm_serial = c->serial; np->kind = kind; np->ctx = ctx; np->fused = fused;
-    np->T = fused ? epi_mhl_fused_tile_positions() : epi_mhl_tile_positions();
-    std::vector<int32_t> owner;
-    if (c->world == 1 && c->test_shared > 0) forced_keys(ranges[0], ranges[1], c->test_shared, &np->keys, &owner);
-    else EPI_TRY(shared_keys_of(ranges, c->world, &np->keys, &owner));
-    np->owned.resize(owner.size());
-    for (size_t i = 0; i < owner.size(); i++) np->owned[i] = owner[i] == c->rank ? 1 : 0;
-    b->shard.plans.push_back(std::move(np));
-    plan = b->shard.plans.back().get();
-  }
-  const int32_t nshared = (int32_t)plan->keys.size();
-  const int T = plan->T;
-  const size_t cnt_bytes = plan->fused ? (size_t)nshared * 4 * T * 4 : (size_t)nshared * 16 * T * 4;
-  const size_t sum_bytes = plan->fused ? (size_t)nshared * 6 * T * 8 : (size_t)nshared * (size_t)epi_mhl_slab_sums() * 8;
-  if (nshared > 0) {
-    EPI_TRY(b->shard.own_slab.ensure(cnt_bytes));
-    EPI_TRY(b->shard.own_slab2.ensure(sum_bytes));
-    EPI_HIP(hipMemsetAsync(b->shard.own_slab.p, 0, cnt_bytes, s));
-    EPI_HIP(hipMemsetAsync(b->shard.own_slab2.p, 0, sum_bytes, s));
-  }
-  if (plan->fused)
-    EPI_TRY(epi_batch_mhl_set_shared_fused(b, plan->keys.data(), plan->owned.data(), nshared, nshared ? b->shard.own_slab.as<int32_t>() : nullptr,
-                                           nshared ? b->shard.own_slab2.as<int64_t>() : nullptr));
-  else
-    EPI_TRY(epi_batch_mhl_set_shared(b, plan->keys.data(), plan->owned.data(), nshared, nshared ? b->shard.own_slab.as<int32_t>() : nullptr,
-                                     nshared ? b->shard.own_slab2.as<int64_t>() : nullptr));
+  const epi_shard_plan *plan = nullptr;
+  EPI_TRY(shard_plan(b, c, s, [&](const epi_shard_plan &p) { return p.kind != SLAB_CX && p.ctx == ctx; },
+                     // both tile grids' ranges and whether this rank's rows allow the one-pass kernel: one all-gather decides path and tiles
+                     [&](std::vector<int64_t> &mine) {
+                       int32_t ok = 0;
+                       EPI_TRY(epi_batch_mhl_fused_ok(b, ctx, s, &ok));
+                       mine = {0, -1, 0, -1, ok};
+                       EPI_TRY(epi_batch_tile_key_range_for(b, epi_mhl_tile_positions(), s, &mine[0], &mine[1]));
+                       if (ok) EPI_TRY(epi_batch_tile_key_range_for(b, epi_mhl_fused_tile_positions(), s, &mine[2], &mine[3]));
+                       return (int)EPI_OK;
+                     },
+                     [&](const std::vector<int64_t> &all, epi_shard_plan *np, int64_t *ranges) {
+                       bool fused = true;
+                       for (int r = 0; r < c->world; r++) fused = fused && all[5 * r + 4] != 0;
+                       for (int r = 0; r < c->world; r++) { ranges[2 * r] = all[5 * r + (fused ? 2 : 0)]; ranges[2 * r + 1] = all[5 * r + (fused ? 3 : 1)]; }
+                       np->kind = fused ? SLAB_MHL_FUSED : SLAB_MHL; np->ctx = ctx;
+                       np->T = fused ? epi_mhl_fused_tile_positions() : epi_mhl_tile_positions();
+                     }, &plan));
   int64_t nrow = 0;
-  int rc = epi_batch_mhl_report_dev(b, ctx, hmax, hmin, max_ooctx_meth_frac, s, &nrow);
-  if (rc == EPI_OK && nshared > 0) {
-    if (c->nccl) {
-      ncclResult_t r = rccl().AllReduce(b->shard.own_slab.p, b->shard.own_slab.p, cnt_bytes / 4, ncclInt32, ncclSum, c->nccl, s);
-      if (r == ncclSuccess) r = rccl().AllReduce(b->shard.own_slab2.p, b->shard.own_slab2.p, sum_bytes / 8, ncclInt64, ncclSum, c->nccl, s);
-      if (r != ncclSuccess) rc = fail(EPI_ERR_HIP, "ncclAllReduce failed: %s", rccl().GetErrorString(r));
-      c->last_bytes = (int64_t)(cnt_bytes + sum_bytes);
-    }
-    if (rc == EPI_OK) rc = epi_batch_mhl_finish_shared(b, s, &nrow);
-  }
-  (void)epi_batch_mhl_set_shared(b, nullptr, nullptr, 0, nullptr, nullptr);
-  if (rc != EPI_OK) return rc;
+  EPI_TRY(shard_exchange(b, c, *plan, s, [&](bool) { return epi_batch_mhl_report_dev(b, ctx, hmax, hmin, max_ooctx_meth_frac, s, &nrow); },
+                         [&]() { return epi_batch_mhl_finish_shared(b, s, &nrow); }));
   *nrow_out = nrow;
   return EPI_OK;
 }

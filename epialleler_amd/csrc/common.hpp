@@ -230,11 +230,11 @@ struct CxState {                                // cx_report.hip
   // CX reports written straight into the caller's columns (direct mode): the tile offsets and row counts of the last
   // pool report, for its context mask (key = mask | 1 << 31; 0: none), tile size and tile count
   struct { DevBuf off, cnt; uint32_t key = 0; int32_t T = 0, nt = 0; int64_t nrow = 0; } kept;
-  // One host synchronisation for a sharded CX report (comm.hip): with `defer` set the first half queues its kernels and
-  // returns without reading anything back; the second half reads and checks everything at once.  Allowed only when an
-  // earlier report on this (immutable) batch and tile size found no ultra-deep tile that the host would have to finish
-  // before the slab may travel (noheavy_T / _rows: the tile size and threshold that was observed for).
-  bool defer = false, deferred = false; uint32_t def_heavy_done = 0; int32_t noheavy_T = 0, noheavy_rows = 0;
+  // One host synchronisation for a sharded CX report (comm.hip asks for it: cx_report_shared's `defer`): the first half
+  // queues its kernels and returns without reading anything back (`deferred`); the second half reads and checks everything
+  // at once.  Allowed only when an earlier report on this (immutable) batch and tile size found no ultra-deep tile that the
+  // host would have to finish before the slab may travel (noheavy_T / _rows: the tile size and threshold that was observed for).
+  bool deferred = false; uint32_t def_heavy_done = 0; int32_t noheavy_T = 0, noheavy_rows = 0;
   DevBuf deep_list;                             // tiles the lean kernel hands to the general one
   DevBuf pass_tmp;                              // pass flags when thresholding could not be fused and the caller wants none
   DevBuf thr_tab;                               // fused thresholding: decision table for thr_tab_prm over totals 0..thr_tab_len
@@ -256,16 +256,21 @@ struct MhlState {                               // mhl_report.hip, mhl_fused.hip
 
 // multi-GPU shared tiles (comm.hip): which tiles dump their raw sums into a slab, and the slab(s) attached for them
 enum SlabKind { SLAB_NONE, SLAB_CX, SLAB_MHL, SLAB_MHL_FUSED };   // _MHL: k_mhl_tiles' layout; _MHL_FUSED: the fused kernel's (mhl_common.hpp)
+// Elements of the slabs per shared tile, int32 counters and int64 sums (none for CX): the one place besides the kernels that
+// knows them (tiles.hip).  T: the CX report's tile size (it depends on the contexts reported; each lMHL kernel has its own).
+struct SlabShape { size_t cnt, sum; };
+SlabShape slab_shape(SlabKind kind, int T);
 struct ShardState {
   std::vector<int64_t> keys, dev_keys;          // dev_*: what d_keys / d_owned currently hold
   std::vector<int32_t> owned, dev_owned;
   DevBuf d_keys, d_owned, d_slot_tile;
-  DevBuf own_slab, own_slab2;                   // the slabs of the library's own sharded entry points
+  SlabKind kind = SLAB_NONE;                    // what is attached (attach_shared), in the caller's memory or the two buffers below:
+  int32_t *d_cnt = nullptr;                     // ... the counter slab
+  int64_t *d_sum = nullptr;                     // ... the sum slab (none for SLAB_CX)
+  // the library's own sharded entry points (comm.hip): their slabs and the plans they remember.  A CX report has no sums:
+  // lib_sum then serves as the scratch counter slab of its pool retry.
+  DevBuf lib_cnt, lib_sum;
   std::vector<std::shared_ptr<epi_shard_plan>> plans;
-  SlabKind kind = SLAB_NONE;                    // what is attached (the caller's memory) ...
-  int32_t *d_slab = nullptr;                    // ... SLAB_CX
-  int32_t *d_mhl_cnt_slab = nullptr;            // ... SLAB_MHL, SLAB_MHL_FUSED: counters and 64-bit sums
-  int64_t *d_mhl_sum_slab = nullptr;
 };
 
 // The pair table of the last allele-specific methylation report (asm_report.hip): one piece per group of sites, in site
@@ -453,8 +458,29 @@ int layout_copy_range(const uint8_t *src, int64_t c0, int64_t c1, const int64_t 
 // `hinted` (may be null): the caller accepts a tile count remembered from an earlier call on this batch and tile size
 // (no host round trip in the middle of the index build) and verifies it against Scalars::ntiles at its own synchronisation.
 int build_tiles(epi_batch *b, hipStream_t s, int32_t tile_positions, RowStats *h_stats, int32_t *ntiles_out, bool *hinted = nullptr);
-// the key bookkeeping and uploads of the *_set_shared entry points (tiles.hip)
-int attach_shared(epi_batch *b, const int64_t *h_keys, const int32_t *h_owned, int32_t nshared);
+// What every *_set_shared entry point does behind its argument checks (tiles.hip): the shared tile keys, which of them this
+// rank owns, and the slabs of `kind` their tiles add into; nshared = 0 detaches everything.
+int attach_shared(epi_batch *b, const int64_t *h_keys, const int32_t *h_owned, int32_t nshared, SlabKind kind, int32_t *d_cnt, int64_t *d_sum);
+// Zeroes the attached slabs behind what `s` holds: a rerun of a first half adds into them again.  T: as for slab_shape.
+int zero_shared_slabs(epi_batch *b, int T, hipStream_t s);
+// Tail of every sharded report's second half, behind its owners' emit (tiles.hip): the tiles' row offsets, the one
+// synchronisation, `deferred` (may be null: checks the first half left for this read-back), the pool check against the
+// report's overflow base and capacity, the finished report's state (`done`).
+int finish_shared_rows(epi_batch *b, hipStream_t s, ReportKind done, size_t ovf_base, size_t pool_cap, const char *overflow_msg,
+                       int (*deferred)(epi_batch *, const Scalars &), int64_t *nrow_out);
+
+// First half of the library's sharded CX report (cx_report.hip): epi_batch_cx_report_dev (thr = null) or
+// epi_batch_cytosine_report_dev, which never defer; defer: where the batch allows it, read nothing back (CxState::deferred).
+struct CxThreshold {                      // fused thresholding request (null = use the pass vector)
+  const char *cls[4];
+  ThrParams prm;
+  static CxThreshold of(const char *ctx_meth, const char *ctx_unmeth, const char *ooctx_meth, const char *ooctx_unmeth, uint32_t min_n_ctx,
+                        double min_ctx_meth_frac, double max_ooctx_meth_frac) {
+    return {{ctx_meth, ctx_unmeth, ooctx_meth ? ooctx_meth : "", ooctx_unmeth ? ooctx_unmeth : ""}, {min_n_ctx, min_ctx_meth_frac, max_ooctx_meth_frac}};
+  }
+};
+int cx_report_shared(epi_batch *b, const int32_t *d_pass, const CxThreshold *thr, int32_t *d_pass_out, const char *ctx, bool defer,
+                     hipStream_t s, int64_t *nrow_out);
 
 // Row pool of a report: a slot per tile + an overflow region (the scheme: tiles.hip, with layout_pool)
 struct PoolLayout {

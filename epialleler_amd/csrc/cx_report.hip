@@ -1430,10 +1430,6 @@ static int make_report_lut(uint32_t ctx_mask, ClassLut *lut, uint32_t *ctx_of_pl
   return np;
 }
 
-struct CxThreshold {                      // fused thresholding request (null = use the pass vector)
-  const char *cls[4];
-  ThrParams prm;
-};
 
 // The fused kernel's LUT.  Fusable: the report has one context k, the thresholding classes are that context
 // (ctx_meth = {k}, ctx_unmeth = {k | 8}) and no class string repeats a letter.  Also picks the stand-in code for bytes
@@ -1547,17 +1543,20 @@ static int cx_layout_pool(epi_batch *b, uint32_t ctx_mask, CxPlan &p) {
   return EPI_OK;
 }
 
+// rows of the pool that a kernel may address (row indices are u32)
+static uint32_t cx_pool_cap(const epi_batch *b) { return (uint32_t)(b->pool.row_cap > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : b->pool.row_cap); }
+
 // The batch's tile table, row pool (as it is now: a regrown pool is bound again) and the layout of its last report
 static void cx_bind_pool(const epi_batch *b, Cx2Args &a) {
   a.tiles = b->tix.tiles.as<Tile>();
   a.cursor = &report_scalars(b)->cursor;
   a.tile_nrow = b->pool.tile_nrow.as<uint32_t>();
   a.tile_base = b->pool.tile_base.as<uint32_t>();
-  a.slab = b->shard.d_slab;
+  a.slab = b->shard.kind == SLAB_CX ? b->shard.d_cnt : nullptr;
   a.pool_key = b->pool.key.as<uint32_t>();
   a.pool_meth = b->pool.a.as<uint32_t>();
   a.pool_unmeth = b->pool.b.as<uint32_t>();
-  a.pool_cap = (uint32_t)(b->pool.row_cap > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : b->pool.row_cap);
+  a.pool_cap = cx_pool_cap(b);
   a.slot_rows = b->cx.last_slot;
   a.ovf_base = b->cx.last_ovf;
 }
@@ -1691,9 +1690,10 @@ static int cx_keep_offsets(epi_batch *b, uint32_t ctx_mask, const CxPlan &p, uin
 // while every tile's row count is the kept one: true for valid XM codes whatever `pass` is, not for the unused low
 // nibbles 1, 3 and 4 under failed reads, nor for rows rewritten in place.  A launch in which any tile's count differs
 // forgets the record and reruns through the pool (*written = 0), which keeps its offsets instead.
+// defer: the first half of the library's sharded report may leave its synchronisation to the second (cx_report_shared).
 static int cx_report_impl(epi_batch *b, const int32_t *d_pass, const CxThreshold *thr, int32_t *d_pass_out, const char *ctx,
                           hipStream_t s, int64_t *nrow_out, int32_t *const *d_cols = nullptr, int64_t cap = 0,
-                          int *written = nullptr) {
+                          int *written = nullptr, bool defer = false) {
   *nrow_out = 0;
   if (written) *written = 0;
   b->last_kind = KIND_NONE;
@@ -1773,10 +1773,10 @@ static int cx_report_impl(epi_batch *b, const int32_t *d_pass, const CxThreshold
   for (int run = 0;; run++) {
     cx_bind_pool(b, a);
     EPI_TRY(cx_queue_attempt(b, p, a, s, direct || run > 0));
-    if (run == 0 && b->cx.defer && p.nshared > 0 && p.nt_hinted && b->cx.noheavy_T == T && b->cx.noheavy_rows == a.heavy_rows) {
+    if (run == 0 && defer && p.nshared > 0 && p.nt_hinted && b->cx.noheavy_T == T && b->cx.noheavy_rows == a.heavy_rows) {
       // sharded report with one host synchronisation: nothing is read back here; epi_batch_cx_finish_shared checks the tile
-      // count, the heavy-tile count and the pool at its own synchronisation (comm.hip reruns the first half into a scratch
-      // slab if the pool turns out too small)
+      // count, the heavy-tile count and the pool at its own synchronisation (cx_deferred_checks; comm.hip reruns the first
+      // half into a scratch slab if the pool turns out too small)
       b->cx.deferred = true;
       b->cx.def_heavy_done = p.chained ? CX_HEAVY_CAP : 0u;
       b->last_kind = KIND_CX_SHARED;
@@ -1786,8 +1786,7 @@ static int cx_report_impl(epi_batch *b, const int32_t *d_pass, const CxThreshold
     if (p.pool.ovf_base + host.cursor + p.headroom <= a.pool_cap) break;
     if (run == 1) return fail(EPI_ERR_STATE, "row pool overflow after regrow");
     EPI_TRY(ensure_pool(b, p.pool.ovf_base + host.cursor + (host.cursor >> 4) + 1024 + p.headroom));   // exact need is known now: rerun once
-    if (p.nshared > 0)   // the rerun adds into the slab again
-      EPI_HIP(hipMemsetAsync(b->shard.d_slab, 0, (size_t)p.nshared * kCxPlanes * T * 4, s));
+    EPI_TRY(zero_shared_slabs(b, T, s));                   // the rerun adds into the slab again
   }
   uint32_t &slot_state = cx_slot_state(b, ctx_mask);
   if (host.cursor > host.rows / 8 && slot_state < (uint32_t)(2 * T)) slot_state *= 2;   // too many tiles outgrew their slot
@@ -1798,6 +1797,29 @@ static int cx_report_impl(epi_batch *b, const int32_t *d_pass, const CxThreshold
   b->last_nrow = host.rows;
   *nrow_out = host.rows;
   return cx_keep_offsets(b, ctx_mask, p, host.rows, s);
+}
+
+int cx_report_shared(epi_batch *b, const int32_t *d_pass, const CxThreshold *thr, int32_t *d_pass_out, const char *ctx, bool defer,
+                     hipStream_t s, int64_t *nrow_out) {
+  return cx_report_impl(b, d_pass, thr, d_pass_out, ctx, s, nrow_out, nullptr, 0, nullptr, defer);
+}
+
+// A first half that read nothing back (CxState::deferred): its checks, at the second half's synchronisation
+static int cx_deferred_checks(epi_batch *b, const Scalars &host) {
+  if (!b->cx.deferred) return EPI_OK;
+  b->cx.deferred = false;
+  EPI_TRY(cx_check_tile_count(b, true, host.ntiles, b->last_ntiles));
+  if (host.heavy_count > b->cx.def_heavy_done) {
+    batch_rows_changed(b);
+    return fail(EPI_ERR_STATE, "ultra-deep tiles appeared in a batch that had none (%u): the rows of this batch changed", host.heavy_count);
+  }
+  if ((size_t)b->cx.last_ovf + host.cursor > cx_pool_cap(b)) {
+    // the pool was too small for the rows of this report: the caller reruns the first half (which grows it) into a
+    // scratch slab and emits the shared tiles from the slab that has already been reduced
+    b->last_kind = KIND_NONE;
+    return EPI_RETRY_POOL;
+  }
+  return EPI_OK;
 }
 
 }  // namespace epi
@@ -1849,9 +1871,7 @@ int epi_batch_cytosine_report_into_dev(epi_batch *b, const char *ctx_meth, const
   if (!b || !ctx || !nrow_out || !ctx_meth || !ctx_unmeth || cap < 0 || (cap > 0 && !d_cols))
     return fail(EPI_ERR_ARG, "epi_batch_cytosine_report_dev: bad arguments");
   EPI_HIP(hipSetDevice(b->eng->device));
-  CxThreshold t;
-  t.cls[0] = ctx_meth; t.cls[1] = ctx_unmeth; t.cls[2] = ooctx_meth ? ooctx_meth : ""; t.cls[3] = ooctx_unmeth ? ooctx_unmeth : "";
-  t.prm.min_n_ctx = min_n_ctx; t.prm.min_ctx_meth_frac = min_ctx_meth_frac; t.prm.max_ooctx_meth_frac = max_ooctx_meth_frac;
+  const CxThreshold t = CxThreshold::of(ctx_meth, ctx_unmeth, ooctx_meth, ooctx_unmeth, min_n_ctx, min_ctx_meth_frac, max_ooctx_meth_frac);
   return cx_report_impl(b, nullptr, &t, d_pass_out, ctx, pick_stream(b, stream), nrow_out, d_cols, cap, written);
 }
 
@@ -1862,8 +1882,7 @@ int epi_batch_cx_finish_shared(epi_batch *b, const char *ctx, void *stream, int6
   if (b->last_kind != KIND_CX_SHARED) return fail(EPI_ERR_STATE, "epi_batch_cx_finish_shared without a sharded epi_batch_cx_report_dev");
   EPI_HIP(hipSetDevice(b->eng->device));
   hipStream_t s = pick_stream(b, stream);
-  const int32_t nt = b->last_ntiles;
-  if (nt == 0) { b->last_kind = KIND_CX; b->last_nrow = 0; *nrow_out = 0; return EPI_OK; }   // this rank holds no rows: owns no tile
+  if (b->last_ntiles == 0) { b->last_kind = KIND_CX; b->last_nrow = 0; *nrow_out = 0; return EPI_OK; }   // this rank holds no rows: owns no tile
   Cx2Args a;
   memset(&a, 0, sizeof(a));
   cx_bind_pool(b, a);
@@ -1871,40 +1890,13 @@ int epi_batch_cx_finish_shared(epi_batch *b, const char *ctx, void *stream, int6
   launch_cx_emit_slab(b->cx.last_np, (int)b->shard.keys.size(), s, a, b->shard.d_owned.as<int32_t>(),
                       b->shard.d_slot_tile.as<int32_t>());
   EPI_HIP(hipGetLastError());
-  EPI_TRY(scan_exclusive_u32(a.tile_nrow, b->pool.tile_out.as<uint32_t>(), nt, &report_scalars(b)->rows, b->scan_tmp, s));
-  Scalars host;                                             // overflow rows handed out, total rows: one sync
-  EPI_TRY(read_report_scalars(b, s, &host));
-  if (b->cx.deferred) {
-    // the first half read nothing back: its checks happen here, with the report's only synchronisation
-    b->cx.deferred = false;
-    EPI_TRY(cx_check_tile_count(b, true, host.ntiles, nt));
-    if (host.heavy_count > b->cx.def_heavy_done) {
-      batch_rows_changed(b);
-      return fail(EPI_ERR_STATE, "ultra-deep tiles appeared in a batch that had none (%u): the rows of this batch changed", host.heavy_count);
-    }
-    if ((size_t)a.ovf_base + host.cursor > a.pool_cap) {      // (the cursor has served the shared tiles' rows as well by now)
-      // the pool was too small for the rows of this report: the caller reruns the first half (which grows it) into a
-      // scratch slab and emits the shared tiles from the slab that has already been reduced
-      b->last_kind = KIND_NONE;
-      return EPI_RETRY_POOL;
-    }
-  }
-  // cannot overflow: the first half kept 2*kTile rows per shared tile free
-  if ((size_t)a.ovf_base + host.cursor > a.pool_cap) return fail(EPI_ERR_STATE, "row pool overflow in sharded report");
-  const uint32_t total = host.rows;
-  b->last_kind = KIND_CX;
-  b->last_nrow = total;
-  *nrow_out = total;
-  return EPI_OK;
+  return finish_shared_rows(b, s, KIND_CX, a.ovf_base, a.pool_cap, "row pool overflow in sharded report", cx_deferred_checks, nrow_out);
 }
 
 int epi_batch_cx_set_shared(epi_batch *b, const int64_t *h_keys, const int32_t *h_owned, int32_t nshared,
                             int32_t *d_slab) {
   if (nshared > 0 && !d_slab) return fail(EPI_ERR_ARG, "epi_batch_cx_set_shared: bad arguments");
-  EPI_TRY(attach_shared(b, h_keys, h_owned, nshared));
-  b->shard.kind = nshared > 0 ? SLAB_CX : SLAB_NONE;
-  b->shard.d_slab = nshared > 0 ? d_slab : nullptr;
-  return EPI_OK;
+  return attach_shared(b, h_keys, h_owned, nshared, SLAB_CX, d_slab, nullptr);
 }
 
 int epi_batch_tile_key_range(epi_batch *b, void *stream, int64_t *first_key, int64_t *last_key) {

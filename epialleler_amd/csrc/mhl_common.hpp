@@ -16,6 +16,7 @@ constexpr int MHL_T = kMhlTile;
 constexpr int MHL_SLEN = (kMhlTile + 1) + ((kMhlTile + 1) >> 3) + 1;
 __host__ __device__ constexpr int mhl_pad(int p) { return p + (p >> 3); }
 constexpr int MHL_NSUM = 6 * MHL_SLEN;            // u64 per tile: difference arrays of sum S(M), sum h, sum S(h), two strands each
+constexpr int MHL_CNT_PLANES = 16;                // u32 planes of MHL_T counters per tile in the heavy and shared slabs
 constexpr int MHL_BLK_SHIFT = 11;                 // a block of the multi-block row kernel: 64 lanes x 32 bytes
 constexpr int MHL_REGIONS = 64, MHL_CUR_STRIDE = 32;   // record allocation cursors (u64 each, 256 B apart)
 #ifndef EPI_MHL_NU
@@ -152,9 +153,6 @@ int ensure_mhl_pool(epi_batch *b, size_t rows);
 int mhl_layout_pool(epi_batch *b, uint32_t &slot_state, int T, int32_t nt, size_t headroom, PoolLayout *l);
 int pick_mhl_group(int32_t max_len);             // lanes per read x chunks per lane as G * 8 + C (0: longer than 64 lanes cover)
 ClassLut make_mhl_lut(uint32_t ctx_mask);
-// Tail of the second half of a sharded report, either path: the tiles' row offsets, the one synchronisation, the pool
-// check, the finished report's state
-int mhl_finish_rows(epi_batch *b, hipStream_t s, int64_t *nrow_out);
 
 // Check build (EPI_CHECK, EPI_MHL_CHECK): the record of the first index violation {code, v0, v1, block, thread} that the
 // kernels of either path fill -- cleared before a report's first kernel, read back behind an attempt
@@ -181,6 +179,11 @@ inline uint32_t mhl_single_context(uint32_t ctx_mask) {
 
 // rows of the pool that a kernel may address (row indices are u32)
 inline uint32_t mhl_pool_cap(const epi_batch *b) { return (uint32_t)(mhl_pool_rows(b) > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : mhl_pool_rows(b)); }
+
+// Tail of the second half of a sharded lMHL report, either path, behind its owners' emit
+inline int mhl_finish_rows(epi_batch *b, hipStream_t s, int64_t *nrow_out) {
+  return finish_shared_rows(b, s, KIND_MHL, b->mhl.last_ovf, mhl_pool_cap(b), "row pool overflow in sharded lMHL report", nullptr, nrow_out);
+}
 
 // The batch's tile table, row pool (as it is now: a regrown pool is bound again) and the layout of its last lMHL report, into
 // the argument struct of either path (MhlArgs, MhlFArgs: the members have the same names)

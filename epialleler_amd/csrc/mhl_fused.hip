@@ -1006,8 +1006,8 @@ static int mhlf_fill_args(epi_batch *b, uint32_t ctx_mask, uint32_t H, int hmin,
   a.deep_list = b->pool.heavy_list.as<uint32_t>();
   a.max_rows = MHLF_FAST_ROWS;
   if (options().heavy_rows > 0 && options().heavy_rows < a.max_rows) a.max_rows = options().heavy_rows;   // test hook (EPIHIP_HEAVY_ROWS)
-  a.slab_cnt = b->shard.d_mhl_cnt_slab;
-  a.slab_sum = reinterpret_cast<unsigned long long *>(b->shard.d_mhl_sum_slab);
+  a.slab_cnt = b->shard.d_cnt;
+  a.slab_sum = reinterpret_cast<unsigned long long *>(b->shard.d_sum);
   a.nrows = b->n;
 #ifdef EPI_CHECK
   EPI_TRY(mhl_check_begin(b, s, &a.dbg));
@@ -1034,10 +1034,7 @@ static int mhlf_attempt(epi_batch *b, const MhlfPlan &p, MhlFArgs &a, uint32_t H
   mhl_bind_pool(b, a);
   if (attempt > 0) {
     EPI_HIP(hipMemsetAsync(&sc->cursor, 0, offsetof(Scalars, unused6) - offsetof(Scalars, cursor), s));   // cursor .. fold_cursor
-    if (p.nshared > 0) {                                   // the rerun adds into the slabs again
-      EPI_HIP(hipMemsetAsync(a.slab_cnt, 0, (size_t)p.nshared * MHLF_CNT_PLANES * MHLF_T * 4, s));
-      EPI_HIP(hipMemsetAsync(a.slab_sum, 0, (size_t)p.nshared * MHLF_SUM_PLANES * MHLF_T * 8, s));
-    }
+    EPI_TRY(zero_shared_slabs(b, MHLF_T, s));              // the rerun adds into the slabs again
   }
   a.tile_list = nullptr;
   prof_begin("mhl_tiles", s);
@@ -1126,8 +1123,8 @@ int mhl_fused_finish_shared(epi_batch *b, hipStream_t s, int64_t *nrow_out) {
     MhlFArgs a{};
     mhl_bind_pool(b, a);
     a.ctx = mhl_single_context(b->mhl.ctx_mask);
-    a.slab_cnt = b->shard.d_mhl_cnt_slab;
-    a.slab_sum = reinterpret_cast<unsigned long long *>(b->shard.d_mhl_sum_slab);
+    a.slab_cnt = b->shard.d_cnt;
+    a.slab_sum = reinterpret_cast<unsigned long long *>(b->shard.d_sum);
     hipLaunchKernelGGL(k_mhlf_emit_slab, dim3((unsigned)b->shard.keys.size()), dim3(MHLF_WG), 0, s, a, b->shard.d_owned.as<int32_t>(),
                        b->shard.d_slot_tile.as<int32_t>());
     EPI_HIP(hipGetLastError());

@@ -756,6 +756,7 @@ __global__ __launch_bounds__(WG, (mhl_waves_per_simd<WG, ST>())) void k_mhl_tile
 }
 
 // One chunk of the candidate rows of one heavy tile -> added into that tile's slab in HBM.
+static_assert(MHL_CNT_PLANES == 16, "k_mhl_heavy, k_mhl_emit_heavy, k_mhl_emit_slab and the slab dump step their counter slabs by 16 * MHL_T");
 template <int G, int WG, class ST>
 __global__ __launch_bounds__(WG, (mhl_waves_per_simd<WG, ST>())) void k_mhl_heavy(MhlArgs a) {
   constexpr int T = MHL_T;
@@ -1022,8 +1023,8 @@ static int mhl_fill_args(epi_batch *b, MhlPlan &p, uint32_t ctx_mask, uint32_t H
   a.heavy_list = b->pool.heavy_list.as<uint32_t>();
   a.heavy_count = &sc->heavy_count;
   a.heavy_max = &sc->heavy_max;
-  a.shared_cnt = reinterpret_cast<uint32_t *>(b->shard.d_mhl_cnt_slab);
-  a.shared_sums = reinterpret_cast<unsigned long long *>(b->shard.d_mhl_sum_slab);
+  a.shared_cnt = reinterpret_cast<uint32_t *>(b->shard.d_cnt);
+  a.shared_sums = reinterpret_cast<unsigned long long *>(b->shard.d_sum);
   return EPI_OK;
 }
 
@@ -1102,11 +1103,11 @@ static int mhl_pass2(epi_batch *b, const MhlPlan &p, MhlArgs &a, hipStream_t s, 
   EPI_TRY(read_report_scalars(b, s, host));
   if (host->heavy_count > 0) {
     const uint32_t nheavy = host->heavy_count, nchunks = (host->heavy_max + (uint32_t)a.heavy_chunk - 1) / (uint32_t)a.heavy_chunk;
-    EPI_TRY(b->pool.heavy_slab.ensure((size_t)nheavy * 16 * MHL_T * 4));
+    EPI_TRY(b->pool.heavy_slab.ensure((size_t)nheavy * MHL_CNT_PLANES * MHL_T * 4));
     EPI_TRY(b->pool.heavy_sums.ensure((size_t)nheavy * MHL_NSUM * 8));
     a.heavy_cnt = b->pool.heavy_slab.as<uint32_t>();
     a.heavy_sums = b->pool.heavy_sums.as<unsigned long long>();
-    EPI_HIP(hipMemsetAsync(a.heavy_cnt, 0, (size_t)nheavy * 16 * MHL_T * 4, s));
+    EPI_HIP(hipMemsetAsync(a.heavy_cnt, 0, (size_t)nheavy * MHL_CNT_PLANES * MHL_T * 4, s));
     EPI_HIP(hipMemsetAsync(a.heavy_sums, 0, (size_t)nheavy * MHL_NSUM * 8, s));
     prof_begin("mhl_heavy", s);
     if (p.narrow) launch_mhl_heavy<uint32_t>(p.tg, nheavy, nchunks, s, a); else launch_mhl_heavy<unsigned long long>(p.tg, nheavy, nchunks, s, a);
@@ -1119,13 +1120,9 @@ static int mhl_pass2(epi_batch *b, const MhlPlan &p, MhlArgs &a, hipStream_t s, 
 }
 
 // The overflow region was too small for the `used` rows that went through the cursor: the exact need is known now
-static int mhl_regrow_pool(epi_batch *b, const MhlPlan &p, const MhlArgs &a, uint32_t used, hipStream_t s) {
+static int mhl_regrow_pool(epi_batch *b, const MhlPlan &p, uint32_t used, hipStream_t s) {
   EPI_TRY(ensure_mhl_pool(b, p.pool.ovf_base + used + (used >> 4) + 1024 + p.headroom));
-  if (p.nshared > 0) {   // the rerun adds into the shared slabs again
-    EPI_HIP(hipMemsetAsync(a.shared_cnt, 0, (size_t)p.nshared * 16 * MHL_T * 4, s));
-    EPI_HIP(hipMemsetAsync(a.shared_sums, 0, (size_t)p.nshared * MHL_NSUM * 8, s));
-  }
-  return EPI_OK;
+  return zero_shared_slabs(b, MHL_T, s);                   // the rerun adds into the shared slabs again
 }
 
 // The two-kernel path on a resident batch.  At most three attempts: one that finds the record space of pass 1 too small,
@@ -1171,23 +1168,10 @@ static int mhl_report_impl(epi_batch *b, uint32_t ctx_mask, uint32_t H, int hmin
     EPI_TRY(mhl_pass2(b, p, a, s, attempt, &host));
     if (p.pool.ovf_base + host.cursor + p.headroom <= a.pool_cap) break;
     if (attempt == 2) return fail(EPI_ERR_STATE, "row pool overflow after regrow");
-    EPI_TRY(mhl_regrow_pool(b, p, a, host.cursor, s));
+    EPI_TRY(mhl_regrow_pool(b, p, host.cursor, s));
   }
   if (host.cursor > host.rows / 8 && b->mhl.slot < 2u * MHL_T) b->mhl.slot *= 2;   // too many tiles outgrew their slot
   if (p.nshared > 0) { b->last_kind = KIND_MHL_SHARED; return EPI_OK; }     // caller continues with epi_batch_mhl_finish_shared
-  b->last_kind = KIND_MHL;
-  b->last_nrow = host.rows;
-  *nrow_out = host.rows;
-  return EPI_OK;
-}
-
-int mhl_finish_rows(epi_batch *b, hipStream_t s, int64_t *nrow_out) {
-  Scalars *sc = report_scalars(b);
-  EPI_TRY(scan_exclusive_u32(b->pool.tile_nrow.as<uint32_t>(), b->pool.tile_out.as<uint32_t>(), b->last_ntiles, &sc->rows, b->scan_tmp, s));
-  Scalars host;
-  EPI_TRY(read_report_scalars(b, s, &host));
-  // cannot overflow: the first half kept 2 T rows per shared tile free
-  if ((size_t)b->mhl.last_ovf + host.cursor > mhl_pool_cap(b)) return fail(EPI_ERR_STATE, "row pool overflow in sharded lMHL report");
   b->last_kind = KIND_MHL;
   b->last_nrow = host.rows;
   *nrow_out = host.rows;
@@ -1218,19 +1202,10 @@ int epi_batch_mhl_report_dev(epi_batch *b, const char *ctx, int hmax, int hmin, 
 int epi_mhl_tile_positions(void) { return MHL_T; }
 int epi_mhl_slab_sums(void) { return MHL_NSUM; }
 
-static int mhl_set_shared(epi_batch *b, const int64_t *h_keys, const int32_t *h_owned, int32_t nshared, int32_t *d_cnt_slab,
-                          int64_t *d_sum_slab, SlabKind kind) {
-  if (nshared > 0 && (!d_cnt_slab || !d_sum_slab)) return fail(EPI_ERR_ARG, "epi_batch_mhl_set_shared: NULL slab");
-  EPI_TRY(attach_shared(b, h_keys, h_owned, nshared));
-  b->shard.kind = nshared > 0 ? kind : SLAB_NONE;
-  b->shard.d_mhl_cnt_slab = nshared > 0 ? d_cnt_slab : nullptr;
-  b->shard.d_mhl_sum_slab = nshared > 0 ? d_sum_slab : nullptr;
-  return EPI_OK;
-}
-
 int epi_batch_mhl_set_shared(epi_batch *b, const int64_t *h_keys, const int32_t *h_owned, int32_t nshared,
                              int32_t *d_cnt_slab, int64_t *d_sum_slab) {
-  return mhl_set_shared(b, h_keys, h_owned, nshared, d_cnt_slab, d_sum_slab, SLAB_MHL);
+  if (nshared > 0 && (!d_cnt_slab || !d_sum_slab)) return fail(EPI_ERR_ARG, "epi_batch_mhl_set_shared: NULL slab");
+  return attach_shared(b, h_keys, h_owned, nshared, SLAB_MHL, d_cnt_slab, d_sum_slab);
 }
 
 int epi_mhl_fused_tile_positions(void) { return MHLF_T; }
@@ -1248,7 +1223,8 @@ int epi_batch_mhl_fused_ok(epi_batch *b, const char *ctx, void *stream, int32_t 
 
 int epi_batch_mhl_set_shared_fused(epi_batch *b, const int64_t *h_keys, const int32_t *h_owned, int32_t nshared,
                                    int32_t *d_cnt_slab, int64_t *d_sum_slab) {
-  return mhl_set_shared(b, h_keys, h_owned, nshared, d_cnt_slab, d_sum_slab, SLAB_MHL_FUSED);
+  if (nshared > 0 && (!d_cnt_slab || !d_sum_slab)) return fail(EPI_ERR_ARG, "epi_batch_mhl_set_shared: NULL slab");
+  return attach_shared(b, h_keys, h_owned, nshared, SLAB_MHL_FUSED, d_cnt_slab, d_sum_slab);
 }
 
 // Second half of a sharded lMHL report: the slabs have been sum-reduced across ranks.
@@ -1263,8 +1239,8 @@ int epi_batch_mhl_finish_shared(epi_batch *b, void *stream, int64_t *nrow_out) {
   MhlArgs a{};
   mhl_bind_pool(b, a);
   a.ctx_mask = b->mhl.ctx_mask;
-  a.shared_cnt = reinterpret_cast<uint32_t *>(b->shard.d_mhl_cnt_slab);
-  a.shared_sums = reinterpret_cast<unsigned long long *>(b->shard.d_mhl_sum_slab);
+  a.shared_cnt = reinterpret_cast<uint32_t *>(b->shard.d_cnt);
+  a.shared_sums = reinterpret_cast<unsigned long long *>(b->shard.d_sum);
   hipLaunchKernelGGL((k_mhl_emit_slab<MHL_WG>), dim3((unsigned)b->shard.keys.size()), dim3(MHL_WG), 0, s, a,
                      b->shard.d_owned.as<int32_t>(), b->shard.d_slot_tile.as<int32_t>());
   EPI_HIP(hipGetLastError());

@@ -10,7 +10,7 @@
 // the reference's "flush the map when start > max_pos" windowing
 // (src/rcpp_cx_report.cpp:113) and the key sort of a sort+segmented-reduce
 // scheme: the input order already is the sort.
-#include "common.hpp"
+#include "mhl_common.hpp"   // (common.hpp; the lMHL kernels' slab constants for slab_shape)
 #include <stdlib.h>
 #include <string.h>
 
@@ -260,9 +260,19 @@ int fetch_row_stats(epi_batch *b, hipStream_t s) {
   return EPI_OK;
 }
 
-// The shared tile keys of a sharded report and which of them this rank owns (keys strictly increasing; nshared = 0: none), with
-// no slab attached: what every *_set_shared entry point does first.  A tile's slot is assigned when the tile table is built.
-int attach_shared(epi_batch *b, const int64_t *h_keys, const int32_t *h_owned, int32_t nshared) {
+// The slabs of a shared tile, from the kernels' own constants
+SlabShape slab_shape(SlabKind kind, int T) {
+  switch (kind) {
+    case SLAB_CX: return {(size_t)kCxPlanes * T, 0};
+    case SLAB_MHL: return {(size_t)MHL_CNT_PLANES * MHL_T, (size_t)MHL_NSUM};
+    case SLAB_MHL_FUSED: return {(size_t)MHLF_CNT_PLANES * MHLF_T, (size_t)MHLF_SUM_PLANES * MHLF_T};
+    default: return {0, 0};
+  }
+}
+
+// The shared tile keys of a sharded report and which of them this rank owns (keys strictly increasing), with the slabs their
+// tiles add into; nshared = 0: none, nothing attached.  A tile's slot is assigned when the tile table is built.
+int attach_shared(epi_batch *b, const int64_t *h_keys, const int32_t *h_owned, int32_t nshared, SlabKind kind, int32_t *d_cnt, int64_t *d_sum) {
   if (!b || nshared < 0 || (nshared > 0 && (!h_keys || !h_owned)))
     return fail(EPI_ERR_ARG, "epi_batch_cx_set_shared: bad arguments");
   for (int32_t i = 1; i < nshared; i++)
@@ -271,15 +281,41 @@ int attach_shared(epi_batch *b, const int64_t *h_keys, const int32_t *h_owned, i
   ShardState &sh = b->shard;
   sh.keys.assign(h_keys, h_keys + nshared);
   sh.owned.assign(h_owned, h_owned + nshared);
-  sh.kind = SLAB_NONE; sh.d_slab = nullptr; sh.d_mhl_cnt_slab = nullptr; sh.d_mhl_sum_slab = nullptr;
+  sh.kind = SLAB_NONE; sh.d_cnt = nullptr; sh.d_sum = nullptr;
+  if (nshared == 0) return EPI_OK;
   // a sharded run attaches the same keys for every report: skip the copies when the device already holds them
-  if (nshared == 0 || (sh.dev_keys == sh.keys && sh.dev_owned == sh.owned)) return EPI_OK;
-  EPI_TRY(sh.d_keys.ensure((size_t)nshared * 8));
-  EPI_TRY(sh.d_owned.ensure((size_t)nshared * 4));
-  EPI_HIP(hipMemcpy(sh.d_keys.p, h_keys, (size_t)nshared * 8, hipMemcpyHostToDevice));
-  EPI_HIP(hipMemcpy(sh.d_owned.p, h_owned, (size_t)nshared * 4, hipMemcpyHostToDevice));
-  sh.dev_keys = sh.keys;
-  sh.dev_owned = sh.owned;
+  if (sh.dev_keys != sh.keys || sh.dev_owned != sh.owned) {
+    EPI_TRY(sh.d_keys.ensure((size_t)nshared * 8));
+    EPI_TRY(sh.d_owned.ensure((size_t)nshared * 4));
+    EPI_HIP(hipMemcpy(sh.d_keys.p, h_keys, (size_t)nshared * 8, hipMemcpyHostToDevice));
+    EPI_HIP(hipMemcpy(sh.d_owned.p, h_owned, (size_t)nshared * 4, hipMemcpyHostToDevice));
+    sh.dev_keys = sh.keys;
+    sh.dev_owned = sh.owned;
+  }
+  sh.kind = kind; sh.d_cnt = d_cnt; sh.d_sum = d_sum;
+  return EPI_OK;
+}
+
+int zero_shared_slabs(epi_batch *b, int T, hipStream_t s) {
+  const ShardState &sh = b->shard;
+  const SlabShape shape = slab_shape(sh.kind, T);
+  if (shape.cnt) EPI_HIP(hipMemsetAsync(sh.d_cnt, 0, sh.keys.size() * shape.cnt * 4, s));
+  if (shape.sum) EPI_HIP(hipMemsetAsync(sh.d_sum, 0, sh.keys.size() * shape.sum * 8, s));
+  return EPI_OK;
+}
+
+int finish_shared_rows(epi_batch *b, hipStream_t s, ReportKind done, size_t ovf_base, size_t pool_cap, const char *overflow_msg,
+                       int (*deferred)(epi_batch *, const Scalars &), int64_t *nrow_out) {
+  Scalars *sc = report_scalars(b);
+  EPI_TRY(scan_exclusive_u32(b->pool.tile_nrow.as<uint32_t>(), b->pool.tile_out.as<uint32_t>(), b->last_ntiles, &sc->rows, b->scan_tmp, s));
+  Scalars host;                                             // overflow rows handed out, total rows: one sync
+  EPI_TRY(read_report_scalars(b, s, &host));
+  if (deferred) EPI_TRY(deferred(b, host));
+  // cannot overflow: the first half kept 2 T rows per shared tile free
+  if (ovf_base + host.cursor > pool_cap) return fail(EPI_ERR_STATE, "%s", overflow_msg);
+  b->last_kind = done;
+  b->last_nrow = host.rows;
+  *nrow_out = host.rows;
   return EPI_OK;
 }
 

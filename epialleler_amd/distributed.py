@@ -34,7 +34,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .api import CONTEXT_TO_BASES, ProcessedBam, Report, _ptr_array, _stream
+from .api import CONTEXT_TO_BASES, CX_COLUMNS, MHL_COLUMNS, ProcessedBam, Report, _ptr_array, _stream
 
 
 def shared_tile_keys(ranges):
@@ -68,6 +68,11 @@ def shared_tile_keys(ranges):
     return np.asarray(ks, np.int64), np.asarray([keys[k] for k in ks], np.int32)
 
 
+def _world_rank(group):
+    import torch.distributed as dist
+    return (dist.get_world_size(group), dist.get_rank(group)) if dist.is_initialized() else (1, 0)
+
+
 class HipShardEngine:
     """One rank's shard on its MI355X (product engine; no CPU path)."""
 
@@ -78,7 +83,7 @@ class HipShardEngine:
         self.h = self.bam.batch()
         self.lib = _lib.load()
         self.device = torch.device("cuda", self.bam.device)
-        self._slab = None
+        self._slabs = {}                      # "cx": [counters], "mhl": [counters, sums] -- the tensors of the last attach
         self._range = {}
         self.last_exchange_bytes = 0          # bytes this rank handed to the last report's all-reduce(s)
         self.comm = None                      # epi_comm: RCCL behind the C ABI (attach_comm)
@@ -90,8 +95,7 @@ class HipShardEngine:
         the middle of the shard are treated as shared, so that slab, all-reduce and the owners' emit run on one GPU."""
         import torch.distributed as dist
         torch = self.torch
-        world = dist.get_world_size(group) if dist.is_initialized() else 1
-        rank = dist.get_rank(group) if dist.is_initialized() else 0
+        world, rank = _world_rank(group)
         idbuf = (C.c_ubyte * 128)()
         if rank == 0:
             _lib.check(self.lib.epi_comm_unique_id(idbuf))
@@ -113,58 +117,81 @@ class HipShardEngine:
             self.lib.epi_comm_free(self.comm)
             self.comm = None
 
+    # ---- what both paths share: this rank's rows of the finished report, the slabs of the two-step path ------------------
+    def _stream(self):
+        return _stream(self.bam.device)
+
+    def _fetch_cx(self, n):
+        """This rank's [6, n] columns of the finished CX report."""
+        cols = self.torch.empty((6, n), dtype=self.torch.int32, device=self.device)     # row i = column i, contiguous
+        if n:
+            _lib.check(self.lib.epi_batch_cx_fetch_dev(self.h, _ptr_array([cols[i] for i in range(6)]), self._stream()))
+        return cols
+
+    def _fetch_mhl(self, n):
+        """This rank's ([5, n] int32, [2, n] float64) columns of the finished lMHL report."""
+        icols = self.torch.empty((5, n), dtype=self.torch.int32, device=self.device)
+        dcols = self.torch.empty((2, n), dtype=self.torch.float64, device=self.device)
+        if n:
+            _lib.check(self.lib.epi_batch_mhl_fetch_dev(self.h, _ptr_array([icols[i] for i in range(5)]),
+                                                        _ptr_array([dcols[i] for i in range(2)]), self._stream()))
+        return icols, dcols
+
+    def _attach_slabs(self, kind, keys, owned, ctx=None):
+        """Zeroed slabs for the shared tiles `keys` of a "cx", "mhl" or "mhlf" report, attached to the batch with the keys
+        and this rank's owned flags (no keys: everything detached).  Elements per tile, from the library's tile sizes
+        (include/epihip.h): CX int32 [16][T]; two-kernel lMHL int32 [16][T] and epi_mhl_slab_sums() int64; one-pass lMHL
+        int32 [4][T] and int64 [6][T]."""
+        torch, lib = self.torch, self.lib
+        if kind == "cx":
+            per_tile, set_shared = (16 * self.tile_positions(ctx),), lib.epi_batch_cx_set_shared
+        elif kind == "mhlf":
+            T = lib.epi_mhl_fused_tile_positions()
+            per_tile, set_shared = (4 * T, 6 * T), lib.epi_batch_mhl_set_shared_fused
+        else:
+            per_tile, set_shared = (16 * lib.epi_mhl_tile_positions(), lib.epi_mhl_slab_sums()), lib.epi_batch_mhl_set_shared
+        want = [max(keys.size, 1) * k for k in per_tile]
+        slabs = self._slabs.get(kind[:3])
+        if slabs is None or [t.numel() for t in slabs] != want:
+            slabs = [torch.zeros(w, dtype=dt, device=self.device) for w, dt in zip(want, (torch.int32, torch.int64))]
+            self._slabs[kind[:3]] = slabs
+        else:
+            for t in slabs:
+                t.zero_()
+        keys = np.ascontiguousarray(keys, np.int64)
+        owned = np.ascontiguousarray(owned, np.int32)
+        ptr = lambda p: C.c_void_p(p) if keys.size else None
+        _lib.check(set_shared(self.h, ptr(keys.ctypes.data), ptr(owned.ctypes.data), int(keys.size), *[ptr(t.data_ptr()) for t in slabs]))
+        self._nshared = int(keys.size)
+        return slabs
+
+    def _attach_cx_slab(self, keys, owned, ctx):           # the CX slab alone (tests/test_gpu_fdrp.py attaches one without a report)
+        return self._attach_slabs("cx", keys, owned, ctx)[0]
+
+    # ---- CX ------------------------------------------------------------------------------------------
     def native_cx(self, pass_, ctx, threshold=None):
         """epi_batch_cytosine_report_sharded: steps 1-5 in one C call; returns this rank's [6, nrow] columns."""
-        torch = self.torch
         nrow = C.c_int64(0)
         thr = threshold or (None, None, None, None, 0, 0.0, 0.0)
         enc = lambda v: _lib.enc(v) if v is not None else None
         _lib.check(self.lib.epi_batch_cytosine_report_sharded(
             self.h, self.comm, enc(thr[0]), enc(thr[1]), enc(thr[2]), enc(thr[3]), int(thr[4]), float(thr[5]), float(thr[6]),
             C.c_void_p(pass_.data_ptr()) if (pass_ is not None and threshold is None and self.bam.n) else None,
-            _lib.enc(ctx), None, _stream(self.bam.device), C.byref(nrow)))
-        n = nrow.value
-        cols = torch.empty((6, n), dtype=torch.int32, device=self.device)
-        if n:
-            _lib.check(self.lib.epi_batch_cx_fetch_dev(self.h, _ptr_array([cols[i] for i in range(6)]), _stream(self.bam.device)))
+            _lib.enc(ctx), None, self._stream(), C.byref(nrow)))
+        cols = self._fetch_cx(nrow.value)
         self.last_exchange_bytes = int(self.lib.epi_comm_last_exchange_bytes(self.comm))
         return cols
-
-    def native_mhl(self, ctx, hmax, hmin, max_oo):
-        """epi_batch_mhl_report_sharded; returns this rank's ([5, nrow] int32, [2, nrow] float64) columns."""
-        torch = self.torch
-        nrow = C.c_int64(0)
-        _lib.check(self.lib.epi_batch_mhl_report_sharded(self.h, self.comm, _lib.enc(ctx), int(hmax), int(hmin), float(max_oo),
-                                                         _stream(self.bam.device), C.byref(nrow)))
-        n = nrow.value
-        icols = torch.empty((5, n), dtype=torch.int32, device=self.device)
-        dcols = torch.empty((2, n), dtype=torch.float64, device=self.device)
-        if n:
-            _lib.check(self.lib.epi_batch_mhl_fetch_dev(self.h, _ptr_array([icols[i] for i in range(5)]),
-                                                        _ptr_array([dcols[i] for i in range(2)]), _stream(self.bam.device)))
-        self.last_exchange_bytes = int(self.lib.epi_comm_last_exchange_bytes(self.comm))
-        return icols, dcols
 
     def tile_positions(self, ctx="Z"):
         """Positions per CX tile for this report context string (one reported context: 2048, else 1024)."""
         return self.lib.epi_cx_tile_positions(_lib.enc(ctx))
-
-    def mhl_fused_ok(self, ctx):
-        """Can THIS rank's rows take the one-pass lMHL kernel for `ctx`?  (All ranks must take the same path: the
-        answers are combined in _exchange_ranges.)"""
-        ok = C.c_int32(0)
-        _lib.check(self.lib.epi_batch_mhl_fused_ok(self.h, _lib.enc(ctx), _stream(self.bam.device), C.byref(ok)))
-        return bool(ok.value)
-
-    def mhl_tile_positions(self, fused):
-        return self.lib.epi_mhl_fused_tile_positions() if fused else self.lib.epi_mhl_tile_positions()
 
     def key_range(self, kind="cx", ctx="Z"):
         # a property of the resident (immutable) shard and the tile grid: computed once per tile size
         T = self.tile_positions(ctx) if kind == "cx" else self.mhl_tile_positions(kind == "mhlf")
         if (kind, T) not in self._range:
             a, b = C.c_int64(0), C.c_int64(-1)
-            _lib.check(self.lib.epi_batch_tile_key_range_for(self.h, T, _stream(self.bam.device), C.byref(a), C.byref(b)))
+            _lib.check(self.lib.epi_batch_tile_key_range_for(self.h, T, self._stream(), C.byref(a), C.byref(b)))
             self._range[(kind, T)] = (a.value, b.value)
         return self._range[(kind, T)]
 
@@ -173,32 +200,14 @@ class HipShardEngine:
         return rcpp_threshold_reads(self.bam, ctx_meth, ctx_unmeth, ooctx_meth, ooctx_unmeth, min_n, min_frac,
                                     max_oo, as_device=True)
 
-    def _attach_cx_slab(self, keys, owned, ctx):
-        torch = self.torch
-        T = self.tile_positions(ctx)
-        want = max(keys.size, 1) * 16 * T
-        if self._slab is None or self._slab.numel() != want:
-            self._slab = torch.zeros(want, dtype=torch.int32, device=self.device)
-        else:
-            self._slab.zero_()
-        keys = np.ascontiguousarray(keys, np.int64)
-        owned = np.ascontiguousarray(owned, np.int32)
-        _lib.check(self.lib.epi_batch_cx_set_shared(
-            self.h, C.c_void_p(keys.ctypes.data) if keys.size else None,
-            C.c_void_p(owned.ctypes.data) if keys.size else None, int(keys.size),
-            C.c_void_p(self._slab.data_ptr()) if keys.size else None))
-        self._nshared = int(keys.size)
-        return self._slab
-
     def cx_accumulate(self, pass_, ctx, keys, owned):
-        self._attach_cx_slab(keys, owned, ctx)
-        self._nshared = int(keys.size)
+        slab = self._attach_cx_slab(keys, owned, ctx)
         nrow = C.c_int64(0)
         _lib.check(self.lib.epi_batch_cx_report_dev(
             self.h, C.c_void_p(pass_.data_ptr()) if pass_ is not None and self.bam.n else None,
-            _lib.enc(ctx), _stream(self.bam.device), C.byref(nrow)))
+            _lib.enc(ctx), self._stream(), C.byref(nrow)))
         self._nrow = nrow.value
-        return self._slab
+        return slab
 
     def cx_accumulate_fused(self, thr, ctx, keys, owned):
         """cx_accumulate with the thresholding (thr = the seven rcpp_threshold_reads arguments) done inside the tile kernel."""
@@ -206,86 +215,68 @@ class HipShardEngine:
         nrow = C.c_int64(0)
         _lib.check(self.lib.epi_batch_cytosine_report_dev(
             self.h, _lib.enc(thr[0]), _lib.enc(thr[1]), _lib.enc(thr[2]), _lib.enc(thr[3]), int(thr[4]), float(thr[5]),
-            float(thr[6]), _lib.enc(ctx), None, _stream(self.bam.device), C.byref(nrow)))
+            float(thr[6]), _lib.enc(ctx), None, self._stream(), C.byref(nrow)))
         self._nrow = nrow.value
         return slab
 
     def cx_finish(self, ctx):
-        torch = self.torch
         nrow = C.c_int64(self._nrow)
         if self._nshared:
-            _lib.check(self.lib.epi_batch_cx_finish_shared(self.h, _lib.enc(ctx), _stream(self.bam.device), C.byref(nrow)))
-        n = nrow.value
-        cols = torch.empty((6, n), dtype=torch.int32, device=self.device)     # row i = column i, contiguous
-        if n:
-            _lib.check(self.lib.epi_batch_cx_fetch_dev(self.h, _ptr_array([cols[i] for i in range(6)]),
-                                                       _stream(self.bam.device)))
+            _lib.check(self.lib.epi_batch_cx_finish_shared(self.h, _lib.enc(ctx), self._stream(), C.byref(nrow)))
+        cols = self._fetch_cx(nrow.value)
         # detach the shared-tile state so that later single-GPU calls on this batch emit every tile
         _lib.check(self.lib.epi_batch_cx_set_shared(self.h, None, None, 0, None))
         return cols
 
-
     # ---- lMHL -----------------------------------------------------------------------------------
+    def native_mhl(self, ctx, hmax, hmin, max_oo):
+        """epi_batch_mhl_report_sharded; returns this rank's ([5, nrow] int32, [2, nrow] float64) columns."""
+        nrow = C.c_int64(0)
+        _lib.check(self.lib.epi_batch_mhl_report_sharded(self.h, self.comm, _lib.enc(ctx), int(hmax), int(hmin), float(max_oo),
+                                                         self._stream(), C.byref(nrow)))
+        cols = self._fetch_mhl(nrow.value)
+        self.last_exchange_bytes = int(self.lib.epi_comm_last_exchange_bytes(self.comm))
+        return cols
+
+    def mhl_fused_ok(self, ctx):
+        """Can THIS rank's rows take the one-pass lMHL kernel for `ctx`?  (All ranks must take the same path: the
+        answers are combined in _exchange_ranges.)"""
+        ok = C.c_int32(0)
+        _lib.check(self.lib.epi_batch_mhl_fused_ok(self.h, _lib.enc(ctx), self._stream(), C.byref(ok)))
+        return bool(ok.value)
+
+    def mhl_tile_positions(self, fused):
+        return self.lib.epi_mhl_fused_tile_positions() if fused else self.lib.epi_mhl_tile_positions()
+
     def mhl_accumulate(self, ctx, hmax, hmin, max_oo, keys, owned, fused=False):
-        torch = self.torch
-        n = max(keys.size, 1)
-        if fused:        # the one-pass kernel's slabs: int32 [n][4][T] and int64 [n][6][T] (include/epihip.h)
-            T = self.lib.epi_mhl_fused_tile_positions()
-            want = (n * 4 * T, n * 6 * T)
-        else:
-            T, NS = self.lib.epi_mhl_tile_positions(), self.lib.epi_mhl_slab_sums()
-            want = (n * 16 * T, n * NS)
-        if getattr(self, "_mcnt", None) is None or (self._mcnt.numel(), self._msum.numel()) != want:
-            self._mcnt = torch.zeros(want[0], dtype=torch.int32, device=self.device)
-            self._msum = torch.zeros(want[1], dtype=torch.int64, device=self.device)
-        else:
-            self._mcnt.zero_()
-            self._msum.zero_()
-        keys = np.ascontiguousarray(keys, np.int64)
-        owned = np.ascontiguousarray(owned, np.int32)
-        set_shared = self.lib.epi_batch_mhl_set_shared_fused if fused else self.lib.epi_batch_mhl_set_shared
-        _lib.check(set_shared(
-            self.h, C.c_void_p(keys.ctypes.data) if keys.size else None,
-            C.c_void_p(owned.ctypes.data) if keys.size else None, int(keys.size),
-            C.c_void_p(self._mcnt.data_ptr()) if keys.size else None,
-            C.c_void_p(self._msum.data_ptr()) if keys.size else None))
-        self._nshared = int(keys.size)
+        cnt, sums = self._attach_slabs("mhlf" if fused else "mhl", keys, owned)
         nrow = C.c_int64(0)
         _lib.check(self.lib.epi_batch_mhl_report_dev(self.h, _lib.enc(ctx), int(hmax), int(hmin), float(max_oo),
-                                                     _stream(self.bam.device), C.byref(nrow)))
+                                                     self._stream(), C.byref(nrow)))
         self._nrow = nrow.value
-        return self._mcnt, self._msum
+        return cnt, sums
 
     def mhl_finish(self):
-        torch = self.torch
         nrow = C.c_int64(self._nrow)
         if self._nshared:
-            _lib.check(self.lib.epi_batch_mhl_finish_shared(self.h, _stream(self.bam.device), C.byref(nrow)))
-        n = nrow.value
-        icols = torch.empty((5, n), dtype=torch.int32, device=self.device)
-        dcols = torch.empty((2, n), dtype=torch.float64, device=self.device)
-        if n:
-            _lib.check(self.lib.epi_batch_mhl_fetch_dev(self.h, _ptr_array([icols[i] for i in range(5)]),
-                                                        _ptr_array([dcols[i] for i in range(2)]), _stream(self.bam.device)))
+            _lib.check(self.lib.epi_batch_mhl_finish_shared(self.h, self._stream(), C.byref(nrow)))
+        cols = self._fetch_mhl(nrow.value)
         _lib.check(self.lib.epi_batch_mhl_set_shared(self.h, None, None, 0, None, None))
-        return icols, dcols
+        return cols
 
 
 def _exchange_ranges(engine, kind, group, ctx="Z"):
-    """all_gather of every rank's (first,last) tile key -> (ranges, world, rank).  The shards and the tile grid do not
-    change, so the exchange is done once per (engine, tile grid, group) and remembered on the engine."""
+    """all_gather of every rank's (first,last) tile key -> every rank's range (lMHL: (ranges, fused)).  The shards and the
+    tile grid do not change, so the exchange is done once per (engine, tile grid, group) and remembered on the engine."""
     import torch
     import torch.distributed as dist
-    world = dist.get_world_size(group) if dist.is_initialized() else 1
-    rank = dist.get_rank(group) if dist.is_initialized() else 0
+    world, _ = _world_rank(group)
     memo = engine.__dict__.setdefault("_all_ranges", {})
-    T = engine.tile_positions(ctx) if kind == "cx" else 0
-    kind = (kind, T if kind == "cx" else ctx)
-    if (kind, id(group), world) in memo:
-        return memo[(kind, id(group), world)], world, rank
-    if kind[0] == "cx":
-        first, last = engine.key_range("cx", ctx)
-        mine = [first, last]
+    memo_key = ((kind, engine.tile_positions(ctx) if kind == "cx" else ctx), id(group), world)
+    if memo_key in memo:
+        return memo[memo_key]
+    if kind == "cx":
+        mine = list(engine.key_range("cx", ctx))
     else:
         # lMHL: both tile grids' ranges and whether this rank's rows allow the one-pass kernel; the ranks take it only
         # if all of them can (one all_gather decides path and shared tiles alike)
@@ -300,13 +291,29 @@ def _exchange_ranges(engine, kind, group, ctx="Z"):
         rows = [[int(v) for v in t.cpu().tolist()] for t in allr]
     else:
         rows = [mine]
-    if kind[0] == "cx":
+    if kind == "cx":
         ranges = [tuple(r) for r in rows]
     else:
         fused = all(r[4] for r in rows)
         ranges = ([(r[2], r[3]) for r in rows] if fused else [(r[0], r[1]) for r in rows], fused)
-    memo[(kind, id(group), world)] = ranges
-    return ranges, world, rank
+    memo[memo_key] = ranges
+    return ranges
+
+
+def _shared_tiles(ranges, group):
+    """Step 2: (shared tile keys, this rank's owned flags) from every rank's key range."""
+    keys, owner = shared_tile_keys(ranges)
+    return keys, (owner == _world_rank(group)[1]).astype(np.int32)
+
+
+def _all_reduce(engine, slabs, nshared, group):
+    """Step 4: the one data-path collective, all_reduce(sum) of each slab (nothing to do without a shared tile or a second rank)."""
+    import torch.distributed as dist
+    exchange = _world_rank(group)[0] > 1 and nshared > 0
+    engine.last_exchange_bytes = sum(int(t.numel() * t.element_size()) for t in slabs) if exchange else 0
+    if exchange:
+        for t in slabs:
+            dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
 
 
 def _gather_rows(tensors, group, world, rank, dev):
@@ -340,42 +347,29 @@ def _gather_rows(tensors, group, world, rank, dev):
     return outs
 
 
+def _report(engine, blocks, names, group, gather, levels):
+    """Step 6: this rank's column blocks ([k, nrow] tensors, the columns in `names` order) -> the Report; with gather=True
+    and more than one rank the full table on rank 0 (rows -> rank 0, concatenated in rank order), None elsewhere."""
+    world, rank = _world_rank(group)
+    if gather and world > 1:
+        blocks = _gather_rows(blocks, group, world, rank, engine.device)
+        if blocks is None:
+            return None
+    return Report(dict(zip(names, [blk[i] for blk in blocks for i in range(blk.shape[0])])), levels)
+
+
 def sharded_mhl_report(engine, ctx, hmax, hmin, max_ooctx_meth_frac, group=None, gather=True, levels=None):
     """rcpp_mhl_report over row-range shards (same exchange as the CX table, on 512-position tiles; the
     64-bit sums travel as int64 and add with wrap-around, which is what unsigned addition does)."""
-    import torch.distributed as dist
     if getattr(engine, "comm", None) is not None:          # RCCL behind the C ABI: steps 1-5 in one call
-        world = dist.get_world_size(group) if dist.is_initialized() else 1
-        rank = dist.get_rank(group) if dist.is_initialized() else 0
-        icols, dcols = engine.native_mhl(ctx, hmax, hmin, max_ooctx_meth_frac)
-        names = ("rname", "strand", "pos", "context", "coverage", "length", "lmhl")
-        if gather and world > 1:
-            got = _gather_rows([icols, dcols], group, world, rank, engine.device)
-            if got is None:
-                return None
-            icols, dcols = got
-        return Report(dict(zip(names, [icols[i] for i in range(5)] + [dcols[i] for i in range(2)])), levels)
-    (ranges, fused), world, rank = _exchange_ranges(engine, "mhl", group, ctx)
-    keys, owner = shared_tile_keys(ranges)
-    owned = (owner == rank).astype(np.int32)
-    if fused:
-        cnt_slab, sum_slab = engine.mhl_accumulate(ctx, hmax, hmin, max_ooctx_meth_frac, keys, owned, fused=True)
+        blocks = engine.native_mhl(ctx, hmax, hmin, max_ooctx_meth_frac)
     else:
-        cnt_slab, sum_slab = engine.mhl_accumulate(ctx, hmax, hmin, max_ooctx_meth_frac, keys, owned)
-    engine.last_exchange_bytes = (int(cnt_slab.numel() * cnt_slab.element_size() + sum_slab.numel() * sum_slab.element_size())
-                                  if (world > 1 and keys.size) else 0)
-    if world > 1 and keys.size:
-        dist.all_reduce(cnt_slab, op=dist.ReduceOp.SUM, group=group)
-        dist.all_reduce(sum_slab, op=dist.ReduceOp.SUM, group=group)
-    icols, dcols = engine.mhl_finish()
-    names = ("rname", "strand", "pos", "context", "coverage", "length", "lmhl")
-    if gather and world > 1:
-        got = _gather_rows([icols, dcols], group, world, rank, engine.device)
-        if got is None:
-            return None
-        icols, dcols = got
-    cols = [icols[i] for i in range(5)] + [dcols[i] for i in range(2)]
-    return Report(dict(zip(names, cols)), levels)
+        ranges, fused = _exchange_ranges(engine, "mhl", group, ctx)
+        keys, owned = _shared_tiles(ranges, group)
+        slabs = engine.mhl_accumulate(ctx, hmax, hmin, max_ooctx_meth_frac, keys, owned, fused=fused)
+        _all_reduce(engine, slabs, keys.size, group)
+        blocks = engine.mhl_finish()
+    return _report(engine, blocks, MHL_COLUMNS, group, gather, levels)
 
 
 def sharded_mhl(engine, haplotype_context="CG", max_haplotype_window=0, min_haplotype_length=0,
@@ -390,40 +384,19 @@ def sharded_cx_report(engine, pass_, ctx, group=None, gather=True, levels=None, 
     """rcpp_cx_report over row-range shards.  Returns the full Report on rank 0 (None elsewhere)
     when gather=True, else this rank's rows (rank order = table order).  threshold = the seven
     rcpp_threshold_reads arguments: thresholding is then done inside the tile kernel (pass_ is ignored)."""
-    import torch
-    import torch.distributed as dist
-    names = ("rname", "strand", "pos", "context", "meth", "unmeth")
     if getattr(engine, "comm", None) is not None:          # RCCL behind the C ABI: steps 1-5 in one call
-        world = dist.get_world_size(group) if dist.is_initialized() else 1
-        rank = dist.get_rank(group) if dist.is_initialized() else 0
         cols = engine.native_cx(pass_, ctx, threshold)
-        if gather and world > 1:
-            got = _gather_rows([cols], group, world, rank, engine.device)
-            if got is None:
-                return None
-            cols = got[0]
-        return Report({k: cols[i] for i, k in enumerate(names)}, levels)
-    ranges, world, rank = _exchange_ranges(engine, "cx", group, ctx)
-    dev = engine.device
-    keys, owner = shared_tile_keys(ranges)
-    owned = (owner == rank).astype(np.int32)
-    if threshold is not None and hasattr(engine, "cx_accumulate_fused"):
-        slab = engine.cx_accumulate_fused(threshold, ctx, keys, owned)
     else:
-        if threshold is not None:
-            pass_ = engine.threshold(*threshold)
-        slab = engine.cx_accumulate(pass_, ctx, keys, owned)
-    engine.last_exchange_bytes = int(slab.numel() * slab.element_size()) if (world > 1 and keys.size) else 0
-    if world > 1 and keys.size:
-        dist.all_reduce(slab, op=dist.ReduceOp.SUM, group=group)      # the one data-path collective
-    cols = engine.cx_finish(ctx)                                      # [6, nrow_local] int32
-    names = ("rname", "strand", "pos", "context", "meth", "unmeth")
-    if not gather or world == 1:
-        return Report({k: cols[i] for i, k in enumerate(names)}, levels)
-    got = _gather_rows([cols], group, world, rank, dev)               # rows -> rank 0, concatenated in rank order
-    if got is None:
-        return None
-    return Report({k: got[0][i] for i, k in enumerate(names)}, levels)
+        keys, owned = _shared_tiles(_exchange_ranges(engine, "cx", group, ctx), group)
+        if threshold is not None and hasattr(engine, "cx_accumulate_fused"):
+            slab = engine.cx_accumulate_fused(threshold, ctx, keys, owned)
+        else:
+            if threshold is not None:
+                pass_ = engine.threshold(*threshold)
+            slab = engine.cx_accumulate(pass_, ctx, keys, owned)
+        _all_reduce(engine, [slab], keys.size, group)
+        cols = engine.cx_finish(ctx)                       # [6, nrow_local] int32
+    return _report(engine, [cols], CX_COLUMNS, group, gather, levels)
 
 
 def sharded_cytosine_report(engine, threshold_reads=True, threshold_context="CG", min_context_sites=2,

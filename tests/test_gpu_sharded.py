@@ -243,6 +243,87 @@ def test_library_comm_single_rank(tmp_path):
                                    float_cols=("length", "lmhl"))
 
 
+SEAM_REPORTS = ("CG", "CX", "Zz", "ZzXxHh")                # thresholded CG, un-thresholded CX; one-pass and two-kernel lMHL
+
+
+def _seam_case(name):
+    """The two ends of "which tiles are shared": a batch without rows (no tile at all), and 40 rows of 100 bytes whose
+    positions all lie in the 1024-position tile [2048, 3072) of one reference sequence -- with 5 forced shared tiles every
+    tile of every grid (2048, 1024 and 512 positions) is shared and owned, none is local."""
+    if name == "empty":
+        z = np.zeros(0, np.int32)
+        return {"xm": np.zeros(0, np.uint8), "off": np.zeros(1, np.int64), "rname": z, "strand": z, "start": z}
+    t = synth_np.random_templates(np.random.default_rng(5), 40, 100, 100, 1, 1024 - 100 + 1, alphabet="." * 30 + "z" * 30 + "Z" * 40 + "hxHX")   # (few out-of-context calls: most reads pass)
+    t["start"] = (t["start"] + 2047).astype(np.int32)
+    assert t["start"].min() >= 2048 and t["start"].max() + 100 <= 3072
+    return t
+
+
+def _seam_worker(rank, port, outdir):
+    """Both seam batches through the four sharded reports on the library communicator (world size 1, 5 forced shared
+    tiles), then the plain cytosine report on the same batch: the shared-tile state must be gone."""
+    sys.path.insert(0, HERE)
+    sys.path.insert(0, os.path.dirname(HERE))
+    os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+    import torch
+    torch.cuda.set_device(0)
+    import epialleler_amd as ea
+    from epialleler_amd import distributed as D
+    for name in ("empty", "one_tile"):
+        t = _seam_case(name)
+        shard = ea.ProcessedBam.from_arrays(t["xm"], t["off"], t["rname"], t["strand"], t["start"])
+        eng = D.HipShardEngine(shard).attach_comm(test_shared=5)
+        sent = []
+        for what in SEAM_REPORTS:
+            if what in ("CG", "CX"):
+                rep = D.sharded_cytosine_report(eng, threshold_reads=what == "CG", report_context=what, gather=True)
+            else:
+                rep = D.sharded_mhl_report(eng, what, 0, 0, 0.1, gather=True)
+            sent.append(eng.last_exchange_bytes)
+            np.savez(os.path.join(outdir, "seam_%s_%s.npz" % (name, what)), **{k: v.cpu().numpy() for k, v in rep.items()})
+        np.save(os.path.join(outdir, "seam_%s_bytes.npy" % name), np.asarray(sent, np.int64))
+        np.savez(os.path.join(outdir, "seam_%s_plain.npz" % name), **dict(ea.generateCytosineReport(shard, threshold_reads=True)))
+        eng.close_comm()
+        shard.close()
+
+
+@pytest.fixture(scope="module")
+def seam_dir(tmp_path_factory):
+    import torch.multiprocessing as mp
+    d = str(tmp_path_factory.mktemp("seam"))
+    mp.spawn(_seam_worker, args=(_free_port(), d), nprocs=1, join=True)
+    return d
+
+
+def _seam_tables(seam_dir, name):
+    load = lambda what: dict(np.load(os.path.join(seam_dir, "seam_%s_%s.npz" % (name, what))))
+    return {what: load(what) for what in SEAM_REPORTS + ("plain",)}, np.load(os.path.join(seam_dir, "seam_%s_bytes.npy" % name))
+
+
+def test_sharded_reports_of_a_batch_without_rows(seam_dir):
+    got, sent = _seam_tables(seam_dir, "empty")
+    assert sent.tolist() == [0, 0, 0, 0]                    # no tile, so no shared tile: nothing travels
+    for what in SEAM_REPORTS + ("plain",):
+        assert got[what] and all(v.size == 0 for v in got[what].values()), what
+
+
+def test_sharded_reports_with_every_tile_shared(seam_dir):
+    got, sent = _seam_tables(seam_dir, "one_tile")
+    assert all(b > 0 for b in sent.tolist()), sent
+    t = _seam_case("one_tile")
+    c = H.CONTEXT_TO_BASES["CG"]
+    p = orc.threshold_reads(t["xm"], t["off"], c["ctx_meth"], c["ctx_unmeth"], c["ooctx_meth"], c["ooctx_unmeth"], 2, 0.5, 0.1)
+    want_cg = orc.cx_report(t["xm"], t["off"], t["rname"], t["strand"], t["start"], p, "Z")
+    assert want_cg["pos"].size > 0
+    H.assert_reports_equal(got["CG"], want_cg)
+    H.assert_reports_equal(got["plain"], want_cg)
+    H.assert_reports_equal(got["CX"], orc.cx_report(t["xm"], t["off"], t["rname"], t["strand"], t["start"], None, "ZXH"))
+    for ctx in ("Zz", "ZzXxHh"):
+        want = orc.mhl_report(t["xm"], t["off"], t["rname"], t["strand"], t["start"], ctx, 0, 0, 0.1)
+        assert want["pos"].size > 0
+        H.assert_reports_equal(got[ctx], want, float_cols=("length", "lmhl"))
+
+
 def _nccl_worker(rank, world, port, outdir):
     """Real RCCL ranks, one GPU each (needs >= 2 devices): sharded CX and lMHL tables gathered on rank 0."""
     sys.path.insert(0, HERE)
