@@ -6,10 +6,10 @@ callMethylation, rcpp_simulate_bam for simulateBam) behind the reference's own R
 Compute lives in csrc/ (hand-written HIP for gfx950 behind the C ABI of
 include/epihip.h); this package is the host-side mirror of the R functions.
 """
-from .api import (CONTEXT_TO_BASES, CONTEXT_LEVELS, FDRP_COLUMNS, GROUP_COMPARE_COLUMNS, GROUP_TESTS, P_ADJUST_METHODS, REGION_COLUMNS, STRAND_LEVELS, ProcessedBam, Report, adjustPValues, adjustReport,  # noqa: F401
+from .api import (CONTEXT_TO_BASES, CONTEXT_LEVELS, FDRP_COLUMNS, GROUP_COMPARE_COLUMNS, GROUP_TESTS, MBIAS_COLUMNS, P_ADJUST_METHODS, REGION_COLUMNS, STRAND_LEVELS, ProcessedBam, Report, adjustPValues, adjustReport,  # noqa: F401
                   chisqPValues, compareCytosineGroups, compareCytosineReports, compareHeterogeneity, generateGroupDmrReport, rcpp_cx_compare_groups, tTestPValues,
                   cytosine_report_fused, fisherExact, generateAdjustedDmrReport, generateCytosineReport, generateDmrReport, generateFdrpReport, generateHaplotypeBlocks, generateHeterogeneityReport, generateLinkageReport,
-                  generateMhlReport, preprocessBam,
+                  generateMbiasReport, generateMhlReport, preprocessBam, rcpp_mbias_report, suggestTrim,
                   rcpp_cx_compare, rcpp_cx_compare_regions, rcpp_cx_report, rcpp_fdrp_report, rcpp_heterogeneity_compare, rcpp_heterogeneity_report, rcpp_linkage_blocks, rcpp_linkage_report,
                   rcpp_extract_patterns, rcpp_extract_patterns_multi, rcpp_get_xm_beta, rcpp_mhl_report, rcpp_region_report, rcpp_summarise_patterns_multi,
                   rcpp_threshold_reads, writeReport)

@@ -180,6 +180,7 @@ _SIGS = {
     "epi_batch_region_report_dev": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _CS, _I32, _I32, _I32, _F64, _F64, _F64, C.POINTER(_VP), C.POINTER(_VP),
                                               _VP]),
     "epi_region_counter_bytes": (C.c_int, [_I64, _I32, C.POINTER(_I64)]),
+    "epi_batch_mbias_report_dev": (C.c_int, [_VP, _I32, _VP, _VP, _VP]),
     "epi_batch_asm_report_dev": (C.c_int, [_VP, _VP, _VP, _VP, _I64, _CS, _I32, _I32, _F64, C.POINTER(_VP), C.POINTER(_VP), _VP,
                                            C.POINTER(_I64)]),
     "epi_batch_asm_fetch_dev": (C.c_int, [_VP, C.POINTER(_VP), C.POINTER(_VP), _VP]),

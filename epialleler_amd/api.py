@@ -564,6 +564,69 @@ def rcpp_region_report(df, regions, ctx, min_sites, max_sites, reverse_offset, u
     return Report(dict(zip(REGION_COLUMNS, cols)), bam.levels)
 
 
+MBIAS_COLUMNS = ("end", "strand", "context", "offset", "meth", "unmeth", "beta")
+MBIAS_END_LEVELS = ("start", "end")
+_MBIAS_CODES = (2, 6, 7)                                  # context codes in table order: CHH, CHG, CG
+_MBIAS_MAX_OFFSET = 1024
+
+
+def _beta(meth, unmeth):
+    """meth / (meth + unmeth) in float64, NaN at 0 / 0 (numpy arrays or tensors)"""
+    if isinstance(meth, np.ndarray):
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return meth.astype(np.float64) / (meth + unmeth).astype(np.float64)
+    return meth.double() / (meth + unmeth).double()
+
+
+def _mbias_select(rep, codes):
+    """The rows of an M-bias report (and of its totals) whose context code is one of `codes`, in their order"""
+    def rows(r):
+        ctx = r["context"]
+        keep = np.isin(ctx, codes) if isinstance(ctx, np.ndarray) else sum(ctx == c for c in codes).bool()
+        out = Report({k: v[keep] for k, v in r.items()}, r.levels["rname"])
+        out.levels = dict(r.levels)
+        return out
+    out = rows(rep)
+    out.totals = rows(rep.totals)
+    return out
+
+
+def rcpp_mbias_report(df, max_offset, as_device=False):
+    """Methylation by offset from either end of the template (include/epihip.h, epi_batch_mbias_report_dev): 12 * max_offset
+    dense rows in the order end (1 = start, 2 = end), strand, context (2 = CHH, 6 = CHG, 7 = CG), offset (0-based), all-zero
+    rows included; meth and unmeth (int32) count the bytes of that class at that offset of that end over every row of the
+    batch, beta = meth / (meth + unmeth) in float64 (NaN at 0 / 0).  The Report's `totals` (always on the host) has one row
+    per strand and context over every byte of the batch: strand, context, meth, unmeth (int64) and beta."""
+    torch = _torch()
+    max_offset = _whole_number(max_offset, "max.offset", 1, _MBIAS_MAX_OFFSET)
+    bam = _as_bam(df)
+    b = bam.batch()
+    dev = "cuda:%d" % bam.device
+    counts = torch.empty(24 * max_offset, dtype=torch.int64, device=dev)
+    totals = torch.empty(12, dtype=torch.int64, device=dev)
+    _lib.check(_lib.load().epi_batch_mbias_report_dev(b, max_offset, C.c_void_p(counts.data_ptr()), C.c_void_p(totals.data_ptr()),
+                                                      _stream(bam.device)))
+    if int(counts.max()) > 2 ** 31 - 1:                   # (a cell gets at most one count per row)
+        raise ValueError("rcpp_mbias_report: a cell counts more than 2^31 - 1 rows, which an int32 column cannot hold")
+    cells = counts.view(-1, 2).to(torch.int32)
+    meth, unmeth = cells[:, 0].contiguous(), cells[:, 1].contiguous()
+    grid = np.indices((2, 2, 3, max_offset), dtype=np.int32).reshape(4, -1)
+    keys = [grid[0] + 1, grid[1] + 1, np.asarray(_MBIAS_CODES, np.int32)[grid[2]], grid[3]]
+    if as_device:
+        cols = [torch.from_numpy(np.ascontiguousarray(k)).to(dev) for k in keys] + [meth, unmeth]
+    else:
+        cols = keys + [meth.cpu().numpy(), unmeth.cpu().numpy()]
+    cols.append(_beta(cols[4], cols[5]))
+    rep = Report(dict(zip(MBIAS_COLUMNS, cols)), bam.levels)
+    rep.levels["end"] = MBIAS_END_LEVELS
+    t = totals.cpu().numpy().reshape(6, 2)
+    tg = np.indices((2, 3), dtype=np.int32).reshape(2, -1)
+    tm, tu = np.ascontiguousarray(t[:, 0]), np.ascontiguousarray(t[:, 1])
+    rep.totals = Report(dict(strand=tg[0] + 1, context=np.asarray(_MBIAS_CODES, np.int32)[tg[1]], meth=tm, unmeth=tu, beta=_beta(tm, tu)),
+                        bam.levels)
+    return rep
+
+
 CX_COMPARE_COLUMNS = ("rname", "strand", "pos", "context", "meth_a", "unmeth_a", "meth_b", "unmeth_b", "beta_a", "beta_b", "delta_beta", "p")
 DMR_COLUMNS = ("rname", "start", "end", "nsites", "direction", "beta_a", "beta_b", "delta_beta", "mean_delta_beta", "p")
 
@@ -1131,6 +1194,61 @@ def generateFdrpReport(bam, report_file=None, fdrp_context=None, flank_sites=8, 
     rep = rcpp_fdrp_report(bam, c["ctx_meth"] + c["ctx_unmeth"], flank_sites, max_reads, min_overlap, max_distance,
                            max_outofcontext_beta, min_reads, as_device=as_device)
     return _deliver(rep, report_file, gzip)
+
+
+def _context_codes(context):
+    """The context codes (2 = CHH, 6 = CHG, 7 = CG) of one of _CTX_CHOICES"""
+    return [((ord(ch) + 2) >> 2) & 7 for ch in CONTEXT_TO_BASES[context]["ctx_meth"]]
+
+
+def generateMbiasReport(bam, report_file=None, report_context="CX", max_offset=150, gzip=False, verbose=False, as_device=False,
+                        **preprocess_args):
+    """M-bias table: methylation as a function of the offset from either end of the template, per strand and context -- the
+    quality-control table that tells how many end bases to pass as preprocessBam(trim=) (suggestTrim reads it off).  Every
+    template counts as it is packed: no thresholding, no read rule.  One row per end ("start": offset 0 is the template's
+    first base; "end": offset 0 is its last), strand, context of `report_context` and offset 0 .. max_offset - 1 (1 to 1024
+    offsets), rows without calls included: meth, unmeth and beta = meth / (meth + unmeth).  Offsets are template
+    coordinates, the filler between mates included, so trim = (t5, t3) removes exactly the offsets < t5 of "start" and < t3
+    of "end".  The Report's `totals` gives meth, unmeth and beta per strand and context over ALL bases, whatever max_offset
+    is: its CHG and CHH rows are the usual estimate of incomplete bisulfite conversion.  The kernel counts every context;
+    report_context only selects the rows.  The reference has no such report."""
+    report_context = _match_arg(report_context, _CTX_CHOICES, "report.context")
+    max_offset = _whole_number(max_offset, "max.offset", 1, _MBIAS_MAX_OFFSET)
+    bam = preprocessBam(bam, **preprocess_args)
+    rep = rcpp_mbias_report(bam, max_offset, as_device=as_device)
+    if report_context != "CX":
+        rep = _mbias_select(rep, _context_codes(report_context))
+    return _deliver(rep, report_file, gzip)
+
+
+def suggestTrim(report, context="CG", max_delta=0.05, min_calls=100, run=3):
+    """(trim5, trim3) for preprocessBam(trim=) from an M-bias report (generateMbiasReport): per end, the number of leading
+    offsets to cut so that the next `run` offsets all conform to the plateau.  Per end the two strands of `context` are
+    pooled; with D0 = max_offset // 2 the plateau is sum_{d >= D0} meth / sum_{d >= D0} (meth + unmeth) (ValueError when no
+    call lies there); offset d conforms when it has fewer than min_calls calls or |beta_d - plateau| <= max_delta; the trim
+    is the smallest t in [0, D0] such that every d in [t, min(t + run, D0)) conforms.  trim5 comes from the "start" table,
+    trim3 from the "end" table.  Which physical ends these are: a paired-end template starts with one mate's 5' end and
+    ends with the other mate's 5' end, so both trims cut 5' ends of reads; for single-end rows "start" is the read's 5' end
+    on strand '+' and its 3' end on strand '-' (the template is stored in reference direction)."""
+    context = _match_arg(context, _CTX_CHOICES, "context")
+    run = _whole_number(run, "run", 1)
+    cols = {k: (report[k].cpu().numpy() if hasattr(report[k], "cpu") else np.asarray(report[k])) for k in ("end", "context", "offset", "meth", "unmeth")}
+    max_offset = int(cols["offset"].max()) + 1 if cols["offset"].size else 0
+    d0 = max_offset // 2
+    in_ctx = np.isin(cols["context"], _context_codes(context))
+    trims = []
+    for end in (1, 2):
+        keep = in_ctx & (cols["end"] == end)
+        meth = np.bincount(cols["offset"][keep], weights=cols["meth"][keep], minlength=max_offset).astype(np.int64)
+        calls = meth + np.bincount(cols["offset"][keep], weights=cols["unmeth"][keep], minlength=max_offset).astype(np.int64)
+        if calls[d0:].sum() == 0:
+            raise ValueError("suggestTrim: the %s table has no %s call at offsets >= %d to take the plateau from"
+                             % (MBIAS_END_LEVELS[end - 1], context, d0))
+        plateau = np.float64(meth[d0:].sum()) / np.float64(calls[d0:].sum())
+        with np.errstate(invalid="ignore", divide="ignore"):
+            conforms = (calls < min_calls) | (np.abs(meth.astype(np.float64) / calls.astype(np.float64) - plateau) <= max_delta)
+        trims.append(next(t for t in range(d0 + 1) if conforms[t:min(t + run, d0)].all()))
+    return tuple(trims)
 
 
 def _cytosine_comparison(bam_a, bam_b, threshold_reads, threshold_context, min_context_sites, min_context_beta, max_outofcontext_beta,

@@ -634,6 +634,36 @@ int epi_batch_region_report_dev(epi_batch *b, const int32_t *d_chr, const int32_
                                 int32_t *const d_icols[15], double *const d_dcols[6], void *stream);
 int epi_region_counter_bytes(int64_t nregions, int32_t max_sites, int64_t *bytes_out);
 
+/* M-bias report: methylation by offset from either end of the template, per strand and context -- the table a user reads
+ * preprocessBam's `trim` off -- and the totals per strand and context over every byte, whose non-CpG part is the usual
+ * estimate of the bisulfite conversion.  The reference has no such report.
+ *  Definition (all integers).  Row x has strand s = strand[x] in {1, 2}, length L = len[x] and bytes b_0 .. b_{L-1} with
+ *            codes c_i = b_i & 15.  A code has a class when it is one of
+ *              7 (CG, methylated), 15 (CG, unmethylated), 6 (CHG, methylated), 14 (CHG, unmethylated), 2 (CHH, methylated),
+ *              10 (CHH, unmethylated);
+ *            every other code (5, 13, the filler 11, '.' 12 and the unused ones) has no class and counts nowhere.  For every
+ *            byte i that has a class:
+ *              totals[s][ctx][state] += 1                                (once per byte, whatever max_offset is)
+ *              if i < max_offset:         start[s][ctx][i][state] += 1
+ *              if L - 1 - i < max_offset: end[s][ctx][L - 1 - i][state] += 1
+ *            A byte of a row shorter than 2 max_offset may count in both tables.  Offsets are template (reference-spaced)
+ *            coordinates, filler included -- the coordinates trim cuts in: trim5 = t removes exactly the offsets < t of the
+ *            start table, trim3 likewise of the end table.  There is no read rule, no thresholding and no majority rule:
+ *            every row counts, and the rows need not be sorted.
+ *  Outputs   1 <= max_offset <= 1024.  d_counts: 2 * 2 * 3 * max_offset * 2 device int64, indexed
+ *            ((((e * 2 + (s - 1)) * 3 + k) * max_offset + d) * 2 + state), e = 0 for start and 1 for end, k = 0, 1, 2 for the
+ *            context codes 2 (CHH), 6 (CHG), 7 (CG), d the offset, state = 0 for methylated and 1 for unmethylated.  d_totals:
+ *            12 device int64, indexed (((s - 1) * 3 + k) * 2 + state).
+ * A NULL batch or output, or max_offset out of range: EPI_ERR_ARG with a message that names the argument, before any work;
+ * nothing is written.  A strand outside {1, 2} on a row with bytes, or bad offsets: EPI_ERR_ARG as the cytosine report raises
+ * them, nothing written.  An empty batch: both arrays are zeroed, EPI_OK.  The call is stateless with respect to the batch: it
+ * writes the caller's arrays, keeps nothing and disturbs no other report's state (tile index, kept cell lists, site table,
+ * allele pairs); its scratch -- per workgroup (at most 1024) 24 max_offset u32 cells and twelve u64 totals, 14 MiB at
+ * max_offset = 150 and 96 MiB at 1024 -- goes with it on every return path (epi_device_allocations reads the same before and
+ * after).  Synchronises `stream` once, at its end.  Sums of integers: the result is the same from run to run.  Single GPU only:
+ * the counters are additive over row shards, so the sharded form is a sum; it is not built.  (csrc/mbias.hip has the data path.) */
+int epi_batch_mbias_report_dev(epi_batch *b, int32_t max_offset, int64_t *d_counts, int64_t *d_totals, void *stream);
+
 /* Allele-specific methylation report: does methylation differ between the two alleles of a heterozygous SNV?  Per (SNV,
  * cytosine) the calls of the reads that carry the reference allele against those of the reads that carry the alternative
  * one, with a Fisher exact test, and the same pooled per SNV (what CGmapTools asm, MethPipe allelicmeth and DAMEfinder's SNP
