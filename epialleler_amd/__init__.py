@@ -12,7 +12,8 @@ from .api import (CONTEXT_TO_BASES, CONTEXT_LEVELS, FDRP_COLUMNS, GROUP_COMPARE_
                   generateMbiasReport, generateMhlReport, preprocessBam, rcpp_mbias_report, suggestTrim,
                   rcpp_cx_compare, rcpp_cx_compare_regions, rcpp_cx_report, rcpp_fdrp_report, rcpp_heterogeneity_compare, rcpp_heterogeneity_report, rcpp_linkage_blocks, rcpp_linkage_report,
                   rcpp_extract_patterns, rcpp_extract_patterns_multi, rcpp_get_xm_beta, rcpp_mhl_report, rcpp_region_report, rcpp_summarise_patterns_multi,
-                  rcpp_threshold_reads, writeReport)
+                  rcpp_threshold_reads, writeReport,
+                  SMOOTH_COLUMNS, generateSmoothedReport, mergeCpgStrands, rcpp_cx_merge_strands, rcpp_cx_smooth, smoothCytosineReport)
 from .bed import (Bed, Ecdf, extractPatterns, extractPatternsBed, generateAmpliconReport, generateBedEcdf,  # noqa: F401
                   generateBedReport, generateCaptureReport, generateRegionReport, readBed, selectPatterns, summarisePatterns)
 from .genome import Genome, callMethylation, preprocessGenome, rcpp_call_methylation_genome, rcpp_read_genome  # noqa: F401

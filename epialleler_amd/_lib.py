@@ -196,6 +196,14 @@ _SIGS = {
     "epi_cx_groups_dev": (C.c_int, [_VP, C.POINTER(_VP), C.POINTER(_I64), _I32, _I32, _I32, _I32, _I32, _I32, C.POINTER(_VP), C.POINTER(_VP),
                                     _I64, _VP, C.POINTER(_I64), C.POINTER(_I64)]),
     "epi_cx_groups_scratch_bytes": (C.c_int, [_I64, C.POINTER(_I64)]),
+    "epi_cx_merge_strands_dev": (C.c_int, [_VP, C.POINTER(_VP), _I64, C.POINTER(_VP), _I64, _VP, C.POINTER(_I64), C.POINTER(_I64),
+                                           C.POINTER(_I64), C.POINTER(_I64)]),
+    "epi_cx_smooth_dev": (C.c_int, [_VP, C.POINTER(_VP), _I64, _I32, _I32, _I32, _I32, C.POINTER(_VP), C.POINTER(_VP), _VP, C.POINTER(_I64),
+                                    C.POINTER(_I64)]),
+    "epi_cx_smooth_scratch_bytes": (C.c_int, [_I64, C.POINTER(_I64)]),
+    "epi_smooth_window": (C.c_int, [_VP, _VP, _VP, _I64, _I64, _I32, _I32, C.POINTER(_F64), C.POINTER(_I32), C.POINTER(_F64)]),
+    "epi_smooth_tile_sites": (C.c_int, []),
+    "epi_smooth_stage_sites": (C.c_int, []),
     "epi_tile_positions": (C.c_int, []),
     "epi_cx_tile_positions": (C.c_int, [_CS]),
     "epi_batch_tile_key_range": (C.c_int, [_VP, _VP, C.POINTER(_I64), C.POINTER(_I64)]),

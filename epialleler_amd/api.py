@@ -679,6 +679,108 @@ def rcpp_cx_compare(rep_a, rep_b, min_coverage=1, as_device=False):
     return _table_to_host(rep, as_device)
 
 
+SMOOTH_COLUMNS = CX_COLUMNS + ("nsites", "halfwidth", "degree", "beta", "smoothed", "weight")
+_SMOOTH_MAX_BANDWIDTH, _SMOOTH_MAX_WINDOW, _SMOOTH_MAX_DEGREE = 2 ** 30, 65536, 2        # EPI_SMOOTH_MAX_*
+
+
+def _smooth_args(bandwidth, min_sites, max_gap, degree):
+    return (_whole_number(bandwidth, "bandwidth", 1, _SMOOTH_MAX_BANDWIDTH), _whole_number(min_sites, "min.sites", 1, _SMOOTH_MAX_WINDOW),
+            _whole_number(max_gap, "max.gap", 0, 2 ** 31 - 1), _whole_number(degree, "degree", 0, _SMOOTH_MAX_DEGREE))
+
+
+def rcpp_cx_merge_strands(rep, as_device=False):
+    """CpG strand merging of a device cytosine report (include/epihip.h, epi_cx_merge_strands_dev): the '-' row of a CpG at
+    pos + 1 is added to the '+' row at pos; a '-' CpG row without a '+' partner moves to (pos - 1, '+') where nothing stands
+    in its way and stays otherwise; every other row is copied.  Rows ascending in (rname, pos, strand).  The Report carries
+    rep's levels and `nmerged`, `nmoved`, `nkept`: the pairs, and the lone '-' CpG rows that moved and that stayed."""
+    torch = _torch()
+    lib = _lib.load()
+    cols = _device_columns(rep, CX_COLUMNS, "rcpp_cx_merge_strands")
+    dev = cols[0].device
+    n = int(cols[0].numel())
+    out, _ = _table_cols(6, 0, n, dev)
+    counts = [C.c_int64(0) for _ in range(4)]
+    _lib.check(lib.epi_cx_merge_strands_dev(_engine(dev.index), _ptr_array(cols), n, _ptr_array(out), n, _stream(dev.index),
+                                            *[C.byref(c) for c in counts]))
+    res = Report(dict(zip(CX_COLUMNS, [c[:counts[0].value] for c in out])), rep.levels["rname"])
+    res.nmerged, res.nmoved, res.nkept = counts[1].value, counts[2].value, counts[3].value
+    return _table_to_host(res, as_device)
+
+
+def rcpp_cx_smooth(rep, bandwidth=1000, min_sites=70, max_gap=10 ** 8, degree=2, as_device=False):
+    """Local-regression smoothing of a device cytosine report (include/epihip.h, epi_cx_smooth_dev, has the definitions):
+    per row a tricube-weighted, coverage-weighted polynomial fit of `degree` over the neighbouring cytosines of the same
+    rname, strand and context -- those closer than max(bandwidth, the distance that takes in min_sites sites), within a
+    cluster of sites whose neighbours are at most max_gap apart.  SMOOTH_COLUMNS: the six columns of rep, nsites,
+    halfwidth, degree (the degree the fit could use; -1: no coverage in the window), beta, smoothed and weight, in rep's
+    row order.  The Report carries rep's levels, `ncluster` and `max_window`."""
+    bandwidth, min_sites, max_gap, degree = _smooth_args(bandwidth, min_sites, max_gap, degree)
+    torch = _torch()
+    lib = _lib.load()
+    cols = _device_columns(rep, CX_COLUMNS, "rcpp_cx_smooth")
+    dev = cols[0].device
+    n = int(cols[0].numel())
+    icols, dcols = _table_cols(9, 3, n, dev)
+    ncluster, max_window = C.c_int64(0), C.c_int64(0)
+    _lib.check(lib.epi_cx_smooth_dev(_engine(dev.index), _ptr_array(cols), n, bandwidth, min_sites, max_gap, degree, _ptr_array(icols),
+                                     _ptr_array(dcols), _stream(dev.index), C.byref(ncluster), C.byref(max_window)))
+    res = Report(dict(zip(SMOOTH_COLUMNS, icols + dcols)), rep.levels["rname"])
+    res.ncluster, res.max_window = ncluster.value, max_window.value
+    return _table_to_host(res, as_device)
+
+
+def _cx_report_on_device(report, what):
+    """(device Report, was it one already) of a cytosine report on the host or on a device: a host one is uploaded."""
+    torch = _torch()
+    missing = [k for k in CX_COLUMNS if k not in report]
+    if missing:
+        raise TypeError("%s: expected a cytosine report with the column '%s'" % (what, missing[0]))
+    if all(isinstance(report[k], torch.Tensor) and report[k].is_cuda for k in CX_COLUMNS):
+        return report, True
+    cols = []
+    for k in CX_COLUMNS:
+        a = report[k].cpu().numpy() if isinstance(report[k], torch.Tensor) else np.asarray(report[k])
+        if a.dtype.kind not in "iu" or a.ndim != 1 or a.shape != np.shape(report[CX_COLUMNS[0]]):
+            raise TypeError("%s: column '%s' does not fit the table (integer columns of one length)" % (what, k))
+        if a.size and (a.min() < -2 ** 31 or a.max() > 2 ** 31 - 1):
+            raise ValueError("%s: column '%s' should hold 32-bit integers" % (what, k))
+        cols.append(np.ascontiguousarray(a, np.int32))
+    _, _, dev = _engine_of(())
+    out = Report({k: torch.from_numpy(a).to(dev) for k, a in zip(CX_COLUMNS, cols)}, report.levels["rname"])
+    out.levels = dict(report.levels)
+    return out, False
+
+
+def mergeCpgStrands(report):
+    """A cytosine report (generateCytosineReport, on the host or with as_device=True) with the two strands of every CpG
+    merged into one row at the '+' strand's position, meth and unmeth summed: Bismark's --merge_CpG, methylKit's
+    destrand=TRUE (rcpp_cx_merge_strands has the rules for a CpG seen on one strand only).  A host report is uploaded and
+    the result comes back to the host; a device report gives a device report.  The Report keeps `levels` and carries
+    `nmerged`, `nmoved` and `nkept`.  The reference has no such function."""
+    rep, on_device = _cx_report_on_device(report, "mergeCpgStrands")
+    out = rcpp_cx_merge_strands(rep, as_device=on_device)
+    out.levels = dict(report.levels)
+    return out
+
+
+def smoothCytosineReport(report, bandwidth=1000, min_sites=70, max_gap=10 ** 8, degree=2):
+    """A cytosine report (on the host or a device, thresholded or not, strands merged or not) with three columns that make
+    low-coverage data comparable -- the raw beta, `smoothed`, a local polynomial regression of methylation over the
+    neighbouring cytosines of the same sequence, strand and context, and its `weight` (the kernel-weighted coverage of the
+    window) -- and the window's `nsites`, `halfwidth` and the `degree` the fit used (the idea of bsseq's BSmooth and of
+    DSS's smoothing, as a weighted least-squares fit on the beta scale): the window of a cytosine holds the sites closer
+    than max(bandwidth, the distance that takes in min_sites sites), and never reaches across a gap of more than max_gap
+    bases; degree 0 is a weighted mean, 1 a local line, 2 a local parabola (lowered where the window cannot support it).
+    A cytosine without coverage gets a smoothed value from its neighbours; a window without any coverage gives NaN.  A
+    host report is uploaded and the result comes back to the host; a device report gives a device report.  The Report keeps
+    `levels` and carries `ncluster` and `max_window`.  The reference has no such function."""
+    args = _smooth_args(bandwidth, min_sites, max_gap, degree)
+    rep, on_device = _cx_report_on_device(report, "smoothCytosineReport")
+    out = rcpp_cx_smooth(rep, *args, as_device=on_device)
+    out.levels = dict(report.levels)
+    return out
+
+
 def _region_args(max_p, min_delta_beta, max_gap, min_sites, p_name="max.p"):
     for value, name in ((max_p, p_name), (min_delta_beta, "min.delta.beta")):
         if isinstance(value, bool) or not 0 <= value <= 1:
@@ -1277,6 +1379,31 @@ def compareCytosineReports(bam_a, bam_b, report_file=None, threshold_reads=True,
     no such report."""
     rep = _cytosine_comparison(bam_a, bam_b, threshold_reads, threshold_context, min_context_sites, min_context_beta,
                                max_outofcontext_beta, report_context, min_coverage, preprocess_args)
+    return _deliver(rep, report_file, gzip, as_device)
+
+
+def generateSmoothedReport(bam, report_file=None, threshold_reads=True, threshold_context=None, min_context_sites=2,
+                           min_context_beta=0.5, max_outofcontext_beta=0.1, report_context=None, merge_strands=True, bandwidth=1000,
+                           min_sites=70, max_gap=10 ** 8, degree=2, gzip=False, verbose=False, as_device=False, **preprocess_args):
+    """The smoothed cytosine report of one sample: the table generateCytosineReport gives with these arguments, on the
+    device, its CpG strands merged (mergeCpgStrands) when merge_strands is set, then smoothed (smoothCytosineReport has the
+    columns and the meaning of bandwidth, min_sites, max_gap and degree).  Every argument is checked before a file is
+    opened.  The Report carries `ncluster`, `max_window` and, when merged, `nmerged`, `nmoved`, `nkept`.  The reference has
+    no such report."""
+    threshold_context = _match_arg(threshold_context, _CTX_CHOICES, "threshold.context")
+    report_context = threshold_context if report_context is None else _match_arg(report_context, _CTX_CHOICES, "report.context")
+    if not isinstance(merge_strands, (bool, np.bool_)):
+        raise ValueError("'merge.strands' should be TRUE or FALSE")
+    args = _smooth_args(bandwidth, min_sites, max_gap, degree)
+    bam = preprocessBam(bam, **preprocess_args)
+    rep = generateCytosineReport(bam, None, threshold_reads, threshold_context, min_context_sites, min_context_beta,
+                                 max_outofcontext_beta, report_context, as_device=True)
+    counts = {}
+    if merge_strands:
+        rep = rcpp_cx_merge_strands(rep, as_device=True)
+        counts = dict(nmerged=rep.nmerged, nmoved=rep.nmoved, nkept=rep.nkept)
+    rep = rcpp_cx_smooth(rep, *args, as_device=True)
+    rep.__dict__.update(counts)
     return _deliver(rep, report_file, gzip, as_device)
 
 

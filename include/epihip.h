@@ -881,6 +881,97 @@ int epi_cx_groups_dev(epi_engine *e, const int32_t *const *d_tabs, const int64_t
                       int64_t *nrow_out);
 int epi_cx_groups_scratch_bytes(int64_t total_rows, int64_t *bytes_out);
 
+/* CpG strand merging of a cytosine report (Bismark --merge_CpG, methylKit destrand = TRUE): the '-' row of a CpG at pos + 1 is
+ * added to the '+' row at pos.  The reference has no such call.  Stateless, like epi_cx_compare_dev: the call reads the six
+ * device columns of a CX table (rname, strand, pos, context, meth, unmeth), writes six device columns of the caller (which must
+ * not overlap the input), holds its scratch (8 bytes per row) for the length of the call (epi_device_allocations reads the
+ * same after it as before, on every return path) and touches no batch.  It synchronises `stream`, once before anything is
+ * written.
+ *  Input     precondition, checked on the device: the rows strictly ascend in (rname, pos, strand), strand is 1 or 2, meth
+ *            and unmeth are not negative.  Otherwise EPI_ERR_ARG, and nothing is written.
+ *  Minus CpG a row with strand 2 whose context code is 7 (CG).  Its partner: the row immediately before it, when that has the
+ *            same rname, pos one less, strand 1 and context code 7.
+ *  Rows      a minus CpG (rname, q, '-') with a partner: ONE output row at the partner's place -- the partner's rname, strand
+ *            1, the partner's pos, context 7, meth and unmeth summed; a sum above 2^31 - 1 is EPI_ERR_ARG, and nothing is
+ *            written.  Without a partner: the row becomes (rname, 1, q - 1) with its own context and counts when q >= 2 and
+ *            the row before it, if any, is strictly below (rname, q - 1, '+') in table order; otherwise it is left exactly as
+ *            it is (something already stands at or above (rname, q - 1, '+'): a non-CG '+' row there, or a '-' row).  Every
+ *            other row is copied unchanged.  The output strictly ascends again: a moved row stays above its predecessor by
+ *            the rule that lets it move, and below its successor, which was above (rname, q, '-').
+ *  Counts    *nrow_out = the output's rows = n - *nmerged_out; *nmerged_out = the pairs; *nmoved_out = the minus CpGs that
+ *            moved; *nkept_out = the minus CpGs left as they are.
+ *  Capacity  the columns hold `cap` rows.  cap < *nrow_out: EPI_ERR_ARG, nothing is written, *nrow_out is the count needed.
+ *            cap >= n always suffices.  n == 0: an empty table.  n >= 2^31: EPI_ERR_ARG. */
+int epi_cx_merge_strands_dev(epi_engine *e, const int32_t *const d_in[6], int64_t n, int32_t *const d_out[6], int64_t cap,
+                             void *stream, int64_t *nrow_out, int64_t *nmerged_out, int64_t *nmoved_out, int64_t *nkept_out);
+
+/* Local-regression smoothing of a cytosine report (the idea of bsseq's BSmooth and DSS's smoothing): a tricube-weighted,
+ * coverage-weighted local polynomial of methylation over neighbouring cytosines, with a bandwidth that widens where
+ * cytosines are sparse.  The reference has no such call.  Stateless, like epi_cx_compare_dev: six device columns of a CX
+ * table in (thresholded or not, merged or not), nine int32 and three double device columns of n rows each out, in the
+ * input's row order (they must not overlap the input); the scratch is held for the length of the call
+ * (epi_device_allocations reads the same after it as before, on every return path), no batch is touched.  It synchronises
+ * `stream`, once before anything is written.
+ *  Input     precondition, checked on the device: the rows strictly ascend in (rname, pos, strand); strand is 1 or 2; the
+ *            context code is 0 to 7; pos, meth and unmeth are not negative.  Otherwise EPI_ERR_ARG, nothing is written.
+ *  Limits    degree 0 to EPI_SMOOTH_MAX_DEGREE, bandwidth 1 to EPI_SMOOTH_MAX_BANDWIDTH, max_gap >= 0, min_sites 1 to
+ *            EPI_SMOOTH_MAX_WINDOW, 0 <= n < 2^31: anything else is EPI_ERR_ARG before any device work.
+ *  Series    the rows of one (rname, strand, context code), in ascending pos.  Every row is smoothed within its own series:
+ *            both strands and several contexts may be interleaved.  A series is cut into clusters wherever two neighbours
+ *            are MORE than max_gap apart.  *ncluster_out = the clusters.
+ *  Window    site i of a cluster of c sites: k = min(min_sites, c); D_i = the smallest distance within which at least k
+ *            sites of the cluster lie, site i included (the k-th smallest |pos_j - pos_i|); H_i = max(bandwidth, D_i).  The
+ *            window's sites are those of the cluster with |pos_j - pos_i| < H_i (a site at exactly H_i has weight 0).
+ *            *max_window_out = the largest number of sites in a window.  Above EPI_SMOOTH_MAX_WINDOW: EPI_ERR_ARG, found
+ *            before any fit runs, nothing is written -- a careless bandwidth does not become an n^2 kernel.
+ *  Fit       all in fp64, every product and sum one correctly rounded operation, in exactly this order (one copy of it,
+ *            csrc/smooth_math.hpp, is compiled into the host function and the kernel without fast-math and without
+ *            contraction).  Per window site j in ascending j, accumulated by the one thread that owns site i:
+ *              d = pos_j - pos_i (integer)   u = (double)d / (double)H_i   a = |u|
+ *              c = 1 - (a*a)*a               t = (c*c)*c                   u2 = u*u
+ *              w = t * (double)(meth_j + unmeth_j)                         v = t * (double)meth_j
+ *              S0 += w   S1 += w*u   S2 += w*u2   S3 += (w*u2)*u   S4 += (w*u2)*u2
+ *              T0 += v   T1 += v*u   T2 += v*u2
+ *            The intercept at u = 0 by an LDL^T solve of the weighted normal equations, a relative pivot test lowering the
+ *            degree (kPivot = 1e-4):
+ *              not (S0 > 0)                                   -> smoothed = NaN, degree_used = -1
+ *              d0 = S0; l10 = S1/d0; d1 = S2 - l10*S1
+ *              degree >= 1 and d1 > kPivot*S2                 -> degree_used >= 1, else 0
+ *              l20 = S2/d0; l21 = (S3 - l20*S1)/d1; d2 = (S4 - l20*S2) - l21*(l21*d1)
+ *              degree == 2 and d2 > kPivot*S4                 -> degree_used = 2
+ *              deg 0: a0 = T0/d0
+ *              deg 1: z1 = T1 - l10*T0;  a1 = z1/d1;  a0 = T0/d0 - l10*a1
+ *              deg 2: z1 as above;  z2 = (T2 - l20*T0) - l21*z1;  a2 = z2/d2;  a1 = z1/d1 - l21*a2
+ *                     a0 = (T0/d0 - l10*a1) - l20*a2
+ *              smoothed = min(1, max(0, a0))
+ *            No launch shape enters a result: the columns compare bit for bit with a sequential evaluation in IEEE double.
+ *            Against exact rational arithmetic with the fit of the same degree_used the largest absolute error of smoothed
+ *            is 1.8e-12 (tests/test_smooth_host.py; the pivot test is what keeps one-sided windows at cluster ends from
+ *            extrapolating through nearly collinear points).
+ *  Columns   nine int32: the six of the input, nsites = the window's sites at any coverage, halfwidth = H_i, degree =
+ *            degree_used.  Three double: beta = meth / (meth + unmeth), one IEEE division, NaN at zero coverage; smoothed;
+ *            weight = S0.  A site with zero coverage still gets a smoothed value from its neighbours.
+ *  Memory    52 bytes per row (the sort's workspace, 24; pos, meth, coverage in series order, H, window bounds and cluster
+ *            starts, 28) and the sort's digit tables; epi_cx_smooth_scratch_bytes gives the figure for n rows, 0 for none,
+ *            or EPI_ERR_ARG outside 0 <= n < 2^31 (it needs no device).
+ * epi_smooth_window is host code and needs no device: the same arithmetic over the window of site i of ONE series (pos
+ * ascending, n >= 1 sites, 0 <= i < n, halfwidth >= 1 given by the caller): the sites with |pos_j - pos_i| < halfwidth in
+ * ascending j; *weight = S0.  epi_smooth_tile_sites and epi_smooth_stage_sites: the consecutive series-ordered sites a
+ * workgroup of the fit kernel owns, and the largest range of sites it stages in LDS (a longer one is read from global
+ * memory, with the same results).
+ * No binomial local likelihood, no standard errors, no sharded form. */
+#define EPI_SMOOTH_MAX_DEGREE 2
+#define EPI_SMOOTH_MAX_BANDWIDTH 1073741824
+#define EPI_SMOOTH_MAX_WINDOW 65536
+int epi_cx_smooth_dev(epi_engine *e, const int32_t *const d_in[6], int64_t n, int32_t bandwidth, int32_t min_sites,
+                      int32_t max_gap, int32_t degree, int32_t *const d_icols[9], double *const d_dcols[3], void *stream,
+                      int64_t *ncluster_out, int64_t *max_window_out);
+int epi_cx_smooth_scratch_bytes(int64_t n, int64_t *bytes_out);
+int epi_smooth_window(const int32_t *pos, const int32_t *meth, const int32_t *unmeth, int64_t n, int64_t i, int32_t halfwidth,
+                      int32_t degree, double *smoothed, int32_t *degree_used, double *weight);
+int epi_smooth_tile_sites(void);
+int epi_smooth_stage_sites(void);
+
 /* rcpp_extract_patterns (src/rcpp_extract_patterns.cpp:26-211; caller .getPatterns, R/internal.R:683-714):
  * methylation patterns of the reads overlapping one target.  Library-owned host table: per pattern strand, start,
  * end, nbase, beta, the FNV-1a hash the R side prints as 16 hex digits ("pattern"), the ordered column positions
