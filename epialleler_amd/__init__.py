@@ -13,7 +13,9 @@ from .api import (CONTEXT_TO_BASES, CONTEXT_LEVELS, FDRP_COLUMNS, GROUP_COMPARE_
                   rcpp_cx_compare, rcpp_cx_compare_regions, rcpp_cx_report, rcpp_fdrp_report, rcpp_heterogeneity_compare, rcpp_heterogeneity_report, rcpp_linkage_blocks, rcpp_linkage_report,
                   rcpp_extract_patterns, rcpp_extract_patterns_multi, rcpp_get_xm_beta, rcpp_mhl_report, rcpp_region_report, rcpp_summarise_patterns_multi,
                   rcpp_threshold_reads, writeReport,
-                  SMOOTH_COLUMNS, generateSmoothedReport, mergeCpgStrands, rcpp_cx_merge_strands, rcpp_cx_smooth, smoothCytosineReport)
+                  SMOOTH_COLUMNS, generateSmoothedReport, mergeCpgStrands, rcpp_cx_merge_strands, rcpp_cx_smooth, smoothCytosineReport,
+                  EPI_SEGMENT_MAX_COVERAGE, EPI_SEGMENT_MAX_SITES, EPI_SEGMENT_MAX_STATES, EPI_SEGMENT_MIN_STATES, SEGMENT_COLUMNS, SEGMENT_SITE_COLUMNS,
+                  generateSegmentReport, rcpp_cx_segment, segmentCytosineReport)
 from .bed import (Bed, Ecdf, extractPatterns, extractPatternsBed, generateAmpliconReport, generateBedEcdf,  # noqa: F401
                   generateBedReport, generateCaptureReport, generateRegionReport, readBed, selectPatterns, summarisePatterns)
 from .genome import Genome, callMethylation, preprocessGenome, rcpp_call_methylation_genome, rcpp_read_genome  # noqa: F401

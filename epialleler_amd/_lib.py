@@ -78,6 +78,11 @@ class SimColumn(C.Structure):
                 ("offsets", C.c_void_p), ("len", C.c_int64), ("period", C.c_int64)]
 
 
+class SegmentFit(C.Structure):
+    _fields_ = [("nstates", C.c_int32), ("iterations", C.c_int32), ("converged", C.c_int32), ("unused", C.c_int32), ("score", C.c_int64),
+                ("p", C.c_double * 4), ("trans", C.c_double * 16), ("init", C.c_double * 4)]
+
+
 def build(force=False):
     """Compile every HIP translation unit for gfx950 (hipcc cross-compiles without a GPU)."""
     cmd = ["make", "-C", CSRC, "-j8", "libepihip.so"]
@@ -204,6 +209,14 @@ _SIGS = {
     "epi_smooth_window": (C.c_int, [_VP, _VP, _VP, _I64, _I64, _I32, _I32, C.POINTER(_F64), C.POINTER(_I32), C.POINTER(_F64)]),
     "epi_smooth_tile_sites": (C.c_int, []),
     "epi_smooth_stage_sites": (C.c_int, []),
+    "epi_cx_segment_dev": (C.c_int, [_VP, C.POINTER(_VP), _I64, _I32, _VP, _VP, _VP, _I32, _I32, _I32, _VP, C.POINTER(_VP), C.POINTER(_VP), _I64,
+                                     _VP, C.POINTER(SegmentFit), C.POINTER(_I64), C.POINTER(_I64)]),
+    "epi_cx_segment_scratch_bytes": (C.c_int, [_I64, _I32, C.POINTER(_I64)]),
+    "epi_segment_quantise": (C.c_int, [_I32, _VP, _VP, _VP, _VP]),
+    "epi_segment_reestimate": (C.c_int, [_I32, _VP, _VP, _VP, _VP]),
+    "epi_segment_chain_host": (C.c_int, [_I32, _VP, _VP, _VP, _I64, _I32, _VP, C.POINTER(_I64)]),
+    "epi_segment_block_sites": (C.c_int, []),
+    "epi_segment_thread_sites": (C.c_int, []),
     "epi_tile_positions": (C.c_int, []),
     "epi_cx_tile_positions": (C.c_int, [_CS]),
     "epi_batch_tile_key_range": (C.c_int, [_VP, _VP, C.POINTER(_I64), C.POINTER(_I64)]),

@@ -781,6 +781,112 @@ def smoothCytosineReport(report, bandwidth=1000, min_sites=70, max_gap=10 ** 8, 
     return out
 
 
+SEGMENT_SITE_COLUMNS = CX_COLUMNS + ("state",)
+SEGMENT_COLUMNS = ("rname", "strand", "context", "start", "end", "state", "nsites", "meth", "unmeth", "beta")
+EPI_SEGMENT_MIN_STATES, EPI_SEGMENT_MAX_STATES, EPI_SEGMENT_MAX_COVERAGE, EPI_SEGMENT_MAX_SITES = 2, 4, 32767, 2 ** 26
+_SEGMENT_FLOOR = 2.0 ** -16                                # the smallest probability of a model (include/epihip.h, Model)
+
+
+def _segment_args(max_gap, max_coverage, max_iter):
+    return (_whole_number(max_gap, "max.gap", 0, 2 ** 31 - 1), _whole_number(max_coverage, "max.coverage", 1, EPI_SEGMENT_MAX_COVERAGE),
+            _whole_number(max_iter, "max.iter", 1, 2 ** 31 - 1))
+
+
+def _segment_numbers(values, name, shape):
+    try:
+        a = np.array(values, dtype=np.float64)
+    except (TypeError, ValueError):
+        a = None
+    if a is None or a.shape != shape or np.asarray(values).dtype.kind not in "fiu":
+        raise ValueError("'%s' should hold %s numbers" % (name, " x ".join(str(x) for x in shape)))
+    return np.ascontiguousarray(a)
+
+
+def _segment_model(p, trans, init):
+    """(p, trans, init) as contiguous float64 arrays of K, K x K and K entries, checked as epi_cx_segment_dev checks them."""
+    k = len(p) if hasattr(p, "__len__") else 0
+    if not EPI_SEGMENT_MIN_STATES <= k <= EPI_SEGMENT_MAX_STATES:
+        raise ValueError("'p' should hold %d to %d methylation levels, one per state" % (EPI_SEGMENT_MIN_STATES, EPI_SEGMENT_MAX_STATES))
+    p, trans, init = _segment_numbers(p, "p", (k,)), _segment_numbers(trans, "trans", (k, k)), _segment_numbers(init, "init", (k,))
+    for a, name, top in ((p, "p", 1.0 - _SEGMENT_FLOOR), (trans, "trans", 1.0), (init, "init", 1.0)):
+        if not ((a >= _SEGMENT_FLOOR) & (a <= top)).all():
+            raise ValueError("every entry of '%s' should lie between 2^-16 and %s" % (name, "1 - 2^-16" if name == "p" else "1"))
+    for row, name in [(trans[j], "every row of 'trans'") for j in range(k)] + [(init, "'init'")]:
+        if not abs(float(np.add.accumulate(row)[-1]) - 1.0) <= 1e-9:
+            raise ValueError("%s should sum to 1" % name)
+    return p, trans, init
+
+
+def _segment_start(state_beta, stay):
+    """The model segmentCytosineReport starts from: the states' levels, trans[j][j] = stay with the rest of a row shared
+    evenly, a uniform init."""
+    k = len(state_beta) if hasattr(state_beta, "__len__") else 0
+    if not EPI_SEGMENT_MIN_STATES <= k <= EPI_SEGMENT_MAX_STATES:
+        raise ValueError("'state.beta' should hold %d to %d methylation levels, one per state" % (EPI_SEGMENT_MIN_STATES, EPI_SEGMENT_MAX_STATES))
+    p = _segment_numbers(state_beta, "state.beta", (k,))
+    if not ((p >= _SEGMENT_FLOOR) & (p <= 1.0 - _SEGMENT_FLOOR)).all():
+        raise ValueError("every entry of 'state.beta' should lie between 2^-16 and 1 - 2^-16")
+    if isinstance(stay, (bool, np.bool_)) or not isinstance(stay, (int, float, np.integer, np.floating)) or \
+            not (stay >= _SEGMENT_FLOOR and (1.0 - stay) / (k - 1) >= _SEGMENT_FLOOR):
+        raise ValueError("'stay' should be a number from 2^-16 to 1 - %d * 2^-16" % (k - 1))
+    trans = np.full((k, k), (1.0 - float(stay)) / (k - 1), np.float64)
+    trans[np.arange(k), np.arange(k)] = float(stay)
+    return _segment_model(p, trans, np.full(k, 1.0 / k, np.float64))
+
+
+def rcpp_cx_segment(rep, p, trans, init, max_gap=5000, max_coverage=1000, max_iter=10, as_device=False):
+    """Methylation segments of a device cytosine report by a hidden Markov model (include/epihip.h, epi_cx_segment_dev, has
+    the model): K = len(p) states with methylation levels p, transitions trans (K x K) and initial distribution init,
+    decoded by exact Viterbi per chain -- the cytosines of one rname, strand and context whose neighbours are at most
+    max_gap apart -- on counts clipped to max_coverage, and refitted by hard EM for at most max_iter decodes (1: a pure
+    decode).  SEGMENT_SITE_COLUMNS: the six columns of rep and `state`, in rep's row order.  The Report carries rep's
+    levels, `segments` (a Report of SEGMENT_COLUMNS: the maximal runs of one state inside a chain), `fit` (p, trans, init,
+    score, iterations, converged), `nchain` and `nsegment`."""
+    p, trans, init = _segment_model(p, trans, init)
+    max_gap, max_coverage, max_iter = _segment_args(max_gap, max_coverage, max_iter)
+    torch = _torch()
+    lib = _lib.load()
+    cols = _device_columns(rep, CX_COLUMNS, "rcpp_cx_segment")
+    dev = cols[0].device
+    n = int(cols[0].numel())
+    k = int(p.size)
+    state = torch.empty(n, dtype=torch.int32, device=dev)
+    icols, dcols = _table_cols(7, 3, n, dev)
+    fit, nchain, nsegment = _lib.SegmentFit(), C.c_int64(0), C.c_int64(0)
+    _lib.check(lib.epi_cx_segment_dev(_engine(dev.index), _ptr_array(cols), n, k, p.ctypes.data, trans.ctypes.data, init.ctypes.data, max_gap,
+                                      max_coverage, max_iter, C.c_void_p(state.data_ptr()), _ptr_array(icols), _ptr_array(dcols), n,
+                                      _stream(dev.index), C.byref(fit), C.byref(nchain), C.byref(nsegment)))
+    levels = rep.levels["rname"]
+    res = Report(dict(zip(SEGMENT_SITE_COLUMNS, cols + [state])), levels)
+    segs = Report(dict(zip(SEGMENT_COLUMNS, [c[:nsegment.value] for c in icols + dcols])), levels)
+    res.segments = _table_to_host(segs, as_device)
+    res.fit = dict(p=np.array(fit.p[:k]), trans=np.array(fit.trans[:k * k]).reshape(k, k), init=np.array(fit.init[:k]), score=int(fit.score),
+                   iterations=int(fit.iterations), converged=int(fit.converged))
+    res.nchain, res.nsegment = nchain.value, nsegment.value
+    return _table_to_host(res, as_device)
+
+
+def segmentCytosineReport(report, state_beta=(0.1, 0.5, 0.9), stay=0.99, max_gap=5000, max_coverage=1000, max_iter=10):
+    """A cytosine report (on the host or a device, strands merged or not) cut into regions of its own: every cytosine gets
+    the `state` of a hidden Markov model whose states emit methylated calls at the levels `state_beta` (two to four of
+    them: say unmethylated, partially and fully methylated), and the maximal runs of one state become `segments` (rname,
+    strand, context, start, end, state, nsites and the run's meth, unmeth and beta) -- the idea of MethylSeekR's UMR / LMR /
+    PMD and methpipe's hmr / pmd.  The model starts with the probability `stay` of keeping a state from one cytosine to the
+    next (the rest shared evenly) and a uniform start, is decoded exactly (Viterbi) per chain of cytosines of one
+    sequence, strand and context whose neighbours are at most max_gap bases apart, with coverage above max_coverage scaled
+    down to it, and is refitted to its own decode (hard EM) until nothing changes or max_iter decodes have run (1: a pure
+    decode of the starting model).  A host report is uploaded and the result comes back to the host; a device report gives
+    a device report.  The Report keeps `levels` and carries `segments`, `fit`, `nchain` and `nsegment`.  The reference has
+    no such function."""
+    p, trans, init = _segment_start(state_beta, stay)
+    args = _segment_args(max_gap, max_coverage, max_iter)
+    rep, on_device = _cx_report_on_device(report, "segmentCytosineReport")
+    out = rcpp_cx_segment(rep, p, trans, init, *args, as_device=on_device)
+    out.levels = dict(report.levels)
+    out.segments.levels = dict(report.levels)
+    return out
+
+
 def _region_args(max_p, min_delta_beta, max_gap, min_sites, p_name="max.p"):
     for value, name in ((max_p, p_name), (min_delta_beta, "min.delta.beta")):
         if isinstance(value, bool) or not 0 <= value <= 1:
@@ -1405,6 +1511,39 @@ def generateSmoothedReport(bam, report_file=None, threshold_reads=True, threshol
     rep = rcpp_cx_smooth(rep, *args, as_device=True)
     rep.__dict__.update(counts)
     return _deliver(rep, report_file, gzip, as_device)
+
+
+def generateSegmentReport(bam, report_file=None, threshold_reads=True, threshold_context=None, min_context_sites=2,
+                          min_context_beta=0.5, max_outofcontext_beta=0.1, report_context=None, merge_strands=True,
+                          state_beta=(0.1, 0.5, 0.9), stay=0.99, max_gap=5000, max_coverage=1000, max_iter=10, gzip=False, verbose=False,
+                          as_device=False, **preprocess_args):
+    """The methylation segments of one sample: the table generateCytosineReport gives with these arguments, on the device,
+    its CpG strands merged (mergeCpgStrands) when merge_strands is set, then segmented (segmentCytosineReport has the model
+    and the meaning of state_beta, stay, max_gap, max_coverage and max_iter).  The report is the SEGMENT table (rname,
+    strand, context, start, end, state, nsites, meth, unmeth, beta), which generateRegionReport and extractPatternsBed take
+    as regions.  Every argument is checked before a file is opened.  The Report carries `sites` (the per-cytosine table
+    with `state`), `fit`, `nchain`, `nsegment` and, when merged, `nmerged`, `nmoved`, `nkept`.  The reference has no such
+    report."""
+    threshold_context = _match_arg(threshold_context, _CTX_CHOICES, "threshold.context")
+    report_context = threshold_context if report_context is None else _match_arg(report_context, _CTX_CHOICES, "report.context")
+    if not isinstance(merge_strands, (bool, np.bool_)):
+        raise ValueError("'merge.strands' should be TRUE or FALSE")
+    p, trans, init = _segment_start(state_beta, stay)
+    args = _segment_args(max_gap, max_coverage, max_iter)
+    bam = preprocessBam(bam, **preprocess_args)
+    rep = generateCytosineReport(bam, None, threshold_reads, threshold_context, min_context_sites, min_context_beta,
+                                 max_outofcontext_beta, report_context, as_device=True)
+    counts = {}
+    if merge_strands:
+        rep = rcpp_cx_merge_strands(rep, as_device=True)
+        counts = dict(nmerged=rep.nmerged, nmoved=rep.nmoved, nkept=rep.nkept)
+    sites = rcpp_cx_segment(rep, p, trans, init, *args, as_device=True)
+    seg = sites.segments
+    del sites.segments
+    seg.sites = _table_to_host(sites, as_device)
+    seg.fit, seg.nchain, seg.nsegment = sites.fit, sites.nchain, sites.nsegment
+    seg.__dict__.update(counts)
+    return _deliver(seg, report_file, gzip, as_device)
 
 
 def generateDmrReport(bam_a, bam_b, report_file=None, threshold_reads=True, threshold_context=None, min_context_sites=2,

@@ -11,7 +11,8 @@
 //           (rname, q - 1, '+') -- and whatever the predecessor itself becomes is not above what it was -- and it stays below
 //           its successor, which was above (rname, q, '-') and hence at (rname, q', .) with q' > q or on a later rname; if
 //           the successor moves or is a pair's '+' row it ends at q' - 1 >= q > q - 1 or stays.
-//  Smooth   k_sm_key checks the rows and writes (class byte, row) pairs; one stable radix pass (radix_sort.hip) brings the
+//  Smooth   (the series order and its cuts: cx_series.hpp, shared with segment.hip)
+//           k_sm_key checks the rows and writes (class byte, row) pairs; one stable radix pass (radix_sort.hip) brings the
 //           rows into series order: the rows of one (strand, context) together, (rname, pos) ascending within.  k_sm_flag
 //           gathers pos, meth and coverage into series order and flags the first site of every cluster; the scan over the
 //           flags numbers the clusters, k_sm_cstart lists their first sites.  k_smooth_bounds: a thread per site finds D
@@ -24,7 +25,7 @@
 //           range [jlo(first), jhi(last)): it is staged in LDS once when it holds at most SM_STAGE sites, and read from
 //           global memory otherwise (a thread whose window is not inside the staged range reads global memory too: no
 //           index depends on the monotonicity).  The same values reach the same operations either way.
-#include "cx_table.hpp"
+#include "cx_series.hpp"
 #include "radix_sort.hpp"
 #include "smooth_math.hpp"
 
@@ -140,10 +141,7 @@ static_assert(sizeof(SmScalars) == 64, "SmScalars layout");
 __global__ __launch_bounds__(SM_WG) void k_sm_key(CxTab t, uint64_t *__restrict__ key, uint32_t *__restrict__ val, SmScalars *__restrict__ sc) {
   const uint32_t i = blockIdx.x * (uint32_t)SM_WG + threadIdx.x;
   if (i >= t.n) return;
-  const int32_t strand = t.strand[i], ctx = t.context[i];
-  if (i > 0 && !cx_above(t, i)) atomicOr(&sc->unsorted, 1u);
-  if ((strand != 1 && strand != 2) || ctx < 0 || ctx > 7 || t.pos[i] < 0 || t.meth[i] < 0 || t.unmeth[i] < 0) atomicOr(&sc->bad, 1u);
-  key[i] = (uint64_t)((((uint32_t)(strand - 1) & 1u) << 3) | ((uint32_t)ctx & 7u));
+  key[i] = series_key(t, i, &sc->unsorted, &sc->bad);
   val[i] = i;
 }
 
@@ -160,12 +158,7 @@ __global__ __launch_bounds__(SM_WG) void k_sm_flag(CxTab t, const uint64_t *__re
   const uint32_t row = ord[s];
   const int32_t pos = t.pos[row], m = t.meth[row];
   o.pos[s] = pos; o.meth[s] = m; o.cov[s] = (uint32_t)m + (uint32_t)t.unmeth[row];
-  uint32_t f = 1;
-  if (s > 0) {
-    const uint32_t prev = ord[s - 1];
-    f = key[s] != key[s - 1] || t.rname[prev] != t.rname[row] || (int64_t)pos - (int64_t)t.pos[prev] > (int64_t)max_gap ? 1u : 0u;
-  }
-  flag[s] = f;
+  flag[s] = series_head(t, key, ord, s, row, pos, max_gap);
 }
 
 // cstart[c]: the first site of cluster c; cstart[ncluster] = n
@@ -320,9 +313,8 @@ static int cx_smooth(epi_engine *e, const int32_t *const d_in[6], int64_t n, con
 
   SmScalars h;                                                // the one synchronisation before anything is written
   EPI_TRY(read_scalars(e, s, sc, sizeof(h), &h));
-  if (h.unsorted) return fail(EPI_ERR_ARG, "%s: the rows of the table are not strictly ascending in (rname, pos, strand)", who);
-  if (h.bad)
-    return fail(EPI_ERR_ARG, "%s: a row has a negative pos, a strand other than 1 and 2, a context code outside 0 .. 7 or a negative count", who);
+  if (h.unsorted) return fail(EPI_ERR_ARG, series_unsorted_message(), who);
+  if (h.bad) return fail(EPI_ERR_ARG, series_bad_message(), who);
   *ncluster_out = h.ncluster;
   *max_window_out = h.max_window;
   if (h.max_window > (uint32_t)EPI_SMOOTH_MAX_WINDOW)

@@ -972,6 +972,83 @@ int epi_smooth_window(const int32_t *pos, const int32_t *meth, const int32_t *un
 int epi_smooth_tile_sites(void);
 int epi_smooth_stage_sites(void);
 
+/* Methylation segments of ONE sample's cytosine report: a small hidden Markov model over the series of cytosines, decoded by
+ * exact Viterbi and refitted by hard EM (the idea of MethylSeekR's UMR / LMR / PMD and of methpipe's hmr / pmd).  The
+ * reference has no such call.  Stateless, like epi_cx_smooth_dev: six device columns of a CX table in; one int32 device
+ * column of n states out, in the input's row order, and a segment table of seven int32 and three double device columns (none
+ * may overlap the input); the scratch is held for the length of the call (epi_device_allocations reads the same after it as
+ * before, on every return path), no batch is touched.  It synchronises `stream`: once for the input's verdict, once per refit
+ * iteration, and once before anything is written.  The whole model is stated in integers, so the parallel decode equals the
+ * sequential loop at every tie: no result depends on a launch shape and nothing is compared with a tolerance.
+ *  Input     precondition, checked on the device, the smoother's: the rows strictly ascend in (rname, pos, strand); strand
+ *            is 1 or 2; the context code is 0 to 7; pos, meth and unmeth are not negative.
+ *  Series    the smoother's order and cuts: the rows ordered by class (strand - 1) * 8 + context, stably, so a class ascends
+ *            in (rname, pos).  A CHAIN starts at a class change, at an rname change, or where pos - previous pos > max_gap.
+ *            *nchain_out = the chains.
+ *  Model     K = nstates states, EPI_SEGMENT_MIN_STATES <= K <= EPI_SEGMENT_MAX_STATES.  p[k]: the methylation level of state
+ *            k; trans[j * K + k]: the transition from j to k; init[k]: the initial distribution.  Every entry of all three
+ *            lies in [2^-16, 1] (p additionally <= 1 - 2^-16); every row of trans, and init, sums to 1 within 1e-9 (summed
+ *            in index order).  States need not be ordered or distinct.
+ *  Quantise  q(x) = floor(log(x) * 65536 + 0.5) as an integer; log is libm's in fp64, in a host unit built without fast-math
+ *            and without contraction.  A[k] = q(p[k]), B[k] = q(1 - p[k]), T[j][k] = q(trans[j][k]), I[k] = q(init[k]): all
+ *            <= 0, and >= -726817 for a caller's parameters.
+ *  Counts    cov = meth + unmeth in int64; if cov > max_coverage then m' = (meth * max_coverage) / cov (integer division)
+ *            and u' = max_coverage - m', else m' = meth, u' = unmeth.  1 <= max_coverage <= EPI_SEGMENT_MAX_COVERAGE.
+ *            The emission of site i in state k is e_i(k) = m'_i * A[k] + u'_i * B[k] in int64 (the binomial coefficient is
+ *            the same for every state and is left out).
+ *  Decode    per chain of sites 0 .. L - 1:  delta_0(k) = I[k] + e_0(k);  delta_i(k) = max_j (delta_{i-1}(j) + T[j][k]) +
+ *            e_i(k), psi_i(k) = the SMALLEST j attaining that maximum; the last state is the SMALLEST k attaining max
+ *            delta_{L-1}; state_{i-1} = psi_i(state_i).  The chain's score is max delta_{L-1}; score = the sum of the chains'
+ *            scores.
+ *  Bound     n <= EPI_SEGMENT_MAX_SITES = 2^26.  A site adds at least -(32767 * 726817 + 2^21) > -2^35 to a score (a
+ *            refitted transition or start is >= q(1 / (2^26 + 4)) = -1181078 > -2^21), so every partial score lies in
+ *            (-2^62, 0]: nothing can overflow.
+ *  Refit     hard EM, max_iter >= 1 decodes.  For it = 1 .. max_iter: decode; if it == max_iter stop.  Count over all chains
+ *            in int64: M[k], U[k] = the sums of m', u' over the sites in state k; N[j][k] = adjacent in-chain pairs going
+ *            from j to k; S[k] = chains that start in state k.  Re-estimate on the host in fp64, one IEEE division each:
+ *            p[k] = (M + 1) / (M + U + 2), clamped to [2^-16, 1 - 2^-16], kept when M + U = 0; trans[j][k] = (N[j][k] + 1) /
+ *            (sum_k N[j][k] + K), the row kept when its sum is 0; init[k] = (S[k] + 1) / (sum S + K).  Quantise; if all four
+ *            tables equal the previous iteration's, converged = 1 and stop.  The parameters reported are those of the last
+ *            decode; iterations = the decodes.  max_iter = 1 is a pure decode with the caller's parameters.
+ *  Outputs   d_state[row] = the row's state.  The segment table: the maximal runs of one state inside a chain, in series
+ *            order; int32 rname, strand, context, start, end (the first and last site's pos), state, nsites; double meth,
+ *            unmeth (the run's RAW counts, summed in int64 and converted: exact, they are below 2^53) and beta = meth /
+ *            (meth + unmeth), NaN at 0 / 0.  *nsegment_out = its rows; *fit_out = the fit.
+ *  Errors    EPI_ERR_ARG for anything outside the above (n > 2^26 is refused before any pointer is read).  On any error
+ *            nothing is written, neither columns nor outputs -- but when the segment table needs more than seg_cap rows,
+ *            *nsegment_out is set to the count needed (the message names "rows to write, room for").  seg_cap >= n always
+ *            suffices.  n == 0: EPI_OK, iterations = 0, score = 0, the caller's parameters in *fit_out, no column touched.
+ *  Memory    about 30 bytes per row (the sort's workspace, 24; a word, an f byte and a state per site) plus 8 K^2 + 8 K + 10
+ *            bytes per epi_segment_block_sites() rows; epi_cx_segment_scratch_bytes gives the figure, 0 for no rows, or
+ *            EPI_ERR_ARG outside 0 <= n <= 2^26 or for a bad nstates (it needs no device).
+ * Host functions that need no device (csrc/segment_host.cpp, on the arithmetic the kernels share, csrc/segment_math.hpp):
+ * epi_segment_quantise: the argument checks of Model, then tables_out = A[K], B[K], T[K * K] (row-major), I[K].
+ * epi_segment_reestimate: the re-estimate of Refit, in place, from counts = M[K], U[K], N[K * K], S[K] (each 0 to 2^42).
+ * epi_segment_chain_host: the plain loop of Decode over ONE chain of 1 <= n <= 2^26 sites from such tables (A and B in
+ * [-726817, 0], T and I in [-2^21, 0]): n states and the chain's score.
+ * epi_segment_block_sites, epi_segment_thread_sites: the series-ordered sites one workgroup scans and one thread walks.
+ * No posterior probabilities (forward-backward), no distance-dependent transitions, no beta-binomial emissions, no sharded form. */
+#define EPI_SEGMENT_MIN_STATES 2
+#define EPI_SEGMENT_MAX_STATES 4
+#define EPI_SEGMENT_MAX_COVERAGE 32767
+#define EPI_SEGMENT_MAX_SITES 67108864
+typedef struct {
+  int32_t nstates, iterations, converged, unused;
+  int64_t score;
+  double p[4], trans[16], init[4];          /* trans: nstates x nstates, row-major, packed */
+} epi_segment_fit;
+int epi_cx_segment_dev(epi_engine *e, const int32_t *const d_in[6], int64_t n, int32_t nstates, const double *p,
+                       const double *trans, const double *init, int32_t max_gap, int32_t max_coverage, int32_t max_iter,
+                       int32_t *d_state, int32_t *const d_seg_i[7], double *const d_seg_d[3], int64_t seg_cap, void *stream,
+                       epi_segment_fit *fit_out, int64_t *nchain_out, int64_t *nsegment_out);
+int epi_cx_segment_scratch_bytes(int64_t n, int32_t nstates, int64_t *bytes_out);
+int epi_segment_quantise(int32_t nstates, const double *p, const double *trans, const double *init, int32_t *tables_out);
+int epi_segment_reestimate(int32_t nstates, const int64_t *counts, double *p, double *trans, double *init);
+int epi_segment_chain_host(int32_t nstates, const int32_t *tables, const int32_t *meth, const int32_t *unmeth, int64_t n,
+                           int32_t max_coverage, int32_t *state_out, int64_t *score_out);
+int epi_segment_block_sites(void);
+int epi_segment_thread_sites(void);
+
 /* rcpp_extract_patterns (src/rcpp_extract_patterns.cpp:26-211; caller .getPatterns, R/internal.R:683-714):
  * methylation patterns of the reads overlapping one target.  Library-owned host table: per pattern strand, start,
  * end, nbase, beta, the FNV-1a hash the R side prints as 16 hex digits ("pattern"), the ordered column positions

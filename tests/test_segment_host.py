@@ -1,0 +1,402 @@
+"""segmentCytosineReport / generateSegmentReport / rcpp_cx_segment on the host side: the exported symbols, the limits, the
+Makefile lines, the functions' signatures, argument checks before any I/O, the library's checks that need no device, the loud
+failure without one (the decode runs on the GPU; there is no CPU path), epi_cx_segment_scratch_bytes, and the three host
+functions -- epi_segment_quantise, epi_segment_reestimate, epi_segment_chain_host -- against the restatement
+(tests/segment_np.py) on seeded inputs.  Everything is compared exactly, the doubles of a re-estimate bit for bit."""
+import ctypes as C
+import inspect
+import os
+import re
+
+import numpy as np
+import pytest
+
+import helpers as H
+import segment_np as G
+import smooth_np as S
+import epialleler_amd as ea
+from epialleler_amd import _lib
+
+NEW_SYMBOLS = ("epi_cx_segment_dev", "epi_cx_segment_scratch_bytes", "epi_segment_quantise", "epi_segment_reestimate", "epi_segment_chain_host",
+               "epi_segment_block_sites", "epi_segment_thread_sites")
+EMPTY = inspect.Parameter.empty
+CALL_ARGS = [("max_gap", 5000), ("max_coverage", 1000), ("max_iter", 10)]
+SEGMENT_ARGS = [("state_beta", (0.1, 0.5, 0.9)), ("stay", 0.99)] + CALL_ARGS
+
+
+def _has_gpu():
+    try:
+        import torch
+        return torch.cuda.is_available()
+    except Exception:
+        return False
+
+
+def _dbl(x):
+    return np.ascontiguousarray(np.asarray(x, np.float64).reshape(-1))
+
+
+def test_symbols_declared_exported_and_listed():
+    _lib.build()
+    with open(os.path.join(H.GOLDEN, "..", "..", "include", "epihip.h")) as f:
+        text = f.read()
+    hdr = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    for name in NEW_SYMBOLS:
+        assert name in _lib.EXPORTED_SYMBOLS
+        assert hasattr(_lib.load(), name)
+        assert re.search(r"\bint %s\(" % name, hdr)
+    assert re.search(r"\}\s*epi_segment_fit;", hdr)
+    for name, value in (("EPI_SEGMENT_MIN_STATES", G.MIN_STATES), ("EPI_SEGMENT_MAX_STATES", G.MAX_STATES),
+                        ("EPI_SEGMENT_MAX_COVERAGE", G.MAX_COVERAGE), ("EPI_SEGMENT_MAX_SITES", G.MAX_SITES)):
+        assert re.search(r"^#define %s\s+%d$" % (name, value), hdr, flags=re.M), name
+        assert getattr(ea, name) == value
+    with open(os.path.join(_lib.CSRC, "Makefile")) as f:
+        mk = f.read()
+    assert re.search(r"^SRCS := .*\bsegment\.hip\b", mk, flags=re.M) and re.search(r"^HOST_SRCS := .*\bsegment_host\.cpp\b", mk, flags=re.M)
+    assert re.search(r"^HOST_HDRS := .*\bsegment_math\.hpp\b", mk, flags=re.M)
+    assert re.search(r"^segment_host\.o: HOST_FPFLAGS := -fno-fast-math -ffp-contract=off$", mk, flags=re.M)
+    assert ea.SEGMENT_SITE_COLUMNS == G.SITE_COLUMNS and ea.SEGMENT_COLUMNS == G.SEGMENT_COLUMNS and ea.api.CX_COLUMNS == G.CX
+    lib = _lib.load()
+    block, thread = lib.epi_segment_block_sites(), lib.epi_segment_thread_sites()
+    assert 1 <= thread <= 64 and block % thread == 0 and 64 <= block // thread <= 1024 and (block // thread) % 64 == 0
+    # the series rules have one wording, which the smoother and the segmentation both include
+    with open(os.path.join(_lib.CSRC, "smooth.hip")) as f:
+        smooth = f.read()
+    with open(os.path.join(_lib.CSRC, "segment.hip")) as f:
+        segment = f.read()
+    for text in (smooth, segment):
+        assert '#include "cx_series.hpp"' in text and "series_key(" in text and "series_head(" in text and "max_gap ?" not in text
+
+
+def test_signatures_and_defaults():
+    p = inspect.signature(ea.segmentCytosineReport).parameters
+    assert [(k, v.default) for k, v in p.items()] == [("report", EMPTY)] + SEGMENT_ARGS
+    p = inspect.signature(ea.rcpp_cx_segment).parameters
+    assert [(k, v.default) for k, v in p.items()] == [("rep", EMPTY), ("p", EMPTY), ("trans", EMPTY), ("init", EMPTY)] + CALL_ARGS + [("as_device", False)]
+    p = inspect.signature(ea.generateSegmentReport).parameters
+    c = inspect.signature(ea.generateCytosineReport).parameters
+    shared = [k for k in c if k not in ("gzip", "verbose", "as_device", "preprocess_args")]
+    assert [(k, v.default) for k, v in p.items() if v.kind is not v.VAR_KEYWORD] == \
+        [(k, c[k].default) for k in shared] + [("merge_strands", True)] + SEGMENT_ARGS + [("gzip", False), ("verbose", False), ("as_device", False)]
+    assert [k for k, v in p.items() if v.kind is v.VAR_KEYWORD] == ["preprocess_args"]
+    assert all("levels" not in k for fn in (ea.segmentCytosineReport, ea.rcpp_cx_segment, ea.generateSegmentReport)
+               for k in inspect.signature(fn).parameters)
+
+
+BAD_CALL = [dict(max_gap=-1), dict(max_gap=2 ** 31), dict(max_gap=0.5), dict(max_gap=True), dict(max_coverage=0), dict(max_coverage=32768),
+            dict(max_coverage=1.5), dict(max_coverage=False), dict(max_iter=0), dict(max_iter=-3), dict(max_iter=2.5), dict(max_iter=True)]
+BAD_START = [dict(state_beta=(0.5,)), dict(state_beta=(0.1, 0.2, 0.3, 0.4, 0.5)), dict(state_beta=0.5), dict(state_beta=(0.0, 0.5)),
+             dict(state_beta=(0.1, 1.0)), dict(state_beta=(0.1, float("nan"))), dict(state_beta=("a", "b")), dict(state_beta=(True, False)),
+             dict(stay=0.0), dict(stay=1.0), dict(stay=1.5), dict(stay=True), dict(stay="0.9"), dict(stay=None), dict(stay=float("nan"))]
+BAD_REPORT = [dict(threshold_context="CpG"), dict(report_context="cg"), dict(merge_strands=1), dict(merge_strands=None)]
+MESSAGES = {"threshold_context": "'threshold.context' should be one of 'CG', 'CHG', 'CHH', 'CxG', 'CX'",
+            "report_context": "'report.context' should be one of 'CG', 'CHG', 'CHH', 'CxG', 'CX'",
+            "merge_strands": "'merge.strands' should be TRUE or FALSE", "max_gap": "'max.gap' should be an integer from 0 to 2147483647",
+            "max_coverage": "'max.coverage' should be an integer from 1 to 32767", "max_iter": "'max.iter' should be an integer from 1 to 2147483647",
+            "state_beta": "'state.beta'", "stay": "'stay' should be a number from 2^-16 to 1 - "}
+
+
+@pytest.mark.parametrize("kw", BAD_CALL + BAD_START + BAD_REPORT)
+def test_bad_arguments_raise_before_io(kw):
+    with pytest.raises(ValueError) as ei:
+        ea.generateSegmentReport("no-such-file.bam", **kw)         # (opening it would raise "Unable to open BAM file")
+    (name,) = kw
+    assert MESSAGES[name] in str(ei.value) and "no-such-file" not in str(ei.value) and "open" not in str(ei.value)
+
+
+GOOD = ([0.1, 0.9], [[0.9, 0.1], [0.2, 0.8]], [0.5, 0.5])
+BAD_MODEL = [(dict(p=[0.5]), "'p' should hold 2 to 4"), (dict(p=[0.1] * 5), "'p' should hold 2 to 4"), (dict(p=0.5), "'p' should hold 2 to 4"),
+             (dict(p=[0.0, 0.9]), "'p' should lie"), (dict(p=[0.1, 1.0]), "'p' should lie"), (dict(p=[0.1, float("nan")]), "'p' should lie"),
+             (dict(p=[2.0 ** -17, 0.9]), "'p' should lie"), (dict(p=["a", "b"]), "'p' should hold 2 numbers"),
+             (dict(trans=[[0.9, 0.1]]), "'trans' should hold 2 x 2"), (dict(trans=[0.9, 0.1, 0.2, 0.8]), "'trans' should hold 2 x 2"),
+             (dict(trans=[[1.0, 0.0], [0.2, 0.8]]), "'trans' should lie"), (dict(trans=[[0.9, 0.2], [0.2, 0.8]]), "row of 'trans' should sum"),
+             (dict(trans=[[0.9, 0.1], [0.2, 0.8 - 1e-8]]), "row of 'trans' should sum"), (dict(init=[0.5, 0.25, 0.25]), "'init' should hold 2"),
+             (dict(init=[1.0, 0.0]), "'init' should lie"), (dict(init=[0.5, 0.6]), "'init' should sum"), (dict(init=[0.7, 0.7]), "'init' should sum")]
+
+
+@pytest.mark.parametrize("kw", BAD_CALL)
+def test_bad_call_arguments_raise_before_the_device(kw):
+    host = ea.Report(S.MERGE_KAT, ["chr1", "chr2"])
+    (name,) = kw
+    for call in (lambda: ea.segmentCytosineReport(host, **kw), lambda: ea.rcpp_cx_segment(host, *GOOD, **kw)):
+        with pytest.raises(ValueError) as ei:                      # (without a device the next step would raise EpihipError or TypeError)
+            call()
+        assert MESSAGES[name] in str(ei.value)
+
+
+@pytest.mark.parametrize("kw", BAD_START)
+def test_bad_start_arguments_raise_before_the_device(kw):
+    host = ea.Report(S.MERGE_KAT, ["chr1", "chr2"])
+    (name,) = kw
+    with pytest.raises(ValueError) as ei:
+        ea.segmentCytosineReport(host, **kw)
+    assert MESSAGES[name] in str(ei.value)
+
+
+@pytest.mark.parametrize("kw,word", BAD_MODEL)
+def test_bad_models_raise_before_the_device(kw, word):
+    host = ea.Report(S.MERGE_KAT, ["chr1", "chr2"])
+    model = dict(zip(("p", "trans", "init"), GOOD))
+    model.update(kw)
+    with pytest.raises(ValueError) as ei:
+        ea.rcpp_cx_segment(host, model["p"], model["trans"], model["init"])
+    assert word.replace("'p' should lie", "every entry of 'p' should lie").replace("'trans' should lie", "every entry of 'trans' should lie") \
+        .replace("'init' should lie", "every entry of 'init' should lie") in str(ei.value)
+
+
+def test_good_arguments_reach_the_file():
+    for kw in (dict(max_gap=0, max_coverage=1, max_iter=1), dict(max_gap=2 ** 31 - 1, max_coverage=32767, max_iter=2 ** 31 - 1),
+               dict(state_beta=(2.0 ** -16, 1 - 2.0 ** -16), stay=2.0 ** -16), dict(state_beta=[0.2, 0.4, 0.6, 0.8], stay=1 - 3 * 2.0 ** -16),
+               dict(state_beta=np.asarray([0.3, 0.3]), stay=np.float64(0.5)), dict(merge_strands=False, report_context="CX", threshold_reads=False)):
+        with pytest.raises(Exception) as ei:
+            ea.generateSegmentReport("no-such-file.bam", **kw)
+        assert not isinstance(ei.value, ValueError) or "should" not in str(ei.value), kw
+
+
+def test_table_checks_need_no_device():
+    with pytest.raises(TypeError) as ei:
+        ea.segmentCytosineReport(ea.Report(dict(rname=np.zeros(1, np.int32)), ["chr1"]))
+    assert "'strand'" in str(ei.value)
+    bad = dict(S.MERGE_KAT)
+    bad["meth"] = bad["meth"].astype(np.float64)
+    with pytest.raises(TypeError) as ei:
+        ea.segmentCytosineReport(ea.Report(bad, ["chr1", "chr2"]))
+    assert "'meth'" in str(ei.value)
+    with pytest.raises(TypeError):                                 # a host table is no device Report
+        ea.rcpp_cx_segment(ea.Report(S.MERGE_KAT, ["chr1", "chr2"]), *GOOD)
+
+
+def _raw_args(K=2, p=None, trans=None, init=None):
+    m = G.start_model((0.1, 0.5, 0.9, 0.7)[:min(max(K, 2), 4)], 0.9)      # (K = 1, 5: refused by their number alone)
+    return [_dbl(x) for x in (m[0] if p is None else p, m[1] if trans is None else trans, m[2] if init is None else init)]
+
+
+def test_null_and_bad_arguments_of_the_library():
+    lib = _lib.load()
+    fit, nchain, nseg = _lib.SegmentFit(), C.c_int64(-1), C.c_int64(-1)
+    fit.iterations = -5
+    cols = (C.c_void_p * 7)()
+
+    def call(n=1, K=2, model=None, max_gap=5000, max_coverage=1000, max_iter=10, cap=1, outs=(fit, nchain, nseg)):
+        p, trans, init = model if model is not None else _raw_args(K)
+        refs = [C.byref(x) if x is not None else None for x in outs]
+        return lib.epi_cx_segment_dev(None, cols, n, K, p.ctypes.data, trans.ctypes.data, init.ctypes.data, max_gap, max_coverage, max_iter, None, cols,
+                                      cols, cap, None, *refs)
+
+    # the limits come before anything else: no engine is needed to be told, and no output is written
+    for kw, word in ((dict(K=1), b"nstates"), (dict(K=5), b"nstates"), (dict(model=_raw_args(2, p=[0.0, 0.5])), b"p[0]"),
+                     (dict(model=_raw_args(2, p=[0.5, 1.0])), b"p[1]"), (dict(model=_raw_args(2, p=[0.5, float("nan")])), b"p[1]"),
+                     (dict(model=_raw_args(2, trans=[1.0, 0.0, 0.5, 0.5])), b"trans[0][1]"), (dict(model=_raw_args(2, trans=[0.6, 0.5, 0.5, 0.5])), b"row 0"),
+                     (dict(model=_raw_args(2, trans=[0.5, 0.5, 0.5, 0.5 - 1e-8])), b"row 1"), (dict(model=_raw_args(2, init=[1.0, 2.0 ** -17])), b"init[1]"),
+                     (dict(model=_raw_args(2, init=[0.5, 0.6])), b"init does not sum"), (dict(max_gap=-1), b"max_gap"), (dict(max_coverage=0), b"max_coverage"),
+                     (dict(max_coverage=32768), b"max_coverage"), (dict(max_iter=0), b"max_iter"), (dict(n=-1), b"negative"), (dict(cap=-1), b"negative"),
+                     (dict(n=2 ** 26 + 1), b"2^26"), (dict(), b"NULL")):
+        assert call(**kw) == _lib.EPI_ERR_ARG and word in lib.epi_last_error(), (kw, lib.epi_last_error())
+        assert (fit.iterations, nchain.value, nseg.value) == (-5, -1, -1)
+    assert call(model=_raw_args(2, trans=[0.5, 0.5, 0.5, 0.5 - 1e-10])) == _lib.EPI_ERR_ARG and b"NULL" in lib.epi_last_error()   # (the sum passes)
+    for outs in ((None, nchain, nseg), (fit, None, nseg), (fit, nchain, None)):
+        assert call(outs=outs) == _lib.EPI_ERR_ARG and b"NULL" in lib.epi_last_error()
+
+
+def test_scratch_bytes():
+    lib = _lib.load()
+    out = C.c_int64(-1)
+    B = lib.epi_segment_block_sites()
+    r16 = lambda x: (x + 15) // 16 * 16
+    sort_blocks = lambda n: (n + 4095) // 4096
+
+    def want(n, K):
+        if n == 0:
+            return 0
+        nblk = (n + B - 1) // B
+        return (r16(24 * n + sort_blocks(n) * 2048) + r16(4 * n) + 2 * r16(n) + nblk * (8 * K * K + 8 + 8 * K) + 2 * r16(nblk) + sort_blocks(n) * 4 + 256)
+
+    for K in (2, 3, 4):
+        for n in (0, 1, 2, B - 1, B, B + 1, 4097, 2 ** 26):
+            assert lib.epi_cx_segment_scratch_bytes(n, K, C.byref(out)) == _lib.EPI_OK and out.value == want(n, K), (n, K)
+    assert want(2 ** 26, 4) < 31 * 2 ** 26
+    for n, K in ((2 ** 26 + 1, 3), (-1, 3), (10, 1), (10, 5)):
+        assert lib.epi_cx_segment_scratch_bytes(n, K, C.byref(out)) == _lib.EPI_ERR_ARG and out.value == 0
+    assert lib.epi_cx_segment_scratch_bytes(1, 3, None) == _lib.EPI_ERR_ARG
+
+
+def test_fails_loudly_without_gpu():
+    if _has_gpu():
+        pytest.skip("GPU present")
+    host = ea.Report(S.MERGE_KAT, ["chr1", "chr2"])
+    t = H.templates_from_xm(["Z.z.Z.z", "z.Z.z.Z"], [1, 1], [1, 1])
+    bam = ea.ProcessedBam.from_arrays(t["xm"], t["off"], t["rname"], t["strand"], t["start"], None)
+    for call in (lambda: ea.segmentCytosineReport(host), lambda: ea.generateSegmentReport(bam)):
+        with pytest.raises(ea.EpihipError) as ei:
+            call()
+        assert ei.value.code == 5 and "no CPU fallback" in str(ei.value)
+
+
+# ---- the host functions --------------------------------------------------------------------------------------------------
+
+def _quantise(K, p, trans, init):
+    lib = _lib.load()
+    out = np.full(3 * K + K * K, 7, np.int32)
+    p, trans, init = _dbl(p), _dbl(trans), _dbl(init)
+    rc = lib.epi_segment_quantise(K, p.ctypes.data, trans.ctypes.data, init.ctypes.data, out.ctypes.data)
+    return rc, out.tolist()
+
+
+def test_quantise_is_the_restatement():
+    lib = _lib.load()
+    assert G.q(2.0 ** -16) == G.Q_FLOOR and G.q(1.0) == 0 and G.q(0.5) == -45426 and G.q(1 - 2.0 ** -16) == -1
+    n_models = 0
+    for seed in range(120):
+        rng = np.random.default_rng(100 + seed)
+        K = 2 + seed % 3
+        p, trans, init = G.random_model(rng, K, dyadic=seed % 2 == 0)
+        if seed % 5 == 0:                                          # p at both clamps, probabilities at the floor
+            p[0], p[-1] = 2.0 ** -16, 1 - 2.0 ** -16
+            trans[0] = [1 - (K - 1) * 2.0 ** -16] + [2.0 ** -16] * (K - 1)
+        rc, got = _quantise(K, p, trans, init)
+        want = G.tables_flat(G.quantise(p, trans, init))
+        assert rc == _lib.EPI_OK and got == want, seed
+        assert max(got) <= 0 and min(got) >= G.Q_FLOOR
+        n_models += 1
+    assert n_models == 120
+    rc, got = _quantise(2, [2.0 ** -16, 1 - 2.0 ** -16], [[0.5, 0.5], [2.0 ** -16, 1 - 2.0 ** -16]], [0.5, 0.5])
+    assert rc == 0 and got == [G.Q_FLOOR, -1, -1, G.Q_FLOOR, -45426, -45426, G.Q_FLOOR, -1, -45426, -45426]
+    for K, p, trans, init, word in ((1, [0.5], [[1.0]], [1.0], b"nstates"), (5, [0.5] * 5, [[0.2] * 5] * 5, [0.2] * 5, b"nstates"),
+                                    (2, [0.0, 0.5], [[0.5, 0.5]] * 2, [0.5, 0.5], b"p[0]"), (2, [0.5, 1 - 2.0 ** -17], [[0.5, 0.5]] * 2, [0.5, 0.5], b"p[1]"),
+                                    (2, [0.5, 0.5], [[0.5, 0.5], [1.0, 2.0 ** -17]], [0.5, 0.5], b"trans[1][1]"),
+                                    (2, [0.5, 0.5], [[0.5, 0.5], [0.5, 0.5 + 2e-9]], [0.5, 0.5], b"row 1"),
+                                    (2, [0.5, 0.5], [[0.5, 0.5]] * 2, [0.25, 0.5], b"init does not sum"),
+                                    (2, [0.5, 0.5], [[0.5, 0.5]] * 2, [float("inf"), 0.5], b"init[0]")):
+        rc, got = _quantise(K, p, trans, init)
+        assert rc == _lib.EPI_ERR_ARG and word in lib.epi_last_error() and set(got) == {7}, word
+    x = _dbl([0.5, 0.5])
+    assert lib.epi_segment_quantise(2, None, x.ctypes.data, x.ctypes.data, x.ctypes.data) == _lib.EPI_ERR_ARG
+    assert lib.epi_segment_quantise(2, x.ctypes.data, _dbl([0.5] * 4).ctypes.data, x.ctypes.data, None) == _lib.EPI_ERR_ARG
+
+
+def _reestimate(K, counts, p, trans, init):
+    lib = _lib.load()
+    c = np.ascontiguousarray(counts, np.int64)
+    p, trans, init = _dbl(p).copy(), _dbl(trans).copy(), _dbl(init).copy()
+    rc = lib.epi_segment_reestimate(K, c.ctypes.data, p.ctypes.data, trans.ctypes.data, init.ctypes.data)
+    return rc, p, trans, init
+
+
+def test_reestimate_is_the_restatement_bit_for_bit():
+    lib = _lib.load()
+    seen = dict(p_kept=0, row_kept=0, clamp_lo=0, clamp_hi=0)
+    for seed in range(150):
+        rng = np.random.default_rng(300 + seed)
+        K = 2 + seed % 3
+        p, trans, init = G.random_model(rng, K, dyadic=False)
+        scale = int(rng.choice([1, 10, 10 ** 4, 10 ** 9, 2 ** 40]))
+        M, U = [int(x) for x in rng.integers(0, scale + 1, K)], [int(x) for x in rng.integers(0, scale + 1, K)]
+        N = [[int(x) for x in rng.integers(0, scale + 1, K)] for _ in range(K)]
+        S_ = [int(x) for x in rng.integers(0, scale + 1, K)]
+        if seed % 4 == 0:                                          # the zero-count rules
+            M[0] = U[0] = 0
+            N[K - 1] = [0] * K
+        if seed % 6 == 1:                                          # p at both clamps
+            M[0], U[0], M[1], U[1] = 0, 10 ** 9, 10 ** 9, 0
+        if seed % 7 == 2:
+            S_ = [0] * K
+        rc, gp, gt, gi = _reestimate(K, M + U + [x for row in N for x in row] + S_, p, trans, init)
+        wp, wt, wi = G.reestimate(K, M, U, N, S_, p, trans, init)
+        assert rc == _lib.EPI_OK
+        for got, want in ((gp, wp), (gt, wt), (gi, wi)):
+            assert np.array_equal(G.bits(got), G.bits(want)), seed
+        seen["p_kept"] += sum(M[k] + U[k] == 0 and wp[k] == p[k] for k in range(K))
+        seen["row_kept"] += sum(sum(N[j]) == 0 and wt[j] == trans[j] for j in range(K))
+        seen["clamp_lo"] += sum(x == 2.0 ** -16 for x in wp)
+        seen["clamp_hi"] += sum(x == 1 - 2.0 ** -16 for x in wp)
+        assert abs(sum(wi) - 1) < 1e-12 and all(abs(sum(row) - 1) < 1e-12 for row in wt)
+    assert min(seen.values()) >= 20, seen
+    ok = [1] * 10                                                  # K = 2: M[2], U[2], N[4], S[2]
+    assert _reestimate(2, ok, *GOOD)[0] == _lib.EPI_OK
+    for K, counts, word in ((1, ok, b"nstates"), (5, ok, b"nstates"), (2, [1] * 9 + [-1], b"count"), (2, [2 ** 42 + 1] + [1] * 9, b"count")):
+        assert _reestimate(K, counts, *GOOD)[0] == _lib.EPI_ERR_ARG and word in lib.epi_last_error()
+    x = _dbl([0.5] * 4)
+    assert lib.epi_segment_reestimate(2, None, x.ctypes.data, x.ctypes.data, x.ctypes.data) == _lib.EPI_ERR_ARG
+
+
+def _chain_host(K, tables, meth, unmeth, max_coverage):
+    lib = _lib.load()
+    tb, m, u = (np.ascontiguousarray(x, np.int32) for x in (tables, meth, unmeth))
+    state, score = np.full(max(m.size, 1), -9, np.int32), C.c_int64(-1)
+    rc = lib.epi_segment_chain_host(K, tb.ctypes.data, m.ctypes.data, u.ctypes.data, m.size, max_coverage, state.ctypes.data, C.byref(score))
+    return rc, state[:m.size].tolist(), score.value
+
+
+def test_chain_host_is_the_restatement():
+    n_sites, ties = 0, 0
+    for seed in range(200):
+        rng = np.random.default_rng(700 + seed)
+        K = 2 + seed % 3
+        dyadic = seed % 2 == 0
+        tab = G.quantise(*G.random_model(rng, K, dyadic))
+        L = int(rng.choice([1, 2, 3, 7, 40, 300]))
+        depth = int(rng.choice([0, 1, 2, 3])) if dyadic else int(rng.choice([2, 30, 5000, 2 ** 31 - 1]))
+        cov = rng.integers(0, depth + 1, L)
+        meth = (cov * rng.random(L)).astype(np.int64)
+        max_coverage = int(rng.choice([1, 5, 1000, 32767]))
+        clipped = [G.clip(a, b - a, max_coverage) for a, b in zip(meth.tolist(), cov.tolist())]
+        want_states, want_score = G.decode_chain(tab, [c[0] for c in clipped], [c[1] for c in clipped])
+        rc, states, score = _chain_host(K, G.tables_flat(tab), meth, cov - meth, max_coverage)
+        assert rc == _lib.EPI_OK and states == want_states and score == want_score, seed
+        n_sites += L
+        ties += len(set(tab["A"])) < K or (cov == 0).any()
+    assert n_sites > 8000 and ties > 60
+    # all parameters equal: every path ties, every state is 0
+    tab = G.quantise([0.5] * 3, [[0.25, 0.5, 0.25]] * 3, [0.25, 0.5, 0.25])
+    tab["T"], tab["I"] = [[-90852] * 3] * 3, [-90852] * 3
+    rc, states, score = _chain_host(3, G.tables_flat(tab), [1, 0, 2, 5], [0, 0, 2, 1], 1000)
+    assert rc == 0 and states == [0, 0, 0, 0] and score == 4 * -90852 + 11 * -45426
+
+
+def test_chain_host_arguments():
+    lib = _lib.load()
+    tab = G.tables_flat(G.quantise(*GOOD))
+    assert _chain_host(2, tab, [1, 2], [0, 3], 1000)[0] == _lib.EPI_OK
+    for K, tb, m, u, mc, word in ((1, tab, [1], [1], 1000, b"nstates"), (5, tab, [1], [1], 1000, b"nstates"), (2, tab, [1], [1], 0, b"max_coverage"),
+                                  (2, tab, [1], [1], 32768, b"max_coverage"), (2, tab, [], [], 1000, b"sites"), (2, tab, [1, -1], [1, 1], 1000, b"negative"),
+                                  (2, tab, [1, 1], [1, -2 ** 31], 1000, b"negative"), (2, [1] + tab[1:], [1], [1], 1000, b"table entry 0"),
+                                  (2, [G.Q_FLOOR - 1] + tab[1:], [1], [1], 1000, b"table entry 0"), (2, tab[:9] + [-2 ** 21 - 1], [1], [1], 1000, b"table entry 9")):
+        rc, states, score = _chain_host(K, tb, m, u, mc)
+        assert rc == _lib.EPI_ERR_ARG and word in lib.epi_last_error() and score == -1, word
+    x = np.zeros(4, np.int32)
+    s = C.c_int64()
+    assert lib.epi_segment_chain_host(2, None, x.ctypes.data, x.ctypes.data, 1, 5, x.ctypes.data, C.byref(s)) == _lib.EPI_ERR_ARG
+    assert lib.epi_segment_chain_host(2, np.asarray(tab, np.int32).ctypes.data, x.ctypes.data, x.ctypes.data, 1, 5, x.ctypes.data, None) == _lib.EPI_ERR_ARG
+
+
+# ---- the restatement itself ----------------------------------------------------------------------------------------------
+
+def test_restatement_by_hand():
+    # two states at 1/4 and 3/4, sticky: three methylated sites then three unmethylated ones switch once
+    p, trans, init = [0.25, 0.75], [[0.875, 0.125], [0.125, 0.875]], [0.5, 0.5]
+    t = S.cx_table([(1, 1, 10 * i, S.CG, 4 if i <= 3 else 0, 0 if i <= 3 else 4) for i in range(1, 7)])
+    r = G.segment_np(t, p, trans, init, max_iter=1)
+    assert r["state"].tolist() == [1, 1, 1, 0, 0, 0] and r["nchain"] == 1 and r["nsegment"] == 2
+    assert r["segments"]["start"].tolist() == [10, 40] and r["segments"]["end"].tolist() == [30, 60] and r["segments"]["beta"].tolist() == [1.0, 0.0]
+    want = G.q(0.5) + 4 * G.q(0.875) + G.q(0.125) + 24 * G.q(0.75)
+    assert r["fit"]["score"] == want and r["fit"]["iterations"] == 1 and r["fit"]["converged"] == 0
+    # a gap of max_gap does not cut, one above it does; zero coverage everywhere ties to state 0
+    assert G.segment_np(t, p, trans, init, max_gap=10, max_iter=1)["nchain"] == 1
+    cut = G.segment_np(t, p, trans, init, max_gap=9, max_iter=1)
+    assert cut["nchain"] == 6 and cut["nsegment"] == 6 and cut["fit"]["score"] == 6 * G.q(0.5) + 24 * G.q(0.75)
+    dead = S.cx_table([(1, 1, i, S.CG, 0, 0) for i in range(1, 5)])
+    r = G.segment_np(dead, p, trans, init, max_iter=1)
+    assert r["state"].tolist() == [0] * 4 and np.isnan(r["segments"]["beta"]).all() and r["fit"]["score"] == G.q(0.5) + 3 * G.q(0.875)
+    # the clip: 10 of 40 at max_coverage 5 is 1 of 5
+    assert G.clip(10, 30, 5) == (1, 4) and G.clip(2 ** 31 - 1, 2 ** 31 - 1, 1) == (0, 1) and G.clip(3, 2, 5) == (3, 2)
+    assert G.clip(2 ** 31 - 1, 0, 32767) == (32767, 0)
+    empty = G.segment_np(S.cx_table([]), p, trans, init)
+    assert empty["fit"]["iterations"] == 0 and empty["fit"]["score"] == 0 and empty["nsegment"] == 0
+    # the refit converges on a planted pair of levels
+    rng = np.random.default_rng(5)
+    level = np.repeat([0.1, 0.8, 0.1, 0.8], 100)
+    meth = rng.binomial(10, level)
+    planted = S.cx_table([(1, 1, 10 + 3 * i, S.CG, int(m), int(10 - m)) for i, m in enumerate(meth)])
+    r = G.segment_np(planted, [0.3, 0.6], [[0.9, 0.1], [0.1, 0.9]], [0.5, 0.5])
+    assert r["fit"]["converged"] == 1 and 2 <= r["fit"]["iterations"] <= 10 and r["nsegment"] >= 4
+    assert abs(r["fit"]["p"][0] - 0.1) < 0.05 and abs(r["fit"]["p"][1] - 0.8) < 0.05
