@@ -165,24 +165,8 @@ struct AsmArgs {
   AsmScalars *sc;
 };
 
-// inclusive scan of one value per thread over the workgroup: s[t + 1] (s[0] = 0); wsum: a word per wavefront
-__device__ __forceinline__ void asm_block_scan(uint64_t v, uint64_t *s, uint64_t *wsum) {
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint64_t u = __shfl_up(v, d, 64);
-    if (lane >= d) v += u;
-  }
-  if (lane == 63) wsum[wave] = v;
-  __syncthreads();
-  uint64_t add = 0;
-  for (int w = 0; w < wave; w++) add += wsum[w];
-  s[t + 1] = v + add;
-  if (t == 0) s[0] = 0;
-  __syncthreads();
-}
-
 // the last r in [0, ASM_WG) with s[r] <= j (s ascends, s[ASM_WG] > j: entry r holds item j)
-__device__ __forceinline__ int32_t asm_owner(const uint64_t *s, uint64_t j) {
+__device__ __forceinline__ int32_t asm_owner(const unsigned long long *s, uint64_t j) {
   int32_t a = 0, b = ASM_WG;
   while (b - a > 1) { const int32_t m = (a + b) >> 1; if (s[m] <= j) a = m; else b = m; }
   return a;
@@ -194,10 +178,10 @@ __global__ __launch_bounds__(ASM_WG) void k_asm_walk(AsmArgs a) {
   __shared__ int64_t wkey[ASM_CAP];
   __shared__ uint32_t cnt[3 * ASM_CAP];               // [allele or none][window site]
   __shared__ unsigned long long ev[ASM_CAP];
-  __shared__ uint64_t pre[ASM_WG + 1];                // pairs of the rows before row t
-  __shared__ uint64_t upre[ASM_WG + 1];               // units of the batch's pairs before pair t
-  __shared__ uint64_t epre[ASM_WG + 1];               // events of the round's units before unit t
-  __shared__ uint64_t wsum[ASM_WG / 64];
+  __shared__ unsigned long long pre[ASM_WG + 1];              // pairs of the rows before row t
+  __shared__ unsigned long long upre[ASM_WG + 1];              // units of the batch's pairs before pair t
+  __shared__ unsigned long long epre[ASM_WG + 1];              // events of the round's units before unit t
+  __shared__ unsigned long long wsum[ASM_WG / 64];
   __shared__ int64_t r_off[ASM_WG];
   __shared__ int32_t r_lo[ASM_WG], r_start[ASM_WG], r_len[ASM_WG], r_sd[ASM_WG];
   __shared__ int32_t p_row[ASM_WG], p_site[ASM_WG], p_al[ASM_WG];
@@ -253,12 +237,12 @@ __global__ __launch_bounds__(ASM_WG) void k_asm_walk(AsmArgs a) {
     r_off[t] = a.off[x];
     r_start[t] = st; r_len[t] = l; r_sd[t] = sd;
   }
-  asm_block_scan((uint64_t)c_row, pre, wsum);
+  wg_scan_table<SumU64, ASM_WG>((unsigned long long)c_row, pre, wsum);
   const uint64_t P = pre[ASM_WG];
 
   for (uint64_t pb = 0; pb < P; pb += ASM_WG) {          // 256 pairs, one per thread
     const uint64_t j = pb + t;
-    uint64_t nch = 0;
+    unsigned long long nch = 0;
     if (j < P) {
       const int32_t r = asm_owner(pre, j);
       const int32_t site = r_lo[r] + (int32_t)(j - pre[r]);
@@ -284,7 +268,7 @@ __global__ __launch_bounds__(ASM_WG) void k_asm_walk(AsmArgs a) {
       }
       p_row[t] = r; p_site[t] = site; p_al[t] = al; p_ip[t] = ip; p_c0[t] = c0;
     }
-    asm_block_scan(nch, upre, wsum);
+    wg_scan_table<SumU64, ASM_WG>(nch, upre, wsum);
     const uint64_t U = upre[ASM_WG];
 
     for (uint64_t ub = 0; ub < U; ub += ASM_WG) {          // 256 units, one per thread
@@ -329,7 +313,7 @@ __global__ __launch_bounds__(ASM_WG) void k_asm_walk(AsmArgs a) {
           }
         }
       } else {
-        asm_block_scan((uint64_t)ne, epre, wsum);
+        wg_scan_table<SumU64, ASM_WG>((unsigned long long)ne, epre, wsum);
         const uint64_t total = epre[ASM_WG];
         if (total) {                                           // (uniform)
           if (t == 0) s_base = atomicAdd(&a.sc->cursor, (unsigned long long)total);

@@ -32,7 +32,7 @@ __global__ __launch_bounds__(BF_ROWS) void k_base_freqs(const uint8_t *__restric
                                                         int64_t nsite, uint32_t *__restrict__ counts) {
   __shared__ uint32_t cnt[BF_COLS * BF_CAP];        // [column][window site]
   __shared__ int64_t wkey[BF_CAP];
-  __shared__ uint64_t pre[BF_ROWS + 1];             // pairs of the rows before row t
+  __shared__ unsigned long long pre[BF_ROWS + 1], wsum[BF_ROWS / 64];   // pairs of the rows before row t; the scan's word per wave
   __shared__ int64_t r_base[BF_ROWS];               // off[x] - start[x]: the byte of position p is xm[r_base + p]
   __shared__ int32_t r_lo[BF_ROWS], r_col[BF_ROWS];
   __shared__ int64_t red_min[BF_ROWS / 64], red_max[BF_ROWS / 64];
@@ -83,19 +83,7 @@ __global__ __launch_bounds__(BF_ROWS) void k_base_freqs(const uint8_t *__restric
     const int32_t p = pass ? pass[x] : 1;
     r_col[t] = (sd - 1) * 5 + (p != 0 ? 10 : 0);    // R logical: NA (INT_MIN) is TRUE
   }
-  uint64_t v = (uint64_t)c_row;                      // inclusive scan: in the wavefront, then over the four wavefronts
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint64_t u = __shfl_up(v, d, 64);
-    if (lane >= d) v += u;
-  }
-  if (lane == 63) pre[BF_ROWS - 3 + wave] = v;       // (slots that the exclusive prefix overwrites only after the barrier)
-  __syncthreads();
-  uint64_t add = 0;
-  for (int w = 0; w < wave; w++) add += pre[BF_ROWS - 3 + w];
-  __syncthreads();
-  pre[t + 1] = v + add;
-  if (t == 0) pre[0] = 0;
-  __syncthreads();
+  wg_scan_table<SumU64, BF_ROWS>((unsigned long long)c_row, pre, wsum);
   const uint64_t P = pre[BF_ROWS];
 
   // 3. one byte load and one counter per pair

@@ -36,7 +36,7 @@ __device__ __forceinline__ uint32_t wave_cigar_walk(const uint32_t *__restrict__
     if (o < n_cig) { const uint32_t v = cigar[o]; op = v & 15; len = v >> 4; }
     const uint32_t ql = (op == 0 || op == 1 || op == 4 || op == 7 || op == 8) ? len : 0;
     const uint32_t rl = (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) ? len : 0;
-    const uint32_t qe = qcarry + wave_scan_u32(ql), re = rcarry + wave_scan_u32(rl);
+    const uint32_t qe = qcarry + wave_scan_dpp(ql), re = rcarry + wave_scan_dpp(rl);
     s.qe[lane] = qe;
     s.rs[lane] = re - rl;
     s.op[lane] = (uint8_t)op;

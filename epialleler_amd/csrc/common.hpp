@@ -546,26 +546,6 @@ __device__ __forceinline__ bool epi_dev_check(uint32_t *dbg, bool ok, uint32_t c
 #endif
 #endif
 
-// Wave-level scans and reductions as DPP moves (row_shr 1, 2, 4, 8 inside a row of 16 lanes, then row_bcast:15 into
-// rows 1 and 3 and row_bcast:31 into rows 2 and 3): VALU instructions, where __shfl_* is a ds_bpermute through the
-// LDS pipe with ~100 cycles of latency.  Device code only.
-#ifdef __HIPCC__
-// (bound_ctrl = true on the row shifts: a lane without a source reads 0, the same value as `old` = 0 would give it, and the
-//  compiler can then fold move and add into one v_add_u32_dpp instead of v_mov 0 + v_mov_dpp + v_add)
-__device__ __forceinline__ uint32_t wave_scan_u32(uint32_t v) {      // inclusive prefix sum over the 64 lanes
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, true);
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, true);
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, true);
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, true);
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, false);
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, false);
-  return v;
-}
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {       // sum over the 64 lanes (uniform result)
-  return (uint32_t)__builtin_amdgcn_readlane((int)wave_scan_u32(v), 63);
-}
-#endif
-
 // Counter-based hashing (splitmix64's finaliser), shared by the synthetic generator (synth.hip) and simulateBam's random
 // bases (simulate_bam.hip); tests/synth_np.py and epialleler_amd/simulate.py restate it in numpy.
 __host__ __device__ __forceinline__ uint64_t mix64(uint64_t z) {
@@ -586,3 +566,7 @@ inline int check_grid(int64_t blocks, int threads, const char *what) {
 }
 
 }  // namespace epi
+
+#ifdef __HIPCC__
+#include "scan.hpp"   // wave, workgroup and device scans, wave_sum_u32: device code, for every .hip unit
+#endif

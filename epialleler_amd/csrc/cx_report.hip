@@ -653,7 +653,7 @@ __device__ __forceinline__ void cx2_prefix(uint32_t *arr, uint32_t *s_scan, uint
   for (int j = 0; j < PPT; j++) x[j] = arr[tid * PPT + j];
 #pragma unroll
   for (int j = 1; j < PPT; j++) x[j] += x[j - 1];
-  const uint32_t inc = wave_scan_u32(x[PPT - 1]);
+  const uint32_t inc = wave_scan_dpp(x[PPT - 1]);
   if (lane == 63) s_scan[wave] = inc;
   __syncthreads();
   uint32_t before = inc - x[PPT - 1];

@@ -19,7 +19,7 @@
 
 namespace epi {
 
-constexpr int LY_ROWS = 1024;                     // rows per block of the offset scan (256 threads x 4)
+constexpr int LY_WG = 256, LY_ITEMS = 4;          // the offset scan: 1024 rows per workgroup
 
 // what row x adds to the running offset: its bytes and the filler behind it, so that row x + 1 starts congruent to its
 // start position (by induction: off[x] = start[x] (mod A) and off[x + 1] = off[x] + len + ((start[x + 1] - start[x] - len) mod A))
@@ -30,78 +30,16 @@ __device__ __forceinline__ uint32_t ly_item(const int32_t *__restrict__ start, c
   return l + pad;
 }
 
-__device__ __forceinline__ unsigned long long ly_wave_incl(unsigned long long v, int lane) {
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const unsigned long long o = __shfl_up(v, d, 64);
-    if (lane >= d) v += o;
-  }
-  return v;
-}
-
-// exclusive prefix of one value per thread over a 256-thread block; *total = the block's sum
-__device__ __forceinline__ unsigned long long ly_block_excl(unsigned long long v, unsigned long long *total, unsigned long long *s_w /* [5] */) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const unsigned long long inc = ly_wave_incl(v, lane);
-  __syncthreads();                                // (s_w may still be read from a previous round)
-  if (lane == 63) s_w[wave] = inc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned long long acc = 0;
-    for (int w = 0; w < 4; w++) { const unsigned long long t = s_w[w]; s_w[w] = acc; acc += t; }
-    s_w[4] = acc;
-  }
-  __syncthreads();
-  *total = s_w[4];
-  return s_w[wave] + inc - v;
-}
-
-__global__ __launch_bounds__(256) void k_ly_sums(const int32_t *__restrict__ start, const int32_t *__restrict__ len, int64_t n, uint32_t am,
-                                                  unsigned long long *__restrict__ bsum) {
-  __shared__ unsigned long long s_w[5];
-  const int64_t x0 = (int64_t)blockIdx.x * LY_ROWS + (int64_t)threadIdx.x * 4;
-  unsigned long long v = 0;
-#pragma unroll
-  for (int i = 0; i < 4; i++) if (x0 + i < n) v += ly_item(start, len, x0 + i, n, am);
-  unsigned long long total;
-  (void)ly_block_excl(v, &total, s_w);
-  if (threadIdx.x == 0) bsum[blockIdx.x] = total;
-}
-
-// one block: exclusive scan of bsum[0 .. nb) in place, starting at `first`; the end of the data to *d_end
-__global__ __launch_bounds__(256) void k_ly_scan(unsigned long long *__restrict__ bsum, int64_t nb, unsigned long long first,
-                                                  unsigned long long *__restrict__ d_end) {
-  __shared__ unsigned long long s_w[5];
-  unsigned long long carry = first;
-  for (int64_t base = 0; base < nb; base += 256) {
-    const int64_t i = base + threadIdx.x;
-    const unsigned long long v = i < nb ? bsum[i] : 0ull;
-    unsigned long long total;
-    const unsigned long long ex = ly_block_excl(v, &total, s_w);
-    if (i < nb) bsum[i] = carry + ex;
-    carry += total;
-  }
-  if (threadIdx.x == 0) *d_end = carry;
-}
-
-__global__ __launch_bounds__(256) void k_ly_offsets(const int32_t *__restrict__ start, const int32_t *__restrict__ len, int64_t n, uint32_t am,
-                                                     const unsigned long long *__restrict__ bsum, const unsigned long long *__restrict__ d_end,
-                                                     int64_t *__restrict__ off_out) {
-  __shared__ unsigned long long s_w[5];
-  const int64_t x0 = (int64_t)blockIdx.x * LY_ROWS + (int64_t)threadIdx.x * 4;
-  uint32_t it[4];
-  unsigned long long v = 0;
-#pragma unroll
-  for (int i = 0; i < 4; i++) { it[i] = x0 + i < n ? ly_item(start, len, x0 + i, n, am) : 0u; v += it[i]; }
-  unsigned long long total;
-  unsigned long long o = bsum[blockIdx.x] + ly_block_excl(v, &total, s_w);
-#pragma unroll
-  for (int i = 0; i < 4; i++) {
-    if (x0 + i < n) off_out[x0 + i] = (int64_t)o;
-    o += it[i];
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0) off_out[n] = (int64_t)*d_end;
-}
+struct LyItem {                                    // element x of the offset scan
+  const int32_t *start, *len;
+  int64_t n;
+  uint32_t am;
+  __device__ unsigned long long operator()(int64_t x) const { return ly_item(start, len, x, n, am); }
+};
+struct LyStoreOffset {
+  int64_t *off;
+  __device__ void operator()(int64_t x, unsigned long long ex, unsigned long long) const { off[x] = (int64_t)ex; }
+};
 
 struct __attribute__((packed, aligned(1))) LyU4u { uint32_t x, y, z, w; };
 
@@ -164,19 +102,16 @@ int layout_copy_range(const uint8_t *src, int64_t c0, int64_t c1, const int64_t 
 // *head = the filler in front of row 0.  One host synchronisation (the arena is allocated to size).
 int layout_offsets(epi_batch *b, int modulus, hipStream_t s, DevBuf *new_off, unsigned long long *h_end, uint32_t *head) {
   const int64_t n = b->n;
-  const int64_t nb = (n + LY_ROWS - 1) / LY_ROWS;
   const uint32_t am = (uint32_t)modulus - 1u;
   DevBuf tmp;
-  EPI_TRY(tmp.ensure((size_t)(nb + 2) * 8));
   EPI_TRY(new_off->ensure((size_t)(n + 1) * 8));
-  unsigned long long *bsum = tmp.as<unsigned long long>(), *d_end = bsum + nb;
+  int64_t *off = new_off->as<int64_t>();
+  unsigned long long *d_end = reinterpret_cast<unsigned long long *>(off + n);   // the scan's total is off[n]
   int32_t first_start = 0;
   EPI_TRY(read_scalars(b, s, b->start, 4, &first_start));
   *head = (uint32_t)first_start & am;
-  hipLaunchKernelGGL(k_ly_sums, dim3((unsigned)nb), dim3(256), 0, s, b->start, b->len, n, am, bsum);
-  hipLaunchKernelGGL(k_ly_scan, dim3(1), dim3(256), 0, s, bsum, nb, (unsigned long long)*head, d_end);
-  hipLaunchKernelGGL(k_ly_offsets, dim3((unsigned)nb), dim3(256), 0, s, b->start, b->len, n, am, bsum, d_end, new_off->as<int64_t>());
-  if (hipGetLastError() != hipSuccess) return fail(EPI_ERR_HIP, "layout: launch failed");
+  EPI_TRY((device_scan<SumU64, LY_ITEMS, LY_WG>(n, LyItem{b->start, b->len, n, am}, LyStoreOffset{off}, (unsigned long long)*head, d_end,
+                                                tmp, s)));
   return read_scalars(b, s, d_end, 8, h_end);                // (synchronises: tmp may go)
 }
 

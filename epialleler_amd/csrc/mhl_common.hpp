@@ -128,25 +128,6 @@ __device__ __forceinline__ uint32_t grp_or(uint32_t v) {
   else return v;
 }
 
-template <int CTRL, int ROWS>
-__device__ __forceinline__ uint32_t mhl_dpp(uint32_t v) {
-  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROWS, 0xF, ROWS == 0xF);   // lanes without a source get 0
-}
-template <int CTRL, int ROWS>
-__device__ __forceinline__ unsigned long long mhl_dpp(unsigned long long v) {
-  return ((unsigned long long)mhl_dpp<CTRL, ROWS>((uint32_t)(v >> 32)) << 32) | mhl_dpp<CTRL, ROWS>((uint32_t)v);
-}
-template <class ST>
-__device__ __forceinline__ ST mhl_wave_scan(ST v) {
-  v += mhl_dpp<0x111, 0xF>(v);
-  v += mhl_dpp<0x112, 0xF>(v);
-  v += mhl_dpp<0x114, 0xF>(v);
-  v += mhl_dpp<0x118, 0xF>(v);
-  v += mhl_dpp<0x142, 0xA>(v);
-  v += mhl_dpp<0x143, 0xC>(v);
-  return v;
-}
-
 // ---- host helpers defined in mhl_report.hip ---------------------------------------------------------------------------
 size_t mhl_pool_rows(const epi_batch *b);
 int ensure_mhl_pool(epi_batch *b, size_t rows);

@@ -385,7 +385,7 @@ __device__ __forceinline__ void mhlf_scan_array(X *arr, int lane) {
     X *p = arr + (64 * j + lane) * 4;
     X v0 = p[0], v1 = p[1], v2 = p[2], v3 = p[3];
     v1 += v0; v2 += v1; v3 += v2;
-    const X inc = mhl_wave_scan<X>(v3);
+    const X inc = wave_scan_dpp<X>(v3);
     const X base = inc - v3 + carry;
     p[0] = v0 + base; p[1] = v1 + base; p[2] = v2 + base; p[3] = v3 + base;
     if constexpr (sizeof(X) == 8) {
@@ -440,7 +440,7 @@ __device__ __forceinline__ void mhlf_emit(const MhlFArgs &a, int tile, bool fold
       nr += ok;
     }
   }
-  const uint32_t inc = wave_scan_u32(nr);
+  const uint32_t inc = wave_scan_dpp(nr);
   if (lane == 63) s_scan[wave] = inc;
   __syncthreads();
   if (threadIdx.x == 0) {

@@ -222,7 +222,7 @@ __global__ __launch_bounds__(256) void k_mhl_rows(RowsArgs a) {
   const uint32_t nrec = run_count(P) + run_count(Q);
 
   // record slots: exclusive scan over the workgroup, one cursor atomic per workgroup
-  const uint32_t inc = wave_scan_u32(nrec);
+  const uint32_t inc = wave_scan_dpp(nrec);
   if (lane == 63) s_w[wave] = inc;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -600,7 +600,7 @@ __device__ __forceinline__ void mhl_emit(const MhlArgs &a, int tile, const MhlLd
     for (int j = 0; j < PER; j++) x[j] = arr[j];
 #pragma unroll
     for (int j = 1; j < PER; j++) x[j] += x[j - 1];
-    const ST inc = mhl_wave_scan<ST>(x[PER - 1]);
+    const ST inc = wave_scan_dpp<ST>(x[PER - 1]);
     const ST ex = inc - x[PER - 1];
 #pragma unroll
     for (int j = 0; j < PER; j++) arr[j] = x[j] + ex;

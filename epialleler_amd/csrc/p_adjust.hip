@@ -8,16 +8,14 @@
 //  Sort     least significant byte first, per byte that is left: radix_sort.hip's stable LSD sort, in a SortPairs workspace
 //           (radix_sort.hpp) that is one piece of the call's arena.
 //  Terms   k_padj_terms: t_r of the method, in the header's operation order, from the sorted keys; then a device-wide
-//           inclusive scan of doubles under min or max (k_dscan_reduce, k_dscan_carry, k_dscan_apply: reduce-then-scan as
-//           util.hip's three launches; min and max are exact and associative, so no launch shape enters a result), walking
-//           the ranks downwards for the suffix minimum.
+//           inclusive scan of doubles under min or max (scan.hpp's three launches; min and max are exact and associative,
+//           so no launch shape enters a result), walking the ranks downwards for the suffix minimum.
 //  Scatter  k_padj_scatter: q[order[r]] = min(1, t_r), NaN for the ranks of the NaN rows; order[r] to the caller.
 #include "radix_sort.hpp"
 
 namespace epi {
 
 constexpr int PADJ_WG = 256;
-constexpr int PADJ_WAVES = PADJ_WG / 64;
 constexpr int PADJ_KEY_ITEMS = 8;                              // rows per thread of k_padj_keys
 constexpr int PADJ_KEY_TILE = PADJ_WG * PADJ_KEY_ITEMS;
 constexpr int DSCAN_ITEMS = 4;                                 // consecutive terms per thread of the double scan
@@ -111,108 +109,22 @@ __global__ __launch_bounds__(PADJ_WG) void k_padj_terms(const uint64_t *__restri
 }
 
 // ---- inclusive scan of doubles under min or max ------------------------------------------------------------------------------
-// Logical element L of the scan is t[L], or t[m - 1 - L] when `rev` (a suffix scan).  A workgroup owns DSCAN_BLOCK logical
-// elements, a thread DSCAN_ITEMS consecutive ones.
-
-template <bool MAX> __device__ __forceinline__ double dscan_op(double a, double b) { return MAX ? (a > b ? a : b) : (a < b ? a : b); }
-template <bool MAX> __device__ __forceinline__ double dscan_identity() { return MAX ? -__builtin_inf() : __builtin_inf(); }
-
-// inclusive scan of one value per thread across the workgroup; *total = the workgroup's aggregate
-template <bool MAX> __device__ __forceinline__ double dscan_block(double v, double *total, double *s_wave /* [PADJ_WAVES] */) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const double o = __shfl_up(v, d, 64);
-    if (lane >= d) v = dscan_op<MAX>(o, v);
-  }
-  if (lane == 63) s_wave[wave] = v;
-  __syncthreads();
-  double before = dscan_identity<MAX>(), all = dscan_identity<MAX>();
-  for (int w = 0; w < PADJ_WAVES; w++) {
-    const double x = s_wave[w];
-    if (w < wave) before = dscan_op<MAX>(before, x);
-    all = dscan_op<MAX>(all, x);
-  }
-  __syncthreads();
-  *total = all;
-  return dscan_op<MAX>(before, v);
-}
-
-template <bool MAX> __global__ __launch_bounds__(PADJ_WG) void k_dscan_reduce(const double *__restrict__ t, uint32_t m, int rev,
-                                                                              double *__restrict__ agg) {
-  __shared__ double s_wave[PADJ_WAVES];
-  const uint32_t base = blockIdx.x * (uint32_t)DSCAN_BLOCK + threadIdx.x * (uint32_t)DSCAN_ITEMS;
-  double acc = dscan_identity<MAX>();
-#pragma unroll
-  for (int i = 0; i < DSCAN_ITEMS; i++) {
-    const uint32_t L = base + (uint32_t)i;
-    if (L < m) acc = dscan_op<MAX>(acc, t[rev ? m - 1u - L : L]);
-  }
-  double total;
-  (void)dscan_block<MAX>(acc, &total, s_wave);
-  if (threadIdx.x == 0) agg[blockIdx.x] = total;
-}
-
-// one workgroup: agg[k] <- the aggregate of everything in front of workgroup k (the identity for k = 0)
-template <bool MAX> __global__ __launch_bounds__(PADJ_WG) void k_dscan_carry(double *__restrict__ agg, uint32_t nb) {
-  __shared__ double s_wave[PADJ_WAVES], s_last[PADJ_WAVES];
-  double carry = dscan_identity<MAX>();
-  for (uint32_t base = 0; base < nb; base += PADJ_WG) {
-    const uint32_t k = base + threadIdx.x;
-    const double v = k < nb ? agg[k] : dscan_identity<MAX>();
-    double total;
-    const double inc = dscan_block<MAX>(v, &total, s_wave);
-    const double prev = __shfl_up(inc, 1, 64);                                // exclusive = the inclusive value of the thread before
-    if ((threadIdx.x & 63) == 63) s_last[threadIdx.x >> 6] = inc;
-    __syncthreads();
-    double ex = carry;
-    if ((threadIdx.x & 63) != 0) ex = dscan_op<MAX>(carry, prev);
-    else if (threadIdx.x != 0) ex = dscan_op<MAX>(carry, s_last[(threadIdx.x >> 6) - 1]);
-    if (k < nb) agg[k] = ex;
-    carry = dscan_op<MAX>(carry, total);
-    __syncthreads();
-  }
-}
-
-template <bool MAX> __global__ __launch_bounds__(PADJ_WG) void k_dscan_apply(double *__restrict__ t, uint32_t m, int rev,
-                                                                             const double *__restrict__ agg) {
-  __shared__ double s_wave[PADJ_WAVES], s_last[PADJ_WAVES];
-  const uint32_t base = blockIdx.x * (uint32_t)DSCAN_BLOCK + threadIdx.x * (uint32_t)DSCAN_ITEMS;
-  double x[DSCAN_ITEMS];
-  double acc = dscan_identity<MAX>();
-#pragma unroll
-  for (int i = 0; i < DSCAN_ITEMS; i++) {
-    const uint32_t L = base + (uint32_t)i;
-    x[i] = L < m ? t[rev ? m - 1u - L : L] : dscan_identity<MAX>();
-    acc = dscan_op<MAX>(acc, x[i]);
-    x[i] = acc;                                                               // inclusive within the thread
-  }
-  double total;
-  const double inc = dscan_block<MAX>(acc, &total, s_wave);                   // inclusive over the threads' aggregates
-  // what lies in front of this thread: the workgroups before, and the threads before in this workgroup
-  const double prev = __shfl_up(inc, 1, 64);
-  if ((threadIdx.x & 63) == 63) s_last[threadIdx.x >> 6] = inc;
-  __syncthreads();
-  double front = agg[blockIdx.x];
-  if ((threadIdx.x & 63) != 0) front = dscan_op<MAX>(front, prev);
-  else if (threadIdx.x != 0) front = dscan_op<MAX>(front, s_last[(threadIdx.x >> 6) - 1]);
-#pragma unroll
-  for (int i = 0; i < DSCAN_ITEMS; i++) {
-    const uint32_t L = base + (uint32_t)i;
-    if (L < m) t[rev ? m - 1u - L : L] = dscan_op<MAX>(front, x[i]);
-  }
-}
+// In place (scan.hpp: an element is loaded and stored by the same thread).  Element L of the scan is t[L], or t[m - 1 - L] when
+// `rev` (a suffix scan): reversal is the functor's business, not the scan's.  k_padj_terms writes finite terms >= +0.0 (p in
+// [0, 1] after the range check, N and c finite and positive): no NaN and no -0.0, so min and max are exact and order-free.
+struct PadjTermRef {
+  double *t;
+  uint32_t m;
+  bool rev;
+  __device__ double &at(int64_t L) const { return t[rev ? (int64_t)m - 1 - L : L]; }
+  __device__ double operator()(int64_t L) const { return at(L); }
+  __device__ void operator()(int64_t L, double, double inclusive) const { at(L) = inclusive; }
+};
 
 template <bool MAX> static int dscan_inclusive(double *t, uint32_t m, bool rev, DevBuf &tmp, hipStream_t s) {
-  if (m == 0) return EPI_OK;
-  const uint32_t nb = (m + DSCAN_BLOCK - 1) / DSCAN_BLOCK;
-  EPI_TRY(tmp.ensure((size_t)nb * 8));
-  double *agg = tmp.as<double>();
-  hipLaunchKernelGGL(k_dscan_reduce<MAX>, dim3(nb), dim3(PADJ_WG), 0, s, t, m, rev ? 1 : 0, agg);
-  hipLaunchKernelGGL(k_dscan_carry<MAX>, dim3(1), dim3(PADJ_WG), 0, s, agg, nb);
-  hipLaunchKernelGGL(k_dscan_apply<MAX>, dim3(nb), dim3(PADJ_WG), 0, s, t, m, rev ? 1 : 0, agg);
-  EPI_HIP(hipGetLastError());
-  return EPI_OK;
+  using Op = MinMaxF64<MAX>;
+  const PadjTermRef ref{t, m, rev};
+  return device_scan<Op, DSCAN_ITEMS, PADJ_WG>((int64_t)m, ref, ref, Op::identity(), nullptr, tmp, s);
 }
 
 // ---- scatter ---------------------------------------------------------------------------------------------------------------

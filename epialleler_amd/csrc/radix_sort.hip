@@ -71,11 +71,7 @@ __global__ __launch_bounds__(RSORT_WG) void k_rsort_scatter(const uint64_t *__re
     const uint32_t d = threadIdx.x;
     uint32_t c[RSORT_WAVES], total = 0;
     for (int w = 0; w < RSORT_WAVES; w++) { c[w] = s_cnt[w][d]; total += c[w]; }
-    const uint32_t inc = wave_scan_u32(total);
-    if (lane == 63) s_wsum[wave] = inc;
-    __syncthreads();
-    uint32_t start = inc - total;
-    for (uint32_t w = 0; w < wave; w++) start += s_wsum[w];
+    const uint32_t start = wg_scan_excl<SumU32, RSORT_WG>(total, s_wsum);
     s_goff[d] = off[(size_t)d * nblk + blockIdx.x] - start;                   // (mod 2^32) + a key's place in the tile = its place in the output
     uint32_t at = start;
     for (int w = 0; w < RSORT_WAVES; w++) { s_cnt[w][d] = at; at += c[w]; }

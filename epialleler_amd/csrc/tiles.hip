@@ -105,7 +105,7 @@ __device__ __forceinline__ RowTiles row_tiles(int64_t s, int32_t r, int64_t sp, 
 
 // The tile table in two passes over (start, rname) with nothing stored per row in between: pass A (FILL = false)
 // reduces the per-row tile counts of a block of TB_ROWS rows to one number; after a single-block scan of those
-// (k_scan_bsums) pass B (FILL = true) recomputes the counts, scans them inside the block and writes the tiles.
+// (scan_block_sums_inplace) pass B (FILL = true) recomputes the counts, scans them inside the block and writes the tiles.
 // A thread owns TB_ITEMS CONSECUTIVE rows: four 16-byte loads bring their columns, a row's predecessor is the
 // thread's previous row, and the scan in row order is a serial prefix inside the thread plus one wavefront scan of
 // the thread totals (the first version strided the rows over the threads: 32 scalar loads and eight wavefront scans
@@ -132,7 +132,6 @@ __global__ __launch_bounds__(TB_THREADS) void k_tile_pass(const int32_t *__restr
     sc->deep_count = 0;
     sc->fold_cursor = 0;
   }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t x0 = (int64_t)blockIdx.x * TB_ROWS + (int64_t)threadIdx.x * TB_ITEMS;
   int32_t st[TB_ITEMS + 1], rn[TB_ITEMS + 1];              // [0] = the predecessor of the thread's first row
 #pragma unroll
@@ -161,12 +160,8 @@ __global__ __launch_bounds__(TB_THREADS) void k_tile_pass(const int32_t *__restr
     }
     tot += c[i];
   }
-  const uint32_t inc = wave_scan_u32(tot);
-  if (lane == 63) s_tot[wave] = inc;
-  __syncthreads();
-  uint32_t btot = 0, wbase = 0;
-#pragma unroll
-  for (int w = 0; w < TB_THREADS / 64; w++) { const uint32_t t = s_tot[w]; if (w < wave) wbase += t; btot += t; }
+  uint32_t btot;
+  const uint32_t tbase = wg_scan_excl<SumU32, TB_THREADS>(tot, s_tot, &btot);
   if (!FILL) {
     if (threadIdx.x == 0) bsum[blockIdx.x] = btot;
     return;
@@ -178,7 +173,7 @@ __global__ __launch_bounds__(TB_THREADS) void k_tile_pass(const int32_t *__restr
       else if (blockIdx.x == 0) atomicMax(&sc->ntiles, (uint32_t)cap);
     }
   }
-  uint32_t before = bsum[blockIdx.x] + wbase + inc - tot;  // tiles created by rows before the thread's first row
+  uint32_t before = bsum[blockIdx.x] + tbase;             // tiles created by rows before the thread's first row
   const int64_t T = 1LL << sh;
 #pragma unroll
   for (int i = 0; i < TB_ITEMS; i++) {
