@@ -93,6 +93,22 @@ struct DevBuf {
   bool owned = true;
 };
 
+// The scratch of a stateless call as one allocation, released when the call returns: a unit's layout reserves its pieces (which
+// fixes `used`, the figure its *_scratch_bytes entry point states), alloc() takes the bytes, at() hands a piece out.  Pieces lie back
+// to back in the order reserved, nothing padded in between: a layout puts 64-bit members first, and at() refuses a misaligned piece.
+struct ScratchArena {
+  DevBuf mem;
+  size_t used = 0;
+  // `bytes` at the current end; the piece takes up `bytes` rounded up to a multiple of `round` (a power of two)
+  size_t reserve(size_t bytes, size_t round = 1) { const size_t at = used; used += (bytes + round - 1) & ~(round - 1); return at; }
+  int alloc() { return mem.ensure(used); }
+  template <class T> int at(size_t off, T **piece, size_t align = alignof(T)) const {   // align: where the kernels read wider than T
+    if (off % align != 0) return fail(EPI_ERR_STATE, "scratch piece at byte %zu, not a multiple of the %zu its elements need", off, align);
+    *piece = reinterpret_cast<T *>(mem.as<char>() + off);
+    return EPI_OK;
+  }
+};
+
 struct ProfEntry { double ms = 0; int64_t n = 0; };
 
 // ---- state of the reports that count over the per-strand site table -------------
@@ -440,6 +456,7 @@ int stage_send(epi_engine *eng, int k, void *d_dst, size_t bytes);
 // util kernels (util.hip)
 int scan_exclusive_u32(const uint32_t *d_in, uint32_t *d_out, int64_t n, uint32_t *d_total,
                        DevBuf &tmp, hipStream_t s);
+inline size_t scan_tmp_bytes(int64_t n) { return (size_t)((n + 4095) / 4096 * 4); }   // what it takes of tmp: its block sums
 int scan_block_sums_inplace(uint32_t *d_bsum, int64_t nb, uint32_t *d_total, hipStream_t s);
 
 // tile index (tiles.hip)

@@ -163,23 +163,16 @@ __global__ __launch_bounds__(CXC_WG) void k_reg_emit(RegIn t, const uint32_t *__
 
 // ---- host --------------------------------------------------------------------------------------------------------------
 
-struct Scratch { DevBuf flag, off, brow, scal, scan_tmp; };   // (goes when the call returns)
-
-static int cx_compare(epi_engine *e, const int32_t *const d_a[6], int64_t na, const int32_t *const d_b[6], int64_t nb, int32_t min_coverage,
-                      int32_t *const d_icols[8], double *const d_dcols[4], int64_t cap, hipStream_t s, int64_t *ncommon_out,
-                      int64_t *nrow_out) {
+static int cx_compare(epi_engine *e, const CxTab &a, const CxTab &b, int32_t min_coverage, int32_t *const d_icols[8], double *const d_dcols[4],
+                      int64_t cap, hipStream_t s, int64_t *ncommon_out, int64_t *nrow_out) {
   const char *who = "epi_cx_compare_dev";
-  const CxTab a = cx_tab(d_a, na), b = cx_tab(d_b, nb);
-  const int64_t nblk_a = (na + CXC_WG - 1) / CXC_WG, nblk_b = (nb + CXC_WG - 1) / CXC_WG;
+  const int64_t na = a.n, nblk_a = (na + CXC_WG - 1) / CXC_WG, nblk_b = ((int64_t)b.n + CXC_WG - 1) / CXC_WG;
   EPI_TRY(check_grid(nblk_a, CXC_WG, "cytosine comparison site kernels"));
   EPI_TRY(check_grid(nblk_b, CXC_WG, "cytosine comparison site kernels"));
-  Scratch w;
-  EPI_TRY(w.flag.ensure((size_t)na * 4));
-  EPI_TRY(w.off.ensure((size_t)na * 4));
-  EPI_TRY(w.brow.ensure((size_t)na * 4));
-  EPI_TRY(w.scal.ensure(64));
-  uint32_t *scal = w.scal.as<uint32_t>();                     // [0] a unsorted, [1] b unsorted, [2] common rows, [3] reported rows
-  uint32_t *keep = w.flag.as<uint32_t>(), *off = w.off.as<uint32_t>(), *brow = w.brow.as<uint32_t>();
+  CxKeepScratch w;                                            // keep flags, their scan, the matched rows of b
+  EPI_TRY(w.take(na, 3));
+  uint32_t *scal = w.scal;                                    // [0] a unsorted, [1] b unsorted, [2] common rows, [3] reported rows
+  uint32_t *keep = w.flag, *off = keep + na, *brow = off + na;
   EPI_HIP(hipMemsetAsync(scal, 0, 64, s));
   prof_begin("cxcmp_match", s);
   hipLaunchKernelGGL(k_cxc_sorted, dim3((unsigned)nblk_a), dim3(CXC_WG), 0, s, a, &scal[0]);
@@ -195,10 +188,9 @@ static int cx_compare(epi_engine *e, const int32_t *const d_a[6], int64_t na, co
     return fail(EPI_ERR_ARG, "%s: the rows of the %s table are not strictly ascending in (rname, pos, strand)", who, h[0] ? "first" : "second");
   *ncommon_out = h[2];
   *nrow_out = h[3];
-  if ((int64_t)h[3] > cap) return fail(EPI_ERR_ARG, "%s: %lld rows to write, room for %lld", who, (long long)h[3], (long long)cap);
+  EPI_TRY(cx_rows_fit(who, "rows", h[3], cap));
   if (h[3] == 0) return EPI_OK;
-  for (int i = 0; i < 8; i++) if (!d_icols[i]) return fail(EPI_ERR_ARG, "%s: NULL column", who);
-  for (int i = 0; i < 4; i++) if (!d_dcols[i]) return fail(EPI_ERR_ARG, "%s: NULL column", who);
+  EPI_TRY(cx_cols_arg(who, d_icols, 8, d_dcols, 4));
   CxcOut o;
   o.rname = d_icols[0]; o.strand = d_icols[1]; o.pos = d_icols[2]; o.context = d_icols[3];
   o.meth_a = d_icols[4]; o.unmeth_a = d_icols[5]; o.meth_b = d_icols[6]; o.unmeth_b = d_icols[7];
@@ -219,11 +211,9 @@ static int cx_regions(epi_engine *e, const int32_t *const d_icols[8], const doub
   const char *who = "epi_cx_compare_regions_dev";
   const int64_t nblk = (n + CXC_WG - 1) / CXC_WG;
   EPI_TRY(check_grid(nblk, CXC_WG, "cytosine comparison region kernels"));
-  Scratch w;
-  EPI_TRY(w.flag.ensure((size_t)n * 4));
-  EPI_TRY(w.off.ensure((size_t)n * 4));
-  EPI_TRY(w.scal.ensure(64));
-  uint32_t *scal = w.scal.as<uint32_t>(), *flag = w.flag.as<uint32_t>(), *off = w.off.as<uint32_t>();
+  CxKeepScratch w;
+  EPI_TRY(w.take(n, 2));
+  uint32_t *scal = w.scal, *flag = w.flag, *off = flag + n;
   RegIn t;
   t.rname = d_icols[0]; t.pos = d_icols[2];
   t.meth_a = d_icols[4]; t.unmeth_a = d_icols[5]; t.meth_b = d_icols[6]; t.unmeth_b = d_icols[7];
@@ -239,9 +229,9 @@ static int cx_regions(epi_engine *e, const int32_t *const d_icols[8], const doub
   uint32_t h = 0;
   EPI_TRY(read_scalars(e, s, scal, sizeof(h), &h));
   *nregion_out = h;
-  if ((int64_t)h > cap) return fail(EPI_ERR_ARG, "%s: %lld regions to write, room for %lld", who, (long long)h, (long long)cap);
+  EPI_TRY(cx_rows_fit(who, "regions", h, cap));
   if (h == 0) return EPI_OK;
-  for (int i = 0; i < 5; i++) if (!d_ricols[i] || !d_rdcols[i]) return fail(EPI_ERR_ARG, "%s: NULL column", who);
+  EPI_TRY(cx_cols_arg(who, d_ricols, 5, d_rdcols, 5));
   RegOut o;
   o.rname = d_ricols[0]; o.start = d_ricols[1]; o.end = d_ricols[2]; o.nsites = d_ricols[3]; o.direction = d_ricols[4];
   o.beta_a = d_rdcols[0]; o.beta_b = d_rdcols[1]; o.delta_beta = d_rdcols[2]; o.mean_delta_beta = d_rdcols[3]; o.p = d_rdcols[4];
@@ -274,14 +264,13 @@ int epi_cx_compare_dev(epi_engine *e, const int32_t *const d_a[6], int64_t na, c
   const char *who = "epi_cx_compare_dev";
   if (!e || !ncommon_out || !nrow_out) return fail(EPI_ERR_ARG, "%s: NULL argument", who);
   *ncommon_out = 0; *nrow_out = 0;
-  if (na < 0 || nb < 0 || cap < 0) return fail(EPI_ERR_ARG, "%s: negative row count or capacity", who);
-  if ((na > 0 && !d_a) || (nb > 0 && !d_b) || (cap > 0 && (!d_icols || !d_dcols))) return fail(EPI_ERR_ARG, "%s: NULL argument", who);
-  if (na >= (1LL << 31) || nb >= (1LL << 31)) return fail(EPI_ERR_ARG, "%s: %lld and %lld rows", who, (long long)na, (long long)nb);
-  for (int i = 0; i < 6; i++)
-    if ((na > 0 && !d_a[i]) || (nb > 0 && !d_b[i])) return fail(EPI_ERR_ARG, "%s: NULL column", who);
+  CxTab a, b;
+  EPI_TRY(cx_tab_arg(who, d_a, na, kCxMaxRows, &a, cap));
+  EPI_TRY(cx_tab_arg(who, d_b, nb, kCxMaxRows, &b));
+  if (cap > 0 && (!d_icols || !d_dcols)) return fail(EPI_ERR_ARG, "%s: NULL argument", who);
   if (na == 0 || nb == 0) return EPI_OK;
   EPI_HIP(hipSetDevice(e->device));
-  return cx_compare(e, d_a, na, d_b, nb, min_coverage, d_icols, d_dcols, cap, reinterpret_cast<hipStream_t>(stream), ncommon_out, nrow_out);
+  return cx_compare(e, a, b, min_coverage, d_icols, d_dcols, cap, reinterpret_cast<hipStream_t>(stream), ncommon_out, nrow_out);
 }
 
 int epi_cx_compare_regions_dev(epi_engine *e, const int32_t *const d_icols[8], const double *const d_dcols[4], int64_t n, double max_p,
@@ -294,12 +283,10 @@ int epi_cx_compare_regions_dev(epi_engine *e, const int32_t *const d_icols[8], c
   if (!(min_delta_beta >= 0.0 && min_delta_beta <= 1.0)) return fail(EPI_ERR_ARG, "%s: min_delta_beta = %g, from 0 to 1", who, min_delta_beta);
   if (max_gap < 0) return fail(EPI_ERR_ARG, "%s: negative max_gap", who);
   if (min_sites < 1) return fail(EPI_ERR_ARG, "%s: min_sites = %d, regions hold at least one site", who, min_sites);
-  if (n < 0 || cap < 0) return fail(EPI_ERR_ARG, "%s: negative row count or capacity", who);
-  if (n >= (1LL << 31)) return fail(EPI_ERR_ARG, "%s: %lld rows", who, (long long)n);
-  if ((n > 0 && (!d_icols || !d_dcols)) || (cap > 0 && (!d_ricols || !d_rdcols))) return fail(EPI_ERR_ARG, "%s: NULL argument", who);
+  EPI_TRY(cx_rows_arg(who, n, kCxMaxRows, cap));
+  if (cap > 0 && (!d_ricols || !d_rdcols)) return fail(EPI_ERR_ARG, "%s: NULL argument", who);
   if (n == 0) return EPI_OK;
-  for (int i = 0; i < 8; i++) if (!d_icols[i]) return fail(EPI_ERR_ARG, "%s: NULL column", who);
-  for (int i = 0; i < 4; i++) if (!d_dcols[i]) return fail(EPI_ERR_ARG, "%s: NULL column", who);
+  EPI_TRY(cx_cols_arg(who, d_icols, 8, d_dcols, 4));
   EPI_HIP(hipSetDevice(e->device));
   return cx_regions(e, d_icols, d_dcols, n, max_p, min_delta_beta, max_gap, min_sites, d_ricols, d_rdcols, cap,
                     reinterpret_cast<hipStream_t>(stream), nregion_out);

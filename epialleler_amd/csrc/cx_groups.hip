@@ -27,6 +27,7 @@ namespace epi {
 constexpr int CXG_WG = 256;
 constexpr int CXG_MAX_GROUP = 32;                             // samples a side
 constexpr int CXG_MAX_RUN = 2 * CXG_MAX_GROUP;                // entries of a site: one per sample
+constexpr CxRowLimit CXG_MAX_ROWS = {(1LL << 32) - 1, "2^32 - 1"};   // of all samples together: the sort's values are 32-bit
 constexpr uint32_t CXG_KEY_BYTES = 0x7Fu;                     // the key's 56 bits
 constexpr uint32_t CXG_BAD_ROW = 1u, CXG_BAD_POOLED = 2u;     // bits of CxgScalars::bad
 
@@ -209,17 +210,15 @@ __global__ __launch_bounds__(CXG_WG) void k_cxg_emit(CxgSorted t, const uint32_t
 
 // ---- host --------------------------------------------------------------------------------------------------------------
 
-// the call's scratch for n rows: the sort's workspace, the rows' two counts, the scan's block sums (over the rows' flags; the
-// tables' are fewer) and the scalars
-static int64_t cxg_scratch_bytes(int64_t n) {
-  if (n < 0 || n >= (1LL << 32)) return -1;
-  if (n == 0) return 0;
-  return (int64_t)SortPairs::bytes((size_t)n) + 8 * n + (n + 4095) / 4096 * 4 + 64;
-}
+// The call's scratch for n rows, and what epi_cx_groups_scratch_bytes states: the sort's workspace, the rows' two counts, the
+// scalars and the scan's block sums (over the rows' flags; the tables' are fewer)
+struct CxgLayout : ScratchArena {
+  size_t sort, counts, scal, scan;
+  explicit CxgLayout(int64_t n) { sort = reserve(SortPairs::bytes((size_t)n)); counts = reserve((size_t)n * 8); scal = reserve(64); scan = reserve(scan_tmp_bytes(n)); }
+};
 
 struct CxgCall {
-  const int32_t *const *tabs;
-  const int64_t *nrows;
+  const CxTab *tabs;
   int32_t n_a, n_b, min_cov, min_a, min_b, test;
   int32_t *const *icols;
   double *const *dcols;
@@ -230,25 +229,22 @@ static int cx_groups(epi_engine *e, const CxgCall &c, hipStream_t s, int64_t *ns
   const char *who = "epi_cx_groups_dev";
   const int64_t n = c.total, nblk = (n + CXG_WG - 1) / CXG_WG;
   EPI_TRY(check_grid(nblk, CXG_WG, "cytosine group comparison kernels"));
-  DevBuf d_rows, d_scal, scan_tmp;                            // (go when the call returns)
-  EPI_TRY(d_rows.ensure(SortPairs::bytes((size_t)n) + (size_t)n * 8));   // the sort's workspace, then the two counts
-  EPI_TRY(d_scal.ensure(64));
-  EPI_TRY(scan_tmp.ensure((size_t)((n + 4095) / 4096 * 4)));              // (the larger of the two scans: no growth between the kernels)
-  SortPairs sort(d_rows.p, (size_t)n);
-  CxgRows rows;
-  rows.key = sort.keys_in(); rows.val = sort.vals_in();
-  rows.meth = reinterpret_cast<int32_t *>(d_rows.as<char>() + SortPairs::bytes((size_t)n)); rows.unmeth = rows.meth + n;
-  CxgScalars *sc = d_scal.as<CxgScalars>();
+  CxgLayout w(n);                                             // (goes when the call returns)
+  EPI_TRY(w.alloc());
+  uint64_t *sort_mem; CxgRows rows; CxgScalars *sc; uint32_t *scan;
+  EPI_TRY(w.at(w.sort, &sort_mem)); EPI_TRY(w.at(w.counts, &rows.meth)); EPI_TRY(w.at(w.scal, &sc)); EPI_TRY(w.at(w.scan, &scan));
+  SortPairs sort(sort_mem, (size_t)n);
+  DevBuf scan_tmp = DevBuf::view(scan, scan_tmp_bytes(n));
+  rows.key = sort.keys_in(); rows.val = sort.vals_in(); rows.unmeth = rows.meth + n;
   EPI_HIP(hipMemsetAsync(sc, 0, 64, s));
 
   prof_begin("cxg_key", s);
   int64_t base = 0, first_b = 0;
   for (int k = 0; k < c.n_a + c.n_b; k++) {
     if (k == c.n_a) first_b = base;
-    const int64_t nk = c.nrows[k];
+    const int64_t nk = c.tabs[k].n;
     if (nk == 0) continue;
-    hipLaunchKernelGGL(k_cxg_key, dim3((unsigned)((nk + CXG_WG - 1) / CXG_WG)), dim3(CXG_WG), 0, s, cx_tab(c.tabs + 6 * k, nk), (uint32_t)base,
-                       (uint32_t)k, rows, sc);
+    hipLaunchKernelGGL(k_cxg_key, dim3((unsigned)((nk + CXG_WG - 1) / CXG_WG)), dim3(CXG_WG), 0, s, c.tabs[k], (uint32_t)base, (uint32_t)k, rows, sc);
     base += nk;
   }
   prof_end("cxg_key", s);
@@ -282,11 +278,12 @@ static int cx_groups(epi_engine *e, const CxgCall &c, hipStream_t s, int64_t *ns
   *nrow_out = h.nrow;
   if (h.bad & CXG_BAD_POOLED)
     return fail(EPI_ERR_ARG, "%s: a group's pooled meth + unmeth at a reported site exceeds 2^31 - 1, which an int32 column cannot hold", who);
-  if ((int64_t)h.nrow > c.cap) return fail(EPI_ERR_ARG, "%s: %lld rows to write, room for %lld", who, (long long)h.nrow, (long long)c.cap);
+  EPI_TRY(cx_rows_fit(who, "rows", h.nrow, c.cap));
   if (h.nrow == 0) return EPI_OK;
+  EPI_TRY(cx_cols_arg(who, c.icols, 10, c.dcols, 11));
   CxgOut o;
-  for (int i = 0; i < 10; i++) { if (!c.icols || !c.icols[i]) return fail(EPI_ERR_ARG, "%s: NULL column", who); o.icol[i] = c.icols[i]; }
-  for (int i = 0; i < 11; i++) { if (!c.dcols || !c.dcols[i]) return fail(EPI_ERR_ARG, "%s: NULL column", who); o.dcol[i] = c.dcols[i]; }
+  for (int i = 0; i < 10; i++) o.icol[i] = c.icols[i];
+  for (int i = 0; i < 11; i++) o.dcol[i] = c.dcols[i];
   o.nrow = h.nrow;
   prof_begin("cxg_emit", s);
   hipLaunchKernelGGL(k_cxg_emit, dim3((unsigned)nblk), dim3(CXG_WG), 0, s, t, flag, off, o);
@@ -322,9 +319,8 @@ int epi_dist_tail_dev(epi_engine *e, int32_t kind, const double *d_x, const doub
 int epi_cx_groups_scratch_bytes(int64_t total_rows, int64_t *bytes_out) {
   if (!bytes_out) return fail(EPI_ERR_ARG, "epi_cx_groups_scratch_bytes: NULL argument");
   *bytes_out = 0;
-  const int64_t bytes = cxg_scratch_bytes(total_rows);
-  if (bytes < 0) return fail(EPI_ERR_ARG, "epi_cx_groups_scratch_bytes: %lld rows, the samples hold 0 to 2^32 - 1 together", (long long)total_rows);
-  *bytes_out = bytes;
+  EPI_TRY(cx_rows_arg("epi_cx_groups_scratch_bytes", total_rows, CXG_MAX_ROWS));
+  if (total_rows > 0) *bytes_out = (int64_t)CxgLayout(total_rows).used;
   return EPI_OK;
 }
 
@@ -343,17 +339,18 @@ int epi_cx_groups_dev(epi_engine *e, const int32_t *const *d_tabs, const int64_t
   if (!d_tabs || !nrows) return fail(EPI_ERR_ARG, "%s: NULL argument", who);
   if (cap < 0) return fail(EPI_ERR_ARG, "%s: negative capacity", who);
   int64_t total = 0;
+  CxTab tabs[CXG_MAX_RUN];
   for (int k = 0; k < n_a + n_b; k++) {
-    if (nrows[k] < 0 || nrows[k] >= (1LL << 32)) return fail(EPI_ERR_ARG, "%s: table %d has %lld rows", who, k, (long long)nrows[k]);
+    char table[64];
+    snprintf(table, sizeof table, "%s: table %d", who, k);
+    EPI_TRY(cx_tab_arg(table, d_tabs + 6 * k, nrows[k], CXG_MAX_ROWS, &tabs[k]));
     total += nrows[k];
-    if (nrows[k] > 0)
-      for (int i = 0; i < 6; i++) if (!d_tabs[6 * k + i]) return fail(EPI_ERR_ARG, "%s: NULL column in table %d", who, k);
   }
-  if (total >= (1LL << 32)) return fail(EPI_ERR_ARG, "%s: %lld rows in all, the samples hold fewer than 2^32 together", who, (long long)total);
+  if (total > CXG_MAX_ROWS.rows) return fail(EPI_ERR_ARG, "%s: %lld rows in all, the samples hold fewer than 2^32 together", who, (long long)total);
   if (total == 0) return EPI_OK;
   EPI_HIP(hipSetDevice(e->device));
   CxgCall c;
-  c.tabs = d_tabs; c.nrows = nrows; c.n_a = n_a; c.n_b = n_b; c.min_cov = min_coverage; c.min_a = min_samples_a; c.min_b = min_samples_b;
+  c.tabs = tabs; c.n_a = n_a; c.n_b = n_b; c.min_cov = min_coverage; c.min_a = min_samples_a; c.min_b = min_samples_b;
   c.test = test; c.icols = d_icols; c.dcols = d_dcols; c.cap = cap; c.total = total;
   return cx_groups(e, c, reinterpret_cast<hipStream_t>(stream), nsite_out, nrow_out);
 }

@@ -143,13 +143,6 @@ __global__ __launch_bounds__(PADJ_WG) void k_padj_scatter(const uint32_t *__rest
 
 // ---- host ------------------------------------------------------------------------------------------------------------------
 
-struct PadjScratch {                    // one allocation, released when the call returns; the buffers are pieces of it
-  DevBuf arena;
-  size_t used = 0;
-  size_t reserve(size_t bytes) { const size_t at = used; used += (bytes + 255) & ~(size_t)255; return at; }
-  template <class T> T *at(size_t off) const { return reinterpret_cast<T *>(arena.as<char>() + off); }
-};
-
 static int p_adjust(epi_engine *e, const double *d_p, int64_t n, int32_t method, int64_t n_tests, double *d_q, int32_t *d_order,
                     hipStream_t s, int64_t *nvalid_out) {
   const char *who = "epi_p_adjust_dev";
@@ -157,14 +150,14 @@ static int p_adjust(epi_engine *e, const double *d_p, int64_t n, int32_t method,
   const int64_t nblk_key = (n + PADJ_KEY_TILE - 1) / PADJ_KEY_TILE, nblk_row = (n + PADJ_WG - 1) / PADJ_WG;
   const int64_t nblk_scan = ((int64_t)SortPairs::table_words((size_t)n) + 4095) / 4096, nblk_dscan = (n + DSCAN_BLOCK - 1) / DSCAN_BLOCK;
   EPI_TRY(check_grid(nblk_row, PADJ_WG, "p-value adjustment kernels"));
-  PadjScratch w;
-  const size_t o_scal = w.reserve(sizeof(PadjScalars) + 8 * 256 * 4), o_sort = w.reserve(SortPairs::bytes((size_t)n));
-  const size_t o_terms = w.reserve((size_t)n * 8), o_scan = w.reserve((size_t)nblk_scan * 4), o_agg = w.reserve((size_t)nblk_dscan * 8);
-  EPI_TRY(w.arena.ensure(w.used));
-  SortPairs sort(w.at<void>(o_sort), (size_t)n);
-  double *const terms = w.at<double>(o_terms);
-  DevBuf scan_tmp = DevBuf::view(w.at<void>(o_scan), (size_t)nblk_scan * 4), agg = DevBuf::view(w.at<void>(o_agg), (size_t)nblk_dscan * 8);
-  PadjScalars *sc = w.at<PadjScalars>(o_scal);
+  ScratchArena w;                                             // every piece rounded to 256 bytes
+  const size_t o_scal = w.reserve(sizeof(PadjScalars) + 8 * 256 * 4, 256), o_sort = w.reserve(SortPairs::bytes((size_t)n), 256);
+  const size_t o_terms = w.reserve((size_t)n * 8, 256), o_scan = w.reserve((size_t)nblk_scan * 4, 256), o_agg = w.reserve((size_t)nblk_dscan * 8, 256);
+  EPI_TRY(w.alloc());
+  PadjScalars *sc; uint64_t *sort_mem; double *terms, *agg_mem; uint32_t *scan_mem;
+  EPI_TRY(w.at(o_scal, &sc)); EPI_TRY(w.at(o_sort, &sort_mem)); EPI_TRY(w.at(o_terms, &terms)); EPI_TRY(w.at(o_scan, &scan_mem)); EPI_TRY(w.at(o_agg, &agg_mem));
+  SortPairs sort(sort_mem, (size_t)n);
+  DevBuf scan_tmp = DevBuf::view(scan_mem, (size_t)nblk_scan * 4), agg = DevBuf::view(agg_mem, (size_t)nblk_dscan * 8);
   uint32_t *ghist = reinterpret_cast<uint32_t *>(sc + 1);
   EPI_HIP(hipMemsetAsync(sc, 0, sizeof(PadjScalars) + 8 * 256 * 4, s));
   prof_begin("padj_keys", s);

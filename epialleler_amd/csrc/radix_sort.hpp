@@ -1,6 +1,6 @@
 // Stable LSD radix sort of (64-bit key, 32-bit value) pairs (radix_sort.hip has the kernels), and the one workspace type its
 // callers place in their scratch: the p-value adjustment (p_adjust.hip), the FDRP report's site -> rows index (fdrp.hip), the
-// allele-specific report's events (asm_report.hip) and the group comparison's rows (cx_groups.hip).
+// allele-specific report's events (asm_report.hip), the group comparison's rows (cx_groups.hip) and cx_series.hpp's series order.
 #pragma once
 #include "common.hpp"
 

@@ -3,7 +3,7 @@
 // replaced.  The call is stateless: it reads the caller's six CX columns, writes columns of the caller, takes its scratch for
 // the length of the call and touches no batch.  All on the call's stream, every phase a launch of its own -- no kernel waits
 // on another workgroup:
-//  Order     k_sg_key (cx_series.hpp's row checks and class byte), one stable radix pass, k_sg_gather: the sites in series
+//  Order     cx_series.hpp's series_sort (the row checks and class byte, one stable radix pass), k_sg_gather: the sites in series
 //            order as one word each (clipped counts m', u' and the chain-head bit, cx_series.hpp's rule).  One read of the
 //            scalars: the input's errors end the call here.
 //  Forward   a segmented inclusive scan of max-plus matrices.  A site inside a chain is M[j][k] = T[j][k] + e(k); a chain's
@@ -32,7 +32,6 @@
 //            a whole run (a thread per run start doing so took two thirds of a decode on long runs: profiles/segment_report.txt).
 // Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): DESIGN 4.21 has the table; no kernel uses scratch memory.
 #include "cx_series.hpp"
-#include "radix_sort.hpp"
 #include "segment_math.hpp"
 
 namespace epi {
@@ -54,13 +53,6 @@ struct SgScalars {
 static_assert(sizeof(SgScalars) == 256 && offsetof(SgScalars, score) == 16, "SgScalars layout");
 
 // ---- series order ------------------------------------------------------------------------------------------------------
-
-__global__ __launch_bounds__(SG_WG) void k_sg_key(CxTab t, uint64_t *__restrict__ key, uint32_t *__restrict__ val, SgScalars *__restrict__ sc) {
-  const uint32_t i = blockIdx.x * (uint32_t)SG_WG + threadIdx.x;
-  if (i >= t.n) return;
-  key[i] = series_key(t, i, &sc->unsorted, &sc->bad);
-  val[i] = i;
-}
 
 __global__ __launch_bounds__(SG_WG) void k_sg_gather(CxTab t, const uint64_t *__restrict__ key, const uint32_t *__restrict__ ord, int32_t max_gap,
                                                      int32_t max_coverage, uint32_t *__restrict__ w, SgScalars *__restrict__ sc) {
@@ -424,42 +416,31 @@ __global__ __launch_bounds__(SG_WG) void k_sg_emit_rows(SgOut o) {
 
 // ---- host ----------------------------------------------------------------------------------------------------------------
 
-static size_t round16(size_t x) { return (x + 15) & ~(size_t)15; }      // (the site words are read 16 bytes at a time)
 static int64_t sg_blocks(int64_t n) { return (n + SG_B - 1) / SG_B; }
 
-// the call's scratch behind the sort's workspace: the site words, the f bytes, the states in series order, the workgroups'
-// aggregates, carries and maps
-struct SgLayout {
-  size_t w, fmap, sstate, blkagg, carry, blkmap, blkin, total;
+// The call's scratch, which epi_cx_segment_scratch_bytes states: the sort's workspace; the scalars (64-bit atomics); the site words
+// (read 16 bytes at a time), f bytes and states (8 at a time); the workgroups' aggregates, carries (64-bit), maps; the scan's block sums
+struct SgLayout : ScratchArena {
+  size_t sort, scal, w, fmap, sstate, blkagg, carry, blkmap, blkin, scan;
   SgLayout(int64_t n, int K) {
     const size_t nblk = (size_t)sg_blocks(n);
-    size_t at = round16(SortPairs::bytes((size_t)n));
-    w = at; at += round16((size_t)n * 4);
-    fmap = at; at += round16((size_t)n);
-    sstate = at; at += round16((size_t)n);
-    blkagg = at; at += nblk * (size_t)(8 * K * K + 8);
-    carry = at; at += nblk * (size_t)(8 * K);
-    blkmap = at; at += round16(nblk);
-    blkin = at; at += round16(nblk);
-    total = at;
+    sort = reserve(SortPairs::bytes((size_t)n), 16); scal = reserve(sizeof(SgScalars));
+    w = reserve((size_t)n * 4, 16); fmap = reserve((size_t)n, 16); sstate = reserve((size_t)n, 16);
+    blkagg = reserve(nblk * (size_t)(8 * K * K + 8)); carry = reserve(nblk * (size_t)(8 * K));
+    blkmap = reserve(nblk, 16); blkin = reserve(nblk, 16); scan = reserve(scan_tmp_bytes(n));
   }
 };
 
-static int64_t sg_scratch_bytes(int64_t n, int K) {
-  if (n == 0) return 0;
-  return (int64_t)SgLayout(n, K).total + (n + 4095) / 4096 * 4 + (int64_t)sizeof(SgScalars);
-}
-
 struct SgBufs {
-  const uint32_t *w; uint8_t *fmap, *sstate; void *blkagg, *carry; uint8_t *blkmap, *blkin; SgScalars *sc;
+  const uint32_t *w; uint8_t *fmap, *sstate; uint64_t *blkagg, *carry; uint8_t *blkmap, *blkin; SgScalars *sc;   // (blkagg, carry: FwdAgg<K>, Vec<K>)
   uint32_t n, nblk;
 };
 
 // one decode: the forward and the backward scan, three launches each
 template <int K> static void sg_decode(const SgBufs &b, const sg::Tables &t, hipStream_t s) {
   static_assert(sizeof(FwdAgg<K>) == 8 * K * K + 8 && sizeof(sg::Vec<K>) == 8 * K, "the layout's element sizes");
-  FwdAgg<K> *blkagg = static_cast<FwdAgg<K> *>(b.blkagg);
-  sg::Vec<K> *carry = static_cast<sg::Vec<K> *>(b.carry);
+  FwdAgg<K> *blkagg = reinterpret_cast<FwdAgg<K> *>(b.blkagg);
+  sg::Vec<K> *carry = reinterpret_cast<sg::Vec<K> *>(b.carry);
   prof_begin("segment_fwd_agg", s);
   hipLaunchKernelGGL(k_sg_fwd_agg<K>, dim3(b.nblk), dim3(SG_WG), 0, s, b.w, b.n, t, blkagg);
   prof_end("segment_fwd_agg", s);
@@ -490,35 +471,24 @@ struct SgCall {
   int32_t *d_state; int32_t *const *seg_i; double *const *seg_d; int64_t seg_cap;
 };
 
-static int cx_segment(epi_engine *e, const int32_t *const d_in[6], int64_t n, const SgCall &c, epi_segment_fit &fit, hipStream_t s,
-                      int64_t *nchain_out, int64_t *nsegment_out) {
+static int cx_segment(epi_engine *e, const CxTab &t, const SgCall &c, epi_segment_fit &fit, hipStream_t s, int64_t *nchain_out,
+                      int64_t *nsegment_out) {
   const char *who = "epi_cx_segment_dev";
   const int K = c.K;
-  const CxTab t = cx_tab(d_in, n);
-  const int64_t nsite_blk = (n + SG_WG - 1) / SG_WG;
+  const int64_t n = t.n, nsite_blk = (n + SG_WG - 1) / SG_WG;
   EPI_TRY(check_grid(nsite_blk, SG_WG, "segmentation kernels"));
-  const SgLayout lay(n, K);
-  DevBuf d_work, d_scal, scan_tmp;                            // (go when the call returns)
-  EPI_TRY(d_work.ensure(lay.total));
-  EPI_TRY(d_scal.ensure(sizeof(SgScalars)));
-  EPI_TRY(scan_tmp.ensure((size_t)((n + 4095) / 4096 * 4)));  // (the larger of the scans: no growth between the kernels)
-  SortPairs sort(d_work.p, (size_t)n);
-  char *base = d_work.as<char>();
-  uint32_t *w = reinterpret_cast<uint32_t *>(base + lay.w);
-  SgScalars *sc = d_scal.as<SgScalars>();
-  SgBufs b;
-  b.w = w; b.fmap = reinterpret_cast<uint8_t *>(base + lay.fmap); b.sstate = reinterpret_cast<uint8_t *>(base + lay.sstate);
-  b.blkagg = base + lay.blkagg; b.carry = base + lay.carry;
-  b.blkmap = reinterpret_cast<uint8_t *>(base + lay.blkmap); b.blkin = reinterpret_cast<uint8_t *>(base + lay.blkin);
-  b.sc = sc; b.n = (uint32_t)n; b.nblk = (uint32_t)sg_blocks(n);
+  SgLayout lay(n, K);                                         // (goes when the call returns)
+  EPI_TRY(lay.alloc());
+  uint64_t *sort_mem; uint32_t *w, *scan; SgScalars *sc; SgBufs b;
+  EPI_TRY(lay.at(lay.sort, &sort_mem)); EPI_TRY(lay.at(lay.scal, &sc)); EPI_TRY(lay.at(lay.w, &w, 16)); EPI_TRY(lay.at(lay.fmap, &b.fmap, 8));
+  EPI_TRY(lay.at(lay.sstate, &b.sstate, 8)); EPI_TRY(lay.at(lay.blkagg, &b.blkagg)); EPI_TRY(lay.at(lay.carry, &b.carry));
+  EPI_TRY(lay.at(lay.blkmap, &b.blkmap)); EPI_TRY(lay.at(lay.blkin, &b.blkin)); EPI_TRY(lay.at(lay.scan, &scan));
+  SortPairs sort(sort_mem, (size_t)n);
+  DevBuf scan_tmp = DevBuf::view(scan, scan_tmp_bytes(n));
+  b.w = w; b.sc = sc; b.n = (uint32_t)n; b.nblk = (uint32_t)sg_blocks(n);
   EPI_HIP(hipMemsetAsync(sc, 0, sizeof(SgScalars), s));
 
-  prof_begin("segment_sort", s);
-  hipLaunchKernelGGL(k_sg_key, dim3((unsigned)nsite_blk), dim3(SG_WG), 0, s, t, sort.keys_in(), sort.vals_in(), sc);
-  const int rc_sort = sort.sort(0x1u, scan_tmp, s);           // one stable pass over the class byte
-  prof_end("segment_sort", s);
-  EPI_HIP(hipGetLastError());
-  EPI_TRY(rc_sort);
+  EPI_TRY(series_sort(t, sort, &sc->unsorted, &sc->bad, scan_tmp, "segment_sort", s));
   const uint32_t *ord = sort.vals();
   prof_begin("segment_gather", s);
   hipLaunchKernelGGL(k_sg_gather, dim3((unsigned)nsite_blk), dim3(SG_WG), 0, s, t, sort.keys(), ord, c.max_gap, c.max_coverage, w, sc);
@@ -527,8 +497,7 @@ static int cx_segment(epi_engine *e, const int32_t *const d_in[6], int64_t n, co
 
   SgScalars h;                                                // the input's verdict, before any decode
   EPI_TRY(read_scalars(e, s, sc, sizeof(h), &h));
-  if (h.unsorted) return fail(EPI_ERR_ARG, series_unsorted_message(), who);
-  if (h.bad) return fail(EPI_ERR_ARG, series_bad_message(), who);
+  EPI_TRY(series_verdict(who, h.unsorted, h.bad));
   const int64_t nchain = h.nchain;
 
   int32_t words[28], next_words[28];
@@ -576,10 +545,8 @@ static int cx_segment(epi_engine *e, const int32_t *const d_in[6], int64_t n, co
   EPI_HIP(hipGetLastError());
   EPI_TRY(rc_scan);
   EPI_TRY(read_scalars(e, s, sc, sizeof(h), &h));             // the last synchronisation before anything is written
-  if ((int64_t)h.nsegment > c.seg_cap) {
-    *nsegment_out = h.nsegment;
-    return fail(EPI_ERR_ARG, "%s: %lld rows to write, room for %lld", who, (long long)h.nsegment, (long long)c.seg_cap);
-  }
+  *nsegment_out = h.nsegment;                                 // (the count needed, when the refusal below is the answer)
+  EPI_TRY(cx_rows_fit(who, "rows", h.nsegment, c.seg_cap));
   SgOut o;
   o.state = c.d_state;
   for (int i = 0; i < 7; i++) o.icol[i] = c.seg_i[i];
@@ -596,7 +563,7 @@ static int cx_segment(epi_engine *e, const int32_t *const d_in[6], int64_t n, co
   EPI_HIP(hipGetLastError());
   EPI_HIP(hipStreamSynchronize(s));                           // (the scratch goes back when this returns)
   fit.iterations = iterations; fit.converged = converged; fit.score = (int64_t)h.score;
-  *nchain_out = nchain; *nsegment_out = h.nsegment;
+  *nchain_out = nchain;
   return EPI_OK;
 }
 
@@ -615,8 +582,8 @@ int epi_cx_segment_scratch_bytes(int64_t n, int32_t nstates, int64_t *bytes_out)
   *bytes_out = 0;
   if (nstates < EPI_SEGMENT_MIN_STATES || nstates > EPI_SEGMENT_MAX_STATES)
     return fail(EPI_ERR_ARG, "%s: nstates = %d, from %d to %d", who, nstates, EPI_SEGMENT_MIN_STATES, EPI_SEGMENT_MAX_STATES);
-  if (n < 0 || n > EPI_SEGMENT_MAX_SITES) return fail(EPI_ERR_ARG, "%s: %lld rows, a call takes 0 to 2^26", who, (long long)n);
-  *bytes_out = sg_scratch_bytes(n, nstates);
+  EPI_TRY(cx_rows_arg(who, n, {EPI_SEGMENT_MAX_SITES, "2^26"}));
+  if (n > 0) *bytes_out = (int64_t)SgLayout(n, nstates).used;
   return EPI_OK;
 }
 
@@ -631,22 +598,20 @@ int epi_cx_segment_dev(epi_engine *e, const int32_t *const d_in[6], int64_t n, i
   if (max_coverage < 1 || max_coverage > EPI_SEGMENT_MAX_COVERAGE)
     return fail(EPI_ERR_ARG, "%s: max_coverage = %d, from 1 to %d", who, max_coverage, EPI_SEGMENT_MAX_COVERAGE);
   if (max_iter < 1) return fail(EPI_ERR_ARG, "%s: max_iter = %d, at least 1", who, max_iter);
-  if (n < 0 || seg_cap < 0) return fail(EPI_ERR_ARG, "%s: negative row count or capacity", who);
-  if (n > EPI_SEGMENT_MAX_SITES) return fail(EPI_ERR_ARG, "%s: %lld rows, a call takes at most 2^26", who, (long long)n);
+  CxTab t;
+  EPI_TRY(cx_tab_arg(who, d_in, n, {EPI_SEGMENT_MAX_SITES, "2^26"}, &t, seg_cap));
   if (!e) return fail(EPI_ERR_ARG, "%s: NULL argument", who);
   epi_segment_fit fit = {};
   fit.nstates = nstates;
   for (int k = 0; k < nstates; k++) { fit.p[k] = p[k]; fit.init[k] = init[k]; }
   for (int x = 0; x < nstates * nstates; x++) fit.trans[x] = trans[x];
   if (n == 0) { *fit_out = fit; *nchain_out = 0; *nsegment_out = 0; return EPI_OK; }
-  if (!d_in || !d_state || !d_seg_i || !d_seg_d) return fail(EPI_ERR_ARG, "%s: NULL argument", who);
-  for (int i = 0; i < 6; i++) if (!d_in[i]) return fail(EPI_ERR_ARG, "%s: NULL column", who);
-  for (int i = 0; i < 7; i++) if (!d_seg_i[i]) return fail(EPI_ERR_ARG, "%s: NULL column", who);
-  for (int i = 0; i < 3; i++) if (!d_seg_d[i]) return fail(EPI_ERR_ARG, "%s: NULL column", who);
+  if (!d_state) return fail(EPI_ERR_ARG, "%s: NULL argument", who);
+  EPI_TRY(cx_cols_arg(who, d_seg_i, 7, d_seg_d, 3));
   EPI_HIP(hipSetDevice(e->device));
   SgCall c = {nstates, max_gap, max_coverage, max_iter, d_state, d_seg_i, d_seg_d, seg_cap};
   int64_t nchain = 0;
-  EPI_TRY(cx_segment(e, d_in, n, c, fit, reinterpret_cast<hipStream_t>(stream), &nchain, nsegment_out));
+  EPI_TRY(cx_segment(e, t, c, fit, reinterpret_cast<hipStream_t>(stream), &nchain, nsegment_out));
   *fit_out = fit; *nchain_out = nchain;
   return EPI_OK;
 }

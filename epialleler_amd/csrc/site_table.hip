@@ -1,5 +1,6 @@
 // The per-strand site table's construction and the host steps every report over it shares (description: site_table.hpp).
 #include "site_table.hpp"
+#include "cx_table.hpp"
 
 namespace epi {
 
@@ -54,8 +55,7 @@ int site_fetch_begin(const char *who, epi_batch *b, ReportKind kind, const char 
   if (b->last_kind != kind || (blocks && !b->sites.link.blocks)) return fail(EPI_ERR_STATE, "%s: no finished %s on this batch", who, what);
   const int64_t n = blocks ? b->sites.link.nblock : b->last_nrow;
   if (n == 0) return EPI_OK;
-  for (int i = 0; i < ni; i++) if (!icols[i]) return fail(EPI_ERR_ARG, "%s: NULL column", who);
-  for (int i = 0; i < nd; i++) if (!dcols[i]) return fail(EPI_ERR_ARG, "%s: NULL column", who);
+  EPI_TRY(cx_cols_arg(who, icols, ni, dcols, nd));
   EPI_HIP(hipSetDevice(b->eng->device));
   *s = pick_stream(b, stream);
   *nrow = n;

@@ -12,8 +12,8 @@
 //           its successor, which was above (rname, q, '-') and hence at (rname, q', .) with q' > q or on a later rname; if
 //           the successor moves or is a pair's '+' row it ends at q' - 1 >= q > q - 1 or stays.
 //  Smooth   (the series order and its cuts: cx_series.hpp, shared with segment.hip)
-//           k_sm_key checks the rows and writes (class byte, row) pairs; one stable radix pass (radix_sort.hip) brings the
-//           rows into series order: the rows of one (strand, context) together, (rname, pos) ascending within.  k_sm_flag
+//           series_sort: k_series_key checks the rows and writes (class byte, row) pairs; one stable radix pass (radix_sort.hip) brings
+//           the rows into series order: the rows of one (strand, context) together, (rname, pos) ascending within.  k_sm_flag
 //           gathers pos, meth and coverage into series order and flags the first site of every cluster; the scan over the
 //           flags numbers the clusters, k_sm_cstart lists their first sites.  k_smooth_bounds: a thread per site finds D
 //           (binary search over the k-wide runs that contain the site), H and the window [jlo, jhi) (two binary searches).
@@ -26,7 +26,6 @@
 //           global memory otherwise (a thread whose window is not inside the staged range reads global memory too: no
 //           index depends on the monotonicity).  The same values reach the same operations either way.
 #include "cx_series.hpp"
-#include "radix_sort.hpp"
 #include "smooth_math.hpp"
 
 namespace epi {
@@ -97,20 +96,18 @@ __global__ __launch_bounds__(SM_WG) void k_mg_emit(CxTab t, const uint32_t *__re
 
 struct MgCounts { int64_t *nrow, *nmerged, *nmoved, *nkept; };
 
-static int cx_merge(epi_engine *e, const int32_t *const d_in[6], int64_t n, int32_t *const d_out[6], int64_t cap, hipStream_t s, MgCounts c) {
+static int cx_merge(epi_engine *e, const CxTab &t, int32_t *const d_out[6], int64_t cap, hipStream_t s, MgCounts c) {
   const char *who = "epi_cx_merge_strands_dev";
-  const CxTab t = cx_tab(d_in, n);
-  const int64_t nblk = (n + SM_WG - 1) / SM_WG;
+  const int64_t n = t.n, nblk = (n + SM_WG - 1) / SM_WG;
   EPI_TRY(check_grid(nblk, SM_WG, "strand merging kernels"));
-  DevBuf d_flag, d_scal, scan_tmp;                            // (go when the call returns)
-  EPI_TRY(d_flag.ensure((size_t)n * 8));
-  EPI_TRY(d_scal.ensure(64));
-  uint32_t *keep = d_flag.as<uint32_t>(), *off = keep + n;
-  MgScalars *sc = d_scal.as<MgScalars>();
+  CxKeepScratch w;                                            // keep flags and their scan
+  EPI_TRY(w.take(n, 2));
+  MgScalars *sc = reinterpret_cast<MgScalars *>(w.scal);
+  uint32_t *keep = w.flag, *off = keep + n;
   EPI_HIP(hipMemsetAsync(sc, 0, 64, s));
   prof_begin("cxmerge_flag", s);
   hipLaunchKernelGGL(k_mg_flag, dim3((unsigned)nblk), dim3(SM_WG), 0, s, t, keep, sc);
-  const int rc_scan = scan_exclusive_u32(keep, off, n, &sc->nrow, scan_tmp, s);
+  const int rc_scan = scan_exclusive_u32(keep, off, n, &sc->nrow, w.scan_tmp, s);
   prof_end("cxmerge_flag", s);
   EPI_HIP(hipGetLastError());
   EPI_TRY(rc_scan);
@@ -120,9 +117,9 @@ static int cx_merge(epi_engine *e, const int32_t *const d_in[6], int64_t n, int3
   if (h.bad) return fail(EPI_ERR_ARG, "%s: a row has a strand other than 1 and 2 or a negative count", who);
   if (h.overflow) return fail(EPI_ERR_ARG, "%s: the summed meth or unmeth of a CpG exceeds 2^31 - 1, which an int32 column cannot hold", who);
   *c.nrow = h.nrow; *c.nmerged = h.nmerged; *c.nmoved = h.nmoved; *c.nkept = h.nkept;
-  if ((int64_t)h.nrow > cap) return fail(EPI_ERR_ARG, "%s: %lld rows to write, room for %lld", who, (long long)h.nrow, (long long)cap);
+  EPI_TRY(cx_rows_fit(who, "rows", h.nrow, cap));
+  EPI_TRY(cx_cols_arg(who, d_out, 6, nullptr, 0));
   MgOut o;
-  for (int i = 0; i < 6; i++) if (!d_out || !d_out[i]) return fail(EPI_ERR_ARG, "%s: NULL column", who);
   o.rname = d_out[0]; o.strand = d_out[1]; o.pos = d_out[2]; o.context = d_out[3]; o.meth = d_out[4]; o.unmeth = d_out[5];
   o.nrow = h.nrow;
   prof_begin("cxmerge_emit", s);
@@ -137,13 +134,6 @@ static int cx_merge(epi_engine *e, const int32_t *const d_in[6], int64_t n, int3
 
 struct SmScalars { uint32_t unsorted, bad, ncluster, max_window, unused[12]; };
 static_assert(sizeof(SmScalars) == 64, "SmScalars layout");
-
-__global__ __launch_bounds__(SM_WG) void k_sm_key(CxTab t, uint64_t *__restrict__ key, uint32_t *__restrict__ val, SmScalars *__restrict__ sc) {
-  const uint32_t i = blockIdx.x * (uint32_t)SM_WG + threadIdx.x;
-  if (i >= t.n) return;
-  key[i] = series_key(t, i, &sc->unsorted, &sc->bad);
-  val[i] = i;
-}
 
 struct SmSeries {                      // the table in series order
   int32_t *pos, *meth;
@@ -262,43 +252,34 @@ __global__ __launch_bounds__(SM_TILE) void k_smooth_fit(CxTab t, const uint32_t 
 
 // ---- host --------------------------------------------------------------------------------------------------------------
 
-// the call's scratch for n rows: the sort's workspace; pos, meth, coverage in series order, H, jlo, jhi and the cluster
-// starts (7 n + 1 words, rounded to 8 bytes); the scan's block sums; the scalars
-static size_t sm_words(int64_t n) { return ((size_t)n * 7 + 2) & ~(size_t)1; }
-static int64_t sm_scratch_bytes(int64_t n) {
-  if (n < 0 || n >= (1LL << 31)) return -1;
-  if (n == 0) return 0;
-  return (int64_t)SortPairs::bytes((size_t)n) + (int64_t)sm_words(n) * 4 + (n + 4095) / 4096 * 4 + 64;
-}
+// The call's scratch, which epi_cx_smooth_scratch_bytes states: the sort's workspace; pos, meth, coverage in series order, H, jlo, jhi
+// and the cluster starts (7 n + 1 words, rounded to 8 bytes); the scalars; the scan's block sums (the sort's table has fewer)
+struct SmLayout : ScratchArena {
+  size_t sort, words, scal, scan;
+  explicit SmLayout(int64_t n) {
+    sort = reserve(SortPairs::bytes((size_t)n)); words = reserve(((size_t)n * 7 + 1) * 4, 8); scal = reserve(64); scan = reserve(scan_tmp_bytes(n));
+  }
+};
 
 struct SmCall { int32_t bandwidth, min_sites, max_gap, degree; int32_t *const *icols; double *const *dcols; };
 
-static int cx_smooth(epi_engine *e, const int32_t *const d_in[6], int64_t n, const SmCall &c, hipStream_t s, int64_t *ncluster_out,
-                     int64_t *max_window_out) {
+static int cx_smooth(epi_engine *e, const CxTab &t, const SmCall &c, hipStream_t s, int64_t *ncluster_out, int64_t *max_window_out) {
   const char *who = "epi_cx_smooth_dev";
-  const CxTab t = cx_tab(d_in, n);
-  const int64_t nblk = (n + SM_WG - 1) / SM_WG;
+  const int64_t n = t.n, nblk = (n + SM_WG - 1) / SM_WG;
   EPI_TRY(check_grid(nblk, SM_WG, "smoothing kernels"));
-  DevBuf d_work, d_scal, scan_tmp;                            // (go when the call returns)
-  EPI_TRY(d_work.ensure(SortPairs::bytes((size_t)n) + sm_words(n) * 4));
-  EPI_TRY(d_scal.ensure(64));
-  EPI_TRY(scan_tmp.ensure((size_t)((n + 4095) / 4096 * 4)));  // (the larger of the scans: no growth between the kernels)
-  SortPairs sort(d_work.p, (size_t)n);
-  int32_t *words = reinterpret_cast<int32_t *>(d_work.as<char>() + SortPairs::bytes((size_t)n));
+  SmLayout lay(n);                                            // (goes when the call returns)
+  EPI_TRY(lay.alloc());
+  uint64_t *sort_mem; int32_t *words; SmScalars *sc; uint32_t *scan;
+  EPI_TRY(lay.at(lay.sort, &sort_mem)); EPI_TRY(lay.at(lay.words, &words)); EPI_TRY(lay.at(lay.scal, &sc)); EPI_TRY(lay.at(lay.scan, &scan));
+  SortPairs sort(sort_mem, (size_t)n);
+  DevBuf scan_tmp = DevBuf::view(scan, scan_tmp_bytes(n));
   SmSeries ser;
   ser.pos = words; ser.meth = words + n; ser.cov = reinterpret_cast<uint32_t *>(words + 2 * n); ser.n = (uint32_t)n;
   SmWin w;
   w.H = words + 3 * n; w.jlo = reinterpret_cast<uint32_t *>(words + 4 * n); w.jhi = reinterpret_cast<uint32_t *>(words + 5 * n);
   uint32_t *cstart = reinterpret_cast<uint32_t *>(words + 6 * n);          // n + 1 entries
-  SmScalars *sc = d_scal.as<SmScalars>();
   EPI_HIP(hipMemsetAsync(sc, 0, 64, s));
-
-  prof_begin("smooth_sort", s);
-  hipLaunchKernelGGL(k_sm_key, dim3((unsigned)nblk), dim3(SM_WG), 0, s, t, sort.keys_in(), sort.vals_in(), sc);
-  const int rc_sort = sort.sort(0x1u, scan_tmp, s);           // one stable pass over the class byte
-  prof_end("smooth_sort", s);
-  EPI_HIP(hipGetLastError());
-  EPI_TRY(rc_sort);
+  EPI_TRY(series_sort(t, sort, &sc->unsorted, &sc->bad, scan_tmp, "smooth_sort", s));
 
   const uint32_t *ord = sort.vals();
   uint32_t *flag = sort.spare<uint32_t>(), *off = flag + n;
@@ -313,8 +294,7 @@ static int cx_smooth(epi_engine *e, const int32_t *const d_in[6], int64_t n, con
 
   SmScalars h;                                                // the one synchronisation before anything is written
   EPI_TRY(read_scalars(e, s, sc, sizeof(h), &h));
-  if (h.unsorted) return fail(EPI_ERR_ARG, series_unsorted_message(), who);
-  if (h.bad) return fail(EPI_ERR_ARG, series_bad_message(), who);
+  EPI_TRY(series_verdict(who, h.unsorted, h.bad));
   *ncluster_out = h.ncluster;
   *max_window_out = h.max_window;
   if (h.max_window > (uint32_t)EPI_SMOOTH_MAX_WINDOW)
@@ -347,14 +327,13 @@ int epi_cx_merge_strands_dev(epi_engine *e, const int32_t *const d_in[6], int64_
   const char *who = "epi_cx_merge_strands_dev";
   if (!e || !nrow_out || !nmerged_out || !nmoved_out || !nkept_out) return fail(EPI_ERR_ARG, "%s: NULL argument", who);
   *nrow_out = 0; *nmerged_out = 0; *nmoved_out = 0; *nkept_out = 0;
-  if (n < 0 || cap < 0) return fail(EPI_ERR_ARG, "%s: negative row count or capacity", who);
-  if (n >= (1LL << 31)) return fail(EPI_ERR_ARG, "%s: %lld rows", who, (long long)n);
-  if ((n > 0 && !d_in) || (cap > 0 && !d_out)) return fail(EPI_ERR_ARG, "%s: NULL argument", who);
-  for (int i = 0; i < 6; i++) if (n > 0 && !d_in[i]) return fail(EPI_ERR_ARG, "%s: NULL column", who);
+  CxTab t;
+  EPI_TRY(cx_tab_arg(who, d_in, n, kCxMaxRows, &t, cap));
+  if (cap > 0 && !d_out) return fail(EPI_ERR_ARG, "%s: NULL argument", who);
   if (n == 0) return EPI_OK;
   EPI_HIP(hipSetDevice(e->device));
   MgCounts c = {nrow_out, nmerged_out, nmoved_out, nkept_out};
-  return cx_merge(e, d_in, n, d_out, cap, reinterpret_cast<hipStream_t>(stream), c);
+  return cx_merge(e, t, d_out, cap, reinterpret_cast<hipStream_t>(stream), c);
 }
 
 int epi_smooth_tile_sites(void) { return SM_TILE; }
@@ -363,9 +342,8 @@ int epi_smooth_stage_sites(void) { return SM_STAGE; }
 int epi_cx_smooth_scratch_bytes(int64_t n, int64_t *bytes_out) {
   if (!bytes_out) return fail(EPI_ERR_ARG, "epi_cx_smooth_scratch_bytes: NULL argument");
   *bytes_out = 0;
-  const int64_t bytes = sm_scratch_bytes(n);
-  if (bytes < 0) return fail(EPI_ERR_ARG, "epi_cx_smooth_scratch_bytes: %lld rows, a table holds 0 to 2^31 - 1", (long long)n);
-  *bytes_out = bytes;
+  EPI_TRY(cx_rows_arg("epi_cx_smooth_scratch_bytes", n, kCxMaxRows));
+  if (n > 0) *bytes_out = (int64_t)SmLayout(n).used;
   return EPI_OK;
 }
 
@@ -381,17 +359,14 @@ int epi_cx_smooth_dev(epi_engine *e, const int32_t *const d_in[6], int64_t n, in
   if (max_gap < 0) return fail(EPI_ERR_ARG, "%s: negative max_gap", who);
   if (min_sites < 1 || min_sites > EPI_SMOOTH_MAX_WINDOW)
     return fail(EPI_ERR_ARG, "%s: min_sites = %d, from 1 to %d", who, min_sites, EPI_SMOOTH_MAX_WINDOW);
-  if (n < 0) return fail(EPI_ERR_ARG, "%s: negative row count", who);
-  if (n >= (1LL << 31)) return fail(EPI_ERR_ARG, "%s: %lld rows", who, (long long)n);
+  CxTab t;
+  EPI_TRY(cx_tab_arg(who, d_in, n, kCxMaxRows, &t));
   if (!e) return fail(EPI_ERR_ARG, "%s: NULL argument", who);
   if (n == 0) return EPI_OK;
-  if (!d_in || !d_icols || !d_dcols) return fail(EPI_ERR_ARG, "%s: NULL argument", who);
-  for (int i = 0; i < 6; i++) if (!d_in[i]) return fail(EPI_ERR_ARG, "%s: NULL column", who);
-  for (int i = 0; i < 9; i++) if (!d_icols[i]) return fail(EPI_ERR_ARG, "%s: NULL column", who);
-  for (int i = 0; i < 3; i++) if (!d_dcols[i]) return fail(EPI_ERR_ARG, "%s: NULL column", who);
+  EPI_TRY(cx_cols_arg(who, d_icols, 9, d_dcols, 3));
   EPI_HIP(hipSetDevice(e->device));
   SmCall c = {bandwidth, min_sites, max_gap, degree, d_icols, d_dcols};
-  return cx_smooth(e, d_in, n, c, reinterpret_cast<hipStream_t>(stream), ncluster_out, max_window_out);
+  return cx_smooth(e, t, c, reinterpret_cast<hipStream_t>(stream), ncluster_out, max_window_out);
 }
 
 }  // extern "C"

@@ -59,13 +59,18 @@ def test_symbols_declared_exported_and_listed():
     lib = _lib.load()
     block, thread = lib.epi_segment_block_sites(), lib.epi_segment_thread_sites()
     assert 1 <= thread <= 64 and block % thread == 0 and 64 <= block // thread <= 1024 and (block // thread) % 64 == 0
-    # the series rules have one wording, which the smoother and the segmentation both include
+    # the series rules have one wording, which the smoother and the segmentation both include: the step into series order whole
+    # (the key rule is called by cx_series.hpp's own kernel alone), the head rule from a kernel of their own
     with open(os.path.join(_lib.CSRC, "smooth.hip")) as f:
         smooth = f.read()
     with open(os.path.join(_lib.CSRC, "segment.hip")) as f:
         segment = f.read()
+    with open(os.path.join(_lib.CSRC, "cx_series.hpp")) as f:
+        series = f.read()
+    assert len(re.findall(r"\bseries_key\(", series)) == 2 and series.count("__global__") == 1
     for text in (smooth, segment):
-        assert '#include "cx_series.hpp"' in text and "series_key(" in text and "series_head(" in text and "max_gap ?" not in text
+        assert '#include "cx_series.hpp"' in text and "series_sort(" in text and "series_key(" not in text and "series_head(" in text
+        assert "max_gap ?" not in text
 
 
 def test_signatures_and_defaults():
